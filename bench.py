@@ -9,6 +9,10 @@ Search call over a batch of `--nq` synthetic queries already resident in HBM.
   python bench.py --gpus N --steps K --warmup W          (N=1 default)
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
+A plain run sets up the index, warms up, times the K steps and prints the line.  --full adds every other leg:
+recall@10 against flat search, the CPU baseline, the plugin leg, the other operating points and shapes.
+--dump-outputs DIR writes the last timed step's results (distances.npy float32, labels.npy float64) to DIR.
+
 N>1: the index is sharded by IVF list across the ranks (gamma_amd/dist.py): every rank scans the
 lists it owns for the whole batch, an RCCL all-to-all hands each rank the candidates of its query
 slice, merge + re-rank there.  A step then holds N x nq queries (per-GPU scan work constant:
@@ -46,8 +50,13 @@ def main():
     ap.add_argument("--k", type=int, default=10)
     ap.add_argument("--no-rank", action="store_true")
     ap.add_argument("--coarse-mode", type=int, default=-1)
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline budget (0 = skip)")
-    ap.add_argument("--recall-queries", type=int, default=1000)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, run every other leg too: recall@10, the step-0 checks of the multi-GPU "
+                         "placements, the host-buffer figure, the plugin leg, the extra legs, the shape legs, the CPU baseline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's results to DIR: distances.npy (float32) and labels.npy (float64)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: CPU baseline budget (0 = skip)")
+    ap.add_argument("--recall-queries", type=int, default=1000, help="--full: queries of the recall@10 check (0 = skip)")
     ap.add_argument("--force-dist", action="store_true",
                     help="run the sharded orchestration (gamma_amd.dist) even on one GPU")
     ap.add_argument("--backend", default="nccl",
@@ -77,11 +86,11 @@ def main():
     ap.add_argument("--dup-queries", type=int, default=0,
                     help="experiment: every batch repeats its first N queries (the lists they probe stay cache "
                          "resident: what the scan costs without its table traffic)")
-    ap.add_argument("--batches", default="1,32,1024", help="batch sizes of the qps_by_batch leg (BASELINE.md protocol)")
-    ap.add_argument("--no-plugin", action="store_true", help="skip the leg that drives the HIPIVFPQ plugin (Indexing, Add, Search with host buffers)")
-    ap.add_argument("--no-shapes", action="store_true", help="skip the reduced C4 / C5 shape legs (child processes, ~1 min)")
+    ap.add_argument("--batches", default="1,32,1024", help="--full: batch sizes of the qps_by_batch leg (BASELINE.md protocol)")
+    ap.add_argument("--no-plugin", action="store_true", help="--full: skip the leg that drives the HIPIVFPQ plugin (Indexing, Add, Search with host buffers)")
+    ap.add_argument("--no-shapes", action="store_true", help="--full: skip the reduced C4 / C5 shape legs (child processes, ~1 min)")
     ap.add_argument("--no-extra", action="store_true",
-                    help="skip the extra legs (exact ties, batch sizes 1/32/1024, coarse_mode 0, C2 flat)")
+                    help="--full: skip the extra legs (exact ties, batch sizes 1/32/1024, coarse_mode 0, C2 flat)")
     ap.add_argument("--pmc-traffic", type=float, default=None,
                     help="HBM bytes per scan launch from a separate rocprofv3 --pmc pass")
     ap.add_argument("--workload", default="c3", choices=["c3", "c4", "c5"],
@@ -100,6 +109,8 @@ def main():
     ap.add_argument("--insert-rate", type=float, default=10000.0, help="--workload c5: vectors per second of the realtime insert leg")
     ap.add_argument("--insert-seconds", type=float, default=12.0, help="--workload c5: length of the insert leg")
     a = ap.parse_args()
+    if a.dump_outputs and (a.in_process or a.workload != "c3"):
+        ap.error("--dump-outputs: the C3 workload through this process only (--workload c4 / c5: --scale-dump)")
 
     # `python bench.py --gpus N` without a launcher: this process only starts the N ranks (one fresh process per
     # GPU, RCCL rendezvous on 127.0.0.1) -- BEFORE anything here touches the GPU -- and waits for them; rank 0
@@ -260,9 +271,9 @@ def main():
             return out
         return gdist.sharded_search(backend, xb, k, args)
 
-    # ---- recall@10 against exact flat search on the GPU (rank 0 data is complete: raw replicated)
+    # ---- recall@10 against exact flat search on the GPU (rank 0 data is complete: raw replicated; --full)
     recall = None
-    nrq = min(a.recall_queries, gnq)
+    nrq = min(a.recall_queries, gnq) if a.full else 0
     if nrq > 0:
         Dg, Ig = step(0, stream=False)
         torch.cuda.synchronize()
@@ -274,10 +285,10 @@ def main():
         log("[rank %d] recall@%d = %.4f over %d queries" % (rank, k, recall, nrq))
 
     # both placements answer step 0: the list-sharded result table (two-phase scan, packed exchange, merge at the owners)
-    # must be the replicated one -- labels and distance bits -- so that a scaling run carries its own correctness bit
+    # must be the replicated one -- labels and distance bits -- so that a scaling run carries its own correctness bit (--full)
     sharded_equals_replicated = None
     exchange_per_step = None
-    if both:
+    if both and a.full:
         set_placement(False)
         backend.exchange_stats = {}
         Ds0, Is0 = step(0, stream=False)
@@ -295,7 +306,7 @@ def main():
                              "candidates_sent_by_rank_0_entries_per_query": None if not es.get("queries") else round(es["exchange_entries"] / es["queries"], 1),
                              "whole_tables_would_be_bytes": (gnq // world) * R * 12 * (world - 1)}
         log("[rank %d] sharded == replicated on step 0: %s" % (rank, sharded_equals_replicated))
-    elif use_dist and not replicate:
+    elif use_dist and not replicate and a.full:
         backend.exchange_stats = {}
         step(0, stream=False)
         es = backend.exchange_stats
@@ -336,15 +347,18 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
+        last = None
         for i in range(a.steps):
-            step(a.warmup + i)
+            last = step(a.warmup + i)
         if rstream is not None and mode["replicate"]:
-            rstream.flush()                  # the last step's results: gathered inside the timed region
+            last = rstream.flush()           # the last step's results: gathered inside the timed region
         t_enq = time.perf_counter() - t0     # host time to enqueue the steps (log only)
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
         dt_ = time.perf_counter() - t0
+        # (the buffers the steps return are reused by later calls: --dump-outputs keeps a copy of the last step's)
+        last = tuple(t.clone() for t in last) if (a.dump_outputs and last is not None) else None
         log("[rank %d] %s: host enqueue %.3f ms/step of %.3f ms/step" % (
             rank, "single GPU" if not use_dist else ("replicate" if mode["replicate"] else "shard"), t_enq / a.steps * 1e3,
             dt_ / a.steps * 1e3))
@@ -352,27 +366,27 @@ def main():
             tt = torch.tensor([dt_], dtype=torch.float64, device=dev)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             dt_ = float(tt.item())
-        return dt_, g.profile()
+        return dt_, g.profile(), last
 
     placement_qps = {}
     if both:
         set_placement(False)
-        dt_s, prof_s = timed_region()
+        dt_s, prof_s, last_s = timed_region()
         set_placement(True)
-        dt_r, prof_r = timed_region()
+        dt_r, prof_r, last_r = timed_region()
         placement_qps = {"shard": gnq * a.steps / dt_s, "replicate": gnq * a.steps / dt_r}
         if dt_s <= dt_r:          # `value` = the faster placement, named in config.placement
             set_placement(False)
-            dt, prof_first = dt_s, prof_s
+            dt, prof_first, last_out = dt_s, prof_s, last_s
         else:
-            dt, prof_first = dt_r, prof_r
+            dt, prof_first, last_out = dt_r, prof_r, last_r
         replicate = mode["replicate"]
     else:
-        dt, prof_first = timed_region()
+        dt, prof_first, last_out = timed_region()
         if use_dist:
             placement_qps = {("replicate" if replicate else "shard"): gnq * a.steps / dt}
     prof = prof_timed = prof_first
-    if a.timed_events != "all":
+    if a.timed_events != "all" and a.full:
         # every stage + the algorithmic bytes of the same launches: the same steps again, untimed
         g.profile_enable(True)
         g.profile_reset()
@@ -391,6 +405,8 @@ def main():
             dist.destroy_process_group()
         _flush_c_stdio()      # (this rank's RCCL banner: out now, long before rank 0 prints the line)
         return
+    if last_out is not None:
+        dump_outputs(a.dump_outputs, *last_out)
 
     qps = gnq * a.steps / dt
     scan_ms, scan_n = prof["scan"]
@@ -403,9 +419,9 @@ def main():
     log("stage avg us per launch:", stages, "scan bytes/launch %.0f" % bytes_per_launch)
 
     # host-buffer entry point (what the RetrievalModel boundary hands over): H2D queries + D2H
-    # results included.  Reported for DESIGN.md; never `value`.
+    # results included.  Reported for DESIGN.md; never `value`.  Everything from here on: --full
     host_qps = None
-    if world == 1:
+    if world == 1 and a.full:
         qh = queries[:a.nq]
         g.ivfpq_search(qh, k, args)
         t1 = time.perf_counter()
@@ -417,7 +433,7 @@ def main():
     # baseline (the compiled library at its default BLAS threshold) -- and the plugin leg: both BEFORE the legs below
     # insert into and delete from the index
     gpu_res = None
-    if world == 1:
+    if world == 1 and a.full:
         g.set_exact_ties(True)
         g.set_deferred_replay(False)
         g.ivfpq_search_device(d_q.data_ptr(), a.nq, k, args, d_D.data_ptr(), d_I.data_ptr())
@@ -429,7 +445,7 @@ def main():
     #      (gamma_amd/host/harness_c_api.cc): vectors stored, Indexing(), Add() in the engine's batches of 10 000, then
     #      Search() with HOST buffers in and out -- 16384-query and 1024-query calls.  Never `value` (PCIe inclusive).
     plugin_leg = None
-    if world == 1 and not a.no_extra and not a.no_plugin:
+    if world == 1 and a.full and not a.no_extra and not a.no_plugin:
         try:
             plugin_leg = plugin_bench(a, base, queries, cc, pq, g, d_q, d_D, d_I, k, args)
         except Exception as e:      # noqa: BLE001 -- a leg never fails the bench
@@ -439,7 +455,7 @@ def main():
     # ---- the other operating points BASELINE.md / SURVEY 8d name, each a short bounded leg on the same index
     #      (single GPU only; none of them is `value`) ----
     extra = {}
-    if world == 1 and not a.no_extra:
+    if world == 1 and a.full and not a.no_extra:
         def timed(fn, n, warm=3):
             for _ in range(warm):
                 fn()
@@ -665,7 +681,7 @@ def main():
     # (g) the other BASELINE shapes at a size that builds in seconds, so that the driver's line carries a timing of
     #     them too (full size -- 100 M x 128 and 10 M x 768 -- takes minutes to generate: tools/c4_scale.py 1e8,
     #     tools/c5_scale.py 1e7 16384).  Child processes: each tool builds its own index.
-    if world == 1 and not a.no_extra and not a.no_shapes:
+    if world == 1 and a.full and not a.no_extra and not a.no_shapes:
         import re
         import subprocess
         here = os.path.dirname(os.path.abspath(__file__))
@@ -709,7 +725,7 @@ def main():
 
     cpu = None
     labels_vs_cpu = None
-    if world == 1 and a.cpu_seconds > 0:
+    if world == 1 and a.full and a.cpu_seconds > 0:
         # (gpu_res: batch 0 through the device's default path, taken before the legs that change the index)
         cpu = cpu_baseline(a, base, queries, cc, pq, g, lno, codes, list_sizes, gpu_res)
         labels_vs_cpu = cpu.pop("labels_equal_to_cpu_baseline", None) if cpu else None
@@ -717,7 +733,7 @@ def main():
     # (f') the same index with 5 % of its documents deleted (the LAST leg: it changes the index): large batches run over lists
     #      cut down to the live entries once per call (csrc/kernels.hip k_compact_lists) instead of testing the delete
     #      bitmap for every scored code
-    if world == 1 and not a.no_extra:
+    if world == 1 and a.full and not a.no_extra:
         rng_d = np.random.default_rng(5)
         dead = rng_d.choice(N, N // 20, replace=False)
         bmd = np.zeros((N >> 3) + 1, dtype=np.uint8)
@@ -779,6 +795,7 @@ def main():
                  "top-k" % (world, world))),
             "stage_us": stages,
             "stage_timing": "HIP events in the timed region: " + a.timed_events,
+            "full": a.full,
             "value_is": "device-pointer Search calls, each COMPLETE when it returns (exact ties on, replay inside the call)" if not deferred else
                         "a STREAM of device-pointer calls with the deferred tie replay (--deferred-replay): flagged rows complete one call later",
             "indexing_seconds": None if train_s is None else round(train_s, 2),
@@ -818,6 +835,21 @@ def main():
         dist.destroy_process_group()
     _flush_c_stdio()
     print(json.dumps(out), flush=True)
+
+
+def dump_outputs(path, D, I, limit=64000000):
+    """The (D, I) a caller of the timed path receives, as DIR/distances.npy (float32) and DIR/labels.npy (float64: every id
+    is exact).  Beyond `limit` bytes in all, a fixed seeded sample of the query rows (sorted) is written instead."""
+    os.makedirs(path, exist_ok=True)
+    D = D.cpu().numpy().astype(np.float32)
+    I = I.cpu().numpy().astype(np.float64)
+    cap = (limit - 4096) // (D.shape[1] * 4 + I.shape[1] * 8)
+    if D.shape[0] > cap:
+        rows = np.sort(np.random.default_rng(0).choice(D.shape[0], cap, replace=False))
+        D, I = D[rows], I[rows]
+    np.save(os.path.join(path, "distances.npy"), D)
+    np.save(os.path.join(path, "labels.npy"), I)
+    log("outputs of the last timed step: %s (%d x %d)" % (path, D.shape[0], D.shape[1]))
 
 
 def _flush_c_stdio():

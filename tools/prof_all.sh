@@ -50,7 +50,7 @@ except Exception:
   rm -rf $out/raw_$name
 }
 want c3 && stats c3_bench $root/bench.py --steps 20 --warmup 5 --cpu-seconds 0 --recall-queries 0 --no-extra --no-shapes
-want c3default && stats c3_bench_default_command $root/bench.py   # the driver's exact command (every leg of the default run)
+want c3default && stats c3_bench_default_command $root/bench.py --full   # every leg of the full run
 want c3nocf && stats c3_bench_no_filter_pass $root/tools/run_env.py GAMMA_HIP_NO_SCAN_CF=1 $root/bench.py --steps 20 --warmup 5 --cpu-seconds 0 --recall-queries 0 --no-extra --no-shapes
 want c2 && stats c2_flat $root/tools/flat_bench.py
 want c4 && stats c4_shape_8m $root/tools/c4_scale.py 8e6

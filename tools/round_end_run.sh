@@ -24,7 +24,7 @@ for mode in q8 noq8; do
 done
 unset GAMMA_HIP_NO_Q8
 } > gpurun_out/r05_scale_runs.txt 2>&1
-python bench.py > gpurun_out/r05_bench.json 2> gpurun_out/r05_bench.err
-tail -c 600 gpurun_out/r05_bench.json
+python bench.py --full > "${OUT_DIR:-${TMPDIR:-/tmp}}/r05_bench.json" 2> "${OUT_DIR:-${TMPDIR:-/tmp}}/r05_bench.err"
+tail -c 600 "${OUT_DIR:-${TMPDIR:-/tmp}}/r05_bench.json"
 timeout 2400 python -m pytest tests -m gpu -q --durations=6 > gpurun_out/r5_suite_final.log 2>&1
 tail -12 gpurun_out/r5_suite_final.log

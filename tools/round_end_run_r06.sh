@@ -16,5 +16,5 @@ timeout 900 python bench.py --workload c5 --steps 8 --warmup 4 --scale-recall-nu
 } > gpurun_out/r06_scale_runs.txt 2>&1
 G1=2 timeout 600 python tools/shard_two_phase.py 2e7 2,4,8 100 2>&1 | grep -v amdgpu.ids > gpurun_out/r06_emul_20m_final.txt
 G1=2 timeout 900 python tools/shard_two_phase.py 1e8 2,4,8 150 2>&1 | grep -v amdgpu.ids > gpurun_out/r06_emul_100m_final.txt
-python bench.py > gpurun_out/r06_bench.json 2> gpurun_out/r06_bench.err
-tail -c 400 gpurun_out/r06_bench.json
+python bench.py --full > "${OUT_DIR:-${TMPDIR:-/tmp}}/r06_bench.json" 2> "${OUT_DIR:-${TMPDIR:-/tmp}}/r06_bench.err"
+tail -c 400 "${OUT_DIR:-${TMPDIR:-/tmp}}/r06_bench.json"
