@@ -89,6 +89,15 @@ SYMBOLS = {
     "gamma_hip_ivfpq_update": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, u8p]),
     "gamma_hip_vid2docid_append": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_int32)]),
     "gamma_hip_vid2docid_count": (C.c_int64, [C.c_void_p]),
+    "gamma_hip_binivf_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "gamma_hip_binivf_train": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, u8p, C.c_int, u8p]),
+    "gamma_hip_binivf_set_trained": (C.c_int, [C.c_void_p, u8p]),
+    "gamma_hip_binivf_assign": (C.c_int, [C.c_void_p, C.c_int64, u8p, C.c_int, i32p, i64p]),
+    "gamma_hip_binivf_add": (C.c_int, [C.c_void_p, C.c_int64, u8p, C.c_int64]),
+    "gamma_hip_binivf_search": (C.c_int, [C.c_void_p, C.POINTER(SearchParams), C.c_int, u8p, C.c_int, f32p, i64p]),
+    "gamma_hip_binivf_search_device": (C.c_int, [C.c_void_p, C.POINTER(SearchParams), C.c_int, C.c_void_p, C.c_int,
+                                                 C.c_void_p, C.c_void_p]),
+    "gamma_hip_binivf_stats": (C.c_int, [C.c_void_p, i64p, C.c_int]),
     "gamma_hip_ivfflat_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "gamma_hip_ivfflat_set_trained": (C.c_int, [C.c_void_p, f32p]),
     "gamma_hip_ivfflat_search": (C.c_int, [C.c_void_p, C.POINTER(SearchParams), C.c_int, f32p, C.c_int, f32p, i64p]),

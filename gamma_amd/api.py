@@ -368,6 +368,55 @@ class GammaHip:
     def ivfflat_search_device(self, d_x, nq, k, args, d_D, d_I):
         self._ck(self.L.gamma_hip_ivfflat_search_device(self.h, args.ref(), nq, d_x, k, d_D, d_I), "ivfflat_search_device")
 
+    # ---- binary IVF (codes of nbits bits: uint8 rows of nbits / 8 bytes) ----
+    def binivf_init(self, nbits, nlist, bucket_init_size=1000, bucket_max_size=1280000):
+        self._ck(self.L.gamma_hip_binivf_init(self.h, nbits, nlist, bucket_init_size, bucket_max_size), "binivf_init")
+        self.d, self.nlist, self.M = nbits, nlist, nbits // 8
+
+    def binivf_train(self, codes, nlist):
+        """IndexBinaryIVF::train on the device: the centroid codes [nlist, nbits / 8]"""
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        out = np.empty((nlist, codes.shape[1]), dtype=np.uint8)
+        self._ck(self.L.gamma_hip_binivf_train(self.h, codes.shape[1] * 8, codes.shape[0], _p(codes, _lib.u8p), nlist,
+                                               _p(out, _lib.u8p)), "binivf_train")
+        return out
+
+    def binivf_set_trained(self, centroid_codes):
+        cc = np.ascontiguousarray(centroid_codes, dtype=np.uint8)
+        self._ck(self.L.gamma_hip_binivf_set_trained(self.h, _p(cc, _lib.u8p)), "binivf_set_trained")
+
+    def binivf_assign(self, codes, k=1):
+        """quantizer->search with k: (distances int32 [n, k], labels int64 [n, k])"""
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        n = codes.shape[0]
+        D = np.empty((n, k), dtype=np.int32)
+        I = np.empty((n, k), dtype=np.int64)
+        self._ck(self.L.gamma_hip_binivf_assign(self.h, n, _p(codes, _lib.u8p), k, _p(D, _lib.i32p), _p(I, _lib.i64p)),
+                 "binivf_assign")
+        return D, I
+
+    def binivf_add(self, codes, first_vid):
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        self._ck(self.L.gamma_hip_binivf_add(self.h, codes.shape[0], _p(codes, _lib.u8p), first_vid), "binivf_add")
+
+    def binivf_search(self, x, k, args):
+        x = np.ascontiguousarray(x, dtype=np.uint8)
+        nq = x.shape[0]
+        D = np.empty((nq, max(k, 0)), dtype=np.float32)
+        I = np.empty((nq, max(k, 0)), dtype=np.int64)
+        self._ck(self.L.gamma_hip_binivf_search(self.h, args.ref(), nq, _p(x, _lib.u8p), k, _p(D, _lib.f32p),
+                                                _p(I, _lib.i64p)), "binivf_search")
+        return D, I
+
+    def binivf_search_device(self, d_x, nq, k, args, d_D, d_I):
+        self._ck(self.L.gamma_hip_binivf_search_device(self.h, args.ref(), nq, d_x, k, d_D, d_I), "binivf_search_device")
+
+    def binivf_stats(self, reset=False):
+        """(queries searched, heap admissions of their scans)"""
+        out = np.zeros(2, dtype=np.int64)
+        self._ck(self.L.gamma_hip_binivf_stats(self.h, _p(out, _lib.i64p), 1 if reset else 0), "binivf_stats")
+        return int(out[0]), int(out[1])
+
     def last_stages(self, nq, nprobe, R):
         cd = np.empty((nq, nprobe), dtype=np.float32)
         ci = np.empty((nq, nprobe), dtype=np.int64)

@@ -332,6 +332,11 @@ struct gamma_hip_index {
         return dd >= 0 && dd < bitmap_bits && !h_bitmap.empty() && ((h_bitmap[dd >> 3] >> (dd & 7)) & 1);
     }
     bool ivfflat = false;      // gamma_hip_ivfflat_init: lists of vector ids (1 dummy code byte), rows from the raw store
+    // gamma_hip_binivf_init (ivfflat is set too: no PQ tables, no code sums): lists of binary codes (code_size = nbits / 8),
+    // d = nbits; the centroid codes, the search's {queries, heap admissions} counters (gamma_hip_binivf_stats)
+    bool binivf = false;
+    uint8_t* d_bin_cc = nullptr;
+    unsigned long long* d_bin_stats = nullptr;
     int coarse_cap = gh::kCoarseCap;
     unsigned long long* d_tie_stats = nullptr;   // {coarse rows redone, top-R cuts through a tie, queries replayed}
     // what stage A leaves for the tie replay of stage B (ties.hip)

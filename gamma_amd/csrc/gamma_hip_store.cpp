@@ -1,6 +1,7 @@
 // gamma_hip_store.cpp -- the writers of libgamma_hip.so: the realtime inverted-list arena (growth law, repack,
 // versioned (offset, length) tables), training state, Add / Update / Delete / compaction, device-side encoding, the raw
 // vector store, scalar columns and the delete bitmap.  C ABI: include/gamma_hip.h.
+#include "binivf.h"
 #include "gamma_hip_internal.h"
 
 namespace ghi {
@@ -955,7 +956,7 @@ int gamma_hip_bitmap_set(gamma_hip_index* h, const int64_t* docids, int64_t n, i
 
 /* ---- IVFPQ / IVFFLAT models ----------------------------------------------------------- */
 static int ivf_init_locked(gamma_hip_index* h, int d, int nlist, int M, int metric, int bucket_init_size,
-                           int bucket_max_size, bool flat);
+                           int bucket_max_size, bool flat, bool binary = false);
 int gamma_hip_ivfpq_init(gamma_hip_index* h, int d, int nlist, int M, int nbits, int metric,
                          int bucket_init_size, int bucket_max_size) {
     if (!h) return GAMMA_HIP_EINVAL;
@@ -982,8 +983,9 @@ int gamma_hip_ivfpq_use_precomputed_table(gamma_hip_index* h) {
     return h->table_mode;
 }
 
+// binary: the binary IVF model -- no float centroids, PQ codebooks or tables (gamma_hip_binivf_init)
 static int ivf_init_locked(gamma_hip_index* h, int d, int nlist, int M, int metric, int bucket_init_size,
-                           int bucket_max_size, bool flat) {
+                           int bucket_max_size, bool flat, bool binary) {
     if (metric != GAMMA_HIP_METRIC_IP && metric != GAMMA_HIP_METRIC_L2) return fail(h, GAMMA_HIP_EINVAL, "bad metric");
     GH_CHECK(h, hipSetDevice(h->device));
     h->ivfflat = flat;
@@ -1000,10 +1002,13 @@ static int ivf_init_locked(gamma_hip_index* h, int d, int nlist, int M, int metr
     h->metric = metric;
     h->bucket_init = bucket_init_size > 0 ? bucket_init_size : 1000;
     h->bucket_max = bucket_max_size > 0 ? bucket_max_size : 1280000;
-    GH_CHECK(h, hipMalloc((void**)&h->d_cc, (size_t)nlist * d * sizeof(float)));
-    GH_CHECK(h, hipMalloc((void**)&h->d_cc_norms, (size_t)nlist * sizeof(float)));
-    GH_CHECK(h, hipMalloc((void**)&h->d_pqc, flat ? 256 : (size_t)M * 256 * h->dsub * sizeof(float)));
-    if (flat || h->table_mode == 1) GH_CHECK(h, hipMalloc((void**)&h->d_T2, flat ? 256 : (size_t)nlist * M * 256 * sizeof(float)));
+    if (!binary) {
+        GH_CHECK(h, hipMalloc((void**)&h->d_cc, (size_t)nlist * d * sizeof(float)));
+        GH_CHECK(h, hipMalloc((void**)&h->d_cc_norms, (size_t)nlist * sizeof(float)));
+        GH_CHECK(h, hipMalloc((void**)&h->d_pqc, flat ? 256 : (size_t)M * 256 * h->dsub * sizeof(float)));
+        if (flat || h->table_mode == 1)
+            GH_CHECK(h, hipMalloc((void**)&h->d_T2, flat ? 256 : (size_t)nlist * M * 256 * sizeof(float)));
+    }
     for (int v = 0; v < H::NVER; v++) {
         GH_CHECK(h, hipMalloc((void**)&h->d_ver_off[v], (size_t)nlist * sizeof(int64_t)));
         GH_CHECK(h, hipMalloc((void**)&h->d_ver_len[v], (size_t)nlist * sizeof(int)));
@@ -1039,11 +1044,38 @@ int gamma_hip_ivfflat_init(gamma_hip_index* h, int d, int nlist, int metric, int
 int gamma_hip_ivfflat_set_trained(gamma_hip_index* h, const float* cc) {
     if (!h || !cc) return GAMMA_HIP_EINVAL;
     WriteLock lk(h);
-    if (!h->ivf_init || !h->ivfflat) return fail(h, GAMMA_HIP_EINVAL, "ivfflat not initialised");
+    if (!h->ivf_init || !h->ivfflat || h->binivf) return fail(h, GAMMA_HIP_EINVAL, "ivfflat not initialised");
     GH_CHECK(h, hipSetDevice(h->device));
     GH_CHECK(h, hipMemcpyAsync(h->d_cc, cc, (size_t)h->nlist * h->d * sizeof(float), hipMemcpyHostToDevice, h->wstream));
     gh::launch_row_norms(h->wstream, h->d_cc, h->nlist, h->d, h->d_cc_norms);
     GH_CHECK(h, hipGetLastError());
+    GH_CHECK(h, hipStreamSynchronize(h->wstream));
+    h->trained = true;
+    return GAMMA_HIP_OK;
+}
+
+int gamma_hip_binivf_init(gamma_hip_index* h, int nbits, int nlist, int bucket_init_size, int bucket_max_size) {
+    if (!h) return GAMMA_HIP_EINVAL;
+    WriteLock lk(h);
+    if (h->ivf_init) return fail(h, GAMMA_HIP_EINVAL, "already initialised");
+    if (nbits <= 0 || nbits % 8 != 0 || nbits / 8 > gh::kBinMaxCodeSize || nlist <= 0)
+        return fail(h, GAMMA_HIP_EINVAL, "bad nbits / nlist (nbits % 8 == 0, at most 2048 bits)");
+    // the IVFFLAT set-up with M = code_size: code_size bytes per list entry; no float centroids, PQ tables or code sums
+    GH_TRY(ivf_init_locked(h, nbits, nlist, nbits / 8, GAMMA_HIP_METRIC_L2, bucket_init_size, bucket_max_size, true, true));
+    h->binivf = true;
+    GH_CHECK(h, hipMalloc((void**)&h->d_bin_cc, (size_t)nlist * h->code_size));
+    GH_CHECK(h, hipMalloc((void**)&h->d_bin_stats, 2 * sizeof(unsigned long long)));
+    GH_CHECK(h, hipMemset(h->d_bin_stats, 0, 2 * sizeof(unsigned long long)));
+    return GAMMA_HIP_OK;
+}
+
+int gamma_hip_binivf_set_trained(gamma_hip_index* h, const uint8_t* centroid_codes) {
+    if (!h || !centroid_codes) return GAMMA_HIP_EINVAL;
+    WriteLock lk(h);
+    if (!h->ivf_init || !h->binivf) return fail(h, GAMMA_HIP_EINVAL, "binivf not initialised");
+    GH_CHECK(h, hipSetDevice(h->device));
+    GH_CHECK(h, hipMemcpyAsync(h->d_bin_cc, centroid_codes, (size_t)h->nlist * h->code_size, hipMemcpyHostToDevice,
+                               h->wstream));
     GH_CHECK(h, hipStreamSynchronize(h->wstream));
     h->trained = true;
     return GAMMA_HIP_OK;
@@ -1482,6 +1514,7 @@ int gamma_hip_ivfpq_encode_each(gamma_hip_index* h, int64_t n, const float* vecs
 static int encode_host(gamma_hip_index* h, int64_t n, const float* vecs, int64_t* list_nos, uint8_t* codes, bool exact) {
     if (!h || n < 0 || (n > 0 && (!vecs || !list_nos || !codes))) return GAMMA_HIP_EINVAL;
     WriteLock lk(h);
+    if (h->binivf) return fail(h, GAMMA_HIP_EINVAL, "binary IVF handle: gamma_hip_binivf_add");
     if (!h->trained) return fail(h, GAMMA_HIP_ENOTTRAINED, "not trained");
     if (n == 0) return GAMMA_HIP_OK;
     if (!exact && blas_form_not_restated(n, h->nlist, h->d)) h->blas_unrestated++;

@@ -10,6 +10,7 @@
 // compiled faiss (tests/test_training_cpu.py).
 #include <random>
 
+#include "binivf.h"
 #include "gamma_hip_internal.h"
 
 using namespace ghi;
@@ -58,44 +59,63 @@ int split_clusters(int d, int k, int64_t n, float* hassign, float* centroids) {
     return nsplit;
 }
 
-}  // namespace
 
-extern "C" {
-
-void gamma_hip_rand_perm(int32_t* perm, int64_t n, int64_t seed) {
-    std::vector<int> p;
-    rand_perm(p, (size_t)std::max<int64_t>(n, 0), seed);
-    for (int64_t i = 0; i < n; i++) perm[i] = p[i];
+// binary_to_real (faiss:utils/utils.cpp:634-638) of one code of d bits
+void bin_decode_row(const uint8_t* c, int d, float* out) {
+    for (int i = 0; i < d; i++) out[i] = (float)(2 * ((c[i >> 3] >> (i & 7)) & 1) - 1);
 }
 
-int gamma_hip_kmeans(gamma_hip_index* h, int d, int64_t n, const float* x_in, int k, int niter, int64_t seed,
-                     int max_points_per_centroid, float* centroids, float* objective) {
-    if (!h || d <= 0 || k <= 0 || niter < 0 || max_points_per_centroid <= 0 || !x_in || !centroids) return GAMMA_HIP_EINVAL;
+}  // namespace
+
+namespace ghi {
+
+// Clustering::train (x_in: n x d floats) or Clustering::train_encoded through IndexBinaryIVF's IndexLSH codec (codes_in:
+// n codes of d bits, decoded to +-1 -- on the device for the training set, on the host for the k initial rows; the
+// assignment searches blocks of decode_block_size = 32768 points, faiss:Clustering.cpp:378-393, so the exact form is
+// chosen per block)
+static int kmeans_run(gamma_hip_index* h, int d, int64_t n, const float* x_in, const uint8_t* codes_in, int k, int niter,
+                      int64_t seed, int max_points_per_centroid, float* centroids, float* objective) {
+    if (!h || d <= 0 || k <= 0 || niter < 0 || max_points_per_centroid <= 0 || (!x_in && !codes_in) || !centroids)
+        return GAMMA_HIP_EINVAL;
+    if (codes_in && d % 8 != 0) return GAMMA_HIP_EINVAL;
     if (n < k) return fail(h, GAMMA_HIP_EINVAL, "k-means: fewer training points than clusters");
     SearchLock lk(h);
     GH_CHECK(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
     if (objective) *objective = 0.f;
+    const size_t cs = (size_t)d / 8;
     // subsample_training_set (:92-120): the first k * max_points of a permutation
     std::vector<float> xsub;
+    std::vector<uint8_t> csub;
     const float* x = x_in;
+    const uint8_t* codes = codes_in;
     if (n > (int64_t)k * max_points_per_centroid) {
         std::vector<int> perm;
         rand_perm(perm, (size_t)n, seed);
         const int64_t n2 = (int64_t)k * max_points_per_centroid;
-        xsub.resize((size_t)n2 * d);
-        for (int64_t i = 0; i < n2; i++) memcpy(&xsub[(size_t)i * d], x_in + (size_t)perm[i] * d, sizeof(float) * d);
+        if (codes) {
+            csub.resize((size_t)n2 * cs);
+            for (int64_t i = 0; i < n2; i++) memcpy(&csub[(size_t)i * cs], codes_in + (size_t)perm[i] * cs, cs);
+            codes = csub.data();
+        } else {
+            xsub.resize((size_t)n2 * d);
+            for (int64_t i = 0; i < n2; i++) memcpy(&xsub[(size_t)i * d], x_in + (size_t)perm[i] * d, sizeof(float) * d);
+            x = xsub.data();
+        }
         n = n2;
-        x = xsub.data();
     }
+    auto row = [&](int64_t i, float* out) {
+        if (codes) bin_decode_row(codes + (size_t)i * cs, d, out);
+        else memcpy(out, x + (size_t)i * d, sizeof(float) * d);
+    };
     if (n == k) {   // :334-355
-        memcpy(centroids, x, sizeof(float) * (size_t)d * k);
+        for (int i = 0; i < k; i++) row(i, centroids + (size_t)i * d);
         return GAMMA_HIP_OK;
     }
     {   // initial centroids: k points of a second permutation (:412-420)
         std::vector<int> perm;
         rand_perm(perm, (size_t)n, seed + 1);
-        for (int i = 0; i < k; i++) memcpy(centroids + (size_t)i * d, x + (size_t)perm[i] * d, sizeof(float) * d);
+        for (int i = 0; i < k; i++) row(perm[i], centroids + (size_t)i * d);
     }
     if (niter == 0) return GAMMA_HIP_OK;
     // device state: the training set (resident for the whole run), the centroids, their norms
@@ -115,19 +135,33 @@ int gamma_hip_kmeans(gamma_hip_index* h, int d, int64_t n, const float* x_in, in
     GH_CHECK(h, d_order.ensure((size_t)n * sizeof(int)));
     GH_CHECK(h, d_seg.ensure((size_t)(k + 1) * sizeof(int)));
     GH_CHECK(h, d_has.ensure((size_t)k * sizeof(float)));
-    GH_CHECK(h, hipMemcpyAsync(d_x.p, x, (size_t)n * d * sizeof(float), hipMemcpyHostToDevice, s));
+    if (codes) {   // the codes go up, the +-1 floats are made on the device
+        DevBuf d_codes;
+        GH_CHECK(h, d_codes.ensure((size_t)n * cs));
+        GH_CHECK(h, hipMemcpyAsync(d_codes.p, codes, (size_t)n * cs, hipMemcpyHostToDevice, s));
+        gh::launch_bin_decode(s, d_codes.as<uint8_t>(), n, d, d_x.as<float>());
+        GH_CHECK(h, hipGetLastError());
+        GH_CHECK(h, hipStreamSynchronize(s));
+        d_codes.release();
+    } else {
+        GH_CHECK(h, hipMemcpyAsync(d_x.p, x, (size_t)n * d * sizeof(float), hipMemcpyHostToDevice, s));
+    }
     GH_CHECK(h, hipMemcpyAsync(d_cen.p, centroids, (size_t)k * d * sizeof(float), hipMemcpyHostToDevice, s));
-    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n, (int64_t)(h->dist_budget_bytes / ((size_t)k * sizeof(float)))));
+    int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n, (int64_t)(h->dist_budget_bytes / ((size_t)k * sizeof(float)))));
+    if (codes) chunk = std::min<int64_t>(chunk, 32768);   // decode_block_size: one index.search per block
     GH_CHECK(h, h->w_mat.ensure((size_t)chunk * k * sizeof(float)));
     std::vector<int> assign(n), order(n), seg(k + 1);
     std::vector<float> hassign(k), dis;
-    const bool exact = n < 20;   // IndexFlatL2::search: the exact form below 20 queries (faiss:utils/distances.cpp:346)
-    if (!exact && blas_form_not_restated(n, k, d)) h->blas_unrestated++;
+    // IndexFlatL2::search: the exact form below 20 queries (faiss:utils/distances.cpp:346) -- of the whole call, or of
+    // each decode block
+    const bool exact_all = n < 20;
+    if (!exact_all && blas_form_not_restated(n, k, d)) h->blas_unrestated++;
     for (int it = 0; it < niter; it++) {
         // index.search(nx, x, 1, dis, assign)
-        if (!exact) gh::launch_row_norms(s, d_cen.as<float>(), k, d, d_cn.as<float>());
+        gh::launch_row_norms(s, d_cen.as<float>(), k, d, d_cn.as<float>());
         for (int64_t i0 = 0; i0 < n; i0 += chunk) {
             const int64_t nc = std::min(chunk, n - i0);
+            const bool exact = codes ? nc < 20 : exact_all;
             if (exact) gh::launch_pairwise(s, true, d_x.as<float>() + i0 * d, (int)nc, d, d_cen.as<float>(), k, h->w_mat.as<float>(), k);
             else gh::launch_l2_gemmform(s, d_x.as<float>() + i0 * d, (int)nc, d, d_cen.as<float>(), k, nullptr, d_cn.as<float>(),
                                         h->w_mat.as<float>(), k, true);
@@ -176,6 +210,40 @@ int gamma_hip_kmeans(gamma_hip_index* h, int d, int64_t n, const float* x_in, in
         float obj = 0;   // :478-481, float accumulation in point order
         for (int64_t j = 0; j < n; j++) obj += dis[j];
         *objective = obj;
+    }
+    return GAMMA_HIP_OK;
+}
+
+}  // namespace ghi
+
+extern "C" void gamma_hip_rand_perm(int32_t* perm, int64_t n, int64_t seed) {
+    std::vector<int> p;
+    rand_perm(p, (size_t)std::max<int64_t>(n, 0), seed);
+    for (int64_t i = 0; i < n; i++) perm[i] = p[i];
+}
+
+extern "C" {
+
+int gamma_hip_kmeans(gamma_hip_index* h, int d, int64_t n, const float* x_in, int k, int niter, int64_t seed,
+                     int max_points_per_centroid, float* centroids, float* objective) {
+    if (!x_in) return GAMMA_HIP_EINVAL;
+    return kmeans_run(h, d, n, x_in, nullptr, k, niter, seed, max_points_per_centroid, centroids, objective);
+}
+
+// IndexBinaryIVF::train as GammaIndexBinaryIVF configures it (gamma_index_binary_ivf.cc:90-124,208-266;
+// faiss:IndexBinaryIVF.cpp:241-280): Clustering(nbits, nlist) with niter 10, seed 1234, 256 points per centroid, trained
+// on the codes through the IndexLSH codec (+-1 floats), then real_to_binary (faiss:utils/utils.cpp:640-650: bit set only
+// for a component > 0).  codes: n x nbits / 8 bytes; centroid_codes: nlist x nbits / 8 bytes out.
+int gamma_hip_binivf_train(gamma_hip_index* h, int nbits, int64_t n, const uint8_t* codes, int nlist, uint8_t* centroid_codes) {
+    if (!h || nbits <= 0 || nbits % 8 != 0 || nlist <= 0 || !codes || !centroid_codes) return GAMMA_HIP_EINVAL;
+    std::vector<float> cen((size_t)nlist * nbits);
+    GH_TRY(kmeans_run(h, nbits, n, nullptr, codes, nlist, 10, 1234, 256, cen.data(), nullptr));
+    const int cs = nbits / 8;
+    for (int64_t i = 0; i < (int64_t)nlist * cs; i++) {
+        uint8_t b = 0;
+        for (int j = 0; j < 8; j++)
+            if (cen[(size_t)i * 8 + j] > 0) b |= (uint8_t)(1 << j);
+        centroid_codes[i] = b;
     }
     return GAMMA_HIP_OK;
 }

@@ -57,6 +57,25 @@ HOST_SYMBOLS = {
     "gh_iwpq_read": (C.c_int, [C.c_char_p, i64p, f32p, f32p, i64p, _lib.u8p, i64p]),
 }
 
+# the binary models' harness (gamma_amd/host/harness_binary.cc): rows are codes of d_bytes bytes
+u8p = _lib.u8p
+BIN_SYMBOLS = {
+    "gh_bin_new": (C.c_void_p, [C.c_char_p, C.c_int]),
+    "gh_bin_free": (None, [C.c_void_p]),
+    "gh_bin_init": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
+    "gh_bin_store": (None, [C.c_void_p, C.c_int, u8p]),
+    "gh_bin_indexing": (C.c_int, [C.c_void_p]),
+    "gh_bin_add": (C.c_int, [C.c_void_p, C.c_int, u8p]),
+    "gh_bin_update": (C.c_int, [C.c_void_p, C.c_int64, u8p]),
+    "gh_bin_delete": (C.c_int, [C.c_void_p, i64p, C.c_int]),
+    "gh_bin_search": (C.c_int, [C.c_void_p, C.c_char_p, C.c_float, C.c_float, C.c_int, u8p, C.c_int, f32p, i64p,
+                                C.c_int, i64p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "gh_bin_dump": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "gh_bin_load": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "gh_bin_mem_bytes": (C.c_long, [C.c_void_p]),
+    "gh_bin_binivf_state": (None, [C.c_void_p, C.POINTER(C.c_int)]),
+}
+
 _host = None
 FLT_MIN = float(np.finfo(np.float32).tiny)
 FLT_MAX = float(np.finfo(np.float32).max)
@@ -69,7 +88,7 @@ def load_host():
             raise _lib.GammaHipError("libgamma_host.so not found at %s -- run `make -C gamma_amd/host`"
                                      % HOST_LIB_PATH)
         L = C.CDLL(HOST_LIB_PATH)
-        for name, (res, args) in HOST_SYMBOLS.items():
+        for name, (res, args) in list(HOST_SYMBOLS.items()) + list(BIN_SYMBOLS.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -325,3 +344,77 @@ class PluginModel:
         if self.L.gh_host_ivfpq_state(self.h, _f(cc), _f(pq)):
             return None
         return cc, pq
+
+
+class BinaryPluginModel:
+    """The binary counterpart of PluginModel: one RetrievalModel (HIPBINARYIVF) over an in-memory BINARY store of
+    d_bytes-byte codes."""
+
+    def __init__(self, retrieval_type, d_bytes, model_param="", indexing_size=0):
+        self.L = load_host()
+        self.d_bytes = d_bytes
+        self.h = self.L.gh_bin_new(retrieval_type.encode(), d_bytes)
+        if not self.h:
+            raise _lib.GammaHipError("model %r is not registered" % retrieval_type)
+        rc = self.L.gh_bin_init(self.h, model_param.encode(), indexing_size)
+        if rc:
+            self.close()
+            raise _lib.GammaHipError("Init(%r) returned %d" % (model_param, rc))
+
+    def close(self):
+        if self.h:
+            self.L.gh_bin_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def store(self, codes):
+        codes = np.ascontiguousarray(codes, np.uint8)
+        self.L.gh_bin_store(self.h, codes.shape[0], codes.ctypes.data_as(u8p))
+
+    def indexing(self):
+        return self.L.gh_bin_indexing(self.h)
+
+    def add(self, codes):
+        """model->Add of codes already in the store; True when added"""
+        codes = np.ascontiguousarray(codes, np.uint8)
+        return self.L.gh_bin_add(self.h, codes.shape[0], codes.ctypes.data_as(u8p)) == 1
+
+    def update(self, vid, code):
+        code = np.ascontiguousarray(code, np.uint8)
+        return self.L.gh_bin_update(self.h, vid, code.ctypes.data_as(u8p))
+
+    def delete(self, vids):
+        vids = np.ascontiguousarray(vids, np.int64)
+        return self.L.gh_bin_delete(self.h, vids.ctypes.data_as(i64p), vids.size)
+
+    def search(self, x, k, retrieval_params="", min_score=FLT_MIN, max_score=FLT_MAX, ranges=None):
+        """ranges: None or [(docids, b_not_in)] range results.  Returns (rc, D, I)."""
+        x = np.ascontiguousarray(x, np.uint8)
+        n = x.shape[0]
+        D = np.empty((n, k), np.float32)
+        I = np.empty((n, k), np.int64)
+        ranges = ranges or []
+        docs = np.ascontiguousarray(np.concatenate([np.asarray(d, np.int64) for d, _ in ranges])
+                                    if ranges else np.zeros(1, np.int64), np.int64)
+        counts = (C.c_int * max(1, len(ranges)))(*[len(d) for d, _ in ranges])
+        nots = (C.c_int * max(1, len(ranges)))(*[1 if b else 0 for _, b in ranges])
+        rc = self.L.gh_bin_search(self.h, retrieval_params.encode(), min_score, max_score, n, x.ctypes.data_as(u8p), k,
+                                  _f(D), I.ctypes.data_as(i64p), len(ranges), docs.ctypes.data_as(i64p), counts, nots)
+        return rc, D, I
+
+    def dump(self, path):
+        return self.L.gh_bin_dump(self.h, path.encode())
+
+    def load(self, path):
+        return self.L.gh_bin_load(self.h, path.encode())
+
+    def mem_bytes(self):
+        return self.L.gh_bin_mem_bytes(self.h)
+
+    def state(self):
+        """(nlist, nprobe, nbits, trained) of a HIPBINARYIVF model"""
+        out = (C.c_int * 4)()
+        self.L.gh_bin_binivf_state(self.h, out)
+        return dict(zip(["nlist", "nprobe", "nbits", "trained"], list(out)))

@@ -382,6 +382,43 @@ int gamma_hip_ivfflat_search(gamma_hip_index* h, const gamma_hip_search_params* 
 int gamma_hip_ivfflat_search_device(gamma_hip_index* h, const gamma_hip_search_params* p, int nq, const float* d_x,
                                     int k, float* d_distances, int64_t* d_labels);
 
+/* ---- binary IVF (index/impl/gamma_index_binary_ivf.{h,cc}, faiss 1.7.1 IndexBinaryIVF) ------------------------------
+ * Codes of nbits bits (nbits % 8 == 0, at most 2048; VectorValueType::BINARY), Hamming distances.  The lists are the
+ * realtime lists of the other models with code_size = nbits / 8 (RTInvertIndex(nlist, code_size, ..), :103-106): after
+ * _init the list entry points above serve the handle unchanged -- gamma_hip_ivfpq_add_keys(_batch), _delete (Delete
+ * only counts, :275-279; this model never compacts), _get_list, _list_size, _list_capacity, _arena_stats.  The entry
+ * points of the float models (PQ / IVFFLAT training, encode, add, update_batch, searches) answer GAMMA_HIP_EINVAL on a
+ * binary handle.  Update, Dump and Load are no-ops in the reference (gamma_index_binary_ivf.h:99-104); they have no
+ * counterpart here. */
+/* replaces Init (:82-124): nlist = ncentroids, bucket_init_size = max(1000, indexing_size / ncentroids), bucket_max 1280000 */
+int gamma_hip_binivf_init(gamma_hip_index* h, int nbits, int nlist, int bucket_init_size, int bucket_max_size);
+/* replaces IndexBinaryIVF::train as Indexing runs it (:208-266, faiss:IndexBinaryIVF.cpp:241-280): the codes decoded to
+ * +-1 on the device, the k-means of gamma_hip_kmeans (niter 10, seed 1234, 256 points per centroid; n == nlist copies),
+ * real_to_binary.  codes: n x nbits / 8 host; centroid_codes: nlist x nbits / 8 host out.  Needs no _init. */
+int gamma_hip_binivf_train(gamma_hip_index* h, int nbits, int64_t n, const uint8_t* codes, int nlist, uint8_t* centroid_codes);
+/* quantizer->add of the trained centroid codes (nlist x nbits / 8) */
+int gamma_hip_binivf_set_trained(gamma_hip_index* h, const uint8_t* centroid_codes);
+/* replaces quantizer->search (IndexBinaryFlat::search, faiss:IndexBinaryFlat.cpp:33-59): the k nearest centroids of n
+ * codes, best first, equal distances in the heap's order; k > nlist pads with label -1 / distance INT32_MAX.  k = 1 is
+ * quantizer->assign (the lowest centroid index among equal distances).  distances may be NULL.  k <= 4096. */
+int gamma_hip_binivf_assign(gamma_hip_index* h, int64_t n, const uint8_t* codes, int k, int32_t* distances, int64_t* labels);
+/* replaces Add (:148-206): assign + AddKeys, vids first_vid .. first_vid + n - 1; GAMMA_HIP_ENOTTRAINED before training */
+int gamma_hip_binivf_add(gamma_hip_index* h, int64_t n, const uint8_t* codes, int64_t first_vid);
+/* replaces Search + search_knn_hamming_heap (:281-404): x nq x nbits / 8 host; distances / labels nq x k host, best first,
+ * empty slots label -1 / distance 2147483648.0f ((float)INT32_MAX).  Of gamma_hip_search_params it uses nprobe (the
+ * request's if it lies in (0, nlist], else 20), min_score / max_score (IsSimilarScoreValid on the Hamming distance; the
+ * default window [FLT_MIN, FLT_MAX] excludes distance 0), the range filters, the device field and term filters; metric,
+ * recall_num, has_rank, coarse_mode and exact_ties are ignored -- the reference's heap order is the only mode.
+ * k > 4096 (the scan's heap is in LDS) or nprobe > 4096: GAMMA_HIP_EUNSUPPORTED. */
+int gamma_hip_binivf_search(gamma_hip_index* h, const gamma_hip_search_params* p, int nq, const uint8_t* x, int k,
+                            float* distances, int64_t* labels);
+/* same, all pointers in device memory, enqueued on the handle's stream, no sync */
+int gamma_hip_binivf_search_device(gamma_hip_index* h, const gamma_hip_search_params* p, int nq, const uint8_t* d_x, int k,
+                                   float* d_distances, int64_t* d_labels);
+/* {queries searched, heap admissions of their scans} since the last reset (the serial part of a query's scan); counted
+ * only by searches made while gamma_hip_profile_enable is on */
+int gamma_hip_binivf_stats(gamma_hip_index* h, int64_t* out2, int reset);
+
 /* ---- search ------------------------------------------------------------------------ */
 /* replaces GammaIVFPQIndex::Search (gamma_index_ivfpq.cc:514-566 + search_preassigned
  * :701-890).  x: nq*d fp32 host; distances/labels: nq*k host, best first, unused slots
