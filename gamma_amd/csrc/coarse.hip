@@ -630,14 +630,8 @@ void launch_coarse_fused(hipStream_t s, const CoarseFusedPlan& pl, void* ws, con
     // (the recompute stays on the caller's stream: beside the caller's next kernel -- the query tables, which fill the
     //  chip -- its few workgroups wait for slots and the launch takes 65 us instead of 25; the walk, one wave per row and
     //  all latency, is what runs beside it)
-    static const bool store_side = getenv("GAMMA_HIP_COARSE_STORE_SIDE") != nullptr;
     hipStream_t rs = s;
     const bool forked = side && fork && join;
-    if (forked && store_side) {
-        (void)hipEventRecord(fork, s);
-        (void)hipStreamWaitEvent(side, fork, 0);
-        rs = side;
-    }
     float* full = reinterpret_cast<float*>(b + pl.off_full);
     {
         // (64 strips: the few workgroups that have rows to do take one tile each at nlist 4096 -- the launch is the latency of one)
@@ -654,7 +648,7 @@ void launch_coarse_fused(hipStream_t s, const CoarseFusedPlan& pl, void* ws, con
         }
 #undef GH_CR
     }
-    if (forked && !store_side) {
+    if (forked) {
         (void)hipEventRecord(fork, s);
         (void)hipStreamWaitEvent(side, fork, 0);
         rs = side;

@@ -133,10 +133,8 @@ static void combine_worker(gamma_hip_index* h) {
     for (auto& e : done_ev)
         // (blocking: the worker sleeps while the GPU runs its batch instead of spinning on a core for the whole busy
         //  period -- with 128 clients under the test box's 16-core quota 275 k -> 328 k queries/s sustained, the
-        //  median latency no worse; GAMMA_HIP_COMB_SPIN=1 spins)
-        if (hipEventCreateWithFlags(&e, hipEventDisableTiming | (getenv("GAMMA_HIP_COMB_SPIN") ? 0 : hipEventBlockingSync)) !=
-            hipSuccess)
-            e = nullptr;
+        //  median latency no worse)
+        if (hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventBlockingSync) != hipSuccess) e = nullptr;
     static const bool dbg = getenv("GAMMA_HIP_COMB_DBG") != nullptr;   // phase times of the worker, printed at exit
     double us_stage = 0, us_deliver = 0, us_sync = 0;
     long n_batches = 0, n_reqs = 0;
@@ -146,15 +144,9 @@ static void combine_worker(gamma_hip_index* h) {
         if (h->comb_stop) break;
         h->comb_busy = true;
         // The handle stays busy until the queue is drained.  One batch at a time: formed, staged, enqueued, awaited
-        // through its event, handed to the notifier.  GAMMA_HIP_COMB_PIPELINE=1 keeps TWO in flight (batch N+1 is
-        // formed and enqueued while the GPU runs batch N; the stream orders them, so workspaces are reused safely and
-        // results land in different staging sets; search_mu is then held across batches and given up at least every
-        // 32).  Measured with closed-loop single-query clients (tools/plugin_clients.py): no gain -- 8 threads 67 k
-        // against 67 k queries/s, 32 threads 190 k against 196 k, 128 threads 440 k against 470 k with a worse p99: the
-        // batches get smaller by what the overlap saves, each still pays its fixed 20 us of enqueue and ~45 us of GPU.
-        Batch prev;
-        bool have_prev = false;
-        int streak = 0;
+        // through its event, handed to the notifier; search_mu is given up after every batch.  (Two batches in flight --
+        // batch N+1 formed and enqueued while the GPU runs batch N -- was tried and removed: no gain, the batches get smaller
+        // by what the overlap saves; numbers in DESIGN_HISTORY.md.)
         // await and deliver a batch; its per-request redo when the batch failed as a whole
         auto finish = [&](Batch& b) {
             if (b.enqueued) {
@@ -244,7 +236,7 @@ static void combine_worker(gamma_hip_index* h) {
                     static const bool no_map = getenv("GAMMA_HIP_NO_MAPPED_RESULTS") != nullptr;
                     const bool map_ok = !no_map && h->comb_pin_dev[set] != nullptr;
                     set_busy[set].store(true, std::memory_order_release);
-                    if (!holding) {        // held while batches are in flight (the workspaces are in use), see below
+                    if (!holding) {        // held while the batch is in flight (the workspaces are in use)
                         h->search_mu.lock();
                         holding = true;
                     }
@@ -274,47 +266,19 @@ static void combine_worker(gamma_hip_index* h) {
                 set = (set + 1) % NSET;
             }
             const auto t_b = std::chrono::steady_clock::now();
-            // the batch before this one: await, deliver.  A failed batch is finished before anything else goes on.
-            if (have_prev) {
-                finish(prev);
-                have_prev = false;
-            }
+            if (!cur.grp.empty()) finish(cur);
             const auto t_c = std::chrono::steady_clock::now();
-            static const bool pipeline = getenv("GAMMA_HIP_COMB_PIPELINE") != nullptr;   // off: measured, see above
-            if (pipeline && cur.enqueued && cur.rc == GAMMA_HIP_OK && ++streak < 32) {
-                prev = std::move(cur);
-                have_prev = true;
-            } else if (!cur.grp.empty()) {
-                finish(cur);
-                streak = 32;
-            }
-            if (streak >= 32 && !have_prev) {   // nothing in flight: let others at the handle
-                if (holding) {
-                    h->search_mu.unlock();
-                    holding = false;
-                }
-                streak = 0;
+            if (holding) {   // nothing in flight: let others at the handle
+                h->search_mu.unlock();
+                holding = false;
             }
             if (dbg) {
                 us_stage += std::chrono::duration<double, std::micro>(t_b - t_a).count();
                 us_sync += std::chrono::duration<double, std::micro>(t_c - t_b).count();
             }
             lk.lock();
-            if (h->comb_q.empty()) {
-                if (have_prev) {   // drain the pipeline; requests may arrive meanwhile
-                    lk.unlock();
-                    finish(prev);
-                    have_prev = false;
-                    lk.lock();
-                }
-                if (h->comb_q.empty()) break;
-            }
+            if (h->comb_q.empty()) break;
         }
-        if (holding) {
-            h->search_mu.unlock();
-            holding = false;
-        }
-        streak = 0;
         h->comb_busy = false;
     }
     lk.unlock();
@@ -327,8 +291,8 @@ static void combine_worker(gamma_hip_index* h) {
     for (auto& e : done_ev)
         if (e) (void)hipEventDestroy(e);
     if (dbg && n_batches)
-        fprintf(stderr, "combine worker: %ld batches, %.1f requests each; per batch: group+stage+enqueue %.1f us (the batch before it on the GPU meanwhile), "
-                "(unused %.1f) then waiting for that batch %.1f us\n", n_batches, (double)n_reqs / n_batches, us_stage / n_batches, us_deliver / n_batches,
+        fprintf(stderr, "combine worker: %ld batches, %.1f requests each; per batch: group+stage+enqueue %.1f us, "
+                "(unused %.1f) then waiting for it and handing it on %.1f us\n", n_batches, (double)n_reqs / n_batches, us_stage / n_batches, us_deliver / n_batches,
                 us_sync / n_batches);
 }
 

@@ -317,12 +317,11 @@ int ivfpq_stage_a(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int
     // (with the byte-table filter pass a consumer probe costs a third of a producer's: five probes bound nearly as well as
     //  eight -- C3: scan 729 us at 8, 691 at 6, 676 at 5, 671 at 4 but with queries whose slices overflow; GAMMA_HIP_SCAN_G to sweep)
     static const bool no_c8 = getenv("GAMMA_HIP_NO_C8") != nullptr;
-    static const bool c8_m32 = getenv("GAMMA_HIP_C8_M32") != nullptr;
     // (recall_num up to 512 since round 6 -- with the wave-per-query selection of eight sorted runs, select.hip: C3 at
     //  recall_num 300 3.00 -> 2.07 ms per 16384 queries (scan 0.475 -> 0.675 of the roofline, select 910 -> 277 us), the C4 shape
     //  at 8 M 5.19 -> 3.96 ms per 8192; the candidate stages (1536 / 768 slots) overflow into the unfiltered path as ever)
-    static const int cf_maxr = getenv("GAMMA_HIP_CF_MAXR") ? atoi(getenv("GAMMA_HIP_CF_MAXR")) : 512;
-    const bool c8_shape = !no_c8 && l2 && (M == 16 || (M == 32 && c8_m32)) && R <= cf_maxr && h->d_sums && h->d_t2max;
+    constexpr int cf_maxr = 512;
+    const bool c8_shape = !no_c8 && l2 && M == 16 && R <= cf_maxr && h->d_sums && h->d_t2max;
     if (G0 == 8 && c8_shape && P > 8) G0 = 5;
     int64_t t2_bytes = (int64_t)nlist * M * 256 * sizeof(float);
     const bool compacted = shard && pre_dis && pre_probe;
@@ -364,10 +363,9 @@ int ivfpq_stage_a(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int
     // unfiltered selection is latency-bound anyway
     // (one group per query -- few probes, or a shard -- is fine: the producer bounds and compacts its own candidates)
     // (recall_num up to 1024 since round 5: slices of 2048 items and k_select_final_wg beyond 256 -- the configurations that need
-    //  a long short-list, full-size C5 at ~1000, keep the pre-filter; GAMMA_HIP_BOUND_MAXR: the old gate for A/B runs)
-    static const int scan_gmin = getenv("GAMMA_HIP_SCAN_GMIN") ? atoi(getenv("GAMMA_HIP_SCAN_GMIN")) : 4;
-    static const int bound_maxr = getenv("GAMMA_HIP_BOUND_MAXR") ? atoi(getenv("GAMMA_HIP_BOUND_MAXR")) : 1024;
-    bool bounded = (!shard || compacted) && h->scan_bound && R <= std::min(1024, bound_maxr) && P <= 128 && G >= (two ? 1 : scan_gmin);
+    //  a long short-list, full-size C5 at ~1000, keep the pre-filter)
+    constexpr int scan_gmin = 4, bound_maxr = 1024;
+    bool bounded = (!shard || compacted) && h->scan_bound && R <= bound_maxr && P <= 128 && G >= (two ? 1 : scan_gmin);
     if (bounded) {
         // feedback (gamma_hip_internal.h, bound_*): the counts of some recent call are in the pinned words
         static const bool no_fb = getenv("GAMMA_HIP_NO_BOUND_FEEDBACK") != nullptr;
@@ -417,15 +415,14 @@ int ivfpq_stage_a(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int
     // L2 table mode 0 (no precomputed table, H::table_mode): per-list tables from the residual (scan.hip RES) -- the plain and
     // the bounded loop; no query table, none of the passes built on T2 sums (d_sums is null: cf / c8 / q8 are off by their own gates)
     const bool res = l2 && h->table_mode == 0;
-    const bool fuse_ip = bounded && !res && PGN == 1 && (M == 16 || M == 32) && !getenv("GAMMA_HIP_NO_FUSED_IP");
+    static const bool no_fused_ip = getenv("GAMMA_HIP_NO_FUSED_IP") != nullptr;
+    const bool fuse_ip = bounded && !res && PGN == 1 && (M == 16 || M == 32) && !no_fused_ip;
     // the bounded scan's per-call state (repair list, ready words, survivor counts) is sized here, before the pair offsets,
     // whose kernel clears it together with the tie flags -- one launch instead of four fills in front of the scan
     // (byte-table filter pass: a first group of a few probes bounds loosely for some queries -- slices of 2048 keep them out of the
-    //  unfiltered path; GAMMA_HIP_SLICE_CAP to sweep)
-    static const int cap_env = getenv("GAMMA_HIP_SLICE_CAP") ? atoi(getenv("GAMMA_HIP_SLICE_CAP")) : 0;
-    // (clamped to 2048: the selection and the tie replay hold one slice in LDS)
-    const int cap = cap_env > 0 ? std::min(2048, std::max(cap_env, gh::scan_slice_cap(R))) : gh::scan_slice_cap(R);
-    bool cf_ok = false, q8_ok = false, q8_fused = false, one_wg = false;
+    //  unfiltered path; never beyond 2048: the selection and the tie replay hold one slice in LDS)
+    const int cap = gh::scan_slice_cap(R);
+    bool cf_ok = false, q8_ok = false;
     int PGM = PGN, nsl = PGN, cf_span = 0;
     unsigned long long* ready = nullptr;
     if (bounded) {
@@ -443,7 +440,7 @@ int ivfpq_stage_a(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int
         // with its own stage and slice (round 4, profiles/r04_scale_runs.txt) -- the margin candidates' exact recompute
         // and the second look at the codes cost more than the table build they save.  The split (cf_span) stays for the
         // lists in between: a consumer group takes at most ~64 k codes.
-        static const double cf_maxlen = getenv("GAMMA_HIP_SCAN_CF_MAXLEN") ? atof(getenv("GAMMA_HIP_SCAN_CF_MAXLEN")) : 2000.0;
+        constexpr double cf_maxlen = 2000.0;
         static const double cf_codes = getenv("GAMMA_HIP_SCAN_CF_CODES") ? atof(getenv("GAMMA_HIP_SCAN_CF_CODES")) : 65536.0;
         // (and short-lists only: the pass stages SCAN_CF_CAP = 768 candidates per consumer workgroup)
         cf_ok = !no_cf && R <= cf_maxr && (!h->prefiltered || h->cmp_has_sums) && PGN > 1 && mean_len <= cf_maxlen &&
@@ -451,7 +448,6 @@ int ivfpq_stage_a(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int
         // list-major byte-table pass for the consumer probes (q8scan.hip, round 5): same conditions as the filter pass it
         // replaces, one validity predicate for the whole call, not a shard (GAMMA_HIP_NO_Q8: the query-major pass, for A/B)
         static const bool no_q8 = getenv("GAMMA_HIP_NO_Q8") != nullptr;
-        static const double q8_maxlen = getenv("GAMMA_HIP_Q8_MAXLEN") ? atof(getenv("GAMMA_HIP_Q8_MAXLEN")) : 1e12;
         // (long lists: a tile's table staging and its chain of dependent loads are amortised over thousands of codes; at C3's
         //  244 codes per list a tile is one step of 64 codes per wave and the pass is latency-bound -- measured slower than the
         //  query-major pass there, profiles/r05_q8_*.txt -- so short lists keep the query-major filter pass)
@@ -465,7 +461,7 @@ int ivfpq_stage_a(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int
                 // (shadow lists of the standing deletes are as long as the lists: the pass stays on over them -- C4 shape at 20 M with
                 //  5 % deleted: 6.2 ms per 8192 queries without it, 4.5 unfiltered; lists cut down under a request's own clause
                 //  are as short as the clause makes them: the query-major pass)
-                (!h->prefiltered || (h->cmp_has_sums && !h->cmp_by_clause)) && !fc.d_qf && PGN > 1 && mean_len <= q8_maxlen &&
+                (!h->prefiltered || (h->cmp_has_sums && !h->cmp_by_clause)) && !fc.d_qf && PGN > 1 &&
                 gh::scan_cf_applies(l2, M, P, G, h->d_sums && h->d_t2max, false) && gh::q8_supported(M, P, G, q_stride0) && mean_len >= q8_minlen && nlist <= 16384;
         if (q8_ok) cf_ok = false;
         if (q8_ok) {
@@ -477,20 +473,10 @@ int ivfpq_stage_a(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int
             nc = std::max(1, std::min(nc, std::max(1, PGN - 1)));
             cf_span = nc > 1 ? (rest + nc - 1) / nc : 0;
             PGM = 1 + (nc > 1 ? (rest + cf_span - 1) / cf_span : 1);
-            // ONE workgroup per query (scan.hip, ScanBound::prod_c8): the bound from byte-image estimates of the first group, then
-            // the filter pass over all probes in the same workgroup; slice 0 = the survivors, slice 1 = those of the second stage
-            // of a query whose first group took the regular producer
-            // OFF by default (GAMMA_HIP_PROD_C8=1, parity-tested): the image's PROVEN error width (2.03 M delta: all sixteen
-            // quantisation errors of a code aligned) is ~14 times the typical error, the bound lets 875 survivors per query through
-            // instead of 225 and most queries overflow their slice (C3: scan 958 us, select 672 us against 613 / 101)
-            static const bool prod_c8_on = getenv("GAMMA_HIP_PROD_C8") != nullptr && atoi(getenv("GAMMA_HIP_PROD_C8")) != 0;
-            // (no validity predicates on this path: under a filter the first group rarely holds recall_num valid codes)
-            one_wg = prod_c8_on && c8_shape && M == 16 && !shard && !two && cf_span == 0 && P <= 64 && !need_ids;
-            if (one_wg) PGM = 1;
         } else {
             PGM = PGN;   // probe groups of the main launch
         }
-        if (!q8_ok) nsl = one_wg ? 2 : PGM;   // one survivor slice per probe group (slice 0: the producer's own)
+        if (!q8_ok) nsl = PGM;   // one survivor slice per probe group (slice 0: the producer's own)
         // rq | ready[nq] | gcnt[nq][nsl]   (rq: count + list of the queries that need the repair launch, 8-byte aligned)
         const size_t rq_bytes = (((size_t)nq + 1) * sizeof(int) + 7) & ~(size_t)7;
         GH_CHECK(h, h->w_scnt.ensure(rq_bytes + (size_t)nq * (sizeof(unsigned long long) + (size_t)nsl * sizeof(int))));
@@ -500,18 +486,9 @@ int ivfpq_stage_a(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int
     }
     {
         StageScope t(h, GAMMA_HIP_STAGE_TABLES);
-        // two-phase list shard on the list-major pass: every consumer of the query tables computes them on the fly (the
-        // producers: IPF; k_q8_quant / k_q8_exact: fx) -- W x 32 KB per query through HBM otherwise; only the rows of the
-        // queries the repair launch re-scores are written (launch_pq_ip_table_rows below)
-        // MEASURED SLOWER and off by default (GAMMA_HIP_Q8_FUSED_IP=1): an entry of the table is 4 bytes, the dsub = 4 codebook
-        // row it is made from 16 -- every workgroup pulling the 128 KB codebook through the L2 costs more than the 32 KB table
-        // from HBM (one emulated rank of 8, C4 shape 20 M: tables 0.49 -> 0.05 ms but scan 4.35 -> 5.5).  What does pay is
-        // k_q8_exact computing only its candidates' entries (Q8Args::xd).
-        static const bool q8_fused_on = getenv("GAMMA_HIP_Q8_FUSED_IP") != nullptr;
-        q8_fused = two && q8_ok && q8_fused_on && (M == 16 || M == 32);
         if (!fuse_ip && !res) {
             GH_CHECK(h, h->w_st2.ensure((size_t)nq * M * 256 * sizeof(float)));
-            if (!q8_fused) gh::launch_pq_ip_table(s, d_x, nq, d, M, h->d_pqc, h->w_st2.as<float>());
+            gh::launch_pq_ip_table(s, d_x, nq, d, M, h->d_pqc, h->w_st2.as<float>());
         }
         GH_TRY(coarse_join(h));
         // a deferred replay of the previous call / chunk reads what is written from here on (flag lists, pair offsets,
@@ -616,27 +593,11 @@ int ivfpq_stage_a(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int
         sb.t2max_all = h->t2max_all;
         sb.pair_base = h->w_pair_base.as<int64_t>();
         sb.cf_span = cf_ok ? cf_span : 0;
-        static const int spins_env = getenv("GAMMA_HIP_SCAN_SPINS") ? atoi(getenv("GAMMA_HIP_SCAN_SPINS")) : 0;
-        sb.spins = spins_env;
         sb.timeouts = h->d_bound_stat + 4;
         sb.slice_cap = cap;
-        // the producer on the filter pass's arithmetic too (scan.hip, prod_cf; with the query-major filter pass, not for shards).
-        // OFF by default: measured slower at C3 -- scan 828 us against 784 (878 before the variant was held to six waves per
-        // SIMD: 89 VGPRs), + 25 us for re-scoring the first group of the tie-flagged queries in front of the replay: the
-        // producer's chain (table, per-wave list walk, histogram, candidate pass, exact recompute, flush) is no shorter than
-        // eight per-list tables, and its bound is looser by the margin.  GAMMA_HIP_PROD_CF=1 turns it on (parity-tested).
-        static const bool prod_cf_on = getenv("GAMMA_HIP_PROD_CF") != nullptr;
-        sb.prod_cf = (cf_ok && !shard && prod_cf_on) ? 1 : 0;
         // the consumers' filter pass on a byte image of the query's table (scan.hip, "byte table")
-        const bool c8_on = c8_shape;
-        const int c8_mode = 1;
-        static const int scan_batch = getenv("GAMMA_HIP_SCAN_BATCH") ? atoi(getenv("GAMMA_HIP_SCAN_BATCH")) : 0;
-        sb.batch = scan_batch;
+        sb.c8 = (cf_ok && c8_shape && (cf_span > 0 ? cf_span : P - G) <= 64) ? 1 : 0;
         sb.dbg_part = h->scan_dbg_now;
-        sb.c8 = (cf_ok && !sb.prod_cf && c8_on && (cf_span > 0 ? cf_span : P - G) <= 64) ? c8_mode : 0;
-        sb.prod_c8 = (one_wg && sb.c8) ? 1 : 0;
-        if (one_wg && !sb.c8) return fail(h, GAMMA_HIP_EINVAL, "one workgroup per query without the byte-image pass");
-        const bool prod_approx = sb.prod_cf || sb.prod_c8;   // group 0's slab segment does not hold the reference's values
         // two-phase shard search: the producers' bounds out, the reduced (global) bounds back into the ready words
         auto exchange = [&]() -> int {
             gh::launch_bound_export(s, l2, sb.ready, nq, bx->d_bound);
@@ -667,7 +628,7 @@ int ivfpq_stage_a(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int
             gh::launch_ivfpq_scan_pair(s, l2, d_x, nq, d, M, P, h->w_probe.as<int>(), dis0, h->d_cc, h->scan_st2(l2), h->d_T2,
                                        h->d_list_off, h->d_list_len, h->d_list_mask, nlist, h->d_codes, h->d_ids,
                                        h->w_pair_off.as<int>(), q_stride, h->w_dist.as<float>(), fc.d_tab, fc.d_qf, need_ids, qperm, G, 0,
-                                       1, 0, &sb, q8_fused ? h->d_pqc : nullptr);
+                                       1, 0, &sb, nullptr);
             if (two) GH_TRY(exchange());   // (the list-major pass below reads the ready words: now the global bounds)
             GH_CHECK(h, h->w_q8.ensure((size_t)nq * M * 256));
             GH_CHECK(h, h->w_q8meta.ensure((size_t)nq * 4 * sizeof(float)));
@@ -679,7 +640,6 @@ int ivfpq_stage_a(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int
             qa.probe_list = h->w_probe.as<int>();
             qa.coarse_dis = dis0;
             qa.st2 = h->w_st2.as<float>();
-            if (q8_fused) qa.fx = d_x;
             static const bool no_demand = getenv("GAMMA_HIP_NO_Q8_DEMAND") != nullptr;
             if (shard && !no_demand) qa.xd = d_x;
             qa.pqc = h->d_pqc;
@@ -732,21 +692,13 @@ int ivfpq_stage_a(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int
         h->bound_calls++;
         if (PGN > 1 && !sb.store_all) {
             // queries the slices could not answer: their consumer groups are scored again, distances stored
-            // (prod_cf: group 0 too -- its slab segment holds approximate values -- and for the queries without a bound as well)
             StageScope t2(h, GAMMA_HIP_STAGE_SCAN, false);
-            if (sb.prod_cf) gh::launch_rq_nobound(s, sb.ready, nq, sb.rq_list, sb.rq_count);
-            if (q8_fused) gh::launch_pq_ip_table_rows(s, d_x, d, M, h->d_pqc, h->w_st2.as<float>(), sb.rq_list, sb.rq_count);
             gh::launch_ivfpq_scan_pair(s, l2, d_x, nq, d, M, P, h->w_probe.as<int>(), dis0, h->d_cc,
                                        h->scan_st2(l2), h->d_T2, h->d_list_off, h->d_list_len, h->d_list_mask,
                                        nlist, h->d_codes, h->d_ids, h->w_pair_off.as<int>(), q_stride,
-                                       h->w_dist.as<float>(), fc.d_tab, fc.d_qf, need_ids, nullptr, G, prod_approx ? 0 : 1,
-                                       prod_approx ? PGN : PGN - 1, shard ? 1 : 0, nullptr, nullptr, sb.rq_list, sb.rq_count);
+                                       h->w_dist.as<float>(), fc.d_tab, fc.d_qf, need_ids, nullptr, G, 1,
+                                       PGN - 1, shard ? 1 : 0, nullptr, nullptr, sb.rq_list, sb.rq_count);
         }
-        h->tie.prod_cf = prod_approx;
-        h->tie.need_ids = need_ids;
-        h->tie.d_ftab = fc.d_tab;
-        h->tie.d_qf = fc.d_qf;
-        h->tie.dis0 = dis0;
         gh::launch_select_topk(s, l2, h->w_dist.as<float>(), q_stride, h->w_qtotal.as<int>(), 0,
                                (int)std::min<int64_t>(q_stride, 1 << 30), nq, R,
                                out_dis, h->w_cand_pos.as<int>(), h->w_sflag.as<uint8_t>());
@@ -756,7 +708,6 @@ int ivfpq_stage_a(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int
             h->tie.bounded = true;
             h->tie.nsl = nsl;
             h->tie.cap = cap;
-            h->tie.slice0_all = sb.prod_c8 != 0;
         }
         if (dbg && shown++ >= dbg_from && shown <= dbg_from + 5) {
             std::vector<uint8_t> hf(nq);
@@ -830,7 +781,6 @@ int ivfpq_stage_b(H* h, const gamma_hip_search_params* p, int nq, const float* d
         a.gcnt = reinterpret_cast<int*>(ready + nq);
         a.nsl = h->tie.nsl;
         a.slice_cap = h->tie.cap;
-        a.slice0_all = h->tie.slice0_all ? 1 : 0;
         a.x = d_x;
         a.d = h->d;
         a.raw = h->d_raw;
@@ -845,16 +795,6 @@ int ivfpq_stage_b(H* h, const gamma_hip_search_params* p, int nq, const float* d
         a.cand_ids = const_cast<int64_t*>(cand_ids);
         a.distances = d_distances;
         a.labels = d_labels;
-        if (h->tie.prod_cf) {
-            // the flagged queries' first probe group: the slab holds the producer's approximate values (ScanBound::prod_cf), the
-            // replay walks the reference's -- re-scored here, on the search stream, in front of the replay (the tables and the
-            // assignment of this call are still in place)
-            gh::launch_ivfpq_scan_pair(s, l2, d_x, nq, h->d, h->M, p->nprobe, h->w_probe.as<int>(), h->tie.dis0, h->d_cc,
-                                       h->scan_st2(l2), h->d_T2, h->d_list_off, h->d_list_len, h->d_list_mask, h->nlist,
-                                       h->d_codes, h->d_ids, h->w_pair_off.as<int>(), h->tie.q_stride, h->w_dist.as<float>(),
-                                       static_cast<const gh::FilterDesc*>(h->tie.d_ftab), h->tie.d_qf, h->tie.need_ids, nullptr,
-                                       h->tie.G, 0, 1, 0, nullptr, nullptr, tf.list, tf.count);
-        }
         static const bool no_side = getenv("GAMMA_HIP_NO_SIDE_STREAM") != nullptr;
         if (h->defer_now && h->side2 && !no_side) {
             // beside whatever the search stream does next that does not touch the replay's inputs (replay_join)
@@ -913,7 +853,7 @@ int ivfpq_stage_b(H* h, const gamma_hip_search_params* p, int nq, const float* d
 // chain costs ~4 us of launch + drain at this size, whatever it computes.
 bool ivfpq_small_ok(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int nq, int R) {
     static const bool off = getenv("GAMMA_HIP_NO_SMALL_PATH") != nullptr;
-    static const int max_nq = getenv("GAMMA_HIP_SMALL_MAX") ? atoi(getenv("GAMMA_HIP_SMALL_MAX")) : 512;
+    constexpr int max_nq = 512;   // (the section's header: the measured cross-over with the regular chain is ~1000)
     // exact coarse distances (faiss below 20 queries) come from the fused first kernel, which covers 16 queries; the
     // GEMM form (20 queries and more) from the regular matrix kernel
     return !off && h->small_path && nq >= 1 && nq <= max_nq &&
@@ -949,12 +889,11 @@ int ivfpq_small(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int n
     // long lists: the scan walks a work list of (query, probe, chunk of the list) units written by the selection kernel,
     // pieces of even size for a grid that fills the chip, instead of one workgroup per pair that runs for as long as its
     // list is (small_presel: tests force the path on short lists)
-    static const int chunk_env = getenv("GAMMA_HIP_SMALL_CHUNK") ? atoi(getenv("GAMMA_HIP_SMALL_CHUNK")) : 512;
     int chunk_len = 0, max_units = 0;
     uint32_t* d_units = nullptr;
     int* d_nunits = nullptr;
     if (h->ntotal / std::max(1, nlist) > 1024 || h->max_list_len > 8192 || h->small_presel > 0) {
-        chunk_len = h->small_presel > 0 ? 512 : std::max(512, (chunk_env + 511) & ~511);
+        chunk_len = 512;
         const int64_t mu = (int64_t)nq * P * (1 + (int64_t)h->max_list_len / chunk_len);
         max_units = (int)std::min<int64_t>(mu, INT32_MAX);
         GH_CHECK(h, h->w_lm_units.ensure((size_t)mu * sizeof(uint32_t)));
@@ -1230,6 +1169,7 @@ int ivfpq_search_device_locked(H* h, const gamma_hip_search_params* p, int nq, c
     } defer_scope{h, h->defer_now};
     const bool defer_inside = chunk < nq && !h->defer_now && h->side2 != nullptr;
     if (defer_inside) h->defer_now = true;
+    static const bool no_rerank_order = getenv("GAMMA_HIP_NO_RERANK_ORDER") != nullptr;
     for (int q0 = 0; q0 < nq; q0 += chunk) {
         const int nc = std::min(chunk, nq - q0);
         if (coarse_first)
@@ -1239,7 +1179,7 @@ int ivfpq_search_device_locked(H* h, const gamma_hip_search_params* p, int nq, c
             GH_TRY(ivfpq_stage_a(h, p, fc.at(q0), nc, d_x + (size_t)q0 * h->d, R));
         GH_TRY(ivfpq_stage_b(h, p, nc, d_x + (size_t)q0 * h->d, R, k, h->w_cand_dis.as<float>(),
                              h->w_cand_ids.as<int64_t>(), d_distances + (size_t)q0 * k,
-                             d_labels + (size_t)q0 * k, getenv("GAMMA_HIP_NO_RERANK_ORDER") ? nullptr : h->last_qperm,
+                             d_labels + (size_t)q0 * k, no_rerank_order ? nullptr : h->last_qperm,
                              /*tie_mode=*/1));
         h->last_nq = nc;
     }
@@ -1531,8 +1471,7 @@ int flat_search_device_locked(H* h, const gamma_hip_search_params* p, int nq, co
     const bool mfma_filter = k <= 256 && N < ((int64_t)1 << 32) && gh::flat_filter_supported(nq, d, N);
     // (long rows: the first chunk's exact kernel runs at ~1.3 TFLOP/s -- 1024 rows of d = 768 instead of 16384: C5 flat, 1 M x 768,
     //  1024 queries: 15.6 / 16.1 / 16.8 / 18.4 ms per call with a first chunk of 2^10 / 2^11 / 2^12 / 2^13 rows)
-    static const int first_log2 = getenv("GAMMA_HIP_FLAT_FIRST_LOG2") ? atoi(getenv("GAMMA_HIP_FLAT_FIRST_LOG2")) : 0;
-    const int fl2 = (first_log2 >= 8 && first_log2 <= 16 && mfma_filter) ? first_log2 : (mfma_filter ? (d > 128 ? 10 : 14) : 16);
+    const int fl2 = mfma_filter ? (d > 128 ? 10 : 14) : 16;
     int64_t rows_chunk = std::max<int64_t>(256, std::min<int64_t>(N, (int64_t)1 << fl2));
     rows_chunk = (rows_chunk + 255) / 256 * 256;
     int qc = (int)std::max<int64_t>(1, std::min<int64_t>(nq, (int64_t)(h->dist_budget_bytes / (rows_chunk * sizeof(float)))));
@@ -1637,7 +1576,7 @@ int flat_search_device_locked(H* h, const gamma_hip_search_params* p, int nq, co
     // lets ~k ln(1 + g) new candidates per query through; fewer, larger passes pay fewer fixed launches (bounds, filter
     // ramp, exact, compact: ~100 us each at C2)
     // (C2, ms per call at growth 2 / 3 / 4 / 6: 2.26 / 2.19 / 2.15 / 2.24)
-    static const int flat_growth = getenv("GAMMA_HIP_FLAT_GROWTH") ? std::max(2, atoi(getenv("GAMMA_HIP_FLAT_GROWTH"))) : 4;
+    constexpr int flat_growth = 4;
     auto pass_rows = [&](int64_t r) { return std::min<int64_t>((int64_t)(flat_growth - 1) * r, N - r); };
     for (int64_t r = rows_chunk; r < N; r += pass_rows(r)) log_nsl++;
     auto bounded = [&](int q0, int nc, bool* redo) -> int {

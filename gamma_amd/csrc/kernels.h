@@ -162,8 +162,6 @@ void launch_bound_export(hipStream_t s, bool l2, const unsigned long long* ready
 void launch_bound_import(hipStream_t s, bool l2, const float* in, int nq, unsigned long long* ready);
 void launch_fill_f32(hipStream_t s, float* p, int n, float v);
 void launch_bound_combine(hipStream_t s, float* acc, const float* in, int n, int take_max);
-void launch_pq_ip_table_rows(hipStream_t s, const float* x, int d, int M, const float* pqc, float* out, const int* rq_list,
-                             const int* rq_count);
 // inner-product scan: dis0[q][p] = <x_q, centroid of probe p> (fvec_inner_product order); the scan takes it
 // through its coarse_dis argument
 void launch_pair_ip(hipStream_t s, const float* x, const float* cc, const int* probe_list, int nq, int P, int d,
@@ -184,14 +182,8 @@ struct ScanBound {
                                 // sum_m T2[list][m][code[m]]; per list sum_m max_c |T2[l][m][c]|.  nullptr: regular loop
     const float* t2max;
     int cf_span;                // filter pass: probes per consumer group behind the producer's G (0: one consumer takes them all)
-    int spins;                  // sleeps a consumer waits for its producer's bound before it goes on without one (0: 2048)
     unsigned long long* timeouts;   // consumers that gave up waiting (diagnostics; may be nullptr)
     int slice_cap;              // items a slice holds: scan_slice_cap(K)
-    int prod_cf;                // != 0 (filter-pass launches only): the PRODUCER scores its probes with the query's table + the per-code
-                                // sums too -- no per-list table -- bounds from those values plus their error margin, and gives only its
-                                // candidates the exact arithmetic.  Its slab segment then holds APPROXIMATE values: the callers re-score
-                                // group 0 (repair launch) for every query whose slab is read (unfiltered selection, tie replay)
-    int batch;                  // queries per XCD by which the producers run ahead of the consumers (0: 64)
     int part;                   // two-phase shard search: 1 = only the producers of this launch work (the consumers leave at once),
                                 // 2 = only the consumers (the bounds are in `ready` already: imported after the reduction across shards)
     int dbg_part;               // timing experiments only (GAMMA_HIP_SCAN_PART): 1 = consumers leave at once, 2 = producers do
@@ -200,12 +192,6 @@ struct ScanBound {
     const int64_t* pair_base;   // filter pass: [nq][P] arena offset of the pair's list (k_pair_offsets) -- with pair_off the pass needs no
                                 // look-up through the list id in front of a list
     float t2max_all;            // filter pass: max over t2max (the margin's bound S without a look-up per list)
-    int prod_c8;                // != 0 (with c8, M = 16, one group per launch, two slices per query): ONE workgroup per query -- the bound from
-                                // byte-image estimates of the first probe group (their recall_num-th smallest + the image's proven error
-                                // width), then the filter pass over ALL probes in the same workgroup (scan.hip, "one workgroup per query").
-                                // The first group's slab segment is NOT written: the callers score group 0 (repair launch) for every
-                                // query whose slab is read (unfiltered selection, tie replay), as with prod_cf; slice 0 holds the
-                                // survivors of every probe (TieReplayArgs::slice0_all)
 };
 // ---- q8scan.hip: the consumer probes of a bounded L2 scan, list-major over byte tables (one list x 8 queries per tile) ----
 struct Q8Args {
@@ -214,7 +200,6 @@ struct Q8Args {
     const int* probe_list;            // [nq][P]
     const float* coarse_dis;          // [nq][P] dis0
     const float* st2;                 // [nq][M][256] fp32 inner-product tables (k_pq_ip_table)
-    const float* fx = nullptr;        // != nullptr: no st2 -- the tables are computed from the queries [nq][d] and the codebook
     const float* pqc = nullptr;
     int d = 0;
     const float* xd = nullptr;        // != nullptr (with pqc, d): k_q8_exact computes the table entries of a query's candidates on
@@ -246,7 +231,6 @@ int q8_cand_cap(int nq);
 size_t q8_int_words(int nq, int P, int G, int nlist);
 void launch_q8_consumers(hipStream_t s, const Q8Args& a);
 int scan_slice_cap(int K);   // 1024 up to recall_num 256, 2048 up to 1024
-void launch_rq_nobound(hipStream_t s, const unsigned long long* ready, int nq, int* rq_list, int* rq_count);
 // true when launch_ivfpq_scan_pair would run the filter pass (CF) for a bounded scan with these arguments; the caller
 // then launches TWO groups per query -- the producer's G probes and one consumer group with all the others
 bool scan_cf_applies(bool l2, int M, int P, int G, bool have_sums, bool store_all);
@@ -403,8 +387,6 @@ struct TieReplayArgs {
                                   // of heap_replace_top (the IVFPQ scanner)
     int fixed_n = 0;              // pair_off == nullptr (flat): every row has fixed_n entries, a position IS the vector id
     int compact_rows = 0;         // slab row i belongs to the i-th flagged query (list[i]) instead of query i
-    int slice0_all = 0;           // slice 0 holds the survivors of EVERY probe (ScanBound::prod_c8): the slices are walked from slice 0 on and
-                                  // entries of the first group (in the slab part already) are skipped
     int always_sliced = 0;        // ready == nullptr: every query is first G slab entries + slices 1.. (flat search with the
                                   // running bound: first row chunk + the candidates each later pass emitted)
 };

@@ -56,24 +56,20 @@ template <int MT> struct Q8Pool { static constexpr int N = MT <= 16 ? 640 : 3584
 constexpr int Q8_POS_BITS = 25;  // candidate = position in the query's segment | probe << 25
 }  // namespace
 
-// candidates a query's list holds (beyond: the query takes the unfiltered path): GAMMA_HIP_Q8_CAND_MB (default 512) MB of
-// workspace spread over the batch, 768 .. 32768 entries per query
+// candidates a query's list holds (beyond: the query takes the unfiltered path): Q8_CAND_MB of workspace spread over the
+// batch, 768 .. 32768 entries per query
+constexpr int64_t Q8_CAND_MB = 512;
 int q8_cand_cap(int nq) {
-    static const int64_t mb = getenv("GAMMA_HIP_Q8_CAND_MB") ? atoll(getenv("GAMMA_HIP_Q8_CAND_MB")) : 512;
-    return (int)std::max<int64_t>(768, std::min<int64_t>(32768, ((mb << 20) / 4) / std::max(1, nq)));
+    return (int)std::max<int64_t>(768, std::min<int64_t>(32768, ((Q8_CAND_MB << 20) / 4) / std::max(1, nq)));
 }
 
 // ------------------------------------------------------------------------------------
 // u8 image of every query's inner-product table (k_pq_ip_table's st2): one workgroup per query, thread = code word c.
 // meta[q] = { cq = 2 sum_m lo_m + 1.02 M delta,  -2 delta,  max |entry|,  0 }
 // ------------------------------------------------------------------------------------
-// fx != nullptr (two-phase list shards, round 6): the table is not in memory -- a shard sees W times the queries of a rank, and
-// W x 32 KB per query written by k_pq_ip_table and read back here and by k_q8_exact was a tenth of its step -- the entries are
-// computed here from the query and the PQ codebook (128 KB, L2-resident), the arithmetic of k_pq_ip_table: identical values.
 template <int MT>
 __global__ __launch_bounds__(256) void k_q8_quant(const float* __restrict__ st2, uint8_t* __restrict__ q8,
-                                                  float4* __restrict__ meta, const float* __restrict__ fx,
-                                                  const float* __restrict__ pqc, int d) {
+                                                  float4* __restrict__ meta) {
     // wave w takes table rows w, w + 4, ..: a row is one 1 KB read of the wave (four code words per lane), its minimum and
     // maximum one wave reduction, its bytes one 256-byte store
     constexpr int NR = MT / 4;
@@ -81,22 +77,8 @@ __global__ __launch_bounds__(256) void k_q8_quant(const float* __restrict__ st2,
     const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     float4 v[NR];
     float lo[NR], range = 0.f, L = 0.f, amax = 0.f;
-    if (fx) {   // (uniform)
-        const int dsub = d / MT;
-        const float* xq = fx + (int64_t)q * d;
 #pragma unroll
-        for (int k = 0; k < NR; k++) {
-            const int m = wv + 4 * k;
-            const float* c = pqc + ((int64_t)m * 256 + 4 * lane) * dsub;
-            v[k].x = fvec_ny_row<false>(xq + m * dsub, c, dsub);
-            v[k].y = fvec_ny_row<false>(xq + m * dsub, c + dsub, dsub);
-            v[k].z = fvec_ny_row<false>(xq + m * dsub, c + 2 * dsub, dsub);
-            v[k].w = fvec_ny_row<false>(xq + m * dsub, c + 3 * dsub, dsub);
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < NR; k++) v[k] = *reinterpret_cast<const float4*>(st2 + ((int64_t)q * MT + wv + 4 * k) * 256 + 4 * lane);
-    }
+    for (int k = 0; k < NR; k++) v[k] = *reinterpret_cast<const float4*>(st2 + ((int64_t)q * MT + wv + 4 * k) * 256 + 4 * lane);
 #pragma unroll
     for (int k = 0; k < NR; k++) {
         float mn = fminf(fminf(v[k].x, v[k].y), fminf(v[k].z, v[k].w)), mx = fmaxf(fmaxf(v[k].x, v[k].y), fmaxf(v[k].z, v[k].w));
@@ -105,6 +87,9 @@ __global__ __launch_bounds__(256) void k_q8_quant(const float* __restrict__ st2,
             mn = fminf(mn, __shfl_xor(mn, o, 64));
             mx = fmaxf(mx, __shfl_xor(mx, o, 64));
         }
+        // (every lane holds the row's minimum and maximum now: kept in scalar registers, the rows themselves fill the vector ones)
+        mn = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(mn)));
+        mx = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(mx)));
         lo[k] = mn;
         range = fmaxf(range, mx - mn);
         L += mn;
@@ -703,7 +688,7 @@ __global__ __launch_bounds__(256) void k_q8_exact(const float* __restrict__ st2,
                                                   const int* __restrict__ pair_off, const unsigned long long* __restrict__ ready,
                                                   const uint32_t* __restrict__ cand, const int* __restrict__ ccnt, int cand_cap,
                                                   unsigned long long* __restrict__ surv, int* __restrict__ gcnt, int cnt_stride,
-                                                  int slice_cap, const float* __restrict__ fx, const float* __restrict__ pqc, int d,
+                                                  int slice_cap, const float* __restrict__ pqc, int d,
                                                   const float* __restrict__ xd) {
     __shared__ float s_lut[MT * 256];
     __shared__ int s_cnt[64];   // survivors per probe group (slice pg holds the positions of probe group pg: the order the tie
@@ -725,16 +710,11 @@ __global__ __launch_bounds__(256) void k_q8_exact(const float* __restrict__ st2,
     // candidate are computed ON DEMAND from the query and the codebook -- n x M x dsub floats from the L2-resident codebook
     // instead of the query's whole 4 M KB table from HBM (k_pq_ip_table's arithmetic: the identical value)
     const bool demand = xd != nullptr && n > 0 && n <= Q8_DEMAND_MAX;
-    const bool fused = !demand && n > 0 && fx != nullptr;
     const int dsub = d > 0 ? d / MT : 1;
-    if (fused) {   // (opt-in: the query's whole table computed here, k_q8_quant's note)
-        const float* xq = fx + (int64_t)q * d;
-#pragma unroll 4
-        for (int i = 0; i < MT; i++) s_lut[i * 256 + tid] = fvec_ny_row<false>(xq + i * dsub, pqc + ((int64_t)i * 256 + tid) * dsub, dsub);
-    } else if (n > 0 && !demand)
+    if (n > 0 && !demand)
         for (int e = tid; e < MT * 256; e += 256) s_lut[e] = st2[(int64_t)q * MT * 256 + e];
     __syncthreads();
-    const float* xq = (demand ? xd : fx) ? (demand ? xd : fx) + (int64_t)q * d : nullptr;
+    const float* xq = demand ? xd + (int64_t)q * d : nullptr;
     const float tau_f = key2f((uint32_t)word);
     for (int c = tid; c < n; c += 256) {
         const uint32_t cd = cand[(int64_t)q * cand_cap + c];
@@ -801,8 +781,8 @@ void launch_q8_consumers(hipStream_t s, const Q8Args& a) {
     // (records are stored per tile, 8 slots each: the slots past a tile's pairs read q = -1)
     (void)hipMemsetAsync(recs, 0xff, (size_t)(pairs / Q8_T + nlist + 1) * Q8_T * sizeof(Q8Rec), s);
     const int cap = q8_cand_cap(nq);
-    if (M == 16) hipLaunchKernelGGL((k_q8_quant<16>), dim3(nq), dim3(256), 0, s, a.st2, a.q8, a.meta, a.fx, a.pqc, a.d);
-    else hipLaunchKernelGGL((k_q8_quant<32>), dim3(nq), dim3(256), 0, s, a.st2, a.q8, a.meta, a.fx, a.pqc, a.d);
+    if (M == 16) hipLaunchKernelGGL((k_q8_quant<16>), dim3(nq), dim3(256), 0, s, a.st2, a.q8, a.meta);
+    else hipLaunchKernelGGL((k_q8_quant<32>), dim3(nq), dim3(256), 0, s, a.st2, a.q8, a.meta);
     const size_t hl = (size_t)nlist * sizeof(int);
     hipLaunchKernelGGL((k_q8_hist<false>), dim3(Q8_NW), dim3(1024), hl, s, a.probe_list, nq, P, G, a.ready, a.list_len, a.list_mask,
                        nlist, hist, (Q8Rec*)nullptr, a.rq_list, a.rq_count, a.coarse_dis, a.t2max, a.meta, a.pair_off, off, tile_first);
@@ -812,14 +792,13 @@ void launch_q8_consumers(hipStream_t s, const Q8Args& a) {
     hipLaunchKernelGGL((k_q8_hist<true>), dim3(Q8_NW), dim3(1024), hl, s, a.probe_list, nq, P, G, a.ready, a.list_len, a.list_mask,
                        nlist, hist, recs, a.rq_list, a.rq_count, a.coarse_dis, a.t2max, a.meta, a.pair_off, off, tile_first);
     // short lists: the pipelined kernel (a tile is a step or two per wave: everything is latency); long lists: the plain loop
-    static const double sl_len = getenv("GAMMA_HIP_Q8_SL_LEN") ? atof(getenv("GAMMA_HIP_Q8_SL_LEN")) : 1000.0;
-    const bool sl = a.mean_len < sl_len;
+    constexpr double Q8_SL_LEN = 1000.0;
+    const bool sl = a.mean_len < Q8_SL_LEN;
     const size_t lut_bytes = (size_t)M * (M <= 16 ? 288 : 256) * 8;
     const size_t lds = sl ? lut_bytes + 4 * Q8_T * sizeof(Q8Rec) + (9 * Q8_T + 8) * sizeof(int) + 3 * (size_t)Q8_SL_POOL * sizeof(uint32_t)
                           : lut_bytes + 11 * 8 * sizeof(int) + (size_t)(M <= 16 ? Q8Pool<16>::N : Q8Pool<32>::N) * sizeof(uint32_t);
     const int per_cu = std::max(1, std::min(8, (int)((160 * 1024) / (lds + 512))));
-    static const int grid_env = getenv("GAMMA_HIP_Q8_GRID") ? atoi(getenv("GAMMA_HIP_Q8_GRID")) : 0;
-    const unsigned grid = grid_env > 0 ? (unsigned)grid_env : (unsigned)(256 * per_cu);
+    const unsigned grid = (unsigned)(256 * per_cu);
     static std::atomic<uint64_t> attr{0};   // the attribute is per DEVICE (an in-process group launches this on every member's device)
     if (first_call_on_device(attr)) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_q8_filter<32, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 << 10);
@@ -840,12 +819,12 @@ void launch_q8_consumers(hipStream_t s, const Q8Args& a) {
         if (sl) GH_Q8F(k_q8_filter_sl, 16);
         else GH_Q8F(k_q8_filter, 16);
         hipLaunchKernelGGL((k_q8_exact<16>), dim3(nq), dim3(256), 0, s, a.st2, a.T2, nq, P, G, a.probe_list, a.coarse_dis, a.list_off,
-                           a.codes, a.pair_off, a.ready, a.cand, ccnt, cap, a.surv, a.gcnt, a.cnt_stride, a.slice_cap, a.fx, a.pqc, a.d, a.xd);
+                           a.codes, a.pair_off, a.ready, a.cand, ccnt, cap, a.surv, a.gcnt, a.cnt_stride, a.slice_cap, a.pqc, a.d, a.xd);
     } else {
         if (sl) GH_Q8F(k_q8_filter_sl, 32);
         else GH_Q8F(k_q8_filter, 32);
         hipLaunchKernelGGL((k_q8_exact<32>), dim3(nq), dim3(256), 0, s, a.st2, a.T2, nq, P, G, a.probe_list, a.coarse_dis, a.list_off,
-                           a.codes, a.pair_off, a.ready, a.cand, ccnt, cap, a.surv, a.gcnt, a.cnt_stride, a.slice_cap, a.fx, a.pqc, a.d, a.xd);
+                           a.codes, a.pair_off, a.ready, a.cand, ccnt, cap, a.surv, a.gcnt, a.cnt_stride, a.slice_cap, a.pqc, a.d, a.xd);
     }
 #undef GH_Q8F
 #undef GH_Q8F1

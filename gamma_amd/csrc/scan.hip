@@ -46,6 +46,7 @@ constexpr int SCAN_STAGE = 256;                  // survivors staged in LDS per 
 constexpr int SCAN_SLICE = 1024;                 // candidate slice of one workgroup (global) up to recall_num 256; a producer needs recall_num +
                                                  // one histogram bin: 2048 beyond (ScanBound::slice_cap, scan_slice_cap)
 constexpr int SCAN_BATCH = 64;                   // queries per XCD by which producers run ahead
+constexpr int SCAN_SPINS = 1 << 11;              // polls (s_sleep 16 each, ~2e6 cycles in all) a consumer waits for its query's bound
 
 // amdgpu_num_sgpr(96): 8 waves per SIMD need <= 96 SGPRs each (800 per SIMD); the FILT variant
 // would otherwise take 100 and lose one of the eight resident workgroups per CU
@@ -57,20 +58,12 @@ constexpr int SCAN_BATCH = 64;                   // queries per XCD by which pro
 // per-list table -- see "filter pass" in the body.
 constexpr int SCAN_CF_CAP = 768;   // filter-pass candidates staged per workgroup (8 bytes each)
 constexpr int C8_CAND = 1536;      // byte-table pass: its candidates sit in the 12 KB of the fp32 table's place that the bytes leave free (M = 16)
-// PCF (with CF): the producer runs on the filter pass's arithmetic too (ScanBound::prod_cf) -- a variant of its own: the extra
-// path costs the plain filter-pass kernel 16 VGPRs (73 -> 89: six -> five waves per SIMD) even when it is not taken
 // C8 (with CF): the filter pass gathers BYTES (ScanBound::c8; "byte table" in the body).
 // RES (L2 table mode 0, round 6): the index has NO precomputed table -- it would exceed faiss's precomputed_table_max_bytes
 // (faiss:IndexIVFPQ.cpp:441-449) -- and the reference scores every (query, list) pair with the distance table of the RESIDUAL:
 // r = x_q - centroid_l, lut[m][j] = fvec_L2sqr_ny(r_m, c_mj), dis0 = 0 (index/impl/gamma_index_ivfpq.h:239-245).  Here `st2`
 // points at the PQ codebook and `T2` is null; the residual sits in LDS behind the staging words.
-// PC8 (with C8, round 6): the producer scores its group on the byte image as well (ScanBound::prod_c8), see "producer on the byte image"
-constexpr int PC8_MAXN = 3072;     // codes of a producer's group whose lower estimates fit the 12 KB behind the byte image (M = 16)
-constexpr int PC8_MAXG = 8;        // lists of the estimate group
-// LDS byte offset of the residual image (M = 16): behind the table's place, the survivor stage, the 16 words, the list counter's 16 bytes
-// and the estimate group's lists -- the dynamic buffer is all of the kernel's LDS and starts at address 0 (see lut_gather)
-constexpr int PC8_IMG2_OFF = 16 * 1024 + SCAN_STAGE * 8 + 64 + 16 + PC8_MAXG * 24;
-template <bool L2, int MT, bool FILT, bool IPF, bool UNITS, bool CF, bool PCF, bool C8 = false, bool RES = false, bool PC8 = false>
+template <bool L2, int MT, bool FILT, bool IPF, bool UNITS, bool CF, bool C8 = false, bool RES = false>
 __device__ __forceinline__ void scan_pair_body(
 
         const float* __restrict__ x, int nq, int d, int M, int P, int G, const int* __restrict__ probe_list,
@@ -116,7 +109,7 @@ __device__ __forceinline__ void scan_pair_body(
         // its producer, by when the bound is normally there.  The query's table st2[q] is still in
         // this XCD's L2 when its consumers arrive.
         const int nq8 = (nq + 7) >> 3;
-        const int SB = sb.batch > 0 ? sb.batch : SCAN_BATCH;
+        constexpr int SB = SCAN_BATCH;
         if (slot < SB) {
             pg = 0;
             qslot = slot;
@@ -168,8 +161,8 @@ __device__ __forceinline__ void scan_pair_body(
     int& s_ncand = *(reinterpret_cast<int*>(s_stage + SCAN_STAGE) + 14);                       // CF: staged candidates
     uint2* s_cand = reinterpret_cast<uint2*>(reinterpret_cast<int*>(s_stage + SCAN_STAGE) + 16);  // CF: [SCAN_CF_CAP]
     float* s_res = reinterpret_cast<float*>(reinterpret_cast<int*>(s_stage + SCAN_STAGE) + 16);   // RES (never with CF): [d]
-    static_assert(!RES || (L2 && !CF && !IPF && !PCF && !C8), "residual tables: the plain L2 loop only");
-    static_assert(!PC8 || (C8 && MT == 16), "producer on the byte image: the M = 16 byte-image kernel");
+    static_assert(!RES || (L2 && !CF && !IPF && !C8), "residual tables: the plain L2 loop only");
+    static_assert(!C8 || MT == 16, "byte image: M = 16 only (its candidates sit in the 12 KB the bytes leave free)");
     int cbase = 0;     // unit mode: first code of the unit within its list
     int lut_q = -1;    // unit mode, inner product: the query whose table is in LDS
     int lut_pair = -1; // unit mode, L2: the (query, probe) pair whose table is in LDS
@@ -241,25 +234,13 @@ __device__ __forceinline__ void scan_pair_body(
     }
     const float* st2q = st2 + (int64_t)q * msz;
     float s2r[MT > 0 ? MT : 1];
-    // (uniform) this workgroup is a producer that takes the byte image: its group fits the estimates' place in LDS and holds
-    // at least recall_num codes
-    bool pc8 = false;
-    int g_est = 0;   // lists of the estimate group: the longest prefix of the first probe group whose codes fit the estimates' place
-    if constexpr (PC8) {
-        if (pg == 0 && sb.prod_c8) {
-            const int* po = pair_off + (int64_t)q * (P + 1);
-            pc8 = true;
-            for (int g = 1; g <= min(min(G, P), PC8_MAXG); g++)
-                if (po[g] <= PC8_MAXN) g_est = g;
-        }
-    }
     if (IPF && MT > 0) {
         // same arithmetic as k_pq_ip_table: one fvec_inner_products_ny row per (m, code word)
         const int dsub = d / M;
         const float* xq = x + (int64_t)q * d;
 #pragma unroll
         for (int i = 0; i < MT; i++) s2r[i] = fvec_ny_row<false>(xq + i * dsub, st2 + ((int64_t)i * 256 + tid) * dsub, dsub);
-    } else if (C8 && (pg > 0 || pc8)) {
+    } else if (C8 && pg > 0) {
         // byte table: wave w reads table rows w, w + 4, .. (four code words per lane), see below; s2r is loaded later
     } else if (RES) {
         // no query table: the per-list table comes from the residual and the codebook
@@ -269,7 +250,7 @@ __device__ __forceinline__ void scan_pair_body(
     }
     float4 v8[C8 ? MT / 4 : 1];
     if constexpr (C8) {
-        if (pg > 0 || pc8) {
+        if (pg > 0) {
 #pragma unroll
             for (int k = 0; k < MT / 4; k++)
                 v8[k] = *reinterpret_cast<const float4*>(st2q + ((tid >> 6) + 4 * k) * 256 + 4 * lane);
@@ -286,7 +267,7 @@ __device__ __forceinline__ void scan_pair_body(
         }
     }
     if constexpr (CF && !C8) {
-        if (pg > 0 || PCF) {   // (uniform) largest |entry| of the query's table: one word per wave, read behind the barrier below
+        if (pg > 0) {   // (uniform) largest |entry| of the query's table: one word per wave, read behind the barrier below
             float mxv = 0.f;
 #pragma unroll
             for (int i = 0; i < MT; i++) mxv = fmaxf(mxv, fabsf(s2r[i]));
@@ -306,9 +287,8 @@ __device__ __forceinline__ void scan_pair_body(
                 unsigned long long word;
                 // (bounded: dispatch order is not a contract -- if the producer has not published within ~2e6
                 //  cycles the group goes on without a bound and the query takes the unfiltered selection)
-                const int spin_max = sb.spins > 0 ? sb.spins : (1 << 11);
                 while ((word = __hip_atomic_load(&sb.ready[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == 0ull &&
-                       ++spins < spin_max)
+                       ++spins < SCAN_SPINS)
                     __builtin_amdgcn_s_sleep(16);
                 if (word != 0ull) {
                     s_tau = (word >> 32) == 1ull ? (uint32_t)word : 0xffffffffu;
@@ -328,8 +308,7 @@ __device__ __forceinline__ void scan_pair_body(
     }
     // the byte image of the query's table ("byte table" below), made by the whole workgroup from v8 where the fp32 table would be;
     // contains one barrier, none behind the image's stores
-    auto c8_image = [&](float& qmax, float& c8_cq, float& c8_nd, auto two_c) {
-        constexpr bool TWO = decltype(two_c)::value;   // + the image of the residuals (one workgroup per query, below)
+    auto c8_image = [&](float& qmax, float& c8_cq, float& c8_nd) {
         if constexpr (C8) {
         float lo[MT / 4], range = 0.f, Lsum = 0.f, amax = 0.f;
 #pragma unroll
@@ -357,244 +336,26 @@ __device__ __forceinline__ void scan_pair_body(
         const float delta = (range / 255.f) * 1.000001f;   // (hi - lo) / delta stays below 255.5 whatever the roundings
         const float inv = delta > 0.f ? 1.f / delta : 0.f;
         uint32_t* s_b8 = reinterpret_cast<uint32_t*>(s_lut);
-        const float delta2 = (delta / 255.f) * 1.000001f, inv2 = delta2 > 0.f ? 1.f / delta2 : 0.f;
 #pragma unroll
         for (int k = 0; k < MT / 4; k++) {
             const float f[4] = {v8[k].x, v8[k].y, v8[k].z, v8[k].w};
-            uint32_t w = 0, w2 = 0;
+            uint32_t w = 0;
 #pragma unroll
             for (int e = 0; e < 4; e++) {
                 int u = (int)rintf((f[e] - lo[k]) * inv);
                 u = min(255, max(0, u));
                 w |= (uint32_t)u << (8 * e);
-                if constexpr (TWO) {
-                    // ip = (lo - delta / 2) + delta u + delta2 u2 + e2,  |e2| <= 0.55 delta2 (the residual (ip - lo) - delta u lies in
-                    // [-delta / 2, delta / 2] up to roundings of 3 * 2^-24 of the row's range = 0.004 delta2)
-                    const float r = (f[e] - lo[k]) - delta * (float)u;
-                    int u2 = (int)rintf(__builtin_fmaf(0.5f, delta, r) * inv2);
-                    u2 = min(255, max(0, u2));
-                    w2 |= (uint32_t)u2 << (8 * e);
-                }
             }
             s_b8[((tid >> 6) + 4 * k) * 64 + lane] = w;
-            if constexpr (TWO) s_b8[PC8_IMG2_OFF / 4 + ((tid >> 6) + 4 * k) * 64 + lane] = w2;
         }
         qmax = amax;
         c8_cq = 2.f * Lsum + 1.02f * (float)MT * delta;
         c8_nd = -2.f * delta;
         }
     };
-    // ---- one workgroup per query (ScanBound::prod_c8, round 6): the bound from the BYTE IMAGE, then the filter pass over ALL probes ----
-    // The regular producer builds a 16 KB table per list (the T2 row through the L2, 4096 fma + LDS stores, two barriers) to score
-    // a few hundred codes: 43 % of the launch's workgroup time for 11 % of its codes, and a second workgroup per query that
-    // waits for it, reads the query's table again and makes the byte image again.  All the bound needs is an UPPER bound of the
-    // recall_num-th best exact value.  The image gives every code j of the first group the consumers' test value
-    //       f_j = (dis0 - 2 sum_m lo - 1.02 M delta) + s_j - 2 delta U_j,        f_j - eps <= v_j <= f_j + 2.0202 M delta + eps
-    // (the image's error bound |ip - lo - delta u8| <= 0.5001 delta per entry; eps = 50 * 2^-24 S, the roundings, as in the filter
-    // pass), so the recall_num-th smallest f plus W = 2.03 M delta + 2^-16 S_max bounds the recall_num-th smallest exact value of the
-    // group, hence the query's: estimates of the group in LDS (units of 64 codes dealt round-robin to the waves across all of its
-    // lists), 256-bin histogram, tau1 = edge + W published -- and the SAME workgroup goes on with the filter pass over every probe
-    // of the query, the first group included, against tau1: candidates f <= tau1 + margin get the reference's arithmetic, those with
-    // v <= tau1 are the query's survivors (slice 0; slice 1 stays empty).  No slab segment is written: the callers score group 0
-    // (repair launch) for every query whose slab is read (unfiltered selection, tie replay).
-    // A group that does not fit (more than PC8_MAXN codes, fewer than recall_num valid ones, more than PC8_MAXG lists) takes the
-    // regular producer, and the workgroup then runs the consumers' pass for the other probes as a second stage (slice 1).
-    bool fused = false;
-    float f_qmax = 0.f, f_cq = 0.f, f_nd = 0.f;
-    if constexpr (PC8) {
-        if (pc8) {   // (uniform)
-            float* s_f = s_lut + MT * 64;   // [n0 <= PC8_MAXN]: the estimates (the filter pass's candidates take the place afterwards)
-            uint32_t& s_smax = *(reinterpret_cast<uint32_t*>(s_cand) + 1);
-            // the estimate group's lists: (first code | codes | dis0 | position of the first code in the query's row), read once
-            int64_t* s_moff = reinterpret_cast<int64_t*>(s_cand + 2);             // [PC8_MAXG]
-            int* s_mlen = reinterpret_cast<int*>(s_moff + PC8_MAXG);               // [PC8_MAXG]
-            float* s_mdis = reinterpret_cast<float*>(s_mlen + PC8_MAXG);           // [PC8_MAXG]
-            int* s_mpos = reinterpret_cast<int*>(s_mdis + PC8_MAXG);               // [PC8_MAXG]
-            const int* poff = pair_off + (int64_t)q * (P + 1);
-            const int ng = g_est, n0 = poff[g_est];
-            if (tid < 64) {   // wave 0 (ng <= PC8_MAXG lanes of it)
-                float sl = 0.f;
-                if (tid < ng) {
-                    const int pair = q * P + tid;
-                    const int l = probe_list[pair];
-                    int len = 0;
-                    int64_t off = 0;
-                    float t2m = 0.f;
-                    if (l >= 0 && l < nlist && (!list_mask || list_mask[l])) {
-                        len = max(0, list_len[l]);
-                        off = list_off[l];
-                        t2m = sb.t2max[l];
-                    }
-                    const float dis0 = coarse_dis[pair];
-                    s_moff[tid] = off;
-                    s_mlen[tid] = len;
-                    s_mdis[tid] = dis0;
-                    s_mpos[tid] = poff[tid];
-                    if (len > 0) sl = fabsf(dis0) + t2m;
-                }
-                const uint32_t smx = wave_max_u32(__float_as_uint(sl));   // non-negative floats order as integers
-                if (tid == 0) s_smax = smx;
-            }
-            float qmax = 0.f, c8_cq = 0.f, c8_nd = 0.f;
-            c8_image(qmax, c8_cq, c8_nd, std::true_type{});
-            __syncthreads();   // the images and the lists' data are in place
-            GH_ST(t_pq);
-            GH_ST_CNT(0);
-            GH_ST_ADD(1, t_start, t_pq);
-            // ---- the estimates: units of 64 codes dealt round-robin to the four waves across ALL lists of the group, the next
-            // unit's codes and sums requested before the current unit's gathers.  Both images:
-            //     f2_j = dis0 + s_j - 2 (sum_m (lo_m - delta / 2) + delta U_j + delta2 U2_j) - 1.1 M delta2,
-            //     f2_j - eps <= v_j <= f2_j + 2.2 M delta2 + eps      (|e2| <= 0.55 delta2 per entry, eps: the roundings, <= 2^-16 S)
-            const float delta = -0.5f * c8_nd, delta2 = (delta / 255.f) * 1.000001f;
-            // c8_cq = 2 sum lo + 1.02 M delta  ->  2 sum (lo - delta / 2) + 1.1 M delta2
-            const float cq2 = (c8_cq - 2.02f * (float)MT * delta) + 1.1f * (float)MT * delta2;
-            const float nd2 = -2.f * delta2;
-            {
-                const int wv = tid >> 6;
-                int r = 0, ub = 0;   // cursor of the unit whose codes are being requested: list r, whose first unit is ub
-                int len = ng > 0 ? s_mlen[0] : 0, ns = (len + 63) >> 6;
-                uint4 cn[MT / 16];
-                float sn = 0.f;
-                // state of the requested unit
-                int n_len = 0, n_j0 = 0, n_pos = 0;
-                float n_dis = 0.f;
-                int64_t n_off = 0;
-                bool n_have = false;
-                auto request = [&](int u) {   // (uniform)
-                    while (r < ng && u >= ub + ns) {
-                        ub += ns;
-                        r++;
-                        len = r < ng ? s_mlen[r] : 0;
-                        ns = (len + 63) >> 6;
-                    }
-                    n_have = r < ng;
-                    if (n_have) {
-                        n_len = len;
-                        n_j0 = (u - ub) << 6;
-                        n_pos = s_mpos[r];
-                        n_dis = s_mdis[r];
-                        n_off = s_moff[r];
-                        const int jc = min(n_j0 + lane, n_len - 1);
-                        const uint4* cp = reinterpret_cast<const uint4*>(codes + (n_off + jc) * MT);
-#pragma unroll
-                        for (int u2 = 0; u2 < MT / 16; u2++) cn[u2] = cp[u2];
-                        sn = sb.sums[n_off + jc];
-                    }
-                };
-                int u = wv;
-                request(u);
-                while (n_have) {
-                    const int c_len = n_len, c_j0 = n_j0, c_pos = n_pos;
-                    const float c_dis = n_dis;
-                    uint32_t cw[MT / 4];
-#pragma unroll
-                    for (int u2 = 0; u2 < MT / 16; u2++) {
-                        cw[4 * u2] = cn[u2].x; cw[4 * u2 + 1] = cn[u2].y; cw[4 * u2 + 2] = cn[u2].z; cw[4 * u2 + 3] = cn[u2].w;
-                    }
-                    const float sj = sn;
-                    u += 4;
-                    request(u);
-                    const int j = c_j0 + lane;
-                    uint32_t t[MT], t2[MT];
-#pragma unroll
-                    for (int m = 0; m < MT; m++) t[m] = lut_gather_u8(cw[m >> 2], m & 3, m);
-#pragma unroll
-                    for (int m = 0; m < MT; m++) t2[m] = lut_gather_u8_at<PC8_IMG2_OFF>(cw[m >> 2], m & 3, m);
-                    __builtin_amdgcn_sched_barrier(0);   // all gathers in flight before the adds
-                    uint32_t u4[4] = {t[0], t[1], t[2], t[3]}, v4[4] = {t2[0], t2[1], t2[2], t2[3]};
-#pragma unroll
-                    for (int m = 4; m < MT; m++) {
-                        u4[m & 3] += t[m];
-                        v4[m & 3] += t2[m];
-                    }
-                    const uint32_t U = (u4[0] + u4[1]) + (u4[2] + u4[3]), U2 = (v4[0] + v4[1]) + (v4[2] + v4[3]);
-                    const float f = __builtin_fmaf(nd2, (float)U2, __builtin_fmaf(c8_nd, (float)U, (c_dis - cq2) + sj));
-                    if (j < c_len) {   // (no validity predicates on this path: every code counts)
-                        s_f[c_pos + j] = f;
-                        g_fmn = fminf(g_fmn, f);
-                        g_fmx = fmaxf(g_fmx, f);
-                    }
-                }
-            }
-            GH_ST(t_pl);
-            GH_ST_ADD(3, t_pq, t_pl);
-            // range of the estimates, then the upper edge of the 256-bin histogram's bin that holds the K-th smallest (the regular
-            // producer's procedure, on LDS)
-            int* hist = reinterpret_cast<int*>(s_stage);   // staging has not been used yet
-            uint32_t rmn = 0, rmx = 0;
-            {
-                const float fmn = g_fmn == 0.f ? -0.f : g_fmn, fmx = g_fmx == 0.f ? 0.f : g_fmx;
-                uint32_t mn = g_fmn <= g_fmx ? dis_key<true>(fmn) : 0xffffffffu;
-                uint32_t mx = g_fmn <= g_fmx ? dis_key<true>(fmx) : 0u;
-                mn = wave_min_u32(mn);
-                mx = wave_max_u32(mx);
-                if (lane == 0) {   // (s_red: last read in front of the image's barrier)
-                    s_red[tid >> 6] = mn;
-                    s_red[4 + (tid >> 6)] = mx;
-                }
-                hist[tid] = 0;
-                __syncthreads();   // ... and every wave's estimates are in LDS
-                rmn = min(min(s_red[0], s_red[1]), min(s_red[2], s_red[3]));
-                rmx = max(max(s_red[4], s_red[5]), max(s_red[6], s_red[7]));
-            }
-            GH_ST(t_p1);
-            GH_ST_ADD(16, t_pl, t_p1);
-            uint32_t tk = KEY_SENTINEL - 1u;
-            if (n0 >= sb.K) {   // (uniform)
-                const uint32_t range = rmx - rmn;
-                const int sh = range >= 256u ? (32 - __clz((int)range)) - 8 : 0;   // (range >> sh) < 256
-                for (int i = tid; i < n0; i += 256) atomicAdd(&hist[(dis_key<true>(s_f[i]) - rmn) >> sh], 1);
-                __syncthreads();
-                if (tid < 64) {   // wave 0: scan of the 256 bins, 4 per lane
-                    int c[4], c4 = 0;
-#pragma unroll
-                    for (int u = 0; u < 4; u++) {
-                        c[u] = hist[lane * 4 + u];
-                        c4 += c[u];
-                    }
-                    const int incl = wave_incl_scan(c4);
-                    int run = incl - c4;
-#pragma unroll
-                    for (int u = 0; u < 4; u++) {
-                        if (run < sb.K && sb.K <= run + c[u]) {
-                            unsigned long long edge = (unsigned long long)rmn + (((unsigned long long)(lane * 4 + u) + 1ull) << sh) - 1ull;
-                            if (edge > (unsigned long long)rmx) edge = rmx;
-                            s_tau = (uint32_t)edge;
-                        }
-                        run += c[u];
-                    }
-                }
-                __syncthreads();
-                const float sm = (__uint_as_float(s_smax) + 32.f * qmax) * (1.f / 65536.f);
-                float tau1 = key2f(s_tau) + (2.21f * (float)MT * delta2 + sm);
-                tau1 += fabsf(tau1) * 2.4e-7f;   // the sums' own roundings
-                tk = min(dis_key<true>(tau1), KEY_SENTINEL - 1u);
-                fused = true;
-            }
-            GH_ST(t_pp);
-            GH_ST_ADD(4, t_pl, t_pp);
-            if (tid == 0) {
-                __hip_atomic_store(&sb.ready[q], (1ull << 32) | tk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                sb.gcnt[(int64_t)q * sb.cnt_stride + 1] = 0;   // (slice 1: unused)
-                // a query whose nearest list alone is longer than the estimates' place, or whose first group holds fewer than
-                // recall_num codes: to the unfiltered selection, via an "overflowed" slice (the repair launch scores all its groups)
-                if (!fused) s_nstage = sb.slice_cap + 1;
-            }
-            if (!fused) {
-                flush();
-                return;
-            }
-            tauq = tk;
-            tau_f = key2f(tk);
-            bound_on = true;
-            f_qmax = qmax;
-            f_cq = c8_cq;
-            f_nd = c8_nd;
-        }
-    }
     GH_ST(t_bound);
     if constexpr (CF) {
-        if ((pg > 0 && bound_on) || fused) {   // (uniform)
+        if (pg > 0 && bound_on) {   // (uniform)
             GH_ST_CNT(8);
             GH_ST_ADD(9, t_start, t_bound);
             // ---- filter pass (L2 consumers with a bound) ----------------------------------------------------------
@@ -610,11 +371,8 @@ __device__ __forceinline__ void scan_pair_body(
             // (about as many as end up in the slice) get the EXACT value afterwards -- table entries fetched from
             // the L2-resident T2 row, fma and adds in the reference's order -- and the slice receives what the
             // regular loop would have put there: same keys, same positions.
-            float qmax = f_qmax, c8_cq = f_cq, c8_nd = f_nd;
-            // (one workgroup per query: the image is in place, the pass covers every probe)
-            const int pb = fused ? 0 : p_begin, pe = fused ? P : p_end;
-            if (fused) {
-            } else if constexpr (C8) {
+            float qmax = 0.f, c8_cq = 0.f, c8_nd = 0.f;
+            if constexpr (C8) {
                 // ---- byte table (round 5) --------------------------------------------------------------------------
                 // 64 lanes gathering random fp32 entries of one 256-entry row hit the 32 banks ~3.5 deep (a half wave's 32
                 // requests over 32 banks, 8 entries per bank): 57 % of this kernel's LDS cycles were conflicts.  A row of
@@ -625,7 +383,7 @@ __device__ __forceinline__ void scan_pair_body(
                 // a code is a candidate iff (A + s_j) - 2 delta U <= tau + 2^-16 S.  The image is made HERE (the arithmetic
                 // of k_q8_quant: wave w owns rows w, w + 4, ..; minimum and maximum of a row are one wave reduction) and
                 // lives where the fp32 table will be written for the exact recompute of the candidates.
-                c8_image(qmax, c8_cq, c8_nd, std::false_type{});
+                c8_image(qmax, c8_cq, c8_nd);
             } else {
                 lut_store_begin(lut_m0);
                 lut_store_rows<MT>([&](int i) { return s2r[i]; }, std::make_integer_sequence<int, (MT > 0 ? MT : 1)>{});
@@ -641,7 +399,7 @@ __device__ __forceinline__ void scan_pair_body(
             __syncthreads();   // the LUT and the list counter are in place
             GH_ST(t_quant);
             GH_ST_ADD(10, t_bound, t_quant);
-            const int ng = pe - pb;
+            const int ng = p_end - p_begin;
             // (two copies of the loop, with and without the validity predicates: with their loads -- through generic pointers of
             //  the filter table -- anywhere in the loop body, the compiler's wait-count pass puts `s_waitcnt vmcnt(0)` in front of the
             //  gathers at the join behind them, i.e. every step waited for the NEXT step's codes it had just requested)
@@ -658,7 +416,7 @@ __device__ __forceinline__ void scan_pair_body(
             float mv_dis[NSET];
 #pragma unroll
             for (int t = 0; t < NSET; t++) {
-                const int rr = t * 64 + lane, p = pb + min(rr, ng - 1);
+                const int rr = t * 64 + lane, p = p_begin + min(rr, ng - 1);
                 const int* po = pair_off + (int64_t)q * (P + 1) + p;
                 const int o0 = po[0], o1 = po[1];
                 const int64_t bo = sb.pair_base[(int64_t)q * P + p];
@@ -696,7 +454,7 @@ __device__ __forceinline__ void scan_pair_body(
             if (r_cur < ng) request_first(r_cur);
             const float S_q = sb.t2max_all + 32.f * qmax;
             while (r_cur < ng) {
-                const int p = pb + r_cur, len = rl(mv_len, r_cur), pbase = rl(mv_pos, r_cur);
+                const int p = p_begin + r_cur, len = rl(mv_len, r_cur), pbase = rl(mv_pos, r_cur);
                 const int64_t off = (int64_t)(((uint64_t)(uint32_t)rl(mv_ohi, r_cur) << 32) | (uint32_t)rl(mv_olo, r_cur));
                 float dis0;
                 if constexpr (NSET == 1) dis0 = __builtin_amdgcn_readlane(mv_dis[0], r_cur);
@@ -843,110 +601,15 @@ __device__ __forceinline__ void scan_pair_body(
         }
     }
     if constexpr (C8) {
-        if (pg > 0 || pc8) {   // (uniform) a consumer without a bound / a producer that left the byte image: the regular loop, its table
-                               // entries the regular way
+        if (pg > 0) {   // (uniform) a consumer without a bound: the regular loop, its table entries the regular way
 #pragma unroll
             for (int i = 0; i < MT; i++) s2r[i] = st2q[tid + 256 * i];
-        }
-    }
-    // ---- producer with the filter pass's arithmetic (sb.prod_cf, round 5) ---------------------------------------------------
-    // The producer was the expensive quarter of the launch: a per-list table (16 KB of T2 through the L2, 4096 fma + LDS stores,
-    // two barriers) for lists of a few hundred codes -- 1635 cycles per (query, list) pair against 675 for a consumer pair.
-    // It needs exact values for nothing but its own ~K + one-bin candidates: the bound only has to be an UPPER bound of the
-    // K-th best.  With f_j = (dis0 + s_j) - 2 sum_m ip[c_m] (the consumers' test value, |f_j - v_j| <= 50 * 2^-24 S) the K-th
-    // smallest f plus the margin 2^-17 S_max bounds the K-th smallest exact value, so: score the group with the query's table
-    // alone, histogram the f's, publish tau' = edge + margin, recompute exactly the codes with f <= tau' + margin and keep
-    // those with v <= tau'.  The slab segment of group 0 holds the f's, NOT the reference's values (see ScanBound::prod_cf).
-    float prod_smax = 0.f;
-    bool prod_done = false;
-    if constexpr (CF && PCF) {
-        if (pg == 0) {   // (uniform)
-            prod_done = true;
-            lut_store_begin(lut_m0);
-            lut_store_rows<MT>([&](int i) { return s2r[i]; }, std::make_integer_sequence<int, (MT > 0 ? MT : 1)>{});
-            lut_store_done();
-            int& s_next = *reinterpret_cast<int*>(s_cand + SCAN_CF_CAP);
-            uint32_t& s_smax = *(reinterpret_cast<uint32_t*>(s_cand + SCAN_CF_CAP) + 1);
-            if (tid == 0) {
-                s_next = 0;
-                s_smax = 0u;
-            }
-            __syncthreads();   // the LUT, the list counter and the per-wave maxima are in place
-            const float qmax = __uint_as_float(max(max(s_red[0], s_red[1]), max(s_red[2], s_red[3])));
-            const int ng = p_end - p_begin;
-            for (;;) {
-                int r = 0;
-                if (lane == 0) r = atomicAdd(&s_next, 1);
-                r = __builtin_amdgcn_readfirstlane(r);
-                if (r >= ng) break;
-                const int p = p_begin + r, pair = q * P + p;
-                const int l = probe_list[pair];
-                if (l < 0 || l >= nlist) continue;            // uniform per wave
-                if (list_mask && !list_mask[l]) continue;
-                const int len = list_len[l];
-                if (len <= 0) continue;
-                const int64_t off = list_off[l];
-                const uint8_t* lc = codes + off * MT;
-                const float* ls = sb.sums + off;
-                const int64_t* lid = ids + off;
-                const float dis0 = coarse_dis[pair];
-                float* o = out + (int64_t)q * q_stride + pair_off[(int64_t)q * (P + 1) + p];
-                prod_smax = fmaxf(prod_smax, fabsf(dis0) + sb.t2max[l] + 32.f * qmax);
-                uint4 cn[MT / 16];
-                float sn;
-                {
-                    const int jc = min(lane, len - 1);
-                    const uint4* cp = reinterpret_cast<const uint4*>(lc + (int64_t)jc * MT);
-#pragma unroll
-                    for (int u = 0; u < MT / 16; u++) cn[u] = cp[u];
-                    sn = ls[jc];
-                }
-                for (int j0 = 0; j0 < len; j0 += 64) {
-                    const int j = j0 + lane;
-                    uint32_t cw[MT / 4];
-#pragma unroll
-                    for (int u = 0; u < MT / 16; u++) {
-                        cw[4 * u] = cn[u].x; cw[4 * u + 1] = cn[u].y; cw[4 * u + 2] = cn[u].z; cw[4 * u + 3] = cn[u].w;
-                    }
-                    const float sj = sn;
-                    if (j0 + 64 < len) {   // (uniform)
-                        const int jc = min(j + 64, len - 1);
-                        const uint4* cp = reinterpret_cast<const uint4*>(lc + (int64_t)jc * MT);
-#pragma unroll
-                        for (int u = 0; u < MT / 16; u++) cn[u] = cp[u];
-                        sn = ls[jc];
-                    }
-                    bool ok = j < len;
-                    if (need_ids && ok) {
-                        const int64_t id = lid[j];
-                        ok = id >= 0;
-                        if (ok) ok = is_valid_doc(filt, id);
-                    }
-                    float t[MT];
-#pragma unroll
-                    for (int m = 0; m < MT; m++) t[m] = lut_gather(cw[m >> 2], m & 3, m);
-                    __builtin_amdgcn_sched_barrier(0);
-                    float g4[4] = {t[0], t[1], t[2], t[3]};
-#pragma unroll
-                    for (int m = 4; m < MT; m++) g4[m & 3] += t[m];
-                    const float g = (g4[0] + g4[1]) + (g4[2] + g4[3]);
-                    const float f = __builtin_fmaf(-2.f, g, dis0 + sj);
-                    if (j < len) {
-                        const float val = ok ? f : sentinel;
-                        o[j] = val;
-                        g_fmn = fminf(g_fmn, ok ? val : INFINITY);
-                        g_fmx = fmaxf(g_fmx, ok ? val : -INFINITY);
-                        g_nv += ok ? 1 : 0;
-                    }
-                }
-            }
-            if (lane == 0) atomicMax(&s_smax, __float_as_uint(prod_smax));   // non-negative floats order as integers
         }
     }
     if (!L2) __syncthreads();   // the LUT (written once per query) is complete; L2 rebuilds it per list
     GH_ST(t_lists);
     if (FILT && pg == 0) { GH_ST_CNT(0); GH_ST_ADD(1, t_start, t_lists); }
-    for (int p = p_begin; p < (prod_done ? p_begin : p_end); p++) {
+    for (int p = p_begin; p < p_end; p++) {
         GH_ST(t_l0);
         const int pair = q * P + p;
         const int l = probe_list[pair];
@@ -1237,18 +900,6 @@ __device__ __forceinline__ void scan_pair_body(
             // list shard, each a latency-bound pass over its slab behind the chunk's scan.
             tau = KEY_SENTINEL - 1u;
         }
-        float prod_m = 0.f;
-        if constexpr (CF && PCF) {
-            if (prod_done && tau < KEY_SENTINEL) {   // (uniform) the bound of the EXACT values: the f's edge + their error margin
-                const uint32_t smax = *(reinterpret_cast<const uint32_t*>(s_cand + SCAN_CF_CAP) + 1);
-                prod_m = __uint_as_float(smax) * (1.f / 131072.f);
-                if (tau < KEY_SENTINEL - 1u) {
-                    float tp = key2f(tau) + prod_m;
-                    tp += fabsf(tp) * 1.2e-7f;   // the sum's own rounding
-                    tau = min(dis_key<L2>(tp), KEY_SENTINEL - 1u);
-                }
-            }
-        }
         if (threadIdx.x == 0)
             __hip_atomic_store(&sb.ready[q], tau < KEY_SENTINEL ? ((1ull << 32) | tau) : (2ull << 32),
                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1257,72 +908,7 @@ __device__ __forceinline__ void scan_pair_body(
         // the group's own candidates within the bound become its survivor slice (slice 0), like a
         // consumer's: k_select_final then reads a few hundred items per query and never the distance
         // buffer (one wave walking a long first group -- 24 k candidates at C4 -- was the slow part)
-        bool prod_exact = false;
-        if constexpr (CF && PCF) prod_exact = prod_done;
-        if (tau < KEY_SENTINEL && prod_exact) {   // uniform
-            if constexpr (CF && PCF) {
-                // candidates: f <= tau' + margin (every code whose exact value is within tau' is among them), then the exact
-                // value in the reference's order of operations -- the list's T2 row from the L2, the query's table in LDS
-                __syncthreads();        // the histogram (aliasing the staging area) has been read
-                const float taup = key2f(tau);
-                float thr = taup + prod_m;
-                thr += fabsf(thr) * 1.2e-7f;
-                for (int i0 = 0; i0 < n0; i0 += 256) {
-                    const int idx = i0 + (int)threadIdx.x;
-                    const float fv = o0[min(idx, n0 - 1)];
-                    const bool cand = idx < n0 && fv <= thr;   // (the sentinel is +inf)
-                    const unsigned long long bal = __ballot(cand);
-                    if (bal) {
-                        int base = 0;
-                        if (lane == 0) base = atomicAdd(&s_ncand, __popcll(bal));
-                        base = __builtin_amdgcn_readfirstlane(base);   // (lane 0 holds it: no LDS permute)
-                        const int slot = base + __popcll(bal & ((1ull << lane) - 1ull));
-                        if (cand && slot < SCAN_CF_CAP) s_cand[slot] = make_uint2((uint32_t)idx, 0u);
-                    }
-                }
-                __syncthreads();
-                const int nc = s_ncand;
-                if (nc > SCAN_CF_CAP) {   // (uniform) more candidates than the stage holds: the query takes the unfiltered path
-                    if (tid == 0) s_nstage = sb.slice_cap + 1;
-                } else {
-                    const int* poff = pair_off + (int64_t)q * (P + 1);
-                    for (int c0 = 0; c0 < nc; c0 += 256) {   // uniform trip count: append() ballots
-                        const int c = c0 + tid;
-                        bool keep = false;
-                        float dis = 0.f;
-                        int pos = 0;
-                        if (c < nc) {
-                            pos = (int)s_cand[c].x;
-                            int p = p_begin;
-                            for (int pp = p_begin + 1; pp < p_end; pp++) p = poff[pp] <= pos ? pp : p;   // last probe with off <= pos
-                            const int pair = q * P + p;
-                            const int l = probe_list[pair];
-                            const int j = pos - poff[p];
-                            const uint8_t* cj = codes + (list_off[l] + j) * MT;
-                            const float* t2 = T2 + (int64_t)l * msz;
-                            uint32_t cw[MT / 4];
-#pragma unroll
-                            for (int u = 0; u < MT / 16; u++) {
-                                const uint4 cv = reinterpret_cast<const uint4*>(cj)[u];
-                                cw[4 * u] = cv.x; cw[4 * u + 1] = cv.y; cw[4 * u + 2] = cv.z; cw[4 * u + 3] = cv.w;
-                            }
-                            dis = coarse_dis[pair];
-#pragma unroll
-                            for (int m0 = 0; m0 < MT; m0 += 8) {
-                                float a[8];
-#pragma unroll
-                                for (int m = 0; m < 8; m++) a[m] = t2[(m0 + m) * 256 + ((cw[(m0 + m) >> 2] >> (8 * (m & 3))) & 255u)];
-#pragma unroll
-                                for (int m = 0; m < 8; m++)
-                                    dis += __builtin_fmaf(-2.0f, s_lut[(m0 + m) * 256 + ((cw[(m0 + m) >> 2] >> (8 * (m & 3))) & 255u)], a[m]);
-                            }
-                            keep = dis <= taup;
-                        }
-                        append(keep, dis, pos);
-                    }
-                }
-            }
-        } else if (tau < KEY_SENTINEL) {   // uniform
+        if (tau < KEY_SENTINEL) {   // uniform
             __syncthreads();        // the histogram (aliasing the staging area) has been read
             for (int i0 = 0; i0 < n0; i0 += 256 * 8) {
                 float t[8];
@@ -1374,7 +960,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void k_iv
         float* __restrict__ out, const FilterDesc* __restrict__ ftab, const int* __restrict__ qfil, int need_ids,
         float sentinel, const int* __restrict__ qperm, int pg_lo, int pg_cnt, int sparse, ScanBound sb,
         const int* __restrict__ rq_list, const int* __restrict__ rq_count, int chunk_len) {
-    scan_pair_body<L2, MT, FILT, IPF, UNITS, CF, false>(x, nq, d, M, P, G, probe_list, coarse_dis, cc, st2, T2, list_off, list_len, list_mask, nlist, codes, ids, pair_off, q_stride, out, ftab, qfil, need_ids, sentinel, qperm, pg_lo, pg_cnt, sparse, sb, rq_list, rq_count, chunk_len);
+    scan_pair_body<L2, MT, FILT, IPF, UNITS, CF>(x, nq, d, M, P, G, probe_list, coarse_dis, cc, st2, T2, list_off, list_len, list_mask, nlist, codes, ids, pair_off, q_stride, out, ftab, qfil, need_ids, sentinel, qperm, pg_lo, pg_cnt, sparse, sb, rq_list, rq_count, chunk_len);
 }
 // L2 table mode 0: per-list tables from the residual (RES in the body)
 template <int MT, bool FILT, bool UNITS>
@@ -1389,23 +975,7 @@ __global__ __launch_bounds__(256) void k_ivfpq_scan_pair_res(
         float* __restrict__ out, const FilterDesc* __restrict__ ftab, const int* __restrict__ qfil, int need_ids,
         float sentinel, const int* __restrict__ qperm, int pg_lo, int pg_cnt, int sparse, ScanBound sb,
         const int* __restrict__ rq_list, const int* __restrict__ rq_count, int chunk_len) {
-    scan_pair_body<true, MT, FILT, false, UNITS, false, false, false, true>(x, nq, d, M, P, G, probe_list, coarse_dis, cc, pqc, T2, list_off, list_len, list_mask, nlist, codes, ids, pair_off, q_stride, out, ftab, qfil, need_ids, sentinel, qperm, pg_lo, pg_cnt, sparse, sb, rq_list, rq_count, chunk_len);
-}
-
-// filter pass + the producer on its arithmetic (ScanBound::prod_cf): held to six waves per SIMD like the plain filter-pass kernel
-template <int MT>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96), amdgpu_waves_per_eu(6, 8))) void k_ivfpq_scan_pair_pcf(
-
-        const float* __restrict__ x, int nq, int d, int M, int P, int G, const int* __restrict__ probe_list,
-        const float* __restrict__ coarse_dis, const float* __restrict__ cc,
-        const float* __restrict__ st2, const float* __restrict__ T2,
-        const int64_t* __restrict__ list_off, const int* __restrict__ list_len,
-        const uint8_t* __restrict__ list_mask, int nlist, const uint8_t* __restrict__ codes,
-        const int64_t* __restrict__ ids, const int* __restrict__ pair_off, int64_t q_stride,
-        float* __restrict__ out, const FilterDesc* __restrict__ ftab, const int* __restrict__ qfil, int need_ids,
-        float sentinel, const int* __restrict__ qperm, int pg_lo, int pg_cnt, int sparse, ScanBound sb,
-        const int* __restrict__ rq_list, const int* __restrict__ rq_count, int chunk_len) {
-    scan_pair_body<true, MT, true, false, false, true, true>(x, nq, d, M, P, G, probe_list, coarse_dis, cc, st2, T2, list_off, list_len, list_mask, nlist, codes, ids, pair_off, q_stride, out, ftab, qfil, need_ids, sentinel, qperm, pg_lo, pg_cnt, sparse, sb, rq_list, rq_count, chunk_len);
+    scan_pair_body<true, MT, FILT, false, UNITS, false, false, true>(x, nq, d, M, P, G, probe_list, coarse_dis, cc, pqc, T2, list_off, list_len, list_mask, nlist, codes, ids, pair_off, q_stride, out, ftab, qfil, need_ids, sentinel, qperm, pg_lo, pg_cnt, sparse, sb, rq_list, rq_count, chunk_len);
 }
 
 // filter pass on the byte table (ScanBound::c8)
@@ -1421,49 +991,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(112), amdgpu_wa
         float* __restrict__ out, const FilterDesc* __restrict__ ftab, const int* __restrict__ qfil, int need_ids,
         float sentinel, const int* __restrict__ qperm, int pg_lo, int pg_cnt, int sparse, ScanBound sb,
         const int* __restrict__ rq_list, const int* __restrict__ rq_count, int chunk_len) {
-    scan_pair_body<true, MT, true, false, false, true, false, true>(x, nq, d, M, P, G, probe_list, coarse_dis, cc, st2, T2, list_off, list_len, list_mask, nlist, codes, ids, pair_off, q_stride, out, ftab, qfil, need_ids, sentinel, qperm, pg_lo, pg_cnt, sparse, sb, rq_list, rq_count, chunk_len);
-}
-
-// ... with the producer on the byte image as well (ScanBound::prod_c8)
-template <int MT>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(112), amdgpu_waves_per_eu(7, 8))) void k_ivfpq_scan_pair_pc8(
-
-        const float* __restrict__ x, int nq, int d, int M, int P, int G, const int* __restrict__ probe_list,
-        const float* __restrict__ coarse_dis, const float* __restrict__ cc,
-        const float* __restrict__ st2, const float* __restrict__ T2,
-        const int64_t* __restrict__ list_off, const int* __restrict__ list_len,
-        const uint8_t* __restrict__ list_mask, int nlist, const uint8_t* __restrict__ codes,
-        const int64_t* __restrict__ ids, const int* __restrict__ pair_off, int64_t q_stride,
-        float* __restrict__ out, const FilterDesc* __restrict__ ftab, const int* __restrict__ qfil, int need_ids,
-        float sentinel, const int* __restrict__ qperm, int pg_lo, int pg_cnt, int sparse, ScanBound sb,
-        const int* __restrict__ rq_list, const int* __restrict__ rq_count, int chunk_len) {
-    scan_pair_body<true, MT, true, false, false, true, false, true, false, true>(x, nq, d, M, P, G, probe_list, coarse_dis, cc, st2, T2, list_off, list_len, list_mask, nlist, codes, ids, pair_off, q_stride, out, ftab, qfil, need_ids, sentinel, qperm, pg_lo, pg_cnt, sparse, sb, rq_list, rq_count, chunk_len);
-}
-
-// (M = 32: the 32 KB table leaves four workgroups per CU whatever the registers)
-__global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void k_ivfpq_scan_pair_c8m32(
-
-        const float* __restrict__ x, int nq, int d, int M, int P, int G, const int* __restrict__ probe_list,
-        const float* __restrict__ coarse_dis, const float* __restrict__ cc,
-        const float* __restrict__ st2, const float* __restrict__ T2,
-        const int64_t* __restrict__ list_off, const int* __restrict__ list_len,
-        const uint8_t* __restrict__ list_mask, int nlist, const uint8_t* __restrict__ codes,
-        const int64_t* __restrict__ ids, const int* __restrict__ pair_off, int64_t q_stride,
-        float* __restrict__ out, const FilterDesc* __restrict__ ftab, const int* __restrict__ qfil, int need_ids,
-        float sentinel, const int* __restrict__ qperm, int pg_lo, int pg_cnt, int sparse, ScanBound sb,
-        const int* __restrict__ rq_list, const int* __restrict__ rq_count, int chunk_len) {
-    scan_pair_body<true, 32, true, false, false, true, false, true>(x, nq, d, M, P, G, probe_list, coarse_dis, cc, st2, T2, list_off, list_len, list_mask, nlist, codes, ids, pair_off, q_stride, out, ftab, qfil, need_ids, sentinel, qperm, pg_lo, pg_cnt, sparse, sb, rq_list, rq_count, chunk_len);
-}
-
-// queries WITHOUT a bound join the repair list (ScanBound::prod_cf launches: their first group's slab segment holds the
-// producer's approximate values, and the unfiltered selection reads the slab)
-__global__ __launch_bounds__(256) void k_rq_nobound(const unsigned long long* __restrict__ ready, int nq, int* __restrict__ rq_list,
-                                                    int* __restrict__ rq_count) {
-    const int q = blockIdx.x * 256 + threadIdx.x;
-    if (q < nq && (ready[q] >> 32) != 1ull) rq_list[atomicAdd(rq_count, 1)] = q;
-}
-void launch_rq_nobound(hipStream_t s, const unsigned long long* ready, int nq, int* rq_list, int* rq_count) {
-    if (nq > 0) hipLaunchKernelGGL(k_rq_nobound, dim3((nq + 255) / 256), dim3(256), 0, s, ready, nq, rq_list, rq_count);
+    scan_pair_body<true, MT, true, false, false, true, true>(x, nq, d, M, P, G, probe_list, coarse_dis, cc, st2, T2, list_off, list_len, list_mask, nlist, codes, ids, pair_off, q_stride, out, ftab, qfil, need_ids, sentinel, qperm, pg_lo, pg_cnt, sparse, sb, rq_list, rq_count, chunk_len);
 }
 
 int scan_slice_cap(int K) { return K <= 256 ? SCAN_SLICE : 2 * SCAN_SLICE; }
@@ -1499,7 +1027,6 @@ void launch_ivfpq_scan_pair(hipStream_t s, bool l2, const float* x, int nq, int 
             (void)hipStreamSynchronize(s);
             (void)hipMemcpyFromSymbol(t, HIP_SYMBOL(g_scan_t), sizeof(t));
             const double np = (double)std::max<unsigned long long>(1, t[0]), nc = (double)std::max<unsigned long long>(1, t[8]);
-            fprintf(stderr, "pc8: range %.0f, hist1 %.0f, exact loop %.0f, candidates %.1f of %.1f\n", t[16] / np, t[17] / np, t[18] / np, t[19] / np, t[20] / np);
             fprintf(stderr, "scan phases, shader cycles per workgroup -- producers (%llu): start %.0f, lists total %.0f (of which table builds incl. "
                     "their waits %.0f), bound %.0f, own slice %.0f; consumers (%llu): to the bound %.0f, byte image %.0f, filter loop %.0f, exact + flush %.0f\n",
                     t[0], t[1] / np, t[3] / np, t[2] / np, t[4] / np, t[5] / np, t[8], t[9] / nc, t[10] / nc, t[11] / nc, t[12] / nc);
@@ -1530,7 +1057,7 @@ void launch_ivfpq_scan_pair(hipStream_t s, bool l2, const float* x, int nq, int 
     if (res) lds += (size_t)d * sizeof(float);   // the residual
     dim3 grid((unsigned)(8 * (int64_t)((nq + 7) / 8) * pg_cnt));
     if (bound) {   // P(0) | P(t+1) C(t) ...: whole batches, see the kernel
-        const int SB = bound->batch > 0 ? bound->batch : SCAN_BATCH;
+        constexpr int SB = SCAN_BATCH;
         const int64_t nq8 = (nq + 7) / 8, nb = (nq8 + SB - 1) / SB;
         grid.x = (unsigned)(8 * (SB + nb * SB * pg_cnt));
     }
@@ -1538,7 +1065,7 @@ void launch_ivfpq_scan_pair(hipStream_t s, bool l2, const float* x, int nq, int 
     sb.slice_cap = SCAN_SLICE;
     if (bound) sb = *bound;
     // filter pass for the consumers of a bounded L2 scan: needs the per-code sums (sb.sums) and survivor-only consumers
-    const bool cf = bound && l2 && !pqc_fused && (pg_cnt > 1 || (sb.prod_c8 && pg_cnt == 1 && P > G)) && sb.sums && sb.t2max &&
+    const bool cf = bound && l2 && !pqc_fused && pg_cnt > 1 && sb.sums && sb.t2max &&
                     !sb.store_all && (M == 16 || M == 32);
     if (rq_list) {   // repair launch: a fixed grid loops over the flagged (query, group) items
         if (bound || pqc_fused) {
@@ -1552,15 +1079,11 @@ void launch_ivfpq_scan_pair(hipStream_t s, bool l2, const float* x, int nq, int 
         grid.x = (unsigned)std::min<int64_t>(max_units, 256 * per_cu);
     }
     // the filter pass holds its group's lists one per lane (two registers for the fp32 pass, one for the byte image)
-    if (cf && (!sb.pair_base || (sb.cf_span > 0 ? sb.cf_span : (sb.prod_c8 ? P : P - G)) > (sb.c8 ? 64 : 128))) {
-        launch_refused("launch_ivfpq_scan_pair: the filter pass needs pair_base and at most 64 (byte image) / 128 lists per consumer group");
+    if (cf && (!sb.pair_base || (sb.cf_span > 0 ? sb.cf_span : P - G) > (sb.c8 ? 64 : 128) || (sb.c8 && M != 16))) {
+        launch_refused("launch_ivfpq_scan_pair: the filter pass needs pair_base and at most 64 (byte image, M = 16 only) / 128 lists per consumer group");
         return;
     }
-    if (sb.prod_c8 && !(cf && sb.c8 && M == 16 && pg_cnt == 1 && sb.cnt_stride >= 2 && sb.cf_span == 0)) {
-        launch_refused("launch_ivfpq_scan_pair: one workgroup per query (prod_c8) needs the M = 16 byte-image pass, one group per launch and two slices");
-        return;
-    }
-    if (cf) lds += (sb.c8 ? 0 : SCAN_CF_CAP * sizeof(uint2)) + 16 + (sb.prod_c8 ? PC8_MAXG * 24 + 4096 : 0);
+    if (cf) lds += (sb.c8 ? 0 : SCAN_CF_CAP * sizeof(uint2)) + 16;
 #define GH_SCAN(LL, MT, FF)                                                                       \
     GH_SCAN4(LL, MT, FF, false)
 #define GH_SCAN4(LL, MT, FF, II) GH_SCAN5(LL, MT, FF, II, false)
@@ -1629,15 +1152,8 @@ void launch_ivfpq_scan_pair(hipStream_t s, bool l2, const float* x, int nq, int 
                        probe_list, coarse_dis, cc, st2, T2, list_off, list_len, list_mask, nlist, codes, ids, pair_off,  \
                        q_stride, out, ftab, qfil, need_ids, INFINITY, qperm, pg_lo, pg_cnt, sparse, sb, rq_list,         \
                        rq_count, chunk_len)
-        if (sb.prod_cf) {
-            if (M == 16) GH_SCAN_CF(k_ivfpq_scan_pair_pcf<16>);
-            else GH_SCAN_CF(k_ivfpq_scan_pair_pcf<32>);
-        } else if (sb.prod_c8) {
-            GH_SCAN_CF(k_ivfpq_scan_pair_pc8<16>);
-        } else if (sb.c8 && M == 16) {
+        if (sb.c8) {
             GH_SCAN_CF(k_ivfpq_scan_pair_c8<16>);
-        } else if (sb.c8) {
-            GH_SCAN_CF(k_ivfpq_scan_pair_c8m32);
         } else {
             if (M == 16) GH_SCAN_CF((k_ivfpq_scan_pair<true, 16, true, false, false, true>));
             else GH_SCAN_CF((k_ivfpq_scan_pair<true, 32, true, false, false, true>));

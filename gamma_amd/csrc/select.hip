@@ -1776,6 +1776,8 @@ static void launch_sel(hipStream_t s, const float* vals, int64_t seg_stride, con
     hipLaunchKernelGGL((k_select2<SMALLEST, NPT>), dim3(nseg), dim3(256), lds, s, vals, seg_stride, \
                        seg_len, fixed_len, K, Kpad, out_vals, out_pos, only)
     static const bool no_wave = getenv("GAMMA_HIP_NO_WAVE_SELECT") != nullptr;
+    static const bool no_stream = getenv("GAMMA_HIP_NO_STREAM_SELECT") != nullptr;
+    static const bool no_stream_2k = getenv("GAMMA_HIP_NO_STREAM_SELECT_2K") != nullptr;
     if (K <= 64 && max_len <= 512 && !no_wave && !only)    // short rows (the coarse sample): 8 keys per lane
         hipLaunchKernelGGL((k_select_wave<SMALLEST, 8>), dim3((nseg + 3) / 4), dim3(256), 0, s, vals, seg_stride,
                            seg_len, fixed_len, nseg, K, out_vals, out_pos, nullptr);
@@ -1784,12 +1786,11 @@ static void launch_sel(hipStream_t s, const float* vals, int64_t seg_stride, con
                            seg_len, fixed_len, nseg, K, out_vals, out_pos, nullptr);
     else if (max_len <= 256 * 4) GH_SEL(4);
     else if (max_len <= 256 * 16) GH_SEL(16);
-    else if (K <= 1024 && (seg_stride & 3) == 0 && (reinterpret_cast<uintptr_t>(vals) & 15) == 0 &&
-             !getenv("GAMMA_HIP_NO_STREAM_SELECT"))
+    else if (K <= 1024 && (seg_stride & 3) == 0 && (reinterpret_cast<uintptr_t>(vals) & 15) == 0 && !no_stream)
         hipLaunchKernelGGL((k_select_stream<SMALLEST>), dim3(nseg), dim3(256), 0, s, vals, seg_stride,
                            seg_len, fixed_len, K, Kpad, out_vals, out_pos, only);
-    else if (K <= 2048 && (seg_stride & 3) == 0 && (reinterpret_cast<uintptr_t>(vals) & 15) == 0 &&
-             !getenv("GAMMA_HIP_NO_STREAM_SELECT") && !getenv("GAMMA_HIP_NO_STREAM_SELECT_2K"))
+    else if (K <= 2048 && (seg_stride & 3) == 0 && (reinterpret_cast<uintptr_t>(vals) & 15) == 0 && !no_stream &&
+             !no_stream_2k)
         hipLaunchKernelGGL((k_select_stream<SMALLEST, 4096>), dim3(nseg), dim3(256), 0, s, vals, seg_stride,
                            seg_len, fixed_len, K, Kpad, out_vals, out_pos, only);
     else GH_SEL(0);
@@ -2605,7 +2606,8 @@ void launch_small_tail(hipStream_t s, bool l2, const float* slab, int64_t q_stri
     }
     static unsigned long long* dbg = nullptr;
     static int shown = 0;
-    if (getenv("GAMMA_HIP_SM_DBG")) {
+    static const bool want_dbg = getenv("GAMMA_HIP_SM_DBG") != nullptr;
+    if (want_dbg) {
         if (!dbg) (void)hipMalloc((void**)&dbg, 64);
         if (shown++ % 10 == 9) {
             unsigned long long h[8];

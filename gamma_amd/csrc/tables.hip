@@ -350,21 +350,6 @@ void launch_bound_import(hipStream_t s, bool l2, const float* in, int nq, unsign
     if (l2) hipLaunchKernelGGL(k_bound_import<true>, dim3((nq + 255) / 256), dim3(256), 0, s, in, nq, ready);
     else hipLaunchKernelGGL(k_bound_import<false>, dim3((nq + 255) / 256), dim3(256), 0, s, in, nq, ready);
 }
-// st2 rows of the queries in a device list (the repair launch of a call whose tables were computed on the fly)
-__global__ __launch_bounds__(256) void k_pq_ip_table_rows(const float* __restrict__ x, int d, int M, const float* __restrict__ pqc,
-                                                          float* __restrict__ out, const int* __restrict__ rq_list,
-                                                          const int* __restrict__ rq_count) {
-    const int n = *rq_count, dsub = d / M, j = threadIdx.x;
-    for (int w = blockIdx.x; w < n; w += gridDim.x) {
-        const int q = rq_list[w];
-        for (int m = 0; m < M; m++)
-            out[((int64_t)q * M + m) * 256 + j] = fvec_ny_row<false>(x + (int64_t)q * d + m * dsub, pqc + ((int64_t)m * 256 + j) * dsub, dsub);
-    }
-}
-void launch_pq_ip_table_rows(hipStream_t s, const float* x, int d, int M, const float* pqc, float* out, const int* rq_list,
-                             const int* rq_count) {
-    hipLaunchKernelGGL(k_pq_ip_table_rows, dim3(1024), dim3(256), 0, s, x, d, M, pqc, out, rq_list, rq_count);
-}
 __global__ __launch_bounds__(256) void k_bound_combine(float* __restrict__ acc, const float* __restrict__ in, int n, int take_max) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < n) acc[i] = take_max ? fmaxf(acc[i], in[i]) : fminf(acc[i], in[i]);

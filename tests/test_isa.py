@@ -22,8 +22,9 @@ TARGET = "hipv4-amdgcn-amd-amdhsa--gfx950"
 def _code_objects(tmp):
     """every gfx950 code object of the library (one per .hip translation unit)"""
     fat = os.path.join(tmp, "fat.bin")
+    # (objcopy with no output operand rewrites its input in place: the copy goes to tmp, the library is only read)
     subprocess.run([os.path.join(LLVM, "llvm-objcopy") if os.path.exists(os.path.join(LLVM, "llvm-objcopy")) else "objcopy",
-                    "--dump-section", ".hip_fatbin=" + fat, LIB], check=True, capture_output=True)
+                    "--dump-section", ".hip_fatbin=" + fat, LIB, os.path.join(tmp, "lib_copy.so")], check=True, capture_output=True)
     data = open(fat, "rb").read()
     starts = [m.start() for m in re.finditer(re.escape(b"__CLANG_OFFLOAD_BUNDLE__"), data)]
     out = []
