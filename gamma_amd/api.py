@@ -106,6 +106,7 @@ class GammaHip:
         self.h = h
         self.d = None
         self.M = None
+        self.ksub = 256   # 16 after ivfpq4_init
 
     def close(self):
         if getattr(self, "h", None):
@@ -186,6 +187,17 @@ class GammaHip:
                                              bucket_max_size), "ivfpq_init")
         self.d, self.nlist, self.M = d, nlist, M
 
+    def ivfpq4_init(self, d, nlist, M, metric=METRIC_L2, bucket_init_size=1000, bucket_max_size=1280000):
+        """4-bit PQ codes (nbits_per_idx = 4): ksub = 16, code_size = (4 M + 7) / 8, packed as faiss's PQEncoderGeneric
+        packs them; the ivfpq_* methods serve the handle afterwards (include/gamma_hip.h)"""
+        self._ck(self.L.gamma_hip_ivfpq4_init(self.h, d, nlist, M, metric, bucket_init_size, bucket_max_size),
+                 "ivfpq4_init")
+        self.d, self.nlist, self.M, self.ksub = d, nlist, M, 16
+
+    def _code_width(self):
+        # bytes per list entry: M, or (4 M + 7) / 8 on a 4-bit handle
+        return (4 * self.M + 7) // 8 if self.ksub == 16 else self.M
+
     def ivfpq_set_trained(self, coarse_centroids, pq_centroids, table=None):
         cc, pq = _f32(coarse_centroids), _f32(pq_centroids)
         t = _f32(table) if table is not None else None
@@ -201,7 +213,7 @@ class GammaHip:
         return m
 
     def ivfpq_table(self):
-        out = np.empty((self.nlist, self.M, 256), dtype=np.float32)
+        out = np.empty((self.nlist, self.M, self.ksub), dtype=np.float32)
         self._ck(self.L.gamma_hip_ivfpq_get_precomputed_table(self.h, _p(out, _lib.f32p)), "get_table")
         return out
 
@@ -276,7 +288,7 @@ class GammaHip:
     def get_list(self, l):
         n = self.list_size(l)
         ids = np.empty(n, dtype=np.int64)
-        codes = np.empty((n, self.M), dtype=np.uint8)
+        codes = np.empty((n, self._code_width()), dtype=np.uint8)
         self._ck(self.L.gamma_hip_ivfpq_get_list(self.h, l, _p(ids, _lib.i64p), _p(codes, _lib.u8p)),
                  "get_list")
         return ids, codes
@@ -300,11 +312,12 @@ class GammaHip:
 
     def ivfpq_train(self, x, nlist, M):
         """IndexIVFPQ::train as GammaIVFPQIndex::Indexing runs it, on the device: (coarse centroids [nlist, d], PQ codebooks
-        [M, 256, d / M]) -- the library's own training, bit for bit (gamma_hip_ivfpq_train)"""
+        [M, 256, d / M]; [M, 16, d / M] on a handle initialised by ivfpq4_init) -- the library's own training, bit for bit
+        (gamma_hip_ivfpq_train)"""
         x = _f32(x)
         d = x.shape[1]
         cc = np.empty((nlist, d), dtype=np.float32)
-        pq = np.empty((M, 256, d // M), dtype=np.float32)
+        pq = np.empty((M, self.ksub, d // M), dtype=np.float32)
         self._ck(self.L.gamma_hip_ivfpq_train(self.h, d, x.shape[0], _p(x, _lib.f32p), nlist, M, _p(cc, _lib.f32p),
                                               _p(pq, _lib.f32p)), "ivfpq_train")
         return cc, pq
@@ -324,7 +337,7 @@ class GammaHip:
         vecs = _f32(vecs)
         n = vecs.shape[0]
         lno = np.empty(n, dtype=np.int64)
-        codes = np.empty((n, self.M), dtype=np.uint8)
+        codes = np.empty((n, self._code_width()), dtype=np.uint8)
         self._ck(self.L.gamma_hip_ivfpq_encode(self.h, n, _p(vecs, _lib.f32p), _p(lno, _lib.i64p),
                                                _p(codes, _lib.u8p)), "encode")
         return lno, codes

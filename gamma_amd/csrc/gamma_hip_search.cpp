@@ -3,6 +3,7 @@
 // (include/gamma_hip.h).  No CPU fallback: every entry point runs the HIP kernels or returns an error.
 #include "gamma_hip_internal.h"
 #include "gamma_hip_search.h"
+#include "pq4.h"
 
 namespace ghi {
 
@@ -245,12 +246,27 @@ struct BoundXchg {
     }
 };
 
+// a 4-bit handle (gamma_hip_ivfpq4_init) behind an entry point that is 8-bit only: never silent
+static int pq4_refuse(H* h, const char* what) {
+    h->err = std::string("4-bit handle: ") + what + " is 8-bit only";
+    return GAMMA_HIP_EUNSUPPORTED;
+}
+#define GH_NO_PQ4(h, what)                                                \
+    do {                                                                  \
+        if ((h)->ksub == gh::kPq4Ksub) return pq4_refuse((h), (what));    \
+    } while (0)
+
 int ivfpq_stage_a(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int nq,
                   const float* d_x, int R, const float* pre_dis = nullptr, const int* pre_probe = nullptr,
                   bool shard = false, float* out_dis = nullptr, int64_t* out_ids = nullptr, BoundXchg* bx = nullptr) {
     const int P = p->nprobe, d = h->d, M = h->M, nlist = h->nlist;
     const bool two = bx && bx->two_phase;
     const bool l2 = p->metric == GAMMA_HIP_METRIC_L2;
+    // 4-bit codes (pq4.hip) take ONE path: shared coarse quantizer, k_pq4_ip_table, pair offsets, k_ivfpq4_scan_pair
+    // unbounded, the unfiltered selection -- the bounded scan with its feedback, fused / residual tables and the byte
+    // passes (cf, c8, q8) are 8-bit kernels and are gated off below
+    const bool pq4 = h->ksub == gh::kPq4Ksub;
+    if (pq4 && (shard || bx)) return pq4_refuse(h, "a list-shard search");
     hipStream_t s = h->stream;
     // this call reads the lists through the version of their (offset, length) tables that is current now:
     // behind the writer's copies (ver_ev), and the version is not reused before the kernels below are done (rd_ev)
@@ -321,9 +337,9 @@ int ivfpq_stage_a(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int
     //  recall_num 300 3.00 -> 2.07 ms per 16384 queries (scan 0.475 -> 0.675 of the roofline, select 910 -> 277 us), the C4 shape
     //  at 8 M 5.19 -> 3.96 ms per 8192; the candidate stages (1536 / 768 slots) overflow into the unfiltered path as ever)
     constexpr int cf_maxr = 512;
-    const bool c8_shape = !no_c8 && l2 && M == 16 && R <= cf_maxr && h->d_sums && h->d_t2max;
+    const bool c8_shape = !pq4 && !no_c8 && l2 && M == 16 && R <= cf_maxr && h->d_sums && h->d_t2max;
     if (G0 == 8 && c8_shape && P > 8) G0 = 5;
-    int64_t t2_bytes = (int64_t)nlist * M * 256 * sizeof(float);
+    int64_t t2_bytes = (int64_t)nlist * M * h->ksub * sizeof(float);
     const bool compacted = shard && pre_dis && pre_probe;
     if (two) {
         // the producers take the query's nearest G1 owned probes only: everything else waits for the GLOBAL bound
@@ -365,7 +381,7 @@ int ivfpq_stage_a(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int
     // (recall_num up to 1024 since round 5: slices of 2048 items and k_select_final_wg beyond 256 -- the configurations that need
     //  a long short-list, full-size C5 at ~1000, keep the pre-filter)
     constexpr int scan_gmin = 4, bound_maxr = 1024;
-    bool bounded = (!shard || compacted) && h->scan_bound && R <= bound_maxr && P <= 128 && G >= (two ? 1 : scan_gmin);
+    bool bounded = !pq4 && (!shard || compacted) && h->scan_bound && R <= bound_maxr && P <= 128 && G >= (two ? 1 : scan_gmin);
     if (bounded) {
         // feedback (gamma_hip_internal.h, bound_*): the counts of some recent call are in the pinned words
         static const bool no_fb = getenv("GAMMA_HIP_NO_BOUND_FEEDBACK") != nullptr;
@@ -414,9 +430,9 @@ int ivfpq_stage_a(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int
     }
     // L2 table mode 0 (no precomputed table, H::table_mode): per-list tables from the residual (scan.hip RES) -- the plain and
     // the bounded loop; no query table, none of the passes built on T2 sums (d_sums is null: cf / c8 / q8 are off by their own gates)
-    const bool res = l2 && h->table_mode == 0;
+    const bool res = !pq4 && l2 && h->table_mode == 0;
     static const bool no_fused_ip = getenv("GAMMA_HIP_NO_FUSED_IP") != nullptr;
-    const bool fuse_ip = bounded && !res && PGN == 1 && (M == 16 || M == 32) && !no_fused_ip;
+    const bool fuse_ip = !pq4 && bounded && !res && PGN == 1 && (M == 16 || M == 32) && !no_fused_ip;
     // the bounded scan's per-call state (repair list, ready words, survivor counts) is sized here, before the pair offsets,
     // whose kernel clears it together with the tie flags -- one launch instead of four fills in front of the scan
     // (byte-table filter pass: a first group of a few probes bounds loosely for some queries -- slices of 2048 keep them out of the
@@ -486,7 +502,10 @@ int ivfpq_stage_a(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int
     }
     {
         StageScope t(h, GAMMA_HIP_STAGE_TABLES);
-        if (!fuse_ip && !res) {
+        if (pq4) {
+            GH_CHECK(h, h->w_st2.ensure((size_t)nq * M * gh::kPq4Ksub * sizeof(float)));
+            gh::launch_pq4_ip_table(s, d_x, nq, d, M, h->d_pqc, h->w_st2.as<float>());
+        } else if (!fuse_ip && !res) {
             GH_CHECK(h, h->w_st2.ensure((size_t)nq * M * 256 * sizeof(float)));
             gh::launch_pq_ip_table(s, d_x, nq, d, M, h->d_pqc, h->w_st2.as<float>());
         }
@@ -557,6 +576,12 @@ int ivfpq_stage_a(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int
     }
     auto scan = [&](int gsz, int pg_lo, int pg_cnt, const gh::ScanBound* bound, bool count) {
         StageScope t(h, GAMMA_HIP_STAGE_SCAN, count);
+        if (pq4) {   // (bounded is false: gsz = G, every probe group, no bound)
+            gh::launch_ivfpq4_scan_pair(s, l2, nq, M, P, h->w_probe.as<int>(), dis0, h->w_st2.as<float>(), h->d_T2, h->d_list_off,
+                                        h->d_list_len, h->d_list_mask, nlist, h->d_codes, h->d_ids, h->w_pair_off.as<int>(),
+                                        q_stride, h->w_dist.as<float>(), fc.d_tab, fc.d_qf, need_ids, qperm, gsz, pg_cnt);
+            return;
+        }
         gh::launch_ivfpq_scan_pair(s, l2, d_x, nq, d, M, P, h->w_probe.as<int>(),
                                    dis0, h->d_cc, h->scan_st2(l2), h->d_T2,
                                    h->d_list_off, h->d_list_len, h->d_list_mask, nlist, h->d_codes,
@@ -856,7 +881,8 @@ bool ivfpq_small_ok(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, i
     constexpr int max_nq = 512;   // (the section's header: the measured cross-over with the regular chain is ~1000)
     // exact coarse distances (faiss below 20 queries) come from the fused first kernel, which covers 16 queries; the
     // GEMM form (20 queries and more) from the regular matrix kernel
-    return !off && h->small_path && nq >= 1 && nq <= max_nq &&
+    // (a 4-bit handle takes the regular chain: the small path's fused kernels are 8-bit)
+    return !off && h->ksub == 256 && h->small_path && nq >= 1 && nq <= max_nq &&
            p->nprobe <= 128 && R <= 1024 && !h->profile && !fc.d_qf && !h->d_list_mask &&
            h->nlist <= 16384 &&
            (int64_t)p->nprobe * std::max(1, h->max_list_len) <= (1 << 22) &&
@@ -1936,6 +1962,7 @@ int gamma_hip_ivfpq_search_shard(gamma_hip_index* h, const gamma_hip_search_para
                                  const float* d_x, int k, float* d_recall_dis, int64_t* d_recall_ids) {
     if (!h) return GAMMA_HIP_EINVAL;
     SearchLock lk(h);
+    GH_NO_PQ4(h, "gamma_hip_ivfpq_search_shard");
     GH_TRY(replay_join(h));
     GH_TRY(ivfpq_check(h, p, nq, k));
     if (k <= 0 || nq == 0) return GAMMA_HIP_OK;
@@ -2003,6 +2030,7 @@ static int shard_preassigned(gamma_hip_index* h, const gamma_hip_search_params* 
             }
         }
     } reduce_once{h, bx, nq, p && p->metric == GAMMA_HIP_METRIC_L2};
+    GH_NO_PQ4(h, "gamma_hip_ivfpq_search_shard_preassigned / _bounded");
     GH_TRY(replay_join(h));
     GH_TRY(ivfpq_check(h, p, nq, k));
     if (k <= 0 || nq == 0) return GAMMA_HIP_OK;
@@ -2127,6 +2155,7 @@ static int merge_rerank_impl(gamma_hip_index* h, const gamma_hip_search_params* 
                              int q0, int nq_local, float* d_distances, int64_t* d_labels) {
     if (!h) return GAMMA_HIP_EINVAL;
     SearchLock lk(h);
+    GH_NO_PQ4(h, "gamma_hip_ivfpq_merge_rerank(_exact)");
     GH_TRY(replay_join(h));
     GH_TRY(ivfpq_check(h, p, nq, k));
     if (nshards <= 0 || q0 < 0 || nq_local < 0 || q0 + nq_local > nq) return fail(h, GAMMA_HIP_EINVAL, "bad shard/query range");
@@ -2215,6 +2244,7 @@ int gamma_hip_ivfpq_shard_exact(gamma_hip_index* h, const gamma_hip_search_param
     if (nq <= 0 || R <= 0) return GAMMA_HIP_OK;
     if (!d_x || !d_ids || !d_exact) return GAMMA_HIP_EINVAL;
     SearchLock lk(h);
+    GH_NO_PQ4(h, "gamma_hip_ivfpq_shard_exact");
     GH_TRY(replay_join(h));
     if (!h->d_raw || h->raw_d != h->d) return fail(h, GAMMA_HIP_EINVAL, "no raw store");
     GH_CHECK(h, hipSetDevice(h->device));
@@ -2232,6 +2262,7 @@ int gamma_hip_ivfpq_shard_export_exact(gamma_hip_index* h, const gamma_hip_searc
     if (nf <= 0) return GAMMA_HIP_OK;
     if (!d_xf || !d_vals || !d_ids || !d_off || !d_bound_f || !d_ex || stride < 1) return GAMMA_HIP_EINVAL;
     SearchLock lk(h);
+    GH_NO_PQ4(h, "gamma_hip_ivfpq_shard_export_exact");
     if (!h->d_raw || h->raw_d != h->d || !h->raw_sparse) return fail(h, GAMMA_HIP_EINVAL, "export of exact distances: a sharded raw store (gamma_hip_raw_put)");
     GH_CHECK(h, hipSetDevice(h->device));
     gh::launch_export_exact(h->stream, p->metric == GAMMA_HIP_METRIC_L2, d_xf, nf, h->d, h->d_raw, h->d_raw_slot, h->raw_slot_cap,
@@ -2244,6 +2275,7 @@ int gamma_hip_ivfpq_shard_cut_flags(gamma_hip_index* h, int nq, uint8_t* d_flags
     if (!h || nq < 0 || (nq > 0 && !d_flags)) return GAMMA_HIP_EINVAL;
     if (nq == 0) return GAMMA_HIP_OK;
     SearchLock lk(h);
+    GH_NO_PQ4(h, "gamma_hip_ivfpq_shard_cut_flags");
     GH_CHECK(h, hipSetDevice(h->device));
     if (h->shard_cut_nq == nq) {
         GH_CHECK(h, hipMemcpyAsync(d_flags, h->shard_cut_chunked ? h->w_shard_cut.p : h->w_tcut.p, (size_t)nq,
@@ -2258,6 +2290,7 @@ int gamma_hip_ivfpq_shard_cut_flags(gamma_hip_index* h, int nq, uint8_t* d_flags
 int gamma_hip_ivfpq_merge_set_shard_flags(gamma_hip_index* h, const uint8_t* d_flags) {
     if (!h) return GAMMA_HIP_EINVAL;
     SearchLock lk(h);
+    GH_NO_PQ4(h, "gamma_hip_ivfpq_merge_set_shard_flags");
     h->merge_shard_flags = d_flags;
     return GAMMA_HIP_OK;
 }
@@ -2265,6 +2298,7 @@ int gamma_hip_ivfpq_merge_set_shard_flags(gamma_hip_index* h, const uint8_t* d_f
 int gamma_hip_ivfpq_merge_flagged(gamma_hip_index* h, int* n_flagged, const int32_t** d_list) {
     if (!h || !n_flagged) return GAMMA_HIP_EINVAL;
     SearchLock lk(h);
+    GH_NO_PQ4(h, "gamma_hip_ivfpq_merge_flagged");
     *n_flagged = 0;
     if (d_list) *d_list = nullptr;
     if (!h->merge_flags) return GAMMA_HIP_OK;
@@ -2322,6 +2356,7 @@ int gamma_hip_ivfpq_shard_export_rows(gamma_hip_index* h, const gamma_hip_search
     if (nf <= 0) return GAMMA_HIP_OK;
     if (!d_probe_f) return GAMMA_HIP_EINVAL;
     SearchLock lk(h);
+    GH_NO_PQ4(h, "gamma_hip_ivfpq_shard_export_rows");
     GH_TRY(replay_join(h));
     if (!h->ivf_init || h->ivfflat) return fail(h, GAMMA_HIP_EINVAL, "ivfpq not initialised");
     GH_CHECK(h, hipSetDevice(h->device));
@@ -2341,6 +2376,7 @@ int gamma_hip_ivfpq_shard_export(gamma_hip_index* h, const gamma_hip_search_para
                                  int32_t* d_off) {
     if (!h) return GAMMA_HIP_EINVAL;
     SearchLock lk(h);
+    GH_NO_PQ4(h, "gamma_hip_ivfpq_shard_export");
     GH_TRY(replay_join(h));
     GH_TRY(ivfpq_check(h, p, nf, 1));
     if (nf == 0) return GAMMA_HIP_OK;
@@ -2400,6 +2436,7 @@ static int merge_replay_impl(gamma_hip_index* h, const gamma_hip_search_params* 
                              int k, const int32_t* d_list, float* d_distances, int64_t* d_labels) {
     if (!h) return GAMMA_HIP_EINVAL;
     SearchLock lk(h);
+    GH_NO_PQ4(h, "gamma_hip_ivfpq_merge_replay(_exact)");
     GH_TRY(ivfpq_check(h, p, nf, k));
     if (nf == 0 || k <= 0) return GAMMA_HIP_OK;
     if (!d_x_slice || !d_vals_all || !d_ids_all || !d_off_all || !d_list || !d_distances || !d_labels)

@@ -3,6 +3,7 @@
 // vector store, scalar columns and the delete bitmap.  C ABI: include/gamma_hip.h.
 #include "binivf.h"
 #include "gamma_hip_internal.h"
+#include "pq4.h"
 
 namespace ghi {
 
@@ -983,6 +984,25 @@ int gamma_hip_ivfpq_use_precomputed_table(gamma_hip_index* h) {
     return h->table_mode;
 }
 
+// nbits_per_idx = 4 (gamma_index_ivfpq.cc:167-170): 16 centroids per sub-quantizer, two indices per code byte
+int gamma_hip_ivfpq4_init(gamma_hip_index* h, int d, int nlist, int M, int metric, int bucket_init_size,
+                          int bucket_max_size) {
+    if (!h) return GAMMA_HIP_EINVAL;
+    WriteLock lk(h);
+    if (h->ivf_init) return fail(h, GAMMA_HIP_EINVAL, "already initialised");
+    if (d <= 0 || nlist <= 0 || M <= 0) return fail(h, GAMMA_HIP_EINVAL, "bad d/nlist/M");
+    if (d % M != 0) return fail(h, GAMMA_HIP_EINVAL, "d must be divisible by nsubvector");
+    if (d / M > 64) return fail(h, GAMMA_HIP_EINVAL, "dsub > 64 unsupported");
+    if (gh::pq4_code_size(M) > gh::kPq4MaxCodeSize)
+        return fail(h, GAMMA_HIP_EINVAL, "4-bit codes: code_size = (4 * nsubvector + 7) / 8 > 64 unsupported");
+    if ((int64_t)nlist * M * gh::kPq4Ksub * (int64_t)sizeof(float) > g_table_max_bytes.load())
+        return fail(h, GAMMA_HIP_EUNSUPPORTED, "4-bit codes: the precomputed table would exceed precomputed_table_max_bytes (table mode 0 is 8-bit only)");
+    h->ksub = gh::kPq4Ksub;
+    const int rc = ivf_init_locked(h, d, nlist, M, metric, bucket_init_size, bucket_max_size, false);
+    if (rc != GAMMA_HIP_OK) h->ksub = 256;
+    return rc;
+}
+
 // binary: the binary IVF model -- no float centroids, PQ codebooks or tables (gamma_hip_binivf_init)
 static int ivf_init_locked(gamma_hip_index* h, int d, int nlist, int M, int metric, int bucket_init_size,
                            int bucket_max_size, bool flat, bool binary) {
@@ -992,22 +1012,24 @@ static int ivf_init_locked(gamma_hip_index* h, int d, int nlist, int M, int metr
     // initialize_IVFPQ_precomputed_table's rule (faiss:IndexIVFPQ.cpp:441-449): `table_size > max` keeps mode 0.  faiss
     // applies it at train / Load; the outcome depends on nlist, M and the process-wide limit only, so it is fixed here,
     // where the arena decides whether it keeps the per-code table sums (they are sums of T2 entries: none in mode 0).
-    h->table_mode = (!flat && (int64_t)nlist * M * 256 * (int64_t)sizeof(float) > g_table_max_bytes.load()) ? 0 : 1;
-    h->keep_sums = !flat && h->table_mode == 1 && getenv("GAMMA_HIP_NO_CODE_SUMS") == nullptr;
+    const int ksub = h->ksub;   // 256, or 16 on a 4-bit handle (gamma_hip_ivfpq4_init, which has ruled table mode 0 out)
+    h->table_mode = (!flat && (int64_t)nlist * M * ksub * (int64_t)sizeof(float) > g_table_max_bytes.load()) ? 0 : 1;
+    // (4-bit: no code sums -- the passes built on them, cf / c8 / q8, are 8-bit kernels)
+    h->keep_sums = !flat && ksub == 256 && h->table_mode == 1 && getenv("GAMMA_HIP_NO_CODE_SUMS") == nullptr;
     h->d = d;
     h->nlist = nlist;
     h->M = M;
     h->dsub = d / M;
-    h->code_size = M;   // IVFFLAT: M = 1, one dummy byte per entry (the arena code keeps its shape)
+    h->code_size = ksub == gh::kPq4Ksub ? gh::pq4_code_size(M) : M;   // IVFFLAT: M = 1, one dummy byte per entry (the arena code keeps its shape)
     h->metric = metric;
     h->bucket_init = bucket_init_size > 0 ? bucket_init_size : 1000;
     h->bucket_max = bucket_max_size > 0 ? bucket_max_size : 1280000;
     if (!binary) {
         GH_CHECK(h, hipMalloc((void**)&h->d_cc, (size_t)nlist * d * sizeof(float)));
         GH_CHECK(h, hipMalloc((void**)&h->d_cc_norms, (size_t)nlist * sizeof(float)));
-        GH_CHECK(h, hipMalloc((void**)&h->d_pqc, flat ? 256 : (size_t)M * 256 * h->dsub * sizeof(float)));
+        GH_CHECK(h, hipMalloc((void**)&h->d_pqc, flat ? 256 : (size_t)M * ksub * h->dsub * sizeof(float)));
         if (flat || h->table_mode == 1)
-            GH_CHECK(h, hipMalloc((void**)&h->d_T2, flat ? 256 : (size_t)nlist * M * 256 * sizeof(float)));
+            GH_CHECK(h, hipMalloc((void**)&h->d_T2, flat ? 256 : (size_t)nlist * M * ksub * sizeof(float)));
     }
     for (int v = 0; v < H::NVER; v++) {
         GH_CHECK(h, hipMalloc((void**)&h->d_ver_off[v], (size_t)nlist * sizeof(int64_t)));
@@ -1086,8 +1108,8 @@ int gamma_hip_ivfpq_set_trained(gamma_hip_index* h, const float* cc, const float
     WriteLock lk(h);
     if (!h->ivf_init || h->ivfflat) return fail(h, GAMMA_HIP_EINVAL, "ivfpq not initialised");
     GH_CHECK(h, hipSetDevice(h->device));
-    const size_t ncc = (size_t)h->nlist * h->d, npq = (size_t)h->M * 256 * h->dsub;
-    const size_t nt = (size_t)h->nlist * h->M * 256;
+    const size_t ncc = (size_t)h->nlist * h->d, npq = (size_t)h->M * h->ksub * h->dsub;
+    const size_t nt = (size_t)h->nlist * h->M * h->ksub;
     GH_CHECK(h, hipMemcpyAsync(h->d_cc, cc, ncc * sizeof(float), hipMemcpyHostToDevice, h->wstream));
     GH_CHECK(h, hipMemcpyAsync(h->d_pqc, pqc, npq * sizeof(float), hipMemcpyHostToDevice, h->wstream));
     gh::launch_row_norms(h->wstream, h->d_cc, h->nlist, h->d, h->d_cc_norms);
@@ -1095,6 +1117,8 @@ int gamma_hip_ivfpq_set_trained(gamma_hip_index* h, const float* cc, const float
         // no table (a supplied one is not taken either: the reference would not have built it)
     } else if (table)
         GH_CHECK(h, hipMemcpyAsync(h->d_T2, table, nt * sizeof(float), hipMemcpyHostToDevice, h->wstream));
+    else if (h->ksub == gh::kPq4Ksub)
+        gh::launch_pq4_precompute_table(h->wstream, h->d_cc, h->nlist, h->d, h->M, h->d_pqc, h->d_T2);
     else
         gh::launch_precompute_table(h->wstream, h->d_cc, h->nlist, h->d, h->M, h->d_pqc, h->d_T2);
     {
@@ -1130,7 +1154,7 @@ int gamma_hip_ivfpq_get_precomputed_table(gamma_hip_index* h, float* out) {
     if (!h->trained) return fail(h, GAMMA_HIP_ENOTTRAINED, "not trained");
     if (h->table_mode == 0) return fail(h, GAMMA_HIP_EUNSUPPORTED, "table mode 0: no precomputed table (it would exceed precomputed_table_max_bytes)");
     GH_CHECK(h, hipSetDevice(h->device));
-    GH_CHECK(h, hipMemcpyAsync(out, h->d_T2, (size_t)h->nlist * h->M * 256 * sizeof(float),
+    GH_CHECK(h, hipMemcpyAsync(out, h->d_T2, (size_t)h->nlist * h->M * h->ksub * sizeof(float),
                                hipMemcpyDeviceToHost, h->wstream));
     GH_CHECK(h, hipStreamSynchronize(h->wstream));
     return GAMMA_HIP_OK;
@@ -1462,6 +1486,7 @@ int gamma_hip_ivfpq_set_list_mask(gamma_hip_index* h, const uint8_t* owned) {
     if (!h) return GAMMA_HIP_EINVAL;
     WriteLock lk(h);
     if (!h->ivf_init) return fail(h, GAMMA_HIP_EINVAL, "ivfpq not initialised");
+    if (h->ksub == gh::kPq4Ksub) return fail(h, GAMMA_HIP_EUNSUPPORTED, "4-bit handle: list shards (gamma_hip_ivfpq_set_list_mask) are 8-bit only");
     GH_CHECK(h, hipSetDevice(h->device));
     GH_CHECK(h, lk.exclusive());
     if (!owned) {
@@ -1494,6 +1519,7 @@ static int encode_locked(H* h, int64_t n, const float* d_vecs, int* d_assign, ui
     gh::launch_select_topk(s, true, h->we_mat.as<float>(), nlist, nullptr, nlist, nlist, (int)n, 1,
                            h->we_cdis.as<float>(), d_assign);
     if (h->ivfflat) GH_CHECK(h, hipMemsetAsync(d_codes_out, 0, (size_t)n, s));   // the dummy byte of every entry
+    else if (h->ksub == gh::kPq4Ksub) gh::launch_pq4_encode(s, d_vecs, n, d, h->M, d_assign, h->d_cc, h->d_pqc, d_codes_out);
     else gh::launch_pq_encode(s, d_vecs, n, d, h->M, d_assign, h->d_cc, h->d_pqc, d_codes_out);
     GH_CHECK(h, hipGetLastError());
     return GAMMA_HIP_OK;

@@ -253,11 +253,18 @@ int gamma_hip_binivf_train(gamma_hip_index* h, int nbits, int64_t n, const uint8
 // train_residual_o (faiss:IndexIVFPQ.cpp:67-106): at most 256 * 256 points (fvecs_maybe_subsample with pq.cp.seed =
 // 1234), their residuals to the nearest coarse centroid (by_residual), and ProductQuantizer::train: one
 // Clustering(dsub, 256, niter 25) per sub-quantizer.  coarse: nlist*d, pq: M*256*(d/M) fp32 host out.
+// On a handle initialised as 4-bit (gamma_hip_ivfpq4_init) ksub is 16: at most 256 * 16 points
+// (pq.cp.max_points_per_centroid * pq.ksub, faiss:IndexIVFPQ.cpp:67-131), Clustering(dsub, 16, niter 25), pq: M*16*(d/M).
 int gamma_hip_ivfpq_train(gamma_hip_index* h, int d, int64_t n, const float* x, int nlist, int M, float* coarse, float* pq) {
     if (!h || d <= 0 || nlist <= 0 || M <= 0 || d % M != 0 || !x || !coarse || !pq) return GAMMA_HIP_EINVAL;
     int rc = gamma_hip_kmeans(h, d, n, x, nlist, 10, 1234, 256, coarse, nullptr);
     if (rc) return rc;
-    const int64_t nmax = 256 * 256;
+    int ksub = 256;
+    {
+        std::lock_guard<std::mutex> g(h->mu);
+        if (h->ivf_init && !h->ivfflat) ksub = h->ksub;
+    }
+    const int64_t nmax = 256 * (int64_t)ksub;
     std::vector<float> subset;
     const float* xs = x;
     int64_t ns = n;
@@ -281,7 +288,7 @@ int gamma_hip_ivfpq_train(gamma_hip_index* h, int d, int64_t n, const float* x, 
             const float* c = coarse + (size_t)assign[i] * d + m * dsub;
             for (int t = 0; t < dsub; t++) slice[(size_t)i * dsub + t] = xi[t] - c[t];
         }
-        rc = gamma_hip_kmeans(h, dsub, ns, slice.data(), 256, 25, 1234, 256, pq + (size_t)m * 256 * dsub, nullptr);
+        rc = gamma_hip_kmeans(h, dsub, ns, slice.data(), ksub, 25, 1234, 256, pq + (size_t)m * ksub * dsub, nullptr);
         if (rc) return rc;
     }
     return GAMMA_HIP_OK;

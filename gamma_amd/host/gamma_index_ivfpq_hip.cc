@@ -114,6 +114,29 @@ int HIPIVFPQModelParams::Parse(const char *str) {
   return 0;
 }
 
+namespace {
+struct ListsInitEntry {
+  int nbits;
+  HIPListsInitFn fn;
+};
+// (a function-local static: registrations run during static initialisation, in any order)
+std::vector<ListsInitEntry> &ListsInits() {
+  static std::vector<ListsInitEntry> v;
+  return v;
+}
+}  // namespace
+
+int RegisterHIPListsInit(int nbits, HIPListsInitFn fn) {
+  ListsInits().push_back({nbits, fn});
+  return 0;
+}
+
+HIPListsInitFn FindHIPListsInit(int nbits) {
+  for (const ListsInitEntry &e : ListsInits())
+    if (e.nbits == nbits) return e.fn;
+  return nullptr;
+}
+
 GammaIVFPQHIPIndex::GammaIVFPQHIPIndex() {}
 
 GammaIVFPQHIPIndex::~GammaIVFPQHIPIndex() {
@@ -162,10 +185,17 @@ int GammaIVFPQHIPIndex::Init(const std::string &model_parameters, int indexing_s
          "available on the HIP path)", d_, pa.nsubvector);
     return -2;
   }
-  if (pa.has_hnsw || pa.has_opq || pa.support_indivisible_nsubvector || pa.nbits_per_idx != 8) {
-    HLOG("hnsw / opq / padded dimensions / nbits_per_idx != 8 are not supported by HIPIVFPQ");
+  // nbits_per_idx other than 8: through a registered lists initialiser (4: gamma_index_ivfpq4_hip.cc), else rejected
+  const HIPListsInitFn lists_init = pa.nbits_per_idx == 8 ? nullptr : FindHIPListsInit(pa.nbits_per_idx);
+  if (pa.has_hnsw || pa.has_opq || pa.support_indivisible_nsubvector || (pa.nbits_per_idx != 8 && !lists_init)) {
+    HLOG("hnsw / opq / padded dimensions / nbits_per_idx other than 8 and 4 are not supported by HIPIVFPQ");
     return -2;
   }
+  if (lists_init && pa.devices.size() > 1) {
+    HLOG("nbits_per_idx = %d with several devices is not supported (the group of handles is 8-bit only)", pa.nbits_per_idx);
+    return -2;
+  }
+  nbits_ = pa.nbits_per_idx;
   nlist_ = pa.ncentroids;
   M_ = pa.nsubvector;
   metric_type_ = pa.metric_type;
@@ -176,9 +206,9 @@ int GammaIVFPQHIPIndex::Init(const std::string &model_parameters, int indexing_s
   }
   if (OpenDevices(pa.devices, pa.replicate)) return -1;
   int rc = ForAll([&](gamma_hip_index *m) {
-    int r = gamma_hip_ivfpq_init(m, d_, nlist_, M_, 8,
-                                 metric_type_ == DistanceComputeType::L2 ? GAMMA_HIP_METRIC_L2 : GAMMA_HIP_METRIC_IP,
-                                 pa.bucket_init_size, pa.bucket_max_size);
+    const int metric = metric_type_ == DistanceComputeType::L2 ? GAMMA_HIP_METRIC_L2 : GAMMA_HIP_METRIC_IP;
+    int r = lists_init ? lists_init(m, d_, nlist_, M_, metric, pa.bucket_init_size, pa.bucket_max_size)
+                       : gamma_hip_ivfpq_init(m, d_, nlist_, M_, 8, metric, pa.bucket_init_size, pa.bucket_max_size);
     if (!r) r = gamma_hip_raw_init(m, d_);
     if (!r) r = gamma_hip_set_exact_ties(m, pa.exact_ties ? 1 : 0);
     if (!r && pa.perf_stages) r = gamma_hip_profile_enable(m, 1);
@@ -230,7 +260,7 @@ int GammaIVFPQHIPIndex::TrainCoarse(size_t num, const float *xt) {
 int GammaIVFPQHIPIndex::TrainOnHost(size_t num, const float *xt) {
   // IndexIVFPQ::train (train_q1 + train_residual_o + ProductQuantizer::train) on the device: gamma_hip_ivfpq_train
   coarse_centroids_.resize((size_t)nlist_ * d_);
-  pq_centroids_.resize((size_t)M_ * 256 * (d_ / M_));
+  pq_centroids_.resize((size_t)M_ * Ksub() * (d_ / M_));
   return gamma_hip_ivfpq_train(h_, d_, (int64_t)num, xt, nlist_, M_, coarse_centroids_.data(), pq_centroids_.data());
 }
 
@@ -505,7 +535,7 @@ int GammaIVFPQHIPIndex::UploadEngineBitmap() {
 
 int GammaIVFPQHIPIndex::SetTrained(const float *coarse, const float *pq) {
   coarse_centroids_.assign(coarse, coarse + (size_t)nlist_ * d_);
-  pq_centroids_.assign(pq, pq + (size_t)M_ * 256 * (d_ / M_));
+  pq_centroids_.assign(pq, pq + (size_t)M_ * Ksub() * (d_ / M_));
   if (ForAll([&](gamma_hip_index *m) {
         return gamma_hip_ivfpq_set_trained(m, coarse_centroids_.data(), pq_centroids_.data(), nullptr);
       }))
@@ -542,9 +572,9 @@ int GammaIVFPQHIPIndex::Dump(const std::string &dir) {
   f.nprobe = (size_t)nprobe_;
   f.coarse = coarse_centroids_;
   f.by_residual = true;
-  f.code_size = (size_t)M_;
+  f.code_size = CodeSize();
   f.M = (size_t)M_;
-  f.nbits = 8;
+  f.nbits = (size_t)nbits_;
   f.pq = pq_centroids_;
   f.sizes.resize(nlist_);
   f.codes.resize(nlist_);
@@ -555,7 +585,7 @@ int GammaIVFPQHIPIndex::Dump(const std::string &dir) {
     f.sizes[l] = (size_t)len;
     if (len == 0) continue;
     f.ids[l].resize(len);
-    f.codes[l].resize((size_t)len * M_);
+    f.codes[l].resize((size_t)len * CodeSize());
     if (grp_ ? gamma_hip_group_ivfpq_get_list(grp_, l, f.ids[l].data(), f.codes[l].data())
              : gamma_hip_ivfpq_get_list(h_, l, f.ids[l].data(), f.codes[l].data()))
       return -1;
@@ -581,8 +611,8 @@ int GammaIVFPQHIPIndex::Load(const std::string &dir) {
     HLOG("cannot read %s (%d)", path.c_str(), rc);
     return -1;
   }
-  if (f.d != d_ || (int)f.nlist != nlist_ || (int)f.M != M_ || f.nbits != 8 || (int)f.code_size != M_ ||
-      !f.by_residual || f.pq.size() != (size_t)M_ * 256 * (d_ / M_)) {
+  if (f.d != d_ || (int)f.nlist != nlist_ || (int)f.M != M_ || (int)f.nbits != nbits_ || f.code_size != CodeSize() ||
+      !f.by_residual || f.pq.size() != (size_t)M_ * Ksub() * (d_ / M_)) {
     HLOG("index file does not match the table's retrieval_param");
     return -1;
   }

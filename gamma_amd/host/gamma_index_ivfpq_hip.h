@@ -7,7 +7,8 @@
 // return codes, same Search contract.  The parameter classes carry a HIP prefix: the plugin is compiled
 // INTO libgamma next to the reference's own IVFPQ model, where a second
 // tig_gamma::IVFPQModelParams with another layout would be an ODR violation.  Unsupported on device and rejected in Init like any bad parameter:
-// hnsw quantizer, opq, support_indivisible_nsubvector, nbits_per_idx != 8.
+// hnsw quantizer, opq, support_indivisible_nsubvector, nbits_per_idx other than 8 and 4 (4: one device only, through the
+// lists initialiser that gamma_index_ivfpq4_hip.cc registers).
 #pragma once
 #include <atomic>
 #include <mutex>
@@ -44,6 +45,14 @@ class HIPIVFPQRetrievalParameters : public RetrievalParameters {
   int nprobe_;
   int exact_ties_;
 };
+
+// Lists initialiser of an nbits_per_idx other than 8 (4: gamma_hip_ivfpq4_init).  The translation unit that carries the ABI
+// call registers it at static-initialisation time, the idiom of REGISTER_MODEL; HIPIVFPQ::Init looks it up by
+// nbits_per_idx and rejects the value where none is registered (a build without that unit).
+typedef int (*HIPListsInitFn)(gamma_hip_index *h, int d, int nlist, int M, int metric, int bucket_init_size,
+                              int bucket_max_size);
+int RegisterHIPListsInit(int nbits, HIPListsInitFn fn);
+HIPListsInitFn FindHIPListsInit(int nbits);
 
 struct HIPIVFPQModelParams {
   int ncentroids = 2048;
@@ -122,6 +131,10 @@ class GammaIVFPQHIPIndex : public RetrievalModel {
   std::atomic<int64_t> ties_said_{0};   // WarnTiesNotHonoured: what this model has reported so far
   HIPIVFPQModelParams *model_param_ = nullptr;
   int64_t raw_uploaded_ = 0;
+  // nbits_per_idx: 8, or 4 (16 centroids per sub-quantizer, two indices per code byte as faiss's PQEncoderGeneric packs them)
+  int nbits_ = 8;
+  size_t Ksub() const { return (size_t)1 << nbits_; }
+  size_t CodeSize() const { return ((size_t)nbits_ * M_ + 7) / 8; }
 };
 
 // "HIPIVFFLAT": the reference's IVFFLAT model (index/impl/gamma_index_ivfflat.{h,cc}) on the device.  Same JSON

@@ -338,9 +338,10 @@ class PluginModel:
         pq = np.ascontiguousarray(pq, np.float32)
         return self.L.gh_host_ivfpq_set_trained(self.h, _f(coarse), _f(pq))
 
-    def trained_state(self, nlist, M):
+    def trained_state(self, nlist, M, ksub=256):
+        # ksub = 16 for a model initialised with "nbits_per_idx": 4
         cc = np.empty((nlist, self.d), np.float32)
-        pq = np.empty((M, 256, self.d // M), np.float32)
+        pq = np.empty((M, ksub, self.d // M), np.float32)
         if self.L.gh_host_ivfpq_state(self.h, _f(cc), _f(pq)):
             return None
         return cc, pq

@@ -243,6 +243,21 @@ int gamma_hip_bitmap_set(gamma_hip_index* h, const int64_t* docids, int64_t n, i
  * nbits must be 8, d % M == 0 (OPQ / HNSW quantizer / padding are rejected: EINVAL) */
 int gamma_hip_ivfpq_init(gamma_hip_index* h, int d, int nlist, int M, int nbits, int metric,
                          int bucket_init_size, int bucket_max_size);
+/* 4-bit PQ codes.  Replaces GammaIVFPQIndex::Init with nbits_per_idx = 4 (gamma_index_ivfpq.cc:167-170: the value goes
+ * straight into faiss::ProductQuantizer; the scanner is templated over the PQ decoder, gamma_index_ivfpq.h:540-601):
+ * ksub = 16, code_size = (4 M + 7) / 8, sub-quantizer m in bits [4m, 4m + 4) of the code -- an even m in the low nibble of
+ * byte m / 2 -- as PQEncoderGeneric packs them (faiss:impl/ProductQuantizer-inl.h:10-44); with an odd M the last high
+ * nibble is 0.  Requires d % M == 0, d / M <= 64 and code_size <= 64 (EINVAL otherwise).  After this init the entry points
+ * of an 8-bit handle serve the handle, sized by its ksub: _set_trained (pq_centroids M x 16 x dsub, table nlist x M x 16),
+ * _get_precomputed_table, _train (16 centroids per sub-quantizer from the residuals of at most 256 * 16 points,
+ * faiss:IndexIVFPQ.cpp:67-131), _add, _encode, _encode_each, _update_batch, _apply_updates, _add_keys(_batch), _get_list,
+ * _code_size, _delete, _compact_if_need, the raw store, _search, _search_device(_wait) and _last_stages.  Results are the
+ * reference's bit for bit, ties included, as for 8 bits.  GAMMA_HIP_EUNSUPPORTED with a message, never a silent
+ * fall-back: the shard, merge and export entry points, gamma_hip_ivfpq_set_list_mask, and this init itself when the
+ * precomputed table nlist * M * 16 * 4 bytes would exceed precomputed_table_max_bytes (table mode 0).  The group
+ * (gamma_hip_group_*) stays 8-bit.  gamma_hip_ivfpq_init keeps refusing nbits != 8. */
+int gamma_hip_ivfpq4_init(gamma_hip_index* h, int d, int nlist, int M, int metric, int bucket_init_size,
+                          int bucket_max_size);
 /* quantizer->xb (nlist*d), pq.centroids (M*ksub*dsub), and the precomputed table
  * (faiss:IndexIVFPQ.cpp:412-479; NULL => computed on device with identical arithmetic) */
 int gamma_hip_ivfpq_set_trained(gamma_hip_index* h, const float* coarse_centroids,
