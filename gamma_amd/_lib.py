@@ -139,6 +139,9 @@ SYMBOLS = {
                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gamma_hip_raw_put": (C.c_int, [C.c_void_p, C.c_int64, i64p, f32p]),
+    "gamma_hip_raw_drop": (C.c_int, [C.c_void_p, C.c_int64, i64p]),
+    "gamma_hip_raw_clear": (C.c_int, [C.c_void_p]),
+    "gamma_hip_raw_sparse_stats": (C.c_int, [C.c_void_p, i64p]),
     "gamma_hip_ivfpq_shard_exact": (C.c_int, [C.c_void_p, C.POINTER(SearchParams), C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "gamma_hip_ivfpq_merge_rerank_exact": (C.c_int, [C.c_void_p, C.POINTER(SearchParams), C.c_int, C.c_int, C.c_void_p, C.c_int,
                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
@@ -197,6 +200,9 @@ SYMBOLS = {
     "gamma_hip_group_ivfpq_search_device": (C.c_int, [C.c_void_p, C.POINTER(SearchParams), C.c_int, C.c_void_p, C.c_int,
                                                       C.c_void_p, C.c_void_p]),
     "gamma_hip_group_total_mem_bytes": (C.c_int64, [C.c_void_p]),
+    "gamma_hip_group_set_raw_placement": (C.c_int, [C.c_void_p, C.c_int]),
+    "gamma_hip_group_raw_placement": (C.c_int, [C.c_void_p]),
+    "gamma_hip_group_raw_put": (C.c_int, [C.c_void_p, C.c_int64, i64p, f32p, i64p]),
     "gamma_hip_total_mem_bytes": (C.c_int64, [C.c_void_p]),
     "gamma_hip_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "gamma_hip_profile_reset": (C.c_int, [C.c_void_p]),

@@ -140,6 +140,20 @@ class GammaHip:
         vecs = _f32(vecs)
         self._ck(self.L.gamma_hip_raw_put(self.h, len(vids), _p(vids, _lib.i64p), _p(vecs, _lib.f32p)), "raw_put")
 
+    def raw_drop(self, vids):
+        """a sparse store forgets the rows of these vector ids (those it does not hold are ignored); their rows are reused"""
+        vids = np.ascontiguousarray(vids, dtype=np.int64)
+        self._ck(self.L.gamma_hip_raw_drop(self.h, len(vids), _p(vids, _lib.i64p)), "raw_drop")
+
+    def raw_clear(self):
+        """the store as after raw_init: no rows, neither dense nor sparse"""
+        self._ck(self.L.gamma_hip_raw_clear(self.h), "raw_clear")
+
+    def raw_sparse_stats(self):
+        out = np.zeros(3, dtype=np.int64)
+        self._ck(self.L.gamma_hip_raw_sparse_stats(self.h, _p(out, _lib.i64p)), "raw_sparse_stats")
+        return dict(live=int(out[0]), slots=int(out[1]), free=int(out[2]))
+
     def raw_write(self, first_vid, vecs):
         vecs = _f32(vecs)
         self._ck(self.L.gamma_hip_raw_write(self.h, first_vid, vecs.shape[0], _p(vecs, _lib.f32p)), "raw_write")
@@ -719,6 +733,23 @@ class GammaHipGroup:
     def set_placement(self, replicate):
         """before set_owners: True = every member holds every list and a search splits the queries"""
         self._ck(self.L.gamma_hip_group_set_placement(self.g, 1 if replicate else 0), "group_set_placement")
+
+    def set_raw_placement(self, sharded):
+        """before any raw row is written: True = every row once, at the member that owns its vector's list (add / update /
+        raw_put route the rows; a has_rank search computes the exact distances where the rows are)"""
+        self._ck(self.L.gamma_hip_group_set_raw_placement(self.g, 1 if sharded else 0), "group_set_raw_placement")
+
+    def raw_placement(self):
+        return bool(self.L.gamma_hip_group_raw_placement(self.g))
+
+    def raw_put(self, vids, vecs):
+        """rows to the members that list their vector ids (keys added without vectors); returns how many nobody lists"""
+        vids = np.ascontiguousarray(vids, dtype=np.int64)
+        vecs = _f32(vecs)
+        skipped = np.zeros(1, dtype=np.int64)
+        self._ck(self.L.gamma_hip_group_raw_put(self.g, len(vids), _p(vids, _lib.i64p), _p(vecs, _lib.f32p), _p(skipped, _lib.i64p)),
+                 "group_raw_put")
+        return int(skipped[0])
 
     def add(self, vecs, first_vid):
         vecs = _f32(vecs)

@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "../../include/gamma_hip.h"
+#include "gamma_hip_group_ext.h"
 
 namespace {
 
@@ -134,6 +135,9 @@ struct gamma_hip_group {
     std::mutex mu;            // one group-level call at a time
     int next_enc = 0;         // members take turns encoding Add / Update batches
     bool replicate = false;   // gamma_hip_group_set_placement: every member holds every list, queries are split
+    // gamma_hip_group_set_raw_placement: every raw row exactly once, in the sparse store of the member that owns its list;
+    // the exact distances of a has_rank search are computed there and travel with the candidates
+    bool raw_sharded = false;
     // 0: peer copies; 1 (default since round 6; GAMMA_HIP_GROUP_RCCL=0 turns it off): RCCL wherever a communicator of the
     // members' DISTINCT devices can be formed -- members sharing a device, a missing librccl.so or a failing
     // ncclCommInitAll fall back to peer copies and say so (gamma_hip_group_transport)
@@ -149,6 +153,9 @@ struct gamma_hip_group {
         GBuf fx, fcd, fpr, sx, scd, spr, ex_vals, ex_ids, ex_off, av, ai, ao, cutf, cutall;
         // two-phase shard search: the bounds this member's scan exports (what its peers read), its working copy, a peer's
         GBuf bound, bound_pub, bound_peer;
+        // raw rows sharded with the lists: exact distances of this member's candidates, of the own slice's candidates from every
+        // member; tie phase: the flagged queries' bounds (owner side / shard side), the export's exact distances, the owner's copy
+        GBuf rex, all_ex, fbd, sbd, ex_ex, ae;
         hipEvent_t ev_coarse = nullptr, ev_scan = nullptr, ev_tie = nullptr, ev_bound = nullptr;
     };
     std::vector<Member> mb;
@@ -203,6 +210,12 @@ int member_fail(gamma_hip_group* g, int i, int rc) {
     return rc;
 }
 
+// the sparse raw store's entries this file may not name (gamma_hip_group_ext.h); null in a build without them
+const gamma_group_ext::RawOps*& raw_ops() {
+    static const gamma_group_ext::RawOps* ops = nullptr;
+    return ops;
+}
+
 // src on device sd -> dst on device dd, ordered on stream s (a stream of device dd)
 hipError_t copy_between(void* dst, int dd, const void* src, int sd, size_t bytes, hipStream_t s) {
     if (bytes == 0) return hipSuccess;
@@ -211,6 +224,78 @@ hipError_t copy_between(void* dst, int dd, const void* src, int sd, size_t bytes
 }
 
 }  // namespace
+
+namespace gamma_group_ext {
+
+int register_raw_ops(const RawOps* ops) {
+    raw_ops() = ops;
+    return 1;
+}
+
+int set_raw_sharded(gamma_hip_group* g, int sharded) {
+    if (!g || (sharded != 0 && sharded != 1)) return GAMMA_HIP_EINVAL;
+    std::lock_guard<std::mutex> lk(g->mu);
+    if (g->raw_sharded == (sharded != 0)) return GAMMA_HIP_OK;
+    const RawOps* rops = raw_ops();
+    if (!rops) return gfail(g, GAMMA_HIP_EUNSUPPORTED, "set_raw_placement: sharded raw rows are not built in");
+    if (sharded && g->replicate) return gfail(g, GAMMA_HIP_EINVAL, "set_raw_placement: sharded raw rows cannot go with replicated lists");
+    for (size_t i = 0; i < g->m.size(); i++)
+        if (rops->raw_count(g->m[i]) != 0) return gfail(g, GAMMA_HIP_EINVAL, "set_raw_placement: before any raw row is written");
+    if (sharded) {
+        // every member's (empty) store takes the sparse form now: a member that owns no vector yet answers all the same
+        for (size_t i = 0; i < g->m.size(); i++) {
+            const int rc = gamma_hip_raw_put(g->m[i], 0, nullptr, nullptr);
+            if (rc) return member_fail(g, (int)i, rc);
+        }
+    } else {
+        // back to rows by vector id: the (empty) sparse stores become untyped again
+        for (size_t i = 0; i < g->m.size(); i++) {
+            const int rc = rops->raw_clear(g->m[i]);
+            if (rc) return member_fail(g, (int)i, rc);
+        }
+    }
+    g->raw_sharded = sharded != 0;
+    return GAMMA_HIP_OK;
+}
+
+int raw_sharded(const gamma_hip_group* g) { return g && g->raw_sharded ? 1 : 0; }
+
+int raw_put(gamma_hip_group* g, int64_t n, const int64_t* vids, const float* vecs, int64_t* n_skipped) {
+    if (n_skipped) *n_skipped = 0;
+    if (!g || n < 0 || n > INT32_MAX || (n > 0 && (!vids || !vecs))) return GAMMA_HIP_EINVAL;
+    std::lock_guard<std::mutex> lk(g->mu);
+    if (!g->raw_sharded) return gfail(g, GAMMA_HIP_EINVAL, "raw_put: gamma_hip_group_set_raw_placement(g, 1) first");
+    if (n == 0) return GAMMA_HIP_OK;
+    const int W = (int)g->m.size();
+    const int d = gamma_hip_ivfpq_dim(g->m[0]);
+    if (d <= 0) return gfail(g, GAMMA_HIP_EINVAL, "raw_put: members not initialised");
+    std::vector<int> where(n, -1);
+    std::vector<uint8_t> has(n);
+    for (int i = 0; i < W; i++) {
+        const int rc = gamma_hip_ivfpq_has_vid(g->m[i], vids, (int)n, has.data());
+        if (rc) return member_fail(g, i, rc);
+        for (int64_t j = 0; j < n; j++)
+            if (has[j]) where[j] = i;
+    }
+    int64_t skipped = 0;
+    for (int i = 0; i < W; i++) {
+        std::vector<int64_t> v;
+        std::vector<float> x;
+        for (int64_t j = 0; j < n; j++) {
+            if (where[j] != i) continue;
+            v.push_back(vids[j]);
+            x.insert(x.end(), vecs + (size_t)j * d, vecs + (size_t)(j + 1) * d);
+        }
+        if (v.empty()) continue;
+        const int rc = gamma_hip_raw_put(g->m[i], (int64_t)v.size(), v.data(), x.data());
+        if (rc) return member_fail(g, i, rc);
+    }
+    for (int64_t j = 0; j < n; j++) skipped += where[j] < 0;
+    if (n_skipped) *n_skipped = skipped;
+    return GAMMA_HIP_OK;
+}
+
+}  // namespace gamma_group_ext
 
 extern "C" {
 
@@ -272,7 +357,8 @@ int gamma_hip_group_destroy(gamma_hip_group* g) {
         (void)gamma_hip_synchronize(g->m[i]);
         gamma_hip_group::Member& b = g->mb[i];
         for (GBuf* p : {&b.x, &b.cdis, &b.probe, &b.rdis, &b.rids, &b.all_dis, &b.all_ids, &b.D, &b.I, &b.fx, &b.fcd, &b.fpr, &b.sx,
-                        &b.scd, &b.spr, &b.ex_vals, &b.ex_ids, &b.ex_off, &b.av, &b.ai, &b.ao, &b.cutf, &b.cutall})
+                        &b.scd, &b.spr, &b.ex_vals, &b.ex_ids, &b.ex_off, &b.av, &b.ai, &b.ao, &b.cutf, &b.cutall, &b.bound, &b.bound_pub, &b.bound_peer, &b.rex, &b.all_ex, &b.fbd, &b.sbd,
+                        &b.ex_ex, &b.ae})
             p->release();
         if (b.ev_tie) (void)hipEventDestroy(b.ev_tie);
         if (b.ev_bound) (void)hipEventDestroy(b.ev_bound);
@@ -359,6 +445,7 @@ int gamma_hip_group_set_placement(gamma_hip_group* g, int replicate) {
     std::lock_guard<std::mutex> lk(g->mu);
     if (!g->owner.empty() && g->replicate != (replicate != 0))
         return gfail(g, GAMMA_HIP_EINVAL, "set_placement: before gamma_hip_group_set_owners");
+    if (replicate && g->raw_sharded) return gfail(g, GAMMA_HIP_EINVAL, "set_placement: replicated lists cannot go with sharded raw rows");
     g->replicate = replicate != 0;
     return GAMMA_HIP_OK;
 }
@@ -378,6 +465,9 @@ int gamma_hip_group_ivfpq_add(gamma_hip_group* g, int64_t n, const float* vecs, 
     const int e = g->next_enc++ % W;
     const int cs = gamma_hip_ivfpq_code_size(g->m[e]);
     if (cs <= 0) return gfail(g, GAMMA_HIP_EINVAL, "add: members not initialised");
+    const int d = gamma_hip_ivfpq_dim(g->m[e]);
+    const bool rows = g->raw_sharded && !g->replicate;   // every vector's row goes to the owner of its list, with its keys
+    std::vector<float> gvecs;
     std::vector<int64_t> lno(n);
     std::vector<uint8_t> codes((size_t)n * cs);
     int rc = gamma_hip_ivfpq_encode(g->m[e], n, vecs, lno.data(), codes.data());
@@ -393,9 +483,11 @@ int gamma_hip_group_ivfpq_add(gamma_hip_group* g, int64_t n, const float* vecs, 
         std::vector<int32_t> lists, counts;
         std::vector<int64_t> vids;
         std::vector<uint8_t> gcodes;
+        gvecs.clear();
         for (int64_t i = 0; i < n; i++) {
             const int64_t src = order[i];
             if (!g->replicate && g->owner[lno[src]] != o) continue;
+            if (rows) gvecs.insert(gvecs.end(), vecs + (size_t)src * d, vecs + (size_t)(src + 1) * d);
             if (lists.empty() || lists.back() != (int32_t)lno[src]) {
                 lists.push_back((int32_t)lno[src]);
                 counts.push_back(0);
@@ -411,6 +503,10 @@ int gamma_hip_group_ivfpq_add(gamma_hip_group* g, int64_t n, const float* vecs, 
                 if (rc) return member_fail(g, i, rc);
             }
             break;
+        }
+        if (rows) {   // the rows first: a vector is listed only once its row is in place
+            rc = gamma_hip_raw_put(g->m[o], (int64_t)vids.size(), vids.data(), gvecs.data());
+            if (rc) return member_fail(g, o, rc);
         }
         rc = gamma_hip_ivfpq_add_keys_batch(g->m[o], (int)lists.size(), lists.data(), counts.data(), vids.data(), gcodes.data());
         if (rc) return member_fail(g, o, rc);
@@ -488,9 +584,17 @@ int gamma_hip_group_ivfpq_update(gamma_hip_group* g, int n, const int64_t* vids,
     // belong to different members: per member the entries that concern it, in batch order
     std::vector<std::vector<int>> idx(W);
     std::vector<std::vector<uint8_t>> ops(W);
+    // sharded raw rows: where a vector's row was before the batch and the last entry of the batch that names it
+    struct RowMove { int from, last; };
+    std::unordered_map<int64_t, RowMove> moves;
     for (int j = 0; j < n; j++) {
         auto it = holder.find(vids[j]);
         if (it == holder.end()) continue;   // never added: Update ignores it (:307-311)
+        if (g->raw_sharded) {
+            auto mv = moves.find(vids[j]);
+            if (mv == moves.end()) moves.emplace(vids[j], RowMove{it->second, j});
+            else mv->second.last = j;
+        }
         if (lno[j] < 0 || lno[j] >= nlist) continue;
         const int from = it->second, to = g->owner[lno[j]];
         if (from == to) {
@@ -502,6 +606,34 @@ int gamma_hip_group_ivfpq_update(gamma_hip_group* g, int n, const int64_t* vids,
             idx[to].push_back(j);
             ops[to].push_back(1);     // the owner of the new list appends
             it->second = to;
+        }
+    }
+    if (g->raw_sharded) {
+        // The rows follow their vectors: the last vector a batch gives a vid is put at the member that lists it after the
+        // batch (in place when it stayed, a new row when it moved), then the member that listed it before forgets its row.
+        // Puts before drops, rows before lists: at no point is a listed vector without a row.
+        const gamma_group_ext::RawOps* rops = raw_ops();
+        if (!rops) return gfail(g, GAMMA_HIP_EUNSUPPORTED, "update: sharded raw rows are not built in");
+        const int d = gamma_hip_ivfpq_dim(g->m[e]);
+        std::vector<std::vector<int64_t>> pv(W), dv(W);
+        std::vector<std::vector<float>> px(W);
+        for (int j = 0; j < n; j++) {   // (batch order: the same sequence of puts on every run)
+            auto mv = moves.find(vids[j]);
+            if (mv == moves.end() || mv->second.last != j) continue;
+            const int to = holder[vids[j]];
+            pv[to].push_back(vids[j]);
+            px[to].insert(px[to].end(), vecs + (size_t)j * d, vecs + (size_t)(j + 1) * d);
+            if (mv->second.from != to) dv[mv->second.from].push_back(vids[j]);
+        }
+        for (int i = 0; i < W; i++) {
+            if (pv[i].empty()) continue;
+            rc = gamma_hip_raw_put(g->m[i], (int64_t)pv[i].size(), pv[i].data(), px[i].data());
+            if (rc) return member_fail(g, i, rc);
+        }
+        for (int i = 0; i < W; i++) {
+            if (dv[i].empty()) continue;
+            rc = rops->raw_drop(g->m[i], (int64_t)dv[i].size(), dv[i].data());
+            if (rc) return member_fail(g, i, rc);
         }
     }
     for (int i = 0; i < W; i++) {
@@ -605,6 +737,9 @@ static int group_search(gamma_hip_group* g, const gamma_hip_search_params* p, in
             }
         }
     }
+    // raw rows sharded with the lists: the exact distances of compute_dis are computed where the rows are and travel with the
+    // candidates (has_rank = 0: nothing is computed, nothing more is sent)
+    const bool rs = g->raw_sharded && !g->replicate && pp.has_rank != 0;
     const bool use_rccl = g->transport == 1 && !g->replicate && (int)g->comm.size() == W;
     if (use_rccl) g->rccl_calls++;
     RcclApi* const nccl = use_rccl ? rccl_api() : nullptr;
@@ -781,6 +916,11 @@ static int group_search(gamma_hip_group* g, const gamma_hip_search_params* p, in
             //  in the go / no-go snapshot instead of leaving its peers inside a collective -- ADVICE r4.  An RCCL error AFTER the
             //  barrier is fatal for the group: nothing can call a member back out of ncclGroupEnd)
             hip(b.cutall.ensure((size_t)W * per), "alloc");
+            if (rs) {   // exact distances of the candidates this member is about to send, where it holds the row
+                hip(b.rex.ensure((size_t)nq * R * sizeof(float)), "alloc");
+                hip(b.all_ex.ensure((size_t)W * per * R * sizeof(float)), "alloc");
+                if (rc == GAMMA_HIP_OK) abi(gamma_hip_ivfpq_shard_exact(h, &pp, nq, b.x.as<float>(), b.rids.as<int64_t>(), R, b.rex.as<float>()));
+            }
             hip(hipEventRecord(b.ev_scan, s), "record");
         }
         all_ok = g->bar.arrive(rc == GAMMA_HIP_OK);   // every member's candidate tables are on its stream
@@ -798,11 +938,13 @@ static int group_search(gamma_hip_group* g, const gamma_hip_search_params* p, in
                     ncc(nccl->Send(b.rdis.as<float>() + (size_t)a0 * R, (size_t)(a1 - a0) * R * sizeof(float), kNcclChar, j, g->comm[i], s), "ncclSend");
                     ncc(nccl->Send(b.rids.as<int64_t>() + (size_t)a0 * R, (size_t)(a1 - a0) * R * sizeof(int64_t), kNcclChar, j, g->comm[i], s), "ncclSend");
                     ncc(nccl->Send(b.cutf.as<uint8_t>() + a0, (size_t)(a1 - a0), kNcclChar, j, g->comm[i], s), "ncclSend");
+                    if (rs) ncc(nccl->Send(b.rex.as<float>() + (size_t)a0 * R, (size_t)(a1 - a0) * R * sizeof(float), kNcclChar, j, g->comm[i], s), "ncclSend");
                 }
                 if (nql > 0) {
                     ncc(nccl->Recv(b.all_dis.as<float>() + (size_t)j * per * R, (size_t)nql * R * sizeof(float), kNcclChar, j, g->comm[i], s), "ncclRecv");
                     ncc(nccl->Recv(b.all_ids.as<int64_t>() + (size_t)j * per * R, (size_t)nql * R * sizeof(int64_t), kNcclChar, j, g->comm[i], s), "ncclRecv");
                     ncc(nccl->Recv(b.cutall.as<uint8_t>() + (size_t)j * per, (size_t)nql, kNcclChar, j, g->comm[i], s), "ncclRecv");
+                    if (rs) ncc(nccl->Recv(b.all_ex.as<float>() + (size_t)j * per * R, (size_t)nql * R * sizeof(float), kNcclChar, j, g->comm[i], s), "ncclRecv");
                 }
             }
             ncc(nccl->GroupEnd(), "ncclGroupEnd");
@@ -814,12 +956,19 @@ static int group_search(gamma_hip_group* g, const gamma_hip_search_params* p, in
                                  g->dev[j], (size_t)nql * R * sizeof(float), s), "candidate exchange");
                 hip(copy_between(b.all_ids.as<int64_t>() + (size_t)j * per * R, g->dev[i], g->mb[j].rids.as<int64_t>() + (size_t)q0 * R,
                                  g->dev[j], (size_t)nql * R * sizeof(int64_t), s), "candidate exchange");
+                if (rs)
+                    hip(copy_between(b.all_ex.as<float>() + (size_t)j * per * R, g->dev[i], g->mb[j].rex.as<float>() + (size_t)q0 * R,
+                                     g->dev[j], (size_t)nql * R * sizeof(float), s), "candidate exchange");
             }
             for (int j = 0; j < W && rc == GAMMA_HIP_OK && !nccl; j++)
                 hip(copy_between(b.cutall.as<uint8_t>() + (size_t)j * per, g->dev[i], g->mb[j].cutf.as<uint8_t>() + q0, g->dev[j], (size_t)nql, s),
                     "cut flags");
             if (rc == GAMMA_HIP_OK) abi(gamma_hip_ivfpq_merge_set_shard_flags(h, b.cutall.as<uint8_t>()));
-            if (rc == GAMMA_HIP_OK)
+            if (rc == GAMMA_HIP_OK && rs)
+                abi(gamma_hip_ivfpq_merge_rerank_exact(h, &pp, W, per, b.x.as<float>() + (size_t)q0 * d, k, b.all_dis.as<float>(),
+                                                       b.all_ids.as<int64_t>(), b.all_ex.as<float>(), 0, nql, b.D.as<float>(),
+                                                       b.I.as<int64_t>()));
+            else if (rc == GAMMA_HIP_OK)
                 abi(gamma_hip_ivfpq_merge_rerank(h, &pp, W, per, b.x.as<float>() + (size_t)q0 * d, k, b.all_dis.as<float>(),
                                                  b.all_ids.as<int64_t>(), 0, nql, b.D.as<float>(), b.I.as<int64_t>()));
         }
@@ -849,6 +998,10 @@ static int group_search(gamma_hip_group* g, const gamma_hip_search_params* p, in
                             hip(b.fx.ensure((size_t)nf * d * sizeof(float)), "alloc");
                             hip(b.fcd.ensure((size_t)nf * P * sizeof(float)), "alloc");
                             hip(b.fpr.ensure((size_t)nf * P * sizeof(int32_t)), "alloc");
+                            if (rs) hip(b.fbd.ensure((size_t)nf * sizeof(float)), "alloc");
+                            // (sharded rows: the flagged queries' reduced bounds of the scan -- only exported entries within
+                            //  them can be members of the recall_num-heap, only those get an exact distance)
+                            if (rc == GAMMA_HIP_OK && rs) abi(gamma_hip_gather_rows(h, b.bound.as<float>() + q0, 1, lists[o] + f0, nf, b.fbd.p));
                             if (rc == GAMMA_HIP_OK) {
                                 abi(gamma_hip_gather_rows(h, b.x.as<float>() + (size_t)q0 * d, d, lists[o] + f0, nf, b.fx.p));
                                 abi(gamma_hip_gather_rows(h, b.cdis.as<float>() + (size_t)q0 * P, P, lists[o] + f0, nf, b.fcd.p));
@@ -862,12 +1015,14 @@ static int group_search(gamma_hip_group* g, const gamma_hip_search_params* p, in
                         hip(b.scd.ensure((size_t)nf * P * sizeof(float)), "alloc");
                         hip(b.spr.ensure((size_t)nf * P * sizeof(int32_t)), "alloc");
                         hip(b.ex_off.ensure((size_t)nf * (P + 1) * sizeof(int32_t)), "alloc");
+                        if (rs) hip(b.sbd.ensure((size_t)nf * sizeof(float)), "alloc");
                         rowmax[i] = 0;
                         if (ok2 && rc == GAMMA_HIP_OK) {
                             if (i != o) hip(hipStreamWaitEvent(s, ob.ev_tie, 0), "wait");
                             hip(copy_between(b.sx.p, g->dev[i], ob.fx.p, g->dev[o], (size_t)nf * d * sizeof(float), s), "tie inputs");
                             hip(copy_between(b.scd.p, g->dev[i], ob.fcd.p, g->dev[o], (size_t)nf * P * sizeof(float), s), "tie inputs");
                             hip(copy_between(b.spr.p, g->dev[i], ob.fpr.p, g->dev[o], (size_t)nf * P * sizeof(int32_t), s), "tie inputs");
+                            if (rs) hip(copy_between(b.sbd.p, g->dev[i], ob.fbd.p, g->dev[o], (size_t)nf * sizeof(float), s), "tie inputs");
                             // how long this member's export rows get: the exports of all members share one row stride
                             int64_t mine = 0;
                             if (rc == GAMMA_HIP_OK) abi(gamma_hip_ivfpq_shard_export_rows(h, &pp, nf, b.spr.as<int32_t>(), &mine));
@@ -881,13 +1036,21 @@ static int group_search(gamma_hip_group* g, const gamma_hip_search_params* p, in
                         if (ok2 && rc == GAMMA_HIP_OK)
                             abi(gamma_hip_ivfpq_shard_export(h, &pp, nf, b.sx.as<float>(), b.scd.as<float>(), b.spr.as<int32_t>(), stride,
                                                              b.ex_vals.as<float>(), b.ex_ids.as<int64_t>(), b.ex_off.as<int32_t>()));
+                        if (rs) hip(b.ex_ex.ensure((size_t)nf * stride * sizeof(float)), "alloc");
+                        if (rs && ok2 && rc == GAMMA_HIP_OK)
+                            abi(gamma_hip_ivfpq_shard_export_exact(h, &pp, nf, b.sx.as<float>(), b.ex_vals.as<float>(), b.ex_ids.as<int64_t>(),
+                                                                   b.ex_off.as<int32_t>(), stride, b.sbd.as<float>(), b.ex_ex.as<float>()));
                         hip(hipStreamSynchronize(s), "sync");
                         ok2 = g->bar.arrive(rc == GAMMA_HIP_OK);   // every member's export is complete
                         if (i == o && ok2) {
                             hip(b.av.ensure((size_t)W * nf * stride * sizeof(float)), "alloc");
                             hip(b.ai.ensure((size_t)W * nf * stride * sizeof(int64_t)), "alloc");
                             hip(b.ao.ensure((size_t)W * nf * (P + 1) * sizeof(int32_t)), "alloc");
+                            if (rs) hip(b.ae.ensure((size_t)W * nf * stride * sizeof(float)), "alloc");
                             for (int j = 0; j < W && rc == GAMMA_HIP_OK; j++) {
+                                if (rs)
+                                    hip(copy_between(b.ae.as<float>() + (size_t)j * nf * stride, g->dev[i], g->mb[j].ex_ex.p, g->dev[j],
+                                                     (size_t)nf * stride * sizeof(float), s), "exports");
                                 hip(copy_between(b.av.as<float>() + (size_t)j * nf * stride, g->dev[i], g->mb[j].ex_vals.p, g->dev[j],
                                                  (size_t)nf * stride * sizeof(float), s), "exports");
                                 hip(copy_between(b.ai.as<int64_t>() + (size_t)j * nf * stride, g->dev[i], g->mb[j].ex_ids.p, g->dev[j],
@@ -895,7 +1058,11 @@ static int group_search(gamma_hip_group* g, const gamma_hip_search_params* p, in
                                 hip(copy_between(b.ao.as<int32_t>() + (size_t)j * nf * (P + 1), g->dev[i], g->mb[j].ex_off.p, g->dev[j],
                                                  (size_t)nf * (P + 1) * sizeof(int32_t), s), "exports");
                             }
-                            if (rc == GAMMA_HIP_OK)
+                            if (rc == GAMMA_HIP_OK && rs)
+                                abi(gamma_hip_ivfpq_merge_replay_exact(h, &pp, W, nf, b.x.as<float>() + (size_t)q0 * d, stride, b.av.as<float>(),
+                                                                       b.ai.as<int64_t>(), b.ao.as<int32_t>(), b.ae.as<float>(), k, lists[o] + f0,
+                                                                       b.D.as<float>(), b.I.as<int64_t>()));
+                            else if (rc == GAMMA_HIP_OK)
                                 abi(gamma_hip_ivfpq_merge_replay(h, &pp, W, nf, b.x.as<float>() + (size_t)q0 * d, stride, b.av.as<float>(),
                                                                  b.ai.as<int64_t>(), b.ao.as<int32_t>(), k, lists[o] + f0, b.D.as<float>(),
                                                                  b.I.as<int64_t>()));

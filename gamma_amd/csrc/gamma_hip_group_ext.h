@@ -1,0 +1,26 @@
+// gamma_hip_group_ext.h -- the seam between gamma_hip_group.cpp and gamma_hip_group_rawshard.cpp.
+//
+// gamma_hip_group.cpp is built in two settings: into libgamma_hip.so, and -- by the sanitizer builds of the tests -- against a
+// CPU stub of the C ABI that predates the sparse raw store's drop / count entries.  It therefore names none of them: the
+// entries the sharded raw placement needs reach it through the table below, registered at static-initialisation time by
+// gamma_hip_group_rawshard.cpp, which also defines the public gamma_hip_group_*raw* entries on top of the functions declared
+// here.  A build without that file has no table, and the sharded raw placement is refused with a message.
+#pragma once
+#include <stdint.h>
+
+#include "../../include/gamma_hip.h"
+
+namespace gamma_group_ext {
+
+struct RawOps {
+    int (*raw_drop)(gamma_hip_index*, int64_t, const int64_t*);
+    int64_t (*raw_count)(gamma_hip_index*);
+    int (*raw_clear)(gamma_hip_index*);
+};
+int register_raw_ops(const RawOps* ops);   // returns 1 (a value for a static initialiser)
+
+int set_raw_sharded(gamma_hip_group* g, int sharded);
+int raw_sharded(const gamma_hip_group* g);
+int raw_put(gamma_hip_group* g, int64_t n, const int64_t* vids, const float* vecs, int64_t* n_skipped);
+
+}  // namespace gamma_group_ext

@@ -20,6 +20,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 #include "kernels.h"
@@ -199,6 +200,10 @@ struct gamma_hip_index {
     std::vector<int32_t> h_raw_slot;
     int32_t* d_raw_slot = nullptr;
     int64_t raw_slot_cap = 0;
+    // a sparse store's rows can be rewritten in place, dropped (gamma_hip_raw_drop) and their rows reused: nraw = rows handed
+    // out so far, raw_live of them hold a vector, raw_free lists the others (reused, last freed first, before the store grows)
+    int64_t raw_live = 0;
+    std::vector<int32_t> raw_free;
     // The store grows IN PLACE where the runtime offers virtual memory management: one address range reserved up
     // front, physical chunks mapped behind the rows as they come -- no copy, no second allocation, no wait for the
     // searches in flight (the reference keeps 500 000-vector segments for the same reason, vector/memory_raw_vector.cc:

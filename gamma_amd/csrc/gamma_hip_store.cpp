@@ -781,42 +781,180 @@ int gamma_hip_raw_append(gamma_hip_index* h, int64_t n, const float* vecs) {
     return GAMMA_HIP_OK;
 }
 
+// the device's vid -> row table reaches vector id `hi`: a larger array and the whole mirror when it does not (rare: the
+// table grows by half; readers are drained first), nothing otherwise -- single entries go through k_raw_slot_scatter
+static int raw_slot_reserve(H* h, int64_t hi) {
+    if (hi < h->raw_slot_cap) return GAMMA_HIP_OK;
+    const int64_t ncap = std::max<int64_t>(hi + 1 + (hi + 1) / 2, 1 << 16);
+    int32_t* np = nullptr;
+    if (h->wl) GH_CHECK(h, h->wl->exclusive());
+    GH_CHECK(h, hipMalloc((void**)&np, (size_t)ncap * sizeof(int32_t)));
+    hipError_t e = hipMemsetAsync(np, 0xff, (size_t)ncap * sizeof(int32_t), h->wstream);
+    if (e == hipSuccess && !h->h_raw_slot.empty())
+        e = hipMemcpyAsync(np, h->h_raw_slot.data(), h->h_raw_slot.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->wstream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->wstream);
+    if (e != hipSuccess) {
+        (void)hipFree(np);
+        GH_CHECK(h, e);
+    }
+    if (h->d_raw_slot) GH_CHECK(h, hipFree(h->d_raw_slot));
+    h->d_raw_slot = np;
+    h->raw_slot_cap = ncap;
+    return GAMMA_HIP_OK;
+}
+
+// Rows of a sparse store.  A vector the store holds keeps its row (rewritten in place), a new one takes a freed row before
+// the store grows.  What a search in flight may read is never written under it: new rows at the end of the store are
+// reachable by no search yet (the caller lists a vector after its row is in place, and this call returns with the writer
+// stream drained); a rewrite in place and the reuse of a freed row wait for the searches in flight first (exclusive()) --
+// a freed row belonged to a vector this handle no longer lists, which only a search enqueued before it left can still reach.
+// On the writer stream the rows go before the table entries that point at them.
 int gamma_hip_raw_put(gamma_hip_index* h, int64_t n, const int64_t* vids, const float* vecs) {
     if (!h || n < 0 || (n > 0 && (!vids || !vecs))) return GAMMA_HIP_EINVAL;
     WriteLock lk(h);
     if (h->raw_d <= 0) return fail(h, GAMMA_HIP_EINVAL, "raw store not initialised");
     if (!h->raw_sparse && h->nraw > 0) return fail(h, GAMMA_HIP_EINVAL, "raw_put on a store that holds rows by vector id");
-    if (n == 0) return GAMMA_HIP_OK;
-    int64_t lo = INT64_MAX, hi = -1;
+    if (n == 0) {   // the first call turns the empty store into the sparse form, rows or not (a shard that owns no vector yet)
+        if (!h->raw_sparse) {
+            GH_CHECK(h, hipSetDevice(h->device));
+            GH_TRY(raw_reserve(h, 1));
+            h->raw_sparse = true;
+        }
+        return GAMMA_HIP_OK;
+    }
+    int64_t hi = -1;
     for (int64_t i = 0; i < n; i++) {
         if (vids[i] < 0 || vids[i] >= ((int64_t)1 << 31)) return fail(h, GAMMA_HIP_EINVAL, "raw_put: vector id out of range");
-        lo = std::min(lo, vids[i]);
         hi = std::max(hi, vids[i]);
     }
-    h->raw_sparse = true;
-    GH_CHECK(h, hipSetDevice(h->device));
-    GH_TRY(raw_reserve(h, h->nraw + n));
-    GH_CHECK(h, hipMemcpyAsync(h->d_raw + h->nraw * h->raw_d, vecs, (size_t)n * h->raw_d * sizeof(float),
-                               hipMemcpyHostToDevice, h->wstream));
-    if ((int64_t)h->h_raw_slot.size() <= hi) h->h_raw_slot.resize((size_t)hi + 1, -1);
-    for (int64_t i = 0; i < n; i++) h->h_raw_slot[vids[i]] = (int32_t)(h->nraw + i);
-    if (hi >= h->raw_slot_cap) {   // the device map grows: a new array, the whole mirror (readers are drained first)
-        const int64_t ncap = std::max<int64_t>(hi + 1 + (hi + 1) / 2, 1 << 16);
-        int32_t* np = nullptr;
-        if (h->wl) GH_CHECK(h, h->wl->exclusive());
-        GH_CHECK(h, hipMalloc((void**)&np, (size_t)ncap * sizeof(int32_t)));
-        GH_CHECK(h, hipMemsetAsync(np, 0xff, (size_t)ncap * sizeof(int32_t), h->wstream));
-        GH_CHECK(h, hipMemcpyAsync(np, h->h_raw_slot.data(), h->h_raw_slot.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->wstream));
-        GH_CHECK(h, hipStreamSynchronize(h->wstream));
-        if (h->d_raw_slot) GH_CHECK(h, hipFree(h->d_raw_slot));
-        h->d_raw_slot = np;
-        h->raw_slot_cap = ncap;
-    } else {
-        GH_CHECK(h, hipMemcpyAsync(h->d_raw_slot + lo, h->h_raw_slot.data() + lo, (size_t)(hi - lo + 1) * sizeof(int32_t),
-                                   hipMemcpyHostToDevice, h->wstream));
+    // the row of every entry; nothing of the handle changes before the device memory is there
+    std::vector<int32_t> pairs((size_t)n * 2);
+    std::unordered_map<int64_t, int64_t> seen;   // vid -> its latest entry of this batch (the last one named wins)
+    seen.reserve((size_t)n * 2);
+    const int64_t nfree = (int64_t)h->raw_free.size();
+    int64_t used_free = 0, grow = 0, fresh = 0;
+    bool touches_old = false, in_order = true;
+    for (int64_t i = 0; i < n; i++) {
+        const int64_t v = vids[i];
+        int32_t row;
+        auto it = seen.find(v);
+        if (it != seen.end()) {
+            row = pairs[2 * it->second + 1];
+            pairs[2 * it->second] = pairs[2 * it->second + 1] = -1;
+            it->second = i;
+            in_order = false;
+        } else {
+            const int32_t held = (size_t)v < h->h_raw_slot.size() ? h->h_raw_slot[v] : -1;
+            if (held >= 0) {
+                row = held;
+                touches_old = true;
+            } else {
+                fresh++;
+                if (used_free < nfree) {
+                    row = h->raw_free[nfree - 1 - used_free++];
+                    touches_old = true;
+                } else {
+                    if (h->nraw + grow >= ((int64_t)1 << 31) - 1) return fail(h, GAMMA_HIP_EFULL, "raw_put: more than 2^31 rows");
+                    row = (int32_t)(h->nraw + grow++);
+                }
+            }
+            seen.emplace(v, i);
+        }
+        pairs[2 * i] = (int32_t)v;
+        pairs[2 * i + 1] = row;
     }
+    in_order = in_order && !touches_old;   // rows nraw, nraw + 1, ..: the batch is the tail of the store as it stands
+    GH_CHECK(h, hipSetDevice(h->device));
+    if (touches_old) GH_CHECK(h, lk.exclusive());
+    GH_TRY(raw_reserve(h, h->nraw + grow));
+    GH_TRY(raw_slot_reserve(h, hi));
+    GH_CHECK(h, h->we_chk.ensure((size_t)n * 2 * sizeof(int32_t)));
+    if (!in_order) GH_CHECK(h, h->we_stage.ensure((size_t)n * h->raw_d * sizeof(float)));
+    h->raw_sparse = true;
+    GH_CHECK(h, hipMemcpyAsync(h->we_chk.p, pairs.data(), (size_t)n * 2 * sizeof(int32_t), hipMemcpyHostToDevice, h->wstream));
+    if (in_order) {
+        GH_CHECK(h, hipMemcpyAsync(h->d_raw + h->nraw * h->raw_d, vecs, (size_t)n * h->raw_d * sizeof(float), hipMemcpyHostToDevice,
+                                   h->wstream));
+    } else {
+        GH_CHECK(h, hipMemcpyAsync(h->we_stage.p, vecs, (size_t)n * h->raw_d * sizeof(float), hipMemcpyHostToDevice, h->wstream));
+        gh::launch_raw_rows_scatter(h->wstream, h->we_stage.as<float>(), h->we_chk.as<int32_t>(), n, h->raw_d, h->d_raw, h->raw_cap);
+    }
+    gh::launch_raw_slot_scatter(h->wstream, h->we_chk.as<int32_t>(), n, h->d_raw_slot, h->raw_slot_cap);
+    GH_CHECK(h, hipGetLastError());
     GH_CHECK(h, hipStreamSynchronize(h->wstream));
-    h->nraw += n;
+    if ((int64_t)h->h_raw_slot.size() <= hi) h->h_raw_slot.resize((size_t)hi + 1, -1);
+    for (int64_t i = 0; i < n; i++)
+        if (pairs[2 * i] >= 0) h->h_raw_slot[pairs[2 * i]] = pairs[2 * i + 1];
+    h->raw_free.resize((size_t)(nfree - used_free));
+    h->nraw += grow;
+    h->raw_live += fresh;
+    lk.shared();
+    return GAMMA_HIP_OK;
+}
+
+// the store forgets rows: their table entries go to -1 (one 4-byte store each: a search beside it reads the old row, intact,
+// or none), the rows to the free list
+int gamma_hip_raw_drop(gamma_hip_index* h, int64_t n, const int64_t* vids) {
+    if (!h || n < 0 || (n > 0 && !vids)) return GAMMA_HIP_EINVAL;
+    WriteLock lk(h);
+    if (!h->raw_sparse) {
+        if (h->nraw > 0) return fail(h, GAMMA_HIP_EINVAL, "raw_drop on a store that holds rows by vector id");
+        return GAMMA_HIP_OK;   // empty: nothing to forget
+    }
+    std::vector<int32_t> pairs;
+    for (int64_t i = 0; i < n; i++) {
+        const int64_t v = vids[i];
+        if (v < 0 || (size_t)v >= h->h_raw_slot.size() || h->h_raw_slot[v] < 0) continue;
+        pairs.push_back((int32_t)v);
+        pairs.push_back(-1);
+        h->raw_free.push_back(h->h_raw_slot[v]);
+        h->h_raw_slot[v] = -1;
+        h->raw_live--;
+    }
+    if (pairs.empty()) return GAMMA_HIP_OK;
+    GH_CHECK(h, hipSetDevice(h->device));
+    GH_CHECK(h, h->we_chk.ensure(pairs.size() * sizeof(int32_t)));
+    GH_CHECK(h, hipMemcpyAsync(h->we_chk.p, pairs.data(), pairs.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->wstream));
+    gh::launch_raw_slot_scatter(h->wstream, h->we_chk.as<int32_t>(), (int64_t)pairs.size() / 2, h->d_raw_slot, h->raw_slot_cap);
+    GH_CHECK(h, hipGetLastError());
+    GH_CHECK(h, hipStreamSynchronize(h->wstream));
+    return GAMMA_HIP_OK;
+}
+
+// back to the state after gamma_hip_raw_init: no rows, no table, neither dense nor sparse yet
+int gamma_hip_raw_clear(gamma_hip_index* h) {
+    if (!h) return GAMMA_HIP_EINVAL;
+    WriteLock lk(h);
+    GH_CHECK(h, hipSetDevice(h->device));
+    GH_CHECK(h, lk.exclusive());   // the rows are given back: no search may be reading them
+    if (h->raw_vmm) {
+        h->raw_vm.unmap_all();   // (the address range stays reserved)
+        if (h->raw_vm.tainted) {   // unmapped without a fence: these addresses are not mapped again
+            h->vm_retired.push_back(std::move(h->raw_vm));
+            h->raw_vm = VmRange();
+            h->raw_vmm = false;
+            h->d_raw = nullptr;
+        }
+    } else if (h->d_raw) {
+        GH_CHECK(h, hipFree(h->d_raw));
+        h->d_raw = nullptr;
+    }
+    if (h->d_raw_slot) GH_CHECK(h, hipFree(h->d_raw_slot));
+    h->d_raw_slot = nullptr;
+    h->raw_slot_cap = 0;
+    std::vector<int32_t>().swap(h->h_raw_slot);
+    std::vector<int32_t>().swap(h->raw_free);
+    h->nraw = h->raw_cap = h->raw_live = 0;
+    h->raw_sparse = false;
+    return GAMMA_HIP_OK;
+}
+
+int gamma_hip_raw_sparse_stats(gamma_hip_index* h, int64_t* out3) {
+    if (!h || !out3) return GAMMA_HIP_EINVAL;
+    std::lock_guard<std::mutex> g(h->mu);
+    out3[0] = h->raw_sparse ? h->raw_live : 0;
+    out3[1] = h->raw_sparse ? h->nraw : 0;
+    out3[2] = (int64_t)h->raw_free.size();
     return GAMMA_HIP_OK;
 }
 
@@ -882,7 +1020,7 @@ int gamma_hip_raw_gets(gamma_hip_index* h, int64_t n, const int64_t* vids, float
     return GAMMA_HIP_OK;
 }
 
-int64_t gamma_hip_raw_count(gamma_hip_index* h) { return h ? h->nraw : -1; }
+int64_t gamma_hip_raw_count(gamma_hip_index* h) { return h ? (h->raw_sparse ? h->raw_live : h->nraw) : -1; }
 
 int gamma_hip_raw_stats(gamma_hip_index* h, int64_t* out4) {
     if (!h || !out4) return GAMMA_HIP_EINVAL;

@@ -439,6 +439,9 @@ void launch_take_ids(hipStream_t s, const int* pos, const int64_t* src_ids, int6
 void launch_bitmap_set(hipStream_t s, uint8_t* bm, const int64_t* docids, int64_t n, int64_t nbits,
                        int value);
 void launch_mark_moved(hipStream_t s, int64_t* ids, int64_t pos);
+// sparse raw store: pairs [n][2] = (vector id, row); the vid -> row table's entries, and the staged rows into their rows
+void launch_raw_slot_scatter(hipStream_t s, const int32_t* pairs, int64_t n, int32_t* tab, int64_t ntab);
+void launch_raw_rows_scatter(hipStream_t s, const float* stage, const int32_t* pairs, int64_t n, int d, float* raw, int64_t cap);
 void launch_list_checksum(hipStream_t s, const uint8_t* codes, const int64_t* ids, const int64_t* off, const int* len, int nlist,
                           int M, int max_len, unsigned long long* out);
 void launch_repack_lists(hipStream_t s, const uint8_t* oc, const int64_t* oi, uint8_t* nc, int64_t* ni,

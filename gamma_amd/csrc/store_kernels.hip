@@ -101,6 +101,46 @@ void launch_mark_moved(hipStream_t s, int64_t* ids, int64_t pos) {
     hipLaunchKernelGGL(k_mark_moved, dim3(1), dim3(64), 0, s, ids, pos);
 }
 
+// Sparse raw store (gamma_hip_raw_put / _drop): pairs[i] = (vector id, row) -- the entry of the vid -> row table is
+// rewritten (row -1: the store forgets the vector); a pair with vid < 0 is skipped.  4 bytes per touched vid instead of
+// an upload of the table's span.
+__global__ __launch_bounds__(256) void k_raw_slot_scatter(const int2* __restrict__ pairs, int64_t n, int32_t* __restrict__ tab,
+                                                          int64_t ntab) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int2 pr = pairs[i];
+    if (pr.x >= 0 && (int64_t)pr.x < ntab) tab[pr.x] = pr.y;
+}
+void launch_raw_slot_scatter(hipStream_t s, const int32_t* pairs, int64_t n, int32_t* tab, int64_t ntab) {
+    if (n <= 0 || ntab <= 0) return;
+    hipLaunchKernelGGL(k_raw_slot_scatter, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const int2*>(pairs), n,
+                       tab, ntab);
+}
+// ... and the uploaded rows stage[i] into their rows raw[pairs[i].y] (fresh, reused or rewritten in place; a pair with a
+// negative row is skipped, rows >= cap are never written).  V = float4 when d % 4 == 0 (rows are 16-byte aligned then).
+template <typename V>
+__global__ __launch_bounds__(256) void k_raw_rows_scatter(const V* __restrict__ stage, const int2* __restrict__ pairs, int64_t n,
+                                                          int dv, V* __restrict__ raw, int64_t cap) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n * dv) return;
+    const int64_t i = t / dv;
+    const int c = (int)(t - i * dv);
+    const int row = pairs[i].y;
+    if (row >= 0 && (int64_t)row < cap) raw[(int64_t)row * dv + c] = stage[t];
+}
+void launch_raw_rows_scatter(hipStream_t s, const float* stage, const int32_t* pairs, int64_t n, int d, float* raw, int64_t cap) {
+    if (n <= 0 || d <= 0 || cap <= 0) return;
+    const int2* pr = reinterpret_cast<const int2*>(pairs);
+    if ((d & 3) == 0) {
+        const int64_t tot = n * (d >> 2);
+        hipLaunchKernelGGL((k_raw_rows_scatter<float4>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s,
+                           reinterpret_cast<const float4*>(stage), pr, n, d >> 2, reinterpret_cast<float4*>(raw), cap);
+    } else {
+        const int64_t tot = n * d;
+        hipLaunchKernelGGL((k_raw_rows_scatter<float>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, stage, pr, n, d, raw, cap);
+    }
+}
+
 // Arena repack (gamma_hip_store.cpp, arena_repack): every list's live entries move from (old arrays, old offset)
 // to (new arrays, new offset).  grid = (nlist, chunks); the code bytes move as dwords when M % 4 == 0.
 __global__ __launch_bounds__(256) void k_repack_lists(const uint8_t* __restrict__ oc, const int64_t* __restrict__ oi,

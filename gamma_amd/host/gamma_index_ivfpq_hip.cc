@@ -91,6 +91,14 @@ int HIPIVFPQModelParams::Parse(const char *str) {
     }
     replicate = !strcasecmp("replicate", plc.c_str());
   }
+  std::string rpl;
+  if (!jp.GetString("raw_placement", rpl)) {   // several devices, lists sharded: "replicated" (the default) | "sharded"
+    if (strcasecmp("replicated", rpl.c_str()) && strcasecmp("sharded", rpl.c_str())) {
+      HLOG("invalid raw_placement = %s", rpl.c_str());
+      return -1;
+    }
+    raw_sharded = !strcasecmp("sharded", rpl.c_str());
+  }
   if (!jp.GetInt("bucket_init_size", v)) {
     if (v < -1) return -1;
     if (v > 0) bucket_init_size = v;
@@ -124,7 +132,18 @@ std::vector<ListsInitEntry> &ListsInits() {
   static std::vector<ListsInitEntry> v;
   return v;
 }
+const HIPRawShardOps *&RawShardOps() {
+  static const HIPRawShardOps *ops = nullptr;
+  return ops;
+}
 }  // namespace
+
+int RegisterHIPRawShard(const HIPRawShardOps *ops) {
+  RawShardOps() = ops;
+  return 0;
+}
+
+const HIPRawShardOps *FindHIPRawShard() { return RawShardOps(); }
 
 int RegisterHIPListsInit(int nbits, HIPListsInitFn fn) {
   ListsInits().push_back({nbits, fn});
@@ -203,6 +222,14 @@ int GammaIVFPQHIPIndex::Init(const std::string &model_parameters, int indexing_s
   if (pa.devices.size() > 1 && pa.device_filters) {
     HLOG("device_filters with several devices is not supported (the columns live on one handle)");
     return -2;
+  }
+  if (pa.raw_sharded) {
+    rawshard_ = FindHIPRawShard();
+    if (pa.devices.size() < 2 || pa.replicate || !rawshard_) {
+      HLOG("raw_placement = sharded needs several devices and placement = shard%s",
+           rawshard_ ? "" : " (and this build of the plugin carries no sharded raw rows)");
+      return -2;
+    }
   }
   if (OpenDevices(pa.devices, pa.replicate)) return -1;
   int rc = ForAll([&](gamma_hip_index *m) {
@@ -319,8 +346,12 @@ bool GammaIVFPQHIPIndex::Add(int n, const uint8_t *vec) {
   // same rows at the same time (EnsureRaw) rewrites identical bytes instead of appending them twice.
   const float *v = reinterpret_cast<const float *>(vec);
   const int64_t end = (int64_t)indexed_vec_count_ + n;
-  if (EnsureRaw(indexed_vec_count_)) return false;
-  {
+  if (rawshard_) {
+    // sharded rows: the group puts every row beside its keys at the owner of its list (gamma_hip_group_ivfpq_add below);
+    // the first Add after training retires member 0's mirror of the untrained model
+    if (ShardRows()) return false;
+  } else {
+    if (EnsureRaw(indexed_vec_count_)) return false;
     std::lock_guard<std::mutex> g(raw_mu_);
     if (ForAll([&](gamma_hip_index *m) { return gamma_hip_raw_write(m, indexed_vec_count_, n, v); })) return false;
     raw_uploaded_ = std::max(raw_uploaded_, end);
@@ -352,7 +383,12 @@ int GammaIVFPQHIPIndex::Update(const std::vector<int64_t> &ids, const std::vecto
   }
   {
     std::lock_guard<std::mutex> g(raw_mu_);   // rows the mirror has not reached yet are skipped: EnsureRaw brings them
-    if (ForAll([&](gamma_hip_index *m) { return gamma_hip_raw_update_batch(m, (int64_t)n, ids.data(), x.data()); })) return -1;
+    if (rawshard_) {
+      // sharded rows: the group's Update has rewritten or moved them with their vectors; before that only member 0 mirrors
+      if (!rows_sharded_ && gamma_hip_raw_update_batch(h_, (int64_t)n, ids.data(), x.data())) return -1;
+    } else if (ForAll([&](gamma_hip_index *m) { return gamma_hip_raw_update_batch(m, (int64_t)n, ids.data(), x.data()); })) {
+      return -1;
+    }
   }
   if (grp_) gamma_hip_group_ivfpq_compact_if_need(grp_);
   else gamma_hip_ivfpq_compact_if_need(h_);   // gamma_index_ivfpq.cc:420
@@ -407,7 +443,17 @@ int GammaIVFPQHIPIndex::Search(RetrievalContext *retrieval_context, int n, const
     FillRangeFilters(cond, p, rf);
   const float *xq = reinterpret_cast<const float *>(x);
   int rc;
-  if ((cond && cond->brute_force_search) || !is_trained_) {
+  if (((cond && cond->brute_force_search) || !is_trained_) && rawshard_) {
+    // sharded rows: member 0 mirrors the store until the first Add after training; the mirror cannot go away under the
+    // flat search (raw_mu_ through the call).  Afterwards no device holds every row: refused, never a wrong answer.
+    std::lock_guard<std::mutex> g(raw_mu_);
+    if (rows_sharded_) {
+      HLOG("brute_force_search is not available once the raw vectors are sharded (raw_placement = sharded)");
+      return -3;
+    }
+    if (EnsureRawLocked((int64_t)vector_->MetaInfo()->Size())) return -1;
+    rc = gamma_hip_flat_search(h_, &p, n, xq, k, distances, ids);
+  } else if ((cond && cond->brute_force_search) || !is_trained_) {
     if (EnsureRaw((int64_t)vector_->MetaInfo()->Size())) return -1;
     rc = gamma_hip_flat_search(h_, &p, n, xq, k, distances, ids);   // gamma_index_ivfpq.cc:529-537
   } else {
@@ -495,6 +541,11 @@ void GammaIVFPQHIPIndex::PerfLabels(GammaSearchCondition *cond) {
 // "read the watermark, copy, advance it" one step, and the rows go to their own positions.
 int GammaIVFPQHIPIndex::EnsureRaw(int64_t upto) {
   std::lock_guard<std::mutex> g(raw_mu_);
+  return EnsureRawLocked(upto);
+}
+
+int GammaIVFPQHIPIndex::EnsureRawLocked(int64_t upto) {
+  if (rows_sharded_) return 0;   // the group holds the rows
   const int64_t step = 65536;
   for (int64_t i0 = raw_uploaded_; i0 < upto; i0 += step) {
     const int64_t nb = std::min(step, upto - i0);
@@ -504,8 +555,48 @@ int GammaIVFPQHIPIndex::EnsureRaw(int64_t upto) {
     if (vector_->Gets(vids, sv)) return -1;
     std::vector<float> buf((size_t)nb * d_);
     for (int64_t i = 0; i < nb; i++) memcpy(&buf[(size_t)i * d_], sv.Get((int)i), sizeof(float) * d_);
-    if (ForAll([&](gamma_hip_index *m) { return gamma_hip_raw_write(m, i0, nb, buf.data()); })) return -1;
+    // ("raw_placement": "sharded": the mirror of the untrained model lives on member 0 alone -- brute force runs there)
+    if (rawshard_ ? gamma_hip_raw_write(h_, i0, nb, buf.data())
+                  : ForAll([&](gamma_hip_index *m) { return gamma_hip_raw_write(m, i0, nb, buf.data()); }))
+      return -1;
     raw_uploaded_ = i0 + nb;
+  }
+  return 0;
+}
+
+// "raw_placement": "sharded", once: member 0's mirror by vid is cleared and the group switches to sharded rows
+int GammaIVFPQHIPIndex::ShardRows() {
+  std::lock_guard<std::mutex> g(raw_mu_);
+  if (rows_sharded_) return 0;
+  int rc = rawshard_->raw_clear(h_);
+  if (!rc) rc = rawshard_->set_raw_placement(grp_, 1);
+  if (rc) {
+    HLOG("cannot shard the raw vectors: %s (%s)", gamma_hip_strerror(rc), gamma_hip_group_last_error(grp_));
+    return -1;
+  }
+  raw_uploaded_ = 0;
+  rows_sharded_ = true;
+  return 0;
+}
+
+// after a Load: every owner gets the rows of its lists from the engine's vector store, in bounded batches (vids nobody
+// lists -- superseded by an Update before the dump -- are skipped by the group)
+int GammaIVFPQHIPIndex::PutRowsFromStore(int64_t upto) {
+  const int64_t step = 65536;
+  for (int64_t i0 = 0; i0 < upto; i0 += step) {
+    const int64_t nb = std::min(step, upto - i0);
+    std::vector<int64_t> vids(nb);
+    for (int64_t i = 0; i < nb; i++) vids[i] = i0 + i;
+    ScopeVectors sv;
+    if (vector_->Gets(vids, sv)) return -1;
+    std::vector<float> buf((size_t)nb * d_);
+    for (int64_t i = 0; i < nb; i++) memcpy(&buf[(size_t)i * d_], sv.Get((int)i), sizeof(float) * d_);
+    int64_t skipped = 0;
+    const int rc = rawshard_->group_raw_put(grp_, nb, vids.data(), buf.data(), &skipped);
+    if (rc) {
+      HLOG("cannot restore the raw vectors: %s (%s)", gamma_hip_strerror(rc), gamma_hip_group_last_error(grp_));
+      return -1;
+    }
   }
   return 0;
 }
@@ -639,7 +730,12 @@ int GammaIVFPQHIPIndex::Load(const std::string &dir) {
   }
   indexed_vec_count_ = (int)count;
   // raw vectors for the re-rank come back from the engine's vector store
-  if (EnsureRaw(std::min<int64_t>(indexed_vec_count_, (int64_t)vector_->MetaInfo()->Size()))) return -1;
+  const int64_t rows = std::min<int64_t>(indexed_vec_count_, (int64_t)vector_->MetaInfo()->Size());
+  if (rawshard_) {
+    if (ShardRows() || PutRowsFromStore(rows)) return -1;
+  } else if (EnsureRaw(rows)) {
+    return -1;
+  }
   return indexed_vec_count_;
 }
 

@@ -54,6 +54,18 @@ typedef int (*HIPListsInitFn)(gamma_hip_index *h, int d, int nlist, int M, int m
 int RegisterHIPListsInit(int nbits, HIPListsInitFn fn);
 HIPListsInitFn FindHIPListsInit(int nbits);
 
+// "raw_placement": "sharded" (several devices, lists sharded): every raw row once, on the device that owns its list.  The ABI
+// entries that takes beyond those of the replicated mirror -- the group's placement switch and row routing, the store's clear --
+// are registered by gamma_index_ivfpq_rawshard_hip.cc at static-initialisation time (the idiom of RegisterHIPListsInit):
+// builds of the plugin against a C ABI without them leave that file out, and HIPIVFPQ::Init then rejects the value.
+struct HIPRawShardOps {
+  int (*set_raw_placement)(gamma_hip_group *g, int sharded);
+  int (*group_raw_put)(gamma_hip_group *g, int64_t n, const int64_t *vids, const float *vecs, int64_t *n_skipped);
+  int (*raw_clear)(gamma_hip_index *h);
+};
+int RegisterHIPRawShard(const HIPRawShardOps *ops);
+const HIPRawShardOps *FindHIPRawShard();
+
 struct HIPIVFPQModelParams {
   int ncentroids = 2048;
   int nsubvector = 64;
@@ -72,6 +84,8 @@ struct HIPIVFPQModelParams {
                                  // process (gamma_hip_group_*); empty: one GPU, GAMMA_HIP_DEVICE or 0
   bool replicate = false;        // HIP only: "placement": "replicate" -- every device holds every list, a search splits
                                  // the queries (results of one GPU bit for bit); "shard" (default): by IVF list
+  bool raw_sharded = false;      // HIP only: "raw_placement": "sharded" -- with several devices and list placement every raw
+                                 // vector lives once, on the device that owns its list; "replicated" (default): on all
   int Parse(const char *str);   // 0 ok, -1 bad (same rules as gamma_index_ivfpq.h:708-851)
 };
 
@@ -106,6 +120,9 @@ class GammaIVFPQHIPIndex : public RetrievalModel {
   int TrainCoarse(size_t num, const float *xt);
   int TrainingSet(std::vector<float> &xt, size_t &num);
   int EnsureRaw(int64_t upto);
+  int EnsureRawLocked(int64_t upto);   // raw_mu_ held
+  int ShardRows();                     // "raw_placement": "sharded": member 0's dense mirror goes, the group takes the rows
+  int PutRowsFromStore(int64_t upto);  // ... and after a Load gets them from the engine's vector store
   int UploadEngineBitmap();
   int SyncVid2DocID(int64_t upto);   // multi-vector documents: docids of vids [0, upto) to the device (VIDMgr)
   std::mutex raw_mu_;   // raw_uploaded_ + the mirror writes (Search threads, the indexing thread, Load)
@@ -131,6 +148,11 @@ class GammaIVFPQHIPIndex : public RetrievalModel {
   std::atomic<int64_t> ties_said_{0};   // WarnTiesNotHonoured: what this model has reported so far
   HIPIVFPQModelParams *model_param_ = nullptr;
   int64_t raw_uploaded_ = 0;
+  // "raw_placement": "sharded".  Until the first Add after training (or a Load) member 0 alone mirrors the vector store by
+  // vid, for the brute-force search of an untrained model; from then on (rows_sharded_) the group keeps every row at the
+  // owner of its list, Add and Update hand the rows to the group, and a brute-force request is refused.
+  const HIPRawShardOps *rawshard_ = nullptr;
+  bool rows_sharded_ = false;          // under raw_mu_
   // nbits_per_idx: 8, or 4 (16 centroids per sub-quantizer, two indices per code byte as faiss's PQEncoderGeneric packs them)
   int nbits_ = 8;
   size_t Ksub() const { return (size_t)1 << nbits_; }

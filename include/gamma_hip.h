@@ -227,8 +227,22 @@ int gamma_hip_raw_gets(gamma_hip_index* h, int64_t n, const int64_t* vids, float
  * answers GAMMA_HIP_EUNSUPPORTED.  Replaces MemoryRawVector::GetVector for the rows a shard owns
  * (vector/memory_raw_vector.cc:136-142). */
 int gamma_hip_raw_put(gamma_hip_index* h, int64_t n, const int64_t* vids, const float* vecs);
+/* A sparse store's rows can be rewritten, dropped and reused (a realtime Update that moves a vector to a list of another
+ * shard takes its row along).  gamma_hip_raw_put on a vector id the store already holds rewrites that row IN PLACE (named twice
+ * in one call: the last one wins); gamma_hip_raw_drop makes the store forget rows -- vector ids it does not hold are ignored --
+ * and later puts reuse the freed rows before the store grows.  A store that holds rows by vector id (raw_append / raw_write)
+ * answers GAMMA_HIP_EINVAL to a drop.  A search enqueued before such a call never reads a half-written row: a rewrite in place
+ * and the reuse of a freed row wait for the searches in flight, a new row at the end of the store is listed only afterwards
+ * (DESIGN.md 9). */
+int gamma_hip_raw_drop(gamma_hip_index* h, int64_t n, const int64_t* vids);
+/* empties the store -- rows, vid -> row table, free list -- back to the state after gamma_hip_raw_init (neither dense nor
+ * sparse yet: a store mirrored by vector id before training can become a sparse one).  Waits for the searches in flight. */
+int gamma_hip_raw_clear(gamma_hip_index* h);
+/* out3 = {rows that hold a vector, rows handed out so far, freed rows waiting for reuse} of a sparse store (zeros otherwise) */
+int gamma_hip_raw_sparse_stats(gamma_hip_index* h, int64_t* out3);
+/* rows of a store by vector id; of a sparse store the rows that hold a vector */
 int64_t gamma_hip_raw_count(gamma_hip_index* h);
-/* out4 = {rows, rows the mapped / allocated memory holds, reallocations that MOVED the store so far, 1 when the store
+/* out4 = {rows (a sparse store: rows handed out so far), rows the mapped / allocated memory holds, reallocations that MOVED the store so far, 1 when the store
  * grows in place (virtual memory management: physical chunks mapped behind the rows, nothing ever moves or waits for
  * the searches in flight -- what the reference gets from its 500 000-vector segments, vector/memory_raw_vector.cc:90-142)} */
 int gamma_hip_raw_stats(gamma_hip_index* h, int64_t* out4);
@@ -672,6 +686,21 @@ int gamma_hip_group_ivfpq_search(gamma_hip_group* g, const gamma_hip_search_para
 int gamma_hip_group_ivfpq_search_device(gamma_hip_group* g, const gamma_hip_search_params* p, int nq, const float* d_x,
                                         int k, float* d_distances, int64_t* d_labels);
 int64_t gamma_hip_group_total_mem_bytes(gamma_hip_group* g);
+/* Raw vectors of a list-sharded group.  0 (default): REPLICATED -- every member mirrors every row (the caller writes them
+ * through gamma_hip_group_member, as the plugins do).  1: SHARDED -- every row lives exactly once, in the sparse store
+ * (gamma_hip_raw_put) of the member that owns its vector's list: gamma_hip_group_ivfpq_add puts the rows beside the keys,
+ * gamma_hip_group_ivfpq_update rewrites the row of a vector that stays on its member in place and moves the row of one that
+ * leaves (put at the new owner, gamma_hip_raw_drop at the old one), and a has_rank search computes the exact distances where
+ * the rows are (gamma_hip_ivfpq_shard_exact / _shard_export_exact) and sends them with the candidates to the owner of the
+ * query slice (_merge_rerank_exact / _merge_replay_exact); with has_rank = 0 nothing more is computed or sent.  Results stay
+ * those of one handle holding every list and every row.  Allowed only while no member holds a row and not together with
+ * gamma_hip_group_set_placement(1) (GAMMA_HIP_EINVAL); every member's raw store must be initialised (gamma_hip_raw_init). */
+int gamma_hip_group_set_raw_placement(gamma_hip_group* g, int sharded);
+int gamma_hip_group_raw_placement(const gamma_hip_group* g);
+/* rows for callers that add keys without vectors (gamma_hip_group_ivfpq_add_keys after a Load): row vecs[i] goes to the member
+ * that lists vector id vids[i] (gamma_hip_ivfpq_has_vid); ids nobody lists are skipped and counted in *n_skipped (may be NULL).
+ * Sharded raw placement only. */
+int gamma_hip_group_raw_put(gamma_hip_group* g, int64_t n, const int64_t* vids, const float* vecs, int64_t* n_skipped);
 
 /* ---- accounting (GetTotalMemBytes, index/retrieval_model.h:287; PerfTool :23-50) ------ */
 int64_t gamma_hip_total_mem_bytes(gamma_hip_index* h);

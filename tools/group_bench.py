@@ -30,6 +30,8 @@ def main():
     ap.add_argument("--recall-num", type=int, default=200)
     ap.add_argument("--k", type=int, default=10)
     ap.add_argument("--placement", default="auto", choices=["auto", "shard", "replicate"])
+    ap.add_argument("--raw-placement", default="replicated", choices=["replicated", "sharded"],
+                    help="sharded: every raw row once, at the member that owns its list (lists sharded: --placement auto means shard)")
     a = ap.parse_args()
     import torch
     from gamma_amd import api, synth
@@ -40,15 +42,20 @@ def main():
     nb = 2
     queries = synth.sift_like(gnq * nb, d=d, seed=4321)
     cc, pq = api.train_ivfpq(base[:min(a.n, a.nlist * 64)], a.nlist, a.m)
-    replicate = a.placement == "replicate" or (a.placement == "auto" and a.n * (a.m + 12) <= (2 << 30))
+    raw_sharded = a.raw_placement == "sharded"
+    if raw_sharded and a.placement == "replicate":
+        ap.error("--raw-placement sharded goes with lists sharded by owner, not with --placement replicate")
+    replicate = not raw_sharded and (a.placement == "replicate" or (a.placement == "auto" and a.n * (a.m + 12) <= (2 << 30)))
     grp = api.GammaHipGroup(devices)
     grp.set_placement(replicate)
     for m in grp.members:
         m.ivfpq_init(d, a.nlist, a.m, 8, api.METRIC_L2, bucket_init_size=max(1000, int(2.5 * a.n / a.nlist / (1 if replicate else W))))
         m.ivfpq_set_trained(cc, pq, None)
         m.raw_init(d)
-        for i0 in range(0, a.n, 1 << 18):
+        for i0 in range(0, a.n if not raw_sharded else 0, 1 << 18):
             m.raw_append(base[i0:i0 + (1 << 18)])
+    if raw_sharded:
+        grp.set_raw_placement(True)                              # grp.add puts every row at the owner of its list
     lno, _ = grp.members[0].encode(base[:min(a.n, 262144)])
     grp.set_owners(np.bincount(lno, minlength=a.nlist))          # balanced by the list sizes of a sample
     t0 = time.time()
@@ -75,10 +82,16 @@ def main():
         step(a.warmup + i)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    # recall@10 of the last batch against the exact flat search of member 0 (raw vectors are replicated)
+    # recall@10 of the last batch against the exact flat search of member 0 (raw vectors replicated), or -- no member holds
+    # every row -- against the exact neighbours worked out with torch
     nrq = 500
     xb = queries[((a.warmup + a.steps - 1) % nb) * gnq:][:nrq]
-    Df, If = grp.members[0].flat_search(xb, a.k, api.SearchArgs(metric=api.METRIC_L2, min_score=0.0, max_score=1e30))
+    if raw_sharded:
+        tb = torch.from_numpy(base).to(dev0)
+        If = torch.topk((tb * tb).sum(1)[None, :] - 2.0 * (torch.from_numpy(xb).to(dev0) @ tb.T), a.k, largest=False).indices.cpu().numpy()
+        del tb
+    else:
+        Df, If = grp.members[0].flat_search(xb, a.k, api.SearchArgs(metric=api.METRIC_L2, min_score=0.0, max_score=1e30))
     Ig = d_I[:nrq].cpu().numpy()
     recall = sum(len(set(Ig[i].tolist()) & set(If[i].tolist())) for i in range(nrq)) / float(nrq * a.k)
     out = {"metric": "queries/sec @ recall@10>=0.95, IVFPQ nlist=%d nprobe=%d" % (a.nlist, a.nprobe),
@@ -90,7 +103,7 @@ def main():
                       if not replicate else "C3 through the in-process group: %d members%s, %d queries per member and step, lists "
                       "REPLICATED, queries split" % (W, " on ONE GPU (functional check)" if a.one_gpu else "", a.nq),
                       "parallelism": "in-process, %s x%d" % ("query-parallel over replicas" if replicate else "list-sharded", W), "recall_at_10": round(recall, 4),
-                      "build_s": round(build_s, 1), "device_bytes": grp.total_mem_bytes()}}
+                      "build_s": round(build_s, 1), "device_bytes": grp.total_mem_bytes(), "raw_placement": a.raw_placement}}
     print(json.dumps(out), flush=True)
     grp.close()
 
