@@ -588,7 +588,13 @@ class GammaHip:
         self._ck(self.L.gamma_hip_set_workspace_budget(self.h, int(nbytes)), "set_workspace_budget")
 
     def set_coarse_fused(self, on=True, list_cap=128):
-        self._ck(self.L.gamma_hip_set_coarse_fused(self.h, 1 if on else 0, list_cap), "set_coarse_fused")
+        """False / 0: matrix path; True / 1: matrix-free path, bf16 filter where supported; 2: matrix-free path, fp32 filter."""
+        self._ck(self.L.gamma_hip_set_coarse_fused(self.h, int(on), list_cap), "set_coarse_fused")
+
+    def coarse_filter_stats(self):
+        out = np.zeros(4, np.int64)
+        self._ck(self.L.gamma_hip_coarse_filter_stats(self.h, _p(out, _lib.i64p)), "coarse_filter_stats")
+        return dict(zip(["given_up", "queries", "backoffs", "fp32_calls_left"], [int(v) for v in out]))
 
     def set_small_path(self, on=True):
         """True / False, or an int >= 2: on, with the two-level selection of long candidate rows forced (that many slices)."""

@@ -23,6 +23,40 @@
 // only centroid tiles go through LDS, double-buffered, one barrier per tile.  A wave alternates between the two
 // 32-column blocks of a tile; the epilogue of one block is interleaved, instruction by instruction, with the
 // MFMAs of the next, so the matrix pipe does not wait for the VALU work.  LDS: 2 x 64 x (d+1) floats = 66 KB at d = 128 -> two workgroups per CU.
+//
+// bf16 filter (step B of the default mode; gamma_hip_set_coarse_fused(h, 1, ..)).  The discard decision of step B does
+// not need the reference's arithmetic, it needs a bound with a proven margin (flat_mfma.hip does the same for flat
+// search).  k_coarse_filter_bf16 computes ip~ = xh.yh + xh.yl + xl.yh on v_mfma_f32_32x32x16_bf16 (24 MFMAs per 32 x 32
+// block where the fp32 kernel has 64, on a pipe 16 x as fast), the centroids from an image built once per trained
+// index (k_coarse_image), and k_coarse_final<.., BF> gives the exact operation order only to what survives.  Step A
+// (the sample) and the bound tau stay exact: fp32 MFMA, as before.
+//   Margin.  computed_exact = max(0, fma(-2, ip, xn + yn)), ip the k-ascending fma chain.  With d <= 128:
+//     dropped products  |xl.yl + rx.y + x.ry| <= 3.1 * 2^-18 |x||y|                          (|rx| <= 2^-18 |x| per element)
+//     fp32 accumulation of 3 d exact bf16 products (any order)   <= 3 d 2^-24 |x||y| = 2.3e-5 |x||y|
+//     the exact chain's own d roundings of partial sums <= |x||y|  <= d 2^-24 |x||y| = 7.7e-6 |x||y|
+//     => |ip~ - ip| <= 4.3e-5 |x||y| <= 2.15e-5 (xn + yn), doubled by the factor -2 of the fma: 4.3e-5 (xn + yn)
+//     the filter's xn~ (another summation order than fvec_norm_L2sqr; yn is the exact array) <= d 2^-24 xn = 7.7e-6 xn
+//     the roundings of xn + yn and of the final fma, on both sides                           <= 4 * 2^-24 (xn + yn)
+//     |d~ - computed_exact| <= 5.1e-5 (xn + yn) =: the proven bound; used: eps_qc = c (xn + yn), c = 2^-13 = 1.22e-4
+//     (kCoarseBfMargin in kernels.h; tests/test_coarse_margin_cpu.py measures 2e-6 .. 5e-6).  The slack of 2.4 covers
+//     the roundings of forming (1 - c) xn~ + (1 - c) yn and M_q below.  The clamp at 0 only moves computed_exact
+//     towards d~ + eps.
+//   Domain.  2^-64 <= xn <= 2^120 and yn <= 2^120 (kCoarseBfXnMin / kCoarseBfNormMax): no overflow in xn + yn or 2 ip;
+//     a product that underflows (or a lo part flushed in the split) is an absolute error below 2^-126 |y_k| resp.
+//     2^-126, 3 d of them stay 2^40 below c xn.  A query outside the domain is reported as an overflowed list and
+//     redone by the repair kernels; an index with a centroid norm outside it (or not finite) keeps the fp32 filter.
+//     Non-finite query components make xn non-finite: outside the domain, same path as before this filter existed.
+//   Selection.  The filter keeps L = d~ - eps_qc <= computed_exact whenever L <= tau.  tau is an exact upper bound of
+//     the P-th smallest exact value, so everything among the P smallest -- and everything tied with the P-th -- has
+//     L <= exact <= tau and is kept.  k_coarse_final then tightens: with M_q = 2 c (xn + max_c yn) >= 2 eps_qc, let kb be
+//     a value with P entries of L <= kb (sample entries count with L = exact).  Each of them has exact <= L + 2 eps_qc
+//     <= kb + M_q, so the P-th smallest exact value is T <= kb + M_q, and every entry with exact <= T, ties at T
+//     included, has L <= T <= kb + M_q.  Entries are discarded only when L > kb + M_q, i.e. when their approximation
+//     d~ = L + eps exceeds the bound on the approximations by more than 2 eps.  What is kept (about 1.3 P plus the
+//     band) gets the exact chain; ranking and the tie flag work on exact keys only, as before.
+//   Mass overflow.  Data whose norms dwarf its distances (every component + 1000) puts most of a strip inside the
+//     band; every list overflows and every query would go through the one-workgroup-per-query repair.  The handle
+//     counts the queries the bf16 chain gave up on and falls back to the fp32 filter (gamma_hip_internal.h, cbf_*).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>
@@ -31,6 +65,7 @@
 #include <algorithm>
 #include <type_traits>
 
+#include "bf16_split.h"
 #include "device_math.h"
 #include "heap_dev.h"
 #include "kernels.h"
@@ -247,6 +282,163 @@ __global__ __launch_bounds__(256, 2) void k_coarse_fused(const float* __restrict
 }
 
 
+// ---- the filter on the bf16 matrix pipe (header: "bf16 filter") ----
+// Centroid image, built once per trained index: tile t (64 centroids) = two blocks of 32 columns, each
+// [part hi | lo][k step of 16][k half of 8][column 0..31][8 bf16] -- the B fragments of v_mfma_f32_32x32x16_bf16 as a
+// lane reads them (16 bytes per lane, consecutive lanes consecutive: conflict-free), so that a tile goes global -> LDS
+// as it is.  MFMA slot (k step kk, half kh, t) holds element kh * D/2 + 8 kk + t, for queries and centroids alike.
+// hc[col] = (1 - c) |y_col|^2; NaN for the padding columns of the last tile (a NaN fails every compare).
+__global__ __launch_bounds__(256) void k_coarse_image(const float* __restrict__ y, const float* __restrict__ yn, int ny,
+                                                      int ny_pad, int D, char* __restrict__ img, float* __restrict__ hc) {
+    const int KK = D / 16;
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= ny_pad * (D / 8)) return;
+    const int c = idx / (D / 8), kg = idx % (D / 8);
+    float f[8];
+#pragma unroll
+    for (int t = 0; t < 8; t++) f[t] = c < ny ? y[(int64_t)c * D + kg * 8 + t] : 0.f;
+    uint4 hi, lo;
+    split_bf16x8(f, hi, lo);
+    const int kh = kg / KK, kk = kg % KK, j = c & 31;
+    char* base = img + (int64_t)(c >> 5) * (D * 128);
+    *reinterpret_cast<uint4*>(base + ((((0 * KK + kk) * 2 + kh) * 32 + j) * 16)) = hi;
+    *reinterpret_cast<uint4*>(base + ((((1 * KK + kk) * 2 + kh) * 32 + j) * 16)) = lo;
+    if (kg == 0) hc[c] = c < ny ? (1.f - kCoarseBfMargin) * yn[c] : __uint_as_float(0x7fc00000u);
+}
+
+// Same ownership as k_coarse_fused (128 queries x one strip of 64-centroid tiles, wave w = rows 32w..32w+31, slots by
+// ballot, out-of-range buffer stores), but: the queries' bf16 hi / lo A fragments in registers (64 VGPRs at d = 128),
+// centroid tiles of the image by LDS-DMA, double-buffered, 24 MFMAs per 32 x 32 block, and per element
+//      L = fma(-2, ip~, (1 - c) xn~ + (1 - c) yn)   -- a lower bound of the exact distance (header) --   pass: L <= tau.
+// A survivor stores (centroid, bits of L).  A row outside the magnitude domain passes nothing and reports an
+// overflowed list, which sends it to the repair kernel.  Measured with v_mfma_f32_32x32x16_bf16 only (the C layout
+// is the one the slot counters of k_coarse_fused are built on; 16x16x32 was not tried).
+template <int NCH>   // d = 16 * NCH
+__global__ __launch_bounds__(256, 2) void k_coarse_filter_bf16(const float* __restrict__ x, int nq,
+                                                               const char* __restrict__ img, const float* __restrict__ hc,
+                                                               int ny, int col0, const float* __restrict__ tau,
+                                                               int tiles_per_strip, int cap, int cap_stride,
+                                                               unsigned long long* __restrict__ cand,
+                                                               int* __restrict__ cand_cnt, int nseg) {
+    constexpr int D = 16 * NCH, KK = NCH, BLK = D * 128, TILE = 2 * BLK;
+    constexpr int LPT = TILE / (256 * 16);   // 1 KB pieces per wave and tile
+    static_assert(TILE % (256 * 16) == 0, "tile staged by whole rounds of the workgroup");
+    extern __shared__ __attribute__((aligned(16))) char s_cimg[];   // [2][TILE]
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, kh = lane >> 5, j = lane & 31;
+    const int seg = blockIdx.x, q_base = blockIdx.y * 128;
+    const int ntiles = (ny - col0 + 63) >> 6;
+    const int t0 = seg * tiles_per_strip, t1 = min(ntiles, t0 + tiles_per_strip);
+    auto stage = [&](int t, int b) {
+        const char* src = img + (int64_t)((col0 >> 6) + t) * TILE + (w * LPT) * 1024 + lane * 16;
+        char* dst = s_cimg + b * TILE + (w * LPT) * 1024;
+#pragma unroll
+        for (int u = 0; u < LPT; u++)
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + u * 1024),
+                                             (__attribute__((address_space(3))) void*)(dst + u * 1024), 16, 0, 0);
+    };
+    if (t0 < t1) stage(t0, 0);
+    // ---- this wave's 32 queries: lane (j, kh) holds half a row, split once ----
+    bf16x8 ah[KK], al[KK];
+    float a_row, t_row;
+    int ok_row;
+    {
+        const int row = q_base + w * 32 + j;
+        const float* xp = x + (int64_t)min(row, nq - 1) * D + (D / 2) * kh;
+        float ss = 0.f;
+#pragma unroll
+        for (int kk = 0; kk < KK; kk++) {
+            const float4 v0 = *reinterpret_cast<const float4*>(xp + 8 * kk);
+            const float4 v1 = *reinterpret_cast<const float4*>(xp + 8 * kk + 4);
+            const float f[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+#pragma unroll
+            for (int t = 0; t < 8; t++) ss = __builtin_fmaf(f[t], f[t], ss);
+            uint4 hi, lo;
+            split_bf16x8(f, hi, lo);
+            ah[kk] = __builtin_bit_cast(bf16x8, hi);
+            al[kk] = __builtin_bit_cast(bf16x8, lo);
+        }
+        const float xn = ss + __shfl_xor(ss, 32, 64);
+        ok_row = (xn >= kCoarseBfXnMin && xn <= kCoarseBfNormMax) ? 1 : 0;   // false for NaN
+        a_row = (1.f - kCoarseBfMargin) * xn;
+        t_row = (row < nq && ok_row) ? tau[row] : -INFINITY;
+        if (row >= nq) ok_row = 1;
+    }
+    // the lane's 16 rows of a C block: i(r) = (r & 3) + 8 (r >> 2) + 4 kh; lane i holds row i's values
+    float ar[16], tr[16];
+    int bad = 0;
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const int i = (r & 3) + 8 * (r >> 2) + 4 * kh;
+        ar[r] = __shfl(a_row, i, 64);
+        tr[r] = __shfl(t_row, i, 64);
+        bad |= __shfl(ok_row, i, 64) ? 0 : (1 << r);
+    }
+    int cnt[16];
+#pragma unroll
+    for (int r = 0; r < 16; r++) cnt[r] = 0;
+    const uint32_t lt_mask = (1u << j) - 1u;
+    const unsigned row_stride = (unsigned)nseg * (unsigned)cap_stride;
+    const unsigned lane_row = ((unsigned)((q_base + w * 32 + 4 * kh) * nseg + seg)) * (unsigned)cap_stride;
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
+        cand, 0, (int)min((int64_t)nq * nseg * cap_stride * 8, (int64_t)0x7fffffff), 0x00020000);
+    constexpr unsigned OOB = 0x80000000u;
+    const int sh = lane & 32;
+    int rs[16];
+#pragma unroll
+    for (int r = 0; r < 16; r++) rs[r] = ((r & 3) + 8 * (r >> 2)) * (int)row_stride * 8;
+    __syncthreads();
+    for (int t = t0; t < t1; t++) {
+        const int b = (t - t0) & 1;
+        const int colb = col0 + t * 64;
+        float hcv[2];
+        hcv[0] = hc[colb + j];   // the image's padding covers whole tiles
+        hcv[1] = hc[colb + 32 + j];
+        if (t + 1 < t1) stage(t + 1, b ^ 1);   // in flight during the MFMAs
+        f32x16 acc[2];
+#pragma unroll
+        for (int nt = 0; nt < 2; nt++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) acc[nt][r] = 0.f;
+        const char* tb = s_cimg + b * TILE + (kh * 32 + j) * 16;
+#pragma unroll
+        for (int kk = 0; kk < KK; kk++) {
+#pragma unroll
+            for (int nt = 0; nt < 2; nt++) {
+                const bf16x8 bh = *reinterpret_cast<const bf16x8*>(tb + nt * BLK + ((0 * KK + kk) * 2) * 512);
+                const bf16x8 bl = *reinterpret_cast<const bf16x8*>(tb + nt * BLK + ((1 * KK + kk) * 2) * 512);
+                acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[kk], bh, acc[nt], 0, 0, 0);
+                acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[kk], bl, acc[nt], 0, 0, 0);
+                acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[kk], bh, acc[nt], 0, 0, 0);
+            }
+        }
+#pragma unroll
+        for (int nt = 0; nt < 2; nt++) {
+            const unsigned colv = (unsigned)(colb + nt * 32 + j);
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const float L = __builtin_fmaf(-2.f, acc[nt][r], ar[r] + hcv[nt]);
+                const bool pass = L <= tr[r];
+                const unsigned long long mask = __ballot(pass);
+                const uint32_t mh = (uint32_t)(mask >> sh);
+                const unsigned slot = min((unsigned)cnt[r] + (unsigned)__popc(mh & lt_mask), (unsigned)cap);
+                u32x2 item;
+                item.x = colv;
+                item.y = __float_as_uint(L);
+                __builtin_amdgcn_raw_buffer_store_b64(item, rsrc, pass ? (lane_row + slot) * 8u : OOB, rs[r], 0);
+                cnt[r] += __popc(mh);
+            }
+        }
+        __syncthreads();   // every wave is through buffer b; the next tile's LDS-DMA has landed
+    }
+    if (j == 0) {
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            const int row = q_base + w * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
+            if (row < nq) cand_cnt[row * nseg + seg] = ((bad >> r) & 1) ? cap + 1 : cnt[r];
+        }
+    }
+}
+
 // K-th smallest (with multiplicity) of the 64 lane values: the value v with #(m < v) < K <= #(m <= v)
 __device__ __forceinline__ uint32_t wave_kth_smallest(uint32_t m, int K) {
     int lt = 0, le = 0;
@@ -306,22 +498,47 @@ __global__ __launch_bounds__(256) void k_coarse_bound(const float* __restrict__ 
 // rank-sorted in LDS.  A query with an overflowed strip list, or too many entries at the bound, goes to
 // k_coarse_repair.
 constexpr int CF_BUF = 256;
-template <int SNPL, int MAXSEG>
+// BF (the survivors come from k_coarse_filter_bf16 and carry lower bounds L of their exact distance, the sample
+// entries their exact distance): the bound is tightened on the L's with the margin M_q added (header, "selection"),
+// what is left gets its exact distance -- the k-ascending fma chain, the norms of fvec_norm_L2sqr, bit for bit what
+// k_coarse_fused stores -- and only then is ranked and checked for ties.  stat: {queries given up on, queries}.
+template <int SNPL, int MAXSEG, bool BF = false>
 __global__ __launch_bounds__(256) void k_coarse_final(const float* __restrict__ mat, const float* __restrict__ tau,
                                                       const unsigned long long* __restrict__ cand,
                                                       const int* __restrict__ cand_cnt, int nseg, int cap,
                                                       int cap_stride, int nq, int P, float* __restrict__ out_dis,
-                                                      int* __restrict__ out_idx, int* __restrict__ ovf, int flag_ties) {
+                                                      int* __restrict__ out_idx, int* __restrict__ ovf, int flag_ties,
+                                                      const float* __restrict__ x, const float* __restrict__ y,
+                                                      const float* __restrict__ yn, int d, float yn_max,
+                                                      unsigned long long* __restrict__ stat) {
     constexpr int NPL = SNPL + 2 * MAXSEG;
     __shared__ unsigned long long s_buf[4][CF_BUF];
+    __shared__ __attribute__((aligned(16))) float s_xq[BF ? 4 : 1][BF ? 128 : 1];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int q = blockIdx.x * 4 + w;
+    if (BF && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(stat + 1, (unsigned long long)nq);
     if (q >= nq) return;   // whole wave; no workgroup barrier below
     unsigned long long* buf = s_buf[w];
     const int cnt = lane < nseg ? cand_cnt[q * nseg + lane] : 0;
     if (__ballot(cnt > cap)) {
-        if (lane == 0) ovf[1 + atomicAdd(ovf, 1)] = q;
+        if (lane == 0) {
+            ovf[1 + atomicAdd(ovf, 1)] = q;
+            if (BF) atomicAdd(stat, 1ull);
+        }
         return;
+    }
+    float margin = 0.f;
+    if constexpr (BF) {
+        float ss = 0.f;
+        for (int k = lane; k < d; k += 64) {
+            const float xv = x[(int64_t)q * d + k];
+            s_xq[w][k] = xv;
+            ss = __builtin_fmaf(xv, xv, ss);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
+        // M_q >= 2 eps_qc for every centroid; the factor covers the different summation order of the filter's xn~
+        margin = 2.f * kCoarseBfMargin * 1.0009765625f * (ss + yn_max);
     }
     unsigned long long it[NPL];
     {
@@ -342,6 +559,13 @@ __global__ __launch_bounds__(256) void k_coarse_final(const float* __restrict__ 
         const int e0 = (lane - 4 * sg) & 63;
         it[SNPL + 2 * sg] = e0 < c ? p[e0] : ~0ull;
         it[SNPL + 2 * sg + 1] = e0 + 64 < c ? p[e0 + 64] : ~0ull;
+        if constexpr (BF) {   // (centroid, bits of L) -> (key of L, centroid)
+#pragma unroll
+            for (int h2 = 0; h2 < 2; h2++) {
+                unsigned long long& v = it[SNPL + 2 * sg + h2];
+                if (v != ~0ull) v = ((unsigned long long)f2key(__uint_as_float((uint32_t)(v >> 32))) << 32) | (uint32_t)v;
+            }
+        }
     }
     uint32_t m0 = 0xffffffffu, m1 = 0xffffffffu;   // empty slots carry the largest key
 #pragma unroll
@@ -352,14 +576,22 @@ __global__ __launch_bounds__(256) void k_coarse_final(const float* __restrict__ 
         else m0 = k < m0 ? k : m0;
     }
     // 0xffffffff when fewer than P lanes (P > 32: lane halves) hold entries: keep all
-    const uint32_t kb = P <= 32 ? wave_kth_smallest(m0 < m1 ? m0 : m1, P) : wave_kth_smallest2(m0, m1, P);
+    uint32_t kb = P <= 32 ? wave_kth_smallest(m0 < m1 ? m0 : m1, P) : wave_kth_smallest2(m0, m1, P);
+    if constexpr (BF) {
+        // P entries have L <= kb, hence exact <= kb + M_q; whatever is among the P smallest, or tied with the P-th, has
+        // L <= exact <= kb + M_q
+        if (kb != 0xffffffffu) kb = f2key(key2f(kb) + margin);
+    }
     int c = 0;
 #pragma unroll
     for (int j = 0; j < NPL; j++) c += ((uint32_t)(it[j] >> 32) <= kb && it[j] != ~0ull) ? 1 : 0;
     const int incl = wave_incl_scan_i(c);
     const int tot = __shfl(incl, 63, 64);
     if (tot > CF_BUF) {   // mass ties at the bound: not worth a second path here
-        if (lane == 0) ovf[1 + atomicAdd(ovf, 1)] = q;
+        if (lane == 0) {
+            ovf[1 + atomicAdd(ovf, 1)] = q;
+            if (BF) atomicAdd(stat, 1ull);
+        }
         return;
     }
     int off = incl - c;
@@ -367,6 +599,38 @@ __global__ __launch_bounds__(256) void k_coarse_final(const float* __restrict__ 
     for (int j = 0; j < NPL; j++)
         if ((uint32_t)(it[j] >> 32) <= kb && it[j] != ~0ull) buf[off++] = it[j];
     __builtin_amdgcn_wave_barrier();
+    if constexpr (BF) {
+        // exact norm of the query: fvec_norm_L2sqr, 4 accumulators, (a0 + a1) + (a2 + a3)
+        const float* sx = s_xq[w];
+        const int l4 = lane & 3;
+        float nacc = 0.f;
+        for (int i = 0; i < d; i += 4) {
+            const float xv = sx[i + l4];
+            nacc = __builtin_fmaf(xv, xv, nacc);
+        }
+        const float t01 = nacc + __shfl_down(nacc, 1, 4);
+        const float xn = __shfl(t01 + __shfl_down(t01, 2, 4), 0, 64);
+        for (int e = lane; e < tot; e += 64) {
+            const uint32_t col = (uint32_t)buf[e];
+            if (col >= (uint32_t)(64 * SNPL)) {   // a survivor of the filter: one lane, one k-ascending chain
+                const float4* yr = reinterpret_cast<const float4*>(y + (int64_t)col * d);
+                float ip = 0.f;
+#pragma unroll 4
+                for (int k4 = 0; k4 < (d >> 2); k4++) {
+                    const float4 yv = yr[k4];
+                    const float4 xv = *reinterpret_cast<const float4*>(sx + 4 * k4);
+                    ip = __builtin_fmaf(xv.x, yv.x, ip);
+                    ip = __builtin_fmaf(xv.y, yv.y, ip);
+                    ip = __builtin_fmaf(xv.z, yv.z, ip);
+                    ip = __builtin_fmaf(xv.w, yv.w, ip);
+                }
+                float dis = __builtin_fmaf(-2.f, ip, xn + yn[col]);
+                if (dis < 0.f) dis = 0.f;
+                buf[e] = ((unsigned long long)f2key(dis) << 32) | col;
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
     // rank sort of the tot (<= 256) distinct items: lane holds items lane, lane + 64, ..
     unsigned long long mine[CF_BUF / 64];
     int rr[CF_BUF / 64];
@@ -546,9 +810,23 @@ CoarseFusedPlan coarse_fused_plan(int nq, int nlist, int P, int cap, bool exact_
     return pl;
 }
 
+size_t coarse_image_bytes(int d, int nlist) {
+    const size_t ny_pad = ((size_t)nlist + 63) / 64 * 64;
+    return ny_pad * d * 4 + ny_pad * sizeof(float);   // hi + lo, 2 bytes each per element; hc behind them
+}
+bool coarse_image_supported(int d, int nlist) { return (d == 32 || d == 64 || d == 96 || d == 128) && nlist >= 2048; }
+void launch_coarse_image(hipStream_t s, const float* y, const float* yn, int nlist, int d, void* image) {
+    const int ny_pad = (nlist + 63) / 64 * 64;
+    const int n = ny_pad * (d / 8);
+    char* img = static_cast<char*>(image);
+    hipLaunchKernelGGL(k_coarse_image, dim3((n + 255) / 256), dim3(256), 0, s, y, yn, nlist, ny_pad, d, img,
+                       reinterpret_cast<float*>(img + (size_t)ny_pad * d * 4));
+}
+
 void launch_coarse_fused(hipStream_t s, const CoarseFusedPlan& pl, void* ws, const float* x, int nq, int d,
                          const float* y, int nlist, const float* yn, int P, float* out_dis, int* out_idx, bool exact_ties,
-                         unsigned long long* tie_stats, hipStream_t side, hipEvent_t fork, hipEvent_t join) {
+                         unsigned long long* tie_stats, hipStream_t side, hipEvent_t fork, hipEvent_t join,
+                         const CoarseBf16* bf) {
     char* b = static_cast<char*>(ws);
     float* mat = reinterpret_cast<float*>(b + pl.off_mat);
     float* tau = reinterpret_cast<float*>(b + pl.off_tau);
@@ -584,6 +862,17 @@ void launch_coarse_fused(hipStream_t s, const CoarseFusedPlan& pl, void* ws, con
     else hipLaunchKernelGGL(k_coarse_bound<32>, dim3((nq + 3) / 4), dim3(256), 0, s, mat, nq, P, tau, ovf);
     // B: the other columns, filtered
     dim3 grid((unsigned)pl.nseg, (unsigned)((nq + 127) / 128));
+#define GH_CB(NCH)                                                                                                      \
+    do {                                                                                                                \
+        static std::atomic<uint64_t> attr{0};   /* per device */                                                        \
+        if (first_call_on_device(attr)) {                                                                               \
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_coarse_filter_bf16<NCH>),                         \
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 2 * (16 * NCH) * 128);            \
+        }                                                                                                               \
+        hipLaunchKernelGGL((k_coarse_filter_bf16<NCH>), grid, dim3(256), (size_t)2 * 2 * (16 * NCH) * 128, s, x, nq,    \
+                           static_cast<const char*>(bf->img), bf->hc, nlist, pl.sample, tau, pl.tiles_per_strip, pl.cap, \
+                           pl.cap_stride, cand, cnt, pl.nseg);                                                          \
+    } while (0)
 #define GH_CF(NCH)                                                                                                      \
     do {                                                                                                                \
         static std::atomic<uint64_t> attr{0};   /* per device */                                                        \
@@ -594,17 +883,33 @@ void launch_coarse_fused(hipStream_t s, const CoarseFusedPlan& pl, void* ws, con
         hipLaunchKernelGGL((k_coarse_fused<NCH>), grid, dim3(256), lds, s, x, nq, y, nlist, pl.sample, yn, tau,         \
                            pl.tiles_per_strip, pl.cap, pl.cap_stride, cand, cnt, pl.nseg, nullptr);                          \
     } while (0)
-    switch (d) {
-        case 32: GH_CF(2); break;
-        case 64: GH_CF(4); break;
-        case 96: GH_CF(6); break;
-        default: GH_CF(8); break;
+    if (bf) {
+        switch (d) {
+            case 32: GH_CB(2); break;
+            case 64: GH_CB(4); break;
+            case 96: GH_CB(6); break;
+            default: GH_CB(8); break;
+        }
+    } else {
+        switch (d) {
+            case 32: GH_CF(2); break;
+            case 64: GH_CF(4); break;
+            case 96: GH_CF(6); break;
+            default: GH_CF(8); break;
+        }
     }
 #undef GH_CF
+#undef GH_CB
     // C + D
+#define GH_FIN1(SN, MS, BFV)                                                                                            \
+    hipLaunchKernelGGL((k_coarse_final<SN, MS, BFV>), dim3((nq + 3) / 4), dim3(256), 0, s, mat, tau, cand, cnt, pl.nseg, \
+                       pl.cap, pl.cap_stride, nq, P, out_dis, out_idx, ovf, exact_ties ? 1 : 0, x, y, yn, d,            \
+                       bf ? bf->yn_max : 0.f, bf ? bf->stat : nullptr)
 #define GH_FIN(SN, MS)                                                                                                  \
-    hipLaunchKernelGGL((k_coarse_final<SN, MS>), dim3((nq + 3) / 4), dim3(256), 0, s, mat, tau, cand, cnt, pl.nseg, pl.cap, \
-                       pl.cap_stride, nq, P, out_dis, out_idx, ovf, exact_ties ? 1 : 0)
+    do {                                                                                                                \
+        if (bf) GH_FIN1(SN, MS, true);                                                                                  \
+        else GH_FIN1(SN, MS, false);                                                                                    \
+    } while (0)
     if (pl.sample == 512) {
         if (pl.nseg <= 4) GH_FIN(8, 4);
         else if (pl.nseg <= 8) GH_FIN(8, 8);
@@ -617,6 +922,7 @@ void launch_coarse_fused(hipStream_t s, const CoarseFusedPlan& pl, void* ws, con
         else GH_FIN(32, 16);
     }
 #undef GH_FIN
+#undef GH_FIN1
     if (!exact_ties) {
         hipLaunchKernelGGL(k_coarse_repair, dim3(kCoarseRepairGrid), dim3(256), (size_t)d * sizeof(float), s, x, d, y, nlist, yn,
                            ovf, scratch, P, out_dis, out_idx);

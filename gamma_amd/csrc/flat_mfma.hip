@@ -45,38 +45,19 @@
 
 #include "device_math.h"
 #include "filter_dev.h"
+#include "bf16_split.h"
 #include "block_utils.h"
 #include "kernels.h"
 #include "rerank_dev.h"
 
 namespace gh {
 
-typedef __attribute__((__vector_size__(8 * sizeof(__bf16)))) __bf16 bf16x8;
 typedef float ff32x16 __attribute__((ext_vector_type(16)));
 
 constexpr float FM_C = 1.220703125e-4f;   // 2^-13, see the margin above
 constexpr int FM_QT = 64;                 // queries per LDS tile
 constexpr int FM_ROWS = 128;              // rows per workgroup (4 waves: 2 row groups x 2 query halves)
 constexpr int FM_NT = 256;                // threads per workgroup
-
-// two floats -> two bf16 (round to nearest even), lo in bits 0..15
-__device__ __forceinline__ uint32_t cvt_pk_bf16(float lo, float hi) {
-    uint32_t r;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-    return r;
-}
-// 8 floats -> (hi, lo) bf16x8: hi = bf16(f), lo = bf16(f - hi)
-__device__ __forceinline__ void split_bf16x8(const float* f, uint4& hi, uint4& lo) {
-    uint32_t h[4], l[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        h[i] = cvt_pk_bf16(f[2 * i], f[2 * i + 1]);
-        const float h0 = __uint_as_float(h[i] << 16), h1 = __uint_as_float(h[i] & 0xffff0000u);
-        l[i] = cvt_pk_bf16(f[2 * i] - h0, f[2 * i + 1] - h1);   // the differences are exact in fp32
-    }
-    hi = make_uint4(h[0], h[1], h[2], h[3]);
-    lo = make_uint4(l[0], l[1], l[2], l[3]);
-}
 
 // bytes of the LDS image of one 32-query block: [part hi | lo][k step of 16][k half of 8][query 0..31][8 bf16]
 __host__ __device__ constexpr int fm_mt_bytes(int D) { return 2 * (D / 16) * 2 * 32 * 16; }

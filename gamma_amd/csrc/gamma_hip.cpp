@@ -134,7 +134,7 @@ int gamma_hip_destroy(gamma_hip_index* h) {
     if (h->d_raw_slot) (void)hipFree(h->d_raw_slot);
     void* ptrs[] = {h->d_list_rank, h->d_raw, h->d_bitmap, h->d_cc, h->d_cc_norms, h->d_pqc, h->d_T2, h->d_codes,
                     h->d_ids, h->d_list_mask, h->d_scan_codes, h->d_tie_stats, h->d_v2d, h->d_sums, h->d_t2max, h->d_bound_stat,
-                    h->d_bin_cc, h->d_bin_stats};
+                    h->d_bin_cc, h->d_bin_stats, h->d_cc_img, h->d_cbf_stat};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     for (auto& kv : h->fields)
@@ -149,6 +149,8 @@ int gamma_hip_destroy(gamma_hip_index* h) {
     if (h->dir_pin) (void)hipHostFree(h->dir_pin);
     if (h->bound_copy_ev) (void)hipEventDestroy(h->bound_copy_ev);
     if (h->pin_bound_stat) (void)hipHostFree(h->pin_bound_stat);
+    if (h->cbf_copy_ev) (void)hipEventDestroy(h->cbf_copy_ev);
+    if (h->pin_cbf_stat) (void)hipHostFree(h->pin_cbf_stat);
     if (h->pin_flat_over) (void)hipHostFree(h->pin_flat_over);
     DevBuf* bufs[] = {&h->w_mat, &h->w_coarse_dis, &h->w_probe, &h->w_xn, &h->w_st2, &h->w_pair_off,
                       &h->w_qtotal, &h->w_dist, &h->w_cand_dis, &h->w_cand_pos, &h->w_cand_ids,
@@ -219,8 +221,25 @@ int gamma_hip_set_exact_ties(gamma_hip_index* h, int on) {
 int gamma_hip_set_coarse_fused(gamma_hip_index* h, int on, int list_cap) {
     if (!h || list_cap < 1 || list_cap > gh::kCoarseCap) return GAMMA_HIP_EINVAL;
     SearchLock lk(h);
-    h->coarse_fused = on != 0;
+    h->coarse_fused = on == 0 ? 0 : (on == 2 ? 2 : 1);
     h->coarse_cap = list_cap;
+    h->cbf_off_calls = 0;
+    return GAMMA_HIP_OK;
+}
+
+int gamma_hip_coarse_filter_stats(gamma_hip_index* h, int64_t* out4) {
+    if (!h || !out4) return GAMMA_HIP_EINVAL;
+    SearchLock lk(h);
+    unsigned long long v[2] = {0, 0};
+    if (h->d_cbf_stat) {
+        GH_CHECK(h, hipSetDevice(h->device));
+        GH_CHECK(h, hipStreamSynchronize(h->stream));
+        GH_CHECK(h, hipMemcpy(v, h->d_cbf_stat, sizeof(v), hipMemcpyDeviceToHost));
+    }
+    out4[0] = (int64_t)v[0];
+    out4[1] = (int64_t)v[1];
+    out4[2] = h->cbf_backoffs;
+    out4[3] = h->cbf_off_calls;
     return GAMMA_HIP_OK;
 }
 
@@ -305,6 +324,7 @@ int64_t gamma_hip_total_mem_bytes(gamma_hip_index* h) {
         b += h->arena_cap * (h->code_size + (int64_t)sizeof(int64_t));
         if (h->d_sums) b += h->arena_cap * (int64_t)sizeof(float) + (int64_t)h->nlist * 4;
         b += (int64_t)h->nlist * 12;
+        b += (int64_t)h->cc_img_bytes;
         // the shadow arena of calls that run over lists compacted under their filter (kept between calls)
         b += (int64_t)(h->w_cmp_codes.cap + h->w_cmp_ids.cap + h->w_cmp_len.cap);
     }

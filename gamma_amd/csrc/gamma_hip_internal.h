@@ -323,7 +323,25 @@ struct gamma_hip_index {
     std::atomic<int64_t> ties_unhonoured{0};   // gamma_hip_ties_not_honoured
     int scan_dbg_now = 0;   // GAMMA_HIP_SCAN_PART (timing experiments)
     std::atomic<int64_t> blas_unrestated{0};   // gamma_hip_blas_form_not_restated
-    bool coarse_fused = true;  // gamma_hip_set_coarse_fused
+    int coarse_fused = 1;      // gamma_hip_set_coarse_fused: 0 matrix path, 1 bf16 filter where supported, 2 fp32 fused path
+    // bf16 filter of the fused coarse path (coarse.hip): the centroids' hi / lo image in the MFMA fragment layout, rebuilt
+    // wherever d_cc_norms is; cc_img_ok: every centroid norm lies in the filter's magnitude domain.
+    // Feedback on the pattern of the bounded scan's: k_coarse_final counts the queries the bf16 chain gave up on (margin
+    // band wider than the strip lists: data with norms >> distances; queries outside the domain); the cumulative pair
+    // comes back through pinned words, and while more than 1/8 of the recent queries of one kind of call (nlist, nprobe,
+    // d) were given up on, the handle runs the fp32 filter, re-probing every 256 calls.  Results are the same either way.
+    void* d_cc_img = nullptr;
+    size_t cc_img_bytes = 0;
+    bool cc_img_ok = false;
+    float cc_norm_max = 0.f;
+    unsigned long long* d_cbf_stat = nullptr;     // {given up on, queries}
+    unsigned long long* pin_cbf_stat = nullptr;
+    unsigned long long cbf_seen[2] = {0, 0};
+    hipEvent_t cbf_copy_ev = nullptr;
+    bool cbf_copy_pending = false;
+    uint64_t cbf_sig = 0;
+    int cbf_off_calls = 0;                         // fp32 calls left before the re-probe
+    int64_t cbf_backoffs = 0, cbf_calls = 0;       // times the handle turned the bf16 filter off; calls that ran it
     bool small_path = true;    // gamma_hip_set_small_path
     int small_presel = 0;      // 0: pre-selection by estimate, > 0: always, that many slices (tests)
     // multi-vector documents (VIDMgr::VID2DocID, vector/raw_vector_common.h:90-95): docid of every vid, host + device;

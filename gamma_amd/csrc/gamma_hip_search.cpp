@@ -168,7 +168,44 @@ int ivfpq_coarse(H* h, const gamma_hip_search_params* p, int nq, const float* d_
     if (mode < 0) mode = nq < 20 ? 0 : 1;  // faiss:utils/distances.cpp:303,346
     // large batches: no distance matrix (coarse.hip); with exact ties its rows with a tie near the cut are recomputed
     // and replayed through the reference's heap by the repair kernel
-    const bool fused = mode == 1 && h->coarse_fused && gh::coarse_fused_supported(nq, d, nlist, P, tie_on(p));
+    const bool fused = mode == 1 && h->coarse_fused != 0 && gh::coarse_fused_supported(nq, d, nlist, P, tie_on(p));
+    // the filter launch on the bf16 pipe (coarse.hip): needs the centroid image with every norm in the domain; turned off
+    // for a while by the handle when the recent calls of this kind handed too many queries to the repair kernels
+    bool bf16 = fused && h->coarse_fused == 1 && h->d_cc_img && h->cc_img_ok;
+    if (bf16) {
+        const uint64_t sig = ((uint64_t)nlist << 32) ^ ((uint64_t)P << 16) ^ (uint64_t)d ^ (1ull << 63);
+        auto landed = [&]() {
+            if (h->cbf_copy_pending && hipEventQuery(h->cbf_copy_ev) == hipSuccess) h->cbf_copy_pending = false;
+            else if (h->cbf_copy_pending) (void)hipGetLastError();
+            return !h->cbf_copy_pending;
+        };
+        if (sig != h->cbf_sig) {   // another kind of call: what was learnt does not carry over
+            h->cbf_sig = sig;
+            h->cbf_off_calls = 0;
+            if (h->cbf_copy_pending) {
+                (void)hipEventSynchronize(h->cbf_copy_ev);
+                h->cbf_copy_pending = false;
+            }
+            h->cbf_seen[0] = h->pin_cbf_stat[0];
+            h->cbf_seen[1] = h->pin_cbf_stat[1];
+        }
+        if (h->cbf_off_calls > 0) {
+            if (--h->cbf_off_calls > 0) bf16 = false;   // (0: this call re-probes)
+        } else if (landed()) {
+            // the counters are cumulative and the pair is read only behind the copy that wrote it
+            const unsigned long long u = h->pin_cbf_stat[0], n = h->pin_cbf_stat[1];
+            const unsigned long long dn = n - h->cbf_seen[1], du = std::min(u - h->cbf_seen[0], dn);
+            if (dn >= 2048) {
+                h->cbf_seen[0] = u;
+                h->cbf_seen[1] = n;
+                if (8 * du > dn) {
+                    h->cbf_off_calls = 256;
+                    h->cbf_backoffs++;
+                    bf16 = false;
+                }
+            }
+        }
+    }
     gh::CoarseFusedPlan plan;
     if (fused) {
         plan = gh::coarse_fused_plan(nq, nlist, P, h->coarse_cap, tie_on(p));
@@ -186,9 +223,26 @@ int ivfpq_coarse(H* h, const gamma_hip_search_params* p, int nq, const float* d_
     if (fused) {
         static const bool no_side = getenv("GAMMA_HIP_NO_SIDE_STREAM") != nullptr;
         const bool side = tie_on(p) && defer_join && !no_side;
+        gh::CoarseBf16 bf;
+        if (bf16) {
+            const size_t ny_pad = ((size_t)nlist + 63) / 64 * 64;
+            bf.img = h->d_cc_img;
+            bf.hc = reinterpret_cast<const float*>(static_cast<const char*>(h->d_cc_img) + ny_pad * d * 4);
+            bf.yn_max = h->cc_norm_max;
+            bf.stat = h->d_cbf_stat;
+        }
         gh::launch_coarse_fused(s, plan, h->w_mat.p, d_x, nq, d, h->d_cc, nlist, h->d_cc_norms, P, out_dis, out_probe,
-                                tie_on(p), h->d_tie_stats, side ? h->side : nullptr, h->ev_fork, h->ev_join);
+                                tie_on(p), h->d_tie_stats, side ? h->side : nullptr, h->ev_fork, h->ev_join,
+                                bf16 ? &bf : nullptr);
         h->coarse_join_pending = side;
+        if (bf16) {
+            h->cbf_calls++;
+            if (!h->cbf_copy_pending) {   // one copy in flight at a time: the pinned pair belongs to one state of the counters
+                GH_CHECK(h, hipMemcpyAsync(h->pin_cbf_stat, h->d_cbf_stat, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+                GH_CHECK(h, hipEventRecord(h->cbf_copy_ev, s));
+                h->cbf_copy_pending = true;
+            }
+        }
         static const bool dbg = getenv("GAMMA_HIP_COARSE_DBG") != nullptr;
         if (dbg) {   // how many queries the strip lists could not hold (they went through the repair kernel)
             int n_ovf = 0;

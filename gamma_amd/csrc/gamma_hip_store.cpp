@@ -1201,6 +1201,39 @@ int gamma_hip_ivfflat_init(gamma_hip_index* h, int d, int nlist, int metric, int
     return ivf_init_locked(h, d, nlist, 1, metric, bucket_init_size, bucket_max_size, true);
 }
 
+// The bf16 hi / lo image of the centroids for the coarse filter (coarse.hip), wherever the centroids and their norms
+// are set: once per trained index.  Call with the norms launched on wstream; synchronises it.
+static int build_coarse_image(H* h) {
+    h->cc_img_ok = false;
+    if (!gh::coarse_image_supported(h->d, h->nlist)) return GAMMA_HIP_OK;
+    const size_t bytes = gh::coarse_image_bytes(h->d, h->nlist);
+    if (!h->d_cc_img) {
+        GH_CHECK(h, hipMalloc(&h->d_cc_img, bytes));
+        h->cc_img_bytes = bytes;
+    }
+    if (!h->d_cbf_stat) {
+        GH_CHECK(h, hipMalloc((void**)&h->d_cbf_stat, 2 * sizeof(unsigned long long)));
+        GH_CHECK(h, hipMemset(h->d_cbf_stat, 0, 2 * sizeof(unsigned long long)));
+        GH_CHECK(h, hipHostMalloc((void**)&h->pin_cbf_stat, 2 * sizeof(unsigned long long), hipHostMallocDefault));
+        h->pin_cbf_stat[0] = h->pin_cbf_stat[1] = 0;
+        GH_CHECK(h, hipEventCreateWithFlags(&h->cbf_copy_ev, hipEventDisableTiming));
+    }
+    gh::launch_coarse_image(h->wstream, h->d_cc, h->d_cc_norms, h->nlist, h->d, h->d_cc_img);
+    GH_CHECK(h, hipGetLastError());
+    std::vector<float> nn((size_t)h->nlist);
+    GH_CHECK(h, hipMemcpyAsync(nn.data(), h->d_cc_norms, nn.size() * sizeof(float), hipMemcpyDeviceToHost, h->wstream));
+    GH_CHECK(h, hipStreamSynchronize(h->wstream));
+    float mx = 0.f;
+    bool ok = true;
+    for (float v : nn) {
+        if (!(v <= gh::kCoarseBfNormMax)) ok = false;   // NaN included
+        else mx = std::max(mx, v);
+    }
+    h->cc_norm_max = mx;
+    h->cc_img_ok = ok;
+    return GAMMA_HIP_OK;
+}
+
 int gamma_hip_ivfflat_set_trained(gamma_hip_index* h, const float* cc) {
     if (!h || !cc) return GAMMA_HIP_EINVAL;
     WriteLock lk(h);
@@ -1209,6 +1242,7 @@ int gamma_hip_ivfflat_set_trained(gamma_hip_index* h, const float* cc) {
     GH_CHECK(h, hipMemcpyAsync(h->d_cc, cc, (size_t)h->nlist * h->d * sizeof(float), hipMemcpyHostToDevice, h->wstream));
     gh::launch_row_norms(h->wstream, h->d_cc, h->nlist, h->d, h->d_cc_norms);
     GH_CHECK(h, hipGetLastError());
+    GH_TRY(build_coarse_image(h));
     GH_CHECK(h, hipStreamSynchronize(h->wstream));
     h->trained = true;
     return GAMMA_HIP_OK;
@@ -1251,6 +1285,7 @@ int gamma_hip_ivfpq_set_trained(gamma_hip_index* h, const float* cc, const float
     GH_CHECK(h, hipMemcpyAsync(h->d_cc, cc, ncc * sizeof(float), hipMemcpyHostToDevice, h->wstream));
     GH_CHECK(h, hipMemcpyAsync(h->d_pqc, pqc, npq * sizeof(float), hipMemcpyHostToDevice, h->wstream));
     gh::launch_row_norms(h->wstream, h->d_cc, h->nlist, h->d, h->d_cc_norms);
+    GH_TRY(build_coarse_image(h));
     if (h->table_mode == 0) {
         // no table (a supplied one is not taken either: the reference would not have built it)
     } else if (table)

@@ -266,6 +266,20 @@ struct CoarseFusedPlan {
     int sample, nseg, tiles_per_strip, cap, cap_stride;
     size_t off_mat, off_tau, off_cand, off_cnt, off_ovf, off_scratch, off_full, bytes;
 };
+// bf16 filter of the fused path (coarse.hip, "bf16 filter"): |L~ - exact| margin c (xn + yn), and the magnitude domain
+// of its derivation; queries outside it go to the repair list, an index with a centroid outside it keeps the fp32 filter
+constexpr float kCoarseBfMargin = 1.220703125e-4f;     // c = 2^-13
+constexpr float kCoarseBfXnMin = 5.421010862427522e-20f;    // 2^-64  <= |x|^2
+constexpr float kCoarseBfNormMax = 1.329227995784916e+36f;  // 2^120  >= |x|^2, |y|^2
+struct CoarseBf16 {
+    const void* img;             // launch_coarse_image
+    const float* hc;             // (1 - c) |y|^2 per image column
+    float yn_max;                // largest centroid norm
+    unsigned long long* stat;    // {queries the bf16 chain gave up on, queries}, cumulative
+};
+size_t coarse_image_bytes(int d, int nlist);
+bool coarse_image_supported(int d, int nlist);
+void launch_coarse_image(hipStream_t s, const float* y, const float* yn, int nlist, int d, void* image);
 bool coarse_fused_supported(int nq, int d, int nlist, int P, bool exact_ties = false);
 CoarseFusedPlan coarse_fused_plan(int nq, int nlist, int P, int cap, bool exact_ties = false);
 // rows[0] distance rows mat[i][0..nlist) of the queries rows[1 + i], each walked through faiss's result heap
@@ -275,7 +289,8 @@ void launch_coarse_heap_rows(hipStream_t s, const float* mat, int nlist, int nq,
 void launch_coarse_fused(hipStream_t s, const CoarseFusedPlan& pl, void* ws, const float* x, int nq, int d,
                          const float* y, int nlist, const float* yn, int P, float* out_dis, int* out_idx,
                          bool exact_ties = false, unsigned long long* tie_stats = nullptr,
-                         hipStream_t side = nullptr, hipEvent_t fork = nullptr, hipEvent_t join = nullptr);
+                         hipStream_t side = nullptr, hipEvent_t fork = nullptr, hipEvent_t join = nullptr,
+                         const CoarseBf16* bf = nullptr);   // bf: the filter launch on the bf16 pipe
 // small batches: exact coarse distances [nq][nlist] + inner-product tables [nq][M][256] in one launch; false = shape
 // not covered (nq > 16), nothing launched
 bool launch_small_coarse_ip(hipStream_t s, const float* x, int nq, int d, const float* cc, int nlist, float* mat, int M,

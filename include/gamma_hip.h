@@ -166,10 +166,15 @@ int gamma_hip_set_workspace_budget(gamma_hip_index* h, int64_t bytes);
  * (gamma_hip_ties_not_honoured). */
 int gamma_hip_set_exact_ties(gamma_hip_index* h, int on);
 /* Coarse quantizer of large batches (>= 4096 queries, >= 2048 lists, d in {32, 64, 96, 128}, nprobe <= 64) without
- * the [nq][nlist] distance matrix (csrc/coarse.hip).  on: 1 = automatic (default), 0 = always the matrix path.
+ * the [nq][nlist] distance matrix (csrc/coarse.hip).  on: see below.
  * list_cap: capacity of a query's per-strip survivor list, 1..128 (default 128); a query that overflows it is redone
  * by the repair kernel -- tests shrink it to force that path.  Results are identical either way. */
 int gamma_hip_set_coarse_fused(gamma_hip_index* h, int on, int list_cap);
+/* on: 0 = distance matrix + selection; 1 (default) = matrix-free path with the bf16 filter where the shape and the
+ * centroids allow it, the fp32 filter elsewhere; 2 = matrix-free path with the fp32 filter.  Same results in all.
+ * out4: {queries the bf16 chain handed to the repair kernels, queries it ran on, times the handle switched itself to
+ * the fp32 filter, fp32 calls left before it probes the bf16 filter again} */
+int gamma_hip_coarse_filter_stats(gamma_hip_index* h, int64_t* out4);
 /* Calls of up to 512 queries (nprobe <= 128, recall_num <= 1024) run as a chain of
  * four or five fused kernels instead of eleven (DESIGN.md "small batches").  on: 1 = automatic (default), 0 = always
  * the regular chain, n >= 2 = automatic with the two-level selection of long candidate rows forced on with n slices
