@@ -81,6 +81,11 @@ SYMBOLS = {
     "gamma_hip_bitmap_set": (C.c_int, [C.c_void_p, i64p, C.c_int64, C.c_int]),
     "gamma_hip_ivfpq_init": (C.c_int, [C.c_void_p] + [C.c_int] * 7),
     "gamma_hip_ivfpq4_init": (C.c_int, [C.c_void_p] + [C.c_int] * 6),
+    "gamma_hip_opq_set": (C.c_int, [C.c_void_p, f32p]),
+    "gamma_hip_opq_get": (C.c_int, [C.c_void_p, f32p]),
+    "gamma_hip_opq_apply": (C.c_int, [C.c_void_p, C.c_int64, f32p, f32p]),
+    "gamma_hip_opq_apply_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "gamma_hip_opq_train": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, f32p, C.c_int, C.c_int, f32p, C.POINTER(C.c_float)]),
     "gamma_hip_ivfpq_set_trained": (C.c_int, [C.c_void_p, f32p, f32p, f32p]),
     "gamma_hip_ivfpq_get_precomputed_table": (C.c_int, [C.c_void_p, f32p]),
     "gamma_hip_set_precomputed_table_max_bytes": (C.c_int, [C.c_int64]),

@@ -208,6 +208,46 @@ class GammaHip:
                  "ivfpq4_init")
         self.d, self.nlist, self.M, self.ksub = d, nlist, M, 16
 
+    # ---- OPQ rotation ----
+    def opq_set(self, A):
+        """the d x d rotation (row-major, xt = A x) of an 8-bit IVFPQ handle whose lists are still empty; from then on add,
+        encode, update_batch and the IVFPQ searches rotate inside the library"""
+        A = _f32(A)
+        d = self.L.gamma_hip_ivfpq_dim(self.h)
+        if d > 0 and A.shape != (d, d):
+            raise ValueError("opq_set: the matrix must be d x d")
+        self._ck(self.L.gamma_hip_opq_set(self.h, _p(A, _lib.f32p)), "opq_set")
+
+    def opq_get(self):
+        """the matrix set by opq_set, or None"""
+        d = self.L.gamma_hip_ivfpq_dim(self.h)
+        A = np.empty((d, d), dtype=np.float32)
+        rc = self.L.gamma_hip_opq_get(self.h, _p(A, _lib.f32p))
+        if rc < 0:
+            self._ck(rc, "opq_get")
+        return A if rc == 1 else None
+
+    def opq_apply(self, x):
+        """x A^T for host rows, in the arithmetic of the contract (one fp32 fmaf chain per element)"""
+        x = _f32(x)
+        xt = np.empty_like(x)
+        self._ck(self.L.gamma_hip_opq_apply(self.h, x.shape[0], _p(x, _lib.f32p), _p(xt, _lib.f32p)), "opq_apply")
+        return xt
+
+    def opq_train(self, x, M_opq, niter=0):
+        """OPQMatrix::train on the device (gamma_hip_opq_train; niter <= 0: the library's 50): (A [d, d], mean squared PQ
+        error of the last alternation).  Changes nothing on the handle: pass A to opq_set"""
+        x = _f32(x)
+        d = x.shape[1]
+        A = np.empty((d, d), dtype=np.float32)
+        obj = C.c_float(0)
+        self._ck(self.L.gamma_hip_opq_train(self.h, d, x.shape[0], _p(x, _lib.f32p), M_opq, niter, _p(A, _lib.f32p),
+                                            C.byref(obj)), "opq_train")
+        return A, float(obj.value)
+
+    def opq_apply_device(self, d_x, n, d_xt):
+        self._ck(self.L.gamma_hip_opq_apply_device(self.h, n, d_x, d_xt), "opq_apply_device")
+
     def _code_width(self):
         # bytes per list entry: M, or (4 M + 7) / 8 on a 4-bit handle
         return (4 * self.M + 7) // 8 if self.ksub == 16 else self.M

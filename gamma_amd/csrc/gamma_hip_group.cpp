@@ -216,6 +216,11 @@ const gamma_group_ext::RawOps*& raw_ops() {
     return ops;
 }
 
+gamma_group_ext::MemberMarkFn& member_mark() {
+    static gamma_group_ext::MemberMarkFn fn = nullptr;
+    return fn;
+}
+
 // src on device sd -> dst on device dd, ordered on stream s (a stream of device dd)
 hipError_t copy_between(void* dst, int dd, const void* src, int sd, size_t bytes, hipStream_t s) {
     if (bytes == 0) return hipSuccess;
@@ -229,6 +234,11 @@ namespace gamma_group_ext {
 
 int register_raw_ops(const RawOps* ops) {
     raw_ops() = ops;
+    return 1;
+}
+
+int register_member_mark(MemberMarkFn fn) {
+    member_mark() = fn;
     return 1;
 }
 
@@ -315,6 +325,7 @@ int gamma_hip_group_create(const int* devices, int n, gamma_hip_group** out) {
             return rc;
         }
         g->m.push_back(h);
+        if (member_mark()) (void)member_mark()(h);
     }
     // direct copies between the members' devices where the fabric allows it (xGMI); failure is not an error, the
     // runtime then stages peer copies itself

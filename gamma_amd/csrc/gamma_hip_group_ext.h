@@ -19,6 +19,12 @@ struct RawOps {
 };
 int register_raw_ops(const RawOps* ops);   // returns 1 (a value for a static initialiser)
 
+// What tells a handle that a group owns it: such a handle refuses an OPQ matrix (gamma_hip_opq_set; the group rotates nothing).
+// Registered by the translation unit that defines gamma_hip_opq_set (gamma_hip_opq.cpp), so every library that can set a matrix
+// also marks its group members -- independent of the raw-shard table above.  The CPU stub of the sanitizer builds has neither.
+typedef int (*MemberMarkFn)(gamma_hip_index*);
+int register_member_mark(MemberMarkFn fn);   // returns 1
+
 int set_raw_sharded(gamma_hip_group* g, int sharded);
 int raw_sharded(const gamma_hip_group* g);
 int raw_put(gamma_hip_group* g, int64_t n, const int64_t* vids, const float* vecs, int64_t* n_skipped);

@@ -279,6 +279,15 @@ struct gamma_hip_index {
     // what the scan launcher takes as (st2, T2): mode 0 -> (the PQ codebook, nullptr), see scan.hip RES
     const float* scan_st2(bool l2) const { return (l2 && table_mode == 0) ? d_pqc : w_st2.as<float>(); }
     bool keep_sums = false;   // set by Init: IVFPQ handles (GAMMA_HIP_NO_CODE_SUMS=1 turns the filter pass off)
+    // OPQ (gamma_hip_opq_set; gamma_hip_opq.cpp): the d x d rotation, device + host copy.  Null = none: every path is the one
+    // it was without it.  Set while the lists are empty and never replaced afterwards, so kernels in flight never lose it.
+    // Vectors that are QUANTISED (coarse quantizer, PQ encoder, query tables, scan) are rotated first -- the writers' into
+    // we_xrot on the writer stream, a search call's into w_xrot on the search stream, once for the whole call before its
+    // first chunk (no growth while the call's kernels are queued; a later call's growth goes through hipFree, which
+    // waits for the device like every other workspace's) -- the exact re-rank and the tie replay read the caller's vectors.
+    float* d_opq = nullptr;
+    std::vector<float> h_opq;
+    bool group_member = false;   // created by gamma_hip_group_create: refuses a matrix
     // list shard over a supplied assignment (gamma_hip_ivfpq_search_shard_preassigned): the longest candidate row of the
     // call, measured on the device -- the slab stride of its chunks (0: nprobe x the longest list)
     int64_t q_stride_cap = 0;
@@ -309,8 +318,8 @@ struct gamma_hip_index {
     DevBuf w_mat, w_coarse_dis, w_probe, w_xn, w_st2, w_pair_off, w_qtotal, w_dist, w_cand_dis,
             w_cand_pos, w_cand_ids, w_exact, w_selv, w_selp, w_x, w_outd, w_outl, w_stage, w_shard_cut, w_filter,
             w_m_dis, w_m_ids, w_part_v, w_part_i, w_assign, w_codes_tmp, w_qperm, w_qbins, w_scnt, w_sflag, w_surv, w_pair_base, w_q8, w_q8meta, w_q8cand, w_q8int,
-            w_pair_ip, w_flat_cand, w_flat_meta, w_full_cdis, w_full_probe, w_ftab, w_qfil, w_tieflag, w_tcut, w_tlist, w_textra, w_fq, w_fraw, w_frcnt, w_lm_units, w_lm_cnt, w_fbits, w_cmp_codes, w_cmp_ids, w_cmp_len, w_cmp_sums, w_fD, w_fI, w_fx, w_fslab, w_flog, w_mr_vals, w_mr_ids, w_mr_meta,
-            we_mat, we_cdis, we_x, we_assign, we_codes, we_stage, we_chk;   // writer side (encode, bitmap_set): never shared with a search
+            w_pair_ip, w_flat_cand, w_flat_meta, w_full_cdis, w_full_probe, w_ftab, w_qfil, w_tieflag, w_tcut, w_tlist, w_textra, w_fq, w_fraw, w_frcnt, w_lm_units, w_lm_cnt, w_fbits, w_cmp_codes, w_cmp_ids, w_cmp_len, w_cmp_sums, w_fD, w_fI, w_fx, w_fslab, w_flog, w_mr_vals, w_mr_ids, w_mr_meta, w_xrot,
+            we_mat, we_cdis, we_x, we_assign, we_codes, we_stage, we_chk, we_xrot;   // writer side (encode, bitmap_set): never shared with a search
     unsigned long long* d_scan_codes = nullptr;
     size_t dist_budget_bytes = (size_t)8 << 30;   // per-chunk ADC distance buffer (288 GB of HBM per GPU)
 

@@ -3,6 +3,7 @@
 // (include/gamma_hip.h).  No CPU fallback: every entry point runs the HIP kernels or returns an error.
 #include "gamma_hip_internal.h"
 #include "gamma_hip_search.h"
+#include "opq.h"
 #include "pq4.h"
 
 namespace ghi {
@@ -305,9 +306,17 @@ static int pq4_refuse(H* h, const char* what) {
     h->err = std::string("4-bit handle: ") + what + " is 8-bit only";
     return GAMMA_HIP_EUNSUPPORTED;
 }
+// a handle with an OPQ matrix (gamma_hip_opq_set) behind an entry point that takes vectors or candidates of several handles:
+// the list shards and their merge rotate nothing -- refused, never silent
+static int opq_refuse(H* h, const char* what) {
+    h->err = std::string("handle with an OPQ matrix: ") + what + " is not supported";
+    return GAMMA_HIP_EUNSUPPORTED;
+}
+// (every entry point that refuses the one refuses the other: the shard, merge and export entries)
 #define GH_NO_PQ4(h, what)                                                \
     do {                                                                  \
         if ((h)->ksub == gh::kPq4Ksub) return pq4_refuse((h), (what));    \
+        if ((h)->d_opq) return opq_refuse((h), (what));                   \
     } while (0)
 
 int ivfpq_stage_a(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int nq,
@@ -945,7 +954,9 @@ bool ivfpq_small_ok(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, i
            (int64_t)nq * p->nprobe * (h->ntotal / std::max(1, h->nlist)) <= 48000000LL && (!p->has_rank || (h->d_raw && h->raw_d == h->d && !h->raw_sparse));
 }
 
-int ivfpq_small(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int nq, const float* d_x, int R, int k,
+// d_x: the vectors that are quantised (a handle with an OPQ matrix: the rotated queries), d_xraw: the caller's, which the
+// exact re-rank and the tie replay measure against the raw store
+int ivfpq_small(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int nq, const float* d_x, const float* d_xraw, int R, int k,
                 float* d_distances, int64_t* d_labels) {
     const int P = p->nprobe, d = h->d, M = h->M, nlist = h->nlist;
     hipStream_t s = h->stream;
@@ -1043,7 +1054,7 @@ int ivfpq_small(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int n
         tr.gcnt = nullptr;
         tr.nsl = 0;
         tr.slice_cap = 0;
-        tr.x = d_x;
+        tr.x = d_xraw;
         tr.d = d;
         tr.raw = h->d_raw;
         tr.nraw = h->nraw;
@@ -1060,7 +1071,7 @@ int ivfpq_small(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int n
     }
     gh::launch_small_tail(s, l2, h->w_dist.as<float>(), q_stride, h->w_qtotal.as<int>(), nq, R, P, h->w_probe.as<int>(),
                           h->w_pair_off.as<int>(), h->d_list_off, h->d_ids, h->w_cand_dis.as<float>(),
-                          h->w_cand_pos.as<int>(), h->w_cand_ids.as<int64_t>(), p->has_rank ? 1 : 0, d_x, d, h->d_raw,
+                          h->w_cand_pos.as<int>(), h->w_cand_ids.as<int64_t>(), p->has_rank ? 1 : 0, d_xraw, d, h->d_raw,
                           h->nraw, k, p->min_score, p->max_score, neutral, d_distances, d_labels, smax,
                           smax ? h->w_selv.as<float>() : nullptr, smax ? h->w_selp.as<int>() : nullptr, 0,
                           ties ? &tr : nullptr, h->d_tie_stats);
@@ -1194,9 +1205,21 @@ int ivfpq_search_device_locked(H* h, const gamma_hip_search_params* p, int nq, c
     // the internal chunks must not re-decide it
     if (pp.coarse_mode < 0) pp.coarse_mode = nq < 20 ? 0 : 1;
     if (pp.coarse_mode == 1 && blas_form_not_restated(nq, h->nlist, h->d)) h->blas_unrestated++;
+    // OPQ (gamma_hip_opq_set): the coarse quantizer, the query tables and the scan see the rotated queries, the exact
+    // re-rank and the tie replay the caller's (gamma_index_ivfpq.cc:514-566 rotates before search_preassigned, compute_dis
+    // reads the raw store with the raw query).  The whole call is rotated here, once, before its first chunk: nothing
+    // grows the buffer while the call's kernels are queued.
+    const float* d_xq = d_x;
+    if (h->d_opq) {
+        GH_CHECK(h, h->w_xrot.ensure((size_t)nq * h->d * sizeof(float)));
+        StageScope t(h, GAMMA_HIP_STAGE_COARSE, false);
+        gh::launch_opq_apply(h->stream, h->d_opq, h->d, d_x, nq, h->w_xrot.as<float>());
+        GH_CHECK(h, hipGetLastError());
+        d_xq = h->w_xrot.as<float>();
+    }
     if (ivfpq_small_ok(h, p, fc, nq, R)) {
         GH_TRY(replay_join(h));
-        GH_TRY(ivfpq_small(h, p, fc, nq, d_x, R, k, d_distances, d_labels));
+        GH_TRY(ivfpq_small(h, p, fc, nq, d_xq, d_x, R, k, d_distances, d_labels));
         h->last_nq = nq;
         h->last_P = p->nprobe;
         h->last_R = R;
@@ -1219,7 +1242,7 @@ int ivfpq_search_device_locked(H* h, const gamma_hip_search_params* p, int nq, c
         GH_CHECK(h, h->w_full_probe.ensure((size_t)nq * P * sizeof(int)));
         const int cc = coarse_chunk(h, nq);
         for (int q0 = 0; q0 < nq; q0 += cc)
-            GH_TRY(ivfpq_coarse(h, p, std::min(cc, nq - q0), d_x + (size_t)q0 * h->d,
+            GH_TRY(ivfpq_coarse(h, p, std::min(cc, nq - q0), d_xq + (size_t)q0 * h->d,
                                 h->w_full_cdis.as<float>() + (size_t)q0 * P, h->w_full_probe.as<int>() + (size_t)q0 * P));
         // The general slab stride is nprobe x the LONGEST list; the batch's longest candidate row is what it needs (full-size
         // C4: the longest list is ~5 x the mean, so the budget cut 8192 queries into three chunks -- and the list-major pass
@@ -1253,10 +1276,10 @@ int ivfpq_search_device_locked(H* h, const gamma_hip_search_params* p, int nq, c
     for (int q0 = 0; q0 < nq; q0 += chunk) {
         const int nc = std::min(chunk, nq - q0);
         if (coarse_first)
-            GH_TRY(ivfpq_stage_a(h, p, fc.at(q0), nc, d_x + (size_t)q0 * h->d, R,
+            GH_TRY(ivfpq_stage_a(h, p, fc.at(q0), nc, d_xq + (size_t)q0 * h->d, R,
                                  h->w_full_cdis.as<float>() + (size_t)q0 * P, h->w_full_probe.as<int>() + (size_t)q0 * P));
         else
-            GH_TRY(ivfpq_stage_a(h, p, fc.at(q0), nc, d_x + (size_t)q0 * h->d, R));
+            GH_TRY(ivfpq_stage_a(h, p, fc.at(q0), nc, d_xq + (size_t)q0 * h->d, R));
         GH_TRY(ivfpq_stage_b(h, p, nc, d_x + (size_t)q0 * h->d, R, k, h->w_cand_dis.as<float>(),
                              h->w_cand_ids.as<int64_t>(), d_distances + (size_t)q0 * k,
                              d_labels + (size_t)q0 * k, no_rerank_order ? nullptr : h->last_qperm,
@@ -2048,6 +2071,7 @@ int gamma_hip_ivfpq_coarse_device(gamma_hip_index* h, const gamma_hip_search_par
                                   const float* d_x, float* d_coarse_dis, int32_t* d_probe) {
     if (!h) return GAMMA_HIP_EINVAL;
     SearchLock lk(h);
+    if (h->d_opq) return opq_refuse(h, "gamma_hip_ivfpq_coarse_device");
     GH_TRY(replay_join(h));
     GH_TRY(ivfpq_check(h, p, nq, 1));
     if (nq == 0) return GAMMA_HIP_OK;

@@ -3,6 +3,7 @@
 // vector store, scalar columns and the delete bitmap.  C ABI: include/gamma_hip.h.
 #include "binivf.h"
 #include "gamma_hip_internal.h"
+#include "opq.h"
 #include "pq4.h"
 
 namespace ghi {
@@ -1660,6 +1661,7 @@ int gamma_hip_ivfpq_set_list_mask(gamma_hip_index* h, const uint8_t* owned) {
     WriteLock lk(h);
     if (!h->ivf_init) return fail(h, GAMMA_HIP_EINVAL, "ivfpq not initialised");
     if (h->ksub == gh::kPq4Ksub) return fail(h, GAMMA_HIP_EUNSUPPORTED, "4-bit handle: list shards (gamma_hip_ivfpq_set_list_mask) are 8-bit only");
+    if (h->d_opq) return fail(h, GAMMA_HIP_EUNSUPPORTED, "handle with an OPQ matrix: list shards (gamma_hip_ivfpq_set_list_mask) are not supported");
     GH_CHECK(h, hipSetDevice(h->device));
     GH_CHECK(h, lk.exclusive());
     if (!owned) {
@@ -1726,7 +1728,14 @@ static int encode_host(gamma_hip_index* h, int64_t n, const float* vecs, int64_t
         GH_CHECK(h, h->we_assign.ensure((size_t)nc * sizeof(int)));
         GH_CHECK(h, h->we_codes.ensure((size_t)nc * h->code_size));
         GH_CHECK(h, hipMemcpyAsync(h->we_x.p, vecs + i0 * h->d, (size_t)nc * h->d * sizeof(float), hipMemcpyHostToDevice, h->wstream));
-        GH_TRY(encode_locked(h, nc, h->we_x.as<float>(), h->we_assign.as<int>(), h->we_codes.as<uint8_t>(), exact));
+        const float* d_vecs = h->we_x.as<float>();
+        if (h->d_opq) {   // OPQ: assignment and codes are those of the rotated vectors (gamma_index_ivfpq.cc:375-512)
+            GH_CHECK(h, h->we_xrot.ensure((size_t)nc * h->d * sizeof(float)));
+            gh::launch_opq_apply(h->wstream, h->d_opq, h->d, d_vecs, nc, h->we_xrot.as<float>());
+            GH_CHECK(h, hipGetLastError());
+            d_vecs = h->we_xrot.as<float>();
+        }
+        GH_TRY(encode_locked(h, nc, d_vecs, h->we_assign.as<int>(), h->we_codes.as<uint8_t>(), exact));
         GH_CHECK(h, hipMemcpyAsync(assign.data(), h->we_assign.p, (size_t)nc * sizeof(int), hipMemcpyDeviceToHost, h->wstream));
         GH_CHECK(h, hipMemcpyAsync(codes + i0 * h->code_size, h->we_codes.p, (size_t)nc * h->code_size, hipMemcpyDeviceToHost, h->wstream));
         GH_CHECK(h, hipStreamSynchronize(h->wstream));

@@ -118,6 +118,13 @@ int HIPIVFPQModelParams::Parse(const char *str) {
   utils::JsonParser sub;
   has_hnsw = !jp.GetObject("hnsw", sub);
   has_opq = !jp.GetObject("opq", sub);
+  if (has_opq && !sub.GetInt("nsubvector", v)) {   // gamma_index_ivfpq.h:835-847: default 64 (-1 keeps it)
+    if (v <= 0 && v != -1) {
+      HLOG("invalid opq_nsubvector = %d", v);
+      return -1;
+    }
+    if (v > 0) opq_nsubvector = v;
+  }
   if (ncentroids <= 0 || nsubvector <= 0 || nbits_per_idx <= 0) return -1;
   return 0;
 }
@@ -144,6 +151,18 @@ int RegisterHIPRawShard(const HIPRawShardOps *ops) {
 }
 
 const HIPRawShardOps *FindHIPRawShard() { return RawShardOps(); }
+
+namespace {
+const HIPOpqOps *&OpqOps() {
+  static const HIPOpqOps *ops = nullptr;
+  return ops;
+}
+}  // namespace
+int RegisterHIPOpq(const HIPOpqOps *ops) {
+  OpqOps() = ops;
+  return 0;
+}
+const HIPOpqOps *FindHIPOpq() { return OpqOps(); }
 
 int RegisterHIPListsInit(int nbits, HIPListsInitFn fn) {
   ListsInits().push_back({nbits, fn});
@@ -206,9 +225,22 @@ int GammaIVFPQHIPIndex::Init(const std::string &model_parameters, int indexing_s
   }
   // nbits_per_idx other than 8: through a registered lists initialiser (4: gamma_index_ivfpq4_hip.cc), else rejected
   const HIPListsInitFn lists_init = pa.nbits_per_idx == 8 ? nullptr : FindHIPListsInit(pa.nbits_per_idx);
-  if (pa.has_hnsw || pa.has_opq || pa.support_indivisible_nsubvector || (pa.nbits_per_idx != 8 && !lists_init)) {
-    HLOG("hnsw / opq / padded dimensions / nbits_per_idx other than 8 and 4 are not supported by HIPIVFPQ");
+  opq_ = pa.has_opq ? FindHIPOpq() : nullptr;
+  if (pa.has_hnsw || (pa.has_opq && !opq_) || pa.support_indivisible_nsubvector || (pa.nbits_per_idx != 8 && !lists_init)) {
+    HLOG("hnsw / padded dimensions / nbits_per_idx other than 8 and 4%s are not supported by HIPIVFPQ",
+         pa.has_opq && !opq_ ? " / opq (this build of the plugin carries no OPQ entries)" : "");
     return -2;
+  }
+  if (opq_) {
+    if (d_ % pa.opq_nsubvector != 0) {   // gamma_index_ivfpq.cc:158-163
+      HLOG("%d %% %d != 0, opq nsubvector should be divisible by dimension.", d_, pa.opq_nsubvector);
+      return -2;
+    }
+    if (pa.devices.size() > 1 || pa.nbits_per_idx != 8) {
+      HLOG("opq with several devices or with nbits_per_idx = 4 is not supported");
+      return -2;
+    }
+    opq_M_ = pa.opq_nsubvector;
   }
   if (lists_init && pa.devices.size() > 1) {
     HLOG("nbits_per_idx = %d with several devices is not supported (the group of handles is 8-bit only)", pa.nbits_per_idx);
@@ -299,7 +331,21 @@ int GammaIVFPQHIPIndex::Indexing() {
   std::vector<float> xt;
   size_t num = 0;
   if (TrainingSet(xt, num)) return -1;
-  int rc = TrainOnHost(num, xt.data());
+  int rc = 0;
+  if (opq_) {   // gamma_index_ivfpq.cc:336-346: train the rotation, then everything else on the rotated set
+    opq_A_.resize((size_t)d_ * d_);
+    std::vector<float> rot(xt.size());
+    rc = opq_->train(h_, d_, (int64_t)num, xt.data(), opq_M_, 0, opq_A_.data(), nullptr);
+    if (!rc) rc = opq_->set(h_, opq_A_.data());
+    if (!rc) rc = opq_->apply(h_, (int64_t)num, xt.data(), rot.data());
+    if (rc) {
+      HLOG("opq training failed: %s (%s)", gamma_hip_strerror(rc), gamma_hip_last_error(h_));
+      opq_A_.clear();
+      return -1;
+    }
+    xt.swap(rot);
+  }
+  if (!rc) rc = TrainOnHost(num, xt.data());
   if (!rc) rc = ForAll([&](gamma_hip_index *m) {
     return gamma_hip_ivfpq_set_trained(m, coarse_centroids_.data(), pq_centroids_.data(), nullptr);
   });
@@ -667,6 +713,7 @@ int GammaIVFPQHIPIndex::Dump(const std::string &dir) {
   f.M = (size_t)M_;
   f.nbits = (size_t)nbits_;
   f.pq = pq_centroids_;
+  if (opq_) f.opq = opq_A_;   // the "LTra" record between the product quantizer and the lists (gamma_index_ivfpq.cc:979-984)
   f.sizes.resize(nlist_);
   f.codes.resize(nlist_);
   f.ids.resize(nlist_);
@@ -706,6 +753,18 @@ int GammaIVFPQHIPIndex::Load(const std::string &dir) {
       !f.by_residual || f.pq.size() != (size_t)M_ * Ksub() * (d_ / M_)) {
     HLOG("index file does not match the table's retrieval_param");
     return -1;
+  }
+  if ((opq_ != nullptr) != !f.opq.empty()) {
+    HLOG("index file %s an opq record, the table's retrieval_param %s opq", f.opq.empty() ? "has no" : "has",
+         opq_ ? "names" : "does not name");
+    return -1;
+  }
+  if (opq_) {   // read_opq (gamma_index_ivfpq.cc:1017-1019): on the handle before the lists are filled
+    if (opq_->set(h_, f.opq.data())) {
+      HLOG("cannot set the opq matrix: %s", gamma_hip_last_error(h_));
+      return -1;
+    }
+    opq_A_ = f.opq;
   }
   if (grp_) {   // several GPUs: list -> GPU balanced by the dumped list sizes, before the lists come back
     std::vector<int64_t> weight(nlist_);

@@ -7,7 +7,8 @@
 // return codes, same Search contract.  The parameter classes carry a HIP prefix: the plugin is compiled
 // INTO libgamma next to the reference's own IVFPQ model, where a second
 // tig_gamma::IVFPQModelParams with another layout would be an ODR violation.  Unsupported on device and rejected in Init like any bad parameter:
-// hnsw quantizer, opq, support_indivisible_nsubvector, nbits_per_idx other than 8 and 4 (4: one device only, through the
+// hnsw quantizer, support_indivisible_nsubvector, opq together with several devices or 4-bit codes (opq itself: through the
+// ops table that gamma_index_ivfpq_opq_hip.cc registers; trained in Indexing, carried by Dump / Load as the "LTra" record), nbits_per_idx other than 8 and 4 (4: one device only, through the
 // lists initialiser that gamma_index_ivfpq4_hip.cc registers).
 #pragma once
 #include <atomic>
@@ -66,6 +67,18 @@ struct HIPRawShardOps {
 int RegisterHIPRawShard(const HIPRawShardOps *ops);
 const HIPRawShardOps *FindHIPRawShard();
 
+// "opq": the rotation's entries of the C ABI (gamma_hip_opq_train / _set / _get / _apply) reach the model through this table,
+// registered at static-initialisation time by gamma_index_ivfpq_opq_hip.cc -- the only host file that names them.  A build of
+// the plugin without that file (against a C ABI without those entries) has no table, and HIPIVFPQ::Init rejects "opq".
+struct HIPOpqOps {
+  int (*train)(gamma_hip_index *h, int d, int64_t n, const float *x, int M_opq, int niter, float *A, float *objective);
+  int (*set)(gamma_hip_index *h, const float *A);
+  int (*get)(gamma_hip_index *h, float *A);
+  int (*apply)(gamma_hip_index *h, int64_t n, const float *x, float *xt);
+};
+int RegisterHIPOpq(const HIPOpqOps *ops);
+const HIPOpqOps *FindHIPOpq();
+
 struct HIPIVFPQModelParams {
   int ncentroids = 2048;
   int nsubvector = 64;
@@ -75,6 +88,7 @@ struct HIPIVFPQModelParams {
   DistanceComputeType metric_type = DistanceComputeType::INNER_PRODUCT;
   bool has_hnsw = false;
   bool has_opq = false;
+  int opq_nsubvector = 64;       // "opq": {"nsubvector": N} (gamma_index_ivfpq.h:835-847)
   int bucket_init_size = 1000;
   int bucket_max_size = 1280000;
   bool device_filters = false;   // HIP only: evaluate range / term filters on device-resident columns (filter_bridge.h)
@@ -114,8 +128,11 @@ class GammaIVFPQHIPIndex : public RetrievalModel {
   DistanceComputeType metric_type_ = DistanceComputeType::INNER_PRODUCT;
   int indexed_vec_count_ = 0;
   std::vector<float> coarse_centroids_, pq_centroids_;
+  std::vector<float> opq_A_;   // "opq": the trained / loaded rotation, d x d row-major (empty before training)
 
  protected:
+  const HIPOpqOps *opq_ = nullptr;   // non-null: the model was created with "opq"
+  int opq_M_ = 0;
   int TrainOnHost(size_t num, const float *xt);
   int TrainCoarse(size_t num, const float *xt);
   int TrainingSet(std::vector<float> &xt, size_t &num);

@@ -357,6 +357,32 @@ int gh_host_ivfpq_state(void *hp, float *cc, float *pq) {
   return 0;
 }
 
+// the rotation of a HIPIVFPQ model created with "opq": d * d floats into A (may be NULL); 1 when it holds one, 0 when not
+int gh_host_ivfpq_opq(void *hp, float *A) {
+  GammaIVFPQHIPIndex *m = dynamic_cast<GammaIVFPQHIPIndex *>(((Host *)hp)->model);
+  if (!m) return -1;
+  if (m->opq_A_.empty()) return 0;
+  if (A) memcpy(A, m->opq_A_.data(), sizeof(float) * m->opq_A_.size());
+  return 1;
+}
+// IwPQ files with and without the "LTra" record (host only): `in` rewritten to `out` with the record holding A (n floats) or,
+// A == NULL, without one; and the record of a file: its float count (0: none), A_out filled up to cap floats; < 0: ReadIwPQ's
+int gh_iwpq_rewrite_opq(const char *in, const char *out, const float *A, int64_t n) {
+  IwPQFile f;
+  const int rc = ReadIwPQ(in, &f);
+  if (rc) return rc;
+  if (A) f.opq.assign(A, A + n);
+  else f.opq.clear();
+  return WriteIwPQ(out, f);
+}
+int64_t gh_iwpq_read_opq(const char *path, float *A_out, int64_t cap) {
+  IwPQFile f;
+  const int rc = ReadIwPQ(path, &f);
+  if (rc) return rc;
+  if (A_out) memcpy(A_out, f.opq.data(), sizeof(float) * std::min<size_t>(f.opq.size(), (size_t)cap));
+  return (int64_t)f.opq.size();
+}
+
 int gh_host_ivfpq_set_trained(void *hp, const float *cc, const float *pq) {
   GammaIVFPQHIPIndex *m = dynamic_cast<GammaIVFPQHIPIndex *>(((Host *)hp)->model);
   if (GammaIVFFlatHIPIndex *fl = dynamic_cast<GammaIVFFlatHIPIndex *>(((Host *)hp)->model)) return fl->SetTrainedCoarse(cc);

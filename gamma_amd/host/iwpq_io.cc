@@ -99,6 +99,19 @@ static int write_file(const std::string &path, const IwPQFile &x, bool flat, int
     o.one<size_t>(x.M);
     o.one<size_t>(x.nbits);
     o.vec(x.pq);
+    if (!x.opq.empty()) {              // write_opq, index/gamma_index_io.cc:225-240
+      if (x.opq.size() != (size_t)x.d * (size_t)x.d) {
+        fclose(fp);
+        return -2;
+      }
+      o.one<uint32_t>(fourcc("LTra"));
+      o.one<uint8_t>(0);               // have_bias
+      o.vec(x.opq);
+      o.one<size_t>(0);                // b: empty
+      o.one<int>(x.d);                 // d_in
+      o.one<int>(x.d);                 // d_out
+      o.one<uint8_t>(1);               // is_trained
+    }
   }
   o.one<uint32_t>(fourcc("ilar"));
   o.one<size_t>(x.nlist);
@@ -163,7 +176,24 @@ static int read_file(const std::string &path, IwPQFile *x, bool flat, int *index
       x->code_size = sizeof(float) * (size_t)x->d;
     }
     in.one(h);
-    if (!in.ok || h != fourcc("ilar")) { rc = -2; break; }   // an opq record would sit here: unsupported
+    x->opq.clear();
+    if (in.ok && !flat && h == fourcc("LTra")) {   // read_opq, index/gamma_index_io.cc:242-260
+      uint8_t have_bias = 0, trained = 0;
+      std::vector<float> b;
+      int d_in = 0, d_out = 0;
+      in.one(have_bias);
+      in.vec(x->opq, kMax);
+      in.vec(b, kMax);
+      in.one(d_in);
+      in.one(d_out);
+      in.one(trained);
+      if (!in.ok || d_in != x->d || d_out != x->d || x->opq.size() != (size_t)x->d * (size_t)x->d || have_bias || !b.empty()) {
+        rc = -2;
+        break;
+      }
+      in.one(h);
+    }
+    if (!in.ok || h != fourcc("ilar")) { rc = -2; break; }
     size_t nl = 0, cs = 0;
     in.one(nl);
     in.one(cs);

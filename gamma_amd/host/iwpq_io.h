@@ -9,6 +9,9 @@
 //                direct map : u8 type (0) | vector<i64> (empty)
 //   u8 by_residual | size_t code_size
 //   product quantizer : size_t d | size_t M | size_t nbits | vector<float> centroids
+//   [opq rotation     : u32 "LTra" | u8 have_bias (0) | vector<float> A (d_out * d_in) | vector<float> b (empty)
+//                       | i32 d_in | i32 d_out | u8 is_trained (1)      -- only for a model with "opq"
+//                       (write_opq / read_opq, index/gamma_index_io.cc:225-260; gamma_index_ivfpq.cc:979-984,1017-1019)]
 //   inverted lists    : u32 "ilar" | size_t nlist | size_t code_size | u32 "full" | vector<size_t> sizes
 //                       then for every non-empty list: codes[size*code_size] | i64 ids[size]
 //                       (ids keep bit 63 = superseded; "sprs" = (list, size) pairs is also read)
@@ -30,6 +33,7 @@ struct IwPQFile {
   bool by_residual = true;
   size_t code_size = 0, M = 0, nbits = 8;
   std::vector<float> pq;      // M * 256 * (d / M)
+  std::vector<float> opq;     // d * d row-major (xt = A x); empty: the file has no "LTra" record
   std::vector<size_t> sizes;  // nlist
   std::vector<std::vector<uint8_t>> codes;
   std::vector<std::vector<int64_t>> ids;

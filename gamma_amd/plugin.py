@@ -49,6 +49,9 @@ HOST_SYMBOLS = {
     "gh_host_mem_bytes": (C.c_long, [C.c_void_p]),
     "gh_host_ivfpq_state": (C.c_int, [C.c_void_p, f32p, f32p]),
     "gh_host_ivfpq_set_trained": (C.c_int, [C.c_void_p, f32p, f32p]),
+    "gh_host_ivfpq_opq": (C.c_int, [C.c_void_p, f32p]),
+    "gh_iwpq_rewrite_opq": (C.c_int, [C.c_char_p, C.c_char_p, f32p, C.c_int64]),
+    "gh_iwpq_read_opq": (C.c_int64, [C.c_char_p, f32p, C.c_int64]),
     "gh_parse_ivfpq_model_params": (None, [C.c_char_p, C.POINTER(C.c_int)]),
     "gh_parse_ivfpq_retrieval_params": (None, [C.c_char_p, C.POINTER(C.c_int)]),
     "gh_model_registered": (C.c_int, [C.c_char_p]),
@@ -345,6 +348,27 @@ class PluginModel:
         if self.L.gh_host_ivfpq_state(self.h, _f(cc), _f(pq)):
             return None
         return cc, pq
+
+
+    def opq_matrix(self):
+        """the rotation of a model created with "opq" (after Indexing or Load), or None"""
+        A = np.empty((self.d, self.d), np.float32)
+        return A if self.L.gh_host_ivfpq_opq(self.h, _f(A)) == 1 else None
+
+
+def iwpq_rewrite_opq(path_in, path_out, A=None):
+    """path_in rewritten to path_out with the "LTra" record holding A, or without a record (A None); WriteIwPQ's / ReadIwPQ's rc"""
+    if A is None:
+        return load_host().gh_iwpq_rewrite_opq(path_in.encode(), path_out.encode(), None, 0)
+    A = np.ascontiguousarray(A, np.float32)
+    return load_host().gh_iwpq_rewrite_opq(path_in.encode(), path_out.encode(), _f(A), A.size)
+
+
+def iwpq_read_opq(path, d):
+    """(rc, A): rc < 0 ReadIwPQ's error; A the d x d matrix of the file's "LTra" record or None"""
+    A = np.empty((d, d), np.float32)
+    n = load_host().gh_iwpq_read_opq(path.encode(), _f(A), A.size)
+    return (int(n), None) if n <= 0 else (0, A)
 
 
 class BinaryPluginModel:

@@ -259,7 +259,8 @@ int gamma_hip_bitmap_set(gamma_hip_index* h, const int64_t* docids, int64_t n, i
 
 /* ---- IVFPQ model state (faiss::IndexIVFPQ members the scanner reads) --------------- */
 /* replaces GammaIVFPQIndex::Init's parameter checks (gamma_index_ivfpq.cc:119-214);
- * nbits must be 8, d % M == 0 (OPQ / HNSW quantizer / padding are rejected: EINVAL) */
+ * nbits must be 8, d % M == 0 (HNSW quantizer / padding are rejected: EINVAL; an OPQ rotation is set afterwards,
+ * gamma_hip_opq_set) */
 int gamma_hip_ivfpq_init(gamma_hip_index* h, int d, int nlist, int M, int nbits, int metric,
                          int bucket_init_size, int bucket_max_size);
 /* 4-bit PQ codes.  Replaces GammaIVFPQIndex::Init with nbits_per_idx = 4 (gamma_index_ivfpq.cc:167-170: the value goes
@@ -277,6 +278,48 @@ int gamma_hip_ivfpq_init(gamma_hip_index* h, int d, int nlist, int M, int nbits,
  * (gamma_hip_group_*) stays 8-bit.  gamma_hip_ivfpq_init keeps refusing nbits != 8. */
 int gamma_hip_ivfpq4_init(gamma_hip_index* h, int d, int nlist, int M, int metric, int bucket_init_size,
                           int bucket_max_size);
+/* ---- OPQ rotation ("opq": {"nsubvector": N} of the reference's IVFPQ model) ---------------------------------------
+ * Replaces faiss::OPQMatrix* opq_ as GammaIVFPQIndex uses it (index/impl/gamma_index_ivfpq.h:745, gamma_index_ivfpq.cc:
+ * 155-166): every vector is rotated before the coarse quantizer and the PQ encoder (Add :424-512, Update :375-422), every
+ * query before the coarse quantizer and the scan (:514-566); the exact re-rank (compute_dis :646-680) keeps reading the
+ * raw store with the raw query.
+ * Arithmetic (ours, fixed by contract; DESIGN.md "OPQ"): xt[i] = sum_j A[i*d + j] * x[j] as ONE fp32 accumulator starting
+ * at +0, j ascending, one fmaf per term -- independent of the batch size, of the row's position in the batch and of the
+ * kernel that serves the shape.  The reference's LinearTransform::apply_noalloc (faiss:VectorTransform.cpp:41-80) is one
+ * sgemm_ call whose summation order its BLAS picks from the shape: the same vector rotates to different bits there in
+ * Update (n = 1) and in Add, so there is no reference bit pattern to restate; within d fmaf roundings of the exact product
+ * both are.  Everything downstream of the rotated vectors stays the reference's bit for bit.
+ * _set: A is d x d row-major.  Valid on an 8-bit IVFPQ handle after gamma_hip_ivfpq_init while its lists are empty
+ *   (GAMMA_HIP_EINVAL once they hold entries: their codes are of unrotated vectors).  GAMMA_HIP_EUNSUPPORTED with a message on
+ *   an IVFFLAT, binary or 4-bit handle, on a list shard (gamma_hip_ivfpq_set_list_mask) and on a member of a group.
+ *   Afterwards gamma_hip_ivfpq_add, _encode, _encode_each, _update_batch and the searches gamma_hip_ivfpq_search,
+ *   _search_device, _search_device_wait rotate inside the library: their callers keep passing raw vectors.
+ *   gamma_hip_ivfpq_train, gamma_hip_kmeans and gamma_hip_assign take vectors as given (the reference hands them the rotated
+ *   set, gamma_index_ivfpq.cc:336-346); flat search is untouched.  GAMMA_HIP_EUNSUPPORTED with a message, never silent, on a
+ *   handle with a matrix: the shard, merge and export entry points, gamma_hip_ivfpq_coarse_device and
+ *   gamma_hip_ivfpq_set_list_mask.  A handle without a matrix takes exactly the paths it took before.
+ * _get: 1 and the matrix in A_out (may be NULL) when one is set, 0 when none is, < 0 on error.
+ * _apply: xt = x A^T for n host rows (the plugin rotates its training set with it); _apply_device: device pointers,
+ *   enqueued on the handle's stream, no sync, x and xt distinct.  GAMMA_HIP_EINVAL without a matrix. */
+int gamma_hip_opq_set(gamma_hip_index* h, const float* A);
+int gamma_hip_opq_get(gamma_hip_index* h, float* A_out);
+int gamma_hip_opq_apply(gamma_hip_index* h, int64_t n, const float* x, float* xt);
+int gamma_hip_opq_apply_device(gamma_hip_index* h, int64_t n, const float* d_x, float* d_xt);
+/* replaces OPQMatrix::train (faiss:VectorTransform.cpp:986-1200) as GammaIVFPQIndex::Indexing runs it on OPQMatrix(d, M_opq, d)
+ * (gamma_index_ivfpq.cc:155-166,336-340): at most 65536 points (rand_perm, seed 1234), centred; a random orthonormal start
+ * from a fixed seed; niter (<= 0: 50) alternations of { rotate; train an 8-bit PQ of M_opq sub-quantizers -- 256-centroid
+ * k-means, 40 iterations in the first alternation and 4 afterwards from the previous centroids, max_points_per_centroid 1000;
+ * encode and decode; the d x d cross-product of the set and its reconstruction; its orthogonal polar factor as the next
+ * rotation }.  The set stays on the device for the rotation, the k-means, the assignment, the decode and the cross-product;
+ * the polar factor is a one-sided Jacobi SVD in double on the host (in-tree: the library links no BLAS or LAPACK),
+ * orthonormalised in double and rounded once to fp32.  The library's sgeqrf / sgesvd are not bit-reproducible across thread
+ * counts (its own source says so, :997-1012), so parity with it is a matter of QUALITY -- the PQ error of the trained rotation
+ * lies within the spread of the library's own runs from different starts (tests/test_gpu_opq_train.py) -- while two calls on
+ * the same input return the same bytes.  x: n*d fp32 host, n >= 256 and d % M_opq == 0 (GAMMA_HIP_EINVAL with a message
+ * otherwise); A_out: d*d row-major, xt = A x; objective_out (may be NULL): mean squared PQ error of the last alternation.
+ * Needs no _init and changes nothing on the handle: set the result with gamma_hip_opq_set. */
+int gamma_hip_opq_train(gamma_hip_index* h, int d, int64_t n, const float* x, int M_opq, int niter, float* A_out,
+                        float* objective_out);
 /* quantizer->xb (nlist*d), pq.centroids (M*ksub*dsub), and the precomputed table
  * (faiss:IndexIVFPQ.cpp:412-479; NULL => computed on device with identical arithmetic) */
 int gamma_hip_ivfpq_set_trained(gamma_hip_index* h, const float* coarse_centroids,
