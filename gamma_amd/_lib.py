@@ -61,6 +61,8 @@ SYMBOLS = {
     "gamma_hip_term_count": (C.c_int64, [C.c_void_p, C.c_int]),
     "gamma_hip_term_update": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int32, C.POINTER(C.c_int32)]),
     "gamma_hip_raw_init": (C.c_int, [C.c_void_p, C.c_int]),
+    "gamma_hip_raw_init_f16": (C.c_int, [C.c_void_p, C.c_int]),
+    "gamma_hip_raw_elem_bytes": (C.c_int, [C.c_void_p]),
     "gamma_hip_raw_append": (C.c_int, [C.c_void_p, C.c_int64, f32p]),
     "gamma_hip_raw_update": (C.c_int, [C.c_void_p, C.c_int64, f32p]),
     "gamma_hip_ivfpq_arena_stats": (C.c_int, [C.c_void_p, i64p]),

@@ -126,9 +126,20 @@ class GammaHip:
                 self.L.gamma_hip_last_error(self.h).decode()))
 
     # ---- raw store / bitmap ----
-    def raw_init(self, d):
-        self._ck(self.L.gamma_hip_raw_init(self.h, d), "raw_init")
+    def raw_init(self, d, dtype="float32"):
+        """dtype "float16": rows of IEEE binary16 -- the writers round the caller's fp32, the exact re-rank of the IVFPQ
+        search reads the rounded rows (include/gamma_hip.h, gamma_hip_raw_init_f16)"""
+        if dtype == "float32":
+            self._ck(self.L.gamma_hip_raw_init(self.h, d), "raw_init")
+        elif dtype == "float16":
+            self._ck(self.L.gamma_hip_raw_init_f16(self.h, d), "raw_init_f16")
+        else:
+            raise ValueError("raw_init: dtype must be 'float32' or 'float16', not %r" % (dtype,))
         self.raw_d = d
+
+    def raw_elem_bytes(self):
+        """bytes per element of the raw store: 4, 2 (float16 rows) or 0 before raw_init"""
+        return int(self.L.gamma_hip_raw_elem_bytes(self.h))
 
     def raw_append(self, vecs):
         vecs = _f32(vecs)
@@ -174,6 +185,13 @@ class GammaHip:
     def raw_update(self, vid, vec):
         vec = _f32(vec)
         self._ck(self.L.gamma_hip_raw_update(self.h, vid, _p(vec, _lib.f32p)), "raw_update")
+
+    def raw_update_batch(self, vids, vecs):
+        """rows vids[i] rewritten with vecs[i], one wait for the device (vids the store has not reached are skipped)"""
+        vids = np.ascontiguousarray(vids, dtype=np.int64).ravel()
+        vecs = _f32(vecs)
+        self._ck(self.L.gamma_hip_raw_update_batch(self.h, len(vids), _p(vids, _lib.i64p), _p(vecs, _lib.f32p)),
+                 "raw_update_batch")
 
     def raw_gets(self, vids):
         """VectorReader::Gets: rows of the device store by vector id"""

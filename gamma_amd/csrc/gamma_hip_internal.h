@@ -193,6 +193,13 @@ struct gamma_hip_index {
     int raw_d = 0;
     float* d_raw = nullptr;
     int64_t nraw = 0, raw_cap = 0;
+    // gamma_hip_raw_init_f16: rows of IEEE binary16 behind a pointer of their own -- d_raw stays null, so a reader that was
+    // not taught the half rows fails its "needs the raw store" check instead of misreading bytes.  Same growth machinery,
+    // rows of 2 * raw_d bytes; the writers round the caller's fp32 on the writer stream (store_kernels.hip).
+    bool raw_half = false;
+    uint16_t* d_raw_h = nullptr;
+    size_t raw_esz() const { return raw_half ? sizeof(uint16_t) : sizeof(float); }
+    bool has_raw_rows() const { return d_raw != nullptr || d_raw_h != nullptr; }
     // raw vectors SHARDED with their lists (gamma_hip_raw_put, round 6): the store holds the rows of the vectors in this shard's
     // lists only, in arrival order; raw_slot[vid] = row (-1: held by another shard).  Such a handle re-ranks nothing by itself --
     // has_rank searches, flat search and raw_gets refuse -- it serves _shard_exact / _shard_export_exact.

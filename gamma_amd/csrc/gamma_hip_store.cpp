@@ -717,28 +717,47 @@ int64_t gamma_hip_term_count(gamma_hip_index* h, int field_id) {
     return it == h->terms.end() ? 0 : it->second.ndocs;
 }
 
-int gamma_hip_raw_init(gamma_hip_index* h, int d) {
+static const char* const kHalfStore = "the raw store holds float16 rows (gamma_hip_raw_init_f16)";
+
+// the rows, whichever element type the store was initialised with
+static inline char* raw_rows(H* h) { return h->raw_half ? reinterpret_cast<char*>(h->d_raw_h) : reinterpret_cast<char*>(h->d_raw); }
+static inline void raw_rows_set(H* h, void* p) {
+    if (h->raw_half) h->d_raw_h = reinterpret_cast<uint16_t*>(p);
+    else h->d_raw = reinterpret_cast<float*>(p);
+}
+
+static int raw_init_as(gamma_hip_index* h, int d, bool half) {
     if (!h || d <= 0) return GAMMA_HIP_EINVAL;
     WriteLock lk(h);
     if (h->raw_d != 0 && h->raw_d != d) return fail(h, GAMMA_HIP_EINVAL, "raw store dimension mismatch");
+    if (h->raw_d != 0 && h->raw_half != half) return fail(h, GAMMA_HIP_EINVAL, "the raw store's element type is fixed at its first init");
+    h->raw_half = half;
     if (h->raw_d == 0 && !getenv("GAMMA_HIP_NO_RAW_VMM")) {
         // reserve the address range the store may ever need (the device's memory): physical chunks are mapped into it
         // as rows arrive (raw_reserve).  Any failure -- here or of the FIRST chunk -- leaves the reallocating store.
         GH_CHECK(h, hipSetDevice(h->device));
         if (h->raw_vm.reserve(h->device, (size_t)64 << 20)) {   // chunks of whole 64 MB
             h->raw_vmm = true;
-            h->d_raw = reinterpret_cast<float*>(h->raw_vm.base);
+            raw_rows_set(h, h->raw_vm.base);
         }
     }
     h->raw_d = d;
     return GAMMA_HIP_OK;
 }
 
+int gamma_hip_raw_init(gamma_hip_index* h, int d) { return raw_init_as(h, d, false); }
+int gamma_hip_raw_init_f16(gamma_hip_index* h, int d) { return raw_init_as(h, d, true); }
+int gamma_hip_raw_elem_bytes(gamma_hip_index* h) {
+    if (!h) return GAMMA_HIP_EINVAL;
+    std::lock_guard<std::mutex> g(h->mu);
+    return h->raw_d > 0 ? (int)h->raw_esz() : 0;
+}
+
 static int raw_reserve(H* h, int64_t need) {
     if (need <= h->raw_cap) return GAMMA_HIP_OK;
     if (h->raw_vmm) {
         // map more physical memory behind the rows in place: nothing moves
-        const size_t row = (size_t)h->raw_d * sizeof(float);
+        const size_t row = (size_t)h->raw_d * h->raw_esz();
         const char* what = "";
         hipError_t e = h->raw_vm.map_to((size_t)need * row, &what);
         if (e == hipSuccess) {
@@ -749,21 +768,71 @@ static int raw_reserve(H* h, int64_t need) {
         // nothing is mapped yet: the range is given back and the store reallocates from here on
         h->raw_vm.release();
         h->raw_vmm = false;
-        h->d_raw = nullptr;
+        raw_rows_set(h, nullptr);
     }
     h->raw_regrows++;
     int64_t ncap = std::max<int64_t>(need, h->raw_cap + h->raw_cap / 2);
     ncap = std::max<int64_t>(ncap, 1024);
-    float* np = nullptr;
+    void* np = nullptr;
     if (h->wl) GH_CHECK(h, h->wl->exclusive());   // the old store is freed below
-    GH_CHECK(h, hipMalloc((void**)&np, (size_t)ncap * h->raw_d * sizeof(float)));
+    GH_CHECK(h, hipMalloc(&np, (size_t)ncap * h->raw_d * h->raw_esz()));
     if (h->nraw > 0)
-        GH_CHECK(h, hipMemcpyAsync(np, h->d_raw, (size_t)h->nraw * h->raw_d * sizeof(float),
+        GH_CHECK(h, hipMemcpyAsync(np, raw_rows(h), (size_t)h->nraw * h->raw_d * h->raw_esz(),
                                    hipMemcpyDeviceToDevice, h->wstream));
     GH_CHECK(h, hipStreamSynchronize(h->wstream));
-    if (h->d_raw) GH_CHECK(h, hipFree(h->d_raw));
-    h->d_raw = np;
+    if (raw_rows(h)) GH_CHECK(h, hipFree(raw_rows(h)));
+    raw_rows_set(h, np);
     h->raw_cap = ncap;
+    return GAMMA_HIP_OK;
+}
+
+// ---- float16 store: what the writers do instead of their copy --------------------------------------------------------
+// A finite fp32 value that rounds to an infinite half (|x| >= 65520: the midpoint of 65504 and 2^16 rounds to even = up) is an
+// error of the caller's, found before anything of the store changes.  NaN and +-inf pass: they are stored as they convert.
+static inline float half_bits_to_float(uint16_t b) {
+    const uint32_t sign = (uint32_t)(b & 0x8000u) << 16, e = (b >> 10) & 0x1fu, m = b & 0x3ffu;
+    uint32_t u;
+    if (e == 0x1fu) u = sign | 0x7f800000u | (m << 13);                       // inf, NaN (payload kept)
+    else if (e != 0) u = sign | ((e + 112u) << 23) | (m << 13);               // normal
+    else if (m == 0) u = sign;                                                // zero
+    else {                                                                    // subnormal half = m * 2^-24: a normal float
+        int s = 0;
+        uint32_t mm = m;
+        while (!(mm & 0x400u)) { mm <<= 1; s++; }
+        u = sign | ((uint32_t)(113 - s) << 23) | ((mm & 0x3ffu) << 13);
+    }
+    float f;
+    memcpy(&f, &u, sizeof(f));
+    return f;
+}
+
+static int raw_half_check(H* h, int64_t count, const float* v) {
+    for (int64_t i = 0; i < count; i++) {
+        const float a = fabsf(v[i]);
+        if (a >= 65520.f && a != INFINITY)
+            return fail(h, GAMMA_HIP_EINVAL, "raw store (float16): a finite value is outside binary16's range (|x| >= 65520); nothing was written");
+    }
+    return GAMMA_HIP_OK;
+}
+
+// n caller rows -> rows first, first + 1, .. (vids == nullptr) or rows vids[i] (those outside [0, nrows) are skipped) of the half
+// store: staged as fp32 through the writer's staging buffer in pieces, rounded by k_raw_rows_to_half on the writer stream.  The
+// caller has checked the values, reserved the rows and waits for the stream.
+static int raw_half_rows_in(H* h, int64_t first, const int64_t* vids, int64_t n, const float* vecs, int64_t nrows) {
+    const int d = h->raw_d;
+    const int64_t piece = std::max<int64_t>(1, ((int64_t)16 << 20) / d);   // 64 MB of fp32 per piece
+    GH_CHECK(h, h->we_stage.ensure((size_t)std::min(piece, n) * d * sizeof(float)));
+    if (vids) {
+        GH_CHECK(h, h->we_chk.ensure((size_t)n * sizeof(int64_t)));
+        GH_CHECK(h, hipMemcpyAsync(h->we_chk.p, vids, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, h->wstream));
+    }
+    for (int64_t i0 = 0; i0 < n; i0 += piece) {
+        const int64_t m = std::min(piece, n - i0);
+        GH_CHECK(h, hipMemcpyAsync(h->we_stage.p, vecs + i0 * d, (size_t)m * d * sizeof(float), hipMemcpyHostToDevice, h->wstream));
+        gh::launch_raw_rows_to_half(h->wstream, h->we_stage.as<float>(), vids ? h->we_chk.as<int64_t>() + i0 : nullptr, first + i0, m, d,
+                                    h->d_raw_h, nrows);
+    }
+    GH_CHECK(h, hipGetLastError());
     return GAMMA_HIP_OK;
 }
 
@@ -773,10 +842,14 @@ int gamma_hip_raw_append(gamma_hip_index* h, int64_t n, const float* vecs) {
     if (h->raw_d <= 0) return fail(h, GAMMA_HIP_EINVAL, "raw store not initialised");
     if (h->raw_sparse) return fail(h, GAMMA_HIP_EUNSUPPORTED, "the raw store holds this shard's rows only (gamma_hip_raw_put)");
     if (n == 0) return GAMMA_HIP_OK;
+    if (h->raw_half) GH_TRY(raw_half_check(h, n * h->raw_d, vecs));
     GH_CHECK(h, hipSetDevice(h->device));
     GH_TRY(raw_reserve(h, h->nraw + n));
-    GH_CHECK(h, hipMemcpyAsync(h->d_raw + h->nraw * h->raw_d, vecs, (size_t)n * h->raw_d * sizeof(float),
-                               hipMemcpyHostToDevice, h->wstream));
+    if (h->raw_half)
+        GH_TRY(raw_half_rows_in(h, h->nraw, nullptr, n, vecs, h->raw_cap));
+    else
+        GH_CHECK(h, hipMemcpyAsync(h->d_raw + h->nraw * h->raw_d, vecs, (size_t)n * h->raw_d * sizeof(float),
+                                   hipMemcpyHostToDevice, h->wstream));
     GH_CHECK(h, hipStreamSynchronize(h->wstream));
     h->nraw += n;
     return GAMMA_HIP_OK;
@@ -814,6 +887,7 @@ int gamma_hip_raw_put(gamma_hip_index* h, int64_t n, const int64_t* vids, const 
     if (!h || n < 0 || (n > 0 && (!vids || !vecs))) return GAMMA_HIP_EINVAL;
     WriteLock lk(h);
     if (h->raw_d <= 0) return fail(h, GAMMA_HIP_EINVAL, "raw store not initialised");
+    if (h->raw_half) return fail(h, GAMMA_HIP_EUNSUPPORTED, kHalfStore);   // rows sharded with their lists are fp32
     if (!h->raw_sparse && h->nraw > 0) return fail(h, GAMMA_HIP_EINVAL, "raw_put on a store that holds rows by vector id");
     if (n == 0) {   // the first call turns the empty store into the sparse form, rows or not (a shard that owns no vector yet)
         if (!h->raw_sparse) {
@@ -898,6 +972,7 @@ int gamma_hip_raw_put(gamma_hip_index* h, int64_t n, const int64_t* vids, const 
 int gamma_hip_raw_drop(gamma_hip_index* h, int64_t n, const int64_t* vids) {
     if (!h || n < 0 || (n > 0 && !vids)) return GAMMA_HIP_EINVAL;
     WriteLock lk(h);
+    if (h->raw_half) return fail(h, GAMMA_HIP_EUNSUPPORTED, kHalfStore);
     if (!h->raw_sparse) {
         if (h->nraw > 0) return fail(h, GAMMA_HIP_EINVAL, "raw_drop on a store that holds rows by vector id");
         return GAMMA_HIP_OK;   // empty: nothing to forget
@@ -934,11 +1009,11 @@ int gamma_hip_raw_clear(gamma_hip_index* h) {
             h->vm_retired.push_back(std::move(h->raw_vm));
             h->raw_vm = VmRange();
             h->raw_vmm = false;
-            h->d_raw = nullptr;
+            raw_rows_set(h, nullptr);
         }
-    } else if (h->d_raw) {
-        GH_CHECK(h, hipFree(h->d_raw));
-        h->d_raw = nullptr;
+    } else if (raw_rows(h)) {
+        GH_CHECK(h, hipFree(raw_rows(h)));
+        raw_rows_set(h, nullptr);
     }
     if (h->d_raw_slot) GH_CHECK(h, hipFree(h->d_raw_slot));
     h->d_raw_slot = nullptr;
@@ -966,10 +1041,14 @@ int gamma_hip_raw_write(gamma_hip_index* h, int64_t first_vid, int64_t n, const 
     if (h->raw_d <= 0) return fail(h, GAMMA_HIP_EINVAL, "raw store not initialised");
     if (first_vid > h->nraw) return fail(h, GAMMA_HIP_EINVAL, "raw write would leave a gap");
     if (n == 0) return GAMMA_HIP_OK;
+    if (h->raw_half) GH_TRY(raw_half_check(h, n * h->raw_d, vecs));
     GH_CHECK(h, hipSetDevice(h->device));
     GH_TRY(raw_reserve(h, first_vid + n));
-    GH_CHECK(h, hipMemcpyAsync(h->d_raw + first_vid * h->raw_d, vecs, (size_t)n * h->raw_d * sizeof(float),
-                               hipMemcpyHostToDevice, h->wstream));
+    if (h->raw_half)
+        GH_TRY(raw_half_rows_in(h, first_vid, nullptr, n, vecs, h->raw_cap));
+    else
+        GH_CHECK(h, hipMemcpyAsync(h->d_raw + first_vid * h->raw_d, vecs, (size_t)n * h->raw_d * sizeof(float),
+                                   hipMemcpyHostToDevice, h->wstream));
     GH_CHECK(h, hipStreamSynchronize(h->wstream));
     h->nraw = std::max(h->nraw, first_vid + n);
     return GAMMA_HIP_OK;
@@ -980,9 +1059,13 @@ int gamma_hip_raw_update(gamma_hip_index* h, int64_t vid, const float* vec) {
     WriteLock lk(h);
     if (h->raw_sparse) return fail(h, GAMMA_HIP_EUNSUPPORTED, "the raw store holds this shard's rows only (gamma_hip_raw_put)");
     if (vid < 0 || vid >= h->nraw) return fail(h, GAMMA_HIP_EINVAL, "vid out of range");
+    if (h->raw_half) GH_TRY(raw_half_check(h, h->raw_d, vec));
     GH_CHECK(h, hipSetDevice(h->device));
-    GH_CHECK(h, hipMemcpyAsync(h->d_raw + vid * h->raw_d, vec, (size_t)h->raw_d * sizeof(float),
-                               hipMemcpyHostToDevice, h->wstream));
+    if (h->raw_half)
+        GH_TRY(raw_half_rows_in(h, vid, nullptr, 1, vec, h->nraw));
+    else
+        GH_CHECK(h, hipMemcpyAsync(h->d_raw + vid * h->raw_d, vec, (size_t)h->raw_d * sizeof(float),
+                                   hipMemcpyHostToDevice, h->wstream));
     GH_CHECK(h, hipStreamSynchronize(h->wstream));
     return GAMMA_HIP_OK;
 }
@@ -993,6 +1076,22 @@ int gamma_hip_raw_update_batch(gamma_hip_index* h, int64_t n, const int64_t* vid
     if (n == 0) return GAMMA_HIP_OK;
     WriteLock lk(h);
     if (h->raw_sparse) return fail(h, GAMMA_HIP_EUNSUPPORTED, "the raw store holds this shard's rows only (gamma_hip_raw_put)");
+    if (h->raw_half) {
+        for (int64_t i = 0; i < n; i++)
+            if (vids[i] >= 0 && vids[i] < h->nraw) GH_TRY(raw_half_check(h, h->raw_d, vecs + i * h->raw_d));
+        // one kernel writes all rows: of a vid named twice the last entry wins, as with the fp32 store's ordered copies
+        std::vector<int64_t> v(vids, vids + n);
+        std::unordered_map<int64_t, int64_t> last;
+        for (int64_t i = 0; i < n; i++) {
+            auto it = last.find(v[i]);
+            if (it != last.end()) v[it->second] = -1;
+            last[v[i]] = i;
+        }
+        GH_CHECK(h, hipSetDevice(h->device));
+        GH_TRY(raw_half_rows_in(h, 0, v.data(), n, vecs, h->nraw));
+        GH_CHECK(h, hipStreamSynchronize(h->wstream));
+        return GAMMA_HIP_OK;
+    }
     GH_CHECK(h, hipSetDevice(h->device));
     for (int64_t i = 0; i < n; i++) {
         if (vids[i] < 0 || vids[i] >= h->nraw) continue;
@@ -1014,6 +1113,15 @@ int gamma_hip_raw_gets(gamma_hip_index* h, int64_t n, const int64_t* vids, float
     for (int64_t i = 0; i < n; i++)
         if (vids[i] < 0 || vids[i] >= h->nraw) return fail(h, GAMMA_HIP_EINVAL, "vid out of range");
     GH_CHECK(h, hipSetDevice(h->device));
+    if (h->raw_half) {   // the half rows come back as they are and are widened here (exact)
+        std::vector<uint16_t> hb((size_t)n * h->raw_d);
+        for (int64_t i = 0; i < n; i++)
+            GH_CHECK(h, hipMemcpyAsync(hb.data() + i * h->raw_d, h->d_raw_h + vids[i] * h->raw_d, (size_t)h->raw_d * sizeof(uint16_t),
+                                       hipMemcpyDeviceToHost, h->wstream));
+        GH_CHECK(h, hipStreamSynchronize(h->wstream));
+        for (size_t i = 0; i < hb.size(); i++) out[i] = half_bits_to_float(hb[i]);
+        return GAMMA_HIP_OK;
+    }
     for (int64_t i = 0; i < n; i++)
         GH_CHECK(h, hipMemcpyAsync(out + i * h->raw_d, h->d_raw + vids[i] * h->raw_d, (size_t)h->raw_d * sizeof(float),
                                    hipMemcpyDeviceToHost, h->wstream));

@@ -368,6 +368,14 @@ void launch_rerank_topk(hipStream_t s, bool l2, const float* x, int nq, int d, c
                         float max_score, float neutral, float* distances, int64_t* labels,
                         const int* qperm = nullptr,   // qperm: run the queries in this order (speed only)
                         const TieFlags* ties = nullptr);
+// float16 raw store (gamma_hip_raw_init_f16): the two re-rank launches over rows of IEEE binary16 -- the exact distance is that
+// of the fp32 query and float(half row) in the same operation order.  Rows with d % 8 == 0 are 16-byte aligned and read with
+// one 16-byte load per lane; every other d with 2-byte loads.
+void launch_rerank_dist_h(hipStream_t s, bool l2, const float* x, int nq, int d, const uint16_t* raw, int64_t nraw,
+                          const int64_t* cand_ids, int R, float min_score, float max_score, float* out);
+void launch_rerank_topk_h(hipStream_t s, bool l2, const float* x, int nq, int d, const uint16_t* raw, int64_t nraw,
+                          const int64_t* cand_ids, int R, int k, float min_score, float max_score, float neutral, float* distances,
+                          int64_t* labels, const int* qperm = nullptr, const TieFlags* ties = nullptr);
 // what k_tie_replay needs to redo one query (ties.hip)
 struct TieReplayArgs {
     const int* list;              // flagged queries, *count of them
@@ -404,6 +412,7 @@ struct TieReplayArgs {
     int compact_rows = 0;         // slab row i belongs to the i-th flagged query (list[i]) instead of query i
     int always_sliced = 0;        // ready == nullptr: every query is first G slab entries + slices 1.. (flat search with the
                                   // running bound: first row chunk + the candidates each later pass emitted)
+    const uint16_t* raw_h = nullptr;   // float16 raw store: the rows (raw is null then); launch_tie_replay takes the half-row kernels
 };
 int tie_replay_max_k();
 int tie_small_max_k();
@@ -457,6 +466,9 @@ void launch_mark_moved(hipStream_t s, int64_t* ids, int64_t pos);
 // sparse raw store: pairs [n][2] = (vector id, row); the vid -> row table's entries, and the staged rows into their rows
 void launch_raw_slot_scatter(hipStream_t s, const int32_t* pairs, int64_t n, int32_t* tab, int64_t ntab);
 void launch_raw_rows_scatter(hipStream_t s, const float* stage, const int32_t* pairs, int64_t n, int d, float* raw, int64_t cap);
+// float16 raw store: n staged fp32 rows rounded to binary16 into rows first + i, or vids[i] (outside [0, nrows): skipped)
+void launch_raw_rows_to_half(hipStream_t s, const float* stage, const int64_t* vids, int64_t first, int64_t n, int d, uint16_t* raw,
+                             int64_t nrows);
 void launch_list_checksum(hipStream_t s, const uint8_t* codes, const int64_t* ids, const int64_t* off, const int* len, int nlist,
                           int M, int max_len, unsigned long long* out);
 void launch_repack_lists(hipStream_t s, const uint8_t* oc, const int64_t* oi, uint8_t* nc, int64_t* ni,

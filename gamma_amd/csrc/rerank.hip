@@ -4,6 +4,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <type_traits>
 #include <utility>
 
 #include "block_utils.h"
@@ -58,10 +59,11 @@ void launch_map_candidates(hipStream_t s, const int* pos, int nq, int R, int P,
 // per candidate = the 8 lane accumulators of fvec_L2sqr / fvec_inner_product; the
 // cross-lane reduction mirrors extractf128 + add + 2x haddps.  grid = nq, block = 256
 // (32 candidates in flight).  Out-of-window scores and empty slots get the sentinel.
+// ROW = uint16_t: a float16 raw store (rerank_dev.h: the same arithmetic over the widened row).
 // ------------------------------------------------------------------------------------
-template <bool L2>
+template <bool L2, typename ROW = float>
 __global__ __launch_bounds__(256) void k_rerank_dist(const float* __restrict__ x, int d,
-                                                     const float* __restrict__ raw, int64_t nraw,
+                                                     const ROW* __restrict__ raw, int64_t nraw,
                                                      const int64_t* __restrict__ cand_ids, int R,
                                                      float min_score, float max_score,
                                                      float* __restrict__ out, const int32_t* __restrict__ slot, int64_t nslot) {
@@ -93,6 +95,17 @@ void launch_rerank_dist(hipStream_t s, bool l2, const float* x, int nq, int d, c
     else
         hipLaunchKernelGGL((k_rerank_dist<false>), dim3(nq, gy), dim3(256), 0, s, x, d, raw, nraw,
                            cand_ids, R, min_score, max_score, out, slot, nslot);
+}
+void launch_rerank_dist_h(hipStream_t s, bool l2, const float* x, int nq, int d, const uint16_t* raw, int64_t nraw,
+                          const int64_t* cand_ids, int R, float min_score, float max_score, float* out) {
+    if (nq <= 0) return;
+    const int gy = (R + 31) / 32;
+    if (l2)
+        hipLaunchKernelGGL((k_rerank_dist<true, uint16_t>), dim3(nq, gy), dim3(256), 0, s, x, d, raw, nraw, cand_ids, R, min_score,
+                           max_score, out, nullptr, (int64_t)0);
+    else
+        hipLaunchKernelGGL((k_rerank_dist<false, uint16_t>), dim3(nq, gy), dim3(256), 0, s, x, d, raw, nraw, cand_ids, R, min_score,
+                           max_score, out, nullptr, (int64_t)0);
 }
 
 // Exact distances of the entries of an exported candidate stream that can still be members of the recall_num-heap: ADC value
@@ -205,9 +218,10 @@ void launch_lookup_exact(hipStream_t s, bool l2, const float* all_dis, const int
 // distances keep the ADC order of the candidates -- and the first k go out with their ids
 // (empty slots: -1 / heap neutral).  R <= 1024.
 // ------------------------------------------------------------------------------------
-template <bool L2>
+// ROW = uint16_t: a float16 raw store (eight lanes per candidate as for fp32 rows; the row loads: rerank_dev.h).
+template <bool L2, typename ROW = float>
 __global__ __launch_bounds__(256) void k_rerank_topk(const float* __restrict__ x, int d,
-                                                     const float* __restrict__ raw, int64_t nraw,
+                                                     const ROW* __restrict__ raw, int64_t nraw,
                                                      const int64_t* __restrict__ cand_ids, int R, int k,
                                                      float min_score, float max_score, float neutral,
                                                      float* __restrict__ distances,
@@ -241,7 +255,19 @@ __global__ __launch_bounds__(256) void k_rerank_topk(const float* __restrict__ x
             s_it[r] = ((unsigned long long)key << 32) | (unsigned)r;
         }
     };
-    if (d == 128 && nraw > 0) {   // (nraw == 0: row 0 of the reserved range may not be mapped yet -- the predicated path below never touches it)
+    // every d of half rows, and the fp32 rows of a d other than 128: 32 candidates per round, eight lanes each
+    auto rounds_of_32 = [&]() {
+        for (int r0 = 0; r0 < R; r0 += 32) {
+            const int r = r0 + g;
+            int64_t id = -1;
+            if (r < R) id = s_id[r];
+            const bool live = id >= 0 && id < nraw;
+            put(r, live, rerank_dist8<L2>(xq, raw + (live ? id : 0) * d, d, l, live));
+        }
+    };
+    if constexpr (!std::is_same<ROW, float>::value) {
+        rounds_of_32();
+    } else if (d == 128 && nraw > 0) {   // (nraw == 0: row 0 of the reserved range may not be mapped yet -- the predicated path below never touches it)
         // d = 128 (C3, C4): the lane's 16 query elements stay in registers for all candidates (they were half of the loads), and TWO
         // candidates per group of 8 lanes are in flight -- the rows are 512 bytes from all over the raw store, the workgroup's seven
         // rounds of dependent row loads were what it waited for.  Same arithmetic as rerank_dist8 (rerank_dev.h): the lane's fma chain
@@ -280,13 +306,7 @@ __global__ __launch_bounds__(256) void k_rerank_topk(const float* __restrict__ x
             put(rb, lb, tb + __shfl_down(tb, 2, 8));
         }
     } else {
-        for (int r0 = 0; r0 < R; r0 += 32) {
-            const int r = r0 + g;
-            int64_t id = -1;
-            if (r < R) id = s_id[r];
-            const bool live = id >= 0 && id < nraw;
-            put(r, live, rerank_dist8<L2>(xq, raw + (live ? id : 0) * d, d, l, live));
-        }
+        rounds_of_32();
     }
     if (tf.list && threadIdx.x == 0) s_tie = tf.cut ? tf.cut[q] : 0;
     // Only the first k + 1 items are read below (the k results; whether two of the first k + 1 exact distances are equal).  Up to
@@ -389,6 +409,19 @@ void launch_rerank_topk(hipStream_t s, bool l2, const float* x, int nq, int d, c
     else
         hipLaunchKernelGGL((k_rerank_topk<false>), grid, dim3(256), 0, s, x, d, raw, nraw, cand_ids,
                            R, k, min_score, max_score, neutral, distances, labels, nq, qperm, tf);
+}
+void launch_rerank_topk_h(hipStream_t s, bool l2, const float* x, int nq, int d, const uint16_t* raw, int64_t nraw,
+                          const int64_t* cand_ids, int R, int k, float min_score, float max_score, float neutral, float* distances,
+                          int64_t* labels, const int* qperm, const TieFlags* ties) {
+    if (nq <= 0) return;
+    const dim3 grid((unsigned)(8 * ((nq + 7) / 8)));
+    const TieFlags tf = ties ? *ties : TieFlags{};
+    if (l2)
+        hipLaunchKernelGGL((k_rerank_topk<true, uint16_t>), grid, dim3(256), 0, s, x, d, raw, nraw, cand_ids, R, k, min_score,
+                           max_score, neutral, distances, labels, nq, qperm, tf);
+    else
+        hipLaunchKernelGGL((k_rerank_topk<false, uint16_t>), grid, dim3(256), 0, s, x, d, raw, nraw, cand_ids, R, k, min_score,
+                           max_score, neutral, distances, labels, nq, qperm, tf);
 }
 
 // ------------------------------------------------------------------------------------

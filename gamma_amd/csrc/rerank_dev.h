@@ -5,6 +5,7 @@
 // 4-lane and masked tails, (s0+s1)+(s2+s3).  All 8 threads of a group call it together (shuffles);
 // the result is valid on thread l8 == 0.  live == false: no loads, result unspecified.
 #pragma once
+#include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 
 namespace gh {
@@ -67,6 +68,117 @@ __device__ __forceinline__ float rerank_dist8(const float* __restrict__ xq, cons
     }
     const float t01 = s + __shfl_down(s, 1, 8);   // lane 0: s0+s1, lane 2: s2+s3
     return t01 + __shfl_down(t01, 2, 8);          // lane 0: (s0+s1)+(s2+s3)
+}
+
+// ---- rows of IEEE binary16 (gamma_hip_raw_init_f16) ------------------------------------------------------------------
+// The same distance over float(half row): the widening is exact, so the value is fvec_L2sqr / fvec_inner_product of the
+// fp32 query and the widened row, operation for operation.
+__device__ __forceinline__ float half_bits_f(uint32_t b) { return __half2float(__ushort_as_half((unsigned short)b)); }
+
+// d % 8 == 0 (rows are 16-byte aligned): lane m of the group loads 16 bytes = the 8 consecutive halves 64c + 8m .. + 7 of each
+// 64-element chunk c -- one full 128-byte line per candidate and request, where "lane l loads element l + 8u" with 2-byte
+// loads would ask for a quarter line per request.  Accumulator lane j needs the elements 64c + 8m + j, m = 0..7, in this order:
+// column j of the 8 x 8 matrix whose row m lane m holds.  Three butterfly exchanges transpose it (xor 4: 4-element blocks,
+// xor 2: element pairs = dwords, xor 1: the halves of a dword, packed two to a dword), six shuffles per 64 elements.
+__device__ __forceinline__ void half_rows_transpose8(const uint4 w, int l, uint32_t e[8]) {
+    const bool b4 = l & 4, b2 = l & 2, b1 = l & 1;
+    // xor 4: lanes 0-3 keep columns 0-3 of their row and get columns 0-3 of row l + 4; lanes 4-7 the other way round
+    const uint32_t r0 = __shfl_xor(b4 ? w.x : w.z, 4, 8), r1 = __shfl_xor(b4 ? w.y : w.w, 4, 8);
+    const uint32_t A0 = b4 ? r0 : w.x, A1 = b4 ? r1 : w.y;   // row (l & 3),     column pairs 0, 1 of the lane's column block
+    const uint32_t B0 = b4 ? w.z : r0, B1 = b4 ? w.w : r1;   // row (l & 3) + 4
+    // xor 2: one column pair of rows r, r + 2, r + 4, r + 6 (r = l & 1)
+    const uint32_t rA = __shfl_xor(b2 ? A0 : A1, 2, 8), rB = __shfl_xor(b2 ? B0 : B1, 2, 8);
+    const uint32_t P0 = b2 ? rA : A0, P1 = b2 ? A1 : rA, P2 = b2 ? rB : B0, P3 = b2 ? B1 : rB;
+    // xor 1: the even lane keeps the low halves (its column) and sends the high ones, the odd lane the other way round
+    const uint32_t k0 = b1 ? P0 >> 16 : P0 & 0xffffu, k1 = b1 ? P1 >> 16 : P1 & 0xffffu;
+    const uint32_t k2 = b1 ? P2 >> 16 : P2 & 0xffffu, k3 = b1 ? P3 >> 16 : P3 & 0xffffu;
+    const uint32_t s0 = b1 ? P0 & 0xffffu : P0 >> 16, s1 = b1 ? P1 & 0xffffu : P1 >> 16;
+    const uint32_t s2 = b1 ? P2 & 0xffffu : P2 >> 16, s3 = b1 ? P3 & 0xffffu : P3 >> 16;
+    const uint32_t R0 = __shfl_xor(s0 | (s1 << 16), 1, 8), R1 = __shfl_xor(s2 | (s3 << 16), 1, 8);
+    const uint32_t g0 = R0 & 0xffffu, g1 = R0 >> 16, g2 = R1 & 0xffffu, g3 = R1 >> 16;   // the partner's rows r' + 2i, r' = 1 - r
+    e[0] = b1 ? g0 : k0; e[1] = b1 ? k0 : g0;
+    e[2] = b1 ? g1 : k1; e[3] = b1 ? k1 : g1;
+    e[4] = b1 ? g2 : k2; e[5] = b1 ? k2 : g2;
+    e[6] = b1 ? g3 : k3; e[7] = b1 ? k3 : g3;
+}
+
+// Same contract as rerank_dist8 above (all 8 threads of a group call it together, result on thread l == 0).
+template <bool L2>
+__device__ __forceinline__ float rerank_dist8(const float* __restrict__ xq, const uint16_t* __restrict__ v, int d,
+                                              int l, bool live) {
+    const int d8 = d & ~7;
+    float a = 0.f;
+    if ((d & 7) == 0) {   // (uniform) wide loads
+        // the row loads of four chunks (256 elements) are requested before the first transpose: the chains are sequential by
+        // construction, the loads need not be (d = 128: both of its loads at once, d = 768: three rounds instead of twelve)
+        for (int c0 = 0; c0 < d; c0 += 256) {
+            uint4 w[4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                w[u] = make_uint4(0u, 0u, 0u, 0u);
+                if (live && c0 + 64 * u + 8 * l < d) w[u] = *reinterpret_cast<const uint4*>(v + c0 + 64 * u + 8 * l);
+            }
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const int cu = c0 + 64 * u;
+                if (cu < d) {   // (uniform)
+                    float xx[8];
+#pragma unroll
+                    for (int m = 0; m < 8; m++) xx[m] = (live && cu + 8 * m < d) ? xq[cu + 8 * m + l] : 0.f;
+                    uint32_t e[8];
+                    half_rows_transpose8(w[u], l, e);
+#pragma unroll
+                    for (int m = 0; m < 8; m++) {
+                        if (cu + 8 * m < d) {   // (uniform) the last chunk of a d that is no multiple of 64 is short
+                            const float y = half_bits_f(e[m]);
+                            if (L2) {
+                                const float t = xx[m] - y;
+                                a = __builtin_fmaf(t, t, a);
+                            } else {
+                                a = __builtin_fmaf(xx[m], y, a);
+                            }
+                        }
+                    }
+                }
+            }
+        }
+    } else if (live) {   // rows aligned to 2 bytes only: element loads, lane l takes l, l + 8, ..
+        for (int i = l; i < d8; i += 8) {
+            const float y = half_bits_f(v[i]);
+            if (L2) {
+                const float t = xq[i] - y;
+                a = __builtin_fmaf(t, t, a);
+            } else {
+                a = __builtin_fmaf(xq[i], y, a);
+            }
+        }
+    }
+    float s = __shfl_down(a, 4, 8) + a;   // s[l] = acc[l+4] + acc[l] for l < 4
+    int rem = d - d8, i = d8;
+    if (live && rem >= 4) {
+        if (l < 4) {
+            const float y = half_bits_f(v[i + l]);
+            if (L2) {
+                const float t = xq[i + l] - y;
+                s = __builtin_fmaf(t, t, s);
+            } else {
+                s = __builtin_fmaf(xq[i + l], y, s);
+            }
+        }
+        i += 4;
+        rem -= 4;
+    }
+    if (live && l < rem) {
+        const float y = half_bits_f(v[i + l]);
+        if (L2) {
+            const float t = xq[i + l] - y;
+            s = __builtin_fmaf(t, t, s);
+        } else {
+            s = __builtin_fmaf(xq[i + l], y, s);
+        }
+    }
+    const float t01 = s + __shfl_down(s, 1, 8);
+    return t01 + __shfl_down(t01, 2, 8);
 }
 
 }  // namespace gh

@@ -1,5 +1,6 @@
 // store_kernels.hip -- kernels of the writers and the trainer: shard gathers, bitmap bits, superseded marks, arena repack,
 // per-code table sums of the filter pass, centroid sums of k-means, PQ encode.
+#include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -138,6 +139,40 @@ void launch_raw_rows_scatter(hipStream_t s, const float* stage, const int32_t* p
     } else {
         const int64_t tot = n * d;
         hipLaunchKernelGGL((k_raw_rows_scatter<float>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, stage, pr, n, d, raw, cap);
+    }
+}
+
+// float16 raw store (gamma_hip_raw_init_f16): the staged fp32 rows rounded to IEEE binary16 -- round to nearest even, subnormal
+// halves kept (the wave's fp16 denormal mode is on by default), NaN / inf as they convert -- into rows first + i, or vids[i]
+// when vids is given (a vid outside [0, nrows) is skipped; rows >= nrows are never written).  Row pairs of elements go out as
+// one dword where the row is even-aligned (d even), single halves otherwise.
+template <bool PAIR>
+__global__ __launch_bounds__(256) void k_raw_rows_to_half(const float* __restrict__ stage, const int64_t* __restrict__ vids, int64_t first,
+                                                          int64_t n, int d, uint16_t* __restrict__ raw, int64_t nrows) {
+    const int dv = PAIR ? d >> 1 : d;
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n * dv) return;
+    const int64_t i = t / dv;
+    const int c = (int)(t - i * dv);
+    const int64_t row = vids ? vids[i] : first + i;
+    if (row < 0 || row >= nrows) return;
+    if (PAIR) {
+        const float2 f = reinterpret_cast<const float2*>(stage)[t];   // (d even: element pairs never straddle rows)
+        const uint32_t lo = __half_as_ushort(__float2half_rn(f.x)), hi = __half_as_ushort(__float2half_rn(f.y));
+        reinterpret_cast<uint32_t*>(raw)[row * dv + c] = lo | (hi << 16);
+    } else {
+        raw[row * d + c] = __half_as_ushort(__float2half_rn(stage[t]));
+    }
+}
+void launch_raw_rows_to_half(hipStream_t s, const float* stage, const int64_t* vids, int64_t first, int64_t n, int d, uint16_t* raw,
+                             int64_t nrows) {
+    if (n <= 0 || d <= 0 || nrows <= 0) return;
+    if ((d & 1) == 0) {
+        const int64_t tot = n * (d >> 1);
+        hipLaunchKernelGGL((k_raw_rows_to_half<true>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, stage, vids, first, n, d, raw, nrows);
+    } else {
+        const int64_t tot = n * d;
+        hipLaunchKernelGGL((k_raw_rows_to_half<false>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, stage, vids, first, n, d, raw, nrows);
     }
 }
 

@@ -99,6 +99,14 @@ int HIPIVFPQModelParams::Parse(const char *str) {
     }
     raw_sharded = !strcasecmp("sharded", rpl.c_str());
   }
+  std::string rdt;
+  if (!jp.GetString("raw_dtype", rdt)) {   // the device's raw rows: "float32" (the default) | "float16"
+    if (strcasecmp("float32", rdt.c_str()) && strcasecmp("float16", rdt.c_str())) {
+      HLOG("invalid raw_dtype = %s", rdt.c_str());
+      return -1;
+    }
+    raw_f16 = !strcasecmp("float16", rdt.c_str());
+  }
   if (!jp.GetInt("bucket_init_size", v)) {
     if (v < -1) return -1;
     if (v > 0) bucket_init_size = v;
@@ -163,6 +171,18 @@ int RegisterHIPOpq(const HIPOpqOps *ops) {
   return 0;
 }
 const HIPOpqOps *FindHIPOpq() { return OpqOps(); }
+
+namespace {
+HIPRawInitFn &RawInitF16() {
+  static HIPRawInitFn fn = nullptr;
+  return fn;
+}
+}  // namespace
+int RegisterHIPRawInitF16(HIPRawInitFn fn) {
+  RawInitF16() = fn;
+  return 0;
+}
+HIPRawInitFn FindHIPRawInitF16() { return RawInitF16(); }
 
 int RegisterHIPListsInit(int nbits, HIPListsInitFn fn) {
   ListsInits().push_back({nbits, fn});
@@ -263,12 +283,19 @@ int GammaIVFPQHIPIndex::Init(const std::string &model_parameters, int indexing_s
       return -2;
     }
   }
+  const HIPRawInitFn raw_init_f16 = pa.raw_f16 ? FindHIPRawInitF16() : nullptr;
+  if (pa.raw_f16 && (!raw_init_f16 || pa.devices.size() > 1)) {
+    HLOG("raw_dtype = float16 %s", raw_init_f16 ? "with several devices is not supported (the group's members hold fp32 rows)"
+                                                : "is not supported by this build of the plugin (it carries no float16 raw store)");
+    return -2;
+  }
+  raw_f16_ = pa.raw_f16;
   if (OpenDevices(pa.devices, pa.replicate)) return -1;
   int rc = ForAll([&](gamma_hip_index *m) {
     const int metric = metric_type_ == DistanceComputeType::L2 ? GAMMA_HIP_METRIC_L2 : GAMMA_HIP_METRIC_IP;
     int r = lists_init ? lists_init(m, d_, nlist_, M_, metric, pa.bucket_init_size, pa.bucket_max_size)
                        : gamma_hip_ivfpq_init(m, d_, nlist_, M_, 8, metric, pa.bucket_init_size, pa.bucket_max_size);
-    if (!r) r = gamma_hip_raw_init(m, d_);
+    if (!r) r = raw_init_f16 ? raw_init_f16(m, d_) : gamma_hip_raw_init(m, d_);
     if (!r) r = gamma_hip_set_exact_ties(m, pa.exact_ties ? 1 : 0);
     if (!r && pa.perf_stages) r = gamma_hip_profile_enable(m, 1);
     return r;
@@ -489,6 +516,11 @@ int GammaIVFPQHIPIndex::Search(RetrievalContext *retrieval_context, int n, const
     FillRangeFilters(cond, p, rf);
   const float *xq = reinterpret_cast<const float *>(x);
   int rc;
+  if (((cond && cond->brute_force_search) || !is_trained_) && raw_f16_) {
+    // the flat search reads fp32 rows, the device holds rounded ones: refused, never an answer over other rows
+    HLOG("brute_force_search (and the search of an untrained model) is not available with raw_dtype = float16");
+    return -3;
+  }
   if (((cond && cond->brute_force_search) || !is_trained_) && rawshard_) {
     // sharded rows: member 0 mirrors the store until the first Add after training; the mirror cannot go away under the
     // flat search (raw_mu_ through the call).  Afterwards no device holds every row: refused, never a wrong answer.

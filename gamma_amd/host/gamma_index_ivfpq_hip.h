@@ -67,6 +67,13 @@ struct HIPRawShardOps {
 int RegisterHIPRawShard(const HIPRawShardOps *ops);
 const HIPRawShardOps *FindHIPRawShard();
 
+// "raw_dtype": "float16": the raw store's initialiser for rows of IEEE binary16 (gamma_hip_raw_init_f16), registered at
+// static-initialisation time by gamma_index_ivfpq_rawf16_hip.cc -- the only host file that names it (the idiom of
+// RegisterHIPListsInit).  A build of the plugin without that file has none, and HIPIVFPQ::Init rejects the value.
+typedef int (*HIPRawInitFn)(gamma_hip_index *h, int d);
+int RegisterHIPRawInitF16(HIPRawInitFn fn);
+HIPRawInitFn FindHIPRawInitF16();
+
 // "opq": the rotation's entries of the C ABI (gamma_hip_opq_train / _set / _get / _apply) reach the model through this table,
 // registered at static-initialisation time by gamma_index_ivfpq_opq_hip.cc -- the only host file that names them.  A build of
 // the plugin without that file (against a C ABI without those entries) has no table, and HIPIVFPQ::Init rejects "opq".
@@ -100,6 +107,8 @@ struct HIPIVFPQModelParams {
                                  // the queries (results of one GPU bit for bit); "shard" (default): by IVF list
   bool raw_sharded = false;      // HIP only: "raw_placement": "sharded" -- with several devices and list placement every raw
                                  // vector lives once, on the device that owns its list; "replicated" (default): on all
+  bool raw_f16 = false;          // HIP only: "raw_dtype": "float16" -- the device's raw rows (what compute_dis reads) are IEEE
+                                 // binary16, rounded from the engine's fp32 on upload; "float32" (default).  One device only.
   int Parse(const char *str);   // 0 ok, -1 bad (same rules as gamma_index_ivfpq.h:708-851)
 };
 
@@ -169,6 +178,7 @@ class GammaIVFPQHIPIndex : public RetrievalModel {
   // vid, for the brute-force search of an untrained model; from then on (rows_sharded_) the group keeps every row at the
   // owner of its list, Add and Update hand the rows to the group, and a brute-force request is refused.
   const HIPRawShardOps *rawshard_ = nullptr;
+  bool raw_f16_ = false;               // "raw_dtype": "float16": no device holds fp32 rows -- brute-force search is refused
   bool rows_sharded_ = false;          // under raw_mu_
   // nbits_per_idx: 8, or 4 (16 centroids per sub-quantizer, two indices per code byte as faiss's PQEncoderGeneric packs them)
   int nbits_ = 8;

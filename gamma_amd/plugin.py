@@ -54,6 +54,7 @@ HOST_SYMBOLS = {
     "gh_iwpq_read_opq": (C.c_int64, [C.c_char_p, f32p, C.c_int64]),
     "gh_parse_ivfpq_model_params": (None, [C.c_char_p, C.POINTER(C.c_int)]),
     "gh_parse_ivfpq_retrieval_params": (None, [C.c_char_p, C.POINTER(C.c_int)]),
+    "gh_parse_ivfpq_raw_dtype": (None, [C.c_char_p, C.POINTER(C.c_int)]),
     "gh_model_registered": (C.c_int, [C.c_char_p]),
     "gh_iwpq_write": (C.c_int, [C.c_char_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, f32p, C.c_int, f32p,
                                 i64p, _lib.u8p, i64p]),
@@ -109,6 +110,13 @@ def parse_model_params(s):
     keys = ["rc", "ncentroids", "nsubvector", "nbits_per_idx", "nprobe", "metric", "bucket_init_size",
             "bucket_max_size", "has_hnsw", "has_opq"]
     return dict(zip(keys, list(out)))
+
+
+def parse_raw_dtype(s):
+    """(rc of HIPIVFPQModelParams::Parse, "float16" or "float32") for the model parameters s"""
+    out = (C.c_int * 2)()
+    load_host().gh_parse_ivfpq_raw_dtype(s.encode(), out)
+    return int(out[0]), "float16" if out[1] else "float32"
 
 
 def parse_retrieval_params(s):

@@ -251,6 +251,21 @@ int64_t gamma_hip_raw_count(gamma_hip_index* h);
  * grows in place (virtual memory management: physical chunks mapped behind the rows, nothing ever moves or waits for
  * the searches in flight -- what the reference gets from its 500 000-vector segments, vector/memory_raw_vector.cc:90-142)} */
 int gamma_hip_raw_stats(gamma_hip_index* h, int64_t* out4);
+/* A store of IEEE binary16 rows instead of gamma_hip_raw_init's fp32 rows: half the bytes held, half the bytes the exact
+ * re-rank gathers (the reference's lossy store of its own is "compress" / ZFP, vector/raw_vector.h:179-213, decompressed for
+ * compute_dis; this replaces MemoryRawVector's fp32 rows, vector/memory_raw_vector.cc:90-142, the same way).  The element type
+ * is fixed here.  The writers (raw_append / raw_write / raw_update / raw_update_batch) take fp32 and round on the writer
+ * stream: round to nearest even, subnormal halves kept -- what numpy's float32 -> float16 gives; a FINITE value whose half is
+ * infinite (|x| >= 65520) fails the call with GAMMA_HIP_EINVAL before anything of the store changes; NaN and +-inf are stored
+ * as they convert.  Only the store is rounded: training, assignment, residuals and codes see the caller's fp32.  The exact
+ * distance of a has_rank IVFPQ search is fvec_L2sqr / fvec_inner_product of the fp32 query and float(half row) (the widening
+ * is exact) in the reference's operation order, so given the rounded rows every result is the reference's, ties included.
+ * gamma_hip_raw_gets widens.  Served: gamma_hip_ivfpq_search and its device-pointer forms (8-bit, 4-bit, OPQ handles).
+ * GAMMA_HIP_EUNSUPPORTED: gamma_hip_raw_put / _raw_drop, flat and IVFFLAT search, gamma_hip_ivfpq_shard_exact /
+ * _shard_export_exact, _merge_rerank / _merge_replay with has_rank and no travelled distances. */
+int gamma_hip_raw_init_f16(gamma_hip_index* h, int d);
+/* bytes of one element of the raw store: 4 (gamma_hip_raw_init), 2 (gamma_hip_raw_init_f16), 0 before either */
+int gamma_hip_raw_elem_bytes(gamma_hip_index* h);
 
 /* ---- delete bitmap (bitmap::BitmapManager, util/bitmap_manager.cc:171-192): bit = docid,
  *      byte docid>>3, mask 1<<(docid&7) --------------------------------------------------- */
