@@ -133,13 +133,21 @@ class GammaHip:
             self._ck(self.L.gamma_hip_raw_init(self.h, d), "raw_init")
         elif dtype == "float16":
             self._ck(self.L.gamma_hip_raw_init_f16(self.h, d), "raw_init_f16")
+        elif dtype in ("uint8", "int8"):
+            # rows of one byte per element: the writers store a value only if it converts exactly, and refuse the call otherwise
+            # (include/gamma_hip.h, gamma_hip_raw_init_i8)
+            self._ck(self.L.gamma_hip_raw_init_i8(self.h, d, 1 if dtype == "int8" else 0), "raw_init_i8")
         else:
-            raise ValueError("raw_init: dtype must be 'float32' or 'float16', not %r" % (dtype,))
+            raise ValueError("raw_init: dtype must be 'float32', 'float16', 'uint8' or 'int8', not %r" % (dtype,))
         self.raw_d = d
 
     def raw_elem_bytes(self):
-        """bytes per element of the raw store: 4, 2 (float16 rows) or 0 before raw_init"""
+        """bytes per element of the raw store: 4, 2 (float16 rows), 1 (uint8 / int8 rows) or 0 before raw_init"""
         return int(self.L.gamma_hip_raw_elem_bytes(self.h))
+
+    def raw_elem_type(self):
+        """element type of the raw store: 0 float32, 1 float16, 2 uint8, 3 int8"""
+        return int(self.L.gamma_hip_raw_elem_type(self.h))
 
     def raw_append(self, vecs):
         vecs = _f32(vecs)

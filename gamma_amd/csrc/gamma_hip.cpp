@@ -117,6 +117,7 @@ int gamma_hip_destroy(gamma_hip_index* h) {
         h->raw_vm.release();
         h->d_raw = nullptr;
         h->d_raw_h = nullptr;
+        h->d_raw_b = nullptr;
     }
     // (release() of a range that was never reserved does nothing; an arena that left virtual memory management after a
     //  failed repack read-back still owns its reserved ranges)
@@ -133,7 +134,7 @@ int gamma_hip_destroy(gamma_hip_index* h) {
         h->d_sums = nullptr;
     }
     if (h->d_raw_slot) (void)hipFree(h->d_raw_slot);
-    void* ptrs[] = {h->d_list_rank, h->d_raw, h->d_raw_h, h->d_bitmap, h->d_cc, h->d_cc_norms, h->d_pqc, h->d_T2, h->d_codes,
+    void* ptrs[] = {h->d_list_rank, h->d_raw, h->d_raw_h, h->d_raw_b, h->d_bitmap, h->d_cc, h->d_cc_norms, h->d_pqc, h->d_T2, h->d_codes,
                     h->d_ids, h->d_list_mask, h->d_scan_codes, h->d_tie_stats, h->d_v2d, h->d_sums, h->d_t2max, h->d_bound_stat,
                     h->d_bin_cc, h->d_bin_stats, h->d_cc_img, h->d_cbf_stat, h->d_opq};
     for (void* p : ptrs)

@@ -198,8 +198,13 @@ struct gamma_hip_index {
     // rows of 2 * raw_d bytes; the writers round the caller's fp32 on the writer stream (store_kernels.hip).
     bool raw_half = false;
     uint16_t* d_raw_h = nullptr;
-    size_t raw_esz() const { return raw_half ? sizeof(uint16_t) : sizeof(float); }
-    bool has_raw_rows() const { return d_raw != nullptr || d_raw_h != nullptr; }
+    // gamma_hip_raw_init_i8: rows of one byte per element, uint8 (raw_byte = 1) or int8 (2), behind a third pointer for the same
+    // reason; rows of raw_d bytes.  The writers take fp32 that converts exactly, checked on the host (gamma_hip_raw_i8_check).
+    int raw_byte = 0;
+    uint8_t* d_raw_b = nullptr;
+    size_t raw_esz() const { return raw_byte ? 1 : raw_half ? sizeof(uint16_t) : sizeof(float); }
+    bool has_raw_rows() const { return d_raw != nullptr || d_raw_h != nullptr || d_raw_b != nullptr; }
+    int raw_elem_type() const { return raw_byte ? 1 + raw_byte : raw_half ? 1 : 0; }   // 0 fp32, 1 float16, 2 uint8, 3 int8
     // raw vectors SHARDED with their lists (gamma_hip_raw_put, round 6): the store holds the rows of the vectors in this shard's
     // lists only, in arrival order; raw_slot[vid] = row (-1: held by another shard).  Such a handle re-ranks nothing by itself --
     // has_rank searches, flat search and raw_gets refuse -- it serves _shard_exact / _shard_export_exact.

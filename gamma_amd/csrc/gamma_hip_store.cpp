@@ -718,20 +718,26 @@ int64_t gamma_hip_term_count(gamma_hip_index* h, int field_id) {
 }
 
 static const char* const kHalfStore = "the raw store holds float16 rows (gamma_hip_raw_init_f16)";
+static const char* const kByteStore = "the raw store holds 8-bit rows (gamma_hip_raw_init_i8)";
 
 // the rows, whichever element type the store was initialised with
-static inline char* raw_rows(H* h) { return h->raw_half ? reinterpret_cast<char*>(h->d_raw_h) : reinterpret_cast<char*>(h->d_raw); }
+static inline char* raw_rows(H* h) {
+    return h->raw_byte ? reinterpret_cast<char*>(h->d_raw_b) : h->raw_half ? reinterpret_cast<char*>(h->d_raw_h) : reinterpret_cast<char*>(h->d_raw);
+}
 static inline void raw_rows_set(H* h, void* p) {
-    if (h->raw_half) h->d_raw_h = reinterpret_cast<uint16_t*>(p);
+    if (h->raw_byte) h->d_raw_b = reinterpret_cast<uint8_t*>(p);
+    else if (h->raw_half) h->d_raw_h = reinterpret_cast<uint16_t*>(p);
     else h->d_raw = reinterpret_cast<float*>(p);
 }
 
-static int raw_init_as(gamma_hip_index* h, int d, bool half) {
+// et: 0 fp32, 1 float16, 2 uint8, 3 int8 (gamma_hip_raw_elem_type)
+static int raw_init_as(gamma_hip_index* h, int d, int et) {
     if (!h || d <= 0) return GAMMA_HIP_EINVAL;
     WriteLock lk(h);
     if (h->raw_d != 0 && h->raw_d != d) return fail(h, GAMMA_HIP_EINVAL, "raw store dimension mismatch");
-    if (h->raw_d != 0 && h->raw_half != half) return fail(h, GAMMA_HIP_EINVAL, "the raw store's element type is fixed at its first init");
-    h->raw_half = half;
+    if (h->raw_d != 0 && h->raw_elem_type() != et) return fail(h, GAMMA_HIP_EINVAL, "the raw store's element type is fixed at its first init");
+    h->raw_half = et == 1;
+    h->raw_byte = et >= 2 ? et - 1 : 0;
     if (h->raw_d == 0 && !getenv("GAMMA_HIP_NO_RAW_VMM")) {
         // reserve the address range the store may ever need (the device's memory): physical chunks are mapped into it
         // as rows arrive (raw_reserve).  Any failure -- here or of the FIRST chunk -- leaves the reallocating store.
@@ -745,8 +751,14 @@ static int raw_init_as(gamma_hip_index* h, int d, bool half) {
     return GAMMA_HIP_OK;
 }
 
-int gamma_hip_raw_init(gamma_hip_index* h, int d) { return raw_init_as(h, d, false); }
-int gamma_hip_raw_init_f16(gamma_hip_index* h, int d) { return raw_init_as(h, d, true); }
+int gamma_hip_raw_init(gamma_hip_index* h, int d) { return raw_init_as(h, d, 0); }
+int gamma_hip_raw_init_f16(gamma_hip_index* h, int d) { return raw_init_as(h, d, 1); }
+int gamma_hip_raw_init_i8(gamma_hip_index* h, int d, int is_signed) { return raw_init_as(h, d, is_signed ? 3 : 2); }
+int gamma_hip_raw_elem_type(gamma_hip_index* h) {
+    if (!h) return GAMMA_HIP_EINVAL;
+    std::lock_guard<std::mutex> g(h->mu);
+    return h->raw_elem_type();
+}
 int gamma_hip_raw_elem_bytes(gamma_hip_index* h) {
     if (!h) return GAMMA_HIP_EINVAL;
     std::lock_guard<std::mutex> g(h->mu);
@@ -815,10 +827,43 @@ static int raw_half_check(H* h, int64_t count, const float* v) {
     return GAMMA_HIP_OK;
 }
 
+// ---- byte store (gamma_hip_raw_init_i8): lossless or refused ----------------------------------------------------------
+// A value is storable when it is finite, integral and inside the element type's range: exactly when float(T(x)) == x (-0.0
+// compares equal to 0 and is stored as 0).  The comparisons are false for NaN; +-inf and the fractions fail them or the trunc.
+int gamma_hip_raw_i8_check(const float* x, int64_t n, int is_signed, int64_t* first_bad) {
+    if (n < 0 || (n > 0 && !x)) return GAMMA_HIP_EINVAL;
+    const float lo = is_signed ? -128.f : 0.f, hi = is_signed ? 127.f : 255.f;
+    for (int64_t i = 0; i < n; i++) {
+        const float v = x[i];
+        if (!(v >= lo && v <= hi && v == truncf(v))) {
+            if (first_bad) *first_bad = i;
+            return GAMMA_HIP_EINVAL;
+        }
+    }
+    return GAMMA_HIP_OK;
+}
+
+// the writers' check in front of their reservation: base = the position of v[0] in the caller's array (for the message)
+static int raw_byte_check(H* h, int64_t count, const float* v, int64_t base = 0) {
+    int64_t bad = -1;
+    if (gamma_hip_raw_i8_check(v, count, h->raw_byte == 2, &bad) == GAMMA_HIP_OK) return GAMMA_HIP_OK;
+    char msg[256];
+    snprintf(msg, sizeof(msg), "raw store (%s, gamma_hip_raw_init_i8): value %g at position %lld (row %lld, element %lld) is not exactly storable; nothing was written",
+             h->raw_byte == 2 ? "int8" : "uint8", (double)v[bad], (long long)(base + bad), (long long)((base + bad) / h->raw_d),
+             (long long)((base + bad) % h->raw_d));
+    return fail(h, GAMMA_HIP_EINVAL, msg);
+}
+// the check of a writer's values for the store's element type (fp32 rows take everything)
+static int raw_narrow_check(H* h, int64_t count, const float* v) {
+    if (h->raw_byte) return raw_byte_check(h, count, v);
+    if (h->raw_half) return raw_half_check(h, count, v);
+    return GAMMA_HIP_OK;
+}
+
 // n caller rows -> rows first, first + 1, .. (vids == nullptr) or rows vids[i] (those outside [0, nrows) are skipped) of the half
-// store: staged as fp32 through the writer's staging buffer in pieces, rounded by k_raw_rows_to_half on the writer stream.  The
-// caller has checked the values, reserved the rows and waits for the stream.
-static int raw_half_rows_in(H* h, int64_t first, const int64_t* vids, int64_t n, const float* vecs, int64_t nrows) {
+// or byte store: staged as fp32 through the writer's staging buffer in pieces, converted by k_raw_rows_to_half / _to_bytes on the
+// writer stream.  The caller has checked the values, reserved the rows and waits for the stream.
+static int raw_narrow_rows_in(H* h, int64_t first, const int64_t* vids, int64_t n, const float* vecs, int64_t nrows) {
     const int d = h->raw_d;
     const int64_t piece = std::max<int64_t>(1, ((int64_t)16 << 20) / d);   // 64 MB of fp32 per piece
     GH_CHECK(h, h->we_stage.ensure((size_t)std::min(piece, n) * d * sizeof(float)));
@@ -829,8 +874,12 @@ static int raw_half_rows_in(H* h, int64_t first, const int64_t* vids, int64_t n,
     for (int64_t i0 = 0; i0 < n; i0 += piece) {
         const int64_t m = std::min(piece, n - i0);
         GH_CHECK(h, hipMemcpyAsync(h->we_stage.p, vecs + i0 * d, (size_t)m * d * sizeof(float), hipMemcpyHostToDevice, h->wstream));
-        gh::launch_raw_rows_to_half(h->wstream, h->we_stage.as<float>(), vids ? h->we_chk.as<int64_t>() + i0 : nullptr, first + i0, m, d,
-                                    h->d_raw_h, nrows);
+        if (h->raw_byte)
+            gh::launch_raw_rows_to_bytes(h->wstream, h->we_stage.as<float>(), vids ? h->we_chk.as<int64_t>() + i0 : nullptr, first + i0, m,
+                                         d, h->d_raw_b, nrows);
+        else
+            gh::launch_raw_rows_to_half(h->wstream, h->we_stage.as<float>(), vids ? h->we_chk.as<int64_t>() + i0 : nullptr, first + i0, m, d,
+                                        h->d_raw_h, nrows);
     }
     GH_CHECK(h, hipGetLastError());
     return GAMMA_HIP_OK;
@@ -842,11 +891,11 @@ int gamma_hip_raw_append(gamma_hip_index* h, int64_t n, const float* vecs) {
     if (h->raw_d <= 0) return fail(h, GAMMA_HIP_EINVAL, "raw store not initialised");
     if (h->raw_sparse) return fail(h, GAMMA_HIP_EUNSUPPORTED, "the raw store holds this shard's rows only (gamma_hip_raw_put)");
     if (n == 0) return GAMMA_HIP_OK;
-    if (h->raw_half) GH_TRY(raw_half_check(h, n * h->raw_d, vecs));
+    GH_TRY(raw_narrow_check(h, n * h->raw_d, vecs));
     GH_CHECK(h, hipSetDevice(h->device));
     GH_TRY(raw_reserve(h, h->nraw + n));
-    if (h->raw_half)
-        GH_TRY(raw_half_rows_in(h, h->nraw, nullptr, n, vecs, h->raw_cap));
+    if (h->raw_half || h->raw_byte)
+        GH_TRY(raw_narrow_rows_in(h, h->nraw, nullptr, n, vecs, h->raw_cap));
     else
         GH_CHECK(h, hipMemcpyAsync(h->d_raw + h->nraw * h->raw_d, vecs, (size_t)n * h->raw_d * sizeof(float),
                                    hipMemcpyHostToDevice, h->wstream));
@@ -888,6 +937,7 @@ int gamma_hip_raw_put(gamma_hip_index* h, int64_t n, const int64_t* vids, const 
     WriteLock lk(h);
     if (h->raw_d <= 0) return fail(h, GAMMA_HIP_EINVAL, "raw store not initialised");
     if (h->raw_half) return fail(h, GAMMA_HIP_EUNSUPPORTED, kHalfStore);   // rows sharded with their lists are fp32
+    if (h->raw_byte) return fail(h, GAMMA_HIP_EUNSUPPORTED, kByteStore);
     if (!h->raw_sparse && h->nraw > 0) return fail(h, GAMMA_HIP_EINVAL, "raw_put on a store that holds rows by vector id");
     if (n == 0) {   // the first call turns the empty store into the sparse form, rows or not (a shard that owns no vector yet)
         if (!h->raw_sparse) {
@@ -973,6 +1023,7 @@ int gamma_hip_raw_drop(gamma_hip_index* h, int64_t n, const int64_t* vids) {
     if (!h || n < 0 || (n > 0 && !vids)) return GAMMA_HIP_EINVAL;
     WriteLock lk(h);
     if (h->raw_half) return fail(h, GAMMA_HIP_EUNSUPPORTED, kHalfStore);
+    if (h->raw_byte) return fail(h, GAMMA_HIP_EUNSUPPORTED, kByteStore);
     if (!h->raw_sparse) {
         if (h->nraw > 0) return fail(h, GAMMA_HIP_EINVAL, "raw_drop on a store that holds rows by vector id");
         return GAMMA_HIP_OK;   // empty: nothing to forget
@@ -1041,11 +1092,11 @@ int gamma_hip_raw_write(gamma_hip_index* h, int64_t first_vid, int64_t n, const 
     if (h->raw_d <= 0) return fail(h, GAMMA_HIP_EINVAL, "raw store not initialised");
     if (first_vid > h->nraw) return fail(h, GAMMA_HIP_EINVAL, "raw write would leave a gap");
     if (n == 0) return GAMMA_HIP_OK;
-    if (h->raw_half) GH_TRY(raw_half_check(h, n * h->raw_d, vecs));
+    GH_TRY(raw_narrow_check(h, n * h->raw_d, vecs));
     GH_CHECK(h, hipSetDevice(h->device));
     GH_TRY(raw_reserve(h, first_vid + n));
-    if (h->raw_half)
-        GH_TRY(raw_half_rows_in(h, first_vid, nullptr, n, vecs, h->raw_cap));
+    if (h->raw_half || h->raw_byte)
+        GH_TRY(raw_narrow_rows_in(h, first_vid, nullptr, n, vecs, h->raw_cap));
     else
         GH_CHECK(h, hipMemcpyAsync(h->d_raw + first_vid * h->raw_d, vecs, (size_t)n * h->raw_d * sizeof(float),
                                    hipMemcpyHostToDevice, h->wstream));
@@ -1059,10 +1110,10 @@ int gamma_hip_raw_update(gamma_hip_index* h, int64_t vid, const float* vec) {
     WriteLock lk(h);
     if (h->raw_sparse) return fail(h, GAMMA_HIP_EUNSUPPORTED, "the raw store holds this shard's rows only (gamma_hip_raw_put)");
     if (vid < 0 || vid >= h->nraw) return fail(h, GAMMA_HIP_EINVAL, "vid out of range");
-    if (h->raw_half) GH_TRY(raw_half_check(h, h->raw_d, vec));
+    GH_TRY(raw_narrow_check(h, h->raw_d, vec));
     GH_CHECK(h, hipSetDevice(h->device));
-    if (h->raw_half)
-        GH_TRY(raw_half_rows_in(h, vid, nullptr, 1, vec, h->nraw));
+    if (h->raw_half || h->raw_byte)
+        GH_TRY(raw_narrow_rows_in(h, vid, nullptr, 1, vec, h->nraw));
     else
         GH_CHECK(h, hipMemcpyAsync(h->d_raw + vid * h->raw_d, vec, (size_t)h->raw_d * sizeof(float),
                                    hipMemcpyHostToDevice, h->wstream));
@@ -1076,9 +1127,12 @@ int gamma_hip_raw_update_batch(gamma_hip_index* h, int64_t n, const int64_t* vid
     if (n == 0) return GAMMA_HIP_OK;
     WriteLock lk(h);
     if (h->raw_sparse) return fail(h, GAMMA_HIP_EUNSUPPORTED, "the raw store holds this shard's rows only (gamma_hip_raw_put)");
-    if (h->raw_half) {
+    if (h->raw_half || h->raw_byte) {
         for (int64_t i = 0; i < n; i++)
-            if (vids[i] >= 0 && vids[i] < h->nraw) GH_TRY(raw_half_check(h, h->raw_d, vecs + i * h->raw_d));
+            if (vids[i] >= 0 && vids[i] < h->nraw) {
+                if (h->raw_byte) GH_TRY(raw_byte_check(h, h->raw_d, vecs + i * h->raw_d, i * h->raw_d));
+                else GH_TRY(raw_half_check(h, h->raw_d, vecs + i * h->raw_d));
+            }
         // one kernel writes all rows: of a vid named twice the last entry wins, as with the fp32 store's ordered copies
         std::vector<int64_t> v(vids, vids + n);
         std::unordered_map<int64_t, int64_t> last;
@@ -1088,7 +1142,7 @@ int gamma_hip_raw_update_batch(gamma_hip_index* h, int64_t n, const int64_t* vid
             last[v[i]] = i;
         }
         GH_CHECK(h, hipSetDevice(h->device));
-        GH_TRY(raw_half_rows_in(h, 0, v.data(), n, vecs, h->nraw));
+        GH_TRY(raw_narrow_rows_in(h, 0, v.data(), n, vecs, h->nraw));
         GH_CHECK(h, hipStreamSynchronize(h->wstream));
         return GAMMA_HIP_OK;
     }
@@ -1120,6 +1174,18 @@ int gamma_hip_raw_gets(gamma_hip_index* h, int64_t n, const int64_t* vids, float
                                        hipMemcpyDeviceToHost, h->wstream));
         GH_CHECK(h, hipStreamSynchronize(h->wstream));
         for (size_t i = 0; i < hb.size(); i++) out[i] = half_bits_to_float(hb[i]);
+        return GAMMA_HIP_OK;
+    }
+    if (h->raw_byte) {   // the byte rows come back as they are and are widened here (exact)
+        std::vector<uint8_t> bb((size_t)n * h->raw_d);
+        for (int64_t i = 0; i < n; i++)
+            GH_CHECK(h, hipMemcpyAsync(bb.data() + i * h->raw_d, h->d_raw_b + vids[i] * h->raw_d, (size_t)h->raw_d, hipMemcpyDeviceToHost,
+                                       h->wstream));
+        GH_CHECK(h, hipStreamSynchronize(h->wstream));
+        if (h->raw_byte == 2)
+            for (size_t i = 0; i < bb.size(); i++) out[i] = (float)(int8_t)bb[i];
+        else
+            for (size_t i = 0; i < bb.size(); i++) out[i] = (float)bb[i];
         return GAMMA_HIP_OK;
     }
     for (int64_t i = 0; i < n; i++)

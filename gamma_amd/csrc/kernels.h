@@ -376,6 +376,13 @@ void launch_rerank_dist_h(hipStream_t s, bool l2, const float* x, int nq, int d,
 void launch_rerank_topk_h(hipStream_t s, bool l2, const float* x, int nq, int d, const uint16_t* raw, int64_t nraw,
                           const int64_t* cand_ids, int R, int k, float min_score, float max_score, float neutral, float* distances,
                           int64_t* labels, const int* qperm = nullptr, const TieFlags* ties = nullptr);
+// byte raw store (gamma_hip_raw_init_i8): the same two launches over rows of uint8 (is_signed = false) or int8 elements, widened
+// exactly.  Rows with d % 16 == 0 are read with 16-byte loads, d % 4 == 0 with dword loads, every other d with byte loads.
+void launch_rerank_dist_b(hipStream_t s, bool l2, const float* x, int nq, int d, const uint8_t* raw, bool is_signed, int64_t nraw,
+                          const int64_t* cand_ids, int R, float min_score, float max_score, float* out);
+void launch_rerank_topk_b(hipStream_t s, bool l2, const float* x, int nq, int d, const uint8_t* raw, bool is_signed, int64_t nraw,
+                          const int64_t* cand_ids, int R, int k, float min_score, float max_score, float neutral, float* distances,
+                          int64_t* labels, const int* qperm = nullptr, const TieFlags* ties = nullptr);
 // what k_tie_replay needs to redo one query (ties.hip)
 struct TieReplayArgs {
     const int* list;              // flagged queries, *count of them
@@ -413,6 +420,8 @@ struct TieReplayArgs {
     int always_sliced = 0;        // ready == nullptr: every query is first G slab entries + slices 1.. (flat search with the
                                   // running bound: first row chunk + the candidates each later pass emitted)
     const uint16_t* raw_h = nullptr;   // float16 raw store: the rows (raw is null then); launch_tie_replay takes the half-row kernels
+    const uint8_t* raw_b = nullptr;    // byte raw store: the rows (raw and raw_h are null then), int8 when raw_b_signed, else uint8
+    int raw_b_signed = 0;
 };
 int tie_replay_max_k();
 int tie_small_max_k();
@@ -469,6 +478,10 @@ void launch_raw_rows_scatter(hipStream_t s, const float* stage, const int32_t* p
 // float16 raw store: n staged fp32 rows rounded to binary16 into rows first + i, or vids[i] (outside [0, nrows): skipped)
 void launch_raw_rows_to_half(hipStream_t s, const float* stage, const int64_t* vids, int64_t first, int64_t n, int d, uint16_t* raw,
                              int64_t nrows);
+// byte raw store: n staged fp32 rows (checked by the host: every value is exactly storable) converted into rows first + i, or
+// vids[i] (outside [0, nrows): skipped)
+void launch_raw_rows_to_bytes(hipStream_t s, const float* stage, const int64_t* vids, int64_t first, int64_t n, int d, uint8_t* raw,
+                              int64_t nrows);
 void launch_list_checksum(hipStream_t s, const uint8_t* codes, const int64_t* ids, const int64_t* off, const int* len, int nlist,
                           int M, int max_len, unsigned long long* out);
 void launch_repack_lists(hipStream_t s, const uint8_t* oc, const int64_t* oi, uint8_t* nc, int64_t* ni,

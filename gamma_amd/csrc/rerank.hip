@@ -60,6 +60,7 @@ void launch_map_candidates(hipStream_t s, const int* pos, int nq, int R, int P,
 // cross-lane reduction mirrors extractf128 + add + 2x haddps.  grid = nq, block = 256
 // (32 candidates in flight).  Out-of-window scores and empty slots get the sentinel.
 // ROW = uint16_t: a float16 raw store (rerank_dev.h: the same arithmetic over the widened row).
+// ROW = uint8_t / int8_t: a store of byte rows (gamma_hip_raw_init_i8), likewise.
 // ------------------------------------------------------------------------------------
 template <bool L2, typename ROW = float>
 __global__ __launch_bounds__(256) void k_rerank_dist(const float* __restrict__ x, int d,
@@ -106,6 +107,25 @@ void launch_rerank_dist_h(hipStream_t s, bool l2, const float* x, int nq, int d,
     else
         hipLaunchKernelGGL((k_rerank_dist<false, uint16_t>), dim3(nq, gy), dim3(256), 0, s, x, d, raw, nraw, cand_ids, R, min_score,
                            max_score, out, nullptr, (int64_t)0);
+}
+template <typename ROW>
+static void launch_rerank_dist_b_(hipStream_t s, bool l2, const float* x, int nq, int d, const ROW* raw, int64_t nraw,
+                                  const int64_t* cand_ids, int R, float min_score, float max_score, float* out) {
+    const int gy = (R + 31) / 32;
+    if (l2)
+        hipLaunchKernelGGL((k_rerank_dist<true, ROW>), dim3(nq, gy), dim3(256), 0, s, x, d, raw, nraw, cand_ids, R, min_score,
+                           max_score, out, nullptr, (int64_t)0);
+    else
+        hipLaunchKernelGGL((k_rerank_dist<false, ROW>), dim3(nq, gy), dim3(256), 0, s, x, d, raw, nraw, cand_ids, R, min_score,
+                           max_score, out, nullptr, (int64_t)0);
+}
+void launch_rerank_dist_b(hipStream_t s, bool l2, const float* x, int nq, int d, const uint8_t* raw, bool is_signed, int64_t nraw,
+                          const int64_t* cand_ids, int R, float min_score, float max_score, float* out) {
+    if (nq <= 0) return;
+    if (is_signed)
+        launch_rerank_dist_b_(s, l2, x, nq, d, reinterpret_cast<const int8_t*>(raw), nraw, cand_ids, R, min_score, max_score, out);
+    else
+        launch_rerank_dist_b_(s, l2, x, nq, d, raw, nraw, cand_ids, R, min_score, max_score, out);
 }
 
 // Exact distances of the entries of an exported candidate stream that can still be members of the recall_num-heap: ADC value
@@ -219,6 +239,7 @@ void launch_lookup_exact(hipStream_t s, bool l2, const float* all_dis, const int
 // (empty slots: -1 / heap neutral).  R <= 1024.
 // ------------------------------------------------------------------------------------
 // ROW = uint16_t: a float16 raw store (eight lanes per candidate as for fp32 rows; the row loads: rerank_dev.h).
+// ROW = uint8_t / int8_t: byte rows, eight lanes per candidate; d = 128 keeps the query in registers as the fp32 rows do.
 template <bool L2, typename ROW = float>
 __global__ __launch_bounds__(256) void k_rerank_topk(const float* __restrict__ x, int d,
                                                      const ROW* __restrict__ raw, int64_t nraw,
@@ -265,7 +286,62 @@ __global__ __launch_bounds__(256) void k_rerank_topk(const float* __restrict__ x
             put(r, live, rerank_dist8<L2>(xq, raw + (live ? id : 0) * d, d, l, live));
         }
     };
-    if constexpr (!std::is_same<ROW, float>::value) {
+    if constexpr (std::is_same<ROW, uint8_t>::value || std::is_same<ROW, int8_t>::value) {
+        if (d == 128 && nraw > 0) {
+            // the fp32 rows' d = 128 form over byte rows: the lane's 16 query elements in registers, two candidates per group in
+            // flight, a row = eight 16-byte loads that the group's lanes share (rerank_dev.h, rerank_dist8_bytes: lane l's elements
+            // l + 8u are byte l & 3 of the dwords (l >> 2) + 2u).  Same chain, same reduction.
+            constexpr bool SG = std::is_same<ROW, int8_t>::value;
+            const int sh = 8 * (l & 3);
+            const bool hi = l & 4;
+            float xx[16];
+#pragma unroll
+            for (int u = 0; u < 16; u++) xx[u] = xq[l + 8 * u];
+            for (int r0 = 0; r0 < R; r0 += 64) {
+                const int ra = r0 + g, rb = r0 + 32 + g;
+                const int64_t ida = ra < R ? s_id[ra] : -1, idb = rb < R ? s_id[rb] : -1;
+                const bool la = ida >= 0 && ida < nraw, lb = idb >= 0 && idb < nraw;
+                const uint4* va = reinterpret_cast<const uint4*>(raw + (la ? ida : 0) * 128);
+                const uint4* vb = reinterpret_cast<const uint4*>(raw + (lb ? idb : 0) * 128);
+                uint32_t ea[16], eb[16];   // the lane's dword of every 8 elements, picked as the chunk arrives
+#pragma unroll
+                for (int u = 0; u < 8; u++) {
+                    const uint4 w = va[u];
+                    const uint32_t wx = w.x, wy = w.y, wz = w.z, ww = w.w;
+                    ea[2 * u] = hi ? wy : wx;
+                    ea[2 * u + 1] = hi ? ww : wz;
+                }
+#pragma unroll
+                for (int u = 0; u < 8; u++) {
+                    const uint4 w = vb[u];
+                    const uint32_t wx = w.x, wy = w.y, wz = w.z, ww = w.w;
+                    eb[2 * u] = hi ? wy : wx;
+                    eb[2 * u + 1] = hi ? ww : wz;
+                }
+                float a = 0.f, b = 0.f;
+#pragma unroll
+                for (int u = 0; u < 16; u++) {
+                    const float fa = byte_row_f<SG>((ea[u] >> sh) & 0xffu), fb = byte_row_f<SG>((eb[u] >> sh) & 0xffu);
+                    if (L2) {
+                        const float ta = xx[u] - fa, tb = xx[u] - fb;
+                        a = __builtin_fmaf(ta, ta, a);
+                        b = __builtin_fmaf(tb, tb, b);
+                    } else {
+                        a = __builtin_fmaf(xx[u], fa, a);
+                        b = __builtin_fmaf(xx[u], fb, b);
+                    }
+                }
+                if (!la) a = 0.f;
+                if (!lb) b = 0.f;
+                const float sa = __shfl_down(a, 4, 8) + a, sb_ = __shfl_down(b, 4, 8) + b;
+                const float ta = sa + __shfl_down(sa, 1, 8), tb = sb_ + __shfl_down(sb_, 1, 8);
+                put(ra, la, ta + __shfl_down(ta, 2, 8));
+                put(rb, lb, tb + __shfl_down(tb, 2, 8));
+            }
+        } else {
+            rounds_of_32();
+        }
+    } else if constexpr (!std::is_same<ROW, float>::value) {
         rounds_of_32();
     } else if (d == 128 && nraw > 0) {   // (nraw == 0: row 0 of the reserved range may not be mapped yet -- the predicated path below never touches it)
         // d = 128 (C3, C4): the lane's 16 query elements stay in registers for all candidates (they were half of the loads), and TWO
@@ -422,6 +498,29 @@ void launch_rerank_topk_h(hipStream_t s, bool l2, const float* x, int nq, int d,
     else
         hipLaunchKernelGGL((k_rerank_topk<false, uint16_t>), grid, dim3(256), 0, s, x, d, raw, nraw, cand_ids, R, k, min_score,
                            max_score, neutral, distances, labels, nq, qperm, tf);
+}
+template <typename ROW>
+static void launch_rerank_topk_b_(hipStream_t s, bool l2, const float* x, int nq, int d, const ROW* raw, int64_t nraw,
+                                  const int64_t* cand_ids, int R, int k, float min_score, float max_score, float neutral,
+                                  float* distances, int64_t* labels, const int* qperm, const TieFlags& tf) {
+    const dim3 grid((unsigned)(8 * ((nq + 7) / 8)));
+    if (l2)
+        hipLaunchKernelGGL((k_rerank_topk<true, ROW>), grid, dim3(256), 0, s, x, d, raw, nraw, cand_ids, R, k, min_score,
+                           max_score, neutral, distances, labels, nq, qperm, tf);
+    else
+        hipLaunchKernelGGL((k_rerank_topk<false, ROW>), grid, dim3(256), 0, s, x, d, raw, nraw, cand_ids, R, k, min_score,
+                           max_score, neutral, distances, labels, nq, qperm, tf);
+}
+void launch_rerank_topk_b(hipStream_t s, bool l2, const float* x, int nq, int d, const uint8_t* raw, bool is_signed, int64_t nraw,
+                          const int64_t* cand_ids, int R, int k, float min_score, float max_score, float neutral, float* distances,
+                          int64_t* labels, const int* qperm, const TieFlags* ties) {
+    if (nq <= 0) return;
+    const TieFlags tf = ties ? *ties : TieFlags{};
+    if (is_signed)
+        launch_rerank_topk_b_(s, l2, x, nq, d, reinterpret_cast<const int8_t*>(raw), nraw, cand_ids, R, k, min_score, max_score,
+                              neutral, distances, labels, qperm, tf);
+    else
+        launch_rerank_topk_b_(s, l2, x, nq, d, raw, nraw, cand_ids, R, k, min_score, max_score, neutral, distances, labels, qperm, tf);
 }
 
 // ------------------------------------------------------------------------------------

@@ -181,4 +181,110 @@ __device__ __forceinline__ float rerank_dist8(const float* __restrict__ xq, cons
     return t01 + __shfl_down(t01, 2, 8);
 }
 
+// ---- rows of one byte per element (gamma_hip_raw_init_i8) ------------------------------------------------------------
+// The same distance over float(byte row): uint8 and int8 widen exactly.  b = the byte as an unsigned value; for int8 the byte
+// with its sign bit flipped is value + 128, converted as an unsigned byte and shifted back (both steps exact).
+template <bool SIGNED>
+__device__ __forceinline__ float byte_row_f(uint32_t b) {
+    return SIGNED ? (float)(b ^ 0x80u) - 128.0f : (float)b;
+}
+
+// Same contract as rerank_dist8 above.  Lane l's elements l + 8u are byte l & 3 of the row's dwords (l >> 2) + 2u, so no lane
+// needs another lane's bytes and nothing is transposed:
+//   d % 16 == 0 (rows 16-byte aligned): the eight lanes of a group load the SAME 16 bytes (one request per candidate, half
+//                the load instructions of the fp32 rows) and each takes its two elements out of them, selected on scalars as
+//                the chunk arrives; a span of 128 elements is eight such loads in front of the chain;
+//   d % 4 == 0  (rows 4-byte aligned): one dword load per element;
+//   other d:     byte loads.
+template <bool L2, bool SIGNED>
+__device__ __forceinline__ float rerank_dist8_bytes(const float* __restrict__ xq, const uint8_t* __restrict__ v, int d,
+                                                    int l, bool live) {
+    const int d8 = d & ~7;
+    const int sh = 8 * (l & 3);
+    float a = 0.f;
+    auto step = [&](float x, float y) {
+        if (L2) {
+            const float t = x - y;
+            a = __builtin_fmaf(t, t, a);
+        } else {
+            a = __builtin_fmaf(x, y, a);
+        }
+    };
+    if (live) {
+        if ((d & 15) == 0) {   // (uniform)
+            const bool hi = l & 4;
+            const uint4* __restrict__ v4 = reinterpret_cast<const uint4*>(v);
+            const int nc = d >> 4;   // chunks of 16 elements
+            int c = 0;
+            for (; c + 8 <= nc; c += 8) {
+                // the lane's two dwords of each chunk are picked as the chunk arrives (value selects on scalars: a select
+                // between members of an array of uint4 becomes an indexed read of a private array, i.e. scratch)
+                uint32_t e0[8], e1[8];
+                float xx[16];
+#pragma unroll
+                for (int u = 0; u < 8; u++) {
+                    const uint4 w = v4[c + u];
+                    const uint32_t wx = w.x, wy = w.y, wz = w.z, ww = w.w;
+                    e0[u] = hi ? wy : wx;
+                    e1[u] = hi ? ww : wz;
+                }
+#pragma unroll
+                for (int u = 0; u < 16; u++) xx[u] = xq[16 * c + 8 * u + l];
+#pragma unroll
+                for (int u = 0; u < 8; u++) {
+                    step(xx[2 * u], byte_row_f<SIGNED>((e0[u] >> sh) & 0xffu));
+                    step(xx[2 * u + 1], byte_row_f<SIGNED>((e1[u] >> sh) & 0xffu));
+                }
+            }
+            for (; c < nc; c++) {
+                const uint4 w = v4[c];
+                const uint32_t wx = w.x, wy = w.y, wz = w.z, ww = w.w;
+                step(xq[16 * c + l], byte_row_f<SIGNED>(((hi ? wy : wx) >> sh) & 0xffu));
+                step(xq[16 * c + 8 + l], byte_row_f<SIGNED>(((hi ? ww : wz) >> sh) & 0xffu));
+            }
+        } else if ((d & 3) == 0) {   // (uniform)
+            const uint32_t* __restrict__ v1 = reinterpret_cast<const uint32_t*>(v);
+            for (int i = l; i < d8; i += 8) step(xq[i], byte_row_f<SIGNED>((v1[i >> 2] >> sh) & 0xffu));
+        } else {
+            for (int i = l; i < d8; i += 8) step(xq[i], byte_row_f<SIGNED>(v[i]));
+        }
+    }
+    float s = __shfl_down(a, 4, 8) + a;   // s[l] = acc[l+4] + acc[l] for l < 4
+    int rem = d - d8, i = d8;
+    if (live && rem >= 4) {
+        if (l < 4) {
+            const float y = byte_row_f<SIGNED>(v[i + l]);
+            if (L2) {
+                const float t = xq[i + l] - y;
+                s = __builtin_fmaf(t, t, s);
+            } else {
+                s = __builtin_fmaf(xq[i + l], y, s);
+            }
+        }
+        i += 4;
+        rem -= 4;
+    }
+    if (live && l < rem) {
+        const float y = byte_row_f<SIGNED>(v[i + l]);
+        if (L2) {
+            const float t = xq[i + l] - y;
+            s = __builtin_fmaf(t, t, s);
+        } else {
+            s = __builtin_fmaf(xq[i + l], y, s);
+        }
+    }
+    const float t01 = s + __shfl_down(s, 1, 8);
+    return t01 + __shfl_down(t01, 2, 8);
+}
+template <bool L2>
+__device__ __forceinline__ float rerank_dist8(const float* __restrict__ xq, const uint8_t* __restrict__ v, int d, int l,
+                                              bool live) {
+    return rerank_dist8_bytes<L2, false>(xq, v, d, l, live);
+}
+template <bool L2>
+__device__ __forceinline__ float rerank_dist8(const float* __restrict__ xq, const int8_t* __restrict__ v, int d, int l,
+                                              bool live) {
+    return rerank_dist8_bytes<L2, true>(xq, reinterpret_cast<const uint8_t*>(v), d, l, live);
+}
+
 }  // namespace gh

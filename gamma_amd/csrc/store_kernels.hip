@@ -176,6 +176,41 @@ void launch_raw_rows_to_half(hipStream_t s, const float* stage, const int64_t* v
     }
 }
 
+// byte raw store (gamma_hip_raw_init_i8): the staged fp32 rows -- integral and inside the element type's range, the host checked
+// every value -- into rows first + i, or vids[i] (a vid outside [0, nrows) is skipped; rows >= nrows are never written).  The
+// stored byte is the low byte of the value's two's complement, which is the uint8 and the int8 encoding alike.  QUAD (d % 4 ==
+// 0, rows dword-aligned): four elements per dword store; otherwise byte stores.
+template <bool QUAD>
+__global__ __launch_bounds__(256) void k_raw_rows_to_bytes(const float* __restrict__ stage, const int64_t* __restrict__ vids, int64_t first,
+                                                           int64_t n, int d, uint8_t* __restrict__ raw, int64_t nrows) {
+    const int dv = QUAD ? d >> 2 : d;
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n * dv) return;
+    const int64_t i = t / dv;
+    const int c = (int)(t - i * dv);
+    const int64_t row = vids ? vids[i] : first + i;
+    if (row < 0 || row >= nrows) return;
+    if (QUAD) {
+        const float4 f = reinterpret_cast<const float4*>(stage)[t];   // (d % 4 == 0: element quads never straddle rows)
+        const uint32_t b0 = (uint32_t)(int)f.x & 0xffu, b1 = (uint32_t)(int)f.y & 0xffu, b2 = (uint32_t)(int)f.z & 0xffu,
+                       b3 = (uint32_t)(int)f.w & 0xffu;
+        reinterpret_cast<uint32_t*>(raw)[row * dv + c] = b0 | (b1 << 8) | (b2 << 16) | (b3 << 24);
+    } else {
+        raw[row * d + c] = (uint8_t)((uint32_t)(int)stage[t] & 0xffu);
+    }
+}
+void launch_raw_rows_to_bytes(hipStream_t s, const float* stage, const int64_t* vids, int64_t first, int64_t n, int d, uint8_t* raw,
+                              int64_t nrows) {
+    if (n <= 0 || d <= 0 || nrows <= 0) return;
+    if ((d & 3) == 0) {
+        const int64_t tot = n * (d >> 2);
+        hipLaunchKernelGGL((k_raw_rows_to_bytes<true>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, stage, vids, first, n, d, raw, nrows);
+    } else {
+        const int64_t tot = n * d;
+        hipLaunchKernelGGL((k_raw_rows_to_bytes<false>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, stage, vids, first, n, d, raw, nrows);
+    }
+}
+
 // Arena repack (gamma_hip_store.cpp, arena_repack): every list's live entries move from (old arrays, old offset)
 // to (new arrays, new offset).  grid = (nlist, chunks); the code bytes move as dwords when M % 4 == 0.
 __global__ __launch_bounds__(256) void k_repack_lists(const uint8_t* __restrict__ oc, const int64_t* __restrict__ oi,

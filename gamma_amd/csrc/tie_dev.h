@@ -60,7 +60,8 @@ __device__ __forceinline__ TieLds tie_carve(char* p, int R, int k, int P, int sl
 // One query, replayed the way the reference runs it.  Called by all NT threads of a workgroup (NT a multiple
 // of 64, <= 1024); `lds` = tie_replay_lds_bytes_(R, k, P, SLAB) bytes, 16-byte aligned, free for this call.
 // HALF: the raw rows are IEEE binary16 (a.raw_h; gamma_hip_raw_init_f16) -- only the row reads of the exact distances differ.
-template <bool L2, int NT, int SLAB = TR_SLAB, int STG = TR_STAGE, int MAXK = TR_MAXK, bool HALF = false>
+// BYTE: 1 = rows of uint8, 2 = rows of int8 (a.raw_b; gamma_hip_raw_init_i8), likewise.
+template <bool L2, int NT, int SLAB = TR_SLAB, int STG = TR_STAGE, int MAXK = TR_MAXK, bool HALF = false, int BYTE = 0>
 __device__ __forceinline__ void tie_replay_query(const TieReplayArgs& a, int q, char* lds, unsigned long long* dbg,
                                                  int slab_row = -1) {
 #define GH_TT(i) do { if (dbg && threadIdx.x == 0) dbg[i] = wall_clock64(); } while (0)
@@ -251,6 +252,8 @@ __device__ __forceinline__ void tie_replay_query(const TieReplayArgs& a, int q, 
                 }
             } else if constexpr (HALF) {
                 dis = rerank_dist8<L2>(xq, a.raw_h + (live ? id : 0) * a.d, a.d, l8, live);
+            } else if constexpr (BYTE != 0) {
+                dis = rerank_dist8_bytes<L2, BYTE == 2>(xq, a.raw_b + (live ? id : 0) * a.d, a.d, l8, live);
             } else {
                 dis = rerank_dist8<L2>(xq, a.raw + (live ? id : 0) * a.d, a.d, l8, live);
             }

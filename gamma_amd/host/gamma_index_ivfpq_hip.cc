@@ -100,12 +100,14 @@ int HIPIVFPQModelParams::Parse(const char *str) {
     raw_sharded = !strcasecmp("sharded", rpl.c_str());
   }
   std::string rdt;
-  if (!jp.GetString("raw_dtype", rdt)) {   // the device's raw rows: "float32" (the default) | "float16"
-    if (strcasecmp("float32", rdt.c_str()) && strcasecmp("float16", rdt.c_str())) {
+  if (!jp.GetString("raw_dtype", rdt)) {   // the device's raw rows: "float32" (the default) | "float16" | "uint8" | "int8"
+    if (strcasecmp("float32", rdt.c_str()) && strcasecmp("float16", rdt.c_str()) && strcasecmp("uint8", rdt.c_str()) &&
+        strcasecmp("int8", rdt.c_str())) {
       HLOG("invalid raw_dtype = %s", rdt.c_str());
       return -1;
     }
     raw_f16 = !strcasecmp("float16", rdt.c_str());
+    raw_i8 = !strcasecmp("uint8", rdt.c_str()) ? 1 : !strcasecmp("int8", rdt.c_str()) ? 2 : 0;
   }
   if (!jp.GetInt("bucket_init_size", v)) {
     if (v < -1) return -1;
@@ -183,6 +185,18 @@ int RegisterHIPRawInitF16(HIPRawInitFn fn) {
   return 0;
 }
 HIPRawInitFn FindHIPRawInitF16() { return RawInitF16(); }
+
+namespace {
+const HIPRawI8Ops *&RawI8Ops() {
+  static const HIPRawI8Ops *ops = nullptr;
+  return ops;
+}
+}  // namespace
+int RegisterHIPRawI8(const HIPRawI8Ops *ops) {
+  RawI8Ops() = ops;
+  return 0;
+}
+const HIPRawI8Ops *FindHIPRawI8() { return RawI8Ops(); }
 
 int RegisterHIPListsInit(int nbits, HIPListsInitFn fn) {
   ListsInits().push_back({nbits, fn});
@@ -290,12 +304,21 @@ int GammaIVFPQHIPIndex::Init(const std::string &model_parameters, int indexing_s
     return -2;
   }
   raw_f16_ = pa.raw_f16;
+  const HIPRawI8Ops *raw_i8_ops = pa.raw_i8 ? FindHIPRawI8() : nullptr;
+  if (pa.raw_i8 && (!raw_i8_ops || pa.devices.size() > 1)) {
+    HLOG("raw_dtype = %s %s", pa.raw_i8 == 2 ? "int8" : "uint8",
+         raw_i8_ops ? "with several devices is not supported (the group's members hold fp32 rows)"
+                     : "is not supported by this build of the plugin (it carries no 8-bit raw store)");
+    return -2;
+  }
+  raw_i8_ = pa.raw_i8;
+  raw_i8_ops_ = raw_i8_ops;
   if (OpenDevices(pa.devices, pa.replicate)) return -1;
   int rc = ForAll([&](gamma_hip_index *m) {
     const int metric = metric_type_ == DistanceComputeType::L2 ? GAMMA_HIP_METRIC_L2 : GAMMA_HIP_METRIC_IP;
     int r = lists_init ? lists_init(m, d_, nlist_, M_, metric, pa.bucket_init_size, pa.bucket_max_size)
                        : gamma_hip_ivfpq_init(m, d_, nlist_, M_, 8, metric, pa.bucket_init_size, pa.bucket_max_size);
-    if (!r) r = raw_init_f16 ? raw_init_f16(m, d_) : gamma_hip_raw_init(m, d_);
+    if (!r) r = raw_i8_ops ? raw_i8_ops->init(m, d_, pa.raw_i8 == 2) : raw_init_f16 ? raw_init_f16(m, d_) : gamma_hip_raw_init(m, d_);
     if (!r) r = gamma_hip_set_exact_ties(m, pa.exact_ties ? 1 : 0);
     if (!r && pa.perf_stages) r = gamma_hip_profile_enable(m, 1);
     return r;
@@ -412,6 +435,15 @@ int GammaIVFPQHIPIndex::TrainingSet(std::vector<float> &xt, size_t &num) {
   return 0;
 }
 
+bool GammaIVFPQHIPIndex::RowsStorable(const char *what, const float *x, int64_t nrows) {
+  if (!raw_i8_) return true;
+  int64_t bad = -1;
+  if (!raw_i8_ops_->check(x, nrows * d_, raw_i8_ == 2, &bad)) return true;
+  HLOG("%s refused: raw_dtype = %s stores a value only if it converts exactly, and element %d of row %lld is %g", what,
+       raw_i8_ == 2 ? "int8" : "uint8", (int)(bad % d_), (long long)(bad / d_), (double)x[bad]);
+  return false;
+}
+
 bool GammaIVFPQHIPIndex::Add(int n, const uint8_t *vec) {
   // vids are consecutive from indexed_vec_count_ (gamma_index_ivfpq.cc:475-489); the raw
   // vectors are mirrored to HBM for the exact re-rank (VectorReader::Gets on the CPU path).
@@ -419,6 +451,7 @@ bool GammaIVFPQHIPIndex::Add(int n, const uint8_t *vec) {
   // same rows at the same time (EnsureRaw) rewrites identical bytes instead of appending them twice.
   const float *v = reinterpret_cast<const float *>(vec);
   const int64_t end = (int64_t)indexed_vec_count_ + n;
+  if (!RowsStorable("add", v, n)) return false;   // before anything changes: no row, no key
   if (rawshard_) {
     // sharded rows: the group puts every row beside its keys at the owner of its list (gamma_hip_group_ivfpq_add below);
     // the first Add after training retires member 0's mirror of the untrained model
@@ -448,6 +481,7 @@ int GammaIVFPQHIPIndex::Update(const std::vector<int64_t> &ids, const std::vecto
   if (vecs.size() != n) return -1;
   std::vector<float> x(n * (size_t)d_);
   for (size_t i = 0; i < n; i++) memcpy(&x[i * d_], vecs[i], sizeof(float) * d_);
+  if (!RowsStorable("update", x.data(), (int64_t)n)) return -1;   // before the lists change
   int rc = grp_ ? gamma_hip_group_ivfpq_update(grp_, (int)n, ids.data(), x.data())
                 : gamma_hip_ivfpq_update_batch(h_, (int)n, ids.data(), x.data());
   if (rc) {
@@ -519,6 +553,11 @@ int GammaIVFPQHIPIndex::Search(RetrievalContext *retrieval_context, int n, const
   if (((cond && cond->brute_force_search) || !is_trained_) && raw_f16_) {
     // the flat search reads fp32 rows, the device holds rounded ones: refused, never an answer over other rows
     HLOG("brute_force_search (and the search of an untrained model) is not available with raw_dtype = float16");
+    return -3;
+  }
+  if (((cond && cond->brute_force_search) || !is_trained_) && raw_i8_) {
+    HLOG("brute_force_search (and the search of an untrained model) is not available with raw_dtype = %s",
+         raw_i8_ == 2 ? "int8" : "uint8");
     return -3;
   }
   if (((cond && cond->brute_force_search) || !is_trained_) && rawshard_) {

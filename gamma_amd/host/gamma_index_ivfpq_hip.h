@@ -73,6 +73,15 @@ const HIPRawShardOps *FindHIPRawShard();
 typedef int (*HIPRawInitFn)(gamma_hip_index *h, int d);
 int RegisterHIPRawInitF16(HIPRawInitFn fn);
 HIPRawInitFn FindHIPRawInitF16();
+// "raw_dtype": "uint8" | "int8": the byte store's entries of the C ABI -- its initialiser (gamma_hip_raw_init_i8) and the
+// writers' acceptance predicate (gamma_hip_raw_i8_check) -- registered the same way by gamma_index_ivfpq_rawi8_hip.cc, the only
+// host file that names them.  Without that file Init rejects the two values.
+struct HIPRawI8Ops {
+  int (*init)(gamma_hip_index *h, int d, int is_signed);
+  int (*check)(const float *x, int64_t n, int is_signed, int64_t *first_bad);
+};
+int RegisterHIPRawI8(const HIPRawI8Ops *ops);
+const HIPRawI8Ops *FindHIPRawI8();
 
 // "opq": the rotation's entries of the C ABI (gamma_hip_opq_train / _set / _get / _apply) reach the model through this table,
 // registered at static-initialisation time by gamma_index_ivfpq_opq_hip.cc -- the only host file that names them.  A build of
@@ -109,6 +118,8 @@ struct HIPIVFPQModelParams {
                                  // vector lives once, on the device that owns its list; "replicated" (default): on all
   bool raw_f16 = false;          // HIP only: "raw_dtype": "float16" -- the device's raw rows (what compute_dis reads) are IEEE
                                  // binary16, rounded from the engine's fp32 on upload; "float32" (default).  One device only.
+  int raw_i8 = 0;                // HIP only: "raw_dtype": "uint8" (1) | "int8" (2) -- the device's raw rows are one byte per
+                                 // element; a row that does not convert exactly is refused by Add / Update.  One device only.
   int Parse(const char *str);   // 0 ok, -1 bad (same rules as gamma_index_ivfpq.h:708-851)
 };
 
@@ -179,6 +190,9 @@ class GammaIVFPQHIPIndex : public RetrievalModel {
   // owner of its list, Add and Update hand the rows to the group, and a brute-force request is refused.
   const HIPRawShardOps *rawshard_ = nullptr;
   bool raw_f16_ = false;               // "raw_dtype": "float16": no device holds fp32 rows -- brute-force search is refused
+  int raw_i8_ = 0;                     // "raw_dtype": "uint8" (1) | "int8" (2): likewise
+  const HIPRawI8Ops *raw_i8_ops_ = nullptr;
+  bool RowsStorable(const char *what, const float *x, int64_t nrows);   // byte store: one log line for the first refused value
   bool rows_sharded_ = false;          // under raw_mu_
   // nbits_per_idx: 8, or 4 (16 centroids per sub-quantizer, two indices per code byte as faiss's PQEncoderGeneric packs them)
   int nbits_ = 8;

@@ -403,11 +403,12 @@ void gh_parse_ivfpq_model_params(const char *str, int *out) {
   out[8] = p.has_hnsw;
   out[9] = p.has_opq;
 }
-// the HIP-only "raw_dtype" key of HIPIVFPQModelParams::Parse: out = {rc, 1 for "float16" / 0 for "float32" and the default}
+// the HIP-only "raw_dtype" key of HIPIVFPQModelParams::Parse: out = {rc, 0 for "float32" and the default / 1 for "float16" /
+// 2 for "uint8" / 3 for "int8"}
 void gh_parse_ivfpq_raw_dtype(const char *str, int *out) {
   HIPIVFPQModelParams p;
   out[0] = p.Parse(str);
-  out[1] = p.raw_f16 ? 1 : 0;
+  out[1] = p.raw_i8 ? 1 + p.raw_i8 : p.raw_f16 ? 1 : 0;
 }
 // HIPIVFPQRetrievalParameters via Parse on an un-Init'ed model: out = {rc, metric, recall_num, nprobe}
 void gh_parse_ivfpq_retrieval_params(const char *str, int *out) {

@@ -113,10 +113,10 @@ def parse_model_params(s):
 
 
 def parse_raw_dtype(s):
-    """(rc of HIPIVFPQModelParams::Parse, "float16" or "float32") for the model parameters s"""
+    """(rc of HIPIVFPQModelParams::Parse, "float32", "float16", "uint8" or "int8") for the model parameters s"""
     out = (C.c_int * 2)()
     load_host().gh_parse_ivfpq_raw_dtype(s.encode(), out)
-    return int(out[0]), "float16" if out[1] else "float32"
+    return int(out[0]), ("float32", "float16", "uint8", "int8")[out[1]]
 
 
 def parse_retrieval_params(s):

@@ -264,8 +264,29 @@ int gamma_hip_raw_stats(gamma_hip_index* h, int64_t* out4);
  * GAMMA_HIP_EUNSUPPORTED: gamma_hip_raw_put / _raw_drop, flat and IVFFLAT search, gamma_hip_ivfpq_shard_exact /
  * _shard_export_exact, _merge_rerank / _merge_replay with has_rank and no travelled distances. */
 int gamma_hip_raw_init_f16(gamma_hip_index* h, int d);
-/* bytes of one element of the raw store: 4 (gamma_hip_raw_init), 2 (gamma_hip_raw_init_f16), 0 before either */
+/* bytes of one element of the raw store: 4 (gamma_hip_raw_init), 2 (gamma_hip_raw_init_f16), 1 (gamma_hip_raw_init_i8), 0 before
+ * any of them */
 int gamma_hip_raw_elem_bytes(gamma_hip_index* h);
+/* A store of one byte per element: uint8 rows, range [0, 255] (is_signed = 0), or int8 rows, range [-128, 127] (is_signed = 1) --
+ * a quarter of the fp32 store's bytes, and LOSSLESS OR REFUSED: the writers (raw_append / raw_write / raw_update /
+ * raw_update_batch) take fp32 and store a value only if it is finite, integral and inside the element type's range, which is
+ * exactly when float(T(x)) == x (-0.0 is accepted and stored as 0).  Any other value -- NaN, +-inf, a fraction, a value out of
+ * range -- fails the call with GAMMA_HIP_EINVAL before anything changes: no byte of the store, no counter, no list; last_error
+ * names the offending position.  The element type is fixed at the first init; a second init with another type or d answers
+ * GAMMA_HIP_EINVAL.  Only the store is narrow: training, assignment, residuals and codes see the caller's fp32.  A byte widens
+ * to fp32 exactly, so the exact distance of a has_rank IVFPQ search -- fvec_L2sqr / fvec_inner_product of the fp32 query and the
+ * widened row in the reference's operation order -- and with it every result, ties included, is what the fp32 store gives.
+ * gamma_hip_raw_gets widens.  Served and refused as for gamma_hip_raw_init_f16: served are gamma_hip_ivfpq_search and its
+ * device-pointer forms (8-bit, 4-bit, OPQ handles); GAMMA_HIP_EUNSUPPORTED: gamma_hip_raw_put / _raw_drop, flat and IVFFLAT
+ * search, gamma_hip_ivfpq_shard_exact / _shard_export_exact, _merge_rerank / _merge_replay with has_rank and no travelled
+ * distances. */
+int gamma_hip_raw_init_i8(gamma_hip_index* h, int d, int is_signed);
+/* element type of the raw store: 0 fp32 (also before any init), 1 float16, 2 uint8, 3 int8 */
+int gamma_hip_raw_elem_type(gamma_hip_index* h);
+/* The byte store's acceptance predicate, as the writers apply it: GAMMA_HIP_OK when every one of the n values is storable in
+ * uint8 (is_signed = 0) or int8 (is_signed = 1); otherwise GAMMA_HIP_EINVAL, and *first_bad (when not null) is the index of the
+ * first value that is refused.  Pure host code: no handle, no device call. */
+int gamma_hip_raw_i8_check(const float* x, int64_t n, int is_signed, int64_t* first_bad);
 
 /* ---- delete bitmap (bitmap::BitmapManager, util/bitmap_manager.cc:171-192): bit = docid,
  *      byte docid>>3, mask 1<<(docid&7) --------------------------------------------------- */
