@@ -666,6 +666,11 @@ class GammaHip:
         """True / False, or an int >= 2: on, with the two-level selection of long candidate rows forced (that many slices)."""
         self._ck(self.L.gamma_hip_set_small_path(self.h, int(on)), "set_small_path")
 
+    def set_flat_narrow_rows(self, on=True):
+        """True: flat_search serves a float16 / uint8 / int8 raw store (byte-identical to an fp32 store of the widened rows);
+        False (the default): it refuses one, as every other reader of fp32 rows does."""
+        self._ck(self.L.gamma_hip_set_flat_narrow_rows(self.h, 1 if on else 0), "set_flat_narrow_rows")
+
     def tie_stats(self, reset=False):
         out = np.zeros(3, np.int64)
         self._ck(self.L.gamma_hip_tie_stats(self.h, _p(out, _lib.i64p), 1 if reset else 0), "tie_stats")

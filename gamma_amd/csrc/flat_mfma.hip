@@ -45,6 +45,7 @@
 
 #include "device_math.h"
 #include "filter_dev.h"
+#include "flat_rows_dev.h"
 #include "bf16_split.h"
 #include "block_utils.h"
 #include "kernels.h"
@@ -105,11 +106,12 @@ __global__ __launch_bounds__(256) void k_flat_bounds(const float* __restrict__ x
     bnd[nq_pad + q] = gv;
 }
 
+template <class Row = float>
 struct FlatFilterArgs {
     const char* qimg;          // k_flat_prep_queries
     const float* bnd;          // k_flat_bounds: a_q [nq_pad] | g_q [nq_pad]
     int nq, nq_pad;
-    const float* y;            // rows of the pass
+    const Row* y;              // rows of the pass
     int64_t ny;
     int64_t row_base;          // store row of y[0]
     uint2* pairs;              // survivors (query, store row), any order
@@ -121,8 +123,12 @@ constexpr int FM_NSUB = 32;     // the global pair list is FM_NSUB segments, eac
                                 // (workgroup b appends to segment b % FM_NSUB): reservations do not queue on ONE address
 constexpr int FM_CTR_STRIDE = 32;   // ints between the segments' counters
 
-template <bool L2, int D>
-__global__ __launch_bounds__(FM_NT) void k_flat_filter(FlatFilterArgs a) {
+// Row: the rows' element type.  Narrow rows (flat search over a float16 / uint8 / int8 store) are loaded narrow and widened
+// exactly; the norm comes from the widened values in the same fma chain.  A binary16 value IS hi + lo (11 significant bits, two
+// bf16 of 8) and a byte value IS hi alone, so the dropped-row term ry of the margin above is 0 and the margin holds unchanged.
+// Byte rows therefore keep no lo fragments and leave the ah x bl product out -- it would add exact zeros.
+template <bool L2, int D, class Row = float>
+__global__ __launch_bounds__(FM_NT) void k_flat_filter(FlatFilterArgs<Row> a) {
     constexpr int KK = D / 16;
     constexpr int TILE = 2 * fm_mt_bytes(D);   // bytes of a 64-query tile
     constexpr int LPT = TILE / (FM_NT * 16);   // 1 KB pieces per wave and tile
@@ -136,25 +142,54 @@ __global__ __launch_bounds__(FM_NT) void k_flat_filter(FlatFilterArgs a) {
     const int rg = w >> 1, mh = w & 1, kh = lane >> 5, j = lane & 31;
     const int64_t r0 = (int64_t)blockIdx.x * FM_ROWS + rg * 64;
     // ---- this wave's 64 rows: bf16 hi / lo B fragments in registers, norms ----
-    bf16x8 bh[2][KK], bl[2][KK];
+    constexpr bool BYTE = RowKind<Row>::byte;
+    bf16x8 bh[2][KK], bl[2][BYTE ? 1 : KK];
     float hrow[2];
 #pragma unroll
     for (int nt = 0; nt < 2; nt++) {
         const int64_t r = r0 + nt * 32 + j;
         const bool live = r < a.ny;
-        const float* yp = a.y + (live ? r : 0) * D + (D / 2) * kh;   // this lane's half row, contiguous
+        const Row* yp = a.y + (live ? r : 0) * D + (D / 2) * kh;   // this lane's half row, contiguous
         float ss = 0.f;
+        if constexpr (BYTE) {
+            // 16 bytes = two k steps (KK is even, the half row D / 2 bytes: 16-byte aligned); the values are exact in ONE bf16
+            static_assert(KK % 2 == 0, "byte rows: two k steps per 16-byte load");
 #pragma unroll
-        for (int kk = 0; kk < KK; kk++) {
-            const float4 v0 = *reinterpret_cast<const float4*>(yp + 8 * kk);
-            const float4 v1 = *reinterpret_cast<const float4*>(yp + 8 * kk + 4);
-            const float f[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+            for (int k2 = 0; k2 < KK / 2; k2++) {
+                const uint4 v = *reinterpret_cast<const uint4*>(yp + 16 * k2);
+                float f[16];
+                row_dword_f<Row>(v.x, f);
+                row_dword_f<Row>(v.y, f + 4);
+                row_dword_f<Row>(v.z, f + 8);
+                row_dword_f<Row>(v.w, f + 12);
 #pragma unroll
-            for (int t = 0; t < 8; t++) ss = __builtin_fmaf(f[t], f[t], ss);
-            uint4 hi, lo;
-            split_bf16x8(f, hi, lo);
-            bh[nt][kk] = __builtin_bit_cast(bf16x8, hi);
-            bl[nt][kk] = __builtin_bit_cast(bf16x8, lo);
+                for (int t = 0; t < 16; t++) ss = __builtin_fmaf(f[t], f[t], ss);
+#pragma unroll
+                for (int u = 0; u < 2; u++) {
+                    const uint4 hi = make_uint4(cvt_pk_bf16(f[8 * u], f[8 * u + 1]), cvt_pk_bf16(f[8 * u + 2], f[8 * u + 3]),
+                                                cvt_pk_bf16(f[8 * u + 4], f[8 * u + 5]), cvt_pk_bf16(f[8 * u + 6], f[8 * u + 7]));
+                    bh[nt][2 * k2 + u] = __builtin_bit_cast(bf16x8, hi);
+                }
+            }
+        } else {
+#pragma unroll
+            for (int kk = 0; kk < KK; kk++) {
+                float f[8];
+                if constexpr (RowKind<Row>::fp32) {
+                    const float4 v0 = *reinterpret_cast<const float4*>(yp + 8 * kk);
+                    const float4 v1 = *reinterpret_cast<const float4*>(yp + 8 * kk + 4);
+                    f[0] = v0.x; f[1] = v0.y; f[2] = v0.z; f[3] = v0.w;
+                    f[4] = v1.x; f[5] = v1.y; f[6] = v1.z; f[7] = v1.w;
+                } else {
+                    row_widen8<Row>(row_load8<Row>(yp + 8 * kk), f);   // 16 bytes of halves
+                }
+#pragma unroll
+                for (int t = 0; t < 8; t++) ss = __builtin_fmaf(f[t], f[t], ss);
+                uint4 hi, lo;
+                split_bf16x8(f, hi, lo);
+                bh[nt][kk] = __builtin_bit_cast(bf16x8, hi);
+                bl[nt][kk] = __builtin_bit_cast(bf16x8, lo);
+            }
         }
         const float yn = ss + __shfl_xor(ss, 32, 64);
         // L2: h = (1 - c) yn / 2; inner product: h = sqrt(yn).  A row past the end never passes.
@@ -224,7 +259,7 @@ __global__ __launch_bounds__(FM_NT) void k_flat_filter(FlatFilterArgs a) {
 #pragma unroll
             for (int nt = 0; nt < 2; nt++) {
                 acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh[nt][kk], acc[nt], 0, 0, 0);
-                acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl[nt][kk], acc[nt], 0, 0, 0);
+                if constexpr (!BYTE) acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl[nt][kk], acc[nt], 0, 0, 0);
                 acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh[nt][kk], acc[nt], 0, 0, 0);
             }
         }
@@ -285,9 +320,9 @@ __global__ __launch_bounds__(FM_NT) void k_flat_filter(FlatFilterArgs a) {
 }
 
 // the survivors' exact distances, 8 threads per survivor (the 8 AVX lane accumulators of the reference's kernels)
-template <bool L2>
+template <bool L2, class Row = float>
 __global__ __launch_bounds__(256) void k_flat_exact(const uint2* __restrict__ pairs, const int* __restrict__ npairs, int cap,
-                                                    const float* __restrict__ x, int d, const float* __restrict__ store,
+                                                    const float* __restrict__ x, int d, const Row* __restrict__ store,
                                                     FilterDesc filt, int use_filter, float min_score, float max_score,
                                                     FlatEmit em, int* __restrict__ overflow) {
     const int l8 = threadIdx.x & 7, g = threadIdx.x >> 3;
@@ -370,8 +405,9 @@ __global__ __launch_bounds__(256) void k_flat_prep_queries_rt(const float* __res
     *reinterpret_cast<uint4*>(base + ((((1 * KK + kk) * 2 + kh) * 32 + i) * 16)) = lo;
 }
 
-template <bool L2, bool LO_L2>   // LO_L2: d > 1024, only the hi half of the image fits the LDS (a kernel of its own: the choice costs the others nothing)
-__global__ __launch_bounds__(FM_NT) void k_flat_filter_big(FlatFilterArgs a, int D, float c_margin) {
+template <bool L2, bool LO_L2, class Row = float>   // LO_L2: d > 1024, only the hi half of the image fits the LDS (a kernel of its own: the choice costs the others nothing)
+__global__ __launch_bounds__(FM_NT) void k_flat_filter_big(FlatFilterArgs<Row> a, int D, float c_margin) {
+    constexpr bool BYTE = RowKind<Row>::byte;   // (narrow rows: see k_flat_filter)
     const int KK = D / 16;
     const int IMG = fm_mt_bytes(D);
     extern __shared__ __attribute__((aligned(16))) char s_fm[];
@@ -419,7 +455,7 @@ __global__ __launch_bounds__(FM_NT) void k_flat_filter_big(FlatFilterArgs a, int
     const char* tg = a.qimg + (int64_t)mt * IMG + (kh * 32 + j) * 16;    // the same fragment in the image in memory
     for (int64_t st = s_lo; st < s_hi; st++) {
         const int64_t r0 = st * 256 + w * 64;
-        const float* yp[2];
+        const Row* yp[2];
         bool live[2];
 #pragma unroll
         for (int nt = 0; nt < 2; nt++) {
@@ -433,37 +469,37 @@ __global__ __launch_bounds__(FM_NT) void k_flat_filter_big(FlatFilterArgs a, int
 #pragma unroll
             for (int r = 0; r < 16; r++) acc[nt][r] = 0.f;
         float ss[2] = {0.f, 0.f};
-        float4 v[2][2];
+        Raw8<Row> v[2];   // the step's 8 elements of each row as loaded: 32 / 16 / 8 bytes
 #pragma unroll
-        for (int nt = 0; nt < 2; nt++) {
-            v[nt][0] = *reinterpret_cast<const float4*>(yp[nt]);
-            v[nt][1] = *reinterpret_cast<const float4*>(yp[nt] + 4);
-        }
+        for (int nt = 0; nt < 2; nt++) v[nt] = row_load8<Row>(yp[nt]);
         for (int kk = 0; kk < KK; kk++) {
             bf16x8 bh[2], bl[2];
 #pragma unroll
             for (int nt = 0; nt < 2; nt++) {
-                const float f[8] = {v[nt][0].x, v[nt][0].y, v[nt][0].z, v[nt][0].w, v[nt][1].x, v[nt][1].y, v[nt][1].z, v[nt][1].w};
+                float f[8];
+                row_widen8<Row>(v[nt], f);
 #pragma unroll
                 for (int t = 0; t < 8; t++) ss[nt] = __builtin_fmaf(f[t], f[t], ss[nt]);
                 uint4 hi, lo;
-                split_bf16x8(f, hi, lo);
+                if constexpr (BYTE) {   // exact in one bf16: no lo fragment
+                    hi = make_uint4(cvt_pk_bf16(f[0], f[1]), cvt_pk_bf16(f[2], f[3]), cvt_pk_bf16(f[4], f[5]), cvt_pk_bf16(f[6], f[7]));
+                    lo = make_uint4(0u, 0u, 0u, 0u);
+                } else {
+                    split_bf16x8(f, hi, lo);
+                }
                 bh[nt] = __builtin_bit_cast(bf16x8, hi);
                 bl[nt] = __builtin_bit_cast(bf16x8, lo);
             }
-            if (kk + 1 < KK) {   // the next step's floats, in flight during this step's products
+            if (kk + 1 < KK) {   // the next step's elements, in flight during this step's products
 #pragma unroll
-                for (int nt = 0; nt < 2; nt++) {
-                    v[nt][0] = *reinterpret_cast<const float4*>(yp[nt] + 8 * (kk + 1));
-                    v[nt][1] = *reinterpret_cast<const float4*>(yp[nt] + 8 * (kk + 1) + 4);
-                }
+                for (int nt = 0; nt < 2; nt++) v[nt] = row_load8<Row>(yp[nt] + 8 * (kk + 1));
             }
             const bf16x8 ah = *reinterpret_cast<const bf16x8*>(tb + ((0 * KK + kk) * 2) * 512);
             const bf16x8 al = *reinterpret_cast<const bf16x8*>((lo_in_l2 ? tg : tb) + ((1 * KK + kk) * 2) * 512);
 #pragma unroll
             for (int nt = 0; nt < 2; nt++) {
                 acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh[nt], acc[nt], 0, 0, 0);
-                acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl[nt], acc[nt], 0, 0, 0);
+                if constexpr (!BYTE) acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl[nt], acc[nt], 0, 0, 0);
                 acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh[nt], acc[nt], 0, 0, 0);
             }
         }
@@ -535,22 +571,23 @@ void launch_flat_prep_queries(hipStream_t s, const float* x, int nq, int d, void
 #undef GH_PREP
 }
 
-template <bool L2, int D>
-static void launch_filter_t(hipStream_t s, const FlatFilterArgs& a) {
+template <bool L2, int D, class Row>
+static void launch_filter_t(hipStream_t s, const FlatFilterArgs<Row>& a) {
     constexpr size_t lds = 2 * 2 * (size_t)fm_mt_bytes(D) + 4 * FM_QT * sizeof(float) + (FM_NT / 64) * FM_WLIST * sizeof(uint2);
     static std::atomic<uint64_t> attr{0};   // per device
     if (first_call_on_device(attr))
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_flat_filter<L2, D>), hipFuncAttributeMaxDynamicSharedMemorySize,
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_flat_filter<L2, D, Row>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)lds);
-    hipLaunchKernelGGL((k_flat_filter<L2, D>), dim3((unsigned)((a.ny + FM_ROWS - 1) / FM_ROWS)), dim3(FM_NT), lds, s, a);
+    hipLaunchKernelGGL((k_flat_filter<L2, D, Row>), dim3((unsigned)((a.ny + FM_ROWS - 1) / FM_ROWS)), dim3(FM_NT), lds, s, a);
 }
 
 size_t flat_filter_bounds_bytes(int nq) { return (size_t)2 * ((nq + FM_QT - 1) / FM_QT * FM_QT) * sizeof(float); }
 
-void launch_flat_filter(hipStream_t s, bool l2, int d, const void* qimage, const float* xn, const uint32_t* tau, float* bounds,
-                        int nq, const float* y, int64_t ny, int64_t row_base, void* pairs, int* npairs, int64_t cap) {
+template <class Row>
+static void flat_filter_rows(hipStream_t s, bool l2, int d, const void* qimage, const float* xn, const uint32_t* tau, float* bounds,
+                             int nq, const Row* y, int64_t ny, int64_t row_base, void* pairs, int* npairs, int64_t cap) {
     if (nq <= 0 || ny <= 0) return;
-    FlatFilterArgs a;
+    FlatFilterArgs<Row> a;
     a.qimg = static_cast<const char*>(qimage);
     a.nq = nq;
     a.nq_pad = (nq + FM_QT - 1) / FM_QT * FM_QT;
@@ -566,8 +603,8 @@ void launch_flat_filter(hipStream_t s, bool l2, int d, const void* qimage, const
     a.cap = (int)std::min<int64_t>(cap / FM_NSUB, INT32_MAX);   // per segment
 #define GH_FILT(DD)                                   \
     do {                                              \
-        if (l2) launch_filter_t<true, DD>(s, a);      \
-        else launch_filter_t<false, DD>(s, a);        \
+        if (l2) launch_filter_t<true, DD, Row>(s, a); \
+        else launch_filter_t<false, DD, Row>(s, a);   \
     } while (0)
     switch (d) {
         case 128: GH_FILT(128); break;
@@ -578,20 +615,20 @@ void launch_flat_filter(hipStream_t s, bool l2, int d, const void* qimage, const
             const size_t lds = (size_t)fm_mt_bytes(d) / (d > 1024 ? 2 : 1) + (FM_NT / 64) * FM_WLIST * sizeof(uint2);
             static std::atomic<uint64_t> attr{0};   // per device
             if (first_call_on_device(attr)) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_flat_filter_big<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 << 10);
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_flat_filter_big<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 << 10);
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_flat_filter_big<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 << 10);
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_flat_filter_big<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 << 10);
+                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_flat_filter_big<true, false, Row>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 << 10);
+                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_flat_filter_big<false, false, Row>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 << 10);
+                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_flat_filter_big<true, true, Row>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 << 10);
+                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_flat_filter_big<false, true, Row>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 << 10);
             }
             const int qb = a.nq_pad / 32;
             const int64_t steps = (a.ny + 255) / 256;
             const int slices = (int)std::max<int64_t>(1, std::min<int64_t>(steps, (2048 + qb - 1) / qb));
             if (d > 1024) {
-                if (l2) hipLaunchKernelGGL((k_flat_filter_big<true, true>), dim3(qb, slices), dim3(FM_NT), lds, s, a, d, cm);
-                else hipLaunchKernelGGL((k_flat_filter_big<false, true>), dim3(qb, slices), dim3(FM_NT), lds, s, a, d, cm);
+                if (l2) hipLaunchKernelGGL((k_flat_filter_big<true, true, Row>), dim3(qb, slices), dim3(FM_NT), lds, s, a, d, cm);
+                else hipLaunchKernelGGL((k_flat_filter_big<false, true, Row>), dim3(qb, slices), dim3(FM_NT), lds, s, a, d, cm);
             } else {
-                if (l2) hipLaunchKernelGGL((k_flat_filter_big<true, false>), dim3(qb, slices), dim3(FM_NT), lds, s, a, d, cm);
-                else hipLaunchKernelGGL((k_flat_filter_big<false, false>), dim3(qb, slices), dim3(FM_NT), lds, s, a, d, cm);
+                if (l2) hipLaunchKernelGGL((k_flat_filter_big<true, false, Row>), dim3(qb, slices), dim3(FM_NT), lds, s, a, d, cm);
+                else hipLaunchKernelGGL((k_flat_filter_big<false, false, Row>), dim3(qb, slices), dim3(FM_NT), lds, s, a, d, cm);
             }
             break;
         }
@@ -599,20 +636,52 @@ void launch_flat_filter(hipStream_t s, bool l2, int d, const void* qimage, const
 #undef GH_FILT
 }
 
-void launch_flat_exact(hipStream_t s, bool l2, const void* pairs, const int* npairs, int64_t cap, const float* x, int nq, int d,
-                       const float* store, const FilterDesc& filt, float min_score, float max_score, const FlatEmit& em,
-                       int* overflow) {
+void launch_flat_filter(hipStream_t s, bool l2, int d, const void* qimage, const float* xn, const uint32_t* tau, float* bounds,
+                        int nq, const float* y, int64_t ny, int64_t row_base, void* pairs, int* npairs, int64_t cap) {
+    flat_filter_rows<float>(s, l2, d, qimage, xn, tau, bounds, nq, y, ny, row_base, pairs, npairs, cap);
+}
+void launch_flat_filter(hipStream_t s, bool l2, int d, const void* qimage, const float* xn, const uint32_t* tau, float* bounds,
+                        int nq, const RowsRef& y, int64_t ny, int64_t row_base, void* pairs, int* npairs, int64_t cap) {
+    switch (y.et) {
+        case 0: flat_filter_rows(s, l2, d, qimage, xn, tau, bounds, nq, y.as<float>(), ny, row_base, pairs, npairs, cap); break;
+        case 1: flat_filter_rows(s, l2, d, qimage, xn, tau, bounds, nq, y.as<uint16_t>(), ny, row_base, pairs, npairs, cap); break;
+        case 2: flat_filter_rows(s, l2, d, qimage, xn, tau, bounds, nq, y.as<uint8_t>(), ny, row_base, pairs, npairs, cap); break;
+        case 3: flat_filter_rows(s, l2, d, qimage, xn, tau, bounds, nq, y.as<int8_t>(), ny, row_base, pairs, npairs, cap); break;
+        default: launch_refused("launch_flat_filter: unknown row element type");
+    }
+}
+
+template <class Row>
+static void flat_exact_rows(hipStream_t s, bool l2, const void* pairs, const int* npairs, int64_t cap, const float* x, int nq, int d,
+                            const Row* store, const FilterDesc& filt, float min_score, float max_score, const FlatEmit& em,
+                            int* overflow) {
     if (nq <= 0) return;
     const int use_filter = (filt.del_bitmap || filt.has_range || filt.n_field > 0 || filt.n_term > 0 || filt.vid2doc) ? 1 : 0;
     const dim3 grid(1024);
     const uint2* pp = static_cast<const uint2*>(pairs);
     const int icap = (int)std::min<int64_t>(cap / FM_NSUB, INT32_MAX);   // per segment
     if (l2)
-        hipLaunchKernelGGL((k_flat_exact<true>), grid, dim3(256), 0, s, pp, npairs, icap, x, d, store, filt, use_filter, min_score,
+        hipLaunchKernelGGL((k_flat_exact<true, Row>), grid, dim3(256), 0, s, pp, npairs, icap, x, d, store, filt, use_filter, min_score,
                            max_score, em, overflow);
     else
-        hipLaunchKernelGGL((k_flat_exact<false>), grid, dim3(256), 0, s, pp, npairs, icap, x, d, store, filt, use_filter,
+        hipLaunchKernelGGL((k_flat_exact<false, Row>), grid, dim3(256), 0, s, pp, npairs, icap, x, d, store, filt, use_filter,
                            min_score, max_score, em, overflow);
+}
+void launch_flat_exact(hipStream_t s, bool l2, const void* pairs, const int* npairs, int64_t cap, const float* x, int nq, int d,
+                       const float* store, const FilterDesc& filt, float min_score, float max_score, const FlatEmit& em,
+                       int* overflow) {
+    flat_exact_rows<float>(s, l2, pairs, npairs, cap, x, nq, d, store, filt, min_score, max_score, em, overflow);
+}
+void launch_flat_exact(hipStream_t s, bool l2, const void* pairs, const int* npairs, int64_t cap, const float* x, int nq, int d,
+                       const RowsRef& store, const FilterDesc& filt, float min_score, float max_score, const FlatEmit& em,
+                       int* overflow) {
+    switch (store.et) {
+        case 0: flat_exact_rows(s, l2, pairs, npairs, cap, x, nq, d, store.as<float>(), filt, min_score, max_score, em, overflow); break;
+        case 1: flat_exact_rows(s, l2, pairs, npairs, cap, x, nq, d, store.as<uint16_t>(), filt, min_score, max_score, em, overflow); break;
+        case 2: flat_exact_rows(s, l2, pairs, npairs, cap, x, nq, d, store.as<uint8_t>(), filt, min_score, max_score, em, overflow); break;
+        case 3: flat_exact_rows(s, l2, pairs, npairs, cap, x, nq, d, store.as<int8_t>(), filt, min_score, max_score, em, overflow); break;
+        default: launch_refused("launch_flat_exact: unknown row element type");
+    }
 }
 
 }  // namespace gh

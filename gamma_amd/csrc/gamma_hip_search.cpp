@@ -1544,16 +1544,21 @@ int ivfflat_search_device_locked(H* h, const gamma_hip_search_params* p, int nq,
 int flat_search_device_locked(H* h, const gamma_hip_search_params* p, int nq, const float* d_x, int k,
                               float* d_distances, int64_t* d_labels) {
     if (h->raw_sparse) return fail(h, GAMMA_HIP_EUNSUPPORTED, "the raw store holds this shard's rows only (gamma_hip_raw_put)");
-    if (h->raw_half) return half_refuse(h, "flat search");
-    if (h->raw_byte) return byte_refuse(h, "flat search");
+    // (a narrow store is served only after gamma_hip_set_flat_narrow_rows: the refusal is what every caller had before)
+    if (h->raw_half && !h->flat_narrow_rows) return half_refuse(h, "flat search");
+    if (h->raw_byte && !h->flat_narrow_rows) return byte_refuse(h, "flat search");
     GH_TRY(check_params(h, p, nq, k));
     gamma_hip_search_params pp;   // (the chunked paths run for k + 1 results: k = 4096, the ABI's largest, is beyond the mode)
     GH_TRY(resolve_ties(h, p, &pp, k + 1 <= gh::tie_replay_max_k() && h->nraw < ((int64_t)1 << 31),
                         "exact_ties = 1 with k = 4096 or 2^31 rows (flat search)"));
     p = &pp;
-    if (!h->d_raw && h->nraw > 0) return fail(h, GAMMA_HIP_EINVAL, "raw store not initialised");
+    if (!h->has_raw_rows() && h->nraw > 0) return fail(h, GAMMA_HIP_EINVAL, "raw store not initialised");
     if (h->raw_d <= 0) return fail(h, GAMMA_HIP_EINVAL, "raw store not initialised");
     if (k <= 0 || nq == 0) return GAMMA_HIP_OK;
+    // the store's rows as every reader below takes them: pointer + element type (fp32 rows: the launches they always were)
+    const gh::RowsRef rows{h->raw_byte ? static_cast<const void*>(h->d_raw_b) : h->raw_half ? static_cast<const void*>(h->d_raw_h)
+                                                                                          : static_cast<const void*>(h->d_raw),
+                           h->raw_elem_type()};
     GH_CHECK(h, hipSetDevice(h->device));
     const bool l2 = p->metric == GAMMA_HIP_METRIC_L2;
     const float neutral = l2 ? 3.402823466e+38f : -3.402823466e+38f;
@@ -1575,7 +1580,7 @@ int flat_search_device_locked(H* h, const gamma_hip_search_params* p, int nq, co
             GH_CHECK(h, h->w_cand_dis.ensure((size_t)nq * k * sizeof(float)));
             GH_CHECK(h, h->w_cand_ids.ensure((size_t)nq * k * sizeof(int64_t)));
             StageScope t(h, GAMMA_HIP_STAGE_FLAT);
-            gh::launch_pairwise_filtered(s, l2, d_x, nq, d, h->d_raw, N, h->w_dist.as<float>(), stride, filt, p->min_score,
+            gh::launch_pairwise_filtered(s, l2, d_x, nq, d, rows, N, h->w_dist.as<float>(), stride, filt, p->min_score,
                                          p->max_score, 0);
             int smax = h->small_presel > 0 ? h->small_presel : (N > 16384 ? (int)std::min<int64_t>(64, (N + 16383) / 16384) : 0);
             if (smax > 0) {
@@ -1591,6 +1596,7 @@ int flat_search_device_locked(H* h, const gamma_hip_search_params* p, int nq, co
                               d_labels, (int)N);
                 tr.d = d;
             }
+            // (has_rank = 0: the tail selects from the slab and reads no row -- its fp32 row pointer is null for a narrow store)
             gh::launch_small_tail(s, l2, h->w_dist.as<float>(), stride, nullptr, nq, k, 0, nullptr, nullptr, nullptr, nullptr,
                                   h->w_cand_dis.as<float>(), h->w_cand_pos.as<int>(), h->w_cand_ids.as<int64_t>(), 0, d_x, d,
                                   h->d_raw, N, k, p->min_score, p->max_score, neutral, d_distances, d_labels, smax,
@@ -1675,7 +1681,7 @@ int flat_search_device_locked(H* h, const gamma_hip_search_params* p, int nq, co
         for (int c = 0; c < nchunks; c++) {
             const int64_t r0 = (int64_t)c * rows_chunk;
             const int64_t nr = std::min<int64_t>(rows_chunk, N - r0);
-            gh::launch_pairwise_filtered(s, l2, xq, nc, d, h->d_raw + r0 * d, nr, h->w_dist.as<float>(),
+            gh::launch_pairwise_filtered(s, l2, xq, nc, d, rows.at(r0, d), nr, h->w_dist.as<float>(),
                                          rows_chunk, filt, p->min_score, p->max_score, r0);
             // per-chunk top-k: values + positions relative to the chunk
             gh::launch_select_topk(s, l2, h->w_dist.as<float>(), rows_chunk, nullptr, (int)nr, (int)nr, nc, k,
@@ -1737,7 +1743,7 @@ int flat_search_device_locked(H* h, const gamma_hip_search_params* p, int nq, co
             lg.nsl = log_nsl;
             GH_CHECK(h, hipMemsetAsync(lg.cnt, 0, (size_t)nc * log_nsl * sizeof(int), s));
         }
-        gh::launch_pairwise_filtered(s, l2, xq, nc, d, h->d_raw, rows_chunk, h->w_dist.as<float>(), rows_chunk, filt,
+        gh::launch_pairwise_filtered(s, l2, xq, nc, d, rows, rows_chunk, h->w_dist.as<float>(), rows_chunk, filt,
                                      p->min_score, p->max_score, 0);
         gh::launch_select_topk(s, l2, h->w_dist.as<float>(), rows_chunk, nullptr, (int)rows_chunk, (int)rows_chunk,
                                nc, k, h->w_cand_dis.as<float>(), h->w_cand_pos.as<int>());
@@ -1760,12 +1766,12 @@ int flat_search_device_locked(H* h, const gamma_hip_search_params* p, int nq, co
             const int64_t nr = pass_rows(r);
             if (mf) {
                 GH_CHECK(h, hipMemsetAsync(npairs, 0, (size_t)gh::flat_filter_counter_bytes(), s));
-                gh::launch_flat_filter(s, l2, d, h->w_fq.p, h->w_xn.as<float>(), tau, bnd, nc, h->d_raw + r * d, nr, r,
+                gh::launch_flat_filter(s, l2, d, h->w_fq.p, h->w_xn.as<float>(), tau, bnd, nc, rows.at(r, d), nr, r,
                                        h->w_fraw.p, npairs, pcap);
-                gh::launch_flat_exact(s, l2, h->w_fraw.p, npairs, pcap, xq, nc, d, h->d_raw, filt, p->min_score, p->max_score,
+                gh::launch_flat_exact(s, l2, h->w_fraw.p, npairs, pcap, xq, nc, d, rows, filt, p->min_score, p->max_score,
                                       em, over);
             } else {
-                gh::launch_pairwise_emit(s, l2, xq, nc, d, h->d_raw + r * d, nr, filt, p->min_score, p->max_score, r, em);
+                gh::launch_pairwise_emit(s, l2, xq, nc, d, rows.at(r, d), nr, filt, p->min_score, p->max_score, r, em);
             }
             lg.pass++;
             gh::launch_flat_compact(s, nc, k, em, tau, over, ties ? &lg : nullptr);
@@ -1831,7 +1837,7 @@ int flat_search_device_locked(H* h, const gamma_hip_search_params* p, int nq, co
                     GH_CHECK(h, h->w_fx.ensure((size_t)nf * d * sizeof(float)));
                     GH_CHECK(h, h->w_fslab.ensure((size_t)nf * stride * sizeof(float)));
                     gh::launch_gather_rows(s, d_x + (size_t)q0 * d, list + f0, nf, d, h->w_fx.as<float>());
-                    gh::launch_pairwise_filtered(s, l2, h->w_fx.as<float>(), nf, d, h->d_raw, N, h->w_fslab.as<float>(), stride, filt,
+                    gh::launch_pairwise_filtered(s, l2, h->w_fx.as<float>(), nf, d, rows, N, h->w_fslab.as<float>(), stride, filt,
                                                  p->min_score, p->max_score, 0);
                     gh::TieReplayArgs t2 = tr;
                     t2.nq = nf;
@@ -2687,6 +2693,7 @@ int gamma_hip_flat_search(gamma_hip_index* h, const gamma_hip_search_params* p, 
                           int k, float* distances, int64_t* labels) {
     if (!h) return GAMMA_HIP_EINVAL;
     // small unfiltered calls from concurrent client threads share device batches (see gamma_hip_ivfpq_search)
+    // (a narrow store is never combined, whatever gamma_hip_set_flat_narrow_rows says)
     if (h->combine && p && nq > 0 && nq <= COMB_MAX_NQ && k > 0 && x && distances && labels && h->raw_d > 0 && !h->raw_half && !h->raw_byte &&
         !p->has_range && p->n_range == 0 && p->n_field == 0 && p->n_term == 0)
         return combined_search(h, p, nq, x, k, distances, labels, /*kind=*/1);

@@ -79,6 +79,17 @@ void launch_pairwise_filtered(hipStream_t s, bool l2, const float* x, int nq, in
                               const float* y, int64_t ny, float* out, int64_t ld_out,
                               const FilterDesc& filt, float min_score, float max_score,
                               int64_t row_base);
+// Rows of the raw store as the flat path's readers take them: base pointer and element type (gamma_hip_raw_elem_type: 0 fp32,
+// 1 float16, 2 uint8, 3 int8).  The overloads that take one launch, for et == 0, exactly what the float overloads launch.
+struct RowsRef {
+    const void* p = nullptr;
+    int et = 0;
+    size_t esz() const { return et == 0 ? 4 : et == 1 ? 2 : 1; }
+    RowsRef at(int64_t row, int d) const { return RowsRef{static_cast<const char*>(p) + (size_t)row * d * esz(), et}; }
+    template <class T> const T* as() const { return static_cast<const T*>(p); }
+};
+void launch_pairwise_filtered(hipStream_t s, bool l2, const float* x, int nq, int d, const RowsRef& y, int64_t ny, float* out,
+                              int64_t ld_out, const FilterDesc& filt, float min_score, float max_score, int64_t row_base);
 // Flat search with a running bound: candidate lists of the queries of one call
 struct FlatEmit {
     const uint32_t* tau;        // [nq] key bound per query (0xff7fffff = anything valid)
@@ -92,6 +103,8 @@ int flat_list_cap();
 void launch_pairwise_emit(hipStream_t s, bool l2, const float* x, int nq, int d, const float* y, int64_t ny,
                           const FilterDesc& filt, float min_score, float max_score, int64_t row_base,
                           const FlatEmit& em);
+void launch_pairwise_emit(hipStream_t s, bool l2, const float* x, int nq, int d, const RowsRef& y, int64_t ny,
+                          const FilterDesc& filt, float min_score, float max_score, int64_t row_base, const FlatEmit& em);
 // candidate lists from the first chunk's top-k (vals / positions inside the chunk starting at row r0)
 void launch_flat_init(hipStream_t s, bool l2, const float* vals, const int* pos, int nq, int k, int64_t r0,
                       const FlatEmit& em, uint32_t* tau, int* kept = nullptr);   // kept: FlatLog::kept
@@ -124,6 +137,12 @@ void launch_flat_filter(hipStream_t s, bool l2, int d, const void* qimage, const
                         int nq, const float* y, int64_t ny, int64_t row_base, void* pairs, int* npairs, int64_t cap);
 void launch_flat_exact(hipStream_t s, bool l2, const void* pairs, const int* npairs, int64_t cap, const float* x, int nq, int d,
                        const float* store, const FilterDesc& filt, float min_score, float max_score, const FlatEmit& em,
+                       int* overflow);
+// (rows of any element type; `store` is the store's row 0)
+void launch_flat_filter(hipStream_t s, bool l2, int d, const void* qimage, const float* xn, const uint32_t* tau, float* bounds,
+                        int nq, const RowsRef& y, int64_t ny, int64_t row_base, void* pairs, int* npairs, int64_t cap);
+void launch_flat_exact(hipStream_t s, bool l2, const void* pairs, const int* npairs, int64_t cap, const float* x, int nq, int d,
+                       const RowsRef& store, const FilterDesc& filt, float min_score, float max_score, const FlatEmit& em,
                        int* overflow);
 // How the compiled reference's sgemm_ (MKL, the BLAS faiss links in the reference's build) sums the K dimension of
 // exhaustive_L2sqr_blas's x . y^T (faiss:utils/distances.cpp:215-296), measured against the compiled library

@@ -13,6 +13,7 @@
 #include "block_utils.h"
 #include "device_math.h"
 #include "filter_dev.h"
+#include "flat_rows_dev.h"
 #include "kernels.h"
 #include "rerank_dev.h"
 #include "scan_dev.h"
@@ -39,9 +40,11 @@ const char* launch_refused_take() {
 // block's query range; the query vector is wave-uniform and comes in through scalar
 // loads.  grid = (ceil(ny/256), ceil(nq/q_per_block)).
 // ------------------------------------------------------------------------------------
-template <bool L2, int D, bool FILTER>
+// Row: the rows' element type (float; uint16_t = IEEE binary16, uint8_t, int8_t: flat search over a narrow store,
+// gamma_hip_set_flat_narrow_rows).  A narrow row is widened as it is loaded -- exactly -- and is fp32 from then on.
+template <bool L2, int D, bool FILTER, class Row = float>
 __device__ __forceinline__ void pairwise_rowreg_body(int bx, int by, const float* __restrict__ x, int nq,
-                                                     const float* __restrict__ y, int64_t ny,
+                                                     const Row* __restrict__ y, int64_t ny,
                                                      float* __restrict__ out, int64_t ld_out,
                                                      int q_per_block, const FilterDesc& filt,
                                                      float min_score, float max_score,
@@ -51,7 +54,24 @@ __device__ __forceinline__ void pairwise_rowreg_body(int bx, int by, const float
     const int q1 = min(nq, q0 + q_per_block);
     float yr[D];
     const bool live = row < ny;
-    if (live) {
+    if constexpr (!RowKind<Row>::fp32) {
+        if (live) {   // D elements = whole 16-byte pieces (D % 16 == 0), the row 16-byte aligned
+            constexpr int P16 = 16 / (int)sizeof(Row);
+            const uint4* yp = reinterpret_cast<const uint4*>(y + row * D);
+#pragma unroll
+            for (int i = 0; i < D / P16; i++) {
+                const uint4 v = yp[i];
+                constexpr int PD = P16 / 4;   // elements per dword
+                row_dword_f<Row>(v.x, yr + P16 * i);
+                row_dword_f<Row>(v.y, yr + P16 * i + PD);
+                row_dword_f<Row>(v.z, yr + P16 * i + 2 * PD);
+                row_dword_f<Row>(v.w, yr + P16 * i + 3 * PD);
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < D; i++) yr[i] = 0.f;
+        }
+    } else if (live) {
         const float4* yp = reinterpret_cast<const float4*>(y + row * D);
 #pragma unroll
         for (int i = 0; i < D / 4; i++) {
@@ -89,15 +109,15 @@ __device__ __forceinline__ void pairwise_rowreg_body(int bx, int by, const float
         if (live) out[(int64_t)q * ld_out + row] = dis;
     }
 }
-template <bool L2, int D, bool FILTER>
+template <bool L2, int D, bool FILTER, class Row = float>
 __global__ __launch_bounds__(256) void k_pairwise_rowreg(const float* __restrict__ x, int nq,
-                                                         const float* __restrict__ y, int64_t ny,
+                                                         const Row* __restrict__ y, int64_t ny,
                                                          float* __restrict__ out, int64_t ld_out,
                                                          int q_per_block, FilterDesc filt,
                                                          float min_score, float max_score,
                                                          float sentinel, int64_t row_base) {
-    pairwise_rowreg_body<L2, D, FILTER>(blockIdx.x, blockIdx.y, x, nq, y, ny, out, ld_out, q_per_block, filt, min_score,
-                                        max_score, sentinel, row_base);
+    pairwise_rowreg_body<L2, D, FILTER, Row>(blockIdx.x, blockIdx.y, x, nq, y, ny, out, ld_out, q_per_block, filt, min_score,
+                                             max_score, sentinel, row_base);
 }
 
 // Same contract, queries staged in LDS and broadcast (one ds_read_b128 feeds a whole wave), packed
@@ -111,9 +131,9 @@ constexpr int PW_QT = 32;
 // the nq x ny distance slab, append (key << 32 | row id) of every distance within the query's current
 // bound tau[q] to the query's candidate list (cand[q][cap], cnt[q]; an atomic per survivor, and there
 // are about k per query and chunk).  Keys order like the distances ("smaller is better").
-template <bool L2, int D, bool FILTER, bool EMIT = false>
+template <bool L2, int D, bool FILTER, bool EMIT = false, class Row = float>
 __global__ __launch_bounds__(256) void k_pairwise_lds(const float* __restrict__ x, int nq,
-                                                      const float* __restrict__ y, int64_t ny,
+                                                      const Row* __restrict__ y, int64_t ny,
                                                       float* __restrict__ out, int64_t ld_out,
                                                       int q_per_block, FilterDesc filt, float min_score,
                                                       float max_score, float sentinel, int64_t row_base,
@@ -133,7 +153,37 @@ __global__ __launch_bounds__(256) void k_pairwise_lds(const float* __restrict__ 
     const int q1 = min(nq, q0 + q_per_block);
     f32x2 yr[D / 4];
     const bool live = row < ny;
-    {
+    if constexpr (RowKind<Row>::half) {
+        // narrow rows: both threads of a row ask for the SAME 16 bytes (one request; D * 2 bytes a row, 16-byte aligned) --
+        // the 8 halves 8i .. 8i + 7 -- and each keeps its 4: dwords x, y (even thread) or z, w (odd thread)
+        const uint4* yp = reinterpret_cast<const uint4*>(y + (live ? row : 0) * D);
+#pragma unroll
+        for (int i = 0; i < D / 8; i++) {
+            const uint4 v = yp[i];
+            const uint32_t vx = v.x, vy = v.y, vz = v.z, vw = v.w;   // (value selects on scalars, never an indexed private array)
+            float f[4];
+            row_dword_f<Row>(half ? vz : vx, f);
+            row_dword_f<Row>(half ? vw : vy, f + 2);
+            yr[2 * i] = f32x2{f[0], f[1]};
+            yr[2 * i + 1] = f32x2{f[2], f[3]};
+        }
+    } else if constexpr (RowKind<Row>::byte) {
+        // 16 bytes = the element groups 2i and 2i + 1 (D % 16 == 0: whole pieces, the row 16-byte aligned); the even thread's
+        // elements are dwords x and z, the odd thread's y and w
+        const uint4* yp = reinterpret_cast<const uint4*>(y + (live ? row : 0) * D);
+#pragma unroll
+        for (int i = 0; i < D / 16; i++) {
+            const uint4 v = yp[i];
+            const uint32_t vx = v.x, vy = v.y, vz = v.z, vw = v.w;
+            float f[8];
+            row_dword_f<Row>(half ? vy : vx, f);
+            row_dword_f<Row>(half ? vw : vz, f + 4);
+            yr[4 * i] = f32x2{f[0], f[1]};
+            yr[4 * i + 1] = f32x2{f[2], f[3]};
+            yr[4 * i + 2] = f32x2{f[4], f[5]};
+            yr[4 * i + 3] = f32x2{f[6], f[7]};
+        }
+    } else {
         const float4* yp = reinterpret_cast<const float4*>(y + (live ? row : 0) * D) + half;
 #pragma unroll
         for (int i = 0; i < D / 8; i++) {
@@ -211,9 +261,10 @@ __global__ __launch_bounds__(256) void k_pairwise_lds(const float* __restrict__ 
 }
 
 // generic-d fallback: same contract, row streamed from memory per query.
-template <bool L2, bool FILTER>
+// (narrow rows: any d, so a row may be aligned to its element only -- element loads, widened on load)
+template <bool L2, bool FILTER, class Row = float>
 __global__ __launch_bounds__(256) void k_pairwise_generic(const float* __restrict__ x, int nq, int d,
-                                                          const float* __restrict__ y, int64_t ny,
+                                                          const Row* __restrict__ y, int64_t ny,
                                                           float* __restrict__ out, int64_t ld_out,
                                                           int q_per_block, FilterDesc filt,
                                                           float min_score, float max_score,
@@ -222,11 +273,13 @@ __global__ __launch_bounds__(256) void k_pairwise_generic(const float* __restric
     if (row >= ny) return;
     const int q0 = blockIdx.y * q_per_block;
     const int q1 = min(nq, q0 + q_per_block);
-    const float* yr = y + row * d;
+    const Row* yr = y + row * d;
     bool valid = true;
     if (FILTER) valid = is_valid_doc(filt, row_base + row);
     for (int q = q0; q < q1; q++) {
-        float dis = fvec_dist<L2>(x + (int64_t)q * d, yr, d);
+        float dis;
+        if constexpr (RowKind<Row>::fp32) dis = fvec_dist<L2>(x + (int64_t)q * d, yr, d);
+        else dis = fvec_dist<L2>(x + (int64_t)q * d, RowElems<Row>{yr}, d);
         if (FILTER) {
             if (!valid || !(dis <= max_score && dis >= min_score)) dis = sentinel;
         }
@@ -255,14 +308,14 @@ static int pairwise_q_per_block(int nq, int64_t row_blocks) {
     return q_per_block;
 }
 
-template <bool L2>
-static void launch_pairwise_emit_t(hipStream_t s, const float* x, int nq, int d, const float* y, int64_t ny,
+template <bool L2, class Row = float>
+static void launch_pairwise_emit_t(hipStream_t s, const float* x, int nq, int d, const Row* y, int64_t ny,
                                    const FilterDesc& filt, float min_score, float max_score, float sentinel,
                                    int64_t row_base, const FlatEmit& em) {
     const int q_per_block = pairwise_q_per_block(nq, (ny + 255) / 256);
     const dim3 grid((unsigned)((ny + 127) / 128), (unsigned)((nq + q_per_block - 1) / q_per_block));
 #define GH_EMIT(DD)                                                                                         \
-    hipLaunchKernelGGL((k_pairwise_lds<L2, DD, true, true>), grid, dim3(256), 0, s, x, nq, y, ny, nullptr, 0, \
+    hipLaunchKernelGGL((k_pairwise_lds<L2, DD, true, true, Row>), grid, dim3(256), 0, s, x, nq, y, ny, nullptr, 0, \
                        q_per_block, filt, min_score, max_score, sentinel, row_base, em)
     switch (d) {
         case 128: GH_EMIT(128); break;
@@ -283,8 +336,8 @@ void launch_pairwise_emit(hipStream_t s, bool l2, const float* x, int nq, int d,
     else launch_pairwise_emit_t<false>(s, x, nq, d, y, ny, filt, min_score, max_score, -INFINITY, row_base, em);
 }
 
-template <bool L2, bool FILTER>
-static void launch_pairwise_t(hipStream_t s, const float* x, int nq, int d, const float* y,
+template <bool L2, bool FILTER, class Row = float>
+static void launch_pairwise_t(hipStream_t s, const float* x, int nq, int d, const Row* y,
                               int64_t ny, float* out, int64_t ld_out, const FilterDesc& filt,
                               float min_score, float max_score, float sentinel,
                               int64_t row_base) {
@@ -298,11 +351,11 @@ static void launch_pairwise_t(hipStream_t s, const float* x, int nq, int d, cons
 #define GH_ROWREG(DD)                                                                                  \
     do {                                                                                               \
         if (use_lds)                                                                                   \
-            hipLaunchKernelGGL((k_pairwise_lds<L2, DD, FILTER>), dim3((unsigned)((ny + 127) / 128), grid.y), \
+            hipLaunchKernelGGL((k_pairwise_lds<L2, DD, FILTER, false, Row>), dim3((unsigned)((ny + 127) / 128), grid.y), \
                                dim3(256), 0, s, x, nq, y, ny, out, ld_out, q_per_block, filt, min_score, \
                                max_score, sentinel, row_base, FlatEmit{});                             \
         else                                                                                           \
-            hipLaunchKernelGGL((k_pairwise_rowreg<L2, DD, FILTER>), grid, dim3(256), 0, s, x, nq, y, ny, \
+            hipLaunchKernelGGL((k_pairwise_rowreg<L2, DD, FILTER, Row>), grid, dim3(256), 0, s, x, nq, y, ny, \
                                out, ld_out, q_per_block, filt, min_score, max_score, sentinel, row_base); \
     } while (0)
     switch (d) {
@@ -312,7 +365,7 @@ static void launch_pairwise_t(hipStream_t s, const float* x, int nq, int d, cons
         case 32: GH_ROWREG(32); break;
         case 16: GH_ROWREG(16); break;
         default:
-            hipLaunchKernelGGL((k_pairwise_generic<L2, FILTER>), grid, dim3(256), 0, s, x, nq, d, y,
+            hipLaunchKernelGGL((k_pairwise_generic<L2, FILTER, Row>), grid, dim3(256), 0, s, x, nq, d, y,
                                ny, out, ld_out, q_per_block, filt, min_score, max_score, sentinel,
                                row_base);
     }
@@ -416,6 +469,42 @@ void launch_pairwise_filtered(hipStream_t s, bool l2, const float* x, int nq, in
     else
         launch_pairwise_t<false, true>(s, x, nq, d, y, ny, out, ld_out, filt, min_score, max_score,
                                        -INFINITY, row_base);
+}
+
+// ---- flat search over a narrow raw store: the same launches over rows of float16 / uint8 / int8 (fp32 rows go through the
+//      entry points above: same instantiation, same grid) ----
+template <class Row>
+static void pairwise_filtered_rows(hipStream_t s, bool l2, const float* x, int nq, int d, const Row* y, int64_t ny, float* out,
+                                   int64_t ld_out, const FilterDesc& filt, float min_score, float max_score, int64_t row_base) {
+    if (l2) launch_pairwise_t<true, true, Row>(s, x, nq, d, y, ny, out, ld_out, filt, min_score, max_score, INFINITY, row_base);
+    else launch_pairwise_t<false, true, Row>(s, x, nq, d, y, ny, out, ld_out, filt, min_score, max_score, -INFINITY, row_base);
+}
+void launch_pairwise_filtered(hipStream_t s, bool l2, const float* x, int nq, int d, const RowsRef& y, int64_t ny, float* out,
+                              int64_t ld_out, const FilterDesc& filt, float min_score, float max_score, int64_t row_base) {
+    switch (y.et) {
+        case 0: launch_pairwise_filtered(s, l2, x, nq, d, y.as<float>(), ny, out, ld_out, filt, min_score, max_score, row_base); break;
+        case 1: pairwise_filtered_rows(s, l2, x, nq, d, y.as<uint16_t>(), ny, out, ld_out, filt, min_score, max_score, row_base); break;
+        case 2: pairwise_filtered_rows(s, l2, x, nq, d, y.as<uint8_t>(), ny, out, ld_out, filt, min_score, max_score, row_base); break;
+        case 3: pairwise_filtered_rows(s, l2, x, nq, d, y.as<int8_t>(), ny, out, ld_out, filt, min_score, max_score, row_base); break;
+        default: launch_refused("launch_pairwise_filtered: unknown row element type");
+    }
+}
+template <class Row>
+static void pairwise_emit_rows(hipStream_t s, bool l2, const float* x, int nq, int d, const Row* y, int64_t ny,
+                               const FilterDesc& filt, float min_score, float max_score, int64_t row_base, const FlatEmit& em) {
+    if (ny <= 0 || nq <= 0) return;
+    if (l2) launch_pairwise_emit_t<true, Row>(s, x, nq, d, y, ny, filt, min_score, max_score, INFINITY, row_base, em);
+    else launch_pairwise_emit_t<false, Row>(s, x, nq, d, y, ny, filt, min_score, max_score, -INFINITY, row_base, em);
+}
+void launch_pairwise_emit(hipStream_t s, bool l2, const float* x, int nq, int d, const RowsRef& y, int64_t ny,
+                          const FilterDesc& filt, float min_score, float max_score, int64_t row_base, const FlatEmit& em) {
+    switch (y.et) {
+        case 0: launch_pairwise_emit(s, l2, x, nq, d, y.as<float>(), ny, filt, min_score, max_score, row_base, em); break;
+        case 1: pairwise_emit_rows(s, l2, x, nq, d, y.as<uint16_t>(), ny, filt, min_score, max_score, row_base, em); break;
+        case 2: pairwise_emit_rows(s, l2, x, nq, d, y.as<uint8_t>(), ny, filt, min_score, max_score, row_base, em); break;
+        case 3: pairwise_emit_rows(s, l2, x, nq, d, y.as<int8_t>(), ny, filt, min_score, max_score, row_base, em); break;
+        default: launch_refused("launch_pairwise_emit: unknown row element type");
+    }
 }
 
 }  // namespace gh

@@ -16,6 +16,46 @@ namespace tig_gamma {
 
 REGISTER_MODEL(HIPFLAT, GammaFLATHIPIndex);
 
+#define FLOG(...)                         \
+  do {                                    \
+    fprintf(stderr, "[HIPFLAT] ");        \
+    fprintf(stderr, __VA_ARGS__);         \
+    fprintf(stderr, "\n");                \
+  } while (0)
+
+namespace {
+HIPFlatRowsFn &FlatRows() {
+  static HIPFlatRowsFn fn = nullptr;
+  return fn;
+}
+}  // namespace
+int RegisterHIPFlatRows(HIPFlatRowsFn fn) {
+  FlatRows() = fn;
+  return 0;
+}
+HIPFlatRowsFn FindHIPFlatRows() { return FlatRows(); }
+
+int GammaFLATHIPIndex::ParseRawDtype(const std::string &model_parameters, int *et) {
+  *et = 0;
+  if (model_parameters == "") return 0;
+  utils::JsonParser jp;
+  if (jp.Parse(model_parameters.c_str())) return -1;
+  std::string rdt;
+  if (jp.GetString("raw_dtype", rdt)) return 0;
+  static const char *const names[4] = {"float32", "float16", "uint8", "int8"};
+  for (int i = 0; i < 4; i++)
+    if (!strcasecmp(names[i], rdt.c_str())) {
+      *et = i;
+      return 0;
+    }
+  FLOG("invalid raw_dtype = %s", rdt.c_str());
+  return -1;
+}
+
+bool GammaFLATHIPIndex::RowsStorable(const char *what, const float *x, int64_t nrows) {
+  return raw_et_ < 2 || HIPRowsStorableI8(raw_i8_ops_, raw_et_ == 3, d_, "HIPFLAT", what, x, nrows);   // HIPIVFPQ's rule
+}
+
 GammaFLATHIPIndex::~GammaFLATHIPIndex() {
   if (h_) gamma_hip_destroy(h_);
 }
@@ -35,11 +75,22 @@ int GammaFLATHIPIndex::Init(const std::string &model_parameters, int indexing_si
     if (!jp.GetInt("device_filters", v)) device_filters_ = v != 0;   // HIP only, see filter_bridge.h
     if (!jp.GetInt("exact_ties", v)) exact_ties_ = v != 0;           // HIP only: the reference's heap order inside ties (default on)
   }
+  if (ParseRawDtype(model_parameters, &raw_et_)) return -1;
+  // a narrow store needs its initialiser and the handle's switch; a build without one of them rejects the value
+  const HIPFlatRowsFn flat_rows = raw_et_ ? FindHIPFlatRows() : nullptr;
+  const HIPRawInitFn init_f16 = raw_et_ == 1 ? FindHIPRawInitF16() : nullptr;
+  raw_i8_ops_ = raw_et_ >= 2 ? FindHIPRawI8() : nullptr;
+  if (raw_et_ && (!flat_rows || (raw_et_ == 1 ? !init_f16 : !raw_i8_ops_))) {
+    FLOG("raw_dtype: this build of the plugin has no flat search over float16 / uint8 / int8 rows");
+    return -1;
+  }
   d_ = vector_->MetaInfo()->Dimension();
   const char *dev = getenv("GAMMA_HIP_DEVICE");
   if (gamma_hip_create(dev ? atoi(dev) : 0, &h_)) return -1;
   if (gamma_hip_set_exact_ties(h_, exact_ties_ ? 1 : 0)) return -1;
-  return gamma_hip_raw_init(h_, d_) ? -1 : 0;
+  if (!raw_et_) return gamma_hip_raw_init(h_, d_) ? -1 : 0;
+  if (raw_et_ == 1 ? init_f16(h_, d_) : raw_i8_ops_->init(h_, d_, raw_et_ == 3)) return -1;
+  return flat_rows(h_, 1) ? -1 : 0;
 }
 
 RetrievalParameters *GammaFLATHIPIndex::Parse(const std::string &parameters) {
@@ -60,6 +111,7 @@ RetrievalParameters *GammaFLATHIPIndex::Parse(const std::string &parameters) {
 
 bool GammaFLATHIPIndex::Add(int n, const uint8_t *vec) {
   // the CPU model reads vector_ at search time; the device keeps a mirror, fed in vid order at explicit rows
+  if (!RowsStorable("add", reinterpret_cast<const float *>(vec), n)) return false;   // before anything changes
   std::lock_guard<std::mutex> g(raw_mu_);
   if (gamma_hip_raw_write(h_, uploaded_, n, reinterpret_cast<const float *>(vec))) return false;
   uploaded_ += n;
@@ -79,6 +131,8 @@ int GammaFLATHIPIndex::SyncVid2DocID(int64_t upto) {
 }
 
 int GammaFLATHIPIndex::Update(const std::vector<int64_t> &ids, const std::vector<const uint8_t *> &vecs) {
+  for (size_t i = 0; i < ids.size(); i++)   // every row before any is written
+    if (!RowsStorable("update", reinterpret_cast<const float *>(vecs[i]), 1)) return -1;
   std::lock_guard<std::mutex> g(raw_mu_);
   for (size_t i = 0; i < ids.size(); i++)
     if (ids[i] < uploaded_ && gamma_hip_raw_update(h_, ids[i], reinterpret_cast<const float *>(vecs[i]))) return -1;
@@ -104,17 +158,23 @@ int GammaFLATHIPIndex::Load(const std::string &dir) {
   }
   std::lock_guard<std::mutex> g(raw_mu_);
   const int64_t nvec = (int64_t)vector_->MetaInfo()->Size();
-  for (int64_t i0 = uploaded_; i0 < nvec; i0 += 65536) {
-    const int64_t nb = std::min<int64_t>(65536, nvec - i0);
-    std::vector<int64_t> vids(nb);
-    for (int64_t i = 0; i < nb; i++) vids[i] = i0 + i;
-    ScopeVectors sv;
-    if (vector_->Gets(vids, sv)) return -1;
-    std::vector<float> buf((size_t)nb * d_);
-    for (int64_t i = 0; i < nb; i++) memcpy(&buf[(size_t)i * d_], sv.Get((int)i), sizeof(float) * d_);
-    if (gamma_hip_raw_write(h_, i0, nb, buf.data())) return -1;
-    uploaded_ = i0 + nb;
-  }
+  // a byte model: a pass over the rows with the acceptance predicate first, so that a refused row leaves the mirror as it was
+  for (int pass = raw_et_ >= 2 ? 0 : 1; pass < 2; pass++)
+    for (int64_t i0 = uploaded_; i0 < nvec; i0 += 65536) {
+      const int64_t nb = std::min<int64_t>(65536, nvec - i0);
+      std::vector<int64_t> vids(nb);
+      for (int64_t i = 0; i < nb; i++) vids[i] = i0 + i;
+      ScopeVectors sv;
+      if (vector_->Gets(vids, sv)) return -1;
+      std::vector<float> buf((size_t)nb * d_);
+      for (int64_t i = 0; i < nb; i++) memcpy(&buf[(size_t)i * d_], sv.Get((int)i), sizeof(float) * d_);
+      if (pass == 0) {
+        if (!RowsStorable("load", buf.data(), nb)) return -1;
+        continue;
+      }
+      if (gamma_hip_raw_write(h_, i0, nb, buf.data())) return -1;
+      uploaded_ = i0 + nb;
+    }
   if (SyncVid2DocID(uploaded_)) return -1;
   return (int)uploaded_;
 }

@@ -1,6 +1,9 @@
 // GammaFLATHIPIndex -- RetrievalModel plugin "HIPFLAT": Gamma's brute-force model
 // (reference index/impl/gamma_index_flat.{h,cc}) on an MI355X.  Same JSON keys
 // (metric_type, parallel_on_queries), same Search contract.
+// HIP only: "raw_dtype": "float32" (the default) | "float16" | "uint8" | "int8" -- the element type of the device's rows, which
+// ARE the index.  Results are those of the fp32 model over the widened rows; a byte model accepts a row only if every value
+// converts exactly (HIPIVFPQ's rule), a float16 model rounds and refuses an overflow.
 #pragma once
 #include <atomic>
 #include <mutex>
@@ -12,6 +15,14 @@
 #include "filter_bridge.h"
 
 namespace tig_gamma {
+
+struct HIPRawI8Ops;   // gamma_index_ivfpq_hip.h
+// Flat search over narrow rows is a switch of the handle (gamma_hip_set_flat_narrow_rows), registered at static-initialisation
+// time by gamma_index_flat_rows_hip.cc -- the only host file that names it (the idiom of RegisterHIPRawI8).  A build of the plugin
+// without that file (against a C ABI without the entry) has none, and HIPFLAT::Init rejects a narrow "raw_dtype".
+typedef int (*HIPFlatRowsFn)(gamma_hip_index *h, int on);
+int RegisterHIPFlatRows(HIPFlatRowsFn fn);
+HIPFlatRowsFn FindHIPFlatRows();
 
 class HIPFlatRetrievalParameters : public RetrievalParameters {
  public:
@@ -45,8 +56,14 @@ class GammaFLATHIPIndex : public RetrievalModel {
   int Dump(const std::string &dir) override { return 0; }
   int Load(const std::string &dir) override;
   DistanceComputeType metric_type_ = DistanceComputeType::INNER_PRODUCT;
+  // the "raw_dtype" key of the model parameters: *et = 0 float32 (also when the key is absent), 1 float16, 2 uint8, 3 int8
+  // (gamma_hip_raw_elem_type); -1 for any other string or parameters that do not parse
+  static int ParseRawDtype(const std::string &model_parameters, int *et);
 
  private:
+  int raw_et_ = 0;
+  const HIPRawI8Ops *raw_i8_ops_ = nullptr;
+  bool RowsStorable(const char *what, const float *x, int64_t nrows);   // byte rows: every value converts exactly
   gamma_hip_index *h_ = nullptr;
   std::atomic<int64_t> ties_said_{0};   // WarnTiesNotHonoured: what this model has reported so far
   int d_ = 0;

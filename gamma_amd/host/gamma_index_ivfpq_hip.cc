@@ -435,13 +435,17 @@ int GammaIVFPQHIPIndex::TrainingSet(std::vector<float> &xt, size_t &num) {
   return 0;
 }
 
-bool GammaIVFPQHIPIndex::RowsStorable(const char *what, const float *x, int64_t nrows) {
-  if (!raw_i8_) return true;
+bool HIPRowsStorableI8(const HIPRawI8Ops *ops, bool is_signed, int d, const char *model, const char *what, const float *x,
+                       int64_t nrows) {
   int64_t bad = -1;
-  if (!raw_i8_ops_->check(x, nrows * d_, raw_i8_ == 2, &bad)) return true;
-  HLOG("%s refused: raw_dtype = %s stores a value only if it converts exactly, and element %d of row %lld is %g", what,
-       raw_i8_ == 2 ? "int8" : "uint8", (int)(bad % d_), (long long)(bad / d_), (double)x[bad]);
+  if (!ops->check(x, nrows * d, is_signed ? 1 : 0, &bad)) return true;
+  fprintf(stderr, "[%s] %s refused: raw_dtype = %s stores a value only if it converts exactly, and element %d of row %lld is %g\n",
+          model, what, is_signed ? "int8" : "uint8", (int)(bad % d), (long long)(bad / d), (double)x[bad]);
   return false;
+}
+
+bool GammaIVFPQHIPIndex::RowsStorable(const char *what, const float *x, int64_t nrows) {
+  return !raw_i8_ || HIPRowsStorableI8(raw_i8_ops_, raw_i8_ == 2, d_, "HIPIVFPQ", what, x, nrows);
 }
 
 bool GammaIVFPQHIPIndex::Add(int n, const uint8_t *vec) {

@@ -82,6 +82,10 @@ struct HIPRawI8Ops {
 };
 int RegisterHIPRawI8(const HIPRawI8Ops *ops);
 const HIPRawI8Ops *FindHIPRawI8();
+// The byte stores' rule in front of a model's writers (HIPIVFPQ and HIPFLAT): true when every value of the nrows x d rows converts
+// exactly; otherwise one log line "[model] what refused: ..." naming row, element and value, and false -- before anything changes.
+bool HIPRowsStorableI8(const HIPRawI8Ops *ops, bool is_signed, int d, const char *model, const char *what, const float *x,
+                       int64_t nrows);
 
 // "opq": the rotation's entries of the C ABI (gamma_hip_opq_train / _set / _get / _apply) reach the model through this table,
 // registered at static-initialisation time by gamma_index_ivfpq_opq_hip.cc -- the only host file that names them.  A build of

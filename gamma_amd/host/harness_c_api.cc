@@ -12,6 +12,7 @@
 #include <thread>
 #include <vector>
 
+#include "gamma_index_flat_hip.h"
 #include "gamma_index_ivfpq_hip.h"
 #include "iwpq_io.h"
 #include "plugin_api.h"
@@ -409,6 +410,12 @@ void gh_parse_ivfpq_raw_dtype(const char *str, int *out) {
   HIPIVFPQModelParams p;
   out[0] = p.Parse(str);
   out[1] = p.raw_i8 ? 1 + p.raw_i8 : p.raw_f16 ? 1 : 0;
+}
+// the HIP-only "raw_dtype" key of the HIPFLAT model's parameters: out = {rc, element type as above}
+void gh_parse_flat_raw_dtype(const char *str, int *out) {
+  int et = 0;
+  out[0] = GammaFLATHIPIndex::ParseRawDtype(str, &et);
+  out[1] = et;
 }
 // HIPIVFPQRetrievalParameters via Parse on an un-Init'ed model: out = {rc, metric, recall_num, nprobe}
 void gh_parse_ivfpq_retrieval_params(const char *str, int *out) {

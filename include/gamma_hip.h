@@ -180,6 +180,14 @@ int gamma_hip_coarse_filter_stats(gamma_hip_index* h, int64_t* out4);
  * the regular chain, n >= 2 = automatic with the two-level selection of long candidate rows forced on with n slices
  * (tests; by default it is used when nprobe x 1.5 mean list lengths exceed 16384).  Results are identical either way. */
 int gamma_hip_set_small_path(gamma_hip_index* h, int on);
+/* Flat search over a narrow raw store.  on: 0 (default) = gamma_hip_flat_search, _flat_search_device and
+ * _flat_search_device_wait refuse a float16 / uint8 / int8 store (gamma_hip_raw_init_f16 / _i8) with
+ * GAMMA_HIP_EUNSUPPORTED, as every other reader of fp32 rows does; 1 = the three serve it: every row is widened to fp32
+ * -- exactly -- as it is loaded and every distance is fvec_L2sqr / fvec_inner_product of the fp32 query and the widened
+ * row, so distances and labels are byte-identical to those of an fp32 store that holds the widened rows (DESIGN.md
+ * section 15).  Nothing else changes: IVFFLAT search, the shard / merge / export entries, gamma_hip_raw_put / _raw_drop
+ * and a sparse store keep refusing a narrow store, and an fp32 store is served as before whatever the switch says. */
+int gamma_hip_set_flat_narrow_rows(gamma_hip_index* h, int on);
 /* out3 = {coarse rows redone, queries whose recall_num cut went through a tie, queries replayed} since creation
  * or the last reset; meaningful with exact ties on */
 int gamma_hip_tie_stats(gamma_hip_index* h, int64_t* out3, int reset);
