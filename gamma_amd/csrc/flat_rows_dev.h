@@ -1,4 +1,5 @@
-// flat_rows_dev.h -- loads of narrow raw rows for the flat path's readers (kernels.hip, flat_mfma.hip): rows of IEEE binary16
+// flat_rows_dev.h -- loads of narrow raw rows for the readers of the flat path (kernels.hip, flat_mfma.hip) and of the
+// IVFFLAT list-major scan (ivfflat.hip): rows of IEEE binary16
 // (uint16_t), uint8 and int8 widen to fp32 EXACTLY, so a reader that widens on load and then runs its fp32 arithmetic unchanged
 // computes, bit for bit, what it computes over an fp32 store that holds the widened rows.  Only loads and widenings live here.
 #pragma once
@@ -79,6 +80,53 @@ __device__ __forceinline__ void row_widen8(const Raw8<Row>& r, float* f) {
     } else {
         row_dword_f<Row>(r.a.x, f);
         row_dword_f<Row>(r.a.y, f + 4);
+    }
+}
+
+// A row held by TWO threads (k_pairwise_lds, k_ivfflat_lm): the even thread owns AVX lanes 0-3 (elements 8i .. 8i + 3), the odd
+// one lanes 4-7, D / 2 values each, as D / 4 packed pairs in element order.  rowp: the row's first element, 16-byte aligned
+// (D % 16 == 0).  Narrow rows: both threads of a row ask for the SAME 16 bytes (one request) and each keeps its dwords --
+// value selects on scalars, never an indexed private array -- widened once.
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+template <class Row, int D>
+__device__ __forceinline__ void row_pair_load(const Row* __restrict__ rowp, int half, f32x2* yr) {
+    if constexpr (RowKind<Row>::half) {
+        // 16 bytes = the 8 halves 8i .. 8i + 7; the even thread's are dwords x, y, the odd thread's z, w
+        const uint4* yp = reinterpret_cast<const uint4*>(rowp);
+#pragma unroll
+        for (int i = 0; i < D / 8; i++) {
+            const uint4 v = yp[i];
+            const uint32_t vx = v.x, vy = v.y, vz = v.z, vw = v.w;
+            float f[4];
+            row_dword_f<Row>(half ? vz : vx, f);
+            row_dword_f<Row>(half ? vw : vy, f + 2);
+            yr[2 * i] = f32x2{f[0], f[1]};
+            yr[2 * i + 1] = f32x2{f[2], f[3]};
+        }
+    } else if constexpr (RowKind<Row>::byte) {
+        // 16 bytes = the element groups 2i and 2i + 1 (whole pieces); the even thread's elements are dwords x and z, the odd
+        // thread's y and w
+        const uint4* yp = reinterpret_cast<const uint4*>(rowp);
+#pragma unroll
+        for (int i = 0; i < D / 16; i++) {
+            const uint4 v = yp[i];
+            const uint32_t vx = v.x, vy = v.y, vz = v.z, vw = v.w;
+            float f[8];
+            row_dword_f<Row>(half ? vy : vx, f);
+            row_dword_f<Row>(half ? vw : vz, f + 4);
+            yr[4 * i] = f32x2{f[0], f[1]};
+            yr[4 * i + 1] = f32x2{f[2], f[3]};
+            yr[4 * i + 2] = f32x2{f[4], f[5]};
+            yr[4 * i + 3] = f32x2{f[6], f[7]};
+        }
+    } else {
+        const float4* yp = reinterpret_cast<const float4*>(rowp) + half;
+#pragma unroll
+        for (int i = 0; i < D / 8; i++) {
+            const float4 v = yp[2 * i];
+            yr[2 * i] = f32x2{v.x, v.y};
+            yr[2 * i + 1] = f32x2{v.z, v.w};
+        }
     }
 }
 

@@ -1321,6 +1321,13 @@ int ivfpq_search_device_locked(H* h, const gamma_hip_search_params* p, int nq, c
     return GAMMA_HIP_OK;
 }
 
+// the raw store's rows as the exact scanners' kernels take them: base pointer + element type (kernels.h)
+gh::RowsRef raw_rows_ref(const H* h) {
+    return gh::RowsRef{h->raw_byte ? static_cast<const void*>(h->d_raw_b) : h->raw_half ? static_cast<const void*>(h->d_raw_h)
+                                                                                     : static_cast<const void*>(h->d_raw),
+                       h->raw_elem_type()};
+}
+
 // ---- IVFFLAT (index/impl/gamma_index_ivfflat.cc:392-567) ------------------------------------------------------
 // coarse quantizer (the IVFPQ one) -> slab offsets -> exact distance of every entry of the probed lists
 // (k_ivfflat_scan) -> top-k of the slab in (distance, scan position) order -> ids.  The reference's k-heap keeps
@@ -1364,8 +1371,8 @@ void flat_tie_args(H* h, gh::TieReplayArgs* tr, bool l2, int nq, int64_t q_strid
     tr->fixed_n = fixed_n;
 }
 
-int ivfflat_small(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int nq, const float* d_x, int k,
-                  float* d_distances, int64_t* d_labels) {
+int ivfflat_small(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, const gh::RowsRef& rows, int nq, const float* d_x,
+                  int k, float* d_distances, int64_t* d_labels) {
     const int P = p->nprobe, d = h->d, nlist = h->nlist;
     const bool l2 = p->metric == GAMMA_HIP_METRIC_L2;
     hipStream_t s = h->stream;
@@ -1392,7 +1399,7 @@ int ivfflat_small(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int
                                    h->w_qtotal.as<int>(), h->w_pair_base.as<int64_t>(), nullptr, nullptr, 0, nullptr, nullptr,
                                    nullptr, 0, tie_on(p) ? 1 : 0, h->d_tie_stats);
     const int need_filter = (fc.any_clause || (h->d_bitmap && h->bitmap_any)) ? 1 : 0;
-    gh::launch_ivfflat_scan(s, l2, d_x, nq, d, P, h->w_pair_off.as<int>(), h->w_pair_base.as<int64_t>(), h->d_ids, h->d_raw,
+    gh::launch_ivfflat_scan(s, l2, d_x, nq, d, P, h->w_pair_off.as<int>(), h->w_pair_base.as<int64_t>(), h->d_ids, rows,
                             h->nraw, q_stride, h->w_dist.as<float>(), fc.d_tab, need_filter, p->min_score, p->max_score);
     int smax = 0;   // long candidate rows: two-level selection (ivfpq_small)
     {
@@ -1430,8 +1437,9 @@ int ivfflat_small(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int
 int ivfflat_search_device_locked(H* h, const gamma_hip_search_params* p, int nq, const float* d_x, int k,
                                  float* d_distances, int64_t* d_labels) {
     if (h->raw_sparse) return fail(h, GAMMA_HIP_EUNSUPPORTED, "the raw store holds this shard's rows only (gamma_hip_raw_put)");
-    if (h->raw_half) return half_refuse(h, "IVFFLAT search");
-    if (h->raw_byte) return byte_refuse(h, "IVFFLAT search");
+    // (a narrow store is served only after gamma_hip_set_ivfflat_narrow_rows: the refusal is what every caller had before)
+    if (h->raw_half && !h->ivfflat_narrow_rows) return half_refuse(h, "IVFFLAT search");
+    if (h->raw_byte && !h->ivfflat_narrow_rows) return byte_refuse(h, "IVFFLAT search");
     GH_TRY(check_params(h, p, nq, k));
     gamma_hip_search_params pp;
     GH_TRY(resolve_ties(h, p, &pp, p->nprobe <= gh::tie_replay_max_probes(), "exact_ties = 1 with nprobe > 1024"));
@@ -1439,8 +1447,10 @@ int ivfflat_search_device_locked(H* h, const gamma_hip_search_params* p, int nq,
     if (!h->ivf_init || !h->ivfflat || h->binivf) return fail(h, GAMMA_HIP_EINVAL, "ivfflat not initialised");
     if (!h->trained) return fail(h, GAMMA_HIP_ENOTTRAINED, "ivfflat not trained");
     if (p->nprobe <= 0 || p->nprobe > h->nlist) return fail(h, GAMMA_HIP_EINVAL, "nprobe out of range");
-    if (!h->d_raw || h->raw_d != h->d) return fail(h, GAMMA_HIP_EINVAL, "ivfflat needs the raw store");
+    if (!h->has_raw_rows() || h->raw_d != h->d) return fail(h, GAMMA_HIP_EINVAL, "ivfflat needs the raw store");
     if (k <= 0 || nq == 0) return GAMMA_HIP_OK;
+    // the store's rows as the scan takes them: pointer + element type (fp32 rows: the launches they always were)
+    const gh::RowsRef rows = raw_rows_ref(h);
     GH_CHECK(h, hipSetDevice(h->device));
     const bool l2 = p->metric == GAMMA_HIP_METRIC_L2;
     const float neutral = l2 ? 3.402823466e+38f : -3.402823466e+38f;
@@ -1457,7 +1467,7 @@ int ivfflat_search_device_locked(H* h, const gamma_hip_search_params* p, int nq,
         if (!off && h->small_path && nq <= 512 && P <= 128 && k <= 1024 && !h->profile &&
             !fc.d_qf && !h->d_list_mask && nlist <= 16384 && (int64_t)nq * P < 2 * (int64_t)nlist &&
             (int64_t)P * std::max(1, h->max_list_len) <= (1 << 22))
-            return ivfflat_small(h, &pp, fc, nq, d_x, k, d_distances, d_labels);
+            return ivfflat_small(h, &pp, fc, rows, nq, d_x, k, d_distances, d_labels);
     }
     ListCompaction restore(h);
     GH_TRY(compact_lists_for_call(h, &fc, (int64_t)nq * P * (h->ntotal / std::max(1, nlist)), true, &restore));
@@ -1488,11 +1498,11 @@ int ivfflat_search_device_locked(H* h, const gamma_hip_search_params* p, int nq,
             if (!no_lm && gh::ivfflat_lm_supported(h->d) && (int64_t)nc * P >= 2 * (int64_t)nlist && !h->d_list_mask) {
                 GH_CHECK(h, h->w_lm_units.ensure(gh::ivfflat_lm_scratch_bytes(nc, P, nlist)));
                 gh::launch_ivfflat_lm(s, l2, xq, nc, h->d, P, h->w_probe.as<int>(), h->w_pair_off.as<int>(), h->d_list_off,
-                                      h->d_list_len, nlist, h->d_ids, h->d_raw, h->nraw, q_stride, h->w_dist.as<float>(),
+                                      h->d_list_len, nlist, h->d_ids, rows, h->nraw, q_stride, h->w_dist.as<float>(),
                                       fc.d_tab, need_filter, p->min_score, p->max_score, h->w_lm_units.p);
             } else {
                 gh::launch_ivfflat_scan(s, l2, xq, nc, h->d, P, h->w_pair_off.as<int>(), h->w_pair_base.as<int64_t>(),
-                                        h->d_ids, h->d_raw, h->nraw, q_stride, h->w_dist.as<float>(), fc.d_tab, need_filter,
+                                        h->d_ids, rows, h->nraw, q_stride, h->w_dist.as<float>(), fc.d_tab, need_filter,
                                         p->min_score, p->max_score);
             }
         }
@@ -1556,9 +1566,7 @@ int flat_search_device_locked(H* h, const gamma_hip_search_params* p, int nq, co
     if (h->raw_d <= 0) return fail(h, GAMMA_HIP_EINVAL, "raw store not initialised");
     if (k <= 0 || nq == 0) return GAMMA_HIP_OK;
     // the store's rows as every reader below takes them: pointer + element type (fp32 rows: the launches they always were)
-    const gh::RowsRef rows{h->raw_byte ? static_cast<const void*>(h->d_raw_b) : h->raw_half ? static_cast<const void*>(h->d_raw_h)
-                                                                                          : static_cast<const void*>(h->d_raw),
-                           h->raw_elem_type()};
+    const gh::RowsRef rows = raw_rows_ref(h);
     GH_CHECK(h, hipSetDevice(h->device));
     const bool l2 = p->metric == GAMMA_HIP_METRIC_L2;
     const float neutral = l2 ? 3.402823466e+38f : -3.402823466e+38f;

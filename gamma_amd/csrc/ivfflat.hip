@@ -8,6 +8,8 @@
 // sort of the coarse assignment by list).  Distances are the exact fvec_L2sqr / fvec_inner_product of the
 // reference (eight AVX lane accumulators: four per thread of the pair, packed fp32), written to the same slab
 // positions as the pair kernel, so everything downstream is unchanged.  d in {16, 32, 64, 96, 128}.
+// Row: the raw store's element type (float; uint16_t = IEEE binary16, uint8_t, int8_t with gamma_hip_set_ivfflat_narrow_rows).  A
+// narrow row is widened -- exactly -- as the pair of threads loads it (row_pair_load, flat_rows_dev.h) and is fp32 from then on.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -15,12 +17,12 @@
 
 #include "device_math.h"
 #include "filter_dev.h"
+#include "flat_rows_dev.h"
 #include "kernels.h"
 
 namespace gh {
 
 namespace {
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 constexpr int FL_QT = 32;   // queries per LDS tile
 constexpr int FL_UT = 1;    // tiles per work unit (4: no gain at 16384 queries, -12 % at 4096: fewer, longer units)
 constexpr int FL_UQ = FL_QT * FL_UT;
@@ -89,11 +91,11 @@ __global__ __launch_bounds__(256) void k_inv_fill(const int* __restrict__ probe,
     if (l >= 0 && l < nlist && list_len[l] > 0) inv[start[l] + atomicAdd(&cur[l], 1)] = i;
 }
 
-template <bool L2, int D>
+template <bool L2, int D, class Row = float>
 __global__ __launch_bounds__(256) void k_ivfflat_lm(const float* __restrict__ x, int P, const int* __restrict__ pair_off,
                                                     const int64_t* __restrict__ list_off,
                                                     const int* __restrict__ list_len, const int64_t* __restrict__ ids,
-                                                    const float* __restrict__ raw, int64_t nraw,
+                                                    const Row* __restrict__ raw, int64_t nraw,
                                                     const int* __restrict__ inv_start, const int* __restrict__ inv_cnt,
                                                     const int* __restrict__ inv, const int* __restrict__ ustart,
                                                     int nlist, int64_t q_stride,
@@ -128,15 +130,7 @@ __global__ __launch_bounds__(256) void k_ivfflat_lm(const float* __restrict__ x,
         bool live = inrow && id >= 0 && vid < nraw;   // id < 0: bit 63, superseded by an Update
         if (need_filter && live) live = is_valid_doc(ftab[0], vid);
         f32x2 yr[D / 4];
-        {
-            const float4* yp = reinterpret_cast<const float4*>(raw + (live ? vid : 0) * D) + half;
-#pragma unroll
-            for (int i = 0; i < D / 8; i++) {
-                const float4 v = yp[2 * i];
-                yr[2 * i] = f32x2{v.x, v.y};
-                yr[2 * i + 1] = f32x2{v.z, v.w};
-            }
-        }
+        row_pair_load<Row, D>(raw + (live ? vid : 0) * D, half, yr);   // (narrow rows widen here, exactly: flat_rows_dev.h)
         for (int t0 = tq0; t0 < tq1; t0 += FL_QT) {
             const int nqt = min(FL_QT, tq1 - t0);
             __syncthreads();   // the previous tile has been consumed
@@ -195,10 +189,12 @@ bool ivfflat_lm_supported(int d) { return d == 16 || d == 32 || d == 64 || d == 
 // scratch: inv [nq * P] ints, then cnt | start | cur [nlist] ints each
 size_t ivfflat_lm_scratch_bytes(int nq, int P, int nlist) { return ((size_t)nq * P + 4 * (size_t)nlist + 1) * sizeof(int); }
 
-void launch_ivfflat_lm(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* probe, const int* pair_off,
-                       const int64_t* list_off, const int* list_len, int nlist, const int64_t* ids, const float* raw,
-                       int64_t nraw, int64_t q_stride, float* out, const FilterDesc* ftab, int need_filter, float min_score,
-                       float max_score, void* scratch) {
+namespace {
+template <class Row>
+void launch_ivfflat_lm_t(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* probe, const int* pair_off,
+                         const int64_t* list_off, const int* list_len, int nlist, const int64_t* ids, const Row* raw,
+                         int64_t nraw, int64_t q_stride, float* out, const FilterDesc* ftab, int need_filter, float min_score,
+                         float max_score, void* scratch) {
     if (nq <= 0 || P <= 0) return;
     int* inv = static_cast<int*>(scratch);
     int* cnt = inv + (size_t)nq * P;
@@ -211,8 +207,8 @@ void launch_ivfflat_lm(hipStream_t s, bool l2, const float* x, int nq, int d, in
     hipLaunchKernelGGL(k_inv_scan, dim3(1), dim3(1024), 0, s, cnt, list_len, nlist, start, cur, ustart);
     hipLaunchKernelGGL(k_inv_fill, dim3((npairs + 255) / 256), dim3(256), 0, s, probe, npairs, nlist, list_len, start, cur, inv);
     const int grid = 256 * 8;   // persistent: every workgroup walks the unit list with stride gridDim.x
-#define GH_FL(LL, DD)                                                                                              \
-    hipLaunchKernelGGL((k_ivfflat_lm<LL, DD>), dim3(grid), dim3(256), 0, s, x, P, pair_off, list_off, list_len, ids, \
+#define GH_FL(LL, DD)                                                                                                   \
+    hipLaunchKernelGGL((k_ivfflat_lm<LL, DD, Row>), dim3(grid), dim3(256), 0, s, x, P, pair_off, list_off, list_len, ids, \
                        raw, nraw, start, cnt, inv, ustart, nlist, q_stride, out, ftab, need_filter, min_score, max_score)
 #define GH_FLD(LL)                    \
     switch (d) {                      \
@@ -225,6 +221,34 @@ void launch_ivfflat_lm(hipStream_t s, bool l2, const float* x, int nq, int d, in
     if (l2) { GH_FLD(true) } else { GH_FLD(false) }
 #undef GH_FLD
 #undef GH_FL
+}
+}  // namespace
+
+void launch_ivfflat_lm(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* probe, const int* pair_off,
+                       const int64_t* list_off, const int* list_len, int nlist, const int64_t* ids, const float* raw,
+                       int64_t nraw, int64_t q_stride, float* out, const FilterDesc* ftab, int need_filter, float min_score,
+                       float max_score, void* scratch) {
+    launch_ivfflat_lm_t<float>(s, l2, x, nq, d, P, probe, pair_off, list_off, list_len, nlist, ids, raw, nraw, q_stride, out, ftab,
+                               need_filter, min_score, max_score, scratch);
+}
+// rows of any element type (gamma_hip_set_ivfflat_narrow_rows); fp32 rows: the launch above, the kernels it always ran
+void launch_ivfflat_lm(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* probe, const int* pair_off,
+                       const int64_t* list_off, const int* list_len, int nlist, const int64_t* ids, const RowsRef& raw,
+                       int64_t nraw, int64_t q_stride, float* out, const FilterDesc* ftab, int need_filter, float min_score,
+                       float max_score, void* scratch) {
+#define GH_FLR(T)                                                                                                              \
+    launch_ivfflat_lm_t<T>(s, l2, x, nq, d, P, probe, pair_off, list_off, list_len, nlist, ids, raw.as<T>(), nraw, q_stride, out, \
+                           ftab, need_filter, min_score, max_score, scratch)
+    switch (raw.et) {
+        case 0:
+            launch_ivfflat_lm(s, l2, x, nq, d, P, probe, pair_off, list_off, list_len, nlist, ids, raw.as<float>(), nraw, q_stride,
+                              out, ftab, need_filter, min_score, max_score, scratch);
+            break;
+        case 1: GH_FLR(uint16_t); break;
+        case 2: GH_FLR(uint8_t); break;
+        default: GH_FLR(int8_t); break;
+    }
+#undef GH_FLR
 }
 
 }  // namespace gh

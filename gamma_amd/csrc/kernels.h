@@ -335,11 +335,19 @@ void launch_small_tail(hipStream_t s, bool l2, const float* slab, int64_t q_stri
 void launch_ivfflat_scan(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* pair_off,
                          const int64_t* pair_base, const int64_t* ids, const float* raw, int64_t nraw, int64_t q_stride,
                          float* out, const FilterDesc* ftab, int need_filter, float min_score, float max_score);
+// ... over rows of any element type (a narrow row widens to fp32 exactly on load); element type 0 forwards to the launch above
+void launch_ivfflat_scan(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* pair_off,
+                         const int64_t* pair_base, const int64_t* ids, const RowsRef& raw, int64_t nraw, int64_t q_stride,
+                         float* out, const FilterDesc* ftab, int need_filter, float min_score, float max_score);
 // IVFFLAT, list-major (ivfflat.hip): one workgroup per list, every query probing it run past the list's rows
 bool ivfflat_lm_supported(int d);
 size_t ivfflat_lm_scratch_bytes(int nq, int P, int nlist);
 void launch_ivfflat_lm(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* probe, const int* pair_off,
                        const int64_t* list_off, const int* list_len, int nlist, const int64_t* ids, const float* raw,
+                       int64_t nraw, int64_t q_stride, float* out, const FilterDesc* ftab, int need_filter, float min_score,
+                       float max_score, void* scratch);
+void launch_ivfflat_lm(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* probe, const int* pair_off,
+                       const int64_t* list_off, const int* list_len, int nlist, const int64_t* ids, const RowsRef& raw,
                        int64_t nraw, int64_t q_stride, float* out, const FilterDesc* ftab, int need_filter, float min_score,
                        float max_score, void* scratch);
 // returns true when the walk of the tied rows went to `side` (the caller then waits for `join` before reading the result)

@@ -125,7 +125,6 @@ __global__ __launch_bounds__(256) void k_pairwise_rowreg(const float* __restrict
 // (512 B per wave and query at d = 128) and that path, not the VALU, is its limit; here a tile of
 // PW_QT queries is read once per workgroup and the sub / fma pairs run as v_pk_add_f32 /
 // v_pk_fma_f32 on two of the eight lane accumulators at a time (IEEE per component: same bits).
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 constexpr int PW_QT = 32;
 // EMIT (flat search with a running bound, gamma_hip_search.cpp flat_search_device_locked): instead of writing
 // the nq x ny distance slab, append (key << 32 | row id) of every distance within the query's current
@@ -153,45 +152,7 @@ __global__ __launch_bounds__(256) void k_pairwise_lds(const float* __restrict__ 
     const int q1 = min(nq, q0 + q_per_block);
     f32x2 yr[D / 4];
     const bool live = row < ny;
-    if constexpr (RowKind<Row>::half) {
-        // narrow rows: both threads of a row ask for the SAME 16 bytes (one request; D * 2 bytes a row, 16-byte aligned) --
-        // the 8 halves 8i .. 8i + 7 -- and each keeps its 4: dwords x, y (even thread) or z, w (odd thread)
-        const uint4* yp = reinterpret_cast<const uint4*>(y + (live ? row : 0) * D);
-#pragma unroll
-        for (int i = 0; i < D / 8; i++) {
-            const uint4 v = yp[i];
-            const uint32_t vx = v.x, vy = v.y, vz = v.z, vw = v.w;   // (value selects on scalars, never an indexed private array)
-            float f[4];
-            row_dword_f<Row>(half ? vz : vx, f);
-            row_dword_f<Row>(half ? vw : vy, f + 2);
-            yr[2 * i] = f32x2{f[0], f[1]};
-            yr[2 * i + 1] = f32x2{f[2], f[3]};
-        }
-    } else if constexpr (RowKind<Row>::byte) {
-        // 16 bytes = the element groups 2i and 2i + 1 (D % 16 == 0: whole pieces, the row 16-byte aligned); the even thread's
-        // elements are dwords x and z, the odd thread's y and w
-        const uint4* yp = reinterpret_cast<const uint4*>(y + (live ? row : 0) * D);
-#pragma unroll
-        for (int i = 0; i < D / 16; i++) {
-            const uint4 v = yp[i];
-            const uint32_t vx = v.x, vy = v.y, vz = v.z, vw = v.w;
-            float f[8];
-            row_dword_f<Row>(half ? vy : vx, f);
-            row_dword_f<Row>(half ? vw : vz, f + 4);
-            yr[4 * i] = f32x2{f[0], f[1]};
-            yr[4 * i + 1] = f32x2{f[2], f[3]};
-            yr[4 * i + 2] = f32x2{f[4], f[5]};
-            yr[4 * i + 3] = f32x2{f[6], f[7]};
-        }
-    } else {
-        const float4* yp = reinterpret_cast<const float4*>(y + (live ? row : 0) * D) + half;
-#pragma unroll
-        for (int i = 0; i < D / 8; i++) {
-            const float4 v = yp[2 * i];
-            yr[2 * i] = f32x2{v.x, v.y};
-            yr[2 * i + 1] = f32x2{v.z, v.w};
-        }
-    }
+    row_pair_load<Row, D>(y + (live ? row : 0) * D, half, yr);   // (flat_rows_dev.h: narrow rows widen here, exactly)
     bool valid = live;
     if (FILTER && live) valid = is_valid_doc(filt, row_base + row);
     for (int qt = q0; qt < q1; qt += PW_QT) {

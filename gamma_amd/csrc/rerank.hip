@@ -530,12 +530,14 @@ void launch_rerank_topk_b(hipStream_t s, bool l2, const float* x, int nq, int d,
 // of fvec_L2sqr / fvec_inner_product (rerank_dev.h).  Entries with bit 63, filtered docs and scores outside the
 // window get the sentinel; one fp32 per entry into the query's slab at the pair's offset.
 // ------------------------------------------------------------------------------------
-template <bool L2>
+// Row: the raw store's element type (float; uint16_t = IEEE binary16, uint8_t, int8_t with gamma_hip_set_ivfflat_narrow_rows):
+// the row access is rerank_dist8, which widens a narrow row exactly and runs the same fma chain (rerank_dev.h), any d.
+template <bool L2, class Row = float>
 __global__ __launch_bounds__(256) void k_ivfflat_scan(const float* __restrict__ x, int d, int P,
                                                       const int* __restrict__ pair_off,
                                                       const int64_t* __restrict__ pair_base,
                                                       const int64_t* __restrict__ ids,
-                                                      const float* __restrict__ raw, int64_t nraw, int64_t q_stride,
+                                                      const Row* __restrict__ raw, int64_t nraw, int64_t q_stride,
                                                       float* __restrict__ out, const FilterDesc* __restrict__ ftab,
                                                       int need_filter, float min_score, float max_score) {
     const int q = blockIdx.x / P, p = blockIdx.x - q * P;
@@ -570,6 +572,44 @@ void launch_ivfflat_scan(hipStream_t s, bool l2, const float* x, int nq, int d, 
     else
         hipLaunchKernelGGL((k_ivfflat_scan<false>), grid, dim3(256), 0, s, x, d, P, pair_off, pair_base, ids, raw, nraw,
                            q_stride, out, ftab, need_filter, min_score, max_score);
+}
+namespace {
+template <class Row>
+void launch_ivfflat_scan_t(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* pair_off,
+                           const int64_t* pair_base, const int64_t* ids, const Row* raw, int64_t nraw, int64_t q_stride,
+                           float* out, const FilterDesc* ftab, int need_filter, float min_score, float max_score) {
+    if (nq <= 0 || P <= 0) return;
+    const dim3 grid((unsigned)((int64_t)nq * P));
+    if (l2)
+        hipLaunchKernelGGL((k_ivfflat_scan<true, Row>), grid, dim3(256), 0, s, x, d, P, pair_off, pair_base, ids, raw, nraw,
+                           q_stride, out, ftab, need_filter, min_score, max_score);
+    else
+        hipLaunchKernelGGL((k_ivfflat_scan<false, Row>), grid, dim3(256), 0, s, x, d, P, pair_off, pair_base, ids, raw, nraw,
+                           q_stride, out, ftab, need_filter, min_score, max_score);
+}
+}  // namespace
+// rows of any element type (gamma_hip_set_ivfflat_narrow_rows); fp32 rows: the launch above, the kernels it always ran
+void launch_ivfflat_scan(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* pair_off,
+                         const int64_t* pair_base, const int64_t* ids, const RowsRef& raw, int64_t nraw, int64_t q_stride,
+                         float* out, const FilterDesc* ftab, int need_filter, float min_score, float max_score) {
+    switch (raw.et) {
+        case 0:
+            launch_ivfflat_scan(s, l2, x, nq, d, P, pair_off, pair_base, ids, raw.as<float>(), nraw, q_stride, out, ftab,
+                                need_filter, min_score, max_score);
+            break;
+        case 1:
+            launch_ivfflat_scan_t(s, l2, x, nq, d, P, pair_off, pair_base, ids, raw.as<uint16_t>(), nraw, q_stride, out, ftab,
+                                  need_filter, min_score, max_score);
+            break;
+        case 2:
+            launch_ivfflat_scan_t(s, l2, x, nq, d, P, pair_off, pair_base, ids, raw.as<uint8_t>(), nraw, q_stride, out, ftab,
+                                  need_filter, min_score, max_score);
+            break;
+        default:
+            launch_ivfflat_scan_t(s, l2, x, nq, d, P, pair_off, pair_base, ids, raw.as<int8_t>(), nraw, q_stride, out, ftab,
+                                  need_filter, min_score, max_score);
+            break;
+    }
 }
 
 // final outputs from a top-k selection over re-ranked (or flat) candidates:

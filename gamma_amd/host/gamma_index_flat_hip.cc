@@ -36,20 +36,7 @@ int RegisterHIPFlatRows(HIPFlatRowsFn fn) {
 HIPFlatRowsFn FindHIPFlatRows() { return FlatRows(); }
 
 int GammaFLATHIPIndex::ParseRawDtype(const std::string &model_parameters, int *et) {
-  *et = 0;
-  if (model_parameters == "") return 0;
-  utils::JsonParser jp;
-  if (jp.Parse(model_parameters.c_str())) return -1;
-  std::string rdt;
-  if (jp.GetString("raw_dtype", rdt)) return 0;
-  static const char *const names[4] = {"float32", "float16", "uint8", "int8"};
-  for (int i = 0; i < 4; i++)
-    if (!strcasecmp(names[i], rdt.c_str())) {
-      *et = i;
-      return 0;
-    }
-  FLOG("invalid raw_dtype = %s", rdt.c_str());
-  return -1;
+  return HIPParseRawDtype("HIPFLAT", model_parameters, et);   // shared with HIPIVFFLAT (gamma_index_ivfpq_hip.cc)
 }
 
 bool GammaFLATHIPIndex::RowsStorable(const char *what, const float *x, int64_t nrows) {

@@ -1,6 +1,7 @@
 // GammaIVFPQHIPIndex -- see gamma_index_ivfpq_hip.h.  Host side only: parameter handling,
 // training driver, bookkeeping; every distance / scan / selection runs in libgamma_hip.so.
 #include "gamma_index_ivfpq_hip.h"
+#include "gamma_index_flat_hip.h"   // FindHIPFlatRows (HIPIVFFLAT over a narrow store: brute force)
 
 #include "iwpq_io.h"
 
@@ -433,6 +434,23 @@ int GammaIVFPQHIPIndex::TrainingSet(std::vector<float> &xt, size_t &num) {
   xt.resize(num * d_);
   for (size_t i = 0; i < num; i++) memcpy(&xt[i * d_], sv.Get((int)i), sizeof(float) * d_);
   return 0;
+}
+
+int HIPParseRawDtype(const char *model, const std::string &model_parameters, int *et) {
+  *et = 0;
+  if (model_parameters == "") return 0;
+  utils::JsonParser jp;
+  if (jp.Parse(model_parameters.c_str())) return -1;
+  std::string rdt;
+  if (jp.GetString("raw_dtype", rdt)) return 0;
+  static const char *const names[4] = {"float32", "float16", "uint8", "int8"};
+  for (int i = 0; i < 4; i++)
+    if (!strcasecmp(names[i], rdt.c_str())) {
+      *et = i;
+      return 0;
+    }
+  fprintf(stderr, "[%s] invalid raw_dtype = %s\n", model, rdt.c_str());
+  return -1;
 }
 
 bool HIPRowsStorableI8(const HIPRawI8Ops *ops, bool is_signed, int d, const char *model, const char *what, const float *x,
@@ -879,6 +897,22 @@ int GammaIVFPQHIPIndex::Load(const std::string &dir) {
 // ------------------------------------------------------------------------------------------------------------
 REGISTER_MODEL(HIPIVFFLAT, GammaIVFFlatHIPIndex);
 
+namespace {
+HIPIVFFlatRowsFn &IVFFlatRows() {
+  static HIPIVFFlatRowsFn fn = nullptr;
+  return fn;
+}
+}  // namespace
+int RegisterHIPIVFFlatRows(HIPIVFFlatRowsFn fn) {
+  IVFFlatRows() = fn;
+  return 0;
+}
+HIPIVFFlatRowsFn FindHIPIVFFlatRows() { return IVFFlatRows(); }
+
+int GammaIVFFlatHIPIndex::ParseRawDtype(const std::string &model_parameters, int *et) {
+  return HIPParseRawDtype("HIPIVFFLAT", model_parameters, et);
+}
+
 int GammaIVFFlatHIPIndex::Init(const std::string &model_parameters, int indexing_size) {
   indexing_size_ = indexing_size;
   model_param_ = new HIPIVFPQModelParams();   // ncentroids / nprobe / metric_type / bucket sizes / device_filters
@@ -906,6 +940,18 @@ int GammaIVFFlatHIPIndex::Init(const std::string &model_parameters, int indexing
   if (!jp.GetInt("exact_ties", v)) pa.exact_ties = v != 0;
   if (!jp.GetInt("bucket_init_size", v) && v > 0) pa.bucket_init_size = v;
   if (!jp.GetInt("bucket_max_size", v) && v > 0) pa.bucket_max_size = v;
+  int et = 0;
+  if (ParseRawDtype(model_parameters, &et)) return -1;
+  // a narrow store needs its initialiser and the handle's switch; a build without one of them rejects the value
+  const HIPIVFFlatRowsFn ivfflat_rows = et ? FindHIPIVFFlatRows() : nullptr;
+  const HIPRawInitFn init_f16 = et == 1 ? FindHIPRawInitF16() : nullptr;
+  raw_i8_ops_ = et >= 2 ? FindHIPRawI8() : nullptr;
+  if (et && (!ivfflat_rows || (et == 1 ? !init_f16 : !raw_i8_ops_))) {
+    HLOG("HIPIVFFLAT: raw_dtype: this build of the plugin has no IVFFLAT search over float16 / uint8 / int8 rows");
+    return -1;
+  }
+  raw_f16_ = et == 1;
+  raw_i8_ = et >= 2 ? et - 1 : 0;
   if (!vector_) {
     HLOG("vector_ must be set before Init");
     return -1;
@@ -921,7 +967,14 @@ int GammaIVFFlatHIPIndex::Init(const std::string &model_parameters, int indexing
   members_.assign(1, h_);   // one GPU (the sharded group serves HIPIVFPQ)
   rc = gamma_hip_ivfflat_init(h_, d_, nlist_, metric_type_ == DistanceComputeType::L2 ? GAMMA_HIP_METRIC_L2 : GAMMA_HIP_METRIC_IP,
                               pa.bucket_init_size, pa.bucket_max_size);
-  if (!rc) rc = gamma_hip_raw_init(h_, d_);
+  if (!rc) rc = !et ? gamma_hip_raw_init(h_, d_) : et == 1 ? init_f16(h_, d_) : raw_i8_ops_->init(h_, d_, et == 3);
+  if (!rc && et) rc = ivfflat_rows(h_, 1);
+  if (!rc && et) {
+    // brute_force_search and the search of an untrained model go to the flat search: its own switch, where the build has it
+    const HIPFlatRowsFn flat_rows = FindHIPFlatRows();
+    narrow_brute_ = flat_rows != nullptr;
+    if (flat_rows) rc = flat_rows(h_, 1);
+  }
   if (!rc) rc = gamma_hip_set_exact_ties(h_, pa.exact_ties ? 1 : 0);
   if (rc) {
     HLOG("device init failed: %s (%s)", gamma_hip_strerror(rc), gamma_hip_last_error(h_));
@@ -992,6 +1045,11 @@ int GammaIVFFlatHIPIndex::Search(RetrievalContext *retrieval_context, int n, con
   int rc;
   if ((cond && cond->brute_force_search) || !is_trained_) {
     // (the reference's IVFFLAT has no brute-force branch; an untrained model would crash there.  Same service as HIPIVFPQ.)
+    if (!narrow_brute_) {
+      HLOG("HIPIVFFLAT: brute_force_search (and the search of an untrained model) over raw_dtype = %s needs flat search over narrow "
+           "rows, which this build of the plugin does not have", raw_f16_ ? "float16" : raw_i8_ == 2 ? "int8" : "uint8");
+      return -1;
+    }
     if (EnsureRaw((int64_t)vector_->MetaInfo()->Size())) return -1;
     rc = gamma_hip_flat_search(h_, &p, n, xq, k, distances, ids);
   } else {
@@ -1054,6 +1112,21 @@ int GammaIVFFlatHIPIndex::Load(const std::string &dir) {
   int indexed = 0;
   if (ReadIvFl(path, &f, &indexed)) return -1;
   if (f.d != d_ || (int)f.nlist != nlist_ || indexed < 0 || indexed > (int)vector_->MetaInfo()->Size()) return -1;
+  if (raw_i8_) {
+    // a byte model: a pass over the rows it is about to mirror with the acceptance predicate first, so that a refused row
+    // leaves the model as it was (untrained, no lists)
+    std::lock_guard<std::mutex> g(raw_mu_);
+    for (int64_t i0 = raw_uploaded_; i0 < indexed; i0 += 65536) {
+      const int64_t nb = std::min<int64_t>(65536, indexed - i0);
+      std::vector<int64_t> vids(nb);
+      for (int64_t i = 0; i < nb; i++) vids[i] = i0 + i;
+      ScopeVectors sv;
+      if (vector_->Gets(vids, sv)) return -1;
+      std::vector<float> buf((size_t)nb * d_);
+      for (int64_t i = 0; i < nb; i++) memcpy(&buf[(size_t)i * d_], sv.Get((int)i), sizeof(float) * d_);
+      if (!RowsStorable("load", buf.data(), nb)) return -1;
+    }
+  }
   if (SetTrainedCoarse(f.coarse.data())) return -1;
   if (UploadEngineBitmap()) return -1;
   if (SyncVid2DocID((int64_t)vector_->MetaInfo()->Size())) return -1;

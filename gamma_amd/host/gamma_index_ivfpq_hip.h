@@ -87,6 +87,17 @@ const HIPRawI8Ops *FindHIPRawI8();
 bool HIPRowsStorableI8(const HIPRawI8Ops *ops, bool is_signed, int d, const char *model, const char *what, const float *x,
                        int64_t nrows);
 
+// The "raw_dtype" key of the HIPFLAT and HIPIVFFLAT models' parameters: *et = 0 float32 (also: no key), 1 float16, 2 uint8, 3 int8,
+// case-insensitive; any other string: one log line "[model] invalid raw_dtype = ..." and -1.
+int HIPParseRawDtype(const char *model, const std::string &model_parameters, int *et);
+
+// HIPIVFFLAT's "raw_dtype": "float16" | "uint8" | "int8": IVFFLAT search over narrow rows is a switch of the handle
+// (gamma_hip_set_ivfflat_narrow_rows), registered the same way by gamma_index_ivfflat_rows_hip.cc, the only host file that names
+// it.  Without that file HIPIVFFLAT::Init rejects the three values.
+typedef int (*HIPIVFFlatRowsFn)(gamma_hip_index *h, int on);
+int RegisterHIPIVFFlatRows(HIPIVFFlatRowsFn fn);
+HIPIVFFlatRowsFn FindHIPIVFFlatRows();
+
 // "opq": the rotation's entries of the C ABI (gamma_hip_opq_train / _set / _get / _apply) reach the model through this table,
 // registered at static-initialisation time by gamma_index_ivfpq_opq_hip.cc -- the only host file that names them.  A build of
 // the plugin without that file (against a C ABI without those entries) has no table, and HIPIVFPQ::Init rejects "opq".
@@ -210,6 +221,10 @@ class GammaIVFPQHIPIndex : public RetrievalModel {
 // come from the HBM mirror of the vector store the IVFPQ plugin already keeps for its re-rank, so Add / Update /
 // Delete and the raw mirror are inherited; Init, Indexing (coarse k-means only), Search, Dump / Load ("IvFl" file,
 // iwpq_io.h) differ.
+// HIP only: "raw_dtype": "float32" (default) | "float16" | "uint8" | "int8" -- the device's rows are 2 bytes / 1 byte per element,
+// widened exactly as the scan loads them; the byte stores take a row only if it converts exactly (HIPIVFPQ's rule, inherited).
+// Unlike HIPIVFPQ the model serves brute_force_search and the search of an untrained model over a narrow store (flat search
+// over narrow rows, gamma_index_flat_hip.h) where the build has that switch.
 class HIPIVFFlatRetrievalParameters : public RetrievalParameters {
  public:
   HIPIVFFlatRetrievalParameters() : RetrievalParameters(), parallel_on_queries_(true), nprobe_(-1), exact_ties_(0) {}
@@ -239,6 +254,11 @@ class GammaIVFFlatHIPIndex : public GammaIVFPQHIPIndex {
   int Dump(const std::string &dir) override;
   int Load(const std::string &dir) override;
   int SetTrainedCoarse(const float *coarse_centroids);
+  // the "raw_dtype" key of the model's parameters (HIPParseRawDtype)
+  static int ParseRawDtype(const std::string &model_parameters, int *et);
+
+ private:
+  bool narrow_brute_ = true;   // false: a narrow store in a build without flat search over narrow rows -- brute force is refused
 };
 
 }  // namespace tig_gamma

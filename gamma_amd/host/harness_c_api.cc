@@ -417,6 +417,12 @@ void gh_parse_flat_raw_dtype(const char *str, int *out) {
   out[0] = GammaFLATHIPIndex::ParseRawDtype(str, &et);
   out[1] = et;
 }
+// ... and of the HIPIVFFLAT model's
+void gh_parse_ivfflat_raw_dtype(const char *str, int *out) {
+  int et = 0;
+  out[0] = GammaIVFFlatHIPIndex::ParseRawDtype(str, &et);
+  out[1] = et;
+}
 // HIPIVFPQRetrievalParameters via Parse on an un-Init'ed model: out = {rc, metric, recall_num, nprobe}
 void gh_parse_ivfpq_retrieval_params(const char *str, int *out) {
   GammaIVFPQHIPIndex m;

@@ -56,6 +56,7 @@ HOST_SYMBOLS = {
     "gh_parse_ivfpq_retrieval_params": (None, [C.c_char_p, C.POINTER(C.c_int)]),
     "gh_parse_ivfpq_raw_dtype": (None, [C.c_char_p, C.POINTER(C.c_int)]),
     "gh_parse_flat_raw_dtype": (None, [C.c_char_p, C.POINTER(C.c_int)]),
+    "gh_parse_ivfflat_raw_dtype": (None, [C.c_char_p, C.POINTER(C.c_int)]),
     "gh_model_registered": (C.c_int, [C.c_char_p]),
     "gh_iwpq_write": (C.c_int, [C.c_char_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, f32p, C.c_int, f32p,
                                 i64p, _lib.u8p, i64p]),
@@ -124,6 +125,13 @@ def parse_flat_raw_dtype(s):
     """(rc, "float32", "float16", "uint8" or "int8") for the HIPFLAT model parameters s"""
     out = (C.c_int * 2)()
     load_host().gh_parse_flat_raw_dtype(s.encode(), out)
+    return int(out[0]), ("float32", "float16", "uint8", "int8")[out[1]]
+
+
+def parse_ivfflat_raw_dtype(s):
+    """(rc, "float32", "float16", "uint8" or "int8") for the HIPIVFFLAT model parameters s"""
+    out = (C.c_int * 2)()
+    load_host().gh_parse_ivfflat_raw_dtype(s.encode(), out)
     return int(out[0]), ("float32", "float16", "uint8", "int8")[out[1]]
 
 

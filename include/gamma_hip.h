@@ -185,9 +185,19 @@ int gamma_hip_set_small_path(gamma_hip_index* h, int on);
  * GAMMA_HIP_EUNSUPPORTED, as every other reader of fp32 rows does; 1 = the three serve it: every row is widened to fp32
  * -- exactly -- as it is loaded and every distance is fvec_L2sqr / fvec_inner_product of the fp32 query and the widened
  * row, so distances and labels are byte-identical to those of an fp32 store that holds the widened rows (DESIGN.md
- * section 15).  Nothing else changes: IVFFLAT search, the shard / merge / export entries, gamma_hip_raw_put / _raw_drop
+ * section 15).  Nothing else changes: IVFFLAT search (a switch of its own, below), the shard / merge / export entries, gamma_hip_raw_put / _raw_drop
  * and a sparse store keep refusing a narrow store, and an fp32 store is served as before whatever the switch says. */
 int gamma_hip_set_flat_narrow_rows(gamma_hip_index* h, int on);
+/* IVFFLAT search over a narrow raw store; a switch of its own, independent of the one above.  on: 0 (default) =
+ * gamma_hip_ivfflat_search and _ivfflat_search_device refuse a float16 / uint8 / int8 store with GAMMA_HIP_EUNSUPPORTED,
+ * as before; 1 = both serve it.  The reference's lists hold the vectors as fp32 and GammaIVFFlatScanner1::scan_codes
+ * (index/impl/gamma_index_ivfflat.h:52-75) calls faiss::fvec_L2sqr / fvec_inner_product on each; here a list holds vids and
+ * the rows come from the raw store: a narrow row is widened to fp32 -- exactly -- as it is loaded and is the scanner's yj from
+ * then on, so distances and labels are byte-identical to those of an fp32 store that holds the widened rows, exact ties
+ * included.  Nothing else changes: the shard / merge / export entries, gamma_hip_raw_put /
+ * _raw_drop, the combining queue and a sparse store keep refusing a narrow store, and an fp32 store is served as before
+ * whatever the switch says. */
+int gamma_hip_set_ivfflat_narrow_rows(gamma_hip_index* h, int on);
 /* out3 = {coarse rows redone, queries whose recall_num cut went through a tie, queries replayed} since creation
  * or the last reset; meaningful with exact ties on */
 int gamma_hip_tie_stats(gamma_hip_index* h, int64_t* out3, int reset);
