@@ -66,6 +66,12 @@ SYMBOLS = {
     "gamma_hip_raw_init_i8": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "gamma_hip_raw_elem_type": (C.c_int, [C.c_void_p]),
     "gamma_hip_raw_i8_check": (C.c_int, [f32p, C.c_int64, C.c_int, i64p]),
+    "gamma_hip_raw_init_sq8": (C.c_int, [C.c_void_p, C.c_int]),
+    "gamma_hip_raw_sq8_set_ranges": (C.c_int, [C.c_void_p, f32p, f32p]),
+    "gamma_hip_raw_sq8_get_ranges": (C.c_int, [C.c_void_p, f32p, f32p]),
+    "gamma_hip_raw_sq8_train": (C.c_int, [C.c_void_p, C.c_int64, f32p]),
+    "gamma_hip_raw_sq8_check": (C.c_int, [f32p, C.c_int64, i64p]),
+    "gamma_hip_raw_sq8_params": (C.c_int, [C.c_int, f32p, f32p, f32p, f32p]),
     "gamma_hip_raw_append": (C.c_int, [C.c_void_p, C.c_int64, f32p]),
     "gamma_hip_raw_update": (C.c_int, [C.c_void_p, C.c_int64, f32p]),
     "gamma_hip_ivfpq_arena_stats": (C.c_int, [C.c_void_p, i64p]),

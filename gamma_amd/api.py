@@ -137,16 +137,38 @@ class GammaHip:
             # rows of one byte per element: the writers store a value only if it converts exactly, and refuse the call otherwise
             # (include/gamma_hip.h, gamma_hip_raw_init_i8)
             self._ck(self.L.gamma_hip_raw_init_i8(self.h, d, 1 if dtype == "int8" else 0), "raw_init_i8")
+        elif dtype == "sq8":
+            # rows of one scalar-quantised byte per element for float data: lossy, decoded in the re-rank; the ranges come from
+            # raw_sq8_set_ranges / raw_sq8_train before the first row (include/gamma_hip.h, gamma_hip_raw_init_sq8)
+            self._ck(self.L.gamma_hip_raw_init_sq8(self.h, d), "raw_init_sq8")
         else:
-            raise ValueError("raw_init: dtype must be 'float32', 'float16', 'uint8' or 'int8', not %r" % (dtype,))
+            raise ValueError("raw_init: dtype must be 'float32', 'float16', 'uint8', 'int8' or 'sq8', not %r" % (dtype,))
         self.raw_d = d
 
+    def raw_sq8_set_ranges(self, vmin, vmax):
+        """the per-dimension ranges of an sq8 store; only while it holds no row"""
+        vmin, vmax = _f32(vmin).reshape(-1), _f32(vmax).reshape(-1)
+        if len(vmin) != self.raw_d or len(vmax) != self.raw_d:
+            raise ValueError("raw_sq8_set_ranges: vmin and vmax need %d values each" % self.raw_d)
+        self._ck(self.L.gamma_hip_raw_sq8_set_ranges(self.h, _p(vmin, _lib.f32p), _p(vmax, _lib.f32p)), "raw_sq8_set_ranges")
+
+    def raw_sq8_get_ranges(self):
+        """(vmin, vmax) of an sq8 store"""
+        vmin, vmax = np.empty(self.raw_d, dtype=np.float32), np.empty(self.raw_d, dtype=np.float32)
+        self._ck(self.L.gamma_hip_raw_sq8_get_ranges(self.h, _p(vmin, _lib.f32p), _p(vmax, _lib.f32p)), "raw_sq8_get_ranges")
+        return vmin, vmax
+
+    def raw_sq8_train(self, vecs):
+        """the ranges of an sq8 store = per-dimension minimum and maximum of these rows (reduced on the device)"""
+        vecs = _f32(vecs)
+        self._ck(self.L.gamma_hip_raw_sq8_train(self.h, vecs.shape[0], _p(vecs, _lib.f32p)), "raw_sq8_train")
+
     def raw_elem_bytes(self):
-        """bytes per element of the raw store: 4, 2 (float16 rows), 1 (uint8 / int8 rows) or 0 before raw_init"""
+        """bytes per element of the raw store: 4, 2 (float16 rows), 1 (uint8 / int8 / sq8 rows) or 0 before raw_init"""
         return int(self.L.gamma_hip_raw_elem_bytes(self.h))
 
     def raw_elem_type(self):
-        """element type of the raw store: 0 float32, 1 float16, 2 uint8, 3 int8"""
+        """element type of the raw store: 0 float32, 1 float16, 2 uint8, 3 int8, 4 sq8"""
         return int(self.L.gamma_hip_raw_elem_type(self.h))
 
     def raw_append(self, vecs):

@@ -118,6 +118,7 @@ int gamma_hip_destroy(gamma_hip_index* h) {
         h->d_raw = nullptr;
         h->d_raw_h = nullptr;
         h->d_raw_b = nullptr;
+        h->d_raw_q = nullptr;
     }
     // (release() of a range that was never reserved does nothing; an arena that left virtual memory management after a
     //  failed repack read-back still owns its reserved ranges)
@@ -134,7 +135,7 @@ int gamma_hip_destroy(gamma_hip_index* h) {
         h->d_sums = nullptr;
     }
     if (h->d_raw_slot) (void)hipFree(h->d_raw_slot);
-    void* ptrs[] = {h->d_list_rank, h->d_raw, h->d_raw_h, h->d_raw_b, h->d_bitmap, h->d_cc, h->d_cc_norms, h->d_pqc, h->d_T2, h->d_codes,
+    void* ptrs[] = {h->d_list_rank, h->d_raw, h->d_raw_h, h->d_raw_b, h->d_raw_q, h->d_sq8_tab, h->d_bitmap, h->d_cc, h->d_cc_norms, h->d_pqc, h->d_T2, h->d_codes,
                     h->d_ids, h->d_list_mask, h->d_scan_codes, h->d_tie_stats, h->d_v2d, h->d_sums, h->d_t2max, h->d_bound_stat,
                     h->d_bin_cc, h->d_bin_stats, h->d_cc_img, h->d_cbf_stat, h->d_opq};
     for (void* p : ptrs)
@@ -331,6 +332,7 @@ int64_t gamma_hip_total_mem_bytes(gamma_hip_index* h) {
     std::lock_guard<std::mutex> g(h->mu);
     int64_t b = 0;
     b += h->raw_cap * h->raw_d * (int64_t)h->raw_esz() + h->raw_slot_cap * (int64_t)sizeof(int32_t);
+    if (h->d_sq8_tab) b += (int64_t)h->raw_d * 4 * (int64_t)sizeof(float);   // sq8 store: the decode and the encode table
     b += (int64_t)h->bitmap_cap_bytes;
     for (auto& kv : h->fields) b += kv.second.cap * (int64_t)field_elem_size(kv.second.dtype);
     for (auto& kv : h->terms) b += kv.second.cap_docs * 8 + kv.second.cap_tok * 4;

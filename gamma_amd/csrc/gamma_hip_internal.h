@@ -202,9 +202,16 @@ struct gamma_hip_index {
     // reason; rows of raw_d bytes.  The writers take fp32 that converts exactly, checked on the host (gamma_hip_raw_i8_check).
     int raw_byte = 0;
     uint8_t* d_raw_b = nullptr;
-    size_t raw_esz() const { return raw_byte ? 1 : raw_half ? sizeof(uint16_t) : sizeof(float); }
-    bool has_raw_rows() const { return d_raw != nullptr || d_raw_h != nullptr || d_raw_b != nullptr; }
-    int raw_elem_type() const { return raw_byte ? 1 + raw_byte : raw_half ? 1 : 0; }   // 0 fp32, 1 float16, 2 uint8, 3 int8
+    // gamma_hip_raw_init_sq8: rows of one scalar-quantised byte per element behind a fourth pointer, again for that reason; rows of
+    // raw_d bytes, the byte store's growth machinery.  sq8_vmin / sq8_vmax: the ranges (empty until set or trained); d_sq8_tab:
+    // 2 * raw_d float2 -- the readers' decode table {step[j], vmin[j]} and behind it the writers' encode table {inv[j], vmin[j]}.
+    bool raw_sq8 = false;
+    uint8_t* d_raw_q = nullptr;
+    std::vector<float> sq8_vmin, sq8_vmax, sq8_step;
+    float* d_sq8_tab = nullptr;
+    size_t raw_esz() const { return raw_byte || raw_sq8 ? 1 : raw_half ? sizeof(uint16_t) : sizeof(float); }
+    bool has_raw_rows() const { return d_raw != nullptr || d_raw_h != nullptr || d_raw_b != nullptr || d_raw_q != nullptr; }
+    int raw_elem_type() const { return raw_sq8 ? 4 : raw_byte ? 1 + raw_byte : raw_half ? 1 : 0; }   // 0 fp32, 1 float16, 2 uint8, 3 int8, 4 sq8
     // raw vectors SHARDED with their lists (gamma_hip_raw_put, round 6): the store holds the rows of the vectors in this shard's
     // lists only, in arrival order; raw_slot[vid] = row (-1: held by another shard).  Such a handle re-ranks nothing by itself --
     // has_rank searches, flat search and raw_gets refuse -- it serves _shard_exact / _shard_export_exact.

@@ -323,6 +323,11 @@ static int byte_refuse(H* h, const char* what) {
     h->err = std::string("8-bit raw store (gamma_hip_raw_init_i8): ") + what + " reads fp32 rows and is not supported";
     return GAMMA_HIP_EUNSUPPORTED;
 }
+// and for a store of scalar-quantised rows (gamma_hip_raw_init_sq8): only the IVFPQ re-rank and its tie replay decode them
+static int sq8_refuse(H* h, const char* what) {
+    h->err = std::string("sq8 raw store (gamma_hip_raw_init_sq8): ") + what + " reads fp32 rows and is not supported";
+    return GAMMA_HIP_EUNSUPPORTED;
+}
 // (every entry point that refuses the one refuses the other: the shard, merge and export entries)
 #define GH_NO_PQ4(h, what)                                                \
     do {                                                                  \
@@ -886,6 +891,8 @@ int ivfpq_stage_b(H* h, const gamma_hip_search_params* p, int nq, const float* d
         a.raw_h = h->d_raw_h;   // (all but one of the three are null)
         a.raw_b = h->d_raw_b;
         a.raw_b_signed = h->raw_byte == 2;
+        a.raw_q = h->d_raw_q;
+        a.sq8_tab = h->d_sq8_tab;
         a.nraw = h->nraw;
         a.R = R;
         a.k = k;
@@ -915,7 +922,10 @@ int ivfpq_stage_b(H* h, const gamma_hip_search_params* p, int nq, const float* d
         if (h->raw_sparse) return fail(h, GAMMA_HIP_EUNSUPPORTED, "has_rank on a handle that holds its shard's raw rows only: the exact distances travel with the candidates (gamma_hip_ivfpq_shard_exact / _merge_rerank_exact)");
         if (R <= 1024 && (nq >= 256 || ties)) {
             // one fused kernel: exact distances + top-k + output
-            if (h->d_raw_b)
+            if (h->d_raw_q)
+                gh::launch_rerank_topk_sq8(s, l2, d_x, nq, h->d, h->d_raw_q, h->d_sq8_tab, h->nraw, cand_ids, R, k, p->min_score,
+                                           p->max_score, neutral, d_distances, d_labels, qperm, ties ? &tf : nullptr);
+            else if (h->d_raw_b)
                 gh::launch_rerank_topk_b(s, l2, d_x, nq, h->d, h->d_raw_b, h->raw_byte == 2, h->nraw, cand_ids, R, k, p->min_score,
                                          p->max_score, neutral, d_distances, d_labels, qperm, ties ? &tf : nullptr);
             else if (h->d_raw_h)
@@ -931,7 +941,10 @@ int ivfpq_stage_b(H* h, const gamma_hip_search_params* p, int nq, const float* d
         GH_CHECK(h, h->w_exact.ensure((size_t)nq * R * sizeof(float)));
         GH_CHECK(h, h->w_selv.ensure((size_t)nq * k * sizeof(float)));
         GH_CHECK(h, h->w_selp.ensure((size_t)nq * k * sizeof(int)));
-        if (h->d_raw_b)
+        if (h->d_raw_q)
+            gh::launch_rerank_dist_sq8(s, l2, d_x, nq, h->d, h->d_raw_q, h->d_sq8_tab, h->nraw, cand_ids, R, p->min_score,
+                                       p->max_score, h->w_exact.as<float>());
+        else if (h->d_raw_b)
             gh::launch_rerank_dist_b(s, l2, d_x, nq, h->d, h->d_raw_b, h->raw_byte == 2, h->nraw, cand_ids, R, p->min_score,
                                      p->max_score, h->w_exact.as<float>());
         else if (h->d_raw_h)
@@ -979,7 +992,7 @@ bool ivfpq_small_ok(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, i
            (int64_t)p->nprobe * std::max(1, h->max_list_len) <= (1 << 22) &&
            // long lists: beyond ~5e7 codes per call the regular chain's bound filter wins (full-size C4, 390 k codes per
            // query: 64 queries 0.46 ms against 1.04, 256 queries 1.63 against 1.33)
-           // (a float16 or byte raw store leaves d_raw null: its has_rank calls take the regular chain, whose stage B reads the narrow rows)
+           // (a float16, byte or sq8 raw store leaves d_raw null: its has_rank calls take the regular chain, whose stage B reads the narrow rows)
            (int64_t)nq * p->nprobe * (h->ntotal / std::max(1, h->nlist)) <= 48000000LL && (!p->has_rank || (h->d_raw && h->raw_d == h->d && !h->raw_sparse));
 }
 
@@ -1440,6 +1453,7 @@ int ivfflat_search_device_locked(H* h, const gamma_hip_search_params* p, int nq,
     // (a narrow store is served only after gamma_hip_set_ivfflat_narrow_rows: the refusal is what every caller had before)
     if (h->raw_half && !h->ivfflat_narrow_rows) return half_refuse(h, "IVFFLAT search");
     if (h->raw_byte && !h->ivfflat_narrow_rows) return byte_refuse(h, "IVFFLAT search");
+    if (h->raw_sq8) return sq8_refuse(h, "IVFFLAT search");   // (whatever the switch says: the scan decodes nothing)
     GH_TRY(check_params(h, p, nq, k));
     gamma_hip_search_params pp;
     GH_TRY(resolve_ties(h, p, &pp, p->nprobe <= gh::tie_replay_max_probes(), "exact_ties = 1 with nprobe > 1024"));
@@ -1557,6 +1571,7 @@ int flat_search_device_locked(H* h, const gamma_hip_search_params* p, int nq, co
     // (a narrow store is served only after gamma_hip_set_flat_narrow_rows: the refusal is what every caller had before)
     if (h->raw_half && !h->flat_narrow_rows) return half_refuse(h, "flat search");
     if (h->raw_byte && !h->flat_narrow_rows) return byte_refuse(h, "flat search");
+    if (h->raw_sq8) return sq8_refuse(h, "flat search");   // (whatever the switch says)
     GH_TRY(check_params(h, p, nq, k));
     gamma_hip_search_params pp;   // (the chunked paths run for k + 1 results: k = 4096, the ABI's largest, is beyond the mode)
     GH_TRY(resolve_ties(h, p, &pp, k + 1 <= gh::tie_replay_max_k() && h->nraw < ((int64_t)1 << 31),
@@ -2283,6 +2298,7 @@ static int merge_rerank_impl(gamma_hip_index* h, const gamma_hip_search_params* 
     GH_NO_PQ4(h, "gamma_hip_ivfpq_merge_rerank(_exact)");
     if (h->raw_half && p && p->has_rank && !d_all_exact) return half_refuse(h, "gamma_hip_ivfpq_merge_rerank without travelled distances");
     if (h->raw_byte && p && p->has_rank && !d_all_exact) return byte_refuse(h, "gamma_hip_ivfpq_merge_rerank without travelled distances");
+    if (h->raw_sq8 && p && p->has_rank && !d_all_exact) return sq8_refuse(h, "gamma_hip_ivfpq_merge_rerank without travelled distances");
     GH_TRY(replay_join(h));
     GH_TRY(ivfpq_check(h, p, nq, k));
     if (nshards <= 0 || q0 < 0 || nq_local < 0 || q0 + nq_local > nq) return fail(h, GAMMA_HIP_EINVAL, "bad shard/query range");
@@ -2374,6 +2390,7 @@ int gamma_hip_ivfpq_shard_exact(gamma_hip_index* h, const gamma_hip_search_param
     GH_NO_PQ4(h, "gamma_hip_ivfpq_shard_exact");
     if (h->raw_half) return half_refuse(h, "gamma_hip_ivfpq_shard_exact");
     if (h->raw_byte) return byte_refuse(h, "gamma_hip_ivfpq_shard_exact");
+    if (h->raw_sq8) return sq8_refuse(h, "gamma_hip_ivfpq_shard_exact");
     GH_TRY(replay_join(h));
     if (!h->d_raw || h->raw_d != h->d) return fail(h, GAMMA_HIP_EINVAL, "no raw store");
     GH_CHECK(h, hipSetDevice(h->device));
@@ -2394,6 +2411,7 @@ int gamma_hip_ivfpq_shard_export_exact(gamma_hip_index* h, const gamma_hip_searc
     GH_NO_PQ4(h, "gamma_hip_ivfpq_shard_export_exact");
     if (h->raw_half) return half_refuse(h, "gamma_hip_ivfpq_shard_export_exact");
     if (h->raw_byte) return byte_refuse(h, "gamma_hip_ivfpq_shard_export_exact");
+    if (h->raw_sq8) return sq8_refuse(h, "gamma_hip_ivfpq_shard_export_exact");
     if (!h->d_raw || h->raw_d != h->d || !h->raw_sparse) return fail(h, GAMMA_HIP_EINVAL, "export of exact distances: a sharded raw store (gamma_hip_raw_put)");
     GH_CHECK(h, hipSetDevice(h->device));
     gh::launch_export_exact(h->stream, p->metric == GAMMA_HIP_METRIC_L2, d_xf, nf, h->d, h->d_raw, h->d_raw_slot, h->raw_slot_cap,
@@ -2570,6 +2588,7 @@ static int merge_replay_impl(gamma_hip_index* h, const gamma_hip_search_params* 
     GH_NO_PQ4(h, "gamma_hip_ivfpq_merge_replay(_exact)");
     if (h->raw_half && p && p->has_rank && !d_ex_all) return half_refuse(h, "gamma_hip_ivfpq_merge_replay without travelled distances");
     if (h->raw_byte && p && p->has_rank && !d_ex_all) return byte_refuse(h, "gamma_hip_ivfpq_merge_replay without travelled distances");
+    if (h->raw_sq8 && p && p->has_rank && !d_ex_all) return sq8_refuse(h, "gamma_hip_ivfpq_merge_replay without travelled distances");
     GH_TRY(ivfpq_check(h, p, nf, k));
     if (nf == 0 || k <= 0) return GAMMA_HIP_OK;
     if (!d_x_slice || !d_vals_all || !d_ids_all || !d_off_all || !d_list || !d_distances || !d_labels)
@@ -2702,7 +2721,7 @@ int gamma_hip_flat_search(gamma_hip_index* h, const gamma_hip_search_params* p, 
     if (!h) return GAMMA_HIP_EINVAL;
     // small unfiltered calls from concurrent client threads share device batches (see gamma_hip_ivfpq_search)
     // (a narrow store is never combined, whatever gamma_hip_set_flat_narrow_rows says)
-    if (h->combine && p && nq > 0 && nq <= COMB_MAX_NQ && k > 0 && x && distances && labels && h->raw_d > 0 && !h->raw_half && !h->raw_byte &&
+    if (h->combine && p && nq > 0 && nq <= COMB_MAX_NQ && k > 0 && x && distances && labels && h->raw_d > 0 && !h->raw_half && !h->raw_byte && !h->raw_sq8 &&
         !p->has_range && p->n_range == 0 && p->n_field == 0 && p->n_term == 0)
         return combined_search(h, p, nq, x, k, distances, labels, /*kind=*/1);
     return flat_search_host_locked(h, p, nq, x, k, distances, labels);

@@ -719,25 +719,28 @@ int64_t gamma_hip_term_count(gamma_hip_index* h, int field_id) {
 
 static const char* const kHalfStore = "the raw store holds float16 rows (gamma_hip_raw_init_f16)";
 static const char* const kByteStore = "the raw store holds 8-bit rows (gamma_hip_raw_init_i8)";
+static const char* const kSq8Store = "the raw store holds scalar-quantised sq8 rows (gamma_hip_raw_init_sq8)";
 
 // the rows, whichever element type the store was initialised with
 static inline char* raw_rows(H* h) {
-    return h->raw_byte ? reinterpret_cast<char*>(h->d_raw_b) : h->raw_half ? reinterpret_cast<char*>(h->d_raw_h) : reinterpret_cast<char*>(h->d_raw);
+    return h->raw_sq8 ? reinterpret_cast<char*>(h->d_raw_q) : h->raw_byte ? reinterpret_cast<char*>(h->d_raw_b) : h->raw_half ? reinterpret_cast<char*>(h->d_raw_h) : reinterpret_cast<char*>(h->d_raw);
 }
 static inline void raw_rows_set(H* h, void* p) {
-    if (h->raw_byte) h->d_raw_b = reinterpret_cast<uint8_t*>(p);
+    if (h->raw_sq8) h->d_raw_q = reinterpret_cast<uint8_t*>(p);
+    else if (h->raw_byte) h->d_raw_b = reinterpret_cast<uint8_t*>(p);
     else if (h->raw_half) h->d_raw_h = reinterpret_cast<uint16_t*>(p);
     else h->d_raw = reinterpret_cast<float*>(p);
 }
 
-// et: 0 fp32, 1 float16, 2 uint8, 3 int8 (gamma_hip_raw_elem_type)
+// et: 0 fp32, 1 float16, 2 uint8, 3 int8, 4 sq8 (gamma_hip_raw_elem_type)
 static int raw_init_as(gamma_hip_index* h, int d, int et) {
     if (!h || d <= 0) return GAMMA_HIP_EINVAL;
     WriteLock lk(h);
     if (h->raw_d != 0 && h->raw_d != d) return fail(h, GAMMA_HIP_EINVAL, "raw store dimension mismatch");
     if (h->raw_d != 0 && h->raw_elem_type() != et) return fail(h, GAMMA_HIP_EINVAL, "the raw store's element type is fixed at its first init");
     h->raw_half = et == 1;
-    h->raw_byte = et >= 2 ? et - 1 : 0;
+    h->raw_byte = et == 2 || et == 3 ? et - 1 : 0;
+    h->raw_sq8 = et == 4;
     if (h->raw_d == 0 && !getenv("GAMMA_HIP_NO_RAW_VMM")) {
         // reserve the address range the store may ever need (the device's memory): physical chunks are mapped into it
         // as rows arrive (raw_reserve).  Any failure -- here or of the FIRST chunk -- leaves the reallocating store.
@@ -754,6 +757,7 @@ static int raw_init_as(gamma_hip_index* h, int d, int et) {
 int gamma_hip_raw_init(gamma_hip_index* h, int d) { return raw_init_as(h, d, 0); }
 int gamma_hip_raw_init_f16(gamma_hip_index* h, int d) { return raw_init_as(h, d, 1); }
 int gamma_hip_raw_init_i8(gamma_hip_index* h, int d, int is_signed) { return raw_init_as(h, d, is_signed ? 3 : 2); }
+int gamma_hip_raw_init_sq8(gamma_hip_index* h, int d) { return raw_init_as(h, d, 4); }
 int gamma_hip_raw_elem_type(gamma_hip_index* h) {
     if (!h) return GAMMA_HIP_EINVAL;
     std::lock_guard<std::mutex> g(h->mu);
@@ -853,8 +857,130 @@ static int raw_byte_check(H* h, int64_t count, const float* v, int64_t base = 0)
              (long long)((base + bad) % h->raw_d));
     return fail(h, GAMMA_HIP_EINVAL, msg);
 }
+// ---- scalar-quantised store (gamma_hip_raw_init_sq8): lossy, float data ------------------------------------------------
+// the acceptance predicate: every value is finite (-0.0 and values far outside the ranges are: the encoder clips)
+int gamma_hip_raw_sq8_check(const float* x, int64_t n, int64_t* first_bad) {
+    if (n < 0 || (n > 0 && !x)) return GAMMA_HIP_EINVAL;
+    for (int64_t i = 0; i < n; i++)
+        if (!std::isfinite(x[i])) {
+            if (first_bad) *first_bad = i;
+            return GAMMA_HIP_EINVAL;
+        }
+    return GAMMA_HIP_OK;
+}
+
+// step = span / 255 and inv = 255 / span of every dimension, one fp32 operation each (this file is built with
+// -ffp-contract=off and the three operations cannot fuse anyway); span == 0 or an infinite inv: a constant dimension
+int gamma_hip_raw_sq8_params(int d, const float* vmin, const float* vmax, float* step_out, float* inv_out) {
+    if (d <= 0 || !vmin || !vmax) return GAMMA_HIP_EINVAL;
+    for (int j = 0; j < d; j++) {
+        if (!std::isfinite(vmin[j]) || !std::isfinite(vmax[j]) || vmin[j] > vmax[j]) return GAMMA_HIP_EINVAL;
+        const float span = vmax[j] - vmin[j];
+        if (!std::isfinite(span)) return GAMMA_HIP_EINVAL;
+    }
+    for (int j = 0; j < d; j++) {
+        const float span = vmax[j] - vmin[j];
+        float step = span / 255.0f;
+        float inv = 255.0f / span;
+        if (span == 0.0f || !std::isfinite(inv)) step = inv = 0.0f;
+        if (step_out) step_out[j] = step;
+        if (inv_out) inv_out[j] = inv;
+    }
+    return GAMMA_HIP_OK;
+}
+
+// the ranges and both tables of an empty sq8 store (caller holds the write lock)
+static int raw_sq8_set_ranges_locked(H* h, const float* vmin, const float* vmax) {
+    if (!h->raw_sq8) return fail(h, GAMMA_HIP_EINVAL, "gamma_hip_raw_sq8_set_ranges: the raw store is not an sq8 store (gamma_hip_raw_init_sq8)");
+    if (h->nraw > 0) return fail(h, GAMMA_HIP_EINVAL, "gamma_hip_raw_sq8_set_ranges: the sq8 raw store holds rows; the ranges change only while it is empty (after gamma_hip_raw_clear)");
+    const int d = h->raw_d;
+    std::vector<float> step(d), inv(d);
+    if (gamma_hip_raw_sq8_params(d, vmin, vmax, step.data(), inv.data()) != GAMMA_HIP_OK)
+        return fail(h, GAMMA_HIP_EINVAL, "gamma_hip_raw_sq8_set_ranges: every range needs finite bounds, vmin <= vmax and a finite span");
+    std::vector<float> tab((size_t)d * 4);
+    for (int j = 0; j < d; j++) {
+        tab[2 * j] = step[j];
+        tab[2 * j + 1] = vmin[j];
+        tab[2 * d + 2 * j] = inv[j];
+        tab[2 * d + 2 * j + 1] = vmin[j];
+    }
+    GH_CHECK(h, hipSetDevice(h->device));
+    if (!h->d_sq8_tab) GH_CHECK(h, hipMalloc((void**)&h->d_sq8_tab, tab.size() * sizeof(float)));
+    // (the store is empty: no search in flight decodes a row)
+    GH_CHECK(h, hipMemcpyAsync(h->d_sq8_tab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice, h->wstream));
+    GH_CHECK(h, hipStreamSynchronize(h->wstream));
+    h->sq8_vmin.assign(vmin, vmin + d);
+    h->sq8_vmax.assign(vmax, vmax + d);
+    h->sq8_step.swap(step);
+    return GAMMA_HIP_OK;
+}
+
+int gamma_hip_raw_sq8_set_ranges(gamma_hip_index* h, const float* vmin, const float* vmax) {
+    if (!h || !vmin || !vmax) return GAMMA_HIP_EINVAL;
+    WriteLock lk(h);
+    return raw_sq8_set_ranges_locked(h, vmin, vmax);
+}
+
+int gamma_hip_raw_sq8_get_ranges(gamma_hip_index* h, float* vmin, float* vmax) {
+    if (!h || !vmin || !vmax) return GAMMA_HIP_EINVAL;
+    std::lock_guard<std::mutex> g(h->mu);
+    if (!h->raw_sq8 || h->sq8_vmin.empty()) {
+        h->err = "gamma_hip_raw_sq8_get_ranges: no ranges (an sq8 store after gamma_hip_raw_sq8_set_ranges / _train has them)";
+        return GAMMA_HIP_EINVAL;
+    }
+    memcpy(vmin, h->sq8_vmin.data(), h->sq8_vmin.size() * sizeof(float));
+    memcpy(vmax, h->sq8_vmax.data(), h->sq8_vmax.size() * sizeof(float));
+    return GAMMA_HIP_OK;
+}
+
+static int raw_sq8_check(H* h, int64_t count, const float* v, int64_t base = 0);
+
+// per-dimension minimum and maximum of n host rows: staged through the writer's staging buffer in 64 MB pieces, every piece
+// folded into the running result by k_sq8_minmax on the writer stream
+int gamma_hip_raw_sq8_train(gamma_hip_index* h, int64_t n, const float* x) {
+    if (!h || n <= 0 || !x) return GAMMA_HIP_EINVAL;
+    WriteLock lk(h);
+    if (!h->raw_sq8) return fail(h, GAMMA_HIP_EINVAL, "gamma_hip_raw_sq8_train: the raw store is not an sq8 store (gamma_hip_raw_init_sq8)");
+    if (h->nraw > 0) return fail(h, GAMMA_HIP_EINVAL, "gamma_hip_raw_sq8_train: the sq8 raw store holds rows; the ranges change only while it is empty (after gamma_hip_raw_clear)");
+    const int d = h->raw_d;
+    GH_TRY(raw_sq8_check(h, n * d, x));
+    GH_CHECK(h, hipSetDevice(h->device));
+    const int64_t piece = std::max<int64_t>(1, ((int64_t)16 << 20) / d);
+    GH_CHECK(h, h->we_stage.ensure((size_t)std::min(piece, n) * d * sizeof(float)));
+    GH_CHECK(h, h->we_chk.ensure((size_t)d * 2 * sizeof(float)));   // d minima, d maxima
+    for (int64_t i0 = 0; i0 < n; i0 += piece) {
+        const int64_t m = std::min(piece, n - i0);
+        GH_CHECK(h, hipMemcpyAsync(h->we_stage.p, x + i0 * d, (size_t)m * d * sizeof(float), hipMemcpyHostToDevice, h->wstream));
+        gh::launch_sq8_minmax(h->wstream, h->we_stage.as<float>(), m, d, h->we_chk.as<float>(), /*first=*/i0 == 0);
+    }
+    GH_CHECK(h, hipGetLastError());
+    std::vector<float> mm((size_t)d * 2);
+    GH_CHECK(h, hipMemcpyAsync(mm.data(), h->we_chk.p, mm.size() * sizeof(float), hipMemcpyDeviceToHost, h->wstream));
+    GH_CHECK(h, hipStreamSynchronize(h->wstream));
+    for (float& v : mm) v += 0.0f;   // -0.0 -> +0.0: which zero a minimum of both returns depends on the order
+    return raw_sq8_set_ranges_locked(h, mm.data(), mm.data() + d);
+}
+
+// the writers' check in front of their reservation: ranges first, then the values (base: see raw_byte_check)
+static int raw_sq8_check(H* h, int64_t count, const float* v, int64_t base) {
+    int64_t bad = -1;
+    if (gamma_hip_raw_sq8_check(v, count, &bad) == GAMMA_HIP_OK) return GAMMA_HIP_OK;
+    char msg[256];
+    snprintf(msg, sizeof(msg), "raw store (sq8, gamma_hip_raw_init_sq8): value %g at position %lld (row %lld, element %lld) is not finite; nothing was written",
+             (double)v[bad], (long long)(base + bad), (long long)((base + bad) / h->raw_d), (long long)((base + bad) % h->raw_d));
+    return fail(h, GAMMA_HIP_EINVAL, msg);
+}
+static int raw_sq8_need_ranges(H* h) {
+    if (!h->sq8_vmin.empty()) return GAMMA_HIP_OK;
+    return fail(h, GAMMA_HIP_EINVAL, "raw store (sq8, gamma_hip_raw_init_sq8): no ranges yet (gamma_hip_raw_sq8_set_ranges / _train come before the first row); nothing was written");
+}
+
 // the check of a writer's values for the store's element type (fp32 rows take everything)
 static int raw_narrow_check(H* h, int64_t count, const float* v) {
+    if (h->raw_sq8) {
+        GH_TRY(raw_sq8_need_ranges(h));
+        return raw_sq8_check(h, count, v);
+    }
     if (h->raw_byte) return raw_byte_check(h, count, v);
     if (h->raw_half) return raw_half_check(h, count, v);
     return GAMMA_HIP_OK;
@@ -874,7 +1000,10 @@ static int raw_narrow_rows_in(H* h, int64_t first, const int64_t* vids, int64_t 
     for (int64_t i0 = 0; i0 < n; i0 += piece) {
         const int64_t m = std::min(piece, n - i0);
         GH_CHECK(h, hipMemcpyAsync(h->we_stage.p, vecs + i0 * d, (size_t)m * d * sizeof(float), hipMemcpyHostToDevice, h->wstream));
-        if (h->raw_byte)
+        if (h->raw_sq8)
+            gh::launch_raw_rows_to_sq8(h->wstream, h->we_stage.as<float>(), vids ? h->we_chk.as<int64_t>() + i0 : nullptr, first + i0, m, d,
+                                       h->d_sq8_tab + 2 * (size_t)d, h->d_raw_q, nrows);
+        else if (h->raw_byte)
             gh::launch_raw_rows_to_bytes(h->wstream, h->we_stage.as<float>(), vids ? h->we_chk.as<int64_t>() + i0 : nullptr, first + i0, m,
                                          d, h->d_raw_b, nrows);
         else
@@ -894,7 +1023,7 @@ int gamma_hip_raw_append(gamma_hip_index* h, int64_t n, const float* vecs) {
     GH_TRY(raw_narrow_check(h, n * h->raw_d, vecs));
     GH_CHECK(h, hipSetDevice(h->device));
     GH_TRY(raw_reserve(h, h->nraw + n));
-    if (h->raw_half || h->raw_byte)
+    if (h->raw_esz() != sizeof(float))
         GH_TRY(raw_narrow_rows_in(h, h->nraw, nullptr, n, vecs, h->raw_cap));
     else
         GH_CHECK(h, hipMemcpyAsync(h->d_raw + h->nraw * h->raw_d, vecs, (size_t)n * h->raw_d * sizeof(float),
@@ -938,6 +1067,7 @@ int gamma_hip_raw_put(gamma_hip_index* h, int64_t n, const int64_t* vids, const 
     if (h->raw_d <= 0) return fail(h, GAMMA_HIP_EINVAL, "raw store not initialised");
     if (h->raw_half) return fail(h, GAMMA_HIP_EUNSUPPORTED, kHalfStore);   // rows sharded with their lists are fp32
     if (h->raw_byte) return fail(h, GAMMA_HIP_EUNSUPPORTED, kByteStore);
+    if (h->raw_sq8) return fail(h, GAMMA_HIP_EUNSUPPORTED, kSq8Store);
     if (!h->raw_sparse && h->nraw > 0) return fail(h, GAMMA_HIP_EINVAL, "raw_put on a store that holds rows by vector id");
     if (n == 0) {   // the first call turns the empty store into the sparse form, rows or not (a shard that owns no vector yet)
         if (!h->raw_sparse) {
@@ -1024,6 +1154,7 @@ int gamma_hip_raw_drop(gamma_hip_index* h, int64_t n, const int64_t* vids) {
     WriteLock lk(h);
     if (h->raw_half) return fail(h, GAMMA_HIP_EUNSUPPORTED, kHalfStore);
     if (h->raw_byte) return fail(h, GAMMA_HIP_EUNSUPPORTED, kByteStore);
+    if (h->raw_sq8) return fail(h, GAMMA_HIP_EUNSUPPORTED, kSq8Store);
     if (!h->raw_sparse) {
         if (h->nraw > 0) return fail(h, GAMMA_HIP_EINVAL, "raw_drop on a store that holds rows by vector id");
         return GAMMA_HIP_OK;   // empty: nothing to forget
@@ -1095,7 +1226,7 @@ int gamma_hip_raw_write(gamma_hip_index* h, int64_t first_vid, int64_t n, const 
     GH_TRY(raw_narrow_check(h, n * h->raw_d, vecs));
     GH_CHECK(h, hipSetDevice(h->device));
     GH_TRY(raw_reserve(h, first_vid + n));
-    if (h->raw_half || h->raw_byte)
+    if (h->raw_esz() != sizeof(float))
         GH_TRY(raw_narrow_rows_in(h, first_vid, nullptr, n, vecs, h->raw_cap));
     else
         GH_CHECK(h, hipMemcpyAsync(h->d_raw + first_vid * h->raw_d, vecs, (size_t)n * h->raw_d * sizeof(float),
@@ -1112,7 +1243,7 @@ int gamma_hip_raw_update(gamma_hip_index* h, int64_t vid, const float* vec) {
     if (vid < 0 || vid >= h->nraw) return fail(h, GAMMA_HIP_EINVAL, "vid out of range");
     GH_TRY(raw_narrow_check(h, h->raw_d, vec));
     GH_CHECK(h, hipSetDevice(h->device));
-    if (h->raw_half || h->raw_byte)
+    if (h->raw_esz() != sizeof(float))
         GH_TRY(raw_narrow_rows_in(h, vid, nullptr, 1, vec, h->nraw));
     else
         GH_CHECK(h, hipMemcpyAsync(h->d_raw + vid * h->raw_d, vec, (size_t)h->raw_d * sizeof(float),
@@ -1127,10 +1258,12 @@ int gamma_hip_raw_update_batch(gamma_hip_index* h, int64_t n, const int64_t* vid
     if (n == 0) return GAMMA_HIP_OK;
     WriteLock lk(h);
     if (h->raw_sparse) return fail(h, GAMMA_HIP_EUNSUPPORTED, "the raw store holds this shard's rows only (gamma_hip_raw_put)");
-    if (h->raw_half || h->raw_byte) {
+    if (h->raw_esz() != sizeof(float)) {
+        if (h->raw_sq8) GH_TRY(raw_sq8_need_ranges(h));
         for (int64_t i = 0; i < n; i++)
             if (vids[i] >= 0 && vids[i] < h->nraw) {
-                if (h->raw_byte) GH_TRY(raw_byte_check(h, h->raw_d, vecs + i * h->raw_d, i * h->raw_d));
+                if (h->raw_sq8) GH_TRY(raw_sq8_check(h, h->raw_d, vecs + i * h->raw_d, i * h->raw_d));
+                else if (h->raw_byte) GH_TRY(raw_byte_check(h, h->raw_d, vecs + i * h->raw_d, i * h->raw_d));
                 else GH_TRY(raw_half_check(h, h->raw_d, vecs + i * h->raw_d));
             }
         // one kernel writes all rows: of a vid named twice the last entry wins, as with the fp32 store's ordered copies
@@ -1186,6 +1319,19 @@ int gamma_hip_raw_gets(gamma_hip_index* h, int64_t n, const int64_t* vids, float
             for (size_t i = 0; i < bb.size(); i++) out[i] = (float)(int8_t)bb[i];
         else
             for (size_t i = 0; i < bb.size(); i++) out[i] = (float)bb[i];
+        return GAMMA_HIP_OK;
+    }
+    if (h->raw_sq8) {   // the codes come back as they are and are decoded here: a multiply, then an add, each rounded in fp32
+        std::vector<uint8_t> bb((size_t)n * h->raw_d);
+        for (int64_t i = 0; i < n; i++)
+            GH_CHECK(h, hipMemcpyAsync(bb.data() + i * h->raw_d, h->d_raw_q + vids[i] * h->raw_d, (size_t)h->raw_d, hipMemcpyDeviceToHost,
+                                       h->wstream));
+        GH_CHECK(h, hipStreamSynchronize(h->wstream));
+        for (int64_t i = 0; i < n; i++)
+            for (int j = 0; j < h->raw_d; j++) {
+                const float t = (float)bb[i * h->raw_d + j] * h->sq8_step[j];
+                out[i * h->raw_d + j] = h->sq8_vmin[j] + t;
+            }
         return GAMMA_HIP_OK;
     }
     for (int64_t i = 0; i < n; i++)

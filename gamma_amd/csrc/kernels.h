@@ -410,6 +410,13 @@ void launch_rerank_dist_b(hipStream_t s, bool l2, const float* x, int nq, int d,
 void launch_rerank_topk_b(hipStream_t s, bool l2, const float* x, int nq, int d, const uint8_t* raw, bool is_signed, int64_t nraw,
                           const int64_t* cand_ids, int R, int k, float min_score, float max_score, float neutral, float* distances,
                           int64_t* labels, const int* qperm = nullptr, const TieFlags* ties = nullptr);
+// scalar-quantised raw store (gamma_hip_raw_init_sq8): the same two launches over rows of one code per element, decoded through
+// tab = d x {step[j], vmin[j]} (device memory) in front of the fma chain; the byte rows' loads
+void launch_rerank_dist_sq8(hipStream_t s, bool l2, const float* x, int nq, int d, const uint8_t* raw, const float* tab, int64_t nraw,
+                            const int64_t* cand_ids, int R, float min_score, float max_score, float* out);
+void launch_rerank_topk_sq8(hipStream_t s, bool l2, const float* x, int nq, int d, const uint8_t* raw, const float* tab, int64_t nraw,
+                            const int64_t* cand_ids, int R, int k, float min_score, float max_score, float neutral, float* distances,
+                            int64_t* labels, const int* qperm = nullptr, const TieFlags* ties = nullptr);
 // what k_tie_replay needs to redo one query (ties.hip)
 struct TieReplayArgs {
     const int* list;              // flagged queries, *count of them
@@ -449,6 +456,8 @@ struct TieReplayArgs {
     const uint16_t* raw_h = nullptr;   // float16 raw store: the rows (raw is null then); launch_tie_replay takes the half-row kernels
     const uint8_t* raw_b = nullptr;    // byte raw store: the rows (raw and raw_h are null then), int8 when raw_b_signed, else uint8
     int raw_b_signed = 0;
+    const uint8_t* raw_q = nullptr;    // scalar-quantised raw store: the rows (raw, raw_h and raw_b are null then) ...
+    const float* sq8_tab = nullptr;    // ... and their decode table, d x {step[j], vmin[j]}
 };
 int tie_replay_max_k();
 int tie_small_max_k();
@@ -509,6 +518,12 @@ void launch_raw_rows_to_half(hipStream_t s, const float* stage, const int64_t* v
 // vids[i] (outside [0, nrows): skipped)
 void launch_raw_rows_to_bytes(hipStream_t s, const float* stage, const int64_t* vids, int64_t first, int64_t n, int d, uint8_t* raw,
                               int64_t nrows);
+// scalar-quantised raw store (gamma_hip_raw_init_sq8): n staged fp32 rows (checked by the host: every value is finite) encoded
+// with enc = d x {inv[j], vmin[j]} into rows first + i, or vids[i] (outside [0, nrows): skipped)
+void launch_raw_rows_to_sq8(hipStream_t s, const float* stage, const int64_t* vids, int64_t first, int64_t n, int d, const float* enc,
+                            uint8_t* raw, int64_t nrows);
+// mm[j], mm[d + j] = minimum, maximum of dimension j over n staged rows; first: mm is replaced, else folded in
+void launch_sq8_minmax(hipStream_t s, const float* x, int64_t n, int d, float* mm, bool first);
 void launch_list_checksum(hipStream_t s, const uint8_t* codes, const int64_t* ids, const int64_t* off, const int* len, int nlist,
                           int M, int max_len, unsigned long long* out);
 void launch_repack_lists(hipStream_t s, const uint8_t* oc, const int64_t* oi, uint8_t* nc, int64_t* ni,

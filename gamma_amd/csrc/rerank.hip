@@ -61,13 +61,16 @@ void launch_map_candidates(hipStream_t s, const int* pos, int nq, int R, int P,
 // (32 candidates in flight).  Out-of-window scores and empty slots get the sentinel.
 // ROW = uint16_t: a float16 raw store (rerank_dev.h: the same arithmetic over the widened row).
 // ROW = uint8_t / int8_t: a store of byte rows (gamma_hip_raw_init_i8), likewise.
+// ROW = sq8_t: scalar-quantised byte rows (gamma_hip_raw_init_sq8), decoded through tab (rerank_dev.h); tab is null and unread
+// for every other row type.
 // ------------------------------------------------------------------------------------
 template <bool L2, typename ROW = float>
 __global__ __launch_bounds__(256) void k_rerank_dist(const float* __restrict__ x, int d,
                                                      const ROW* __restrict__ raw, int64_t nraw,
                                                      const int64_t* __restrict__ cand_ids, int R,
                                                      float min_score, float max_score,
-                                                     float* __restrict__ out, const int32_t* __restrict__ slot, int64_t nslot) {
+                                                     float* __restrict__ out, const int32_t* __restrict__ slot, int64_t nslot,
+                                                     const float2* __restrict__ tab) {
     const int q = blockIdx.x;
     const int l = threadIdx.x & 7, g = threadIdx.x >> 3;
     const float* xq = x + (int64_t)q * d;
@@ -78,7 +81,11 @@ __global__ __launch_bounds__(256) void k_rerank_dist(const float* __restrict__ x
         if (r < R) id = cand_ids[(int64_t)q * R + r];
         if (slot) id = (id >= 0 && id < nslot) ? (int64_t)slot[id] : -1;   // sharded raw store: the row of this vector HERE
         const bool live = id >= 0 && id < nraw;
-        float dis = rerank_dist8<L2>(xq, raw + (live ? id : 0) * d, d, l, live);
+        float dis;
+        if constexpr (std::is_same<ROW, sq8_t>::value)
+            dis = rerank_dist8_sq8<L2>(xq, reinterpret_cast<const uint8_t*>(raw) + (live ? id : 0) * d, tab, d, l, live);
+        else
+            dis = rerank_dist8<L2>(xq, raw + (live ? id : 0) * d, d, l, live);
         if (l == 0 && r < R) {
             if (!live || !(dis <= max_score && dis >= min_score)) dis = sentinel;
             out[(int64_t)q * R + r] = dis;
@@ -92,10 +99,10 @@ void launch_rerank_dist(hipStream_t s, bool l2, const float* x, int nq, int d, c
     const int gy = (R + 31) / 32;   // 32 candidates (8 lanes each) per workgroup
     if (l2)
         hipLaunchKernelGGL((k_rerank_dist<true>), dim3(nq, gy), dim3(256), 0, s, x, d, raw, nraw, cand_ids,
-                           R, min_score, max_score, out, slot, nslot);
+                           R, min_score, max_score, out, slot, nslot, nullptr);
     else
         hipLaunchKernelGGL((k_rerank_dist<false>), dim3(nq, gy), dim3(256), 0, s, x, d, raw, nraw,
-                           cand_ids, R, min_score, max_score, out, slot, nslot);
+                           cand_ids, R, min_score, max_score, out, slot, nslot, nullptr);
 }
 void launch_rerank_dist_h(hipStream_t s, bool l2, const float* x, int nq, int d, const uint16_t* raw, int64_t nraw,
                           const int64_t* cand_ids, int R, float min_score, float max_score, float* out) {
@@ -103,10 +110,10 @@ void launch_rerank_dist_h(hipStream_t s, bool l2, const float* x, int nq, int d,
     const int gy = (R + 31) / 32;
     if (l2)
         hipLaunchKernelGGL((k_rerank_dist<true, uint16_t>), dim3(nq, gy), dim3(256), 0, s, x, d, raw, nraw, cand_ids, R, min_score,
-                           max_score, out, nullptr, (int64_t)0);
+                           max_score, out, nullptr, (int64_t)0, nullptr);
     else
         hipLaunchKernelGGL((k_rerank_dist<false, uint16_t>), dim3(nq, gy), dim3(256), 0, s, x, d, raw, nraw, cand_ids, R, min_score,
-                           max_score, out, nullptr, (int64_t)0);
+                           max_score, out, nullptr, (int64_t)0, nullptr);
 }
 template <typename ROW>
 static void launch_rerank_dist_b_(hipStream_t s, bool l2, const float* x, int nq, int d, const ROW* raw, int64_t nraw,
@@ -114,10 +121,10 @@ static void launch_rerank_dist_b_(hipStream_t s, bool l2, const float* x, int nq
     const int gy = (R + 31) / 32;
     if (l2)
         hipLaunchKernelGGL((k_rerank_dist<true, ROW>), dim3(nq, gy), dim3(256), 0, s, x, d, raw, nraw, cand_ids, R, min_score,
-                           max_score, out, nullptr, (int64_t)0);
+                           max_score, out, nullptr, (int64_t)0, nullptr);
     else
         hipLaunchKernelGGL((k_rerank_dist<false, ROW>), dim3(nq, gy), dim3(256), 0, s, x, d, raw, nraw, cand_ids, R, min_score,
-                           max_score, out, nullptr, (int64_t)0);
+                           max_score, out, nullptr, (int64_t)0, nullptr);
 }
 void launch_rerank_dist_b(hipStream_t s, bool l2, const float* x, int nq, int d, const uint8_t* raw, bool is_signed, int64_t nraw,
                           const int64_t* cand_ids, int R, float min_score, float max_score, float* out) {
@@ -126,6 +133,20 @@ void launch_rerank_dist_b(hipStream_t s, bool l2, const float* x, int nq, int d,
         launch_rerank_dist_b_(s, l2, x, nq, d, reinterpret_cast<const int8_t*>(raw), nraw, cand_ids, R, min_score, max_score, out);
     else
         launch_rerank_dist_b_(s, l2, x, nq, d, raw, nraw, cand_ids, R, min_score, max_score, out);
+}
+
+void launch_rerank_dist_sq8(hipStream_t s, bool l2, const float* x, int nq, int d, const uint8_t* raw, const float* tab, int64_t nraw,
+                            const int64_t* cand_ids, int R, float min_score, float max_score, float* out) {
+    if (nq <= 0) return;
+    const int gy = (R + 31) / 32;
+    const sq8_t* rows = reinterpret_cast<const sq8_t*>(raw);
+    const float2* t = reinterpret_cast<const float2*>(tab);
+    if (l2)
+        hipLaunchKernelGGL((k_rerank_dist<true, sq8_t>), dim3(nq, gy), dim3(256), 0, s, x, d, rows, nraw, cand_ids, R, min_score,
+                           max_score, out, nullptr, (int64_t)0, t);
+    else
+        hipLaunchKernelGGL((k_rerank_dist<false, sq8_t>), dim3(nq, gy), dim3(256), 0, s, x, d, rows, nraw, cand_ids, R, min_score,
+                           max_score, out, nullptr, (int64_t)0, t);
 }
 
 // Exact distances of the entries of an exported candidate stream that can still be members of the recall_num-heap: ADC value
@@ -240,6 +261,8 @@ void launch_lookup_exact(hipStream_t s, bool l2, const float* all_dis, const int
 // ------------------------------------------------------------------------------------
 // ROW = uint16_t: a float16 raw store (eight lanes per candidate as for fp32 rows; the row loads: rerank_dev.h).
 // ROW = uint8_t / int8_t: byte rows, eight lanes per candidate; d = 128 keeps the query in registers as the fp32 rows do.
+// ROW = sq8_t: scalar-quantised byte rows decoded through tab (null and unread for every other row type); d = 128 keeps the
+// lane's 16 {step, vmin} pairs in registers beside its query elements.
 template <bool L2, typename ROW = float>
 __global__ __launch_bounds__(256) void k_rerank_topk(const float* __restrict__ x, int d,
                                                      const ROW* __restrict__ raw, int64_t nraw,
@@ -247,7 +270,8 @@ __global__ __launch_bounds__(256) void k_rerank_topk(const float* __restrict__ x
                                                      float min_score, float max_score, float neutral,
                                                      float* __restrict__ distances,
                                                      int64_t* __restrict__ labels, int nq,
-                                                     const int* __restrict__ qperm, TieFlags tf) {
+                                                     const int* __restrict__ qperm, TieFlags tf,
+                                                     const float2* __restrict__ tab) {
     __shared__ unsigned long long s_it[1024];
     __shared__ int64_t s_id[1024];
     __shared__ int s_tie;
@@ -283,10 +307,70 @@ __global__ __launch_bounds__(256) void k_rerank_topk(const float* __restrict__ x
             int64_t id = -1;
             if (r < R) id = s_id[r];
             const bool live = id >= 0 && id < nraw;
-            put(r, live, rerank_dist8<L2>(xq, raw + (live ? id : 0) * d, d, l, live));
+            if constexpr (std::is_same<ROW, sq8_t>::value)
+                put(r, live, rerank_dist8_sq8<L2>(xq, reinterpret_cast<const uint8_t*>(raw) + (live ? id : 0) * d, tab, d, l, live));
+            else
+                put(r, live, rerank_dist8<L2>(xq, raw + (live ? id : 0) * d, d, l, live));
         }
     };
-    if constexpr (std::is_same<ROW, uint8_t>::value || std::is_same<ROW, int8_t>::value) {
+    if constexpr (std::is_same<ROW, sq8_t>::value) {
+        if (d == 128 && nraw > 0) {
+            // the byte rows' d = 128 form with the decode in front of the chain: the lane's 16 query elements and its 16
+            // {step, vmin} pairs in registers, two candidates per group in flight, a row = eight 16-byte loads the group shares
+            const uint8_t* rows = reinterpret_cast<const uint8_t*>(raw);
+            const int sh = 8 * (l & 3);
+            const bool hi = l & 4;
+            float xx[16];
+            float2 tt[16];
+#pragma unroll
+            for (int u = 0; u < 16; u++) xx[u] = xq[l + 8 * u];
+#pragma unroll
+            for (int u = 0; u < 16; u++) tt[u] = tab[l + 8 * u];
+            for (int r0 = 0; r0 < R; r0 += 64) {
+                const int ra = r0 + g, rb = r0 + 32 + g;
+                const int64_t ida = ra < R ? s_id[ra] : -1, idb = rb < R ? s_id[rb] : -1;
+                const bool la = ida >= 0 && ida < nraw, lb = idb >= 0 && idb < nraw;
+                const uint4* va = reinterpret_cast<const uint4*>(rows + (la ? ida : 0) * 128);
+                const uint4* vb = reinterpret_cast<const uint4*>(rows + (lb ? idb : 0) * 128);
+                uint32_t ea[16], eb[16];   // the lane's dword of every 8 elements, picked as the chunk arrives
+#pragma unroll
+                for (int u = 0; u < 8; u++) {
+                    const uint4 w = va[u];
+                    const uint32_t wx = w.x, wy = w.y, wz = w.z, ww = w.w;
+                    ea[2 * u] = hi ? wy : wx;
+                    ea[2 * u + 1] = hi ? ww : wz;
+                }
+#pragma unroll
+                for (int u = 0; u < 8; u++) {
+                    const uint4 w = vb[u];
+                    const uint32_t wx = w.x, wy = w.y, wz = w.z, ww = w.w;
+                    eb[2 * u] = hi ? wy : wx;
+                    eb[2 * u + 1] = hi ? ww : wz;
+                }
+                float a = 0.f, b = 0.f;
+#pragma unroll
+                for (int u = 0; u < 16; u++) {
+                    const float fa = sq8_row_f((ea[u] >> sh) & 0xffu, tt[u]), fb = sq8_row_f((eb[u] >> sh) & 0xffu, tt[u]);
+                    if (L2) {
+                        const float ta = xx[u] - fa, tb = xx[u] - fb;
+                        a = __builtin_fmaf(ta, ta, a);
+                        b = __builtin_fmaf(tb, tb, b);
+                    } else {
+                        a = __builtin_fmaf(xx[u], fa, a);
+                        b = __builtin_fmaf(xx[u], fb, b);
+                    }
+                }
+                if (!la) a = 0.f;
+                if (!lb) b = 0.f;
+                const float sa = __shfl_down(a, 4, 8) + a, sb_ = __shfl_down(b, 4, 8) + b;
+                const float ta = sa + __shfl_down(sa, 1, 8), tb = sb_ + __shfl_down(sb_, 1, 8);
+                put(ra, la, ta + __shfl_down(ta, 2, 8));
+                put(rb, lb, tb + __shfl_down(tb, 2, 8));
+            }
+        } else {
+            rounds_of_32();
+        }
+    } else if constexpr (std::is_same<ROW, uint8_t>::value || std::is_same<ROW, int8_t>::value) {
         if (d == 128 && nraw > 0) {
             // the fp32 rows' d = 128 form over byte rows: the lane's 16 query elements in registers, two candidates per group in
             // flight, a row = eight 16-byte loads that the group's lanes share (rerank_dev.h, rerank_dist8_bytes: lane l's elements
@@ -481,10 +565,10 @@ void launch_rerank_topk(hipStream_t s, bool l2, const float* x, int nq, int d, c
     const TieFlags tf = ties ? *ties : TieFlags{};
     if (l2)
         hipLaunchKernelGGL((k_rerank_topk<true>), grid, dim3(256), 0, s, x, d, raw, nraw, cand_ids,
-                           R, k, min_score, max_score, neutral, distances, labels, nq, qperm, tf);
+                           R, k, min_score, max_score, neutral, distances, labels, nq, qperm, tf, nullptr);
     else
         hipLaunchKernelGGL((k_rerank_topk<false>), grid, dim3(256), 0, s, x, d, raw, nraw, cand_ids,
-                           R, k, min_score, max_score, neutral, distances, labels, nq, qperm, tf);
+                           R, k, min_score, max_score, neutral, distances, labels, nq, qperm, tf, nullptr);
 }
 void launch_rerank_topk_h(hipStream_t s, bool l2, const float* x, int nq, int d, const uint16_t* raw, int64_t nraw,
                           const int64_t* cand_ids, int R, int k, float min_score, float max_score, float neutral, float* distances,
@@ -494,10 +578,10 @@ void launch_rerank_topk_h(hipStream_t s, bool l2, const float* x, int nq, int d,
     const TieFlags tf = ties ? *ties : TieFlags{};
     if (l2)
         hipLaunchKernelGGL((k_rerank_topk<true, uint16_t>), grid, dim3(256), 0, s, x, d, raw, nraw, cand_ids, R, k, min_score,
-                           max_score, neutral, distances, labels, nq, qperm, tf);
+                           max_score, neutral, distances, labels, nq, qperm, tf, nullptr);
     else
         hipLaunchKernelGGL((k_rerank_topk<false, uint16_t>), grid, dim3(256), 0, s, x, d, raw, nraw, cand_ids, R, k, min_score,
-                           max_score, neutral, distances, labels, nq, qperm, tf);
+                           max_score, neutral, distances, labels, nq, qperm, tf, nullptr);
 }
 template <typename ROW>
 static void launch_rerank_topk_b_(hipStream_t s, bool l2, const float* x, int nq, int d, const ROW* raw, int64_t nraw,
@@ -506,10 +590,10 @@ static void launch_rerank_topk_b_(hipStream_t s, bool l2, const float* x, int nq
     const dim3 grid((unsigned)(8 * ((nq + 7) / 8)));
     if (l2)
         hipLaunchKernelGGL((k_rerank_topk<true, ROW>), grid, dim3(256), 0, s, x, d, raw, nraw, cand_ids, R, k, min_score,
-                           max_score, neutral, distances, labels, nq, qperm, tf);
+                           max_score, neutral, distances, labels, nq, qperm, tf, nullptr);
     else
         hipLaunchKernelGGL((k_rerank_topk<false, ROW>), grid, dim3(256), 0, s, x, d, raw, nraw, cand_ids, R, k, min_score,
-                           max_score, neutral, distances, labels, nq, qperm, tf);
+                           max_score, neutral, distances, labels, nq, qperm, tf, nullptr);
 }
 void launch_rerank_topk_b(hipStream_t s, bool l2, const float* x, int nq, int d, const uint8_t* raw, bool is_signed, int64_t nraw,
                           const int64_t* cand_ids, int R, int k, float min_score, float max_score, float neutral, float* distances,
@@ -521,6 +605,22 @@ void launch_rerank_topk_b(hipStream_t s, bool l2, const float* x, int nq, int d,
                               neutral, distances, labels, qperm, tf);
     else
         launch_rerank_topk_b_(s, l2, x, nq, d, raw, nraw, cand_ids, R, k, min_score, max_score, neutral, distances, labels, qperm, tf);
+}
+
+void launch_rerank_topk_sq8(hipStream_t s, bool l2, const float* x, int nq, int d, const uint8_t* raw, const float* tab, int64_t nraw,
+                            const int64_t* cand_ids, int R, int k, float min_score, float max_score, float neutral, float* distances,
+                            int64_t* labels, const int* qperm, const TieFlags* ties) {
+    if (nq <= 0) return;
+    const dim3 grid((unsigned)(8 * ((nq + 7) / 8)));
+    const TieFlags tf = ties ? *ties : TieFlags{};
+    const sq8_t* rows = reinterpret_cast<const sq8_t*>(raw);
+    const float2* t = reinterpret_cast<const float2*>(tab);
+    if (l2)
+        hipLaunchKernelGGL((k_rerank_topk<true, sq8_t>), grid, dim3(256), 0, s, x, d, rows, nraw, cand_ids, R, k, min_score,
+                           max_score, neutral, distances, labels, nq, qperm, tf, t);
+    else
+        hipLaunchKernelGGL((k_rerank_topk<false, sq8_t>), grid, dim3(256), 0, s, x, d, rows, nraw, cand_ids, R, k, min_score,
+                           max_score, neutral, distances, labels, nq, qperm, tf, t);
 }
 
 // ------------------------------------------------------------------------------------

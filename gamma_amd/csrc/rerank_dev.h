@@ -287,4 +287,99 @@ __device__ __forceinline__ float rerank_dist8(const float* __restrict__ xq, cons
     return rerank_dist8_bytes<L2, true>(xq, reinterpret_cast<const uint8_t*>(v), d, l, live);
 }
 
+// ---- rows of one scalar-quantised byte per element (gamma_hip_raw_init_sq8) ---------------------------------------------
+// The same distance over the DECODED row: element j of a row is w = vmin[j] + float(code) * step[j], a multiply and then an
+// add, each rounded in fp32 (the __f*_rn intrinsics never contract into an fma), in front of the unchanged fma chain.  The
+// decode is not folded into the query: that would change bits.  tab[j] = {step[j], vmin[j]}: one 8-byte load per element beside
+// the query's 4-byte load, the same 64 consecutive bytes for the eight lanes of every group (a table of 8 d bytes, resident in
+// the caches).  sq8_t is the row type the kernels are instantiated over.
+struct sq8_t {
+    uint8_t code;
+};
+__device__ __forceinline__ float sq8_row_f(uint32_t b, const float2 t) { return __fadd_rn(t.y, __fmul_rn((float)b, t.x)); }
+
+// Same contract as rerank_dist8 above; the byte rows' loads (rerank_dist8_bytes): d % 16 == 0 shares 16-byte loads in the group,
+// d % 4 == 0 dword loads, other d byte loads.
+template <bool L2>
+__device__ __forceinline__ float rerank_dist8_sq8(const float* __restrict__ xq, const uint8_t* __restrict__ v,
+                                                  const float2* __restrict__ tab, int d, int l, bool live) {
+    const int d8 = d & ~7;
+    const int sh = 8 * (l & 3);
+    float a = 0.f;
+    auto step = [&](float x, float y) {
+        if (L2) {
+            const float t = x - y;
+            a = __builtin_fmaf(t, t, a);
+        } else {
+            a = __builtin_fmaf(x, y, a);
+        }
+    };
+    if (live) {
+        if ((d & 15) == 0) {   // (uniform)
+            const bool hi = l & 4;
+            const uint4* __restrict__ v4 = reinterpret_cast<const uint4*>(v);
+            const int nc = d >> 4;   // chunks of 16 elements
+            int c = 0;
+            for (; c + 8 <= nc; c += 8) {
+                uint32_t e0[8], e1[8];
+                float xx[16];
+                float2 tt[16];
+#pragma unroll
+                for (int u = 0; u < 8; u++) {
+                    const uint4 w = v4[c + u];
+                    const uint32_t wx = w.x, wy = w.y, wz = w.z, ww = w.w;
+                    e0[u] = hi ? wy : wx;
+                    e1[u] = hi ? ww : wz;
+                }
+#pragma unroll
+                for (int u = 0; u < 16; u++) xx[u] = xq[16 * c + 8 * u + l];
+#pragma unroll
+                for (int u = 0; u < 16; u++) tt[u] = tab[16 * c + 8 * u + l];
+#pragma unroll
+                for (int u = 0; u < 8; u++) {
+                    step(xx[2 * u], sq8_row_f((e0[u] >> sh) & 0xffu, tt[2 * u]));
+                    step(xx[2 * u + 1], sq8_row_f((e1[u] >> sh) & 0xffu, tt[2 * u + 1]));
+                }
+            }
+            for (; c < nc; c++) {
+                const uint4 w = v4[c];
+                const uint32_t wx = w.x, wy = w.y, wz = w.z, ww = w.w;
+                step(xq[16 * c + l], sq8_row_f(((hi ? wy : wx) >> sh) & 0xffu, tab[16 * c + l]));
+                step(xq[16 * c + 8 + l], sq8_row_f(((hi ? ww : wz) >> sh) & 0xffu, tab[16 * c + 8 + l]));
+            }
+        } else if ((d & 3) == 0) {   // (uniform)
+            const uint32_t* __restrict__ v1 = reinterpret_cast<const uint32_t*>(v);
+            for (int i = l; i < d8; i += 8) step(xq[i], sq8_row_f((v1[i >> 2] >> sh) & 0xffu, tab[i]));
+        } else {
+            for (int i = l; i < d8; i += 8) step(xq[i], sq8_row_f(v[i], tab[i]));
+        }
+    }
+    float s = __shfl_down(a, 4, 8) + a;   // s[l] = acc[l+4] + acc[l] for l < 4
+    int rem = d - d8, i = d8;
+    if (live && rem >= 4) {
+        if (l < 4) {
+            const float y = sq8_row_f(v[i + l], tab[i + l]);
+            if (L2) {
+                const float t = xq[i + l] - y;
+                s = __builtin_fmaf(t, t, s);
+            } else {
+                s = __builtin_fmaf(xq[i + l], y, s);
+            }
+        }
+        i += 4;
+        rem -= 4;
+    }
+    if (live && l < rem) {
+        const float y = sq8_row_f(v[i + l], tab[i + l]);
+        if (L2) {
+            const float t = xq[i + l] - y;
+            s = __builtin_fmaf(t, t, s);
+        } else {
+            s = __builtin_fmaf(xq[i + l], y, s);
+        }
+    }
+    const float t01 = s + __shfl_down(s, 1, 8);
+    return t01 + __shfl_down(t01, 2, 8);
+}
+
 }  // namespace gh

@@ -211,6 +211,82 @@ void launch_raw_rows_to_bytes(hipStream_t s, const float* stage, const int64_t* 
     }
 }
 
+// scalar-quantised raw store (gamma_hip_raw_init_sq8): the staged fp32 rows -- finite, the host checked every value -- encoded into
+// rows first + i, or vids[i] (a vid outside [0, nrows) is skipped; rows >= nrows are never written).  enc[j] = {inv[j], vmin[j]}.
+// The code of a value: a subtract, a multiply, a round-half-to-even and a clamp, each rounded in fp32 (no fma: the __f*_rn
+// intrinsics never contract); inv == 0 marks a constant dimension, code 0.  QUAD (d % 4 == 0, rows dword-aligned): four codes per
+// dword store; otherwise byte stores.
+__device__ __forceinline__ uint32_t sq8_encode(float x, const float2 e) {
+    const float r = fminf(fmaxf(rintf(__fmul_rn(__fsub_rn(x, e.y), e.x)), 0.0f), 255.0f);
+    return e.x == 0.0f ? 0u : (uint32_t)r;
+}
+template <bool QUAD>
+__global__ __launch_bounds__(256) void k_raw_rows_to_sq8(const float* __restrict__ stage, const int64_t* __restrict__ vids, int64_t first,
+                                                         int64_t n, int d, const float2* __restrict__ enc, uint8_t* __restrict__ raw,
+                                                         int64_t nrows) {
+    const int dv = QUAD ? d >> 2 : d;
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n * dv) return;
+    const int64_t i = t / dv;
+    const int c = (int)(t - i * dv);
+    const int64_t row = vids ? vids[i] : first + i;
+    if (row < 0 || row >= nrows) return;
+    if (QUAD) {
+        const float4 f = reinterpret_cast<const float4*>(stage)[t];   // (d % 4 == 0: element quads never straddle rows)
+        const uint32_t b0 = sq8_encode(f.x, enc[4 * c]), b1 = sq8_encode(f.y, enc[4 * c + 1]), b2 = sq8_encode(f.z, enc[4 * c + 2]),
+                       b3 = sq8_encode(f.w, enc[4 * c + 3]);
+        reinterpret_cast<uint32_t*>(raw)[row * dv + c] = b0 | (b1 << 8) | (b2 << 16) | (b3 << 24);
+    } else {
+        raw[row * d + c] = (uint8_t)sq8_encode(stage[t], enc[c]);
+    }
+}
+void launch_raw_rows_to_sq8(hipStream_t s, const float* stage, const int64_t* vids, int64_t first, int64_t n, int d, const float* enc,
+                            uint8_t* raw, int64_t nrows) {
+    if (n <= 0 || d <= 0 || nrows <= 0) return;
+    const float2* e = reinterpret_cast<const float2*>(enc);
+    if ((d & 3) == 0) {
+        const int64_t tot = n * (d >> 2);
+        hipLaunchKernelGGL((k_raw_rows_to_sq8<true>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, stage, vids, first, n, d, e, raw, nrows);
+    } else {
+        const int64_t tot = n * d;
+        hipLaunchKernelGGL((k_raw_rows_to_sq8<false>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, stage, vids, first, n, d, e, raw, nrows);
+    }
+}
+
+// Per-dimension minimum and maximum of n staged rows (gamma_hip_raw_sq8_train), every value finite.  Workgroup b owns the 64
+// dimensions 64 b ..: thread (ty, tx) folds rows ty, ty + 4, .. of dimension 64 b + tx (a wave reads 256 consecutive bytes of a
+// row), the four partial results meet in LDS, and the result replaces mm (first) or is folded into it: mm[j] = minimum,
+// mm[d + j] = maximum.  Minimum and maximum are exact in any order.
+__global__ __launch_bounds__(256) void k_sq8_minmax(const float* __restrict__ x, int64_t n, int d, float* __restrict__ mm, int first) {
+    __shared__ float s_lo[4][64], s_hi[4][64];
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const int j = blockIdx.x * 64 + tx;
+    float lo = INFINITY, hi = -INFINITY;
+    if (j < d)
+        for (int64_t r = ty; r < n; r += 4) {
+            const float v = x[r * d + j];
+            lo = fminf(lo, v);
+            hi = fmaxf(hi, v);
+        }
+    s_lo[ty][tx] = lo;
+    s_hi[ty][tx] = hi;
+    __syncthreads();
+    if (ty == 0 && j < d) {
+        lo = fminf(fminf(s_lo[0][tx], s_lo[1][tx]), fminf(s_lo[2][tx], s_lo[3][tx]));
+        hi = fmaxf(fmaxf(s_hi[0][tx], s_hi[1][tx]), fmaxf(s_hi[2][tx], s_hi[3][tx]));
+        if (!first) {
+            lo = fminf(lo, mm[j]);
+            hi = fmaxf(hi, mm[d + j]);
+        }
+        mm[j] = lo;
+        mm[d + j] = hi;
+    }
+}
+void launch_sq8_minmax(hipStream_t s, const float* x, int64_t n, int d, float* mm, bool first) {
+    if (n <= 0 || d <= 0) return;
+    hipLaunchKernelGGL(k_sq8_minmax, dim3((unsigned)((d + 63) / 64)), dim3(256), 0, s, x, n, d, mm, first ? 1 : 0);
+}
+
 // Arena repack (gamma_hip_store.cpp, arena_repack): every list's live entries move from (old arrays, old offset)
 // to (new arrays, new offset).  grid = (nlist, chunks); the code bytes move as dwords when M % 4 == 0.
 __global__ __launch_bounds__(256) void k_repack_lists(const uint8_t* __restrict__ oc, const int64_t* __restrict__ oi,

@@ -61,6 +61,7 @@ __device__ __forceinline__ TieLds tie_carve(char* p, int R, int k, int P, int sl
 // of 64, <= 1024); `lds` = tie_replay_lds_bytes_(R, k, P, SLAB) bytes, 16-byte aligned, free for this call.
 // HALF: the raw rows are IEEE binary16 (a.raw_h; gamma_hip_raw_init_f16) -- only the row reads of the exact distances differ.
 // BYTE: 1 = rows of uint8, 2 = rows of int8 (a.raw_b; gamma_hip_raw_init_i8), likewise.
+// BYTE: 3 = scalar-quantised rows (a.raw_q decoded through a.sq8_tab; gamma_hip_raw_init_sq8), likewise.
 template <bool L2, int NT, int SLAB = TR_SLAB, int STG = TR_STAGE, int MAXK = TR_MAXK, bool HALF = false, int BYTE = 0>
 __device__ __forceinline__ void tie_replay_query(const TieReplayArgs& a, int q, char* lds, unsigned long long* dbg,
                                                  int slab_row = -1) {
@@ -252,6 +253,8 @@ __device__ __forceinline__ void tie_replay_query(const TieReplayArgs& a, int q, 
                 }
             } else if constexpr (HALF) {
                 dis = rerank_dist8<L2>(xq, a.raw_h + (live ? id : 0) * a.d, a.d, l8, live);
+            } else if constexpr (BYTE == 3) {
+                dis = rerank_dist8_sq8<L2>(xq, a.raw_q + (live ? id : 0) * a.d, reinterpret_cast<const float2*>(a.sq8_tab), a.d, l8, live);
             } else if constexpr (BYTE != 0) {
                 dis = rerank_dist8_bytes<L2, BYTE == 2>(xq, a.raw_b + (live ? id : 0) * a.d, a.d, l8, live);
             } else {

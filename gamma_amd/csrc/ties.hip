@@ -55,7 +55,7 @@ __global__ __launch_bounds__(256) void k_tie_replay(TieReplayArgs a) {
                                                              a.compact_rows ? fi : -1);
 }
 
-// float16 (HALF) and byte (BYTE = 1 uint8, 2 int8) raw stores, the IVFPQ replay of stage B: the same three kernels as for fp32 rows
+// float16 (HALF), byte (BYTE = 1 uint8, 2 int8) and scalar-quantised (BYTE = 3) raw stores, the IVFPQ replay of stage B: the same three kernels as for fp32 rows
 // with the row reads of that store
 template <bool HALF, int BYTE>
 static void launch_tie_replay_narrow(hipStream_t s, bool l2, const TieReplayArgs& a, int grid) {
@@ -105,6 +105,10 @@ void launch_tie_replay(hipStream_t s, bool l2, const TieReplayArgs& a0) {
     const int grid = std::min(a.nq, 1024);
     if (a.slice_cap > 2048) {   // callers gate on this
         launch_refused("launch_tie_replay: survivor slices of more than 2048 items");
+        return;
+    }
+    if (a.raw_q) {
+        launch_tie_replay_narrow<false, 3>(s, l2, a, grid);
         return;
     }
     if (a.raw_b) {

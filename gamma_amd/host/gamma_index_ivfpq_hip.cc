@@ -101,14 +101,15 @@ int HIPIVFPQModelParams::Parse(const char *str) {
     raw_sharded = !strcasecmp("sharded", rpl.c_str());
   }
   std::string rdt;
-  if (!jp.GetString("raw_dtype", rdt)) {   // the device's raw rows: "float32" (the default) | "float16" | "uint8" | "int8"
+  if (!jp.GetString("raw_dtype", rdt)) {   // the device's raw rows: "float32" (the default) | "float16" | "uint8" | "int8" | "sq8"
     if (strcasecmp("float32", rdt.c_str()) && strcasecmp("float16", rdt.c_str()) && strcasecmp("uint8", rdt.c_str()) &&
-        strcasecmp("int8", rdt.c_str())) {
+        strcasecmp("int8", rdt.c_str()) && strcasecmp("sq8", rdt.c_str())) {
       HLOG("invalid raw_dtype = %s", rdt.c_str());
       return -1;
     }
     raw_f16 = !strcasecmp("float16", rdt.c_str());
     raw_i8 = !strcasecmp("uint8", rdt.c_str()) ? 1 : !strcasecmp("int8", rdt.c_str()) ? 2 : 0;
+    raw_sq8 = !strcasecmp("sq8", rdt.c_str());
   }
   if (!jp.GetInt("bucket_init_size", v)) {
     if (v < -1) return -1;
@@ -198,6 +199,18 @@ int RegisterHIPRawI8(const HIPRawI8Ops *ops) {
   return 0;
 }
 const HIPRawI8Ops *FindHIPRawI8() { return RawI8Ops(); }
+
+namespace {
+const HIPRawSq8Ops *&RawSq8Ops() {
+  static const HIPRawSq8Ops *ops = nullptr;
+  return ops;
+}
+}  // namespace
+int RegisterHIPRawSq8(const HIPRawSq8Ops *ops) {
+  RawSq8Ops() = ops;
+  return 0;
+}
+const HIPRawSq8Ops *FindHIPRawSq8() { return RawSq8Ops(); }
 
 int RegisterHIPListsInit(int nbits, HIPListsInitFn fn) {
   ListsInits().push_back({nbits, fn});
@@ -314,12 +327,19 @@ int GammaIVFPQHIPIndex::Init(const std::string &model_parameters, int indexing_s
   }
   raw_i8_ = pa.raw_i8;
   raw_i8_ops_ = raw_i8_ops;
+  const HIPRawSq8Ops *raw_sq8_ops = pa.raw_sq8 ? FindHIPRawSq8() : nullptr;
+  if (pa.raw_sq8 && (!raw_sq8_ops || pa.devices.size() > 1)) {
+    HLOG("raw_dtype = sq8 %s", raw_sq8_ops ? "with several devices is not supported (the group's members hold fp32 rows)"
+                                           : "is not supported by this build of the plugin (it carries no sq8 raw store)");
+    return -2;
+  }
+  raw_sq8_ops_ = raw_sq8_ops;
   if (OpenDevices(pa.devices, pa.replicate)) return -1;
   int rc = ForAll([&](gamma_hip_index *m) {
     const int metric = metric_type_ == DistanceComputeType::L2 ? GAMMA_HIP_METRIC_L2 : GAMMA_HIP_METRIC_IP;
     int r = lists_init ? lists_init(m, d_, nlist_, M_, metric, pa.bucket_init_size, pa.bucket_max_size)
                        : gamma_hip_ivfpq_init(m, d_, nlist_, M_, 8, metric, pa.bucket_init_size, pa.bucket_max_size);
-    if (!r) r = raw_i8_ops ? raw_i8_ops->init(m, d_, pa.raw_i8 == 2) : raw_init_f16 ? raw_init_f16(m, d_) : gamma_hip_raw_init(m, d_);
+    if (!r) r = raw_sq8_ops ? raw_sq8_ops->init(m, d_) : raw_i8_ops ? raw_i8_ops->init(m, d_, pa.raw_i8 == 2) : raw_init_f16 ? raw_init_f16(m, d_) : gamma_hip_raw_init(m, d_);
     if (!r) r = gamma_hip_set_exact_ties(m, pa.exact_ties ? 1 : 0);
     if (!r && pa.perf_stages) r = gamma_hip_profile_enable(m, 1);
     return r;
@@ -383,6 +403,15 @@ int GammaIVFPQHIPIndex::Indexing() {
   size_t num = 0;
   if (TrainingSet(xt, num)) return -1;
   int rc = 0;
+  if (raw_sq8_ops_) {
+    // "raw_dtype": "sq8": the store's ranges from the training rows (as the engine holds them: the store keeps the caller's rows,
+    // not the rotated ones), before any row is mirrored -- a narrow store's mirror is written from Add on
+    rc = raw_sq8_ops_->train(h_, (int64_t)num, xt.data());
+    if (rc) {
+      HLOG("sq8 range training failed: %s (%s)", gamma_hip_strerror(rc), gamma_hip_last_error(h_));
+      return -1;
+    }
+  }
   if (opq_) {   // gamma_index_ivfpq.cc:336-346: train the rotation, then everything else on the rotated set
     opq_A_.resize((size_t)d_ * d_);
     std::vector<float> rot(xt.size());
@@ -463,6 +492,13 @@ bool HIPRowsStorableI8(const HIPRawI8Ops *ops, bool is_signed, int d, const char
 }
 
 bool GammaIVFPQHIPIndex::RowsStorable(const char *what, const float *x, int64_t nrows) {
+  if (raw_sq8_ops_) {
+    int64_t bad = -1;
+    if (!raw_sq8_ops_->check(x, nrows * d_, &bad)) return true;
+    fprintf(stderr, "[HIPIVFPQ] %s refused: raw_dtype = sq8 stores a value only if it is finite, and element %d of row %lld is %g\n",
+            what, (int)(bad % d_), (long long)(bad / d_), (double)x[bad]);
+    return false;
+  }
   return !raw_i8_ || HIPRowsStorableI8(raw_i8_ops_, raw_i8_ == 2, d_, "HIPIVFPQ", what, x, nrows);
 }
 
@@ -580,6 +616,10 @@ int GammaIVFPQHIPIndex::Search(RetrievalContext *retrieval_context, int n, const
   if (((cond && cond->brute_force_search) || !is_trained_) && raw_i8_) {
     HLOG("brute_force_search (and the search of an untrained model) is not available with raw_dtype = %s",
          raw_i8_ == 2 ? "int8" : "uint8");
+    return -3;
+  }
+  if (((cond && cond->brute_force_search) || !is_trained_) && raw_sq8_ops_) {
+    HLOG("brute_force_search (and the search of an untrained model) is not available with raw_dtype = sq8");
     return -3;
   }
   if (((cond && cond->brute_force_search) || !is_trained_) && rawshard_) {
@@ -825,6 +865,58 @@ int GammaIVFPQHIPIndex::Dump(const std::string &dir) {
     HLOG("write error, index dir=%s", index_dir.c_str());
     return -1;
   }
+  if (raw_sq8_ops_ && DumpSq8Ranges(index_dir)) return -1;   // a side file: ivfpq.index stays what the reference writes
+  return 0;
+}
+
+// raw_sq8.ranges: magic "SQ8R", int32 d, d floats vmin, d floats vmax
+namespace {
+const char kSq8RangesMagic[4] = {'S', 'Q', '8', 'R'};
+}
+int GammaIVFPQHIPIndex::DumpSq8Ranges(const std::string &index_dir) {
+  std::vector<float> r((size_t)d_ * 2);
+  if (raw_sq8_ops_->get_ranges(h_, r.data(), r.data() + d_)) {
+    HLOG("cannot read the sq8 ranges: %s", gamma_hip_last_error(h_));
+    return -1;
+  }
+  const std::string path = index_dir + "/raw_sq8.ranges";
+  FILE *fp = fopen(path.c_str(), "wb");
+  const int32_t d32 = d_;
+  const bool ok = fp && fwrite(kSq8RangesMagic, 1, 4, fp) == 4 && fwrite(&d32, sizeof(d32), 1, fp) == 1 &&
+                  fwrite(r.data(), sizeof(float), r.size(), fp) == r.size();
+  if ((fp && fclose(fp)) || !ok) {
+    HLOG("write error, %s", path.c_str());
+    return -1;
+  }
+  return 0;
+}
+
+int GammaIVFPQHIPIndex::Sq8Ranges(float *vmin, float *vmax) {
+  if (!raw_sq8_ops_) return -1;
+  return raw_sq8_ops_->get_ranges(h_, vmin, vmax) ? 0 : 1;
+}
+
+int GammaIVFPQHIPIndex::LoadSq8Ranges(const std::string &index_dir) {
+  const std::string path = index_dir + "/raw_sq8.ranges";
+  FILE *fp = fopen(path.c_str(), "rb");
+  if (!fp) {
+    HLOG("raw_dtype = sq8 needs %s beside ivfpq.index (the ranges the rows were encoded with), and it is missing", path.c_str());
+    return -1;
+  }
+  char magic[4] = {0, 0, 0, 0};
+  int32_t d32 = 0;
+  std::vector<float> r((size_t)d_ * 2);
+  const bool head = fread(magic, 1, 4, fp) == 4 && fread(&d32, sizeof(d32), 1, fp) == 1;
+  const bool ok = head && !memcmp(magic, kSq8RangesMagic, 4) && d32 == d_ && fread(r.data(), sizeof(float), r.size(), fp) == r.size();
+  fclose(fp);
+  if (!ok) {
+    HLOG("%s is not the sq8 ranges of a %d-dimensional model (bad magic, another dimension or a short file)", path.c_str(), d_);
+    return -1;
+  }
+  if (raw_sq8_ops_->set_ranges(h_, r.data(), r.data() + d_)) {
+    HLOG("cannot set the sq8 ranges: %s", gamma_hip_last_error(h_));
+    return -1;
+  }
   return 0;
 }
 
@@ -852,6 +944,8 @@ int GammaIVFPQHIPIndex::Load(const std::string &dir) {
          opq_ ? "names" : "does not name");
     return -1;
   }
+  // "raw_dtype": "sq8": the ranges come back before anything of the model changes and before the mirror is re-encoded below
+  if (raw_sq8_ops_ && LoadSq8Ranges(dir + "/" + vector_->MetaInfo()->AbsoluteName())) return -1;
   if (opq_) {   // read_opq (gamma_index_ivfpq.cc:1017-1019): on the handle before the lists are filled
     if (opq_->set(h_, f.opq.data())) {
       HLOG("cannot set the opq matrix: %s", gamma_hip_last_error(h_));

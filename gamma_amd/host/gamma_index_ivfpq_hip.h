@@ -86,6 +86,18 @@ const HIPRawI8Ops *FindHIPRawI8();
 // exactly; otherwise one log line "[model] what refused: ..." naming row, element and value, and false -- before anything changes.
 bool HIPRowsStorableI8(const HIPRawI8Ops *ops, bool is_signed, int d, const char *model, const char *what, const float *x,
                        int64_t nrows);
+// "raw_dtype": "sq8": the scalar-quantised store's entries of the C ABI -- its initialiser, the ranges (set / get / train) and the
+// writers' acceptance predicate -- registered the same way by gamma_index_ivfpq_rawsq8_hip.cc, the only host file that names
+// them.  Without that file Init rejects the value.
+struct HIPRawSq8Ops {
+  int (*init)(gamma_hip_index *h, int d);
+  int (*set_ranges)(gamma_hip_index *h, const float *vmin, const float *vmax);
+  int (*get_ranges)(gamma_hip_index *h, float *vmin, float *vmax);
+  int (*train)(gamma_hip_index *h, int64_t n, const float *x);
+  int (*check)(const float *x, int64_t n, int64_t *first_bad);
+};
+int RegisterHIPRawSq8(const HIPRawSq8Ops *ops);
+const HIPRawSq8Ops *FindHIPRawSq8();
 
 // The "raw_dtype" key of the HIPFLAT and HIPIVFFLAT models' parameters: *et = 0 float32 (also: no key), 1 float16, 2 uint8, 3 int8,
 // case-insensitive; any other string: one log line "[model] invalid raw_dtype = ..." and -1.
@@ -135,6 +147,8 @@ struct HIPIVFPQModelParams {
                                  // binary16, rounded from the engine's fp32 on upload; "float32" (default).  One device only.
   int raw_i8 = 0;                // HIP only: "raw_dtype": "uint8" (1) | "int8" (2) -- the device's raw rows are one byte per
                                  // element; a row that does not convert exactly is refused by Add / Update.  One device only.
+  bool raw_sq8 = false;          // HIP only: "raw_dtype": "sq8" -- the device's raw rows are one scalar-quantised byte per element
+                                 // (lossy; ranges = per-dimension minimum / maximum of the training rows).  One device only.
   int Parse(const char *str);   // 0 ok, -1 bad (same rules as gamma_index_ivfpq.h:708-851)
 };
 
@@ -158,6 +172,7 @@ class GammaIVFPQHIPIndex : public RetrievalModel {
   int SetTrained(const float *coarse_centroids, const float *pq_centroids);
 
   // exposed for the harness / tests
+  int Sq8Ranges(float *vmin, float *vmax);   // "raw_dtype": "sq8": the store's ranges, d floats each; 1 has them, 0 not, -1 no sq8 model
   bool is_trained_ = false;
   int d_ = 0, nlist_ = 0, M_ = 0, nprobe_ = 80;
   DistanceComputeType metric_type_ = DistanceComputeType::INNER_PRODUCT;
@@ -207,7 +222,12 @@ class GammaIVFPQHIPIndex : public RetrievalModel {
   bool raw_f16_ = false;               // "raw_dtype": "float16": no device holds fp32 rows -- brute-force search is refused
   int raw_i8_ = 0;                     // "raw_dtype": "uint8" (1) | "int8" (2): likewise
   const HIPRawI8Ops *raw_i8_ops_ = nullptr;
-  bool RowsStorable(const char *what, const float *x, int64_t nrows);   // byte store: one log line for the first refused value
+  bool RowsStorable(const char *what, const float *x, int64_t nrows);   // byte / sq8 store: one log line for the first refused value
+  // "raw_dtype": "sq8": likewise.  The ranges are trained by Indexing() before the first row is mirrored, written by Dump to the
+  // side file raw_sq8.ranges beside ivfpq.index and set again by Load before the mirror is re-encoded.
+  const HIPRawSq8Ops *raw_sq8_ops_ = nullptr;
+  int DumpSq8Ranges(const std::string &index_dir);
+  int LoadSq8Ranges(const std::string &index_dir);
   bool rows_sharded_ = false;          // under raw_mu_
   // nbits_per_idx: 8, or 4 (16 centroids per sub-quantizer, two indices per code byte as faiss's PQEncoderGeneric packs them)
   int nbits_ = 8;

@@ -366,6 +366,11 @@ int gh_host_ivfpq_opq(void *hp, float *A) {
   if (A) memcpy(A, m->opq_A_.data(), sizeof(float) * m->opq_A_.size());
   return 1;
 }
+// the ranges of a HIPIVFPQ model created with "raw_dtype": "sq8": d floats each; 1 when it has them, 0 when not yet, -1 otherwise
+int gh_host_ivfpq_sq8_ranges(void *hp, float *vmin, float *vmax) {
+  GammaIVFPQHIPIndex *m = dynamic_cast<GammaIVFPQHIPIndex *>(((Host *)hp)->model);
+  return m ? m->Sq8Ranges(vmin, vmax) : -1;
+}
 // IwPQ files with and without the "LTra" record (host only): `in` rewritten to `out` with the record holding A (n floats) or,
 // A == NULL, without one; and the record of a file: its float count (0: none), A_out filled up to cap floats; < 0: ReadIwPQ's
 int gh_iwpq_rewrite_opq(const char *in, const char *out, const float *A, int64_t n) {
@@ -405,11 +410,11 @@ void gh_parse_ivfpq_model_params(const char *str, int *out) {
   out[9] = p.has_opq;
 }
 // the HIP-only "raw_dtype" key of HIPIVFPQModelParams::Parse: out = {rc, 0 for "float32" and the default / 1 for "float16" /
-// 2 for "uint8" / 3 for "int8"}
+// 2 for "uint8" / 3 for "int8" / 4 for "sq8"}
 void gh_parse_ivfpq_raw_dtype(const char *str, int *out) {
   HIPIVFPQModelParams p;
   out[0] = p.Parse(str);
-  out[1] = p.raw_i8 ? 1 + p.raw_i8 : p.raw_f16 ? 1 : 0;
+  out[1] = p.raw_sq8 ? 4 : p.raw_i8 ? 1 + p.raw_i8 : p.raw_f16 ? 1 : 0;
 }
 // the HIP-only "raw_dtype" key of the HIPFLAT model's parameters: out = {rc, element type as above}
 void gh_parse_flat_raw_dtype(const char *str, int *out) {

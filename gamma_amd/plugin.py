@@ -50,6 +50,7 @@ HOST_SYMBOLS = {
     "gh_host_ivfpq_state": (C.c_int, [C.c_void_p, f32p, f32p]),
     "gh_host_ivfpq_set_trained": (C.c_int, [C.c_void_p, f32p, f32p]),
     "gh_host_ivfpq_opq": (C.c_int, [C.c_void_p, f32p]),
+    "gh_host_ivfpq_sq8_ranges": (C.c_int, [C.c_void_p, f32p, f32p]),
     "gh_iwpq_rewrite_opq": (C.c_int, [C.c_char_p, C.c_char_p, f32p, C.c_int64]),
     "gh_iwpq_read_opq": (C.c_int64, [C.c_char_p, f32p, C.c_int64]),
     "gh_parse_ivfpq_model_params": (None, [C.c_char_p, C.POINTER(C.c_int)]),
@@ -115,10 +116,10 @@ def parse_model_params(s):
 
 
 def parse_raw_dtype(s):
-    """(rc of HIPIVFPQModelParams::Parse, "float32", "float16", "uint8" or "int8") for the model parameters s"""
+    """(rc of HIPIVFPQModelParams::Parse, "float32", "float16", "uint8", "int8" or "sq8") for the model parameters s"""
     out = (C.c_int * 2)()
     load_host().gh_parse_ivfpq_raw_dtype(s.encode(), out)
-    return int(out[0]), ("float32", "float16", "uint8", "int8")[out[1]]
+    return int(out[0]), ("float32", "float16", "uint8", "int8", "sq8")[out[1]]
 
 
 def parse_flat_raw_dtype(s):
@@ -378,6 +379,11 @@ class PluginModel:
         """the rotation of a model created with "opq" (after Indexing or Load), or None"""
         A = np.empty((self.d, self.d), np.float32)
         return A if self.L.gh_host_ivfpq_opq(self.h, _f(A)) == 1 else None
+
+    def sq8_ranges(self):
+        """(vmin, vmax) of a model created with "raw_dtype": "sq8" (after Indexing or Load), or None"""
+        vmin, vmax = np.empty(self.d, np.float32), np.empty(self.d, np.float32)
+        return (vmin, vmax) if self.L.gh_host_ivfpq_sq8_ranges(self.h, _f(vmin), _f(vmax)) == 1 else None
 
 
 def iwpq_rewrite_opq(path_in, path_out, A=None):

@@ -282,7 +282,7 @@ int gamma_hip_raw_stats(gamma_hip_index* h, int64_t* out4);
  * GAMMA_HIP_EUNSUPPORTED: gamma_hip_raw_put / _raw_drop, flat and IVFFLAT search, gamma_hip_ivfpq_shard_exact /
  * _shard_export_exact, _merge_rerank / _merge_replay with has_rank and no travelled distances. */
 int gamma_hip_raw_init_f16(gamma_hip_index* h, int d);
-/* bytes of one element of the raw store: 4 (gamma_hip_raw_init), 2 (gamma_hip_raw_init_f16), 1 (gamma_hip_raw_init_i8), 0 before
+/* bytes of one element of the raw store: 4 (gamma_hip_raw_init), 2 (gamma_hip_raw_init_f16), 1 (gamma_hip_raw_init_i8, gamma_hip_raw_init_sq8), 0 before
  * any of them */
 int gamma_hip_raw_elem_bytes(gamma_hip_index* h);
 /* A store of one byte per element: uint8 rows, range [0, 255] (is_signed = 0), or int8 rows, range [-128, 127] (is_signed = 1) --
@@ -299,12 +299,44 @@ int gamma_hip_raw_elem_bytes(gamma_hip_index* h);
  * search, gamma_hip_ivfpq_shard_exact / _shard_export_exact, _merge_rerank / _merge_replay with has_rank and no travelled
  * distances. */
 int gamma_hip_raw_init_i8(gamma_hip_index* h, int d, int is_signed);
-/* element type of the raw store: 0 fp32 (also before any init), 1 float16, 2 uint8, 3 int8 */
+/* element type of the raw store: 0 fp32 (also before any init), 1 float16, 2 uint8, 3 int8, 4 sq8 (gamma_hip_raw_init_sq8) */
 int gamma_hip_raw_elem_type(gamma_hip_index* h);
 /* The byte store's acceptance predicate, as the writers apply it: GAMMA_HIP_OK when every one of the n values is storable in
  * uint8 (is_signed = 0) or int8 (is_signed = 1); otherwise GAMMA_HIP_EINVAL, and *first_bad (when not null) is the index of the
  * first value that is refused.  Pure host code: no handle, no device call. */
 int gamma_hip_raw_i8_check(const float* x, int64_t n, int is_signed, int64_t* first_bad);
+/* A SCALAR-QUANTISED store of one byte per element for float data (element type 4, "sq8"): a quarter of the fp32 store's bytes,
+ * and LOSSY.  Per dimension j the store keeps vmin[j] <= vmax[j] (fp32, finite) and, derived on the host in fp32 with one IEEE
+ * operation each (gamma_hip_raw_sq8_params): span = vmax - vmin, step = span / 255, inv = 255 / span; a dimension whose span
+ * is 0 or whose inv is not finite is constant, step = inv = 0.
+ *   encode (the writers, on the device): c = inv[j] == 0 ? 0 : (uint8) min(max(rintf((x - vmin[j]) * inv[j]), 0), 255) -- a
+ *            subtract, a multiply, a round-half-to-even and a clamp, each rounded in fp32, no fma; values outside the range clip;
+ *   decode (the readers):                w = vmin[j] + (float)c * step[j] -- a multiply, then an add, each rounded in fp32.
+ * The exact distance of a has_rank IVFPQ search is fvec_L2sqr / fvec_inner_product of the fp32 query and the DECODED row in the
+ * reference's operation order, so every result, ties included, is what an fp32 store of the decoded rows gives.  Only the store
+ * is quantised: training, assignment, residuals and codes see the caller's fp32.  The writers (raw_append / raw_write /
+ * raw_update / raw_update_batch) take fp32; a non-finite value fails the call with GAMMA_HIP_EINVAL before anything changes, and
+ * so does a writer called with n > 0 before the ranges exist.  gamma_hip_raw_gets returns decoded rows.  The element type is
+ * fixed at the first init.  Served: gamma_hip_ivfpq_search and its device-pointer forms (8-bit, 4-bit, OPQ handles).
+ * GAMMA_HIP_EUNSUPPORTED: gamma_hip_raw_put / _raw_drop, flat and IVFFLAT search (whatever gamma_hip_set_flat_narrow_rows /
+ * _set_ivfflat_narrow_rows say), gamma_hip_ivfpq_shard_exact / _shard_export_exact, _merge_rerank / _merge_replay with has_rank
+ * and no travelled distances. */
+int gamma_hip_raw_init_sq8(gamma_hip_index* h, int d);
+/* The ranges of an sq8 store: d floats each.  set is allowed only while the store holds no row (after the init, or after
+ * gamma_hip_raw_clear, which keeps the ranges); otherwise, and for a non-finite bound, vmin > vmax or a span that is not
+ * finite, GAMMA_HIP_EINVAL.  get answers GAMMA_HIP_EINVAL before any ranges exist. */
+int gamma_hip_raw_sq8_set_ranges(gamma_hip_index* h, const float* vmin, const float* vmax);
+int gamma_hip_raw_sq8_get_ranges(gamma_hip_index* h, float* vmin, float* vmax);
+/* sets the ranges to the per-dimension minimum and maximum of n host rows (n > 0, every value finite), reduced on the device;
+ * minimum and maximum do not depend on the order of the reduction, so the result is exact (a zero comes back as +0.0) */
+int gamma_hip_raw_sq8_train(gamma_hip_index* h, int64_t n, const float* x);
+/* The sq8 store's acceptance predicate, as the writers apply it: GAMMA_HIP_OK when every one of the n values is finite;
+ * otherwise GAMMA_HIP_EINVAL, and *first_bad (when not null) is the index of the first value that is refused.  Pure host code:
+ * no handle, no device call. */
+int gamma_hip_raw_sq8_check(const float* x, int64_t n, int64_t* first_bad);
+/* step_out[j], inv_out[j] of the ranges, by the derivation above (either output may be null).  GAMMA_HIP_EINVAL for a
+ * non-finite bound, vmin > vmax or a span that is not finite.  Pure host code. */
+int gamma_hip_raw_sq8_params(int d, const float* vmin, const float* vmax, float* step_out, float* inv_out);
 
 /* ---- delete bitmap (bitmap::BitmapManager, util/bitmap_manager.cc:171-192): bit = docid,
  *      byte docid>>3, mask 1<<(docid&7) --------------------------------------------------- */
