@@ -118,6 +118,14 @@ SYMBOLS = {
     "gamma_hip_binivf_search_device": (C.c_int, [C.c_void_p, C.POINTER(SearchParams), C.c_int, C.c_void_p, C.c_int,
                                                  C.c_void_p, C.c_void_p]),
     "gamma_hip_binivf_stats": (C.c_int, [C.c_void_p, i64p, C.c_int]),
+    "gamma_hip_binflat_init": (C.c_int, [C.c_void_p, C.c_int]),
+    "gamma_hip_binflat_append": (C.c_int, [C.c_void_p, C.c_int64, u8p]),
+    "gamma_hip_binflat_count": (C.c_int64, [C.c_void_p]),
+    "gamma_hip_binflat_search": (C.c_int, [C.c_void_p, C.POINTER(SearchParams), C.c_int, u8p, C.c_int, f32p, i64p]),
+    "gamma_hip_binflat_search_device": (C.c_int, [C.c_void_p, C.POINTER(SearchParams), C.c_int, C.c_void_p, C.c_int,
+                                                  C.c_void_p, C.c_void_p]),
+    "gamma_hip_binflat_chunk_rows": (C.c_int, []),
+    "gamma_hip_binflat_stats": (C.c_int, [C.c_void_p, i64p, C.c_int]),
     "gamma_hip_ivfflat_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "gamma_hip_ivfflat_set_trained": (C.c_int, [C.c_void_p, f32p]),
     "gamma_hip_ivfflat_search": (C.c_int, [C.c_void_p, C.POINTER(SearchParams), C.c_int, f32p, C.c_int, f32p, i64p]),

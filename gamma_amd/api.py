@@ -532,6 +532,39 @@ class GammaHip:
         self._ck(self.L.gamma_hip_binivf_stats(self.h, _p(out, _lib.i64p), 1 if reset else 0), "binivf_stats")
         return int(out[0]), int(out[1])
 
+    # ---- exact Hamming (binary flat) search: faiss:IndexBinaryFlat.cpp / utils/hamming.cpp:230-265, answered as
+    #      GammaIVFBinaryScannerL2::scan_codes answers one list holding every code in vid order ----
+    def binflat_init(self, nbits):
+        self._ck(self.L.gamma_hip_binflat_init(self.h, nbits), "binflat_init")
+
+    def binflat_append(self, codes):
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        self._ck(self.L.gamma_hip_binflat_append(self.h, codes.shape[0], _p(codes, _lib.u8p)), "binflat_append")
+
+    def binflat_count(self):
+        return int(self.L.gamma_hip_binflat_count(self.h))
+
+    def binflat_chunk_rows(self):
+        return int(self.L.gamma_hip_binflat_chunk_rows())
+
+    def binflat_search(self, x, k, args):
+        x = np.ascontiguousarray(x, dtype=np.uint8)
+        nq = x.shape[0]
+        D = np.empty((nq, max(k, 0)), dtype=np.float32)
+        I = np.empty((nq, max(k, 0)), dtype=np.int64)
+        self._ck(self.L.gamma_hip_binflat_search(self.h, args.ref(), nq, _p(x, _lib.u8p), k, _p(D, _lib.f32p),
+                                                 _p(I, _lib.i64p)), "binflat_search")
+        return D, I
+
+    def binflat_search_device(self, d_x, nq, k, args, d_D, d_I):
+        self._ck(self.L.gamma_hip_binflat_search_device(self.h, args.ref(), nq, d_x, k, d_D, d_I), "binflat_search_device")
+
+    def binflat_stats(self, reset=False):
+        """(queries searched, candidates collected, heap admissions, query sub-batches)"""
+        out = np.zeros(4, dtype=np.int64)
+        self._ck(self.L.gamma_hip_binflat_stats(self.h, _p(out, _lib.i64p), 1 if reset else 0), "binflat_stats")
+        return tuple(int(v) for v in out)
+
     def last_stages(self, nq, nprobe, R):
         cd = np.empty((nq, nprobe), dtype=np.float32)
         ci = np.empty((nq, nprobe), dtype=np.int64)

@@ -137,7 +137,7 @@ int gamma_hip_destroy(gamma_hip_index* h) {
     if (h->d_raw_slot) (void)hipFree(h->d_raw_slot);
     void* ptrs[] = {h->d_list_rank, h->d_raw, h->d_raw_h, h->d_raw_b, h->d_raw_q, h->d_sq8_tab, h->d_bitmap, h->d_cc, h->d_cc_norms, h->d_pqc, h->d_T2, h->d_codes,
                     h->d_ids, h->d_list_mask, h->d_scan_codes, h->d_tie_stats, h->d_v2d, h->d_sums, h->d_t2max, h->d_bound_stat,
-                    h->d_bin_cc, h->d_bin_stats, h->d_cc_img, h->d_cbf_stat, h->d_opq};
+                    h->d_bin_cc, h->d_bin_stats, h->d_bf_codes, h->d_bf_stats, h->d_cc_img, h->d_cbf_stat, h->d_opq};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     for (auto& kv : h->fields)
@@ -162,7 +162,7 @@ int gamma_hip_destroy(gamma_hip_index* h) {
                       &h->w_codes_tmp, &h->w_qperm, &h->w_qbins, &h->w_scnt, &h->w_sflag, &h->w_surv, &h->w_pair_base,
                       &h->w_pair_ip, &h->w_flat_cand, &h->w_flat_meta, &h->w_full_cdis,
                       &h->w_full_probe, &h->w_ftab, &h->w_qfil, &h->w_tieflag, &h->w_tcut, &h->w_tlist, &h->w_lm_units, &h->w_lm_cnt, &h->w_fbits, &h->w_cmp_codes, &h->w_cmp_ids, &h->w_cmp_len, &h->w_cmp_sums, &h->w_fD, &h->w_fI, &h->w_fx, &h->w_fslab, &h->w_flog, &h->w_mr_vals, &h->w_mr_ids, &h->w_mr_meta,
-                      &h->we_mat, &h->we_cdis, &h->we_x, &h->we_assign, &h->we_codes, &h->we_stage, &h->w_xrot, &h->we_xrot};
+                      &h->we_mat, &h->we_cdis, &h->we_x, &h->we_assign, &h->we_codes, &h->we_stage, &h->w_xrot, &h->we_xrot, &h->w_bf_hist, &h->w_bf_meta, &h->w_bf_cand};
     for (DevBuf* b : bufs) b->release();
     (void)hipStreamDestroy(h->stream);
     (void)hipStreamDestroy(h->wstream);
@@ -336,6 +336,7 @@ int64_t gamma_hip_total_mem_bytes(gamma_hip_index* h) {
     b += (int64_t)h->bitmap_cap_bytes;
     for (auto& kv : h->fields) b += kv.second.cap * (int64_t)field_elem_size(kv.second.dtype);
     for (auto& kv : h->terms) b += kv.second.cap_docs * 8 + kv.second.cap_tok * 4;
+    b += h->bf_cap * (int64_t)h->bf_cs;   // the binary flat store
     if (h->ivf_init) {
         b += (int64_t)h->nlist * h->d * 4 + (int64_t)h->nlist * 4 + (int64_t)h->M * 256 * h->dsub * 4;
         if (h->d_T2) b += h->ivfflat ? 256 : (int64_t)h->nlist * h->M * 256 * 4;

@@ -337,7 +337,7 @@ struct gamma_hip_index {
     DevBuf w_mat, w_coarse_dis, w_probe, w_xn, w_st2, w_pair_off, w_qtotal, w_dist, w_cand_dis,
             w_cand_pos, w_cand_ids, w_exact, w_selv, w_selp, w_x, w_outd, w_outl, w_stage, w_shard_cut, w_filter,
             w_m_dis, w_m_ids, w_part_v, w_part_i, w_assign, w_codes_tmp, w_qperm, w_qbins, w_scnt, w_sflag, w_surv, w_pair_base, w_q8, w_q8meta, w_q8cand, w_q8int,
-            w_pair_ip, w_flat_cand, w_flat_meta, w_full_cdis, w_full_probe, w_ftab, w_qfil, w_tieflag, w_tcut, w_tlist, w_textra, w_fq, w_fraw, w_frcnt, w_lm_units, w_lm_cnt, w_fbits, w_cmp_codes, w_cmp_ids, w_cmp_len, w_cmp_sums, w_fD, w_fI, w_fx, w_fslab, w_flog, w_mr_vals, w_mr_ids, w_mr_meta, w_xrot,
+            w_pair_ip, w_flat_cand, w_flat_meta, w_full_cdis, w_full_probe, w_ftab, w_qfil, w_tieflag, w_tcut, w_tlist, w_textra, w_fq, w_fraw, w_frcnt, w_lm_units, w_lm_cnt, w_fbits, w_cmp_codes, w_cmp_ids, w_cmp_len, w_cmp_sums, w_fD, w_fI, w_fx, w_fslab, w_flog, w_mr_vals, w_mr_ids, w_mr_meta, w_xrot, w_bf_hist, w_bf_meta, w_bf_cand,
             we_mat, we_cdis, we_x, we_assign, we_codes, we_stage, we_chk, we_xrot;   // writer side (encode, bitmap_set): never shared with a search
     unsigned long long* d_scan_codes = nullptr;
     size_t dist_budget_bytes = (size_t)8 << 30;   // per-chunk ADC distance buffer (288 GB of HBM per GPU)
@@ -390,6 +390,16 @@ struct gamma_hip_index {
     bool binivf = false;
     uint8_t* d_bin_cc = nullptr;
     unsigned long long* d_bin_stats = nullptr;
+    // gamma_hip_binflat_init (gamma_hip_binflat.cpp): every code in vid order for the exact Hamming search, rows of bf_cs
+    // bytes; bf_count is published after the rows it counts are in place; {queries, candidates, heap admissions} counters
+    // and the number of query sub-batches (gamma_hip_binflat_stats); host images of a call's candidate totals / segment bases
+    bool bf_init = false;
+    int bf_cs = 0;
+    uint8_t* d_bf_codes = nullptr;
+    int64_t bf_count = 0, bf_cap = 0, bf_subbatches = 0;
+    unsigned long long* d_bf_stats = nullptr;
+    std::vector<uint32_t> bf_tot_h;
+    std::vector<int64_t> bf_base_h;
     int coarse_cap = gh::kCoarseCap;
     unsigned long long* d_tie_stats = nullptr;   // {coarse rows redone, top-R cuts through a tie, queries replayed}
     // what stage A leaves for the tie replay of stage B (ties.hip)

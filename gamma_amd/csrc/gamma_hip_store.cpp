@@ -1575,6 +1575,7 @@ int gamma_hip_binivf_init(gamma_hip_index* h, int nbits, int nlist, int bucket_i
     if (h->ivf_init) return fail(h, GAMMA_HIP_EINVAL, "already initialised");
     if (nbits <= 0 || nbits % 8 != 0 || nbits / 8 > gh::kBinMaxCodeSize || nlist <= 0)
         return fail(h, GAMMA_HIP_EINVAL, "bad nbits / nlist (nbits % 8 == 0, at most 2048 bits)");
+    if (h->bf_init && h->bf_cs != nbits / 8) return fail(h, GAMMA_HIP_EINVAL, "nbits differs from the binary flat store's");
     // the IVFFLAT set-up with M = code_size: code_size bytes per list entry; no float centroids, PQ tables or code sums
     GH_TRY(ivf_init_locked(h, nbits, nlist, nbits / 8, GAMMA_HIP_METRIC_L2, bucket_init_size, bucket_max_size, true, true));
     h->binivf = true;

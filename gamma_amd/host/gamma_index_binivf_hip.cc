@@ -111,6 +111,38 @@ int GammaBinaryIVFHIPIndex::SyncVid2DocID(int64_t upto) {
   return gamma_hip_vid2docid_append(h_, (int64_t)m.size(), m.data());
 }
 
+// mirror rows [flat_mirrored_, upto) of the engine's store into the flat store of the exact search, and their docids.
+// Called from Search (any number of client threads); add_mu_ makes "read the watermark, copy, advance it" one step and
+// keeps it apart from Add's vid -> docid sync.  Update is the reference's no-op, so a mirrored row never changes.
+int GammaBinaryIVFHIPIndex::EnsureFlat(int64_t upto) {
+  std::lock_guard<std::mutex> g(add_mu_);
+  int rc = 0;
+  if (!flat_init_) {
+    if ((rc = gamma_hip_binflat_init(h_, nbits_))) {
+      BLOG("flat store init failed: %s (%s)", gamma_hip_strerror(rc), gamma_hip_last_error(h_));
+      return -1;
+    }
+    flat_init_ = true;
+  }
+  const int cs = nbits_ / 8;
+  const int64_t step = 65536;
+  for (int64_t i0 = flat_mirrored_; i0 < upto; i0 += step) {
+    const int64_t nb = std::min(step, upto - i0);
+    std::vector<int64_t> vids((size_t)nb);
+    for (int64_t i = 0; i < nb; i++) vids[(size_t)i] = i0 + i;
+    ScopeVectors sv;
+    if (vector_->Gets(vids, sv)) return -1;
+    std::vector<uint8_t> buf((size_t)nb * cs);
+    for (int64_t i = 0; i < nb; i++) memcpy(&buf[(size_t)i * cs], sv.Get((int)i), cs);
+    if ((rc = gamma_hip_binflat_append(h_, nb, buf.data()))) {
+      BLOG("flat store append failed: %s (%s)", gamma_hip_strerror(rc), gamma_hip_last_error(h_));
+      return -1;
+    }
+    flat_mirrored_ = i0 + nb;
+  }
+  return SyncVid2DocID(flat_mirrored_) ? -1 : 0;
+}
+
 // Add (:148-206): assign + AddKeys, vids from indexed_vec_count_; before training the reference throws -- false here
 bool GammaBinaryIVFHIPIndex::Add(int n, const uint8_t *vec) {
   if (!is_trained_) return false;
@@ -140,12 +172,16 @@ int GammaBinaryIVFHIPIndex::Delete(const std::vector<int64_t> &ids) {
 // window of the search condition; distances are Hamming distances as floats, empty slots (float)INT32_MAX / -1
 int GammaBinaryIVFHIPIndex::Search(RetrievalContext *retrieval_context, int n, const uint8_t *x, int k, float *distances,
                                    int64_t *ids) {
-  if (!is_trained_ || x == nullptr) return -1;
+  if (x == nullptr) return -1;
   HIPBinaryIVFRetrievalParameters *rp =
       dynamic_cast<HIPBinaryIVFRetrievalParameters *>(retrieval_context->RetrievalParams());
   HIPBinaryIVFRetrievalParameters defaults;
   if (rp == nullptr) rp = &defaults;
   GammaSearchCondition *cond = dynamic_cast<GammaSearchCondition *>(retrieval_context);
+  // brute_force_search, and every search of a model that is not trained yet, is the exact Hamming search over all the rows
+  // the engine's store holds (the float models send both to their flat search)
+  const bool brute = (cond && cond->brute_force_search) || !is_trained_;
+  if (brute && EnsureFlat((int64_t)vector_->MetaInfo()->Size())) return -1;
   gamma_hip_search_params p;
   memset(&p, 0, sizeof(p));
   p.metric = GAMMA_HIP_METRIC_L2;
@@ -157,8 +193,9 @@ int GammaBinaryIVFHIPIndex::Search(RetrievalContext *retrieval_context, int n, c
   std::vector<gamma_hip_term_filter> tf;
   if (!(device_filters_ && columns_.Prepare(h_, cond, DocCountOf(this, (int64_t)vector_->MetaInfo()->Size()), p, ff, tf)))
     FillRangeFilters(cond, p, rf);
-  const int rc = gamma_hip_binivf_search(h_, &p, n, x, k, distances, ids);
-  if (rc) BLOG("search failed: %s (%s)", gamma_hip_strerror(rc), gamma_hip_last_error(h_));
+  const int rc = brute ? gamma_hip_binflat_search(h_, &p, n, x, k, distances, ids)
+                       : gamma_hip_binivf_search(h_, &p, n, x, k, distances, ids);
+  if (rc) BLOG("%ssearch failed: %s (%s)", brute ? "brute-force " : "", gamma_hip_strerror(rc), gamma_hip_last_error(h_));
   return rc;
 }
 

@@ -2,7 +2,8 @@
 // (reference index/impl/gamma_index_binary_ivf.{h,cc}) on an MI355X.  Same JSON keys ("ncentroids" in the model
 // parameters, "nprobe" in the retrieval parameters), same Init / Indexing / Add / Search contract; Update, Dump and Load
 // are the reference's no-ops (gamma_index_binary_ivf.h:99-104).  The store is a BINARY RawVector whose Dimension() counts
-// bytes.
+// bytes.  HIP only: brute_force_search, and the search of a model that is not trained yet, answer exactly over every row
+// of the store (gamma_hip_binflat_search over a mirror kept by EnsureFlat; the reference returns -1 / ignores the flag).
 #pragma once
 #include <atomic>
 #include <mutex>
@@ -48,8 +49,11 @@ class GammaBinaryIVFHIPIndex : public RetrievalModel {
 
  private:
   int SyncVid2DocID(int64_t upto);
+  int EnsureFlat(int64_t upto);   // brute_force_search / untrained model: the exact search's mirror of the store
   gamma_hip_index *h_ = nullptr;
   int64_t indexed_vec_count_ = 0;
+  bool flat_init_ = false;       // (under add_mu_)
+  int64_t flat_mirrored_ = 0;    // rows of the engine's store in the flat store (under add_mu_)
   std::mutex add_mu_;
   bool device_filters_ = false;
   DeviceColumns columns_;

@@ -120,6 +120,37 @@ int gh_bin_search(void *hp, const char *retrieval_params, float min_score, float
   if (!cond.retrieval_params_) return -100;
   return h->model->Search(&cond, n, x, k, distances, ids);
 }
+// gh_bin_search with GammaSearchCondition::brute_force_search = (brute != 0)
+int gh_bin_search_brute(void *hp, const char *retrieval_params, float min_score, float max_score, int n, const uint8_t *x,
+                        int k, float *distances, int64_t *ids, int n_range, const int64_t *docids, const int *counts,
+                        const int *not_in, int brute) {
+  BinHost *h = (BinHost *)hp;
+  PerfTool perf;
+  GammaSearchCondition cond(&perf);
+  MultiRangeQueryResults mr;
+  size_t off = 0;
+  for (int i = 0; i < n_range; i++) {
+    RangeQueryResult r;
+    if (counts[i] > 0) {
+      for (int j = 0; j < counts[i]; j++) r.SetRange((int)docids[off + j], (int)docids[off + j]);
+    } else {
+      r.SetRange(0, 0);
+    }
+    r.Resize();
+    for (int j = 0; j < counts[i]; j++) r.Set((int)docids[off + j] - r.MinAligned());
+    r.SetNotIn(not_in[i] != 0);
+    off += counts[i];
+    mr.Add(std::move(r));
+  }
+  if (n_range > 0) cond.range_query_result = &mr;
+  cond.topn = k;
+  cond.min_score = min_score;
+  cond.max_score = max_score;
+  cond.brute_force_search = brute != 0;
+  cond.retrieval_params_ = h->model->Parse(retrieval_params);
+  if (!cond.retrieval_params_) return -100;
+  return h->model->Search(&cond, n, x, k, distances, ids);
+}
 int gh_bin_dump(void *hp, const char *dir) { return ((BinHost *)hp)->model->Dump(dir); }
 int gh_bin_load(void *hp, const char *dir) { return ((BinHost *)hp)->model->Load(dir); }
 long gh_bin_mem_bytes(void *hp) { return ((BinHost *)hp)->model->GetTotalMemBytes(); }

@@ -77,6 +77,8 @@ BIN_SYMBOLS = {
     "gh_bin_delete": (C.c_int, [C.c_void_p, i64p, C.c_int]),
     "gh_bin_search": (C.c_int, [C.c_void_p, C.c_char_p, C.c_float, C.c_float, C.c_int, u8p, C.c_int, f32p, i64p,
                                 C.c_int, i64p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "gh_bin_search_brute": (C.c_int, [C.c_void_p, C.c_char_p, C.c_float, C.c_float, C.c_int, u8p, C.c_int, f32p, i64p,
+                                      C.c_int, i64p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]),
     "gh_bin_dump": (C.c_int, [C.c_void_p, C.c_char_p]),
     "gh_bin_load": (C.c_int, [C.c_void_p, C.c_char_p]),
     "gh_bin_mem_bytes": (C.c_long, [C.c_void_p]),
@@ -444,8 +446,9 @@ class BinaryPluginModel:
         vids = np.ascontiguousarray(vids, np.int64)
         return self.L.gh_bin_delete(self.h, vids.ctypes.data_as(i64p), vids.size)
 
-    def search(self, x, k, retrieval_params="", min_score=FLT_MIN, max_score=FLT_MAX, ranges=None):
-        """ranges: None or [(docids, b_not_in)] range results.  Returns (rc, D, I)."""
+    def search(self, x, k, retrieval_params="", min_score=FLT_MIN, max_score=FLT_MAX, ranges=None, brute=False):
+        """ranges: None or [(docids, b_not_in)] range results; brute: the condition's brute_force_search.
+        Returns (rc, D, I)."""
         x = np.ascontiguousarray(x, np.uint8)
         n = x.shape[0]
         D = np.empty((n, k), np.float32)
@@ -455,8 +458,13 @@ class BinaryPluginModel:
                                     if ranges else np.zeros(1, np.int64), np.int64)
         counts = (C.c_int * max(1, len(ranges)))(*[len(d) for d, _ in ranges])
         nots = (C.c_int * max(1, len(ranges)))(*[1 if b else 0 for _, b in ranges])
-        rc = self.L.gh_bin_search(self.h, retrieval_params.encode(), min_score, max_score, n, x.ctypes.data_as(u8p), k,
-                                  _f(D), I.ctypes.data_as(i64p), len(ranges), docs.ctypes.data_as(i64p), counts, nots)
+        if brute:
+            rc = self.L.gh_bin_search_brute(self.h, retrieval_params.encode(), min_score, max_score, n,
+                                            x.ctypes.data_as(u8p), k, _f(D), I.ctypes.data_as(i64p), len(ranges),
+                                            docs.ctypes.data_as(i64p), counts, nots, 1)
+        else:
+            rc = self.L.gh_bin_search(self.h, retrieval_params.encode(), min_score, max_score, n, x.ctypes.data_as(u8p), k,
+                                      _f(D), I.ctypes.data_as(i64p), len(ranges), docs.ctypes.data_as(i64p), counts, nots)
         return rc, D, I
 
     def dump(self, path):

@@ -582,6 +582,42 @@ int gamma_hip_binivf_search_device(gamma_hip_index* h, const gamma_hip_search_pa
  * only by searches made while gamma_hip_profile_enable is on */
 int gamma_hip_binivf_stats(gamma_hip_index* h, int64_t* out2, int reset);
 
+/* ---- exact Hamming (binary flat) search (faiss:IndexBinaryFlat.cpp, utils/hamming.cpp:230-265) ------------------------
+ * Every stored code in vid order, and over them the answer GammaIVFBinaryScannerL2::scan_codes
+ * (gamma_index_binary_ivf.cc:333-448) gives for ONE list that holds every code in vid order: IsValid on the vid (delete
+ * bitmap, range results including NOT, device columns, vid -> docid), the Hamming distance, IsSimilarScoreValid,
+ * `dis < simi[0]` -> heap_pop + heap_push, heap_reorder -- labels and distance bits at every rank, ties included.  One
+ * query is spread over the whole device. */
+/* the store behind IndexBinaryFlat (faiss:IndexBinaryFlat.cpp: xb, code_size = nbits / 8).  nbits % 8 == 0, at most 2048.
+ * On a fresh handle or on a binary IVF handle (before or after gamma_hip_binivf_init; the nbits must match); a handle of a
+ * float model answers GAMMA_HIP_EINVAL.  Repeating the call with the same nbits is a no-op. */
+int gamma_hip_binflat_init(gamma_hip_index* h, int nbits);
+/* IndexBinaryFlat::add (faiss:IndexBinaryFlat.cpp).  codes: n x nbits / 8 host; the new vids are count .. count + n - 1.
+ * A search never reads a half-written row: the rows go up on the writer stream and the count is published after them;
+ * growth that frees or moves memory waits for the searches in flight. */
+int gamma_hip_binflat_append(gamma_hip_index* h, int64_t n, const uint8_t* codes);
+/* IndexBinaryFlat::ntotal: rows stored; -1 before _init */
+int64_t gamma_hip_binflat_count(gamma_hip_index* h);
+/* IndexBinaryFlat::search (faiss:IndexBinaryFlat.cpp, hammings_knn_hc faiss:utils/hamming.cpp:230-265) with the scanner's
+ * admission and validity rules (gamma_index_binary_ivf.cc:333-448).  x nq x nbits / 8 host; distances / labels nq x k host,
+ * best first, empty slots label -1 / distance 2147483648.0f ((float)INT32_MAX).  Of gamma_hip_search_params it uses
+ * min_score / max_score (the default window [FLT_MIN, FLT_MAX] excludes distance 0), the range filters, the device field
+ * and term filters; metric, nprobe, recall_num, has_rank, coarse_mode and exact_ties are ignored.  k > 4096:
+ * GAMMA_HIP_EUNSUPPORTED.  The candidate counts of a call are data dependent; the queries run in sub-batches that fit
+ * gamma_hip_set_workspace_budget (never wrong, only slower). */
+int gamma_hip_binflat_search(gamma_hip_index* h, const gamma_hip_search_params* p, int nq, const uint8_t* x, int k,
+                             float* distances, int64_t* labels);
+/* same, all pointers in device memory, on the handle's stream; the call reads its candidate totals back once per round
+ * of queries (one small copy), what follows is enqueued without a sync */
+int gamma_hip_binflat_search_device(gamma_hip_index* h, const gamma_hip_search_params* p, int nq, const uint8_t* d_x, int k,
+                                    float* d_distances, int64_t* d_labels);
+/* rows per chunk of the search kernels: the unit of the candidate bounds that let scan_codes' heap
+ * (gamma_index_binary_ivf.cc:407-448) be replayed over a part of the rows only */
+int gamma_hip_binflat_chunk_rows(void);
+/* {queries searched, candidates collected, heap admissions of the replays (scan_codes' `dis < simi[0]`,
+ * gamma_index_binary_ivf.cc:407-448), query sub-batches} since the last reset */
+int gamma_hip_binflat_stats(gamma_hip_index* h, int64_t* out4, int reset);
+
 /* ---- search ------------------------------------------------------------------------ */
 /* replaces GammaIVFPQIndex::Search (gamma_index_ivfpq.cc:514-566 + search_preassigned
  * :701-890).  x: nq*d fp32 host; distances/labels: nq*k host, best first, unused slots
