@@ -717,6 +717,12 @@ class GammaHip:
         self._ck(self.L.gamma_hip_coarse_filter_stats(self.h, _p(out, _lib.i64p)), "coarse_filter_stats")
         return dict(zip(["given_up", "queries", "backoffs", "fp32_calls_left"], [int(v) for v in out]))
 
+    def flat_filter_stats(self, reset=False):
+        """(filter passes launched, (query, row) pairs they scored, passes redone without the bound) of flat_search."""
+        out = np.zeros(3, np.int64)
+        self._ck(self.L.gamma_hip_flat_filter_stats(self.h, _p(out, _lib.i64p), 1 if reset else 0), "flat_filter_stats")
+        return tuple(int(v) for v in out)
+
     def set_small_path(self, on=True):
         """True / False, or an int >= 2: on, with the two-level selection of long candidate rows forced (that many slices)."""
         self._ck(self.L.gamma_hip_set_small_path(self.h, int(on)), "set_small_path")
@@ -958,6 +964,16 @@ def set_precomputed_table_max_bytes(nbytes):
 
 def get_precomputed_table_max_bytes():
     return int(_lib.load().gamma_hip_get_precomputed_table_max_bytes())
+
+
+def flat_filter_shape(d):
+    """(d_pad, margin) of flat_search's matrix-pipe filter for rows of d floats -- the filter pads a row to d_pad = ceil32(d)
+    with exact zeros and lets a row through when its approximate distance is within margin * (|x|^2 + |y|^2) of the bound --
+    or None when rows of that length have no filter kernel (they are scored exactly throughout).  No device call."""
+    dp, m = C.c_int(0), C.c_float(0.0)
+    if not _lib.load().gamma_hip_flat_filter_shape(int(d), C.byref(dp), C.byref(m)):
+        return None
+    return int(dp.value), float(m.value)
 
 
 def train_ivfpq(x, nlist, M, device=0):

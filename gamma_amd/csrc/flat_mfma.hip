@@ -15,6 +15,12 @@
 //                   append to the query's candidate list -- item for item what k_pairwise_lds<.., EMIT> appends, so
 //                   k_flat_compact, the tie log and every result are unchanged.
 //
+// Three filter kernels, one survivors' list and one exact stage:
+//   k_flat_filter      d in {32, 64, 96, 128}: the rows' fragments in registers, queries stream through LDS (below)
+//   k_flat_filter_big  d % 32 == 0, 128 < d <= 1536: a block of 32 queries in LDS, rows stream (further down)
+//   k_flat_filter_any  every other 1 <= d <= 4096: the same streaming design over rows padded to a multiple of 32 with exact
+//                      zeros, loads that respect the rows' true alignment, the image split between LDS and L2 (at the end)
+//
 // Margin (D <= 128; norms xn = |x|^2, yn = |y|^2 in fp32):
 //   dropped products  |xl.yl + rx.y + x.ry| <= 3.1 * 2^-18 |x||y|          (Cauchy-Schwarz over the elements)
 //   fp32 accumulation of 3 D exact products        <= 3 D 2^-24 |x||y|  = 2.3e-5 |x||y| at D = 128
@@ -539,25 +545,276 @@ __global__ __launch_bounds__(FM_NT) void k_flat_filter_big(FlatFilterArgs<Row> a
     if (wcnt > 0) flush();
 }
 
+// ------------------------------------------------------------------------------------
+// Any row length 1 <= d <= 4096: every d that is neither one of the four register-resident lengths nor a
+// multiple of 32 up to 1536 -- GloVe / fastText rows of 100, 200, 300 floats, 1000, the 2048 / 3072 / 4096 floats of text
+// embeddings.  The streaming design of k_flat_filter_big, as a kernel of its own, with three differences.
+//   Padding.  d_pad = ceil32(d).  The query image is built for d_pad with exact zeros behind element d
+//     (k_flat_prep_queries_pad), the row fragments hold exact zeros there: the padding adds exact zeros to the approximate
+//     inner product and to the row norm, and the margin rule above holds with d_pad for d.  A lane's half row is
+//     [kh * d_pad / 2, ..) of the PADDED row.
+//   Row loads.  Row r starts at r * d elements: 16-byte aligned only when d * sizeof(Row) % 16 == 0.  ALIGNED (fp32 d % 4 == 0,
+//     binary16 / bytes d % 8 == 0): the wide loads of k_flat_filter_big, each predicated on lying inside the row as a whole
+//     (a float4 of an fp32 row, the 8 elements of a narrow one: d % 4 / d % 8 == 0 makes them all-in or all-out).  Otherwise
+//     element loads of the row's own type, each predicated on its element index.  A masked element is an exact zero; no
+//     lane reads past the last element of its row, and a lane whose row is past the end of the pass loads nothing.
+//   Rows longer than 1536.  The image of a query block is d_pad x 128 bytes = 2 d_pad / 16 fragment blocks of 1 KB,
+//     [hi k steps | lo k steps].  The first `nl` blocks live in the LDS, the rest is read from the image in memory (L2) the way
+//     LO_L2 does: the hi fragments first -- each is the operand of two of the three products --, then as many lo fragments
+//     as still fit.  The k loop runs in three ranges (hi + lo in LDS | hi in LDS | neither), each with its own loads.
+// Margin tiers beyond 1536 (bound(d) = (3.1 * 2^-18 + (4.25 d + 8) 2^-24) (xn + yn), the four terms listed above):
+//   d_pad <= 2176: bound 5.64e-4, margin 2^-10 = 9.77e-4 (headroom 1.73)
+//   d_pad <= 4096: bound 1.05e-3, margin 2^-9  = 1.95e-3 (headroom 1.86)     -- the existing tiers' smallest headroom is
+//   1.72 (d = 512: 2.44e-4 over 1.42e-4).
+// ------------------------------------------------------------------------------------
+constexpr int FM_ANY_MAX_D = 4096;
+constexpr int FM_ANY_NL = 152;   // 1 KB fragment blocks of the image a workgroup may keep in the LDS (+ 8 KB of lists = 160 KB)
+__host__ __device__ constexpr int fm_pad32(int d) { return (d + 31) / 32 * 32; }
+
+float flat_filter_margin_pad(int d_pad) { return d_pad <= 1536 ? flat_filter_margin(d_pad) : (d_pad <= 2176 ? 9.765625e-4f : 1.953125e-3f); }
+
+// the image of k_flat_prep_queries_rt for d_pad, from queries of d floats: elements >= d are exact zeros
+__global__ __launch_bounds__(256) void k_flat_prep_queries_pad(const float* __restrict__ x, int nq, int nq_pad, int D, int DP,
+                                                               char* __restrict__ out) {
+    const int KK = DP / 16;
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= nq_pad * (DP / 8)) return;
+    const int q = idx / (DP / 8), kg = idx % (DP / 8);
+    float f[8];
+#pragma unroll
+    for (int t = 0; t < 8; t++) f[t] = (q < nq && kg * 8 + t < D) ? x[(int64_t)q * D + kg * 8 + t] : 0.f;
+    uint4 hi, lo;
+    split_bf16x8(f, hi, lo);
+    const int mt = q >> 5, i = q & 31, kh = kg / KK, kk = kg % KK;
+    char* base = out + (int64_t)mt * fm_mt_bytes(DP);
+    *reinterpret_cast<uint4*>(base + ((((0 * KK + kk) * 2 + kh) * 32 + i) * 16)) = hi;
+    *reinterpret_cast<uint4*>(base + ((((1 * KK + kk) * 2 + kh) * 32 + i) * 16)) = lo;
+}
+
+// 8 consecutive elements of a row as loaded, of which the first n (<= 0: none) lie inside the row; the others are zeros.
+// AL: p is aligned to 8 elements (fp32: to 4 -- two loads) and n % 8 == 0 (fp32: n % 4 == 0), so a wide load is inside the row or
+// not issued.  !AL: p is aligned to its element only.
+template <class Row, bool AL> struct RawAny { Raw8<Row> v; };
+template <class Row> struct RawAny<Row, false> { Row e[8]; };
+template <class Row, bool AL>
+__device__ __forceinline__ RawAny<Row, AL> row_load8_masked(const Row* __restrict__ p, int n) {
+    RawAny<Row, AL> r;
+    if constexpr (!AL) {
+#pragma unroll
+        for (int t = 0; t < 8; t++) r.e[t] = t < n ? p[t] : (Row)0;
+    } else if constexpr (RowKind<Row>::fp32) {
+        r.v.a = make_float4(0.f, 0.f, 0.f, 0.f);
+        r.v.b = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (n >= 4) r.v.a = *reinterpret_cast<const float4*>(p);
+        if (n >= 8) r.v.b = *reinterpret_cast<const float4*>(p + 4);
+    } else if constexpr (RowKind<Row>::half) {
+        r.v.a = make_uint4(0u, 0u, 0u, 0u);
+        if (n >= 8) r.v.a = *reinterpret_cast<const uint4*>(p);
+    } else {
+        r.v.a = make_uint2(0u, 0u);
+        if (n >= 8) r.v.a = *reinterpret_cast<const uint2*>(p);
+    }
+    return r;
+}
+template <class Row, bool AL>
+__device__ __forceinline__ void row_widen8_any(const RawAny<Row, AL>& r, float* f) {
+    if constexpr (AL) {
+        row_widen8<Row>(r.v, f);
+    } else {
+#pragma unroll
+        for (int t = 0; t < 8; t++) f[t] = row_elem_f<Row>(r.e[t]);
+    }
+}
+
+template <bool L2, bool AL, class Row = float>
+__global__ __launch_bounds__(FM_NT) void k_flat_filter_any(FlatFilterArgs<Row> a, int D, int DP, int nl, float c_margin) {
+    constexpr bool BYTE = RowKind<Row>::byte;   // (narrow rows: see k_flat_filter)
+    const int KK = DP / 16;
+    const int IMG = fm_mt_bytes(DP);
+    extern __shared__ __attribute__((aligned(16))) char s_fm[];
+    char* s_img = s_fm;                                                   // [nl KB] the head of the block's image
+    uint2* s_list = reinterpret_cast<uint2*>(s_fm + nl * 1024);           // [4 waves][FM_WLIST]
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int kh = lane >> 5, j = lane & 31;
+    const int mt = blockIdx.x;
+    {
+        const uint4* src = reinterpret_cast<const uint4*>(a.qimg + (int64_t)mt * IMG);
+        uint4* dst = reinterpret_cast<uint4*>(s_img);
+        for (int i = tid; i < nl * 64; i += FM_NT) dst[i] = src[i];
+    }
+    // this lane's 16 queries: i = (reg & 3) + 8 (reg >> 2) + 4 kh
+    float av[16], gv[16];
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const int qi = mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
+        av[r] = a.bnd[qi];
+        gv[r] = L2 ? 1.f : a.bnd[a.nq_pad + qi];
+    }
+    __syncthreads();
+    uint2* wl = s_list + w * FM_WLIST;
+    int wcnt = 0;   // wave-uniform
+    const int sub = (int)((blockIdx.x + blockIdx.y * gridDim.x) & (FM_NSUB - 1));
+    int* seg_ctr = a.npairs + sub * FM_CTR_STRIDE;
+    uint2* seg = a.pairs + (int64_t)sub * a.cap;
+    auto flush = [&]() {
+        int base = 0;
+        if (lane == 0) base = atomicAdd(seg_ctr, wcnt);
+        base = __builtin_amdgcn_readfirstlane(base);
+        __builtin_amdgcn_wave_barrier();
+        for (int i = lane; i < wcnt; i += 64)
+            if (base + i < a.cap) seg[base + i] = wl[i];
+        __builtin_amdgcn_wave_barrier();
+        wcnt = 0;
+    };
+    // row slice of this workgroup: whole steps of 256 rows
+    const int64_t steps = (a.ny + 255) / 256, per = (steps + gridDim.y - 1) / gridDim.y;
+    const int64_t s_lo = (int64_t)blockIdx.y * per, s_hi = min(steps, s_lo + per);
+    const char* tb = s_img + (kh * 32 + j) * 16;
+    const char* tg = a.qimg + (int64_t)mt * IMG + (kh * 32 + j) * 16;    // the same fragment in the image in memory
+    // k ranges: [0, ka) hi and lo fragments in the LDS, [ka, kb) hi only, [kb, KK) neither
+    const int ka = max(0, nl - KK), kb = min(KK, nl);
+    // elements of this lane's half of the padded row that exist: [kh * DP / 2, D)
+    const int half_n = min(DP / 2, D - kh * (DP / 2));
+    for (int64_t st = s_lo; st < s_hi; st++) {
+        const int64_t r0 = st * 256 + w * 64;
+        const Row* yp[2];
+        bool live[2];
+        int lim[2];   // (a row past the end of the pass: nothing is loaded)
+#pragma unroll
+        for (int nt = 0; nt < 2; nt++) {
+            const int64_t r = r0 + nt * 32 + j;
+            live[nt] = r < a.ny;
+            lim[nt] = live[nt] ? half_n : 0;
+            yp[nt] = a.y + (live[nt] ? r : 0) * D + (DP / 2) * kh;
+        }
+        ff32x16 acc[2];
+#pragma unroll
+        for (int nt = 0; nt < 2; nt++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) acc[nt][r] = 0.f;
+        float ss[2] = {0.f, 0.f};
+        RawAny<Row, AL> v[2];
+#pragma unroll
+        for (int nt = 0; nt < 2; nt++) v[nt] = row_load8_masked<Row, AL>(yp[nt], lim[nt]);
+        auto kstep = [&](int kk, const char* hp, const char* lp) {
+            bf16x8 bh[2], bl[2];
+#pragma unroll
+            for (int nt = 0; nt < 2; nt++) {
+                float f[8];
+                row_widen8_any<Row, AL>(v[nt], f);
+#pragma unroll
+                for (int t = 0; t < 8; t++) ss[nt] = __builtin_fmaf(f[t], f[t], ss[nt]);
+                uint4 hi, lo;
+                if constexpr (BYTE) {   // exact in one bf16: no lo fragment
+                    hi = make_uint4(cvt_pk_bf16(f[0], f[1]), cvt_pk_bf16(f[2], f[3]), cvt_pk_bf16(f[4], f[5]), cvt_pk_bf16(f[6], f[7]));
+                    lo = make_uint4(0u, 0u, 0u, 0u);
+                } else {
+                    split_bf16x8(f, hi, lo);
+                }
+                bh[nt] = __builtin_bit_cast(bf16x8, hi);
+                bl[nt] = __builtin_bit_cast(bf16x8, lo);
+            }
+            if (kk + 1 < KK) {   // the next step's elements, in flight during this step's products
+#pragma unroll
+                for (int nt = 0; nt < 2; nt++) v[nt] = row_load8_masked<Row, AL>(yp[nt] + 8 * (kk + 1), lim[nt] - 8 * (kk + 1));
+            }
+            const bf16x8 ah = *reinterpret_cast<const bf16x8*>(hp + ((0 * KK + kk) * 2) * 512);
+            const bf16x8 al = *reinterpret_cast<const bf16x8*>(lp + ((1 * KK + kk) * 2) * 512);
+#pragma unroll
+            for (int nt = 0; nt < 2; nt++) {
+                acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh[nt], acc[nt], 0, 0, 0);
+                if constexpr (!BYTE) acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl[nt], acc[nt], 0, 0, 0);
+                acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh[nt], acc[nt], 0, 0, 0);
+            }
+        };
+        int kk = 0;
+        for (; kk < ka; kk++) kstep(kk, tb, tb);
+        for (; kk < kb; kk++) kstep(kk, tb, tg);
+        for (; kk < KK; kk++) kstep(kk, tg, tg);
+        float hrow[2];
+#pragma unroll
+        for (int nt = 0; nt < 2; nt++) {
+            const float yn = ss[nt] + __shfl_xor(ss[nt], 32, 64);
+            hrow[nt] = !live[nt] ? (L2 ? INFINITY : -INFINITY) : (L2 ? 0.5f * (1.f - c_margin) * yn : __builtin_sqrtf(yn));
+        }
+        unsigned long long m[2][16], any = 0ull;
+#pragma unroll
+        for (int nt = 0; nt < 2; nt++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const float t = L2 ? av[r] + hrow[nt] : __builtin_fmaf(gv[r], hrow[nt], av[r]);
+                m[nt][r] = __ballot(acc[nt][r] >= t);
+                any |= m[nt][r];
+            }
+        if (any) {
+#pragma unroll
+            for (int nt = 0; nt < 2; nt++)
+#pragma unroll
+                for (int r = 0; r < 16; r++) {
+                    const unsigned long long mm = m[nt][r];
+                    if (mm) {   // scalar branch
+                        const int n = __popcll(mm);
+                        if (wcnt + n > FM_WLIST) flush();
+                        if ((mm >> lane) & 1ull) {
+                            const uint32_t q = (uint32_t)(mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh);
+                            wl[wcnt + __popcll(mm & ((1ull << lane) - 1ull))] = make_uint2(q, (uint32_t)(a.row_base + r0 + nt * 32 + j));
+                        }
+                        wcnt += n;
+                    }
+                }
+        }
+    }
+    if (wcnt > 0) flush();
+}
+
+// which kernel serves rows of d elements: 1 = k_flat_filter, 2 = k_flat_filter_big, 3 = k_flat_filter_any, 0 = none
+static int flat_filter_kind(int d) {
+    if (d == 128 || d == 96 || d == 64 || d == 32) return 1;
+    if (d > 128 && d <= 1536 && d % 32 == 0) return 2;
+    return d >= 1 && d <= FM_ANY_MAX_D ? 3 : 0;
+}
+int flat_filter_shape(int d, int* d_pad, float* margin) {
+    if (flat_filter_kind(d) == 0) return 0;
+    if (d_pad) *d_pad = fm_pad32(d);
+    if (margin) *margin = flat_filter_margin_pad(fm_pad32(d));
+    return 1;
+}
+bool flat_filter_new_shape(int d) { return flat_filter_kind(d) == 3; }
+// blocks of 1 KB of a query block's image that k_flat_filter_any keeps in the LDS
+static int flat_any_lds_blocks(int d_pad) {
+    static const int cap = [] {
+        const char* e = getenv("GAMMA_HIP_FLAT_ANYD_LDS_KB");   // (measurements: DESIGN section 19)
+        const int v = e ? atoi(e) : FM_ANY_NL;
+        return std::max(1, std::min(FM_ANY_NL, v));
+    }();
+    return std::min(2 * (d_pad / 16), cap);
+}
+
 bool flat_filter_supported(int nq, int d, int64_t ny) {
-    static const bool off = getenv("GAMMA_HIP_NO_FLAT_MFMA") != nullptr;
-    static const bool off_big = getenv("GAMMA_HIP_NO_FLAT_MFMA_BIG") != nullptr;
-    const bool small = d == 128 || d == 96 || d == 64 || d == 32;
-    const bool big = !off_big && d > 128 && d <= 1536 && d % 32 == 0;   // k_flat_filter_big: the query block's image is d x 128 bytes (LDS; beyond 1024 half of it)
-    return !off && (small || big) && nq >= 64 && ny >= 4096;
+    static const bool off = getenv("GAMMA_HIP_NO_FLAT_MFMA") != nullptr;            // every filter kernel
+    static const bool off_big = getenv("GAMMA_HIP_NO_FLAT_MFMA_BIG") != nullptr;    // the long rows: d > 128, either streaming kernel
+    static const bool off_any = getenv("GAMMA_HIP_NO_FLAT_MFMA_ANYD") != nullptr;   // k_flat_filter_any, whatever d
+    const int kind = flat_filter_kind(d);
+    const bool on = kind == 1 || (kind == 2 && !off_big) || (kind == 3 && !off_any && !(off_big && d > 128));
+    return !off && on && nq >= 64 && ny >= 4096;
 }
 int64_t flat_filter_pair_cap(int nq) { return (int64_t)nq * 1024; }   // ~k survivors per query and pass are expected (all segments)
 int flat_filter_counter_bytes() { return FM_NSUB * FM_CTR_STRIDE * (int)sizeof(int); }
 size_t flat_filter_query_image_bytes(int nq, int d) {
     const int nq_pad = (nq + FM_QT - 1) / FM_QT * FM_QT;
-    return (size_t)(nq_pad / 32) * fm_mt_bytes(d);
+    return (size_t)(nq_pad / 32) * fm_mt_bytes(fm_pad32(d));   // (d % 32 == 0 for the two older kernels)
 }
 
 void launch_flat_prep_queries(hipStream_t s, const float* x, int nq, int d, void* image) {
     if (nq <= 0) return;
     const int nq_pad = (nq + FM_QT - 1) / FM_QT * FM_QT;
-    const int n = nq_pad * (d / 8);
     char* out = static_cast<char*>(image);
+    if (flat_filter_kind(d) == 3) {   // padded to a multiple of 32
+        const int dp = fm_pad32(d), np = nq_pad * (dp / 8);
+        hipLaunchKernelGGL(k_flat_prep_queries_pad, dim3((np + 255) / 256), dim3(256), 0, s, x, nq, nq_pad, d, dp, out);
+        return;
+    }
+    const int n = nq_pad * (d / 8);
 #define GH_PREP(DD) hipLaunchKernelGGL((k_flat_prep_queries<DD>), dim3((n + 255) / 256), dim3(256), 0, s, x, nq, nq_pad, out)
     switch (d) {
         case 128: GH_PREP(128); break;
@@ -591,7 +848,7 @@ static void flat_filter_rows(hipStream_t s, bool l2, int d, const void* qimage, 
     a.qimg = static_cast<const char*>(qimage);
     a.nq = nq;
     a.nq_pad = (nq + FM_QT - 1) / FM_QT * FM_QT;
-    const float cm = flat_filter_margin(d);
+    const float cm = flat_filter_margin_pad(fm_pad32(d));   // (= flat_filter_margin(d) for the two older kernels)
     if (l2) hipLaunchKernelGGL((k_flat_bounds<true>), dim3((a.nq_pad + 255) / 256), dim3(256), 0, s, xn, tau, nq, a.nq_pad, bounds, cm);
     else hipLaunchKernelGGL((k_flat_bounds<false>), dim3((a.nq_pad + 255) / 256), dim3(256), 0, s, xn, tau, nq, a.nq_pad, bounds, cm);
     a.bnd = bounds;
@@ -601,6 +858,31 @@ static void flat_filter_rows(hipStream_t s, bool l2, int d, const void* qimage, 
     a.pairs = static_cast<uint2*>(pairs);
     a.npairs = npairs;
     a.cap = (int)std::min<int64_t>(cap / FM_NSUB, INT32_MAX);   // per segment
+    if (flat_filter_kind(d) == 3) {   // any other length: padded, one workgroup per (block of 32 queries, slice of the rows)
+        const int dp = fm_pad32(d), nl = flat_any_lds_blocks(dp);
+        const size_t lds = (size_t)nl * 1024 + (FM_NT / 64) * FM_WLIST * sizeof(uint2);
+        static std::atomic<uint64_t> attr{0};   // per device
+        if (first_call_on_device(attr)) {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_flat_filter_any<true, true, Row>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 << 10);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_flat_filter_any<false, true, Row>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 << 10);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_flat_filter_any<true, false, Row>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 << 10);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_flat_filter_any<false, false, Row>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 << 10);
+        }
+        // wide loads need every row start and every group of 8 elements aligned to the load
+        const bool al = RowKind<Row>::fp32 ? d % 4 == 0 : d % 8 == 0;
+        const int qb = a.nq_pad / 32;
+        const int64_t steps = (a.ny + 255) / 256;
+        const int slices = (int)std::max<int64_t>(1, std::min<int64_t>(steps, (2048 + qb - 1) / qb));
+        const dim3 grid(qb, slices);
+        if (al) {
+            if (l2) hipLaunchKernelGGL((k_flat_filter_any<true, true, Row>), grid, dim3(FM_NT), lds, s, a, d, dp, nl, cm);
+            else hipLaunchKernelGGL((k_flat_filter_any<false, true, Row>), grid, dim3(FM_NT), lds, s, a, d, dp, nl, cm);
+        } else {
+            if (l2) hipLaunchKernelGGL((k_flat_filter_any<true, false, Row>), grid, dim3(FM_NT), lds, s, a, d, dp, nl, cm);
+            else hipLaunchKernelGGL((k_flat_filter_any<false, false, Row>), grid, dim3(FM_NT), lds, s, a, d, dp, nl, cm);
+        }
+        return;
+    }
 #define GH_FILT(DD)                                   \
     do {                                              \
         if (l2) launch_filter_t<true, DD, Row>(s, a); \

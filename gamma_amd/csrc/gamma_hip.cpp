@@ -246,6 +246,16 @@ int gamma_hip_coarse_filter_stats(gamma_hip_index* h, int64_t* out4) {
     return GAMMA_HIP_OK;
 }
 
+int gamma_hip_flat_filter_shape(int d, int* d_pad, float* margin) { return gh::flat_filter_shape(d, d_pad, margin); }
+
+int gamma_hip_flat_filter_stats(gamma_hip_index* h, int64_t* out3, int reset) {
+    if (!h || !out3) return GAMMA_HIP_EINVAL;
+    out3[0] = reset ? h->ff_passes.exchange(0) : h->ff_passes.load();
+    out3[1] = reset ? h->ff_pairs.exchange(0) : h->ff_pairs.load();
+    out3[2] = reset ? h->ff_redone.exchange(0) : h->ff_redone.load();
+    return GAMMA_HIP_OK;
+}
+
 int gamma_hip_set_small_path(gamma_hip_index* h, int on) {
     if (!h) return GAMMA_HIP_EINVAL;
     SearchLock lk(h);

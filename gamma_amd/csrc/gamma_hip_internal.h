@@ -164,6 +164,7 @@ struct gamma_hip_index {
     //  event, with the handle free, from one of four pinned words, and redoes the call without a bound in the rare yes)
     int* pin_flat_over = nullptr;
     int* flat_over_dst = nullptr;    // set by the _wait entry for the call under way
+    int flat_over_passes = 0;        // filter passes of the call under way whose overflow word the _wait entry reads later
     bool flat_no_bound = false;
     std::atomic<int> big_calls_in_flight{0};
     std::atomic<int64_t> big_calls_overlap_seen_ns{INT64_MIN / 2};
@@ -370,6 +371,8 @@ struct gamma_hip_index {
     uint64_t cbf_sig = 0;
     int cbf_off_calls = 0;                         // fp32 calls left before the re-probe
     int64_t cbf_backoffs = 0, cbf_calls = 0;       // times the handle turned the bf16 filter off; calls that ran it
+    // gamma_hip_flat_filter_stats: filter passes launched, (query, row) pairs they scored, passes redone without the bound
+    std::atomic<int64_t> ff_passes{0}, ff_pairs{0}, ff_redone{0};
     bool small_path = true;    // gamma_hip_set_small_path
     bool flat_narrow_rows = false;   // gamma_hip_set_flat_narrow_rows: flat search serves a float16 / uint8 / int8 raw store
     bool ivfflat_narrow_rows = false;   // gamma_hip_set_ivfflat_narrow_rows: the same for the IVFFLAT search

@@ -1636,7 +1636,15 @@ int flat_search_device_locked(H* h, const gamma_hip_search_params* p, int nq, co
     const bool mfma_filter = k <= 256 && N < ((int64_t)1 << 32) && gh::flat_filter_supported(nq, d, N);
     // (long rows: the first chunk's exact kernel runs at ~1.3 TFLOP/s -- 1024 rows of d = 768 instead of 16384: C5 flat, 1 M x 768,
     //  1024 queries: 15.6 / 16.1 / 16.8 / 18.4 ms per call with a first chunk of 2^10 / 2^11 / 2^12 / 2^13 rows)
-    const int fl2 = mfma_filter ? (d > 128 ? 10 : 14) : 16;
+    // (the lengths of k_flat_filter_any, d <= 128: no k_pairwise_lds variant scores the first chunk -- it runs on the generic
+    //  kernel at the long rows' rate, so it is 2^12 rows, the smallest the filter's gate ny >= 4096 leaves room behind)
+    static const int fl_any = [] {   // (measurements of the any-length shapes only: DESIGN section 19)
+        const char* e = getenv("GAMMA_HIP_FLAT_ANYD_FIRST_LOG2");
+        const int v = e ? atoi(e) : 0;
+        return v >= 8 && v <= 16 ? v : 0;
+    }();
+    const bool new_shape = gh::flat_filter_new_shape(d);
+    const int fl2 = mfma_filter ? (new_shape && fl_any ? fl_any : (d > 128 ? 10 : (new_shape ? 12 : 14))) : 16;
     int64_t rows_chunk = std::max<int64_t>(256, std::min<int64_t>(N, (int64_t)1 << fl2));
     rows_chunk = (rows_chunk + 255) / 256 * 256;
     int qc = (int)std::max<int64_t>(1, std::min<int64_t>(nq, (int64_t)(h->dist_budget_bytes / (rows_chunk * sizeof(float)))));
@@ -1793,6 +1801,8 @@ int flat_search_device_locked(H* h, const gamma_hip_search_params* p, int nq, co
                                        h->w_fraw.p, npairs, pcap);
                 gh::launch_flat_exact(s, l2, h->w_fraw.p, npairs, pcap, xq, nc, d, rows, filt, p->min_score, p->max_score,
                                       em, over);
+                h->ff_passes.fetch_add(1, std::memory_order_relaxed);
+                h->ff_pairs.fetch_add((int64_t)nc * nr, std::memory_order_relaxed);
             } else {
                 gh::launch_pairwise_emit(s, l2, xq, nc, d, rows.at(r, d), nr, filt, p->min_score, p->max_score, r, em);
             }
@@ -1879,6 +1889,7 @@ int flat_search_device_locked(H* h, const gamma_hip_search_params* p, int nq, co
             GH_TRY(bounded(q0, nc, &redo));
             if (ties) GH_TRY(tie_phase(false));   // enqueued before the host learns whether a list overflowed
             if (defer_flat && h->flat_over_dst) {
+                h->flat_over_passes = (mfma_filter && gh::flat_filter_supported(nc, d, N)) ? log_nsl - 1 : 0;   // (counted by the caller if the word says so)
                 // (the caller reads the word after the call's completion event, with the handle free: no host wait under the lock)
                 GH_CHECK(h, hipMemcpyAsync(h->flat_over_dst, h->w_flat_meta.as<int>() + nc + (size_t)nc * 32, sizeof(int),
                                            hipMemcpyDeviceToHost, s));
@@ -1886,6 +1897,7 @@ int flat_search_device_locked(H* h, const gamma_hip_search_params* p, int nq, co
             }
             GH_TRY(overflowed(nc, &redo));
             if (!redo) continue;
+            if (mfma_filter && gh::flat_filter_supported(nc, d, N)) h->ff_redone.fetch_add(log_nsl - 1, std::memory_order_relaxed);
             GH_TRY(replay_join(h));   // (a replay on the side stream writes the rows that are about to be redone)
         }
         GH_TRY(unbounded(q0, nc));
@@ -2678,6 +2690,7 @@ int gamma_hip_flat_search_device_wait(gamma_hip_index* h, const gamma_hip_search
     if (!h) return GAMMA_HIP_EINVAL;
     hipEvent_t ev = nullptr;
     int* over = nullptr;
+    int over_passes = 0;   // filter passes of this call: redone if its overflow word is set
     {
         SearchLock lk(h);
         GH_CHECK(h, hipSetDevice(h->device));
@@ -2692,7 +2705,9 @@ int gamma_hip_flat_search_device_wait(gamma_hip_index* h, const gamma_hip_search
         *over = 0;
         h->defer_now = h->side2 != nullptr;
         h->flat_over_dst = over;
+        h->flat_over_passes = 0;
         const int rc = flat_search_device_locked(h, p, nq, d_x, k, d_distances, d_labels);
+        over_passes = h->flat_over_passes;
         h->defer_now = false;
         h->flat_over_dst = nullptr;
         if (rc != GAMMA_HIP_OK) return rc;
@@ -2706,6 +2721,7 @@ int gamma_hip_flat_search_device_wait(gamma_hip_index* h, const gamma_hip_search
     if (hipEventSynchronize(ev) != hipSuccess) return GAMMA_HIP_EDEVICE;
     if (*over) {   // a survivor list overflowed (adversarial data): the call again without a bound, the plain way
         SearchLock lk(h);
+        h->ff_redone.fetch_add(over_passes, std::memory_order_relaxed);
         h->flat_no_bound = true;
         int rc = replay_join(h);
         if (rc == GAMMA_HIP_OK) rc = flat_search_device_locked(h, p, nq, d_x, k, d_distances, d_labels);

@@ -127,6 +127,9 @@ void launch_row_norms(hipStream_t s, const float* y, int64_t n, int d, float* ou
 // Flat search on the matrix pipe (flat_mfma.hip): a bf16 hi / lo filter with a proven margin + the survivors' exact
 // distances -- appends to the FlatEmit lists exactly the items launch_pairwise_emit would append.
 bool flat_filter_supported(int nq, int d, int64_t ny);
+// rows of d elements have a filter kernel (whatever the switches and gates say): the padded length and the margin constant
+int flat_filter_shape(int d, int* d_pad, float* margin);
+bool flat_filter_new_shape(int d);   // served by k_flat_filter_any (neither a register-resident length nor d % 32 == 0 <= 1536)
 int64_t flat_filter_pair_cap(int nq);
 int flat_filter_counter_bytes();   // the pair list's counters (one per segment, a cache line apart): zeroed before a pass
 size_t flat_filter_query_image_bytes(int nq, int d);

@@ -175,6 +175,18 @@ int gamma_hip_set_coarse_fused(gamma_hip_index* h, int on, int list_cap);
  * out4: {queries the bf16 chain handed to the repair kernels, queries it ran on, times the handle switched itself to
  * the fp32 filter, fp32 calls left before it probes the bf16 filter again} */
 int gamma_hip_coarse_filter_stats(gamma_hip_index* h, int64_t* out4);
+/* Flat search (GammaFLATIndex::Search, index/impl/gamma_index_flat.cc:118-300) scores every row; here the passes behind the
+ * first row chunk run a bf16 filter on the matrix pipe and only its survivors get the reference's arithmetic
+ * (csrc/flat_mfma.hip), so results are the reference's bit for bit.  No handle, no device call:
+ * returns 1 if rows of d floats have a filter kernel (1 <= d <= 4096) and writes the row length the filter pads to
+ * (ceil32(d); elements >= d are exact zeros) and the constant c of its margin c (|x|^2 + |y|^2); returns 0 otherwise
+ * (such rows are scored exactly throughout, as the reference scores them).  The gates of a call -- at least 64 queries,
+ * 4096 rows, k <= 256 -- are not part of the answer. */
+int gamma_hip_flat_filter_shape(int d, int* d_pad, float* margin);
+/* out3 = {filter passes launched, (query, row) pairs those passes scored, passes redone without the running bound after
+ * a survivor list overflowed} since creation or the last reset.  Host-side counters: no synchronisation, no device read.
+ * The reference has no counterpart (it scores every pair: gamma_index_flat.cc:118-300). */
+int gamma_hip_flat_filter_stats(gamma_hip_index* h, int64_t* out3, int reset);
 /* Calls of up to 512 queries (nprobe <= 128, recall_num <= 1024) run as a chain of
  * four or five fused kernels instead of eleven (DESIGN.md "small batches").  on: 1 = automatic (default), 0 = always
  * the regular chain, n >= 2 = automatic with the two-level selection of long candidate rows forced on with n slices
