@@ -112,8 +112,10 @@ __global__ __launch_bounds__(256) void k_flat_bounds(const float* __restrict__ x
     bnd[nq_pad + q] = gv;
 }
 
+// (the decode table of sq8 rows rides in the empty base RowTab<Row>: `tab.t` exists for Row = sq8_t only, and the four other
+//  instantiations keep their layout)
 template <class Row = float>
-struct FlatFilterArgs {
+struct FlatFilterArgs : RowTab<Row> {
     const char* qimg;          // k_flat_prep_queries
     const float* bnd;          // k_flat_bounds: a_q [nq_pad] | g_q [nq_pad]
     int nq, nq_pad;
@@ -133,6 +135,11 @@ constexpr int FM_CTR_STRIDE = 32;   // ints between the segments' counters
 // exactly; the norm comes from the widened values in the same fma chain.  A binary16 value IS hi + lo (11 significant bits, two
 // bf16 of 8) and a byte value IS hi alone, so the dropped-row term ry of the margin above is 0 and the margin holds unchanged.
 // Byte rows therefore keep no lo fragments and leave the ah x bl product out -- it would add exact zeros.
+// sq8 rows (sq8_t, gamma_hip_set_flat_sq8_rows): the codes are loaded the way byte rows are and DECODED, w = vmin[j] + code *
+// step[j] in two fp32 roundings; from there on w is an ordinary finite fp32 value and the kernel is the fp32 rows' kernel --
+// hi and lo fragments, three products, the norm from the decoded values -- so the margin holds as proven for fp32 rows.  (The
+// byte rows' shortcut would be wrong here: a decoded value is not a bf16 value.)  A lane's table entries depend on its k slice
+// only, not on the row: they are loaded once per 16 elements for both of the lane's rows, 32 transient registers.
 template <bool L2, int D, class Row = float>
 __global__ __launch_bounds__(FM_NT) void k_flat_filter(FlatFilterArgs<Row> a) {
     constexpr int KK = D / 16;
@@ -149,10 +156,53 @@ __global__ __launch_bounds__(FM_NT) void k_flat_filter(FlatFilterArgs<Row> a) {
     const int64_t r0 = (int64_t)blockIdx.x * FM_ROWS + rg * 64;
     // ---- this wave's 64 rows: bf16 hi / lo B fragments in registers, norms ----
     constexpr bool BYTE = RowKind<Row>::byte;
+    constexpr bool SQ8 = RowKind<Row>::sq8;
     bf16x8 bh[2][KK], bl[2][BYTE ? 1 : KK];
     float hrow[2];
+    if constexpr (SQ8) {
+        static_assert(KK % 2 == 0, "sq8 rows: two k steps per 16-byte load");
+        const uint4* yq[2];
+        bool live[2];
+        float ss[2] = {0.f, 0.f};
 #pragma unroll
-    for (int nt = 0; nt < 2; nt++) {
+        for (int nt = 0; nt < 2; nt++) {
+            const int64_t r = r0 + nt * 32 + j;
+            live[nt] = r < a.ny;
+            yq[nt] = reinterpret_cast<const uint4*>(a.y + (live[nt] ? r : 0) * D + (D / 2) * kh);
+        }
+#pragma unroll
+        for (int k2 = 0; k2 < KK / 2; k2++) {
+            // the table entries of elements kh * D/2 + 16 k2 + 0..15, for both rows
+            const Tab8<Row> t0 = tab8_load<Row>(a, (D / 2) * kh + 16 * k2), t1 = tab8_load<Row>(a, (D / 2) * kh + 16 * k2 + 8);
+#pragma unroll
+            for (int nt = 0; nt < 2; nt++) {
+                const uint4 v = yq[nt][k2];
+                float f[16];
+                row_dword_f<Row>(v.x, f);
+                row_dword_f<Row>(v.y, f + 4);
+                row_dword_f<Row>(v.z, f + 8);
+                row_dword_f<Row>(v.w, f + 12);
+                row_decode8<Row>(f, t0);
+                row_decode8<Row>(f + 8, t1);
+#pragma unroll
+                for (int t = 0; t < 16; t++) ss[nt] = __builtin_fmaf(f[t], f[t], ss[nt]);
+#pragma unroll
+                for (int u = 0; u < 2; u++) {
+                    uint4 hi, lo;
+                    split_bf16x8(f + 8 * u, hi, lo);
+                    bh[nt][2 * k2 + u] = __builtin_bit_cast(bf16x8, hi);
+                    bl[nt][2 * k2 + u] = __builtin_bit_cast(bf16x8, lo);
+                }
+            }
+        }
+#pragma unroll
+        for (int nt = 0; nt < 2; nt++) {
+            const float yn = ss[nt] + __shfl_xor(ss[nt], 32, 64);
+            hrow[nt] = !live[nt] ? (L2 ? INFINITY : -INFINITY) : (L2 ? 0.5f * (1.f - FM_C) * yn : __builtin_sqrtf(yn));
+        }
+    }
+#pragma unroll
+    for (int nt = 0; nt < (SQ8 ? 0 : 2); nt++) {   // (every other row type)
         const int64_t r = r0 + nt * 32 + j;
         const bool live = r < a.ny;
         const Row* yp = a.y + (live ? r : 0) * D + (D / 2) * kh;   // this lane's half row, contiguous
@@ -330,7 +380,7 @@ template <bool L2, class Row = float>
 __global__ __launch_bounds__(256) void k_flat_exact(const uint2* __restrict__ pairs, const int* __restrict__ npairs, int cap,
                                                     const float* __restrict__ x, int d, const Row* __restrict__ store,
                                                     FilterDesc filt, int use_filter, float min_score, float max_score,
-                                                    FlatEmit em, int* __restrict__ overflow) {
+                                                    FlatEmit em, int* __restrict__ overflow, RowTab<Row> tab) {
     const int l8 = threadIdx.x & 7, g = threadIdx.x >> 3;
     // the list is FM_NSUB segments of `cap` slots (k_flat_filter): their counts, prefix-summed, index the survivors
     __shared__ int s_off[FM_NSUB + 1];
@@ -361,7 +411,11 @@ __global__ __launch_bounds__(256) void k_flat_exact(const uint2* __restrict__ pa
         const uint2 pr = live ? pairs[(int64_t)sg * cap + (s - s_off[sg])] : make_uint2(0u, 0u);
         const int q = (int)pr.x;
         const int64_t row = (int64_t)pr.y;
-        float dis = rerank_dist8<L2>(x + (int64_t)q * d, store + row * d, d, l8, live);
+        float dis;
+        if constexpr (RowKind<Row>::sq8)
+            dis = rerank_dist8_sq8<L2>(x + (int64_t)q * d, reinterpret_cast<const uint8_t*>(store) + row * d, tab.t, d, l8, live);
+        else
+            dis = rerank_dist8<L2>(x + (int64_t)q * d, store + row * d, d, l8, live);
         if (live && l8 == 0) {
             const uint32_t t = em.tau[q];
             const float tau_q = t >= 0xff800000u ? (L2 ? 3.402823466e+38f : -3.402823466e+38f) : key2f(L2 ? t : ~t);
@@ -478,12 +532,14 @@ __global__ __launch_bounds__(FM_NT) void k_flat_filter_big(FlatFilterArgs<Row> a
         Raw8<Row> v[2];   // the step's 8 elements of each row as loaded: 32 / 16 / 8 bytes
 #pragma unroll
         for (int nt = 0; nt < 2; nt++) v[nt] = row_load8<Row>(yp[nt]);
+        Tab8<Row> tt = tab8_load<Row>(a, (D / 2) * kh);   // (sq8 rows: the step's table entries, once for both rows)
         for (int kk = 0; kk < KK; kk++) {
             bf16x8 bh[2], bl[2];
 #pragma unroll
             for (int nt = 0; nt < 2; nt++) {
                 float f[8];
                 row_widen8<Row>(v[nt], f);
+                row_decode8<Row>(f, tt);
 #pragma unroll
                 for (int t = 0; t < 8; t++) ss[nt] = __builtin_fmaf(f[t], f[t], ss[nt]);
                 uint4 hi, lo;
@@ -499,6 +555,7 @@ __global__ __launch_bounds__(FM_NT) void k_flat_filter_big(FlatFilterArgs<Row> a
             if (kk + 1 < KK) {   // the next step's elements, in flight during this step's products
 #pragma unroll
                 for (int nt = 0; nt < 2; nt++) v[nt] = row_load8<Row>(yp[nt] + 8 * (kk + 1));
+                tt = tab8_load<Row>(a, (D / 2) * kh + 8 * (kk + 1));
             }
             const bf16x8 ah = *reinterpret_cast<const bf16x8*>(tb + ((0 * KK + kk) * 2) * 512);
             const bf16x8 al = *reinterpret_cast<const bf16x8*>((lo_in_l2 ? tg : tb) + ((1 * KK + kk) * 2) * 512);
@@ -601,7 +658,7 @@ __device__ __forceinline__ RawAny<Row, AL> row_load8_masked(const Row* __restric
     RawAny<Row, AL> r;
     if constexpr (!AL) {
 #pragma unroll
-        for (int t = 0; t < 8; t++) r.e[t] = t < n ? p[t] : (Row)0;
+        for (int t = 0; t < 8; t++) r.e[t] = t < n ? p[t] : Row{};
     } else if constexpr (RowKind<Row>::fp32) {
         r.v.a = make_float4(0.f, 0.f, 0.f, 0.f);
         r.v.b = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -610,7 +667,7 @@ __device__ __forceinline__ RawAny<Row, AL> row_load8_masked(const Row* __restric
     } else if constexpr (RowKind<Row>::half) {
         r.v.a = make_uint4(0u, 0u, 0u, 0u);
         if (n >= 8) r.v.a = *reinterpret_cast<const uint4*>(p);
-    } else {
+    } else {   // (bytes, sq8 codes)
         r.v.a = make_uint2(0u, 0u);
         if (n >= 8) r.v.a = *reinterpret_cast<const uint2*>(p);
     }
@@ -696,12 +753,16 @@ __global__ __launch_bounds__(FM_NT) void k_flat_filter_any(FlatFilterArgs<Row> a
         RawAny<Row, AL> v[2];
 #pragma unroll
         for (int nt = 0; nt < 2; nt++) v[nt] = row_load8_masked<Row, AL>(yp[nt], lim[nt]);
+        // (sq8 rows: the step's table entries, once for both rows; entries behind element D are {0, 0}, so that a masked code --
+        //  0 -- decodes to the exact zero the padding needs)
+        Tab8<Row> tt = tab8_load<Row>(a, (DP / 2) * kh, half_n);
         auto kstep = [&](int kk, const char* hp, const char* lp) {
             bf16x8 bh[2], bl[2];
 #pragma unroll
             for (int nt = 0; nt < 2; nt++) {
                 float f[8];
                 row_widen8_any<Row, AL>(v[nt], f);
+                row_decode8<Row>(f, tt);
 #pragma unroll
                 for (int t = 0; t < 8; t++) ss[nt] = __builtin_fmaf(f[t], f[t], ss[nt]);
                 uint4 hi, lo;
@@ -717,6 +778,7 @@ __global__ __launch_bounds__(FM_NT) void k_flat_filter_any(FlatFilterArgs<Row> a
             if (kk + 1 < KK) {   // the next step's elements, in flight during this step's products
 #pragma unroll
                 for (int nt = 0; nt < 2; nt++) v[nt] = row_load8_masked<Row, AL>(yp[nt] + 8 * (kk + 1), lim[nt] - 8 * (kk + 1));
+                tt = tab8_load<Row>(a, (DP / 2) * kh + 8 * (kk + 1), half_n - 8 * (kk + 1));
             }
             const bf16x8 ah = *reinterpret_cast<const bf16x8*>(hp + ((0 * KK + kk) * 2) * 512);
             const bf16x8 al = *reinterpret_cast<const bf16x8*>(lp + ((1 * KK + kk) * 2) * 512);
@@ -842,9 +904,11 @@ size_t flat_filter_bounds_bytes(int nq) { return (size_t)2 * ((nq + FM_QT - 1) /
 
 template <class Row>
 static void flat_filter_rows(hipStream_t s, bool l2, int d, const void* qimage, const float* xn, const uint32_t* tau, float* bounds,
-                             int nq, const Row* y, int64_t ny, int64_t row_base, void* pairs, int* npairs, int64_t cap) {
+                             int nq, const Row* y, int64_t ny, int64_t row_base, void* pairs, int* npairs, int64_t cap,
+                             const float* tab = nullptr) {
     if (nq <= 0 || ny <= 0) return;
     FlatFilterArgs<Row> a;
+    static_cast<RowTab<Row>&>(a) = row_tab<Row>(tab);
     a.qimg = static_cast<const char*>(qimage);
     a.nq = nq;
     a.nq_pad = (nq + FM_QT - 1) / FM_QT * FM_QT;
@@ -869,7 +933,7 @@ static void flat_filter_rows(hipStream_t s, bool l2, int d, const void* qimage, 
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_flat_filter_any<false, false, Row>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 << 10);
         }
         // wide loads need every row start and every group of 8 elements aligned to the load
-        const bool al = RowKind<Row>::fp32 ? d % 4 == 0 : d % 8 == 0;
+        const bool al = RowKind<Row>::fp32 ? d % 4 == 0 : d % 8 == 0;   // (sq8 codes: the byte rows' rule)
         const int qb = a.nq_pad / 32;
         const int64_t steps = (a.ny + 255) / 256;
         const int slices = (int)std::max<int64_t>(1, std::min<int64_t>(steps, (2048 + qb - 1) / qb));
@@ -929,6 +993,7 @@ void launch_flat_filter(hipStream_t s, bool l2, int d, const void* qimage, const
         case 1: flat_filter_rows(s, l2, d, qimage, xn, tau, bounds, nq, y.as<uint16_t>(), ny, row_base, pairs, npairs, cap); break;
         case 2: flat_filter_rows(s, l2, d, qimage, xn, tau, bounds, nq, y.as<uint8_t>(), ny, row_base, pairs, npairs, cap); break;
         case 3: flat_filter_rows(s, l2, d, qimage, xn, tau, bounds, nq, y.as<int8_t>(), ny, row_base, pairs, npairs, cap); break;
+        case 4: flat_filter_rows(s, l2, d, qimage, xn, tau, bounds, nq, y.as<sq8_t>(), ny, row_base, pairs, npairs, cap, y.tab); break;
         default: launch_refused("launch_flat_filter: unknown row element type");
     }
 }
@@ -936,7 +1001,7 @@ void launch_flat_filter(hipStream_t s, bool l2, int d, const void* qimage, const
 template <class Row>
 static void flat_exact_rows(hipStream_t s, bool l2, const void* pairs, const int* npairs, int64_t cap, const float* x, int nq, int d,
                             const Row* store, const FilterDesc& filt, float min_score, float max_score, const FlatEmit& em,
-                            int* overflow) {
+                            int* overflow, const float* tab = nullptr) {
     if (nq <= 0) return;
     const int use_filter = (filt.del_bitmap || filt.has_range || filt.n_field > 0 || filt.n_term > 0 || filt.vid2doc) ? 1 : 0;
     const dim3 grid(1024);
@@ -944,10 +1009,10 @@ static void flat_exact_rows(hipStream_t s, bool l2, const void* pairs, const int
     const int icap = (int)std::min<int64_t>(cap / FM_NSUB, INT32_MAX);   // per segment
     if (l2)
         hipLaunchKernelGGL((k_flat_exact<true, Row>), grid, dim3(256), 0, s, pp, npairs, icap, x, d, store, filt, use_filter, min_score,
-                           max_score, em, overflow);
+                           max_score, em, overflow, row_tab<Row>(tab));
     else
         hipLaunchKernelGGL((k_flat_exact<false, Row>), grid, dim3(256), 0, s, pp, npairs, icap, x, d, store, filt, use_filter,
-                           min_score, max_score, em, overflow);
+                           min_score, max_score, em, overflow, row_tab<Row>(tab));
 }
 void launch_flat_exact(hipStream_t s, bool l2, const void* pairs, const int* npairs, int64_t cap, const float* x, int nq, int d,
                        const float* store, const FilterDesc& filt, float min_score, float max_score, const FlatEmit& em,
@@ -962,6 +1027,7 @@ void launch_flat_exact(hipStream_t s, bool l2, const void* pairs, const int* npa
         case 1: flat_exact_rows(s, l2, pairs, npairs, cap, x, nq, d, store.as<uint16_t>(), filt, min_score, max_score, em, overflow); break;
         case 2: flat_exact_rows(s, l2, pairs, npairs, cap, x, nq, d, store.as<uint8_t>(), filt, min_score, max_score, em, overflow); break;
         case 3: flat_exact_rows(s, l2, pairs, npairs, cap, x, nq, d, store.as<int8_t>(), filt, min_score, max_score, em, overflow); break;
+        case 4: flat_exact_rows(s, l2, pairs, npairs, cap, x, nq, d, store.as<sq8_t>(), filt, min_score, max_score, em, overflow, store.tab); break;
         default: launch_refused("launch_flat_exact: unknown row element type");
     }
 }

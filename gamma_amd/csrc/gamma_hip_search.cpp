@@ -1336,6 +1336,7 @@ int ivfpq_search_device_locked(H* h, const gamma_hip_search_params* p, int nq, c
 
 // the raw store's rows as the exact scanners' kernels take them: base pointer + element type (kernels.h)
 gh::RowsRef raw_rows_ref(const H* h) {
+    if (h->raw_sq8) return gh::RowsRef{h->d_raw_q, 4, h->d_sq8_tab};   // the codes and their decode table
     return gh::RowsRef{h->raw_byte ? static_cast<const void*>(h->d_raw_b) : h->raw_half ? static_cast<const void*>(h->d_raw_h)
                                                                                      : static_cast<const void*>(h->d_raw),
                        h->raw_elem_type()};
@@ -1571,7 +1572,7 @@ int flat_search_device_locked(H* h, const gamma_hip_search_params* p, int nq, co
     // (a narrow store is served only after gamma_hip_set_flat_narrow_rows: the refusal is what every caller had before)
     if (h->raw_half && !h->flat_narrow_rows) return half_refuse(h, "flat search");
     if (h->raw_byte && !h->flat_narrow_rows) return byte_refuse(h, "flat search");
-    if (h->raw_sq8) return sq8_refuse(h, "flat search");   // (whatever the switch says)
+    if (h->raw_sq8 && !h->flat_sq8_rows) return sq8_refuse(h, "flat search");   // (whatever that switch says: gamma_hip_set_flat_sq8_rows is this store's)
     GH_TRY(check_params(h, p, nq, k));
     gamma_hip_search_params pp;   // (the chunked paths run for k + 1 results: k = 4096, the ABI's largest, is beyond the mode)
     GH_TRY(resolve_ties(h, p, &pp, k + 1 <= gh::tie_replay_max_k() && h->nraw < ((int64_t)1 << 31),

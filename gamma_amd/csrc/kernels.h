@@ -80,12 +80,14 @@ void launch_pairwise_filtered(hipStream_t s, bool l2, const float* x, int nq, in
                               const FilterDesc& filt, float min_score, float max_score,
                               int64_t row_base);
 // Rows of the raw store as the flat path's readers take them: base pointer and element type (gamma_hip_raw_elem_type: 0 fp32,
-// 1 float16, 2 uint8, 3 int8).  The overloads that take one launch, for et == 0, exactly what the float overloads launch.
+// 1 float16, 2 uint8, 3 int8, 4 sq8).  The overloads that take one launch, for et == 0, exactly what the float overloads launch.
+// tab (et == 4 only): the store's decode table, d x {step[j], vmin[j]} -- per dimension, the same for every row.
 struct RowsRef {
     const void* p = nullptr;
     int et = 0;
+    const float* tab = nullptr;
     size_t esz() const { return et == 0 ? 4 : et == 1 ? 2 : 1; }
-    RowsRef at(int64_t row, int d) const { return RowsRef{static_cast<const char*>(p) + (size_t)row * d * esz(), et}; }
+    RowsRef at(int64_t row, int d) const { return RowsRef{static_cast<const char*>(p) + (size_t)row * d * esz(), et, tab}; }
     template <class T> const T* as() const { return static_cast<const T*>(p); }
 };
 void launch_pairwise_filtered(hipStream_t s, bool l2, const float* x, int nq, int d, const RowsRef& y, int64_t ny, float* out,

@@ -42,13 +42,15 @@ const char* launch_refused_take() {
 // ------------------------------------------------------------------------------------
 // Row: the rows' element type (float; uint16_t = IEEE binary16, uint8_t, int8_t: flat search over a narrow store,
 // gamma_hip_set_flat_narrow_rows).  A narrow row is widened as it is loaded -- exactly -- and is fp32 from then on.
+// sq8_t (gamma_hip_set_flat_sq8_rows): rows of scalar-quantised codes, loaded like uint8 rows and decoded ONCE, as they are
+// loaded, into the registers the fp32 kernel holds its row in (tab: RowTab<Row>, flat_rows_dev.h -- empty for every other type).
 template <bool L2, int D, bool FILTER, class Row = float>
 __device__ __forceinline__ void pairwise_rowreg_body(int bx, int by, const float* __restrict__ x, int nq,
                                                      const Row* __restrict__ y, int64_t ny,
                                                      float* __restrict__ out, int64_t ld_out,
                                                      int q_per_block, const FilterDesc& filt,
                                                      float min_score, float max_score,
-                                                     float sentinel, int64_t row_base) {
+                                                     float sentinel, int64_t row_base, RowTab<Row> tab) {
     const int64_t row = (int64_t)bx * 256 + threadIdx.x;
     const int q0 = by * q_per_block;
     const int q1 = min(nq, q0 + q_per_block);
@@ -66,6 +68,13 @@ __device__ __forceinline__ void pairwise_rowreg_body(int bx, int by, const float
                 row_dword_f<Row>(v.y, yr + P16 * i + PD);
                 row_dword_f<Row>(v.z, yr + P16 * i + 2 * PD);
                 row_dword_f<Row>(v.w, yr + P16 * i + 3 * PD);
+            }
+            if constexpr (RowKind<Row>::sq8) {   // element i is at i in every thread: the table comes through the scalar cache
+#pragma unroll
+                for (int i = 0; i < D; i++) {
+                    const float2 e = tab.t[i];
+                    yr[i] = sq8_dec(yr[i], e.x, e.y);
+                }
             }
         } else {
 #pragma unroll
@@ -115,9 +124,9 @@ __global__ __launch_bounds__(256) void k_pairwise_rowreg(const float* __restrict
                                                          float* __restrict__ out, int64_t ld_out,
                                                          int q_per_block, FilterDesc filt,
                                                          float min_score, float max_score,
-                                                         float sentinel, int64_t row_base) {
+                                                         float sentinel, int64_t row_base, RowTab<Row> tab) {
     pairwise_rowreg_body<L2, D, FILTER, Row>(blockIdx.x, blockIdx.y, x, nq, y, ny, out, ld_out, q_per_block, filt, min_score,
-                                             max_score, sentinel, row_base);
+                                             max_score, sentinel, row_base, tab);
 }
 
 // Same contract, queries staged in LDS and broadcast (one ds_read_b128 feeds a whole wave), packed
@@ -136,7 +145,7 @@ __global__ __launch_bounds__(256) void k_pairwise_lds(const float* __restrict__ 
                                                       float* __restrict__ out, int64_t ld_out,
                                                       int q_per_block, FilterDesc filt, float min_score,
                                                       float max_score, float sentinel, int64_t row_base,
-                                                      FlatEmit em) {
+                                                      FlatEmit em, RowTab<Row> tab) {
     // Two threads per database row: the even one owns AVX lanes 0-3 (elements 8i .. 8i+3), the odd
     // one lanes 4-7, D/2 row values each -- half the registers of a whole row per thread, so
     // several waves fit per SIMD.  Per lane the accumulation order is untouched; the pair's sums
@@ -152,7 +161,7 @@ __global__ __launch_bounds__(256) void k_pairwise_lds(const float* __restrict__ 
     const int q1 = min(nq, q0 + q_per_block);
     f32x2 yr[D / 4];
     const bool live = row < ny;
-    row_pair_load<Row, D>(y + (live ? row : 0) * D, half, yr);   // (flat_rows_dev.h: narrow rows widen here, exactly)
+    row_pair_load<Row, D>(y + (live ? row : 0) * D, half, yr, tab);   // (flat_rows_dev.h: narrow rows widen here, exactly; sq8 rows decode)
     bool valid = live;
     if (FILTER && live) valid = is_valid_doc(filt, row_base + row);
     for (int qt = q0; qt < q1; qt += PW_QT) {
@@ -229,7 +238,7 @@ __global__ __launch_bounds__(256) void k_pairwise_generic(const float* __restric
                                                           float* __restrict__ out, int64_t ld_out,
                                                           int q_per_block, FilterDesc filt,
                                                           float min_score, float max_score,
-                                                          float sentinel, int64_t row_base) {
+                                                          float sentinel, int64_t row_base, RowTab<Row> tab) {
     const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (row >= ny) return;
     const int q0 = blockIdx.y * q_per_block;
@@ -240,6 +249,7 @@ __global__ __launch_bounds__(256) void k_pairwise_generic(const float* __restric
     for (int q = q0; q < q1; q++) {
         float dis;
         if constexpr (RowKind<Row>::fp32) dis = fvec_dist<L2>(x + (int64_t)q * d, yr, d);
+        else if constexpr (RowKind<Row>::sq8) dis = fvec_dist<L2>(x + (int64_t)q * d, RowElems<Row>{yr, tab.t}, d);
         else dis = fvec_dist<L2>(x + (int64_t)q * d, RowElems<Row>{yr}, d);
         if (FILTER) {
             if (!valid || !(dis <= max_score && dis >= min_score)) dis = sentinel;
@@ -272,12 +282,12 @@ static int pairwise_q_per_block(int nq, int64_t row_blocks) {
 template <bool L2, class Row = float>
 static void launch_pairwise_emit_t(hipStream_t s, const float* x, int nq, int d, const Row* y, int64_t ny,
                                    const FilterDesc& filt, float min_score, float max_score, float sentinel,
-                                   int64_t row_base, const FlatEmit& em) {
+                                   int64_t row_base, const FlatEmit& em, RowTab<Row> tab = RowTab<Row>{}) {
     const int q_per_block = pairwise_q_per_block(nq, (ny + 255) / 256);
     const dim3 grid((unsigned)((ny + 127) / 128), (unsigned)((nq + q_per_block - 1) / q_per_block));
 #define GH_EMIT(DD)                                                                                         \
     hipLaunchKernelGGL((k_pairwise_lds<L2, DD, true, true, Row>), grid, dim3(256), 0, s, x, nq, y, ny, nullptr, 0, \
-                       q_per_block, filt, min_score, max_score, sentinel, row_base, em)
+                       q_per_block, filt, min_score, max_score, sentinel, row_base, em, tab)
     switch (d) {
         case 128: GH_EMIT(128); break;
         case 96: GH_EMIT(96); break;
@@ -301,7 +311,7 @@ template <bool L2, bool FILTER, class Row = float>
 static void launch_pairwise_t(hipStream_t s, const float* x, int nq, int d, const Row* y,
                               int64_t ny, float* out, int64_t ld_out, const FilterDesc& filt,
                               float min_score, float max_score, float sentinel,
-                              int64_t row_base) {
+                              int64_t row_base, RowTab<Row> tab = RowTab<Row>{}) {
     if (ny <= 0 || nq <= 0) return;
     const int64_t row_blocks = (ny + 255) / 256;
     const int q_per_block = pairwise_q_per_block(nq, row_blocks);
@@ -314,10 +324,10 @@ static void launch_pairwise_t(hipStream_t s, const float* x, int nq, int d, cons
         if (use_lds)                                                                                   \
             hipLaunchKernelGGL((k_pairwise_lds<L2, DD, FILTER, false, Row>), dim3((unsigned)((ny + 127) / 128), grid.y), \
                                dim3(256), 0, s, x, nq, y, ny, out, ld_out, q_per_block, filt, min_score, \
-                               max_score, sentinel, row_base, FlatEmit{});                             \
+                               max_score, sentinel, row_base, FlatEmit{}, tab);                        \
         else                                                                                           \
             hipLaunchKernelGGL((k_pairwise_rowreg<L2, DD, FILTER, Row>), grid, dim3(256), 0, s, x, nq, y, ny, \
-                               out, ld_out, q_per_block, filt, min_score, max_score, sentinel, row_base); \
+                               out, ld_out, q_per_block, filt, min_score, max_score, sentinel, row_base, tab); \
     } while (0)
     switch (d) {
         case 128: GH_ROWREG(128); break;
@@ -328,7 +338,7 @@ static void launch_pairwise_t(hipStream_t s, const float* x, int nq, int d, cons
         default:
             hipLaunchKernelGGL((k_pairwise_generic<L2, FILTER, Row>), grid, dim3(256), 0, s, x, nq, d, y,
                                ny, out, ld_out, q_per_block, filt, min_score, max_score, sentinel,
-                               row_base);
+                               row_base, tab);
     }
 #undef GH_ROWREG
 }
@@ -432,13 +442,14 @@ void launch_pairwise_filtered(hipStream_t s, bool l2, const float* x, int nq, in
                                        -INFINITY, row_base);
 }
 
-// ---- flat search over a narrow raw store: the same launches over rows of float16 / uint8 / int8 (fp32 rows go through the
-//      entry points above: same instantiation, same grid) ----
+// ---- flat search over a narrow raw store: the same launches over rows of float16 / uint8 / int8, and over sq8 codes with
+//      their decode table (fp32 rows go through the entry points above: same instantiation, same grid) ----
 template <class Row>
 static void pairwise_filtered_rows(hipStream_t s, bool l2, const float* x, int nq, int d, const Row* y, int64_t ny, float* out,
-                                   int64_t ld_out, const FilterDesc& filt, float min_score, float max_score, int64_t row_base) {
-    if (l2) launch_pairwise_t<true, true, Row>(s, x, nq, d, y, ny, out, ld_out, filt, min_score, max_score, INFINITY, row_base);
-    else launch_pairwise_t<false, true, Row>(s, x, nq, d, y, ny, out, ld_out, filt, min_score, max_score, -INFINITY, row_base);
+                                   int64_t ld_out, const FilterDesc& filt, float min_score, float max_score, int64_t row_base,
+                                   const float* tab = nullptr) {
+    if (l2) launch_pairwise_t<true, true, Row>(s, x, nq, d, y, ny, out, ld_out, filt, min_score, max_score, INFINITY, row_base, row_tab<Row>(tab));
+    else launch_pairwise_t<false, true, Row>(s, x, nq, d, y, ny, out, ld_out, filt, min_score, max_score, -INFINITY, row_base, row_tab<Row>(tab));
 }
 void launch_pairwise_filtered(hipStream_t s, bool l2, const float* x, int nq, int d, const RowsRef& y, int64_t ny, float* out,
                               int64_t ld_out, const FilterDesc& filt, float min_score, float max_score, int64_t row_base) {
@@ -447,15 +458,17 @@ void launch_pairwise_filtered(hipStream_t s, bool l2, const float* x, int nq, in
         case 1: pairwise_filtered_rows(s, l2, x, nq, d, y.as<uint16_t>(), ny, out, ld_out, filt, min_score, max_score, row_base); break;
         case 2: pairwise_filtered_rows(s, l2, x, nq, d, y.as<uint8_t>(), ny, out, ld_out, filt, min_score, max_score, row_base); break;
         case 3: pairwise_filtered_rows(s, l2, x, nq, d, y.as<int8_t>(), ny, out, ld_out, filt, min_score, max_score, row_base); break;
+        case 4: pairwise_filtered_rows(s, l2, x, nq, d, y.as<sq8_t>(), ny, out, ld_out, filt, min_score, max_score, row_base, y.tab); break;
         default: launch_refused("launch_pairwise_filtered: unknown row element type");
     }
 }
 template <class Row>
 static void pairwise_emit_rows(hipStream_t s, bool l2, const float* x, int nq, int d, const Row* y, int64_t ny,
-                               const FilterDesc& filt, float min_score, float max_score, int64_t row_base, const FlatEmit& em) {
+                               const FilterDesc& filt, float min_score, float max_score, int64_t row_base, const FlatEmit& em,
+                               const float* tab = nullptr) {
     if (ny <= 0 || nq <= 0) return;
-    if (l2) launch_pairwise_emit_t<true, Row>(s, x, nq, d, y, ny, filt, min_score, max_score, INFINITY, row_base, em);
-    else launch_pairwise_emit_t<false, Row>(s, x, nq, d, y, ny, filt, min_score, max_score, -INFINITY, row_base, em);
+    if (l2) launch_pairwise_emit_t<true, Row>(s, x, nq, d, y, ny, filt, min_score, max_score, INFINITY, row_base, em, row_tab<Row>(tab));
+    else launch_pairwise_emit_t<false, Row>(s, x, nq, d, y, ny, filt, min_score, max_score, -INFINITY, row_base, em, row_tab<Row>(tab));
 }
 void launch_pairwise_emit(hipStream_t s, bool l2, const float* x, int nq, int d, const RowsRef& y, int64_t ny,
                           const FilterDesc& filt, float min_score, float max_score, int64_t row_base, const FlatEmit& em) {
@@ -464,6 +477,7 @@ void launch_pairwise_emit(hipStream_t s, bool l2, const float* x, int nq, int d,
         case 1: pairwise_emit_rows(s, l2, x, nq, d, y.as<uint16_t>(), ny, filt, min_score, max_score, row_base, em); break;
         case 2: pairwise_emit_rows(s, l2, x, nq, d, y.as<uint8_t>(), ny, filt, min_score, max_score, row_base, em); break;
         case 3: pairwise_emit_rows(s, l2, x, nq, d, y.as<int8_t>(), ny, filt, min_score, max_score, row_base, em); break;
+        case 4: pairwise_emit_rows(s, l2, x, nq, d, y.as<sq8_t>(), ny, filt, min_score, max_score, row_base, em, y.tab); break;
         default: launch_refused("launch_pairwise_emit: unknown row element type");
     }
 }

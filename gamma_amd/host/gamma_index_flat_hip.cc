@@ -10,6 +10,7 @@
 #include <strings.h>
 
 #include <algorithm>
+#include <cmath>
 #include <limits>
 
 namespace tig_gamma {
@@ -35,11 +36,59 @@ int RegisterHIPFlatRows(HIPFlatRowsFn fn) {
 }
 HIPFlatRowsFn FindHIPFlatRows() { return FlatRows(); }
 
-int GammaFLATHIPIndex::ParseRawDtype(const std::string &model_parameters, int *et) {
-  return HIPParseRawDtype("HIPFLAT", model_parameters, et);   // shared with HIPIVFFLAT (gamma_index_ivfpq_hip.cc)
+namespace {
+HIPFlatSq8RowsFn &FlatSq8Rows() {
+  static HIPFlatSq8RowsFn fn = nullptr;
+  return fn;
+}
+}  // namespace
+int RegisterHIPFlatSq8Rows(HIPFlatSq8RowsFn fn) {
+  FlatSq8Rows() = fn;
+  return 0;
+}
+HIPFlatSq8RowsFn FindHIPFlatSq8Rows() { return FlatSq8Rows(); }
+
+int GammaFLATHIPIndex::ParseRawDtype(const std::string &model_parameters, int *et, float *sq8_range) {
+  *et = 0;
+  utils::JsonParser jp;
+  std::string rdt;
+  const bool parsed = model_parameters != "" && !jp.Parse(model_parameters.c_str());
+  if (!(parsed && !jp.GetString("raw_dtype", rdt) && !strcasecmp("sq8", rdt.c_str()))) {
+    // every other value: the answer shared with HIPIVFFLAT (gamma_index_ivfpq_hip.cc), which rejects "sq8"
+    if (HIPParseRawDtype("HIPFLAT", model_parameters, et)) return -1;
+    if (parsed && (jp.Contains("sq8_min") || jp.Contains("sq8_max"))) {
+      FLOG("sq8_min / sq8_max come with \"raw_dtype\": \"sq8\" only");
+      *et = 0;
+      return -1;
+    }
+    return 0;
+  }
+  double lo = 0, hi = 0;
+  if (jp.GetDouble("sq8_min", lo) || jp.GetDouble("sq8_max", hi)) {
+    FLOG("raw_dtype = sq8 needs \"sq8_min\" and \"sq8_max\", one range for every dimension, as numbers");
+    return -1;
+  }
+  const float flo = (float)lo, fhi = (float)hi;
+  if (!std::isfinite(flo) || !std::isfinite(fhi) || !(flo <= fhi) || !std::isfinite(fhi - flo)) {
+    FLOG("raw_dtype = sq8: sq8_min = %g, sq8_max = %g is no range (finite as floats, sq8_min <= sq8_max, a finite span)", lo, hi);
+    return -1;
+  }
+  *et = 4;
+  if (sq8_range) {
+    sq8_range[0] = flo;
+    sq8_range[1] = fhi;
+  }
+  return 0;
 }
 
 bool GammaFLATHIPIndex::RowsStorable(const char *what, const float *x, int64_t nrows) {
+  if (raw_et_ == 4) {
+    int64_t bad = -1;
+    if (!raw_sq8_ops_->check(x, nrows * d_, &bad)) return true;
+    FLOG("%s refused: raw_dtype = sq8 stores a value only if it is finite, and element %d of row %lld is %g", what, (int)(bad % d_),
+         (long long)(bad / d_), (double)x[bad]);
+    return false;
+  }
   return raw_et_ < 2 || HIPRowsStorableI8(raw_i8_ops_, raw_et_ == 3, d_, "HIPFLAT", what, x, nrows);   // HIPIVFPQ's rule
 }
 
@@ -62,13 +111,22 @@ int GammaFLATHIPIndex::Init(const std::string &model_parameters, int indexing_si
     if (!jp.GetInt("device_filters", v)) device_filters_ = v != 0;   // HIP only, see filter_bridge.h
     if (!jp.GetInt("exact_ties", v)) exact_ties_ = v != 0;           // HIP only: the reference's heap order inside ties (default on)
   }
-  if (ParseRawDtype(model_parameters, &raw_et_)) return -1;
+  float sq8_range[2] = {0.f, 0.f};
+  if (ParseRawDtype(model_parameters, &raw_et_, sq8_range)) return -1;
   // a narrow store needs its initialiser and the handle's switch; a build without one of them rejects the value
-  const HIPFlatRowsFn flat_rows = raw_et_ ? FindHIPFlatRows() : nullptr;
+  const bool narrow = raw_et_ >= 1 && raw_et_ <= 3;
+  const HIPFlatRowsFn flat_rows = narrow ? FindHIPFlatRows() : nullptr;
   const HIPRawInitFn init_f16 = raw_et_ == 1 ? FindHIPRawInitF16() : nullptr;
-  raw_i8_ops_ = raw_et_ >= 2 ? FindHIPRawI8() : nullptr;
-  if (raw_et_ && (!flat_rows || (raw_et_ == 1 ? !init_f16 : !raw_i8_ops_))) {
+  raw_i8_ops_ = raw_et_ == 2 || raw_et_ == 3 ? FindHIPRawI8() : nullptr;
+  if (narrow && (!flat_rows || (raw_et_ == 1 ? !init_f16 : !raw_i8_ops_))) {
     FLOG("raw_dtype: this build of the plugin has no flat search over float16 / uint8 / int8 rows");
+    return -1;
+  }
+  // (sq8: the store's entries that HIPIVFPQ's sq8 store registered, and a switch of its own)
+  const HIPFlatSq8RowsFn flat_sq8_rows = raw_et_ == 4 ? FindHIPFlatSq8Rows() : nullptr;
+  raw_sq8_ops_ = raw_et_ == 4 ? FindHIPRawSq8() : nullptr;
+  if (raw_et_ == 4 && (!flat_sq8_rows || !raw_sq8_ops_)) {
+    FLOG("raw_dtype: this build of the plugin has no flat search over sq8 rows");
     return -1;
   }
   d_ = vector_->MetaInfo()->Dimension();
@@ -76,6 +134,11 @@ int GammaFLATHIPIndex::Init(const std::string &model_parameters, int indexing_si
   if (gamma_hip_create(dev ? atoi(dev) : 0, &h_)) return -1;
   if (gamma_hip_set_exact_ties(h_, exact_ties_ ? 1 : 0)) return -1;
   if (!raw_et_) return gamma_hip_raw_init(h_, d_) ? -1 : 0;
+  if (raw_et_ == 4) {   // one range for every dimension, from the parameters (Load re-encodes with the same)
+    const std::vector<float> vmin((size_t)d_, sq8_range[0]), vmax((size_t)d_, sq8_range[1]);
+    if (raw_sq8_ops_->init(h_, d_) || raw_sq8_ops_->set_ranges(h_, vmin.data(), vmax.data())) return -1;
+    return flat_sq8_rows(h_, 1) ? -1 : 0;
+  }
   if (raw_et_ == 1 ? init_f16(h_, d_) : raw_i8_ops_->init(h_, d_, raw_et_ == 3)) return -1;
   return flat_rows(h_, 1) ? -1 : 0;
 }
@@ -145,7 +208,7 @@ int GammaFLATHIPIndex::Load(const std::string &dir) {
   }
   std::lock_guard<std::mutex> g(raw_mu_);
   const int64_t nvec = (int64_t)vector_->MetaInfo()->Size();
-  // a byte model: a pass over the rows with the acceptance predicate first, so that a refused row leaves the mirror as it was
+  // a byte or sq8 model: a pass over the rows with the acceptance predicate first, so that a refused row leaves the mirror as it was
   for (int pass = raw_et_ >= 2 ? 0 : 1; pass < 2; pass++)
     for (int64_t i0 = uploaded_; i0 < nvec; i0 += 65536) {
       const int64_t nb = std::min<int64_t>(65536, nvec - i0);

@@ -4,6 +4,9 @@
 // HIP only: "raw_dtype": "float32" (the default) | "float16" | "uint8" | "int8" -- the element type of the device's rows, which
 // ARE the index.  Results are those of the fp32 model over the widened rows; a byte model accepts a row only if every value
 // converts exactly (HIPIVFPQ's rule), a float16 model rounds and refuses an overflow.
+// "raw_dtype": "sq8" with "sq8_min": <number> and "sq8_max": <number> (both required, and only with sq8): rows of one
+// scalar-quantised byte per element, ONE range for every dimension -- a flat model has no training step in which ranges could be
+// learned.  Results are those of the fp32 model over the decoded rows; a row is accepted only if every value is finite.
 #pragma once
 #include <atomic>
 #include <mutex>
@@ -17,12 +20,18 @@
 namespace tig_gamma {
 
 struct HIPRawI8Ops;   // gamma_index_ivfpq_hip.h
+struct HIPRawSq8Ops;  // gamma_index_ivfpq_hip.h
 // Flat search over narrow rows is a switch of the handle (gamma_hip_set_flat_narrow_rows), registered at static-initialisation
 // time by gamma_index_flat_rows_hip.cc -- the only host file that names it (the idiom of RegisterHIPRawI8).  A build of the plugin
 // without that file (against a C ABI without the entry) has none, and HIPFLAT::Init rejects a narrow "raw_dtype".
 typedef int (*HIPFlatRowsFn)(gamma_hip_index *h, int on);
 int RegisterHIPFlatRows(HIPFlatRowsFn fn);
 HIPFlatRowsFn FindHIPFlatRows();
+// The same for an sq8 store: a switch of its own (gamma_hip_set_flat_sq8_rows), registered by gamma_index_flat_sq8_hip.cc -- the
+// only host file that names it.  Without that file HIPFLAT::Init rejects "raw_dtype": "sq8".
+typedef int (*HIPFlatSq8RowsFn)(gamma_hip_index *h, int on);
+int RegisterHIPFlatSq8Rows(HIPFlatSq8RowsFn fn);
+HIPFlatSq8RowsFn FindHIPFlatSq8Rows();
 
 class HIPFlatRetrievalParameters : public RetrievalParameters {
  public:
@@ -57,13 +66,16 @@ class GammaFLATHIPIndex : public RetrievalModel {
   int Load(const std::string &dir) override;
   DistanceComputeType metric_type_ = DistanceComputeType::INNER_PRODUCT;
   // the "raw_dtype" key of the model parameters: *et = 0 float32 (also when the key is absent), 1 float16, 2 uint8, 3 int8
-  // (gamma_hip_raw_elem_type); -1 for any other string or parameters that do not parse
-  static int ParseRawDtype(const std::string &model_parameters, int *et);
+  // (gamma_hip_raw_elem_type), 4 sq8 with its range in sq8_range[2] = {sq8_min, sq8_max} (if given); -1, one log line and
+  // *et = 0 for any other string, parameters that do not parse, sq8 without both of its keys as numbers, a bound that is not
+  // finite as a float, sq8_min > sq8_max or a span that is not finite, and for either key beside another raw_dtype
+  static int ParseRawDtype(const std::string &model_parameters, int *et, float *sq8_range = nullptr);
 
  private:
   int raw_et_ = 0;
   const HIPRawI8Ops *raw_i8_ops_ = nullptr;
-  bool RowsStorable(const char *what, const float *x, int64_t nrows);   // byte rows: every value converts exactly
+  const HIPRawSq8Ops *raw_sq8_ops_ = nullptr;
+  bool RowsStorable(const char *what, const float *x, int64_t nrows);   // byte rows: every value converts exactly; sq8: is finite
   gamma_hip_index *h_ = nullptr;
   std::atomic<int64_t> ties_said_{0};   // WarnTiesNotHonoured: what this model has reported so far
   int d_ = 0;

@@ -210,6 +210,17 @@ int gamma_hip_set_flat_narrow_rows(gamma_hip_index* h, int on);
  * _raw_drop, the combining queue and a sparse store keep refusing a narrow store, and an fp32 store is served as before
  * whatever the switch says. */
 int gamma_hip_set_ivfflat_narrow_rows(gamma_hip_index* h, int on);
+/* Flat search over a scalar-quantised raw store (gamma_hip_raw_init_sq8); a switch of its own, independent of the two above.
+ * on: 0 (default) = gamma_hip_flat_search, _flat_search_device and _flat_search_device_wait refuse an sq8 store with
+ * GAMMA_HIP_EUNSUPPORTED, as before and whatever gamma_hip_set_flat_narrow_rows says; 1 = the three serve it: every code is
+ * decoded as it is loaded, w = vmin[j] + float(code) * step[j] -- a multiply, then an add, each rounded in fp32, never an fma
+ * and never folded into the query -- and every distance is fvec_L2sqr / fvec_inner_product of the fp32 query and the decoded
+ * row, so distances and labels are byte-identical to those of an fp32 store that holds the decoded rows, exact ties included
+ * (DESIGN.md section 20).  The reference has no scalar-quantised flat model; the yardstick is its flat search
+ * (gamma_index_flat.cc:118-300) over the rows the store holds.  Nothing else changes: IVFFLAT search, the shard / merge /
+ * export entries, gamma_hip_raw_put / _raw_drop, the combining queue and a sparse store keep refusing an sq8 store, and an
+ * fp32, float16 or byte store is served or refused as before whatever this switch says. */
+int gamma_hip_set_flat_sq8_rows(gamma_hip_index* h, int on);
 /* out3 = {coarse rows redone, queries whose recall_num cut went through a tie, queries replayed} since creation
  * or the last reset; meaningful with exact ties on */
 int gamma_hip_tie_stats(gamma_hip_index* h, int64_t* out3, int reset);
