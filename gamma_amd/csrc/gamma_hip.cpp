@@ -1,6 +1,7 @@
 // gamma_hip.cpp -- libgamma_hip.so, C ABI of include/gamma_hip.h: the handle's life cycle, the per-handle switches,
 // memory accounting and stage profiling.  The writers (realtime lists, raw store, columns, bitmap) are in
-// gamma_hip_store.cpp, the search pipelines and their entry points in gamma_hip_search.cpp, the handle itself in
+// gamma_hip_store.cpp, the search pipelines and their entry points in gamma_hip_search.cpp and its three siblings
+// (gamma_hip_search_ivfflat.cpp, _flat.cpp, _shard.cpp), the handle itself in
 // gamma_hip_internal.h.  No CPU fallback anywhere: an entry point runs the HIP kernels or returns an error.
 #include "gamma_hip_internal.h"
 

@@ -1,6 +1,7 @@
 // gamma_hip_internal.h -- the handle of libgamma_hip.so (HBM-resident state, workspaces, locks) and the helpers its
 // translation units share: gamma_hip.cpp (life cycle, switches, accounting), gamma_hip_store.cpp (realtime lists,
-// raw store, columns, bitmap: the writers), gamma_hip_search.cpp (the search pipelines and their entry points).
+// raw store, columns, bitmap: the writers), gamma_hip_search.cpp / _ivfflat.cpp / _flat.cpp / _shard.cpp (the search
+// pipelines and their entry points), gamma_hip_combine.cpp (the combining queue).
 #pragma once
 #include "../../include/gamma_hip.h"
 
@@ -426,7 +427,7 @@ struct gamma_hip_index {
         float* D;
         int64_t* I;
         int rc = 0;
-        // delivery (gamma_hip_search.cpp, combine_worker): every waiter sleeps on its OWN mutex + condition variable; the
+        // delivery (gamma_hip_combine.cpp, combine_worker): every waiter sleeps on its OWN mutex + condition variable; the
         // worker's helper copies a batch's rows into the callers' buffers, links the waiters into a forest, wakes the
         // first FAN, and every woken waiter wakes FAN more on its way out -- a batch of 128 is awake after three hops
         // instead of 128 wake-ups issued by one thread through one mutex

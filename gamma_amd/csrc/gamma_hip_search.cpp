@@ -1,10 +1,12 @@
-// gamma_hip_search.cpp -- the search pipelines of libgamma_hip.so (IVFPQ stages A and B, the small-batch chains, IVFFLAT,
-// flat), validity filters, the combining queue of small concurrent calls and the search entry points of the C ABI
-// (include/gamma_hip.h).  No CPU fallback: every entry point runs the HIP kernels or returns an error.
+// gamma_hip_search.cpp -- what every search of libgamma_hip.so shares (validity filters, parameter checks, the exact-ties
+// choice, the coarse quantizer, the exact scanners' row reference and tie-replay arguments), the IVFPQ pipeline (stages A
+// and B, the small-batch chain, list compaction, the chunked driver) and the IVFPQ entry points of the C ABI
+// (include/gamma_hip.h).  IVFFLAT, flat and the list-shard / merge entries are gamma_hip_search_ivfflat.cpp, _flat.cpp and
+// _shard.cpp; the combining queue is gamma_hip_combine.cpp.  No CPU fallback: every entry point runs the HIP kernels or
+// returns an error.
 #include "gamma_hip_internal.h"
 #include "gamma_hip_search.h"
 #include "opq.h"
-#include "pq4.h"
 
 namespace ghi {
 
@@ -130,13 +132,7 @@ int check_params(H* h, const gamma_hip_search_params* p, int nq, int k) {
     return GAMMA_HIP_OK;
 }
 
-// A request's exact-ties choice (gamma_hip_search_params.exact_ties: 0 = the handle's setting, 1 on, -1 off) is resolved
-// ONCE per call, at the entry point, into the call's own copy of the parameter block (exact_ties = 1 / -1); everything
-// below reads tie_on(p) -- the handle is not touched.  in_range: the shape is one the replay covers (every recall_num / k
-// the ABI accepts; nprobe <= 1024).  Beyond it a request that asked for the mode explicitly gets GAMMA_HIP_EUNSUPPORTED;
-// one that relies on the handle's default runs with the (distance, position) order inside ties and is COUNTED
-// (gamma_hip_ties_not_honoured) -- never silently.
-static inline bool tie_on(const gamma_hip_search_params* p) { return p->exact_ties > 0; }
+// (the exact-ties choice of a request: gamma_hip_search.h)
 int resolve_ties(H* h, const gamma_hip_search_params* p, gamma_hip_search_params* pp, bool in_range, const char* what) {
     *pp = *p;
     bool want = p->exact_ties != 0 ? p->exact_ties > 0 : h->exact_ties;
@@ -149,9 +145,7 @@ int resolve_ties(H* h, const gamma_hip_search_params* p, gamma_hip_search_params
     return GAMMA_HIP_OK;
 }
 
-// ---- IVFPQ stage A: coarse + tables + scan + top-R + ids ------------------------------
-// results: w_cand_dis [nq*R] (ADC distance, best first, sentinel pad), w_cand_ids [nq*R]
-// the assignment is complete on the stream (the heap replay of tied rows may still be running on the side stream)
+// ---- the coarse quantizer (IVFPQ and IVFFLAT) ------------------------------------------
 int coarse_join(H* h) {
     if (h->coarse_join_pending) {
         GH_CHECK(h, hipStreamWaitEvent(h->stream, h->ev_join, 0));
@@ -160,9 +154,7 @@ int coarse_join(H* h) {
     return GAMMA_HIP_OK;
 }
 
-// defer_join: the caller has kernels to launch that do not read the assignment and calls coarse_join itself
-int ivfpq_coarse(H* h, const gamma_hip_search_params* p, int nq, const float* d_x, float* out_dis = nullptr,
-                 int* out_probe = nullptr, bool defer_join = false) {
+int ivfpq_coarse(H* h, const gamma_hip_search_params* p, int nq, const float* d_x, float* out_dis, int* out_probe, bool defer_join) {
     const int P = p->nprobe, d = h->d, nlist = h->nlist;
     hipStream_t s = h->stream;
     int mode = p->coarse_mode;
@@ -278,66 +270,11 @@ int ivfpq_coarse(H* h, const gamma_hip_search_params* p, int nq, const float* d_
     return GAMMA_HIP_OK;
 }
 
-// pre_dis / pre_probe: coarse assignment computed elsewhere (sharded search: the rank owning the
-// query slice), device pointers [nq*nprobe]; nullptr = run the coarse quantizer here
-// Two-phase list-shard search (round 6): between the producers (the query's nearest probes OWNED BY THIS SHARD: they
-// bound the shard's recall_num-th best) and the consumers (all its other probes) the bounds of all shards are reduced
-// -- min for L2, max for inner product: one float per query -- so that every shard filters against a bound of the GLOBAL
-// recall_num-th best instead of its own, W times looser one.  `reduce` is the caller's collective (RCCL all-reduce in
-// gamma_amd/dist.py, peer reads in the in-process group); it is called exactly ONCE per shard call, with neutral values
-// when this call cannot run in two phases.
-struct BoundXchg {
-    float* d_bound = nullptr;                  // [nq of the whole call] the caller's buffer; holds the reduced bounds afterwards
-    gamma_hip_bound_reduce_fn fn = nullptr;
-    void* user = nullptr;
-    bool called = false;
-    bool two_phase = false;                    // this call runs in two phases (one chunk, bounded scan possible)
-    int P_in = 0;                              // row length of the supplied assignment (p->nprobe is the compacted rows')
-    int G1 = 2;                                // probes of the producers' group
-    int reduce(H* h, int nq, bool l2) {
-        called = true;
-        const int rc = fn ? fn(user, d_bound, nq, l2 ? 0 : 1, (void*)h->stream) : 0;
-        return rc ? fail(h, GAMMA_HIP_EDEVICE, "bound reduction callback failed") : GAMMA_HIP_OK;
-    }
-};
-
-// a 4-bit handle (gamma_hip_ivfpq4_init) behind an entry point that is 8-bit only: never silent
-static int pq4_refuse(H* h, const char* what) {
-    h->err = std::string("4-bit handle: ") + what + " is 8-bit only";
-    return GAMMA_HIP_EUNSUPPORTED;
-}
-// a handle with an OPQ matrix (gamma_hip_opq_set) behind an entry point that takes vectors or candidates of several handles:
-// the list shards and their merge rotate nothing -- refused, never silent
-static int opq_refuse(H* h, const char* what) {
-    h->err = std::string("handle with an OPQ matrix: ") + what + " is not supported";
-    return GAMMA_HIP_EUNSUPPORTED;
-}
-// a float16 raw store (gamma_hip_raw_init_f16) behind a reader of fp32 rows: the exact re-rank of the IVFPQ search and its tie
-// replay read half rows, nothing else does -- refused, never silent
-static int half_refuse(H* h, const char* what) {
-    h->err = std::string("float16 raw store (gamma_hip_raw_init_f16): ") + what + " reads fp32 rows and is not supported";
-    return GAMMA_HIP_EUNSUPPORTED;
-}
-// the same for a store of byte rows (gamma_hip_raw_init_i8)
-static int byte_refuse(H* h, const char* what) {
-    h->err = std::string("8-bit raw store (gamma_hip_raw_init_i8): ") + what + " reads fp32 rows and is not supported";
-    return GAMMA_HIP_EUNSUPPORTED;
-}
-// and for a store of scalar-quantised rows (gamma_hip_raw_init_sq8): only the IVFPQ re-rank and its tie replay decode them
-static int sq8_refuse(H* h, const char* what) {
-    h->err = std::string("sq8 raw store (gamma_hip_raw_init_sq8): ") + what + " reads fp32 rows and is not supported";
-    return GAMMA_HIP_EUNSUPPORTED;
-}
-// (every entry point that refuses the one refuses the other: the shard, merge and export entries)
-#define GH_NO_PQ4(h, what)                                                \
-    do {                                                                  \
-        if ((h)->ksub == gh::kPq4Ksub) return pq4_refuse((h), (what));    \
-        if ((h)->d_opq) return opq_refuse((h), (what));                   \
-    } while (0)
-
+// ---- IVFPQ stage A: coarse + tables + scan + top-R + ids ------------------------------
+// results: w_cand_dis [nq*R] (ADC distance, best first, sentinel pad), w_cand_ids [nq*R]
 int ivfpq_stage_a(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int nq,
-                  const float* d_x, int R, const float* pre_dis = nullptr, const int* pre_probe = nullptr,
-                  bool shard = false, float* out_dis = nullptr, int64_t* out_ids = nullptr, BoundXchg* bx = nullptr) {
+                  const float* d_x, int R, const float* pre_dis, const int* pre_probe,
+                  bool shard, float* out_dis, int64_t* out_ids, BoundXchg* bx) {
     const int P = p->nprobe, d = h->d, M = h->M, nlist = h->nlist;
     const bool two = bx && bx->two_phase;
     const bool l2 = p->metric == GAMMA_HIP_METRIC_L2;
@@ -850,10 +787,9 @@ int ivfpq_stage_a(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int
 // ---- stage B: compute_dis (gamma_index_ivfpq.cc:642-697) ------------------------------
 int ivfpq_stage_b(H* h, const gamma_hip_search_params* p, int nq, const float* d_x, int R, int k,
                   const float* cand_dis, const int64_t* cand_ids, float* d_distances,
-                  int64_t* d_labels, const int* qperm = nullptr, int tie_mode = 0) {   // 1: flag + replay; 2: flag only
-                                                                                         // (merge of shards: w_tcut / w_tlist set up by the caller)
+                  int64_t* d_labels, const int* qperm, int tie_mode) {
     const bool l2 = p->metric == GAMMA_HIP_METRIC_L2;
-    const float neutral = l2 ? 3.402823466e+38f : -3.402823466e+38f;
+    const float neutral = neutral_of(l2);
     hipStream_t s = h->stream;
     StageScope t(h, GAMMA_HIP_STAGE_RERANK);
     // exact ties: the final-stage kernel lists the queries with a tie among their first k+1 distances (or with a
@@ -1014,7 +950,7 @@ int ivfpq_small(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int n
     GH_CHECK(h, h->w_cand_pos.ensure((size_t)nq * R * sizeof(int)));
     GH_CHECK(h, h->w_cand_dis.ensure((size_t)nq * R * sizeof(float)));
     GH_CHECK(h, h->w_cand_ids.ensure((size_t)nq * R * sizeof(int64_t)));
-    const int64_t q_stride = (std::max<int64_t>(1, (int64_t)P * std::max(1, h->max_list_len)) + 3) & ~(int64_t)3;
+    const int64_t q_stride = slab_q_stride(h, P);
     GH_CHECK(h, h->w_dist.ensure((size_t)nq * q_stride * sizeof(float)));
     // (folding the selection into the first launch -- last workgroup done selects -- was tried: the device-scope
     // release / acquire it needs costs more than the launch it saves, 24 us against 4 + 8: the XCDs' L2s are
@@ -1061,20 +997,13 @@ int ivfpq_small(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int n
                                h->d_codes, h->d_ids, h->w_pair_off.as<int>(), q_stride, h->w_dist.as<float>(), fc.d_tab,
                                fc.d_qf, need_ids, nullptr, 1, 0, P, 0, nullptr, nullptr, reinterpret_cast<const int*>(d_units), d_nunits,
                                chunk_len, max_units);
-    const float neutral = l2 ? 3.402823466e+38f : -3.402823466e+38f;
+    const float neutral = neutral_of(l2);
     // long candidate rows (expected nprobe x 1.5 mean list lengths beyond what one workgroup keeps in registers): a first
     // selection over slices of the row by several workgroups per query, then the tail among their survivors
-    int smax = 0;
-    {
-        const int64_t slice = 16384;   // select.hip SM_SLICE
-        const int64_t est = (int64_t)P * (h->ntotal / std::max(1, nlist)) * 3 / 2;
-        const int64_t bound = (int64_t)P * std::max(1, h->max_list_len);
-        if (h->small_presel > 0) smax = h->small_presel;
-        else if (est > slice) smax = (int)std::min<int64_t>(std::min<int64_t>(64, (bound + slice - 1) / slice), std::max(2, 4096 / nq));
-        if (smax > 0) {
-            GH_CHECK(h, h->w_selv.ensure((size_t)nq * smax * R * sizeof(float)));
-            GH_CHECK(h, h->w_selp.ensure(((size_t)nq * smax * R + (size_t)nq * smax) * sizeof(int)));   // + a cut flag per slice
-        }
+    const int smax = small_presel_slices(h, P, nq);
+    if (smax > 0) {
+        GH_CHECK(h, h->w_selv.ensure((size_t)nq * smax * R * sizeof(float)));
+        GH_CHECK(h, h->w_selp.ensure(((size_t)nq * smax * R + (size_t)nq * smax) * sizeof(int)));   // + a cut flag per slice
     }
     // exact ties: a query with a tie at the recall_num or k cut is replayed through the reference's heaps inside the
     // tail kernel (tie_dev.h), from the whole slab row
@@ -1136,8 +1065,6 @@ int ivfpq_check(H* h, const gamma_hip_search_params* p, int nq, int k) {
     return GAMMA_HIP_OK;
 }
 
-// queries per internal chunk: the coarse distance matrix (nlist floats per query) and the ADC distance
-// slab (nprobe x longest list floats per query) each stay inside the workspace budget
 int coarse_chunk(H* h, int nq) {
     const int64_t by_mat = (int64_t)(h->dist_budget_bytes / ((size_t)h->nlist * sizeof(float)));
     return (int)std::max<int64_t>(1, std::min<int64_t>(by_mat, nq));
@@ -1148,31 +1075,6 @@ int scan_chunk(H* h, int nq, int P) {
     return (int)std::max<int64_t>(1, std::min<int64_t>(by_dist, nq));
 }
 int query_chunk(H* h, int nq, int P) { return std::min(coarse_chunk(h, nq), scan_chunk(h, nq, P)); }
-
-// Large filtered batches: the lists are cut down to the entries that pass -- once per call, the predicate does not
-// depend on the query (kernels.hip k_compact_lists) -- and the call runs unfiltered over the shadow lists.  Worth it
-// when the call tests several times as many entries as the index holds; GAMMA_HIP_LIST_COMPACT=0/1 never / always.
-// The handle's list pointers are swapped until the ListCompaction object goes out of scope (the caller holds the
-// search lock and h->mu for the whole enqueue).
-struct ListCompaction {
-    H* h;
-    uint8_t* codes;
-    int64_t* ids;
-    int* len;
-    float* sums;
-    bool on = false;
-    explicit ListCompaction(H* h_) : h(h_), codes(h_->d_codes), ids(h_->d_ids), len(h_->d_list_len), sums(h_->d_sums) {}
-    ~ListCompaction() {
-        if (on) {
-            h->d_codes = codes;
-            h->d_ids = ids;
-            h->d_list_len = len;
-            h->d_sums = sums;
-            h->prefiltered = false;
-            h->cmp_has_sums = false;
-        }
-    }
-};
 
 int compact_lists_for_call(H* h, FiltCtx* fc, int64_t est, bool allowed, ListCompaction* lc) {
     const bool need = fc->any_clause || (h->d_bitmap && h->bitmap_any) || h->n_moved > 0;
@@ -1334,7 +1236,7 @@ int ivfpq_search_device_locked(H* h, const gamma_hip_search_params* p, int nq, c
     return GAMMA_HIP_OK;
 }
 
-// the raw store's rows as the exact scanners' kernels take them: base pointer + element type (kernels.h)
+// ---- what the exact scanners (IVFFLAT, flat) share ------------------------------------
 gh::RowsRef raw_rows_ref(const H* h) {
     if (h->raw_sq8) return gh::RowsRef{h->d_raw_q, 4, h->d_sq8_tab};   // the codes and their decode table
     return gh::RowsRef{h->raw_byte ? static_cast<const void*>(h->d_raw_b) : h->raw_half ? static_cast<const void*>(h->d_raw_h)
@@ -1342,16 +1244,8 @@ gh::RowsRef raw_rows_ref(const H* h) {
                        h->raw_elem_type()};
 }
 
-// ---- IVFFLAT (index/impl/gamma_index_ivfflat.cc:392-567) ------------------------------------------------------
-// coarse quantizer (the IVFPQ one) -> slab offsets -> exact distance of every entry of the probed lists
-// (k_ivfflat_scan) -> top-k of the slab in (distance, scan position) order -> ids.  The reference's k-heap keeps
-// the same k entries (up to its order inside exact ties).
-// IVFFLAT, small batches: the chain of ivfpq_small without tables and re-rank -- exact coarse distances | top-nprobe +
-// slab offsets | exact distances of the probed lists' rows, one workgroup per pair | top-k + ids + score window
-// the replay of a query of the exact scanners (IVFFLAT: P > 0, the slab in probe order; flat: P == 0, fixed_n rows in
-// vid order): the k-heap IS the result heap, score window and filters are already in the slab (sentinels)
 void flat_tie_args(H* h, gh::TieReplayArgs* tr, bool l2, int nq, int64_t q_stride, int P, int k, const float* d_x, float* cand_dis,
-                   int64_t* cand_ids, float* d_distances, int64_t* d_labels, int fixed_n = 0) {
+                   int64_t* cand_ids, float* d_distances, int64_t* d_labels, int fixed_n) {
     tr->list = nullptr;
     tr->count = nullptr;
     tr->nq = nq;
@@ -1376,547 +1270,13 @@ void flat_tie_args(H* h, gh::TieReplayArgs* tr, bool l2, int nq, int64_t q_strid
     tr->has_rank = 0;
     tr->min_score = -INFINITY;
     tr->max_score = INFINITY;
-    tr->neutral = l2 ? 3.402823466e+38f : -3.402823466e+38f;
+    tr->neutral = neutral_of(l2);
     tr->cand_dis = cand_dis;
     tr->cand_ids = cand_ids;
     tr->distances = d_distances;
     tr->labels = d_labels;
     tr->pop_push = 1;
     tr->fixed_n = fixed_n;
-}
-
-int ivfflat_small(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, const gh::RowsRef& rows, int nq, const float* d_x,
-                  int k, float* d_distances, int64_t* d_labels) {
-    const int P = p->nprobe, d = h->d, nlist = h->nlist;
-    const bool l2 = p->metric == GAMMA_HIP_METRIC_L2;
-    hipStream_t s = h->stream;
-    const int ver = h->cur_ver;
-    GH_CHECK(h, hipStreamWaitEvent(s, h->ver_ev[ver], 0));
-    GH_CHECK(h, h->w_mat.ensure((size_t)nq * nlist * sizeof(float)));
-    GH_CHECK(h, h->w_coarse_dis.ensure((size_t)nq * P * sizeof(float)));
-    GH_CHECK(h, h->w_probe.ensure((size_t)nq * P * sizeof(int)));
-    GH_CHECK(h, h->w_pair_off.ensure((size_t)nq * (P + 1) * sizeof(int)));
-    GH_CHECK(h, h->w_pair_base.ensure((size_t)nq * P * sizeof(int64_t)));
-    GH_CHECK(h, h->w_qtotal.ensure((size_t)nq * sizeof(int)));
-    GH_CHECK(h, h->w_cand_pos.ensure((size_t)nq * k * sizeof(int)));
-    GH_CHECK(h, h->w_cand_dis.ensure((size_t)nq * k * sizeof(float)));
-    GH_CHECK(h, h->w_cand_ids.ensure((size_t)nq * k * sizeof(int64_t)));
-    const int64_t q_stride = (std::max<int64_t>(1, (int64_t)P * std::max(1, h->max_list_len)) + 3) & ~(int64_t)3;
-    GH_CHECK(h, h->w_dist.ensure((size_t)nq * q_stride * sizeof(float)));
-    if (p->coarse_mode == 1) {
-        gh::launch_l2_gemmform(s, d_x, nq, d, h->d_cc, nlist, nullptr, h->d_cc_norms, h->w_mat.as<float>(), nlist, true);
-    } else if (!gh::launch_small_coarse_ip(s, d_x, nq, d, h->d_cc, nlist, h->w_mat.as<float>(), 0, nullptr, nullptr)) {
-        gh::launch_pairwise(s, true, d_x, nq, d, h->d_cc, nlist, h->w_mat.as<float>(), nlist);   // exact, more than 16 queries
-    }
-    gh::launch_small_coarse_select(s, h->w_mat.as<float>(), nlist, nq, P, h->w_coarse_dis.as<float>(), h->w_probe.as<int>(),
-                                   h->d_list_len, h->d_list_mask, h->d_list_off, h->w_pair_off.as<int>(),
-                                   h->w_qtotal.as<int>(), h->w_pair_base.as<int64_t>(), nullptr, nullptr, 0, nullptr, nullptr,
-                                   nullptr, 0, tie_on(p) ? 1 : 0, h->d_tie_stats);
-    const int need_filter = (fc.any_clause || (h->d_bitmap && h->bitmap_any)) ? 1 : 0;
-    gh::launch_ivfflat_scan(s, l2, d_x, nq, d, P, h->w_pair_off.as<int>(), h->w_pair_base.as<int64_t>(), h->d_ids, rows,
-                            h->nraw, q_stride, h->w_dist.as<float>(), fc.d_tab, need_filter, p->min_score, p->max_score);
-    int smax = 0;   // long candidate rows: two-level selection (ivfpq_small)
-    {
-        const int64_t slice = 16384;
-        const int64_t est = (int64_t)P * (h->ntotal / std::max(1, nlist)) * 3 / 2;
-        const int64_t bound = (int64_t)P * std::max(1, h->max_list_len);
-        if (h->small_presel > 0) smax = h->small_presel;
-        else if (est > slice) smax = (int)std::min<int64_t>(std::min<int64_t>(64, (bound + slice - 1) / slice), std::max(2, 4096 / nq));
-        if (smax > 0) {
-            GH_CHECK(h, h->w_selv.ensure((size_t)nq * smax * k * sizeof(float)));
-            GH_CHECK(h, h->w_selp.ensure(((size_t)nq * smax * k + (size_t)nq * smax) * sizeof(int)));   // + a cut flag per slice
-        }
-    }
-    const float neutral = l2 ? 3.402823466e+38f : -3.402823466e+38f;
-    // exact ties: a query with equal distances at the k cut or among its k results is replayed through the scanner's
-    // heap (heap_pop + heap_push per accepted entry, heap_reorder: gamma_index_ivfflat.h:52-75) inside the tail kernel
-    gh::TieReplayArgs tr;
-    const bool ties = tie_on(p) && k <= gh::tie_small_max_k();   // (the caller's gate: k <= 1024)
-    if (ties) flat_tie_args(h, &tr, l2, nq, q_stride, P, k, d_x, h->w_cand_dis.as<float>(), h->w_cand_ids.as<int64_t>(), d_distances,
-                            d_labels);
-    gh::launch_small_tail(s, l2, h->w_dist.as<float>(), q_stride, h->w_qtotal.as<int>(), nq, k, P, h->w_probe.as<int>(),
-                          h->w_pair_off.as<int>(), h->d_list_off, h->d_ids, h->w_cand_dis.as<float>(),
-                          h->w_cand_pos.as<int>(), h->w_cand_ids.as<int64_t>(), 0, d_x, d, h->d_raw, h->nraw, k, p->min_score,
-                          p->max_score, neutral, d_distances, d_labels, smax, smax ? h->w_selv.as<float>() : nullptr,
-                          smax ? h->w_selp.as<int>() : nullptr, 0, ties ? &tr : nullptr, h->d_tie_stats);
-    GH_CHECK(h, hipEventRecord(h->rd_ev[ver], s));
-    h->rd_set[ver] = true;
-    h->last_nq = nq;
-    h->last_P = P;
-    h->last_R = k;
-    GH_CHECK(h, hipGetLastError());
-    return GAMMA_HIP_OK;
-}
-
-int ivfflat_search_device_locked(H* h, const gamma_hip_search_params* p, int nq, const float* d_x, int k,
-                                 float* d_distances, int64_t* d_labels) {
-    if (h->raw_sparse) return fail(h, GAMMA_HIP_EUNSUPPORTED, "the raw store holds this shard's rows only (gamma_hip_raw_put)");
-    // (a narrow store is served only after gamma_hip_set_ivfflat_narrow_rows: the refusal is what every caller had before)
-    if (h->raw_half && !h->ivfflat_narrow_rows) return half_refuse(h, "IVFFLAT search");
-    if (h->raw_byte && !h->ivfflat_narrow_rows) return byte_refuse(h, "IVFFLAT search");
-    if (h->raw_sq8) return sq8_refuse(h, "IVFFLAT search");   // (whatever the switch says: the scan decodes nothing)
-    GH_TRY(check_params(h, p, nq, k));
-    gamma_hip_search_params pp;
-    GH_TRY(resolve_ties(h, p, &pp, p->nprobe <= gh::tie_replay_max_probes(), "exact_ties = 1 with nprobe > 1024"));
-    p = &pp;
-    if (!h->ivf_init || !h->ivfflat || h->binivf) return fail(h, GAMMA_HIP_EINVAL, "ivfflat not initialised");
-    if (!h->trained) return fail(h, GAMMA_HIP_ENOTTRAINED, "ivfflat not trained");
-    if (p->nprobe <= 0 || p->nprobe > h->nlist) return fail(h, GAMMA_HIP_EINVAL, "nprobe out of range");
-    if (!h->has_raw_rows() || h->raw_d != h->d) return fail(h, GAMMA_HIP_EINVAL, "ivfflat needs the raw store");
-    if (k <= 0 || nq == 0) return GAMMA_HIP_OK;
-    // the store's rows as the scan takes them: pointer + element type (fp32 rows: the launches they always were)
-    const gh::RowsRef rows = raw_rows_ref(h);
-    GH_CHECK(h, hipSetDevice(h->device));
-    const bool l2 = p->metric == GAMMA_HIP_METRIC_L2;
-    const float neutral = l2 ? 3.402823466e+38f : -3.402823466e+38f;
-    gh::FilterDesc filt;
-    GH_TRY(build_filter(h, p, &filt, nullptr, (int64_t)nq * p->nprobe * (h->ntotal / std::max(1, h->nlist))));
-    FiltCtx fc;
-    GH_TRY(filt_ctx_single(h, filt, &fc));
-    if (pp.coarse_mode < 0) pp.coarse_mode = nq < 20 ? 0 : 1;   // faiss:utils/distances.cpp:303,346, whole call
-    if (pp.coarse_mode == 1 && blas_form_not_restated(nq, h->nlist, h->d)) h->blas_unrestated++;
-    const int P = pp.nprobe, nlist = h->nlist;
-    hipStream_t s = h->stream;
-    {   // small batches, as long as the pair-per-workgroup scan is the one that would run anyway (below 2 nlist pairs)
-        static const bool off = getenv("GAMMA_HIP_NO_SMALL_PATH") != nullptr;
-        if (!off && h->small_path && nq <= 512 && P <= 128 && k <= 1024 && !h->profile &&
-            !fc.d_qf && !h->d_list_mask && nlist <= 16384 && (int64_t)nq * P < 2 * (int64_t)nlist &&
-            (int64_t)P * std::max(1, h->max_list_len) <= (1 << 22))
-            return ivfflat_small(h, &pp, fc, rows, nq, d_x, k, d_distances, d_labels);
-    }
-    ListCompaction restore(h);
-    GH_TRY(compact_lists_for_call(h, &fc, (int64_t)nq * P * (h->ntotal / std::max(1, nlist)), true, &restore));
-    const int chunk = scan_chunk(h, nq, P);
-    const int need_filter = (!h->prefiltered && (fc.any_clause || (h->d_bitmap && h->bitmap_any))) ? 1 : 0;
-    for (int q0 = 0; q0 < nq; q0 += chunk) {
-        const int nc = std::min(chunk, nq - q0);
-        const float* xq = d_x + (size_t)q0 * h->d;
-        const int ver = h->cur_ver;
-        GH_CHECK(h, hipStreamWaitEvent(s, h->ver_ev[ver], 0));
-        GH_CHECK(h, h->w_pair_off.ensure((size_t)nc * (P + 1) * sizeof(int)));
-        GH_CHECK(h, h->w_pair_base.ensure((size_t)nc * P * sizeof(int64_t)));
-        GH_CHECK(h, h->w_qtotal.ensure((size_t)nc * sizeof(int)));
-        GH_CHECK(h, h->w_cand_pos.ensure((size_t)nc * k * sizeof(int)));
-        GH_CHECK(h, h->w_cand_dis.ensure((size_t)nc * k * sizeof(float)));
-        GH_CHECK(h, h->w_cand_ids.ensure((size_t)nc * k * sizeof(int64_t)));
-        GH_TRY(ivfpq_coarse(h, &pp, nc, xq));
-        gh::launch_pair_offsets(s, h->w_probe.as<int>(), nc, P, h->d_list_len, h->d_list_mask, nlist,
-                                h->w_pair_off.as<int>(), h->w_qtotal.as<int>(), nullptr, h->d_list_off,
-                                h->w_pair_base.as<int64_t>());
-        const int64_t q_stride = (std::max<int64_t>(1, (int64_t)P * std::max(1, h->max_list_len)) + 3) & ~(int64_t)3;
-        GH_CHECK(h, h->w_dist.ensure((size_t)nc * q_stride * sizeof(float)));
-        {
-            StageScope t(h, GAMMA_HIP_STAGE_SCAN);
-            // enough (query, probe) pairs that lists are shared: list-major (ivfflat.hip), a list's rows are read once
-            // for all the queries probing it; else one workgroup per pair
-            static const bool no_lm = getenv("GAMMA_HIP_NO_IVFFLAT_LM") != nullptr;
-            if (!no_lm && gh::ivfflat_lm_supported(h->d) && (int64_t)nc * P >= 2 * (int64_t)nlist && !h->d_list_mask) {
-                GH_CHECK(h, h->w_lm_units.ensure(gh::ivfflat_lm_scratch_bytes(nc, P, nlist)));
-                gh::launch_ivfflat_lm(s, l2, xq, nc, h->d, P, h->w_probe.as<int>(), h->w_pair_off.as<int>(), h->d_list_off,
-                                      h->d_list_len, nlist, h->d_ids, rows, h->nraw, q_stride, h->w_dist.as<float>(),
-                                      fc.d_tab, need_filter, p->min_score, p->max_score, h->w_lm_units.p);
-            } else {
-                gh::launch_ivfflat_scan(s, l2, xq, nc, h->d, P, h->w_pair_off.as<int>(), h->w_pair_base.as<int64_t>(),
-                                        h->d_ids, rows, h->nraw, q_stride, h->w_dist.as<float>(), fc.d_tab, need_filter,
-                                        p->min_score, p->max_score);
-            }
-        }
-        {
-            StageScope t(h, GAMMA_HIP_STAGE_SELECT);
-            gh::launch_select_topk(s, l2, h->w_dist.as<float>(), q_stride, h->w_qtotal.as<int>(), 0,
-                                   (int)std::min<int64_t>(q_stride, 1 << 30), nc, k, h->w_cand_dis.as<float>(),
-                                   h->w_cand_pos.as<int>());
-            gh::launch_map_candidates(s, h->w_cand_pos.as<int>(), nc, k, P, h->w_probe.as<int>(), h->w_pair_off.as<int>(),
-                                      h->d_list_off, h->d_ids, h->w_cand_ids.as<int64_t>());
-            const bool ties = tie_on(p);
-            gh::TieFlags tf;
-            if (ties) {
-                // equal distances at the k cut or among the k selected: the scanner's heap decides (ties.hip)
-                GH_CHECK(h, h->w_tcut.ensure((size_t)nc));
-                GH_CHECK(h, h->w_tlist.ensure(((size_t)nc + 1) * sizeof(int)));
-                GH_CHECK(h, hipMemsetAsync(h->w_tlist.p, 0, sizeof(int), s));
-                GH_CHECK(h, hipMemsetAsync(h->w_tcut.p, 0, (size_t)nc, s));
-                gh::launch_flag_cut_ties(s, h->w_dist.as<float>(), q_stride, h->w_qtotal.as<int>(), nc, k, h->w_cand_dis.as<float>(),
-                                         h->w_cand_pos.as<int>(), nullptr, h->w_tcut.as<uint8_t>(), 0, 1);
-                tf.cut = h->w_tcut.as<uint8_t>();
-                tf.count = h->w_tlist.as<int>();
-                tf.list = h->w_tlist.as<int>() + 1;
-                tf.stats = h->d_tie_stats;
-            }
-            gh::launch_finalize_norank(s, h->w_cand_dis.as<float>(), h->w_cand_ids.as<int64_t>(), nc, k, k, p->min_score,
-                                       p->max_score, neutral, d_distances + (size_t)q0 * k, d_labels + (size_t)q0 * k,
-                                       ties ? &tf : nullptr);
-            if (ties) {
-                gh::TieReplayArgs tr;
-                flat_tie_args(h, &tr, l2, nc, q_stride, P, k, xq, h->w_cand_dis.as<float>(), h->w_cand_ids.as<int64_t>(),
-                              d_distances + (size_t)q0 * k, d_labels + (size_t)q0 * k);
-                tr.list = tf.list;
-                tr.count = tf.count;
-                gh::launch_tie_replay(s, l2, tr);
-            }
-        }
-        GH_CHECK(h, hipEventRecord(h->rd_ev[ver], s));
-        h->rd_set[ver] = true;
-        h->last_nq = nc;
-    }
-    h->last_P = P;
-    h->last_R = k;
-    GH_CHECK(h, hipGetLastError());
-    return GAMMA_HIP_OK;
-}
-
-// ---- flat ------------------------------------------------------------------------------
-int flat_search_device_locked(H* h, const gamma_hip_search_params* p, int nq, const float* d_x, int k,
-                              float* d_distances, int64_t* d_labels) {
-    if (h->raw_sparse) return fail(h, GAMMA_HIP_EUNSUPPORTED, "the raw store holds this shard's rows only (gamma_hip_raw_put)");
-    // (a narrow store is served only after gamma_hip_set_flat_narrow_rows: the refusal is what every caller had before)
-    if (h->raw_half && !h->flat_narrow_rows) return half_refuse(h, "flat search");
-    if (h->raw_byte && !h->flat_narrow_rows) return byte_refuse(h, "flat search");
-    if (h->raw_sq8 && !h->flat_sq8_rows) return sq8_refuse(h, "flat search");   // (whatever that switch says: gamma_hip_set_flat_sq8_rows is this store's)
-    GH_TRY(check_params(h, p, nq, k));
-    gamma_hip_search_params pp;   // (the chunked paths run for k + 1 results: k = 4096, the ABI's largest, is beyond the mode)
-    GH_TRY(resolve_ties(h, p, &pp, k + 1 <= gh::tie_replay_max_k() && h->nraw < ((int64_t)1 << 31),
-                        "exact_ties = 1 with k = 4096 or 2^31 rows (flat search)"));
-    p = &pp;
-    if (!h->has_raw_rows() && h->nraw > 0) return fail(h, GAMMA_HIP_EINVAL, "raw store not initialised");
-    if (h->raw_d <= 0) return fail(h, GAMMA_HIP_EINVAL, "raw store not initialised");
-    if (k <= 0 || nq == 0) return GAMMA_HIP_OK;
-    // the store's rows as every reader below takes them: pointer + element type (fp32 rows: the launches they always were)
-    const gh::RowsRef rows = raw_rows_ref(h);
-    GH_CHECK(h, hipSetDevice(h->device));
-    const bool l2 = p->metric == GAMMA_HIP_METRIC_L2;
-    const float neutral = l2 ? 3.402823466e+38f : -3.402823466e+38f;
-    const float sentinel = l2 ? INFINITY : -INFINITY;
-    const int d = h->raw_d;
-    const int64_t N = h->nraw;
-    hipStream_t s = h->stream;
-    gh::FilterDesc filt;
-    GH_TRY(build_filter(h, p, &filt, nullptr, (int64_t)nq * N));
-    {   // small calls: the whole store as ONE row chunk, then the small-batch chains' selection -- three or four launches
-        // instead of three per 65536 rows (1 M x 128, one query: 49 launches, 1.1 ms)
-        static const bool off = getenv("GAMMA_HIP_NO_SMALL_PATH") != nullptr;
-        const int64_t stride = (N + 3) & ~(int64_t)3;
-        if (!off && h->small_path && nq <= 64 && k <= 1024 && N >= 1 && N <= ((int64_t)1 << 22) && !h->profile &&
-            (size_t)nq * stride * sizeof(float) <= std::min<size_t>(h->dist_budget_bytes, (size_t)1 << 30)) {
-            GH_TRY(replay_join(h));
-            GH_CHECK(h, h->w_dist.ensure((size_t)nq * stride * sizeof(float)));
-            GH_CHECK(h, h->w_cand_pos.ensure((size_t)nq * k * sizeof(int)));
-            GH_CHECK(h, h->w_cand_dis.ensure((size_t)nq * k * sizeof(float)));
-            GH_CHECK(h, h->w_cand_ids.ensure((size_t)nq * k * sizeof(int64_t)));
-            StageScope t(h, GAMMA_HIP_STAGE_FLAT);
-            gh::launch_pairwise_filtered(s, l2, d_x, nq, d, rows, N, h->w_dist.as<float>(), stride, filt, p->min_score,
-                                         p->max_score, 0);
-            int smax = h->small_presel > 0 ? h->small_presel : (N > 16384 ? (int)std::min<int64_t>(64, (N + 16383) / 16384) : 0);
-            if (smax > 0) {
-                GH_CHECK(h, h->w_selv.ensure((size_t)nq * smax * k * sizeof(float)));
-                GH_CHECK(h, h->w_selp.ensure(((size_t)nq * smax * k + (size_t)nq * smax) * sizeof(int)));   // + a cut flag per slice
-            }
-            // exact ties: a query with equal distances at the k cut or among its k results is replayed through the
-            // reference's heap over the whole row (gamma_index_flat.cc:118-300: heap_pop + heap_push in vid order)
-            gh::TieReplayArgs tr;
-            const bool ties = tie_on(p) && k <= gh::tie_small_max_k();   // (this path's gate: k <= 1024)
-            if (ties) {
-                flat_tie_args(h, &tr, l2, nq, stride, 0, k, d_x, h->w_cand_dis.as<float>(), h->w_cand_ids.as<int64_t>(), d_distances,
-                              d_labels, (int)N);
-                tr.d = d;
-            }
-            // (has_rank = 0: the tail selects from the slab and reads no row -- its fp32 row pointer is null for a narrow store)
-            gh::launch_small_tail(s, l2, h->w_dist.as<float>(), stride, nullptr, nq, k, 0, nullptr, nullptr, nullptr, nullptr,
-                                  h->w_cand_dis.as<float>(), h->w_cand_pos.as<int>(), h->w_cand_ids.as<int64_t>(), 0, d_x, d,
-                                  h->d_raw, N, k, p->min_score, p->max_score, neutral, d_distances, d_labels, smax,
-                                  smax ? h->w_selv.as<float>() : nullptr, smax ? h->w_selp.as<int>() : nullptr, (int)N,
-                                  ties ? &tr : nullptr, h->d_tie_stats);
-            GH_CHECK(h, hipGetLastError());
-            return GAMMA_HIP_OK;
-        }
-    }
-    // query chunks x row chunks so the distance slab stays inside the budget
-    // The matrix-pipe filter (flat_mfma.hip: bf16 hi / lo products with a proven margin, exact distances of the ~k survivors
-    // per query and pass) takes the passes behind the first row chunk when the shape has a variant; the first chunk -- scored
-    // exactly for every query, the only part still on the vector ALU -- is then 16384 rows instead of 65536.
-    const bool mfma_filter = k <= 256 && N < ((int64_t)1 << 32) && gh::flat_filter_supported(nq, d, N);
-    // (long rows: the first chunk's exact kernel runs at ~1.3 TFLOP/s -- 1024 rows of d = 768 instead of 16384: C5 flat, 1 M x 768,
-    //  1024 queries: 15.6 / 16.1 / 16.8 / 18.4 ms per call with a first chunk of 2^10 / 2^11 / 2^12 / 2^13 rows)
-    // (the lengths of k_flat_filter_any, d <= 128: no k_pairwise_lds variant scores the first chunk -- it runs on the generic
-    //  kernel at the long rows' rate, so it is 2^12 rows, the smallest the filter's gate ny >= 4096 leaves room behind)
-    static const int fl_any = [] {   // (measurements of the any-length shapes only: DESIGN section 19)
-        const char* e = getenv("GAMMA_HIP_FLAT_ANYD_FIRST_LOG2");
-        const int v = e ? atoi(e) : 0;
-        return v >= 8 && v <= 16 ? v : 0;
-    }();
-    const bool new_shape = gh::flat_filter_new_shape(d);
-    const int fl2 = mfma_filter ? (new_shape && fl_any ? fl_any : (d > 128 ? 10 : (new_shape ? 12 : 14))) : 16;
-    int64_t rows_chunk = std::max<int64_t>(256, std::min<int64_t>(N, (int64_t)1 << fl2));
-    rows_chunk = (rows_chunk + 255) / 256 * 256;
-    int qc = (int)std::max<int64_t>(1, std::min<int64_t>(nq, (int64_t)(h->dist_budget_bytes / (rows_chunk * sizeof(float)))));
-    const int nchunks = (int)std::max<int64_t>(1, (N + rows_chunk - 1) / rows_chunk);
-    // exact ties: the paths below order results on (distance, row id); the reference's heap (heap_pop + heap_push in
-    // vid order, heap_reorder: gamma_index_flat.cc:118-300) orders equal distances its own way and decides which members
-    // of a tie at the cut stay.  Run for k + 1 results, list the queries with two equal distances among them and replay
-    // those through the heap over a freshly computed distance row (k_tie_replay).
-    const int k_out = k;
-    const bool ties = tie_on(p) && N > 0;
-    if (ties) k = k + 1;
-    // Overlapping callers (gamma_hip_flat_search_device_wait): this call's tie replay goes to the side stream when the call is one
-    // query chunk; a call that finds a FLAT replay pending does not wait for it -- it works in the other bank of the buffers the
-    // replay reads and waits, in stream order, only for the replay that last read that bank.
-    const bool defer_flat = h->defer_now && h->side2 != nullptr && ties && qc >= nq;
-    if (h->replay_pending) {
-        if (defer_flat && h->replay_is_flat) {
-            DevBuf* cur[5] = {&h->w_dist, &h->w_flog, &h->w_tlist, &h->w_cand_dis, &h->w_cand_ids};
-            for (int i = 0; i < 5; i++) std::swap(*cur[i], h->fbank[i]);
-            h->flat_bank ^= 1;
-            if (h->bank_used[h->flat_bank]) GH_CHECK(h, hipStreamWaitEvent(s, h->ev_bank[h->flat_bank], 0));
-            // (replay_pending stays: whoever comes next and cannot switch banks joins)
-        } else {
-            GH_TRY(replay_join(h));
-        }
-    }
-    auto flat_replay = [&](const gh::TieReplayArgs& tr) -> int {
-        if (!defer_flat) {
-            gh::launch_tie_replay(s, l2, tr);
-            return GAMMA_HIP_OK;
-        }
-        const int b = h->flat_bank;
-        if (!h->ev_bank[b]) GH_CHECK(h, hipEventCreateWithFlags(&h->ev_bank[b], hipEventDisableTiming));
-        GH_CHECK(h, hipEventRecord(h->ev_rfork, s));
-        GH_CHECK(h, hipStreamWaitEvent(h->side2, h->ev_rfork, 0));
-        gh::launch_tie_replay(h->side2, l2, tr);
-        GH_CHECK(h, hipEventRecord(h->ev_rdone, h->side2));
-        GH_CHECK(h, hipEventRecord(h->ev_bank[b], h->side2));
-        h->bank_used[b] = true;
-        h->replay_pending = true;
-        h->replay_is_flat = true;
-        return GAMMA_HIP_OK;
-    };
-    GH_CHECK(h, h->w_dist.ensure((size_t)qc * rows_chunk * sizeof(float)));
-    GH_CHECK(h, h->w_part_v.ensure((size_t)qc * nchunks * k * sizeof(float)));
-    GH_CHECK(h, h->w_part_i.ensure((size_t)qc * nchunks * k * sizeof(int64_t)));
-    GH_CHECK(h, h->w_selv.ensure((size_t)qc * k * sizeof(float)));
-    GH_CHECK(h, h->w_selp.ensure((size_t)qc * k * sizeof(int)));
-    GH_CHECK(h, h->w_cand_pos.ensure((size_t)qc * k * sizeof(int)));
-    GH_CHECK(h, h->w_cand_dis.ensure((size_t)qc * k * sizeof(float)));
-    if (ties) {
-        GH_CHECK(h, h->w_fD.ensure((size_t)qc * k * sizeof(float)));
-        GH_CHECK(h, h->w_fI.ensure((size_t)qc * k * sizeof(int64_t)));
-        GH_CHECK(h, h->w_tlist.ensure(((size_t)qc + 1) * sizeof(int)));
-        GH_CHECK(h, h->w_cand_ids.ensure((size_t)qc * k * sizeof(int64_t)));
-    }
-    // where the paths write their [nc][k] result of query chunk q0
-    auto outD = [&](int q0) { return ties ? h->w_fD.as<float>() : d_distances + (size_t)q0 * k; };
-    auto outI = [&](int q0) { return ties ? h->w_fI.as<int64_t>() : d_labels + (size_t)q0 * k; };
-    StageScope t(h, GAMMA_HIP_STAGE_FLAT);
-    // the reference's loop: every row, one query at a time, a k-heap (gamma_index_flat.cc:118-300).
-    // Here: distance slab of one row chunk -> per-chunk top-k -> merge of the chunks' tables.
-    auto unbounded = [&](int q0, int nc) -> int {
-        const float* xq = d_x + (size_t)q0 * d;
-        for (int c = 0; c < nchunks; c++) {
-            const int64_t r0 = (int64_t)c * rows_chunk;
-            const int64_t nr = std::min<int64_t>(rows_chunk, N - r0);
-            gh::launch_pairwise_filtered(s, l2, xq, nc, d, rows.at(r0, d), nr, h->w_dist.as<float>(),
-                                         rows_chunk, filt, p->min_score, p->max_score, r0);
-            // per-chunk top-k: values + positions relative to the chunk
-            gh::launch_select_topk(s, l2, h->w_dist.as<float>(), rows_chunk, nullptr, (int)nr, (int)nr, nc, k,
-                                   h->w_cand_dis.as<float>(), h->w_cand_pos.as<int>());
-            // scatter into the partial table [q][chunk][k] with global ids
-            // (reuse finalize_topk: labels = pos, then offset by r0 on the fly below)
-            gh::launch_finalize_topk(s, h->w_cand_dis.as<float>(), h->w_cand_pos.as<int>(), nc, k, nullptr,
-                                     0, r0, sentinel, h->w_selv.as<float>(),
-                                     h->w_part_i.as<int64_t>() + (size_t)c * nc * k);
-            GH_CHECK(h, hipMemcpyAsync(h->w_part_v.as<float>() + (size_t)c * nc * k, h->w_selv.p,
-                                       (size_t)nc * k * sizeof(float), hipMemcpyDeviceToDevice, s));
-        }
-        // merge: layout [chunk][q][k] == the sharded layout [shard][nq][R]
-        GH_CHECK(h, h->w_m_dis.ensure((size_t)nc * nchunks * k * sizeof(float)));
-        GH_CHECK(h, h->w_m_ids.ensure((size_t)nc * nchunks * k * sizeof(int64_t)));
-        gh::launch_gather_shards(s, h->w_part_v.as<float>(), h->w_part_i.as<int64_t>(), nchunks, nc, k,
-                                 h->w_m_dis.as<float>(), h->w_m_ids.as<int64_t>(), sentinel);
-        gh::launch_select_topk(s, l2, h->w_m_dis.as<float>(), (int64_t)nchunks * k, nullptr, nchunks * k,
-                               nchunks * k, nc, k, h->w_selv.as<float>(), h->w_selp.as<int>());
-        gh::launch_finalize_topk(s, h->w_selv.as<float>(), h->w_selp.as<int>(), nc, k,
-                                 h->w_m_ids.as<int64_t>(), (int64_t)nchunks * k, 0, neutral,
-                                 outD(q0), outI(q0));
-        return GAMMA_HIP_OK;
-    };
-    // Running bound: only the first chunk goes through a distance slab.  Its k-th best bounds the
-    // answer; the remaining rows are scored in passes that double the rows seen so far, each pass
-    // appending only the distances within the current bound to the query's candidate list (about k
-    // per pass and query) and ending with a compaction that tightens the bound.  The k smallest
-    // (distance, row id) items are the same either way.  A list that overflows (rows arriving in
-    // improving order) is detected and the call redone without a bound.
-    const int cap = gh::flat_list_cap();
-    int log_nsl = 1;   // slices of the log: one per pass of the running bound (+ slice 0, the first chunk's slab)
-    // pass sizes: every pass scores (growth - 1) x the rows scored so far -- with a bound from r rows a pass over g r more
-    // lets ~k ln(1 + g) new candidates per query through; fewer, larger passes pay fewer fixed launches (bounds, filter
-    // ramp, exact, compact: ~100 us each at C2)
-    // (C2, ms per call at growth 2 / 3 / 4 / 6: 2.26 / 2.19 / 2.15 / 2.24)
-    constexpr int flat_growth = 4;
-    auto pass_rows = [&](int64_t r) { return std::min<int64_t>((int64_t)(flat_growth - 1) * r, N - r); };
-    for (int64_t r = rows_chunk; r < N; r += pass_rows(r)) log_nsl++;
-    auto bounded = [&](int q0, int nc, bool* redo) -> int {
-        const float* xq = d_x + (size_t)q0 * d;
-        GH_CHECK(h, h->w_flat_cand.ensure((size_t)nc * cap * sizeof(unsigned long long)));
-        // tau[nc] | cnt[nc * CS] | overflow -- the counters one 128-byte line apart: ~140 appends per query and pass are
-        // returning atomics, and 32 queries' counters on one line serialised 4500 of them (C2 exact passes 49 / 66 / 84 -> 30 / 31 / 37 us)
-        constexpr int CS = 32;
-        GH_CHECK(h, h->w_flat_meta.ensure((size_t)(nc + (size_t)nc * CS + 1) * sizeof(int)));
-        uint32_t* tau = h->w_flat_meta.as<uint32_t>();
-        int* cnt = h->w_flat_meta.as<int>() + nc;
-        int* over = cnt + (size_t)nc * CS;
-        gh::FlatEmit em{tau, h->w_flat_cand.as<unsigned long long>(), cnt, cap, CS};
-        GH_CHECK(h, hipMemsetAsync(over, 0, sizeof(int), s));
-        gh::FlatLog lg;
-        if (ties) {   // what every pass appends is kept for the replay (slice `pass` of the query)
-            GH_CHECK(h, h->w_flog.ensure((size_t)nc * log_nsl * cap * sizeof(unsigned long long) +
-                                         (size_t)nc * (log_nsl + 1) * sizeof(int)));
-            lg.items = h->w_flog.as<unsigned long long>();
-            lg.cnt = reinterpret_cast<int*>(lg.items + (size_t)nc * log_nsl * cap);
-            lg.kept = lg.cnt + (size_t)nc * log_nsl;
-            lg.nsl = log_nsl;
-            GH_CHECK(h, hipMemsetAsync(lg.cnt, 0, (size_t)nc * log_nsl * sizeof(int), s));
-        }
-        gh::launch_pairwise_filtered(s, l2, xq, nc, d, rows, rows_chunk, h->w_dist.as<float>(), rows_chunk, filt,
-                                     p->min_score, p->max_score, 0);
-        gh::launch_select_topk(s, l2, h->w_dist.as<float>(), rows_chunk, nullptr, (int)rows_chunk, (int)rows_chunk,
-                               nc, k, h->w_cand_dis.as<float>(), h->w_cand_pos.as<int>());
-        gh::launch_flat_init(s, l2, h->w_cand_dis.as<float>(), h->w_cand_pos.as<int>(), nc, k, 0, em, tau, lg.kept);
-        const bool mf = mfma_filter && gh::flat_filter_supported(nc, d, N);
-        const int64_t pcap = gh::flat_filter_pair_cap(nc);
-        float* bnd = nullptr;
-        int* npairs = nullptr;
-        if (mf) {   // once per query chunk: norms and the queries' bf16 hi / lo image
-            GH_CHECK(h, h->w_xn.ensure((size_t)nc * sizeof(float)));
-            GH_CHECK(h, h->w_fq.ensure(gh::flat_filter_query_image_bytes(nc, d)));
-            GH_CHECK(h, h->w_fraw.ensure((size_t)pcap * 8));
-            GH_CHECK(h, h->w_frcnt.ensure(gh::flat_filter_counter_bytes() + gh::flat_filter_bounds_bytes(nc)));   // pair counters | bounds
-            npairs = h->w_frcnt.as<int>();
-            bnd = reinterpret_cast<float*>(h->w_frcnt.as<char>() + gh::flat_filter_counter_bytes());
-            gh::launch_row_norms(s, xq, nc, d, h->w_xn.as<float>());
-            gh::launch_flat_prep_queries(s, xq, nc, d, h->w_fq.p);
-        }
-        for (int64_t r = rows_chunk; r < N;) {
-            const int64_t nr = pass_rows(r);
-            if (mf) {
-                GH_CHECK(h, hipMemsetAsync(npairs, 0, (size_t)gh::flat_filter_counter_bytes(), s));
-                gh::launch_flat_filter(s, l2, d, h->w_fq.p, h->w_xn.as<float>(), tau, bnd, nc, rows.at(r, d), nr, r,
-                                       h->w_fraw.p, npairs, pcap);
-                gh::launch_flat_exact(s, l2, h->w_fraw.p, npairs, pcap, xq, nc, d, rows, filt, p->min_score, p->max_score,
-                                      em, over);
-                h->ff_passes.fetch_add(1, std::memory_order_relaxed);
-                h->ff_pairs.fetch_add((int64_t)nc * nr, std::memory_order_relaxed);
-            } else {
-                gh::launch_pairwise_emit(s, l2, xq, nc, d, rows.at(r, d), nr, filt, p->min_score, p->max_score, r, em);
-            }
-            lg.pass++;
-            gh::launch_flat_compact(s, nc, k, em, tau, over, ties ? &lg : nullptr);
-            r += nr;
-        }
-        gh::launch_flat_final(s, l2, nc, k, em, neutral, outD(q0), outI(q0));
-        GH_CHECK(h, hipGetLastError());
-        // (whether a list overflowed -- then the call is redone without a bound -- is read back by the caller AFTER it has
-        //  enqueued the tie phase: the device never waits for the host)
-        *redo = false;
-        return GAMMA_HIP_OK;
-    };
-    auto overflowed = [&](int nc, bool* yes) -> int {
-        int h_over = 0;
-        GH_CHECK(h, hipMemcpyAsync(&h_over, h->w_flat_meta.as<int>() + nc + (size_t)nc * 32, sizeof(int), hipMemcpyDeviceToHost, s));
-        GH_CHECK(h, hipStreamSynchronize(s));
-        *yes = h_over != 0;
-        return GAMMA_HIP_OK;
-    };
-    for (int q0 = 0; q0 < nq; q0 += qc) {
-        const int nc = std::min(qc, nq - q0);
-        if (N == 0) {
-            // nothing to scan: all-empty result
-            GH_CHECK(h, hipMemsetAsync(h->w_selp.p, 0xff, (size_t)nc * k * sizeof(int), s));
-            gh::launch_finalize_topk(s, h->w_selv.as<float>(), h->w_selp.as<int>(), nc, k, nullptr, 0, 0,
-                                     neutral, outD(q0), outI(q0));
-            continue;
-        }
-        auto tie_phase = [&](bool redo) -> int {
-            int* count = h->w_tlist.as<int>();
-            int* list = count + 1;
-            GH_CHECK(h, hipMemsetAsync(count, 0, sizeof(int), s));
-            gh::launch_flat_take_flag(s, h->w_fD.as<float>(), h->w_fI.as<int64_t>(), nc, k_out, d_distances + (size_t)q0 * k_out,
-                                      d_labels + (size_t)q0 * k_out, list, count, h->d_tie_stats);
-            gh::TieReplayArgs tr;
-            flat_tie_args(h, &tr, l2, nc, rows_chunk, 0, k_out, d_x + (size_t)q0 * d, h->w_cand_dis.as<float>(),
-                          h->w_cand_ids.as<int64_t>(), d_distances + (size_t)q0 * k_out, d_labels + (size_t)q0 * k_out, (int)N);
-            tr.d = d;
-            tr.list = list;
-            tr.count = count;
-            if (!redo) {
-                // the running bound: the stream the heap saw = the first row chunk (its slab is intact) + what every
-                // later pass appended to the query's list, in row order
-                tr.G = (int)rows_chunk;
-                tr.always_sliced = 1;
-                tr.surv = h->w_flog.as<unsigned long long>();
-                tr.gcnt = reinterpret_cast<const int*>(tr.surv + (size_t)nc * log_nsl * cap);
-                tr.nsl = log_nsl;
-                tr.slice_cap = cap;
-                GH_TRY(flat_replay(tr));
-            } else if (nchunks == 1) {
-                GH_TRY(flat_replay(tr));   // the one slab holds every row
-            } else {
-                GH_TRY(replay_join(h));
-                // several row chunks through one slab: the rows of the flagged queries are computed again
-                int nflag = 0;
-                GH_CHECK(h, hipMemcpyAsync(&nflag, count, sizeof(int), hipMemcpyDeviceToHost, s));
-                GH_CHECK(h, hipStreamSynchronize(s));
-                const int64_t stride = (N + 3) & ~(int64_t)3;
-                const int fcap = (int)std::max<int64_t>(1, std::min<int64_t>(1024, (int64_t)(h->dist_budget_bytes / ((size_t)stride * sizeof(float)))));
-                for (int f0 = 0; f0 < nflag; f0 += fcap) {
-                    const int nf = std::min(fcap, nflag - f0);
-                    GH_CHECK(h, h->w_fx.ensure((size_t)nf * d * sizeof(float)));
-                    GH_CHECK(h, h->w_fslab.ensure((size_t)nf * stride * sizeof(float)));
-                    gh::launch_gather_rows(s, d_x + (size_t)q0 * d, list + f0, nf, d, h->w_fx.as<float>());
-                    gh::launch_pairwise_filtered(s, l2, h->w_fx.as<float>(), nf, d, rows, N, h->w_fslab.as<float>(), stride, filt,
-                                                 p->min_score, p->max_score, 0);
-                    gh::TieReplayArgs t2 = tr;
-                    t2.nq = nf;
-                    t2.slab = h->w_fslab.as<float>();
-                    t2.q_stride = stride;
-                    t2.list = list + f0;
-                    t2.compact_rows = 1;
-                    gh::launch_tie_replay(s, l2, t2);
-                }
-            }
-            return GAMMA_HIP_OK;
-        };
-        bool redo = true;
-        if (!h->flat_no_bound && k <= 256 && N > rows_chunk && N < ((int64_t)1 << 32) &&
-            (gh::pairwise_can_emit(nc, d, N - rows_chunk) || (mfma_filter && gh::flat_filter_supported(nc, d, N)))) {
-            GH_TRY(bounded(q0, nc, &redo));
-            if (ties) GH_TRY(tie_phase(false));   // enqueued before the host learns whether a list overflowed
-            if (defer_flat && h->flat_over_dst) {
-                h->flat_over_passes = (mfma_filter && gh::flat_filter_supported(nc, d, N)) ? log_nsl - 1 : 0;   // (counted by the caller if the word says so)
-                // (the caller reads the word after the call's completion event, with the handle free: no host wait under the lock)
-                GH_CHECK(h, hipMemcpyAsync(h->flat_over_dst, h->w_flat_meta.as<int>() + nc + (size_t)nc * 32, sizeof(int),
-                                           hipMemcpyDeviceToHost, s));
-                continue;
-            }
-            GH_TRY(overflowed(nc, &redo));
-            if (!redo) continue;
-            if (mfma_filter && gh::flat_filter_supported(nc, d, N)) h->ff_redone.fetch_add(log_nsl - 1, std::memory_order_relaxed);
-            GH_TRY(replay_join(h));   // (a replay on the side stream writes the rows that are about to be redone)
-        }
-        GH_TRY(unbounded(q0, nc));
-        if (ties) GH_TRY(tie_phase(true));
-    }
-    GH_CHECK(h, hipGetLastError());
-    return GAMMA_HIP_OK;
-}
-
-int flat_search_host_locked(gamma_hip_index* h, const gamma_hip_search_params* p, int nq, const float* x, int k,
-                                  float* distances, int64_t* labels) {
-    SearchLock lk(h);
-    GH_TRY(check_params(h, p, nq, k));
-    if (h->raw_d <= 0) return fail(h, GAMMA_HIP_EINVAL, "raw store not initialised");
-    if (nq > 0 && k > 0 && (!x || !distances || !labels)) return fail(h, GAMMA_HIP_EINVAL, "null buffer");
-    return host_search(h, nq, h->raw_d, x, k, distances, labels, [&](const float* dx, float* dd, int64_t* dl) {
-        return flat_search_device_locked(h, p, nq, dx, k, dd, dl);
-    }, true, &lk);
 }
 
 int ivfpq_search_host_locked(gamma_hip_index* h, const gamma_hip_search_params* p, int nq, const float* x,
@@ -2039,26 +1399,6 @@ int gamma_hip_ivfpq_search_device_wait(gamma_hip_index* h, const gamma_hip_searc
     return e == hipSuccess ? GAMMA_HIP_OK : GAMMA_HIP_EDEVICE;
 }
 
-int gamma_hip_ivfflat_search_device(gamma_hip_index* h, const gamma_hip_search_params* p, int nq, const float* d_x,
-                                    int k, float* d_distances, int64_t* d_labels) {
-    if (!h) return GAMMA_HIP_EINVAL;
-    SearchLock lk(h);
-    GH_TRY(replay_join(h));
-    return ivfflat_search_device_locked(h, p, nq, d_x, k, d_distances, d_labels);
-}
-
-int gamma_hip_ivfflat_search(gamma_hip_index* h, const gamma_hip_search_params* p, int nq, const float* x, int k,
-                             float* distances, int64_t* labels) {
-    if (!h) return GAMMA_HIP_EINVAL;
-    SearchLock lk(h);
-    GH_TRY(check_params(h, p, nq, k));
-    if (!h->ivf_init || !h->ivfflat || h->binivf) return fail(h, GAMMA_HIP_EINVAL, "ivfflat not initialised");
-    if (nq > 0 && k > 0 && (!x || !distances || !labels)) return fail(h, GAMMA_HIP_EINVAL, "null buffer");
-    return host_search(h, nq, h->d, x, k, distances, labels, [&](const float* dx, float* dd, int64_t* dl) {
-        return ivfflat_search_device_locked(h, p, nq, dx, k, dd, dl);
-    }, true, &lk);
-}
-
 int gamma_hip_ivfpq_search(gamma_hip_index* h, const gamma_hip_search_params* p, int nq, const float* x,
                            int k, float* distances, int64_t* labels) {
     if (!h) return GAMMA_HIP_EINVAL;
@@ -2110,38 +1450,6 @@ int gamma_hip_ivfpq_last_stages(gamma_hip_index* h, float* coarse_dis, int64_t* 
     return GAMMA_HIP_OK;
 }
 
-int gamma_hip_ivfpq_search_shard(gamma_hip_index* h, const gamma_hip_search_params* p, int nq,
-                                 const float* d_x, int k, float* d_recall_dis, int64_t* d_recall_ids) {
-    if (!h) return GAMMA_HIP_EINVAL;
-    SearchLock lk(h);
-    GH_NO_PQ4(h, "gamma_hip_ivfpq_search_shard");
-    GH_TRY(replay_join(h));
-    GH_TRY(ivfpq_check(h, p, nq, k));
-    if (k <= 0 || nq == 0) return GAMMA_HIP_OK;
-    if (!d_x || !d_recall_dis || !d_recall_ids) return fail(h, GAMMA_HIP_EINVAL, "null buffer");
-    GH_CHECK(h, hipSetDevice(h->device));
-    const int R = std::max(p->recall_num, k);
-    gh::FilterDesc filt;
-    GH_TRY(build_filter(h, p, &filt));
-    FiltCtx fc;
-    GH_TRY(filt_ctx_single(h, filt, &fc));
-    gamma_hip_search_params pp;
-    GH_TRY(resolve_ties(h, p, &pp, p->nprobe <= gh::tie_replay_max_probes(), "exact_ties = 1 with nprobe > 1024"));
-    if (pp.coarse_mode < 0) pp.coarse_mode = nq < 20 ? 0 : 1;   // decided on the whole call, not per chunk
-    if (pp.coarse_mode == 1 && blas_form_not_restated(nq, h->nlist, h->d)) h->blas_unrestated++;
-    p = &pp;
-    const int chunk = query_chunk(h, nq, p->nprobe);
-    for (int q0 = 0; q0 < nq; q0 += chunk) {
-        const int nc = std::min(chunk, nq - q0);
-        GH_TRY(ivfpq_stage_a(h, p, fc.at(q0), nc, d_x + (size_t)q0 * h->d, R, nullptr, nullptr, /*shard=*/true,
-                             d_recall_dis + (size_t)q0 * R, d_recall_ids + (size_t)q0 * R));
-        h->last_nq = nc;
-    }
-    h->last_P = p->nprobe;
-    h->last_R = R;
-    return GAMMA_HIP_OK;
-}
-
 int gamma_hip_ivfpq_coarse_device(gamma_hip_index* h, const gamma_hip_search_params* p, int nq,
                                   const float* d_x, float* d_coarse_dis, int32_t* d_probe) {
     if (!h) return GAMMA_HIP_EINVAL;
@@ -2164,312 +1472,6 @@ int gamma_hip_ivfpq_coarse_device(gamma_hip_index* h, const gamma_hip_search_par
         GH_TRY(ivfpq_coarse(h, p, std::min(chunk, nq - q0), d_x + (size_t)q0 * h->d, d_coarse_dis + (size_t)q0 * P,
                             d_probe + (size_t)q0 * P));
     GH_CHECK(h, hipGetLastError());
-    return GAMMA_HIP_OK;
-}
-
-static int shard_preassigned(gamma_hip_index* h, const gamma_hip_search_params* p, int nq,
-                             const float* d_x, const float* d_coarse_dis,
-                             const int32_t* d_probe, int k, float* d_recall_dis,
-                             int64_t* d_recall_ids, ghi::BoundXchg* bx) {
-    if (!h) return GAMMA_HIP_EINVAL;
-    SearchLock lk(h);
-    // (a call with a reduction makes it exactly once, whatever happens: the other shards are waiting in theirs)
-    struct ReduceOnce {
-        H* h; ghi::BoundXchg* bx; int nq; bool l2;
-        ~ReduceOnce() {
-            if (bx && !bx->called && bx->d_bound && nq > 0) {
-                gh::launch_fill_f32(h->stream, bx->d_bound, nq, l2 ? INFINITY : -INFINITY);
-                (void)bx->reduce(h, nq, l2);
-            }
-        }
-    } reduce_once{h, bx, nq, p && p->metric == GAMMA_HIP_METRIC_L2};
-    GH_NO_PQ4(h, "gamma_hip_ivfpq_search_shard_preassigned / _bounded");
-    GH_TRY(replay_join(h));
-    GH_TRY(ivfpq_check(h, p, nq, k));
-    if (k <= 0 || nq == 0) return GAMMA_HIP_OK;
-    if (!d_coarse_dis || !d_probe) return fail(h, GAMMA_HIP_EINVAL, "null coarse assignment");
-    if (!d_x || !d_recall_dis || !d_recall_ids) return fail(h, GAMMA_HIP_EINVAL, "null buffer");
-    if (bx && !bx->d_bound) return fail(h, GAMMA_HIP_EINVAL, "null bound buffer");
-    GH_CHECK(h, hipSetDevice(h->device));
-    const int R = std::max(p->recall_num, k), P = p->nprobe;
-    gamma_hip_search_params pp;
-    GH_TRY(resolve_ties(h, p, &pp, P <= gh::tie_replay_max_probes(), "exact_ties = 1 with nprobe > 1024"));
-    p = &pp;
-    gh::FilterDesc filt;
-    GH_TRY(build_filter(h, p, &filt));
-    FiltCtx fc;
-    GH_TRY(filt_ctx_single(h, filt, &fc));
-    int chunk = query_chunk(h, nq, P);
-    struct StrideScope {   // the measured stride holds for this call only
-        H* h;
-        ~StrideScope() { h->q_stride_cap = 0; }
-    } stride_scope{h};
-    static const bool no_two = getenv("GAMMA_HIP_NO_TWO_PHASE") != nullptr;
-    if (chunk < nq || (bx && !no_two)) {
-        // A shard scans ~P / W of a query's probes, but the slab stride of the general path is P x the longest list:
-        // the budget then cuts the batch (W times the queries of one rank) into many chunks, each with its own launches
-        // and its own handful of fallback queries (full-size C4, W = 8: 20 chunks, 5.7 ms of a 37 ms step).  The
-        // assignment is on the device: one small kernel measures the longest candidate row of THIS batch over THIS
-        // shard's lists, the host reads the one word back (the call is tens of milliseconds long) and sizes the chunks
-        // by it.
-        GH_CHECK(h, h->w_shard_cut.ensure(std::max<size_t>((size_t)nq, 16)));   // (its first word; the flags come later)
-        gh::launch_max_local_total(h->stream, d_probe, nq, P, h->d_list_len, h->d_list_mask, h->nlist, h->w_shard_cut.as<int>());
-        int mx[2] = {0, 0};
-        GH_CHECK(h, hipMemcpyAsync(mx, h->w_shard_cut.p, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        GH_CHECK(h, hipStreamSynchronize(h->stream));
-        h->q_stride_cap = (std::max<int64_t>(mx[0], 1) + 3) & ~(int64_t)3;
-        const int64_t by_dist = (int64_t)(h->dist_budget_bytes / ((size_t)h->q_stride_cap * sizeof(float)));
-        chunk = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(by_dist, coarse_chunk(h, nq)), nq));
-        if (bx && !no_two && chunk < nq && (int64_t)nq <= coarse_chunk(h, nq)) {
-            // Two phases need the batch in ONE chunk (one reduction per call).  The slab of a W-rank job's batch -- W x the
-            // queries of a rank, each with its longest-case row -- can exceed the general workspace budget (full-size C4, 8
-            // shards: ~40 GB against 32); a list shard holds 1 / W of the index, so the memory is there: up to half of what
-            // is free now (the workspace stays allocated for the calls that follow).
-            size_t free_b = 0, total_b = 0;
-            const size_t need = (size_t)nq * (size_t)h->q_stride_cap * sizeof(float);
-            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need <= h->w_dist.cap + free_b / 2) chunk = nq;
-            else (void)hipGetLastError();
-        }
-        if (bx && !no_two && chunk >= nq) {
-            // two phases (ivfpq_stage_a, BoundXchg): the batch runs as ONE chunk, so the reduction is one collective; the scan
-            // behind sees a search of P' probes -- the most owned probes any query of the batch has -- all of them dense
-            const char* g1e = getenv("GAMMA_HIP_SHARD_G1");   // (read per call: tools sweep it inside one process)
-            const int g1_env = g1e ? atoi(g1e) : 2;
-            bx->two_phase = true;
-            bx->P_in = P;
-            bx->G1 = std::max(1, g1_env);
-            const int g = bx->G1;
-            pp.nprobe = std::max(1, std::min(P, ((std::max(mx[1], 1) + g - 1) / g) * g));
-        }
-    }
-    const int P_in = P;
-    const int Pe = pp.nprobe;   // rows of the compacted assignment the scan sees (P unless two phases)
-    bool all_cut = true;
-    for (int q0 = 0; q0 < nq; q0 += chunk) {
-        const int nc = std::min(chunk, nq - q0);
-        GH_TRY(ivfpq_stage_a(h, p, fc.at(q0), nc, d_x + (size_t)q0 * h->d, R, d_coarse_dis + (size_t)q0 * P_in,
-                             d_probe + (size_t)q0 * P_in, /*shard=*/true, d_recall_dis + (size_t)q0 * R,
-                             d_recall_ids + (size_t)q0 * R, (bx && bx->two_phase) ? bx : nullptr));
-        h->last_nq = nc;
-        if (chunk < nq && h->shard_cut_nq == nc) {   // a call of several chunks: the cut-tie flags of all of them
-            GH_CHECK(h, h->w_shard_cut.ensure((size_t)nq));
-            GH_CHECK(h, hipMemcpyAsync(h->w_shard_cut.as<uint8_t>() + q0, h->w_tcut.p, (size_t)nc, hipMemcpyDeviceToDevice, h->stream));
-        } else if (chunk < nq) {
-            all_cut = false;
-        }
-    }
-    h->shard_cut_chunked = chunk < nq && all_cut;
-    if (h->shard_cut_chunked) h->shard_cut_nq = nq;
-    h->last_P = Pe;
-    h->last_R = R;
-    return GAMMA_HIP_OK;
-}
-
-int gamma_hip_ivfpq_search_shard_preassigned(gamma_hip_index* h, const gamma_hip_search_params* p, int nq,
-                                             const float* d_x, const float* d_coarse_dis,
-                                             const int32_t* d_probe, int k, float* d_recall_dis,
-                                             int64_t* d_recall_ids) {
-    return shard_preassigned(h, p, nq, d_x, d_coarse_dis, d_probe, k, d_recall_dis, d_recall_ids, nullptr);
-}
-
-int gamma_hip_bound_combine(void* stream, float* d_acc, const float* d_in, int n, int take_max) {
-    if (n < 0 || (n > 0 && (!d_acc || !d_in))) return GAMMA_HIP_EINVAL;
-    gh::launch_bound_combine(static_cast<hipStream_t>(stream), d_acc, d_in, n, take_max);
-    return hipGetLastError() == hipSuccess ? GAMMA_HIP_OK : GAMMA_HIP_EDEVICE;
-}
-
-int gamma_hip_ivfpq_search_shard_bounded(gamma_hip_index* h, const gamma_hip_search_params* p, int nq,
-                                         const float* d_x, const float* d_coarse_dis, const int32_t* d_probe, int k,
-                                         float* d_recall_dis, int64_t* d_recall_ids, float* d_bound,
-                                         gamma_hip_bound_reduce_fn reduce, void* user) {
-    ghi::BoundXchg bx;
-    bx.d_bound = d_bound;
-    bx.fn = reduce;
-    bx.user = user;
-    return shard_preassigned(h, p, nq, d_x, d_coarse_dis, d_probe, k, d_recall_dis, d_recall_ids, &bx);
-}
-
-static int merge_rerank_impl(gamma_hip_index* h, const gamma_hip_search_params* p, int nshards, int nq,
-                             const float* d_x, int k, const float* d_all_dis, const int64_t* d_all_ids, const float* d_all_exact,
-                             int q0, int nq_local, float* d_distances, int64_t* d_labels);
-int gamma_hip_ivfpq_merge_rerank(gamma_hip_index* h, const gamma_hip_search_params* p, int nshards, int nq,
-                                 const float* d_x, int k, const float* d_all_dis, const int64_t* d_all_ids,
-                                 int q0, int nq_local, float* d_distances, int64_t* d_labels) {
-    return merge_rerank_impl(h, p, nshards, nq, d_x, k, d_all_dis, d_all_ids, nullptr, q0, nq_local, d_distances, d_labels);
-}
-int gamma_hip_ivfpq_merge_rerank_exact(gamma_hip_index* h, const gamma_hip_search_params* p, int nshards, int nq,
-                                       const float* d_x, int k, const float* d_all_dis, const int64_t* d_all_ids,
-                                       const float* d_all_exact, int q0, int nq_local, float* d_distances, int64_t* d_labels) {
-    if (!d_all_exact) return GAMMA_HIP_EINVAL;
-    return merge_rerank_impl(h, p, nshards, nq, d_x, k, d_all_dis, d_all_ids, d_all_exact, q0, nq_local, d_distances, d_labels);
-}
-static int merge_rerank_impl(gamma_hip_index* h, const gamma_hip_search_params* p, int nshards, int nq,
-                             const float* d_x, int k, const float* d_all_dis, const int64_t* d_all_ids, const float* d_all_exact,
-                             int q0, int nq_local, float* d_distances, int64_t* d_labels) {
-    if (!h) return GAMMA_HIP_EINVAL;
-    SearchLock lk(h);
-    GH_NO_PQ4(h, "gamma_hip_ivfpq_merge_rerank(_exact)");
-    if (h->raw_half && p && p->has_rank && !d_all_exact) return half_refuse(h, "gamma_hip_ivfpq_merge_rerank without travelled distances");
-    if (h->raw_byte && p && p->has_rank && !d_all_exact) return byte_refuse(h, "gamma_hip_ivfpq_merge_rerank without travelled distances");
-    if (h->raw_sq8 && p && p->has_rank && !d_all_exact) return sq8_refuse(h, "gamma_hip_ivfpq_merge_rerank without travelled distances");
-    GH_TRY(replay_join(h));
-    GH_TRY(ivfpq_check(h, p, nq, k));
-    if (nshards <= 0 || q0 < 0 || nq_local < 0 || q0 + nq_local > nq) return fail(h, GAMMA_HIP_EINVAL, "bad shard/query range");
-    if (k <= 0 || nq_local == 0) return GAMMA_HIP_OK;
-    GH_CHECK(h, hipSetDevice(h->device));
-    const bool l2 = p->metric == GAMMA_HIP_METRIC_L2;
-    const int R = std::max(p->recall_num, k);
-    if ((int64_t)nshards * R > (int64_t)1 << 24) return fail(h, GAMMA_HIP_EINVAL, "too many candidates");
-    hipStream_t s = h->stream;
-    GH_CHECK(h, h->w_cand_dis.ensure((size_t)nq_local * R * sizeof(float)));
-    GH_CHECK(h, h->w_cand_ids.ensure((size_t)nq_local * R * sizeof(int64_t)));
-    {
-        StageScope t(h, GAMMA_HIP_STAGE_SELECT);
-        static const bool no_merge_kernel = getenv("GAMMA_HIP_NO_MERGE_KERNEL") != nullptr;
-        if (no_merge_kernel ||
-            !gh::launch_merge_shards(s, l2, d_all_dis, d_all_ids, nshards, nq, R, q0, nq_local,
-                                     h->w_cand_dis.as<float>(), h->w_cand_ids.as<int64_t>())) {
-            // general shapes: transpose to [nq][W * R], select, translate positions to ids
-            GH_CHECK(h, h->w_m_dis.ensure((size_t)nq * nshards * R * sizeof(float)));
-            GH_CHECK(h, h->w_m_ids.ensure((size_t)nq * nshards * R * sizeof(int64_t)));
-            GH_CHECK(h, h->w_cand_pos.ensure((size_t)nq_local * R * sizeof(int)));
-            gh::launch_gather_shards(s, d_all_dis, d_all_ids, nshards, nq, R, h->w_m_dis.as<float>(),
-                                     h->w_m_ids.as<int64_t>(), l2 ? INFINITY : -INFINITY);
-            const int64_t stride = (int64_t)nshards * R;
-            gh::launch_select_topk(s, l2, h->w_m_dis.as<float>() + (size_t)q0 * stride, stride, nullptr,
-                                   (int)stride, (int)stride, nq_local, R, h->w_cand_dis.as<float>(),
-                                   h->w_cand_pos.as<int>());
-            gh::launch_take_ids(s, h->w_cand_pos.as<int>(), h->w_m_ids.as<int64_t>() + (size_t)q0 * stride, stride,
-                                nq_local, R, h->w_cand_ids.as<int64_t>());
-        }
-        GH_CHECK(h, hipGetLastError());
-    }
-    // exact ties: the slice's queries whose result a tie can change are listed (gamma_hip_ivfpq_merge_flagged); the
-    // caller gathers their candidate streams from the shards and has them replayed (gamma_hip_ivfpq_merge_replay)
-    gamma_hip_search_params pp;
-    GH_TRY(resolve_ties(h, p, &pp, p->nprobe <= gh::tie_replay_max_probes(), "exact_ties = 1 with nprobe > 1024"));
-    p = &pp;
-    const bool ties = tie_on(p);
-    h->merge_flags = ties;
-    h->merge_nql = nq_local;
-    if (ties) {
-        GH_CHECK(h, h->w_tcut.ensure((size_t)nq_local));
-        GH_CHECK(h, h->w_tlist.ensure(((size_t)nq_local + 1) * sizeof(int)));
-        GH_CHECK(h, hipMemsetAsync(h->w_tlist.p, 0, sizeof(int), s));
-        gh::launch_flag_merge_cut(s, d_all_dis, nshards, nq, R, q0, nq_local, h->w_cand_dis.as<float>(), h->w_cand_ids.as<int64_t>(),
-                                  h->w_tcut.as<uint8_t>(), h->merge_shard_flags);
-    }
-    h->merge_shard_flags = nullptr;   // one merge, with ties or without
-    if (d_all_exact && p->has_rank) {
-        // raw vectors sharded with their lists: the exact distance of every candidate travelled with it (computed by the shard
-        // that holds the row, score window applied there).  compute_dis (gamma_index_ivfpq.cc:646-680) from those: the merged
-        // candidates' distances are looked up in the shard tables, then the non-fused finish of stage B -- top-k of the row of
-        // exact distances (equal distances keep the ADC order), output, tie flags.
-        const float neutral = l2 ? 3.402823466e+38f : -3.402823466e+38f;
-        StageScope t(h, GAMMA_HIP_STAGE_RERANK);
-        GH_CHECK(h, h->w_exact.ensure((size_t)nq_local * R * sizeof(float)));
-        GH_CHECK(h, h->w_selv.ensure((size_t)nq_local * k * sizeof(float)));
-        GH_CHECK(h, h->w_selp.ensure((size_t)nq_local * k * sizeof(int)));
-        gh::launch_lookup_exact(s, l2, d_all_dis, d_all_ids, d_all_exact, nshards, nq, R, q0, nq_local, h->w_cand_dis.as<float>(),
-                                h->w_cand_ids.as<int64_t>(), h->w_exact.as<float>());
-        gh::launch_select_topk(s, l2, h->w_exact.as<float>(), R, nullptr, R, R, nq_local, k, h->w_selv.as<float>(), h->w_selp.as<int>());
-        gh::launch_finalize_topk(s, h->w_selv.as<float>(), h->w_selp.as<int>(), nq_local, k, h->w_cand_ids.as<int64_t>(), R, 0, neutral,
-                                 d_distances, d_labels);
-        if (ties) {
-            gh::TieFlags tf;
-            tf.cut = h->w_tcut.as<uint8_t>();
-            tf.count = h->w_tlist.as<int>();
-            tf.list = h->w_tlist.as<int>() + 1;
-            tf.stats = h->d_tie_stats;
-            GH_CHECK(h, h->w_textra.ensure((size_t)nq_local));
-            GH_CHECK(h, hipMemsetAsync(h->w_textra.p, 0, (size_t)nq_local, s));
-            gh::launch_flag_cut_ties(s, h->w_exact.as<float>(), R, nullptr, nq_local, k, h->w_selv.as<float>(), h->w_selp.as<int>(),
-                                     nullptr, h->w_textra.as<uint8_t>(), R, 1);
-            gh::launch_tie_list(s, tf.cut, h->w_textra.as<uint8_t>(), nq_local, tf.list, tf.count, tf.stats);
-        }
-        GH_CHECK(h, hipGetLastError());
-        return GAMMA_HIP_OK;
-    }
-    return ivfpq_stage_b(h, p, nq_local, d_x + (size_t)q0 * h->d, R, k, h->w_cand_dis.as<float>(),
-                         h->w_cand_ids.as<int64_t>(), d_distances, d_labels, nullptr, ties ? 2 : 0);
-}
-
-int gamma_hip_ivfpq_shard_exact(gamma_hip_index* h, const gamma_hip_search_params* p, int nq, const float* d_x,
-                                const int64_t* d_ids, int R, float* d_exact) {
-    if (!h || !p) return GAMMA_HIP_EINVAL;
-    if (nq <= 0 || R <= 0) return GAMMA_HIP_OK;
-    if (!d_x || !d_ids || !d_exact) return GAMMA_HIP_EINVAL;
-    SearchLock lk(h);
-    GH_NO_PQ4(h, "gamma_hip_ivfpq_shard_exact");
-    if (h->raw_half) return half_refuse(h, "gamma_hip_ivfpq_shard_exact");
-    if (h->raw_byte) return byte_refuse(h, "gamma_hip_ivfpq_shard_exact");
-    if (h->raw_sq8) return sq8_refuse(h, "gamma_hip_ivfpq_shard_exact");
-    GH_TRY(replay_join(h));
-    if (!h->d_raw || h->raw_d != h->d) return fail(h, GAMMA_HIP_EINVAL, "no raw store");
-    GH_CHECK(h, hipSetDevice(h->device));
-    // (a dense store answers for every id; a sharded one for the vectors it holds, the sentinel elsewhere)
-    gh::launch_rerank_dist(h->stream, p->metric == GAMMA_HIP_METRIC_L2, d_x, nq, h->d, h->d_raw, h->nraw, d_ids, R, p->min_score,
-                           p->max_score, d_exact, h->raw_sparse ? h->d_raw_slot : nullptr, h->raw_sparse ? h->raw_slot_cap : 0);
-    GH_CHECK(h, hipGetLastError());
-    return GAMMA_HIP_OK;
-}
-
-int gamma_hip_ivfpq_shard_export_exact(gamma_hip_index* h, const gamma_hip_search_params* p, int nf, const float* d_xf,
-                                       const float* d_vals, const int64_t* d_ids, const int32_t* d_off, int64_t stride,
-                                       const float* d_bound_f, float* d_ex) {
-    if (!h || !p) return GAMMA_HIP_EINVAL;
-    if (nf <= 0) return GAMMA_HIP_OK;
-    if (!d_xf || !d_vals || !d_ids || !d_off || !d_bound_f || !d_ex || stride < 1) return GAMMA_HIP_EINVAL;
-    SearchLock lk(h);
-    GH_NO_PQ4(h, "gamma_hip_ivfpq_shard_export_exact");
-    if (h->raw_half) return half_refuse(h, "gamma_hip_ivfpq_shard_export_exact");
-    if (h->raw_byte) return byte_refuse(h, "gamma_hip_ivfpq_shard_export_exact");
-    if (h->raw_sq8) return sq8_refuse(h, "gamma_hip_ivfpq_shard_export_exact");
-    if (!h->d_raw || h->raw_d != h->d || !h->raw_sparse) return fail(h, GAMMA_HIP_EINVAL, "export of exact distances: a sharded raw store (gamma_hip_raw_put)");
-    GH_CHECK(h, hipSetDevice(h->device));
-    gh::launch_export_exact(h->stream, p->metric == GAMMA_HIP_METRIC_L2, d_xf, nf, h->d, h->d_raw, h->d_raw_slot, h->raw_slot_cap,
-                            d_vals, d_ids, stride, d_off, p->nprobe, d_bound_f, d_ex);
-    GH_CHECK(h, hipGetLastError());
-    return GAMMA_HIP_OK;
-}
-
-int gamma_hip_ivfpq_shard_cut_flags(gamma_hip_index* h, int nq, uint8_t* d_flags) {
-    if (!h || nq < 0 || (nq > 0 && !d_flags)) return GAMMA_HIP_EINVAL;
-    if (nq == 0) return GAMMA_HIP_OK;
-    SearchLock lk(h);
-    GH_NO_PQ4(h, "gamma_hip_ivfpq_shard_cut_flags");
-    GH_CHECK(h, hipSetDevice(h->device));
-    if (h->shard_cut_nq == nq) {
-        GH_CHECK(h, hipMemcpyAsync(d_flags, h->shard_cut_chunked ? h->w_shard_cut.p : h->w_tcut.p, (size_t)nq,
-                                   hipMemcpyDeviceToDevice, h->stream));
-    } else {
-        // no flags from the last shard search (exact ties off, or beyond the replay's range): "may have cut a tie"
-        GH_CHECK(h, hipMemsetAsync(d_flags, 1, (size_t)nq, h->stream));
-    }
-    return GAMMA_HIP_OK;
-}
-
-int gamma_hip_ivfpq_merge_set_shard_flags(gamma_hip_index* h, const uint8_t* d_flags) {
-    if (!h) return GAMMA_HIP_EINVAL;
-    SearchLock lk(h);
-    GH_NO_PQ4(h, "gamma_hip_ivfpq_merge_set_shard_flags");
-    h->merge_shard_flags = d_flags;
-    return GAMMA_HIP_OK;
-}
-
-int gamma_hip_ivfpq_merge_flagged(gamma_hip_index* h, int* n_flagged, const int32_t** d_list) {
-    if (!h || !n_flagged) return GAMMA_HIP_EINVAL;
-    SearchLock lk(h);
-    GH_NO_PQ4(h, "gamma_hip_ivfpq_merge_flagged");
-    *n_flagged = 0;
-    if (d_list) *d_list = nullptr;
-    if (!h->merge_flags) return GAMMA_HIP_OK;
-    GH_CHECK(h, hipSetDevice(h->device));
-    int n = 0;
-    GH_CHECK(h, hipMemcpyAsync(&n, h->w_tlist.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    GH_CHECK(h, hipStreamSynchronize(h->stream));
-    *n_flagged = std::min(n, h->merge_nql);
-    if (d_list) *d_list = h->w_tlist.as<int32_t>() + 1;
     return GAMMA_HIP_OK;
 }
 
@@ -2499,250 +1501,5 @@ int gamma_hip_debug_heap_stream(gamma_hip_index* h, int op, int k, int n, const 
     }
     return GAMMA_HIP_OK;
 }
-
-int gamma_hip_gather_rows(gamma_hip_index* h, const void* d_src, int row_words, const int32_t* d_list, int n, void* d_dst) {
-    if (!h || row_words <= 0 || n < 0) return GAMMA_HIP_EINVAL;
-    if (n == 0) return GAMMA_HIP_OK;
-    if (!d_src || !d_list || !d_dst) return GAMMA_HIP_EINVAL;
-    SearchLock lk(h);
-    GH_CHECK(h, hipSetDevice(h->device));
-    gh::launch_gather_words(h->stream, d_src, d_list, n, row_words, d_dst);
-    GH_CHECK(h, hipGetLastError());
-    return GAMMA_HIP_OK;
-}
-
-int gamma_hip_ivfpq_shard_export_rows(gamma_hip_index* h, const gamma_hip_search_params* p, int nf, const int32_t* d_probe_f,
-                                      int64_t* max_entries) {
-    if (!h || !p || !max_entries) return GAMMA_HIP_EINVAL;
-    *max_entries = 0;
-    if (nf <= 0) return GAMMA_HIP_OK;
-    if (!d_probe_f) return GAMMA_HIP_EINVAL;
-    SearchLock lk(h);
-    GH_NO_PQ4(h, "gamma_hip_ivfpq_shard_export_rows");
-    GH_TRY(replay_join(h));
-    if (!h->ivf_init || h->ivfflat) return fail(h, GAMMA_HIP_EINVAL, "ivfpq not initialised");
-    GH_CHECK(h, hipSetDevice(h->device));
-    GH_CHECK(h, h->w_qtotal.ensure(sizeof(int)));
-    GH_CHECK(h, hipMemsetAsync(h->w_qtotal.p, 0, sizeof(int), h->stream));
-    GH_CHECK(h, hipStreamWaitEvent(h->stream, h->ver_ev[h->cur_ver], 0));
-    gh::launch_shard_export_rows(h->stream, d_probe_f, nf, p->nprobe, h->d_list_len, h->d_list_mask, h->nlist, h->w_qtotal.as<int>());
-    int mx = 0;
-    GH_CHECK(h, hipMemcpyAsync(&mx, h->w_qtotal.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    GH_CHECK(h, hipStreamSynchronize(h->stream));
-    *max_entries = mx;
-    return GAMMA_HIP_OK;
-}
-
-int gamma_hip_ivfpq_shard_export(gamma_hip_index* h, const gamma_hip_search_params* p, int nf, const float* d_xf,
-                                 const float* d_cdis_f, const int32_t* d_probe_f, int64_t stride, float* d_vals, int64_t* d_ids,
-                                 int32_t* d_off) {
-    if (!h) return GAMMA_HIP_EINVAL;
-    SearchLock lk(h);
-    GH_NO_PQ4(h, "gamma_hip_ivfpq_shard_export");
-    GH_TRY(replay_join(h));
-    GH_TRY(ivfpq_check(h, p, nf, 1));
-    if (nf == 0) return GAMMA_HIP_OK;
-    if (!d_xf || !d_cdis_f || !d_probe_f || !d_vals || !d_ids || !d_off) return fail(h, GAMMA_HIP_EINVAL, "null buffer");
-    if (p->nprobe > gh::tie_replay_max_probes()) return fail(h, GAMMA_HIP_EINVAL, "nprobe beyond the replay's range");
-    GH_CHECK(h, hipSetDevice(h->device));
-    const int P = p->nprobe, R = std::max(p->recall_num, 1);
-    if (stride < 1) return fail(h, GAMMA_HIP_EINVAL, "stride");
-    gamma_hip_search_params pp = *p;   // the scan behind an export flags nothing: its top-R goes to scratch
-    pp.exact_ties = -1;
-    p = &pp;
-    gh::FilterDesc filt;
-    GH_TRY(build_filter(h, p, &filt));
-    FiltCtx fc;
-    GH_TRY(filt_ctx_single(h, filt, &fc));
-    // the plain scan (every distance of the owned probed lists in the slab, scan order); its top-R goes to scratch
-    const bool saved_bound = h->scan_bound;
-    h->scan_bound = false;
-    const int chunk = query_chunk(h, nf, P);
-    int rc = GAMMA_HIP_OK;
-    for (int f0 = 0; f0 < nf && rc == GAMMA_HIP_OK; f0 += chunk) {
-        const int nc = std::min(chunk, nf - f0);
-        rc = h->w_m_dis.ensure((size_t)nc * R * sizeof(float)) == hipSuccess &&
-                     h->w_m_ids.ensure((size_t)nc * R * sizeof(int64_t)) == hipSuccess
-                 ? GAMMA_HIP_OK
-                 : fail(h, GAMMA_HIP_ENOMEM, "export scratch");
-        if (rc == GAMMA_HIP_OK)
-            rc = ivfpq_stage_a(h, p, fc.at(f0), nc, d_xf + (size_t)f0 * h->d, R, d_cdis_f + (size_t)f0 * P,
-                               d_probe_f + (size_t)f0 * P, /*shard=*/true, h->w_m_dis.as<float>(), h->w_m_ids.as<int64_t>());
-        if (rc == GAMMA_HIP_OK)
-            gh::launch_shard_export(h->stream, d_probe_f + (size_t)f0 * P, nc, P, h->d_list_len, h->d_list_off, h->d_list_mask,
-                                    h->nlist, h->d_ids, h->w_dist.as<float>(), h->tie.q_stride, stride,
-                                    d_vals + (size_t)f0 * stride, d_ids + (size_t)f0 * stride, d_off + (size_t)f0 * (P + 1));
-    }
-    h->scan_bound = saved_bound;
-    if (rc != GAMMA_HIP_OK) return rc;
-    GH_CHECK(h, hipGetLastError());
-    return GAMMA_HIP_OK;
-}
-
-static int merge_replay_impl(gamma_hip_index* h, const gamma_hip_search_params* p, int nshards, int nf, const float* d_x_slice,
-                             int64_t stride, const float* d_vals_all, const int64_t* d_ids_all, const int32_t* d_off_all, const float* d_ex_all,
-                             int k, const int32_t* d_list, float* d_distances, int64_t* d_labels);
-int gamma_hip_ivfpq_merge_replay(gamma_hip_index* h, const gamma_hip_search_params* p, int nshards, int nf, const float* d_x_slice,
-                                 int64_t stride, const float* d_vals_all, const int64_t* d_ids_all, const int32_t* d_off_all, int k,
-                                 const int32_t* d_list, float* d_distances, int64_t* d_labels) {
-    return merge_replay_impl(h, p, nshards, nf, d_x_slice, stride, d_vals_all, d_ids_all, d_off_all, nullptr, k, d_list, d_distances, d_labels);
-}
-int gamma_hip_ivfpq_merge_replay_exact(gamma_hip_index* h, const gamma_hip_search_params* p, int nshards, int nf, const float* d_x_slice,
-                                       int64_t stride, const float* d_vals_all, const int64_t* d_ids_all, const int32_t* d_off_all,
-                                       const float* d_ex_all, int k, const int32_t* d_list, float* d_distances, int64_t* d_labels) {
-    if (!d_ex_all) return GAMMA_HIP_EINVAL;
-    return merge_replay_impl(h, p, nshards, nf, d_x_slice, stride, d_vals_all, d_ids_all, d_off_all, d_ex_all, k, d_list, d_distances, d_labels);
-}
-static int merge_replay_impl(gamma_hip_index* h, const gamma_hip_search_params* p, int nshards, int nf, const float* d_x_slice,
-                             int64_t stride, const float* d_vals_all, const int64_t* d_ids_all, const int32_t* d_off_all, const float* d_ex_all,
-                             int k, const int32_t* d_list, float* d_distances, int64_t* d_labels) {
-    if (!h) return GAMMA_HIP_EINVAL;
-    SearchLock lk(h);
-    GH_NO_PQ4(h, "gamma_hip_ivfpq_merge_replay(_exact)");
-    if (h->raw_half && p && p->has_rank && !d_ex_all) return half_refuse(h, "gamma_hip_ivfpq_merge_replay without travelled distances");
-    if (h->raw_byte && p && p->has_rank && !d_ex_all) return byte_refuse(h, "gamma_hip_ivfpq_merge_replay without travelled distances");
-    if (h->raw_sq8 && p && p->has_rank && !d_ex_all) return sq8_refuse(h, "gamma_hip_ivfpq_merge_replay without travelled distances");
-    GH_TRY(ivfpq_check(h, p, nf, k));
-    if (nf == 0 || k <= 0) return GAMMA_HIP_OK;
-    if (!d_x_slice || !d_vals_all || !d_ids_all || !d_off_all || !d_list || !d_distances || !d_labels)
-        return fail(h, GAMMA_HIP_EINVAL, "null buffer");
-    if (!h->merge_flags) return fail(h, GAMMA_HIP_EINVAL, "no merge with tie flags before the replay");
-    GH_CHECK(h, hipSetDevice(h->device));
-    const bool l2 = p->metric == GAMMA_HIP_METRIC_L2;
-    const int P = p->nprobe, R = std::max(p->recall_num, k);
-    if (R > gh::tie_replay_max_k() || P > gh::tie_replay_max_probes()) return fail(h, GAMMA_HIP_EINVAL, "beyond the replay's range");
-    if (p->has_rank && !d_ex_all && (!h->d_raw || h->raw_d != h->d || h->raw_sparse))
-        return fail(h, GAMMA_HIP_EINVAL, "has_rank needs the raw store (or the exact distances exported with the streams)");
-    hipStream_t s = h->stream;
-    const int64_t mstride = ((int64_t)nshards * stride + 3) & ~(int64_t)3;   // a row assembled from every shard's export
-    GH_CHECK(h, h->w_mr_vals.ensure((size_t)nf * mstride * sizeof(float)));
-    GH_CHECK(h, h->w_mr_ids.ensure((size_t)nf * mstride * sizeof(int64_t)));
-    GH_CHECK(h, h->w_mr_meta.ensure((size_t)nf * (P + 1) * sizeof(int32_t) + (size_t)nf * P * sizeof(int64_t) + 64));
-    int64_t* m_base = h->w_mr_meta.as<int64_t>();
-    int* count = reinterpret_cast<int*>(m_base + (size_t)nf * P);
-    int32_t* m_off = count + 16;
-    GH_CHECK(h, hipMemcpyAsync(count, &nf, sizeof(int), hipMemcpyHostToDevice, s));
-    gh::launch_merge_streams(s, nshards, nf, P, stride, mstride, d_vals_all, d_ids_all, d_off_all, h->w_mr_vals.as<float>(),
-                             h->w_mr_ids.as<int64_t>(), m_off, m_base, l2 ? INFINITY : -INFINITY);
-    gh::TieReplayArgs a;
-    if (d_ex_all && p->has_rank) {
-        // the exported exact distances, assembled probe by probe exactly like the ADC values (same positions); the ids of this
-        // second pass go to scratch.  A member of the recall_num-heap whose distance no shard exported is COUNTED and fails the call.
-        GH_CHECK(h, h->w_fslab.ensure((size_t)nf * mstride * sizeof(float)));
-        GH_CHECK(h, h->w_m_ids.ensure((size_t)nf * mstride * sizeof(int64_t)));
-        GH_CHECK(h, h->w_lm_cnt.ensure(64));
-        GH_CHECK(h, hipMemsetAsync(h->w_lm_cnt.p, 0, sizeof(int), s));
-        gh::launch_merge_streams(s, nshards, nf, P, stride, mstride, d_ex_all, d_ids_all, d_off_all, h->w_fslab.as<float>(),
-                                 h->w_m_ids.as<int64_t>(), m_off, m_base, __builtin_nanf(""));
-        a.ex_slab = h->w_fslab.as<float>();
-        a.ex_missing = h->w_lm_cnt.as<int>();
-    }
-    a.list = d_list;
-    a.count = count;
-    a.nq = nf;
-    a.slab = h->w_mr_vals.as<float>();
-    a.q_stride = mstride;
-    a.pair_off = m_off;
-    a.pair_base = m_base;
-    a.ids = h->w_mr_ids.as<int64_t>();
-    a.P = P;
-    a.G = P;
-    a.ready = nullptr;
-    a.surv = nullptr;
-    a.gcnt = nullptr;
-    a.nsl = 0;
-    a.slice_cap = 0;
-    a.x = d_x_slice;
-    a.d = h->d;
-    a.raw = h->d_raw;
-    a.nraw = h->nraw;
-    a.R = R;
-    a.k = k;
-    a.has_rank = p->has_rank ? 1 : 0;
-    a.min_score = p->min_score;
-    a.max_score = p->max_score;
-    a.neutral = l2 ? 3.402823466e+38f : -3.402823466e+38f;
-    a.cand_dis = h->w_cand_dis.as<float>();     // the merged tables of the slice (gamma_hip_ivfpq_merge_rerank)
-    a.cand_ids = h->w_cand_ids.as<int64_t>();
-    a.distances = d_distances;
-    a.labels = d_labels;
-    a.compact_rows = 1;
-    gh::launch_tie_replay(s, l2, a);
-    GH_CHECK(h, hipGetLastError());
-    if (a.ex_missing) {
-        int missing = 0;
-        GH_CHECK(h, hipMemcpyAsync(&missing, a.ex_missing, sizeof(int), hipMemcpyDeviceToHost, s));
-        GH_CHECK(h, hipStreamSynchronize(s));
-        if (missing) return fail(h, GAMMA_HIP_EDEVICE, "tie replay: a member of the recall_num-heap arrived without its exact distance");
-    }
-    return GAMMA_HIP_OK;
-}
-
-int gamma_hip_flat_search_device(gamma_hip_index* h, const gamma_hip_search_params* p, int nq,
-                                 const float* d_x, int k, float* d_distances, int64_t* d_labels) {
-    if (!h) return GAMMA_HIP_EINVAL;
-    SearchLock lk(h);
-    GH_TRY(replay_join(h));
-    return flat_search_device_locked(h, p, nq, d_x, k, d_distances, d_labels);
-}
-
-int gamma_hip_flat_search_device_wait(gamma_hip_index* h, const gamma_hip_search_params* p, int nq,
-                                      const float* d_x, int k, float* d_distances, int64_t* d_labels) {
-    if (!h) return GAMMA_HIP_EINVAL;
-    hipEvent_t ev = nullptr;
-    int* over = nullptr;
-    int over_passes = 0;   // filter passes of this call: redone if its overflow word is set
-    {
-        SearchLock lk(h);
-        GH_CHECK(h, hipSetDevice(h->device));
-        const unsigned slot = h->call_seq++ & 3u;
-        if (!h->ev_call[slot]) GH_CHECK(h, hipEventCreateWithFlags(&h->ev_call[slot], hipEventDisableTiming));
-        ev = h->ev_call[slot];
-        if (!h->pin_flat_over) {
-            GH_CHECK(h, hipHostMalloc((void**)&h->pin_flat_over, 4 * sizeof(int), hipHostMallocDefault));
-            memset(h->pin_flat_over, 0, 4 * sizeof(int));
-        }
-        over = h->pin_flat_over + slot;
-        *over = 0;
-        h->defer_now = h->side2 != nullptr;
-        h->flat_over_dst = over;
-        h->flat_over_passes = 0;
-        const int rc = flat_search_device_locked(h, p, nq, d_x, k, d_distances, d_labels);
-        over_passes = h->flat_over_passes;
-        h->defer_now = false;
-        h->flat_over_dst = nullptr;
-        if (rc != GAMMA_HIP_OK) return rc;
-        // (the main stream carries the copy of the overflow word; the side stream, if a replay is pending, the last writes)
-        if (h->replay_pending) {
-            GH_CHECK(h, hipEventRecord(h->ev_rfork, h->stream));
-            GH_CHECK(h, hipStreamWaitEvent(h->side2, h->ev_rfork, 0));
-        }
-        GH_CHECK(h, hipEventRecord(ev, h->replay_pending ? h->side2 : h->stream));
-    }
-    if (hipEventSynchronize(ev) != hipSuccess) return GAMMA_HIP_EDEVICE;
-    if (*over) {   // a survivor list overflowed (adversarial data): the call again without a bound, the plain way
-        SearchLock lk(h);
-        h->ff_redone.fetch_add(over_passes, std::memory_order_relaxed);
-        h->flat_no_bound = true;
-        int rc = replay_join(h);
-        if (rc == GAMMA_HIP_OK) rc = flat_search_device_locked(h, p, nq, d_x, k, d_distances, d_labels);
-        h->flat_no_bound = false;
-        if (rc != GAMMA_HIP_OK) return rc;
-        GH_CHECK(h, hipStreamSynchronize(h->stream));
-    }
-    return GAMMA_HIP_OK;
-}
-
-int gamma_hip_flat_search(gamma_hip_index* h, const gamma_hip_search_params* p, int nq, const float* x,
-                          int k, float* distances, int64_t* labels) {
-    if (!h) return GAMMA_HIP_EINVAL;
-    // small unfiltered calls from concurrent client threads share device batches (see gamma_hip_ivfpq_search)
-    // (a narrow store is never combined, whatever gamma_hip_set_flat_narrow_rows says)
-    if (h->combine && p && nq > 0 && nq <= COMB_MAX_NQ && k > 0 && x && distances && labels && h->raw_d > 0 && !h->raw_half && !h->raw_byte && !h->raw_sq8 &&
-        !p->has_range && p->n_range == 0 && p->n_field == 0 && p->n_term == 0)
-        return combined_search(h, p, nq, x, k, distances, labels, /*kind=*/1);
-    return flat_search_host_locked(h, p, nq, x, k, distances, labels);
-}
-
 
 }  // extern "C"

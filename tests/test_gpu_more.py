@@ -177,7 +177,7 @@ def test_flat_parity(metric, d):
             ctx = B.make_ctx(docids_bitmap=bm, range_filters=rf_o, **WIDE)
             D, I = B.flat_search(base, q, k, metric, ctx)
             # calls of up to 64 queries take the whole store as one chunk and the small-batch chains' selection
-            # (gamma_hip_search.cpp, flat_search_device_locked); without it: row chunks + merge.  3: the two-level
+            # (gamma_hip_search_flat.cpp, flat_search_device_locked); without it: row chunks + merge.  3: the two-level
             # selection with three slices only (slices longer than the registers hold)
             res = []
             for mode in (0, 1, 3):
