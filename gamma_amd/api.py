@@ -737,6 +737,13 @@ class GammaHip:
         False (the default): it refuses one.  Independent of set_flat_narrow_rows."""
         self._ck(self.L.gamma_hip_set_ivfflat_narrow_rows(self.h, 1 if on else 0), "set_ivfflat_narrow_rows")
 
+    def ivfflat_scan_stats(self, reset=False):
+        """(calls the small path served, query chunks scanned by the pair kernel, by the fixed-length list-major kernel, by the
+        row-sliced list-major kernel) of ivfflat_search."""
+        out = np.zeros(4, np.int64)
+        self._ck(self.L.gamma_hip_ivfflat_scan_stats(self.h, _p(out, _lib.i64p), 1 if reset else 0), "ivfflat_scan_stats")
+        return tuple(int(v) for v in out)
+
     def set_flat_sq8_rows(self, on=True):
         """True: flat_search serves an sq8 raw store (byte-identical to an fp32 store of the decoded rows); False (the
         default): it refuses one.  Independent of set_flat_narrow_rows."""
@@ -979,6 +986,17 @@ def flat_filter_shape(d):
     if not _lib.load().gamma_hip_flat_filter_shape(int(d), C.byref(dp), C.byref(m)):
         return None
     return int(dp.value), float(m.value)
+
+
+def ivfflat_lm_shape(d):
+    """(kind, slab, qtile) of ivfflat_search's list-major scan for rows of d floats: kind 0 = none (one workgroup per (query,
+    probe) pair always), 1 = fixed-length (d in {16, 32, 64, 96, 128}), 2 = row-sliced (the other multiples of 16 up to 4096);
+    slab = the elements of a row held in registers at a time, qtile = the queries per tile (both 0 with kind 0).  No device call."""
+    kind, slab, qtile = C.c_int(0), C.c_int(0), C.c_int(0)
+    rc = _lib.load().gamma_hip_ivfflat_lm_shape(int(d), C.byref(kind), C.byref(slab), C.byref(qtile))
+    if rc != 0:
+        raise _lib.GammaHipError("ivfflat_lm_shape: %d" % rc)
+    return int(kind.value), int(slab.value), int(qtile.value)
 
 
 def train_ivfpq(x, nlist, M, device=0):

@@ -257,6 +257,21 @@ int gamma_hip_flat_filter_stats(gamma_hip_index* h, int64_t* out3, int reset) {
     return GAMMA_HIP_OK;
 }
 
+int gamma_hip_ivfflat_lm_shape(int d, int* kind, int* slab, int* qtile) {
+    if (!kind || !slab || !qtile) return GAMMA_HIP_EINVAL;
+    gh::ivfflat_lm_shape(d, kind, slab, qtile);
+    return GAMMA_HIP_OK;
+}
+
+int gamma_hip_ivfflat_scan_stats(gamma_hip_index* h, int64_t* out4, int reset) {
+    if (!h || !out4) return GAMMA_HIP_EINVAL;
+    out4[0] = reset ? h->fl_small.exchange(0) : h->fl_small.load();
+    out4[1] = reset ? h->fl_pair.exchange(0) : h->fl_pair.load();
+    out4[2] = reset ? h->fl_lm.exchange(0) : h->fl_lm.load();
+    out4[3] = reset ? h->fl_lms.exchange(0) : h->fl_lms.load();
+    return GAMMA_HIP_OK;
+}
+
 int gamma_hip_set_small_path(gamma_hip_index* h, int on) {
     if (!h) return GAMMA_HIP_EINVAL;
     SearchLock lk(h);

@@ -374,6 +374,9 @@ struct gamma_hip_index {
     int64_t cbf_backoffs = 0, cbf_calls = 0;       // times the handle turned the bf16 filter off; calls that ran it
     // gamma_hip_flat_filter_stats: filter passes launched, (query, row) pairs they scored, passes redone without the bound
     std::atomic<int64_t> ff_passes{0}, ff_pairs{0}, ff_redone{0};
+    // gamma_hip_ivfflat_scan_stats: calls the small path served; query chunks of the chunked path scanned by the pair kernel,
+    // by the fixed-length list-major kernel, by the row-sliced one
+    std::atomic<int64_t> fl_small{0}, fl_pair{0}, fl_lm{0}, fl_lms{0};
     bool small_path = true;    // gamma_hip_set_small_path
     bool flat_narrow_rows = false;   // gamma_hip_set_flat_narrow_rows: flat search serves a float16 / uint8 / int8 raw store
     bool ivfflat_narrow_rows = false;   // gamma_hip_set_ivfflat_narrow_rows: the same for the IVFFLAT search

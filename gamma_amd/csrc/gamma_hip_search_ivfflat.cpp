@@ -100,8 +100,10 @@ int ivfflat_search_device_locked(H* h, const gamma_hip_search_params* p, int nq,
         static const bool off = getenv("GAMMA_HIP_NO_SMALL_PATH") != nullptr;
         if (!off && h->small_path && nq <= 512 && P <= 128 && k <= 1024 && !h->profile &&
             !fc.d_qf && !h->d_list_mask && nlist <= 16384 && (int64_t)nq * P < 2 * (int64_t)nlist &&
-            (int64_t)P * std::max(1, h->max_list_len) <= (1 << 22))
+            (int64_t)P * std::max(1, h->max_list_len) <= (1 << 22)) {
+            h->fl_small.fetch_add(1, std::memory_order_relaxed);
             return ivfflat_small(h, &pp, fc, rows, nq, d_x, k, d_distances, d_labels);
+        }
     }
     ListCompaction restore(h);
     GH_TRY(compact_lists_for_call(h, &fc, (int64_t)nq * P * (h->ntotal / std::max(1, nlist)), true, &restore));
@@ -127,14 +129,19 @@ int ivfflat_search_device_locked(H* h, const gamma_hip_search_params* p, int nq,
         {
             StageScope t(h, GAMMA_HIP_STAGE_SCAN);
             // enough (query, probe) pairs that lists are shared: list-major (ivfflat.hip), a list's rows are read once
-            // for all the queries probing it; else one workgroup per pair
+            // for all the queries probing it (d in {16, 32, 64, 96, 128}) or once per tile of them (the row-sliced kernel: every
+            // other d % 16 == 0 up to 4096); else one workgroup per pair
             static const bool no_lm = getenv("GAMMA_HIP_NO_IVFFLAT_LM") != nullptr;
-            if (!no_lm && gh::ivfflat_lm_supported(h->d) && (int64_t)nc * P >= 2 * (int64_t)nlist && !h->d_list_mask) {
+            int lm_kind = 0, lm_slab = 0, lm_qtile = 0;
+            gh::ivfflat_lm_shape(h->d, &lm_kind, &lm_slab, &lm_qtile);
+            if (!no_lm && lm_kind != 0 && (int64_t)nc * P >= 2 * (int64_t)nlist && !h->d_list_mask) {
+                (lm_kind == 1 ? h->fl_lm : h->fl_lms).fetch_add(1, std::memory_order_relaxed);
                 GH_CHECK(h, h->w_lm_units.ensure(gh::ivfflat_lm_scratch_bytes(nc, P, nlist)));
                 gh::launch_ivfflat_lm(s, l2, xq, nc, h->d, P, h->w_probe.as<int>(), h->w_pair_off.as<int>(), h->d_list_off,
                                       h->d_list_len, nlist, h->d_ids, rows, h->nraw, q_stride, h->w_dist.as<float>(),
                                       fc.d_tab, need_filter, p->min_score, p->max_score, h->w_lm_units.p);
             } else {
+                h->fl_pair.fetch_add(1, std::memory_order_relaxed);
                 gh::launch_ivfflat_scan(s, l2, xq, nc, h->d, P, h->w_pair_off.as<int>(), h->w_pair_base.as<int64_t>(),
                                         h->d_ids, rows, h->nraw, q_stride, h->w_dist.as<float>(), fc.d_tab, need_filter,
                                         p->min_score, p->max_score);

@@ -7,7 +7,8 @@
 // The (query, probe) pairs of a list come from an inverse index built per call (count / scan / fill: a counting
 // sort of the coarse assignment by list).  Distances are the exact fvec_L2sqr / fvec_inner_product of the
 // reference (eight AVX lane accumulators: four per thread of the pair, packed fp32), written to the same slab
-// positions as the pair kernel, so everything downstream is unchanged.  d in {16, 32, 64, 96, 128}.
+// positions as the pair kernel, so everything downstream is unchanged.  d in {16, 32, 64, 96, 128}: k_ivfflat_lm, the whole row
+// in registers; every other d % 16 == 0 up to 4096: k_ivfflat_lms below, the row walked in slabs.
 // Row: the raw store's element type (float; uint16_t = IEEE binary16, uint8_t, int8_t with gamma_hip_set_ivfflat_narrow_rows).  A
 // narrow row is widened -- exactly -- as the pair of threads loads it (row_pair_load, flat_rows_dev.h) and is fp32 from then on.
 #include <hip/hip_runtime.h>
@@ -26,6 +27,8 @@ namespace {
 constexpr int FL_QT = 32;   // queries per LDS tile
 constexpr int FL_UT = 1;    // tiles per work unit (4: no gain at 16384 queries, -12 % at 4096: fewer, longer units)
 constexpr int FL_UQ = FL_QT * FL_UT;
+constexpr int FS_QT = 16;      // row-sliced kernel: queries per LDS tile = per work unit (their partial sums stay in registers)
+constexpr int FS_SLAB = 128;   // row-sliced kernel: elements of a row a pair of threads holds at a time
 }  // namespace
 
 __global__ __launch_bounds__(256) void k_inv_count(const int* __restrict__ probe, int npairs, int nlist,
@@ -37,9 +40,9 @@ __global__ __launch_bounds__(256) void k_inv_count(const int* __restrict__ probe
 }
 // start[l] = exclusive prefix of cnt; cur[l] = 0; ustart[l] = exclusive prefix of the list's work units
 // (query tiles x 128-row chunks), ustart[nlist] = their total.  One block.
-__global__ __launch_bounds__(1024) void k_inv_scan(const int* __restrict__ cnt, const int* __restrict__ list_len, int nlist,
-                                                   int* __restrict__ start, int* __restrict__ cur,
-                                                   int* __restrict__ ustart) {
+template <int UQ>
+__device__ __forceinline__ void inv_scan_body(const int* __restrict__ cnt, const int* __restrict__ list_len, int nlist,
+                                              int* __restrict__ start, int* __restrict__ cur, int* __restrict__ ustart) {
     __shared__ int s_w[2][16];
     __shared__ int s_run[2];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -48,7 +51,7 @@ __global__ __launch_bounds__(1024) void k_inv_scan(const int* __restrict__ cnt, 
     for (int b = 0; b < nlist; b += 1024) {
         const int i = b + tid;
         const int v = i < nlist ? cnt[i] : 0;
-        const int u = (i < nlist && v > 0) ? ((v + FL_UQ - 1) / FL_UQ) * ((list_len[i] + 127) / 128) : 0;
+        const int u = (i < nlist && v > 0) ? ((v + UQ - 1) / UQ) * ((list_len[i] + 127) / 128) : 0;
         int incl = v, uincl = u;
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {
@@ -81,6 +84,17 @@ __global__ __launch_bounds__(1024) void k_inv_scan(const int* __restrict__ cnt, 
         __syncthreads();
     }
     if (tid == 0) ustart[nlist] = s_run[1];
+}
+__global__ __launch_bounds__(1024) void k_inv_scan(const int* __restrict__ cnt, const int* __restrict__ list_len, int nlist,
+                                                   int* __restrict__ start, int* __restrict__ cur,
+                                                   int* __restrict__ ustart) {
+    inv_scan_body<FL_UQ>(cnt, list_len, nlist, start, cur, ustart);
+}
+// the same prefix with the row-sliced kernel's query tile (k_ivfflat_lms below)
+__global__ __launch_bounds__(1024) void k_inv_scan_s(const int* __restrict__ cnt, const int* __restrict__ list_len, int nlist,
+                                                     int* __restrict__ start, int* __restrict__ cur,
+                                                     int* __restrict__ ustart) {
+    inv_scan_body<FS_QT>(cnt, list_len, nlist, start, cur, ustart);
 }
 __global__ __launch_bounds__(256) void k_inv_fill(const int* __restrict__ probe, int npairs, int nlist,
                                                   const int* __restrict__ list_len, const int* __restrict__ start,
@@ -184,7 +198,138 @@ __global__ __launch_bounds__(256) void k_ivfflat_lm(const float* __restrict__ x,
     }
 }
 
+// ---- rows of any d % 16 == 0 up to 4096: the row-sliced list-major kernel ------------------------------------------------
+// A row of d floats does not fit in the registers of two threads (768 floats: 384 each), so the pair of threads walks it in
+// slabs of FS_SLAB = 128 elements -- 64 registers each, the load of k_ivfflat_lm<.., 128> -- and the last d % 128 elements in
+// pieces of 64 / 32 / 16 (every type keeps its 16-byte loads: d % 16 == 0).  What crosses a slab is the partial sums: the
+// eight AVX lane accumulators of every query of the tile, four per thread as two packed pairs, FS_QT x 2 f32x2 = 64 registers
+// at FS_QT = 16.  So a work unit is (list, 128-row chunk, ONE tile of 16 of the queries probing the list) and a row is read
+// once per tile, ceil(n / 16) times for n probing queries (k_ivfflat_lm: once; the pair kernel: n times).  Per slab the
+// tile's query elements are staged in LDS (16 x 128 floats, 8 KB) and every query's fma chain runs on from where the slab
+// before left it: each lane accumulator is ONE chain over its elements in ascending order, exactly fvec_L2sqr /
+// fvec_inner_product's, and the epilogue is k_ivfflat_lm's.  The slab loop is a run-time loop over d; the query loop is
+// unrolled so that the accumulators are registers (a branch per query on the wave-uniform tile length).
+template <bool L2, class Row, int LEN>
+__device__ __forceinline__ void lms_piece(const Row* __restrict__ rowp, const float* __restrict__ x, int d, int e0, int half,
+                                          int tid, int nqt, const int* s_q, float4* s_x, f32x2 (&acc)[FS_QT][2]) {
+    f32x2 yr[LEN / 4];
+    row_pair_load<Row, LEN>(rowp + e0, half, yr);   // in flight while the tile's queries are staged
+    __syncthreads();   // the previous piece has been consumed (first piece: s_q is written)
+    for (int e = tid; e < nqt * (LEN / 4); e += 256) {
+        const int qi = e / (LEN / 4), c = e - qi * (LEN / 4);
+        s_x[e] = reinterpret_cast<const float4*>(x + (int64_t)s_q[qi] * d + e0)[c];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int qi = 0; qi < FS_QT; qi++) {
+        if (qi < nqt) {
+            const float4* xq = s_x + qi * (LEN / 4) + half;
+#pragma unroll
+            for (int i0 = 0; i0 < LEN / 8; i0 += 8) {
+                float4 xa[8];
+#pragma unroll
+                for (int u = 0; u < 8; u++) xa[u] = (i0 + u) < LEN / 8 ? xq[2 * (i0 + u)] : float4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int u = 0; u < 8; u++) {
+                    const int i = i0 + u;
+                    if (i < LEN / 8) {
+                        const f32x2 xv[2] = {f32x2{xa[u].x, xa[u].y}, f32x2{xa[u].z, xa[u].w}};
+#pragma unroll
+                        for (int k = 0; k < 2; k++) {
+                            if (L2) {
+                                const f32x2 t = xv[k] - yr[2 * i + k];
+                                acc[qi][k] = __builtin_elementwise_fma(t, t, acc[qi][k]);
+                            } else {
+                                acc[qi][k] = __builtin_elementwise_fma(xv[k], yr[2 * i + k], acc[qi][k]);
+                            }
+                        }
+                    }
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+    }
+}
+
+template <bool L2, class Row>
+__global__ __launch_bounds__(256) void k_ivfflat_lms(const float* __restrict__ x, int d, int P, const int* __restrict__ pair_off,
+                                                     const int64_t* __restrict__ list_off,
+                                                     const int* __restrict__ list_len, const int64_t* __restrict__ ids,
+                                                     const Row* __restrict__ raw, int64_t nraw,
+                                                     const int* __restrict__ inv_start, const int* __restrict__ inv_cnt,
+                                                     const int* __restrict__ inv, const int* __restrict__ ustart,
+                                                     int nlist, int64_t q_stride,
+                                                     float* __restrict__ out, const FilterDesc* __restrict__ ftab,
+                                                     int need_filter, float min_score, float max_score) {
+    __shared__ float4 s_x[FS_QT * FS_SLAB / 4];
+    __shared__ int s_q[FS_QT];
+    __shared__ int s_off[FS_QT];
+    const int tid = threadIdx.x, half = tid & 1;
+    const float sentinel = L2 ? INFINITY : -INFINITY;
+    const int nunits = ustart[nlist];
+    for (int u = blockIdx.x; u < nunits; u += gridDim.x) {
+        int lo = 0, hi = nlist - 1;
+        while (lo < hi) {   // last list with ustart[l] <= u
+            const int mid = (lo + hi + 1) >> 1;
+            if (ustart[mid] <= u) lo = mid; else hi = mid - 1;
+        }
+        const int l = lo;
+        const int len = list_len[l], n = inv_cnt[l];
+        const int chunks = (len + 127) / 128, rel = u - ustart[l];
+        const int tq0 = (rel / chunks) * FS_QT, nqt = min(FS_QT, n - tq0), r0 = (rel - (rel / chunks) * chunks) * 128;
+        const int64_t base = list_off[l];
+        const int j = r0 + (tid >> 1);
+        const bool inrow = j < len;
+        int64_t id = -1;
+        if (inrow) id = ids[base + j];
+        const int64_t vid = id & 0x7fffffffffffffffLL;
+        bool live = inrow && id >= 0 && vid < nraw;   // id < 0: bit 63, superseded by an Update
+        if (need_filter && live) live = is_valid_doc(ftab[0], vid);
+        const Row* rowp = raw + (live ? vid : 0) * d;
+        __syncthreads();   // the previous unit has stored its distances: s_q, s_off are free
+        if (tid < nqt) {
+            const int pr = inv[inv_start[l] + tq0 + tid];
+            const int q = pr / P;
+            s_q[tid] = q;
+            s_off[tid] = pair_off[(int64_t)q * (P + 1) + (pr - q * P)];
+        }
+        f32x2 acc[FS_QT][2];
+#pragma unroll
+        for (int qi = 0; qi < FS_QT; qi++) acc[qi][0] = acc[qi][1] = f32x2{0.f, 0.f};
+        int e0 = 0;
+        for (; e0 + FS_SLAB <= d; e0 += FS_SLAB) lms_piece<L2, Row, FS_SLAB>(rowp, x, d, e0, half, tid, nqt, s_q, s_x, acc);
+        if (d - e0 >= 64) {
+            lms_piece<L2, Row, 64>(rowp, x, d, e0, half, tid, nqt, s_q, s_x, acc);
+            e0 += 64;
+        }
+        if (d - e0 >= 32) {
+            lms_piece<L2, Row, 32>(rowp, x, d, e0, half, tid, nqt, s_q, s_x, acc);
+            e0 += 32;
+        }
+        if (d - e0 >= 16) lms_piece<L2, Row, 16>(rowp, x, d, e0, half, tid, nqt, s_q, s_x, acc);
+#pragma unroll
+        for (int qi = 0; qi < FS_QT; qi++) {
+            if (qi < nqt) {
+                // even thread: AVX lanes 0..3, odd thread: lanes 4..7;  s[l] = acc[l+4] + acc[l]
+                float s0, s1, s2, s3;
+                add_xor1_x4(acc[qi][0].x, acc[qi][0].y, acc[qi][1].x, acc[qi][1].y, s0, s1, s2, s3);
+                float dis = hsum4(s0, s1, s2, s3);
+                if (!live || !(dis <= max_score && dis >= min_score)) dis = sentinel;
+                if (inrow && half == 0) out[(int64_t)s_q[qi] * q_stride + s_off[qi] + j] = dis;
+            }
+        }
+    }
+}
+
 bool ivfflat_lm_supported(int d) { return d == 16 || d == 32 || d == 64 || d == 96 || d == 128; }
+
+int ivfflat_lm_shape(int d, int* kind, int* slab, int* qtile) {
+    const int k = ivfflat_lm_supported(d) ? 1 : (d >= 16 && d <= 4096 && d % 16 == 0) ? 2 : 0;
+    *kind = k;
+    *slab = k == 1 ? d : k == 2 ? FS_SLAB : 0;
+    *qtile = k == 1 ? FL_QT : k == 2 ? FS_QT : 0;
+    return k;
+}
 
 // scratch: inv [nq * P] ints, then cnt | start | cur [nlist] ints each
 size_t ivfflat_lm_scratch_bytes(int nq, int P, int nlist) { return ((size_t)nq * P + 4 * (size_t)nlist + 1) * sizeof(int); }
@@ -204,9 +349,20 @@ void launch_ivfflat_lm_t(hipStream_t s, bool l2, const float* x, int nq, int d, 
     const int npairs = nq * P;
     (void)hipMemsetAsync(cnt, 0, (size_t)nlist * sizeof(int), s);
     hipLaunchKernelGGL(k_inv_count, dim3((npairs + 255) / 256), dim3(256), 0, s, probe, npairs, nlist, list_len, cnt);
-    hipLaunchKernelGGL(k_inv_scan, dim3(1), dim3(1024), 0, s, cnt, list_len, nlist, start, cur, ustart);
+    const bool sliced = !ivfflat_lm_supported(d);   // (the caller asked ivfflat_lm_shape: d % 16 == 0, d <= 4096)
+    if (sliced) hipLaunchKernelGGL(k_inv_scan_s, dim3(1), dim3(1024), 0, s, cnt, list_len, nlist, start, cur, ustart);
+    else hipLaunchKernelGGL(k_inv_scan, dim3(1), dim3(1024), 0, s, cnt, list_len, nlist, start, cur, ustart);
     hipLaunchKernelGGL(k_inv_fill, dim3((npairs + 255) / 256), dim3(256), 0, s, probe, npairs, nlist, list_len, start, cur, inv);
     const int grid = 256 * 8;   // persistent: every workgroup walks the unit list with stride gridDim.x
+    if (sliced) {
+        if (l2)
+            hipLaunchKernelGGL((k_ivfflat_lms<true, Row>), dim3(grid), dim3(256), 0, s, x, d, P, pair_off, list_off, list_len, ids,
+                               raw, nraw, start, cnt, inv, ustart, nlist, q_stride, out, ftab, need_filter, min_score, max_score);
+        else
+            hipLaunchKernelGGL((k_ivfflat_lms<false, Row>), dim3(grid), dim3(256), 0, s, x, d, P, pair_off, list_off, list_len, ids,
+                               raw, nraw, start, cnt, inv, ustart, nlist, q_stride, out, ftab, need_filter, min_score, max_score);
+        return;
+    }
 #define GH_FL(LL, DD)                                                                                                   \
     hipLaunchKernelGGL((k_ivfflat_lm<LL, DD, Row>), dim3(grid), dim3(256), 0, s, x, P, pair_off, list_off, list_len, ids, \
                        raw, nraw, start, cnt, inv, ustart, nlist, q_stride, out, ftab, need_filter, min_score, max_score)

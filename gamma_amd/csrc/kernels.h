@@ -346,6 +346,10 @@ void launch_ivfflat_scan(hipStream_t s, bool l2, const float* x, int nq, int d, 
                          float* out, const FilterDesc* ftab, int need_filter, float min_score, float max_score);
 // IVFFLAT, list-major (ivfflat.hip): one workgroup per list, every query probing it run past the list's rows
 bool ivfflat_lm_supported(int d);
+// the list-major form of rows of d floats: *kind 0 = none (the pair kernel), 1 = fixed-length (k_ivfflat_lm: the whole row in
+// registers, d in {16, 32, 64, 96, 128}), 2 = row-sliced (k_ivfflat_lms: every other d % 16 == 0 up to 4096); *slab = the
+// elements of a row a pair of threads holds at a time, *qtile = the queries per LDS tile (both 0 with kind 0).  Returns kind.
+int ivfflat_lm_shape(int d, int* kind, int* slab, int* qtile);
 size_t ivfflat_lm_scratch_bytes(int nq, int P, int nlist);
 void launch_ivfflat_lm(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* probe, const int* pair_off,
                        const int64_t* list_off, const int* list_len, int nlist, const int64_t* ids, const float* raw,

@@ -210,6 +210,20 @@ int gamma_hip_set_flat_narrow_rows(gamma_hip_index* h, int on);
  * _raw_drop, the combining queue and a sparse store keep refusing a narrow store, and an fp32 store is served as before
  * whatever the switch says. */
 int gamma_hip_set_ivfflat_narrow_rows(gamma_hip_index* h, int on);
+/* The list scan of the IVFFLAT search (GammaIVFFlatScanner1::scan_codes, index/impl/gamma_index_ivfflat.h:52-75: one
+ * fvec_L2sqr / fvec_inner_product per entry of a probed list) has a list-major form -- a list's rows are read once per tile
+ * of the queries probing it instead of once per query (csrc/ivfflat.hip, DESIGN.md sections 9 and 22) -- for some row
+ * lengths.  No handle, no device call: *kind = 0 none (d % 16 != 0 or d > 4096: one workgroup per (query, probe) pair
+ * always), 1 = fixed-length (d in {16, 32, 64, 96, 128}: the whole row in registers), 2 = row-sliced (every other multiple of
+ * 16 up to 4096); *slab = the elements of a row held in registers at a time (kind 1: d), *qtile = the queries per tile; both 0
+ * with kind 0.  The gates of a call -- at least 2 nlist (query, probe) pairs, no list mask -- are not part of the answer.
+ * Results are the same bits in every form.  Returns GAMMA_HIP_OK, GAMMA_HIP_EINVAL for a null pointer. */
+int gamma_hip_ivfflat_lm_shape(int d, int* kind, int* slab, int* qtile);
+/* out4 = {IVFFLAT calls served by the small path, query chunks of the chunked path scanned by the pair kernel, by the
+ * fixed-length list-major kernel, by the row-sliced one} since creation or the last reset.  Host-side counters: no
+ * synchronisation, no device read.  The reference has no counterpart (its scanner walks one list for one query:
+ * gamma_index_ivfflat.h:52-75). */
+int gamma_hip_ivfflat_scan_stats(gamma_hip_index* h, int64_t* out4, int reset);
 /* Flat search over a scalar-quantised raw store (gamma_hip_raw_init_sq8); a switch of its own, independent of the two above.
  * on: 0 (default) = gamma_hip_flat_search, _flat_search_device and _flat_search_device_wait refuse an sq8 store with
  * GAMMA_HIP_EUNSUPPORTED, as before and whatever gamma_hip_set_flat_narrow_rows says; 1 = the three serve it: every code is
