@@ -123,7 +123,11 @@ SYMBOLS = {
     "gamma_hip_binivf_search_device": (C.c_int, [C.c_void_p, C.POINTER(SearchParams), C.c_int, C.c_void_p, C.c_int,
                                                  C.c_void_p, C.c_void_p]),
     "gamma_hip_binivf_stats": (C.c_int, [C.c_void_p, i64p, C.c_int]),
-    "gamma_hip_binflat_init": (C.c_int, [C.c_void_p, C.c_int]),
+    "gamma_hip_binivf_set_scan_mode": (C.c_int, [C.c_void_p, C.c_int]),
+    "gamma_hip_binivf_scan_mode": (C.c_int, [C.c_void_p]),
+    "gamma_hip_binivf_scan_shape": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "gamma_hip_binivf_scan_stats": (C.c_int, [C.c_void_p, i64p, C.c_int]),
+    "gamma_hip_binflat_init":(C.c_int, [C.c_void_p, C.c_int]),
     "gamma_hip_binflat_append": (C.c_int, [C.c_void_p, C.c_int64, u8p]),
     "gamma_hip_binflat_count": (C.c_int64, [C.c_void_p]),
     "gamma_hip_binflat_search": (C.c_int, [C.c_void_p, C.POINTER(SearchParams), C.c_int, u8p, C.c_int, f32p, i64p]),

@@ -532,6 +532,21 @@ class GammaHip:
         self._ck(self.L.gamma_hip_binivf_stats(self.h, _p(out, _lib.i64p), 1 if reset else 0), "binivf_stats")
         return int(out[0]), int(out[1])
 
+    def binivf_set_scan_mode(self, mode):
+        """0: one wave per query; 1: a query's scan spread over the device whenever the workspace allows; -1 (default):
+        spread for calls of up to binivf_scan_shape()[1] queries.  The answer is the same in every mode."""
+        self._ck(self.L.gamma_hip_binivf_set_scan_mode(self.h, int(mode)), "binivf_set_scan_mode")
+
+    def binivf_scan_mode(self):
+        return int(self.L.gamma_hip_binivf_scan_mode(self.h))
+
+    def binivf_scan_stats(self, reset=False):
+        """(queries the spread chain answered, their chunks, their candidates, queries that fell back for lack of workspace);
+        counted while profiling is on"""
+        out = np.zeros(4, dtype=np.int64)
+        self._ck(self.L.gamma_hip_binivf_scan_stats(self.h, _p(out, _lib.i64p), 1 if reset else 0), "binivf_scan_stats")
+        return tuple(int(v) for v in out)
+
     # ---- exact Hamming (binary flat) search: faiss:IndexBinaryFlat.cpp / utils/hamming.cpp:230-265, answered as
     #      GammaIVFBinaryScannerL2::scan_codes answers one list holding every code in vid order ----
     def binflat_init(self, nbits):
@@ -997,6 +1012,16 @@ def ivfflat_lm_shape(d):
     if rc != 0:
         raise _lib.GammaHipError("ivfflat_lm_shape: %d" % rc)
     return int(kind.value), int(slab.value), int(qtile.value)
+
+
+def binivf_scan_shape():
+    """(chunk_rows, auto_max_nq) of binivf_search's spread scan: the rows per chunk, and the largest call the automatic scan
+    mode spreads.  No device call."""
+    c, a = C.c_int(0), C.c_int(0)
+    rc = _lib.load().gamma_hip_binivf_scan_shape(C.byref(c), C.byref(a))
+    if rc != 0:
+        raise _lib.GammaHipError("binivf_scan_shape: %d" % rc)
+    return int(c.value), int(a.value)
 
 
 def train_ivfpq(x, nlist, M, device=0):

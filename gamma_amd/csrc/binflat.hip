@@ -20,6 +20,7 @@
 
 #include <algorithm>
 
+#include "bin_dev.h"
 #include "binflat.h"
 #include "filter_dev.h"
 #include "heap_dev.h"
@@ -92,12 +93,6 @@ __device__ __forceinline__ void bf_dist(const uint32_t* qw, int nwq, const uint8
     }
 }
 
-__device__ __forceinline__ unsigned bf_wave_sum(unsigned v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 inline size_t bf_align16(size_t x) { return (x + 15) & ~(size_t)15; }
 inline size_t bf_hist_lds(int qt, int cs) {
     const int nw = (cs + 3) >> 2, nwq = (nw + 3) & ~3;
@@ -146,42 +141,8 @@ __global__ __launch_bounds__(64) void k_binflat_bounds(const uint32_t* __restric
     uint32_t* cum = reinterpret_cast<uint32_t*>(smem);
     const int lane = threadIdx.x;
     for (int q = blockIdx.x; q < nq; q += gridDim.x) {
-        __syncthreads();
-        for (int b = lane; b < nb; b += 64) cum[b] = 0u;
-        __syncthreads();
-        int B = kBinFlatNoBound;    // the k-th smallest valid distance of the rows so far
-        long long cnt_le = 0;       // valid rows so far with dis <= B (all of them while there is no bound)
-        uint32_t run = 0;           // candidates of the chunks so far
-        for (int64_t c = 0; c < nch; c++) {
-            const uint32_t* hc = hist + ((int64_t)q * nch + c) * nb;
-            const int lim = B == kBinFlatNoBound ? nb : B + 1;
-            unsigned s_lt = 0, s_le = 0;
-            for (int b = lane; b < lim; b += 64) {
-                const uint32_t v = hc[b];
-                cum[b] += v;
-                s_le += v;
-                s_lt += b < B ? v : 0u;
-            }
-            s_lt = bf_wave_sum(s_lt);
-            s_le = bf_wave_sum(s_le);
-            if (lane == 0) {
-                bound[(int64_t)q * nch + c] = B;
-                off[(int64_t)q * nch + c] = run;
-            }
-            run += s_lt;
-            cnt_le += s_le;
-            __syncthreads();
-            if (B == kBinFlatNoBound && cnt_le >= k) B = nb - 1;
-            if (B != kBinFlatNoBound) {
-                // B too large while k rows lie strictly below it
-                for (;;) {
-                    const uint32_t at = hs_u(cum[B]);
-                    if (B == 0 || cnt_le - (long long)at < k) break;
-                    cnt_le -= at;
-                    B--;
-                }
-            }
-        }
+        const uint32_t run = bin_bound_walk(hist + (int64_t)q * nch * nb, nch, nb, k, cum, bound + (int64_t)q * nch,
+                                            off + (int64_t)q * nch);
         if (lane == 0) total[q] = run;
     }
 }
@@ -270,57 +231,9 @@ __global__ __launch_bounds__(64) void k_binflat_replay(const uint2* __restrict__
     extern __shared__ __align__(16) char smem[];
     const int lane = threadIdx.x;
     uint2* hK = reinterpret_cast<uint2*>(smem);
-    const bool reg_heap = k <= 15;
-    const bool par_heap = !reg_heap && k <= kParHeapMaxK;
     for (int q = blockIdx.x; q < nq; q += gridDim.x) {
-        __syncthreads();
-        heap_fill(hK, k, lane, 64);   // heap_heapify<CMax<int32_t, idx_t>>
-        __syncthreads();
-        RegHeap<1> rh;
-        rh.fill();
-        float top = kHeapFltMax;
-        unsigned long long nadm = 0;
         const int64_t tot = total ? (int64_t)total[q] : 0;
-        const uint2* cq = cand + (total ? base[q] : 0);
-        for (int64_t j0 = 0; j0 < tot; j0 += 64) {
-            const int64_t j = j0 + lane;
-            uint2 e = make_uint2(0u, 0u);
-            if (j < tot) e = cq[j];
-            const float dv = j < tot ? (float)e.y : INFINITY;
-            // `if (dis < simi[0]) { heap_pop; heap_push }`, the admitted lanes in stream order
-            unsigned long long m = __ballot(top > dv);
-            while (m) {
-                const int sl = (int)__ffsll((long long)m) - 1;
-                const float val = hw_readlane_f(dv, sl);
-                const unsigned pay = (unsigned)hw_readlane_i((int)e.x, sl);
-                if (reg_heap) {
-                    rh.pop(k);
-                    rh.push(k, val, pay);
-                    top = rh.top();
-                } else if (par_heap) {
-                    const float root = par_heap_pop(hK, k);
-                    top = par_heap_push(hK, k, val, pay) ? val : root;
-                } else {
-                    heap_pop_seq(hK, k);
-                    heap_push_seq(hK, k, val, pay);
-                    top = hs_f(hK[1].x);
-                }
-                nadm++;
-                const unsigned long long above = sl >= 63 ? 0ull : (~0ull << (sl + 1));
-                m = __ballot(top > dv) & above;
-            }
-        }
-        // heap_reorder
-        if (reg_heap) {
-            const int real = rh.reorder_pops(k);
-            rh.dump(hK, k);
-            __syncthreads();
-            heap_reorder_tail(hK, k, real);
-        } else {
-            __syncthreads();
-            par_heap_reorder(hK, k);
-        }
-        __syncthreads();
+        const unsigned long long nadm = bin_replay_segment(cand + (total ? base[q] : 0), tot, k, hK);
         for (int i = lane; i < k; i += 64) {
             const uint2 e = hK[1 + i];
             const bool empty = e.y == 0xffffffffu;

@@ -19,53 +19,12 @@
 
 #include <algorithm>
 
+#include "bin_dev.h"
 #include "binivf.h"
 #include "filter_dev.h"
 #include "heap_dev.h"
 
 namespace gh {
-
-namespace {
-__device__ __forceinline__ size_t bin_align16(size_t x) { return (x + 15) & ~(size_t)15; }
-
-// word w of a code: bytes 4w .. 4w + 3, zero beyond cs (the query's padding is zero too: XOR 0)
-__device__ __forceinline__ uint32_t bin_word_bytes(const uint8_t* p, int w, int cs) {
-    uint32_t v = 0;
-#pragma unroll
-    for (int b = 0; b < 4; b++) {
-        const int i = 4 * w + b;
-        if (i < cs) v |= (uint32_t)p[i] << (8 * b);
-    }
-    return v;
-}
-
-// popcount(q ^ c) over a code of cs bytes; q: the query's nw words in LDS (same address on every lane: a broadcast).
-// AL: cs % 4 == 0 (rows are dword aligned); 16-byte loads when cs % 16 == 0.
-template <bool AL>
-__device__ __forceinline__ int bin_hamming(const uint32_t* q, const uint8_t* c, int cs, int nw) {
-    int s = 0;
-    if (AL) {
-        if ((cs & 15) == 0) {
-            const uint4* c4 = reinterpret_cast<const uint4*>(c);
-            for (int i = 0; i < (nw >> 2); i++) {
-                const uint4 v = c4[i];
-                s += __popc(v.x ^ q[4 * i]) + __popc(v.y ^ q[4 * i + 1]) + __popc(v.z ^ q[4 * i + 2]) +
-                     __popc(v.w ^ q[4 * i + 3]);
-            }
-        } else {
-            const uint32_t* c32 = reinterpret_cast<const uint32_t*>(c);
-            for (int w = 0; w < nw; w++) s += __popc(c32[w] ^ q[w]);
-        }
-    } else {
-        for (int w = 0; w < nw; w++) s += __popc(bin_word_bytes(c, w, cs) ^ q[w]);
-    }
-    return s;
-}
-
-__device__ __forceinline__ void bin_load_query(const uint8_t* xq, int cs, int nw, uint32_t* qw) {
-    for (int w = (int)threadIdx.x; w < nw; w += 64) qw[w] = bin_word_bytes(xq, w, cs);
-}
-}  // namespace
 
 // one wave per query (grid-stride); the centroid codes in LDS when cc_lds
 template <bool AL>

@@ -163,7 +163,7 @@ int gamma_hip_destroy(gamma_hip_index* h) {
                       &h->w_codes_tmp, &h->w_qperm, &h->w_qbins, &h->w_scnt, &h->w_sflag, &h->w_surv, &h->w_pair_base,
                       &h->w_pair_ip, &h->w_flat_cand, &h->w_flat_meta, &h->w_full_cdis,
                       &h->w_full_probe, &h->w_ftab, &h->w_qfil, &h->w_tieflag, &h->w_tcut, &h->w_tlist, &h->w_lm_units, &h->w_lm_cnt, &h->w_fbits, &h->w_cmp_codes, &h->w_cmp_ids, &h->w_cmp_len, &h->w_cmp_sums, &h->w_fD, &h->w_fI, &h->w_fx, &h->w_fslab, &h->w_flog, &h->w_mr_vals, &h->w_mr_ids, &h->w_mr_meta,
-                      &h->we_mat, &h->we_cdis, &h->we_x, &h->we_assign, &h->we_codes, &h->we_stage, &h->w_xrot, &h->we_xrot, &h->w_bf_hist, &h->w_bf_meta, &h->w_bf_cand};
+                      &h->we_mat, &h->we_cdis, &h->we_x, &h->we_assign, &h->we_codes, &h->we_stage, &h->w_xrot, &h->we_xrot, &h->w_bf_hist, &h->w_bf_meta, &h->w_bf_cand, &h->w_bs_hist, &h->w_bs_meta, &h->w_bs_cand};
     for (DevBuf* b : bufs) b->release();
     (void)hipStreamDestroy(h->stream);
     (void)hipStreamDestroy(h->wstream);

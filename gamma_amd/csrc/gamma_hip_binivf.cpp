@@ -38,7 +38,39 @@ int bin_search_device_locked(H* h, const gamma_hip_search_params* p, int nq, con
         StageScope t(h, GAMMA_HIP_STAGE_COARSE);
         gh::launch_bin_coarse(s, d_x, nq, xs, h->d_bin_cc, h->nlist, h->code_size, P, h->w_probe.as<int>(), nullptr);
     }
-    {
+    // one wave per query (k_bin_scan), or the query's scan spread over the device (binivf_spread.hip): the same answer.
+    // The chain's workspaces are sized from the longest list of the version this call reads (max_list_len is set where
+    // the version is published), so nothing comes back from the device before the launches.
+    static const bool no_spread = getenv("GAMMA_HIP_NO_BIN_SPREAD") != nullptr;
+    const int mode = no_spread ? 0 : h->bin_scan_mode;
+    bool spread = mode == 1 || (mode == -1 && nq <= gh::kBinSpreadAutoMaxNq);
+    int maxch = 0;
+    int64_t stride = 0;
+    size_t hist_b = 0, meta_b = 0, cand_b = 0;
+    if (spread) {
+        gh::bin_spread_bounds(P, h->nlist, h->max_list_len, &maxch, &stride);
+        hist_b = (size_t)nq * maxch * ((size_t)h->code_size * 8 + 1) * sizeof(uint32_t);
+        meta_b = gh::bin_spread_meta_bytes(nq, maxch);
+        cand_b = (size_t)nq * (size_t)stride * sizeof(uint2);
+        if (nq > gh::kBinSpreadMaxNq || maxch > 65535 * 32 || hist_b + meta_b + cand_b > h->dist_budget_bytes / 2) {
+            spread = false;   // never wrong, only slower
+            if (h->profile) h->bin_sp_fallback += nq;
+        }
+    }
+    if (spread) {
+        GH_CHECK(h, h->w_bs_hist.ensure(hist_b));
+        GH_CHECK(h, h->w_bs_meta.ensure(meta_b));
+        GH_CHECK(h, h->w_bs_cand.ensure(cand_b));
+        const int stages[3] = {GAMMA_HIP_STAGE_TABLES, GAMMA_HIP_STAGE_SCAN, GAMMA_HIP_STAGE_SELECT};
+        for (int st = 0; st < 3; st++) {   // chunk table + histograms + bounds | collect | replay
+            StageScope t(h, stages[st]);
+            gh::launch_bin_spread(s, d_x, nq, xs, h->code_size, h->w_probe.as<int>(), P, h->d_list_off, h->d_list_len,
+                                  h->d_codes, h->d_ids, fc.d_tab, need_filter, p->min_score, p->max_score, k, maxch, stride,
+                                  h->w_bs_hist.as<uint32_t>(), h->w_bs_meta.p, h->w_bs_cand.as<uint2>(), d_distances,
+                                  d_labels, h->profile ? h->d_bin_stats : nullptr,
+                                  h->profile ? h->d_bin_stats + 2 : nullptr, st + 1);
+        }
+    } else {
         StageScope t(h, GAMMA_HIP_STAGE_SCAN);
         gh::launch_bin_scan(s, d_x, nq, xs, h->code_size, h->w_probe.as<int>(), P, h->d_list_off, h->d_list_len, h->d_codes,
                             h->d_ids, fc.d_tab, need_filter, p->min_score, p->max_score, k, d_distances, d_labels,
@@ -184,6 +216,48 @@ int gamma_hip_binivf_stats(gamma_hip_index* h, int64_t* out2, int reset) {
     if (reset) {
         GH_CHECK(h, hipMemsetAsync(h->d_bin_stats, 0, sizeof(v), h->stream));
         GH_CHECK(h, hipStreamSynchronize(h->stream));
+    }
+    return GAMMA_HIP_OK;
+}
+
+// which scan answers a search (both give scan_codes' answer, gamma_index_binary_ivf.cc:333-448): 0 k_bin_scan, one wave
+// per query; 1 the spread chain whenever its workspace fits; -1 the chain for calls of up to auto_max_nq queries
+int gamma_hip_binivf_set_scan_mode(gamma_hip_index* h, int mode) {
+    if (!h) return GAMMA_HIP_EINVAL;
+    SearchLock lk(h);
+    if (!h->ivf_init || !h->binivf) return fail(h, GAMMA_HIP_EINVAL, "binivf not initialised");
+    if (mode < -1 || mode > 1) return fail(h, GAMMA_HIP_EINVAL, "binivf scan mode: -1, 0 or 1");
+    h->bin_scan_mode = mode;
+    return GAMMA_HIP_OK;
+}
+
+int gamma_hip_binivf_scan_mode(const gamma_hip_index* h) {
+    if (!h || !h->ivf_init || !h->binivf) return GAMMA_HIP_EINVAL;
+    return h->bin_scan_mode;
+}
+
+int gamma_hip_binivf_scan_shape(int* chunk_rows, int* auto_max_nq) {
+    if (chunk_rows) *chunk_rows = gh::kBinSpreadChunk;
+    if (auto_max_nq) *auto_max_nq = gh::kBinSpreadAutoMaxNq;
+    return GAMMA_HIP_OK;
+}
+
+// {queries the spread chain answered, their chunks, their candidates, queries that fell back to k_bin_scan for lack of
+// workspace} of the searches made while profiling was on, since the last reset
+int gamma_hip_binivf_scan_stats(gamma_hip_index* h, int64_t* out4, int reset) {
+    if (!h || !out4) return GAMMA_HIP_EINVAL;
+    SearchLock lk(h);
+    if (!h->ivf_init || !h->binivf) return fail(h, GAMMA_HIP_EINVAL, "binivf not initialised");
+    GH_CHECK(h, hipSetDevice(h->device));
+    unsigned long long v[3] = {0, 0, 0};
+    GH_CHECK(h, hipMemcpyAsync(v, h->d_bin_stats + 2, sizeof(v), hipMemcpyDeviceToHost, h->stream));
+    GH_CHECK(h, hipStreamSynchronize(h->stream));
+    for (int i = 0; i < 3; i++) out4[i] = (int64_t)v[i];
+    out4[3] = h->bin_sp_fallback;
+    if (reset) {
+        GH_CHECK(h, hipMemsetAsync(h->d_bin_stats + 2, 0, sizeof(v), h->stream));
+        GH_CHECK(h, hipStreamSynchronize(h->stream));
+        h->bin_sp_fallback = 0;
     }
     return GAMMA_HIP_OK;
 }

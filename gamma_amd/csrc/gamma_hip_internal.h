@@ -339,7 +339,7 @@ struct gamma_hip_index {
     DevBuf w_mat, w_coarse_dis, w_probe, w_xn, w_st2, w_pair_off, w_qtotal, w_dist, w_cand_dis,
             w_cand_pos, w_cand_ids, w_exact, w_selv, w_selp, w_x, w_outd, w_outl, w_stage, w_shard_cut, w_filter,
             w_m_dis, w_m_ids, w_part_v, w_part_i, w_assign, w_codes_tmp, w_qperm, w_qbins, w_scnt, w_sflag, w_surv, w_pair_base, w_q8, w_q8meta, w_q8cand, w_q8int,
-            w_pair_ip, w_flat_cand, w_flat_meta, w_full_cdis, w_full_probe, w_ftab, w_qfil, w_tieflag, w_tcut, w_tlist, w_textra, w_fq, w_fraw, w_frcnt, w_lm_units, w_lm_cnt, w_fbits, w_cmp_codes, w_cmp_ids, w_cmp_len, w_cmp_sums, w_fD, w_fI, w_fx, w_fslab, w_flog, w_mr_vals, w_mr_ids, w_mr_meta, w_xrot, w_bf_hist, w_bf_meta, w_bf_cand,
+            w_pair_ip, w_flat_cand, w_flat_meta, w_full_cdis, w_full_probe, w_ftab, w_qfil, w_tieflag, w_tcut, w_tlist, w_textra, w_fq, w_fraw, w_frcnt, w_lm_units, w_lm_cnt, w_fbits, w_cmp_codes, w_cmp_ids, w_cmp_len, w_cmp_sums, w_fD, w_fI, w_fx, w_fslab, w_flog, w_mr_vals, w_mr_ids, w_mr_meta, w_xrot, w_bf_hist, w_bf_meta, w_bf_cand, w_bs_hist, w_bs_meta, w_bs_cand,
             we_mat, we_cdis, we_x, we_assign, we_codes, we_stage, we_chk, we_xrot;   // writer side (encode, bitmap_set): never shared with a search
     unsigned long long* d_scan_codes = nullptr;
     size_t dist_budget_bytes = (size_t)8 << 30;   // per-chunk ADC distance buffer (288 GB of HBM per GPU)
@@ -397,7 +397,11 @@ struct gamma_hip_index {
     // d = nbits; the centroid codes, the search's {queries, heap admissions} counters (gamma_hip_binivf_stats)
     bool binivf = false;
     uint8_t* d_bin_cc = nullptr;
-    unsigned long long* d_bin_stats = nullptr;
+    unsigned long long* d_bin_stats = nullptr;   // [5]: + the spread scan's {queries, chunks, candidates}
+    // gamma_hip_binivf_set_scan_mode: 0 one wave per query, 1 spread (binivf_spread.hip) whenever the workspace allows,
+    // -1 spread for calls of up to kBinSpreadAutoMaxNq queries; the queries that fell back for lack of workspace
+    int bin_scan_mode = -1;
+    int64_t bin_sp_fallback = 0;
     // gamma_hip_binflat_init (gamma_hip_binflat.cpp): every code in vid order for the exact Hamming search, rows of bf_cs
     // bytes; bf_count is published after the rows it counts are in place; {queries, candidates, heap admissions} counters
     // and the number of query sub-batches (gamma_hip_binflat_stats); host images of a call's candidate totals / segment bases

@@ -1580,8 +1580,8 @@ int gamma_hip_binivf_init(gamma_hip_index* h, int nbits, int nlist, int bucket_i
     GH_TRY(ivf_init_locked(h, nbits, nlist, nbits / 8, GAMMA_HIP_METRIC_L2, bucket_init_size, bucket_max_size, true, true));
     h->binivf = true;
     GH_CHECK(h, hipMalloc((void**)&h->d_bin_cc, (size_t)nlist * h->code_size));
-    GH_CHECK(h, hipMalloc((void**)&h->d_bin_stats, 2 * sizeof(unsigned long long)));
-    GH_CHECK(h, hipMemset(h->d_bin_stats, 0, 2 * sizeof(unsigned long long)));
+    GH_CHECK(h, hipMalloc((void**)&h->d_bin_stats, 5 * sizeof(unsigned long long)));
+    GH_CHECK(h, hipMemset(h->d_bin_stats, 0, 5 * sizeof(unsigned long long)));
     return GAMMA_HIP_OK;
 }
 

@@ -618,6 +618,26 @@ int gamma_hip_binivf_search_device(gamma_hip_index* h, const gamma_hip_search_pa
 /* {queries searched, heap admissions of their scans} since the last reset (the serial part of a query's scan); counted
  * only by searches made while gamma_hip_profile_enable is on */
 int gamma_hip_binivf_stats(gamma_hip_index* h, int64_t* out2, int reset);
+/* Which kernels run GammaIVFBinaryScannerL2::scan_codes (gamma_index_binary_ivf.cc:333-448) for a search; the answer --
+ * labels, distance bits, the order inside ties, the admissions gamma_hip_binivf_stats counts -- is the same in every mode.
+ * 0: one wave per query walks its probed lists.  1: the query's row sequence (probed lists in coarse order, entries in list
+ * order) is cut into chunks that never span two lists and spread over the device: per-chunk distance histograms, the
+ * bounds they give, the rows below the bounds collected in order, the heap replayed over those alone (DESIGN.md section
+ * 23); a call whose workspace (sized from nq x nprobe x the longest list, nothing is read back from the device) exceeds
+ * half of gamma_hip_set_workspace_budget, or of more than 65535 queries, runs as mode 0.  -1 (the default): mode 1 for
+ * calls of up to auto_max_nq queries (gamma_hip_binivf_scan_shape), mode 0 beyond.  Any other mode, or a handle that is
+ * not a binary IVF handle: GAMMA_HIP_EINVAL.  GAMMA_HIP_NO_BIN_SPREAD=1 in the environment makes every mode run as 0. */
+int gamma_hip_binivf_set_scan_mode(gamma_hip_index* h, int mode);
+/* the mode set (-1, 0 or 1) of a binary IVF handle (the scans of gamma_index_binary_ivf.cc:333-448).  Any other handle
+ * answers GAMMA_HIP_EINVAL, whose value is also the automatic mode's: ask binary IVF handles only. */
+int gamma_hip_binivf_scan_mode(const gamma_hip_index* h);
+/* the spread scan's shape (gamma_index_binary_ivf.cc:407-448 is the loop it spreads): *chunk_rows = rows per chunk,
+ * *auto_max_nq = the largest call mode -1 spreads (measured).  Either pointer may be NULL. */
+int gamma_hip_binivf_scan_shape(int* chunk_rows, int* auto_max_nq);
+/* {queries the spread chain answered, their chunks, their candidates (rows replayed through scan_codes' heap,
+ * gamma_index_binary_ivf.cc:407-448), queries that ran as mode 0 under mode 1 or -1 for lack of workspace} since the
+ * last reset; counted only by searches made while gamma_hip_profile_enable is on */
+int gamma_hip_binivf_scan_stats(gamma_hip_index* h, int64_t* out4, int reset);
 
 /* ---- exact Hamming (binary flat) search (faiss:IndexBinaryFlat.cpp, utils/hamming.cpp:230-265) ------------------------
  * Every stored code in vid order, and over them the answer GammaIVFBinaryScannerL2::scan_codes
