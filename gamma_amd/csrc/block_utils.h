@@ -118,6 +118,34 @@ __device__ __forceinline__ uint32_t lane_xor32(uint32_t v) {
         return (uint32_t)__shfl_xor((int)v, STRIDE, 64);
     }
 }
+// strides 16 and 32 on gfx950: v_permlane16_swap / v_permlane32_swap exchange the odd rows (the upper half) of one register with
+// the even rows (the lower half) of another; with the value in both, one result holds the value of the lower partner in every
+// lane and the other the upper partner's -- a vector-ALU move and a select, where __shfl_xor is an LDS-crossbar round trip
+#if defined(__gfx950__) && __has_builtin(__builtin_amdgcn_permlane16_swap) && __has_builtin(__builtin_amdgcn_permlane32_swap)
+#define GH_HAVE_PERMLANE_SWAP 1
+template <int STRIDE>
+__device__ __forceinline__ uint32_t lane_xor32_swap(uint32_t v, int lane) {
+    static_assert(STRIDE == 16 || STRIDE == 32, "row / half swaps");
+    if constexpr (STRIDE == 16) {
+        const auto r = __builtin_amdgcn_permlane16_swap(v, v, false, false);
+        return (lane & 16) ? (uint32_t)r[0] : (uint32_t)r[1];
+    } else {
+        const auto r = __builtin_amdgcn_permlane32_swap(v, v, false, false);
+        return (lane & 32) ? (uint32_t)r[0] : (uint32_t)r[1];
+    }
+}
+#endif
+template <int STRIDE>
+__device__ __forceinline__ unsigned long long lane_xor64_net(unsigned long long x, int lane) {
+#ifdef GH_HAVE_PERMLANE_SWAP
+    if constexpr (STRIDE == 16 || STRIDE == 32) {
+        const uint32_t lo = lane_xor32_swap<STRIDE>((uint32_t)x, lane), hi = lane_xor32_swap<STRIDE>((uint32_t)(x >> 32), lane);
+        return ((unsigned long long)hi << 32) | lo;
+    }
+#endif
+    const uint32_t lo = lane_xor32<STRIDE>((uint32_t)x), hi = lane_xor32<STRIDE>((uint32_t)(x >> 32));
+    return ((unsigned long long)hi << 32) | lo;
+}
 template <int STRIDE>
 __device__ __forceinline__ unsigned long long lane_xor64(unsigned long long x) {
     const uint32_t lo = lane_xor32<STRIDE>((uint32_t)x), hi = lane_xor32<STRIDE>((uint32_t)(x >> 32));
@@ -156,6 +184,55 @@ __device__ __forceinline__ unsigned long long wave_sort64(unsigned long long x) 
 template <int N>
 __device__ __forceinline__ void wave_sort64_multi(unsigned long long (&x)[N]) {
     bitonic_all<2, N>(x, (int)(threadIdx.x & 63));
+}
+
+// ---- one sorting network over 64 N items, N per lane: item i sits in x[i >> 6] of lane i & 63 (N a power of two) ----
+// The bitonic network of 64 N items.  A stage whose partner is 64 or more items away is a compare-exchange between two of the
+// lane's own registers; partners 16 and 32 away are permlane swaps on gfx950, nearer ones the DPP moves above.  Ascending: the
+// item of rank j ends in x[j >> 6] of lane j & 63.  (Against N sorts of 64 and a rank merge by binary searches in LDS, 18 dependent
+// LDS reads per item: k_select_final.)
+template <int SIZE, int STRIDE, int N>
+__device__ __forceinline__ void net_stage(unsigned long long (&x)[N], int lane) {
+    if constexpr (STRIDE >= 64) {
+        constexpr int D = STRIDE / 64;
+#pragma unroll
+        for (int r = 0; r < N; r++) {
+            if ((r & D) == 0) {
+                const bool asc = ((r * 64) & SIZE) == 0;
+                const unsigned long long a = x[r], b = x[r + D];
+                const bool sw = (b < a) == asc;
+                x[r] = sw ? b : a;
+                x[r + D] = sw ? a : b;
+            }
+        }
+    } else {
+#pragma unroll
+        for (int r = 0; r < N; r++) {
+            const unsigned long long y = lane_xor64_net<STRIDE>(x[r], lane);
+            const bool asc = SIZE >= 64 ? (((r * 64) & SIZE) == 0) : ((lane & SIZE) == 0);
+            const bool keep_min = ((lane & STRIDE) == 0) == asc;
+            x[r] = ((x[r] < y) == keep_min) ? x[r] : y;
+        }
+    }
+}
+template <int SIZE, int STRIDE, int N>
+__device__ __forceinline__ void net_size(unsigned long long (&x)[N], int lane) {
+    if constexpr (STRIDE > 0) {
+        net_stage<SIZE, STRIDE, N>(x, lane);
+        net_size<SIZE, (STRIDE >> 1), N>(x, lane);
+    }
+}
+template <int SIZE, int N>
+__device__ __forceinline__ void net_all(unsigned long long (&x)[N], int lane) {
+    if constexpr (SIZE <= 64 * N) {
+        net_size<SIZE, (SIZE >> 1), N>(x, lane);
+        net_all<SIZE * 2, N>(x, lane);
+    }
+}
+template <int N>
+__device__ __forceinline__ void wave_sort_net(unsigned long long (&x)[N]) {
+    static_assert(N >= 1 && (N & (N - 1)) == 0, "a power of two of 64-item rows");
+    net_all<2, N>(x, (int)(threadIdx.x & 63));
 }
 
 }  // namespace gh

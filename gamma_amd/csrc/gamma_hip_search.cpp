@@ -457,6 +457,7 @@ int ivfpq_stage_a(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int
     bool cf_ok = false, q8_ok = false;
     int PGM = PGN, nsl = PGN, cf_span = 0;
     unsigned long long* ready = nullptr;
+    size_t fl_off = 0;   // the fall-through list's place in w_scnt (bounded)
     if (bounded) {
         // filter pass of the consumers (kernels.hip, CF): needs the sums beside the arena the scan reads -- not the
         // shadow arena of a call running over lists compacted under its filter.  With it ONE consumer workgroup per
@@ -509,9 +510,11 @@ int ivfpq_stage_a(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int
             PGM = PGN;   // probe groups of the main launch
         }
         if (!q8_ok) nsl = PGM;   // one survivor slice per probe group (slice 0: the producer's own)
-        // rq | ready[nq] | gcnt[nq][nsl]   (rq: count + list of the queries that need the repair launch, 8-byte aligned)
+        // rq | ready[nq] | gcnt[nq][nsl] | fl   (rq: count + list of the queries that need the repair launch, 8-byte aligned;
+        //  fl: count + list of the queries k_select_final left to the unfiltered selection, flag = 1)
         const size_t rq_bytes = (((size_t)nq + 1) * sizeof(int) + 7) & ~(size_t)7;
-        GH_CHECK(h, h->w_scnt.ensure(rq_bytes + (size_t)nq * (sizeof(unsigned long long) + (size_t)nsl * sizeof(int))));
+        fl_off = rq_bytes + (size_t)nq * (sizeof(unsigned long long) + (size_t)nsl * sizeof(int));
+        GH_CHECK(h, h->w_scnt.ensure(fl_off + ((size_t)nq + 1) * sizeof(int)));
         GH_CHECK(h, h->w_sflag.ensure((size_t)nq));
         GH_CHECK(h, h->w_surv.ensure((size_t)nq * nsl * cap * sizeof(unsigned long long)));
         ready = reinterpret_cast<unsigned long long*>(h->w_scnt.as<char>() + rq_bytes);
@@ -564,6 +567,7 @@ int ivfpq_stage_a(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int
 #endif
             pz.words = h->scan_dbg_now == 2 ? nullptr : ready;
             pz.count_b = h->w_scnt.as<int>();
+            pz.count_c = reinterpret_cast<int*>(h->w_scnt.as<char>() + fl_off);
         }
         gh::launch_pair_offsets(s, h->w_probe.as<int>(), nq, P, h->d_list_len, h->d_list_mask, nlist,
                                 h->w_pair_off.as<int>(), h->w_qtotal.as<int>(),
@@ -616,7 +620,7 @@ int ivfpq_stage_a(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int
                                   out_ids);
         if (h->tie.on)
             gh::launch_flag_cut_ties(s, h->w_dist.as<float>(), q_stride, h->w_qtotal.as<int>(), nq, R, out_dis,
-                                     h->w_cand_pos.as<int>(), nullptr, h->w_tcut.as<uint8_t>());
+                                     h->w_cand_pos.as<int>(), h->w_tcut.as<uint8_t>());
     } else {
         gh::ScanBound sb = {};   // (every field starts at 0: part, dbg_part, c8 ...)
         sb.ready = ready;
@@ -715,12 +719,17 @@ int ivfpq_stage_a(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int
         const bool dbg = dbg_any && (!dbg_shard || shard);
         static const int dbg_from = 8;
         static int shown = 0;
+        // the queries that fall through the bound (a handful of a batch: ~5 of 16384 at C3): the launch behind k_select_final
+        // and the repair scan walks its list of them, as the repair launch walks rq_list
+        int* fl_count = reinterpret_cast<int*>(h->w_scnt.as<char>() + fl_off);
+        const gh::RowList fell(fl_count + 1, fl_count);
         StageScope t(h, GAMMA_HIP_STAGE_SELECT);
         gh::launch_select_final(s, l2, sb.surv, sb.gcnt, nsl, cap, sb.ready, h->w_pair_off.as<int>(), P, nq, R,
                                 h->w_pair_base.as<int64_t>(), h->d_ids,
                                 h->w_sflag.as<uint8_t>(), out_dis,
                                 h->w_cand_pos.as<int>(), out_ids, h->tie.on ? h->w_tcut.as<uint8_t>() : nullptr,
-                                h->d_tie_stats, sb.rq_list, sb.rq_count, h->d_bound_stat + 2 * (h->bound_epoch & 1));
+                                h->d_tie_stats, sb.rq_list, sb.rq_count, h->d_bound_stat + 2 * (h->bound_epoch & 1),
+                                fl_count + 1, fl_count);
         // the counts as of this call, for a later call's decision (16 bytes; ~5 us on the call's critical path, so: the
         // first calls of a kind, then every 16th)
         if ((h->bound_calls < 4 || (h->bound_calls & 15) == 0) && !h->bound_copy_pending) {
@@ -740,12 +749,19 @@ int ivfpq_stage_a(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int
                                        h->w_dist.as<float>(), fc.d_tab, fc.d_qf, need_ids, nullptr, G, 1,
                                        PGN - 1, shard ? 1 : 0, nullptr, nullptr, sb.rq_list, sb.rq_count);
         }
+        // (one launch: a listed row's workgroup selects it, flags a tied cut and looks its ids up)
+        gh::RowTail tail;
+        tail.tflag = h->tie.on ? h->w_tcut.as<uint8_t>() : nullptr;
+        tail.P = P;
+        tail.probe_list = h->w_probe.as<int>();
+        tail.pair_off = h->w_pair_off.as<int>();
+        tail.list_off = h->d_list_off;
+        tail.ids = h->d_ids;
+        tail.cand_ids = out_ids;
         gh::launch_select_topk(s, l2, h->w_dist.as<float>(), q_stride, h->w_qtotal.as<int>(), 0,
                                (int)std::min<int64_t>(q_stride, 1 << 30), nq, R,
-                               out_dis, h->w_cand_pos.as<int>(), h->w_sflag.as<uint8_t>());
+                               out_dis, h->w_cand_pos.as<int>(), fell, &tail);
         if (h->tie.on) {
-            gh::launch_flag_cut_ties(s, h->w_dist.as<float>(), q_stride, h->w_qtotal.as<int>(), nq, R, out_dis,
-                                     h->w_cand_pos.as<int>(), h->w_sflag.as<uint8_t>(), h->w_tcut.as<uint8_t>());
             h->tie.bounded = true;
             h->tie.nsl = nsl;
             h->tie.cap = cap;
@@ -772,9 +788,6 @@ int ivfpq_stage_a(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int
                     (long long)nf, nq, (long long)nobound, (double)tot / nq, (long long)mx, G, PGN, nsl, (long long)q_stride,
                     [&] { unsigned long long t = 0; (void)hipMemcpy(&t, h->d_bound_stat + 4, sizeof(t), hipMemcpyDeviceToHost); return t; }());
         }
-        gh::launch_map_candidates(s, h->w_cand_pos.as<int>(), nq, R, P, h->w_probe.as<int>(),
-                                  h->w_pair_off.as<int>(), h->d_list_off, h->d_ids,
-                                  out_ids, h->w_sflag.as<uint8_t>());
     }
     h->tie.G = G;
     h->tie.q_stride = q_stride;
@@ -899,7 +912,7 @@ int ivfpq_stage_b(H* h, const gamma_hip_search_params* p, int nq, const float* d
             GH_CHECK(h, h->w_textra.ensure((size_t)nq));
             GH_CHECK(h, hipMemsetAsync(h->w_textra.p, 0, (size_t)nq, s));
             gh::launch_flag_cut_ties(s, h->w_exact.as<float>(), R, nullptr, nq, k, h->w_selv.as<float>(), h->w_selp.as<int>(),
-                                     nullptr, h->w_textra.as<uint8_t>(), R, 1);
+                                     h->w_textra.as<uint8_t>(), R, 1);
             gh::launch_tie_list(s, tf.cut, h->w_textra.as<uint8_t>(), nq, tf.list, tf.count, tf.stats);
             if (tie_mode == 1) replay();
         }

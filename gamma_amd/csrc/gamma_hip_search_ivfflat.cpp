@@ -163,7 +163,7 @@ int ivfflat_search_device_locked(H* h, const gamma_hip_search_params* p, int nq,
                 GH_CHECK(h, hipMemsetAsync(h->w_tlist.p, 0, sizeof(int), s));
                 GH_CHECK(h, hipMemsetAsync(h->w_tcut.p, 0, (size_t)nc, s));
                 gh::launch_flag_cut_ties(s, h->w_dist.as<float>(), q_stride, h->w_qtotal.as<int>(), nc, k, h->w_cand_dis.as<float>(),
-                                         h->w_cand_pos.as<int>(), nullptr, h->w_tcut.as<uint8_t>(), 0, 1);
+                                         h->w_cand_pos.as<int>(), h->w_tcut.as<uint8_t>(), 0, 1);
                 tf.cut = h->w_tcut.as<uint8_t>();
                 tf.count = h->w_tlist.as<int>();
                 tf.list = h->w_tlist.as<int>() + 1;

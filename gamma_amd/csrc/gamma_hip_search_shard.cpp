@@ -257,7 +257,7 @@ static int merge_rerank_impl(gamma_hip_index* h, const gamma_hip_search_params* 
             GH_CHECK(h, h->w_textra.ensure((size_t)nq_local));
             GH_CHECK(h, hipMemsetAsync(h->w_textra.p, 0, (size_t)nq_local, s));
             gh::launch_flag_cut_ties(s, h->w_exact.as<float>(), R, nullptr, nq_local, k, h->w_selv.as<float>(), h->w_selp.as<int>(),
-                                     nullptr, h->w_textra.as<uint8_t>(), R, 1);
+                                     h->w_textra.as<uint8_t>(), R, 1);
             gh::launch_tie_list(s, tf.cut, h->w_textra.as<uint8_t>(), nq_local, tf.list, tf.count, tf.stats);
         }
         GH_CHECK(h, hipGetLastError());

@@ -169,6 +169,7 @@ struct PairZero {
     unsigned long long* words = nullptr;
     int* count_a = nullptr;
     int* count_b = nullptr;
+    int* count_c = nullptr;
     // histogram pass of the grid-wide query order (launch_query_order with hist_done): list_rank, qkey[nq], bins
     const int* qo_rank = nullptr;
     int* qo_key = nullptr;
@@ -363,20 +364,45 @@ void launch_ivfflat_lm(hipStream_t s, bool l2, const float* x, int nq, int d, in
 bool launch_coarse_select(hipStream_t s, const float* mat, int nlist, int nq, int K, float* out_vals, int* out_pos,
                           uint8_t* tie_flag, unsigned long long* tie_stats = nullptr, hipStream_t side = nullptr,
                           hipEvent_t fork = nullptr, hipEvent_t join = nullptr);
+// the rows a launch works on, as a list written on the device (k_select_final's fall-through list: a handful of a batch's
+// queries): the grid is a small cap -- row_list_grid -- whose workgroups / waves stride over the list.  Empty: every row.
+struct RowList {
+    const int* rows = nullptr;
+    const int* count = nullptr;
+    RowList() = default;
+    RowList(const int* r, const int* c) : rows(r), count(c) {}
+    explicit operator bool() const { return rows != nullptr; }
+};
+inline int row_list_grid(int nrows) { return nrows < 256 ? nrows : 256; }   // (one workgroup per compute unit)
+// what a listed launch of the selection does for a row once it is selected, in the same workgroup (the two launches that
+// followed it over the same handful of rows): whether the cut went through a group of equal values (launch_flag_cut_ties;
+// tflag null: skipped) and the candidates' ids (launch_map_candidates)
+struct RowTail {
+    uint8_t* tflag = nullptr;
+    int P = 0;
+    const int* probe_list = nullptr;
+    const int* pair_off = nullptr;
+    const int64_t* list_off = nullptr;
+    const int64_t* ids = nullptr;
+    int64_t* cand_ids = nullptr;
+};
 void launch_select_topk(hipStream_t s, bool smallest, const float* vals, int64_t seg_stride,
                         const int* seg_len, int fixed_len, int max_len, int nseg, int K,
-                        float* out_vals, int* out_pos, const uint8_t* only = nullptr);
+                        float* out_vals, int* out_pos, RowList only = {}, const RowTail* tail = nullptr);
 // threshold pre-filter of the scan: exact top-K from the survivor lists (select.hip); rows that end
-// with flag != 0 are left to launch_select_topk(..., only = flag)
+// with flag != 0 are appended to fl_list and left to launch_select_topk(..., only = {fl_list, fl_count})
 void launch_select_final(hipStream_t s, bool smallest, const unsigned long long* surv, const int* gcnt,
                          int nslices, int slice_cap, const unsigned long long* ready, const int* pair_off, int P,
                          int nq, int K, const int64_t* pair_base, const int64_t* ids, uint8_t* flag, float* out_vals,
                          int* out_pos, int64_t* out_ids, uint8_t* cut_tie = nullptr,
-                         unsigned long long* tie_stats = nullptr, int* rq_list = nullptr, int* rq_count = nullptr, unsigned long long* bound_stat = nullptr);   // slices 1.. in their own
-                                                                                        // array [nq][nslices - 1][cap_c]   // cut_tie[q] = 1: the K-th and (K+1)-th keys are equal
+                         unsigned long long* tie_stats = nullptr, int* rq_list = nullptr, int* rq_count = nullptr, unsigned long long* bound_stat = nullptr,
+                         int* fl_list = nullptr, int* fl_count = nullptr);
+// (surv: [nq][nslices][slice_cap] items, slice g of query q at (q * nslices + g) * slice_cap -- the kernels request a slice's
+//  first blocks before they know its count, so every slice must be allocated in full; P >= 1 and slice_cap >= 1.
+//  cut_tie[q] = 1: the K-th and (K+1)-th keys are equal)
 void launch_map_candidates(hipStream_t s, const int* pos, int nq, int R, int P,
                            const int* probe_list, const int* pair_off, const int64_t* list_off,
-                           const int64_t* ids, int64_t* cand_ids, const uint8_t* only = nullptr);
+                           const int64_t* ids, int64_t* cand_ids);
 void launch_rerank_dist(hipStream_t s, bool l2, const float* x, int nq, int d, const float* raw,
                         int64_t nraw, const int64_t* cand_ids, int R, float min_score,
                         float max_score, float* out, const int32_t* slot = nullptr, int64_t nslot = 0);
@@ -477,7 +503,7 @@ void launch_debug_heap_stream(hipStream_t s, int op, int k, int n, const float* 
 int tie_replay_max_probes();
 void launch_tie_replay(hipStream_t s, bool l2, const TieReplayArgs& a);
 void launch_flag_cut_ties(hipStream_t s, const float* slab, int64_t q_stride, const int* q_total, int nq, int K,
-                          const float* sel_vals, const int* sel_pos, const uint8_t* only, uint8_t* tflag,
+                          const float* sel_vals, const int* sel_pos, uint8_t* tflag,
                           int fixed_n = 0, int inside = 0);   // q_total == nullptr: rows of fixed_n entries; inside: also
                                                               // equal values among the selected K
 int coarse_heap_max_k();

@@ -25,33 +25,15 @@ __global__ __launch_bounds__(256) void k_map_candidates(const int* __restrict__ 
                                                         const int* __restrict__ pair_off,
                                                         const int64_t* __restrict__ list_off,
                                                         const int64_t* __restrict__ ids,
-                                                        int64_t* __restrict__ cand_ids,
-                                                        const uint8_t* __restrict__ only) {
-    const int q = blockIdx.x;
-    if (only && !only[q]) return;   // rows k_select_final has already mapped
-    const int* off = pair_off + (int64_t)q * (P + 1);
-    for (int r = threadIdx.x; r < R; r += 256) {
-        const int ps = pos[(int64_t)q * R + r];
-        int64_t id = -1;
-        if (ps >= 0) {
-            // last p with off[p] <= ps
-            int lo = 0, hi = P - 1;
-            while (lo < hi) {
-                int mid = (lo + hi + 1) >> 1;
-                if (off[mid] <= ps) lo = mid; else hi = mid - 1;
-            }
-            const int l = probe_list[(int64_t)q * P + lo];
-            id = ids[list_off[l] + (ps - off[lo])] & 0x7fffffffffffffffLL;
-        }
-        cand_ids[(int64_t)q * R + r] = id;
-    }
+                                                        int64_t* __restrict__ cand_ids) {
+    map_candidates_row(pos, R, P, probe_list, pair_off, list_off, ids, cand_ids, (int)blockIdx.x);
 }
 void launch_map_candidates(hipStream_t s, const int* pos, int nq, int R, int P,
                            const int* probe_list, const int* pair_off, const int64_t* list_off,
-                           const int64_t* ids, int64_t* cand_ids, const uint8_t* only) {
+                           const int64_t* ids, int64_t* cand_ids) {
     if (nq <= 0) return;
     hipLaunchKernelGGL(k_map_candidates, dim3(nq), dim3(256), 0, s, pos, R, P, probe_list, pair_off,
-                       list_off, ids, cand_ids, only);
+                       list_off, ids, cand_ids);
 }
 
 // ------------------------------------------------------------------------------------

@@ -382,4 +382,30 @@ __device__ __forceinline__ float rerank_dist8_sq8(const float* __restrict__ xq, 
     return t01 + __shfl_down(t01, 2, 8);
 }
 
+// positions in a row's candidate segment -> vector ids, by the 256 threads of a workgroup (k_map_candidates, rerank.hip; the
+// listed launches of the unfiltered selection, select.hip)
+__device__ __forceinline__ void map_candidates_row(const int* __restrict__ pos, int R, int P,
+                                                   const int* __restrict__ probe_list,
+                                                   const int* __restrict__ pair_off,
+                                                   const int64_t* __restrict__ list_off,
+                                                   const int64_t* __restrict__ ids,
+                                                   int64_t* __restrict__ cand_ids, int q) {
+    const int* off = pair_off + (int64_t)q * (P + 1);
+    for (int r = threadIdx.x; r < R; r += 256) {
+        const int ps = pos[(int64_t)q * R + r];
+        int64_t id = -1;
+        if (ps >= 0) {
+            // last p with off[p] <= ps
+            int lo = 0, hi = P - 1;
+            while (lo < hi) {
+                int mid = (lo + hi + 1) >> 1;
+                if (off[mid] <= ps) lo = mid; else hi = mid - 1;
+            }
+            const int l = probe_list[(int64_t)q * P + lo];
+            id = ids[list_off[l] + (ps - off[lo])] & 0x7fffffffffffffffLL;
+        }
+        cand_ids[(int64_t)q * R + r] = id;
+    }
+}
+
 }  // namespace gh

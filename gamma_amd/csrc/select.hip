@@ -64,13 +64,20 @@ __device__ __forceinline__ void bitonic_sort_lds(unsigned long long* a, int npad
 }
 }  // namespace
 
+// a listed row after its selection (RowTail, kernels.h): the workgroup has written the row's K values and positions and passed a
+// barrier; wave 0 flags a cut through equal values, all 256 threads look the ids up
+__device__ __forceinline__ void listed_row_tail(const float* __restrict__ vals, int64_t seg_stride, const int* __restrict__ seg_len,
+                                                int fixed_len, int K, const float* out_vals, const int* out_pos,
+                                                const RowTail& t, int seg) {
+    if (t.tflag && threadIdx.x < 64) flag_cut_ties_row(vals, seg_stride, seg_len, K, out_vals, out_pos, t.tflag, fixed_len, 0, seg);
+    if (t.cand_ids) map_candidates_row(out_pos, K, t.P, t.probe_list, t.pair_off, t.list_off, t.ids, t.cand_ids, seg);
+}
+
 template <bool SMALLEST, int NPT>
-__global__ __launch_bounds__(256) void k_select2(const float* __restrict__ vals, int64_t seg_stride,
-                                                 const int* __restrict__ seg_len, int fixed_len, int K,
-                                                 int Kpad, float* __restrict__ out_vals,
-                                                 int* __restrict__ out_pos,
-                                                 const uint8_t* __restrict__ only) {
-    if (only && !only[blockIdx.x]) return;         // rows another kernel has already selected
+__device__ __forceinline__ void select2_row(const float* __restrict__ vals, int64_t seg_stride,
+                                            const int* __restrict__ seg_len, int fixed_len, int K,
+                                            int Kpad, float* __restrict__ out_vals,
+                                            int* __restrict__ out_pos, const int seg) {
     extern __shared__ unsigned long long s_dyn[];  // items[Kpad] | cand[CAP]
     unsigned long long* s_items = s_dyn;
     unsigned long long* s_cand = s_dyn + Kpad;
@@ -79,7 +86,6 @@ __global__ __launch_bounds__(256) void k_select2(const float* __restrict__ vals,
     __shared__ uint32_t s_red[8];
     __shared__ int s_misc[8];
     const int tid = threadIdx.x;
-    const int seg = blockIdx.x;
     const int n = seg_len ? seg_len[seg] : fixed_len;
     const float* v = vals + (int64_t)seg * seg_stride;
 
@@ -250,6 +256,25 @@ __global__ __launch_bounds__(256) void k_select2(const float* __restrict__ vals,
         out_pos[(int64_t)seg * K + r] = pos;
     }
 }
+// one workgroup per row; or (rows != nullptr: the rows another kernel has not selected already, a list written on the
+// device) a small grid whose workgroups stride over the list
+template <bool SMALLEST, int NPT>
+__global__ __launch_bounds__(256) void k_select2(const float* __restrict__ vals, int64_t seg_stride,
+                                                 const int* __restrict__ seg_len, int fixed_len, int K,
+                                                 int Kpad, float* __restrict__ out_vals,
+                                                 int* __restrict__ out_pos,
+                                                 const int* __restrict__ rows, const int* __restrict__ nrows, RowTail tail) {
+    if (!rows) {
+        select2_row<SMALLEST, NPT>(vals, seg_stride, seg_len, fixed_len, K, Kpad, out_vals, out_pos, (int)blockIdx.x);
+        return;
+    }
+    const int nr = *nrows;
+    for (int w = blockIdx.x; w < nr; w += (int)gridDim.x) {
+        select2_row<SMALLEST, NPT>(vals, seg_stride, seg_len, fixed_len, K, Kpad, out_vals, out_pos, rows[w]);
+        __syncthreads();   // the row's results are written; the next row starts over in the same LDS
+        listed_row_tail(vals, seg_stride, seg_len, fixed_len, K, out_vals, out_pos, tail, rows[w]);
+    }
+}
 
 // ------------------------------------------------------------------------------------
 // Streaming variant for long rows (n > 4096, K <= 1024): ONE pass over the row.  Elements
@@ -361,13 +386,11 @@ __device__ uint32_t st_compact(unsigned long long* buf, int n, int K, int* s_his
 }
 }  // namespace
 
-template <bool SMALLEST, int ST_CAPS = 2048>
-__global__ __launch_bounds__(256) void k_select_stream(const float* __restrict__ vals, int64_t seg_stride,
-                                                       const int* __restrict__ seg_len, int fixed_len,
-                                                       int K, int Kpad, float* __restrict__ out_vals,
-                                                       int* __restrict__ out_pos,
-                                                       const uint8_t* __restrict__ only) {
-    if (only && !only[blockIdx.x]) return;         // rows another kernel has already selected
+template <bool SMALLEST, int ST_CAPS>
+__device__ __forceinline__ void select_stream_row(const float* __restrict__ vals, int64_t seg_stride,
+                                                  const int* __restrict__ seg_len, int fixed_len,
+                                                  int K, float* __restrict__ out_vals,
+                                                  int* __restrict__ out_pos, const int seg) {
     __shared__ unsigned long long s_buf[ST_CAPS];
     __shared__ int s_hist[NB];
     __shared__ int s_w[4];
@@ -375,7 +398,6 @@ __global__ __launch_bounds__(256) void k_select_stream(const float* __restrict__
     __shared__ int s_misc[8];
     __shared__ int s_cnt;
     const int tid = threadIdx.x, lane = tid & 63;
-    const int seg = blockIdx.x;
     const int n = seg_len ? seg_len[seg] : fixed_len;
     const float* v = vals + (int64_t)seg * seg_stride;
     if (tid == 0) s_cnt = 0;
@@ -450,6 +472,23 @@ __global__ __launch_bounds__(256) void k_select_stream(const float* __restrict__
         }
         out_vals[(int64_t)seg * K + r] = val;
         out_pos[(int64_t)seg * K + r] = pos;
+    }
+}
+template <bool SMALLEST, int ST_CAPS = 2048>   // rows / nrows: as k_select2
+__global__ __launch_bounds__(256) void k_select_stream(const float* __restrict__ vals, int64_t seg_stride,
+                                                       const int* __restrict__ seg_len, int fixed_len,
+                                                       int K, int Kpad, float* __restrict__ out_vals,
+                                                       int* __restrict__ out_pos,
+                                                       const int* __restrict__ rows, const int* __restrict__ nrows, RowTail tail) {
+    if (!rows) {
+        select_stream_row<SMALLEST, ST_CAPS>(vals, seg_stride, seg_len, fixed_len, K, out_vals, out_pos, (int)blockIdx.x);
+        return;
+    }
+    const int nr = *nrows;
+    for (int w = blockIdx.x; w < nr; w += (int)gridDim.x) {
+        select_stream_row<SMALLEST, ST_CAPS>(vals, seg_stride, seg_len, fixed_len, K, out_vals, out_pos, rows[w]);
+        __syncthreads();   // the row's results are written; the next row starts over in the same LDS
+        listed_row_tail(vals, seg_stride, seg_len, fixed_len, K, out_vals, out_pos, tail, rows[w]);
     }
 }
 
@@ -665,8 +704,9 @@ __global__ __launch_bounds__(256) void k_select_wave(const float* __restrict__ v
 //
 // k_select_final: one wave per query turns the survivor list written by the filtered scan
 // (a few hundred (key, position) items) into the sorted top-K: histogram cut down to <= 256
-// items, four 64-item bitonic sorts in registers (wave shuffles), rank merge by binary search.
-// Lists that overflowed, or cuts that cannot get below 256 items (mass ties), set flag = 1.
+// items, one sorting network over them in registers, four per lane (wave_sort_net, block_utils.h).
+// Lists that overflowed, or cuts that cannot get below 256 items (mass ties), set flag = 1 and are
+// appended to fl_list: the launch behind this one works on the listed rows alone (RowList).
 // ------------------------------------------------------------------------------------
 namespace {
 constexpr int SF_CAND = 384;   // candidates of one query held in LDS (first group within the bound + slices);
@@ -689,24 +729,49 @@ __device__ __forceinline__ void select_final_body(const unsigned long long* __re
                                                       uint8_t* __restrict__ cut_tie,
                                                       unsigned long long* __restrict__ tie_stats,
                                                       int* __restrict__ rq_list, int* __restrict__ rq_count,
-                                                      unsigned long long* __restrict__ bound_stat) {
+                                                      unsigned long long* __restrict__ bound_stat,
+                                                      int* __restrict__ fl_list, int* __restrict__ fl_count) {
     __shared__ int s_hist[4][256];
     constexpr int KEEP = 64 * NR, SFC = NR == 4 ? SF_CAND : 96 * NR;
     __shared__ unsigned long long s_cand[4][SFC];   // candidates, later the <= KEEP kept ones (in place)
     __shared__ int s_off[4][PMAX + 8];
     __shared__ int64_t s_base[4][PMAX];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    // (the wave's index as a scalar: the query's rows are then scalar bases with a lane offset, not a 64-bit address per lane)
+    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int q = blockIdx.x * 4 + w;
     if (bound_stat && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(bound_stat + 1, (unsigned long long)nq);
     if (q >= nq) return;
     const unsigned long long word = ready[q];
     // slice counts of the consumer workgroups (nslices <= 64: one per lane)
     const int my_cnt = lane < nslices ? gcnt[(int64_t)q * nslices + lane] : 0;
+    // Everything the wave reads before the cut is requested here, beside the bound word and the counts, and waited for once: this
+    // query's pair offsets and list bases (P + 1 <= PMAX + 1 entries, see the launcher), and -- two slices -- the first four 64-item
+    // blocks of both.  A slice's address depends on (q, slice) alone and it is allocated to slice_cap items, so what lies past its
+    // count is read (inside the allocation) and never used.  It used to be three dependent round trips: word + counts -> pair
+    // tables -> slices.
+    const int* goff = pair_off + (int64_t)q * (P + 1);
+    int off_r[PMAX / 64 + 1];
+    int64_t base_r[PMAX / 64];
+#pragma unroll
+    for (int u = 0; u <= PMAX / 64; u++) off_r[u] = goff[min(lane + 64 * u, P)];
+#pragma unroll
+    for (int u = 0; u < PMAX / 64; u++) base_r[u] = pair_base[(int64_t)q * P + min(lane + 64 * u, P - 1)];
+    unsigned long long t0[4], t1[4];
+    if (nslices == 2) {
+        const unsigned long long* s0 = surv + (int64_t)q * 2 * slice_cap;
+        const unsigned long long* s1 = s0 + slice_cap;
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            t0[u] = s0[min(64 * u + lane, slice_cap - 1)];
+            t1[u] = s1[min(64 * u + lane, slice_cap - 1)];
+        }
+    }
     // left to the unfiltered selection kernel: no bound (every group stored its distances), or a slice overflowed
     // (groups with a bound did not store: the repair launch scores them again first, rq_list)
     if ((word >> 32) != 1ull) {
         if (lane == 0) {
             flag[q] = 1;
+            if (fl_list) fl_list[atomicAdd(fl_count, 1)] = q;
             if (bound_stat) atomicAdd(bound_stat, 1ull);
         }
         return;
@@ -715,6 +780,7 @@ __device__ __forceinline__ void select_final_body(const unsigned long long* __re
     if (__ballot(my_cnt > slice_cap)) {
         if (lane == 0) {
             flag[q] = 1;
+            if (fl_list) fl_list[atomicAdd(fl_count, 1)] = q;
             if (rq_list) rq_list[atomicAdd(rq_count, 1)] = q;
             if (bound_stat) atomicAdd(bound_stat, 1ull);
         }
@@ -723,11 +789,14 @@ __device__ __forceinline__ void select_final_body(const unsigned long long* __re
     int* hist = s_hist[w];
     unsigned long long* cand = s_cand[w];
     unsigned long long* runs = cand;
-    const int* goff = pair_off + (int64_t)q * (P + 1);
-    int* off = s_off[w];        // this query's pair offsets (P + 1 <= PMAX + 1 entries, see the launcher)
-    for (int i = lane; i <= P; i += 64) off[i] = goff[i];
+    int* off = s_off[w];        // this query's pair offsets
+#pragma unroll
+    for (int u = 0; u <= PMAX / 64; u++)
+        if (lane + 64 * u <= P) off[lane + 64 * u] = off_r[u];
     int64_t* lbase = s_base[w];   // arena offset of each probed list (k_pair_offsets): no probe_list ->
-    for (int i = lane; i < P; i += 64) lbase[i] = pair_base[(int64_t)q * P + i];   // list_off chain at the end
+#pragma unroll
+    for (int u = 0; u < PMAX / 64; u++)
+        if (lane + 64 * u < P) lbase[lane + 64 * u] = base_r[u];   // list_off chain at the end
     // ---- gather the candidate set into LDS: the survivor slices (slice 0 = the first probe group's own
     //      candidates within the bound, appended by its producer workgroup) ----
     int c = 0;
@@ -739,12 +808,6 @@ __device__ __forceinline__ void select_final_body(const unsigned long long* __re
         const int c0 = __shfl(my_cnt, 0, 64), c1 = __shfl(my_cnt, 1, 64);
         const unsigned long long* s0 = slice_ptr(0);
         const unsigned long long* s1 = slice_ptr(1);
-        unsigned long long t0[4], t1[4];
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            t0[u] = s0[min(64 * u + lane, max(c0 - 1, 0))];
-            t1[u] = s1[min(64 * u + lane, max(c1 - 1, 0))];
-        }
         auto take = [&](const unsigned long long* sg, const unsigned long long (&t)[4], int cg) {
             for (int i0 = 0; i0 < cg; i0 += 64) {
                 if (i0 + lane < cg) {
@@ -848,6 +911,7 @@ __device__ __forceinline__ void select_final_body(const unsigned long long* __re
                 if (kept > KEEP) {        // > 256 copies of one key around the K-th: rare, unfiltered path
                     if (lane == 0) {
                         flag[q] = 1;
+                        if (fl_list) fl_list[atomicAdd(fl_count, 1)] = q;
                         if (rq_list) rq_list[atomicAdd(rq_count, 1)] = q;
                         if (bound_stat) atomicAdd(bound_stat, 1ull);
                     }
@@ -875,47 +939,16 @@ __device__ __forceinline__ void select_final_body(const unsigned long long* __re
         m += __popcll(bal);
     });
     __builtin_amdgcn_wave_barrier();
-    // ---- four sorted runs of 64, then rank merge ----
+    // ---- one sorting network over the wave's <= 64 NR items, NR per lane (block_utils.h): rank j ends in x[j >> 6] of lane
+    //      j & 63, which is where the coalesced output pass below wants it ----
     unsigned long long x[NR];
 #pragma unroll
     for (int r = 0; r < NR; r++) x[r] = (r * 64 + lane < m) ? runs[r * 64 + lane] : ~0ull;
     __builtin_amdgcn_wave_barrier();
-    wave_sort64_multi<NR>(x);
-#pragma unroll
-    for (int r = 0; r < NR; r++) runs[r * 64 + lane] = x[r];
-    __builtin_amdgcn_wave_barrier();
+    wave_sort_net<NR>(x);
     const float sentinel = SMALLEST ? INFINITY : -INFINITY;
-    int rk[NR];
 #pragma unroll
-    for (int r = 0; r < NR; r++) {
-        int rank = lane;
-#pragma unroll
-        for (int o = 0; o < NR; o++) {
-            if (o == r) continue;
-            // number of items of run o smaller than x[r]
-            const unsigned long long* ro = runs + o * 64;
-            int lo2 = 0, n2 = 64;
-#pragma unroll
-            for (int st = 0; st < 7; st++) {
-                if (n2 > 0) {
-                    const int half = n2 >> 1;
-                    if (ro[lo2 + half] < x[r]) {
-                        lo2 += half + 1;
-                        n2 -= half + 1;
-                    } else {
-                        n2 = half;
-                    }
-                }
-            }
-            rank += lo2;
-        }
-        rk[r] = rank;
-    }
-    // the K winners in rank order (LDS), then one coalesced pass: rank r = lane + 64 i
-    __builtin_amdgcn_wave_barrier();   // all binary searches have read the runs
-#pragma unroll
-    for (int r = 0; r < NR; r++)
-        if (x[r] != ~0ull && rk[r] < KEEP) runs[rk[r]] = x[r];   // ranks are a permutation of 0..m-1
+    for (int r = 0; r < NR; r++) runs[r * 64 + lane] = x[r];   // (the tie test and the clamped look-ups read by rank)
     __builtin_amdgcn_wave_barrier();
     // exact ties: every candidate at the K-th key is among the m kept items (key <= cutoff), so the cut went
     // through a tie group iff the item of rank K carries the key of rank K - 1
@@ -963,18 +996,18 @@ __device__ __forceinline__ void select_final_body(const unsigned long long* __re
 }
 
 // the kernels: four runs (recall_num <= 256) under a 64-register budget -- eight waves per SIMD: the kernel is a chain of dependent
-// loads per wave (bound word + counts -> slices -> ids), what it gains from is waves in flight (93.8 against 96.5 us at C3) -- and
-// eight runs (recall_num <= 512: 99 registers) without one
+// loads per wave (bound word, counts, pair tables and slices together -> ids), what it gains from is waves in flight (93.8 against
+// 96.5 us at C3) -- and eight runs (recall_num <= 512) without one
 #define GH_SF_PARAMS                                                                                                          \
     const unsigned long long *__restrict__ surv, const int *__restrict__ gcnt, int nslices, int slice_cap,                    \
         const unsigned long long *__restrict__ ready, const int *__restrict__ pair_off, int P, int nq, int K,                 \
         const int64_t *__restrict__ pair_base, const int64_t *__restrict__ ids, uint8_t *__restrict__ flag,                   \
         float *__restrict__ out_vals, int *__restrict__ out_pos, int64_t *__restrict__ out_ids, uint8_t *__restrict__ cut_tie, \
         unsigned long long *__restrict__ tie_stats, int *__restrict__ rq_list, int *__restrict__ rq_count,                    \
-        unsigned long long *__restrict__ bound_stat
+        unsigned long long *__restrict__ bound_stat, int *__restrict__ fl_list, int *__restrict__ fl_count
 #define GH_SF_ARGS                                                                                                                   \
     surv, gcnt, nslices, slice_cap, ready, pair_off, P, nq, K, pair_base, ids, flag, out_vals, out_pos, out_ids, cut_tie, tie_stats, \
-        rq_list, rq_count, bound_stat
+        rq_list, rq_count, bound_stat, fl_list, fl_count
 // (PMAX = 128: the pair tables in LDS leave seven waves per SIMD whatever the registers -- the budget still holds, the compiler says so)
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Wpass-failed"
@@ -1011,7 +1044,8 @@ __global__ __launch_bounds__(256) void k_select_final_wg(const unsigned long lon
                                                          int* __restrict__ out_pos, int64_t* __restrict__ out_ids,
                                                          uint8_t* __restrict__ cut_tie, unsigned long long* __restrict__ tie_stats,
                                                          int* __restrict__ rq_list, int* __restrict__ rq_count,
-                                                         unsigned long long* __restrict__ bound_stat) {
+                                                         unsigned long long* __restrict__ bound_stat,
+                                                         int* __restrict__ fl_list, int* __restrict__ fl_count) {
     __shared__ unsigned long long s_it[SFW_KEEP];
     __shared__ int s_hist[256];
     __shared__ int s_off[128 + 8];
@@ -1024,6 +1058,7 @@ __global__ __launch_bounds__(256) void k_select_final_wg(const unsigned long lon
     if ((word >> 32) != 1ull) {   // no bound: every group stored its distances, the unfiltered selection takes the query
         if (tid == 0) {
             flag[q] = 1;
+            if (fl_list) fl_list[atomicAdd(fl_count, 1)] = q;
             if (bound_stat) atomicAdd(bound_stat, 1ull);
         }
         return;
@@ -1031,6 +1066,7 @@ __global__ __launch_bounds__(256) void k_select_final_wg(const unsigned long lon
     auto give_up = [&]() {   // a slice overflowed / a mass tie: the repair launch scores the consumer groups again, with stores
         if (tid == 0) {
             flag[q] = 1;
+            if (fl_list) fl_list[atomicAdd(fl_count, 1)] = q;
             if (rq_list) rq_list[atomicAdd(rq_count, 1)] = q;
             if (bound_stat) atomicAdd(bound_stat, 1ull);
         }
@@ -1741,7 +1777,7 @@ bool launch_coarse_select(hipStream_t s, const float* mat, int nlist, int nq, in
     } else {
         launch_select_topk(s, true, mat, nlist, nullptr, nlist, nlist, nq, K, out_vals, out_pos);
         (void)hipMemsetAsync(tie_flag, 0, (size_t)nq, s);
-        launch_flag_cut_ties(s, mat, nlist, nullptr, nq, K, out_vals, out_pos, nullptr, tie_flag, nlist, 1);
+        launch_flag_cut_ties(s, mat, nlist, nullptr, nq, K, out_vals, out_pos, tie_flag, nlist, 1);
     }
     hipStream_t rs = s;
     if (side && fork && join) {
@@ -1769,12 +1805,14 @@ int select_kpad(int K) {
 template <bool SMALLEST>
 static void launch_sel(hipStream_t s, const float* vals, int64_t seg_stride, const int* seg_len,
                        int fixed_len, int max_len, int nseg, int K, float* out_vals, int* out_pos,
-                       const uint8_t* only) {
+                       RowList only, const RowTail* tail) {
+    const RowTail rt = (only && tail) ? *tail : RowTail();
     const int Kpad = select_kpad(K);
     const size_t lds = (size_t)(Kpad + CAP) * sizeof(unsigned long long);
+    const int grid = only ? row_list_grid(nseg) : nseg;   // (a listed launch: workgroups stride over the list)
 #define GH_SEL(NPT)                                                                              \
-    hipLaunchKernelGGL((k_select2<SMALLEST, NPT>), dim3(nseg), dim3(256), lds, s, vals, seg_stride, \
-                       seg_len, fixed_len, K, Kpad, out_vals, out_pos, only)
+    hipLaunchKernelGGL((k_select2<SMALLEST, NPT>), dim3(grid), dim3(256), lds, s, vals, seg_stride, \
+                       seg_len, fixed_len, K, Kpad, out_vals, out_pos, only.rows, only.count, rt)
     static const bool no_wave = getenv("GAMMA_HIP_NO_WAVE_SELECT") != nullptr;
     static const bool no_stream = getenv("GAMMA_HIP_NO_STREAM_SELECT") != nullptr;
     static const bool no_stream_2k = getenv("GAMMA_HIP_NO_STREAM_SELECT_2K") != nullptr;
@@ -1787,34 +1825,36 @@ static void launch_sel(hipStream_t s, const float* vals, int64_t seg_stride, con
     else if (max_len <= 256 * 4) GH_SEL(4);
     else if (max_len <= 256 * 16) GH_SEL(16);
     else if (K <= 1024 && (seg_stride & 3) == 0 && (reinterpret_cast<uintptr_t>(vals) & 15) == 0 && !no_stream)
-        hipLaunchKernelGGL((k_select_stream<SMALLEST>), dim3(nseg), dim3(256), 0, s, vals, seg_stride,
-                           seg_len, fixed_len, K, Kpad, out_vals, out_pos, only);
+        hipLaunchKernelGGL((k_select_stream<SMALLEST>), dim3(grid), dim3(256), 0, s, vals, seg_stride,
+                           seg_len, fixed_len, K, Kpad, out_vals, out_pos, only.rows, only.count, rt);
     else if (K <= 2048 && (seg_stride & 3) == 0 && (reinterpret_cast<uintptr_t>(vals) & 15) == 0 && !no_stream &&
              !no_stream_2k)
-        hipLaunchKernelGGL((k_select_stream<SMALLEST, 4096>), dim3(nseg), dim3(256), 0, s, vals, seg_stride,
-                           seg_len, fixed_len, K, Kpad, out_vals, out_pos, only);
+        hipLaunchKernelGGL((k_select_stream<SMALLEST, 4096>), dim3(grid), dim3(256), 0, s, vals, seg_stride,
+                           seg_len, fixed_len, K, Kpad, out_vals, out_pos, only.rows, only.count, rt);
     else GH_SEL(0);
 #undef GH_SEL
 }
 
 void launch_select_topk(hipStream_t s, bool smallest, const float* vals, int64_t seg_stride,
                         const int* seg_len, int fixed_len, int max_len, int nseg, int K,
-                        float* out_vals, int* out_pos, const uint8_t* only) {
+                        float* out_vals, int* out_pos, RowList only, const RowTail* tail) {
     if (nseg <= 0 || K <= 0) return;
     if (smallest)
-        launch_sel<true>(s, vals, seg_stride, seg_len, fixed_len, max_len, nseg, K, out_vals, out_pos, only);
+        launch_sel<true>(s, vals, seg_stride, seg_len, fixed_len, max_len, nseg, K, out_vals, out_pos, only, tail);
     else
-        launch_sel<false>(s, vals, seg_stride, seg_len, fixed_len, max_len, nseg, K, out_vals, out_pos, only);
+        launch_sel<false>(s, vals, seg_stride, seg_len, fixed_len, max_len, nseg, K, out_vals, out_pos, only, tail);
 }
 
 void launch_select_final(hipStream_t s, bool smallest, const unsigned long long* surv, const int* gcnt,
                          int nslices, int slice_cap, const unsigned long long* ready, const int* pair_off, int P,
                          int nq, int K, const int64_t* pair_base, const int64_t* ids, uint8_t* flag, float* out_vals,
                          int* out_pos, int64_t* out_ids, uint8_t* cut_tie, unsigned long long* tie_stats,
-                         int* rq_list, int* rq_count, unsigned long long* bound_stat) {
+                         int* rq_list, int* rq_count, unsigned long long* bound_stat, int* fl_list, int* fl_count) {
     if (nq <= 0) return;
-    if (P > 128 || K > 1024 || (K <= 256 && nslices > 64)) {   // callers gate on this (gamma_hip_search.cpp, ivfpq_stage_a)
-        launch_refused("launch_select_final: nprobe > 128, recall_num > 1024 or more than 64 survivor slices");
+    // (P >= 1 and slice_cap >= 1: the kernels read pair_base[q * P + min(.., P - 1)] and the slices up to slice_cap - 1 before any
+    //  early exit)
+    if (P < 1 || slice_cap < 1 || P > 128 || K > 1024 || (K <= 256 && nslices > 64)) {   // callers gate on this (gamma_hip_search.cpp, ivfpq_stage_a)
+        launch_refused("launch_select_final: nprobe outside 1 ... 128, recall_num > 1024, more than 64 survivor slices or no slice capacity");
         return;
     }
     static const bool no_wave8 = getenv("GAMMA_HIP_NO_SELECT_WAVE8") != nullptr;
@@ -1822,7 +1862,7 @@ void launch_select_final(hipStream_t s, bool smallest, const unsigned long long*
 #define GH_SF8(SM, PM)                                                                                           \
     hipLaunchKernelGGL((k_select_final8<SM, PM>), dim3((nq + 3) / 4), dim3(256), 0, s, surv, gcnt, nslices,   \
                        slice_cap, ready, pair_off, P, nq, K, pair_base, ids, flag,                               \
-                       out_vals, out_pos, out_ids, cut_tie, tie_stats, rq_list, rq_count, bound_stat)
+                       out_vals, out_pos, out_ids, cut_tie, tie_stats, rq_list, rq_count, bound_stat, fl_list, fl_count)
         if (smallest) {
             if (P <= 64) GH_SF8(true, 64);
             else GH_SF8(true, 128);
@@ -1836,16 +1876,16 @@ void launch_select_final(hipStream_t s, bool smallest, const unsigned long long*
     if (K > 256) {          // one workgroup per query (recall_num up to 1024: the callers' gate)
         if (smallest)
             hipLaunchKernelGGL((k_select_final_wg<true>), dim3(nq), dim3(256), 0, s, surv, gcnt, nslices, slice_cap, ready, pair_off, P, nq,
-                               K, pair_base, ids, flag, out_vals, out_pos, out_ids, cut_tie, tie_stats, rq_list, rq_count, bound_stat);
+                               K, pair_base, ids, flag, out_vals, out_pos, out_ids, cut_tie, tie_stats, rq_list, rq_count, bound_stat, fl_list, fl_count);
         else
             hipLaunchKernelGGL((k_select_final_wg<false>), dim3(nq), dim3(256), 0, s, surv, gcnt, nslices, slice_cap, ready, pair_off, P,
-                               nq, K, pair_base, ids, flag, out_vals, out_pos, out_ids, cut_tie, tie_stats, rq_list, rq_count, bound_stat);
+                               nq, K, pair_base, ids, flag, out_vals, out_pos, out_ids, cut_tie, tie_stats, rq_list, rq_count, bound_stat, fl_list, fl_count);
         return;
     }
 #define GH_SF(SM, PM)                                                                                        \
     hipLaunchKernelGGL((k_select_final<SM, PM>), dim3((nq + 3) / 4), dim3(256), 0, s, surv, gcnt, nslices,   \
                        slice_cap, ready, pair_off, P, nq, K, pair_base, ids, flag,                           \
-                       out_vals, out_pos, out_ids, cut_tie, tie_stats, rq_list, rq_count, bound_stat)
+                       out_vals, out_pos, out_ids, cut_tie, tie_stats, rq_list, rq_count, bound_stat, fl_list, fl_count)
     if (smallest) {
         if (P <= 64) GH_SF(true, 64);
         else GH_SF(true, 128);

@@ -170,6 +170,7 @@ __global__ __launch_bounds__(256) void k_pair_offsets(const int* __restrict__ pr
         if (q == 0) {
             if (z.count_a) *z.count_a = 0;
             if (z.count_b) *z.count_b = 0;
+            if (z.count_c) *z.count_c = 0;
         }
         // the histogram pass of the grid-wide query order (k_qo_scan / k_qo_scatter below): key of the query's nearest list
         if (z.qo_bins) {

@@ -150,52 +150,23 @@ void launch_tie_replay(hipStream_t s, bool l2, const TieReplayArgs& a0) {
 // ------------------------------------------------------------------------------------
 // Does the top-K cut of a query go through a group of equal distances?  (unfiltered selection paths:
 // their kernels return exactly K items.)  One wave per query: count the slab entries equal to the K-th
-// selected value, compare with how many of them were selected.  only != nullptr: rows with only[q] != 0.
+// selected value, compare with how many of them were selected (flag_cut_ties_row, tie_dev.h).
 // ------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_flag_cut_ties(const float* __restrict__ slab, int64_t q_stride,
                                                        const int* __restrict__ q_total, int nq, int K,
                                                        const float* __restrict__ sel_vals,
                                                        const int* __restrict__ sel_pos,
-                                                       const uint8_t* __restrict__ only,
                                                        uint8_t* __restrict__ tflag, int fixed_n, int inside) {
-    const int lane = threadIdx.x & 63;
     const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (q >= nq || (only && !only[q])) return;
-    if (inside) {   // two equal values among the selected K (coarse quantizer: the order of the probes)
-        bool eq = false;
-        for (int r = lane; r + 1 < K; r += 64)
-            eq |= sel_pos[(int64_t)q * K + r + 1] >= 0 && sel_vals[(int64_t)q * K + r] == sel_vals[(int64_t)q * K + r + 1];
-        if (__ballot(eq)) {
-            if (lane == 0) tflag[q] = 1;
-            return;
-        }
-    }
-    if (sel_pos[(int64_t)q * K + K - 1] < 0) return;   // fewer than K candidates: nothing was cut
-    const float vk = sel_vals[(int64_t)q * K + K - 1];
-    int in_sel = 0, in_all = 0;
-    for (int r = lane; r < K; r += 64) in_sel += sel_vals[(int64_t)q * K + r] == vk ? 1 : 0;
-    const float* v = slab + (int64_t)q * q_stride;
-    const int n = q_total ? q_total[q] : fixed_n;
-    for (int j0 = 0; j0 < n; j0 += 64 * 8) {
-        float t[8];
-#pragma unroll
-        for (int u = 0; u < 8; u++) t[u] = v[min(j0 + u * 64 + lane, n - 1)];
-#pragma unroll
-        for (int u = 0; u < 8; u++) in_all += (j0 + u * 64 + lane < n && t[u] == vk) ? 1 : 0;
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        in_sel += __shfl_xor(in_sel, off, 64);
-        in_all += __shfl_xor(in_all, off, 64);
-    }
-    if (lane == 0 && in_all > in_sel) tflag[q] = 1;
+    if (q >= nq) return;
+    flag_cut_ties_row(slab, q_stride, q_total, K, sel_vals, sel_pos, tflag, fixed_n, inside, q);
 }
 void launch_flag_cut_ties(hipStream_t s, const float* slab, int64_t q_stride, const int* q_total, int nq, int K,
-                          const float* sel_vals, const int* sel_pos, const uint8_t* only, uint8_t* tflag, int fixed_n,
+                          const float* sel_vals, const int* sel_pos, uint8_t* tflag, int fixed_n,
                           int inside) {
     if (nq <= 0) return;
     hipLaunchKernelGGL(k_flag_cut_ties, dim3((nq + 3) / 4), dim3(256), 0, s, slab, q_stride, q_total, nq, K,
-                       sel_vals, sel_pos, only, tflag, fixed_n, inside);
+                       sel_vals, sel_pos, tflag, fixed_n, inside);
 }
 
 // ------------------------------------------------------------------------------------
