@@ -764,6 +764,11 @@ class GammaHip:
         default): it refuses one.  Independent of set_flat_narrow_rows."""
         self._ck(self.L.gamma_hip_set_flat_sq8_rows(self.h, 1 if on else 0), "set_flat_sq8_rows")
 
+    def set_ivfflat_sq8_rows(self, on=True):
+        """True: ivfflat_search serves an sq8 raw store (byte-identical to an fp32 store of the decoded rows over the same
+        lists); False (the default): it refuses one.  Independent of set_ivfflat_narrow_rows and set_flat_sq8_rows."""
+        self._ck(self.L.gamma_hip_set_ivfflat_sq8_rows(self.h, 1 if on else 0), "set_ivfflat_sq8_rows")
+
     def tie_stats(self, reset=False):
         out = np.zeros(3, np.int64)
         self._ck(self.L.gamma_hip_tie_stats(self.h, _p(out, _lib.i64p), 1 if reset else 0), "tie_stats")

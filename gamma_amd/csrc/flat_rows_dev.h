@@ -173,6 +173,52 @@ __device__ __forceinline__ void row_pair_load(const Row* __restrict__ rowp, int 
     }
 }
 
+// The same pair of threads over sq8 rows with the decode table staged in LDS by the workgroup (the list-major IVFFLAT scan,
+// ivfflat.hip: a persistent kernel, one table for every work unit).  Two steps, so that a reader can put its barriers between
+// them: row_pair_codes asks for the row's 16-byte loads and keeps each thread's two dwords of every load (D / 8 registers);
+// row_pair_decode_lds turns them into the D / 2 decoded values, 16 elements at a time, each step with four 16-byte LDS reads
+// of ITS table entries -- never the whole table in registers in front of the first decode, which is what the compiler made
+// of row_pair_load's global table loads in k_pairwise_lds<., 128> (178 VGPRs against 110).
+// s_tab: the entries of the D elements at rowp, {step, vmin} pairs, as D / 2 float4.  The values are row_pair_load's.
+template <int D>
+__device__ __forceinline__ void row_pair_codes(const sq8_t* __restrict__ rowp, int half, uint32_t* c0, uint32_t* c1) {
+    const uint4* yp = reinterpret_cast<const uint4*>(rowp);
+#pragma unroll
+    for (int i = 0; i < D / 16; i++) {
+        const uint4 v = yp[i];
+        const uint32_t vx = v.x, vy = v.y, vz = v.z, vw = v.w;
+        c0[i] = half ? vy : vx;
+        c1[i] = half ? vw : vz;
+    }
+}
+template <int D>
+__device__ __forceinline__ void row_pair_decode_lds(const uint32_t* c0, const uint32_t* c1, int half, f32x2* yr,
+                                                    const float4* s_tab) {
+#pragma unroll
+    for (int i = 0; i < D / 16; i++) {
+        float f[8];
+        row_dword_f<sq8_t>(c0[i], f);
+        row_dword_f<sq8_t>(c1[i], f + 4);
+        // f[0..3]: elements 16 i + 4 half + 0..3 (float4 8 i + 2 half of the table), f[4..7]: 8 elements further on
+        const float4* tp = s_tab + 8 * i + 2 * half;
+        const float4 t0 = tp[0], t1 = tp[1], t2 = tp[4], t3 = tp[5];
+        f[0] = sq8_dec(f[0], t0.x, t0.y); f[1] = sq8_dec(f[1], t0.z, t0.w);
+        f[2] = sq8_dec(f[2], t1.x, t1.y); f[3] = sq8_dec(f[3], t1.z, t1.w);
+        f[4] = sq8_dec(f[4], t2.x, t2.y); f[5] = sq8_dec(f[5], t2.z, t2.w);
+        f[6] = sq8_dec(f[6], t3.x, t3.y); f[7] = sq8_dec(f[7], t3.z, t3.w);
+        // one step's 16 table registers at a time.  The empty statement makes the step's values exist HERE: left to itself the
+        // compiler keeps every step's LDS reads where they are and sinks the arithmetic behind the reader's next barrier, the
+        // whole table in registers in between (k_ivfflat_lm<., 128, sq8_t>: 182 VGPRs); the fence keeps the next step's reads
+        // behind this one
+        asm volatile("" : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3]), "+v"(f[4]), "+v"(f[5]), "+v"(f[6]), "+v"(f[7]));
+        __builtin_amdgcn_sched_barrier(0);
+        yr[4 * i] = f32x2{f[0], f[1]};
+        yr[4 * i + 1] = f32x2{f[2], f[3]};
+        yr[4 * i + 2] = f32x2{f[4], f[5]};
+        yr[4 * i + 3] = f32x2{f[6], f[7]};
+    }
+}
+
 // ---- the decode-table entries of 8 consecutive elements (the matrix-pipe filters: a lane's elements of a k step) ----
 // Empty and free for the other row types.  j0 % 8 == 0: the 8 entries are 64 aligned bytes.
 template <class Row> struct Tab8 {};

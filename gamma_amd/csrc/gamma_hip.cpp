@@ -301,6 +301,13 @@ int gamma_hip_set_flat_sq8_rows(gamma_hip_index* h, int on) {
     return GAMMA_HIP_OK;
 }
 
+int gamma_hip_set_ivfflat_sq8_rows(gamma_hip_index* h, int on) {
+    if (!h) return GAMMA_HIP_EINVAL;
+    SearchLock lk(h);
+    h->ivfflat_sq8_rows = on != 0;
+    return GAMMA_HIP_OK;
+}
+
 int gamma_hip_tie_stats(gamma_hip_index* h, int64_t* out3, int reset) {
     if (!h || !out3) return GAMMA_HIP_EINVAL;
     SearchLock lk(h);

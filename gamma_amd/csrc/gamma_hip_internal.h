@@ -381,6 +381,7 @@ struct gamma_hip_index {
     bool flat_narrow_rows = false;   // gamma_hip_set_flat_narrow_rows: flat search serves a float16 / uint8 / int8 raw store
     bool ivfflat_narrow_rows = false;   // gamma_hip_set_ivfflat_narrow_rows: the same for the IVFFLAT search
     bool flat_sq8_rows = false;      // gamma_hip_set_flat_sq8_rows: flat search serves an sq8 raw store
+    bool ivfflat_sq8_rows = false;   // gamma_hip_set_ivfflat_sq8_rows: the same for the IVFFLAT search
     int small_presel = 0;      // 0: pre-selection by estimate, > 0: always, that many slices (tests)
     // multi-vector documents (VIDMgr::VID2DocID, vector/raw_vector_common.h:90-95): docid of every vid, host + device;
     // empty = single-vector documents, docid == vid.  Every delete-bitmap / filter test goes through it.

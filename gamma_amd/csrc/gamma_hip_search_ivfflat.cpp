@@ -72,8 +72,8 @@ int ivfflat_search_device_locked(H* h, const gamma_hip_search_params* p, int nq,
                                  float* d_distances, int64_t* d_labels) {
     if (h->raw_sparse) return fail(h, GAMMA_HIP_EUNSUPPORTED, "the raw store holds this shard's rows only (gamma_hip_raw_put)");
     // (a narrow store is served only after gamma_hip_set_ivfflat_narrow_rows: the refusal is what every caller had before;
-    //  an sq8 store whatever the switch says: the scan decodes nothing)
-    if (!raw_store_served(h, h->ivfflat_narrow_rows, false)) return raw_store_refuse(h, "IVFFLAT search");
+    //  an sq8 store only after gamma_hip_set_ivfflat_sq8_rows, whatever the other switches say)
+    if (!raw_store_served(h, h->ivfflat_narrow_rows, h->ivfflat_sq8_rows)) return raw_store_refuse(h, "IVFFLAT search");
     GH_TRY(check_params(h, p, nq, k));
     gamma_hip_search_params pp;
     GH_TRY(resolve_ties(h, p, &pp, p->nprobe <= gh::tie_replay_max_probes(), "exact_ties = 1 with nprobe > 1024"));

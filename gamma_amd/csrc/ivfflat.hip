@@ -11,6 +11,9 @@
 // in registers; every other d % 16 == 0 up to 4096: k_ivfflat_lms below, the row walked in slabs.
 // Row: the raw store's element type (float; uint16_t = IEEE binary16, uint8_t, int8_t with gamma_hip_set_ivfflat_narrow_rows).  A
 // narrow row is widened -- exactly -- as the pair of threads loads it (row_pair_load, flat_rows_dev.h) and is fp32 from then on.
+// sq8_t (gamma_hip_set_ivfflat_sq8_rows): rows of scalar-quantised codes, loaded like uint8 rows and DECODED as they are loaded,
+// w = vmin[j] + code * step[j], from the store's table (tab: RowTab<Row>, empty for every other type) staged in LDS: once per
+// workgroup in k_ivfflat_lm, per piece beside the query elements in k_ivfflat_lms.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -114,13 +117,22 @@ __global__ __launch_bounds__(256) void k_ivfflat_lm(const float* __restrict__ x,
                                                     const int* __restrict__ inv, const int* __restrict__ ustart,
                                                     int nlist, int64_t q_stride,
                                                     float* __restrict__ out, const FilterDesc* __restrict__ ftab,
-                                                    int need_filter, float min_score, float max_score) {
+                                                    int need_filter, float min_score, float max_score, RowTab<Row> tab) {
     __shared__ float4 s_x[FL_QT * D / 4];
     __shared__ int s_q[FL_QT];
     __shared__ int s_off[FL_QT];
     const int tid = threadIdx.x, half = tid & 1;
     const float sentinel = L2 ? INFINITY : -INFINITY;
     const int nunits = ustart[nlist];
+    // sq8 rows: the decode table -- D {step, vmin} pairs, the same for every unit of this persistent kernel -- is staged in
+    // LDS once per workgroup; every unit's row decodes from there, 16 elements per step (row_pair_decode_lds)
+    const float4* s_tab = nullptr;
+    if constexpr (RowKind<Row>::sq8) {
+        __shared__ float4 s_t[D / 2];
+        for (int e = tid; e < D / 2; e += 256) s_t[e] = reinterpret_cast<const float4*>(tab.t)[e];
+        s_tab = s_t;
+        __syncthreads();
+    }
     // a work unit = (list, 128-row chunk, FL_UT tiles of 32 of the queries probing the list): popular and long lists are cut
     // into many units, so the launch is balanced whatever the data looks like
     for (int u = blockIdx.x; u < nunits; u += gridDim.x) {
@@ -144,7 +156,13 @@ __global__ __launch_bounds__(256) void k_ivfflat_lm(const float* __restrict__ x,
         bool live = inrow && id >= 0 && vid < nraw;   // id < 0: bit 63, superseded by an Update
         if (need_filter && live) live = is_valid_doc(ftab[0], vid);
         f32x2 yr[D / 4];
-        row_pair_load<Row, D>(raw + (live ? vid : 0) * D, half, yr);   // (narrow rows widen here, exactly: flat_rows_dev.h)
+        if constexpr (RowKind<Row>::sq8) {
+            uint32_t c0[D / 16], c1[D / 16];
+            row_pair_codes<D>(raw + (live ? vid : 0) * D, half, c0, c1);
+            row_pair_decode_lds<D>(c0, c1, half, yr, s_tab);   // (codes decode here: a multiply, then an add, fp32 from then on)
+        } else {
+            row_pair_load<Row, D>(raw + (live ? vid : 0) * D, half, yr);   // (narrow rows widen here, exactly: flat_rows_dev.h)
+        }
         for (int t0 = tq0; t0 < tq1; t0 += FL_QT) {
             const int nqt = min(FL_QT, tq1 - t0);
             __syncthreads();   // the previous tile has been consumed
@@ -211,15 +229,25 @@ __global__ __launch_bounds__(256) void k_ivfflat_lm(const float* __restrict__ x,
 // unrolled so that the accumulators are registers (a branch per query on the wave-uniform tile length).
 template <bool L2, class Row, int LEN>
 __device__ __forceinline__ void lms_piece(const Row* __restrict__ rowp, const float* __restrict__ x, int d, int e0, int half,
-                                          int tid, int nqt, const int* s_q, float4* s_x, f32x2 (&acc)[FS_QT][2]) {
+                                          int tid, int nqt, const int* s_q, float4* s_x, f32x2 (&acc)[FS_QT][2],
+                                          RowTab<Row> tab, float4* s_tab) {
     f32x2 yr[LEN / 4];
-    row_pair_load<Row, LEN>(rowp + e0, half, yr);   // in flight while the tile's queries are staged
+    constexpr bool SQ8 = RowKind<Row>::sq8;
+    // sq8 rows: the codes are in flight while the tile's queries AND the piece's table entries (elements e0 .. e0 + LEN - 1,
+    // LEN / 2 float4) are staged under the same two barriers; the decode reads the entries from LDS behind the second one
+    uint32_t c0[SQ8 ? LEN / 16 : 1], c1[SQ8 ? LEN / 16 : 1];
+    if constexpr (SQ8) row_pair_codes<LEN>(rowp + e0, half, c0, c1);
+    else row_pair_load<Row, LEN>(rowp + e0, half, yr);   // in flight while the tile's queries are staged
     __syncthreads();   // the previous piece has been consumed (first piece: s_q is written)
     for (int e = tid; e < nqt * (LEN / 4); e += 256) {
         const int qi = e / (LEN / 4), c = e - qi * (LEN / 4);
         s_x[e] = reinterpret_cast<const float4*>(x + (int64_t)s_q[qi] * d + e0)[c];
     }
+    if constexpr (SQ8) {
+        for (int e = tid; e < LEN / 2; e += 256) s_tab[e] = reinterpret_cast<const float4*>(tab.t + e0)[e];
+    }
     __syncthreads();
+    if constexpr (SQ8) row_pair_decode_lds<LEN>(c0, c1, half, yr, s_tab);
 #pragma unroll
     for (int qi = 0; qi < FS_QT; qi++) {
         if (qi < nqt) {
@@ -260,10 +288,15 @@ __global__ __launch_bounds__(256) void k_ivfflat_lms(const float* __restrict__ x
                                                      const int* __restrict__ inv, const int* __restrict__ ustart,
                                                      int nlist, int64_t q_stride,
                                                      float* __restrict__ out, const FilterDesc* __restrict__ ftab,
-                                                     int need_filter, float min_score, float max_score) {
+                                                     int need_filter, float min_score, float max_score, RowTab<Row> tab) {
     __shared__ float4 s_x[FS_QT * FS_SLAB / 4];
     __shared__ int s_q[FS_QT];
     __shared__ int s_off[FS_QT];
+    float4* s_tab = nullptr;   // sq8 rows: the table entries of the piece at hand (lms_piece), 1 KB
+    if constexpr (RowKind<Row>::sq8) {
+        __shared__ float4 s_t[FS_SLAB / 2];
+        s_tab = s_t;
+    }
     const int tid = threadIdx.x, half = tid & 1;
     const float sentinel = L2 ? INFINITY : -INFINITY;
     const int nunits = ustart[nlist];
@@ -297,16 +330,16 @@ __global__ __launch_bounds__(256) void k_ivfflat_lms(const float* __restrict__ x
 #pragma unroll
         for (int qi = 0; qi < FS_QT; qi++) acc[qi][0] = acc[qi][1] = f32x2{0.f, 0.f};
         int e0 = 0;
-        for (; e0 + FS_SLAB <= d; e0 += FS_SLAB) lms_piece<L2, Row, FS_SLAB>(rowp, x, d, e0, half, tid, nqt, s_q, s_x, acc);
+        for (; e0 + FS_SLAB <= d; e0 += FS_SLAB) lms_piece<L2, Row, FS_SLAB>(rowp, x, d, e0, half, tid, nqt, s_q, s_x, acc, tab, s_tab);
         if (d - e0 >= 64) {
-            lms_piece<L2, Row, 64>(rowp, x, d, e0, half, tid, nqt, s_q, s_x, acc);
+            lms_piece<L2, Row, 64>(rowp, x, d, e0, half, tid, nqt, s_q, s_x, acc, tab, s_tab);
             e0 += 64;
         }
         if (d - e0 >= 32) {
-            lms_piece<L2, Row, 32>(rowp, x, d, e0, half, tid, nqt, s_q, s_x, acc);
+            lms_piece<L2, Row, 32>(rowp, x, d, e0, half, tid, nqt, s_q, s_x, acc, tab, s_tab);
             e0 += 32;
         }
-        if (d - e0 >= 16) lms_piece<L2, Row, 16>(rowp, x, d, e0, half, tid, nqt, s_q, s_x, acc);
+        if (d - e0 >= 16) lms_piece<L2, Row, 16>(rowp, x, d, e0, half, tid, nqt, s_q, s_x, acc, tab, s_tab);
 #pragma unroll
         for (int qi = 0; qi < FS_QT; qi++) {
             if (qi < nqt) {
@@ -339,7 +372,7 @@ template <class Row>
 void launch_ivfflat_lm_t(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* probe, const int* pair_off,
                          const int64_t* list_off, const int* list_len, int nlist, const int64_t* ids, const Row* raw,
                          int64_t nraw, int64_t q_stride, float* out, const FilterDesc* ftab, int need_filter, float min_score,
-                         float max_score, void* scratch) {
+                         float max_score, void* scratch, RowTab<Row> tab = RowTab<Row>{}) {
     if (nq <= 0 || P <= 0) return;
     int* inv = static_cast<int*>(scratch);
     int* cnt = inv + (size_t)nq * P;
@@ -357,15 +390,15 @@ void launch_ivfflat_lm_t(hipStream_t s, bool l2, const float* x, int nq, int d, 
     if (sliced) {
         if (l2)
             hipLaunchKernelGGL((k_ivfflat_lms<true, Row>), dim3(grid), dim3(256), 0, s, x, d, P, pair_off, list_off, list_len, ids,
-                               raw, nraw, start, cnt, inv, ustart, nlist, q_stride, out, ftab, need_filter, min_score, max_score);
+                               raw, nraw, start, cnt, inv, ustart, nlist, q_stride, out, ftab, need_filter, min_score, max_score, tab);
         else
             hipLaunchKernelGGL((k_ivfflat_lms<false, Row>), dim3(grid), dim3(256), 0, s, x, d, P, pair_off, list_off, list_len, ids,
-                               raw, nraw, start, cnt, inv, ustart, nlist, q_stride, out, ftab, need_filter, min_score, max_score);
+                               raw, nraw, start, cnt, inv, ustart, nlist, q_stride, out, ftab, need_filter, min_score, max_score, tab);
         return;
     }
 #define GH_FL(LL, DD)                                                                                                   \
     hipLaunchKernelGGL((k_ivfflat_lm<LL, DD, Row>), dim3(grid), dim3(256), 0, s, x, P, pair_off, list_off, list_len, ids, \
-                       raw, nraw, start, cnt, inv, ustart, nlist, q_stride, out, ftab, need_filter, min_score, max_score)
+                       raw, nraw, start, cnt, inv, ustart, nlist, q_stride, out, ftab, need_filter, min_score, max_score, tab)
 #define GH_FLD(LL)                    \
     switch (d) {                      \
         case 128: GH_FL(LL, 128); break; \
@@ -387,7 +420,7 @@ void launch_ivfflat_lm(hipStream_t s, bool l2, const float* x, int nq, int d, in
     launch_ivfflat_lm_t<float>(s, l2, x, nq, d, P, probe, pair_off, list_off, list_len, nlist, ids, raw, nraw, q_stride, out, ftab,
                                need_filter, min_score, max_score, scratch);
 }
-// rows of any element type (gamma_hip_set_ivfflat_narrow_rows); fp32 rows: the launch above, the kernels it always ran
+// rows of any element type (gamma_hip_set_ivfflat_narrow_rows, _sq8_rows); fp32 rows: the launch above, the kernels it always ran
 void launch_ivfflat_lm(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* probe, const int* pair_off,
                        const int64_t* list_off, const int* list_len, int nlist, const int64_t* ids, const RowsRef& raw,
                        int64_t nraw, int64_t q_stride, float* out, const FilterDesc* ftab, int need_filter, float min_score,
@@ -402,7 +435,12 @@ void launch_ivfflat_lm(hipStream_t s, bool l2, const float* x, int nq, int d, in
             break;
         case 1: GH_FLR(uint16_t); break;
         case 2: GH_FLR(uint8_t); break;
-        default: GH_FLR(int8_t); break;
+        case 3: GH_FLR(int8_t); break;
+        case 4:   // (codes are never numbers: an sq8 store goes to the decoding kernels or nowhere)
+            launch_ivfflat_lm_t<sq8_t>(s, l2, x, nq, d, P, probe, pair_off, list_off, list_len, nlist, ids, raw.as<sq8_t>(), nraw,
+                                       q_stride, out, ftab, need_filter, min_score, max_score, scratch, row_tab<sq8_t>(raw.tab));
+            break;
+        default: break;
     }
 #undef GH_FLR
 }

@@ -341,7 +341,8 @@ void launch_small_tail(hipStream_t s, bool l2, const float* slab, int64_t q_stri
 void launch_ivfflat_scan(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* pair_off,
                          const int64_t* pair_base, const int64_t* ids, const float* raw, int64_t nraw, int64_t q_stride,
                          float* out, const FilterDesc* ftab, int need_filter, float min_score, float max_score);
-// ... over rows of any element type (a narrow row widens to fp32 exactly on load); element type 0 forwards to the launch above
+// ... over rows of any element type (a narrow row widens to fp32 exactly on load, an sq8 code is decoded with raw.tab); element
+// type 0 forwards to the launch above; the same for launch_ivfflat_lm below
 void launch_ivfflat_scan(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* pair_off,
                          const int64_t* pair_base, const int64_t* ids, const RowsRef& raw, int64_t nraw, int64_t q_stride,
                          float* out, const FilterDesc* ftab, int need_filter, float min_score, float max_score);

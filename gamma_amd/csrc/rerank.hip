@@ -10,6 +10,7 @@
 #include "block_utils.h"
 #include "device_math.h"
 #include "filter_dev.h"
+#include "flat_rows_dev.h"
 #include "kernels.h"
 #include "rerank_dev.h"
 #include "scan_dev.h"
@@ -614,6 +615,8 @@ void launch_rerank_topk_sq8(hipStream_t s, bool l2, const float* x, int nq, int 
 // ------------------------------------------------------------------------------------
 // Row: the raw store's element type (float; uint16_t = IEEE binary16, uint8_t, int8_t with gamma_hip_set_ivfflat_narrow_rows):
 // the row access is rerank_dist8, which widens a narrow row exactly and runs the same fma chain (rerank_dev.h), any d.
+// sq8_t (gamma_hip_set_ivfflat_sq8_rows): rerank_dist8_sq8 with the store's decode table (tab: RowTab<Row>, flat_rows_dev.h --
+// empty for every other type), the byte rows' loads and the decode in front of the same chain.
 template <bool L2, class Row = float>
 __global__ __launch_bounds__(256) void k_ivfflat_scan(const float* __restrict__ x, int d, int P,
                                                       const int* __restrict__ pair_off,
@@ -621,7 +624,7 @@ __global__ __launch_bounds__(256) void k_ivfflat_scan(const float* __restrict__ 
                                                       const int64_t* __restrict__ ids,
                                                       const Row* __restrict__ raw, int64_t nraw, int64_t q_stride,
                                                       float* __restrict__ out, const FilterDesc* __restrict__ ftab,
-                                                      int need_filter, float min_score, float max_score) {
+                                                      int need_filter, float min_score, float max_score, RowTab<Row> tab) {
     const int q = blockIdx.x / P, p = blockIdx.x - q * P;
     const int off = pair_off[(int64_t)q * (P + 1) + p], len = pair_off[(int64_t)q * (P + 1) + p + 1] - off;
     if (len <= 0) return;   // uniform
@@ -636,7 +639,11 @@ __global__ __launch_bounds__(256) void k_ivfflat_scan(const float* __restrict__ 
         const int64_t vid = id & 0x7fffffffffffffffLL;
         bool live = j < len && id >= 0 && vid < nraw;   // id < 0: bit 63, superseded by an Update
         if (need_filter && live) live = is_valid_doc(ftab[0], vid);
-        float dis = rerank_dist8<L2>(xq, raw + (live ? vid : 0) * d, d, l8, live);
+        float dis;
+        if constexpr (RowKind<Row>::sq8)
+            dis = rerank_dist8_sq8<L2>(xq, reinterpret_cast<const uint8_t*>(raw) + (live ? vid : 0) * d, tab.t, d, l8, live);
+        else
+            dis = rerank_dist8<L2>(xq, raw + (live ? vid : 0) * d, d, l8, live);
         if (l8 == 0 && j < len) {
             if (!live || !(dis <= max_score && dis >= min_score)) dis = sentinel;
             out[(int64_t)q * q_stride + off + j] = dis;
@@ -650,27 +657,28 @@ void launch_ivfflat_scan(hipStream_t s, bool l2, const float* x, int nq, int d, 
     const dim3 grid((unsigned)((int64_t)nq * P));
     if (l2)
         hipLaunchKernelGGL((k_ivfflat_scan<true>), grid, dim3(256), 0, s, x, d, P, pair_off, pair_base, ids, raw, nraw,
-                           q_stride, out, ftab, need_filter, min_score, max_score);
+                           q_stride, out, ftab, need_filter, min_score, max_score, RowTab<float>{});
     else
         hipLaunchKernelGGL((k_ivfflat_scan<false>), grid, dim3(256), 0, s, x, d, P, pair_off, pair_base, ids, raw, nraw,
-                           q_stride, out, ftab, need_filter, min_score, max_score);
+                           q_stride, out, ftab, need_filter, min_score, max_score, RowTab<float>{});
 }
 namespace {
 template <class Row>
 void launch_ivfflat_scan_t(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* pair_off,
                            const int64_t* pair_base, const int64_t* ids, const Row* raw, int64_t nraw, int64_t q_stride,
-                           float* out, const FilterDesc* ftab, int need_filter, float min_score, float max_score) {
+                           float* out, const FilterDesc* ftab, int need_filter, float min_score, float max_score,
+                           RowTab<Row> tab = RowTab<Row>{}) {
     if (nq <= 0 || P <= 0) return;
     const dim3 grid((unsigned)((int64_t)nq * P));
     if (l2)
         hipLaunchKernelGGL((k_ivfflat_scan<true, Row>), grid, dim3(256), 0, s, x, d, P, pair_off, pair_base, ids, raw, nraw,
-                           q_stride, out, ftab, need_filter, min_score, max_score);
+                           q_stride, out, ftab, need_filter, min_score, max_score, tab);
     else
         hipLaunchKernelGGL((k_ivfflat_scan<false, Row>), grid, dim3(256), 0, s, x, d, P, pair_off, pair_base, ids, raw, nraw,
-                           q_stride, out, ftab, need_filter, min_score, max_score);
+                           q_stride, out, ftab, need_filter, min_score, max_score, tab);
 }
 }  // namespace
-// rows of any element type (gamma_hip_set_ivfflat_narrow_rows); fp32 rows: the launch above, the kernels it always ran
+// rows of any element type (gamma_hip_set_ivfflat_narrow_rows, _sq8_rows); fp32 rows: the launch above, the kernels it always ran
 void launch_ivfflat_scan(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* pair_off,
                          const int64_t* pair_base, const int64_t* ids, const RowsRef& raw, int64_t nraw, int64_t q_stride,
                          float* out, const FilterDesc* ftab, int need_filter, float min_score, float max_score) {
@@ -687,10 +695,15 @@ void launch_ivfflat_scan(hipStream_t s, bool l2, const float* x, int nq, int d, 
             launch_ivfflat_scan_t(s, l2, x, nq, d, P, pair_off, pair_base, ids, raw.as<uint8_t>(), nraw, q_stride, out, ftab,
                                   need_filter, min_score, max_score);
             break;
-        default:
+        case 3:
             launch_ivfflat_scan_t(s, l2, x, nq, d, P, pair_off, pair_base, ids, raw.as<int8_t>(), nraw, q_stride, out, ftab,
                                   need_filter, min_score, max_score);
             break;
+        case 4:   // (codes are never numbers: an sq8 store goes to the decoding kernel or nowhere)
+            launch_ivfflat_scan_t(s, l2, x, nq, d, P, pair_off, pair_base, ids, raw.as<sq8_t>(), nraw, q_stride, out, ftab,
+                                  need_filter, min_score, max_score, row_tab<sq8_t>(raw.tab));
+            break;
+        default: break;
     }
 }
 

@@ -900,7 +900,7 @@ int GammaIVFPQHIPIndex::LoadSq8Ranges(const std::string &index_dir) {
   const std::string path = index_dir + "/raw_sq8.ranges";
   FILE *fp = fopen(path.c_str(), "rb");
   if (!fp) {
-    HLOG("raw_dtype = sq8 needs %s beside ivfpq.index (the ranges the rows were encoded with), and it is missing", path.c_str());
+    HLOG("raw_dtype = sq8 needs %s beside the index file (the ranges the rows were encoded with), and it is missing", path.c_str());
     return -1;
   }
   char magic[4] = {0, 0, 0, 0};
@@ -1003,8 +1003,46 @@ int RegisterHIPIVFFlatRows(HIPIVFFlatRowsFn fn) {
 }
 HIPIVFFlatRowsFn FindHIPIVFFlatRows() { return IVFFlatRows(); }
 
+namespace {
+HIPIVFFlatSq8RowsFn &IVFFlatSq8Rows() {
+  static HIPIVFFlatSq8RowsFn fn = nullptr;
+  return fn;
+}
+}  // namespace
+int RegisterHIPIVFFlatSq8Rows(HIPIVFFlatSq8RowsFn fn) {
+  IVFFlatSq8Rows() = fn;
+  return 0;
+}
+HIPIVFFlatSq8RowsFn FindHIPIVFFlatSq8Rows() { return IVFFlatSq8Rows(); }
+
 int GammaIVFFlatHIPIndex::ParseRawDtype(const std::string &model_parameters, int *et) {
-  return HIPParseRawDtype("HIPIVFFLAT", model_parameters, et);
+  *et = 0;
+  utils::JsonParser jp;
+  const bool parsed = model_parameters != "" && !jp.Parse(model_parameters.c_str());
+  std::string rdt;
+  const bool sq8 = parsed && !jp.GetString("raw_dtype", rdt) && !strcasecmp("sq8", rdt.c_str());
+  const bool has_key = parsed && jp.Contains("sq8_ranges");
+  if (!(sq8 && has_key)) {
+    // every other case: the answer shared with HIPFLAT, which rejects "sq8" -- alone and beside sq8_min / sq8_max, as before
+    if (HIPParseRawDtype("HIPIVFFLAT", model_parameters, et)) return -1;
+    if (has_key) {
+      HLOG("HIPIVFFLAT: sq8_ranges comes with \"raw_dtype\": \"sq8\" only");
+      *et = 0;
+      return -1;
+    }
+    return 0;
+  }
+  std::string rng;
+  if (jp.GetString("sq8_ranges", rng) || strcasecmp("trained", rng.c_str())) {
+    HLOG("HIPIVFFLAT: raw_dtype = sq8 needs \"sq8_ranges\": \"trained\" (per-dimension ranges learned by Indexing), the one value defined");
+    return -1;
+  }
+  if (jp.Contains("sq8_min") || jp.Contains("sq8_max")) {
+    HLOG("HIPIVFFLAT: raw_dtype = sq8 takes no sq8_min / sq8_max: its ranges are trained");
+    return -1;
+  }
+  *et = 4;
+  return 0;
 }
 
 int GammaIVFFlatHIPIndex::Init(const std::string &model_parameters, int indexing_size) {
@@ -1037,15 +1075,23 @@ int GammaIVFFlatHIPIndex::Init(const std::string &model_parameters, int indexing
   int et = 0;
   if (ParseRawDtype(model_parameters, &et)) return -1;
   // a narrow store needs its initialiser and the handle's switch; a build without one of them rejects the value
-  const HIPIVFFlatRowsFn ivfflat_rows = et ? FindHIPIVFFlatRows() : nullptr;
+  const bool narrow = et >= 1 && et <= 3;
+  const HIPIVFFlatRowsFn ivfflat_rows = narrow ? FindHIPIVFFlatRows() : nullptr;
   const HIPRawInitFn init_f16 = et == 1 ? FindHIPRawInitF16() : nullptr;
-  raw_i8_ops_ = et >= 2 ? FindHIPRawI8() : nullptr;
-  if (et && (!ivfflat_rows || (et == 1 ? !init_f16 : !raw_i8_ops_))) {
+  raw_i8_ops_ = et == 2 || et == 3 ? FindHIPRawI8() : nullptr;
+  if (narrow && (!ivfflat_rows || (et == 1 ? !init_f16 : !raw_i8_ops_))) {
     HLOG("HIPIVFFLAT: raw_dtype: this build of the plugin has no IVFFLAT search over float16 / uint8 / int8 rows");
     return -1;
   }
+  // (sq8: the store's entries that HIPIVFPQ's sq8 store registered, and the IVFFLAT search's switch for it)
+  const HIPIVFFlatSq8RowsFn ivfflat_sq8_rows = et == 4 ? FindHIPIVFFlatSq8Rows() : nullptr;
+  raw_sq8_ops_ = et == 4 ? FindHIPRawSq8() : nullptr;
+  if (et == 4 && (!ivfflat_sq8_rows || !raw_sq8_ops_)) {
+    HLOG("HIPIVFFLAT: raw_dtype: this build of the plugin has no IVFFLAT search over sq8 rows");
+    return -1;
+  }
   raw_f16_ = et == 1;
-  raw_i8_ = et >= 2 ? et - 1 : 0;
+  raw_i8_ = narrow && et >= 2 ? et - 1 : 0;
   if (!vector_) {
     HLOG("vector_ must be set before Init");
     return -1;
@@ -1061,9 +1107,17 @@ int GammaIVFFlatHIPIndex::Init(const std::string &model_parameters, int indexing
   members_.assign(1, h_);   // one GPU (the sharded group serves HIPIVFPQ)
   rc = gamma_hip_ivfflat_init(h_, d_, nlist_, metric_type_ == DistanceComputeType::L2 ? GAMMA_HIP_METRIC_L2 : GAMMA_HIP_METRIC_IP,
                               pa.bucket_init_size, pa.bucket_max_size);
-  if (!rc) rc = !et ? gamma_hip_raw_init(h_, d_) : et == 1 ? init_f16(h_, d_) : raw_i8_ops_->init(h_, d_, et == 3);
-  if (!rc && et) rc = ivfflat_rows(h_, 1);
-  if (!rc && et) {
+  if (!rc) rc = !et ? gamma_hip_raw_init(h_, d_) : et == 1 ? init_f16(h_, d_) : et == 4 ? raw_sq8_ops_->init(h_, d_)
+                                                                                         : raw_i8_ops_->init(h_, d_, et == 3);
+  if (!rc && narrow) rc = ivfflat_rows(h_, 1);
+  if (!rc && et == 4) {
+    rc = ivfflat_sq8_rows(h_, 1);
+    // brute_force_search on the trained model goes to the flat search over sq8 rows: its own switch, where the build has it
+    const HIPFlatSq8RowsFn flat_sq8_rows = FindHIPFlatSq8Rows();
+    narrow_brute_ = flat_sq8_rows != nullptr;
+    if (!rc && flat_sq8_rows) rc = flat_sq8_rows(h_, 1);
+  }
+  if (!rc && narrow) {
     // brute_force_search and the search of an untrained model go to the flat search: its own switch, where the build has it
     const HIPFlatRowsFn flat_rows = FindHIPFlatRows();
     narrow_brute_ = flat_rows != nullptr;
@@ -1112,6 +1166,15 @@ int GammaIVFFlatHIPIndex::Indexing() {   // IndexIVFFlat::train == the coarse k-
   std::vector<float> xt;
   size_t num = 0;
   if (TrainingSet(xt, num)) return -1;
+  if (raw_sq8_ops_) {
+    // "raw_dtype": "sq8": the store's per-dimension ranges from the training rows, before the coarse k-means and before any
+    // row is mirrored (a narrow store's mirror is written from Add on)
+    const int rc = raw_sq8_ops_->train(h_, (int64_t)num, xt.data());
+    if (rc) {
+      HLOG("sq8 range training failed: %s (%s)", gamma_hip_strerror(rc), gamma_hip_last_error(h_));
+      return -1;
+    }
+  }
   if (TrainCoarse(num, xt.data())) return -1;
   return gamma_hip_ivfflat_set_trained(h_, coarse_centroids_.data()) ? -1 : (is_trained_ = true, 0);
 }
@@ -1139,9 +1202,14 @@ int GammaIVFFlatHIPIndex::Search(RetrievalContext *retrieval_context, int n, con
   int rc;
   if ((cond && cond->brute_force_search) || !is_trained_) {
     // (the reference's IVFFLAT has no brute-force branch; an untrained model would crash there.  Same service as HIPIVFPQ.)
+    if (raw_sq8_ops_ && !is_trained_) {
+      HLOG("HIPIVFFLAT: the search of an untrained model is not available with raw_dtype = sq8 (it has no ranges and holds no row)");
+      return -1;
+    }
     if (!narrow_brute_) {
       HLOG("HIPIVFFLAT: brute_force_search (and the search of an untrained model) over raw_dtype = %s needs flat search over narrow "
-           "rows, which this build of the plugin does not have", raw_f16_ ? "float16" : raw_i8_ == 2 ? "int8" : "uint8");
+           "rows, which this build of the plugin does not have",
+           raw_sq8_ops_ ? "sq8" : raw_f16_ ? "float16" : raw_i8_ == 2 ? "int8" : "uint8");
       return -1;
     }
     if (EnsureRaw((int64_t)vector_->MetaInfo()->Size())) return -1;
@@ -1194,7 +1262,9 @@ int GammaIVFFlatHIPIndex::Dump(const std::string &dir) {
     f.codes[l].resize((size_t)len * f.code_size);
     for (int64_t i = 0; i < len; i++) memcpy(&f.codes[l][(size_t)i * f.code_size], sv.Get((int)i), f.code_size);
   }
-  return WriteIvFl(index_dir + "/ivfflat.index", f, indexed_vec_count_) ? -1 : 0;
+  if (WriteIvFl(index_dir + "/ivfflat.index", f, indexed_vec_count_)) return -1;
+  if (raw_sq8_ops_ && DumpSq8Ranges(index_dir)) return -1;   // a side file: ivfflat.index stays what the fp32 model writes
+  return 0;
 }
 
 int GammaIVFFlatHIPIndex::Load(const std::string &dir) {
@@ -1206,9 +1276,11 @@ int GammaIVFFlatHIPIndex::Load(const std::string &dir) {
   int indexed = 0;
   if (ReadIvFl(path, &f, &indexed)) return -1;
   if (f.d != d_ || (int)f.nlist != nlist_ || indexed < 0 || indexed > (int)vector_->MetaInfo()->Size()) return -1;
-  if (raw_i8_) {
-    // a byte model: a pass over the rows it is about to mirror with the acceptance predicate first, so that a refused row
-    // leaves the model as it was (untrained, no lists)
+  // "raw_dtype": "sq8": the ranges come back before anything of the model changes and before the mirror is re-encoded below
+  if (raw_sq8_ops_ && LoadSq8Ranges(dir + "/" + vector_->MetaInfo()->AbsoluteName())) return -1;
+  if (raw_i8_ || raw_sq8_ops_) {
+    // a byte or sq8 model: a pass over the rows it is about to mirror with the acceptance predicate first, so that a refused
+    // row leaves the model as it was (untrained, no lists)
     std::lock_guard<std::mutex> g(raw_mu_);
     for (int64_t i0 = raw_uploaded_; i0 < indexed; i0 += 65536) {
       const int64_t nb = std::min<int64_t>(65536, indexed - i0);

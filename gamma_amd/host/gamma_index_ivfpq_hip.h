@@ -109,6 +109,12 @@ int HIPParseRawDtype(const char *model, const std::string &model_parameters, int
 typedef int (*HIPIVFFlatRowsFn)(gamma_hip_index *h, int on);
 int RegisterHIPIVFFlatRows(HIPIVFFlatRowsFn fn);
 HIPIVFFlatRowsFn FindHIPIVFFlatRows();
+// HIPIVFFLAT's "raw_dtype": "sq8" (with "sq8_ranges": "trained"): a switch of its own (gamma_hip_set_ivfflat_sq8_rows), registered
+// by gamma_index_ivfflat_sq8_hip.cc -- the only host file that names it; the store's entries are HIPRawSq8Ops above.  Without
+// either HIPIVFFLAT::Init rejects the value.
+typedef int (*HIPIVFFlatSq8RowsFn)(gamma_hip_index *h, int on);
+int RegisterHIPIVFFlatSq8Rows(HIPIVFFlatSq8RowsFn fn);
+HIPIVFFlatSq8RowsFn FindHIPIVFFlatSq8Rows();
 
 // "opq": the rotation's entries of the C ABI (gamma_hip_opq_train / _set / _get / _apply) reach the model through this table,
 // registered at static-initialisation time by gamma_index_ivfpq_opq_hip.cc -- the only host file that names them.  A build of
@@ -224,7 +230,7 @@ class GammaIVFPQHIPIndex : public RetrievalModel {
   const HIPRawI8Ops *raw_i8_ops_ = nullptr;
   bool RowsStorable(const char *what, const float *x, int64_t nrows);   // byte / sq8 store: one log line for the first refused value
   // "raw_dtype": "sq8": likewise.  The ranges are trained by Indexing() before the first row is mirrored, written by Dump to the
-  // side file raw_sq8.ranges beside ivfpq.index and set again by Load before the mirror is re-encoded.
+  // side file raw_sq8.ranges beside ivfpq.index (HIPIVFFLAT: ivfflat.index) and set again by Load before the mirror is re-encoded.
   const HIPRawSq8Ops *raw_sq8_ops_ = nullptr;
   int DumpSq8Ranges(const std::string &index_dir);
   int LoadSq8Ranges(const std::string &index_dir);
@@ -274,7 +280,10 @@ class GammaIVFFlatHIPIndex : public GammaIVFPQHIPIndex {
   int Dump(const std::string &dir) override;
   int Load(const std::string &dir) override;
   int SetTrainedCoarse(const float *coarse_centroids);
-  // the "raw_dtype" key of the model's parameters (HIPParseRawDtype)
+  // the "raw_dtype" key of the model's parameters: HIPParseRawDtype's answer, and *et = 4 for "sq8" together with
+  // "sq8_ranges": "trained" (case-insensitive; the ranges are learned by Indexing() and kept in raw_sq8.ranges beside
+  // ivfflat.index).  -1 and one log line for "sq8" without that key (as before), any other value of the key, the key beside
+  // another raw_dtype, and sq8_min / sq8_max (HIPFLAT's keys: this model's ranges are per dimension and trained)
   static int ParseRawDtype(const std::string &model_parameters, int *et);
 
  private:

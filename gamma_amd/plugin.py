@@ -133,10 +133,11 @@ def parse_flat_raw_dtype(s):
 
 
 def parse_ivfflat_raw_dtype(s):
-    """(rc, "float32", "float16", "uint8" or "int8") for the HIPIVFFLAT model parameters s"""
+    """(rc, "float32", "float16", "uint8", "int8" or "sq8") for the HIPIVFFLAT model parameters s; "sq8" only together with
+    "sq8_ranges": "trained" -- every rejection answers (-1, "float32")"""
     out = (C.c_int * 2)()
     load_host().gh_parse_ivfflat_raw_dtype(s.encode(), out)
-    return int(out[0]), ("float32", "float16", "uint8", "int8")[out[1]]
+    return int(out[0]), ("float32", "float16", "uint8", "int8", "sq8")[out[1]]
 
 
 def parse_retrieval_params(s):

@@ -231,10 +231,23 @@ int gamma_hip_ivfflat_scan_stats(gamma_hip_index* h, int64_t* out4, int reset);
  * and never folded into the query -- and every distance is fvec_L2sqr / fvec_inner_product of the fp32 query and the decoded
  * row, so distances and labels are byte-identical to those of an fp32 store that holds the decoded rows, exact ties included
  * (DESIGN.md section 20).  The reference has no scalar-quantised flat model; the yardstick is its flat search
- * (gamma_index_flat.cc:118-300) over the rows the store holds.  Nothing else changes: IVFFLAT search, the shard / merge /
- * export entries, gamma_hip_raw_put / _raw_drop, the combining queue and a sparse store keep refusing an sq8 store, and an
- * fp32, float16 or byte store is served or refused as before whatever this switch says. */
+ * (gamma_index_flat.cc:118-300) over the rows the store holds.  Nothing else changes: IVFFLAT search (a switch of its own,
+ * below), the shard / merge / export entries, gamma_hip_raw_put / _raw_drop, the combining queue and a sparse store keep
+ * refusing an sq8 store, and an fp32, float16 or byte store is served or refused as before whatever this switch says. */
 int gamma_hip_set_flat_sq8_rows(gamma_hip_index* h, int on);
+/* IVFFLAT search over a scalar-quantised raw store (gamma_hip_raw_init_sq8); a switch of its own, independent of
+ * gamma_hip_set_ivfflat_narrow_rows and gamma_hip_set_flat_sq8_rows.  on: 0 (default) = gamma_hip_ivfflat_search and
+ * _ivfflat_search_device refuse an sq8 store with GAMMA_HIP_EUNSUPPORTED, as before and whatever the two other switches say;
+ * 1 = both serve it, on every path (small path, list-major scan in both forms, pair scan, list masks, exact ties on and off,
+ * score window, delete bitmap, filters, vid -> doc map, entries with bit 63): every code is decoded as it is loaded,
+ * w = vmin[j] + float(code) * step[j] -- a multiply, then an add, each rounded in fp32, never an fma and never folded into
+ * the query -- and is the scanner's yj (GammaIVFFlatScanner1::scan_codes, index/impl/gamma_index_ivfflat.h:52-75) from then
+ * on, so distances and labels are byte-identical to those of an fp32 store that holds the decoded rows over the same lists,
+ * exact ties included.  Only the store is quantised: coarse assignment sees the caller's fp32 rows.
+ * Nothing else changes: the shard / merge / export entries, gamma_hip_raw_put / _raw_drop, the combining queue and a sparse
+ * store keep refusing an sq8 store, and an fp32, float16 or byte store is served or refused as before whatever this switch
+ * says. */
+int gamma_hip_set_ivfflat_sq8_rows(gamma_hip_index* h, int on);
 /* out3 = {coarse rows redone, queries whose recall_num cut went through a tie, queries replayed} since creation
  * or the last reset; meaningful with exact ties on */
 int gamma_hip_tie_stats(gamma_hip_index* h, int64_t* out3, int reset);
@@ -356,7 +369,8 @@ int gamma_hip_raw_i8_check(const float* x, int64_t n, int is_signed, int64_t* fi
  * so does a writer called with n > 0 before the ranges exist.  gamma_hip_raw_gets returns decoded rows.  The element type is
  * fixed at the first init.  Served: gamma_hip_ivfpq_search and its device-pointer forms (8-bit, 4-bit, OPQ handles).
  * GAMMA_HIP_EUNSUPPORTED: gamma_hip_raw_put / _raw_drop, flat and IVFFLAT search (whatever gamma_hip_set_flat_narrow_rows /
- * _set_ivfflat_narrow_rows say), gamma_hip_ivfpq_shard_exact / _shard_export_exact, _merge_rerank / _merge_replay with has_rank
+ * _set_ivfflat_narrow_rows say; each serves an sq8 store after its own switch, gamma_hip_set_flat_sq8_rows /
+ * _set_ivfflat_sq8_rows), gamma_hip_ivfpq_shard_exact / _shard_export_exact, _merge_rerank / _merge_replay with has_rank
  * and no travelled distances. */
 int gamma_hip_raw_init_sq8(gamma_hip_index* h, int d);
 /* The ranges of an sq8 store: d floats each.  set is allowed only while the store holds no row (after the init, or after
