@@ -219,6 +219,18 @@ SYMBOLS = {
                                                C.c_void_p, C.c_void_p, C.c_void_p]),
     "gamma_hip_ivfpq_merge_replay": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gamma_hip_ivfflat_coarse_device": (C.c_int, [C.c_void_p, C.POINTER(SearchParams), C.c_int, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p]),
+    "gamma_hip_ivfflat_search_shard": (C.c_int, [C.c_void_p, C.POINTER(SearchParams), C.c_int, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "gamma_hip_ivfflat_shard_export_rows": (C.c_int, [C.c_void_p, C.POINTER(SearchParams), C.c_int, C.c_void_p, i64p]),
+    "gamma_hip_ivfflat_shard_export": (C.c_int, [C.c_void_p, C.POINTER(SearchParams), C.c_int, C.c_void_p, C.c_void_p, C.c_int64,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gamma_hip_ivfflat_merge": (C.c_int, [C.c_void_p, C.POINTER(SearchParams), C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                          C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "gamma_hip_ivfflat_merge_replay": (C.c_int, [C.c_void_p, C.POINTER(SearchParams), C.c_int, C.c_int, C.c_void_p, C.c_int64,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p]),
     "gamma_hip_set_deferred_replay": (C.c_int, [C.c_void_p, C.c_int]),
     "gamma_hip_join": (C.c_int, [C.c_void_p]),
     "gamma_hip_group_set_placement": (C.c_int, [C.c_void_p, C.c_int]),
@@ -236,6 +248,9 @@ SYMBOLS = {
     "gamma_hip_group_ivfpq_search": (C.c_int, [C.c_void_p, C.POINTER(SearchParams), C.c_int, f32p, C.c_int, f32p, i64p]),
     "gamma_hip_group_ivfpq_search_device": (C.c_int, [C.c_void_p, C.POINTER(SearchParams), C.c_int, C.c_void_p, C.c_int,
                                                       C.c_void_p, C.c_void_p]),
+    "gamma_hip_group_ivfflat_search": (C.c_int, [C.c_void_p, C.POINTER(SearchParams), C.c_int, f32p, C.c_int, f32p, i64p]),
+    "gamma_hip_group_ivfflat_search_device": (C.c_int, [C.c_void_p, C.POINTER(SearchParams), C.c_int, C.c_void_p, C.c_int,
+                                                        C.c_void_p, C.c_void_p]),
     "gamma_hip_group_total_mem_bytes": (C.c_int64, [C.c_void_p]),
     "gamma_hip_group_set_raw_placement": (C.c_int, [C.c_void_p, C.c_int]),
     "gamma_hip_group_raw_placement": (C.c_int, [C.c_void_p]),

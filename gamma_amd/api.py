@@ -703,6 +703,34 @@ class GammaHip:
         self._ck(self.L.gamma_hip_ivfpq_merge_replay(self.h, args.ref(), nshards, nf, d_x_slice, stride, d_vals_all, d_ids_all,
                                                      d_off_all, k, d_list, d_D, d_I), "merge_replay")
 
+    # IVFFLAT over list shards (include/gamma_hip.h): one handle per shard, all pointers are device addresses (ints).  The cut
+    # flags, the flag list and the gather are the generic entries above (ivfpq_shard_cut_flags, ivfpq_merge_set_shard_flags,
+    # ivfpq_merge_flagged, gather_rows): they serve an IVFFLAT handle as they are.
+    def ivfflat_coarse_device(self, d_x, nq, args, d_cdis, d_probe):
+        self._ck(self.L.gamma_hip_ivfflat_coarse_device(self.h, args.ref(), nq, d_x, d_cdis, d_probe), "ivfflat_coarse_device")
+
+    def ivfflat_search_shard(self, d_x, nq, d_cdis, d_probe, k, args, d_dis, d_ids):
+        self._ck(self.L.gamma_hip_ivfflat_search_shard(self.h, args.ref(), nq, d_x, d_cdis, d_probe, k, d_dis, d_ids),
+                 "ivfflat_search_shard")
+
+    def ivfflat_shard_export_rows(self, nf, d_probe_f, args):
+        out = np.zeros(1, dtype=np.int64)
+        self._ck(self.L.gamma_hip_ivfflat_shard_export_rows(self.h, args.ref(), nf, d_probe_f, _p(out, _lib.i64p)),
+                 "ivfflat_shard_export_rows")
+        return int(out[0])
+
+    def ivfflat_shard_export(self, nf, d_xf, d_probe_f, stride, args, d_vals, d_ids, d_off):
+        self._ck(self.L.gamma_hip_ivfflat_shard_export(self.h, args.ref(), nf, d_xf, d_probe_f, stride, d_vals, d_ids, d_off),
+                 "ivfflat_shard_export")
+
+    def ivfflat_merge(self, nshards, nq, k, args, d_all_dis, d_all_ids, q0, nq_local, d_D, d_I):
+        self._ck(self.L.gamma_hip_ivfflat_merge(self.h, args.ref(), nshards, nq, k, d_all_dis, d_all_ids, q0, nq_local, d_D, d_I),
+                 "ivfflat_merge")
+
+    def ivfflat_merge_replay(self, nshards, nf, d_x_slice, stride, d_vals_all, d_ids_all, d_off_all, k, args, d_list, d_D, d_I):
+        self._ck(self.L.gamma_hip_ivfflat_merge_replay(self.h, args.ref(), nshards, nf, d_x_slice, stride, d_vals_all, d_ids_all,
+                                                       d_off_all, k, d_list, d_D, d_I), "ivfflat_merge_replay")
+
     def debug_heap_stream(self, op, k, vals):
         """test hook: (array values, array ids, sorted values, sorted ids) of one heap fed with vals (gamma_hip.h)"""
         vals = _f32(vals).ravel()
@@ -982,6 +1010,21 @@ class GammaHipGroup:
         """queries / results in the memory of member 0's device (raw pointers); synchronous"""
         self._ck(self.L.gamma_hip_group_ivfpq_search_device(self.g, C.byref(args.p), nq, C.c_void_p(d_x), k, C.c_void_p(d_D),
                                                             C.c_void_p(d_I)), "group_search_device")
+
+    def ivfflat_search(self, x, k, args):
+        """GammaIVFFlatIndex::Search over the members (ivfflat_init on each): one handle's results at every rank"""
+        x = _f32(x)
+        nq = x.shape[0]
+        D = np.empty((nq, k), dtype=np.float32)
+        I = np.empty((nq, k), dtype=np.int64)
+        self._ck(self.L.gamma_hip_group_ivfflat_search(self.g, C.byref(args.p), nq, _p(x, _lib.f32p), k, _p(D, _lib.f32p),
+                                                       _p(I, _lib.i64p)), "group_ivfflat_search")
+        return D, I
+
+    def ivfflat_search_device(self, d_x, nq, k, args, d_D, d_I):
+        """queries / results in the memory of member 0's device (raw pointers); synchronous"""
+        self._ck(self.L.gamma_hip_group_ivfflat_search_device(self.g, C.byref(args.p), nq, C.c_void_p(d_x), k, C.c_void_p(d_D),
+                                                              C.c_void_p(d_I)), "group_ivfflat_search_device")
 
     def total_mem_bytes(self):
         return self.L.gamma_hip_group_total_mem_bytes(self.g)

@@ -70,4 +70,26 @@ __device__ __forceinline__ bool is_valid_doc(const FilterDesc& f, int64_t vid) {
     return true;
 }
 
+// The row of a list entry of the IVFFLAT scans (ivfflat.hip, rerank.hip k_ivfflat_scan) and whether it is scanned at all.
+// Dense store (SPARSE = false): the vector id IS the row.  Sparse store (gamma_hip_raw_put: rows sharded with their lists):
+// slot[vid] = the row HERE, -1 = held by another shard -- resolved ONCE per entry, where its id is loaded; an entry without a
+// row here is a filtered entry (it cannot occur for a list this handle holds) and nothing is read through it.  SPARSE is a
+// compile-time variant: the dense kernels are the instantiations they always were, slot / nslot unread.  *row is 0 for an
+// entry that is not scanned (the row the dead lanes of the dense kernels have always read).
+template <bool SPARSE>
+__device__ __forceinline__ bool entry_row(int64_t id, bool inrow, int64_t nraw, const int32_t* __restrict__ slot, int64_t nslot,
+                                          int need_filter, const FilterDesc* __restrict__ ftab, int64_t* row) {
+    const int64_t vid = id & 0x7fffffffffffffffLL;
+    bool live = inrow && id >= 0 && vid < (SPARSE ? nslot : nraw);   // id < 0: bit 63, superseded by an Update
+    if (need_filter && live) live = is_valid_doc(ftab[0], vid);
+    if constexpr (SPARSE) {
+        const int64_t r = live ? (int64_t)slot[vid] : -1;
+        live = r >= 0 && r < nraw;
+        *row = live ? r : 0;
+    } else {
+        *row = live ? vid : 0;
+    }
+    return live;
+}
+
 }  // namespace gh

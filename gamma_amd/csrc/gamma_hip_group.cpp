@@ -221,6 +221,12 @@ gamma_group_ext::MemberMarkFn& member_mark() {
     return fn;
 }
 
+// the IVFFLAT entries this file may not name either (gamma_hip_group_ext.h); null in a build without them
+const gamma_group_ext::IvfflatOps*& ivfflat_ops() {
+    static const gamma_group_ext::IvfflatOps* ops = nullptr;
+    return ops;
+}
+
 // src on device sd -> dst on device dd, ordered on stream s (a stream of device dd)
 hipError_t copy_between(void* dst, int dd, const void* src, int sd, size_t bytes, hipStream_t s) {
     if (bytes == 0) return hipSuccess;
@@ -239,6 +245,11 @@ int register_raw_ops(const RawOps* ops) {
 
 int register_member_mark(MemberMarkFn fn) {
     member_mark() = fn;
+    return 1;
+}
+
+int register_ivfflat_ops(const IvfflatOps* ops) {
+    ivfflat_ops() = ops;
     return 1;
 }
 
@@ -1101,6 +1112,248 @@ static int group_search(gamma_hip_group* g, const gamma_hip_search_params* p, in
     for (int i = 0; i < W; i++)
         if (rcs[i] != GAMMA_HIP_OK) return gfail(g, rcs[i], "member " + std::to_string(i) + ": " + errs[i]);
     return GAMMA_HIP_OK;
+}
+
+// ---- IVFFLAT (gamma_index_ivfflat.cc search_preassigned per member, faiss:IndexShards.cpp:283-345 for the merge) --------------
+// The IVFPQ path's sequence without re-rank and without the bound reduction: coarse quantizer of the own slice | assignment
+// exchanged | shard search of the whole batch over the owned lists (rows from the member's dense or sparse store) | the
+// [W][per][k] tables and cut flags of the own slice pulled | merge | tie phase in rounds of at most 256 flagged queries.
+// Same barriers, same go / no-go snapshots: a member that fails in a phase still arrives at every meeting point, and the call
+// returns that member's error.  The transport is device-to-device copies ordered by events, whatever the group's transport
+// setting says (gamma_hip_group_transport_note says so).  Every entry of the members this needs comes through the table of
+// gamma_hip_group_ext.h.
+static int group_ivfflat_search(gamma_hip_group* g, const gamma_hip_search_params* p, int nq, const float* x, int k,
+                                float* distances, int64_t* labels, bool on_device) {
+    if (!g || !p) return GAMMA_HIP_EINVAL;
+    if (nq < 0) return GAMMA_HIP_EINVAL;
+    if (k <= 0 || nq == 0) return GAMMA_HIP_OK;
+    if (!x || !distances || !labels) return GAMMA_HIP_EINVAL;
+    std::lock_guard<std::mutex> lk(g->mu);
+    const gamma_group_ext::IvfflatOps* ops = ivfflat_ops();
+    if (!ops) return gfail(g, GAMMA_HIP_EUNSUPPORTED, "ivfflat_search: the IVFFLAT search of the group is not built in");
+    if (g->owner.empty()) return gfail(g, GAMMA_HIP_EINVAL, "ivfflat_search: gamma_hip_group_set_owners first");
+    const int W = (int)g->m.size();
+    const int d = gamma_hip_ivfpq_dim(g->m[0]);
+    if (d <= 0) return gfail(g, GAMMA_HIP_EINVAL, "ivfflat_search: members not initialised");
+    const int P = p->nprobe;
+    if (P <= 0) return gfail(g, GAMMA_HIP_EINVAL, "ivfflat_search: nprobe out of range");
+    gamma_hip_search_params pp = *p;
+    if (pp.coarse_mode < 0) pp.coarse_mode = nq < 20 ? 0 : 1;   // resolved on the WHOLE call: the slices must agree
+    if (g->transport == 1 && !g->replicate && g->transport_note.find("IVFFLAT") == std::string::npos)
+        g->transport_note += std::string(g->transport_note.empty() ? "" : "; ") + "IVFFLAT search: peer copies (RCCL serves the IVFPQ search only)";
+    const int per = (nq + W - 1) / W;
+    std::vector<int> rcs(W, GAMMA_HIP_OK);
+    std::vector<std::string> errs(W);
+    std::vector<int64_t> rowmax(W, 0);
+    std::vector<int> nfl(W, 0);
+    std::vector<const int32_t*> lists(W, nullptr);
+    auto slice = [&](int i, int* q0, int* q1) {
+        *q0 = std::min(nq, i * per);
+        *q1 = std::min(nq, *q0 + per);
+    };
+    g->run([&](int i) {
+        gamma_hip_group::Member& b = g->mb[i];
+        gamma_hip_index* h = g->m[i];
+        hipStream_t s = (hipStream_t)gamma_hip_stream(h);
+        int q0, q1;
+        slice(i, &q0, &q1);
+        const int nql = q1 - q0;
+        int& rc = rcs[i];
+        auto hip = [&](hipError_t e, const char* what) {
+            if (e != hipSuccess && rc == GAMMA_HIP_OK) {
+                rc = e == hipErrorOutOfMemory ? GAMMA_HIP_ENOMEM : GAMMA_HIP_EDEVICE;
+                errs[i] = std::string(what) + ": " + hipGetErrorString(e);
+            }
+        };
+        auto abi = [&](int r) {
+            if (r != GAMMA_HIP_OK && rc == GAMMA_HIP_OK) {
+                rc = r;
+                errs[i] = std::string(gamma_hip_strerror(r)) + " (" + gamma_hip_last_error(h) + ")";
+            }
+        };
+        hip(hipSetDevice(g->dev[i]), "hipSetDevice");
+        if (g->replicate) {
+            // query-parallel over replicated lists: the member answers its slice with the single-handle search
+            if (nql <= 0 || rc != GAMMA_HIP_OK) return;
+            const bool local = on_device && g->dev[i] == g->dev[0];
+            const float* xs = x + (size_t)q0 * d;
+            float* Ds = distances + (size_t)q0 * k;
+            int64_t* Is = labels + (size_t)q0 * k;
+            if (!local) {
+                hip(b.x.ensure((size_t)nql * d * sizeof(float)), "alloc");
+                hip(b.D.ensure((size_t)nql * k * sizeof(float)), "alloc");
+                hip(b.I.ensure((size_t)nql * k * sizeof(int64_t)), "alloc");
+                if (rc != GAMMA_HIP_OK) return;
+                if (on_device) hip(copy_between(b.x.p, g->dev[i], xs, g->dev[0], (size_t)nql * d * sizeof(float), s), "queries to the member");
+                else hip(hipMemcpyAsync(b.x.p, xs, (size_t)nql * d * sizeof(float), hipMemcpyHostToDevice, s), "H2D queries");
+            }
+            if (rc == GAMMA_HIP_OK)
+                abi(ops->search_device(h, &pp, nql, local ? xs : b.x.as<float>(), k, local ? Ds : b.D.as<float>(),
+                                       local ? Is : b.I.as<int64_t>()));
+            if (rc == GAMMA_HIP_OK && !local) {
+                if (on_device) {
+                    hip(copy_between(Ds, g->dev[0], b.D.p, g->dev[i], (size_t)nql * k * sizeof(float), s), "results");
+                    hip(copy_between(Is, g->dev[0], b.I.p, g->dev[i], (size_t)nql * k * sizeof(int64_t), s), "results");
+                } else {
+                    hip(hipMemcpyAsync(Ds, b.D.p, (size_t)nql * k * sizeof(float), hipMemcpyDeviceToHost, s), "D2H");
+                    hip(hipMemcpyAsync(Is, b.I.p, (size_t)nql * k * sizeof(int64_t), hipMemcpyDeviceToHost, s), "D2H");
+                }
+            }
+            hip(hipStreamSynchronize(s), "sync");
+            return;
+        }
+        hip(b.x.ensure((size_t)nq * d * sizeof(float)), "alloc");
+        hip(b.cdis.ensure((size_t)W * per * P * sizeof(float)), "alloc");
+        hip(b.probe.ensure((size_t)W * per * P * sizeof(int32_t)), "alloc");
+        hip(b.rdis.ensure((size_t)nq * k * sizeof(float)), "alloc");
+        hip(b.rids.ensure((size_t)nq * k * sizeof(int64_t)), "alloc");
+        hip(b.all_dis.ensure((size_t)W * per * k * sizeof(float)), "alloc");
+        hip(b.all_ids.ensure((size_t)W * per * k * sizeof(int64_t)), "alloc");
+        hip(b.D.ensure((size_t)per * k * sizeof(float)), "alloc");
+        hip(b.I.ensure((size_t)per * k * sizeof(int64_t)), "alloc");
+        // 0. the whole batch to every member; coarse quantizer for the own slice
+        if (rc == GAMMA_HIP_OK) {
+            if (on_device) hip(copy_between(b.x.p, g->dev[i], x, g->dev[0], (size_t)nq * d * sizeof(float), s), "queries to the member");
+            else hip(hipMemcpyAsync(b.x.p, x, (size_t)nq * d * sizeof(float), hipMemcpyHostToDevice, s), "H2D queries");
+            if (nql > 0)
+                abi(ops->coarse_device(h, &pp, nql, b.x.as<float>() + (size_t)q0 * d, b.cdis.as<float>() + (size_t)q0 * P,
+                                       b.probe.as<int32_t>() + (size_t)q0 * P));
+            hip(hipEventRecord(b.ev_coarse, s), "record");
+        }
+        bool all_ok = g->bar.arrive(rc == GAMMA_HIP_OK);   // every member's assignment is on its stream
+        // 1. pull the other slices of the assignment; shard search of the whole batch
+        if (all_ok) {
+            for (int j = 0; j < W; j++) {
+                if (j == i) continue;
+                int a0, a1;
+                slice(j, &a0, &a1);
+                if (a1 <= a0) continue;
+                hip(hipStreamWaitEvent(s, g->mb[j].ev_coarse, 0), "wait");
+                hip(copy_between(b.cdis.as<float>() + (size_t)a0 * P, g->dev[i], g->mb[j].cdis.as<float>() + (size_t)a0 * P, g->dev[j],
+                                 (size_t)(a1 - a0) * P * sizeof(float), s), "assignment exchange");
+                hip(copy_between(b.probe.as<int32_t>() + (size_t)a0 * P, g->dev[i], g->mb[j].probe.as<int32_t>() + (size_t)a0 * P,
+                                 g->dev[j], (size_t)(a1 - a0) * P * sizeof(int32_t), s), "assignment exchange");
+            }
+            if (rc == GAMMA_HIP_OK)
+                abi(ops->search_shard(h, &pp, nq, b.x.as<float>(), b.cdis.as<float>(), b.probe.as<int32_t>(), k, b.rdis.as<float>(),
+                                      b.rids.as<int64_t>()));
+            hip(b.cutf.ensure((size_t)nq), "alloc");
+            if (rc == GAMMA_HIP_OK) abi(gamma_hip_ivfpq_shard_cut_flags(h, nq, b.cutf.as<uint8_t>()));
+            hip(b.cutall.ensure((size_t)W * per), "alloc");
+            hip(hipEventRecord(b.ev_scan, s), "record");
+        }
+        all_ok = g->bar.arrive(rc == GAMMA_HIP_OK);   // every member's tables are on its stream
+        // 2. the [W][per][k] tables and the cut flags of the own slice; 3. merge
+        if (all_ok && nql > 0) {
+            for (int j = 0; j < W; j++) {
+                if (j != i) hip(hipStreamWaitEvent(s, g->mb[j].ev_scan, 0), "wait");
+                hip(copy_between(b.all_dis.as<float>() + (size_t)j * per * k, g->dev[i], g->mb[j].rdis.as<float>() + (size_t)q0 * k,
+                                 g->dev[j], (size_t)nql * k * sizeof(float), s), "candidate exchange");
+                hip(copy_between(b.all_ids.as<int64_t>() + (size_t)j * per * k, g->dev[i], g->mb[j].rids.as<int64_t>() + (size_t)q0 * k,
+                                 g->dev[j], (size_t)nql * k * sizeof(int64_t), s), "candidate exchange");
+                hip(copy_between(b.cutall.as<uint8_t>() + (size_t)j * per, g->dev[i], g->mb[j].cutf.as<uint8_t>() + q0, g->dev[j],
+                                 (size_t)nql, s), "cut flags");
+            }
+            if (rc == GAMMA_HIP_OK) abi(gamma_hip_ivfpq_merge_set_shard_flags(h, b.cutall.as<uint8_t>()));
+            if (rc == GAMMA_HIP_OK)
+                abi(ops->merge(h, &pp, W, per, k, b.all_dis.as<float>(), b.all_ids.as<int64_t>(), 0, nql, b.D.as<float>(), b.I.as<int64_t>()));
+        }
+        // 4. exact ties across members: rounds of at most fcap flagged queries of one owner
+        {
+            int nf_i = 0;
+            const int32_t* list_i = nullptr;
+            if (all_ok && nql > 0 && rc == GAMMA_HIP_OK) abi(gamma_hip_ivfpq_merge_flagged(h, &nf_i, &list_i));
+            nfl[i] = rc == GAMMA_HIP_OK ? nf_i : 0;
+            lists[i] = list_i;
+            all_ok = g->bar.arrive(rc == GAMMA_HIP_OK);
+            int total = 0;
+            for (int j = 0; j < W; j++) total += nfl[j];
+            if (all_ok && total > 0) {
+                const int fcap = 256;
+                for (int o = 0; o < W; o++) {
+                    for (int f0 = 0; f0 < nfl[o]; f0 += fcap) {
+                        const int nf = std::min(fcap, nfl[o] - f0);
+                        if (i == o) {   // the flagged queries' vectors and assignment rows, compact
+                            hip(b.fx.ensure((size_t)nf * d * sizeof(float)), "alloc");
+                            hip(b.fpr.ensure((size_t)nf * P * sizeof(int32_t)), "alloc");
+                            if (rc == GAMMA_HIP_OK) {
+                                abi(gamma_hip_gather_rows(h, b.x.as<float>() + (size_t)q0 * d, d, lists[o] + f0, nf, b.fx.p));
+                                abi(gamma_hip_gather_rows(h, b.probe.as<int32_t>() + (size_t)q0 * P, P, lists[o] + f0, nf, b.fpr.p));
+                            }
+                            hip(hipEventRecord(b.ev_tie, s), "record");
+                        }
+                        bool ok2 = g->bar.arrive(rc == GAMMA_HIP_OK);   // the owner's compact inputs are on its stream
+                        gamma_hip_group::Member& ob = g->mb[o];
+                        hip(b.sx.ensure((size_t)nf * d * sizeof(float)), "alloc");
+                        hip(b.spr.ensure((size_t)nf * P * sizeof(int32_t)), "alloc");
+                        hip(b.ex_off.ensure((size_t)nf * (P + 1) * sizeof(int32_t)), "alloc");
+                        rowmax[i] = 0;
+                        if (ok2 && rc == GAMMA_HIP_OK) {
+                            if (i != o) hip(hipStreamWaitEvent(s, ob.ev_tie, 0), "wait");
+                            hip(copy_between(b.sx.p, g->dev[i], ob.fx.p, g->dev[o], (size_t)nf * d * sizeof(float), s), "tie inputs");
+                            hip(copy_between(b.spr.p, g->dev[i], ob.fpr.p, g->dev[o], (size_t)nf * P * sizeof(int32_t), s), "tie inputs");
+                            int64_t mine = 0;
+                            if (rc == GAMMA_HIP_OK) abi(ops->shard_export_rows(h, &pp, nf, b.spr.as<int32_t>(), &mine));
+                            rowmax[i] = mine;
+                        }
+                        ok2 = g->bar.arrive(rc == GAMMA_HIP_OK);   // every member's longest row is known
+                        int64_t stride = 4;
+                        for (int j = 0; j < W; j++) stride = std::max<int64_t>(stride, (rowmax[j] + 3) & ~(int64_t)3);
+                        hip(b.ex_vals.ensure((size_t)nf * stride * sizeof(float)), "alloc");
+                        hip(b.ex_ids.ensure((size_t)nf * stride * sizeof(int64_t)), "alloc");
+                        if (ok2 && rc == GAMMA_HIP_OK)
+                            abi(ops->shard_export(h, &pp, nf, b.sx.as<float>(), b.spr.as<int32_t>(), stride, b.ex_vals.as<float>(),
+                                                  b.ex_ids.as<int64_t>(), b.ex_off.as<int32_t>()));
+                        hip(hipStreamSynchronize(s), "sync");
+                        ok2 = g->bar.arrive(rc == GAMMA_HIP_OK);   // every member's export is complete
+                        if (i == o && ok2) {
+                            hip(b.av.ensure((size_t)W * nf * stride * sizeof(float)), "alloc");
+                            hip(b.ai.ensure((size_t)W * nf * stride * sizeof(int64_t)), "alloc");
+                            hip(b.ao.ensure((size_t)W * nf * (P + 1) * sizeof(int32_t)), "alloc");
+                            for (int j = 0; j < W && rc == GAMMA_HIP_OK; j++) {
+                                hip(copy_between(b.av.as<float>() + (size_t)j * nf * stride, g->dev[i], g->mb[j].ex_vals.p, g->dev[j],
+                                                 (size_t)nf * stride * sizeof(float), s), "exports");
+                                hip(copy_between(b.ai.as<int64_t>() + (size_t)j * nf * stride, g->dev[i], g->mb[j].ex_ids.p, g->dev[j],
+                                                 (size_t)nf * stride * sizeof(int64_t), s), "exports");
+                                hip(copy_between(b.ao.as<int32_t>() + (size_t)j * nf * (P + 1), g->dev[i], g->mb[j].ex_off.p, g->dev[j],
+                                                 (size_t)nf * (P + 1) * sizeof(int32_t), s), "exports");
+                            }
+                            if (rc == GAMMA_HIP_OK)
+                                abi(ops->merge_replay(h, &pp, W, nf, b.x.as<float>() + (size_t)q0 * d, stride, b.av.as<float>(),
+                                                      b.ai.as<int64_t>(), b.ao.as<int32_t>(), k, lists[o] + f0, b.D.as<float>(),
+                                                      b.I.as<int64_t>()));
+                            hip(hipStreamSynchronize(s), "sync");
+                        }
+                        (void)g->bar.arrive(rc == GAMMA_HIP_OK);   // the exports may be overwritten
+                    }
+                }
+            }
+        }
+        if (all_ok && nql > 0) {   // the slice's rows to the caller
+            if (rc == GAMMA_HIP_OK && on_device) {
+                hip(copy_between(distances + (size_t)q0 * k, g->dev[0], b.D.p, g->dev[i], (size_t)nql * k * sizeof(float), s), "results");
+                hip(copy_between(labels + (size_t)q0 * k, g->dev[0], b.I.p, g->dev[i], (size_t)nql * k * sizeof(int64_t), s), "results");
+            } else if (rc == GAMMA_HIP_OK) {
+                hip(hipMemcpyAsync(distances + (size_t)q0 * k, b.D.p, (size_t)nql * k * sizeof(float), hipMemcpyDeviceToHost, s), "D2H");
+                hip(hipMemcpyAsync(labels + (size_t)q0 * k, b.I.p, (size_t)nql * k * sizeof(int64_t), hipMemcpyDeviceToHost, s), "D2H");
+            }
+        }
+        hip(hipStreamSynchronize(s), "sync");
+        (void)g->bar.arrive(rc == GAMMA_HIP_OK);   // nobody is reading this member's tables any more
+    });
+    for (int i = 0; i < W; i++)
+        if (rcs[i] != GAMMA_HIP_OK) return gfail(g, rcs[i], "member " + std::to_string(i) + ": " + errs[i]);
+    return GAMMA_HIP_OK;
+}
+
+int gamma_hip_group_ivfflat_search(gamma_hip_group* g, const gamma_hip_search_params* p, int nq, const float* x, int k,
+                                   float* distances, int64_t* labels) {
+    return group_ivfflat_search(g, p, nq, x, k, distances, labels, false);
+}
+
+int gamma_hip_group_ivfflat_search_device(gamma_hip_group* g, const gamma_hip_search_params* p, int nq, const float* d_x, int k,
+                                          float* d_distances, int64_t* d_labels) {
+    return group_ivfflat_search(g, p, nq, d_x, k, d_distances, d_labels, true);
 }
 
 }  // extern "C"

@@ -108,16 +108,18 @@ __global__ __launch_bounds__(256) void k_inv_fill(const int* __restrict__ probe,
     if (l >= 0 && l < nlist && list_len[l] > 0) inv[start[l] + atomicAdd(&cur[l], 1)] = i;
 }
 
-template <bool L2, int D, class Row = float>
-__global__ __launch_bounds__(256) void k_ivfflat_lm(const float* __restrict__ x, int P, const int* __restrict__ pair_off,
-                                                    const int64_t* __restrict__ list_off,
-                                                    const int* __restrict__ list_len, const int64_t* __restrict__ ids,
-                                                    const Row* __restrict__ raw, int64_t nraw,
-                                                    const int* __restrict__ inv_start, const int* __restrict__ inv_cnt,
-                                                    const int* __restrict__ inv, const int* __restrict__ ustart,
-                                                    int nlist, int64_t q_stride,
-                                                    float* __restrict__ out, const FilterDesc* __restrict__ ftab,
-                                                    int need_filter, float min_score, float max_score, RowTab<Row> tab) {
+// SPARSE: the rows of a sparse store through its vid -> row table (entry_row, filter_dev.h); the dense kernels pass false
+template <bool L2, int D, class Row, bool SPARSE>
+__device__ __forceinline__ void ivfflat_lm_body(const float* __restrict__ x, int P, const int* __restrict__ pair_off,
+                                                const int64_t* __restrict__ list_off,
+                                                const int* __restrict__ list_len, const int64_t* __restrict__ ids,
+                                                const Row* __restrict__ raw, int64_t nraw,
+                                                const int* __restrict__ inv_start, const int* __restrict__ inv_cnt,
+                                                const int* __restrict__ inv, const int* __restrict__ ustart,
+                                                int nlist, int64_t q_stride,
+                                                float* __restrict__ out, const FilterDesc* __restrict__ ftab,
+                                                int need_filter, float min_score, float max_score, RowTab<Row> tab,
+                                                const int32_t* __restrict__ slot, int64_t nslot) {
     __shared__ float4 s_x[FL_QT * D / 4];
     __shared__ int s_q[FL_QT];
     __shared__ int s_off[FL_QT];
@@ -152,16 +154,15 @@ __global__ __launch_bounds__(256) void k_ivfflat_lm(const float* __restrict__ x,
         const bool inrow = j < len;
         int64_t id = -1;
         if (inrow) id = ids[base + j];
-        const int64_t vid = id & 0x7fffffffffffffffLL;
-        bool live = inrow && id >= 0 && vid < nraw;   // id < 0: bit 63, superseded by an Update
-        if (need_filter && live) live = is_valid_doc(ftab[0], vid);
+        int64_t rw;
+        const bool live = entry_row<SPARSE>(id, inrow, nraw, slot, nslot, need_filter, ftab, &rw);
         f32x2 yr[D / 4];
         if constexpr (RowKind<Row>::sq8) {
             uint32_t c0[D / 16], c1[D / 16];
-            row_pair_codes<D>(raw + (live ? vid : 0) * D, half, c0, c1);
+            row_pair_codes<D>(raw + rw * D, half, c0, c1);
             row_pair_decode_lds<D>(c0, c1, half, yr, s_tab);   // (codes decode here: a multiply, then an add, fp32 from then on)
         } else {
-            row_pair_load<Row, D>(raw + (live ? vid : 0) * D, half, yr);   // (narrow rows widen here, exactly: flat_rows_dev.h)
+            row_pair_load<Row, D>(raw + rw * D, half, yr);   // (narrow rows widen here, exactly: flat_rows_dev.h)
         }
         for (int t0 = tq0; t0 < tq1; t0 += FL_QT) {
             const int nqt = min(FL_QT, tq1 - t0);
@@ -214,6 +215,34 @@ __global__ __launch_bounds__(256) void k_ivfflat_lm(const float* __restrict__ x,
         }
         }
     }
+}
+template <bool L2, int D, class Row = float>
+__global__ __launch_bounds__(256) void k_ivfflat_lm(const float* __restrict__ x, int P, const int* __restrict__ pair_off,
+                                                    const int64_t* __restrict__ list_off,
+                                                    const int* __restrict__ list_len, const int64_t* __restrict__ ids,
+                                                    const Row* __restrict__ raw, int64_t nraw,
+                                                    const int* __restrict__ inv_start, const int* __restrict__ inv_cnt,
+                                                    const int* __restrict__ inv, const int* __restrict__ ustart,
+                                                    int nlist, int64_t q_stride,
+                                                    float* __restrict__ out, const FilterDesc* __restrict__ ftab,
+                                                    int need_filter, float min_score, float max_score, RowTab<Row> tab) {
+    ivfflat_lm_body<L2, D, Row, false>(x, P, pair_off, list_off, list_len, ids, raw, nraw, inv_start, inv_cnt, inv, ustart, nlist,
+                                       q_stride, out, ftab, need_filter, min_score, max_score, tab, nullptr, 0);
+}
+// fp32 rows of a sparse store (the list shards of a group whose rows live with their lists)
+template <bool L2, int D>
+__global__ __launch_bounds__(256) void k_ivfflat_lm_sp(const float* __restrict__ x, int P, const int* __restrict__ pair_off,
+                                                       const int64_t* __restrict__ list_off,
+                                                       const int* __restrict__ list_len, const int64_t* __restrict__ ids,
+                                                       const float* __restrict__ raw, int64_t nraw,
+                                                       const int* __restrict__ inv_start, const int* __restrict__ inv_cnt,
+                                                       const int* __restrict__ inv, const int* __restrict__ ustart,
+                                                       int nlist, int64_t q_stride,
+                                                       float* __restrict__ out, const FilterDesc* __restrict__ ftab,
+                                                       int need_filter, float min_score, float max_score,
+                                                       const int32_t* __restrict__ slot, int64_t nslot) {
+    ivfflat_lm_body<L2, D, float, true>(x, P, pair_off, list_off, list_len, ids, raw, nraw, inv_start, inv_cnt, inv, ustart, nlist,
+                                        q_stride, out, ftab, need_filter, min_score, max_score, RowTab<float>{}, slot, nslot);
 }
 
 // ---- rows of any d % 16 == 0 up to 4096: the row-sliced list-major kernel ------------------------------------------------
@@ -279,16 +308,17 @@ __device__ __forceinline__ void lms_piece(const Row* __restrict__ rowp, const fl
     }
 }
 
-template <bool L2, class Row>
-__global__ __launch_bounds__(256) void k_ivfflat_lms(const float* __restrict__ x, int d, int P, const int* __restrict__ pair_off,
-                                                     const int64_t* __restrict__ list_off,
-                                                     const int* __restrict__ list_len, const int64_t* __restrict__ ids,
-                                                     const Row* __restrict__ raw, int64_t nraw,
-                                                     const int* __restrict__ inv_start, const int* __restrict__ inv_cnt,
-                                                     const int* __restrict__ inv, const int* __restrict__ ustart,
-                                                     int nlist, int64_t q_stride,
-                                                     float* __restrict__ out, const FilterDesc* __restrict__ ftab,
-                                                     int need_filter, float min_score, float max_score, RowTab<Row> tab) {
+template <bool L2, class Row, bool SPARSE>
+__device__ __forceinline__ void ivfflat_lms_body(const float* __restrict__ x, int d, int P, const int* __restrict__ pair_off,
+                                                 const int64_t* __restrict__ list_off,
+                                                 const int* __restrict__ list_len, const int64_t* __restrict__ ids,
+                                                 const Row* __restrict__ raw, int64_t nraw,
+                                                 const int* __restrict__ inv_start, const int* __restrict__ inv_cnt,
+                                                 const int* __restrict__ inv, const int* __restrict__ ustart,
+                                                 int nlist, int64_t q_stride,
+                                                 float* __restrict__ out, const FilterDesc* __restrict__ ftab,
+                                                 int need_filter, float min_score, float max_score, RowTab<Row> tab,
+                                                 const int32_t* __restrict__ slot, int64_t nslot) {
     __shared__ float4 s_x[FS_QT * FS_SLAB / 4];
     __shared__ int s_q[FS_QT];
     __shared__ int s_off[FS_QT];
@@ -315,10 +345,9 @@ __global__ __launch_bounds__(256) void k_ivfflat_lms(const float* __restrict__ x
         const bool inrow = j < len;
         int64_t id = -1;
         if (inrow) id = ids[base + j];
-        const int64_t vid = id & 0x7fffffffffffffffLL;
-        bool live = inrow && id >= 0 && vid < nraw;   // id < 0: bit 63, superseded by an Update
-        if (need_filter && live) live = is_valid_doc(ftab[0], vid);
-        const Row* rowp = raw + (live ? vid : 0) * d;
+        int64_t rw;
+        const bool live = entry_row<SPARSE>(id, inrow, nraw, slot, nslot, need_filter, ftab, &rw);
+        const Row* rowp = raw + rw * d;
         __syncthreads();   // the previous unit has stored its distances: s_q, s_off are free
         if (tid < nqt) {
             const int pr = inv[inv_start[l] + tq0 + tid];
@@ -353,6 +382,43 @@ __global__ __launch_bounds__(256) void k_ivfflat_lms(const float* __restrict__ x
         }
     }
 }
+template <bool L2, class Row>
+__global__ __launch_bounds__(256) void k_ivfflat_lms(const float* __restrict__ x, int d, int P, const int* __restrict__ pair_off,
+                                                     const int64_t* __restrict__ list_off,
+                                                     const int* __restrict__ list_len, const int64_t* __restrict__ ids,
+                                                     const Row* __restrict__ raw, int64_t nraw,
+                                                     const int* __restrict__ inv_start, const int* __restrict__ inv_cnt,
+                                                     const int* __restrict__ inv, const int* __restrict__ ustart,
+                                                     int nlist, int64_t q_stride,
+                                                     float* __restrict__ out, const FilterDesc* __restrict__ ftab,
+                                                     int need_filter, float min_score, float max_score, RowTab<Row> tab) {
+    ivfflat_lms_body<L2, Row, false>(x, d, P, pair_off, list_off, list_len, ids, raw, nraw, inv_start, inv_cnt, inv, ustart, nlist,
+                                     q_stride, out, ftab, need_filter, min_score, max_score, tab, nullptr, 0);
+}
+template <bool L2>
+__global__ __launch_bounds__(256) void k_ivfflat_lms_sp(const float* __restrict__ x, int d, int P, const int* __restrict__ pair_off,
+                                                        const int64_t* __restrict__ list_off,
+                                                        const int* __restrict__ list_len, const int64_t* __restrict__ ids,
+                                                        const float* __restrict__ raw, int64_t nraw,
+                                                        const int* __restrict__ inv_start, const int* __restrict__ inv_cnt,
+                                                        const int* __restrict__ inv, const int* __restrict__ ustart,
+                                                        int nlist, int64_t q_stride,
+                                                        float* __restrict__ out, const FilterDesc* __restrict__ ftab,
+                                                        int need_filter, float min_score, float max_score,
+                                                        const int32_t* __restrict__ slot, int64_t nslot) {
+    ivfflat_lms_body<L2, float, true>(x, d, P, pair_off, list_off, list_len, ids, raw, nraw, inv_start, inv_cnt, inv, ustart, nlist,
+                                      q_stride, out, ftab, need_filter, min_score, max_score, RowTab<float>{}, slot, nslot);
+}
+
+// list_len with the lists a shard's mask does not own set to 0: to the list-major launch an unowned list is an empty list
+__global__ __launch_bounds__(256) void k_masked_list_len(const int* __restrict__ list_len, const uint8_t* __restrict__ mask,
+                                                         int nlist, int* __restrict__ out) {
+    const int l = blockIdx.x * 256 + threadIdx.x;
+    if (l < nlist) out[l] = (!mask || mask[l]) ? list_len[l] : 0;
+}
+void launch_masked_list_len(hipStream_t s, const int* list_len, const uint8_t* mask, int nlist, int* out) {
+    if (nlist > 0) hipLaunchKernelGGL(k_masked_list_len, dim3((nlist + 255) / 256), dim3(256), 0, s, list_len, mask, nlist, out);
+}
 
 bool ivfflat_lm_supported(int d) { return d == 16 || d == 32 || d == 64 || d == 96 || d == 128; }
 
@@ -372,7 +438,8 @@ template <class Row>
 void launch_ivfflat_lm_t(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* probe, const int* pair_off,
                          const int64_t* list_off, const int* list_len, int nlist, const int64_t* ids, const Row* raw,
                          int64_t nraw, int64_t q_stride, float* out, const FilterDesc* ftab, int need_filter, float min_score,
-                         float max_score, void* scratch, RowTab<Row> tab = RowTab<Row>{}) {
+                         float max_score, void* scratch, RowTab<Row> tab = RowTab<Row>{}, const int32_t* slot = nullptr,
+                         int64_t nslot = 0) {
     if (nq <= 0 || P <= 0) return;
     int* inv = static_cast<int*>(scratch);
     int* cnt = inv + (size_t)nq * P;
@@ -387,6 +454,38 @@ void launch_ivfflat_lm_t(hipStream_t s, bool l2, const float* x, int nq, int d, 
     else hipLaunchKernelGGL(k_inv_scan, dim3(1), dim3(1024), 0, s, cnt, list_len, nlist, start, cur, ustart);
     hipLaunchKernelGGL(k_inv_fill, dim3((npairs + 255) / 256), dim3(256), 0, s, probe, npairs, nlist, list_len, start, cur, inv);
     const int grid = 256 * 8;   // persistent: every workgroup walks the unit list with stride gridDim.x
+    if constexpr (RowKind<Row>::fp32) {
+        if (slot) {   // a sparse store: the same two kernels with the vid -> row table (launch_ivfflat_lm_sparse)
+#define GH_FLSP(LL, DD)                                                                                                       \
+    hipLaunchKernelGGL((k_ivfflat_lm_sp<LL, DD>), dim3(grid), dim3(256), 0, s, x, P, pair_off, list_off, list_len, ids, raw, nraw, \
+                       start, cnt, inv, ustart, nlist, q_stride, out, ftab, need_filter, min_score, max_score, slot, nslot)
+#define GH_FLSPD(LL)                      \
+    switch (d) {                          \
+        case 128: GH_FLSP(LL, 128); break; \
+        case 96: GH_FLSP(LL, 96); break;   \
+        case 64: GH_FLSP(LL, 64); break;   \
+        case 32: GH_FLSP(LL, 32); break;   \
+        default: GH_FLSP(LL, 16); break;   \
+    }
+            if (sliced) {
+                if (l2)
+                    hipLaunchKernelGGL((k_ivfflat_lms_sp<true>), dim3(grid), dim3(256), 0, s, x, d, P, pair_off, list_off, list_len,
+                                       ids, raw, nraw, start, cnt, inv, ustart, nlist, q_stride, out, ftab, need_filter, min_score,
+                                       max_score, slot, nslot);
+                else
+                    hipLaunchKernelGGL((k_ivfflat_lms_sp<false>), dim3(grid), dim3(256), 0, s, x, d, P, pair_off, list_off, list_len,
+                                       ids, raw, nraw, start, cnt, inv, ustart, nlist, q_stride, out, ftab, need_filter, min_score,
+                                       max_score, slot, nslot);
+            } else if (l2) {
+                GH_FLSPD(true)
+            } else {
+                GH_FLSPD(false)
+            }
+#undef GH_FLSPD
+#undef GH_FLSP
+            return;
+        }
+    }
     if (sliced) {
         if (l2)
             hipLaunchKernelGGL((k_ivfflat_lms<true, Row>), dim3(grid), dim3(256), 0, s, x, d, P, pair_off, list_off, list_len, ids,
@@ -419,6 +518,15 @@ void launch_ivfflat_lm(hipStream_t s, bool l2, const float* x, int nq, int d, in
                        float max_score, void* scratch) {
     launch_ivfflat_lm_t<float>(s, l2, x, nq, d, P, probe, pair_off, list_off, list_len, nlist, ids, raw, nraw, q_stride, out, ftab,
                                need_filter, min_score, max_score, scratch);
+}
+// fp32 rows of a sparse store: slot [nslot] = vector id -> row of `raw` (nraw rows), -1 = not held here
+void launch_ivfflat_lm_sparse(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* probe, const int* pair_off,
+                              const int64_t* list_off, const int* list_len, int nlist, const int64_t* ids, const float* raw,
+                              int64_t nraw, const int32_t* slot, int64_t nslot, int64_t q_stride, float* out, const FilterDesc* ftab,
+                              int need_filter, float min_score, float max_score, void* scratch) {
+    if (!slot) return;   // (a sparse store without a table holds no row: the caller fills the slab with the sentinel)
+    launch_ivfflat_lm_t<float>(s, l2, x, nq, d, P, probe, pair_off, list_off, list_len, nlist, ids, raw, nraw, q_stride, out, ftab,
+                               need_filter, min_score, max_score, scratch, RowTab<float>{}, slot, nslot);
 }
 // rows of any element type (gamma_hip_set_ivfflat_narrow_rows, _sq8_rows); fp32 rows: the launch above, the kernels it always ran
 void launch_ivfflat_lm(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* probe, const int* pair_off,

@@ -361,6 +361,20 @@ void launch_ivfflat_lm(hipStream_t s, bool l2, const float* x, int nq, int d, in
                        const int64_t* list_off, const int* list_len, int nlist, const int64_t* ids, const RowsRef& raw,
                        int64_t nraw, int64_t q_stride, float* out, const FilterDesc* ftab, int need_filter, float min_score,
                        float max_score, void* scratch);
+// The three scans over the fp32 rows of a SPARSE store (gamma_hip_raw_put: a list shard's own rows): slot [nslot] = vector id ->
+// row of `raw` (nraw rows), -1 = not held here; an entry without a row here gets the sentinel and nothing is read through it.
+// Kernels of their own (the sparse instantiation of each scan's body): the launches above are untouched.  slot == nullptr (a
+// store that never took a row): nothing is launched -- the caller fills the slab with the sentinel.
+void launch_ivfflat_scan_sparse(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* pair_off,
+                                const int64_t* pair_base, const int64_t* ids, const float* raw, int64_t nraw, const int32_t* slot,
+                                int64_t nslot, int64_t q_stride, float* out, const FilterDesc* ftab, int need_filter,
+                                float min_score, float max_score);
+void launch_ivfflat_lm_sparse(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* probe, const int* pair_off,
+                              const int64_t* list_off, const int* list_len, int nlist, const int64_t* ids, const float* raw,
+                              int64_t nraw, const int32_t* slot, int64_t nslot, int64_t q_stride, float* out, const FilterDesc* ftab,
+                              int need_filter, float min_score, float max_score, void* scratch);
+// out[l] = mask[l] ? list_len[l] : 0 -- the list-length table of a list shard: to the list-major launch an unowned list is empty
+void launch_masked_list_len(hipStream_t s, const int* list_len, const uint8_t* mask, int nlist, int* out);
 // returns true when the walk of the tied rows went to `side` (the caller then waits for `join` before reading the result)
 bool launch_coarse_select(hipStream_t s, const float* mat, int nlist, int nq, int K, float* out_vals, int* out_pos,
                           uint8_t* tie_flag, unsigned long long* tie_stats = nullptr, hipStream_t side = nullptr,

@@ -617,14 +617,16 @@ void launch_rerank_topk_sq8(hipStream_t s, bool l2, const float* x, int nq, int 
 // the row access is rerank_dist8, which widens a narrow row exactly and runs the same fma chain (rerank_dev.h), any d.
 // sq8_t (gamma_hip_set_ivfflat_sq8_rows): rerank_dist8_sq8 with the store's decode table (tab: RowTab<Row>, flat_rows_dev.h --
 // empty for every other type), the byte rows' loads and the decode in front of the same chain.
-template <bool L2, class Row = float>
-__global__ __launch_bounds__(256) void k_ivfflat_scan(const float* __restrict__ x, int d, int P,
-                                                      const int* __restrict__ pair_off,
-                                                      const int64_t* __restrict__ pair_base,
-                                                      const int64_t* __restrict__ ids,
-                                                      const Row* __restrict__ raw, int64_t nraw, int64_t q_stride,
-                                                      float* __restrict__ out, const FilterDesc* __restrict__ ftab,
-                                                      int need_filter, float min_score, float max_score, RowTab<Row> tab) {
+// SPARSE: the rows of a sparse store through its vid -> row table (entry_row, filter_dev.h); the dense kernels pass false.
+template <bool L2, class Row, bool SPARSE>
+__device__ __forceinline__ void ivfflat_scan_body(const float* __restrict__ x, int d, int P,
+                                                  const int* __restrict__ pair_off,
+                                                  const int64_t* __restrict__ pair_base,
+                                                  const int64_t* __restrict__ ids,
+                                                  const Row* __restrict__ raw, int64_t nraw, int64_t q_stride,
+                                                  float* __restrict__ out, const FilterDesc* __restrict__ ftab,
+                                                  int need_filter, float min_score, float max_score, RowTab<Row> tab,
+                                                  const int32_t* __restrict__ slot, int64_t nslot) {
     const int q = blockIdx.x / P, p = blockIdx.x - q * P;
     const int off = pair_off[(int64_t)q * (P + 1) + p], len = pair_off[(int64_t)q * (P + 1) + p + 1] - off;
     if (len <= 0) return;   // uniform
@@ -636,19 +638,55 @@ __global__ __launch_bounds__(256) void k_ivfflat_scan(const float* __restrict__ 
         const int j = j0 + g;
         int64_t id = -1;
         if (j < len) id = ids[base + j];
-        const int64_t vid = id & 0x7fffffffffffffffLL;
-        bool live = j < len && id >= 0 && vid < nraw;   // id < 0: bit 63, superseded by an Update
-        if (need_filter && live) live = is_valid_doc(ftab[0], vid);
+        int64_t rw;
+        const bool live = entry_row<SPARSE>(id, j < len, nraw, slot, nslot, need_filter, ftab, &rw);
         float dis;
         if constexpr (RowKind<Row>::sq8)
-            dis = rerank_dist8_sq8<L2>(xq, reinterpret_cast<const uint8_t*>(raw) + (live ? vid : 0) * d, tab.t, d, l8, live);
+            dis = rerank_dist8_sq8<L2>(xq, reinterpret_cast<const uint8_t*>(raw) + rw * d, tab.t, d, l8, live);
         else
-            dis = rerank_dist8<L2>(xq, raw + (live ? vid : 0) * d, d, l8, live);
+            dis = rerank_dist8<L2>(xq, raw + rw * d, d, l8, live);
         if (l8 == 0 && j < len) {
             if (!live || !(dis <= max_score && dis >= min_score)) dis = sentinel;
             out[(int64_t)q * q_stride + off + j] = dis;
         }
     }
+}
+template <bool L2, class Row = float>
+__global__ __launch_bounds__(256) void k_ivfflat_scan(const float* __restrict__ x, int d, int P,
+                                                      const int* __restrict__ pair_off,
+                                                      const int64_t* __restrict__ pair_base,
+                                                      const int64_t* __restrict__ ids,
+                                                      const Row* __restrict__ raw, int64_t nraw, int64_t q_stride,
+                                                      float* __restrict__ out, const FilterDesc* __restrict__ ftab,
+                                                      int need_filter, float min_score, float max_score, RowTab<Row> tab) {
+    ivfflat_scan_body<L2, Row, false>(x, d, P, pair_off, pair_base, ids, raw, nraw, q_stride, out, ftab, need_filter, min_score,
+                                      max_score, tab, nullptr, 0);
+}
+template <bool L2>
+__global__ __launch_bounds__(256) void k_ivfflat_scan_sp(const float* __restrict__ x, int d, int P,
+                                                         const int* __restrict__ pair_off,
+                                                         const int64_t* __restrict__ pair_base,
+                                                         const int64_t* __restrict__ ids,
+                                                         const float* __restrict__ raw, int64_t nraw, int64_t q_stride,
+                                                         float* __restrict__ out, const FilterDesc* __restrict__ ftab,
+                                                         int need_filter, float min_score, float max_score,
+                                                         const int32_t* __restrict__ slot, int64_t nslot) {
+    ivfflat_scan_body<L2, float, true>(x, d, P, pair_off, pair_base, ids, raw, nraw, q_stride, out, ftab, need_filter, min_score,
+                                       max_score, RowTab<float>{}, slot, nslot);
+}
+// fp32 rows of a sparse store: slot [nslot] = vector id -> row of `raw` (nraw rows), -1 = not held here
+void launch_ivfflat_scan_sparse(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* pair_off,
+                                const int64_t* pair_base, const int64_t* ids, const float* raw, int64_t nraw, const int32_t* slot,
+                                int64_t nslot, int64_t q_stride, float* out, const FilterDesc* ftab, int need_filter,
+                                float min_score, float max_score) {
+    if (nq <= 0 || P <= 0 || !slot) return;
+    const dim3 grid((unsigned)((int64_t)nq * P));
+    if (l2)
+        hipLaunchKernelGGL((k_ivfflat_scan_sp<true>), grid, dim3(256), 0, s, x, d, P, pair_off, pair_base, ids, raw, nraw, q_stride,
+                           out, ftab, need_filter, min_score, max_score, slot, nslot);
+    else
+        hipLaunchKernelGGL((k_ivfflat_scan_sp<false>), grid, dim3(256), 0, s, x, d, P, pair_off, pair_base, ids, raw, nraw, q_stride,
+                           out, ftab, need_filter, min_score, max_score, slot, nslot);
 }
 void launch_ivfflat_scan(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* pair_off,
                          const int64_t* pair_base, const int64_t* ids, const float* raw, int64_t nraw, int64_t q_stride,

@@ -26,6 +26,49 @@ REGISTER_MODEL(HIPIVFPQ, GammaIVFPQHIPIndex);
     fprintf(stderr, "\n");             \
   } while (0)
 
+// "devices", "placement", "raw_placement": the keys HIPIVFPQ and HIPIVFFLAT share, one meaning and one parser
+static int ParseDeviceKeys(utils::JsonParser &jp, HIPIVFPQModelParams &pa) {
+  int v = 0;
+  std::string devs;
+  if (!jp.GetString("devices", devs)) {   // "0,1,2,3" (the engine's JsonParser has no arrays)
+    pa.devices.clear();
+    size_t at = 0;
+    while (at < devs.size()) {
+      size_t end = devs.find(',', at);
+      if (end == std::string::npos) end = devs.size();
+      const std::string tok = devs.substr(at, end - at);
+      char *rest = nullptr;
+      const long dv = strtol(tok.c_str(), &rest, 10);
+      if (tok.empty() || (rest && *rest != '\0' && *rest != ' ') || dv < 0) {
+        HLOG("invalid devices = %s", devs.c_str());
+        return -1;
+      }
+      pa.devices.push_back((int)dv);
+      at = end + 1;
+    }
+  } else if (!jp.GetInt("devices", v)) {   // a single ordinal
+    if (v < 0) return -1;
+    pa.devices.assign(1, v);
+  }
+  std::string plc;
+  if (!jp.GetString("placement", plc)) {   // several devices: "shard" (by IVF list, the default) | "replicate"
+    if (strcasecmp("shard", plc.c_str()) && strcasecmp("replicate", plc.c_str())) {
+      HLOG("invalid placement = %s", plc.c_str());
+      return -1;
+    }
+    pa.replicate = !strcasecmp("replicate", plc.c_str());
+  }
+  std::string rpl;
+  if (!jp.GetString("raw_placement", rpl)) {   // several devices, lists sharded: "replicated" (the default) | "sharded"
+    if (strcasecmp("replicated", rpl.c_str()) && strcasecmp("sharded", rpl.c_str())) {
+      HLOG("invalid raw_placement = %s", rpl.c_str());
+      return -1;
+    }
+    pa.raw_sharded = !strcasecmp("sharded", rpl.c_str());
+  }
+  return 0;
+}
+
 int HIPIVFPQModelParams::Parse(const char *str) {
   utils::JsonParser jp;
   if (jp.Parse(str)) {
@@ -63,43 +106,7 @@ int HIPIVFPQModelParams::Parse(const char *str) {
   if (!jp.GetInt("device_filters", v)) device_filters = v != 0;
   if (!jp.GetInt("exact_ties", v)) exact_ties = v != 0;
   if (!jp.GetInt("perf_stages", v)) perf_stages = v != 0;
-  std::string devs;
-  if (!jp.GetString("devices", devs)) {   // "0,1,2,3" (the engine's JsonParser has no arrays)
-    devices.clear();
-    size_t at = 0;
-    while (at < devs.size()) {
-      size_t end = devs.find(',', at);
-      if (end == std::string::npos) end = devs.size();
-      const std::string tok = devs.substr(at, end - at);
-      char *rest = nullptr;
-      const long dv = strtol(tok.c_str(), &rest, 10);
-      if (tok.empty() || (rest && *rest != '\0' && *rest != ' ') || dv < 0) {
-        HLOG("invalid devices = %s", devs.c_str());
-        return -1;
-      }
-      devices.push_back((int)dv);
-      at = end + 1;
-    }
-  } else if (!jp.GetInt("devices", v)) {   // a single ordinal
-    if (v < 0) return -1;
-    devices.assign(1, v);
-  }
-  std::string plc;
-  if (!jp.GetString("placement", plc)) {   // several devices: "shard" (by IVF list, the default) | "replicate"
-    if (strcasecmp("shard", plc.c_str()) && strcasecmp("replicate", plc.c_str())) {
-      HLOG("invalid placement = %s", plc.c_str());
-      return -1;
-    }
-    replicate = !strcasecmp("replicate", plc.c_str());
-  }
-  std::string rpl;
-  if (!jp.GetString("raw_placement", rpl)) {   // several devices, lists sharded: "replicated" (the default) | "sharded"
-    if (strcasecmp("replicated", rpl.c_str()) && strcasecmp("sharded", rpl.c_str())) {
-      HLOG("invalid raw_placement = %s", rpl.c_str());
-      return -1;
-    }
-    raw_sharded = !strcasecmp("sharded", rpl.c_str());
-  }
+  if (ParseDeviceKeys(jp, *this)) return -1;
   std::string rdt;
   if (!jp.GetString("raw_dtype", rdt)) {   // the device's raw rows: "float32" (the default) | "float16" | "uint8" | "int8" | "sq8"
     if (strcasecmp("float32", rdt.c_str()) && strcasecmp("float16", rdt.c_str()) && strcasecmp("uint8", rdt.c_str()) &&
@@ -1015,6 +1022,18 @@ int RegisterHIPIVFFlatSq8Rows(HIPIVFFlatSq8RowsFn fn) {
 }
 HIPIVFFlatSq8RowsFn FindHIPIVFFlatSq8Rows() { return IVFFlatSq8Rows(); }
 
+namespace {
+HIPIVFFlatGroupSearchFn &IVFFlatGroupSearch() {
+  static HIPIVFFlatGroupSearchFn fn = nullptr;
+  return fn;
+}
+}  // namespace
+int RegisterHIPIVFFlatGroup(HIPIVFFlatGroupSearchFn fn) {
+  IVFFlatGroupSearch() = fn;
+  return 0;
+}
+HIPIVFFlatGroupSearchFn FindHIPIVFFlatGroup() { return IVFFlatGroupSearch(); }
+
 int GammaIVFFlatHIPIndex::ParseRawDtype(const std::string &model_parameters, int *et) {
   *et = 0;
   utils::JsonParser jp;
@@ -1092,6 +1111,28 @@ int GammaIVFFlatHIPIndex::Init(const std::string &model_parameters, int indexing
   }
   raw_f16_ = et == 1;
   raw_i8_ = narrow && et >= 2 ? et - 1 : 0;
+  // several devices ("devices": "0,1,..", HIPIVFPQ's keys and parser): the in-process group, where the build carries its IVFFLAT
+  // search (gamma_index_ivfflat_group_hip.cc); without it the keys stay unread and the model opens one handle, as it always did
+  group_search_ = FindHIPIVFFlatGroup();
+  if (group_search_ && ParseDeviceKeys(jp, pa)) return -1;
+  const bool several = group_search_ && pa.devices.size() > 1;
+  if (several && et != 0) {
+    HLOG("HIPIVFFLAT: raw_dtype other than float32 with several devices is not supported (the group's members hold fp32 rows)");
+    return -1;
+  }
+  if (several && pa.device_filters) {
+    HLOG("HIPIVFFLAT: device_filters with several devices is not supported (the columns live on one handle)");
+    return -1;
+  }
+  if (group_search_ && pa.raw_sharded) {
+    rawshard_ = FindHIPRawShard();
+    if (!several || pa.replicate || !rawshard_) {
+      HLOG("HIPIVFFLAT: raw_placement = sharded needs several devices and placement = shard%s",
+           rawshard_ ? "" : " (and this build of the plugin carries no sharded raw rows)");
+      rawshard_ = nullptr;
+      return -1;
+    }
+  }
   if (!vector_) {
     HLOG("vector_ must be set before Init");
     return -1;
@@ -1101,10 +1142,26 @@ int GammaIVFFlatHIPIndex::Init(const std::string &model_parameters, int indexing
   M_ = 1;   // one dummy code byte per list entry (include/gamma_hip.h, IVFFLAT)
   metric_type_ = pa.metric_type;
   nprobe_ = pa.nprobe;
+  int rc;
+  if (several) {   // a group of handles, lists sharded by owner or replicated; h_ is member 0 (fp32 rows on every member)
+    if (OpenDevices(pa.devices, pa.replicate)) return -1;
+    rc = ForAll([&](gamma_hip_index *m) {
+      int r = gamma_hip_ivfflat_init(m, d_, nlist_, metric_type_ == DistanceComputeType::L2 ? GAMMA_HIP_METRIC_L2 : GAMMA_HIP_METRIC_IP,
+                                     pa.bucket_init_size, pa.bucket_max_size);
+      if (!r) r = gamma_hip_raw_init(m, d_);
+      if (!r) r = gamma_hip_set_exact_ties(m, pa.exact_ties ? 1 : 0);
+      return r;
+    });
+    if (rc) {
+      HLOG("device init failed: %s (%s)", gamma_hip_strerror(rc), gamma_hip_last_error(h_));
+      return -1;
+    }
+    return 0;
+  }
   const char *dev = getenv("GAMMA_HIP_DEVICE");
-  int rc = gamma_hip_create(dev ? atoi(dev) : 0, &h_);
+  rc = gamma_hip_create(dev ? atoi(dev) : 0, &h_);
   if (rc) return -1;
-  members_.assign(1, h_);   // one GPU (the sharded group serves HIPIVFPQ)
+  members_.assign(1, h_);   // one GPU
   rc = gamma_hip_ivfflat_init(h_, d_, nlist_, metric_type_ == DistanceComputeType::L2 ? GAMMA_HIP_METRIC_L2 : GAMMA_HIP_METRIC_IP,
                               pa.bucket_init_size, pa.bucket_max_size);
   if (!rc) rc = !et ? gamma_hip_raw_init(h_, d_) : et == 1 ? init_f16(h_, d_) : et == 4 ? raw_sq8_ops_->init(h_, d_)
@@ -1156,7 +1213,10 @@ RetrievalParameters *GammaIVFFlatHIPIndex::Parse(const std::string &parameters) 
 
 int GammaIVFFlatHIPIndex::SetTrainedCoarse(const float *coarse) {
   coarse_centroids_.assign(coarse, coarse + (size_t)nlist_ * d_);
-  if (gamma_hip_ivfflat_set_trained(h_, coarse_centroids_.data())) return -1;
+  if (ForAll([&](gamma_hip_index *m) { return gamma_hip_ivfflat_set_trained(m, coarse_centroids_.data()); })) return -1;
+  // several GPUs: no list sizes to balance yet -- lists are dealt round robin (Indexing balances by the training set's
+  // assignment, Load by the dumped sizes)
+  if (grp_ && gamma_hip_group_owner(grp_, 0) < 0 && gamma_hip_group_set_owners(grp_, nullptr)) return -1;
   is_trained_ = true;
   return 0;
 }
@@ -1175,8 +1235,23 @@ int GammaIVFFlatHIPIndex::Indexing() {   // IndexIVFFlat::train == the coarse k-
       return -1;
     }
   }
-  if (TrainCoarse(num, xt.data())) return -1;
-  return gamma_hip_ivfflat_set_trained(h_, coarse_centroids_.data()) ? -1 : (is_trained_ = true, 0);
+  if (TrainCoarse(num, xt.data())) return -1;   // once, on member 0; the centroids go to every member
+  if (ForAll([&](gamma_hip_index *m) { return gamma_hip_ivfflat_set_trained(m, coarse_centroids_.data()); })) return -1;
+  if (grp_) {
+    // list -> GPU by the training set's list sizes, balanced greedily: the lists never move afterwards
+    std::vector<int32_t> assign(num);
+    int rc = gamma_hip_assign(h_, d_, (int64_t)num, xt.data(), nlist_, coarse_centroids_.data(), assign.data(), nullptr);
+    std::vector<int64_t> weight(nlist_, 0);
+    for (size_t i = 0; i < num && !rc; i++)
+      if (assign[i] >= 0 && assign[i] < nlist_) weight[assign[i]]++;
+    if (!rc) rc = gamma_hip_group_set_owners(grp_, weight.data());
+    if (rc) {
+      HLOG("training failed: %s (%s)", gamma_hip_strerror(rc), gamma_hip_group_last_error(grp_));
+      return -1;
+    }
+  }
+  is_trained_ = true;
+  return 0;
 }
 
 int GammaIVFFlatHIPIndex::Search(RetrievalContext *retrieval_context, int n, const uint8_t *x, int k, float *distances,
@@ -1212,20 +1287,32 @@ int GammaIVFFlatHIPIndex::Search(RetrievalContext *retrieval_context, int n, con
            raw_sq8_ops_ ? "sq8" : raw_f16_ ? "float16" : raw_i8_ == 2 ? "int8" : "uint8");
       return -1;
     }
-    if (EnsureRaw((int64_t)vector_->MetaInfo()->Size())) return -1;
-    rc = gamma_hip_flat_search(h_, &p, n, xq, k, distances, ids);
+    if (rawshard_) {
+      // sharded rows (HIPIVFPQ's rule): member 0 mirrors the store until the first Add after training and serves the flat search
+      // from it (raw_mu_ through the call); afterwards no device holds every row: refused, never a wrong answer
+      std::lock_guard<std::mutex> g(raw_mu_);
+      if (rows_sharded_) {
+        HLOG("HIPIVFFLAT: brute_force_search is not available once the raw vectors are sharded (raw_placement = sharded)");
+        return -3;
+      }
+      if (EnsureRawLocked((int64_t)vector_->MetaInfo()->Size())) return -1;
+      rc = gamma_hip_flat_search(h_, &p, n, xq, k, distances, ids);
+    } else {
+      if (EnsureRaw((int64_t)vector_->MetaInfo()->Size())) return -1;
+      rc = gamma_hip_flat_search(h_, &p, n, xq, k, distances, ids);   // (several devices, rows replicated: member 0 answers)
+    }
   } else {
     // the reference takes retrieval_params->Nprobe() as it is (-1 when the request did not set it: a negative
     // allocation there, gamma_index_ivfflat.cc:405-410); the model's nprobe is the sane reading
     p.nprobe = (rp->Nprobe() > 0 && rp->Nprobe() <= nlist_) ? rp->Nprobe() : nprobe_;
-    rc = gamma_hip_ivfflat_search(h_, &p, n, xq, k, distances, ids);
+    rc = grp_ ? group_search_(grp_, &p, n, xq, k, distances, ids) : gamma_hip_ivfflat_search(h_, &p, n, xq, k, distances, ids);
   }
   if (rc) {
-    HLOG("search failed: %s (%s)", gamma_hip_strerror(rc), gamma_hip_last_error(h_));
+    HLOG("search failed: %s (%s)", gamma_hip_strerror(rc), grp_ ? gamma_hip_group_last_error(grp_) : gamma_hip_last_error(h_));
     return rc;
   }
-  WarnTiesNotHonoured(h_, nullptr, &ties_said_);
-  WarnBlasCorners(h_, nullptr, &blas_said_);
+  WarnTiesNotHonoured(h_, grp_, &ties_said_);
+  WarnBlasCorners(h_, grp_, &blas_said_);
   return 0;
 }
 
@@ -1247,13 +1334,15 @@ int GammaIVFFlatHIPIndex::Dump(const std::string &dir) {
   f.ids.resize(nlist_);
   std::vector<uint8_t> dummy;
   for (int l = 0; l < nlist_; l++) {
-    const int64_t len = gamma_hip_ivfpq_list_size(h_, l);
+    const int64_t len = grp_ ? gamma_hip_group_ivfpq_list_size(grp_, l) : gamma_hip_ivfpq_list_size(h_, l);
     if (len < 0) return -1;
     f.sizes[l] = (size_t)len;
     if (len == 0) continue;
     f.ids[l].resize(len);
     dummy.resize(len);
-    if (gamma_hip_ivfpq_get_list(h_, l, f.ids[l].data(), dummy.data())) return -1;
+    if (grp_ ? gamma_hip_group_ivfpq_get_list(grp_, l, f.ids[l].data(), dummy.data())
+             : gamma_hip_ivfpq_get_list(h_, l, f.ids[l].data(), dummy.data()))
+      return -1;
     // the vectors of the list, from the engine's store (what the reference's lists hold)
     std::vector<int64_t> vids(len);
     for (int64_t i = 0; i < len; i++) vids[i] = f.ids[l][i] & 0x7fffffffffffffffLL;
@@ -1293,6 +1382,11 @@ int GammaIVFFlatHIPIndex::Load(const std::string &dir) {
       if (!RowsStorable("load", buf.data(), nb)) return -1;
     }
   }
+  if (grp_) {   // several GPUs: list -> GPU balanced by the dumped list sizes, before the lists come back
+    std::vector<int64_t> weight(nlist_);
+    for (int l = 0; l < nlist_; l++) weight[l] = (int64_t)f.sizes[l];
+    if (gamma_hip_group_set_owners(grp_, weight.data())) return -1;
+  }
   if (SetTrainedCoarse(f.coarse.data())) return -1;
   if (UploadEngineBitmap()) return -1;
   if (SyncVid2DocID((int64_t)vector_->MetaInfo()->Size())) return -1;
@@ -1302,10 +1396,17 @@ int GammaIVFFlatHIPIndex::Load(const std::string &dir) {
     const size_t n = f.sizes[l];
     if (n == 0) continue;
     dummy.assign(n, 0);
-    if (gamma_hip_ivfpq_add_keys(h_, l, (int)n, f.ids[l].data(), dummy.data())) return -1;
+    if (grp_ ? gamma_hip_group_ivfpq_add_keys(grp_, l, (int)n, f.ids[l].data(), dummy.data())
+             : gamma_hip_ivfpq_add_keys(h_, l, (int)n, f.ids[l].data(), dummy.data()))
+      return -1;
   }
   indexed_vec_count_ = indexed;
-  if (EnsureRaw(std::min<int64_t>(indexed_vec_count_, (int64_t)vector_->MetaInfo()->Size()))) return -1;
+  const int64_t rows = std::min<int64_t>(indexed_vec_count_, (int64_t)vector_->MetaInfo()->Size());
+  if (rawshard_) {   // sharded rows: every owner gets the rows of its lists back from the engine's store
+    if (ShardRows() || PutRowsFromStore(rows)) return -1;
+  } else if (EnsureRaw(rows)) {
+    return -1;
+  }
   return indexed_vec_count_;
 }
 

@@ -116,6 +116,14 @@ typedef int (*HIPIVFFlatSq8RowsFn)(gamma_hip_index *h, int on);
 int RegisterHIPIVFFlatSq8Rows(HIPIVFFlatSq8RowsFn fn);
 HIPIVFFlatSq8RowsFn FindHIPIVFFlatSq8Rows();
 
+// HIPIVFFLAT with "devices": "0,1,.." (several): the in-process group's IVFFLAT search (gamma_hip_group_ivfflat_search), registered
+// the same way by gamma_index_ivfflat_group_hip.cc -- the only host file that names it.  Without that file HIPIVFFLAT reads none of
+// "devices" / "placement" / "raw_placement" and opens one handle, as it always did.
+typedef int (*HIPIVFFlatGroupSearchFn)(gamma_hip_group *g, const gamma_hip_search_params *p, int nq, const float *x, int k,
+                                       float *distances, int64_t *labels);
+int RegisterHIPIVFFlatGroup(HIPIVFFlatGroupSearchFn fn);
+HIPIVFFlatGroupSearchFn FindHIPIVFFlatGroup();
+
 // "opq": the rotation's entries of the C ABI (gamma_hip_opq_train / _set / _get / _apply) reach the model through this table,
 // registered at static-initialisation time by gamma_index_ivfpq_opq_hip.cc -- the only host file that names them.  A build of
 // the plugin without that file (against a C ABI without those entries) has no table, and HIPIVFPQ::Init rejects "opq".
@@ -247,6 +255,8 @@ class GammaIVFPQHIPIndex : public RetrievalModel {
 // come from the HBM mirror of the vector store the IVFPQ plugin already keeps for its re-rank, so Add / Update /
 // Delete and the raw mirror are inherited; Init, Indexing (coarse k-means only), Search, Dump / Load ("IvFl" file,
 // iwpq_io.h) differ.
+// HIP only: "devices": "0,1,..", "placement": "shard" | "replicate", "raw_placement": "replicated" | "sharded" with HIPIVFPQ's
+// meaning -- the index on several GPUs of this process (gamma_hip_group_*), fp32 rows only, no device_filters.
 // HIP only: "raw_dtype": "float32" (default) | "float16" | "uint8" | "int8" -- the device's rows are 2 bytes / 1 byte per element,
 // widened exactly as the scan loads them; the byte stores take a row only if it converts exactly (HIPIVFPQ's rule, inherited).
 // Unlike HIPIVFPQ the model serves brute_force_search and the search of an untrained model over a narrow store (flat search
@@ -287,6 +297,7 @@ class GammaIVFFlatHIPIndex : public GammaIVFPQHIPIndex {
   static int ParseRawDtype(const std::string &model_parameters, int *et);
 
  private:
+  HIPIVFFlatGroupSearchFn group_search_ = nullptr;   // non-null: the build carries the group's IVFFLAT search
   bool narrow_brute_ = true;   // false: a narrow store in a build without flat search over narrow rows -- brute force is refused
 };
 

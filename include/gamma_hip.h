@@ -864,6 +864,53 @@ int gamma_hip_ivfpq_merge_replay(gamma_hip_index* h, const gamma_hip_search_para
                                  const int32_t* d_off_all, int k, const int32_t* d_list, float* d_distances,
                                  int64_t* d_labels);
 
+/* ---- IVFFLAT over list shards: one handle per shard (gamma_hip_ivfpq_set_list_mask), the single-handle building blocks.
+ * Every pointer is a device address.  The rows of a shard come from a dense fp32 store (rows replicated on every shard) or
+ * from a SPARSE one (gamma_hip_raw_put: the rows live with their lists); a float16, 8-bit or sq8 store answers
+ * GAMMA_HIP_EUNSUPPORTED with last_error naming the store.  Limits on k and nprobe are gamma_hip_ivfflat_search's.  What the
+ * existing entries answer is unchanged: gamma_hip_ivfflat_search* on a sparse store stays refused.
+ *   ivfflat_coarse_device  the coarse quantizer alone for a slice of the queries, [nq * nprobe] outputs
+ *                   (gamma_hip_ivfpq_coarse_device refuses an IVFFLAT handle; this is its sibling);
+ *   ivfflat_search_shard   search_preassigned (index/impl/gamma_index_ivfflat.cc) restricted to the lists this handle holds
+ *                   and its mask owns -- what faiss:IndexShards.cpp:283-345 / index/impl/gpu/gamma_gpu_cloner.cpp:200-253 run
+ *                   per shard: [nq][k] best first, padded with (neutral, -1), the score window applied in the scan, local exact
+ *                   ties honoured as in the single-handle search.  The list-major kernels serve it under a mask (an unowned list
+ *                   is an empty list).  d_coarse_dis is not read (kept for the shape of the IVFPQ entry; may be null).  With
+ *                   exact ties on it leaves one cut flag per query of the whole call, whatever the chunking
+ *                   (gamma_hip_set_workspace_budget): the shard's own k cut went through a group of equal distances;
+ *   gamma_hip_ivfpq_shard_cut_flags / _merge_set_shard_flags / _merge_flagged / gamma_hip_gather_rows serve an IVFFLAT handle
+ *                   as they are (they read nothing of the model): the flags after ivfflat_search_shard, before / after
+ *                   ivfflat_merge;
+ *   ivfflat_merge   the W x k candidates per query, [shard][nq][k], for queries [q0, q0 + nq_local): the global top-k best first,
+ *                   padded with (neutral, -1).  With exact ties on a query is FLAGGED when two of the merged first k + 1
+ *                   distances are equal -- two equal among the k taken, or the merged cut passing through a group of equal
+ *                   distances -- or when a shard table whose own cut went through a tie (its cut flag; without the shards' flags
+ *                   every table counts) ends at the merged k-th value.  With exact_ties off the result is the merged top-k:
+ *                   distances identical to one handle's at every rank, ids possibly different inside groups of equal distances;
+ *   ivfflat_shard_export_rows / _shard_export  on EVERY shard for the nf flagged queries: the longest export row (host value),
+ *                   and the rows: exact distances (+-inf = filtered, deleted, superseded or outside the window) and vector ids
+ *                   of the probed lists this shard holds, in list order, rows of `stride` entries, d_off[f][p .. p + 1) = probe p
+ *                   (empty for a list of another shard) -- gamma_hip_ivfpq_shard_export's layout;
+ *   ivfflat_merge_replay   on the slice's owner: the exports are assembled probe by probe into the stream the reference's
+ *                   scanner saw and replayed through ITS heap -- heap_pop + heap_push when dis < top, then heap_reorder
+ *                   (index/impl/gamma_index_ivfflat.h:52-75), not the IVFPQ scanner's heap_replace_top; rows d_list[f] of
+ *                   d_distances / d_labels are rewritten. */
+int gamma_hip_ivfflat_coarse_device(gamma_hip_index* h, const gamma_hip_search_params* p, int nq, const float* d_x,
+                                    float* d_coarse_dis, int32_t* d_probe);
+int gamma_hip_ivfflat_search_shard(gamma_hip_index* h, const gamma_hip_search_params* p, int nq, const float* d_x,
+                                   const float* d_coarse_dis, const int32_t* d_probe, int k, float* d_dis, int64_t* d_ids);
+int gamma_hip_ivfflat_shard_export_rows(gamma_hip_index* h, const gamma_hip_search_params* p, int nf, const int32_t* d_probe_f,
+                                        int64_t* max_entries);
+int gamma_hip_ivfflat_shard_export(gamma_hip_index* h, const gamma_hip_search_params* p, int nf, const float* d_xf,
+                                   const int32_t* d_probe_f, int64_t stride, float* d_vals, int64_t* d_ids, int32_t* d_off);
+int gamma_hip_ivfflat_merge(gamma_hip_index* h, const gamma_hip_search_params* p, int nshards, int nq, int k,
+                            const float* d_all_dis, const int64_t* d_all_ids, int q0, int nq_local, float* d_distances,
+                            int64_t* d_labels);
+int gamma_hip_ivfflat_merge_replay(gamma_hip_index* h, const gamma_hip_search_params* p, int nshards, int nf,
+                                   const float* d_x_slice, int64_t stride, const float* d_vals_all, const int64_t* d_ids_all,
+                                   const int32_t* d_off_all, int k, const int32_t* d_list, float* d_distances,
+                                   int64_t* d_labels);
+
 /* ---- several GPUs in ONE process: a group of handles, the index sharded by IVF list ----------------------------
  * What the reference's GPU model does with faiss's IndexShards / GpuClonerOptions (index/impl/gpu/gamma_gpu_cloner.cpp:200-269,
  * index/impl/gpu/gamma_index_ivfpq_gpu.cc:356-436, faiss:IndexShards.cpp:283-345): one index object, a host thread per
@@ -926,6 +973,23 @@ int gamma_hip_group_ivfpq_search(gamma_hip_group* g, const gamma_hip_search_para
 /* the same with the queries and the result buffers in the memory of member 0's device; returns when the results are there */
 int gamma_hip_group_ivfpq_search_device(gamma_hip_group* g, const gamma_hip_search_params* p, int nq, const float* d_x,
                                         int k, float* d_distances, int64_t* d_labels);
+/* GammaIVFFlatIndex::Search over all members (members initialised with gamma_hip_ivfflat_init; the storage entries above
+ * -- gamma_hip_group_ivfpq_add / _add_keys / _get_list / _update / _delete / _compact_if_need, gamma_hip_group_raw_put -- serve
+ * IVFFLAT members unchanged: code_size is 1, the codes are dummies).  The IVFPQ search's sequence with the same barriers: every
+ * member runs the coarse quantizer of its slice (coarse_mode resolved on the whole call's nq), the assignment is exchanged, every
+ * member runs gamma_hip_ivfflat_search_shard over the whole batch -- rows from its dense store (raw placement 0) or from its
+ * sparse one (raw placement 1) -- each member pulls the [W][per][k] tables and cut flags of its slice, merges
+ * (gamma_hip_ivfflat_merge) and the tie phase runs in rounds of at most 256 flagged queries (_shard_export / _merge_replay).
+ * Results equal one handle's at every rank, exact ties included.  A member that fails in any phase still arrives at every
+ * meeting point, and the call returns that member's error.  With gamma_hip_group_set_placement(1) every member answers its
+ * slice with gamma_hip_ivfflat_search_device.  The exchanges are device-to-device copies ordered by events; a group set to RCCL
+ * uses copies for these calls all the same and says so in gamma_hip_group_transport_note.  A library built without the
+ * IVFFLAT shard entries answers GAMMA_HIP_EUNSUPPORTED. */
+int gamma_hip_group_ivfflat_search(gamma_hip_group* g, const gamma_hip_search_params* p, int nq, const float* x, int k,
+                                   float* distances, int64_t* labels);
+/* the same with the queries and the result buffers in the memory of member 0's device; returns when the results are there */
+int gamma_hip_group_ivfflat_search_device(gamma_hip_group* g, const gamma_hip_search_params* p, int nq, const float* d_x,
+                                          int k, float* d_distances, int64_t* d_labels);
 int64_t gamma_hip_group_total_mem_bytes(gamma_hip_group* g);
 /* Raw vectors of a list-sharded group.  0 (default): REPLICATED -- every member mirrors every row (the caller writes them
  * through gamma_hip_group_member, as the plugins do).  1: SHARDED -- every row lives exactly once, in the sparse store
