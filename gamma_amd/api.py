@@ -901,6 +901,7 @@ class GammaHipGroup:
             m.L = self.L
             m.h = C.c_void_p(self.L.gamma_hip_group_member(g, i))
             m.d = m.M = None
+            m.ksub = 256                         # (as GammaHip.__init__; 16 after ivfpq4_init)
             m.close = lambda: None
             self.members.append(m)
 

@@ -6,8 +6,25 @@
 //
 // Built on the public C ABI of the members only (plus the HIP runtime for the peer copies and events): a member is an
 // ordinary handle with a list mask.  One host thread per member enqueues that member's share of a call on the member's
-// own stream; the threads meet at two barriers (assignment exchanged, candidates exchanged) and cross-device ordering
-// is by events.  gamma_amd/dist.py is the same sequence of steps with one PROCESS per GPU and RCCL collectives.
+// own stream; cross-device ordering is by events.  gamma_amd/dist.py is the same sequence of steps with one PROCESS per
+// GPU and RCCL collectives.
+//
+// THE MEETING POINTS OF A LIST-SHARDED SEARCH.  The members' threads meet (Barrier::arrive) in this order, the same for IVFPQ and
+// IVFFLAT members except where said, and EVERY member reaches EVERY one of them on EVERY path -- a member with an error arrives
+// with "not ok", skips its own work and goes on to the next one; a member that left one out would leave its peers waiting:
+//   1. after the coarse quantizer                      (every member's slice of the assignment is on its stream)
+//   2. IVFPQ only: inside the scan's bound reduction   (every member's bounds are on its stream; a member that never got to
+//                                                       its reduction arrives from scan_owned_lists instead)
+//   3. after the scan                                  (every member's candidate tables are on its stream)
+//   4. after the merge and gamma_hip_ivfpq_merge_flagged (every owner's list of flagged queries is known)
+//   5. per tie round (at most 256 flagged queries of one owner), four times:
+//        the owner's compact inputs are ready | every member's longest export row is known | every export is complete |
+//        the exports may be overwritten
+//   6. at the end                                      (nobody reads this member's tables any more)
+// Whether a phase runs is decided from the snapshot the meeting point before it returns -- the same answer for all members --
+// never from a member's own status: points 2 and 5 exist only where point 1 / point 4 answered "go" for everybody.  Replicated
+// lists (gamma_hip_group_set_placement): every member answers its slice alone and the threads meet nowhere.  member_search()
+// below is this sequence; each meeting point is one call site.
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -221,10 +238,10 @@ gamma_group_ext::MemberMarkFn& member_mark() {
     return fn;
 }
 
-// the IVFFLAT entries this file may not name either (gamma_hip_group_ext.h); null in a build without them
-const gamma_group_ext::IvfflatOps*& ivfflat_ops() {
-    static const gamma_group_ext::IvfflatOps* ops = nullptr;
-    return ops;
+// the IVFFLAT family: entries this file may not name either (gamma_hip_group_ext.h); null in a build without them
+const gamma_group_ext::ShardFamily*& ivfflat_family() {
+    static const gamma_group_ext::ShardFamily* f = nullptr;
+    return f;
 }
 
 // src on device sd -> dst on device dd, ordered on stream s (a stream of device dd)
@@ -248,8 +265,8 @@ int register_member_mark(MemberMarkFn fn) {
     return 1;
 }
 
-int register_ivfflat_ops(const IvfflatOps* ops) {
-    ivfflat_ops() = ops;
+int register_ivfflat_ops(const ShardFamily* family) {
+    ivfflat_family() = family;
     return 1;
 }
 
@@ -703,657 +720,511 @@ int64_t gamma_hip_group_total_mem_bytes(gamma_hip_group* g) {
     return t;
 }
 
-static int group_search(gamma_hip_group* g, const gamma_hip_search_params* p, int nq, const float* x, int k,
-                        float* distances, int64_t* labels, bool on_device);
+}  // extern "C"
 
-int gamma_hip_group_ivfpq_search(gamma_hip_group* g, const gamma_hip_search_params* p, int nq, const float* x, int k,
-                                 float* distances, int64_t* labels) {
-    return group_search(g, p, nq, x, k, distances, labels, false);
+// ---- search: ONE protocol for IVFPQ and IVFFLAT members (the sequence of meeting points: file header) ------------------------
+// IVFPQ: gamma_index_ivfpq.cc search_preassigned + compute_dis per member; IVFFLAT: gamma_index_ivfflat.cc search_preassigned;
+// faiss:IndexShards.cpp:283-345 for the merge.  What differs between the families is in their ShardFamily table
+// (gamma_hip_group_ext.h); the sharded raw rows' entries (IVFPQ only) are called by name under Call::rs.
+namespace {
+
+using gamma_group_ext::ShardFamily;
+typedef gamma_hip_group::Member Member;
+
+const ShardFamily kIvfpqFamily = {
+    "search", gamma_hip_ivfpq_search_device, gamma_hip_ivfpq_coarse_device, gamma_hip_ivfpq_search_shard_bounded,
+    gamma_hip_ivfpq_shard_export_rows, gamma_hip_ivfpq_shard_export, gamma_hip_ivfpq_merge_rerank, gamma_hip_ivfpq_merge_replay,
+    /*wide_tables*/ true, /*bounded_scan*/ true, /*tie_coarse_dis*/ true, /*raw_rows*/ true, /*rccl*/ true,
+};
+
+// one call, shared by the members' threads
+struct Call {
+    gamma_hip_group* g;
+    const ShardFamily* f;
+    gamma_hip_search_params pp;
+    int nq, k, d, P, R, W, per;   // R: width of the candidate tables; per: rows of a slice
+    // on_device: x / distances / labels live on member 0's device (the other members pull the batch over the fabric and push
+    // their slice of the results back); the call still returns when the results are in place
+    const float* x;
+    float* distances;
+    int64_t* labels;
+    bool on_device;
+    // raw rows sharded with the lists: the exact distances of compute_dis are computed where the rows are and travel with the
+    // candidates (has_rank = 0: nothing is computed, nothing more is sent)
+    bool rs;
+    RcclApi* nccl;   // the exchanges go through RCCL; null: peer copies
+    std::vector<int> rcs;
+    std::vector<std::string> errs;
+    std::vector<int64_t> rowmax;          // tie phase: every member's longest export row of the round
+    std::vector<int> nfl;                 // flagged queries of every member's slice
+    std::vector<const int32_t*> lists;    // and the device lists of their slice-local indices
+    void slice(int i, int* q0, int* q1) const {
+        *q0 = std::min(nq, i * per);
+        *q1 = std::min(nq, *q0 + per);
+    }
+};
+
+// one member's share of it: what its thread carries from phase to phase.  The first failure is kept (rc, the text in errs[i]);
+// later steps still run or are skipped on ok(), but WHICH meeting points follow is never decided from it (Barrier::arrive).
+struct Ctx {
+    Call& c;
+    const int i, dev;
+    int q0, nql;
+    Member& b;
+    gamma_hip_index* const h;
+    const hipStream_t s;
+    int& rc;
+    std::string& err;
+    Ctx(Call& call, int member)
+        : c(call), i(member), dev(call.g->dev[member]), b(call.g->mb[member]), h(call.g->m[member]),
+          s((hipStream_t)gamma_hip_stream(call.g->m[member])), rc(call.rcs[member]), err(call.errs[member]) {
+        int q1;
+        c.slice(i, &q0, &q1);
+        nql = q1 - q0;
+    }
+    bool ok() const { return rc == GAMMA_HIP_OK; }
+    void hip(hipError_t e, const char* what) {
+        if (e != hipSuccess && ok()) {
+            rc = e == hipErrorOutOfMemory ? GAMMA_HIP_ENOMEM : GAMMA_HIP_EDEVICE;
+            err = std::string(what) + ": " + hipGetErrorString(e);
+        }
+    }
+    void abi(int r) {
+        if (r != GAMMA_HIP_OK && ok()) {
+            rc = r;
+            err = std::string(gamma_hip_strerror(r)) + " (" + gamma_hip_last_error(h) + ")";
+        }
+    }
+    void ncc(int e, const char* what) {
+        if (e != 0 && ok()) {
+            rc = GAMMA_HIP_EDEVICE;
+            err = std::string(what) + ": " + (c.nccl && c.nccl->GetErrorString ? c.nccl->GetErrorString(e) : "RCCL error");
+        }
+    }
+    void alloc(GBuf& buf, size_t bytes) { hip(buf.ensure(bytes), "alloc"); }
+};
+
+// One column of an exchange: rows of `width` elements of `elem` bytes travel from a member's `src` into this member's `dst`.
+struct Col {
+    GBuf Member::*src;
+    GBuf Member::*dst;
+    size_t elem, width;
+    bool on;
+    const char* what;
+    size_t row() const { return elem * width; }
+};
+// rows [src_row, src_row + rows) of member j's column -> rows [dst_row, ...) of this member's, ordered on this member's stream
+void pull(Ctx& m, const Col& col, int j, size_t dst_row, size_t src_row, size_t rows) {
+    if (!col.on) return;
+    gamma_hip_group* g = m.c.g;
+    m.hip(copy_between((m.b.*col.dst).as<char>() + dst_row * col.row(), m.dev, (g->mb[j].*col.src).as<char>() + src_row * col.row(), g->dev[j],
+                       rows * col.row(), m.s), col.what);
 }
 
-int gamma_hip_group_ivfpq_search_device(gamma_hip_group* g, const gamma_hip_search_params* p, int nq, const float* d_x, int k,
-                                        float* d_distances, int64_t* d_labels) {
-    return group_search(g, p, nq, d_x, k, d_distances, d_labels, true);
+void upload(Ctx& m, const float* src, int rows) {
+    const size_t bytes = (size_t)rows * m.c.d * sizeof(float);
+    if (m.c.on_device) m.hip(copy_between(m.b.x.p, m.dev, src, m.c.g->dev[0], bytes, m.s), "queries to the member");
+    else m.hip(hipMemcpyAsync(m.b.x.p, src, bytes, hipMemcpyHostToDevice, m.s), "H2D queries");
 }
 
-// on_device: x / distances / labels live on member 0's device (the other members pull the batch over the fabric and
-// push their slice of the results back); the call still returns when the results are in place
-static int group_search(gamma_hip_group* g, const gamma_hip_search_params* p, int nq, const float* x, int k,
-                        float* distances, int64_t* labels, bool on_device) {
+// the slice's rows (D, I) to the caller
+void results_to_caller(Ctx& m) {
+    Call& c = m.c;
+    float* Ds = c.distances + (size_t)m.q0 * c.k;
+    int64_t* Is = c.labels + (size_t)m.q0 * c.k;
+    const size_t n = (size_t)m.nql * c.k;
+    if (c.on_device) {
+        m.hip(copy_between(Ds, c.g->dev[0], m.b.D.p, m.dev, n * sizeof(float), m.s), "results");
+        m.hip(copy_between(Is, c.g->dev[0], m.b.I.p, m.dev, n * sizeof(int64_t), m.s), "results");
+    } else {
+        m.hip(hipMemcpyAsync(Ds, m.b.D.p, n * sizeof(float), hipMemcpyDeviceToHost, m.s), "D2H");
+        m.hip(hipMemcpyAsync(Is, m.b.I.p, n * sizeof(int64_t), hipMemcpyDeviceToHost, m.s), "D2H");
+    }
+}
+
+// query-parallel over replicated lists: the member answers its slice with the ordinary single-handle search (exact ties and
+// all); nothing is exchanged but the slice and its k results, and the members meet nowhere
+void replicate_slice(Ctx& m) {
+    Call& c = m.c;
+    if (m.nql <= 0 || !m.ok()) return;
+    const bool local = c.on_device && m.dev == c.g->dev[0];
+    const float* xs = c.x + (size_t)m.q0 * c.d;
+    if (!local) {
+        m.alloc(m.b.x, (size_t)m.nql * c.d * sizeof(float));
+        m.alloc(m.b.D, (size_t)m.nql * c.k * sizeof(float));
+        m.alloc(m.b.I, (size_t)m.nql * c.k * sizeof(int64_t));
+        if (!m.ok()) return;
+        upload(m, xs, m.nql);
+    }
+    if (m.ok())
+        m.abi(c.f->search_device(m.h, &c.pp, m.nql, local ? xs : m.b.x.as<float>(), c.k, local ? c.distances + (size_t)m.q0 * c.k : m.b.D.as<float>(),
+                                 local ? c.labels + (size_t)m.q0 * c.k : m.b.I.as<int64_t>()));
+    if (m.ok() && !local) results_to_caller(m);
+    m.hip(hipStreamSynchronize(m.s), "sync");
+}
+
+// 0. the whole batch to every member (each scans its lists for all queries); coarse quantizer for the own slice
+void upload_and_coarse(Ctx& m) {
+    Call& c = m.c;
+    Member& b = m.b;
+    m.alloc(b.x, (size_t)c.nq * c.d * sizeof(float));
+    // (W * per rows: the in-place all-gather moves whole slices, the last one's tail rows are never read)
+    m.alloc(b.cdis, (size_t)c.W * c.per * c.P * sizeof(float));
+    m.alloc(b.probe, (size_t)c.W * c.per * c.P * sizeof(int32_t));
+    m.alloc(b.rdis, (size_t)c.nq * c.R * sizeof(float));
+    m.alloc(b.rids, (size_t)c.nq * c.R * sizeof(int64_t));
+    m.alloc(b.all_dis, (size_t)c.W * c.per * c.R * sizeof(float));
+    m.alloc(b.all_ids, (size_t)c.W * c.per * c.R * sizeof(int64_t));
+    m.alloc(b.D, (size_t)c.per * c.k * sizeof(float));
+    m.alloc(b.I, (size_t)c.per * c.k * sizeof(int64_t));
+    if (!m.ok()) return;
+    upload(m, c.x, c.nq);
+    if (m.nql > 0)
+        m.abi(c.f->coarse_device(m.h, &c.pp, m.nql, b.x.as<float>() + (size_t)m.q0 * c.d, b.cdis.as<float>() + (size_t)m.q0 * c.P,
+                                 b.probe.as<int32_t>() + (size_t)m.q0 * c.P));
+    m.hip(hipEventRecord(b.ev_coarse, m.s), "record");
+}
+
+// 1a. the other slices of the assignment
+void exchange_assignment(Ctx& m) {
+    Call& c = m.c;
+    const Col cols[] = {{&Member::cdis, &Member::cdis, sizeof(float), (size_t)c.P, true, "assignment exchange"},
+                        {&Member::probe, &Member::probe, sizeof(int32_t), (size_t)c.P, true, "assignment exchange"}};
+    if (c.nccl) {
+        // RCCL: ONE all-gather of the assignment over xGMI (in place: this member's slice sits at its offset already)
+        m.ncc(c.nccl->GroupStart(), "ncclGroupStart");
+        for (const Col& col : cols)
+            m.ncc(c.nccl->AllGather((m.b.*col.dst).as<char>() + (size_t)m.i * c.per * col.row(), (m.b.*col.dst).p, (size_t)c.per * col.row(),
+                                    kNcclChar, c.g->comm[m.i], m.s), "ncclAllGather");
+        m.ncc(c.nccl->GroupEnd(), "ncclGroupEnd");
+        return;
+    }
+    for (int j = 0; j < c.W; j++) {
+        if (j == m.i) continue;
+        int a0, a1;
+        c.slice(j, &a0, &a1);
+        if (a1 <= a0) continue;
+        m.hip(hipStreamWaitEvent(m.s, c.g->mb[j].ev_coarse, 0), "wait");
+        for (const Col& col : cols) pull(m, col, j, a0, a0, a1 - a0);
+    }
+}
+
+// The IVFPQ scan runs in TWO PHASES around a reduction of one float per query (gamma_hip_ivfpq_search_shard_bounded): every
+// member bounds its own recall_num-th best from the query's nearest probes it owns, the minimum (L2) / maximum (IP) over the
+// members bounds the GLOBAL one, and the members' other probes only keep what is within it.  The reduction: ncclAllReduce over
+// xGMI, or -- peer copies -- every member publishes its bounds, the members meet, pull each other's and combine.  It is one more
+// meeting point of the call: a member that does not get as far as its scan arrives there all the same (scan_owned_lists).
+struct BoundMeeting {
+    Ctx* m;
+    bool arrived;
+    bool arrive(bool my_ok) {
+        arrived = true;
+        return m->c.g->bar.arrive(my_ok);   // every member's bounds are on its stream (RCCL: all enter the collective, or none)
+    }
+};
+int reduce_bounds(void* user, float* d_bound, int n, int take_max, void* stream) {
+    BoundMeeting& at = *static_cast<BoundMeeting*>(user);
+    Ctx& m = *at.m;
+    Call& c = m.c;
+    gamma_hip_group* g = c.g;
+    Member& b = m.b;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    bool ok = true;   // (the scan is entered by a member without an error only)
+    if (!c.nccl)
+        ok = b.bound_pub.ensure((size_t)n * sizeof(float)) == hipSuccess && b.bound_peer.ensure((size_t)n * sizeof(float)) == hipSuccess &&
+             hipMemcpyAsync(b.bound_pub.p, d_bound, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, s) == hipSuccess &&
+             hipEventRecord(b.ev_bound, s) == hipSuccess;
+    if (!at.arrive(ok)) return ok ? 0 : 1;   // (the bounds stay this member's own: still valid)
+    if (c.nccl) {
+        const int e = c.nccl->AllReduce(d_bound, d_bound, (size_t)n, kNcclFloat, take_max ? kNcclMax : kNcclMin, g->comm[m.i], s);
+        if (e != 0) m.err = std::string("ncclAllReduce: ") + (c.nccl->GetErrorString ? c.nccl->GetErrorString(e) : "RCCL error");
+        return e != 0;
+    }
+    for (int j = 0; j < c.W && ok; j++) {
+        if (j == m.i) continue;
+        ok = hipStreamWaitEvent(s, g->mb[j].ev_bound, 0) == hipSuccess &&
+             copy_between(b.bound_peer.p, m.dev, g->mb[j].bound_pub.p, g->dev[j], (size_t)n * sizeof(float), s) == hipSuccess &&
+             gamma_hip_bound_combine(stream, d_bound, b.bound_peer.as<float>(), n, take_max) == GAMMA_HIP_OK;
+    }
+    if (!ok) m.err = "bound reduction: peer copy failed";
+    return ok ? 0 : 1;
+}
+
+// 1b. scan of the owned probed lists, local top-R of every query of the batch
+void scan_owned_lists(Ctx& m) {
+    Call& c = m.c;
+    Member& b = m.b;
+    BoundMeeting at{&m, false};
+    if (c.f->bounded_scan) m.alloc(b.bound, (size_t)c.nq * sizeof(float));
+    if (m.ok())
+        m.abi(c.f->scan(m.h, &c.pp, c.nq, b.x.as<float>(), b.cdis.as<float>(), b.probe.as<int32_t>(), c.k, b.rdis.as<float>(),
+                        b.rids.as<int64_t>(), c.f->bounded_scan ? b.bound.as<float>() : nullptr, c.f->bounded_scan ? reduce_bounds : nullptr, &at));
+    if (c.f->bounded_scan && !at.arrived) (void)at.arrive(false);   // (this member never got to the reduction: its peers are waiting there)
+    // did this member's own top-R cut of a query go through a tie?  (the merge at the query's owner asks)
+    m.alloc(b.cutf, (size_t)c.nq);
+    if (m.ok()) m.abi(gamma_hip_ivfpq_shard_cut_flags(m.h, c.nq, b.cutf.as<uint8_t>()));
+    // (what the exchange below receives into is allocated on THIS side of the meeting point: a member that cannot get it says so
+    //  in the go / no-go snapshot instead of leaving its peers inside a collective.  An RCCL error AFTER the meeting point is fatal
+    //  for the group: nothing can call a member back out of ncclGroupEnd)
+    m.alloc(b.cutall, (size_t)c.W * c.per);
+    if (c.rs) {   // exact distances of the candidates this member is about to send, where it holds the row
+        m.alloc(b.rex, (size_t)c.nq * c.R * sizeof(float));
+        m.alloc(b.all_ex, (size_t)c.W * c.per * c.R * sizeof(float));
+        if (m.ok()) m.abi(gamma_hip_ivfpq_shard_exact(m.h, &c.pp, c.nq, b.x.as<float>(), b.rids.as<int64_t>(), c.R, b.rex.as<float>()));
+    }
+    m.hip(hipEventRecord(b.ev_scan, m.s), "record");
+}
+
+// 2. the exchange of the path: the candidates of the own query slice from every member ([W][per][R]), their cut flags, and
+//    their exact distances when the rows are sharded
+void exchange_candidates(Ctx& m) {
+    Call& c = m.c;
+    const Col cols[] = {{&Member::rdis, &Member::all_dis, sizeof(float), (size_t)c.R, true, "candidate exchange"},
+                        {&Member::rids, &Member::all_ids, sizeof(int64_t), (size_t)c.R, true, "candidate exchange"},
+                        {&Member::cutf, &Member::cutall, 1, 1, true, "cut flags"},
+                        {&Member::rex, &Member::all_ex, sizeof(float), (size_t)c.R, c.rs, "candidate exchange"}};
+    if (c.nccl) {
+        // RCCL: the per-shard tables of every owner's slice in one grouped exchange (every member sends slice j of its tables to
+        // member j and receives its own slice of theirs -- an all-to-all over xGMI); members with an empty slice still take part
+        m.ncc(c.nccl->GroupStart(), "ncclGroupStart");
+        for (int j = 0; j < c.W; j++) {   // (never cut short: the other members' halves of the exchange are under way)
+            int a0, a1;
+            c.slice(j, &a0, &a1);
+            for (const Col& col : cols)
+                if (col.on && a1 > a0)
+                    m.ncc(c.nccl->Send((m.b.*col.src).as<char>() + (size_t)a0 * col.row(), (size_t)(a1 - a0) * col.row(), kNcclChar, j,
+                                       c.g->comm[m.i], m.s), "ncclSend");
+            for (const Col& col : cols)
+                if (col.on && m.nql > 0)
+                    m.ncc(c.nccl->Recv((m.b.*col.dst).as<char>() + (size_t)j * c.per * col.row(), (size_t)m.nql * col.row(), kNcclChar, j,
+                                       c.g->comm[m.i], m.s), "ncclRecv");
+        }
+        m.ncc(c.nccl->GroupEnd(), "ncclGroupEnd");
+        return;
+    }
+    for (int j = 0; j < c.W && m.nql > 0; j++) {
+        if (j != m.i) m.hip(hipStreamWaitEvent(m.s, c.g->mb[j].ev_scan, 0), "wait");
+        for (const Col& col : cols) pull(m, col, j, (size_t)j * c.per, m.q0, m.nql);
+    }
+}
+
+// 3. merge of the own slice to the global top-R, compute_dis (IVFPQ) / to the top-k (IVFFLAT)
+void merge_slice(Ctx& m) {
+    Call& c = m.c;
+    Member& b = m.b;
+    const float* xs = b.x.as<float>() + (size_t)m.q0 * c.d;
+    if (m.ok()) m.abi(gamma_hip_ivfpq_merge_set_shard_flags(m.h, b.cutall.as<uint8_t>()));
+    if (m.ok() && c.rs)
+        m.abi(gamma_hip_ivfpq_merge_rerank_exact(m.h, &c.pp, c.W, c.per, xs, c.k, b.all_dis.as<float>(), b.all_ids.as<int64_t>(),
+                                                 b.all_ex.as<float>(), 0, m.nql, b.D.as<float>(), b.I.as<int64_t>()));
+    else if (m.ok())
+        m.abi(c.f->merge(m.h, &c.pp, c.W, c.per, xs, c.k, b.all_dis.as<float>(), b.all_ids.as<int64_t>(), 0, m.nql, b.D.as<float>(),
+                         b.I.as<int64_t>()));
+}
+
+// 4. exact ties across members (include/gamma_hip.h): the queries a tie can change, listed by their owner, get their candidate
+//    streams exported by every member and replayed at the owner.  One round: nf flagged queries of owner o, from f0 of its list.
+void tie_round(Ctx& m, int o, int f0, int nf) {
+    Call& c = m.c;
+    Member& b = m.b;
+    Barrier& bar = c.g->bar;
+    const int32_t* list = c.lists[o] + f0;
+    // the flagged queries' vectors and assignment rows, compact (sharded rows: and their reduced bounds of the scan -- only exported
+    // entries within them can be members of the recall_num-heap, only those get an exact distance)
+    const Col in[] = {{&Member::fx, &Member::sx, sizeof(float), (size_t)c.d, true, "tie inputs"},
+                      {&Member::fcd, &Member::scd, sizeof(float), (size_t)c.P, c.f->tie_coarse_dis, "tie inputs"},
+                      {&Member::fpr, &Member::spr, sizeof(int32_t), (size_t)c.P, true, "tie inputs"},
+                      {&Member::fbd, &Member::sbd, sizeof(float), 1, c.rs, "tie inputs"}};
+    if (m.i == o) {
+        for (const Col& col : in)
+            if (col.on) m.alloc(b.*col.src, (size_t)nf * col.row());
+        if (m.ok() && c.rs) m.abi(gamma_hip_gather_rows(m.h, b.bound.as<float>() + m.q0, 1, list, nf, b.fbd.p));
+        if (m.ok()) {
+            m.abi(gamma_hip_gather_rows(m.h, b.x.as<float>() + (size_t)m.q0 * c.d, c.d, list, nf, b.fx.p));
+            if (c.f->tie_coarse_dis) m.abi(gamma_hip_gather_rows(m.h, b.cdis.as<float>() + (size_t)m.q0 * c.P, c.P, list, nf, b.fcd.p));
+            m.abi(gamma_hip_gather_rows(m.h, b.probe.as<int32_t>() + (size_t)m.q0 * c.P, c.P, list, nf, b.fpr.p));
+        }
+        m.hip(hipEventRecord(b.ev_tie, m.s), "record");
+    }
+    bool go = bar.arrive(m.ok());   // the owner's compact inputs are on its stream
+    for (const Col& col : in)
+        if (col.on) m.alloc(b.*col.dst, (size_t)nf * col.row());
+    m.alloc(b.ex_off, (size_t)nf * (c.P + 1) * sizeof(int32_t));
+    c.rowmax[m.i] = 0;
+    if (go && m.ok()) {
+        if (m.i != o) m.hip(hipStreamWaitEvent(m.s, c.g->mb[o].ev_tie, 0), "wait");
+        for (const Col& col : in) pull(m, col, o, 0, 0, nf);
+        // how long this member's export rows get: the exports of all members share one row stride
+        int64_t mine = 0;
+        if (m.ok()) m.abi(c.f->shard_export_rows(m.h, &c.pp, nf, b.spr.as<int32_t>(), &mine));
+        c.rowmax[m.i] = mine;
+    }
+    go = bar.arrive(m.ok());   // every member's longest row is known
+    int64_t stride = 4;
+    for (int j = 0; j < c.W; j++) stride = std::max<int64_t>(stride, (c.rowmax[j] + 3) & ~(int64_t)3);
+    m.alloc(b.ex_vals, (size_t)nf * stride * sizeof(float));
+    m.alloc(b.ex_ids, (size_t)nf * stride * sizeof(int64_t));
+    if (go && m.ok())
+        m.abi(c.f->shard_export(m.h, &c.pp, nf, b.sx.as<float>(), c.f->tie_coarse_dis ? b.scd.as<float>() : nullptr, b.spr.as<int32_t>(), stride,
+                                b.ex_vals.as<float>(), b.ex_ids.as<int64_t>(), b.ex_off.as<int32_t>()));
+    if (c.rs) m.alloc(b.ex_ex, (size_t)nf * stride * sizeof(float));
+    if (c.rs && go && m.ok())
+        m.abi(gamma_hip_ivfpq_shard_export_exact(m.h, &c.pp, nf, b.sx.as<float>(), b.ex_vals.as<float>(), b.ex_ids.as<int64_t>(),
+                                                 b.ex_off.as<int32_t>(), stride, b.sbd.as<float>(), b.ex_ex.as<float>()));
+    m.hip(hipStreamSynchronize(m.s), "sync");
+    go = bar.arrive(m.ok());   // every member's export is complete
+    if (m.i == o && go) {
+        const Col out[] = {{&Member::ex_ex, &Member::ae, sizeof(float), (size_t)stride, c.rs, "exports"},
+                           {&Member::ex_vals, &Member::av, sizeof(float), (size_t)stride, true, "exports"},
+                           {&Member::ex_ids, &Member::ai, sizeof(int64_t), (size_t)stride, true, "exports"},
+                           {&Member::ex_off, &Member::ao, sizeof(int32_t), (size_t)c.P + 1, true, "exports"}};
+        for (const Col& col : out)
+            if (col.on) m.alloc(b.*col.dst, (size_t)c.W * nf * col.row());
+        for (int j = 0; j < c.W && m.ok(); j++)
+            for (const Col& col : out) pull(m, col, j, (size_t)j * nf, 0, nf);
+        const float* xs = b.x.as<float>() + (size_t)m.q0 * c.d;
+        if (m.ok() && c.rs)
+            m.abi(gamma_hip_ivfpq_merge_replay_exact(m.h, &c.pp, c.W, nf, xs, stride, b.av.as<float>(), b.ai.as<int64_t>(), b.ao.as<int32_t>(),
+                                                     b.ae.as<float>(), c.k, list, b.D.as<float>(), b.I.as<int64_t>()));
+        else if (m.ok())
+            m.abi(c.f->merge_replay(m.h, &c.pp, c.W, nf, xs, stride, b.av.as<float>(), b.ai.as<int64_t>(), b.ao.as<int32_t>(), c.k, list,
+                                    b.D.as<float>(), b.I.as<int64_t>()));
+        m.hip(hipStreamSynchronize(m.s), "sync");
+    }
+    (void)bar.arrive(m.ok());   // the exports may be overwritten
+}
+
+// One member's thread through a call: the phases, and between them the meeting points every member reaches on every path.
+// `go` is the snapshot of the last meeting point -- the same answer for all members; a member's own rc only gates its own work.
+void member_search(Ctx& m) {
+    Call& c = m.c;
+    Barrier& bar = c.g->bar;
+    m.hip(hipSetDevice(m.dev), "hipSetDevice");
+    if (c.g->replicate) return replicate_slice(m);
+    upload_and_coarse(m);
+    bool go = bar.arrive(m.ok());   // every member's assignment is on its stream
+    if (go) {
+        exchange_assignment(m);
+        scan_owned_lists(m);        // (IVFPQ: the meeting point of the bound reduction is in here)
+    }
+    go = bar.arrive(m.ok());        // every member's candidate tables are on its stream
+    if (go) exchange_candidates(m);
+    if (go && m.nql > 0) merge_slice(m);
+    static const bool gdbg = getenv("GAMMA_HIP_GROUP_DBG") != nullptr;
+    const auto tp0 = std::chrono::steady_clock::now();
+    auto since = [&](std::chrono::steady_clock::time_point t) {
+        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
+    };
+    int nf_i = 0;
+    const int32_t* list_i = nullptr;
+    if (go && m.nql > 0 && m.ok()) m.abi(gamma_hip_ivfpq_merge_flagged(m.h, &nf_i, &list_i));
+    c.nfl[m.i] = m.ok() ? nf_i : 0;
+    c.lists[m.i] = list_i;
+    if (gdbg && m.i == 0) fprintf(stderr, "group: member 0 waited %.3f ms for its merge, %d flagged\n", since(tp0), nf_i);
+    go = bar.arrive(m.ok());        // every owner's flagged queries are listed
+    const int fcap = 256;           // flagged queries per round
+    for (int o = 0; o < c.W && go; o++)
+        for (int f0 = 0; f0 < c.nfl[o]; f0 += fcap) tie_round(m, o, f0, std::min(fcap, c.nfl[o] - f0));
+    if (gdbg && m.i == 0) fprintf(stderr, "group: tie phase done %.3f ms after the merge was enqueued\n", since(tp0));
+    // (go: the snapshot of the last meeting point outside the rounds -- the tie phase's own failures show in rc)
+    if (go && m.nql > 0 && m.ok()) results_to_caller(m);
+    m.hip(hipStreamSynchronize(m.s), "sync");
+    (void)bar.arrive(m.ok());       // nobody is reading this member's tables any more
+}
+
+// transport of the exchanges: RCCL when asked for and a communicator of the members' distinct devices can be formed (tried once)
+void form_communicator(gamma_hip_group* g) {
+    const int W = (int)g->m.size();
+    g->comm_tried = true;
+    bool distinct = true;
+    for (int i = 0; i < W; i++)
+        for (int j = 0; j < i; j++) distinct = distinct && g->dev[i] != g->dev[j];
+    RcclApi* api = rccl_api();
+    if (!distinct) {
+        g->transport_note = "RCCL asked for, but members share a device: peer copies";
+    } else if (!api->ok()) {
+        g->transport_note = "RCCL asked for, but librccl.so could not be loaded: peer copies";
+    } else {
+        g->comm.assign(W, nullptr);
+        const int e = api->CommInitAll(g->comm.data(), W, g->dev.data());
+        if (e != 0) {
+            g->comm.clear();
+            g->transport_note = std::string("ncclCommInitAll failed (") + (api->GetErrorString ? api->GetErrorString(e) : "?") + "): peer copies";
+        } else {
+            g->transport_note = "RCCL";
+        }
+    }
+}
+
+int group_search(gamma_hip_group* g, const ShardFamily* f, const gamma_hip_search_params* p, int nq, const float* x, int k, float* distances,
+                 int64_t* labels, bool on_device) {
     if (!g || !p) return GAMMA_HIP_EINVAL;
     if (nq < 0) return GAMMA_HIP_EINVAL;
     if (k <= 0 || nq == 0) return GAMMA_HIP_OK;   // gamma_index_ivfpq.cc:753-756
     if (!x || !distances || !labels) return GAMMA_HIP_EINVAL;
     std::lock_guard<std::mutex> lk(g->mu);
-    if (g->owner.empty()) return gfail(g, GAMMA_HIP_EINVAL, "search: gamma_hip_group_set_owners first");
+    if (!f) return gfail(g, GAMMA_HIP_EUNSUPPORTED, "ivfflat_search: the IVFFLAT search of the group is not built in");
+    const std::string name = f->name;
+    if (g->owner.empty()) return gfail(g, GAMMA_HIP_EINVAL, name + ": gamma_hip_group_set_owners first");
     const int W = (int)g->m.size();
     const int d = gamma_hip_ivfpq_dim(g->m[0]);
-    if (d <= 0) return gfail(g, GAMMA_HIP_EINVAL, "search: members not initialised");
-    const int P = p->nprobe, R = std::max(p->recall_num, k);
-    if (P <= 0) return gfail(g, GAMMA_HIP_EINVAL, "search: nprobe out of range");
+    if (d <= 0) return gfail(g, GAMMA_HIP_EINVAL, name + ": members not initialised");
+    if (p->nprobe <= 0) return gfail(g, GAMMA_HIP_EINVAL, name + ": nprobe out of range");
+    Call c;
+    c.g = g;
+    c.f = f;
     // faiss chooses the coarse path from the size of the WHOLE call (faiss:utils/distances.cpp:346): the slices must agree
-    gamma_hip_search_params pp = *p;
-    if (pp.coarse_mode < 0) pp.coarse_mode = nq < 20 ? 0 : 1;
+    c.pp = *p;
+    if (c.pp.coarse_mode < 0) c.pp.coarse_mode = nq < 20 ? 0 : 1;
     // (gamma_hip_blas_form_not_restated: every member counts the shape of ITS slice -- a remainder block of the whole call
     //  that a slice boundary hides is not counted here)
-    const int per = (nq + W - 1) / W;
-    // transport of the two exchanges of the path: RCCL when asked for and a communicator can be formed
-    if (g->transport == 1 && !g->replicate && !g->comm_tried) {
-        g->comm_tried = true;
-        bool distinct = true;
-        for (int i = 0; i < W; i++)
-            for (int j = 0; j < i; j++) distinct = distinct && g->dev[i] != g->dev[j];
-        RcclApi* api = rccl_api();
-        if (!distinct) {
-            g->transport_note = "RCCL asked for, but members share a device: peer copies";
-        } else if (!api->ok()) {
-            g->transport_note = "RCCL asked for, but librccl.so could not be loaded: peer copies";
-        } else {
-            g->comm.assign(W, nullptr);
-            const int e = api->CommInitAll(g->comm.data(), W, g->dev.data());
-            if (e != 0) {
-                g->comm.clear();
-                g->transport_note = std::string("ncclCommInitAll failed (") + (api->GetErrorString ? api->GetErrorString(e) : "?") + "): peer copies";
-            } else {
-                g->transport_note = "RCCL";
-            }
-        }
-    }
-    // raw rows sharded with the lists: the exact distances of compute_dis are computed where the rows are and travel with the
-    // candidates (has_rank = 0: nothing is computed, nothing more is sent)
-    const bool rs = g->raw_sharded && !g->replicate && pp.has_rank != 0;
-    const bool use_rccl = g->transport == 1 && !g->replicate && (int)g->comm.size() == W;
+    c.nq = nq, c.k = k, c.d = d, c.P = p->nprobe, c.W = W;
+    c.R = f->wide_tables ? std::max(p->recall_num, k) : k;
+    c.per = (nq + W - 1) / W;
+    c.x = x, c.distances = distances, c.labels = labels, c.on_device = on_device;
+    if (f->rccl && g->transport == 1 && !g->replicate && !g->comm_tried) form_communicator(g);
+    if (!f->rccl && g->transport == 1 && !g->replicate && g->transport_note.find("IVFFLAT") == std::string::npos)
+        g->transport_note += std::string(g->transport_note.empty() ? "" : "; ") + "IVFFLAT search: peer copies (RCCL serves the IVFPQ search only)";
+    c.rs = f->raw_rows && g->raw_sharded && !g->replicate && c.pp.has_rank != 0;
+    const bool use_rccl = f->rccl && g->transport == 1 && !g->replicate && (int)g->comm.size() == W;
     if (use_rccl) g->rccl_calls++;
-    RcclApi* const nccl = use_rccl ? rccl_api() : nullptr;
-    std::vector<int> rcs(W, GAMMA_HIP_OK);
-    std::vector<std::string> errs(W);
-    std::vector<int64_t> rowmax(W, 0);                 // tie phase: every member's longest export row of the round
-    std::vector<int> nfl(W, 0);                        // flagged queries of every member's slice
-    std::vector<const int32_t*> lists(W, nullptr);     // and the device lists of their slice-local indices
-    auto slice = [&](int i, int* q0, int* q1) {
-        *q0 = std::min(nq, i * per);
-        *q1 = std::min(nq, *q0 + per);
-    };
+    c.nccl = use_rccl ? rccl_api() : nullptr;
+    c.rcs.assign(W, GAMMA_HIP_OK);
+    c.errs.resize(W);
+    c.rowmax.assign(W, 0);
+    c.nfl.assign(W, 0);
+    c.lists.assign(W, nullptr);
     g->run([&](int i) {
-        gamma_hip_group::Member& b = g->mb[i];
-        gamma_hip_index* h = g->m[i];
-        hipStream_t s = (hipStream_t)gamma_hip_stream(h);
-        int q0, q1;
-        slice(i, &q0, &q1);
-        const int nql = q1 - q0;
-        int& rc = rcs[i];
-        if (g->replicate) {
-            // query-parallel over replicated lists: the member answers its slice with the ordinary single-handle search
-            // (exact ties and all); nothing is exchanged but the slice and its k results
-            auto hipr = [&](hipError_t e, const char* what) {
-                if (e != hipSuccess && rc == GAMMA_HIP_OK) {
-                    rc = e == hipErrorOutOfMemory ? GAMMA_HIP_ENOMEM : GAMMA_HIP_EDEVICE;
-                    errs[i] = std::string(what) + ": " + hipGetErrorString(e);
-                }
-            };
-            hipr(hipSetDevice(g->dev[i]), "hipSetDevice");
-            if (nql <= 0 || rc != GAMMA_HIP_OK) return;
-            const bool local = on_device && g->dev[i] == g->dev[0];
-            const float* xs = x + (size_t)q0 * d;
-            float* Ds = distances + (size_t)q0 * k;
-            int64_t* Is = labels + (size_t)q0 * k;
-            if (!local) {
-                hipr(b.x.ensure((size_t)nql * d * sizeof(float)), "alloc");
-                hipr(b.D.ensure((size_t)nql * k * sizeof(float)), "alloc");
-                hipr(b.I.ensure((size_t)nql * k * sizeof(int64_t)), "alloc");
-                if (rc != GAMMA_HIP_OK) return;
-                if (on_device) hipr(copy_between(b.x.p, g->dev[i], xs, g->dev[0], (size_t)nql * d * sizeof(float), s), "queries to the member");
-                else hipr(hipMemcpyAsync(b.x.p, xs, (size_t)nql * d * sizeof(float), hipMemcpyHostToDevice, s), "H2D queries");
-            }
-            if (rc == GAMMA_HIP_OK) {
-                const int r = gamma_hip_ivfpq_search_device(h, &pp, nql, local ? xs : b.x.as<float>(), k, local ? Ds : b.D.as<float>(),
-                                                           local ? Is : b.I.as<int64_t>());
-                if (r != GAMMA_HIP_OK) {
-                    rc = r;
-                    errs[i] = std::string(gamma_hip_strerror(r)) + " (" + gamma_hip_last_error(h) + ")";
-                }
-            }
-            if (rc == GAMMA_HIP_OK && !local) {
-                if (on_device) {
-                    hipr(copy_between(Ds, g->dev[0], b.D.p, g->dev[i], (size_t)nql * k * sizeof(float), s), "results");
-                    hipr(copy_between(Is, g->dev[0], b.I.p, g->dev[i], (size_t)nql * k * sizeof(int64_t), s), "results");
-                } else {
-                    hipr(hipMemcpyAsync(Ds, b.D.p, (size_t)nql * k * sizeof(float), hipMemcpyDeviceToHost, s), "D2H");
-                    hipr(hipMemcpyAsync(Is, b.I.p, (size_t)nql * k * sizeof(int64_t), hipMemcpyDeviceToHost, s), "D2H");
-                }
-            }
-            hipr(hipStreamSynchronize(s), "sync");
-            return;
-        }
-        auto hip = [&](hipError_t e, const char* what) {
-            if (e != hipSuccess && rc == GAMMA_HIP_OK) {
-                rc = e == hipErrorOutOfMemory ? GAMMA_HIP_ENOMEM : GAMMA_HIP_EDEVICE;
-                errs[i] = std::string(what) + ": " + hipGetErrorString(e);
-            }
-        };
-        auto abi = [&](int r) {
-            if (r != GAMMA_HIP_OK && rc == GAMMA_HIP_OK) {
-                rc = r;
-                errs[i] = std::string(gamma_hip_strerror(r)) + " (" + gamma_hip_last_error(h) + ")";
-            }
-        };
-        hip(hipSetDevice(g->dev[i]), "hipSetDevice");
-        hip(b.x.ensure((size_t)nq * d * sizeof(float)), "alloc");
-        // (W * per rows: the in-place all-gather moves whole slices, the last one's tail rows are never read)
-        hip(b.cdis.ensure((size_t)W * per * P * sizeof(float)), "alloc");
-        hip(b.probe.ensure((size_t)W * per * P * sizeof(int32_t)), "alloc");
-        hip(b.rdis.ensure((size_t)nq * R * sizeof(float)), "alloc");
-        hip(b.rids.ensure((size_t)nq * R * sizeof(int64_t)), "alloc");
-        hip(b.all_dis.ensure((size_t)W * per * R * sizeof(float)), "alloc");
-        hip(b.all_ids.ensure((size_t)W * per * R * sizeof(int64_t)), "alloc");
-        hip(b.D.ensure((size_t)per * k * sizeof(float)), "alloc");
-        hip(b.I.ensure((size_t)per * k * sizeof(int64_t)), "alloc");
-        // 0. the whole batch to every member (each scans its lists for all queries); coarse quantizer for the own slice
-        if (rc == GAMMA_HIP_OK) {
-            if (on_device) hip(copy_between(b.x.p, g->dev[i], x, g->dev[0], (size_t)nq * d * sizeof(float), s), "queries to the member");
-            else hip(hipMemcpyAsync(b.x.p, x, (size_t)nq * d * sizeof(float), hipMemcpyHostToDevice, s), "H2D queries");
-            if (nql > 0)
-                abi(gamma_hip_ivfpq_coarse_device(h, &pp, nql, b.x.as<float>() + (size_t)q0 * d, b.cdis.as<float>() + (size_t)q0 * P,
-                                                  b.probe.as<int32_t>() + (size_t)q0 * P));
-            hip(hipEventRecord(b.ev_coarse, s), "record");
-        }
-        bool all_ok = g->bar.arrive(rc == GAMMA_HIP_OK);   // every member's assignment is on its stream
-        auto ncc = [&](int e, const char* what) {
-            if (e != 0 && rc == GAMMA_HIP_OK) {
-                rc = GAMMA_HIP_EDEVICE;
-                errs[i] = std::string(what) + ": " + (nccl && nccl->GetErrorString ? nccl->GetErrorString(e) : "RCCL error");
-            }
-        };
-        // 1. pull the other slices of the assignment; scan of the owned probed lists, local top-R of every query
-        if (all_ok && nccl) {
-            // RCCL: ONE all-gather of the assignment over xGMI (in place: this member's slice sits at its offset already)
-            ncc(nccl->GroupStart(), "ncclGroupStart");
-            ncc(nccl->AllGather(b.cdis.as<float>() + (size_t)i * per * P, b.cdis.p, (size_t)per * P * sizeof(float), kNcclChar,
-                                g->comm[i], s), "ncclAllGather");
-            ncc(nccl->AllGather(b.probe.as<int32_t>() + (size_t)i * per * P, b.probe.p, (size_t)per * P * sizeof(int32_t), kNcclChar,
-                                g->comm[i], s), "ncclAllGather");
-            ncc(nccl->GroupEnd(), "ncclGroupEnd");
-        }
-        if (all_ok) {
-            for (int j = 0; j < W && !nccl; j++) {
-                if (j == i) continue;
-                int a0, a1;
-                slice(j, &a0, &a1);
-                if (a1 <= a0) continue;
-                hip(hipStreamWaitEvent(s, g->mb[j].ev_coarse, 0), "wait");
-                hip(copy_between(b.cdis.as<float>() + (size_t)a0 * P, g->dev[i], g->mb[j].cdis.as<float>() + (size_t)a0 * P, g->dev[j],
-                                 (size_t)(a1 - a0) * P * sizeof(float), s), "assignment exchange");
-                hip(copy_between(b.probe.as<int32_t>() + (size_t)a0 * P, g->dev[i], g->mb[j].probe.as<int32_t>() + (size_t)a0 * P,
-                                 g->dev[j], (size_t)(a1 - a0) * P * sizeof(int32_t), s), "assignment exchange");
-            }
-            // The scan in TWO PHASES around a reduction of one float per query (gamma_hip_ivfpq_search_shard_bounded): every
-            // member bounds its own recall_num-th best from the query's nearest probes it owns, the minimum (L2) / maximum (IP)
-            // over the members bounds the GLOBAL one, and the members' other probes only keep what is within it.  The
-            // reduction: ncclAllReduce over xGMI, or -- peer copies -- every member publishes its bounds, the members meet at a
-            // barrier, pull each other's and combine.  It is one more meeting point of the call: a member that does not get
-            // as far as its scan arrives there all the same.
-            struct Red {
-                gamma_hip_group* g; int i, W; RcclApi* nccl; bool* ok_in; bool arrived; std::string* err;
-            } red{g, i, W, nccl, nullptr, false, &errs[i]};
-            bool my_ok = rc == GAMMA_HIP_OK;
-            red.ok_in = &my_ok;
-            auto reduce = [](void* user, float* d_bound, int n, int take_max, void* stream) -> int {
-                Red& r = *static_cast<Red*>(user);
-                gamma_hip_group* g = r.g;
-                auto& b = g->mb[r.i];
-                hipStream_t s = static_cast<hipStream_t>(stream);
-                r.arrived = true;
-                if (r.nccl) {
-                    const bool all = g->bar.arrive(*r.ok_in);   // (every member is about to enter the collective, or none does)
-                    if (!all) return 0;
-                    const int e = r.nccl->AllReduce(d_bound, d_bound, (size_t)n, kNcclFloat, take_max ? kNcclMax : kNcclMin, g->comm[r.i], s);
-                    if (e != 0) *r.err = std::string("ncclAllReduce: ") + (r.nccl->GetErrorString ? r.nccl->GetErrorString(e) : "RCCL error");
-                    return e != 0;
-                }
-                bool ok = *r.ok_in && b.bound_pub.ensure((size_t)n * sizeof(float)) == hipSuccess &&
-                          b.bound_peer.ensure((size_t)n * sizeof(float)) == hipSuccess;
-                ok = ok && hipMemcpyAsync(b.bound_pub.p, d_bound, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, s) == hipSuccess &&
-                     hipEventRecord(b.ev_bound, s) == hipSuccess;
-                const bool all = g->bar.arrive(ok);   // every member's bounds are on its stream
-                if (!all) return ok ? 0 : 1;        // (the bounds stay this member's own: still valid)
-                for (int j = 0; j < r.W && ok; j++) {
-                    if (j == r.i) continue;
-                    ok = hipStreamWaitEvent(s, g->mb[j].ev_bound, 0) == hipSuccess &&
-                         copy_between(b.bound_peer.p, g->dev[r.i], g->mb[j].bound_pub.p, g->dev[j], (size_t)n * sizeof(float), s) == hipSuccess &&
-                         gamma_hip_bound_combine(stream, d_bound, b.bound_peer.as<float>(), n, take_max) == GAMMA_HIP_OK;
-                }
-                if (!ok) *r.err = "bound reduction: peer copy failed";
-                return ok ? 0 : 1;
-            };
-            hip(b.bound.ensure((size_t)nq * sizeof(float)), "alloc");
-            my_ok = rc == GAMMA_HIP_OK;
-            if (rc == GAMMA_HIP_OK)
-                abi(gamma_hip_ivfpq_search_shard_bounded(h, &pp, nq, b.x.as<float>(), b.cdis.as<float>(), b.probe.as<int32_t>(), k,
-                                                         b.rdis.as<float>(), b.rids.as<int64_t>(), b.bound.as<float>(), reduce, &red));
-            if (!red.arrived) (void)g->bar.arrive(false);   // (this member never got to the reduction: its peers are waiting there)
-            // did this member's own top-R cut of a query go through a tie?  (the merge at the query's owner asks)
-            hip(b.cutf.ensure((size_t)nq), "alloc");
-            if (rc == GAMMA_HIP_OK) abi(gamma_hip_ivfpq_shard_cut_flags(h, nq, b.cutf.as<uint8_t>()));
-            // (what the exchange below receives into is allocated on THIS side of the barrier: a member that cannot get it says so
-            //  in the go / no-go snapshot instead of leaving its peers inside a collective -- ADVICE r4.  An RCCL error AFTER the
-            //  barrier is fatal for the group: nothing can call a member back out of ncclGroupEnd)
-            hip(b.cutall.ensure((size_t)W * per), "alloc");
-            if (rs) {   // exact distances of the candidates this member is about to send, where it holds the row
-                hip(b.rex.ensure((size_t)nq * R * sizeof(float)), "alloc");
-                hip(b.all_ex.ensure((size_t)W * per * R * sizeof(float)), "alloc");
-                if (rc == GAMMA_HIP_OK) abi(gamma_hip_ivfpq_shard_exact(h, &pp, nq, b.x.as<float>(), b.rids.as<int64_t>(), R, b.rex.as<float>()));
-            }
-            hip(hipEventRecord(b.ev_scan, s), "record");
-        }
-        all_ok = g->bar.arrive(rc == GAMMA_HIP_OK);   // every member's candidate tables are on its stream
-        // 2. the exchange of the path: the candidates of the own query slice from every member ([W][per][R]);
-        // 3. merge to the global top-R, compute_dis, results to the caller
-        if (all_ok && nccl) {
-            // RCCL: the per-shard tables of every owner's slice in one grouped exchange (every member sends slice j of its
-            // tables to member j and receives its own slice of theirs -- an all-to-all over xGMI); members with an empty
-            // slice still take part
-            ncc(nccl->GroupStart(), "ncclGroupStart");
-            for (int j = 0; j < W; j++) {   // (never cut short: the other members' halves of the exchange are under way)
-                int a0, a1;
-                slice(j, &a0, &a1);
-                if (a1 > a0) {
-                    ncc(nccl->Send(b.rdis.as<float>() + (size_t)a0 * R, (size_t)(a1 - a0) * R * sizeof(float), kNcclChar, j, g->comm[i], s), "ncclSend");
-                    ncc(nccl->Send(b.rids.as<int64_t>() + (size_t)a0 * R, (size_t)(a1 - a0) * R * sizeof(int64_t), kNcclChar, j, g->comm[i], s), "ncclSend");
-                    ncc(nccl->Send(b.cutf.as<uint8_t>() + a0, (size_t)(a1 - a0), kNcclChar, j, g->comm[i], s), "ncclSend");
-                    if (rs) ncc(nccl->Send(b.rex.as<float>() + (size_t)a0 * R, (size_t)(a1 - a0) * R * sizeof(float), kNcclChar, j, g->comm[i], s), "ncclSend");
-                }
-                if (nql > 0) {
-                    ncc(nccl->Recv(b.all_dis.as<float>() + (size_t)j * per * R, (size_t)nql * R * sizeof(float), kNcclChar, j, g->comm[i], s), "ncclRecv");
-                    ncc(nccl->Recv(b.all_ids.as<int64_t>() + (size_t)j * per * R, (size_t)nql * R * sizeof(int64_t), kNcclChar, j, g->comm[i], s), "ncclRecv");
-                    ncc(nccl->Recv(b.cutall.as<uint8_t>() + (size_t)j * per, (size_t)nql, kNcclChar, j, g->comm[i], s), "ncclRecv");
-                    if (rs) ncc(nccl->Recv(b.all_ex.as<float>() + (size_t)j * per * R, (size_t)nql * R * sizeof(float), kNcclChar, j, g->comm[i], s), "ncclRecv");
-                }
-            }
-            ncc(nccl->GroupEnd(), "ncclGroupEnd");
-        }
-        if (all_ok && nql > 0) {
-            for (int j = 0; j < W && !nccl; j++) {
-                if (j != i) hip(hipStreamWaitEvent(s, g->mb[j].ev_scan, 0), "wait");
-                hip(copy_between(b.all_dis.as<float>() + (size_t)j * per * R, g->dev[i], g->mb[j].rdis.as<float>() + (size_t)q0 * R,
-                                 g->dev[j], (size_t)nql * R * sizeof(float), s), "candidate exchange");
-                hip(copy_between(b.all_ids.as<int64_t>() + (size_t)j * per * R, g->dev[i], g->mb[j].rids.as<int64_t>() + (size_t)q0 * R,
-                                 g->dev[j], (size_t)nql * R * sizeof(int64_t), s), "candidate exchange");
-                if (rs)
-                    hip(copy_between(b.all_ex.as<float>() + (size_t)j * per * R, g->dev[i], g->mb[j].rex.as<float>() + (size_t)q0 * R,
-                                     g->dev[j], (size_t)nql * R * sizeof(float), s), "candidate exchange");
-            }
-            for (int j = 0; j < W && rc == GAMMA_HIP_OK && !nccl; j++)
-                hip(copy_between(b.cutall.as<uint8_t>() + (size_t)j * per, g->dev[i], g->mb[j].cutf.as<uint8_t>() + q0, g->dev[j], (size_t)nql, s),
-                    "cut flags");
-            if (rc == GAMMA_HIP_OK) abi(gamma_hip_ivfpq_merge_set_shard_flags(h, b.cutall.as<uint8_t>()));
-            if (rc == GAMMA_HIP_OK && rs)
-                abi(gamma_hip_ivfpq_merge_rerank_exact(h, &pp, W, per, b.x.as<float>() + (size_t)q0 * d, k, b.all_dis.as<float>(),
-                                                       b.all_ids.as<int64_t>(), b.all_ex.as<float>(), 0, nql, b.D.as<float>(),
-                                                       b.I.as<int64_t>()));
-            else if (rc == GAMMA_HIP_OK)
-                abi(gamma_hip_ivfpq_merge_rerank(h, &pp, W, per, b.x.as<float>() + (size_t)q0 * d, k, b.all_dis.as<float>(),
-                                                 b.all_ids.as<int64_t>(), 0, nql, b.D.as<float>(), b.I.as<int64_t>()));
-        }
-        // 4. exact ties across members (include/gamma_hip.h): the queries a tie can change, listed by their owner, get their
-        //    candidate streams exported by every member and replayed at the owner
-        static const bool gdbg = getenv("GAMMA_HIP_GROUP_DBG") != nullptr;
-        const auto tp0 = std::chrono::steady_clock::now();
-        auto since = [&](std::chrono::steady_clock::time_point t) {
-            return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
-        };
-        {
-            int nf_i = 0;
-            const int32_t* list_i = nullptr;
-            if (all_ok && nql > 0 && rc == GAMMA_HIP_OK) abi(gamma_hip_ivfpq_merge_flagged(h, &nf_i, &list_i));
-            nfl[i] = rc == GAMMA_HIP_OK ? nf_i : 0;
-            lists[i] = list_i;
-            if (gdbg && i == 0) fprintf(stderr, "group: member 0 waited %.3f ms for its merge, %d flagged\n", since(tp0), nf_i);
-            all_ok = g->bar.arrive(rc == GAMMA_HIP_OK);
-            int total = 0;
-            for (int j = 0; j < W; j++) total += nfl[j];
-            if (all_ok && total > 0) {
-                const int fcap = 256;   // flagged queries per round
-                for (int o = 0; o < W; o++) {
-                    for (int f0 = 0; f0 < nfl[o]; f0 += fcap) {
-                        const int nf = std::min(fcap, nfl[o] - f0);
-                        if (i == o) {   // the flagged queries' vectors and assignment rows, compact
-                            hip(b.fx.ensure((size_t)nf * d * sizeof(float)), "alloc");
-                            hip(b.fcd.ensure((size_t)nf * P * sizeof(float)), "alloc");
-                            hip(b.fpr.ensure((size_t)nf * P * sizeof(int32_t)), "alloc");
-                            if (rs) hip(b.fbd.ensure((size_t)nf * sizeof(float)), "alloc");
-                            // (sharded rows: the flagged queries' reduced bounds of the scan -- only exported entries within
-                            //  them can be members of the recall_num-heap, only those get an exact distance)
-                            if (rc == GAMMA_HIP_OK && rs) abi(gamma_hip_gather_rows(h, b.bound.as<float>() + q0, 1, lists[o] + f0, nf, b.fbd.p));
-                            if (rc == GAMMA_HIP_OK) {
-                                abi(gamma_hip_gather_rows(h, b.x.as<float>() + (size_t)q0 * d, d, lists[o] + f0, nf, b.fx.p));
-                                abi(gamma_hip_gather_rows(h, b.cdis.as<float>() + (size_t)q0 * P, P, lists[o] + f0, nf, b.fcd.p));
-                                abi(gamma_hip_gather_rows(h, b.probe.as<int32_t>() + (size_t)q0 * P, P, lists[o] + f0, nf, b.fpr.p));
-                            }
-                            hip(hipEventRecord(b.ev_tie, s), "record");
-                        }
-                        bool ok2 = g->bar.arrive(rc == GAMMA_HIP_OK);   // the owner's compact inputs are on its stream
-                        gamma_hip_group::Member& ob = g->mb[o];
-                        hip(b.sx.ensure((size_t)nf * d * sizeof(float)), "alloc");
-                        hip(b.scd.ensure((size_t)nf * P * sizeof(float)), "alloc");
-                        hip(b.spr.ensure((size_t)nf * P * sizeof(int32_t)), "alloc");
-                        hip(b.ex_off.ensure((size_t)nf * (P + 1) * sizeof(int32_t)), "alloc");
-                        if (rs) hip(b.sbd.ensure((size_t)nf * sizeof(float)), "alloc");
-                        rowmax[i] = 0;
-                        if (ok2 && rc == GAMMA_HIP_OK) {
-                            if (i != o) hip(hipStreamWaitEvent(s, ob.ev_tie, 0), "wait");
-                            hip(copy_between(b.sx.p, g->dev[i], ob.fx.p, g->dev[o], (size_t)nf * d * sizeof(float), s), "tie inputs");
-                            hip(copy_between(b.scd.p, g->dev[i], ob.fcd.p, g->dev[o], (size_t)nf * P * sizeof(float), s), "tie inputs");
-                            hip(copy_between(b.spr.p, g->dev[i], ob.fpr.p, g->dev[o], (size_t)nf * P * sizeof(int32_t), s), "tie inputs");
-                            if (rs) hip(copy_between(b.sbd.p, g->dev[i], ob.fbd.p, g->dev[o], (size_t)nf * sizeof(float), s), "tie inputs");
-                            // how long this member's export rows get: the exports of all members share one row stride
-                            int64_t mine = 0;
-                            if (rc == GAMMA_HIP_OK) abi(gamma_hip_ivfpq_shard_export_rows(h, &pp, nf, b.spr.as<int32_t>(), &mine));
-                            rowmax[i] = mine;
-                        }
-                        ok2 = g->bar.arrive(rc == GAMMA_HIP_OK);   // every member's longest row is known
-                        int64_t stride = 4;
-                        for (int j = 0; j < W; j++) stride = std::max<int64_t>(stride, (rowmax[j] + 3) & ~(int64_t)3);
-                        hip(b.ex_vals.ensure((size_t)nf * stride * sizeof(float)), "alloc");
-                        hip(b.ex_ids.ensure((size_t)nf * stride * sizeof(int64_t)), "alloc");
-                        if (ok2 && rc == GAMMA_HIP_OK)
-                            abi(gamma_hip_ivfpq_shard_export(h, &pp, nf, b.sx.as<float>(), b.scd.as<float>(), b.spr.as<int32_t>(), stride,
-                                                             b.ex_vals.as<float>(), b.ex_ids.as<int64_t>(), b.ex_off.as<int32_t>()));
-                        if (rs) hip(b.ex_ex.ensure((size_t)nf * stride * sizeof(float)), "alloc");
-                        if (rs && ok2 && rc == GAMMA_HIP_OK)
-                            abi(gamma_hip_ivfpq_shard_export_exact(h, &pp, nf, b.sx.as<float>(), b.ex_vals.as<float>(), b.ex_ids.as<int64_t>(),
-                                                                   b.ex_off.as<int32_t>(), stride, b.sbd.as<float>(), b.ex_ex.as<float>()));
-                        hip(hipStreamSynchronize(s), "sync");
-                        ok2 = g->bar.arrive(rc == GAMMA_HIP_OK);   // every member's export is complete
-                        if (i == o && ok2) {
-                            hip(b.av.ensure((size_t)W * nf * stride * sizeof(float)), "alloc");
-                            hip(b.ai.ensure((size_t)W * nf * stride * sizeof(int64_t)), "alloc");
-                            hip(b.ao.ensure((size_t)W * nf * (P + 1) * sizeof(int32_t)), "alloc");
-                            if (rs) hip(b.ae.ensure((size_t)W * nf * stride * sizeof(float)), "alloc");
-                            for (int j = 0; j < W && rc == GAMMA_HIP_OK; j++) {
-                                if (rs)
-                                    hip(copy_between(b.ae.as<float>() + (size_t)j * nf * stride, g->dev[i], g->mb[j].ex_ex.p, g->dev[j],
-                                                     (size_t)nf * stride * sizeof(float), s), "exports");
-                                hip(copy_between(b.av.as<float>() + (size_t)j * nf * stride, g->dev[i], g->mb[j].ex_vals.p, g->dev[j],
-                                                 (size_t)nf * stride * sizeof(float), s), "exports");
-                                hip(copy_between(b.ai.as<int64_t>() + (size_t)j * nf * stride, g->dev[i], g->mb[j].ex_ids.p, g->dev[j],
-                                                 (size_t)nf * stride * sizeof(int64_t), s), "exports");
-                                hip(copy_between(b.ao.as<int32_t>() + (size_t)j * nf * (P + 1), g->dev[i], g->mb[j].ex_off.p, g->dev[j],
-                                                 (size_t)nf * (P + 1) * sizeof(int32_t), s), "exports");
-                            }
-                            if (rc == GAMMA_HIP_OK && rs)
-                                abi(gamma_hip_ivfpq_merge_replay_exact(h, &pp, W, nf, b.x.as<float>() + (size_t)q0 * d, stride, b.av.as<float>(),
-                                                                       b.ai.as<int64_t>(), b.ao.as<int32_t>(), b.ae.as<float>(), k, lists[o] + f0,
-                                                                       b.D.as<float>(), b.I.as<int64_t>()));
-                            else if (rc == GAMMA_HIP_OK)
-                                abi(gamma_hip_ivfpq_merge_replay(h, &pp, W, nf, b.x.as<float>() + (size_t)q0 * d, stride, b.av.as<float>(),
-                                                                 b.ai.as<int64_t>(), b.ao.as<int32_t>(), k, lists[o] + f0, b.D.as<float>(),
-                                                                 b.I.as<int64_t>()));
-                            hip(hipStreamSynchronize(s), "sync");
-                        }
-                        (void)g->bar.arrive(rc == GAMMA_HIP_OK);   // the exports may be overwritten
-                    }
-                }
-            }
-        }
-        if (gdbg && i == 0) fprintf(stderr, "group: tie phase done %.3f ms after the merge was enqueued\n", since(tp0));
-        // (all_ok: the snapshot of the last barrier every member passed -- the tie phase's own failures show in rc)
-        if (all_ok && nql > 0) {   // the slice's rows to the caller
-            if (rc == GAMMA_HIP_OK && on_device) {
-                hip(copy_between(distances + (size_t)q0 * k, g->dev[0], b.D.p, g->dev[i], (size_t)nql * k * sizeof(float), s), "results");
-                hip(copy_between(labels + (size_t)q0 * k, g->dev[0], b.I.p, g->dev[i], (size_t)nql * k * sizeof(int64_t), s), "results");
-            } else if (rc == GAMMA_HIP_OK) {
-                hip(hipMemcpyAsync(distances + (size_t)q0 * k, b.D.p, (size_t)nql * k * sizeof(float), hipMemcpyDeviceToHost, s), "D2H");
-                hip(hipMemcpyAsync(labels + (size_t)q0 * k, b.I.p, (size_t)nql * k * sizeof(int64_t), hipMemcpyDeviceToHost, s), "D2H");
-            }
-        }
-        hip(hipStreamSynchronize(s), "sync");
-        (void)g->bar.arrive(rc == GAMMA_HIP_OK);   // nobody is reading this member's tables any more
+        Ctx m(c, i);
+        member_search(m);
     });
     for (int i = 0; i < W; i++)
-        if (rcs[i] != GAMMA_HIP_OK) return gfail(g, rcs[i], "member " + std::to_string(i) + ": " + errs[i]);
+        if (c.rcs[i] != GAMMA_HIP_OK) return gfail(g, c.rcs[i], "member " + std::to_string(i) + ": " + c.errs[i]);
     return GAMMA_HIP_OK;
 }
 
-// ---- IVFFLAT (gamma_index_ivfflat.cc search_preassigned per member, faiss:IndexShards.cpp:283-345 for the merge) --------------
-// The IVFPQ path's sequence without re-rank and without the bound reduction: coarse quantizer of the own slice | assignment
-// exchanged | shard search of the whole batch over the owned lists (rows from the member's dense or sparse store) | the
-// [W][per][k] tables and cut flags of the own slice pulled | merge | tie phase in rounds of at most 256 flagged queries.
-// Same barriers, same go / no-go snapshots: a member that fails in a phase still arrives at every meeting point, and the call
-// returns that member's error.  The transport is device-to-device copies ordered by events, whatever the group's transport
-// setting says (gamma_hip_group_transport_note says so).  Every entry of the members this needs comes through the table of
-// gamma_hip_group_ext.h.
-static int group_ivfflat_search(gamma_hip_group* g, const gamma_hip_search_params* p, int nq, const float* x, int k,
-                                float* distances, int64_t* labels, bool on_device) {
-    if (!g || !p) return GAMMA_HIP_EINVAL;
-    if (nq < 0) return GAMMA_HIP_EINVAL;
-    if (k <= 0 || nq == 0) return GAMMA_HIP_OK;
-    if (!x || !distances || !labels) return GAMMA_HIP_EINVAL;
-    std::lock_guard<std::mutex> lk(g->mu);
-    const gamma_group_ext::IvfflatOps* ops = ivfflat_ops();
-    if (!ops) return gfail(g, GAMMA_HIP_EUNSUPPORTED, "ivfflat_search: the IVFFLAT search of the group is not built in");
-    if (g->owner.empty()) return gfail(g, GAMMA_HIP_EINVAL, "ivfflat_search: gamma_hip_group_set_owners first");
-    const int W = (int)g->m.size();
-    const int d = gamma_hip_ivfpq_dim(g->m[0]);
-    if (d <= 0) return gfail(g, GAMMA_HIP_EINVAL, "ivfflat_search: members not initialised");
-    const int P = p->nprobe;
-    if (P <= 0) return gfail(g, GAMMA_HIP_EINVAL, "ivfflat_search: nprobe out of range");
-    gamma_hip_search_params pp = *p;
-    if (pp.coarse_mode < 0) pp.coarse_mode = nq < 20 ? 0 : 1;   // resolved on the WHOLE call: the slices must agree
-    if (g->transport == 1 && !g->replicate && g->transport_note.find("IVFFLAT") == std::string::npos)
-        g->transport_note += std::string(g->transport_note.empty() ? "" : "; ") + "IVFFLAT search: peer copies (RCCL serves the IVFPQ search only)";
-    const int per = (nq + W - 1) / W;
-    std::vector<int> rcs(W, GAMMA_HIP_OK);
-    std::vector<std::string> errs(W);
-    std::vector<int64_t> rowmax(W, 0);
-    std::vector<int> nfl(W, 0);
-    std::vector<const int32_t*> lists(W, nullptr);
-    auto slice = [&](int i, int* q0, int* q1) {
-        *q0 = std::min(nq, i * per);
-        *q1 = std::min(nq, *q0 + per);
-    };
-    g->run([&](int i) {
-        gamma_hip_group::Member& b = g->mb[i];
-        gamma_hip_index* h = g->m[i];
-        hipStream_t s = (hipStream_t)gamma_hip_stream(h);
-        int q0, q1;
-        slice(i, &q0, &q1);
-        const int nql = q1 - q0;
-        int& rc = rcs[i];
-        auto hip = [&](hipError_t e, const char* what) {
-            if (e != hipSuccess && rc == GAMMA_HIP_OK) {
-                rc = e == hipErrorOutOfMemory ? GAMMA_HIP_ENOMEM : GAMMA_HIP_EDEVICE;
-                errs[i] = std::string(what) + ": " + hipGetErrorString(e);
-            }
-        };
-        auto abi = [&](int r) {
-            if (r != GAMMA_HIP_OK && rc == GAMMA_HIP_OK) {
-                rc = r;
-                errs[i] = std::string(gamma_hip_strerror(r)) + " (" + gamma_hip_last_error(h) + ")";
-            }
-        };
-        hip(hipSetDevice(g->dev[i]), "hipSetDevice");
-        if (g->replicate) {
-            // query-parallel over replicated lists: the member answers its slice with the single-handle search
-            if (nql <= 0 || rc != GAMMA_HIP_OK) return;
-            const bool local = on_device && g->dev[i] == g->dev[0];
-            const float* xs = x + (size_t)q0 * d;
-            float* Ds = distances + (size_t)q0 * k;
-            int64_t* Is = labels + (size_t)q0 * k;
-            if (!local) {
-                hip(b.x.ensure((size_t)nql * d * sizeof(float)), "alloc");
-                hip(b.D.ensure((size_t)nql * k * sizeof(float)), "alloc");
-                hip(b.I.ensure((size_t)nql * k * sizeof(int64_t)), "alloc");
-                if (rc != GAMMA_HIP_OK) return;
-                if (on_device) hip(copy_between(b.x.p, g->dev[i], xs, g->dev[0], (size_t)nql * d * sizeof(float), s), "queries to the member");
-                else hip(hipMemcpyAsync(b.x.p, xs, (size_t)nql * d * sizeof(float), hipMemcpyHostToDevice, s), "H2D queries");
-            }
-            if (rc == GAMMA_HIP_OK)
-                abi(ops->search_device(h, &pp, nql, local ? xs : b.x.as<float>(), k, local ? Ds : b.D.as<float>(),
-                                       local ? Is : b.I.as<int64_t>()));
-            if (rc == GAMMA_HIP_OK && !local) {
-                if (on_device) {
-                    hip(copy_between(Ds, g->dev[0], b.D.p, g->dev[i], (size_t)nql * k * sizeof(float), s), "results");
-                    hip(copy_between(Is, g->dev[0], b.I.p, g->dev[i], (size_t)nql * k * sizeof(int64_t), s), "results");
-                } else {
-                    hip(hipMemcpyAsync(Ds, b.D.p, (size_t)nql * k * sizeof(float), hipMemcpyDeviceToHost, s), "D2H");
-                    hip(hipMemcpyAsync(Is, b.I.p, (size_t)nql * k * sizeof(int64_t), hipMemcpyDeviceToHost, s), "D2H");
-                }
-            }
-            hip(hipStreamSynchronize(s), "sync");
-            return;
-        }
-        hip(b.x.ensure((size_t)nq * d * sizeof(float)), "alloc");
-        hip(b.cdis.ensure((size_t)W * per * P * sizeof(float)), "alloc");
-        hip(b.probe.ensure((size_t)W * per * P * sizeof(int32_t)), "alloc");
-        hip(b.rdis.ensure((size_t)nq * k * sizeof(float)), "alloc");
-        hip(b.rids.ensure((size_t)nq * k * sizeof(int64_t)), "alloc");
-        hip(b.all_dis.ensure((size_t)W * per * k * sizeof(float)), "alloc");
-        hip(b.all_ids.ensure((size_t)W * per * k * sizeof(int64_t)), "alloc");
-        hip(b.D.ensure((size_t)per * k * sizeof(float)), "alloc");
-        hip(b.I.ensure((size_t)per * k * sizeof(int64_t)), "alloc");
-        // 0. the whole batch to every member; coarse quantizer for the own slice
-        if (rc == GAMMA_HIP_OK) {
-            if (on_device) hip(copy_between(b.x.p, g->dev[i], x, g->dev[0], (size_t)nq * d * sizeof(float), s), "queries to the member");
-            else hip(hipMemcpyAsync(b.x.p, x, (size_t)nq * d * sizeof(float), hipMemcpyHostToDevice, s), "H2D queries");
-            if (nql > 0)
-                abi(ops->coarse_device(h, &pp, nql, b.x.as<float>() + (size_t)q0 * d, b.cdis.as<float>() + (size_t)q0 * P,
-                                       b.probe.as<int32_t>() + (size_t)q0 * P));
-            hip(hipEventRecord(b.ev_coarse, s), "record");
-        }
-        bool all_ok = g->bar.arrive(rc == GAMMA_HIP_OK);   // every member's assignment is on its stream
-        // 1. pull the other slices of the assignment; shard search of the whole batch
-        if (all_ok) {
-            for (int j = 0; j < W; j++) {
-                if (j == i) continue;
-                int a0, a1;
-                slice(j, &a0, &a1);
-                if (a1 <= a0) continue;
-                hip(hipStreamWaitEvent(s, g->mb[j].ev_coarse, 0), "wait");
-                hip(copy_between(b.cdis.as<float>() + (size_t)a0 * P, g->dev[i], g->mb[j].cdis.as<float>() + (size_t)a0 * P, g->dev[j],
-                                 (size_t)(a1 - a0) * P * sizeof(float), s), "assignment exchange");
-                hip(copy_between(b.probe.as<int32_t>() + (size_t)a0 * P, g->dev[i], g->mb[j].probe.as<int32_t>() + (size_t)a0 * P,
-                                 g->dev[j], (size_t)(a1 - a0) * P * sizeof(int32_t), s), "assignment exchange");
-            }
-            if (rc == GAMMA_HIP_OK)
-                abi(ops->search_shard(h, &pp, nq, b.x.as<float>(), b.cdis.as<float>(), b.probe.as<int32_t>(), k, b.rdis.as<float>(),
-                                      b.rids.as<int64_t>()));
-            hip(b.cutf.ensure((size_t)nq), "alloc");
-            if (rc == GAMMA_HIP_OK) abi(gamma_hip_ivfpq_shard_cut_flags(h, nq, b.cutf.as<uint8_t>()));
-            hip(b.cutall.ensure((size_t)W * per), "alloc");
-            hip(hipEventRecord(b.ev_scan, s), "record");
-        }
-        all_ok = g->bar.arrive(rc == GAMMA_HIP_OK);   // every member's tables are on its stream
-        // 2. the [W][per][k] tables and the cut flags of the own slice; 3. merge
-        if (all_ok && nql > 0) {
-            for (int j = 0; j < W; j++) {
-                if (j != i) hip(hipStreamWaitEvent(s, g->mb[j].ev_scan, 0), "wait");
-                hip(copy_between(b.all_dis.as<float>() + (size_t)j * per * k, g->dev[i], g->mb[j].rdis.as<float>() + (size_t)q0 * k,
-                                 g->dev[j], (size_t)nql * k * sizeof(float), s), "candidate exchange");
-                hip(copy_between(b.all_ids.as<int64_t>() + (size_t)j * per * k, g->dev[i], g->mb[j].rids.as<int64_t>() + (size_t)q0 * k,
-                                 g->dev[j], (size_t)nql * k * sizeof(int64_t), s), "candidate exchange");
-                hip(copy_between(b.cutall.as<uint8_t>() + (size_t)j * per, g->dev[i], g->mb[j].cutf.as<uint8_t>() + q0, g->dev[j],
-                                 (size_t)nql, s), "cut flags");
-            }
-            if (rc == GAMMA_HIP_OK) abi(gamma_hip_ivfpq_merge_set_shard_flags(h, b.cutall.as<uint8_t>()));
-            if (rc == GAMMA_HIP_OK)
-                abi(ops->merge(h, &pp, W, per, k, b.all_dis.as<float>(), b.all_ids.as<int64_t>(), 0, nql, b.D.as<float>(), b.I.as<int64_t>()));
-        }
-        // 4. exact ties across members: rounds of at most fcap flagged queries of one owner
-        {
-            int nf_i = 0;
-            const int32_t* list_i = nullptr;
-            if (all_ok && nql > 0 && rc == GAMMA_HIP_OK) abi(gamma_hip_ivfpq_merge_flagged(h, &nf_i, &list_i));
-            nfl[i] = rc == GAMMA_HIP_OK ? nf_i : 0;
-            lists[i] = list_i;
-            all_ok = g->bar.arrive(rc == GAMMA_HIP_OK);
-            int total = 0;
-            for (int j = 0; j < W; j++) total += nfl[j];
-            if (all_ok && total > 0) {
-                const int fcap = 256;
-                for (int o = 0; o < W; o++) {
-                    for (int f0 = 0; f0 < nfl[o]; f0 += fcap) {
-                        const int nf = std::min(fcap, nfl[o] - f0);
-                        if (i == o) {   // the flagged queries' vectors and assignment rows, compact
-                            hip(b.fx.ensure((size_t)nf * d * sizeof(float)), "alloc");
-                            hip(b.fpr.ensure((size_t)nf * P * sizeof(int32_t)), "alloc");
-                            if (rc == GAMMA_HIP_OK) {
-                                abi(gamma_hip_gather_rows(h, b.x.as<float>() + (size_t)q0 * d, d, lists[o] + f0, nf, b.fx.p));
-                                abi(gamma_hip_gather_rows(h, b.probe.as<int32_t>() + (size_t)q0 * P, P, lists[o] + f0, nf, b.fpr.p));
-                            }
-                            hip(hipEventRecord(b.ev_tie, s), "record");
-                        }
-                        bool ok2 = g->bar.arrive(rc == GAMMA_HIP_OK);   // the owner's compact inputs are on its stream
-                        gamma_hip_group::Member& ob = g->mb[o];
-                        hip(b.sx.ensure((size_t)nf * d * sizeof(float)), "alloc");
-                        hip(b.spr.ensure((size_t)nf * P * sizeof(int32_t)), "alloc");
-                        hip(b.ex_off.ensure((size_t)nf * (P + 1) * sizeof(int32_t)), "alloc");
-                        rowmax[i] = 0;
-                        if (ok2 && rc == GAMMA_HIP_OK) {
-                            if (i != o) hip(hipStreamWaitEvent(s, ob.ev_tie, 0), "wait");
-                            hip(copy_between(b.sx.p, g->dev[i], ob.fx.p, g->dev[o], (size_t)nf * d * sizeof(float), s), "tie inputs");
-                            hip(copy_between(b.spr.p, g->dev[i], ob.fpr.p, g->dev[o], (size_t)nf * P * sizeof(int32_t), s), "tie inputs");
-                            int64_t mine = 0;
-                            if (rc == GAMMA_HIP_OK) abi(ops->shard_export_rows(h, &pp, nf, b.spr.as<int32_t>(), &mine));
-                            rowmax[i] = mine;
-                        }
-                        ok2 = g->bar.arrive(rc == GAMMA_HIP_OK);   // every member's longest row is known
-                        int64_t stride = 4;
-                        for (int j = 0; j < W; j++) stride = std::max<int64_t>(stride, (rowmax[j] + 3) & ~(int64_t)3);
-                        hip(b.ex_vals.ensure((size_t)nf * stride * sizeof(float)), "alloc");
-                        hip(b.ex_ids.ensure((size_t)nf * stride * sizeof(int64_t)), "alloc");
-                        if (ok2 && rc == GAMMA_HIP_OK)
-                            abi(ops->shard_export(h, &pp, nf, b.sx.as<float>(), b.spr.as<int32_t>(), stride, b.ex_vals.as<float>(),
-                                                  b.ex_ids.as<int64_t>(), b.ex_off.as<int32_t>()));
-                        hip(hipStreamSynchronize(s), "sync");
-                        ok2 = g->bar.arrive(rc == GAMMA_HIP_OK);   // every member's export is complete
-                        if (i == o && ok2) {
-                            hip(b.av.ensure((size_t)W * nf * stride * sizeof(float)), "alloc");
-                            hip(b.ai.ensure((size_t)W * nf * stride * sizeof(int64_t)), "alloc");
-                            hip(b.ao.ensure((size_t)W * nf * (P + 1) * sizeof(int32_t)), "alloc");
-                            for (int j = 0; j < W && rc == GAMMA_HIP_OK; j++) {
-                                hip(copy_between(b.av.as<float>() + (size_t)j * nf * stride, g->dev[i], g->mb[j].ex_vals.p, g->dev[j],
-                                                 (size_t)nf * stride * sizeof(float), s), "exports");
-                                hip(copy_between(b.ai.as<int64_t>() + (size_t)j * nf * stride, g->dev[i], g->mb[j].ex_ids.p, g->dev[j],
-                                                 (size_t)nf * stride * sizeof(int64_t), s), "exports");
-                                hip(copy_between(b.ao.as<int32_t>() + (size_t)j * nf * (P + 1), g->dev[i], g->mb[j].ex_off.p, g->dev[j],
-                                                 (size_t)nf * (P + 1) * sizeof(int32_t), s), "exports");
-                            }
-                            if (rc == GAMMA_HIP_OK)
-                                abi(ops->merge_replay(h, &pp, W, nf, b.x.as<float>() + (size_t)q0 * d, stride, b.av.as<float>(),
-                                                      b.ai.as<int64_t>(), b.ao.as<int32_t>(), k, lists[o] + f0, b.D.as<float>(),
-                                                      b.I.as<int64_t>()));
-                            hip(hipStreamSynchronize(s), "sync");
-                        }
-                        (void)g->bar.arrive(rc == GAMMA_HIP_OK);   // the exports may be overwritten
-                    }
-                }
-            }
-        }
-        if (all_ok && nql > 0) {   // the slice's rows to the caller
-            if (rc == GAMMA_HIP_OK && on_device) {
-                hip(copy_between(distances + (size_t)q0 * k, g->dev[0], b.D.p, g->dev[i], (size_t)nql * k * sizeof(float), s), "results");
-                hip(copy_between(labels + (size_t)q0 * k, g->dev[0], b.I.p, g->dev[i], (size_t)nql * k * sizeof(int64_t), s), "results");
-            } else if (rc == GAMMA_HIP_OK) {
-                hip(hipMemcpyAsync(distances + (size_t)q0 * k, b.D.p, (size_t)nql * k * sizeof(float), hipMemcpyDeviceToHost, s), "D2H");
-                hip(hipMemcpyAsync(labels + (size_t)q0 * k, b.I.p, (size_t)nql * k * sizeof(int64_t), hipMemcpyDeviceToHost, s), "D2H");
-            }
-        }
-        hip(hipStreamSynchronize(s), "sync");
-        (void)g->bar.arrive(rc == GAMMA_HIP_OK);   // nobody is reading this member's tables any more
-    });
-    for (int i = 0; i < W; i++)
-        if (rcs[i] != GAMMA_HIP_OK) return gfail(g, rcs[i], "member " + std::to_string(i) + ": " + errs[i]);
-    return GAMMA_HIP_OK;
+}  // namespace
+
+extern "C" {
+
+int gamma_hip_group_ivfpq_search(gamma_hip_group* g, const gamma_hip_search_params* p, int nq, const float* x, int k,
+                                 float* distances, int64_t* labels) {
+    return group_search(g, &kIvfpqFamily, p, nq, x, k, distances, labels, false);
+}
+
+int gamma_hip_group_ivfpq_search_device(gamma_hip_group* g, const gamma_hip_search_params* p, int nq, const float* d_x, int k,
+                                        float* d_distances, int64_t* d_labels) {
+    return group_search(g, &kIvfpqFamily, p, nq, d_x, k, d_distances, d_labels, true);
 }
 
 int gamma_hip_group_ivfflat_search(gamma_hip_group* g, const gamma_hip_search_params* p, int nq, const float* x, int k,
                                    float* distances, int64_t* labels) {
-    return group_ivfflat_search(g, p, nq, x, k, distances, labels, false);
+    return group_search(g, ivfflat_family(), p, nq, x, k, distances, labels, false);
 }
 
 int gamma_hip_group_ivfflat_search_device(gamma_hip_group* g, const gamma_hip_search_params* p, int nq, const float* d_x, int k,
                                           float* d_distances, int64_t* d_labels) {
-    return group_ivfflat_search(g, p, nq, d_x, k, d_distances, d_labels, true);
+    return group_search(g, ivfflat_family(), p, nq, d_x, k, d_distances, d_labels, true);
 }
 
 }  // extern "C"

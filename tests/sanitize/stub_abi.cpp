@@ -290,7 +290,8 @@ int gamma_hip_ivfpq_search_device_wait(gamma_hip_index* h, const gamma_hip_searc
 int gamma_hip_flat_search_device_wait(gamma_hip_index* h, const gamma_hip_search_params* p, int nq, const float* x, int k, float* D, int64_t* I) {
     return gamma_hip_flat_search(h, p, nq, x, k, D, I);
 }
-/* list-shard entry points: not reached in replicate placement */
+/* list-shard entry points: not reached in replicate placement; group_protocol.cc scripts them (Makefile: group_protocol_tsan) */
+#ifndef GAMMA_STUB_SCRIPTED_SHARD
 int gamma_hip_bound_combine(void*, float*, const float*, int, int) { return GAMMA_HIP_EUNSUPPORTED; }
 int gamma_hip_raw_put(gamma_hip_index*, int64_t, const int64_t*, const float*) { return GAMMA_HIP_EUNSUPPORTED; }
 int gamma_hip_ivfpq_shard_exact(gamma_hip_index*, const gamma_hip_search_params*, int, const float*, const int64_t*, int, float*) { return GAMMA_HIP_EUNSUPPORTED; }
@@ -316,4 +317,5 @@ int gamma_hip_ivfpq_shard_export(gamma_hip_index*, const gamma_hip_search_params
                                  float*, int64_t*, int32_t*) { return GAMMA_HIP_EUNSUPPORTED; }
 int gamma_hip_ivfpq_merge_replay(gamma_hip_index*, const gamma_hip_search_params*, int, int, const float*, int64_t, const float*, const int64_t*,
                                  const int32_t*, int, const int32_t*, float*, int64_t*) { return GAMMA_HIP_EUNSUPPORTED; }
+#endif
 }
