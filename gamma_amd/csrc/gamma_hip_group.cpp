@@ -43,6 +43,7 @@
 
 #include "../../include/gamma_hip.h"
 #include "gamma_hip_group_ext.h"
+#include "gamma_hip_group_rccl.h"
 
 namespace {
 
@@ -105,21 +106,12 @@ struct Barrier {
 //      (GAMMA_HIP_GROUP_RCCL=1 or gamma_hip_group_set_transport): peer copies and the barriers below do the same job, and a
 //      group whose members share a device (tests) cannot form a communicator. ----
 namespace {
-struct RcclApi {
-    void* lib = nullptr;
-    int (*CommInitAll)(void**, int, const int*) = nullptr;
-    int (*CommDestroy)(void*) = nullptr;
-    int (*AllGather)(const void*, void*, size_t, int, void*, hipStream_t) = nullptr;
-    int (*AllReduce)(const void*, void*, size_t, int, int, void*, hipStream_t) = nullptr;
-    int (*Send)(const void*, size_t, int, int, void*, hipStream_t) = nullptr;
-    int (*Recv)(void*, size_t, int, int, void*, hipStream_t) = nullptr;
-    int (*GroupStart)() = nullptr;
-    int (*GroupEnd)() = nullptr;
-    const char* (*GetErrorString)(int) = nullptr;
-    bool ok() const { return CommInitAll && CommDestroy && AllGather && AllReduce && Send && Recv && GroupStart && GroupEnd; }
-};
-constexpr int kNcclChar = 0;   // ncclInt8: the exchanges are counted in bytes
-constexpr int kNcclFloat = 7, kNcclMax = 2, kNcclMin = 3;   // ncclFloat32, ncclMax, ncclMin (nccl.h)
+// (the entries' pointer types and the enumerators: gamma_hip_group_rccl.h, checked against the installed rccl.h by the tests)
+using gamma_group_rccl::RcclApi;
+using gamma_group_rccl::kNcclChar;
+using gamma_group_rccl::kNcclFloat;
+using gamma_group_rccl::kNcclMax;
+using gamma_group_rccl::kNcclMin;
 RcclApi* rccl_api() {
     static RcclApi api;
     static std::once_flag once;
