@@ -116,10 +116,7 @@ int gamma_hip_destroy(gamma_hip_index* h) {
     }
     if (h->raw_vmm) {   // the mapped store: unmap the chunks, release them, free the range
         h->raw_vm.release();
-        h->d_raw = nullptr;
-        h->d_raw_h = nullptr;
-        h->d_raw_b = nullptr;
-        h->d_raw_q = nullptr;
+        h->raw_p = nullptr;
     }
     // (release() of a range that was never reserved does nothing; an arena that left virtual memory management after a
     //  failed repack read-back still owns its reserved ranges)
@@ -136,7 +133,7 @@ int gamma_hip_destroy(gamma_hip_index* h) {
         h->d_sums = nullptr;
     }
     if (h->d_raw_slot) (void)hipFree(h->d_raw_slot);
-    void* ptrs[] = {h->d_list_rank, h->d_raw, h->d_raw_h, h->d_raw_b, h->d_raw_q, h->d_sq8_tab, h->d_bitmap, h->d_cc, h->d_cc_norms, h->d_pqc, h->d_T2, h->d_codes,
+    void* ptrs[] = {h->d_list_rank, h->raw_p, h->d_sq8_tab, h->d_bitmap, h->d_cc, h->d_cc_norms, h->d_pqc, h->d_T2, h->d_codes,
                     h->d_ids, h->d_list_mask, h->d_scan_codes, h->d_tie_stats, h->d_v2d, h->d_sums, h->d_t2max, h->d_bound_stat,
                     h->d_bin_cc, h->d_bin_stats, h->d_bf_codes, h->d_bf_stats, h->d_cc_img, h->d_cbf_stat, h->d_opq};
     for (void* p : ptrs)

@@ -192,28 +192,28 @@ struct gamma_hip_index {
     std::string err;
 
     // raw vector store
+    // The rows live behind ONE pointer, raw_p, and raw_et says what they are (gh::RowType, the numbering of
+    // gamma_hip_raw_elem_type; fixed at the first init): fp32 (gamma_hip_raw_init), IEEE binary16 (_init_f16: rows of 2 * raw_d
+    // bytes, the writers round the caller's fp32 on the writer stream, store_kernels.hip), uint8 / int8 (_init_i8: the writers
+    // take fp32 that converts exactly, checked on the host, gamma_hip_raw_i8_check) or one scalar-quantised code per element
+    // (_init_sq8).  One growth machinery for all of them, rows of raw_d * raw_esz() bytes.
+    // Who reads them: a reader of every element type takes raw_rows_ref() and switches on its et.  A reader that was only ever
+    // taught fp32 rows takes raw_f32() and nothing else -- null on a narrow store, so its "needs the raw store" check fails
+    // there instead of misreading bytes.  Nothing outside the store's own bookkeeping touches raw_p.
     int raw_d = 0;
-    float* d_raw = nullptr;
+    int raw_et = gh::ROW_F32;
+    void* raw_p = nullptr;
     int64_t nraw = 0, raw_cap = 0;
-    // gamma_hip_raw_init_f16: rows of IEEE binary16 behind a pointer of their own -- d_raw stays null, so a reader that was
-    // not taught the half rows fails its "needs the raw store" check instead of misreading bytes.  Same growth machinery,
-    // rows of 2 * raw_d bytes; the writers round the caller's fp32 on the writer stream (store_kernels.hip).
-    bool raw_half = false;
-    uint16_t* d_raw_h = nullptr;
-    // gamma_hip_raw_init_i8: rows of one byte per element, uint8 (raw_byte = 1) or int8 (2), behind a third pointer for the same
-    // reason; rows of raw_d bytes.  The writers take fp32 that converts exactly, checked on the host (gamma_hip_raw_i8_check).
-    int raw_byte = 0;
-    uint8_t* d_raw_b = nullptr;
-    // gamma_hip_raw_init_sq8: rows of one scalar-quantised byte per element behind a fourth pointer, again for that reason; rows of
-    // raw_d bytes, the byte store's growth machinery.  sq8_vmin / sq8_vmax: the ranges (empty until set or trained); d_sq8_tab:
-    // 2 * raw_d float2 -- the readers' decode table {step[j], vmin[j]} and behind it the writers' encode table {inv[j], vmin[j]}.
-    bool raw_sq8 = false;
-    uint8_t* d_raw_q = nullptr;
+    // sq8 store: sq8_vmin / sq8_vmax: the ranges (empty until set or trained); d_sq8_tab: 2 * raw_d float2 -- the readers'
+    // decode table {step[j], vmin[j]} and behind it the writers' encode table {inv[j], vmin[j]}.
     std::vector<float> sq8_vmin, sq8_vmax, sq8_step;
     float* d_sq8_tab = nullptr;
-    size_t raw_esz() const { return raw_byte || raw_sq8 ? 1 : raw_half ? sizeof(uint16_t) : sizeof(float); }
-    bool has_raw_rows() const { return d_raw != nullptr || d_raw_h != nullptr || d_raw_b != nullptr || d_raw_q != nullptr; }
-    int raw_elem_type() const { return raw_sq8 ? 4 : raw_byte ? 1 + raw_byte : raw_half ? 1 : 0; }   // 0 fp32, 1 float16, 2 uint8, 3 int8, 4 sq8
+    size_t raw_esz() const { return gh::row_elem_bytes(raw_et); }
+    bool has_raw_rows() const { return raw_p != nullptr; }
+    int raw_elem_type() const { return raw_et; }
+    bool raw_narrow() const { return raw_et != gh::ROW_F32; }   // any store but fp32
+    const float* raw_f32() const { return raw_et == gh::ROW_F32 ? static_cast<const float*>(raw_p) : nullptr; }
+    float* raw_f32() { return raw_et == gh::ROW_F32 ? static_cast<float*>(raw_p) : nullptr; }
     // raw vectors SHARDED with their lists (gamma_hip_raw_put, round 6): the store holds the rows of the vectors in this shard's
     // lists only, in arrival order; raw_slot[vid] = row (-1: held by another shard).  Such a handle re-ranks nothing by itself --
     // has_rank searches, flat search and raw_gets refuse -- it serves _shard_exact / _shard_export_exact.
@@ -504,6 +504,12 @@ struct WriteLock {
 namespace ghi {
 
 using H = gamma_hip_index;
+
+// the raw store's rows as the kernels of every element type take them (kernels.h): base pointer, element type and, for an sq8
+// store, the decode table
+inline gh::RowsRef raw_rows_ref(const H* h) {
+    return gh::RowsRef{h->raw_p, h->raw_et, h->raw_et == gh::ROW_SQ8 ? h->d_sq8_tab : nullptr};
+}
 
 // a search-type call: search_mu for the whole call, mu while it reads the handle and enqueues
 struct SearchLock {

@@ -836,12 +836,7 @@ int ivfpq_stage_b(H* h, const gamma_hip_search_params* p, int nq, const float* d
         a.slice_cap = h->tie.cap;
         a.x = d_x;
         a.d = h->d;
-        a.raw = h->d_raw;
-        a.raw_h = h->d_raw_h;   // (all but one of the three are null)
-        a.raw_b = h->d_raw_b;
-        a.raw_b_signed = h->raw_byte == 2;
-        a.raw_q = h->d_raw_q;
-        a.sq8_tab = h->d_sq8_tab;
+        a.rows = raw_rows_ref(h);
         a.nraw = h->nraw;
         a.R = R;
         a.k = k;
@@ -871,18 +866,8 @@ int ivfpq_stage_b(H* h, const gamma_hip_search_params* p, int nq, const float* d
         if (h->raw_sparse) return fail(h, GAMMA_HIP_EUNSUPPORTED, "has_rank on a handle that holds its shard's raw rows only: the exact distances travel with the candidates (gamma_hip_ivfpq_shard_exact / _merge_rerank_exact)");
         if (R <= 1024 && (nq >= 256 || ties)) {
             // one fused kernel: exact distances + top-k + output
-            if (h->d_raw_q)
-                gh::launch_rerank_topk_sq8(s, l2, d_x, nq, h->d, h->d_raw_q, h->d_sq8_tab, h->nraw, cand_ids, R, k, p->min_score,
-                                           p->max_score, neutral, d_distances, d_labels, qperm, ties ? &tf : nullptr);
-            else if (h->d_raw_b)
-                gh::launch_rerank_topk_b(s, l2, d_x, nq, h->d, h->d_raw_b, h->raw_byte == 2, h->nraw, cand_ids, R, k, p->min_score,
-                                         p->max_score, neutral, d_distances, d_labels, qperm, ties ? &tf : nullptr);
-            else if (h->d_raw_h)
-                gh::launch_rerank_topk_h(s, l2, d_x, nq, h->d, h->d_raw_h, h->nraw, cand_ids, R, k, p->min_score,
-                                         p->max_score, neutral, d_distances, d_labels, qperm, ties ? &tf : nullptr);
-            else
-                gh::launch_rerank_topk(s, l2, d_x, nq, h->d, h->d_raw, h->nraw, cand_ids, R, k, p->min_score,
-                                       p->max_score, neutral, d_distances, d_labels, qperm, ties ? &tf : nullptr);
+            gh::launch_rerank_topk(s, l2, d_x, nq, h->d, raw_rows_ref(h), h->nraw, cand_ids, R, k, p->min_score,
+                                   p->max_score, neutral, d_distances, d_labels, qperm, ties ? &tf : nullptr);
             if (ties && tie_mode == 1) replay();
             GH_CHECK(h, hipGetLastError());
             return GAMMA_HIP_OK;
@@ -890,18 +875,8 @@ int ivfpq_stage_b(H* h, const gamma_hip_search_params* p, int nq, const float* d
         GH_CHECK(h, h->w_exact.ensure((size_t)nq * R * sizeof(float)));
         GH_CHECK(h, h->w_selv.ensure((size_t)nq * k * sizeof(float)));
         GH_CHECK(h, h->w_selp.ensure((size_t)nq * k * sizeof(int)));
-        if (h->d_raw_q)
-            gh::launch_rerank_dist_sq8(s, l2, d_x, nq, h->d, h->d_raw_q, h->d_sq8_tab, h->nraw, cand_ids, R, p->min_score,
-                                       p->max_score, h->w_exact.as<float>());
-        else if (h->d_raw_b)
-            gh::launch_rerank_dist_b(s, l2, d_x, nq, h->d, h->d_raw_b, h->raw_byte == 2, h->nraw, cand_ids, R, p->min_score,
-                                     p->max_score, h->w_exact.as<float>());
-        else if (h->d_raw_h)
-            gh::launch_rerank_dist_h(s, l2, d_x, nq, h->d, h->d_raw_h, h->nraw, cand_ids, R, p->min_score,
-                                     p->max_score, h->w_exact.as<float>());
-        else
-            gh::launch_rerank_dist(s, l2, d_x, nq, h->d, h->d_raw, h->nraw, cand_ids, R, p->min_score,
-                                   p->max_score, h->w_exact.as<float>());
+        gh::launch_rerank_dist(s, l2, d_x, nq, h->d, raw_rows_ref(h), h->nraw, cand_ids, R, p->min_score,
+                               p->max_score, h->w_exact.as<float>());
         gh::launch_select_topk(s, l2, h->w_exact.as<float>(), R, nullptr, R, R, nq, k,
                                h->w_selv.as<float>(), h->w_selp.as<int>());
         gh::launch_finalize_topk(s, h->w_selv.as<float>(), h->w_selp.as<int>(), nq, k, cand_ids, R, 0,
@@ -941,8 +916,8 @@ bool ivfpq_small_ok(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, i
            (int64_t)p->nprobe * std::max(1, h->max_list_len) <= (1 << 22) &&
            // long lists: beyond ~5e7 codes per call the regular chain's bound filter wins (full-size C4, 390 k codes per
            // query: 64 queries 0.46 ms against 1.04, 256 queries 1.63 against 1.33)
-           // (a float16, byte or sq8 raw store leaves d_raw null: its has_rank calls take the regular chain, whose stage B reads the narrow rows)
-           (int64_t)nq * p->nprobe * (h->ntotal / std::max(1, h->nlist)) <= 48000000LL && (!p->has_rank || (h->d_raw && h->raw_d == h->d && !h->raw_sparse));
+           // (raw_f32() is null on a float16, byte or sq8 raw store: its has_rank calls take the regular chain, whose stage B reads the narrow rows)
+           (int64_t)nq * p->nprobe * (h->ntotal / std::max(1, h->nlist)) <= 48000000LL && (!p->has_rank || (h->raw_f32() && h->raw_d == h->d && !h->raw_sparse));
 }
 
 // d_x: the vectors that are quantised (a handle with an OPQ matrix: the rotated queries), d_xraw: the caller's, which the
@@ -1040,7 +1015,7 @@ int ivfpq_small(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int n
         tr.slice_cap = 0;
         tr.x = d_xraw;
         tr.d = d;
-        tr.raw = h->d_raw;
+        tr.rows = gh::RowsRef{h->raw_f32()};   // (ivfpq_small_ok: fp32 rows or no re-rank)
         tr.nraw = h->nraw;
         tr.R = R;
         tr.k = k;
@@ -1055,7 +1030,7 @@ int ivfpq_small(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int n
     }
     gh::launch_small_tail(s, l2, h->w_dist.as<float>(), q_stride, h->w_qtotal.as<int>(), nq, R, P, h->w_probe.as<int>(),
                           h->w_pair_off.as<int>(), h->d_list_off, h->d_ids, h->w_cand_dis.as<float>(),
-                          h->w_cand_pos.as<int>(), h->w_cand_ids.as<int64_t>(), p->has_rank ? 1 : 0, d_xraw, d, h->d_raw,
+                          h->w_cand_pos.as<int>(), h->w_cand_ids.as<int64_t>(), p->has_rank ? 1 : 0, d_xraw, d, h->raw_f32(),
                           h->nraw, k, p->min_score, p->max_score, neutral, d_distances, d_labels, smax,
                           smax ? h->w_selv.as<float>() : nullptr, smax ? h->w_selp.as<int>() : nullptr, 0,
                           ties ? &tr : nullptr, h->d_tie_stats);
@@ -1250,13 +1225,6 @@ int ivfpq_search_device_locked(H* h, const gamma_hip_search_params* p, int nq, c
 }
 
 // ---- what the exact scanners (IVFFLAT, flat) share ------------------------------------
-gh::RowsRef raw_rows_ref(const H* h) {
-    if (h->raw_sq8) return gh::RowsRef{h->d_raw_q, 4, h->d_sq8_tab};   // the codes and their decode table
-    return gh::RowsRef{h->raw_byte ? static_cast<const void*>(h->d_raw_b) : h->raw_half ? static_cast<const void*>(h->d_raw_h)
-                                                                                     : static_cast<const void*>(h->d_raw),
-                       h->raw_elem_type()};
-}
-
 void flat_tie_args(H* h, gh::TieReplayArgs* tr, bool l2, int nq, int64_t q_stride, int P, int k, const float* d_x, float* cand_dis,
                    int64_t* cand_ids, float* d_distances, int64_t* d_labels, int fixed_n) {
     tr->list = nullptr;
@@ -1276,7 +1244,7 @@ void flat_tie_args(H* h, gh::TieReplayArgs* tr, bool l2, int nq, int64_t q_strid
     tr->slice_cap = 0;
     tr->x = d_x;
     tr->d = h->d;
-    tr->raw = h->d_raw;
+    tr->rows = gh::RowsRef{h->raw_f32()};   // (has_rank 0: no row is read -- the fp32 kernels, whatever the store holds)
     tr->nraw = h->nraw;
     tr->R = k;
     tr->k = k;

@@ -91,8 +91,8 @@ static inline int opq_refuse(H* h, const char* what) {
 // Is the handle's store one the search reads?  narrow_rows / sq8_rows: the search's switches for the two kinds of narrow
 // store (false: the search has no reader for them).
 static inline bool raw_store_served(const H* h, bool narrow_rows, bool sq8_rows) {
-    if (h->raw_half || h->raw_byte) return narrow_rows;
-    if (h->raw_sq8) return sq8_rows;
+    if (h->raw_et == gh::ROW_SQ8) return sq8_rows;
+    if (h->raw_narrow()) return narrow_rows;   // float16, uint8, int8
     return true;   // fp32 rows
 }
 static inline int raw_store_refuse(H* h, const char* what) {
@@ -164,8 +164,6 @@ struct ListCompaction {
 };
 int compact_lists_for_call(H* h, FiltCtx* fc, int64_t est, bool allowed, ListCompaction* lc);
 
-// the raw store's rows as the exact scanners' kernels take them: base pointer + element type (kernels.h)
-gh::RowsRef raw_rows_ref(const H* h);
 // the replay of a query of the exact scanners (IVFFLAT: P > 0, the slab in probe order; flat: P == 0, fixed_n rows in
 // vid order): the k-heap IS the result heap, score window and filters are already in the slab (sentinels)
 void flat_tie_args(H* h, gh::TieReplayArgs* tr, bool l2, int nq, int64_t q_stride, int P, int k, const float* d_x, float* cand_dis,

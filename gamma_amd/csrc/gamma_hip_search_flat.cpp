@@ -1,7 +1,7 @@
 // gamma_hip_search_flat.cpp -- the flat (brute force) search of libgamma_hip.so over the raw store's rows: the small path,
 // the chunked paths (running bound with the matrix-pipe filter, row chunks + merge), their exact-ties phase with the two
 // buffer banks of overlapping callers, and the entry points of the C ABI (include/gamma_hip.h).  The exact scanners'
-// helpers (raw_rows_ref, flat_tie_args) and the filters are gamma_hip_search.cpp's (gamma_hip_search.h).
+// helper (flat_tie_args) and the filters are gamma_hip_search.cpp's (gamma_hip_search.h).
 #include "gamma_hip_internal.h"
 #include "gamma_hip_search.h"
 
@@ -158,7 +158,7 @@ int FlatCall::small_path() {
     // (has_rank = 0: the tail selects from the slab and reads no row -- its fp32 row pointer is null for a narrow store)
     gh::launch_small_tail(s, l2, h->w_dist.as<float>(), stride, nullptr, nq, k_out, 0, nullptr, nullptr, nullptr, nullptr,
                           h->w_cand_dis.as<float>(), h->w_cand_pos.as<int>(), h->w_cand_ids.as<int64_t>(), 0, d_x, d,
-                          h->d_raw, N, k_out, p->min_score, p->max_score, neutral, d_distances, d_labels, smax,
+                          h->raw_f32(), N, k_out, p->min_score, p->max_score, neutral, d_distances, d_labels, smax,
                           smax ? h->w_selv.as<float>() : nullptr, smax ? h->w_selp.as<int>() : nullptr, (int)N,
                           small_ties ? &tr : nullptr, h->d_tie_stats);
     GH_CHECK(h, hipGetLastError());
@@ -520,7 +520,7 @@ int gamma_hip_flat_search(gamma_hip_index* h, const gamma_hip_search_params* p, 
     if (!h) return GAMMA_HIP_EINVAL;
     // small unfiltered calls from concurrent client threads share device batches (see gamma_hip_ivfpq_search)
     // (a narrow store is never combined, whatever gamma_hip_set_flat_narrow_rows says)
-    if (h->combine && p && nq > 0 && nq <= COMB_MAX_NQ && k > 0 && x && distances && labels && h->raw_d > 0 && !h->raw_half && !h->raw_byte && !h->raw_sq8 &&
+    if (h->combine && p && nq > 0 && nq <= COMB_MAX_NQ && k > 0 && x && distances && labels && h->raw_d > 0 && !h->raw_narrow() &&
         !p->has_range && p->n_range == 0 && p->n_field == 0 && p->n_term == 0)
         return combined_search(h, p, nq, x, k, distances, labels, /*kind=*/1);
     return flat_search_host_locked(h, p, nq, x, k, distances, labels);

@@ -56,7 +56,7 @@ int ivfflat_small(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, con
                             d_labels);
     gh::launch_small_tail(s, l2, h->w_dist.as<float>(), q_stride, h->w_qtotal.as<int>(), nq, k, P, h->w_probe.as<int>(),
                           h->w_pair_off.as<int>(), h->d_list_off, h->d_ids, h->w_cand_dis.as<float>(),
-                          h->w_cand_pos.as<int>(), h->w_cand_ids.as<int64_t>(), 0, d_x, d, h->d_raw, h->nraw, k, p->min_score,
+                          h->w_cand_pos.as<int>(), h->w_cand_ids.as<int64_t>(), 0, d_x, d, h->raw_f32(), h->nraw, k, p->min_score,
                           p->max_score, neutral, d_distances, d_labels, smax, smax ? h->w_selv.as<float>() : nullptr,
                           smax ? h->w_selp.as<int>() : nullptr, 0, ties ? &tr : nullptr, h->d_tie_stats);
     GH_CHECK(h, hipEventRecord(h->rd_ev[ver], s));

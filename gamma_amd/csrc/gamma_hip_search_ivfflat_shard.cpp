@@ -17,7 +17,7 @@ int ivfflat_shard_check(H* h, const gamma_hip_search_params* p, int nq, int k, c
     if (need_rows && !raw_store_served(h, false, false)) return raw_store_refuse(h, what);
     if (!h->trained) return fail(h, GAMMA_HIP_ENOTTRAINED, "ivfflat not trained");
     if (p->nprobe <= 0 || p->nprobe > h->nlist) return fail(h, GAMMA_HIP_EINVAL, "nprobe out of range");
-    if (need_rows && (!h->d_raw || h->raw_d != h->d)) return fail(h, GAMMA_HIP_EINVAL, "ivfflat needs the raw store");
+    if (need_rows && (!h->raw_f32() || h->raw_d != h->d)) return fail(h, GAMMA_HIP_EINVAL, "ivfflat needs the raw store");
     return GAMMA_HIP_OK;
 }
 
@@ -59,20 +59,20 @@ int ivfflat_shard_scan(H* h, const gamma_hip_search_params* p, const FiltCtx& fc
         }
         if (h->raw_sparse)
             gh::launch_ivfflat_lm_sparse(s, l2, xq, nc, h->d, P, probe, h->w_pair_off.as<int>(), h->d_list_off, len, nlist, h->d_ids,
-                                         h->d_raw, h->nraw, h->d_raw_slot, h->raw_slot_cap, q_stride, h->w_dist.as<float>(), fc.d_tab,
+                                         h->raw_f32(), h->nraw, h->d_raw_slot, h->raw_slot_cap, q_stride, h->w_dist.as<float>(), fc.d_tab,
                                          need_filter, p->min_score, p->max_score, h->w_lm_units.p);
         else
             gh::launch_ivfflat_lm(s, l2, xq, nc, h->d, P, probe, h->w_pair_off.as<int>(), h->d_list_off, len, nlist, h->d_ids,
-                                  h->d_raw, h->nraw, q_stride, h->w_dist.as<float>(), fc.d_tab, need_filter, p->min_score,
+                                  h->raw_f32(), h->nraw, q_stride, h->w_dist.as<float>(), fc.d_tab, need_filter, p->min_score,
                                   p->max_score, h->w_lm_units.p);
     } else {
         h->fl_pair.fetch_add(1, std::memory_order_relaxed);
         if (h->raw_sparse)
             gh::launch_ivfflat_scan_sparse(s, l2, xq, nc, h->d, P, h->w_pair_off.as<int>(), h->w_pair_base.as<int64_t>(), h->d_ids,
-                                           h->d_raw, h->nraw, h->d_raw_slot, h->raw_slot_cap, q_stride, h->w_dist.as<float>(),
+                                           h->raw_f32(), h->nraw, h->d_raw_slot, h->raw_slot_cap, q_stride, h->w_dist.as<float>(),
                                            fc.d_tab, need_filter, p->min_score, p->max_score);
         else
-            gh::launch_ivfflat_scan(s, l2, xq, nc, h->d, P, h->w_pair_off.as<int>(), h->w_pair_base.as<int64_t>(), h->d_ids, h->d_raw,
+            gh::launch_ivfflat_scan(s, l2, xq, nc, h->d, P, h->w_pair_off.as<int>(), h->w_pair_base.as<int64_t>(), h->d_ids, h->raw_f32(),
                                     h->nraw, q_stride, h->w_dist.as<float>(), fc.d_tab, need_filter, p->min_score, p->max_score);
     }
     return GAMMA_HIP_OK;

@@ -276,10 +276,10 @@ int gamma_hip_ivfpq_shard_exact(gamma_hip_index* h, const gamma_hip_search_param
     GH_NO_PQ4(h, "gamma_hip_ivfpq_shard_exact");
     if (!raw_store_served(h, false, false)) return raw_store_refuse(h, "gamma_hip_ivfpq_shard_exact");
     GH_TRY(replay_join(h));
-    if (!h->d_raw || h->raw_d != h->d) return fail(h, GAMMA_HIP_EINVAL, "no raw store");
+    if (!h->raw_f32() || h->raw_d != h->d) return fail(h, GAMMA_HIP_EINVAL, "no raw store");
     GH_CHECK(h, hipSetDevice(h->device));
     // (a dense store answers for every id; a sharded one for the vectors it holds, the sentinel elsewhere)
-    gh::launch_rerank_dist(h->stream, p->metric == GAMMA_HIP_METRIC_L2, d_x, nq, h->d, h->d_raw, h->nraw, d_ids, R, p->min_score,
+    gh::launch_rerank_dist(h->stream, p->metric == GAMMA_HIP_METRIC_L2, d_x, nq, h->d, gh::RowsRef{h->raw_f32()}, h->nraw, d_ids, R, p->min_score,
                            p->max_score, d_exact, h->raw_sparse ? h->d_raw_slot : nullptr, h->raw_sparse ? h->raw_slot_cap : 0);
     GH_CHECK(h, hipGetLastError());
     return GAMMA_HIP_OK;
@@ -294,9 +294,9 @@ int gamma_hip_ivfpq_shard_export_exact(gamma_hip_index* h, const gamma_hip_searc
     SearchLock lk(h);
     GH_NO_PQ4(h, "gamma_hip_ivfpq_shard_export_exact");
     if (!raw_store_served(h, false, false)) return raw_store_refuse(h, "gamma_hip_ivfpq_shard_export_exact");
-    if (!h->d_raw || h->raw_d != h->d || !h->raw_sparse) return fail(h, GAMMA_HIP_EINVAL, "export of exact distances: a sharded raw store (gamma_hip_raw_put)");
+    if (!h->raw_f32() || h->raw_d != h->d || !h->raw_sparse) return fail(h, GAMMA_HIP_EINVAL, "export of exact distances: a sharded raw store (gamma_hip_raw_put)");
     GH_CHECK(h, hipSetDevice(h->device));
-    gh::launch_export_exact(h->stream, p->metric == GAMMA_HIP_METRIC_L2, d_xf, nf, h->d, h->d_raw, h->d_raw_slot, h->raw_slot_cap,
+    gh::launch_export_exact(h->stream, p->metric == GAMMA_HIP_METRIC_L2, d_xf, nf, h->d, h->raw_f32(), h->d_raw_slot, h->raw_slot_cap,
                             d_vals, d_ids, stride, d_off, p->nprobe, d_bound_f, d_ex);
     GH_CHECK(h, hipGetLastError());
     return GAMMA_HIP_OK;
@@ -451,7 +451,7 @@ static int merge_replay_impl(gamma_hip_index* h, const gamma_hip_search_params* 
     const bool l2 = p->metric == GAMMA_HIP_METRIC_L2;
     const int P = p->nprobe, R = std::max(p->recall_num, k);
     if (R > gh::tie_replay_max_k() || P > gh::tie_replay_max_probes()) return fail(h, GAMMA_HIP_EINVAL, "beyond the replay's range");
-    if (p->has_rank && !d_ex_all && (!h->d_raw || h->raw_d != h->d || h->raw_sparse))
+    if (p->has_rank && !d_ex_all && (!h->raw_f32() || h->raw_d != h->d || h->raw_sparse))
         return fail(h, GAMMA_HIP_EINVAL, "has_rank needs the raw store (or the exact distances exported with the streams)");
     hipStream_t s = h->stream;
     const int64_t mstride = ((int64_t)nshards * stride + 3) & ~(int64_t)3;   // a row assembled from every shard's export
@@ -494,7 +494,7 @@ static int merge_replay_impl(gamma_hip_index* h, const gamma_hip_search_params* 
     a.slice_cap = 0;
     a.x = d_x_slice;
     a.d = h->d;
-    a.raw = h->d_raw;
+    a.rows = gh::RowsRef{h->raw_f32()};
     a.nraw = h->nraw;
     a.R = R;
     a.k = k;

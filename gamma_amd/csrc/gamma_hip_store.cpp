@@ -717,37 +717,29 @@ int64_t gamma_hip_term_count(gamma_hip_index* h, int field_id) {
     return it == h->terms.end() ? 0 : it->second.ndocs;
 }
 
-static const char* const kHalfStore = "the raw store holds float16 rows (gamma_hip_raw_init_f16)";
-static const char* const kByteStore = "the raw store holds 8-bit rows (gamma_hip_raw_init_i8)";
-static const char* const kSq8Store = "the raw store holds scalar-quantised sq8 rows (gamma_hip_raw_init_sq8)";
-
-// the rows, whichever element type the store was initialised with
-static inline char* raw_rows(H* h) {
-    return h->raw_sq8 ? reinterpret_cast<char*>(h->d_raw_q) : h->raw_byte ? reinterpret_cast<char*>(h->d_raw_b) : h->raw_half ? reinterpret_cast<char*>(h->d_raw_h) : reinterpret_cast<char*>(h->d_raw);
-}
-static inline void raw_rows_set(H* h, void* p) {
-    if (h->raw_sq8) h->d_raw_q = reinterpret_cast<uint8_t*>(p);
-    else if (h->raw_byte) h->d_raw_b = reinterpret_cast<uint8_t*>(p);
-    else if (h->raw_half) h->d_raw_h = reinterpret_cast<uint16_t*>(p);
-    else h->d_raw = reinterpret_cast<float*>(p);
+// what a narrow store answers to the entry points of the sparse fp32 store (gamma_hip_raw_put, _drop)
+static const char* narrow_store_name(const H* h) {
+    switch (h->raw_et) {
+        case gh::ROW_F16: return "the raw store holds float16 rows (gamma_hip_raw_init_f16)";
+        case gh::ROW_SQ8: return "the raw store holds scalar-quantised sq8 rows (gamma_hip_raw_init_sq8)";
+        default: return "the raw store holds 8-bit rows (gamma_hip_raw_init_i8)";
+    }
 }
 
-// et: 0 fp32, 1 float16, 2 uint8, 3 int8, 4 sq8 (gamma_hip_raw_elem_type)
+// et: gh::RowType (0 fp32, 1 float16, 2 uint8, 3 int8, 4 sq8: gamma_hip_raw_elem_type)
 static int raw_init_as(gamma_hip_index* h, int d, int et) {
     if (!h || d <= 0) return GAMMA_HIP_EINVAL;
     WriteLock lk(h);
     if (h->raw_d != 0 && h->raw_d != d) return fail(h, GAMMA_HIP_EINVAL, "raw store dimension mismatch");
     if (h->raw_d != 0 && h->raw_elem_type() != et) return fail(h, GAMMA_HIP_EINVAL, "the raw store's element type is fixed at its first init");
-    h->raw_half = et == 1;
-    h->raw_byte = et == 2 || et == 3 ? et - 1 : 0;
-    h->raw_sq8 = et == 4;
+    h->raw_et = et;
     if (h->raw_d == 0 && !getenv("GAMMA_HIP_NO_RAW_VMM")) {
         // reserve the address range the store may ever need (the device's memory): physical chunks are mapped into it
         // as rows arrive (raw_reserve).  Any failure -- here or of the FIRST chunk -- leaves the reallocating store.
         GH_CHECK(h, hipSetDevice(h->device));
         if (h->raw_vm.reserve(h->device, (size_t)64 << 20)) {   // chunks of whole 64 MB
             h->raw_vmm = true;
-            raw_rows_set(h, h->raw_vm.base);
+            h->raw_p = h->raw_vm.base;
         }
     }
     h->raw_d = d;
@@ -784,7 +776,7 @@ static int raw_reserve(H* h, int64_t need) {
         // nothing is mapped yet: the range is given back and the store reallocates from here on
         h->raw_vm.release();
         h->raw_vmm = false;
-        raw_rows_set(h, nullptr);
+        h->raw_p = nullptr;
     }
     h->raw_regrows++;
     int64_t ncap = std::max<int64_t>(need, h->raw_cap + h->raw_cap / 2);
@@ -793,11 +785,11 @@ static int raw_reserve(H* h, int64_t need) {
     if (h->wl) GH_CHECK(h, h->wl->exclusive());   // the old store is freed below
     GH_CHECK(h, hipMalloc(&np, (size_t)ncap * h->raw_d * h->raw_esz()));
     if (h->nraw > 0)
-        GH_CHECK(h, hipMemcpyAsync(np, raw_rows(h), (size_t)h->nraw * h->raw_d * h->raw_esz(),
+        GH_CHECK(h, hipMemcpyAsync(np, h->raw_p, (size_t)h->nraw * h->raw_d * h->raw_esz(),
                                    hipMemcpyDeviceToDevice, h->wstream));
     GH_CHECK(h, hipStreamSynchronize(h->wstream));
-    if (raw_rows(h)) GH_CHECK(h, hipFree(raw_rows(h)));
-    raw_rows_set(h, np);
+    if (h->raw_p) GH_CHECK(h, hipFree(h->raw_p));
+    h->raw_p = np;
     h->raw_cap = ncap;
     return GAMMA_HIP_OK;
 }
@@ -822,7 +814,7 @@ static inline float half_bits_to_float(uint16_t b) {
     return f;
 }
 
-static int raw_half_check(H* h, int64_t count, const float* v) {
+static int half_values_check(H* h, int64_t count, const float* v) {
     for (int64_t i = 0; i < count; i++) {
         const float a = fabsf(v[i]);
         if (a >= 65520.f && a != INFINITY)
@@ -848,12 +840,12 @@ int gamma_hip_raw_i8_check(const float* x, int64_t n, int is_signed, int64_t* fi
 }
 
 // the writers' check in front of their reservation: base = the position of v[0] in the caller's array (for the message)
-static int raw_byte_check(H* h, int64_t count, const float* v, int64_t base = 0) {
+static int byte_values_check(H* h, int64_t count, const float* v, int64_t base = 0) {
     int64_t bad = -1;
-    if (gamma_hip_raw_i8_check(v, count, h->raw_byte == 2, &bad) == GAMMA_HIP_OK) return GAMMA_HIP_OK;
+    if (gamma_hip_raw_i8_check(v, count, h->raw_et == gh::ROW_I8, &bad) == GAMMA_HIP_OK) return GAMMA_HIP_OK;
     char msg[256];
     snprintf(msg, sizeof(msg), "raw store (%s, gamma_hip_raw_init_i8): value %g at position %lld (row %lld, element %lld) is not exactly storable; nothing was written",
-             h->raw_byte == 2 ? "int8" : "uint8", (double)v[bad], (long long)(base + bad), (long long)((base + bad) / h->raw_d),
+             h->raw_et == gh::ROW_I8 ? "int8" : "uint8", (double)v[bad], (long long)(base + bad), (long long)((base + bad) / h->raw_d),
              (long long)((base + bad) % h->raw_d));
     return fail(h, GAMMA_HIP_EINVAL, msg);
 }
@@ -890,8 +882,8 @@ int gamma_hip_raw_sq8_params(int d, const float* vmin, const float* vmax, float*
 }
 
 // the ranges and both tables of an empty sq8 store (caller holds the write lock)
-static int raw_sq8_set_ranges_locked(H* h, const float* vmin, const float* vmax) {
-    if (!h->raw_sq8) return fail(h, GAMMA_HIP_EINVAL, "gamma_hip_raw_sq8_set_ranges: the raw store is not an sq8 store (gamma_hip_raw_init_sq8)");
+static int sq8_set_ranges_locked(H* h, const float* vmin, const float* vmax) {
+    if (h->raw_et != gh::ROW_SQ8) return fail(h, GAMMA_HIP_EINVAL, "gamma_hip_raw_sq8_set_ranges: the raw store is not an sq8 store (gamma_hip_raw_init_sq8)");
     if (h->nraw > 0) return fail(h, GAMMA_HIP_EINVAL, "gamma_hip_raw_sq8_set_ranges: the sq8 raw store holds rows; the ranges change only while it is empty (after gamma_hip_raw_clear)");
     const int d = h->raw_d;
     std::vector<float> step(d), inv(d);
@@ -918,13 +910,13 @@ static int raw_sq8_set_ranges_locked(H* h, const float* vmin, const float* vmax)
 int gamma_hip_raw_sq8_set_ranges(gamma_hip_index* h, const float* vmin, const float* vmax) {
     if (!h || !vmin || !vmax) return GAMMA_HIP_EINVAL;
     WriteLock lk(h);
-    return raw_sq8_set_ranges_locked(h, vmin, vmax);
+    return sq8_set_ranges_locked(h, vmin, vmax);
 }
 
 int gamma_hip_raw_sq8_get_ranges(gamma_hip_index* h, float* vmin, float* vmax) {
     if (!h || !vmin || !vmax) return GAMMA_HIP_EINVAL;
     std::lock_guard<std::mutex> g(h->mu);
-    if (!h->raw_sq8 || h->sq8_vmin.empty()) {
+    if (h->raw_et != gh::ROW_SQ8 || h->sq8_vmin.empty()) {
         h->err = "gamma_hip_raw_sq8_get_ranges: no ranges (an sq8 store after gamma_hip_raw_sq8_set_ranges / _train has them)";
         return GAMMA_HIP_EINVAL;
     }
@@ -933,17 +925,17 @@ int gamma_hip_raw_sq8_get_ranges(gamma_hip_index* h, float* vmin, float* vmax) {
     return GAMMA_HIP_OK;
 }
 
-static int raw_sq8_check(H* h, int64_t count, const float* v, int64_t base = 0);
+static int sq8_values_check(H* h, int64_t count, const float* v, int64_t base = 0);
 
 // per-dimension minimum and maximum of n host rows: staged through the writer's staging buffer in 64 MB pieces, every piece
 // folded into the running result by k_sq8_minmax on the writer stream
 int gamma_hip_raw_sq8_train(gamma_hip_index* h, int64_t n, const float* x) {
     if (!h || n <= 0 || !x) return GAMMA_HIP_EINVAL;
     WriteLock lk(h);
-    if (!h->raw_sq8) return fail(h, GAMMA_HIP_EINVAL, "gamma_hip_raw_sq8_train: the raw store is not an sq8 store (gamma_hip_raw_init_sq8)");
+    if (h->raw_et != gh::ROW_SQ8) return fail(h, GAMMA_HIP_EINVAL, "gamma_hip_raw_sq8_train: the raw store is not an sq8 store (gamma_hip_raw_init_sq8)");
     if (h->nraw > 0) return fail(h, GAMMA_HIP_EINVAL, "gamma_hip_raw_sq8_train: the sq8 raw store holds rows; the ranges change only while it is empty (after gamma_hip_raw_clear)");
     const int d = h->raw_d;
-    GH_TRY(raw_sq8_check(h, n * d, x));
+    GH_TRY(sq8_values_check(h, n * d, x));
     GH_CHECK(h, hipSetDevice(h->device));
     const int64_t piece = std::max<int64_t>(1, ((int64_t)16 << 20) / d);
     GH_CHECK(h, h->we_stage.ensure((size_t)std::min(piece, n) * d * sizeof(float)));
@@ -958,11 +950,11 @@ int gamma_hip_raw_sq8_train(gamma_hip_index* h, int64_t n, const float* x) {
     GH_CHECK(h, hipMemcpyAsync(mm.data(), h->we_chk.p, mm.size() * sizeof(float), hipMemcpyDeviceToHost, h->wstream));
     GH_CHECK(h, hipStreamSynchronize(h->wstream));
     for (float& v : mm) v += 0.0f;   // -0.0 -> +0.0: which zero a minimum of both returns depends on the order
-    return raw_sq8_set_ranges_locked(h, mm.data(), mm.data() + d);
+    return sq8_set_ranges_locked(h, mm.data(), mm.data() + d);
 }
 
-// the writers' check in front of their reservation: ranges first, then the values (base: see raw_byte_check)
-static int raw_sq8_check(H* h, int64_t count, const float* v, int64_t base) {
+// the writers' check in front of their reservation: ranges first, then the values (base: see byte_values_check)
+static int sq8_values_check(H* h, int64_t count, const float* v, int64_t base) {
     int64_t bad = -1;
     if (gamma_hip_raw_sq8_check(v, count, &bad) == GAMMA_HIP_OK) return GAMMA_HIP_OK;
     char msg[256];
@@ -970,25 +962,25 @@ static int raw_sq8_check(H* h, int64_t count, const float* v, int64_t base) {
              (double)v[bad], (long long)(base + bad), (long long)((base + bad) / h->raw_d), (long long)((base + bad) % h->raw_d));
     return fail(h, GAMMA_HIP_EINVAL, msg);
 }
-static int raw_sq8_need_ranges(H* h) {
+static int sq8_need_ranges(H* h) {
     if (!h->sq8_vmin.empty()) return GAMMA_HIP_OK;
     return fail(h, GAMMA_HIP_EINVAL, "raw store (sq8, gamma_hip_raw_init_sq8): no ranges yet (gamma_hip_raw_sq8_set_ranges / _train come before the first row); nothing was written");
 }
 
-// the check of a writer's values for the store's element type (fp32 rows take everything)
-static int raw_narrow_check(H* h, int64_t count, const float* v) {
-    if (h->raw_sq8) {
-        GH_TRY(raw_sq8_need_ranges(h));
-        return raw_sq8_check(h, count, v);
+// the check of a writer's values for the store's element type (fp32 rows take everything); base: see byte_values_check
+static int raw_narrow_check(H* h, int64_t count, const float* v, int64_t base = 0) {
+    switch (h->raw_et) {
+        case gh::ROW_F16: return half_values_check(h, count, v);
+        case gh::ROW_U8:
+        case gh::ROW_I8: return byte_values_check(h, count, v, base);
+        case gh::ROW_SQ8: GH_TRY(sq8_need_ranges(h)); return sq8_values_check(h, count, v, base);
+        default: return GAMMA_HIP_OK;
     }
-    if (h->raw_byte) return raw_byte_check(h, count, v);
-    if (h->raw_half) return raw_half_check(h, count, v);
-    return GAMMA_HIP_OK;
 }
 
-// n caller rows -> rows first, first + 1, .. (vids == nullptr) or rows vids[i] (those outside [0, nrows) are skipped) of the half
-// or byte store: staged as fp32 through the writer's staging buffer in pieces, converted by k_raw_rows_to_half / _to_bytes on the
-// writer stream.  The caller has checked the values, reserved the rows and waits for the stream.
+// n caller rows -> rows first, first + 1, .. (vids == nullptr) or rows vids[i] (those outside [0, nrows) are skipped) of a narrow
+// store: staged as fp32 through the writer's staging buffer in pieces, converted by the store's kernel (launch_raw_rows_narrow) on
+// the writer stream.  The caller has checked the values, reserved the rows and waits for the stream.
 static int raw_narrow_rows_in(H* h, int64_t first, const int64_t* vids, int64_t n, const float* vecs, int64_t nrows) {
     const int d = h->raw_d;
     const int64_t piece = std::max<int64_t>(1, ((int64_t)16 << 20) / d);   // 64 MB of fp32 per piece
@@ -1000,17 +992,19 @@ static int raw_narrow_rows_in(H* h, int64_t first, const int64_t* vids, int64_t 
     for (int64_t i0 = 0; i0 < n; i0 += piece) {
         const int64_t m = std::min(piece, n - i0);
         GH_CHECK(h, hipMemcpyAsync(h->we_stage.p, vecs + i0 * d, (size_t)m * d * sizeof(float), hipMemcpyHostToDevice, h->wstream));
-        if (h->raw_sq8)
-            gh::launch_raw_rows_to_sq8(h->wstream, h->we_stage.as<float>(), vids ? h->we_chk.as<int64_t>() + i0 : nullptr, first + i0, m, d,
-                                       h->d_sq8_tab + 2 * (size_t)d, h->d_raw_q, nrows);
-        else if (h->raw_byte)
-            gh::launch_raw_rows_to_bytes(h->wstream, h->we_stage.as<float>(), vids ? h->we_chk.as<int64_t>() + i0 : nullptr, first + i0, m,
-                                         d, h->d_raw_b, nrows);
-        else
-            gh::launch_raw_rows_to_half(h->wstream, h->we_stage.as<float>(), vids ? h->we_chk.as<int64_t>() + i0 : nullptr, first + i0, m, d,
-                                        h->d_raw_h, nrows);
+        gh::launch_raw_rows_narrow(h->wstream, h->we_stage.as<float>(), vids ? h->we_chk.as<int64_t>() + i0 : nullptr, first + i0, m, d,
+                                   h->raw_p, h->raw_et, h->raw_et == gh::ROW_SQ8 ? h->d_sq8_tab + 2 * (size_t)d : nullptr, nrows);
     }
     GH_CHECK(h, hipGetLastError());
+    return GAMMA_HIP_OK;
+}
+
+// n caller rows into rows first, first + 1, .. of the store, on the writer stream: fp32 rows are copied into place, the rows of a
+// narrow store converted on the way (nrows: the rows it may write).  The caller's part is raw_narrow_rows_in's.
+static int raw_rows_in(H* h, int64_t first, int64_t n, const float* vecs, int64_t nrows) {
+    if (h->raw_narrow()) return raw_narrow_rows_in(h, first, nullptr, n, vecs, nrows);
+    GH_CHECK(h, hipMemcpyAsync(h->raw_f32() + first * h->raw_d, vecs, (size_t)n * h->raw_d * sizeof(float), hipMemcpyHostToDevice,
+                               h->wstream));
     return GAMMA_HIP_OK;
 }
 
@@ -1023,11 +1017,7 @@ int gamma_hip_raw_append(gamma_hip_index* h, int64_t n, const float* vecs) {
     GH_TRY(raw_narrow_check(h, n * h->raw_d, vecs));
     GH_CHECK(h, hipSetDevice(h->device));
     GH_TRY(raw_reserve(h, h->nraw + n));
-    if (h->raw_esz() != sizeof(float))
-        GH_TRY(raw_narrow_rows_in(h, h->nraw, nullptr, n, vecs, h->raw_cap));
-    else
-        GH_CHECK(h, hipMemcpyAsync(h->d_raw + h->nraw * h->raw_d, vecs, (size_t)n * h->raw_d * sizeof(float),
-                                   hipMemcpyHostToDevice, h->wstream));
+    GH_TRY(raw_rows_in(h, h->nraw, n, vecs, h->raw_cap));
     GH_CHECK(h, hipStreamSynchronize(h->wstream));
     h->nraw += n;
     return GAMMA_HIP_OK;
@@ -1065,9 +1055,7 @@ int gamma_hip_raw_put(gamma_hip_index* h, int64_t n, const int64_t* vids, const 
     if (!h || n < 0 || (n > 0 && (!vids || !vecs))) return GAMMA_HIP_EINVAL;
     WriteLock lk(h);
     if (h->raw_d <= 0) return fail(h, GAMMA_HIP_EINVAL, "raw store not initialised");
-    if (h->raw_half) return fail(h, GAMMA_HIP_EUNSUPPORTED, kHalfStore);   // rows sharded with their lists are fp32
-    if (h->raw_byte) return fail(h, GAMMA_HIP_EUNSUPPORTED, kByteStore);
-    if (h->raw_sq8) return fail(h, GAMMA_HIP_EUNSUPPORTED, kSq8Store);
+    if (h->raw_narrow()) return fail(h, GAMMA_HIP_EUNSUPPORTED, narrow_store_name(h));   // rows sharded with their lists are fp32
     if (!h->raw_sparse && h->nraw > 0) return fail(h, GAMMA_HIP_EINVAL, "raw_put on a store that holds rows by vector id");
     if (n == 0) {   // the first call turns the empty store into the sparse form, rows or not (a shard that owns no vector yet)
         if (!h->raw_sparse) {
@@ -1128,11 +1116,10 @@ int gamma_hip_raw_put(gamma_hip_index* h, int64_t n, const int64_t* vids, const 
     h->raw_sparse = true;
     GH_CHECK(h, hipMemcpyAsync(h->we_chk.p, pairs.data(), (size_t)n * 2 * sizeof(int32_t), hipMemcpyHostToDevice, h->wstream));
     if (in_order) {
-        GH_CHECK(h, hipMemcpyAsync(h->d_raw + h->nraw * h->raw_d, vecs, (size_t)n * h->raw_d * sizeof(float), hipMemcpyHostToDevice,
-                                   h->wstream));
+        GH_TRY(raw_rows_in(h, h->nraw, n, vecs, h->raw_cap));
     } else {
         GH_CHECK(h, hipMemcpyAsync(h->we_stage.p, vecs, (size_t)n * h->raw_d * sizeof(float), hipMemcpyHostToDevice, h->wstream));
-        gh::launch_raw_rows_scatter(h->wstream, h->we_stage.as<float>(), h->we_chk.as<int32_t>(), n, h->raw_d, h->d_raw, h->raw_cap);
+        gh::launch_raw_rows_scatter(h->wstream, h->we_stage.as<float>(), h->we_chk.as<int32_t>(), n, h->raw_d, h->raw_f32(), h->raw_cap);
     }
     gh::launch_raw_slot_scatter(h->wstream, h->we_chk.as<int32_t>(), n, h->d_raw_slot, h->raw_slot_cap);
     GH_CHECK(h, hipGetLastError());
@@ -1152,9 +1139,7 @@ int gamma_hip_raw_put(gamma_hip_index* h, int64_t n, const int64_t* vids, const 
 int gamma_hip_raw_drop(gamma_hip_index* h, int64_t n, const int64_t* vids) {
     if (!h || n < 0 || (n > 0 && !vids)) return GAMMA_HIP_EINVAL;
     WriteLock lk(h);
-    if (h->raw_half) return fail(h, GAMMA_HIP_EUNSUPPORTED, kHalfStore);
-    if (h->raw_byte) return fail(h, GAMMA_HIP_EUNSUPPORTED, kByteStore);
-    if (h->raw_sq8) return fail(h, GAMMA_HIP_EUNSUPPORTED, kSq8Store);
+    if (h->raw_narrow()) return fail(h, GAMMA_HIP_EUNSUPPORTED, narrow_store_name(h));
     if (!h->raw_sparse) {
         if (h->nraw > 0) return fail(h, GAMMA_HIP_EINVAL, "raw_drop on a store that holds rows by vector id");
         return GAMMA_HIP_OK;   // empty: nothing to forget
@@ -1191,11 +1176,11 @@ int gamma_hip_raw_clear(gamma_hip_index* h) {
             h->vm_retired.push_back(std::move(h->raw_vm));
             h->raw_vm = VmRange();
             h->raw_vmm = false;
-            raw_rows_set(h, nullptr);
+            h->raw_p = nullptr;
         }
-    } else if (raw_rows(h)) {
-        GH_CHECK(h, hipFree(raw_rows(h)));
-        raw_rows_set(h, nullptr);
+    } else if (h->raw_p) {
+        GH_CHECK(h, hipFree(h->raw_p));
+        h->raw_p = nullptr;
     }
     if (h->d_raw_slot) GH_CHECK(h, hipFree(h->d_raw_slot));
     h->d_raw_slot = nullptr;
@@ -1226,11 +1211,7 @@ int gamma_hip_raw_write(gamma_hip_index* h, int64_t first_vid, int64_t n, const 
     GH_TRY(raw_narrow_check(h, n * h->raw_d, vecs));
     GH_CHECK(h, hipSetDevice(h->device));
     GH_TRY(raw_reserve(h, first_vid + n));
-    if (h->raw_esz() != sizeof(float))
-        GH_TRY(raw_narrow_rows_in(h, first_vid, nullptr, n, vecs, h->raw_cap));
-    else
-        GH_CHECK(h, hipMemcpyAsync(h->d_raw + first_vid * h->raw_d, vecs, (size_t)n * h->raw_d * sizeof(float),
-                                   hipMemcpyHostToDevice, h->wstream));
+    GH_TRY(raw_rows_in(h, first_vid, n, vecs, h->raw_cap));
     GH_CHECK(h, hipStreamSynchronize(h->wstream));
     h->nraw = std::max(h->nraw, first_vid + n);
     return GAMMA_HIP_OK;
@@ -1243,11 +1224,7 @@ int gamma_hip_raw_update(gamma_hip_index* h, int64_t vid, const float* vec) {
     if (vid < 0 || vid >= h->nraw) return fail(h, GAMMA_HIP_EINVAL, "vid out of range");
     GH_TRY(raw_narrow_check(h, h->raw_d, vec));
     GH_CHECK(h, hipSetDevice(h->device));
-    if (h->raw_esz() != sizeof(float))
-        GH_TRY(raw_narrow_rows_in(h, vid, nullptr, 1, vec, h->nraw));
-    else
-        GH_CHECK(h, hipMemcpyAsync(h->d_raw + vid * h->raw_d, vec, (size_t)h->raw_d * sizeof(float),
-                                   hipMemcpyHostToDevice, h->wstream));
+    GH_TRY(raw_rows_in(h, vid, 1, vec, h->nraw));
     GH_CHECK(h, hipStreamSynchronize(h->wstream));
     return GAMMA_HIP_OK;
 }
@@ -1258,14 +1235,10 @@ int gamma_hip_raw_update_batch(gamma_hip_index* h, int64_t n, const int64_t* vid
     if (n == 0) return GAMMA_HIP_OK;
     WriteLock lk(h);
     if (h->raw_sparse) return fail(h, GAMMA_HIP_EUNSUPPORTED, "the raw store holds this shard's rows only (gamma_hip_raw_put)");
-    if (h->raw_esz() != sizeof(float)) {
-        if (h->raw_sq8) GH_TRY(raw_sq8_need_ranges(h));
+    if (h->raw_narrow()) {
+        GH_TRY(raw_narrow_check(h, 0, vecs));   // (an sq8 store without ranges refuses, whether or not a row is in range)
         for (int64_t i = 0; i < n; i++)
-            if (vids[i] >= 0 && vids[i] < h->nraw) {
-                if (h->raw_sq8) GH_TRY(raw_sq8_check(h, h->raw_d, vecs + i * h->raw_d, i * h->raw_d));
-                else if (h->raw_byte) GH_TRY(raw_byte_check(h, h->raw_d, vecs + i * h->raw_d, i * h->raw_d));
-                else GH_TRY(raw_half_check(h, h->raw_d, vecs + i * h->raw_d));
-            }
+            if (vids[i] >= 0 && vids[i] < h->nraw) GH_TRY(raw_narrow_check(h, h->raw_d, vecs + i * h->raw_d, i * h->raw_d));
         // one kernel writes all rows: of a vid named twice the last entry wins, as with the fp32 store's ordered copies
         std::vector<int64_t> v(vids, vids + n);
         std::unordered_map<int64_t, int64_t> last;
@@ -1282,7 +1255,7 @@ int gamma_hip_raw_update_batch(gamma_hip_index* h, int64_t n, const int64_t* vid
     GH_CHECK(h, hipSetDevice(h->device));
     for (int64_t i = 0; i < n; i++) {
         if (vids[i] < 0 || vids[i] >= h->nraw) continue;
-        GH_CHECK(h, hipMemcpyAsync(h->d_raw + vids[i] * h->raw_d, vecs + i * h->raw_d, (size_t)h->raw_d * sizeof(float),
+        GH_CHECK(h, hipMemcpyAsync(h->raw_f32() + vids[i] * h->raw_d, vecs + i * h->raw_d, (size_t)h->raw_d * sizeof(float),
                                    hipMemcpyHostToDevice, h->wstream));
     }
     GH_CHECK(h, hipStreamSynchronize(h->wstream));
@@ -1300,44 +1273,37 @@ int gamma_hip_raw_gets(gamma_hip_index* h, int64_t n, const int64_t* vids, float
     for (int64_t i = 0; i < n; i++)
         if (vids[i] < 0 || vids[i] >= h->nraw) return fail(h, GAMMA_HIP_EINVAL, "vid out of range");
     GH_CHECK(h, hipSetDevice(h->device));
-    if (h->raw_half) {   // the half rows come back as they are and are widened here (exact)
-        std::vector<uint16_t> hb((size_t)n * h->raw_d);
-        for (int64_t i = 0; i < n; i++)
-            GH_CHECK(h, hipMemcpyAsync(hb.data() + i * h->raw_d, h->d_raw_h + vids[i] * h->raw_d, (size_t)h->raw_d * sizeof(uint16_t),
-                                       hipMemcpyDeviceToHost, h->wstream));
-        GH_CHECK(h, hipStreamSynchronize(h->wstream));
-        for (size_t i = 0; i < hb.size(); i++) out[i] = half_bits_to_float(hb[i]);
-        return GAMMA_HIP_OK;
-    }
-    if (h->raw_byte) {   // the byte rows come back as they are and are widened here (exact)
-        std::vector<uint8_t> bb((size_t)n * h->raw_d);
-        for (int64_t i = 0; i < n; i++)
-            GH_CHECK(h, hipMemcpyAsync(bb.data() + i * h->raw_d, h->d_raw_b + vids[i] * h->raw_d, (size_t)h->raw_d, hipMemcpyDeviceToHost,
-                                       h->wstream));
-        GH_CHECK(h, hipStreamSynchronize(h->wstream));
-        if (h->raw_byte == 2)
-            for (size_t i = 0; i < bb.size(); i++) out[i] = (float)(int8_t)bb[i];
-        else
-            for (size_t i = 0; i < bb.size(); i++) out[i] = (float)bb[i];
-        return GAMMA_HIP_OK;
-    }
-    if (h->raw_sq8) {   // the codes come back as they are and are decoded here: a multiply, then an add, each rounded in fp32
-        std::vector<uint8_t> bb((size_t)n * h->raw_d);
-        for (int64_t i = 0; i < n; i++)
-            GH_CHECK(h, hipMemcpyAsync(bb.data() + i * h->raw_d, h->d_raw_q + vids[i] * h->raw_d, (size_t)h->raw_d, hipMemcpyDeviceToHost,
-                                       h->wstream));
-        GH_CHECK(h, hipStreamSynchronize(h->wstream));
-        for (int64_t i = 0; i < n; i++)
-            for (int j = 0; j < h->raw_d; j++) {
-                const float t = (float)bb[i * h->raw_d + j] * h->sq8_step[j];
-                out[i * h->raw_d + j] = h->sq8_vmin[j] + t;
-            }
-        return GAMMA_HIP_OK;
-    }
+    // the rows come back as they are: fp32 rows straight into `out`, narrow rows into a byte buffer that is widened below
+    const int d = h->raw_d;
+    const size_t row = (size_t)d * h->raw_esz();
+    std::vector<uint8_t> bb(h->raw_narrow() ? (size_t)n * row : 0);
+    char* dst = h->raw_narrow() ? reinterpret_cast<char*>(bb.data()) : reinterpret_cast<char*>(out);
     for (int64_t i = 0; i < n; i++)
-        GH_CHECK(h, hipMemcpyAsync(out + i * h->raw_d, h->d_raw + vids[i] * h->raw_d, (size_t)h->raw_d * sizeof(float),
-                                   hipMemcpyDeviceToHost, h->wstream));
+        GH_CHECK(h, hipMemcpyAsync(dst + i * row, static_cast<const char*>(h->raw_p) + vids[i] * row, row, hipMemcpyDeviceToHost,
+                                   h->wstream));
     GH_CHECK(h, hipStreamSynchronize(h->wstream));
+    const size_t ne = (size_t)n * d;
+    switch (h->raw_et) {
+        case gh::ROW_F16: {   // widened exactly
+            const uint16_t* hb = reinterpret_cast<const uint16_t*>(bb.data());
+            for (size_t i = 0; i < ne; i++) out[i] = half_bits_to_float(hb[i]);
+            break;
+        }
+        case gh::ROW_U8:
+            for (size_t i = 0; i < ne; i++) out[i] = (float)bb[i];
+            break;
+        case gh::ROW_I8:
+            for (size_t i = 0; i < ne; i++) out[i] = (float)(int8_t)bb[i];
+            break;
+        case gh::ROW_SQ8:   // decoded: a multiply, then an add, each rounded in fp32
+            for (int64_t i = 0; i < n; i++)
+                for (int j = 0; j < d; j++) {
+                    const float t = (float)bb[i * d + j] * h->sq8_step[j];
+                    out[i * d + j] = h->sq8_vmin[j] + t;
+                }
+            break;
+        default: break;   // fp32: in place already
+    }
     return GAMMA_HIP_OK;
 }
 

@@ -79,14 +79,18 @@ void launch_pairwise_filtered(hipStream_t s, bool l2, const float* x, int nq, in
                               const float* y, int64_t ny, float* out, int64_t ld_out,
                               const FilterDesc& filt, float min_score, float max_score,
                               int64_t row_base);
-// Rows of the raw store as the flat path's readers take them: base pointer and element type (gamma_hip_raw_elem_type: 0 fp32,
-// 1 float16, 2 uint8, 3 int8, 4 sq8).  The overloads that take one launch, for et == 0, exactly what the float overloads launch.
-// tab (et == 4 only): the store's decode table, d x {step[j], vmin[j]} -- per dimension, the same for every row.
+// The element types of the raw store's rows (the integers of gamma_hip_raw_elem_type)
+enum RowType : int { ROW_F32 = 0, ROW_F16 = 1, ROW_U8 = 2, ROW_I8 = 3, ROW_SQ8 = 4 };
+inline size_t row_elem_bytes(int et) { return et == ROW_F32 ? 4 : et == ROW_F16 ? 2 : 1; }
+// Rows of the raw store as every reader of more than fp32 rows takes them -- the flat and IVFFLAT scans, the exact re-rank, the
+// tie replay: base pointer and element type.  A launcher that takes one does one switch (et) into its template on the row
+// type (float, uint16_t, uint8_t, int8_t, sq8_t); the flat overloads launch, for ROW_F32, exactly what their float overloads launch.
+// tab (ROW_SQ8 only): the store's decode table, d x {step[j], vmin[j]} -- per dimension, the same for every row.
 struct RowsRef {
     const void* p = nullptr;
-    int et = 0;
+    int et = ROW_F32;
     const float* tab = nullptr;
-    size_t esz() const { return et == 0 ? 4 : et == 1 ? 2 : 1; }
+    size_t esz() const { return row_elem_bytes(et); }
     RowsRef at(int64_t row, int d) const { return RowsRef{static_cast<const char*>(p) + (size_t)row * d * esz(), et, tab}; }
     template <class T> const T* as() const { return static_cast<const T*>(p); }
 };
@@ -418,7 +422,12 @@ void launch_select_final(hipStream_t s, bool smallest, const unsigned long long*
 void launch_map_candidates(hipStream_t s, const int* pos, int nq, int R, int P,
                            const int* probe_list, const int* pair_off, const int64_t* list_off,
                            const int64_t* ids, int64_t* cand_ids);
-void launch_rerank_dist(hipStream_t s, bool l2, const float* x, int nq, int d, const float* raw,
+// The exact re-rank over rows of any element type: the exact distance is that of the fp32 query and the widened (sq8: decoded
+// through raw.tab in front of the fma chain) row in the same operation order.  How a row is loaded depends on its type and d
+// (rerank_dev.h): float16 rows with d % 8 == 0 with one 16-byte load per lane, every other d with 2-byte loads; byte and sq8 rows
+// with d % 16 == 0 with 16-byte loads, d % 4 == 0 with dword loads, every other d with byte loads.
+// slot / nslot: the vid -> row table of a sparse store (below), fp32 rows only -- refused with any other element type.
+void launch_rerank_dist(hipStream_t s, bool l2, const float* x, int nq, int d, const RowsRef& raw,
                         int64_t nraw, const int64_t* cand_ids, int R, float min_score,
                         float max_score, float* out, const int32_t* slot = nullptr, int64_t nslot = 0);
 // raw vectors sharded with their lists (round 6).  slot [nslot]: vector id -> row of `raw` on THIS shard, -1 = held elsewhere.
@@ -440,33 +449,12 @@ struct TieFlags {
     int* count = nullptr;
     unsigned long long* stats = nullptr;
 };
-void launch_rerank_topk(hipStream_t s, bool l2, const float* x, int nq, int d, const float* raw,
+// (rows of any element type, as launch_rerank_dist takes them)
+void launch_rerank_topk(hipStream_t s, bool l2, const float* x, int nq, int d, const RowsRef& raw,
                         int64_t nraw, const int64_t* cand_ids, int R, int k, float min_score,
                         float max_score, float neutral, float* distances, int64_t* labels,
                         const int* qperm = nullptr,   // qperm: run the queries in this order (speed only)
                         const TieFlags* ties = nullptr);
-// float16 raw store (gamma_hip_raw_init_f16): the two re-rank launches over rows of IEEE binary16 -- the exact distance is that
-// of the fp32 query and float(half row) in the same operation order.  Rows with d % 8 == 0 are 16-byte aligned and read with
-// one 16-byte load per lane; every other d with 2-byte loads.
-void launch_rerank_dist_h(hipStream_t s, bool l2, const float* x, int nq, int d, const uint16_t* raw, int64_t nraw,
-                          const int64_t* cand_ids, int R, float min_score, float max_score, float* out);
-void launch_rerank_topk_h(hipStream_t s, bool l2, const float* x, int nq, int d, const uint16_t* raw, int64_t nraw,
-                          const int64_t* cand_ids, int R, int k, float min_score, float max_score, float neutral, float* distances,
-                          int64_t* labels, const int* qperm = nullptr, const TieFlags* ties = nullptr);
-// byte raw store (gamma_hip_raw_init_i8): the same two launches over rows of uint8 (is_signed = false) or int8 elements, widened
-// exactly.  Rows with d % 16 == 0 are read with 16-byte loads, d % 4 == 0 with dword loads, every other d with byte loads.
-void launch_rerank_dist_b(hipStream_t s, bool l2, const float* x, int nq, int d, const uint8_t* raw, bool is_signed, int64_t nraw,
-                          const int64_t* cand_ids, int R, float min_score, float max_score, float* out);
-void launch_rerank_topk_b(hipStream_t s, bool l2, const float* x, int nq, int d, const uint8_t* raw, bool is_signed, int64_t nraw,
-                          const int64_t* cand_ids, int R, int k, float min_score, float max_score, float neutral, float* distances,
-                          int64_t* labels, const int* qperm = nullptr, const TieFlags* ties = nullptr);
-// scalar-quantised raw store (gamma_hip_raw_init_sq8): the same two launches over rows of one code per element, decoded through
-// tab = d x {step[j], vmin[j]} (device memory) in front of the fma chain; the byte rows' loads
-void launch_rerank_dist_sq8(hipStream_t s, bool l2, const float* x, int nq, int d, const uint8_t* raw, const float* tab, int64_t nraw,
-                            const int64_t* cand_ids, int R, float min_score, float max_score, float* out);
-void launch_rerank_topk_sq8(hipStream_t s, bool l2, const float* x, int nq, int d, const uint8_t* raw, const float* tab, int64_t nraw,
-                            const int64_t* cand_ids, int R, int k, float min_score, float max_score, float neutral, float* distances,
-                            int64_t* labels, const int* qperm = nullptr, const TieFlags* ties = nullptr);
 // what k_tie_replay needs to redo one query (ties.hip)
 struct TieReplayArgs {
     const int* list;              // flagged queries, *count of them
@@ -484,7 +472,8 @@ struct TieReplayArgs {
     int nsl, slice_cap;
     const float* x;               // queries [nq][d]
     int d;
-    const float* raw;             // raw vectors (has_rank)
+    RowsRef rows;                 // raw vectors (has_rank), of any element type: launch_tie_replay takes the kernels of rows.et;
+                                  // the small-batch tail (launch_small_tail) replays over fp32 rows only
     int64_t nraw;
     const float* ex_slab = nullptr;   // raw vectors sharded with their lists (round 6): the exact distance of stream entry ps
                                       // travelled with the shards' exports -- [rows][q_stride] like the slab, NaN where a shard
@@ -503,11 +492,6 @@ struct TieReplayArgs {
     int compact_rows = 0;         // slab row i belongs to the i-th flagged query (list[i]) instead of query i
     int always_sliced = 0;        // ready == nullptr: every query is first G slab entries + slices 1.. (flat search with the
                                   // running bound: first row chunk + the candidates each later pass emitted)
-    const uint16_t* raw_h = nullptr;   // float16 raw store: the rows (raw is null then); launch_tie_replay takes the half-row kernels
-    const uint8_t* raw_b = nullptr;    // byte raw store: the rows (raw and raw_h are null then), int8 when raw_b_signed, else uint8
-    int raw_b_signed = 0;
-    const uint8_t* raw_q = nullptr;    // scalar-quantised raw store: the rows (raw, raw_h and raw_b are null then) ...
-    const float* sq8_tab = nullptr;    // ... and their decode table, d x {step[j], vmin[j]}
 };
 int tie_replay_max_k();
 int tie_small_max_k();
@@ -561,17 +545,12 @@ void launch_mark_moved(hipStream_t s, int64_t* ids, int64_t pos);
 // sparse raw store: pairs [n][2] = (vector id, row); the vid -> row table's entries, and the staged rows into their rows
 void launch_raw_slot_scatter(hipStream_t s, const int32_t* pairs, int64_t n, int32_t* tab, int64_t ntab);
 void launch_raw_rows_scatter(hipStream_t s, const float* stage, const int32_t* pairs, int64_t n, int d, float* raw, int64_t cap);
-// float16 raw store: n staged fp32 rows rounded to binary16 into rows first + i, or vids[i] (outside [0, nrows): skipped)
-void launch_raw_rows_to_half(hipStream_t s, const float* stage, const int64_t* vids, int64_t first, int64_t n, int d, uint16_t* raw,
-                             int64_t nrows);
-// byte raw store: n staged fp32 rows (checked by the host: every value is exactly storable) converted into rows first + i, or
-// vids[i] (outside [0, nrows): skipped)
-void launch_raw_rows_to_bytes(hipStream_t s, const float* stage, const int64_t* vids, int64_t first, int64_t n, int d, uint8_t* raw,
-                              int64_t nrows);
-// scalar-quantised raw store (gamma_hip_raw_init_sq8): n staged fp32 rows (checked by the host: every value is finite) encoded
-// with enc = d x {inv[j], vmin[j]} into rows first + i, or vids[i] (outside [0, nrows): skipped)
-void launch_raw_rows_to_sq8(hipStream_t s, const float* stage, const int64_t* vids, int64_t first, int64_t n, int d, const float* enc,
-                            uint8_t* raw, int64_t nrows);
+// narrow raw store: n staged fp32 rows (checked by the host) into rows first + i, or vids[i] (outside [0, nrows): skipped), of
+// `raw` (nrows rows of element type et): rounded to binary16 (ROW_F16), converted exactly (ROW_U8 / ROW_I8: every value is
+// storable) or encoded with enc = d x {inv[j], vmin[j]} (ROW_SQ8: every value is finite; enc is unread otherwise).  ROW_F32 is
+// refused: fp32 rows are copied, not converted.
+void launch_raw_rows_narrow(hipStream_t s, const float* stage, const int64_t* vids, int64_t first, int64_t n, int d, void* raw, int et,
+                            const float* enc, int64_t nrows);
 // mm[j], mm[d + j] = minimum, maximum of dimension j over n staged rows; first: mm is replaced, else folded in
 void launch_sq8_minmax(hipStream_t s, const float* x, int64_t n, int d, float* mm, bool first);
 void launch_list_checksum(hipStream_t s, const uint8_t* codes, const int64_t* ids, const int64_t* off, const int* len, int nlist,

@@ -75,61 +75,47 @@ __global__ __launch_bounds__(256) void k_rerank_dist(const float* __restrict__ x
         }
     }
 }
-void launch_rerank_dist(hipStream_t s, bool l2, const float* x, int nq, int d, const float* raw,
-                        int64_t nraw, const int64_t* cand_ids, int R, float min_score,
-                        float max_score, float* out, const int32_t* slot, int64_t nslot) {
-    if (nq <= 0) return;
-    const int gy = (R + 31) / 32;   // 32 candidates (8 lanes each) per workgroup
-    if (l2)
-        hipLaunchKernelGGL((k_rerank_dist<true>), dim3(nq, gy), dim3(256), 0, s, x, d, raw, nraw, cand_ids,
-                           R, min_score, max_score, out, slot, nslot, nullptr);
-    else
-        hipLaunchKernelGGL((k_rerank_dist<false>), dim3(nq, gy), dim3(256), 0, s, x, d, raw, nraw,
-                           cand_ids, R, min_score, max_score, out, slot, nslot, nullptr);
-}
-void launch_rerank_dist_h(hipStream_t s, bool l2, const float* x, int nq, int d, const uint16_t* raw, int64_t nraw,
-                          const int64_t* cand_ids, int R, float min_score, float max_score, float* out) {
-    if (nq <= 0) return;
-    const int gy = (R + 31) / 32;
-    if (l2)
-        hipLaunchKernelGGL((k_rerank_dist<true, uint16_t>), dim3(nq, gy), dim3(256), 0, s, x, d, raw, nraw, cand_ids, R, min_score,
-                           max_score, out, nullptr, (int64_t)0, nullptr);
-    else
-        hipLaunchKernelGGL((k_rerank_dist<false, uint16_t>), dim3(nq, gy), dim3(256), 0, s, x, d, raw, nraw, cand_ids, R, min_score,
-                           max_score, out, nullptr, (int64_t)0, nullptr);
-}
+namespace {
 template <typename ROW>
-static void launch_rerank_dist_b_(hipStream_t s, bool l2, const float* x, int nq, int d, const ROW* raw, int64_t nraw,
-                                  const int64_t* cand_ids, int R, float min_score, float max_score, float* out) {
-    const int gy = (R + 31) / 32;
-    if (l2)
-        hipLaunchKernelGGL((k_rerank_dist<true, ROW>), dim3(nq, gy), dim3(256), 0, s, x, d, raw, nraw, cand_ids, R, min_score,
-                           max_score, out, nullptr, (int64_t)0, nullptr);
-    else
-        hipLaunchKernelGGL((k_rerank_dist<false, ROW>), dim3(nq, gy), dim3(256), 0, s, x, d, raw, nraw, cand_ids, R, min_score,
-                           max_score, out, nullptr, (int64_t)0, nullptr);
-}
-void launch_rerank_dist_b(hipStream_t s, bool l2, const float* x, int nq, int d, const uint8_t* raw, bool is_signed, int64_t nraw,
-                          const int64_t* cand_ids, int R, float min_score, float max_score, float* out) {
-    if (nq <= 0) return;
-    if (is_signed)
-        launch_rerank_dist_b_(s, l2, x, nq, d, reinterpret_cast<const int8_t*>(raw), nraw, cand_ids, R, min_score, max_score, out);
-    else
-        launch_rerank_dist_b_(s, l2, x, nq, d, raw, nraw, cand_ids, R, min_score, max_score, out);
-}
-
-void launch_rerank_dist_sq8(hipStream_t s, bool l2, const float* x, int nq, int d, const uint8_t* raw, const float* tab, int64_t nraw,
-                            const int64_t* cand_ids, int R, float min_score, float max_score, float* out) {
-    if (nq <= 0) return;
-    const int gy = (R + 31) / 32;
-    const sq8_t* rows = reinterpret_cast<const sq8_t*>(raw);
+void launch_rerank_dist_t(hipStream_t s, bool l2, const float* x, int nq, int d, const ROW* raw, const float* tab, int64_t nraw,
+                          const int64_t* cand_ids, int R, float min_score, float max_score, float* out, const int32_t* slot,
+                          int64_t nslot) {
+    const int gy = (R + 31) / 32;   // 32 candidates (8 lanes each) per workgroup
     const float2* t = reinterpret_cast<const float2*>(tab);
     if (l2)
-        hipLaunchKernelGGL((k_rerank_dist<true, sq8_t>), dim3(nq, gy), dim3(256), 0, s, x, d, rows, nraw, cand_ids, R, min_score,
-                           max_score, out, nullptr, (int64_t)0, t);
+        hipLaunchKernelGGL((k_rerank_dist<true, ROW>), dim3(nq, gy), dim3(256), 0, s, x, d, raw, nraw, cand_ids, R, min_score,
+                           max_score, out, slot, nslot, t);
     else
-        hipLaunchKernelGGL((k_rerank_dist<false, sq8_t>), dim3(nq, gy), dim3(256), 0, s, x, d, rows, nraw, cand_ids, R, min_score,
-                           max_score, out, nullptr, (int64_t)0, t);
+        hipLaunchKernelGGL((k_rerank_dist<false, ROW>), dim3(nq, gy), dim3(256), 0, s, x, d, raw, nraw, cand_ids, R, min_score,
+                           max_score, out, slot, nslot, t);
+}
+}  // namespace
+void launch_rerank_dist(hipStream_t s, bool l2, const float* x, int nq, int d, const RowsRef& raw, int64_t nraw,
+                        const int64_t* cand_ids, int R, float min_score, float max_score, float* out, const int32_t* slot,
+                        int64_t nslot) {
+    if (nq <= 0) return;
+    if (slot && raw.et != ROW_F32) {   // a sparse store holds fp32 rows
+        launch_refused("launch_rerank_dist: a slot table over rows that are not fp32");
+        return;
+    }
+    switch (raw.et) {
+        case ROW_F32:
+            launch_rerank_dist_t(s, l2, x, nq, d, raw.as<float>(), nullptr, nraw, cand_ids, R, min_score, max_score, out, slot, nslot);
+            break;
+        case ROW_F16:
+            launch_rerank_dist_t(s, l2, x, nq, d, raw.as<uint16_t>(), nullptr, nraw, cand_ids, R, min_score, max_score, out, nullptr, 0);
+            break;
+        case ROW_U8:
+            launch_rerank_dist_t(s, l2, x, nq, d, raw.as<uint8_t>(), nullptr, nraw, cand_ids, R, min_score, max_score, out, nullptr, 0);
+            break;
+        case ROW_I8:
+            launch_rerank_dist_t(s, l2, x, nq, d, raw.as<int8_t>(), nullptr, nraw, cand_ids, R, min_score, max_score, out, nullptr, 0);
+            break;
+        case ROW_SQ8:   // (codes are never numbers: an sq8 store goes to the decoding kernel or nowhere)
+            launch_rerank_dist_t(s, l2, x, nq, d, raw.as<sq8_t>(), raw.tab, nraw, cand_ids, R, min_score, max_score, out, nullptr, 0);
+            break;
+        default: launch_refused("launch_rerank_dist: unknown row element type"); break;
+    }
 }
 
 // Exact distances of the entries of an exported candidate stream that can still be members of the recall_num-heap: ADC value
@@ -539,71 +525,49 @@ __global__ __launch_bounds__(256) void k_rerank_topk(const float* __restrict__ x
         labels[(int64_t)q * k + i] = id;
     }
 }
-void launch_rerank_topk(hipStream_t s, bool l2, const float* x, int nq, int d, const float* raw,
-                        int64_t nraw, const int64_t* cand_ids, int R, int k, float min_score,
-                        float max_score, float neutral, float* distances, int64_t* labels, const int* qperm,
-                        const TieFlags* ties) {
-    if (nq <= 0) return;
-    const dim3 grid((unsigned)(8 * ((nq + 7) / 8)));
-    const TieFlags tf = ties ? *ties : TieFlags{};
-    if (l2)
-        hipLaunchKernelGGL((k_rerank_topk<true>), grid, dim3(256), 0, s, x, d, raw, nraw, cand_ids,
-                           R, k, min_score, max_score, neutral, distances, labels, nq, qperm, tf, nullptr);
-    else
-        hipLaunchKernelGGL((k_rerank_topk<false>), grid, dim3(256), 0, s, x, d, raw, nraw, cand_ids,
-                           R, k, min_score, max_score, neutral, distances, labels, nq, qperm, tf, nullptr);
-}
-void launch_rerank_topk_h(hipStream_t s, bool l2, const float* x, int nq, int d, const uint16_t* raw, int64_t nraw,
-                          const int64_t* cand_ids, int R, int k, float min_score, float max_score, float neutral, float* distances,
-                          int64_t* labels, const int* qperm, const TieFlags* ties) {
-    if (nq <= 0) return;
-    const dim3 grid((unsigned)(8 * ((nq + 7) / 8)));
-    const TieFlags tf = ties ? *ties : TieFlags{};
-    if (l2)
-        hipLaunchKernelGGL((k_rerank_topk<true, uint16_t>), grid, dim3(256), 0, s, x, d, raw, nraw, cand_ids, R, k, min_score,
-                           max_score, neutral, distances, labels, nq, qperm, tf, nullptr);
-    else
-        hipLaunchKernelGGL((k_rerank_topk<false, uint16_t>), grid, dim3(256), 0, s, x, d, raw, nraw, cand_ids, R, k, min_score,
-                           max_score, neutral, distances, labels, nq, qperm, tf, nullptr);
-}
+namespace {
 template <typename ROW>
-static void launch_rerank_topk_b_(hipStream_t s, bool l2, const float* x, int nq, int d, const ROW* raw, int64_t nraw,
-                                  const int64_t* cand_ids, int R, int k, float min_score, float max_score, float neutral,
-                                  float* distances, int64_t* labels, const int* qperm, const TieFlags& tf) {
-    const dim3 grid((unsigned)(8 * ((nq + 7) / 8)));
-    if (l2)
-        hipLaunchKernelGGL((k_rerank_topk<true, ROW>), grid, dim3(256), 0, s, x, d, raw, nraw, cand_ids, R, k, min_score,
-                           max_score, neutral, distances, labels, nq, qperm, tf, nullptr);
-    else
-        hipLaunchKernelGGL((k_rerank_topk<false, ROW>), grid, dim3(256), 0, s, x, d, raw, nraw, cand_ids, R, k, min_score,
-                           max_score, neutral, distances, labels, nq, qperm, tf, nullptr);
-}
-void launch_rerank_topk_b(hipStream_t s, bool l2, const float* x, int nq, int d, const uint8_t* raw, bool is_signed, int64_t nraw,
+void launch_rerank_topk_t(hipStream_t s, bool l2, const float* x, int nq, int d, const ROW* raw, const float* tab, int64_t nraw,
                           const int64_t* cand_ids, int R, int k, float min_score, float max_score, float neutral, float* distances,
-                          int64_t* labels, const int* qperm, const TieFlags* ties) {
-    if (nq <= 0) return;
-    const TieFlags tf = ties ? *ties : TieFlags{};
-    if (is_signed)
-        launch_rerank_topk_b_(s, l2, x, nq, d, reinterpret_cast<const int8_t*>(raw), nraw, cand_ids, R, k, min_score, max_score,
-                              neutral, distances, labels, qperm, tf);
-    else
-        launch_rerank_topk_b_(s, l2, x, nq, d, raw, nraw, cand_ids, R, k, min_score, max_score, neutral, distances, labels, qperm, tf);
-}
-
-void launch_rerank_topk_sq8(hipStream_t s, bool l2, const float* x, int nq, int d, const uint8_t* raw, const float* tab, int64_t nraw,
-                            const int64_t* cand_ids, int R, int k, float min_score, float max_score, float neutral, float* distances,
-                            int64_t* labels, const int* qperm, const TieFlags* ties) {
-    if (nq <= 0) return;
+                          int64_t* labels, const int* qperm, const TieFlags& tf) {
     const dim3 grid((unsigned)(8 * ((nq + 7) / 8)));
-    const TieFlags tf = ties ? *ties : TieFlags{};
-    const sq8_t* rows = reinterpret_cast<const sq8_t*>(raw);
     const float2* t = reinterpret_cast<const float2*>(tab);
     if (l2)
-        hipLaunchKernelGGL((k_rerank_topk<true, sq8_t>), grid, dim3(256), 0, s, x, d, rows, nraw, cand_ids, R, k, min_score,
+        hipLaunchKernelGGL((k_rerank_topk<true, ROW>), grid, dim3(256), 0, s, x, d, raw, nraw, cand_ids, R, k, min_score,
                            max_score, neutral, distances, labels, nq, qperm, tf, t);
     else
-        hipLaunchKernelGGL((k_rerank_topk<false, sq8_t>), grid, dim3(256), 0, s, x, d, rows, nraw, cand_ids, R, k, min_score,
+        hipLaunchKernelGGL((k_rerank_topk<false, ROW>), grid, dim3(256), 0, s, x, d, raw, nraw, cand_ids, R, k, min_score,
                            max_score, neutral, distances, labels, nq, qperm, tf, t);
+}
+}  // namespace
+void launch_rerank_topk(hipStream_t s, bool l2, const float* x, int nq, int d, const RowsRef& raw, int64_t nraw,
+                        const int64_t* cand_ids, int R, int k, float min_score, float max_score, float neutral, float* distances,
+                        int64_t* labels, const int* qperm, const TieFlags* ties) {
+    if (nq <= 0) return;
+    const TieFlags tf = ties ? *ties : TieFlags{};
+    switch (raw.et) {
+        case ROW_F32:
+            launch_rerank_topk_t(s, l2, x, nq, d, raw.as<float>(), nullptr, nraw, cand_ids, R, k, min_score, max_score, neutral,
+                                 distances, labels, qperm, tf);
+            break;
+        case ROW_F16:
+            launch_rerank_topk_t(s, l2, x, nq, d, raw.as<uint16_t>(), nullptr, nraw, cand_ids, R, k, min_score, max_score, neutral,
+                                 distances, labels, qperm, tf);
+            break;
+        case ROW_U8:
+            launch_rerank_topk_t(s, l2, x, nq, d, raw.as<uint8_t>(), nullptr, nraw, cand_ids, R, k, min_score, max_score, neutral,
+                                 distances, labels, qperm, tf);
+            break;
+        case ROW_I8:
+            launch_rerank_topk_t(s, l2, x, nq, d, raw.as<int8_t>(), nullptr, nraw, cand_ids, R, k, min_score, max_score, neutral,
+                                 distances, labels, qperm, tf);
+            break;
+        case ROW_SQ8:
+            launch_rerank_topk_t(s, l2, x, nq, d, raw.as<sq8_t>(), raw.tab, nraw, cand_ids, R, k, min_score, max_score, neutral,
+                                 distances, labels, qperm, tf);
+            break;
+        default: launch_refused("launch_rerank_topk: unknown row element type"); break;
+    }
 }
 
 // ------------------------------------------------------------------------------------

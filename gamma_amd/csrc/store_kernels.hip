@@ -164,17 +164,6 @@ __global__ __launch_bounds__(256) void k_raw_rows_to_half(const float* __restric
         raw[row * d + c] = __half_as_ushort(__float2half_rn(stage[t]));
     }
 }
-void launch_raw_rows_to_half(hipStream_t s, const float* stage, const int64_t* vids, int64_t first, int64_t n, int d, uint16_t* raw,
-                             int64_t nrows) {
-    if (n <= 0 || d <= 0 || nrows <= 0) return;
-    if ((d & 1) == 0) {
-        const int64_t tot = n * (d >> 1);
-        hipLaunchKernelGGL((k_raw_rows_to_half<true>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, stage, vids, first, n, d, raw, nrows);
-    } else {
-        const int64_t tot = n * d;
-        hipLaunchKernelGGL((k_raw_rows_to_half<false>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, stage, vids, first, n, d, raw, nrows);
-    }
-}
 
 // byte raw store (gamma_hip_raw_init_i8): the staged fp32 rows -- integral and inside the element type's range, the host checked
 // every value -- into rows first + i, or vids[i] (a vid outside [0, nrows) is skipped; rows >= nrows are never written).  The
@@ -197,17 +186,6 @@ __global__ __launch_bounds__(256) void k_raw_rows_to_bytes(const float* __restri
         reinterpret_cast<uint32_t*>(raw)[row * dv + c] = b0 | (b1 << 8) | (b2 << 16) | (b3 << 24);
     } else {
         raw[row * d + c] = (uint8_t)((uint32_t)(int)stage[t] & 0xffu);
-    }
-}
-void launch_raw_rows_to_bytes(hipStream_t s, const float* stage, const int64_t* vids, int64_t first, int64_t n, int d, uint8_t* raw,
-                              int64_t nrows) {
-    if (n <= 0 || d <= 0 || nrows <= 0) return;
-    if ((d & 3) == 0) {
-        const int64_t tot = n * (d >> 2);
-        hipLaunchKernelGGL((k_raw_rows_to_bytes<true>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, stage, vids, first, n, d, raw, nrows);
-    } else {
-        const int64_t tot = n * d;
-        hipLaunchKernelGGL((k_raw_rows_to_bytes<false>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, stage, vids, first, n, d, raw, nrows);
     }
 }
 
@@ -240,16 +218,37 @@ __global__ __launch_bounds__(256) void k_raw_rows_to_sq8(const float* __restrict
         raw[row * d + c] = (uint8_t)sq8_encode(stage[t], enc[c]);
     }
 }
-void launch_raw_rows_to_sq8(hipStream_t s, const float* stage, const int64_t* vids, int64_t first, int64_t n, int d, const float* enc,
-                            uint8_t* raw, int64_t nrows) {
+// The one launch of the three conversions above: a thread writes 2 (float16) or 4 (bytes, codes) elements where the rows are
+// aligned to that many, else one.
+void launch_raw_rows_narrow(hipStream_t s, const float* stage, const int64_t* vids, int64_t first, int64_t n, int d, void* raw, int et,
+                            const float* enc, int64_t nrows) {
     if (n <= 0 || d <= 0 || nrows <= 0) return;
-    const float2* e = reinterpret_cast<const float2*>(enc);
-    if ((d & 3) == 0) {
-        const int64_t tot = n * (d >> 2);
-        hipLaunchKernelGGL((k_raw_rows_to_sq8<true>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, stage, vids, first, n, d, e, raw, nrows);
-    } else {
-        const int64_t tot = n * d;
-        hipLaunchKernelGGL((k_raw_rows_to_sq8<false>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, stage, vids, first, n, d, e, raw, nrows);
+    const int pack = et == ROW_F16 ? 2 : 4;
+    const bool packed = d % pack == 0;
+    const int64_t tot = n * (packed ? d / pack : d);
+    const dim3 grid((unsigned)((tot + 255) / 256));
+    switch (et) {
+        case ROW_F16: {
+            uint16_t* r = static_cast<uint16_t*>(raw);
+            if (packed) hipLaunchKernelGGL((k_raw_rows_to_half<true>), grid, dim3(256), 0, s, stage, vids, first, n, d, r, nrows);
+            else hipLaunchKernelGGL((k_raw_rows_to_half<false>), grid, dim3(256), 0, s, stage, vids, first, n, d, r, nrows);
+            break;
+        }
+        case ROW_U8:
+        case ROW_I8: {
+            uint8_t* r = static_cast<uint8_t*>(raw);
+            if (packed) hipLaunchKernelGGL((k_raw_rows_to_bytes<true>), grid, dim3(256), 0, s, stage, vids, first, n, d, r, nrows);
+            else hipLaunchKernelGGL((k_raw_rows_to_bytes<false>), grid, dim3(256), 0, s, stage, vids, first, n, d, r, nrows);
+            break;
+        }
+        case ROW_SQ8: {
+            uint8_t* r = static_cast<uint8_t*>(raw);
+            const float2* e = reinterpret_cast<const float2*>(enc);
+            if (packed) hipLaunchKernelGGL((k_raw_rows_to_sq8<true>), grid, dim3(256), 0, s, stage, vids, first, n, d, e, r, nrows);
+            else hipLaunchKernelGGL((k_raw_rows_to_sq8<false>), grid, dim3(256), 0, s, stage, vids, first, n, d, e, r, nrows);
+            break;
+        }
+        default: launch_refused("launch_raw_rows_narrow: not a narrow element type"); break;
     }
 }
 

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "block_utils.h"
 #include "device_math.h"
 #include "heap_dev.h"
@@ -59,10 +61,10 @@ __device__ __forceinline__ TieLds tie_carve(char* p, int R, int k, int P, int sl
 
 // One query, replayed the way the reference runs it.  Called by all NT threads of a workgroup (NT a multiple
 // of 64, <= 1024); `lds` = tie_replay_lds_bytes_(R, k, P, SLAB) bytes, 16-byte aligned, free for this call.
-// HALF: the raw rows are IEEE binary16 (a.raw_h; gamma_hip_raw_init_f16) -- only the row reads of the exact distances differ.
-// BYTE: 1 = rows of uint8, 2 = rows of int8 (a.raw_b; gamma_hip_raw_init_i8), likewise.
-// BYTE: 3 = scalar-quantised rows (a.raw_q decoded through a.sq8_tab; gamma_hip_raw_init_sq8), likewise.
-template <bool L2, int NT, int SLAB = TR_SLAB, int STG = TR_STAGE, int MAXK = TR_MAXK, bool HALF = false, int BYTE = 0>
+// ROW: what a.rows.p points at, the row type of the re-rank kernels (float; uint16_t = IEEE binary16; uint8_t; int8_t; sq8_t =
+// codes decoded through a.rows.tab) -- the caller instantiates the one that a.rows.et names; only the row reads of the exact
+// distances differ.
+template <bool L2, int NT, int SLAB = TR_SLAB, int STG = TR_STAGE, int MAXK = TR_MAXK, typename ROW = float>
 __device__ __forceinline__ void tie_replay_query(const TieReplayArgs& a, int q, char* lds, unsigned long long* dbg,
                                                  int slab_row = -1) {
 #define GH_TT(i) do { if (dbg && threadIdx.x == 0) dbg[i] = wall_clock64(); } while (0)
@@ -251,14 +253,16 @@ __device__ __forceinline__ void tie_replay_query(const TieReplayArgs& a, int q, 
                     if (l8 == 0 && a.ex_missing) atomicAdd(a.ex_missing, 1);
                     live = false;
                 }
-            } else if constexpr (HALF) {
-                dis = rerank_dist8<L2>(xq, a.raw_h + (live ? id : 0) * a.d, a.d, l8, live);
-            } else if constexpr (BYTE == 3) {
-                dis = rerank_dist8_sq8<L2>(xq, a.raw_q + (live ? id : 0) * a.d, reinterpret_cast<const float2*>(a.sq8_tab), a.d, l8, live);
-            } else if constexpr (BYTE != 0) {
-                dis = rerank_dist8_bytes<L2, BYTE == 2>(xq, a.raw_b + (live ? id : 0) * a.d, a.d, l8, live);
+            } else if constexpr (std::is_same<ROW, uint16_t>::value) {
+                dis = rerank_dist8<L2>(xq, static_cast<const uint16_t*>(a.rows.p) + (live ? id : 0) * a.d, a.d, l8, live);
+            } else if constexpr (std::is_same<ROW, sq8_t>::value) {
+                dis = rerank_dist8_sq8<L2>(xq, static_cast<const uint8_t*>(a.rows.p) + (live ? id : 0) * a.d,
+                                           reinterpret_cast<const float2*>(a.rows.tab), a.d, l8, live);
+            } else if constexpr (!std::is_same<ROW, float>::value) {   // uint8_t, int8_t
+                dis = rerank_dist8_bytes<L2, std::is_same<ROW, int8_t>::value>(xq, static_cast<const uint8_t*>(a.rows.p) + (live ? id : 0) * a.d,
+                                                                              a.d, l8, live);
             } else {
-                dis = rerank_dist8<L2>(xq, a.raw + (live ? id : 0) * a.d, a.d, l8, live);
+                dis = rerank_dist8<L2>(xq, static_cast<const float*>(a.rows.p) + (live ? id : 0) * a.d, a.d, l8, live);
             }
             if (l8 == 0 && j < R) {
                 const bool ok = live && dis <= a.max_score && dis >= a.min_score;   // IsSimilarScoreValid

@@ -46,41 +46,43 @@ int tie_small_max_k() { return TR_MAXK; }
 int tie_replay_max_probes() { return TR_MAXP; }
 size_t tie_replay_lds_bytes(int R, int k, int P) { return tie_replay_lds_bytes_(R, k, P); }
 
-template <bool L2, int STG, int MAXK = TR_MAXK, bool HALF = false, int BYTE = 0>
+template <bool L2, int STG, int MAXK = TR_MAXK, typename ROW = float>
 __global__ __launch_bounds__(256) void k_tie_replay(TieReplayArgs a) {
     extern __shared__ __attribute__((aligned(16))) char s_tie_lds[];
     const int nflag = min(*a.count, a.nq);
     for (int fi = blockIdx.x; fi < nflag; fi += gridDim.x)
-        tie_replay_query<L2, 256, TR_SLAB, STG, MAXK, HALF, BYTE>(a, a.list[fi], s_tie_lds, (a.dbg && fi == 0) ? a.dbg : nullptr,
-                                                             a.compact_rows ? fi : -1);
+        tie_replay_query<L2, 256, TR_SLAB, STG, MAXK, ROW>(a, a.list[fi], s_tie_lds, (a.dbg && fi == 0) ? a.dbg : nullptr,
+                                                           a.compact_rows ? fi : -1);
 }
 
-// float16 (HALF), byte (BYTE = 1 uint8, 2 int8) and scalar-quantised (BYTE = 3) raw stores, the IVFPQ replay of stage B: the same three kernels as for fp32 rows
-// with the row reads of that store
-template <bool HALF, int BYTE>
-static void launch_tie_replay_narrow(hipStream_t s, bool l2, const TieReplayArgs& a, int grid) {
+// The three kernels of one row type (ROW: what a.rows.p points at, tie_dev.h), chosen by the sizes of the call
+template <typename ROW>
+static void launch_tie_replay_t(hipStream_t s, bool l2, const TieReplayArgs& a, int grid) {
     if (a.R > TR_MAXK || a.k > TR_MAXK) {
+        // heaps beyond 1024 entries (up to the 4096 the ABI accepts): the same replay with a sort buffer of 4096 items --
+        // up to 155 KB of LDS, one workgroup per CU; a sequential heap_reorder of 4096 entries takes milliseconds, which
+        // is what a request for thousands of results with a tie at its cut costs
         const size_t lds = tie_replay_lds_bytes_(a.R, a.k, a.P, TR_SLAB, TR_MAXK_BIG);
-        static std::atomic<uint64_t> attr_n{0};   // per device (one static per instantiation)
-        if (first_call_on_device(attr_n)) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_tie_replay<true, TR_MAXK_BIG, TR_MAXK_BIG, HALF, BYTE>),
+        static std::atomic<uint64_t> attr{0};   // per device (one static per instantiation, as the attribute is per kernel)
+        if (first_call_on_device(attr)) {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_tie_replay<true, TR_MAXK_BIG, TR_MAXK_BIG, ROW>),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 << 10);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_tie_replay<false, TR_MAXK_BIG, TR_MAXK_BIG, HALF, BYTE>),
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_tie_replay<false, TR_MAXK_BIG, TR_MAXK_BIG, ROW>),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 << 10);
         }
-        if (l2) hipLaunchKernelGGL((k_tie_replay<true, TR_MAXK_BIG, TR_MAXK_BIG, HALF, BYTE>), dim3(grid), dim3(256), lds, s, a);
-        else hipLaunchKernelGGL((k_tie_replay<false, TR_MAXK_BIG, TR_MAXK_BIG, HALF, BYTE>), dim3(grid), dim3(256), lds, s, a);
+        if (l2) hipLaunchKernelGGL((k_tie_replay<true, TR_MAXK_BIG, TR_MAXK_BIG, ROW>), dim3(grid), dim3(256), lds, s, a);
+        else hipLaunchKernelGGL((k_tie_replay<false, TR_MAXK_BIG, TR_MAXK_BIG, ROW>), dim3(grid), dim3(256), lds, s, a);
         return;
     }
-    if (a.slice_cap > TR_STAGE) {   // recall_num beyond 256: slices of 2048 items
+    if (a.slice_cap > TR_STAGE) {   // long slices: recall_num beyond 256; flat search, the candidate lists of the running bound
         const size_t lds = tie_replay_lds_bytes_(a.R, a.k, a.P, TR_SLAB, 2048);
-        if (l2) hipLaunchKernelGGL((k_tie_replay<true, 2048, TR_MAXK, HALF, BYTE>), dim3(grid), dim3(256), lds, s, a);
-        else hipLaunchKernelGGL((k_tie_replay<false, 2048, TR_MAXK, HALF, BYTE>), dim3(grid), dim3(256), lds, s, a);
+        if (l2) hipLaunchKernelGGL((k_tie_replay<true, 2048, TR_MAXK, ROW>), dim3(grid), dim3(256), lds, s, a);
+        else hipLaunchKernelGGL((k_tie_replay<false, 2048, TR_MAXK, ROW>), dim3(grid), dim3(256), lds, s, a);
         return;
     }
     const size_t lds = tie_replay_lds_bytes(a.R, a.k, a.P);
-    if (l2) hipLaunchKernelGGL((k_tie_replay<true, TR_STAGE, TR_MAXK, HALF, BYTE>), dim3(grid), dim3(256), lds, s, a);
-    else hipLaunchKernelGGL((k_tie_replay<false, TR_STAGE, TR_MAXK, HALF, BYTE>), dim3(grid), dim3(256), lds, s, a);
+    if (l2) hipLaunchKernelGGL((k_tie_replay<true, TR_STAGE, TR_MAXK, ROW>), dim3(grid), dim3(256), lds, s, a);
+    else hipLaunchKernelGGL((k_tie_replay<false, TR_STAGE, TR_MAXK, ROW>), dim3(grid), dim3(256), lds, s, a);
 }
 
 void launch_tie_replay(hipStream_t s, bool l2, const TieReplayArgs& a0) {
@@ -107,44 +109,14 @@ void launch_tie_replay(hipStream_t s, bool l2, const TieReplayArgs& a0) {
         launch_refused("launch_tie_replay: survivor slices of more than 2048 items");
         return;
     }
-    if (a.raw_q) {
-        launch_tie_replay_narrow<false, 3>(s, l2, a, grid);
-        return;
+    switch (a.rows.et) {
+        case ROW_F32: launch_tie_replay_t<float>(s, l2, a, grid); break;
+        case ROW_F16: launch_tie_replay_t<uint16_t>(s, l2, a, grid); break;
+        case ROW_U8: launch_tie_replay_t<uint8_t>(s, l2, a, grid); break;
+        case ROW_I8: launch_tie_replay_t<int8_t>(s, l2, a, grid); break;
+        case ROW_SQ8: launch_tie_replay_t<sq8_t>(s, l2, a, grid); break;
+        default: launch_refused("launch_tie_replay: unknown row element type"); break;
     }
-    if (a.raw_b) {
-        if (a.raw_b_signed) launch_tie_replay_narrow<false, 2>(s, l2, a, grid);
-        else launch_tie_replay_narrow<false, 1>(s, l2, a, grid);
-        return;
-    }
-    if (a.raw_h) {
-        launch_tie_replay_narrow<true, 0>(s, l2, a, grid);
-        return;
-    }
-    if (a.R > TR_MAXK || a.k > TR_MAXK) {
-        // heaps beyond 1024 entries (up to the 4096 the ABI accepts): the same replay with a sort buffer of 4096 items --
-        // up to 155 KB of LDS, one workgroup per CU; a sequential heap_reorder of 4096 entries takes milliseconds, which
-        // is what a request for thousands of results with a tie at its cut costs
-        const size_t lds = tie_replay_lds_bytes_(a.R, a.k, a.P, TR_SLAB, TR_MAXK_BIG);
-        static std::atomic<uint64_t> attr{0};   // per device
-        if (first_call_on_device(attr)) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_tie_replay<true, TR_MAXK_BIG, TR_MAXK_BIG>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 << 10);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_tie_replay<false, TR_MAXK_BIG, TR_MAXK_BIG>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 << 10);
-        }
-        if (l2) hipLaunchKernelGGL((k_tie_replay<true, TR_MAXK_BIG, TR_MAXK_BIG>), dim3(grid), dim3(256), lds, s, a);
-        else hipLaunchKernelGGL((k_tie_replay<false, TR_MAXK_BIG, TR_MAXK_BIG>), dim3(grid), dim3(256), lds, s, a);
-        return;
-    }
-    if (a.slice_cap > TR_STAGE) {      // long slices (flat search: the candidate lists of the running bound)
-        const size_t lds = tie_replay_lds_bytes_(a.R, a.k, a.P, TR_SLAB, 2048);
-        if (l2) hipLaunchKernelGGL((k_tie_replay<true, 2048>), dim3(grid), dim3(256), lds, s, a);
-        else hipLaunchKernelGGL((k_tie_replay<false, 2048>), dim3(grid), dim3(256), lds, s, a);
-        return;
-    }
-    const size_t lds = tie_replay_lds_bytes(a.R, a.k, a.P);
-    if (l2) hipLaunchKernelGGL((k_tie_replay<true, TR_STAGE>), dim3(grid), dim3(256), lds, s, a);
-    else hipLaunchKernelGGL((k_tie_replay<false, TR_STAGE>), dim3(grid), dim3(256), lds, s, a);
 }
 
 // ------------------------------------------------------------------------------------
