@@ -56,14 +56,14 @@ int gamma_hip_create(int device, gamma_hip_index** out) {
         hipMemset(h->d_scan_codes, 0, sizeof(unsigned long long)) != hipSuccess ||
         hipMalloc((void**)&h->d_tie_stats, 3 * sizeof(unsigned long long)) != hipSuccess ||
         hipMemset(h->d_tie_stats, 0, 3 * sizeof(unsigned long long)) != hipSuccess ||
-        hipMalloc((void**)&h->d_bound_stat, 5 * sizeof(unsigned long long)) != hipSuccess ||
-        hipMemset(h->d_bound_stat, 0, 5 * sizeof(unsigned long long)) != hipSuccess ||
-        hipHostMalloc((void**)&h->pin_bound_stat, 4 * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess) {
+        hipMalloc((void**)&h->bound_fb.d_stat, 5 * sizeof(unsigned long long)) != hipSuccess ||
+        hipMemset(h->bound_fb.d_stat, 0, 5 * sizeof(unsigned long long)) != hipSuccess ||
+        hipHostMalloc((void**)&h->bound_fb.pin_stat, 4 * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess) {
         (void)hipStreamDestroy(h->stream);
         delete h;
         return GAMMA_HIP_EDEVICE;
     }
-    memset(h->pin_bound_stat, 0, 4 * sizeof(unsigned long long));
+    memset(h->bound_fb.pin_stat, 0, 4 * sizeof(unsigned long long));
     // workspace budget of the chunked buffers: an eighth of the device memory, 1..32 GiB (36 GB -> 32 GiB
     // on a 288 GB MI355X); gamma_hip_set_workspace_budget overrides
     size_t free_b = 0, total_b = 0;
@@ -134,7 +134,7 @@ int gamma_hip_destroy(gamma_hip_index* h) {
     }
     if (h->d_raw_slot) (void)hipFree(h->d_raw_slot);
     void* ptrs[] = {h->d_list_rank, h->raw_p, h->d_sq8_tab, h->d_bitmap, h->d_cc, h->d_cc_norms, h->d_pqc, h->d_T2, h->d_codes,
-                    h->d_ids, h->d_list_mask, h->d_scan_codes, h->d_tie_stats, h->d_v2d, h->d_sums, h->d_t2max, h->d_bound_stat,
+                    h->d_ids, h->d_list_mask, h->d_scan_codes, h->d_tie_stats, h->d_v2d, h->d_sums, h->d_t2max, h->bound_fb.d_stat,
                     h->d_bin_cc, h->d_bin_stats, h->d_bf_codes, h->d_bf_stats, h->d_cc_img, h->d_cbf_stat, h->d_opq};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
@@ -148,8 +148,8 @@ int gamma_hip_destroy(gamma_hip_index* h) {
     for (void* pp : h->comb_pin)
         if (pp) (void)hipHostFree(pp);
     if (h->dir_pin) (void)hipHostFree(h->dir_pin);
-    if (h->bound_copy_ev) (void)hipEventDestroy(h->bound_copy_ev);
-    if (h->pin_bound_stat) (void)hipHostFree(h->pin_bound_stat);
+    if (h->bound_fb.copy_ev) (void)hipEventDestroy(h->bound_fb.copy_ev);
+    if (h->bound_fb.pin_stat) (void)hipHostFree(h->bound_fb.pin_stat);
     if (h->cbf_copy_ev) (void)hipEventDestroy(h->cbf_copy_ev);
     if (h->pin_cbf_stat) (void)hipHostFree(h->pin_cbf_stat);
     if (h->pin_flat_over) (void)hipHostFree(h->pin_flat_over);
@@ -336,8 +336,7 @@ int gamma_hip_blas_form_not_restated(gamma_hip_index* h, int64_t* out_calls, int
 int gamma_hip_set_scan_bound_feedback(gamma_hip_index* h, int on) {
     if (!h) return GAMMA_HIP_EINVAL;
     SearchLock lk(h);
-    h->bound_feedback_off = on == 0;
-    h->bound_off_calls = 0;
+    h->bound_fb.set_on(on != 0);
     return GAMMA_HIP_OK;
 }
 
@@ -347,11 +346,11 @@ int gamma_hip_scan_bound_stats(gamma_hip_index* h, int64_t* out4) {
     GH_CHECK(h, hipSetDevice(h->device));
     GH_CHECK(h, hipStreamSynchronize(h->stream));
     unsigned long long v[5] = {0, 0, 0, 0, 0};
-    GH_CHECK(h, hipMemcpy(v, h->d_bound_stat, sizeof(v), hipMemcpyDeviceToHost));
-    const int slot = h->bound_epoch & 1;   // the counts of the current kind of call
+    GH_CHECK(h, hipMemcpy(v, h->bound_fb.d_stat, sizeof(v), hipMemcpyDeviceToHost));
+    const int slot = h->bound_fb.slot();   // the counts of the current kind of call
     out4[0] = (int64_t)v[2 * slot];
     out4[1] = (int64_t)v[2 * slot + 1];
-    out4[2] = h->bound_backoffs;
+    out4[2] = h->bound_fb.backoffs;
     out4[3] = (int64_t)v[4];
     return GAMMA_HIP_OK;
 }

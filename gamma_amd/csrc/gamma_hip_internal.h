@@ -68,6 +68,55 @@ struct StageEvent {
     bool count;
 };
 
+// The bounded scan's feedback on a handle: the counters k_select_final adds to, their pinned image and the copy between
+// them.  The rules (what a sample decides) are gh::BoundFeedbackState's, scan_plan.h.
+struct BoundFeedback : gh::BoundFeedbackState {
+    unsigned long long* d_stat = nullptr;     // 2 slots x {queries given to the unfiltered selection, queries}, then: consumer groups that gave up waiting
+    unsigned long long* pin_stat = nullptr;   // the two slots as of some recent call (pinned host memory)
+    hipEvent_t copy_ev = nullptr;             // behind the last copy into pin_stat
+    bool copy_pending = false;
+    unsigned long long* d_slot() const { return d_stat + 2 * slot(); }   // the counts of the current kind of call
+    unsigned long long* d_timeouts() const { return d_stat + 4; }
+    // an eligible call: is it bounded?  enabled: ScanSwitches::no_bound_feedback is not set
+    hipError_t begin(hipStream_t s, uint64_t sig_now, bool enabled, bool* bounded) {
+        if (new_kind(sig_now)) {
+            if (copy_pending) {   // a copy of the previous kind's counts still on its way: it lands before the words are reused
+                (void)hipEventSynchronize(copy_ev);
+                copy_pending = false;
+            }
+            pin_stat[2 * slot()] = pin_stat[2 * slot() + 1] = 0;
+            const hipError_t e = hipMemsetAsync(d_slot(), 0, 2 * sizeof(unsigned long long), s);
+            if (e != hipSuccess) return e;
+        }
+        Sample smp = {0, 0};
+        bool landed = false;
+        if (enabled && consults()) {
+            // (the pair is consulted only once the copy that writes it has completed -- copy_ev -- so the two words
+            //  belong to one state of the counters)
+            landed = !copy_pending || hipEventQuery(copy_ev) == hipSuccess;
+            if (landed) copy_pending = false;
+            else (void)hipGetLastError();
+            smp = {pin_stat[2 * slot()], pin_stat[2 * slot() + 1]};
+        }
+        *bounded = step(enabled, landed ? &smp : nullptr);
+        return hipSuccess;
+    }
+    // behind k_select_final of a bounded call: the counts as of this call, for a later call's decision (16 bytes; ~5 us on
+    // the call's critical path, so: the first calls of a kind, then every 16th)
+    hipError_t end(hipStream_t s) {
+        hipError_t e = hipSuccess;
+        if (copy_due() && !copy_pending) {
+            e = hipMemcpyAsync(pin_stat + 2 * slot(), d_slot(), 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s);
+            if (e == hipSuccess && !copy_ev) e = hipEventCreateWithFlags(&copy_ev, hipEventDisableTiming);
+            if (e == hipSuccess) e = hipEventRecord(copy_ev, s);
+            if (e != hipSuccess) return e;
+            copy_pending = true;
+        }
+        calls++;
+        return e;
+    }
+};
+
 }  // namespace ghi
 using ghi::DevBuf;
 using ghi::StageEvent;
@@ -267,22 +316,7 @@ struct gamma_hip_index {
     int* d_list_rank = nullptr;   // spatial order of the coarse centroids (scan locality only)
     bool sort_queries = getenv("GAMMA_HIP_NO_QUERY_SORT") == nullptr;
     bool scan_bound = getenv("GAMMA_HIP_NO_SCAN_BOUND") == nullptr;
-    // Feedback for the bounded scan (results are the same either way): the pre-filter pays when the first probe group
-    // bounds well.  On data where it does not (full-size C5: noise-dominated inner-product vectors, 2460 survivors per
-    // query instead of ~100, every query sent to the unfiltered selection AFTER the filtered scan) the path costs more
-    // than it saves.  k_select_final counts the queries it gives up on; the totals come back through a pinned word every
-    // few calls, and while more than half of the recent queries fell through the handle scans unbounded, re-probing now
-    // and then.
-    unsigned long long* d_bound_stat = nullptr;    // 2 slots x {queries given to the unfiltered selection, queries}, then: consumer groups that gave up waiting
-    unsigned long long* pin_bound_stat = nullptr;  // the two slots as of some recent call (pinned host memory)
-    unsigned long long bound_seen[2] = {0, 0};     // what the last decision had read
-    hipEvent_t bound_copy_ev = nullptr;            // behind the last copy into pin_bound_stat
-    bool bound_copy_pending = false;
-    uint64_t bound_sig = 0;                        // (nprobe, recall_num, metric, filter, shard) of the calls the counts are of
-    int bound_epoch = 0;                           // kinds of call seen; its low bit selects the counter slot
-    bool bound_feedback_off = false;               // gamma_hip_set_scan_bound_feedback(h, 0): the pre-filter whenever it applies
-    int bound_calls = 0, bound_off_calls = 0;      // calls since the last copy; unbounded calls left before the re-probe
-    int64_t bound_backoffs = 0;                    // times the handle turned the pre-filter off
+    ghi::BoundFeedback bound_fb;   // feedback for the bounded scan (scan_plan.h: results are the same either way)
 
     // inverted-list arena
     uint8_t* d_codes = nullptr;

@@ -272,6 +272,146 @@ int ivfpq_coarse(H* h, const gamma_hip_search_params* p, int nq, const float* d_
 
 // ---- IVFPQ stage A: coarse + tables + scan + top-R + ids ------------------------------
 // results: w_cand_dis [nq*R] (ADC distance, best first, sentinel pad), w_cand_ids [nq*R]
+// What runs -- probes per workgroup, bounded or not, which filter pass over how many groups and slices, the slab stride -- is
+// decided by gh::ScanPlan from a gh::ScanShape (scan_plan.h / .cpp: every threshold and switch of the stage); whether an
+// eligible call runs bounded is BoundFeedback's answer (gamma_hip_internal.h).  The functions here carry the plan out.
+
+// what the plan depends on, as plain values
+static gh::ScanShape scan_shape(const H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int nq, int R, bool shard,
+                                bool compacted, const BoundXchg* bx) {
+    gh::ScanShape sh;
+    sh.nq = nq;
+    sh.P = p->nprobe;
+    sh.R = R;
+    sh.M = h->M;
+    sh.nlist = h->nlist;
+    sh.max_list_len = h->max_list_len;
+    sh.q_stride_cap = h->q_stride_cap;
+    sh.l2 = p->metric == GAMMA_HIP_METRIC_L2;
+    sh.pq4 = h->ksub == gh::kPq4Ksub;
+    sh.table_mode = h->table_mode;
+    sh.have_sums = h->d_sums && h->d_t2max;
+    sh.prefiltered = h->prefiltered;
+    sh.cmp_has_sums = h->cmp_has_sums;
+    sh.cmp_by_clause = h->cmp_by_clause;
+    sh.any_clause = fc.any_clause;
+    sh.per_query_filters = fc.d_qf != nullptr;
+    sh.rejects = (h->d_bitmap && h->bitmap_any) || h->n_moved > 0;
+    sh.shard = shard;
+    sh.compacted = compacted;
+    sh.two_phase = bx && bx->two_phase;
+    if (sh.two_phase) sh.G1 = bx->G1;
+    sh.scan_bound = h->scan_bound;
+    sh.sort_queries = h->sort_queries && h->d_list_rank;
+    sh.lists = gh::scan_list_stats(h->ntotal, h->nlist, h->h_list_len.data(), h->h_list_mask.empty() ? nullptr : h->h_list_mask.data(), shard);
+    return sh;
+}
+
+// the arguments every scan launch of a call shares (kernels.h ScanArgs); a call site adds its probe groups, bound, fused
+// codebook, repair list or unit mode
+static gh::ScanArgs scan_args(H* h, bool l2, const FiltCtx& fc, int nq, int P, const float* d_x, const float* dis0, int64_t q_stride,
+                              int need_ids) {
+    gh::ScanArgs a;
+    a.l2 = l2;
+    a.x = d_x;
+    a.nq = nq;
+    a.d = h->d;
+    a.M = h->M;
+    a.P = P;
+    a.probe_list = h->w_probe.as<int>();
+    a.coarse_dis = dis0;
+    a.cc = h->d_cc;
+    a.st2 = h->scan_st2(l2);
+    a.T2 = h->d_T2;
+    a.list_off = h->d_list_off;
+    a.list_len = h->d_list_len;
+    a.list_mask = h->d_list_mask;
+    a.nlist = h->nlist;
+    a.codes = h->d_codes;
+    a.ids = h->d_ids;
+    a.pair_off = h->w_pair_off.as<int>();
+    a.q_stride = q_stride;
+    a.out = h->w_dist.as<float>();
+    a.ftab = fc.d_tab;
+    a.qfil = fc.d_qf;
+    a.need_ids = need_ids;
+    return a;
+}
+
+// the consumer probes of a bounded scan list-major over byte tables (q8scan.hip), behind the producers' launch
+static int scan_list_major(H* h, const gh::ScanPlan& pl, const gh::ScanShape& sh, const gh::ScanBound& sb, const FiltCtx& fc,
+                           const float* d_x, const float* dis0) {
+    const int nq = sh.nq, P = sh.P, M = sh.M, nlist = sh.nlist;
+    GH_CHECK(h, h->w_q8.ensure((size_t)nq * M * 256));
+    GH_CHECK(h, h->w_q8meta.ensure((size_t)nq * 4 * sizeof(float)));
+    GH_CHECK(h, h->w_q8cand.ensure((size_t)nq * gh::q8_cand_cap(nq) * sizeof(uint32_t)));
+    GH_CHECK(h, h->w_q8int.ensure(gh::q8_int_words(nq, P, pl.G, nlist) * sizeof(int)));
+    gh::Q8Args qa;
+    qa.nq = nq; qa.P = P; qa.G = pl.G; qa.M = M; qa.nlist = nlist;
+    qa.mean_len = sh.lists.mean_len;
+    qa.probe_list = h->w_probe.as<int>();
+    qa.coarse_dis = dis0;
+    qa.st2 = h->w_st2.as<float>();
+    if (sh.shard && !gh::ScanSwitches::get().no_q8_demand) qa.xd = d_x;
+    qa.pqc = h->d_pqc;
+    qa.d = h->d;
+    qa.T2 = h->d_T2;
+    qa.t2max = h->d_t2max;
+    qa.sums = h->d_sums;
+    qa.codes = h->d_codes;
+    qa.ids = h->d_ids;
+    qa.list_off = h->d_list_off;
+    qa.list_len = h->d_list_len;
+    qa.list_mask = h->d_list_mask;
+    qa.pair_off = h->w_pair_off.as<int>();
+    qa.ready = sb.ready;
+    qa.ftab = fc.d_tab;
+    qa.need_ids = pl.need_ids;
+    qa.surv = sb.surv;
+    qa.gcnt = sb.gcnt;
+    qa.cnt_stride = pl.nsl;
+    qa.slice_cap = pl.cap;
+    qa.rq_list = sb.rq_list;
+    qa.rq_count = sb.rq_count;
+    qa.q8 = h->w_q8.as<uint8_t>();
+    qa.meta = reinterpret_cast<float4*>(h->w_q8meta.p);
+    qa.cand = h->w_q8cand.as<uint32_t>();
+    qa.iwork = h->w_q8int.as<int>();
+    gh::launch_q8_consumers(h->stream, qa);
+    return GAMMA_HIP_OK;
+}
+
+// GAMMA_HIP_BOUND_DBG=1: the bounded scan's statistics of the 9th .. 14th call; =shard: of list-shard calls only
+// (synchronises the stream)
+static void scan_bound_dump(H* h, bool shard, int nq, const gh::ScanBound& sb, const gh::ScanPlan& pl) {
+    static const bool dbg_any = getenv("GAMMA_HIP_BOUND_DBG") != nullptr;
+    static const bool dbg_shard = dbg_any && getenv("GAMMA_HIP_BOUND_DBG")[0] == 's';
+    static const int dbg_from = 8;
+    static int shown = 0;
+    if (!(dbg_any && (!dbg_shard || shard) && shown++ >= dbg_from && shown <= dbg_from + 5)) return;
+    std::vector<uint8_t> hf(nq);
+    std::vector<int> hc((size_t)nq * pl.nsl);
+    (void)hipStreamSynchronize(h->stream);
+    (void)hipMemcpy(hf.data(), h->w_sflag.p, nq, hipMemcpyDeviceToHost);
+    (void)hipMemcpy(hc.data(), sb.gcnt, hc.size() * sizeof(int), hipMemcpyDeviceToHost);
+    std::vector<unsigned long long> hr(nq);
+    (void)hipMemcpy(hr.data(), sb.ready, (size_t)nq * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+    int64_t nf = 0, tot = 0, mx = 0, nobound = 0;
+    for (int i = 0; i < nq; i++) {
+        nf += hf[i];
+        nobound += (hr[i] >> 32) != 1ull;
+    }
+    for (size_t i = 0; i < hc.size(); i++) {
+        tot += hc[i];
+        mx = std::max<int64_t>(mx, hc[i]);
+    }
+    unsigned long long timeouts = 0;
+    (void)hipMemcpy(&timeouts, h->bound_fb.d_timeouts(), sizeof(timeouts), hipMemcpyDeviceToHost);
+    fprintf(stderr, "scan bound: %lld of %d queries unfiltered (%lld without a bound), survivors per query mean %.1f, "
+            "per slice max %lld; G %d, %d groups, %d slices, q_stride %lld; consumers that gave up waiting so far %llu\n",
+            (long long)nf, nq, (long long)nobound, (double)tot / nq, (long long)mx, pl.G, pl.PGN, pl.nsl, (long long)pl.q_stride, timeouts);
+}
+
 int ivfpq_stage_a(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int nq,
                   const float* d_x, int R, const float* pre_dis, const int* pre_probe,
                   bool shard, float* out_dis, int64_t* out_ids, BoundXchg* bx) {
@@ -280,7 +420,7 @@ int ivfpq_stage_a(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int
     const bool l2 = p->metric == GAMMA_HIP_METRIC_L2;
     // 4-bit codes (pq4.hip) take ONE path: shared coarse quantizer, k_pq4_ip_table, pair offsets, k_ivfpq4_scan_pair
     // unbounded, the unfiltered selection -- the bounded scan with its feedback, fused / residual tables and the byte
-    // passes (cf, c8, q8) are 8-bit kernels and are gated off below
+    // passes (cf, c8, q8) are 8-bit kernels and the plan gates them off
     const bool pq4 = h->ksub == gh::kPq4Ksub;
     if (pq4 && (shard || bx)) return pq4_refuse(h, "a list-shard search");
     hipStream_t s = h->stream;
@@ -304,6 +444,7 @@ int ivfpq_stage_a(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int
         GH_CHECK(h, h->w_cand_ids.ensure((size_t)nq * R * sizeof(int64_t)));
         out_ids = h->w_cand_ids.as<int64_t>();
     }
+    const bool compacted = shard && pre_dis && pre_probe;
     if (pre_dis && pre_probe) {
         if (shard) {
             // dense probe groups for the owned lists (kernels.hip, k_compact_probes)
@@ -319,65 +460,16 @@ int ivfpq_stage_a(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int
         GH_TRY(ivfpq_coarse(h, p, nq, d_x, nullptr, nullptr, /*defer_join=*/true));
     }
     h->scan_pairs += (int64_t)nq * P;
-    // ids are only read during the scan when something can reject an entry: a delete bit,
-    // a range filter, or a superseded (bit 63) slot left behind by Update
-    const int need_ids =
-            (!h->prefiltered && (fc.any_clause || (h->d_bitmap && h->bitmap_any) || h->n_moved > 0)) ? 1 : 0;
-    const int* qperm = nullptr;
-    // Probes per workgroup.  Sharded search with a compacted assignment: a query keeps ~P/W probes on
-    // this shard, all in its first group(s) -- the other P/G - 1 workgroups of the query would start only
-    // to find nothing to do (at W = 8 that was half of the scan time).  When the expected candidate
-    // count per query is small, ONE workgroup takes all of a query's probes (G = P): it bounds the
-    // R-th best itself (producer path of the pre-filter, no consumers), and computes the query's PQ
-    // table on the fly instead of reading it back from HBM (IPF, kernels.hip).
-    // 8 probes per workgroup pay off with short lists (half the query-table re-reads, a tighter bound from a
-    // first group of 8 lists); long lists or many probes balance better with 4 (tools/shape_sweep.py)
-    // codes per list of the lists THIS handle scans: a list shard holds (or, under a mask, scans) 1 / W of the lists
-    double mean_len = (double)h->ntotal / std::max(1, nlist);
-    int64_t owned = nlist;
-    if (shard && !h->h_list_mask.empty()) {
-        int64_t tot = 0;
-        owned = 0;
-        for (int l = 0; l < nlist; l++)
-            if (h->h_list_len[l] > 0 && h->h_list_mask[l]) {
-                owned++;
-                tot += h->h_list_len[l];
-            }
-        mean_len = owned ? (double)tot / (double)owned : 0.0;
-    }
-    int G0 = (mean_len <= 700.0 && P <= 64) ? 8 : 4;
-    // (with the byte-table filter pass a consumer probe costs a third of a producer's: five probes bound nearly as well as
-    //  eight -- C3: scan 729 us at 8, 691 at 6, 676 at 5, 671 at 4 but with queries whose slices overflow; GAMMA_HIP_SCAN_G to sweep)
-    static const bool no_c8 = getenv("GAMMA_HIP_NO_C8") != nullptr;
-    // (recall_num up to 512 since round 6 -- with the wave-per-query selection of eight sorted runs, select.hip: C3 at
-    //  recall_num 300 3.00 -> 2.07 ms per 16384 queries (scan 0.475 -> 0.675 of the roofline, select 910 -> 277 us), the C4 shape
-    //  at 8 M 5.19 -> 3.96 ms per 8192; the candidate stages (1536 / 768 slots) overflow into the unfiltered path as ever)
-    constexpr int cf_maxr = 512;
-    const bool c8_shape = !pq4 && !no_c8 && l2 && M == 16 && R <= cf_maxr && h->d_sums && h->d_t2max;
-    if (G0 == 8 && c8_shape && P > 8) G0 = 5;
-    int64_t t2_bytes = (int64_t)nlist * M * h->ksub * sizeof(float);
-    const bool compacted = shard && pre_dis && pre_probe;
-    if (two) {
-        // the producers take the query's nearest G1 owned probes only: everything else waits for the GLOBAL bound
-        G0 = std::max(1, std::min(bx->G1, P));
-        t2_bytes = owned * M * 256 * (int64_t)sizeof(float);
-    } else if (compacted && h->scan_bound && R <= 256) {
-        if (h->h_list_mask.empty()) {
-            owned = 0;
-            for (int l = 0; l < nlist; l++) owned += h->h_list_len[l] > 0;
-        }
-        t2_bytes = owned * M * 256 * (int64_t)sizeof(float);
-        const double exp_probes = (double)P * (double)owned / std::max(1, nlist);
-        const double exp_cand = exp_probes * mean_len;
-        // (not beyond that: one workgroup walking 50 k - 200 k codes of a query is the long pole of the launch -- full-size
-        //  C4 emulated, profiles/r04_scaling_emul.txt: W = 2 25.4 ms per step with 4 or 8 probes per workgroup, 27.9 with
-        //  16, 31.4 with 32 or 64; W = 4 27.0 / 27.1 / 30.1 / 30.3 / 30.2)
-        if (exp_cand <= 16384.0) {
-            G0 = 1;
-            while (G0 < P) G0 <<= 1;
-        }
-    }
-    const int G = gh::scan_group_size(nq, P, G0), PGN = (P + G - 1) / G;
+    // the plan, in two halves around the feedback's answer
+    const gh::ScanSwitches& sw = gh::ScanSwitches::get();
+    const gh::ScanShape sh = scan_shape(h, p, fc, nq, R, shard, compacted, bx);
+    gh::ScanPlan pl = gh::scan_plan_groups(sh, sw);
+    bool bounded = pl.bound_eligible;
+    if (bounded)
+        GH_CHECK(h, h->bound_fb.begin(s, gh::BoundFeedbackState::signature(P, R, l2, fc.any_clause, shard), !sw.no_bound_feedback, &bounded));
+    gh::scan_plan_passes(pl, sh, sw, bounded);
+    const int G = pl.G, PGN = pl.PGN, PGM = pl.PGM, nsl = pl.nsl, cap = pl.cap;
+    const int64_t q_stride = pl.q_stride;
     // exact ties (ties.hip): queries whose top-R cut goes through a group of equal ADC distances are marked here
     // and redone by the replay at the end of stage B
     h->tie = H::TieCtx();
@@ -386,145 +478,24 @@ int ivfpq_stage_a(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int
     h->tie.on = tie_on(p);
     h->shard_cut_nq = (shard && h->tie.on) ? nq : 0;
     h->shard_cut_chunked = false;
-    // Threshold pre-filter: scan the nearest probe group first, bound each query's R-th best
-    // distance from it, and let the scan of the remaining groups keep a short survivor list per
-    // query; the exact top-R then comes from a few hundred survivors instead of ~10^4 candidates
-    // (select.hip).  Queries without a usable bound fall back to the unfiltered selection.
-    // (sharded without a supplied assignment: probe groups are sparse, nothing to bound from)
-    // small batches: one probe per workgroup, a single list rarely holds R candidates, and the
-    // unfiltered selection is latency-bound anyway
-    // (one group per query -- few probes, or a shard -- is fine: the producer bounds and compacts its own candidates)
-    // (recall_num up to 1024 since round 5: slices of 2048 items and k_select_final_wg beyond 256 -- the configurations that need
-    //  a long short-list, full-size C5 at ~1000, keep the pre-filter)
-    constexpr int scan_gmin = 4, bound_maxr = 1024;
-    bool bounded = !pq4 && (!shard || compacted) && h->scan_bound && R <= bound_maxr && P <= 128 && G >= (two ? 1 : scan_gmin);
-    if (bounded) {
-        // feedback (gamma_hip_internal.h, bound_*): the counts of some recent call are in the pinned words
-        static const bool no_fb = getenv("GAMMA_HIP_NO_BOUND_FEEDBACK") != nullptr;
-        // (what was learnt holds for one kind of call: other cuts or a filter bound differently -- start over, with
-        //  counters of its own: the two slots alternate, so counts of the previous kind still on their way land elsewhere)
-        const uint64_t sig = ((uint64_t)P << 40) ^ ((uint64_t)R << 20) ^ ((uint64_t)(l2 ? 1 : 0) << 1) ^ (fc.any_clause ? 1u : 0u) ^
-                             ((uint64_t)(shard ? 1 : 0) << 2) ^ (1ull << 63);
-        if (sig != h->bound_sig) {
-            h->bound_sig = sig;
-            h->bound_epoch++;
-            h->bound_off_calls = 0;
-            h->bound_calls = 0;
-            h->bound_seen[0] = h->bound_seen[1] = 0;
-            const int slot = h->bound_epoch & 1;
-            if (h->bound_copy_pending) {   // a copy of the previous kind's counts still on its way: it lands before the words are reused
-                (void)hipEventSynchronize(h->bound_copy_ev);
-                h->bound_copy_pending = false;
-            }
-            h->pin_bound_stat[2 * slot] = h->pin_bound_stat[2 * slot + 1] = 0;
-            GH_CHECK(h, hipMemsetAsync(h->d_bound_stat + 2 * slot, 0, 2 * sizeof(unsigned long long), s));
-        }
-        const int slot = h->bound_epoch & 1;
-        if (no_fb || h->bound_feedback_off) {
-        } else if (h->bound_off_calls > 0) {
-            if (--h->bound_off_calls > 0) bounded = false;   // (0: this call re-probes)
-        } else {
-            // (the pair is consulted only once the copy that writes it has completed -- bound_copy_ev -- so the two
-            //  words belong to one state of the counters; a sample that runs backwards, e.g. a late copy landing on words
-            //  zeroed for a new kind of call, is ignored, and the fell-through count can never exceed the queries)
-            const bool landed = !h->bound_copy_pending || hipEventQuery(h->bound_copy_ev) == hipSuccess;
-            if (landed) h->bound_copy_pending = false;
-            else (void)hipGetLastError();
-            const unsigned long long u = h->pin_bound_stat[2 * slot], n = h->pin_bound_stat[2 * slot + 1];
-            const unsigned long long dn = n - h->bound_seen[1];
-            const unsigned long long du = std::min(u >= h->bound_seen[0] ? u - h->bound_seen[0] : 0ull, dn);
-            if (landed && n >= h->bound_seen[1] && u >= h->bound_seen[0] && dn >= 2048) {
-                h->bound_seen[0] = u;
-                h->bound_seen[1] = n;
-                if (2 * du > dn) {   // more than half of the recent queries went to the unfiltered selection anyway
-                    h->bound_off_calls = 256;
-                    h->bound_backoffs++;
-                    bounded = false;
-                }
-            }
-        }
-    }
-    // L2 table mode 0 (no precomputed table, H::table_mode): per-list tables from the residual (scan.hip RES) -- the plain and
-    // the bounded loop; no query table, none of the passes built on T2 sums (d_sums is null: cf / c8 / q8 are off by their own gates)
-    const bool res = !pq4 && l2 && h->table_mode == 0;
-    static const bool no_fused_ip = getenv("GAMMA_HIP_NO_FUSED_IP") != nullptr;
-    const bool fuse_ip = !pq4 && bounded && !res && PGN == 1 && (M == 16 || M == 32) && !no_fused_ip;
     // the bounded scan's per-call state (repair list, ready words, survivor counts) is sized here, before the pair offsets,
     // whose kernel clears it together with the tie flags -- one launch instead of four fills in front of the scan
-    // (byte-table filter pass: a first group of a few probes bounds loosely for some queries -- slices of 2048 keep them out of the
-    //  unfiltered path; never beyond 2048: the selection and the tie replay hold one slice in LDS)
-    const int cap = gh::scan_slice_cap(R);
-    bool cf_ok = false, q8_ok = false;
-    int PGM = PGN, nsl = PGN, cf_span = 0;
     unsigned long long* ready = nullptr;
-    size_t fl_off = 0;   // the fall-through list's place in w_scnt (bounded)
+    int* fl_count = nullptr;   // the fall-through list: count | list
     if (bounded) {
-        // filter pass of the consumers (kernels.hip, CF): needs the sums beside the arena the scan reads -- not the
-        // shadow arena of a call running over lists compacted under its filter.  With it ONE consumer workgroup per
-        // query takes every probe behind the producer's: two groups, two slices per query.
-        static const bool no_cf = getenv("GAMMA_HIP_NO_SCAN_CF") != nullptr;
-        // (short lists only: with thousands of codes per list the per-pair table costs next to nothing, while ONE consumer
-        //  workgroup per query overruns its candidate stage and sends the query to the unfiltered path -- full-size C4, 6100
-        //  codes per list: 38.6 ms per 8192 queries with the filter pass, 27.6 without)
-        // Short lists only (mean <= 2000 codes).  With thousands of codes per list the per-pair table costs next to
-        // nothing and the pass loses: full-size C4 (6100 codes per list, 8192 queries) 27.7 ms without it; 38.6 ms with ONE
-        // consumer workgroup per query (it stages more candidates than its 768 slots hold and the query goes to the
-        // unfiltered path); 32.5 ms with the probes behind the producer's cut into consumer groups of ~48 k codes, each
-        // with its own stage and slice (round 4, profiles/r04_scale_runs.txt) -- the margin candidates' exact recompute
-        // and the second look at the codes cost more than the table build they save.  The split (cf_span) stays for the
-        // lists in between: a consumer group takes at most ~64 k codes.
-        constexpr double cf_maxlen = 2000.0;
-        static const double cf_codes = getenv("GAMMA_HIP_SCAN_CF_CODES") ? atof(getenv("GAMMA_HIP_SCAN_CF_CODES")) : 65536.0;
-        // (and short-lists only: the pass stages SCAN_CF_CAP = 768 candidates per consumer workgroup)
-        cf_ok = !no_cf && R <= cf_maxr && (!h->prefiltered || h->cmp_has_sums) && PGN > 1 && mean_len <= cf_maxlen &&
-                gh::scan_cf_applies(l2, M, P, G, h->d_sums && h->d_t2max, false);
-        // list-major byte-table pass for the consumer probes (q8scan.hip, round 5): same conditions as the filter pass it
-        // replaces, one validity predicate for the whole call, not a shard (GAMMA_HIP_NO_Q8: the query-major pass, for A/B)
-        static const bool no_q8 = getenv("GAMMA_HIP_NO_Q8") != nullptr;
-        // (long lists: a tile's table staging and its chain of dependent loads are amortised over thousands of codes; at C3's
-        //  244 codes per list a tile is one step of 64 codes per wave and the pass is latency-bound -- measured slower than the
-        //  query-major pass there, profiles/r05_q8_*.txt -- so short lists keep the query-major filter pass)
-        // (the switch, measured after the byte image went into the query-major pass: nlist 4096 / M 16 / nprobe 32 -- 732 codes per
-        //  list 2.81 ms query-major, 2.84 list-major; 976: 3.31 / 3.20; 1465: 4.49 / 3.57 -- nlist 16384 / M 32 / nprobe 64 -- 732: 4.35 /
-        //  4.38; 976: 5.36 / 4.87)
-        static const double q8_minlen = getenv("GAMMA_HIP_Q8_MINLEN") ? atof(getenv("GAMMA_HIP_Q8_MINLEN")) : 800.0;
-        const int64_t q_stride0 = (std::max<int64_t>(1, (int64_t)P * std::max(1, h->max_list_len)) + 3) & ~(int64_t)3;
-        // (a list shard with a supplied, compacted assignment runs it too: pairs of lists of other shards are simply not placed)
-        q8_ok = !no_q8 && !no_cf && R <= 1024 && (!shard || compacted) &&
-                // (shadow lists of the standing deletes are as long as the lists: the pass stays on over them -- C4 shape at 20 M with
-                //  5 % deleted: 6.2 ms per 8192 queries without it, 4.5 unfiltered; lists cut down under a request's own clause
-                //  are as short as the clause makes them: the query-major pass)
-                (!h->prefiltered || (h->cmp_has_sums && !h->cmp_by_clause)) && !fc.d_qf && PGN > 1 &&
-                gh::scan_cf_applies(l2, M, P, G, h->d_sums && h->d_t2max, false) && gh::q8_supported(M, P, G, q_stride0) && mean_len >= q8_minlen && nlist <= 16384;
-        if (q8_ok) cf_ok = false;
-        if (q8_ok) {
-            PGM = 1;     // the main launch: producers only
-            nsl = PGN;   // slice 0: the producer's, slices 1 ..: the consumer probe groups' (k_q8_exact)
-        } else if (cf_ok) {
-            const int rest = P - G;
-            int nc = (int)std::ceil(rest * mean_len / cf_codes);
-            nc = std::max(1, std::min(nc, std::max(1, PGN - 1)));
-            cf_span = nc > 1 ? (rest + nc - 1) / nc : 0;
-            PGM = 1 + (nc > 1 ? (rest + cf_span - 1) / cf_span : 1);
-        } else {
-            PGM = PGN;   // probe groups of the main launch
-        }
-        if (!q8_ok) nsl = PGM;   // one survivor slice per probe group (slice 0: the producer's own)
-        // rq | ready[nq] | gcnt[nq][nsl] | fl   (rq: count + list of the queries that need the repair launch, 8-byte aligned;
-        //  fl: count + list of the queries k_select_final left to the unfiltered selection, flag = 1)
-        const size_t rq_bytes = (((size_t)nq + 1) * sizeof(int) + 7) & ~(size_t)7;
-        fl_off = rq_bytes + (size_t)nq * (sizeof(unsigned long long) + (size_t)nsl * sizeof(int));
-        GH_CHECK(h, h->w_scnt.ensure(fl_off + ((size_t)nq + 1) * sizeof(int)));
+        GH_CHECK(h, h->w_scnt.ensure(pl.scnt_bytes));
         GH_CHECK(h, h->w_sflag.ensure((size_t)nq));
         GH_CHECK(h, h->w_surv.ensure((size_t)nq * nsl * cap * sizeof(unsigned long long)));
-        ready = reinterpret_cast<unsigned long long*>(h->w_scnt.as<char>() + rq_bytes);
+        ready = reinterpret_cast<unsigned long long*>(h->w_scnt.as<char>() + pl.ready_off);
+        fl_count = reinterpret_cast<int*>(h->w_scnt.as<char>() + pl.fl_off);
     }
+    const int* qperm = nullptr;
     {
         StageScope t(h, GAMMA_HIP_STAGE_TABLES);
         if (pq4) {
             GH_CHECK(h, h->w_st2.ensure((size_t)nq * M * gh::kPq4Ksub * sizeof(float)));
             gh::launch_pq4_ip_table(s, d_x, nq, d, M, h->d_pqc, h->w_st2.as<float>());
-        } else if (!fuse_ip && !res) {
+        } else if (!pl.fuse_ip && !pl.res) {
             GH_CHECK(h, h->w_st2.ensure((size_t)nq * M * 256 * sizeof(float)));
             gh::launch_pq_ip_table(s, d_x, nq, d, M, h->d_pqc, h->w_st2.as<float>());
         }
@@ -537,11 +508,8 @@ int ivfpq_stage_a(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int
             GH_CHECK(h, h->w_tlist.ensure(((size_t)nq + 1) * sizeof(int)));   // count | list[nq]
         }
         gh::PairZero pz;
-        // enough queries that L2 capacity matters: run them in spatial order (kernels.hip)
-        // (not when the T2 rows of the lists scanned here fit the L2s anyway: a shard of a small index)
-        const bool order = h->sort_queries && h->d_list_rank && nq >= 256 && t2_bytes > ((int64_t)8 << 20);
         int* qo_bins = nullptr;
-        if (order) {
+        if (pl.order) {   // the queries run in spatial order (kernels.hip)
             GH_CHECK(h, h->w_qperm.ensure((size_t)2 * nq * sizeof(int)));   // qperm | qkey
             if (gh::query_order_grid(nq)) {
                 if (!h->w_qbins.p) {   // histogram | cursors; every call leaves the histogram zero
@@ -567,24 +535,19 @@ int ivfpq_stage_a(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int
 #endif
             pz.words = h->scan_dbg_now == 2 ? nullptr : ready;
             pz.count_b = h->w_scnt.as<int>();
-            pz.count_c = reinterpret_cast<int*>(h->w_scnt.as<char>() + fl_off);
+            pz.count_c = fl_count;
         }
         gh::launch_pair_offsets(s, h->w_probe.as<int>(), nq, P, h->d_list_len, h->d_list_mask, nlist,
                                 h->w_pair_off.as<int>(), h->w_qtotal.as<int>(),
                                 h->profile == 1 ? h->d_scan_codes : nullptr, h->d_list_off,
                                 h->w_pair_base.as<int64_t>(), &pz);
-        if (order) {
+        if (pl.order) {
             gh::launch_query_order(s, h->w_probe.as<int>(), nq, P, h->d_list_rank, nlist,
                                    h->w_qperm.as<int>() + nq, h->w_qperm.as<int>(), qo_bins, qo_bins != nullptr);
             qperm = h->w_qperm.as<int>();
         }
         h->last_qperm = qperm;   // stage B runs the re-rank in the same order
     }
-    // per-query slab of the distance buffer; multiple of 4 floats so rows are 16-byte aligned
-    int64_t q_stride = (std::max<int64_t>(1, (int64_t)P * std::max(1, h->max_list_len)) + 3) & ~(int64_t)3;
-    // (the longest candidate row of THIS batch, measured on its assignment: list shards, and whole-index calls whose general
-    //  stride -- nprobe x the longest list -- would cut the batch into chunks)
-    if (h->q_stride_cap > 0) q_stride = std::min(q_stride, h->q_stride_cap);
     GH_CHECK(h, h->w_dist.ensure((size_t)nq * q_stride * sizeof(float)));
     // dis0 of every (query, probe) pair: the coarse distance (L2) or <x_q, centroid> (inner product)
     const float* dis0 = h->w_coarse_dis.as<float>();
@@ -594,23 +557,30 @@ int ivfpq_stage_a(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int
         gh::launch_pair_ip(s, d_x, h->d_cc, h->w_probe.as<int>(), nq, P, d, nlist, h->w_pair_ip.as<float>());
         dis0 = h->w_pair_ip.as<float>();
     }
-    auto scan = [&](int gsz, int pg_lo, int pg_cnt, const gh::ScanBound* bound, bool count) {
-        StageScope t(h, GAMMA_HIP_STAGE_SCAN, count);
-        if (pq4) {   // (bounded is false: gsz = G, every probe group, no bound)
-            gh::launch_ivfpq4_scan_pair(s, l2, nq, M, P, h->w_probe.as<int>(), dis0, h->w_st2.as<float>(), h->d_T2, h->d_list_off,
-                                        h->d_list_len, h->d_list_mask, nlist, h->d_codes, h->d_ids, h->w_pair_off.as<int>(),
-                                        q_stride, h->w_dist.as<float>(), fc.d_tab, fc.d_qf, need_ids, qperm, gsz, pg_cnt);
-            return;
-        }
-        gh::launch_ivfpq_scan_pair(s, l2, d_x, nq, d, M, P, h->w_probe.as<int>(),
-                                   dis0, h->d_cc, h->scan_st2(l2), h->d_T2,
-                                   h->d_list_off, h->d_list_len, h->d_list_mask, nlist, h->d_codes,
-                                   h->d_ids, h->w_pair_off.as<int>(), q_stride, h->w_dist.as<float>(),
-                                   fc.d_tab, fc.d_qf, need_ids, qperm, gsz, pg_lo, pg_cnt, shard ? 1 : 0, bound,
-                                   fuse_ip ? h->d_pqc : nullptr);
+    // one scan launch: probe groups [pg_lo, pg_lo + pg_cnt) of every query, G probes each
+    gh::ScanArgs sa = scan_args(h, l2, fc, nq, P, d_x, dis0, q_stride, pl.need_ids);
+    sa.G = G;
+    sa.qperm = qperm;
+    auto scan = [&](int pg_lo, int pg_cnt, int sparse, const gh::ScanBound* bound, const float* pqc_fused) {
+        gh::ScanArgs a = sa;
+        a.pg_lo = pg_lo;
+        a.pg_cnt = pg_cnt;
+        a.sparse = sparse;
+        a.bound = bound;
+        a.pqc_fused = pqc_fused;
+        gh::launch_ivfpq_scan_pair(s, a);
     };
+    const float* pqc = pl.fuse_ip ? h->d_pqc : nullptr;
     if (!bounded) {
-        scan(G, 0, PGN, nullptr, true);
+        {
+            StageScope t(h, GAMMA_HIP_STAGE_SCAN, true);
+            if (pq4)
+                gh::launch_ivfpq4_scan_pair(s, l2, nq, M, P, h->w_probe.as<int>(), dis0, h->w_st2.as<float>(), h->d_T2, h->d_list_off,
+                                            h->d_list_len, h->d_list_mask, nlist, h->d_codes, h->d_ids, h->w_pair_off.as<int>(),
+                                            q_stride, h->w_dist.as<float>(), fc.d_tab, fc.d_qf, pl.need_ids, qperm, G, PGN);
+            else
+                scan(0, PGN, shard ? 1 : 0, nullptr, pqc);
+        }
         StageScope t(h, GAMMA_HIP_STAGE_SELECT);
         gh::launch_select_topk(s, l2, h->w_dist.as<float>(), q_stride, h->w_qtotal.as<int>(), 0,
                                (int)std::min<int64_t>(q_stride, 1 << 30), nq, R,
@@ -625,7 +595,7 @@ int ivfpq_stage_a(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int
         gh::ScanBound sb = {};   // (every field starts at 0: part, dbg_part, c8 ...)
         sb.ready = ready;
         sb.surv = h->w_surv.as<unsigned long long>();
-        sb.gcnt = reinterpret_cast<int*>(ready + nq);
+        sb.gcnt = reinterpret_cast<int*>(h->w_scnt.as<char>() + pl.gcnt_off);
         sb.K = R;
         sb.cnt_stride = nsl;
         // consumer groups with a bound keep only their survivors; what the unfiltered fallback and the tie replay of a
@@ -633,15 +603,14 @@ int ivfpq_stage_a(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int
         sb.store_all = 0;
         sb.rq_count = h->w_scnt.as<int>();
         sb.rq_list = h->w_scnt.as<int>() + 1;
-        sb.sums = cf_ok ? h->d_sums : nullptr;
-        sb.t2max = cf_ok ? h->d_t2max : nullptr;
+        sb.sums = pl.cf_ok ? h->d_sums : nullptr;
+        sb.t2max = pl.cf_ok ? h->d_t2max : nullptr;
         sb.t2max_all = h->t2max_all;
         sb.pair_base = h->w_pair_base.as<int64_t>();
-        sb.cf_span = cf_ok ? cf_span : 0;
-        sb.timeouts = h->d_bound_stat + 4;
+        sb.cf_span = pl.cf_span;
+        sb.timeouts = h->bound_fb.d_timeouts();
         sb.slice_cap = cap;
-        // the consumers' filter pass on a byte image of the query's table (scan.hip, "byte table")
-        sb.c8 = (cf_ok && c8_shape && (cf_span > 0 ? cf_span : P - G) <= 64) ? 1 : 0;
+        sb.c8 = pl.c8;
         sb.dbg_part = h->scan_dbg_now;
         // two-phase shard search: the producers' bounds out, the reduced (global) bounds back into the ready words
         auto exchange = [&]() -> int {
@@ -650,104 +619,51 @@ int ivfpq_stage_a(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int
             gh::launch_bound_import(s, l2, bx->d_bound, nq, sb.ready);
             return GAMMA_HIP_OK;
         };
-        if (!q8_ok && two) {
+        if (!pl.q8_ok && two) {
             {   // phase 1: the producers alone (one group per query; the plain bounded kernel)
                 StageScope t(h, GAMMA_HIP_STAGE_SCAN, true);
-                gh::launch_ivfpq_scan_pair(s, l2, d_x, nq, d, M, P, h->w_probe.as<int>(), dis0, h->d_cc, h->scan_st2(l2), h->d_T2,
-                                           h->d_list_off, h->d_list_len, h->d_list_mask, nlist, h->d_codes, h->d_ids,
-                                           h->w_pair_off.as<int>(), q_stride, h->w_dist.as<float>(), fc.d_tab, fc.d_qf, need_ids, qperm, G, 0,
-                                           1, 1, &sb, fuse_ip ? h->d_pqc : nullptr);
+                scan(0, 1, 1, &sb, pqc);
             }
             GH_TRY(exchange());
             if (PGM > 1) {   // phase 2: the consumers alone, against the global bounds
+                StageScope t(h, GAMMA_HIP_STAGE_SCAN, false);
                 sb.part = 2;
-                scan(G, 0, PGM, &sb, false);
+                scan(0, PGM, shard ? 1 : 0, &sb, pqc);
                 sb.part = 0;
             }
-        } else if (!q8_ok) {
-            scan(G, 0, PGM, &sb, true);
+        } else if (!pl.q8_ok) {
+            StageScope t(h, GAMMA_HIP_STAGE_SCAN, true);
+            scan(0, PGM, shard ? 1 : 0, &sb, pqc);
         } else {
             // producers (the first G probes: exact, they publish the bounds), then the other probes list-major over byte
             // tables -- all of it one "scan launch" for the stage clock and the roofline figure
             StageScope t(h, GAMMA_HIP_STAGE_SCAN, true);
-            gh::launch_ivfpq_scan_pair(s, l2, d_x, nq, d, M, P, h->w_probe.as<int>(), dis0, h->d_cc, h->scan_st2(l2), h->d_T2,
-                                       h->d_list_off, h->d_list_len, h->d_list_mask, nlist, h->d_codes, h->d_ids,
-                                       h->w_pair_off.as<int>(), q_stride, h->w_dist.as<float>(), fc.d_tab, fc.d_qf, need_ids, qperm, G, 0,
-                                       1, 0, &sb, nullptr);
+            scan(0, 1, 0, &sb, nullptr);
             if (two) GH_TRY(exchange());   // (the list-major pass below reads the ready words: now the global bounds)
-            GH_CHECK(h, h->w_q8.ensure((size_t)nq * M * 256));
-            GH_CHECK(h, h->w_q8meta.ensure((size_t)nq * 4 * sizeof(float)));
-            GH_CHECK(h, h->w_q8cand.ensure((size_t)nq * gh::q8_cand_cap(nq) * sizeof(uint32_t)));
-            GH_CHECK(h, h->w_q8int.ensure(gh::q8_int_words(nq, P, G, nlist) * sizeof(int)));
-            gh::Q8Args qa;
-            qa.nq = nq; qa.P = P; qa.G = G; qa.M = M; qa.nlist = nlist;
-            qa.mean_len = mean_len;
-            qa.probe_list = h->w_probe.as<int>();
-            qa.coarse_dis = dis0;
-            qa.st2 = h->w_st2.as<float>();
-            static const bool no_demand = getenv("GAMMA_HIP_NO_Q8_DEMAND") != nullptr;
-            if (shard && !no_demand) qa.xd = d_x;
-            qa.pqc = h->d_pqc;
-            qa.d = d;
-            qa.T2 = h->d_T2;
-            qa.t2max = h->d_t2max;
-            qa.sums = h->d_sums;
-            qa.codes = h->d_codes;
-            qa.ids = h->d_ids;
-            qa.list_off = h->d_list_off;
-            qa.list_len = h->d_list_len;
-            qa.list_mask = h->d_list_mask;
-            qa.pair_off = h->w_pair_off.as<int>();
-            qa.ready = sb.ready;
-            qa.ftab = fc.d_tab;
-            qa.need_ids = need_ids;
-            qa.surv = sb.surv;
-            qa.gcnt = sb.gcnt;
-            qa.cnt_stride = nsl;
-            qa.slice_cap = cap;
-            qa.rq_list = sb.rq_list;
-            qa.rq_count = sb.rq_count;
-            qa.q8 = h->w_q8.as<uint8_t>();
-            qa.meta = reinterpret_cast<float4*>(h->w_q8meta.p);
-            qa.cand = h->w_q8cand.as<uint32_t>();
-            qa.iwork = h->w_q8int.as<int>();
-            gh::launch_q8_consumers(s, qa);
+            GH_TRY(scan_list_major(h, pl, sh, sb, fc, d_x, dis0));
         }
-        // GAMMA_HIP_BOUND_DBG=1: the bounded scan's statistics of the 9th .. 14th call; =shard: of list-shard calls only
-        static const bool dbg_any = getenv("GAMMA_HIP_BOUND_DBG") != nullptr;
-        static const bool dbg_shard = dbg_any && getenv("GAMMA_HIP_BOUND_DBG")[0] == 's';
-        const bool dbg = dbg_any && (!dbg_shard || shard);
-        static const int dbg_from = 8;
-        static int shown = 0;
         // the queries that fall through the bound (a handful of a batch: ~5 of 16384 at C3): the launch behind k_select_final
         // and the repair scan walks its list of them, as the repair launch walks rq_list
-        int* fl_count = reinterpret_cast<int*>(h->w_scnt.as<char>() + fl_off);
         const gh::RowList fell(fl_count + 1, fl_count);
         StageScope t(h, GAMMA_HIP_STAGE_SELECT);
         gh::launch_select_final(s, l2, sb.surv, sb.gcnt, nsl, cap, sb.ready, h->w_pair_off.as<int>(), P, nq, R,
                                 h->w_pair_base.as<int64_t>(), h->d_ids,
                                 h->w_sflag.as<uint8_t>(), out_dis,
                                 h->w_cand_pos.as<int>(), out_ids, h->tie.on ? h->w_tcut.as<uint8_t>() : nullptr,
-                                h->d_tie_stats, sb.rq_list, sb.rq_count, h->d_bound_stat + 2 * (h->bound_epoch & 1),
+                                h->d_tie_stats, sb.rq_list, sb.rq_count, h->bound_fb.d_slot(),
                                 fl_count + 1, fl_count);
-        // the counts as of this call, for a later call's decision (16 bytes; ~5 us on the call's critical path, so: the
-        // first calls of a kind, then every 16th)
-        if ((h->bound_calls < 4 || (h->bound_calls & 15) == 0) && !h->bound_copy_pending) {
-            GH_CHECK(h, hipMemcpyAsync(h->pin_bound_stat + 2 * (h->bound_epoch & 1), h->d_bound_stat + 2 * (h->bound_epoch & 1),
-                                       2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-            if (!h->bound_copy_ev) GH_CHECK(h, hipEventCreateWithFlags(&h->bound_copy_ev, hipEventDisableTiming));
-            GH_CHECK(h, hipEventRecord(h->bound_copy_ev, s));
-            h->bound_copy_pending = true;
-        }
-        h->bound_calls++;
+        GH_CHECK(h, h->bound_fb.end(s));
         if (PGN > 1 && !sb.store_all) {
             // queries the slices could not answer: their consumer groups are scored again, distances stored
             StageScope t2(h, GAMMA_HIP_STAGE_SCAN, false);
-            gh::launch_ivfpq_scan_pair(s, l2, d_x, nq, d, M, P, h->w_probe.as<int>(), dis0, h->d_cc,
-                                       h->scan_st2(l2), h->d_T2, h->d_list_off, h->d_list_len, h->d_list_mask,
-                                       nlist, h->d_codes, h->d_ids, h->w_pair_off.as<int>(), q_stride,
-                                       h->w_dist.as<float>(), fc.d_tab, fc.d_qf, need_ids, nullptr, G, 1,
-                                       PGN - 1, shard ? 1 : 0, nullptr, nullptr, sb.rq_list, sb.rq_count);
+            gh::ScanArgs a = sa;
+            a.qperm = nullptr;
+            a.pg_lo = 1;
+            a.pg_cnt = PGN - 1;
+            a.sparse = shard ? 1 : 0;
+            a.rq_list = sb.rq_list;
+            a.rq_count = sb.rq_count;
+            gh::launch_ivfpq_scan_pair(s, a);
         }
         // (one launch: a listed row's workgroup selects it, flags a tied cut and looks its ids up)
         gh::RowTail tail;
@@ -766,28 +682,7 @@ int ivfpq_stage_a(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int
             h->tie.nsl = nsl;
             h->tie.cap = cap;
         }
-        if (dbg && shown++ >= dbg_from && shown <= dbg_from + 5) {
-            std::vector<uint8_t> hf(nq);
-            std::vector<int> hc((size_t)nq * nsl);
-            (void)hipStreamSynchronize(s);
-            (void)hipMemcpy(hf.data(), h->w_sflag.p, nq, hipMemcpyDeviceToHost);
-            (void)hipMemcpy(hc.data(), sb.gcnt, hc.size() * sizeof(int), hipMemcpyDeviceToHost);
-            std::vector<unsigned long long> hr(nq);
-            (void)hipMemcpy(hr.data(), sb.ready, (size_t)nq * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-            int64_t nf = 0, tot = 0, mx = 0, nobound = 0;
-            for (int i = 0; i < nq; i++) {
-                nf += hf[i];
-                nobound += (hr[i] >> 32) != 1ull;
-            }
-            for (size_t i = 0; i < hc.size(); i++) {
-                tot += hc[i];
-                mx = std::max<int64_t>(mx, hc[i]);
-            }
-            fprintf(stderr, "scan bound: %lld of %d queries unfiltered (%lld without a bound), survivors per query mean %.1f, "
-                    "per slice max %lld; G %d, %d groups, %d slices, q_stride %lld; consumers that gave up waiting so far %llu\n",
-                    (long long)nf, nq, (long long)nobound, (double)tot / nq, (long long)mx, G, PGN, nsl, (long long)q_stride,
-                    [&] { unsigned long long t = 0; (void)hipMemcpy(&t, h->d_bound_stat + 4, sizeof(t), hipMemcpyDeviceToHost); return t; }());
-        }
+        scan_bound_dump(h, shard, nq, sb, pl);
     }
     h->tie.G = G;
     h->tie.q_stride = q_stride;
@@ -979,12 +874,14 @@ int ivfpq_small(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int n
                                    tie_on(p) ? 1 : 0, h->d_tie_stats);
     h->scan_pairs += (int64_t)nq * P;
     const int need_ids = (!h->prefiltered && (fc.any_clause || (h->d_bitmap && h->bitmap_any) || h->n_moved > 0)) ? 1 : 0;
-    gh::launch_ivfpq_scan_pair(s, l2, d_x, nq, d, M, P, h->w_probe.as<int>(),
-                               l2 ? h->w_coarse_dis.as<float>() : h->w_pair_ip.as<float>(), h->d_cc,
-                               h->scan_st2(l2), h->d_T2, h->d_list_off, h->d_list_len, h->d_list_mask, nlist,
-                               h->d_codes, h->d_ids, h->w_pair_off.as<int>(), q_stride, h->w_dist.as<float>(), fc.d_tab,
-                               fc.d_qf, need_ids, nullptr, 1, 0, P, 0, nullptr, nullptr, reinterpret_cast<const int*>(d_units), d_nunits,
-                               chunk_len, max_units);
+    // one probe per workgroup, every probe; with a unit list: the work list of list chunks
+    gh::ScanArgs sa = scan_args(h, l2, fc, nq, P, d_x, l2 ? h->w_coarse_dis.as<float>() : h->w_pair_ip.as<float>(), q_stride, need_ids);
+    sa.pg_cnt = P;
+    sa.rq_list = reinterpret_cast<const int*>(d_units);
+    sa.rq_count = d_nunits;
+    sa.chunk_len = chunk_len;
+    sa.max_units = max_units;
+    gh::launch_ivfpq_scan_pair(s, sa);
     const float neutral = neutral_of(l2);
     // long candidate rows (expected nprobe x 1.5 mean list lengths beyond what one workgroup keeps in registers): a first
     // selection over slices of the row by several workgroups per query, then the tail among their survivors

@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "scan_plan.h"
+
 namespace gh {
 
 // A launcher that is handed a shape its callers are supposed to rule out does not abort the process (a database server's): it
@@ -255,26 +257,42 @@ struct Q8Args {
     uint32_t* cand;                   // workspace [nq][q8_cand_cap(nq)]
     int* iwork;                       // workspace q8_int_words(..) ints
 };
-bool q8_supported(int M, int P, int G, int64_t q_stride);
 int q8_cand_cap(int nq);
 size_t q8_int_words(int nq, int P, int G, int nlist);
 void launch_q8_consumers(hipStream_t s, const Q8Args& a);
-int scan_slice_cap(int K);   // 1024 up to recall_num 256, 2048 up to 1024
-// true when launch_ivfpq_scan_pair would run the filter pass (CF) for a bounded scan with these arguments; the caller
-// then launches TWO groups per query -- the producer's G probes and one consumer group with all the others
-bool scan_cf_applies(bool l2, int M, int P, int G, bool have_sums, bool store_all);
-int scan_group_size(int nq, int P, int G0 = 8);   // G0: probes per workgroup to start from; shrinks through the powers of two below it
-void launch_ivfpq_scan_pair(hipStream_t s, bool l2, const float* x, int nq, int d, int M, int P,
-                            const int* probe_list, const float* coarse_dis, const float* cc,
-                            const float* st2, const float* T2, const int64_t* list_off,
-                            const int* list_len, const uint8_t* list_mask, int nlist,
-                            const uint8_t* codes, const int64_t* ids, const int* pair_off,
-                            int64_t q_stride, float* out, const FilterDesc* ftab /* device */, const int* qfil /* device, may be null */,
-                            int need_ids,
-                            const int* qperm, int G, int pg_lo, int pg_cnt, int sparse, const ScanBound* bound,
-                            const float* pqc_fused = nullptr,   // != nullptr: query table computed in the kernel
-                            const int* rq_list = nullptr, const int* rq_count = nullptr,   // repair launch (kernels.hip)
-                            int chunk_len = 0, int max_units = 0);   // > 0: rq_list is a work list of list chunks (kernels.hip)
+// (scan_slice_cap, scan_cf_applies, scan_group_size, q8_supported: scan_plan.h)
+// One launch of the list scan.  The first block is the same for every launch of a call (gamma_hip_search.cpp scan_args);
+// a call site sets what it means in the second.
+struct ScanArgs {
+    bool l2 = true;
+    const float* x = nullptr;
+    int nq = 0, d = 0, M = 0, P = 0;
+    const int* probe_list = nullptr;
+    const float* coarse_dis = nullptr;   // dis0 of every (query, probe) pair
+    const float* cc = nullptr;
+    const float* st2 = nullptr;
+    const float* T2 = nullptr;
+    const int64_t* list_off = nullptr;
+    const int* list_len = nullptr;
+    const uint8_t* list_mask = nullptr;
+    int nlist = 0;
+    const uint8_t* codes = nullptr;
+    const int64_t* ids = nullptr;
+    const int* pair_off = nullptr;
+    int64_t q_stride = 0;
+    float* out = nullptr;
+    const FilterDesc* ftab = nullptr;   // device
+    const int* qfil = nullptr;          // device, may be null
+    int need_ids = 0;
+    int G = 1;
+    const int* qperm = nullptr;
+    int pg_lo = 0, pg_cnt = 0, sparse = 0;
+    const ScanBound* bound = nullptr;
+    const float* pqc_fused = nullptr;                       // != nullptr: query table computed in the kernel
+    const int* rq_list = nullptr, *rq_count = nullptr;      // repair launch (scan.hip)
+    int chunk_len = 0, max_units = 0;                       // > 0: rq_list is a work list of list chunks (scan.hip)
+};
+void launch_ivfpq_scan_pair(hipStream_t s, const ScanArgs& a);
 int query_order_bins();
 bool query_order_grid(int nq);   // the batch is sorted over the whole grid (needs bins)
 // bins: 2 * query_order_bins() ints (histogram | cursors) for the grid-wide sort of large batches; the histogram half is

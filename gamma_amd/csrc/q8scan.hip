@@ -53,7 +53,7 @@ template <int MT> struct Q8Lut {
 // candidates staged per tile (all of its queries; more = the tile's queries take the unfiltered path): what the LDS beside
 // the table leaves at four (M = 16) / two (M = 32: long lists, hundreds of candidates from the nearest lists) workgroups per CU
 template <int MT> struct Q8Pool { static constexpr int N = MT <= 16 ? 640 : 3584; };
-constexpr int Q8_POS_BITS = 25;  // candidate = position in the query's segment | probe << 25
+// (Q8_POS_BITS, candidate = position in the query's segment | probe << 25: scan_plan.h)
 }  // namespace
 
 // candidates a query's list holds (beyond: the query takes the unfiltered path): Q8_CAND_MB of workspace spread over the
@@ -754,8 +754,6 @@ __global__ __launch_bounds__(256) void k_q8_exact(const float* __restrict__ st2,
     __syncthreads();
     for (int g = 1 + tid; g < ngroups; g += 256) gcnt[(int64_t)q * cnt_stride + g] = s_cnt[g];
 }
-
-bool q8_supported(int M, int P, int G, int64_t q_stride) { return (M == 16 || M == 32) && P <= 128 && G >= 1 && /* (the caller checks nlist <= 16384: the per-list counters live in LDS) */ (P + G - 1) / G <= 64 && q_stride < ((int64_t)1 << Q8_POS_BITS); }
 
 // workspace: ccnt nq (zeroed here) | hist Q8_NW x nlist | cnt nlist | off nlist+1 | tile_first nlist+1 | n_tiles 1 | pad |
 //            tile_list (int4) | recs (Q8Rec, 32 B)

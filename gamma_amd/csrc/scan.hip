@@ -43,8 +43,7 @@ __device__ unsigned long long g_scan_t[32];
 // ------------------------------------------------------------------------------------
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 constexpr int SCAN_STAGE = 256;                  // survivors staged in LDS per workgroup
-constexpr int SCAN_SLICE = 1024;                 // candidate slice of one workgroup (global) up to recall_num 256; a producer needs recall_num +
-                                                 // one histogram bin: 2048 beyond (ScanBound::slice_cap, scan_slice_cap)
+// (SCAN_SLICE, the candidate slice of one workgroup: scan_plan.h)
 constexpr int SCAN_BATCH = 64;                   // queries per XCD by which producers run ahead
 constexpr int SCAN_SPINS = 1 << 11;              // polls (s_sleep 16 each, ~2e6 cycles in all) a consumer waits for its query's bound
 
@@ -994,30 +993,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(112), amdgpu_wa
     scan_pair_body<true, MT, true, false, false, true, true>(x, nq, d, M, P, G, probe_list, coarse_dis, cc, st2, T2, list_off, list_len, list_mask, nlist, codes, ids, pair_off, q_stride, out, ftab, qfil, need_ids, sentinel, qperm, pg_lo, pg_cnt, sparse, sb, rq_list, rq_count, chunk_len);
 }
 
-int scan_slice_cap(int K) { return K <= 256 ? SCAN_SLICE : 2 * SCAN_SLICE; }
-bool scan_cf_applies(bool l2, int M, int P, int G, bool have_sums, bool store_all) {
-    return l2 && have_sums && !store_all && (M == 16 || M == 32) && P > G;
-}
-
-int scan_group_size(int nq, int P, int G0) {
-    // probes per workgroup: amortise the query table, but keep >= ~4096 workgroups in flight
-    const char* ge = getenv("GAMMA_HIP_SCAN_G");   // (read per call: tools sweep it inside one process)
-    const int g_env = ge ? atoi(ge) : 0;
-    int G = g_env > 0 ? g_env : G0;
-    // (a start that is not a power of two -- 5 with the byte-image pass -- steps to the power of two below it: 5 -> 4 -> 2, not
-    //  5 -> 2, which skipped the G >= 4 the bounded scan needs for batches of 512 .. 585 queries at 32 probes)
-    while (G > 1 && (int64_t)nq * ((P + G - 1) / G) < 4096) G = (G & (G - 1)) ? (1 << (31 - __builtin_clz((unsigned)G))) : G >> 1;
-    return std::max(1, std::min(G, P));
-}
-
-void launch_ivfpq_scan_pair(hipStream_t s, bool l2, const float* x, int nq, int d, int M, int P,
-                            const int* probe_list, const float* coarse_dis, const float* cc,
-                            const float* st2, const float* T2, const int64_t* list_off,
-                            const int* list_len, const uint8_t* list_mask, int nlist,
-                            const uint8_t* codes, const int64_t* ids, const int* pair_off,
-                            int64_t q_stride, float* out, const FilterDesc* ftab, const int* qfil, int need_ids,
-                            const int* qperm, int G, int pg_lo, int pg_cnt, int sparse, const ScanBound* bound,
-                            const float* pqc_fused, const int* rq_list, const int* rq_count, int chunk_len, int max_units) {
+void launch_ivfpq_scan_pair(hipStream_t s, const ScanArgs& a) {
+    const bool l2 = a.l2;
+    const float *x = a.x, *coarse_dis = a.coarse_dis, *cc = a.cc, *st2 = a.st2, *T2 = a.T2, *pqc_fused = a.pqc_fused;
+    const int nq = a.nq, d = a.d, M = a.M, P = a.P, nlist = a.nlist, need_ids = a.need_ids, G = a.G;
+    const int pg_lo = a.pg_lo, pg_cnt = a.pg_cnt, sparse = a.sparse, chunk_len = a.chunk_len, max_units = a.max_units;
+    const int *probe_list = a.probe_list, *list_len = a.list_len, *pair_off = a.pair_off, *qfil = a.qfil, *qperm = a.qperm;
+    const int *rq_list = a.rq_list, *rq_count = a.rq_count;
+    const int64_t *list_off = a.list_off, *ids = a.ids, q_stride = a.q_stride;
+    const uint8_t *list_mask = a.list_mask, *codes = a.codes;
+    float* out = a.out;
+    const FilterDesc* ftab = a.ftab;
+    const ScanBound* bound = a.bound;
     if (nq <= 0 || pg_cnt <= 0) return;
 #ifdef GH_SCAN_TIMING
     {
