@@ -90,15 +90,11 @@ int gamma_hip_destroy(gamma_hip_index* h) {
     for (hipEvent_t& e : h->ev_call)
         if (e) (void)hipEventDestroy(e);
     for (auto& sl : h->hslot) {
-        sl.x.release();
-        sl.D.release();
-        sl.I.release();
         if (sl.pin) (void)hipHostFree(sl.pin);
         if (sl.ev_up) (void)hipEventDestroy(sl.ev_up);
         if (sl.ev_done) (void)hipEventDestroy(sl.ev_done);
     }
     if (h->up_stream) (void)hipStreamDestroy(h->up_stream);
-    for (auto& b : h->fbank) b.release();
     for (hipEvent_t& e : h->ev_bank)
         if (e) (void)hipEventDestroy(e);
     if (h->ev_rfork) (void)hipEventDestroy(h->ev_rfork);
@@ -114,36 +110,12 @@ int gamma_hip_destroy(gamma_hip_index* h) {
         (void)hipEventDestroy(e.a);
         (void)hipEventDestroy(e.b);
     }
-    if (h->raw_vmm) {   // the mapped store: unmap the chunks, release them, free the range
-        h->raw_vm.release();
-        h->raw_p = nullptr;
-    }
-    // (release() of a range that was never reserved does nothing; an arena that left virtual memory management after a
-    //  failed repack read-back still owns its reserved ranges)
-    h->vm_codes.release();
-    h->vm_ids.release();
-    h->vm_sums.release();
-    h->alt_codes.release();
-    h->alt_ids.release();
-    h->alt_sums.release();
-    for (auto& r : h->vm_retired) r.release();
-    if (h->arena_vmm) {
-        h->d_codes = nullptr;
-        h->d_ids = nullptr;
-        h->d_sums = nullptr;
-    }
-    if (h->d_raw_slot) (void)hipFree(h->d_raw_slot);
-    void* ptrs[] = {h->d_list_rank, h->raw_p, h->d_sq8_tab, h->d_bitmap, h->d_cc, h->d_cc_norms, h->d_pqc, h->d_T2, h->d_codes,
-                    h->d_ids, h->d_list_mask, h->d_scan_codes, h->d_tie_stats, h->d_v2d, h->d_sums, h->d_t2max, h->bound_fb.d_stat,
-                    h->d_bin_cc, h->d_bin_stats, h->d_bf_codes, h->d_bf_stats, h->d_cc_img, h->d_cbf_stat, h->d_opq};
+    // the one-shot allocations of the model and the counters (never grown, never moved)
+    void* ptrs[] = {h->d_list_rank, h->d_sq8_tab, h->d_cc, h->d_cc_norms, h->d_pqc, h->d_T2, h->d_list_mask, h->d_scan_codes,
+                    h->d_tie_stats, h->d_t2max, h->bound_fb.d_stat, h->d_bin_cc, h->d_bin_stats, h->d_bf_stats, h->d_cc_img,
+                    h->d_cbf_stat, h->d_opq};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
-    for (auto& kv : h->fields)
-        if (kv.second.d) (void)hipFree(kv.second.d);
-    for (auto& kv : h->terms) {
-        if (kv.second.d_off) (void)hipFree(kv.second.d_off);
-        if (kv.second.d_tok) (void)hipFree(kv.second.d_tok);
-    }
     for (hipEvent_t e : h->event_pool) (void)hipEventDestroy(e);
     for (void* pp : h->comb_pin)
         if (pp) (void)hipHostFree(pp);
@@ -153,19 +125,15 @@ int gamma_hip_destroy(gamma_hip_index* h) {
     if (h->cbf_copy_ev) (void)hipEventDestroy(h->cbf_copy_ev);
     if (h->pin_cbf_stat) (void)hipHostFree(h->pin_cbf_stat);
     if (h->pin_flat_over) (void)hipHostFree(h->pin_flat_over);
-    DevBuf* bufs[] = {&h->w_mat, &h->w_coarse_dis, &h->w_probe, &h->w_xn, &h->w_st2, &h->w_pair_off,
-                      &h->w_qtotal, &h->w_dist, &h->w_cand_dis, &h->w_cand_pos, &h->w_cand_ids,
-                      &h->w_exact, &h->w_selv, &h->w_selp, &h->w_x, &h->w_outd, &h->w_outl, &h->w_stage, &h->w_shard_cut,
-                      &h->w_filter, &h->w_m_dis, &h->w_m_ids, &h->w_part_v, &h->w_part_i, &h->w_assign,
-                      &h->w_codes_tmp, &h->w_qperm, &h->w_qbins, &h->w_scnt, &h->w_sflag, &h->w_surv, &h->w_pair_base,
-                      &h->w_pair_ip, &h->w_flat_cand, &h->w_flat_meta, &h->w_full_cdis,
-                      &h->w_full_probe, &h->w_ftab, &h->w_qfil, &h->w_tieflag, &h->w_tcut, &h->w_tlist, &h->w_lm_units, &h->w_lm_cnt, &h->w_fbits, &h->w_cmp_codes, &h->w_cmp_ids, &h->w_cmp_len, &h->w_cmp_sums, &h->w_fD, &h->w_fI, &h->w_fx, &h->w_fslab, &h->w_flog, &h->w_mr_vals, &h->w_mr_ids, &h->w_mr_meta,
-                      &h->we_mat, &h->we_cdis, &h->we_x, &h->we_assign, &h->we_codes, &h->we_stage, &h->w_xrot, &h->we_xrot, &h->w_bf_hist, &h->w_bf_meta, &h->w_bf_cand, &h->w_bs_hist, &h->w_bs_meta, &h->w_bs_cand};
-    for (DevBuf* b : bufs) b->release();
     (void)hipStreamDestroy(h->stream);
     (void)hipStreamDestroy(h->wstream);
     if (h->side) (void)hipStreamDestroy(h->side);
     if (h->side2) (void)hipStreamDestroy(h->side2);
+    // Everything above is destroyed by hand because the runtime hands it out as a bare handle or pointer: streams, events,
+    // pinned host memory, the one-shot allocations.  Device memory that grows has an owner -- the workspaces (DevBuf), the
+    // raw store, the columns, the bitmap, the tables (DevArray), the arena's sets and the retired address ranges (ArenaSets)
+    // -- and the owners free themselves here, with the handle's device still current (hipSetDevice above) and its streams
+    // drained.
     delete h;
     return GAMMA_HIP_OK;
 }
@@ -367,12 +335,12 @@ int64_t gamma_hip_total_mem_bytes(gamma_hip_index* h) {
     if (!h) return -1;
     std::lock_guard<std::mutex> g(h->mu);
     int64_t b = 0;
-    b += h->raw_cap * h->raw_d * (int64_t)h->raw_esz() + h->raw_slot_cap * (int64_t)sizeof(int32_t);
+    b += h->raw_cap() * h->raw_d * (int64_t)h->raw_esz() + h->raw_slot_cap() * (int64_t)sizeof(int32_t);
     if (h->d_sq8_tab) b += (int64_t)h->raw_d * 4 * (int64_t)sizeof(float);   // sq8 store: the decode and the encode table
-    b += (int64_t)h->bitmap_cap_bytes;
-    for (auto& kv : h->fields) b += kv.second.cap * (int64_t)field_elem_size(kv.second.dtype);
-    for (auto& kv : h->terms) b += kv.second.cap_docs * 8 + kv.second.cap_tok * 4;
-    b += h->bf_cap * (int64_t)h->bf_cs;   // the binary flat store
+    b += (int64_t)h->d_bitmap.cap;
+    for (auto& kv : h->fields) b += (int64_t)kv.second.d.cap;
+    for (auto& kv : h->terms) b += (int64_t)(kv.second.d_off.cap + kv.second.d_tok.cap);
+    b += (int64_t)h->d_bf_codes.cap;   // the binary flat store
     if (h->ivf_init) {
         b += (int64_t)h->nlist * h->d * 4 + (int64_t)h->nlist * 4 + (int64_t)h->M * 256 * h->dsub * 4;
         if (h->d_T2) b += h->ivfflat ? 256 : (int64_t)h->nlist * h->M * 256 * 4;

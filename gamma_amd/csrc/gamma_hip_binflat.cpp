@@ -13,29 +13,15 @@ namespace {
 inline int bin_row_words(int cs) { return (cs + 3) / 4; }
 
 // the store holds cap rows afterwards.  Growth frees the old array, which a search in flight may read: it waits for them
-// (WriteLock::exclusive, the raw store's rule); the rows move on the writer stream.
+// (DevArray::grow, the raw store's rule -- the first allocation waits too, though it frees nothing); the rows move on the
+// writer stream.  Searches may start again afterwards.
 int binflat_reserve(H* h, WriteLock& lk, int64_t cap) {
-    if (cap <= h->bf_cap) return GAMMA_HIP_OK;
-    const int64_t want = std::max<int64_t>(cap, std::max<int64_t>(1024, h->bf_cap + h->bf_cap / 2));
+    if (cap <= h->bf_cap()) return GAMMA_HIP_OK;
+    const int64_t want = std::max<int64_t>(cap, std::max<int64_t>(1024, h->bf_cap() + h->bf_cap() / 2));
     if (want >= ((int64_t)1 << 31)) return fail(h, GAMMA_HIP_EUNSUPPORTED, "binflat: 2^31 rows or more");
-    uint8_t* nu = nullptr;
-    GH_CHECK(h, hipMalloc((void**)&nu, (size_t)want * h->bf_cs));
-    if (h->d_bf_codes) {
-        hipError_t e = lk.exclusive();
-        if (e == hipSuccess && h->bf_count > 0)
-            e = hipMemcpyAsync(nu, h->d_bf_codes, (size_t)h->bf_count * h->bf_cs, hipMemcpyDeviceToDevice, h->wstream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->wstream);
-        if (e != hipSuccess) {
-            (void)hipFree(nu);
-            lk.shared();
-            GH_CHECK(h, e);
-        }
-        (void)hipFree(h->d_bf_codes);
-        lk.shared();
-    }
-    h->d_bf_codes = nu;
-    h->bf_cap = want;
-    return GAMMA_HIP_OK;
+    const int rc = grow_array(h, "binflat", h->d_bf_codes, (size_t)cap * h->bf_cs, (size_t)want * h->bf_cs, (size_t)h->bf_count * h->bf_cs);
+    lk.shared();
+    return rc;
 }
 
 int binflat_search_device_locked(H* h, const gamma_hip_search_params* p, int nq, const uint8_t* d_x, int64_t xs, int k,

@@ -24,43 +24,13 @@
 #include <unordered_map>
 #include <vector>
 
+#include "dev_mem.h"
 #include "kernels.h"
 
 namespace ghi {
 
 constexpr double kPI = 3.14159265;  // realtime/realtime_mem_data.h:24
 constexpr int64_t kDelMask = (int64_t)(1ULL << 63);
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        if (p) {
-            hipError_t e = hipFree(p);
-            if (e != hipSuccess) return e;
-            p = nullptr;
-            cap = 0;
-        }
-        size_t want = bytes + bytes / 8 + 256;
-        hipError_t e = hipMalloc(&p, want);
-        if (e != hipSuccess) {
-            p = nullptr;
-            return e;
-        }
-        cap = want;
-        return hipSuccess;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-    template <typename T>
-    T* as() const {
-        return reinterpret_cast<T*>(p);
-    }
-};
 
 struct StageEvent {
     int stage;
@@ -118,30 +88,9 @@ struct BoundFeedback : gh::BoundFeedbackState {
 };
 
 }  // namespace ghi
-using ghi::DevBuf;
 using ghi::StageEvent;
 
 struct WriteLock;
-
-// A device array that grows in place: an address range reserved once (the device's whole memory -- addresses are free),
-// physical chunks mapped behind what is in use.  Nothing moves, so readers of the mapped part go on while it grows.
-struct VmRange {
-    char* base = nullptr;
-    size_t va_bytes = 0, mapped = 0, gran = 0;
-    int device = 0;
-    std::vector<hipMemGenericAllocationHandle_t> chunks;
-    std::vector<size_t> chunk_bytes;
-    bool tainted = false;   // unmapped without the fence (unmap_all): must not be mapped again
-    bool on() const { return base != nullptr; }
-    // false: the runtime does not offer it (nothing is left behind)
-    bool reserve(int device_, size_t chunk_min);
-    // mapped >= bytes afterwards; grows by at least 1/8 of what is mapped, in whole chunks.  On failure *what names the
-    // step and nothing of the failed step stays mapped.
-    hipError_t map_to(size_t bytes, const char** what);
-    void release();
-    // the physical memory goes back, the address range stays reserved (mapped = 0)
-    void unmap_all();
-};
 
 // GEMM-form distance calls (coarse quantizer, assign, k-means: faiss's exhaustive_L2sqr_blas, faiss:utils/distances.cpp:215-296)
 // whose sgemm_ kernel is NOT restated (oracle/gamma_oracle.c, go_gemm_k_split): K beyond 768 or an odd split, K = 384 with
@@ -241,35 +190,36 @@ struct gamma_hip_index {
     std::string err;
 
     // raw vector store
-    // The rows live behind ONE pointer, raw_p, and raw_et says what they are (gh::RowType, the numbering of
+    // The rows live in ONE array, raw, and raw_et says what they are (gh::RowType, the numbering of
     // gamma_hip_raw_elem_type; fixed at the first init): fp32 (gamma_hip_raw_init), IEEE binary16 (_init_f16: rows of 2 * raw_d
     // bytes, the writers round the caller's fp32 on the writer stream, store_kernels.hip), uint8 / int8 (_init_i8: the writers
     // take fp32 that converts exactly, checked on the host, gamma_hip_raw_i8_check) or one scalar-quantised code per element
     // (_init_sq8).  One growth machinery for all of them, rows of raw_d * raw_esz() bytes.
     // Who reads them: a reader of every element type takes raw_rows_ref() and switches on its et.  A reader that was only ever
     // taught fp32 rows takes raw_f32() and nothing else -- null on a narrow store, so its "needs the raw store" check fails
-    // there instead of misreading bytes.  Nothing outside the store's own bookkeeping touches raw_p.
+    // there instead of misreading bytes.  Nothing outside the store's own bookkeeping touches the array.
     int raw_d = 0;
     int raw_et = gh::ROW_F32;
-    void* raw_p = nullptr;
-    int64_t nraw = 0, raw_cap = 0;
+    ghi::DevArray raw;
+    int64_t nraw = 0;
+    int64_t raw_cap() const { return raw_d > 0 ? (int64_t)(raw.cap / ((size_t)raw_d * raw_esz())) : 0; }   // rows
     // sq8 store: sq8_vmin / sq8_vmax: the ranges (empty until set or trained); d_sq8_tab: 2 * raw_d float2 -- the readers'
     // decode table {step[j], vmin[j]} and behind it the writers' encode table {inv[j], vmin[j]}.
     std::vector<float> sq8_vmin, sq8_vmax, sq8_step;
     float* d_sq8_tab = nullptr;
     size_t raw_esz() const { return gh::row_elem_bytes(raw_et); }
-    bool has_raw_rows() const { return raw_p != nullptr; }
+    bool has_raw_rows() const { return raw.p != nullptr; }
     int raw_elem_type() const { return raw_et; }
     bool raw_narrow() const { return raw_et != gh::ROW_F32; }   // any store but fp32
-    const float* raw_f32() const { return raw_et == gh::ROW_F32 ? static_cast<const float*>(raw_p) : nullptr; }
-    float* raw_f32() { return raw_et == gh::ROW_F32 ? static_cast<float*>(raw_p) : nullptr; }
+    const float* raw_f32() const { return raw_et == gh::ROW_F32 ? static_cast<const float*>(raw.p) : nullptr; }
+    float* raw_f32() { return raw_et == gh::ROW_F32 ? static_cast<float*>(raw.p) : nullptr; }
     // raw vectors SHARDED with their lists (gamma_hip_raw_put, round 6): the store holds the rows of the vectors in this shard's
     // lists only, in arrival order; raw_slot[vid] = row (-1: held by another shard).  Such a handle re-ranks nothing by itself --
     // has_rank searches, flat search and raw_gets refuse -- it serves _shard_exact / _shard_export_exact.
     bool raw_sparse = false;
     std::vector<int32_t> h_raw_slot;
-    int32_t* d_raw_slot = nullptr;
-    int64_t raw_slot_cap = 0;
+    ghi::DevArrayOf<int32_t> d_raw_slot;
+    int64_t raw_slot_cap() const { return (int64_t)(d_raw_slot.cap / sizeof(int32_t)); }   // entries
     // a sparse store's rows can be rewritten in place, dropped (gamma_hip_raw_drop) and their rows reused: nraw = rows handed
     // out so far, raw_live of them hold a vector, raw_free lists the others (reused, last freed first, before the store grows)
     int64_t raw_live = 0;
@@ -278,32 +228,28 @@ struct gamma_hip_index {
     // front, physical chunks mapped behind the rows as they come -- no copy, no second allocation, no wait for the
     // searches in flight (the reference keeps 500 000-vector segments for the same reason, vector/memory_raw_vector.cc:
     // 90-142; a segment table would cost every gather an indirection, a mapped range costs nothing).  Fallback: a
-    // geometric reallocation under the exclusive lock.
-    bool raw_vmm = false;
-    VmRange raw_vm;
-    int64_t raw_regrows = 0;   // reallocations that moved the store (0 with virtual memory management)
+    // geometric reallocation (DevArray::grow; raw.mapped / raw.regrows say which it is and how often it moved).
 
     // numeric scalar columns (on-device range filters)
     struct Column {
         int dtype = 0;
-        uint8_t* d = nullptr;
-        int64_t n = 0, cap = 0;
+        ghi::DevArrayOf<uint8_t> d;
+        int64_t n = 0;
     };
     std::map<int, Column> fields;
     // STRING columns as dictionary-encoded item lists (on-device term filters): doc i = tok[start .. start + len),
     // row word off[i] = start << 16 | len (gamma_hip_term_update rewrites a row)
     struct TermColumn {
-        int64_t* d_off = nullptr;
-        int32_t* d_tok = nullptr;
-        int64_t ndocs = 0, cap_docs = 0, ntok = 0, cap_tok = 0;
+        ghi::DevArrayOf<int64_t> d_off;
+        ghi::DevArrayOf<int32_t> d_tok;
+        int64_t ndocs = 0, ntok = 0;
         std::vector<int64_t> h_rows;   // host copy of the row words
     };
     std::map<int, TermColumn> terms;
 
     // delete bitmap
-    uint8_t* d_bitmap = nullptr;
+    ghi::DevArrayOf<uint8_t> d_bitmap;   // d_bitmap.cap bytes, the host copy beside it
     int64_t bitmap_bits = 0;
-    size_t bitmap_cap_bytes = 0;
     std::vector<uint8_t> h_bitmap;
     bool bitmap_any = false;   // any delete bit set
     int64_t n_moved = 0;       // inverted-list slots marked superseded (bit 63) since creation
@@ -350,10 +296,10 @@ struct gamma_hip_index {
     // the three arena arrays (codes, ids, code sums) are mapped ranges like the raw store where the runtime allows:
     // growth maps chunks behind them -- no copy, no second arena, no exclusive lock (the reference grows per bucket for
     // the same reason, realtime/realtime_mem_data.cc:152-188,426-474).  Fallback: reallocation under the exclusive lock.
-    bool arena_vmm = false;
-    VmRange vm_codes, vm_ids, vm_sums;
-    VmRange alt_codes, alt_ids, alt_sums;   // the repack's target set (the two sets swap roles; see arena_repack)
-    std::vector<VmRange> vm_retired;        // ranges that may not be mapped again (address space only; freed with the handle)
+    // arena.cur owns what d_codes / d_ids / d_sums point at (arena_adopt sets them), arena.alt is the repack's target set
+    // (the two swap roles; see arena_repack), arena.retired the ranges that may not be mapped again.
+    ghi::ArenaSets arena;
+    bool arena_vmm() const { return arena.cur.mapped(); }
     int64_t arena_regrows = 0;   // growths that moved the arena (0 with virtual memory management)
     int64_t repack_min_entries = 1 << 16;                     // no repack for less waste than this
     int64_t n_repacks = 0;
@@ -420,8 +366,7 @@ struct gamma_hip_index {
     // multi-vector documents (VIDMgr::VID2DocID, vector/raw_vector_common.h:90-95): docid of every vid, host + device;
     // empty = single-vector documents, docid == vid.  Every delete-bitmap / filter test goes through it.
     std::vector<int32_t> h_v2d;
-    int32_t* d_v2d = nullptr;
-    int64_t v2d_cap = 0;
+    ghi::DevArrayOf<int32_t> d_v2d;
     int64_t doc_of(int64_t v) const { return (v >= 0 && (size_t)v < h_v2d.size()) ? (int64_t)h_v2d[v] : v; }
     bool doc_deleted(int64_t v) const {
         const int64_t dd = doc_of(v);
@@ -442,8 +387,9 @@ struct gamma_hip_index {
     // and the number of query sub-batches (gamma_hip_binflat_stats); host images of a call's candidate totals / segment bases
     bool bf_init = false;
     int bf_cs = 0;
-    uint8_t* d_bf_codes = nullptr;
-    int64_t bf_count = 0, bf_cap = 0, bf_subbatches = 0;
+    ghi::DevArrayOf<uint8_t> d_bf_codes;
+    int64_t bf_count = 0, bf_subbatches = 0;
+    int64_t bf_cap() const { return bf_cs > 0 ? (int64_t)(d_bf_codes.cap / (size_t)bf_cs) : 0; }   // rows
     unsigned long long* d_bf_stats = nullptr;
     std::vector<uint32_t> bf_tot_h;
     std::vector<int64_t> bf_base_h;
@@ -509,7 +455,7 @@ struct gamma_hip_index {
 
 // a writer call: writer_mu (one writer at a time) + mu; exclusive() before memory that a search in flight may be
 // reading is freed or moved: search_mu as well (no search can start), both streams drained
-struct WriteLock {
+struct WriteLock final : ghi::DevExclusive {
     gamma_hip_index* h;
     std::unique_lock<std::mutex> w, s, m;
     explicit WriteLock(gamma_hip_index* h_) : h(h_), w(h_->writer_mu), s(h_->search_mu, std::defer_lock), m(h_->mu) {
@@ -517,7 +463,7 @@ struct WriteLock {
         h->write_gen++;   // (under mu: searches read it under mu)
     }
     ~WriteLock() { h->wl = nullptr; }
-    hipError_t exclusive() {
+    hipError_t exclusive() override {
         if (!s.owns_lock()) {
             m.unlock();
             s.lock();
@@ -539,10 +485,19 @@ namespace ghi {
 
 using H = gamma_hip_index;
 
+// what DevArray::grow takes as "exclusive": the lock of the writer call under way (a call that holds none has no search
+// beside it to wait for)
+inline DevExclusive& writer_exclusive(H* h) {
+    static struct : DevExclusive {
+        hipError_t exclusive() override { return hipSuccess; }
+    } nobody;
+    return h->wl ? static_cast<DevExclusive&>(*h->wl) : nobody;
+}
+
 // the raw store's rows as the kernels of every element type take them (kernels.h): base pointer, element type and, for an sq8
 // store, the decode table
 inline gh::RowsRef raw_rows_ref(const H* h) {
-    return gh::RowsRef{h->raw_p, h->raw_et, h->raw_et == gh::ROW_SQ8 ? h->d_sq8_tab : nullptr};
+    return gh::RowsRef{h->raw.p, h->raw_et, h->raw_et == gh::ROW_SQ8 ? h->d_sq8_tab : nullptr};
 }
 
 // a search-type call: search_mu for the whole call, mu while it reads the handle and enqueues
@@ -576,6 +531,20 @@ struct SearchLock {
 inline int fail(H* h, int code, const char* msg) {
     h->err = msg;
     return code;
+}
+
+// a failed DevArray / DevColumns growth as the store's error: `who` names the store, `what` the step
+inline int grow_fail(H* h, const char* who, hipError_t e, const char* what) {
+    if (e == hipErrorOutOfMemory && !strcmp(what, "hipMalloc")) return fail(h, GAMMA_HIP_ENOMEM, (std::string(who) + ": out of memory").c_str());
+    if (e == hipErrorOutOfMemory) return fail(h, GAMMA_HIP_ENOMEM, (std::string(who) + ": out of device memory (" + what + ")").c_str());
+    h->err = std::string(who) + ": " + what + " failed: " + hipGetErrorString(e);
+    return GAMMA_HIP_EDEVICE;
+}
+// one array through DevArray::grow on the writer stream, under the writer's lock
+inline int grow_array(H* h, const char* who, DevArray& a, size_t need, size_t want, size_t keep, int fill = -1) {
+    const char* what = "";
+    const hipError_t e = a.grow(need, want, keep, fill, h->wstream, writer_exclusive(h), &what);
+    return e == hipSuccess ? GAMMA_HIP_OK : grow_fail(h, who, e, what);
 }
 
 struct StageScope {

@@ -59,7 +59,7 @@ int ivfflat_shard_scan(H* h, const gamma_hip_search_params* p, const FiltCtx& fc
         }
         if (h->raw_sparse)
             gh::launch_ivfflat_lm_sparse(s, l2, xq, nc, h->d, P, probe, h->w_pair_off.as<int>(), h->d_list_off, len, nlist, h->d_ids,
-                                         h->raw_f32(), h->nraw, h->d_raw_slot, h->raw_slot_cap, q_stride, h->w_dist.as<float>(), fc.d_tab,
+                                         h->raw_f32(), h->nraw, h->d_raw_slot, h->raw_slot_cap(), q_stride, h->w_dist.as<float>(), fc.d_tab,
                                          need_filter, p->min_score, p->max_score, h->w_lm_units.p);
         else
             gh::launch_ivfflat_lm(s, l2, xq, nc, h->d, P, probe, h->w_pair_off.as<int>(), h->d_list_off, len, nlist, h->d_ids,
@@ -69,7 +69,7 @@ int ivfflat_shard_scan(H* h, const gamma_hip_search_params* p, const FiltCtx& fc
         h->fl_pair.fetch_add(1, std::memory_order_relaxed);
         if (h->raw_sparse)
             gh::launch_ivfflat_scan_sparse(s, l2, xq, nc, h->d, P, h->w_pair_off.as<int>(), h->w_pair_base.as<int64_t>(), h->d_ids,
-                                           h->raw_f32(), h->nraw, h->d_raw_slot, h->raw_slot_cap, q_stride, h->w_dist.as<float>(),
+                                           h->raw_f32(), h->nraw, h->d_raw_slot, h->raw_slot_cap(), q_stride, h->w_dist.as<float>(),
                                            fc.d_tab, need_filter, p->min_score, p->max_score);
         else
             gh::launch_ivfflat_scan(s, l2, xq, nc, h->d, P, h->w_pair_off.as<int>(), h->w_pair_base.as<int64_t>(), h->d_ids, h->raw_f32(),

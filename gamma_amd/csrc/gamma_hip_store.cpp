@@ -8,231 +8,35 @@
 
 namespace ghi {
 
-
-// ---- mapped ranges ------------------------------------------------------------------------
-}  // namespace ghi
-bool VmRange::reserve(int device_, size_t chunk_min) {
-    hipMemAllocationProp prop = {};
-    prop.type = hipMemAllocationTypePinned;
-    prop.location.type = hipMemLocationTypeDevice;
-    prop.location.id = device_;
-    size_t g = 0, free_b = 0, total_b = 0;
-    void* va = nullptr;
-    if (hipMemGetAllocationGranularity(&g, &prop, hipMemAllocationGranularityRecommended) != hipSuccess || g == 0 ||
-        hipMemGetInfo(&free_b, &total_b) != hipSuccess || total_b == 0) {
-        (void)hipGetLastError();
-        return false;
-    }
-    // whole chunks of at least 2 MB: hipMemSetAccess refuses chunk sizes that are only a multiple of the reported 4 KB
-    // granularity (tools/exp/vmm_probe.cpp)
-    const size_t chunk = std::max<size_t>(std::max<size_t>(g, chunk_min), (size_t)2 << 20) / g * g;
-    const size_t want = (total_b + chunk - 1) / chunk * chunk;
-    if (hipMemAddressReserve(&va, want, 0, nullptr, 0) != hipSuccess || !va) {
-        (void)hipGetLastError();
-        return false;
-    }
-    base = static_cast<char*>(va);
-    va_bytes = want;
-    mapped = 0;
-    gran = chunk;
-    device = device_;
-    return true;
-}
-static bool vm_unmap_fence();
-hipError_t VmRange::map_to(size_t bytes, const char** what) {
-    *what = "";
-    if (bytes <= mapped) return hipSuccess;
-    size_t add = std::max(bytes - mapped, mapped / 8);   // fewer, larger chunks
-    add = (add + gran - 1) / gran * gran;
-    if (mapped + add > va_bytes) add = va_bytes - mapped;
-    if (mapped + add < bytes) {
-        *what = "beyond the reserved address range";
-        return hipErrorOutOfMemory;
-    }
-    hipMemAllocationProp prop = {};
-    prop.type = hipMemAllocationTypePinned;
-    prop.location.type = hipMemLocationTypeDevice;
-    prop.location.id = device;
-    hipMemGenericAllocationHandle_t hnd;
-    hipError_t e = hipMemCreate(&hnd, add, &prop, 0);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        *what = "hipMemCreate";
-        return e;
-    }
-    char* at = base + mapped;
-    hipMemAccessDesc acc = {};
-    acc.location.type = hipMemLocationTypeDevice;
-    acc.location.id = device;
-    acc.flags = hipMemAccessFlagsProtReadWrite;
-    // beside the kernels of the searches in flight: page-table updates of a range they do not read yet
-    // (tools/exp/vmm_probe.cpp: mapping beside kernels on the range and beside a thread allocating and launching)
-    e = hipMemMap(at, add, 0, hnd, 0);
-    *what = "hipMemMap";
-    if (e == hipSuccess) {
-        e = hipMemSetAccess(at, add, &acc, 1);
-        *what = "hipMemSetAccess";
-        if (e != hipSuccess) {   // seen for chunks that are not a multiple of 2 MB: the whole mapped range is accepted
-            (void)hipGetLastError();
-            e = hipMemSetAccess(base, mapped + add, &acc, 1);
-        }
-        if (e != hipSuccess) {
-            (void)hipMemUnmap(at, add);
-            if (!vm_unmap_fence()) tainted = true;   // (the next map_to would hand out the same address)
-        }
-    }
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipMemRelease(hnd);
-        return e;
-    }
-    chunks.push_back(hnd);
-    chunk_bytes.push_back(add);
-    mapped += add;
-    *what = "";
-    return hipSuccess;
-}
-// An address that was unmapped and is mapped again (to other physical memory) read back stale contents -- zeros -- now and then
-// on this runtime when the GPU was shared with other processes (tests/test_gpu_fuzz.py::test_random_realtime_script under six
-// processes: 10-18 % of the scripts, whether the range was freed and reserved again or merely unmapped and remapped;
-// hipDeviceSynchronize does not help).  An ordinary allocation and release by the runtime in between does (0 of 400): it goes
-// through the driver's page-table path and leaves no stale translation behind.  Every unmap ends with one.
-static bool vm_unmap_fence() {
-    // (the runtime serves allocations below 2 MB from blocks it keeps: 1 MB and 4 KB fences changed nothing, 2 / 4 / 16 / 64 MB
-    //  all cured it -- 0 of 600 scripts each)
-    void* t = nullptr;
-    for (size_t bytes : {(size_t)16 << 20, (size_t)2 << 20}) {
-        if (hipMalloc(&t, bytes) == hipSuccess) {
-            (void)hipFree(t);
-            return true;
-        }
-        (void)hipGetLastError();
-    }
-    return false;   // the device is out of memory: the caller must not map these addresses again
-}
-void VmRange::unmap_all() {
-    if (!base) return;
-    size_t off = 0;
-    for (size_t i = 0; i < chunks.size(); i++) {
-        (void)hipMemUnmap(base + off, chunk_bytes[i]);
-        (void)hipMemRelease(chunks[i]);
-        off += chunk_bytes[i];
-    }
-    if (!chunks.empty() && !vm_unmap_fence()) tainted = true;
-    chunks.clear();
-    chunk_bytes.clear();
-    mapped = 0;
-}
-void VmRange::release() {
-    if (!base) return;
-    size_t off = 0;
-    for (size_t i = 0; i < chunks.size(); i++) {
-        (void)hipMemUnmap(base + off, chunk_bytes[i]);
-        (void)hipMemRelease(chunks[i]);
-        off += chunk_bytes[i];
-    }
-    // (no fence: the address range is NOT given back -- whoever reserved it next would map addresses with stale
-    //  translations; it stays reserved for the life of the process, address space only)
-    if (chunks.empty() || vm_unmap_fence()) (void)hipMemAddressFree(base, va_bytes);
-    chunks.clear();
-    chunk_bytes.clear();
-    base = nullptr;
-    va_bytes = mapped = 0;
-}
-namespace ghi {
-
-static int vm_fail(H* h, const char* who, hipError_t e, const char* what) {
-    if (e == hipErrorOutOfMemory) return fail(h, GAMMA_HIP_ENOMEM, (std::string(who) + ": out of device memory (" + what + ")").c_str());
-    h->err = std::string(who) + ": " + what + " failed: " + hipGetErrorString(e);
-    return GAMMA_HIP_EDEVICE;
-}
-
 // ---- arena ---------------------------------------------------------------------------
-// entries the three mapped arrays hold
-static int64_t arena_vm_cap(const H* h) {
-    int64_t c = std::min<int64_t>((int64_t)(h->vm_codes.mapped / (size_t)h->code_size), (int64_t)(h->vm_ids.mapped / sizeof(int64_t)));
-    if (h->keep_sums) c = std::min<int64_t>(c, (int64_t)(h->vm_sums.mapped / sizeof(float)));
-    return c;
-}
-// the first reservation of an index: mapped ranges when the runtime offers them AND the first chunks map (a failure
-// here leaves the reallocating arena, nothing behind)
-static bool arena_vm_start(H* h, int64_t entries) {
-    if (getenv("GAMMA_HIP_NO_ARENA_VMM")) return false;
-    const size_t chunk = (size_t)8 << 20;
-    const char* what = "";
-    bool ok = h->vm_codes.reserve(h->device, chunk) && h->vm_ids.reserve(h->device, chunk) &&
-              (!h->keep_sums || h->vm_sums.reserve(h->device, chunk));
-    ok = ok && h->vm_codes.map_to((size_t)entries * h->code_size, &what) == hipSuccess &&
-         h->vm_ids.map_to((size_t)entries * sizeof(int64_t), &what) == hipSuccess &&
-         (!h->keep_sums || h->vm_sums.map_to((size_t)entries * sizeof(float), &what) == hipSuccess);
-    if (!ok) {
-        h->vm_codes.release();
-        h->vm_ids.release();
-        h->vm_sums.release();
-        (void)hipGetLastError();
-        return false;
-    }
-    return true;
-}
-static void arena_vm_adopt(H* h) {
-    h->d_codes = reinterpret_cast<uint8_t*>(h->vm_codes.base);
-    h->d_ids = reinterpret_cast<int64_t*>(h->vm_ids.base);
-    h->d_sums = h->keep_sums ? reinterpret_cast<float*>(h->vm_sums.base) : nullptr;
-    h->arena_cap = arena_vm_cap(h);
-}
+// (every array of this file that grows does so through DevArray::grow, dev_mem.h; the growth laws are here)
+static const size_t kArenaChunk = (size_t)8 << 20;   // mapped in chunks of at least 8 MB
+// the readers' pointers and the capacity are the current set's
+static void arena_adopt(H* h) { h->arena.adopt(&h->d_codes, &h->d_ids, &h->d_sums, &h->arena_cap); }
 
 int arena_reserve(H* h, int64_t need_entries) {
-    if (h->arena_used + need_entries <= h->arena_cap) return GAMMA_HIP_OK;
-    if (!h->d_codes && h->arena_cap == 0 && !h->arena_vmm && arena_vm_start(h, h->arena_used + need_entries)) {
-        h->arena_vmm = true;
-        arena_vm_adopt(h);
-        return GAMMA_HIP_OK;
+    const int64_t need = h->arena_used + need_entries;
+    if (need <= h->arena_cap) return GAMMA_HIP_OK;
+    DevColumns& cur = h->arena.cur;
+    if (!h->d_codes && h->arena_cap == 0) {
+        // the first reservation of an index: mapped ranges when the runtime offers them AND the first chunks map (a failure
+        // leaves the reallocating arena, nothing behind)
+        cur.shape((size_t)h->code_size, sizeof(int64_t), h->keep_sums ? sizeof(float) : 0);
+        if (!getenv("GAMMA_HIP_NO_ARENA_VMM") && cur.start_mapped(h->device, kArenaChunk, need)) {
+            arena_adopt(h);
+            return GAMMA_HIP_OK;
+        }
     }
-    if (h->arena_vmm) {
-        // map more physical memory behind the three arrays in place: nothing moves, the searches in flight go on
-        const int64_t need = h->arena_used + need_entries;
-        const char* what = "";
-        hipError_t e = h->vm_codes.map_to((size_t)need * h->code_size, &what);
-        if (e == hipSuccess) e = h->vm_ids.map_to((size_t)need * sizeof(int64_t), &what);
-        if (e == hipSuccess && h->keep_sums) e = h->vm_sums.map_to((size_t)need * sizeof(float), &what);
-        h->arena_cap = arena_vm_cap(h);
-        if (e != hipSuccess) return vm_fail(h, "arena growth", e, what);
-        return GAMMA_HIP_OK;
-    }
-    h->arena_regrows++;
-    int64_t ncap = std::max<int64_t>(h->arena_cap * 2, h->arena_used + need_entries);
+    // mapped: more physical memory behind the arrays in place -- nothing moves, the searches in flight go on.  Otherwise the
+    // arrays move, under the exclusive lock.
+    int64_t ncap = std::max<int64_t>(h->arena_cap * 2, need);
     ncap += ncap / 8;
-    uint8_t* nc = nullptr;
-    int64_t* ni = nullptr;
-    if (h->wl) GH_CHECK(h, h->wl->exclusive());   // the old arrays are freed below: no search may be reading them
-    GH_CHECK(h, hipMalloc((void**)&nc, (size_t)ncap * h->code_size));
-    if (hipMalloc((void**)&ni, (size_t)ncap * sizeof(int64_t)) != hipSuccess) {
-        (void)hipFree(nc);
-        return fail(h, GAMMA_HIP_ENOMEM, "arena growth: out of memory");
-    }
-    float* ns = nullptr;
-    if (h->keep_sums && hipMalloc((void**)&ns, (size_t)ncap * sizeof(float)) != hipSuccess) {
-        (void)hipFree(nc);
-        (void)hipFree(ni);
-        return fail(h, GAMMA_HIP_ENOMEM, "arena growth: out of memory");
-    }
-    if (ns && h->d_sums && h->arena_used > 0)
-        GH_CHECK(h, hipMemcpyAsync(ns, h->d_sums, (size_t)h->arena_used * sizeof(float), hipMemcpyDeviceToDevice, h->wstream));
-    if (h->arena_used > 0) {
-        GH_CHECK(h, hipMemcpyAsync(nc, h->d_codes, (size_t)h->arena_used * h->code_size,
-                                   hipMemcpyDeviceToDevice, h->wstream));
-        GH_CHECK(h, hipMemcpyAsync(ni, h->d_ids, (size_t)h->arena_used * sizeof(int64_t),
-                                   hipMemcpyDeviceToDevice, h->wstream));
-    }
-    GH_CHECK(h, hipStreamSynchronize(h->wstream));
-    if (h->d_codes) GH_CHECK(h, hipFree(h->d_codes));
-    if (h->d_ids) GH_CHECK(h, hipFree(h->d_ids));
-    if (h->d_sums) GH_CHECK(h, hipFree(h->d_sums));
-    h->d_codes = nc;
-    h->d_ids = ni;
-    h->d_sums = ns;
-    h->arena_cap = ncap;
-    return GAMMA_HIP_OK;
+    const bool moves = !cur.mapped();
+    const char* what = "";
+    const hipError_t e = cur.grow(need, ncap, h->arena_used, h->wstream, writer_exclusive(h), &what);
+    arena_adopt(h);   // (also after a failure: a column that did move is read through its new pointer)
+    if (moves && e == hipSuccess) h->arena_regrows++;   // as DevArray::regrows: the moves that happened
+    return e == hipSuccess ? GAMMA_HIP_OK : grow_fail(h, "arena growth", e, what);
 }
 
 // sums of arena entries [pos, pos + n) of list l, behind the copy of their codes on the writer stream
@@ -277,61 +81,23 @@ static int repack_checksums(H* h, const uint8_t* codes, const int64_t* ids, cons
 static const int kRepackMismatch = 1;
 static int arena_repack_once(H* h, bool vmm, const std::vector<int64_t>& noff, int64_t total, int64_t ncap,
                              const std::vector<unsigned long long>& src_sum) {
-    uint8_t* nc = nullptr;
-    int64_t* ni = nullptr;
-    float* ns = nullptr;
-    // Mapped arena: the handle keeps TWO sets of address ranges and the repack moves the lists from the set in use into the
-    // other one (physical chunks mapped there for the occasion), gives the old set's physical memory back and swaps the roles.
-    struct AltGuard {   // an error below gives the target set's physical memory back
+    // The handle keeps TWO column sets and the repack moves the lists from the set in use into the other one -- physical chunks
+    // mapped into its ranges for the occasion, or plain allocations -- gives the old set's memory back and swaps the roles.
+    DevColumns& alt = h->arena.alt;
+    struct TargetGuard {   // an error below gives the target set's memory back
         H* h;
         bool armed = true;
-        ~AltGuard() {
-            if (armed) {
-                h->alt_codes.unmap_all();
-                h->alt_ids.unmap_all();
-                h->alt_sums.unmap_all();
-            }
+        ~TargetGuard() {
+            if (armed) h->arena.alt.clear(&h->arena.retired);
         }
-    } alt_guard{h, vmm};
-    struct MallocGuard {
-        void* p[3] = {nullptr, nullptr, nullptr};
-        bool armed = true;
-        ~MallocGuard() {
-            if (armed)
-                for (void* q : p)
-                    if (q) (void)hipFree(q);
-        }
-    } mg;
-    if (vmm) {
-        for (VmRange* r : {&h->alt_codes, &h->alt_ids, &h->alt_sums})
-            if (r->tainted) {   // unmapped without a fence, or failed a read-back: these addresses are not mapped again
-                h->vm_retired.push_back(std::move(*r));
-                *r = VmRange();
-            }
-        const size_t chunk = (size_t)8 << 20;
-        const char* what = "";
-        hipError_t e = hipSuccess;
-        if ((!h->alt_codes.on() && !h->alt_codes.reserve(h->device, chunk)) || (!h->alt_ids.on() && !h->alt_ids.reserve(h->device, chunk)) ||
-            (h->keep_sums && !h->alt_sums.on() && !h->alt_sums.reserve(h->device, chunk))) {
-            e = hipErrorOutOfMemory;
-            what = "address range";
-        }
-        if (e == hipSuccess) e = h->alt_codes.map_to((size_t)ncap * h->code_size, &what);
-        if (e == hipSuccess) e = h->alt_ids.map_to((size_t)ncap * sizeof(int64_t), &what);
-        if (e == hipSuccess && h->keep_sums) e = h->alt_sums.map_to((size_t)ncap * sizeof(float), &what);
-        if (e != hipSuccess) return vm_fail(h, "arena repack", e, what);
-        nc = reinterpret_cast<uint8_t*>(h->alt_codes.base);
-        ni = reinterpret_cast<int64_t*>(h->alt_ids.base);
-        ns = h->keep_sums ? reinterpret_cast<float*>(h->alt_sums.base) : nullptr;
-    } else {
-        if (hipMalloc((void**)&nc, (size_t)ncap * h->code_size) != hipSuccess) return fail(h, GAMMA_HIP_ENOMEM, "arena repack: out of memory");
-        mg.p[0] = nc;
-        if (hipMalloc((void**)&ni, (size_t)ncap * sizeof(int64_t)) != hipSuccess) return fail(h, GAMMA_HIP_ENOMEM, "arena repack: out of memory");
-        mg.p[1] = ni;
-        if (h->keep_sums && hipMalloc((void**)&ns, (size_t)ncap * sizeof(float)) != hipSuccess)
-            return fail(h, GAMMA_HIP_ENOMEM, "arena repack: out of memory");
-        mg.p[2] = ns;
-    }
+    } guard{h};
+    alt.shape((size_t)h->code_size, sizeof(int64_t), h->keep_sums ? sizeof(float) : 0);
+    const char* what = "";
+    const hipError_t te = vmm ? alt.map_target(h->device, kArenaChunk, ncap, &h->arena.retired, &what)
+                              : alt.alloc_target(ncap, h->wstream, writer_exclusive(h), &h->arena.retired, &what);
+    if (te != hipSuccess) return grow_fail(h, "arena repack", te, what);
+    uint8_t* nc = alt.col[0].as<uint8_t>();
+    int64_t* ni = alt.col[1].as<int64_t>();
     GH_CHECK(h, h->we_stage.ensure((size_t)h->nlist * sizeof(int64_t)));
     GH_CHECK(h, hipMemcpyAsync(h->we_stage.p, noff.data(), (size_t)h->nlist * sizeof(int64_t), hipMemcpyHostToDevice, h->wstream));
     gh::launch_repack_lists(h->wstream, h->d_codes, h->d_ids, nc, ni, h->d_list_off, h->we_stage.as<int64_t>(),
@@ -353,39 +119,16 @@ static int arena_repack_once(H* h, bool vmm, const std::vector<int64_t>& noff, i
         h->repack_verified++;
         if (dst_sum != src_sum) {
             h->repack_verify_failures++;
-            if (vmm) {   // the guard unmaps the target (with its fence); its addresses are never mapped again
-                h->alt_codes.tainted = h->alt_ids.tainted = true;
-                if (h->keep_sums) h->alt_sums.tainted = true;
-            }
+            alt.taint();   // the guard unmaps a mapped target (with its fence); its addresses are never mapped again
             return kRepackMismatch;
         }
     }
-    if (vmm) {
-        alt_guard.armed = false;   // the target set is the arena from here
-        h->vm_codes.unmap_all();
-        h->vm_ids.unmap_all();
-        h->vm_sums.unmap_all();
-        std::swap(h->vm_codes, h->alt_codes);
-        std::swap(h->vm_ids, h->alt_ids);
-        std::swap(h->vm_sums, h->alt_sums);
-        arena_vm_adopt(h);
-    } else {
-        mg.armed = false;
-        if (h->arena_vmm) {   // leaving virtual memory management after a failed read-back: the mapped sets go
-            h->vm_codes.unmap_all();
-            h->vm_ids.unmap_all();
-            h->vm_sums.unmap_all();
-            h->arena_vmm = false;
-        } else {
-            GH_CHECK(h, hipFree(h->d_codes));
-            GH_CHECK(h, hipFree(h->d_ids));
-            if (h->d_sums) GH_CHECK(h, hipFree(h->d_sums));
-        }
-        h->d_codes = nc;
-        h->d_ids = ni;
-        h->d_sums = ns;
-        h->arena_cap = ncap;
-    }
+    // the target set is the arena from here; the old set's memory goes back (a set that leaves virtual memory management
+    // after a failed read-back keeps its ranges reserved, unmapped)
+    guard.armed = false;
+    h->arena.swap_sets();
+    h->arena.alt.clear(&h->arena.retired);
+    arena_adopt(h);
     h->arena_used = total;
     h->arena_waste = 0;
     h->h_list_off = noff;
@@ -406,8 +149,8 @@ int arena_repack(H* h) {
     GH_TRY(publish_meta(h));                      // the device tables the kernels below read = the host mirror
     std::vector<unsigned long long> src_sum;
     GH_TRY(repack_checksums(h, h->d_codes, h->d_ids, h->d_list_off, &src_sum));
-    int rc = arena_repack_once(h, h->arena_vmm, noff, total, ncap, src_sum);
-    if (rc == kRepackMismatch && h->arena_vmm) rc = arena_repack_once(h, false, noff, total, ncap, src_sum);
+    int rc = arena_repack_once(h, h->arena_vmm(), noff, total, ncap, src_sum);
+    if (rc == kRepackMismatch && h->arena_vmm()) rc = arena_repack_once(h, false, noff, total, ncap, src_sum);
     if (rc == kRepackMismatch)
         return fail(h, GAMMA_HIP_EDEVICE, "arena repack: the moved lists did not read back as written (the previous arena stays in use)");
     return rc;
@@ -556,20 +299,11 @@ int gamma_hip_field_append(gamma_hip_index* h, int field_id, int dtype, int64_t 
         return fail(h, GAMMA_HIP_EINVAL, "bad column append");
     GH_CHECK(h, hipSetDevice(h->device));
     auto& c = h->fields[field_id];
-    if (c.n == 0 && c.cap == 0) c.dtype = dtype;
+    if (c.n == 0 && c.d.cap == 0) c.dtype = dtype;
     if (c.dtype != dtype) return fail(h, GAMMA_HIP_EINVAL, "column dtype mismatch");
     const size_t es = field_elem_size(dtype);
-    if (c.n + n > c.cap) {
-        const int64_t ncap = std::max<int64_t>(c.n + n, std::max<int64_t>(1 << 16, c.cap * 2));
-        uint8_t* nd = nullptr;
-        GH_CHECK(h, lk.exclusive());   // the old column is freed below
-        GH_CHECK(h, hipMalloc((void**)&nd, (size_t)ncap * es));
-        if (c.n) GH_CHECK(h, hipMemcpyAsync(nd, c.d, (size_t)c.n * es, hipMemcpyDeviceToDevice, h->wstream));
-        GH_CHECK(h, hipStreamSynchronize(h->wstream));
-        if (c.d) (void)hipFree(c.d);
-        c.d = nd;
-        c.cap = ncap;
-    }
+    const int64_t ncap = std::max<int64_t>(c.n + n, std::max<int64_t>(1 << 16, (int64_t)(c.d.cap / es) * 2));
+    GH_TRY(grow_array(h, "column", c.d, (size_t)(c.n + n) * es, (size_t)ncap * es, (size_t)c.n * es));
     if (n) {
         GH_CHECK(h, hipMemcpyAsync(c.d + (size_t)c.n * es, values, (size_t)n * es, hipMemcpyHostToDevice, h->wstream));
         GH_CHECK(h, hipStreamSynchronize(h->wstream));
@@ -595,17 +329,8 @@ int gamma_hip_vid2docid_append(gamma_hip_index* h, int64_t n, const int32_t* doc
     WriteLock lk(h);
     GH_CHECK(h, hipSetDevice(h->device));
     const int64_t have = (int64_t)h->h_v2d.size();
-    if (have + n > h->v2d_cap) {
-        const int64_t ncap = std::max<int64_t>(have + n, std::max<int64_t>(1 << 16, h->v2d_cap * 2));
-        int32_t* nd = nullptr;
-        GH_CHECK(h, lk.exclusive());   // the old array is freed below
-        GH_CHECK(h, hipMalloc((void**)&nd, (size_t)ncap * sizeof(int32_t)));
-        if (have) GH_CHECK(h, hipMemcpyAsync(nd, h->d_v2d, (size_t)have * sizeof(int32_t), hipMemcpyDeviceToDevice, h->wstream));
-        GH_CHECK(h, hipStreamSynchronize(h->wstream));
-        if (h->d_v2d) (void)hipFree(h->d_v2d);
-        h->d_v2d = nd;
-        h->v2d_cap = ncap;
-    }
+    const int64_t ncap = std::max<int64_t>(have + n, std::max<int64_t>(1 << 16, (int64_t)(h->d_v2d.cap / sizeof(int32_t)) * 2));
+    GH_TRY(grow_array(h, "vid2docid", h->d_v2d, (size_t)(have + n) * sizeof(int32_t), (size_t)ncap * sizeof(int32_t), (size_t)have * sizeof(int32_t)));
     if (n) {
         GH_CHECK(h, hipMemcpyAsync(h->d_v2d + have, docids, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, h->wstream));
         GH_CHECK(h, hipStreamSynchronize(h->wstream));
@@ -630,31 +355,14 @@ int64_t gamma_hip_field_count(gamma_hip_index* h, int field_id) {
 // A STRING column on the device: doc i = items tok[start .. start + len), its row word = start << 16 | len.  One 8-byte
 // word per doc (not CSR offsets) so that a doc's items can be REWRITTEN: the new items go in place when they fit, else
 // to the end of the item array, and the row word -- a single aligned store -- switches the doc over.
-static int term_reserve(gamma_hip_index* h, WriteLock& lk, gamma_hip_index::TermColumn& c, int64_t add_docs, int64_t add_tok) {
-    if (c.ndocs + add_docs <= c.cap_docs && c.ntok + add_tok <= c.cap_tok && c.d_off) return GAMMA_HIP_OK;
-    // growth frees the old arrays: no search may be reading them
-    GH_CHECK(h, lk.exclusive());
-    const int64_t nd = std::max<int64_t>(c.ndocs + add_docs, std::max<int64_t>(1 << 16, c.cap_docs * 2));
-    const int64_t nt = std::max<int64_t>(c.ntok + add_tok, std::max<int64_t>(1 << 16, c.cap_tok * 2));
-    int64_t* no = nullptr;
-    int32_t* ntk = nullptr;
-    GH_CHECK(h, hipMalloc((void**)&no, (size_t)nd * sizeof(int64_t)));
-    if (hipMalloc((void**)&ntk, (size_t)nt * sizeof(int32_t)) != hipSuccess) {
-        (void)hipFree(no);
-        return fail(h, GAMMA_HIP_ENOMEM, "term column: out of memory");
-    }
-    if (c.d_off) {
-        if (c.ndocs) GH_CHECK(h, hipMemcpyAsync(no, c.d_off, (size_t)c.ndocs * sizeof(int64_t), hipMemcpyDeviceToDevice, h->wstream));
-        if (c.ntok) GH_CHECK(h, hipMemcpyAsync(ntk, c.d_tok, (size_t)c.ntok * sizeof(int32_t), hipMemcpyDeviceToDevice, h->wstream));
-    }
-    GH_CHECK(h, hipStreamSynchronize(h->wstream));
-    if (c.d_off) (void)hipFree(c.d_off);
-    if (c.d_tok) (void)hipFree(c.d_tok);
-    c.d_off = no;
-    c.d_tok = ntk;
-    c.cap_docs = nd;
-    c.cap_tok = nt;
-    return GAMMA_HIP_OK;
+static int term_reserve(gamma_hip_index* h, gamma_hip_index::TermColumn& c, int64_t add_docs, int64_t add_tok) {
+    const int64_t cap_docs = (int64_t)(c.d_off.cap / sizeof(int64_t)), cap_tok = (int64_t)(c.d_tok.cap / sizeof(int32_t));
+    if (c.ndocs + add_docs <= cap_docs && c.ntok + add_tok <= cap_tok && c.d_off) return GAMMA_HIP_OK;
+    // both arrays move whenever either is short (so each is asked for its new capacity, not for what it needs)
+    const size_t nd = (size_t)std::max<int64_t>(c.ndocs + add_docs, std::max<int64_t>(1 << 16, cap_docs * 2)) * sizeof(int64_t);
+    const size_t nt = (size_t)std::max<int64_t>(c.ntok + add_tok, std::max<int64_t>(1 << 16, cap_tok * 2)) * sizeof(int32_t);
+    GH_TRY(grow_array(h, "term column", c.d_off, nd, nd, (size_t)c.ndocs * sizeof(int64_t)));
+    return grow_array(h, "term column", c.d_tok, nt, nt, (size_t)c.ntok * sizeof(int32_t));
 }
 
 int gamma_hip_term_append(gamma_hip_index* h, int field_id, int64_t n_docs, const int32_t* counts,
@@ -669,7 +377,7 @@ int gamma_hip_term_append(gamma_hip_index* h, int field_id, int64_t n_docs, cons
         add_tok += counts[i];
     }
     if (add_tok > 0 && !items) return fail(h, GAMMA_HIP_EINVAL, "null items");
-    GH_TRY(term_reserve(h, lk, c, n_docs, add_tok));
+    GH_TRY(term_reserve(h, c, n_docs, add_tok));
     if (n_docs > 0) {
         std::vector<int64_t> rows(n_docs);
         int64_t run = c.ntok;
@@ -698,7 +406,7 @@ int gamma_hip_term_update(gamma_hip_index* h, int field_id, int64_t docid, int32
     const int64_t old = c.h_rows[docid];
     int64_t start = old >> 16;
     if (count > (int32_t)(old & 0xffff)) {   // does not fit in place: the new items go to the end of the item array
-        GH_TRY(term_reserve(h, lk, c, 0, count));
+        GH_TRY(term_reserve(h, c, 0, count));
         start = c.ntok;
         c.ntok += count;
     }
@@ -737,10 +445,7 @@ static int raw_init_as(gamma_hip_index* h, int d, int et) {
         // reserve the address range the store may ever need (the device's memory): physical chunks are mapped into it
         // as rows arrive (raw_reserve).  Any failure -- here or of the FIRST chunk -- leaves the reallocating store.
         GH_CHECK(h, hipSetDevice(h->device));
-        if (h->raw_vm.reserve(h->device, (size_t)64 << 20)) {   // chunks of whole 64 MB
-            h->raw_vmm = true;
-            h->raw_p = h->raw_vm.base;
-        }
+        (void)h->raw.reserve(h->device, (size_t)64 << 20);   // chunks of whole 64 MB
     }
     h->raw_d = d;
     return GAMMA_HIP_OK;
@@ -761,37 +466,13 @@ int gamma_hip_raw_elem_bytes(gamma_hip_index* h) {
     return h->raw_d > 0 ? (int)h->raw_esz() : 0;
 }
 
+// the store holds `need` rows afterwards: chunks mapped behind the rows in place, or a geometric reallocation (a mapped
+// store whose first chunk fails gives its range back and reallocates from then on: DevArray::grow)
 static int raw_reserve(H* h, int64_t need) {
-    if (need <= h->raw_cap) return GAMMA_HIP_OK;
-    if (h->raw_vmm) {
-        // map more physical memory behind the rows in place: nothing moves
-        const size_t row = (size_t)h->raw_d * h->raw_esz();
-        const char* what = "";
-        hipError_t e = h->raw_vm.map_to((size_t)need * row, &what);
-        if (e == hipSuccess) {
-            h->raw_cap = (int64_t)(h->raw_vm.mapped / row);
-            return GAMMA_HIP_OK;
-        }
-        if (h->raw_vm.mapped > 0 || h->nraw > 0) return vm_fail(h, "raw store", e, what);
-        // nothing is mapped yet: the range is given back and the store reallocates from here on
-        h->raw_vm.release();
-        h->raw_vmm = false;
-        h->raw_p = nullptr;
-    }
-    h->raw_regrows++;
-    int64_t ncap = std::max<int64_t>(need, h->raw_cap + h->raw_cap / 2);
-    ncap = std::max<int64_t>(ncap, 1024);
-    void* np = nullptr;
-    if (h->wl) GH_CHECK(h, h->wl->exclusive());   // the old store is freed below
-    GH_CHECK(h, hipMalloc(&np, (size_t)ncap * h->raw_d * h->raw_esz()));
-    if (h->nraw > 0)
-        GH_CHECK(h, hipMemcpyAsync(np, h->raw_p, (size_t)h->nraw * h->raw_d * h->raw_esz(),
-                                   hipMemcpyDeviceToDevice, h->wstream));
-    GH_CHECK(h, hipStreamSynchronize(h->wstream));
-    if (h->raw_p) GH_CHECK(h, hipFree(h->raw_p));
-    h->raw_p = np;
-    h->raw_cap = ncap;
-    return GAMMA_HIP_OK;
+    const size_t row = (size_t)h->raw_d * h->raw_esz();
+    const int64_t cap = h->raw_cap();
+    const int64_t ncap = std::max<int64_t>(std::max<int64_t>(need, cap + cap / 2), 1024);
+    return grow_array(h, "raw store", h->raw, (size_t)need * row, (size_t)ncap * row, (size_t)h->nraw * row);
 }
 
 // ---- float16 store: what the writers do instead of their copy --------------------------------------------------------
@@ -993,7 +674,7 @@ static int raw_narrow_rows_in(H* h, int64_t first, const int64_t* vids, int64_t 
         const int64_t m = std::min(piece, n - i0);
         GH_CHECK(h, hipMemcpyAsync(h->we_stage.p, vecs + i0 * d, (size_t)m * d * sizeof(float), hipMemcpyHostToDevice, h->wstream));
         gh::launch_raw_rows_narrow(h->wstream, h->we_stage.as<float>(), vids ? h->we_chk.as<int64_t>() + i0 : nullptr, first + i0, m, d,
-                                   h->raw_p, h->raw_et, h->raw_et == gh::ROW_SQ8 ? h->d_sq8_tab + 2 * (size_t)d : nullptr, nrows);
+                                   h->raw.p, h->raw_et, h->raw_et == gh::ROW_SQ8 ? h->d_sq8_tab + 2 * (size_t)d : nullptr, nrows);
     }
     GH_CHECK(h, hipGetLastError());
     return GAMMA_HIP_OK;
@@ -1017,7 +698,7 @@ int gamma_hip_raw_append(gamma_hip_index* h, int64_t n, const float* vecs) {
     GH_TRY(raw_narrow_check(h, n * h->raw_d, vecs));
     GH_CHECK(h, hipSetDevice(h->device));
     GH_TRY(raw_reserve(h, h->nraw + n));
-    GH_TRY(raw_rows_in(h, h->nraw, n, vecs, h->raw_cap));
+    GH_TRY(raw_rows_in(h, h->nraw, n, vecs, h->raw_cap()));
     GH_CHECK(h, hipStreamSynchronize(h->wstream));
     h->nraw += n;
     return GAMMA_HIP_OK;
@@ -1026,22 +707,14 @@ int gamma_hip_raw_append(gamma_hip_index* h, int64_t n, const float* vecs) {
 // the device's vid -> row table reaches vector id `hi`: a larger array and the whole mirror when it does not (rare: the
 // table grows by half; readers are drained first), nothing otherwise -- single entries go through k_raw_slot_scatter
 static int raw_slot_reserve(H* h, int64_t hi) {
-    if (hi < h->raw_slot_cap) return GAMMA_HIP_OK;
+    if (hi < h->raw_slot_cap()) return GAMMA_HIP_OK;
     const int64_t ncap = std::max<int64_t>(hi + 1 + (hi + 1) / 2, 1 << 16);
-    int32_t* np = nullptr;
-    if (h->wl) GH_CHECK(h, h->wl->exclusive());
-    GH_CHECK(h, hipMalloc((void**)&np, (size_t)ncap * sizeof(int32_t)));
-    hipError_t e = hipMemsetAsync(np, 0xff, (size_t)ncap * sizeof(int32_t), h->wstream);
-    if (e == hipSuccess && !h->h_raw_slot.empty())
-        e = hipMemcpyAsync(np, h->h_raw_slot.data(), h->h_raw_slot.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->wstream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->wstream);
-    if (e != hipSuccess) {
-        (void)hipFree(np);
-        GH_CHECK(h, e);
-    }
-    if (h->d_raw_slot) GH_CHECK(h, hipFree(h->d_raw_slot));
-    h->d_raw_slot = np;
-    h->raw_slot_cap = ncap;
+    // nothing is carried over on the device: the new table is -1 throughout, then the host mirror goes up -- so a table that
+    // fell behind its mirror (a raw_put or raw_drop that failed half way) is whole again after a growth
+    GH_TRY(grow_array(h, "raw slot table", h->d_raw_slot, (size_t)(hi + 1) * sizeof(int32_t), (size_t)ncap * sizeof(int32_t), 0, 0xff));
+    if (!h->h_raw_slot.empty())
+        GH_CHECK(h, hipMemcpyAsync(h->d_raw_slot, h->h_raw_slot.data(), h->h_raw_slot.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->wstream));
+    GH_CHECK(h, hipStreamSynchronize(h->wstream));
     return GAMMA_HIP_OK;
 }
 
@@ -1116,12 +789,12 @@ int gamma_hip_raw_put(gamma_hip_index* h, int64_t n, const int64_t* vids, const 
     h->raw_sparse = true;
     GH_CHECK(h, hipMemcpyAsync(h->we_chk.p, pairs.data(), (size_t)n * 2 * sizeof(int32_t), hipMemcpyHostToDevice, h->wstream));
     if (in_order) {
-        GH_TRY(raw_rows_in(h, h->nraw, n, vecs, h->raw_cap));
+        GH_TRY(raw_rows_in(h, h->nraw, n, vecs, h->raw_cap()));
     } else {
         GH_CHECK(h, hipMemcpyAsync(h->we_stage.p, vecs, (size_t)n * h->raw_d * sizeof(float), hipMemcpyHostToDevice, h->wstream));
-        gh::launch_raw_rows_scatter(h->wstream, h->we_stage.as<float>(), h->we_chk.as<int32_t>(), n, h->raw_d, h->raw_f32(), h->raw_cap);
+        gh::launch_raw_rows_scatter(h->wstream, h->we_stage.as<float>(), h->we_chk.as<int32_t>(), n, h->raw_d, h->raw_f32(), h->raw_cap());
     }
-    gh::launch_raw_slot_scatter(h->wstream, h->we_chk.as<int32_t>(), n, h->d_raw_slot, h->raw_slot_cap);
+    gh::launch_raw_slot_scatter(h->wstream, h->we_chk.as<int32_t>(), n, h->d_raw_slot, h->raw_slot_cap());
     GH_CHECK(h, hipGetLastError());
     GH_CHECK(h, hipStreamSynchronize(h->wstream));
     if ((int64_t)h->h_raw_slot.size() <= hi) h->h_raw_slot.resize((size_t)hi + 1, -1);
@@ -1158,7 +831,7 @@ int gamma_hip_raw_drop(gamma_hip_index* h, int64_t n, const int64_t* vids) {
     GH_CHECK(h, hipSetDevice(h->device));
     GH_CHECK(h, h->we_chk.ensure(pairs.size() * sizeof(int32_t)));
     GH_CHECK(h, hipMemcpyAsync(h->we_chk.p, pairs.data(), pairs.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->wstream));
-    gh::launch_raw_slot_scatter(h->wstream, h->we_chk.as<int32_t>(), (int64_t)pairs.size() / 2, h->d_raw_slot, h->raw_slot_cap);
+    gh::launch_raw_slot_scatter(h->wstream, h->we_chk.as<int32_t>(), (int64_t)pairs.size() / 2, h->d_raw_slot, h->raw_slot_cap());
     GH_CHECK(h, hipGetLastError());
     GH_CHECK(h, hipStreamSynchronize(h->wstream));
     return GAMMA_HIP_OK;
@@ -1170,24 +843,13 @@ int gamma_hip_raw_clear(gamma_hip_index* h) {
     WriteLock lk(h);
     GH_CHECK(h, hipSetDevice(h->device));
     GH_CHECK(h, lk.exclusive());   // the rows are given back: no search may be reading them
-    if (h->raw_vmm) {
-        h->raw_vm.unmap_all();   // (the address range stays reserved)
-        if (h->raw_vm.tainted) {   // unmapped without a fence: these addresses are not mapped again
-            h->vm_retired.push_back(std::move(h->raw_vm));
-            h->raw_vm = VmRange();
-            h->raw_vmm = false;
-            h->raw_p = nullptr;
-        }
-    } else if (h->raw_p) {
-        GH_CHECK(h, hipFree(h->raw_p));
-        h->raw_p = nullptr;
-    }
-    if (h->d_raw_slot) GH_CHECK(h, hipFree(h->d_raw_slot));
-    h->d_raw_slot = nullptr;
-    h->raw_slot_cap = 0;
+    // (a mapped store keeps its address range unless the unmap went without its fence; the handle has ONE list of ranges
+    //  that may not be mapped again, freed with it -- the arena's sets keep it, the raw store's ranges go there too)
+    h->raw.clear(&h->arena.retired);
+    h->d_raw_slot.clear(&h->arena.retired);
     std::vector<int32_t>().swap(h->h_raw_slot);
     std::vector<int32_t>().swap(h->raw_free);
-    h->nraw = h->raw_cap = h->raw_live = 0;
+    h->nraw = h->raw_live = 0;
     h->raw_sparse = false;
     return GAMMA_HIP_OK;
 }
@@ -1211,7 +873,7 @@ int gamma_hip_raw_write(gamma_hip_index* h, int64_t first_vid, int64_t n, const 
     GH_TRY(raw_narrow_check(h, n * h->raw_d, vecs));
     GH_CHECK(h, hipSetDevice(h->device));
     GH_TRY(raw_reserve(h, first_vid + n));
-    GH_TRY(raw_rows_in(h, first_vid, n, vecs, h->raw_cap));
+    GH_TRY(raw_rows_in(h, first_vid, n, vecs, h->raw_cap()));
     GH_CHECK(h, hipStreamSynchronize(h->wstream));
     h->nraw = std::max(h->nraw, first_vid + n);
     return GAMMA_HIP_OK;
@@ -1279,7 +941,7 @@ int gamma_hip_raw_gets(gamma_hip_index* h, int64_t n, const int64_t* vids, float
     std::vector<uint8_t> bb(h->raw_narrow() ? (size_t)n * row : 0);
     char* dst = h->raw_narrow() ? reinterpret_cast<char*>(bb.data()) : reinterpret_cast<char*>(out);
     for (int64_t i = 0; i < n; i++)
-        GH_CHECK(h, hipMemcpyAsync(dst + i * row, static_cast<const char*>(h->raw_p) + vids[i] * row, row, hipMemcpyDeviceToHost,
+        GH_CHECK(h, hipMemcpyAsync(dst + i * row, static_cast<const char*>(h->raw.p) + vids[i] * row, row, hipMemcpyDeviceToHost,
                                    h->wstream));
     GH_CHECK(h, hipStreamSynchronize(h->wstream));
     const size_t ne = (size_t)n * d;
@@ -1313,27 +975,18 @@ int gamma_hip_raw_stats(gamma_hip_index* h, int64_t* out4) {
     if (!h || !out4) return GAMMA_HIP_EINVAL;
     std::lock_guard<std::mutex> g(h->mu);
     out4[0] = h->nraw;
-    out4[1] = h->raw_cap;
-    out4[2] = h->raw_regrows;
-    out4[3] = h->raw_vmm ? 1 : 0;
+    out4[1] = h->raw_cap();
+    out4[2] = h->raw.regrows;
+    out4[3] = h->raw.mapped ? 1 : 0;
     return GAMMA_HIP_OK;
 }
 
 /* ---- delete bitmap ------------------------------------------------------------------- */
 static int bitmap_reserve(H* h, int64_t nbits) {
     size_t bytes = (((size_t)nbits >> 3) + 1 + 3) & ~(size_t)3;
-    if (bytes <= h->bitmap_cap_bytes) return GAMMA_HIP_OK;
-    size_t ncap = std::max(bytes, h->bitmap_cap_bytes * 2);
-    uint8_t* np = nullptr;
-    if (h->wl) GH_CHECK(h, h->wl->exclusive());   // the old bitmap is freed below
-    GH_CHECK(h, hipMalloc((void**)&np, ncap));
-    GH_CHECK(h, hipMemsetAsync(np, 0, ncap, h->wstream));
-    if (h->d_bitmap)
-        GH_CHECK(h, hipMemcpyAsync(np, h->d_bitmap, h->bitmap_cap_bytes, hipMemcpyDeviceToDevice, h->wstream));
-    GH_CHECK(h, hipStreamSynchronize(h->wstream));
-    if (h->d_bitmap) GH_CHECK(h, hipFree(h->d_bitmap));
-    h->d_bitmap = np;
-    h->bitmap_cap_bytes = ncap;
+    if (bytes <= h->d_bitmap.cap) return GAMMA_HIP_OK;
+    const size_t ncap = std::max(bytes, h->d_bitmap.cap * 2);
+    GH_TRY(grow_array(h, "bitmap", h->d_bitmap, bytes, ncap, h->d_bitmap.cap, 0));
     h->h_bitmap.resize(ncap, 0);
     return GAMMA_HIP_OK;
 }
@@ -1344,7 +997,7 @@ int gamma_hip_bitmap_upload(gamma_hip_index* h, const uint8_t* bitmap, int64_t n
     GH_CHECK(h, hipSetDevice(h->device));
     GH_TRY(bitmap_reserve(h, nbits));
     size_t bytes = ((size_t)nbits >> 3) + 1;  // bitmap::create, util/bitmap.cc:15-23
-    GH_CHECK(h, hipMemsetAsync(h->d_bitmap, 0, h->bitmap_cap_bytes, h->wstream));
+    GH_CHECK(h, hipMemsetAsync(h->d_bitmap, 0, h->d_bitmap.cap, h->wstream));
     GH_CHECK(h, hipMemcpyAsync(h->d_bitmap, bitmap, bytes, hipMemcpyHostToDevice, h->wstream));
     GH_CHECK(h, hipStreamSynchronize(h->wstream));
     std::fill(h->h_bitmap.begin(), h->h_bitmap.end(), 0);
@@ -1908,7 +1561,7 @@ int gamma_hip_ivfpq_arena_growth(gamma_hip_index* h, int64_t* out2) {
     if (!h || !out2) return GAMMA_HIP_EINVAL;
     std::lock_guard<std::mutex> g(h->mu);
     out2[0] = h->arena_regrows;
-    out2[1] = h->arena_vmm ? 1 : 0;
+    out2[1] = h->arena_vmm() ? 1 : 0;
     return GAMMA_HIP_OK;
 }
 

@@ -127,14 +127,7 @@ static int kmeans_run(gamma_hip_index* h, int d, int64_t n, const float* x_in, c
     }
     if (niter == 0) return GAMMA_HIP_OK;
     // device state: the training set (resident for the whole run), the centroids, their norms
-    DevBuf d_x, d_cen, d_cn, d_assign, d_dis, d_order, d_seg, d_has;
-    auto cleanup = [&]() {
-        for (DevBuf* b : {&d_x, &d_cen, &d_cn, &d_assign, &d_dis, &d_order, &d_seg, &d_has}) b->release();
-    };
-    struct Guard {
-        std::function<void()> f;
-        ~Guard() { f(); }
-    } guard{cleanup};
+    DevBuf d_x, d_cen, d_cn, d_assign, d_dis, d_order, d_seg, d_has;   // (freed on every way out)
     if (!dev_x) GH_CHECK(h, d_x.ensure((size_t)n * d * sizeof(float)));
     GH_CHECK(h, d_cen.ensure((size_t)k * d * sizeof(float)));
     GH_CHECK(h, d_cn.ensure((size_t)k * sizeof(float)));
@@ -480,13 +473,7 @@ int gamma_hip_opq_train(gamma_hip_index* h, int d, int64_t n, const float* x, in
     std::vector<float> A((size_t)d * d);
     for (size_t i = 0; i < A.size(); i++) A[i] = (float)Q[i];
 
-    DevBuf d_x, d_xp, d_rec, d_A, d_slice, d_cen, d_cn, d_assign, d_dis, d_P, d_C;
-    struct Guard {
-        std::vector<DevBuf*> b;
-        ~Guard() {
-            for (DevBuf* p : b) p->release();
-        }
-    } guard{{&d_x, &d_xp, &d_rec, &d_A, &d_slice, &d_cen, &d_cn, &d_assign, &d_dis, &d_P, &d_C}};
+    DevBuf d_x, d_xp, d_rec, d_A, d_slice, d_cen, d_cn, d_assign, d_dis, d_P, d_C;   // (freed on every way out)
     hipStream_t s = h->stream;
     {
         SearchLock lk(h);
