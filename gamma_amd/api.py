@@ -760,6 +760,16 @@ class GammaHip:
         self._ck(self.L.gamma_hip_coarse_filter_stats(self.h, _p(out, _lib.i64p)), "coarse_filter_stats")
         return dict(zip(["given_up", "queries", "backoffs", "fp32_calls_left"], [int(v) for v in out]))
 
+    def set_rerank_filter(self, mode=1):
+        """0: off; 1 (default): has_rank calls of 1024 queries and more re-rank behind the byte image of a dense fp32 raw
+        store; 2: every call that reaches the fused re-rank kernel.  Same results in all."""
+        self._ck(self.L.gamma_hip_set_rerank_filter(self.h, int(mode)), "set_rerank_filter")
+
+    def rerank_filter_stats(self):
+        out = np.zeros(5, np.int64)
+        self._ck(self.L.gamma_hip_rerank_filter_stats(self.h, _p(out, _lib.i64p)), "rerank_filter_stats")
+        return dict(zip(["candidates", "survivors", "calls", "backoffs", "image_rows"], [int(v) for v in out]))
+
     def flat_filter_stats(self, reset=False):
         """(filter passes launched, (query, row) pairs they scored, passes redone without the bound) of flat_search."""
         out = np.zeros(3, np.int64)

@@ -113,7 +113,7 @@ int gamma_hip_destroy(gamma_hip_index* h) {
     // the one-shot allocations of the model and the counters (never grown, never moved)
     void* ptrs[] = {h->d_list_rank, h->d_sq8_tab, h->d_cc, h->d_cc_norms, h->d_pqc, h->d_T2, h->d_list_mask, h->d_scan_codes,
                     h->d_tie_stats, h->d_t2max, h->bound_fb.d_stat, h->d_bin_cc, h->d_bin_stats, h->d_bf_stats, h->d_cc_img,
-                    h->d_cbf_stat, h->d_opq};
+                    h->d_cbf_stat, h->d_opq, h->rf.par, h->rf.d_stat};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     for (hipEvent_t e : h->event_pool) (void)hipEventDestroy(e);
@@ -125,6 +125,9 @@ int gamma_hip_destroy(gamma_hip_index* h) {
     if (h->cbf_copy_ev) (void)hipEventDestroy(h->cbf_copy_ev);
     if (h->pin_cbf_stat) (void)hipHostFree(h->pin_cbf_stat);
     if (h->pin_flat_over) (void)hipHostFree(h->pin_flat_over);
+    if (h->rf.copy_ev) (void)hipEventDestroy(h->rf.copy_ev);
+    if (h->rf.built) (void)hipEventDestroy(h->rf.built);
+    if (h->rf.pin_stat) (void)hipHostFree(h->rf.pin_stat);
     (void)hipStreamDestroy(h->stream);
     (void)hipStreamDestroy(h->wstream);
     if (h->side) (void)hipStreamDestroy(h->side);
@@ -209,6 +212,32 @@ int gamma_hip_coarse_filter_stats(gamma_hip_index* h, int64_t* out4) {
     out4[1] = (int64_t)v[1];
     out4[2] = h->cbf_backoffs;
     out4[3] = h->cbf_off_calls;
+    return GAMMA_HIP_OK;
+}
+
+int gamma_hip_set_rerank_filter(gamma_hip_index* h, int mode) {
+    if (!h || mode < 0 || mode > 2) return GAMMA_HIP_EINVAL;
+    SearchLock lk(h);
+    h->rf.mode = mode;
+    h->rf.off_calls = 0;
+    return GAMMA_HIP_OK;
+}
+
+int gamma_hip_rerank_filter_stats(gamma_hip_index* h, int64_t* out5) {
+    if (!h || !out5) return GAMMA_HIP_EINVAL;
+    SearchLock lk(h);
+    std::vector<unsigned long long> v(gh::kRerankFilterStatLines * 16, 0);
+    if (h->rf.d_stat) {
+        GH_CHECK(h, hipSetDevice(h->device));
+        GH_CHECK(h, hipStreamSynchronize(h->stream));
+        GH_CHECK(h, hipMemcpy(v.data(), h->rf.d_stat, gh::rerank_filter_stat_bytes(), hipMemcpyDeviceToHost));
+    }
+    out5[0] = (int64_t)h->rf.cand;
+    out5[1] = 0;
+    for (int i = 0; i < gh::kRerankFilterStatLines; i++) out5[1] += (int64_t)v[16 * i];
+    out5[2] = h->rf.calls;
+    out5[3] = h->rf.backoffs;
+    out5[4] = h->rf.on ? h->nraw : 0;
     return GAMMA_HIP_OK;
 }
 
@@ -337,6 +366,7 @@ int64_t gamma_hip_total_mem_bytes(gamma_hip_index* h) {
     int64_t b = 0;
     b += h->raw_cap() * h->raw_d * (int64_t)h->raw_esz() + h->raw_slot_cap() * (int64_t)sizeof(int32_t);
     if (h->d_sq8_tab) b += (int64_t)h->raw_d * 4 * (int64_t)sizeof(float);   // sq8 store: the decode and the encode table
+    b += (int64_t)(h->rf.rows.cap + h->rf.aux.cap);   // the re-rank filter's image, once a call has built it: d + 8 bytes per row
     b += (int64_t)h->d_bitmap.cap;
     for (auto& kv : h->fields) b += (int64_t)kv.second.d.cap;
     for (auto& kv : h->terms) b += (int64_t)(kv.second.d_off.cap + kv.second.d_tok.cap);

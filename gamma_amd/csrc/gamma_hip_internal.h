@@ -230,6 +230,33 @@ struct gamma_hip_index {
     // 90-142; a segment table would cost every gather an indirection, a mapped range costs nothing).  Fallback: a
     // geometric reallocation (DevArray::grow; raw.mapped / raw.regrows say which it is and how often it moved).
 
+    // Re-rank filter (rerank_filter.hip, gamma_hip_set_rerank_filter): a one-byte image of a dense fp32 store's rows, created by
+    // the first has_rank call that qualifies -- on the search stream, under mu, so beside no writer -- and kept in step by the dense
+    // writers from then on: they re-quantise the rows they wrote on the writer stream (behind `built`), in front of their wait.
+    // raw_clear releases it; it is never dumped or loaded.
+    // Feedback on the pattern of the coarse filter's: the kernel counts the survivors (gh::kRerankFilterStatLines words), the
+    // host the candidates it handed over; the survivor words come back through pinned memory behind an event, paired with the
+    // candidate count as of the launch in front of the copy, and while more than half of the recent candidates of one kind of
+    // call (metric, d, R, k) survived, the handle runs the plain kernel for 256 calls and probes again.  Same results either way.
+    struct RerankImage {
+        ghi::DevArray rows, aux;   // u8[cap][raw_d], {err, nrm}[cap]
+        float* par = nullptr;      // gh::rerank_image_par_bytes(raw_d): lo, Delta, |lo|
+        bool on = false;           // image rows [0, nraw) are those of the store's rows
+        hipEvent_t built = nullptr;
+        int mode = 1;              // 0 off, 1 calls of kAutoMinNq queries and more, 2 every call
+        static constexpr int kAutoMinNq = 1024;
+        unsigned long long* d_stat = nullptr;
+        unsigned long long* pin_stat = nullptr;
+        unsigned long long seen[2] = {0, 0};           // {survivors, candidates} at the last decision
+        unsigned long long cand = 0, cand_at_copy = 0;   // candidates handed to the filter so far; as of the copy under way / landed
+        hipEvent_t copy_ev = nullptr;
+        bool copy_pending = false;
+        uint64_t sig = 0;
+        int off_calls = 0;   // plain calls left before the next probe
+        int64_t backoffs = 0, calls = 0;
+        int64_t cap_rows(int d) const { return d > 0 ? (int64_t)std::min(rows.cap / (size_t)d, aux.cap / (2 * sizeof(float))) : 0; }
+    } rf;
+
     // numeric scalar columns (on-device range filters)
     struct Column {
         int dtype = 0;
@@ -624,6 +651,9 @@ inline int publish_meta(H* h) {
     h->max_list_len = mx;
     return GAMMA_HIP_OK;
 }
+
+// gamma_hip_store.cpp: the re-rank image's arrays hold `need` rows (the caller holds mu)
+int rerank_image_reserve(H* h, int64_t need);
 
 inline size_t field_elem_size(int dtype) {
     return dtype == GAMMA_HIP_FIELD_INT || dtype == GAMMA_HIP_FIELD_FLOAT ? 4 : 8;

@@ -692,6 +692,86 @@ int ivfpq_stage_a(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int
     return GAMMA_HIP_OK;
 }
 
+// ---- the re-rank filter (rerank_filter.hip; the handle's rf) ---------------------------------------------------------------
+// Does this fused re-rank run behind the filter?  Only over a dense fp32 store with rows of a multiple of 16 floats; the first
+// call that qualifies builds the image (one pass for the per-dimension ranges, one that quantises: on the search stream, the
+// caller holds mu so no writer is at work).  The handle's feedback may turn a call down: coarse quantizer's rule and plumbing.
+static int rerank_filter_begin(H* h, bool l2, int nq, int R, int k, bool* use) {
+    H::RerankImage& rf = h->rf;
+    *use = false;
+    if (rf.mode == 0 || (rf.mode == 1 && nq < H::RerankImage::kAutoMinNq)) return GAMMA_HIP_OK;
+    if (!h->raw_f32() || h->raw_sparse || h->nraw <= 0 || !gh::rerank_filter_shape_ok(h->raw_d, R, k)) return GAMMA_HIP_OK;
+    hipStream_t s = h->stream;
+    const int d = h->raw_d;
+    if (!rf.on) {
+        if (!rf.par) {
+            GH_CHECK(h, hipMalloc((void**)&rf.par, gh::rerank_image_par_bytes(gh::kRerankFilterMaxD)));
+            GH_CHECK(h, hipMalloc((void**)&rf.d_stat, gh::rerank_filter_stat_bytes()));
+            GH_CHECK(h, hipMemsetAsync(rf.d_stat, 0, gh::rerank_filter_stat_bytes(), s));
+            GH_CHECK(h, hipHostMalloc((void**)&rf.pin_stat, gh::rerank_filter_stat_bytes(), hipHostMallocDefault));
+            memset(rf.pin_stat, 0, gh::rerank_filter_stat_bytes());
+            GH_CHECK(h, hipEventCreateWithFlags(&rf.copy_ev, hipEventDisableTiming));
+            GH_CHECK(h, hipEventCreateWithFlags(&rf.built, hipEventDisableTiming));
+        }
+        GH_TRY(rerank_image_reserve(h, h->raw_cap()));
+        gh::launch_rerank_image_params(s, h->raw_f32(), h->nraw, d, rf.par);
+        gh::launch_rerank_image_rows(s, h->raw_f32(), nullptr, 0, h->nraw, d, rf.par, rf.rows.as<uint8_t>(), rf.aux.as<float>(), h->nraw);
+        GH_CHECK(h, hipGetLastError());
+        GH_CHECK(h, hipEventRecord(rf.built, s));
+        rf.on = true;
+    }
+    const uint64_t sig = ((uint64_t)R << 40) ^ ((uint64_t)k << 20) ^ ((uint64_t)d << 1) ^ (l2 ? 1u : 0u) ^ (1ull << 63);
+    auto sums = [&](unsigned long long* out2) {
+        out2[0] = 0;
+        for (int i = 0; i < gh::kRerankFilterStatLines; i++) out2[0] += rf.pin_stat[16 * i];
+        out2[1] = rf.cand_at_copy;   // (the copy stands behind the launch that brought the candidates to this count)
+    };
+    if (sig != rf.sig) {   // another kind of call: what was learnt does not carry over
+        rf.sig = sig;
+        rf.off_calls = 0;
+        if (rf.copy_pending) {
+            (void)hipEventSynchronize(rf.copy_ev);
+            rf.copy_pending = false;
+        }
+        sums(rf.seen);
+    }
+    *use = true;
+    if (rf.off_calls > 0) {
+        if (--rf.off_calls > 0) *use = false;   // (0: this call probes again)
+    } else {
+        if (rf.copy_pending && hipEventQuery(rf.copy_ev) == hipSuccess) rf.copy_pending = false;
+        else if (rf.copy_pending) (void)hipGetLastError();
+        if (!rf.copy_pending) {   // the words are read only behind the copy that wrote them
+            unsigned long long now[2];
+            sums(now);
+            const unsigned long long dn = now[1] - rf.seen[1], du = std::min(now[0] - rf.seen[0], dn);
+            if (dn >= 4096) {
+                rf.seen[0] = now[0];
+                rf.seen[1] = now[1];
+                if (2 * du > dn) {
+                    rf.off_calls = 256;
+                    rf.backoffs++;
+                    *use = false;
+                }
+            }
+        }
+    }
+    return GAMMA_HIP_OK;
+}
+// behind a filtered launch: the counters as of this call for a later call's decision (one copy in flight at a time)
+static int rerank_filter_end(H* h, int64_t candidates) {
+    H::RerankImage& rf = h->rf;
+    rf.calls++;
+    rf.cand += (unsigned long long)candidates;
+    if (!rf.copy_pending) {
+        GH_CHECK(h, hipMemcpyAsync(rf.pin_stat, rf.d_stat, gh::rerank_filter_stat_bytes(), hipMemcpyDeviceToHost, h->stream));
+        rf.cand_at_copy = rf.cand;
+        GH_CHECK(h, hipEventRecord(rf.copy_ev, h->stream));
+        rf.copy_pending = true;
+    }
+    return GAMMA_HIP_OK;
+}
+
 // ---- stage B: compute_dis (gamma_index_ivfpq.cc:642-697) ------------------------------
 int ivfpq_stage_b(H* h, const gamma_hip_search_params* p, int nq, const float* d_x, int R, int k,
                   const float* cand_dis, const int64_t* cand_ids, float* d_distances,
@@ -761,8 +841,17 @@ int ivfpq_stage_b(H* h, const gamma_hip_search_params* p, int nq, const float* d
         if (h->raw_sparse) return fail(h, GAMMA_HIP_EUNSUPPORTED, "has_rank on a handle that holds its shard's raw rows only: the exact distances travel with the candidates (gamma_hip_ivfpq_shard_exact / _merge_rerank_exact)");
         if (R <= 1024 && (nq >= 256 || ties)) {
             // one fused kernel: exact distances + top-k + output
-            gh::launch_rerank_topk(s, l2, d_x, nq, h->d, raw_rows_ref(h), h->nraw, cand_ids, R, k, p->min_score,
-                                   p->max_score, neutral, d_distances, d_labels, qperm, ties ? &tf : nullptr);
+            bool filt = false;
+            GH_TRY(rerank_filter_begin(h, l2, nq, R, k, &filt));
+            if (filt) {
+                gh::launch_rerank_topk_filtered(s, l2, d_x, nq, h->d, h->raw_f32(), h->nraw, h->rf.rows.as<uint8_t>(),
+                                                h->rf.aux.as<float>(), h->rf.par, cand_ids, R, k, p->min_score, p->max_score, neutral,
+                                                d_distances, d_labels, qperm, ties ? &tf : nullptr, h->rf.d_stat);
+                GH_TRY(rerank_filter_end(h, (int64_t)nq * R));
+            } else {
+                gh::launch_rerank_topk(s, l2, d_x, nq, h->d, raw_rows_ref(h), h->nraw, cand_ids, R, k, p->min_score,
+                                       p->max_score, neutral, d_distances, d_labels, qperm, ties ? &tf : nullptr);
+            }
             if (ties && tie_mode == 1) replay();
             GH_CHECK(h, hipGetLastError());
             return GAMMA_HIP_OK;

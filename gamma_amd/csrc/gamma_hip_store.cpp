@@ -285,6 +285,18 @@ std::vector<int> centroid_rank(const float* cc, int nlist, int d) {
     return rank;
 }
 
+// ---- the re-rank filter's image of a dense fp32 store (rerank_filter.hip; the handle's rf) ------------------------------------
+// its arrays hold `need` rows: a geometric reallocation that carries the image of the rows present (DevArray::grow)
+int rerank_image_reserve(H* h, int64_t need) {
+    const size_t d = (size_t)h->raw_d, ax = 2 * sizeof(float);
+    const int64_t cap = h->rf.cap_rows(h->raw_d);
+    if (need <= cap) return GAMMA_HIP_OK;
+    const int64_t ncap = std::max<int64_t>(std::max<int64_t>(need, cap + cap / 2), 1024);
+    const size_t keep = h->rf.on ? (size_t)h->nraw : 0;   // (a new image: nothing to carry)
+    GH_TRY(grow_array(h, "re-rank image", h->rf.rows, (size_t)need * d, (size_t)ncap * d, keep * d));
+    return grow_array(h, "re-rank image", h->rf.aux, (size_t)need * ax, (size_t)ncap * ax, keep * ax);
+}
+
 }  // namespace ghi
 
 using namespace ghi;
@@ -472,7 +484,20 @@ static int raw_reserve(H* h, int64_t need) {
     const size_t row = (size_t)h->raw_d * h->raw_esz();
     const int64_t cap = h->raw_cap();
     const int64_t ncap = std::max<int64_t>(std::max<int64_t>(need, cap + cap / 2), 1024);
-    return grow_array(h, "raw store", h->raw, (size_t)need * row, (size_t)ncap * row, (size_t)h->nraw * row);
+    GH_TRY(grow_array(h, "raw store", h->raw, (size_t)need * row, (size_t)ncap * row, (size_t)h->nraw * row));
+    return h->rf.on ? rerank_image_reserve(h, need) : GAMMA_HIP_OK;   // the image grows with its store
+}
+
+// ---- the re-rank filter's image of a dense fp32 store (rerank_filter.hip; the handle's rf; its growth: rerank_image_reserve) ----
+// what a dense writer does behind its row copies, on the writer stream: the image rows of store rows first, first + 1, ..
+// (d_vids == nullptr) or d_vids[i] (device memory), so that an image row is in place whenever its row is
+static int raw_image_rows_in(H* h, int64_t first, const int64_t* d_vids, int64_t n, int64_t nrows) {
+    if (!h->rf.on) return GAMMA_HIP_OK;
+    GH_CHECK(h, hipStreamWaitEvent(h->wstream, h->rf.built, 0));   // the parameters come from the search stream
+    gh::launch_rerank_image_rows(h->wstream, h->raw_f32(), d_vids, first, n, h->raw_d, h->rf.par, h->rf.rows.as<uint8_t>(),
+                                 h->rf.aux.as<float>(), std::min(nrows, h->rf.cap_rows(h->raw_d)));
+    GH_CHECK(h, hipGetLastError());
+    return GAMMA_HIP_OK;
 }
 
 // ---- float16 store: what the writers do instead of their copy --------------------------------------------------------
@@ -699,6 +724,7 @@ int gamma_hip_raw_append(gamma_hip_index* h, int64_t n, const float* vecs) {
     GH_CHECK(h, hipSetDevice(h->device));
     GH_TRY(raw_reserve(h, h->nraw + n));
     GH_TRY(raw_rows_in(h, h->nraw, n, vecs, h->raw_cap()));
+    GH_TRY(raw_image_rows_in(h, h->nraw, nullptr, n, h->raw_cap()));
     GH_CHECK(h, hipStreamSynchronize(h->wstream));
     h->nraw += n;
     return GAMMA_HIP_OK;
@@ -847,6 +873,9 @@ int gamma_hip_raw_clear(gamma_hip_index* h) {
     //  that may not be mapped again, freed with it -- the arena's sets keep it, the raw store's ranges go there too)
     h->raw.clear(&h->arena.retired);
     h->d_raw_slot.clear(&h->arena.retired);
+    h->rf.rows.clear(&h->arena.retired);   // the image goes with its rows; the next call that qualifies builds a new one
+    h->rf.aux.clear(&h->arena.retired);
+    h->rf.on = false;
     std::vector<int32_t>().swap(h->h_raw_slot);
     std::vector<int32_t>().swap(h->raw_free);
     h->nraw = h->raw_live = 0;
@@ -874,6 +903,7 @@ int gamma_hip_raw_write(gamma_hip_index* h, int64_t first_vid, int64_t n, const 
     GH_CHECK(h, hipSetDevice(h->device));
     GH_TRY(raw_reserve(h, first_vid + n));
     GH_TRY(raw_rows_in(h, first_vid, n, vecs, h->raw_cap()));
+    GH_TRY(raw_image_rows_in(h, first_vid, nullptr, n, h->raw_cap()));
     GH_CHECK(h, hipStreamSynchronize(h->wstream));
     h->nraw = std::max(h->nraw, first_vid + n);
     return GAMMA_HIP_OK;
@@ -887,6 +917,7 @@ int gamma_hip_raw_update(gamma_hip_index* h, int64_t vid, const float* vec) {
     GH_TRY(raw_narrow_check(h, h->raw_d, vec));
     GH_CHECK(h, hipSetDevice(h->device));
     GH_TRY(raw_rows_in(h, vid, 1, vec, h->nraw));
+    GH_TRY(raw_image_rows_in(h, vid, nullptr, 1, h->nraw));
     GH_CHECK(h, hipStreamSynchronize(h->wstream));
     return GAMMA_HIP_OK;
 }
@@ -919,6 +950,11 @@ int gamma_hip_raw_update_batch(gamma_hip_index* h, int64_t n, const int64_t* vid
         if (vids[i] < 0 || vids[i] >= h->nraw) continue;
         GH_CHECK(h, hipMemcpyAsync(h->raw_f32() + vids[i] * h->raw_d, vecs + i * h->raw_d, (size_t)h->raw_d * sizeof(float),
                                    hipMemcpyHostToDevice, h->wstream));
+    }
+    if (h->rf.on) {   // (a vid named twice: both entries quantise the row as the last copy left it)
+        GH_CHECK(h, h->we_chk.ensure((size_t)n * sizeof(int64_t)));
+        GH_CHECK(h, hipMemcpyAsync(h->we_chk.p, vids, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, h->wstream));
+        GH_TRY(raw_image_rows_in(h, 0, h->we_chk.as<int64_t>(), n, h->nraw));
     }
     GH_CHECK(h, hipStreamSynchronize(h->wstream));
     return GAMMA_HIP_OK;

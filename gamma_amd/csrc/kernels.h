@@ -473,6 +473,25 @@ void launch_rerank_topk(hipStream_t s, bool l2, const float* x, int nq, int d, c
                         float max_score, float neutral, float* distances, int64_t* labels,
                         const int* qperm = nullptr,   // qperm: run the queries in this order (speed only)
                         const TieFlags* ties = nullptr);
+// rerank_filter.hip: the same re-rank over a dense fp32 store with a one-byte image of its rows in front -- most candidates are
+// proven out of the first k + 1 from the image, the survivors get launch_rerank_topk's arithmetic.  Same outputs, same flags.
+// The margin of the bound (derivation: the file's header) and the longest row the kernel stages.
+constexpr float kRerankFilterMargin = 3.0517578125e-05f;   // M = 2^-15
+constexpr int kRerankFilterMaxD = 1536;
+constexpr int kRerankFilterStatLines = 64;
+inline size_t rerank_filter_stat_bytes() { return (size_t)kRerankFilterStatLines * 16 * sizeof(unsigned long long); }
+bool rerank_filter_shape_ok(int d, int R, int k);   // d % 16 == 0, d <= kRerankFilterMaxD, R <= 1024, min(k + 1, R) <= 64
+inline size_t rerank_image_par_bytes(int d) { return ((size_t)3 * d + 2) * sizeof(float); }
+// par (rerank_image_par_bytes): the image's parameters from the n rows present -- lo[d], Delta, |lo| -- all on the device
+void launch_rerank_image_params(hipStream_t s, const float* rows, int64_t n, int d, float* par);
+// image rows (img: u8[d], aux: {err, nrm} each) of the store's rows first + i, or vids[i] (outside [0, nrows): skipped), i < n
+void launch_rerank_image_rows(hipStream_t s, const float* rows, const int64_t* vids, int64_t first, int64_t n, int d, const float* par,
+                              uint8_t* img, float* aux, int64_t nrows);
+// stat: kRerankFilterStatLines x 16 words; the queries add their survivors to word 0 of a line each (the sum is the count)
+void launch_rerank_topk_filtered(hipStream_t s, bool l2, const float* x, int nq, int d, const float* raw, int64_t nraw, const uint8_t* img,
+                                 const float* aux, const float* par, const int64_t* cand_ids, int R, int k, float min_score,
+                                 float max_score, float neutral, float* distances, int64_t* labels, const int* qperm,
+                                 const TieFlags* ties, unsigned long long* stat);
 // what k_tie_replay needs to redo one query (ties.hip)
 struct TieReplayArgs {
     const int* list;              // flagged queries, *count of them

@@ -13,6 +13,7 @@
 #include "flat_rows_dev.h"
 #include "kernels.h"
 #include "rerank_dev.h"
+#include "rerank_topk_dev.h"
 #include "scan_dev.h"
 
 namespace gh {
@@ -411,10 +412,16 @@ __global__ __launch_bounds__(256) void k_rerank_topk(const float* __restrict__ x
             const float* va = raw + (la ? ida : 0) * 128 + l;
             const float* vb = raw + (lb ? idb : 0) * 128 + l;
             float fa[16], fb[16];
+#if GH_RERANK_TIMING == 1   // timing build (results invalid): the row loads replaced by a constant
+#pragma unroll
+            for (int u = 0; u < 16; u++) fa[u] = (float)(ra + u), fb[u] = (float)(rb + u);
+            (void)va, (void)vb;
+#else
 #pragma unroll
             for (int u = 0; u < 16; u++) fa[u] = va[8 * u];
 #pragma unroll
             for (int u = 0; u < 16; u++) fb[u] = vb[8 * u];
+#endif
             float a = 0.f, b = 0.f;
 #pragma unroll
             for (int u = 0; u < 16; u++) {
@@ -438,92 +445,8 @@ __global__ __launch_bounds__(256) void k_rerank_topk(const float* __restrict__ x
         rounds_of_32();
     }
     if (tf.list && threadIdx.x == 0) s_tie = tf.cut ? tf.cut[q] : 0;
-    // Only the first k + 1 items are read below (the k results; whether two of the first k + 1 exact distances are equal).  Up to
-    // k + 1 = 64: every 64-item run of the R items is sorted by a wave (DPP bitonic stages), the first k + 1 items of a run get
-    // their rank in the whole -- their index in the run + the number of smaller items in every other run (binary searches) --
-    // and the items of rank < k + 1 go to their place: the same first k + 1 entries the full rank sort leaves.  (The full sort
-    // ranks all R items against all R: 200 LDS reads and 600 vector instructions per thread, ~100 of the kernel's 283 us at C3.)
-    const int K1 = min(k + 1, R);
-    if (K1 <= 64) {   // (uniform)
-        const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-        const int nruns = (R + 63) >> 6;   // <= 16
-        __syncthreads();   // every distance is in s_it
-        for (int run = w; run < nruns; run += 4) {
-            const int idx = run * 64 + lane;
-            s_it[idx] = wave_sort64(idx < R ? s_it[idx] : ~0ull);   // (padding sorts last; s_it holds 1024 items)
-        }
-        __syncthreads();
-        unsigned long long xr[4];
-        int rkk[4];
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const int run = w + 4 * u;
-            xr[u] = ~0ull;
-            rkk[u] = K1;
-            if (run < nruns) {   // (uniform)
-                const unsigned long long x = s_it[run * 64 + lane];
-                int rank = lane;
-                if (lane < K1 && x != ~0ull) {
-                    for (int o = 0; o < nruns; o++) {
-                        if (o == run) continue;
-                        const unsigned long long* ro = s_it + o * 64;
-                        int lo = 0, n2 = 64;
-#pragma unroll
-                        for (int st = 0; st < 7; st++) {   // number of items of run o smaller than x
-                            if (n2 > 0) {
-                                const int half = n2 >> 1;
-                                if (ro[lo + half] < x) {
-                                    lo += half + 1;
-                                    n2 -= half + 1;
-                                } else {
-                                    n2 = half;
-                                }
-                            }
-                        }
-                        rank += lo;
-                        if (rank >= K1) break;
-                    }
-                    xr[u] = x;
-                    rkk[u] = rank;
-                }
-            }
-        }
-        __syncthreads();   // every search has read the runs
-#pragma unroll
-        for (int u = 0; u < 4; u++)
-            if (rkk[u] < K1) s_it[rkk[u]] = xr[u];
-        __syncthreads();
-    } else {
-        block_rank_sort<256, 4>(s_it, R);   // R distinct items (the rank field differs)
-    }
-    if (tf.list) {
-        // exact ties (ties.hip): two of the first k+1 exact distances equal -- their order, or which of them
-        // stays inside the k, is decided by the reference's heaps -- or the top-R cut went through a tie
-        for (int i = threadIdx.x; i < k && i + 1 < R; i += 256) {
-            const uint32_t ka = (uint32_t)(s_it[i] >> 32), kb = (uint32_t)(s_it[i + 1] >> 32);
-            if (ka == kb && ka != (L2 ? f2key(sentinel) : ~f2key(sentinel))) s_tie = 1;   // benign race: same value
-        }
-        __syncthreads();
-        if (threadIdx.x == 0 && s_tie) {
-            tf.list[atomicAdd(tf.count, 1)] = q;
-            if (tf.stats) atomicAdd(tf.stats + 2, 1ull);
-        }
-    }
-    for (int i = threadIdx.x; i < k; i += 256) {
-        float val = neutral;
-        int64_t id = -1;
-        if (i < R) {
-            const unsigned long long it = s_it[i];
-            const uint32_t key = (uint32_t)(it >> 32);
-            const float dv = key2f(L2 ? key : ~key);
-            if (dv != sentinel) {
-                val = dv;
-                id = s_id[(uint32_t)it];
-            }
-        }
-        distances[(int64_t)q * k + i] = val;
-        labels[(int64_t)q * k + i] = id;
-    }
+    rerank_first_k(s_it, R, min(k + 1, R));
+    rerank_topk_out<L2>(s_it, s_id, &s_tie, q, R, k, neutral, distances, labels, tf);
 }
 namespace {
 template <typename ROW>

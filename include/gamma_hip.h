@@ -175,6 +175,16 @@ int gamma_hip_set_coarse_fused(gamma_hip_index* h, int on, int list_cap);
  * out4: {queries the bf16 chain handed to the repair kernels, queries it ran on, times the handle switched itself to
  * the fp32 filter, fp32 calls left before it probes the bf16 filter again} */
 int gamma_hip_coarse_filter_stats(gamma_hip_index* h, int64_t* out4);
+/* The exact re-rank (has_rank) over a dense fp32 raw store whose rows are a multiple of 16 floats (up to 1536) can run behind
+ * a filter: a one-byte image of the rows (d + 8 bytes per row, built by the first call that qualifies, kept in step by
+ * raw_append / _write / _update / _update_batch, released by raw_clear, counted in gamma_hip_total_mem_bytes once it exists)
+ * proves most of a query's recall_num candidates out of its first k + 1, and only the others are measured against their
+ * fp32 rows (csrc/rerank_filter.hip).  Results are the same bit for bit.  mode: 0 = off; 1 (default) = calls of 1024 queries
+ * and more; 2 = every call that reaches the fused re-rank kernel.  While more than half of the recent candidates survive, the
+ * handle runs the plain kernel for 256 calls and probes again.
+ * out5: {candidates the filter saw, candidates that survived it, calls it ran in, times the handle backed off, image rows} */
+int gamma_hip_set_rerank_filter(gamma_hip_index* h, int mode);
+int gamma_hip_rerank_filter_stats(gamma_hip_index* h, int64_t* out5);
 /* Flat search (GammaFLATIndex::Search, index/impl/gamma_index_flat.cc:118-300) scores every row; here the passes behind the
  * first row chunk run a bf16 filter on the matrix pipe and only its survivors get the reference's arithmetic
  * (csrc/flat_mfma.hip), so results are the reference's bit for bit.  No handle, no device call:
