@@ -87,8 +87,7 @@ int gamma_hip_destroy(gamma_hip_index* h) {
     if (h->side) (void)hipStreamSynchronize(h->side);
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
     if (h->ev_join) (void)hipEventDestroy(h->ev_join);
-    for (hipEvent_t& e : h->ev_call)
-        if (e) (void)hipEventDestroy(e);
+    h->call_slots.release();
     for (auto& sl : h->hslot) {
         if (sl.pin) (void)hipHostFree(sl.pin);
         if (sl.ev_up) (void)hipEventDestroy(sl.ev_up);
@@ -124,7 +123,6 @@ int gamma_hip_destroy(gamma_hip_index* h) {
     if (h->bound_fb.pin_stat) (void)hipHostFree(h->bound_fb.pin_stat);
     if (h->cbf_copy_ev) (void)hipEventDestroy(h->cbf_copy_ev);
     if (h->pin_cbf_stat) (void)hipHostFree(h->pin_cbf_stat);
-    if (h->pin_flat_over) (void)hipHostFree(h->pin_flat_over);
     if (h->rf.copy_ev) (void)hipEventDestroy(h->rf.copy_ev);
     if (h->rf.built) (void)hipEventDestroy(h->rf.built);
     if (h->rf.pin_stat) (void)hipHostFree(h->rf.pin_stat);

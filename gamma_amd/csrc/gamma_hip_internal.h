@@ -24,6 +24,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "call_slots.h"
 #include "dev_mem.h"
 #include "kernels.h"
 
@@ -132,10 +133,9 @@ struct gamma_hip_index {
     // next call's or chunk's pair offsets) -- its latency hides behind the next coarse quantizer and query tables
     hipEvent_t ev_rfork = nullptr, ev_rdone = nullptr;
     bool defer_replay = false, defer_now = false, replay_pending = false;
-    // gamma_hip_ivfpq_search_device_wait: completion events of the calls in flight (rotating; a waiter that finds its slot
-    // re-recorded by a later call waits for that one -- later implies earlier on in-order streams)
-    hipEvent_t ev_call[4] = {nullptr, nullptr, nullptr, nullptr};
-    unsigned call_seq = 0;
+    // the _wait entries: completion event and pinned overflow word of every call in flight, each owned by its call from the
+    // take under the search lock until its waiter has read the word (call_slots.h)
+    ghi::CallSlots call_slots;
     // large host-buffer IVFPQ calls from several client threads (ivfpq_search_host_overlap): a call's queries go up on
     // `up_stream` into its own staging slot BEFORE it takes the search lock, its results come down behind its tie replay
     // on the side stream into pinned memory, and the caller waits for its own event with the handle already free
@@ -160,8 +160,8 @@ struct gamma_hip_index {
     bool bank_used[2] = {false, false};
     bool replay_is_flat = false;
     // (the flat call's "did a survivor list overflow" word is read by the host; a _wait call reads it AFTER its completion
-    //  event, with the handle free, from one of four pinned words, and redoes the call without a bound in the rare yes)
-    int* pin_flat_over = nullptr;
+    //  event, with the handle free, from the pinned word of its own slot (call_slots), and redoes the call without a bound in
+    //  the rare yes)
     int* flat_over_dst = nullptr;    // set by the _wait entry for the call under way
     int flat_over_passes = 0;        // filter passes of the call under way whose overflow word the _wait entry reads later
     bool flat_no_bound = false;

@@ -468,41 +468,44 @@ int gamma_hip_flat_search_device(gamma_hip_index* h, const gamma_hip_search_para
     return flat_search_device_locked(h, p, nq, d_x, k, d_distances, d_labels);
 }
 
+// the slot's event behind everything of the call that was just enqueued
+// (the main stream carries the copy of the overflow word; the side stream, if a replay is pending, the last writes)
+static int arm_behind_call(H* h, CallSlot* slot) {
+    if (h->replay_pending) {
+        GH_CHECK(h, hipEventRecord(h->ev_rfork, h->stream));
+        GH_CHECK(h, hipStreamWaitEvent(h->side2, h->ev_rfork, 0));
+    }
+    GH_CHECK(h, CallSlots::arm(slot, h->replay_pending ? h->side2 : h->stream));
+    return GAMMA_HIP_OK;
+}
+
 int gamma_hip_flat_search_device_wait(gamma_hip_index* h, const gamma_hip_search_params* p, int nq,
                                       const float* d_x, int k, float* d_distances, int64_t* d_labels) {
     if (!h) return GAMMA_HIP_EINVAL;
-    hipEvent_t ev = nullptr;
-    int* over = nullptr;
+    CallTicket t(h->call_slots);   // this call's event and overflow word: its own until it has read the word (call_slots.h)
     int over_passes = 0;   // filter passes of this call: redone if its overflow word is set
     {
         SearchLock lk(h);
         GH_CHECK(h, hipSetDevice(h->device));
-        const unsigned slot = h->call_seq++ & 3u;
-        if (!h->ev_call[slot]) GH_CHECK(h, hipEventCreateWithFlags(&h->ev_call[slot], hipEventDisableTiming));
-        ev = h->ev_call[slot];
-        if (!h->pin_flat_over) {
-            GH_CHECK(h, hipHostMalloc((void**)&h->pin_flat_over, 4 * sizeof(int), hipHostMallocDefault));
-            memset(h->pin_flat_over, 0, 4 * sizeof(int));
-        }
-        over = h->pin_flat_over + slot;
-        *over = 0;
+        GH_CHECK(h, t.take());
         h->defer_now = h->side2 != nullptr;
-        h->flat_over_dst = over;
+        h->flat_over_dst = t.slot()->over;
         h->flat_over_passes = 0;
-        const int rc = flat_search_device_locked(h, p, nq, d_x, k, d_distances, d_labels);
+        int rc = flat_search_device_locked(h, p, nq, d_x, k, d_distances, d_labels);
         over_passes = h->flat_over_passes;
         h->defer_now = false;
         h->flat_over_dst = nullptr;
-        if (rc != GAMMA_HIP_OK) return rc;
-        // (the main stream carries the copy of the overflow word; the side stream, if a replay is pending, the last writes)
-        if (h->replay_pending) {
-            GH_CHECK(h, hipEventRecord(h->ev_rfork, h->stream));
-            GH_CHECK(h, hipStreamWaitEvent(h->side2, h->ev_rfork, 0));
+        if (rc == GAMMA_HIP_OK) rc = arm_behind_call(h, t.slot());
+        if (rc != GAMMA_HIP_OK) {
+            // (the copy into the slot's word may be on its way already: the slot goes back to the pool only behind it)
+            (void)hipStreamSynchronize(h->stream);
+            return rc;
         }
-        GH_CHECK(h, hipEventRecord(ev, h->replay_pending ? h->side2 : h->stream));
     }
-    if (hipEventSynchronize(ev) != hipSuccess) return GAMMA_HIP_EDEVICE;
-    if (*over) {   // a survivor list overflowed (adversarial data): the call again without a bound, the plain way
+    if (CallSlots::wait(t.slot()) != hipSuccess) return GAMMA_HIP_EDEVICE;
+    const int over = CallSlots::word(t.slot());
+    t.done();   // (the slot goes to the next call before the redo, if there is one)
+    if (over) {   // a survivor list overflowed (adversarial data): the call again without a bound, the plain way
         SearchLock lk(h);
         h->ff_redone.fetch_add(over_passes, std::memory_order_relaxed);
         h->flat_no_bound = true;

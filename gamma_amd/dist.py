@@ -102,8 +102,10 @@ class HipShardBackend:
             if len(mine):
                 order = mine[np.argsort(lno[mine], kind="stable")]
                 lists, counts = np.unique(lno[order], return_counts=True)
-                self.g.add_keys_batch(lists, counts, (first_vid + order).astype(np.int64), np.asarray(codes)[order])
+                # store first, index second (the reference stores a vector before it indexes it): a put that fails leaves no
+                # listed vector without its row, which shard_exact would drop from the re-ranked results
                 self.g.raw_put((first_vid + mine).astype(np.int64), vecs[mine])
+                self.g.add_keys_batch(lists, counts, (first_vid + order).astype(np.int64), np.asarray(codes)[order])
             return
         self.g.raw_append(vecs)
         self.g.add(vecs, first_vid)

@@ -727,7 +727,10 @@ int gamma_hip_set_deferred_replay(gamma_hip_index* h, int on);
  * stream and the NEXT caller's coarse quantizer, query tables and scan run beside it, exactly as under
  * gamma_hip_set_deferred_replay, with no contract on the callers but "wait for your own call".  Two client threads
  * alternating on one handle thus hide each other's replay tail; one thread alone gets what _search_device +
- * gamma_hip_synchronize gives.  d_x must stay untouched until the call returns. */
+ * gamma_hip_synchronize gives.  d_x must stay untouched until the call returns.
+ * Any number of callers may overlap, here and in gamma_hip_flat_search_device_wait: a call owns its completion event (and the
+ * flat call its overflow word) from the moment it is enqueued until its own waiter is through with them; the handle creates
+ * one such pair per call in flight at the same time and reuses them (call_slots.h). */
 int gamma_hip_ivfpq_search_device_wait(gamma_hip_index* h, const gamma_hip_search_params* p, int nq,
                                        const float* d_x, int k, float* d_distances, int64_t* d_labels);
 /* the same contract for the flat search (GammaFLATIndex::Search, gamma_index_flat.cc:118-300): complete on return, and the call's

@@ -483,3 +483,190 @@ def test_concurrent_flat_callers_each_get_a_complete_result(nthreads):
         compare_exact(want[0][1][0], want[0][1][1], D0.cpu().numpy(), I0.cpu().numpy())
     finally:
         g.close()
+
+
+# ---- more callers than any fixed number of completion slots (gamma_amd/csrc/call_slots.h) ---------------------------------------
+# A store on which a flat call's survivor lists MUST overflow for one kind of batch and CANNOT for the other, decided in float64
+# by the test itself: d = 300 (first row chunk: 1024 rows, first filter pass: the 3072 rows behind it), 6001 rows --
+#   rows 0..1023     spread, N(0, 40^2)
+#   rows 1024..4024  a cluster around P ~ N(0, 120^2) in improving order: P + g_j * 0.01 * (3001 - j), the nearest last
+#   rows 4025..6000  spread
+# hot batch: 64 queries at P + 1e-3 * noise -- every row of the cluster is under the bound the first 1024 rows give (capacity of a
+# survivor list: 1024), and the best rows come last, so a truncated list loses them; cold batch: 64 queries at spread rows.
+_OV_D, _OV_FIRST, _OV_CAP, _OV_K = 300, 1024, 1024, 10
+
+
+def _overflow_store():
+    rng = np.random.default_rng(4000)
+    a = rng.standard_normal((1024, _OV_D)) * 40.0
+    P = rng.standard_normal(_OV_D) * 120.0
+    j = np.arange(3001)
+    c = P[None, :] + rng.standard_normal((3001, _OV_D)) * (0.01 * (3001 - j))[:, None]
+    b = rng.standard_normal((1976, _OV_D)) * 40.0
+    return np.concatenate([a, c, b]).astype(np.float32), P
+
+
+def _overflow_batch(rows, P, hot, seed):
+    rng = np.random.default_rng(seed)
+    at = np.repeat(P[None, :], 64, axis=0) if hot else rows[np.concatenate([rng.integers(0, 1024, 32), rng.integers(4025, 6001, 32)])]
+    return (at + 1e-3 * rng.standard_normal((64, _OV_D))).astype(np.float32)
+
+
+def _rows_under_bound(rows, q, lo, hi, kth, margins):
+    """float64: per query, the rows [lo, hi) whose distance is under the kth-best distance among the first row chunk, plus
+    `margins` times the filter's margin 2^-12 (|x|^2 + |y|^2)"""
+    r, x = rows.astype(np.float64), q.astype(np.float64)
+    rn, xn = (r * r).sum(1), (x * x).sum(1)
+    d2 = xn[:, None] + rn[None, :] - 2.0 * (x @ r.T)
+    bound = np.partition(d2[:, :_OV_FIRST], kth - 1, axis=1)[:, kth - 1]
+    slack = margins * 2.0 ** -12 * (xn[:, None] + rn[None, lo:hi])
+    return (d2[:, lo:hi] < bound[:, None] + slack).sum(1)
+
+
+@pytest.mark.parametrize("nthreads", [6, 8])
+def test_more_flat_callers_than_slots_each_read_their_own_overflow_word(nthreads):
+    """gamma_hip_flat_search_device_wait with 6 and 8 callers (the entry once rotated through four completion slots): threads
+    with an even number send batches whose survivor lists overflow -- their calls must be redone without a bound -- the others
+    batches that cannot overflow.  A waiter that read another call's overflow word would return a truncated top-k (lost) or
+    redo for nothing (borrowed): every result is compared bit for bit with the oracle and with the plain call made alone, and
+    the redone-passes counter must have grown by exactly (hot calls) x (what one hot call alone adds)."""
+    import torch
+    rows, P = _overflow_store()
+    N, k, nb, ncalls = len(rows), _OV_K, 2, 8
+    g = api.GammaHip(0)
+    try:
+        g.raw_init(_OV_D)
+        g.raw_append(rows)
+        g.set_small_path(0)
+        dev = torch.device("cuda", 0)
+        args = api.SearchArgs(metric=api.METRIC_L2, **WIDE)      # exact ties: the handle's default (on) -- the deferred word
+        hot = [t % 2 == 0 for t in range(nthreads)]
+        qh = [[_overflow_batch(rows, P, hot[t], 5000 + 10 * t + b) for b in range(nb)] for t in range(nthreads)]
+        # must / cannot overflow, by the reference's arithmetic alone (k-th bound for "must", (k + 1)-th for "cannot": either
+        # way the side that makes the claim harder)
+        for t in range(nthreads):
+            for b in range(nb):
+                if hot[t]:
+                    n = _rows_under_bound(rows, qh[t][b], _OV_FIRST, 4 * _OV_FIRST, k, 0.0)
+                    assert n.min() > _OV_CAP, (t, b, int(n.min()))
+                else:
+                    n = _rows_under_bound(rows, qh[t][b], _OV_FIRST, N, k + 1, 4.0)
+                    assert n.max() < _OV_CAP / 10, (t, b, int(n.max()))
+        qs = [[torch.from_numpy(q).to(dev) for q in row] for row in qh]
+        D0 = torch.empty((64, k), dtype=torch.float32, device=dev)
+        I0 = torch.empty((64, k), dtype=torch.int64, device=dev)
+        want = [[None] * nb for _ in range(nthreads)]
+        r_hot = None
+        for t in range(nthreads):
+            for b in range(nb):
+                Do, Io = B.flat_search(rows, qh[t][b], k, B.METRIC_L2, B.make_ctx(**WIDE))
+                g.flat_search_device(qs[t][b].data_ptr(), 64, k, args, D0.data_ptr(), I0.data_ptr())
+                g.synchronize()
+                want[t][b] = (D0.cpu().numpy().copy(), I0.cpu().numpy().copy())
+                compare_exact(Do, Io, want[t][b][0], want[t][b][1])
+                if hot[t]:
+                    assert Io[:, :k].min() >= 4014, "the best rows were meant to come last"
+                # the batch alone through the entry under test: redone if and only if hot, by the same amount every time
+                before = g.flat_filter_stats()[2]
+                g.flat_search_device_wait(qs[t][b].data_ptr(), 64, k, args, D0.data_ptr(), I0.data_ptr())
+                r = g.flat_filter_stats()[2] - before
+                compare_exact(want[t][b][0], want[t][b][1], D0.cpu().numpy(), I0.cpu().numpy())
+                if hot[t]:
+                    assert r > 0 and r_hot in (None, r), (t, b, r, r_hot)
+                    r_hot = r
+                else:
+                    assert r == 0, (t, b, r)
+        errors = []
+        before = g.flat_filter_stats()[2]
+
+        def client(t):
+            try:
+                Dt = torch.empty((64, k), dtype=torch.float32, device=dev)
+                It = torch.empty((64, k), dtype=torch.int64, device=dev)
+                st = torch.cuda.Stream(device=dev)
+                for rep in range(ncalls):
+                    b = rep % nb
+                    g.flat_search_device_wait(qs[t][b].data_ptr(), 64, k, args, Dt.data_ptr(), It.data_ptr())
+                    # complete on return: read back WITHOUT any further synchronisation of the handle
+                    with torch.cuda.stream(st):
+                        Dh, Ih = Dt.to("cpu", non_blocking=False), It.to("cpu", non_blocking=False)
+                    if Dh.numpy().tobytes() != want[t][b][0].tobytes() or Ih.numpy().tobytes() != want[t][b][1].tobytes():
+                        compare_exact(want[t][b][0], want[t][b][1], Dh.numpy(), Ih.numpy())
+                        raise AssertionError("result bytes differ from the plain call's (thread %d, call %d)" % (t, rep))
+            except BaseException as e:   # noqa: B902
+                errors.append((t, repr(e)))
+        th = [threading.Thread(target=client, args=(t,)) for t in range(nthreads)]
+        for x in th:
+            x.start()
+        for x in th:
+            x.join()
+        assert not errors, errors[:3]
+        redone = g.flat_filter_stats()[2] - before
+        assert redone == sum(hot) * ncalls * r_hot, (redone, sum(hot) * ncalls, r_hot)   # lost: lower; borrowed: higher
+        g.flat_search_device(qs[0][1].data_ptr(), 64, k, args, D0.data_ptr(), I0.data_ptr())
+        g.synchronize()
+        compare_exact(want[0][1][0], want[0][1][1], D0.cpu().numpy(), I0.cpu().numpy())
+    finally:
+        g.close()
+
+
+@pytest.mark.parametrize("nthreads", [6, 8])
+def test_more_ivfpq_callers_than_slots_each_get_a_complete_result(nthreads):
+    """gamma_hip_ivfpq_search_device_wait with 6 and 8 callers: the data recipe of the 2 / 3-thread test (every vector twice, so
+    that every call has a tie replay on the side stream when the next caller starts), batches of 1200 queries -- beyond the
+    small-batch chain, which replays inside its tail kernel -- every result bit for bit the plain call's made alone."""
+    import torch
+    d, nlist, M, N = 32, 64, 8, 20000
+    base = synth.sift_like(N, d=d, seed=31)
+    base[N // 2:] = base[:N // 2]            # every vector twice
+    cc, pq = B.ivfpq_train(base[:6000], nlist, M)
+    g = api.GammaHip(0)
+    try:
+        g.ivfpq_init(d, nlist, M, 8, api.METRIC_L2)
+        g.ivfpq_set_trained(cc, pq, None)
+        g.raw_init(d)
+        g.raw_append(base)
+        g.add(base, 0)
+        dev = torch.device("cuda", 0)
+        nq, k, nb, ncalls = 1200, 10, 3, 6
+        args = api.SearchArgs(metric=api.METRIC_L2, nprobe=16, recall_num=100, has_rank=True, coarse_mode=1, **WIDE)
+        qs = [[torch.from_numpy(synth.sift_like(nq, d=d, seed=6000 + 17 * t + b)).to(dev) for b in range(nb)] for t in range(nthreads)]
+        want = [[None] * nb for _ in range(nthreads)]
+        D0 = torch.empty((nq, k), dtype=torch.float32, device=dev)
+        I0 = torch.empty((nq, k), dtype=torch.int64, device=dev)
+        before, rf_before = g.tie_stats(), g.rerank_filter_stats()["calls"]
+        for t in range(nthreads):
+            for b in range(nb):
+                g.ivfpq_search_device(qs[t][b].data_ptr(), nq, k, args, D0.data_ptr(), I0.data_ptr())
+                g.synchronize()
+                want[t][b] = (D0.cpu().numpy().copy(), I0.cpu().numpy().copy())
+        assert g.tie_stats()["replayed"] > before["replayed"], "the data was meant to flag queries for the replay"
+        # 1200 queries leave the small-batch chain (up to 512): the re-rank behind the byte image, which has_rank calls of 1024
+        # queries and more take, belongs to the regular chain alone
+        assert g.rerank_filter_stats()["calls"] > rf_before, g.rerank_filter_stats()
+        errors = []
+
+        def client(t):
+            try:
+                Dt = torch.empty((nq, k), dtype=torch.float32, device=dev)
+                It = torch.empty((nq, k), dtype=torch.int64, device=dev)
+                st = torch.cuda.Stream(device=dev)
+                for rep in range(ncalls):
+                    b = rep % nb
+                    g.ivfpq_search_device_wait(qs[t][b].data_ptr(), nq, k, args, Dt.data_ptr(), It.data_ptr())
+                    with torch.cuda.stream(st):
+                        Dh, Ih = Dt.to("cpu", non_blocking=False), It.to("cpu", non_blocking=False)
+                    compare_exact(want[t][b][0], want[t][b][1], Dh.numpy(), Ih.numpy())
+            except BaseException as e:   # noqa: B902
+                errors.append((t, repr(e)))
+        th = [threading.Thread(target=client, args=(t,)) for t in range(nthreads)]
+        for x in th:
+            x.start()
+        for x in th:
+            x.join()
+        assert not errors, errors[:3]
+        g.ivfpq_search_device(qs[0][0].data_ptr(), nq, k, args, D0.data_ptr(), I0.data_ptr())
+        g.synchronize()
+        compare_exact(want[0][0][0], want[0][0][1], D0.cpu().numpy(), I0.cpu().numpy())
+    finally:
+        g.close()

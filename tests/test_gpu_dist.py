@@ -239,6 +239,51 @@ def test_sharded_realtime_inserts_route_to_the_list_owner():
             g.close()
 
 
+def test_sharded_add_stores_the_rows_before_it_lists_the_vectors():
+    """HipShardBackend.add with raw_sharded: store first, index second, as the reference does.  gamma_hip_raw_put refuses vector
+    ids from 2^31 on before it changes anything, so an add of 4 vectors at first_vid = 2^31 - 2 must raise and leave NO key
+    behind (keys first would leave listed vectors without rows, which shard_exact drops from re-ranked results without a word);
+    the same vectors at ids the store takes are then found by a has_rank search at their exact distances."""
+    import torch
+    from gamma_amd import api, synth
+    from gamma_amd import dist as gdist
+    from tests.shard_emul import sharded_search_emulated
+    case = fixtures.trained_case(d=32, nlist=64, M=8, N=20000, nq=64, metric=B.METRIC_L2)
+    d, nlist = case["d"], case["nlist"]
+    g = api.GammaHip(0)
+    try:
+        g.ivfpq_init(d, nlist, case["M"], 8, case["metric"], 1000)
+        g.ivfpq_set_trained(case["cc"], case["pq"], None)
+        g.raw_init(d)
+        back = gdist.HipShardBackend(g, 0, raw_sharded=True, owned=np.ones(nlist, np.uint8))
+        back.add(case["base"][:1000], 0)
+        new = synth.sift_like(4, d=d, seed=97)
+        sizes = [g.list_size(l) for l in range(nlist)]
+        assert sum(sizes) == 1000 and g.raw_stats()["rows"] == 1000
+        first = 2 ** 31 - 2
+        with pytest.raises(api.GammaHipError, match="out of range"):
+            back.add(new, first)
+        assert not g.has_vid(first + np.arange(4)).any()
+        assert [g.list_size(l) for l in range(nlist)] == sizes and g.raw_stats()["rows"] == 1000
+        back.add(new, 1000)
+        assert g.has_vid(1000 + np.arange(4)).all() and sum(g.list_size(l) for l in range(nlist)) == 1004
+        # integer-valued rows and queries below 2^8 in 32 dimensions: every distance is an integer below 2^24, exact in fp32
+        q = new.copy()
+        q[:, 0] += 1.0
+        held = np.concatenate([case["base"][:1000], new]).astype(np.float64)
+        args = api.SearchArgs(metric=api.METRIC_L2, nprobe=nlist, recall_num=100, has_rank=True, min_score=-3e38, max_score=3e38,
+                              coarse_mode=1)
+        D, I, _ = sharded_search_emulated([g], torch.from_numpy(q).to(torch.device("cuda", 0)), 10, args, raw_sharded=True)
+        D, I = D.cpu().numpy(), I.cpu().numpy()
+        for i in range(4):
+            assert I[i, 0] == 1000 + i and D[i, 0] == 1.0, (i, I[i], D[i])
+            assert (I[i] >= 0).all() and (I[i] < 1004).all()
+            exact = ((held[I[i]] - q[i].astype(np.float64)) ** 2).sum(1)
+            assert np.array_equal(D[i].astype(np.float64), exact), (i, D[i], exact)
+    finally:
+        g.close()
+
+
 def test_update_across_shards():
     """GammaIVFPQIndex::Update on a list-sharded index (gamma_amd/dist.py sharded_update / route_update): every shard
     is handed the same (vid, vector); the holder of the old entry flags it, the owner of the new list appends.

@@ -14,7 +14,9 @@ can have run over copies; fakerccl_selftest_* holds the stand-in itself to the r
 and all-to-all against a plain loop; a wrong count, a misplaced in-place all-gather, a short recv and another reduction each
 refused at every rank without hanging).  (The combining queue and the store locks of the device library live in translation
 units full of kernel launches: they are exercised by the GPU suites, tests/test_gpu_concurrent.py; GPU sanitizers do not exist
-on this pool.)"""
+on this pool.  Caller bookkeeping that was moved out of those units is checked on the CPU like the code above: the owners of
+device memory by tests/test_dev_mem.py, the completion slots of the _wait entries -- with the interleaving of enqueue, completion
+and wait scripted -- by tests/test_call_slots.py.)"""
 import os
 import shutil
 import subprocess
