@@ -188,6 +188,17 @@ static void check_plans() {
         sh.compacted = false;
         EXPECT_EQ("sparse shard", plan(sh).bounded, 0);
     }
+    {   // the query order: from 256 queries on, when the T2 rows are more than 8 MiB.  The first shape is the one the ordered legs of
+        // tests/test_gpu_rerank_filter_shapes.py run (1024 lists x 16 x 1 KiB = 16 MiB, 300 queries, 32 probes)
+        for (int R : {200, 600}) {
+            EXPECT_EQ("ordered leg", plan(shape(1024, 16, 40000, 32, R, 300)).order, 1);
+            EXPECT_EQ("ordered leg, 1027 queries", plan(shape(1024, 16, 40000, 32, R, 1027)).order, 1);
+            EXPECT_EQ("ordered leg, a chunk of 400", plan(shape(1024, 16, 40000, 32, R, 400)).order, 1);
+            EXPECT_EQ("ordered leg, 256 queries", plan(shape(1024, 16, 40000, 32, R, 256)).order, 1);
+            EXPECT_EQ("ordered leg, 255 queries", plan(shape(1024, 16, 40000, 32, R, 255)).order, 0);
+            EXPECT_EQ("ordered leg, 512 lists", plan(shape(512, 16, 40000, 32, R, 300)).order, 0);   // 8 MiB: not more
+        }
+    }
     {   // what can reject an entry
         ScanShape sh = shape(4096, 16, 1000000, 32, 200, 16384);
         sh.rejects = true;

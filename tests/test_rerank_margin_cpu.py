@@ -1,7 +1,9 @@
 """The bound of the re-rank filter (csrc/rerank_filter.hip), checked on the CPU: a numpy fp32 emulation of the image (lo, Delta,
 the byte rows, err, nrm), of the kernel's estimate and of its lb / ub, against the reference's 8-lane fma chain (fvec_L2sqr /
-fvec_inner_product as csrc/rerank_dev.h runs it) and against the value in float64.  lb <= exact <= ub for every (query, row)
-pair.  The margin is parsed from csrc/kernels.h, the place the kernel takes it from."""
+fvec_inner_product as csrc/rerank_dev.h runs it; tests/rerank_ref.py exact_chain) and against the value in float64.
+lb <= exact <= ub for every (query, row) pair, at the row lengths the kernel admits: 16 (one piece, seven idle lanes), 128 (the
+register form), 272 (lanes with one piece more than others), 768 and 1536 (kRerankFilterMaxD: n of the error analysis at its
+largest).  The margin is parsed from csrc/kernels.h, the place the kernel takes it from."""
 import os
 import re
 
@@ -9,6 +11,7 @@ import numpy as np
 import pytest
 
 from gamma_amd import synth
+from tests.rerank_ref import exact_chain as _exact, fma32 as _fma
 
 _KH = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gamma_amd", "csrc", "kernels.h")
 F = np.float32
@@ -21,12 +24,11 @@ def _constant(name):
 
 
 M = _constant("kRerankFilterMargin")
-NQ, NY = 48, 768
 
 
-def _fma(a, b, c):
-    """fp32 fma: the product of two floats is exact in float64"""
-    return (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(F)
+def _sizes(d):
+    """(queries, rows): the emulation holds nq x ny x d arrays"""
+    return (48, 768) if d < 768 else (8, 256)
 
 
 def _group8(a):
@@ -46,21 +48,6 @@ def _chain16(term, acc_of):
             for l in range(min(8, nc - c0)):
                 acc[..., l] = acc_of(acc[..., l], term[..., 16 * (c0 + l) + e])
     return _group8(acc)
-
-
-def _exact(x, y, l2):
-    """the reference's chain: lane l runs elements l, l + 8, ..; s[l] = acc[l + 4] + acc[l]; (s0 + s1) + (s2 + s3)"""
-    d = x.shape[-1]
-    acc = np.zeros((x.shape[0], y.shape[0], 8), F)
-    for i in range(0, d, 8):
-        xs, ys = x[:, None, i:i + 8], y[None, :, i:i + 8]
-        if l2:
-            t = (xs - ys).astype(F)
-            acc = _fma(t, t, acc)
-        else:
-            acc = _fma(np.broadcast_to(xs, acc.shape), np.broadcast_to(ys, acc.shape), acc)
-    s = acc[..., 4:] + acc[..., :4]
-    return (s[..., 0] + s[..., 1]) + (s[..., 2] + s[..., 3])
 
 
 def _image(y):
@@ -103,6 +90,7 @@ def _bounds(x, im, l2):
 
 
 def _cases(d):
+    NQ, NY = _sizes(d)
     rng = np.random.default_rng(5 + d)
     g_y = (rng.standard_normal((NY, d)) * 20).astype(F)
     g_x = (g_y[rng.integers(0, NY, NQ)] + rng.standard_normal((NQ, d)) * 12).astype(F)
@@ -110,15 +98,23 @@ def _cases(d):
     c_y = (rng.standard_normal((NY, d)) * 300).astype(F)
     c_y[NY // 2:] = c_y[:NY // 2] + (rng.standard_normal((NY // 2, d)) * 1e-3).astype(F)
     c_x = (c_y[rng.integers(0, NY, NQ)] + rng.standard_normal((NQ, d)) * 1e-2).astype(F)
+    # the rows of the GPU legs (tests/test_gpu_rerank_filter_shapes.py): standard normal * 20 + 1000 in fp32, lo != 0 and
+    # x - lo cancels; queries of the same kind, unrelated to the rows
+    s_y = (rng.standard_normal((NY, d)).astype(F) * F(20) + F(1000)).astype(F)
+    s_x = (rng.standard_normal((NQ, d)).astype(F) * F(20) + F(1000)).astype(F)
+    # magnitudes around 1e15 (squares and their sums over 1536 elements stay finite): u |x - lo| against a large lo
+    h_y = (F(1e15) + rng.standard_normal((NY, d)).astype(F) * F(3e13)).astype(F)
+    h_x = (h_y[rng.integers(0, NY, NQ)] + rng.standard_normal((NQ, d)).astype(F) * F(1e13)).astype(F)
     return {"gaussian": (g_x, g_y, g_y), "sift_like": (base[NY:], base[:NY], base[:NY]),
             "offset": (g_x + F(1000), g_y + F(1000), g_y + F(1000)), "cancellation": (c_x, c_y, c_y),
             # the image's range comes from the first rows only: the others clamp
-            "clamped": (g_x, g_y, (g_y[:64] * F(0.05)).astype(F))}
+            "clamped": (g_x, g_y, (g_y[:64] * F(0.05)).astype(F)),
+            "scaled_shifted": (s_x, s_y, s_y), "huge": (h_x, h_y, h_y)}
 
 
 @pytest.mark.parametrize("l2", [True, False])
-@pytest.mark.parametrize("name", ["gaussian", "sift_like", "offset", "cancellation", "clamped"])
-@pytest.mark.parametrize("d", [128, 272])
+@pytest.mark.parametrize("name", ["gaussian", "sift_like", "offset", "cancellation", "clamped", "scaled_shifted", "huge"])
+@pytest.mark.parametrize("d", [16, 128, 272, 768, 1536])
 def test_bounds_hold_for_every_pair(d, name, l2):
     x, y, ranged_on = _cases(d)[name]
     im = _image(y)
