@@ -88,6 +88,8 @@ SYMBOLS = {
     "gamma_hip_coarse_filter_stats": (C.c_int, [C.c_void_p, i64p]),
     "gamma_hip_set_rerank_filter": (C.c_int, [C.c_void_p, C.c_int]),
     "gamma_hip_rerank_filter_stats": (C.c_int, [C.c_void_p, i64p]),
+    "gamma_hip_set_rerank_filter_form": (C.c_int, [C.c_void_p, C.c_int]),
+    "gamma_hip_rerank_filter_form": (C.c_int, [C.c_void_p, i64p]),
     "gamma_hip_flat_filter_shape": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float)]),
     "gamma_hip_flat_filter_stats": (C.c_int, [C.c_void_p, i64p, C.c_int]),
     "gamma_hip_tie_stats": (C.c_int, [C.c_void_p, i64p, C.c_int]),

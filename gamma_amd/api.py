@@ -770,6 +770,19 @@ class GammaHip:
         self._ck(self.L.gamma_hip_rerank_filter_stats(self.h, _p(out, _lib.i64p)), "rerank_filter_stats")
         return dict(zip(["candidates", "survivors", "calls", "backoffs", "image_rows"], [int(v) for v in out]))
 
+    def set_rerank_filter_form(self, form=0):
+        """0 (default): automatic, the wave-per-query kernel where it is admitted (d 128, at most 256 candidates per query) and
+        the call has at least rerank_filter_form()["auto_min_nq"] queries; 1: the workgroup kernel always; 2: the wave form wherever it is admitted.  Same
+        results in all."""
+        self._ck(self.L.gamma_hip_set_rerank_filter_form(self.h, int(form)), "set_rerank_filter_form")
+
+    def rerank_filter_form(self):
+        """the setting, the kernel of the last filtered call (1 workgroup, 2 wave, 0 none yet), filtered calls in the wave form, the
+        query count from which the automatic setting takes the wave form"""
+        out = np.zeros(4, np.int64)
+        self._ck(self.L.gamma_hip_rerank_filter_form(self.h, _p(out, _lib.i64p)), "rerank_filter_form")
+        return dict(zip(["form", "last", "wave_calls", "auto_min_nq"], [int(v) for v in out]))
+
     def flat_filter_stats(self, reset=False):
         """(filter passes launched, (query, row) pairs they scored, passes redone without the bound) of flat_search."""
         out = np.zeros(3, np.int64)

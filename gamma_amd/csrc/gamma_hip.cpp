@@ -239,6 +239,23 @@ int gamma_hip_rerank_filter_stats(gamma_hip_index* h, int64_t* out5) {
     return GAMMA_HIP_OK;
 }
 
+int gamma_hip_set_rerank_filter_form(gamma_hip_index* h, int form) {
+    if (!h || form < 0 || form > 2) return GAMMA_HIP_EINVAL;
+    SearchLock lk(h);
+    h->rf.form = form;
+    return GAMMA_HIP_OK;
+}
+
+int gamma_hip_rerank_filter_form(gamma_hip_index* h, int64_t* out4) {
+    if (!h || !out4) return GAMMA_HIP_EINVAL;
+    SearchLock lk(h);
+    out4[0] = h->rf.form;
+    out4[1] = h->rf.last_form;
+    out4[2] = h->rf.wave_calls;
+    out4[3] = gh::kRerankWaveAutoMinNq;
+    return GAMMA_HIP_OK;
+}
+
 int gamma_hip_flat_filter_shape(int d, int* d_pad, float* margin) { return gh::flat_filter_shape(d, d_pad, margin); }
 
 int gamma_hip_flat_filter_stats(gamma_hip_index* h, int64_t* out3, int reset) {

@@ -245,6 +245,9 @@ struct gamma_hip_index {
         hipEvent_t built = nullptr;
         int mode = 1;              // 0 off, 1 calls of kAutoMinNq queries and more, 2 every call
         static constexpr int kAutoMinNq = 1024;
+        int form = 0;              // gamma_hip_set_rerank_filter_form: 0 automatic, 1 the workgroup kernel always, 2 the wave form wherever admitted
+        int last_form = 0;         // the kernel of the last filtered call: 1 workgroup, 2 wave (0: none yet)
+        int64_t wave_calls = 0;
         unsigned long long* d_stat = nullptr;
         unsigned long long* pin_stat = nullptr;
         unsigned long long seen[2] = {0, 0};           // {survivors, candidates} at the last decision

@@ -844,9 +844,12 @@ int ivfpq_stage_b(H* h, const gamma_hip_search_params* p, int nq, const float* d
             bool filt = false;
             GH_TRY(rerank_filter_begin(h, l2, nq, R, k, &filt));
             if (filt) {
-                gh::launch_rerank_topk_filtered(s, l2, d_x, nq, h->d, h->raw_f32(), h->nraw, h->rf.rows.as<uint8_t>(),
-                                                h->rf.aux.as<float>(), h->rf.par, cand_ids, R, k, p->min_score, p->max_score, neutral,
-                                                d_distances, d_labels, qperm, ties ? &tf : nullptr, h->rf.d_stat);
+                const int ran = gh::launch_rerank_topk_filtered(s, l2, d_x, nq, h->d, h->raw_f32(), h->nraw, h->rf.rows.as<uint8_t>(),
+                                                                h->rf.aux.as<float>(), h->rf.par, cand_ids, R, k, p->min_score,
+                                                                p->max_score, neutral, d_distances, d_labels, qperm,
+                                                                ties ? &tf : nullptr, h->rf.d_stat, h->rf.form);
+                if (ran) h->rf.last_form = ran;
+                if (ran == 2) h->rf.wave_calls++;
                 GH_TRY(rerank_filter_end(h, (int64_t)nq * R));
             } else {
                 gh::launch_rerank_topk(s, l2, d_x, nq, h->d, raw_rows_ref(h), h->nraw, cand_ids, R, k, p->min_score,

@@ -487,11 +487,21 @@ void launch_rerank_image_params(hipStream_t s, const float* rows, int64_t n, int
 // image rows (img: u8[d], aux: {err, nrm} each) of the store's rows first + i, or vids[i] (outside [0, nrows): skipped), i < n
 void launch_rerank_image_rows(hipStream_t s, const float* rows, const int64_t* vids, int64_t first, int64_t n, int d, const float* par,
                               uint8_t* img, float* aux, int64_t nrows);
+// The wave form (k_rerank_topk_filt_wave: one wave per query, no workgroup barrier) takes d == 128, R <= 256, min(k + 1, R) <= 64
+bool rerank_filter_wave_ok(int d, int R, int k);
+// Automatic dispatch takes the wave form from this many queries on.  A wave walks its query's chain alone, so a call that fills
+// the device with waves only thinly is quicker with a workgroup's 256 threads per query (DESIGN.md section 31 has the measurement).
+// The one place the number stands: gamma_hip_rerank_filter_form reports it.
+constexpr int kRerankWaveAutoMinNq = 4096;
 // stat: kRerankFilterStatLines x 16 words; the queries add their survivors to word 0 of a line each (the sum is the count)
-void launch_rerank_topk_filtered(hipStream_t s, bool l2, const float* x, int nq, int d, const float* raw, int64_t nraw, const uint8_t* img,
+// form (gamma_hip_set_rerank_filter_form): 0 = automatic, the wave form where rerank_filter_wave_ok holds and the call has enough
+// queries to fill the device with waves (kRerankWaveAutoMinNq); 1 = the workgroup kernel always; 2 = the wave
+// form wherever rerank_filter_wave_ok holds.
+// Returns the form it launched (1 workgroup kernel, 2 wave form), 0 when it launched nothing.
+int launch_rerank_topk_filtered(hipStream_t s, bool l2, const float* x, int nq, int d, const float* raw, int64_t nraw, const uint8_t* img,
                                  const float* aux, const float* par, const int64_t* cand_ids, int R, int k, float min_score,
                                  float max_score, float neutral, float* distances, int64_t* labels, const int* qperm,
-                                 const TieFlags* ties, unsigned long long* stat);
+                                 const TieFlags* ties, unsigned long long* stat, int form = 0);
 // what k_tie_replay needs to redo one query (ties.hip)
 struct TieReplayArgs {
     const int* list;              // flagged queries, *count of them

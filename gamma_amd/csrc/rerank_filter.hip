@@ -35,9 +35,13 @@
 //
 // Timing builds (results invalid, never committed switched on; what they measured: DESIGN.md section 29): -DGH_RERANK_TIMING=1
 // k_rerank_topk's d = 128 row loads replaced by a constant (rerank.hip); here 2 = no err / nrm loads, 3 = no exact phase, 4 = no
-// survivor counter, 5 = no image loads.
+// survivor counter, 5 = no image loads; 6 = results valid, thread 0 of one workgroup in 16 reads the clock (100 MHz) between the
+// phases and the sums are printed every 20 launches (with -DGH_RERANK_TIMING_FORM=1 the workgroup kernel runs throughout).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#if GH_RERANK_TIMING == 6
+#include <stdio.h>
+#endif
 
 #include <algorithm>
 
@@ -68,6 +72,20 @@ __device__ __forceinline__ float block_sum256(float v, float* red) {
     __syncthreads();
     return (red[0] + red[1]) + (red[2] + red[3]);
 }
+
+#if GH_RERANK_TIMING == 6
+// [i] = clock ticks between marks i and i + 1, summed over the timed workgroups; [15] = their number.  Marks: 0 start, 1 ids and
+// query staged, 2 estimates in LDS, 3 bounds (err / nrm landed), 4 tau, 5 survivors listed, 6 their rows measured, 7 first K1
+// items sorted, 8 output written
+__device__ unsigned long long g_phase_clk[16];
+#define GH_CLK_DECL unsigned long long clk[9]; const bool clk_on = threadIdx.x == 0 && (blockIdx.x & 15) == 0
+#define GH_CLK(i) do { if (clk_on) clk[i] = wall_clock64(); } while (0)
+#define GH_CLK_END do { if (clk_on) { for (int i_ = 0; i_ < 8; i_++) atomicAdd(g_phase_clk + i_, clk[i_ + 1] - clk[i_]); atomicAdd(g_phase_clk + 15, 1ull); } } while (0)
+#else
+#define GH_CLK_DECL
+#define GH_CLK(i)
+#define GH_CLK_END
+#endif
 }  // namespace
 
 // ---- the image's parameters -----------------------------------------------------------------------------------------------------
@@ -224,6 +242,8 @@ __global__ __launch_bounds__(256) void k_rerank_topk_filt(const float* __restric
     __shared__ float s_red[4];
     __shared__ float s_tau;
     __shared__ int s_tie, s_nsv;
+    GH_CLK_DECL;
+    GH_CLK(0);
     int q = blockIdx.x;   // (the query order: k_rerank_topk)
     if (qperm) {
         const int qi = (blockIdx.x & 7) * ((nq + 7) >> 3) + (blockIdx.x >> 3);
@@ -251,6 +271,7 @@ __global__ __launch_bounds__(256) void k_rerank_topk_filt(const float* __restric
     float c0 = 0.f;
     if (!L2) c0 = block_sum256(sc, s_red);   // (uniform)
     // (block_sum256's barriers: s_id, s_x and s_nsv are in place)
+    GH_CLK(1);
 
     // ---- phase 1: estimates from the image, eight lanes per candidate; then every candidate's bounds by a thread of its own ----
     if constexpr (D128) {
@@ -322,6 +343,7 @@ __global__ __launch_bounds__(256) void k_rerank_topk_filt(const float* __restric
         }
     }
     __syncthreads();   // every estimate is in s_bd
+    GH_CLK(2);
     float bd[4];      // L2: lb, inner product: ub -- the bound tau is held against
     bool alive[4];    // not certainly outside the window
 #pragma unroll
@@ -359,6 +381,7 @@ __global__ __launch_bounds__(256) void k_rerank_topk_filt(const float* __restric
             bd[u] = L2 ? lb : ub;
         }
     }
+    GH_CLK(3);
     if (threadIdx.x == 0) {
         if (tf.list) s_tie = tf.cut ? tf.cut[q] : 0;
         s_tau = sentinel;   // (fewer than K1 certainly inside: nothing is proven out)
@@ -384,6 +407,7 @@ __global__ __launch_bounds__(256) void k_rerank_topk_filt(const float* __restric
     }
     __syncthreads();
     const float tau = s_tau;
+    GH_CLK(4);
     const uint32_t skey = L2 ? f2key(sentinel) : ~f2key(sentinel);
     bool sv[4];
 #pragma unroll
@@ -402,6 +426,7 @@ __global__ __launch_bounds__(256) void k_rerank_topk_filt(const float* __restric
         }
     }
     __syncthreads();
+    GH_CLK(5);
 #if GH_RERANK_TIMING == 3   // timing build (results invalid): no survivor gets its exact distance
     const int m = 0;
 #else
@@ -460,6 +485,7 @@ __global__ __launch_bounds__(256) void k_rerank_topk_filt(const float* __restric
             if (live) put(r, dis);
         }
     }
+    GH_CLK(6);
     // the first K1 items: up to 64 survivors are sorted by one wave (every other item carries the sentinel key, as do the places
     // the survivors leave empty); more of them: k_rerank_topk's way
     if (m <= 64) {
@@ -472,23 +498,298 @@ __global__ __launch_bounds__(256) void k_rerank_topk_filt(const float* __restric
     } else {
         rerank_first_k(s_it, R, K1);
     }
+    GH_CLK(7);
     rerank_topk_out<L2>(s_it, s_id, &s_tie, q, R, k, neutral, distances, labels, tf);
+    GH_CLK(8);
+    GH_CLK_END;
 }
+
+// ---- the wave form: d == 128, R <= 256, K1 <= 64 ----------------------------------------------------------------------------------
+// One wave owns one query from its ids to its output and waits for no other wave: no workgroup barrier, 3.5 KB of LDS per wave
+// (ids, estimates / exact keys, the survivor list), so a CU holds as many queries as it holds waves.  The values are those of
+// k_rerank_topk_filt: the same x - lo, xn and c0 (the same sums in the same order), the same estimates, bounds, tau (the head
+// rule included), survivor test and exact arithmetic.  What differs is where things stand:
+//   * lane i holds candidate i + 64 u, u < 4: its id, its {err, nrm} -- requested with the ids in hand, in front of the image
+//     loads and not behind the estimates --, its bounds and its (key, rank) item, all in registers;
+//   * eight candidates per round (eight groups of eight lanes), four rounds' image loads in flight;
+//   * tau and the first K1 items come from wave_sort64 over one run, or -- more than one run: K1 > 16 for tau, more than 64
+//     survivors at the end -- from the sorting network over all 256 items in registers (wave_sort_net).  The items are distinct
+//     (the rank field), so the first K1 of any ascending sort are rerank_first_k's.
+// One wave per workgroup, so workgroup b is query b of the order and runs on XCD b & 7 as k_rerank_topk_filt's does.  (Four
+// waves per workgroup, each on its own, measured slower: DESIGN.md section 31.)
+constexpr int kRerankWaveMaxR = 256;
+
+__device__ __forceinline__ float wave_sum_first(float v) {   // block_sum256's sum over one wave, the value of lane 0 on every lane
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(v)));
+}
+
+template <bool L2>
+__global__ __launch_bounds__(64) void k_rerank_topk_filt_wave(const float* __restrict__ x, const float* __restrict__ raw, int64_t nraw,
+                                                                   const uint8_t* __restrict__ img, const float2* __restrict__ aux,
+                                                                   const float* __restrict__ par, const int64_t* __restrict__ cand_ids,
+                                                                   int R, int k, float min_score, float max_score, float neutral,
+                                                                   float* __restrict__ distances, int64_t* __restrict__ labels, int nq,
+                                                                   const int* __restrict__ qperm, TieFlags tf,
+                                                                   unsigned long long* __restrict__ stat) {
+    __shared__ int64_t s_id[kRerankWaveMaxR];
+    __shared__ uint32_t s_bd[kRerankWaveMaxR];         // the candidates' estimates; then the survivors' exact keys
+    __shared__ unsigned short s_sv[kRerankWaveMaxR];   // the survivors' candidate ranks
+    GH_CLK_DECL;
+    GH_CLK(0);
+    const int lane = threadIdx.x;
+    int q = blockIdx.x;   // (the query order: k_rerank_topk)
+    if (qperm) {
+        const int qi = (blockIdx.x & 7) * ((nq + 7) >> 3) + (blockIdx.x >> 3);
+        if (qi >= nq) return;
+        q = qperm[qi];
+    } else if (q >= nq) {
+        return;
+    }
+    const int l = lane & 7, g = lane >> 3;
+    const float* xq = x + (int64_t)q * 128;
+    const float sentinel = L2 ? INFINITY : -INFINITY;
+    const uint32_t skey = L2 ? f2key(sentinel) : ~f2key(sentinel);
+    const int K1 = min(k + 1, R);
+    // the query's loads go first: what waits for them below then does not wait for the {err, nrm} loads behind them
+    float4 xv4[4], lo4[4];
+    float xh[2], loh[2];
+#pragma unroll
+    for (int v = 0; v < 4; v++) {
+        xv4[v] = *reinterpret_cast<const float4*>(xq + 16 * l + 4 * v);
+        lo4[v] = L2 ? *reinterpret_cast<const float4*>(par + 16 * l + 4 * v) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+#pragma unroll
+    for (int h = 0; h < 2; h++) xh[h] = xq[lane + 64 * h], loh[h] = par[lane + 64 * h];
+    const float delta = par[128], lon = par[129];
+    // ids, and with them every candidate's {err, nrm}
+    bool live[4];
+    float2 ax[4];
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+        const int r = lane + 64 * u;
+        const int64_t id = r < R ? cand_ids[(int64_t)q * R + r] : -1;
+        if (64 * u < R) s_id[r] = id;   // (uniform)
+        live[u] = id >= 0 && id < nraw;
+        ax[u] = make_float2(0.f, 0.f);
+        if (live[u]) ax[u] = aux[id];
+    }
+    int tie = 0;
+    if (tf.list && tf.cut) tie = tf.cut[q];
+    // the query as the filter reads it (lane l: elements 16 l ..), its norm and (inner product) <x, lo>: block_sum256's sums
+    float xx[16];
+#pragma unroll
+    for (int v = 0; v < 4; v++) {
+        xx[4 * v] = xv4[v].x, xx[4 * v + 1] = xv4[v].y, xx[4 * v + 2] = xv4[v].z, xx[4 * v + 3] = xv4[v].w;
+        if (L2) {
+            xx[4 * v] = __fsub_rn(xv4[v].x, lo4[v].x), xx[4 * v + 1] = __fsub_rn(xv4[v].y, lo4[v].y);
+            xx[4 * v + 2] = __fsub_rn(xv4[v].z, lo4[v].z), xx[4 * v + 3] = __fsub_rn(xv4[v].w, lo4[v].w);
+        }
+    }
+    float sq[2], sc[2];
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+        const float v = L2 ? __fsub_rn(xh[h], loh[h]) : xh[h];
+        sq[h] = wave_sum_first(__builtin_fmaf(v, v, 0.f));
+        sc[h] = L2 ? 0.f : wave_sum_first(__builtin_fmaf(xh[h], loh[h], 0.f));
+    }
+    const float xn = sqrtf((sq[0] + sq[1]) + 0.f) * (1.0f + kM);
+    const float c0 = L2 ? 0.f : (sc[0] + sc[1]) + 0.f;
+    wave_lds_sync();   // s_id
+    GH_CLK(1);
+
+    // ---- phase 1: estimates from the image, eight lanes per candidate ----
+    for (int r0 = 0; r0 < R; r0 += 32) {
+        uint4 w[4];
+#pragma unroll
+        for (int f = 0; f < 4; f++) {
+            const int r = r0 + 8 * f + g;
+            const int64_t id = r < R ? s_id[r] : -1;
+            w[f] = make_uint4(0, 0, 0, 0);
+            if (id >= 0 && id < nraw) w[f] = *reinterpret_cast<const uint4*>(img + id * 128 + 16 * l);
+        }
+#pragma unroll
+        for (int f = 0; f < 4; f++) {
+            const uint32_t ww[4] = {w[f].x, w[f].y, w[f].z, w[f].w};
+            float a = 0.f;
+#pragma unroll
+            for (int u = 0; u < 16; u++) {
+                const float uf = byte_f(ww[u >> 2], u & 3);
+                if (L2) {
+                    const float t = __builtin_fmaf(-delta, uf, xx[u]);
+                    a = __builtin_fmaf(t, t, a);
+                } else {
+                    a = __builtin_fmaf(xx[u], uf, a);
+                }
+            }
+            a = group8_sum(a);
+            if (l == 0 && r0 + 8 * f + g < R) s_bd[r0 + 8 * f + g] = __float_as_uint(a);
+        }
+    }
+    wave_lds_sync();   // every estimate is in s_bd
+    GH_CLK(2);
+    // the bounds, where the candidate's {err, nrm} landed
+    unsigned long long it[4];
+    float bd[4];      // L2: lb, inner product: ub -- the bound tau is held against
+    bool alive[4];    // not certainly outside the window
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+        const int r = lane + 64 * u;
+        it[u] = ~0ull;
+        bd[u] = 0.f;
+        alive[u] = false;
+        if (r < R) {
+            const float a = __uint_as_float(s_bd[r]);
+            float lb, ub;
+            if (L2) {
+                const float rt = sqrtf(a);
+                const float slack = __builtin_fmaf(kM, rt + xn, ax[u].x);
+                const float ur = rt + slack, lr = fmaxf(rt - slack, 0.0f);
+                ub = ur * ur * (1.0f + kM);
+                lb = lr * lr * (1.0f - kM);
+            } else {
+                const float est = __builtin_fmaf(delta, a, c0);
+                const float slack = xn * __builtin_fmaf(kM, ax[u].y + lon, ax[u].x);
+                ub = est + slack;
+                lb = est - slack;
+            }
+            const bool inside = live[u] && ub <= max_score && lb >= min_score;
+            alive[u] = live[u] && !(lb > max_score || ub < min_score);
+            const uint32_t key = L2 ? f2key(ub) : ~f2key(lb);
+            if (inside) it[u] = ((unsigned long long)key << 32) | (unsigned)r;
+            bd[u] = L2 ? lb : ub;
+        }
+    }
+    GH_CLK(3);
+    // tau (k_rerank_topk_filt says which candidates it is taken among)
+    uint32_t tkey;
+    if ((K1 <= 16 && R > 64) || R <= 64) {   // (uniform) one run: the head, or all there is
+        tkey = (uint32_t)(wave_sort64(it[0]) >> 32);
+    } else {
+        unsigned long long t4[4] = {it[0], it[1], it[2], it[3]};
+        wave_sort_net<4>(t4);
+        tkey = (uint32_t)(t4[0] >> 32);
+    }
+    tkey = (uint32_t)__shfl((int)tkey, K1 - 1, 64);
+    const float tau = tkey != 0xffffffffu ? key2f(L2 ? tkey : ~tkey) : sentinel;   // (fewer than K1 certainly inside: nothing is proven out)
+    GH_CLK(4);
+    // the survivors, compacted; every other candidate's item is that of an out-of-window exact distance
+    bool sv[4];
+    int m = 0;
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+        const int r = lane + 64 * u;
+        sv[u] = alive[u] && !(L2 ? bd[u] > tau : bd[u] < tau);
+        it[u] = r < R ? (((unsigned long long)skey << 32) | (unsigned)r) : ~0ull;   // (padding sorts last)
+        if (64 * u < R) {   // (uniform)
+            const unsigned long long bal = __ballot(sv[u]);
+            if (sv[u]) s_sv[m + __popcll(bal & ((1ull << lane) - 1ull))] = (unsigned short)r;
+            m += __popcll(bal);
+        }
+    }
+    // counted as k_rerank_topk_filt counts them: one atomic per query, on one of kRerankFilterStatLines words a line apart
+    if (lane == 0 && stat) atomicAdd(stat + 16 * (blockIdx.x & (kRerankFilterStatLines - 1)), (unsigned long long)m);
+    wave_lds_sync();   // s_sv
+    GH_CLK(5);
+
+    // ---- phase 2: k_rerank_topk's arithmetic over the survivors, one per group and round; the keys go to s_bd by rank ----
+    {
+        float x2[16];
+#pragma unroll
+        for (int u = 0; u < 16; u++) x2[u] = xq[l + 8 * u];
+        for (int c0_ = 0; c0_ < m; c0_ += 8) {
+            const int c = c0_ + g;
+            const bool on = c < m;
+            const int r = on ? s_sv[c] : 0;
+            const float* v = raw + (on ? s_id[r] : 0) * 128 + l;
+            float fa[16];
+#pragma unroll
+            for (int u = 0; u < 16; u++) fa[u] = v[8 * u];
+            float a = 0.f;
+#pragma unroll
+            for (int u = 0; u < 16; u++) {
+                if (L2) {
+                    const float t = x2[u] - fa[u];
+                    a = __builtin_fmaf(t, t, a);
+                } else {
+                    a = __builtin_fmaf(x2[u], fa[u], a);
+                }
+            }
+            const float sa = __shfl_down(a, 4, 8) + a;
+            const float ta = sa + __shfl_down(sa, 1, 8);
+            float dis = ta + __shfl_down(ta, 2, 8);
+            if (on && l == 0) {
+                if (!(dis <= max_score && dis >= min_score)) dis = sentinel;
+                s_bd[r] = L2 ? f2key(dis) : ~f2key(dis);
+            }
+        }
+    }
+    wave_lds_sync();   // the survivors' keys
+    GH_CLK(6);
+    // the first K1 items, one per lane
+    unsigned long long first;
+    if (m <= 64) {   // (uniform) every other item carries the sentinel key, as do the places the survivors leave empty
+        unsigned long long mine = ~0ull;
+        if (lane < m) {
+            const unsigned r = s_sv[lane];
+            mine = ((unsigned long long)s_bd[r] << 32) | r;
+        }
+        mine = wave_sort64(mine);
+        first = mine != ~0ull ? mine : ((unsigned long long)skey << 32);
+    } else {
+#pragma unroll
+        for (int u = 0; u < 4; u++)
+            if (sv[u]) it[u] = ((unsigned long long)s_bd[lane + 64 * u] << 32) | (unsigned)(lane + 64 * u);
+        wave_sort_net<4>(it);
+        first = it[0];
+    }
+    GH_CLK(7);
+    rerank_topk_out_wave<L2>(first, s_id, tie, q, R, k, neutral, distances, labels, tf);
+    GH_CLK(8);
+    GH_CLK_END;
+}
+
+bool rerank_filter_wave_ok(int d, int R, int k) { return d == 128 && R >= 1 && R <= kRerankWaveMaxR && std::min(k + 1, R) <= 64; }
 
 bool rerank_filter_shape_ok(int d, int R, int k) { return d > 0 && d % 16 == 0 && d <= kRerankFilterMaxD && R >= 1 && R <= 1024 && std::min(k + 1, R) <= 64; }
 
-void launch_rerank_topk_filtered(hipStream_t s, bool l2, const float* x, int nq, int d, const float* raw, int64_t nraw, const uint8_t* img,
-                                 const float* aux, const float* par, const int64_t* cand_ids, int R, int k, float min_score,
-                                 float max_score, float neutral, float* distances, int64_t* labels, const int* qperm,
-                                 const TieFlags* ties, unsigned long long* stat) {
-    if (nq <= 0) return;
-    if (!rerank_filter_shape_ok(d, R, k) || nraw <= 0) {
+int launch_rerank_topk_filtered(hipStream_t s, bool l2, const float* x, int nq, int d, const float* raw, int64_t nraw, const uint8_t* img,
+                                const float* aux, const float* par, const int64_t* cand_ids, int R, int k, float min_score,
+                                float max_score, float neutral, float* distances, int64_t* labels, const int* qperm,
+                                const TieFlags* ties, unsigned long long* stat, int form) {
+    if (nq <= 0) return 0;
+    if (!rerank_filter_shape_ok(d, R, k) || nraw <= 0 || form < 0 || form > 2) {
         launch_refused("launch_rerank_topk_filtered: a shape its caller rules out");
-        return;
+        return 0;
     }
     const TieFlags tf = ties ? *ties : TieFlags{};
-    const dim3 grid((unsigned)(8 * ((nq + 7) / 8)));
     const float2* ax = reinterpret_cast<const float2*>(aux);
+#if GH_RERANK_TIMING == 6   // timing build: the clock sums so far, every 20 launches
+#ifdef GH_RERANK_TIMING_FORM
+    form = GH_RERANK_TIMING_FORM;
+#endif
+    static int timed_launches = 0;   // (not thread-safe: a timing build is driven by one caller)
+    if (++timed_launches % 20 == 0) {
+        unsigned long long v[16];
+        if (hipStreamSynchronize(s) == hipSuccess && hipMemcpyFromSymbol(v, HIP_SYMBOL(g_phase_clk), sizeof(v)) == hipSuccess && v[15]) {
+            fprintf(stderr, "rerank phase clocks, form %d, %llu workgroups, mean ticks of 10 ns:", form, v[15]);
+            for (int i = 0; i < 8; i++) fprintf(stderr, " %.1f", (double)v[i] / (double)v[15]);
+            fprintf(stderr, "\n");
+        }
+    }
+#endif
+    if (rerank_filter_wave_ok(d, R, k) && (form == 2 || (form == 0 && nq >= kRerankWaveAutoMinNq))) {
+        const dim3 grid((unsigned)(8 * ((nq + 7) / 8)));
+#define GH_FILT_WAVE(L2_)                                                                                                            \
+    hipLaunchKernelGGL((k_rerank_topk_filt_wave<L2_>), grid, dim3(64), 0, s, x, raw, nraw, img, ax, par, cand_ids, R, k, min_score,  \
+                       max_score, neutral, distances, labels, nq, qperm, tf, stat)
+        if (l2) GH_FILT_WAVE(true);
+        else GH_FILT_WAVE(false);
+#undef GH_FILT_WAVE
+        return 2;
+    }
+    const dim3 grid((unsigned)(8 * ((nq + 7) / 8)));
 #define GH_FILT(L2_, D128_)                                                                                                          \
     hipLaunchKernelGGL((k_rerank_topk_filt<L2_, D128_>), grid, dim3(256), 0, s, x, d, raw, nraw, img, ax, par, cand_ids, R, k,      \
                        min_score, max_score, neutral, distances, labels, nq, qperm, tf, stat)
@@ -500,6 +801,7 @@ void launch_rerank_topk_filtered(hipStream_t s, bool l2, const float* x, int nq,
         else GH_FILT(false, false);
     }
 #undef GH_FILT
+    return 1;
 }
 
 }  // namespace gh

@@ -1,6 +1,7 @@
 // rerank_topk_dev.h -- what k_rerank_topk (rerank.hip) and k_rerank_topk_filt (rerank_filter.hip) do with the R (key, candidate
 // rank) items of a query once they stand in LDS: the first k + 1 of them in order, the tie test, the output.  Called by all 256
-// threads of the workgroup.
+// threads of the workgroup.  At the end: the tie test and the output for a query that one wave owns, its first k + 1 items one
+// per lane (k_rerank_topk_filt_wave).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -102,6 +103,48 @@ __device__ __forceinline__ void rerank_topk_out(const unsigned long long* s_it, 
             if (dv != sentinel) {
                 val = dv;
                 id = s_id[(uint32_t)it];
+            }
+        }
+        distances[(int64_t)q * k + i] = val;
+        labels[(int64_t)q * k + i] = id;
+    }
+}
+
+// ---- the same for a query that one wave owns (k_rerank_topk_filt_wave): no workgroup barrier anywhere ----
+// LDS that one lane of a wave wrote and another lane of the same wave reads: the wave's DS instructions execute in program
+// order, so all that is needed is that the compiler keeps that order.
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+// The first K1 = min(k + 1, R) <= 64 items stand one per lane, ascending: `item` of lane i is item i (lanes from K1 on: anything).
+// tie: the query's cut flag (uniform over the wave).  Called by all 64 lanes.
+template <bool L2>
+__device__ __forceinline__ void rerank_topk_out_wave(unsigned long long item, const int64_t* s_id, int tie, int q, int R, int k,
+                                                     float neutral, float* __restrict__ distances, int64_t* __restrict__ labels,
+                                                     const TieFlags& tf) {
+    const float sentinel = L2 ? INFINITY : -INFINITY;
+    const int lane = threadIdx.x & 63;
+    if (tf.list) {
+        const unsigned long long next = __shfl_down(item, 1, 64);
+        const uint32_t ka = (uint32_t)(item >> 32), kb = (uint32_t)(next >> 32);
+        const bool eq = lane < k && lane + 1 < R && ka == kb && ka != (L2 ? f2key(sentinel) : ~f2key(sentinel));
+        if (__ballot(eq)) tie = 1;
+        if (lane == 0 && tie) {
+            tf.list[atomicAdd(tf.count, 1)] = q;
+            if (tf.stats) atomicAdd(tf.stats + 2, 1ull);
+        }
+    }
+    for (int i = lane; i < k; i += 64) {   // (i < k and i < R: i < K1, the lane holds item i)
+        float val = neutral;
+        int64_t id = -1;
+        if (i < R) {
+            const uint32_t key = (uint32_t)(item >> 32);
+            const float dv = key2f(L2 ? key : ~key);
+            if (dv != sentinel) {
+                val = dv;
+                id = s_id[(uint32_t)item];
             }
         }
         distances[(int64_t)q * k + i] = val;

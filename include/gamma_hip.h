@@ -185,6 +185,14 @@ int gamma_hip_coarse_filter_stats(gamma_hip_index* h, int64_t* out4);
  * out5: {candidates the filter saw, candidates that survived it, calls it ran in, times the handle backed off, image rows} */
 int gamma_hip_set_rerank_filter(gamma_hip_index* h, int mode);
 int gamma_hip_rerank_filter_stats(gamma_hip_index* h, int64_t* out5);
+/* The filtered re-rank has two kernels with the same results: one workgroup per query (every shape the filter admits), and one
+ * wave per query (rows of 128 floats, at most 256 candidates per query, min(k + 1, candidates) <= 64).
+ * form: 0 (default) = automatic, the wave form where it is admitted and the call has enough queries to fill the device with
+ * waves (out4[3] says how many); 1 = the workgroup kernel always; 2 = the wave form wherever it is admitted.
+ * out4: {the setting, the kernel of the last filtered call (1 workgroup, 2 wave; 0: none yet), filtered calls in the wave form,
+ * the query count from which automatic takes the wave form} */
+int gamma_hip_set_rerank_filter_form(gamma_hip_index* h, int form);
+int gamma_hip_rerank_filter_form(gamma_hip_index* h, int64_t* out4);
 /* Flat search (GammaFLATIndex::Search, index/impl/gamma_index_flat.cc:118-300) scores every row; here the passes behind the
  * first row chunk run a bf16 filter on the matrix pipe and only its survivors get the reference's arithmetic
  * (csrc/flat_mfma.hip), so results are the reference's bit for bit.  No handle, no device call:
