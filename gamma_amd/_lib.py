@@ -80,6 +80,7 @@ SYMBOLS = {
     "gamma_hip_set_small_path": (C.c_int, [C.c_void_p, C.c_int]),
     "gamma_hip_set_flat_narrow_rows": (C.c_int, [C.c_void_p, C.c_int]),
     "gamma_hip_set_ivfflat_narrow_rows": (C.c_int, [C.c_void_p, C.c_int]),
+    "gamma_hip_set_sparse_narrow_rows": (C.c_int, [C.c_void_p, C.c_int]),
     "gamma_hip_ivfflat_lm_shape": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "gamma_hip_ivfflat_scan_stats": (C.c_int, [C.c_void_p, i64p, C.c_int]),
     "gamma_hip_set_flat_sq8_rows": (C.c_int, [C.c_void_p, C.c_int]),

@@ -803,6 +803,12 @@ class GammaHip:
         False (the default): it refuses one.  Independent of set_flat_narrow_rows."""
         self._ck(self.L.gamma_hip_set_ivfflat_narrow_rows(self.h, 1 if on else 0), "set_ivfflat_narrow_rows")
 
+    def set_sparse_narrow_rows(self, on=True):
+        """True: raw_put / raw_drop and shard_exact / shard_export_exact serve a float16 / uint8 / int8 / sq8 raw store -- rows
+        sharded with their lists in 2 or 1 bytes per element, byte-identical to an fp32 store of the widened rows; False (the
+        default): they refuse one.  Independent of every other switch."""
+        self._ck(self.L.gamma_hip_set_sparse_narrow_rows(self.h, 1 if on else 0), "set_sparse_narrow_rows")
+
     def ivfflat_scan_stats(self, reset=False):
         """(calls the small path served, query chunks scanned by the pair kernel, by the fixed-length list-major kernel, by the
         row-sliced list-major kernel) of ivfflat_search."""

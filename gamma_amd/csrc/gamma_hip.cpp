@@ -303,6 +303,13 @@ int gamma_hip_set_ivfflat_narrow_rows(gamma_hip_index* h, int on) {
     return GAMMA_HIP_OK;
 }
 
+int gamma_hip_set_sparse_narrow_rows(gamma_hip_index* h, int on) {
+    if (!h) return GAMMA_HIP_EINVAL;
+    SearchLock lk(h);
+    h->sparse_narrow_rows = on != 0;
+    return GAMMA_HIP_OK;
+}
+
 int gamma_hip_set_flat_sq8_rows(gamma_hip_index* h, int on) {
     if (!h) return GAMMA_HIP_EINVAL;
     SearchLock lk(h);

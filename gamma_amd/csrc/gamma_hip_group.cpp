@@ -225,6 +225,25 @@ const gamma_group_ext::RawOps*& raw_ops() {
     return ops;
 }
 
+// Narrow raw rows sharded with their lists: the members convert the caller's fp32 rows.  Every member's store has one element
+// type and one set of sq8 ranges -- checked once, when the placement is switched on: neither can change while a store is
+// sparse or holds rows -- so one member's acceptance predicate speaks for all.  It runs over ALL rows of a call before any
+// member is touched: a row a store would refuse fails the call with nothing changed on any member.
+int members_same_rows(gamma_hip_group* g, const char* what) {
+    const gamma_group_ext::RawOps* rops = raw_ops();
+    // (a table without the two entries -- one that registered the fp32 sparse store's only -- has nothing to compare or refuse)
+    for (size_t i = 1; rops && rops->same_rows && i < g->m.size(); i++)
+        if (!rops->same_rows(g->m[0], g->m[i]))
+            return gfail(g, GAMMA_HIP_EINVAL, std::string(what) + ": the members' raw stores differ in element type, row length or sq8 ranges");
+    return GAMMA_HIP_OK;
+}
+int rows_storable(gamma_hip_group* g, int64_t n, const float* vecs) {
+    const gamma_group_ext::RawOps* rops = raw_ops();
+    if (!g->raw_sharded || g->replicate || !rops || !rops->rows_check || g->m.empty()) return GAMMA_HIP_OK;
+    const int rk = rops->rows_check(g->m[0], n, vecs);
+    return rk ? member_fail(g, 0, rk) : GAMMA_HIP_OK;
+}
+
 gamma_group_ext::MemberMarkFn& member_mark() {
     static gamma_group_ext::MemberMarkFn fn = nullptr;
     return fn;
@@ -272,6 +291,8 @@ int set_raw_sharded(gamma_hip_group* g, int sharded) {
     for (size_t i = 0; i < g->m.size(); i++)
         if (rops->raw_count(g->m[i]) != 0) return gfail(g, GAMMA_HIP_EINVAL, "set_raw_placement: before any raw row is written");
     if (sharded) {
+        const int same = members_same_rows(g, "set_raw_placement");
+        if (same) return same;
         // every member's (empty) store takes the sparse form now: a member that owns no vector yet answers all the same
         for (size_t i = 0; i < g->m.size(); i++) {
             const int rc = gamma_hip_raw_put(g->m[i], 0, nullptr, nullptr);
@@ -299,6 +320,10 @@ int raw_put(gamma_hip_group* g, int64_t n, const int64_t* vids, const float* vec
     const int W = (int)g->m.size();
     const int d = gamma_hip_ivfpq_dim(g->m[0]);
     if (d <= 0) return gfail(g, GAMMA_HIP_EINVAL, "raw_put: members not initialised");
+    {
+        const int rk = rows_storable(g, n, vecs);
+        if (rk) return rk;
+    }
     std::vector<int> where(n, -1);
     std::vector<uint8_t> has(n);
     for (int i = 0; i < W; i++) {
@@ -498,6 +523,10 @@ int gamma_hip_group_ivfpq_add(gamma_hip_group* g, int64_t n, const float* vecs, 
     if (cs <= 0) return gfail(g, GAMMA_HIP_EINVAL, "add: members not initialised");
     const int d = gamma_hip_ivfpq_dim(g->m[e]);
     const bool rows = g->raw_sharded && !g->replicate;   // every vector's row goes to the owner of its list, with its keys
+    {
+        const int rk = rows_storable(g, n, vecs);
+        if (rk) return rk;
+    }
     std::vector<float> gvecs;
     std::vector<int64_t> lno(n);
     std::vector<uint8_t> codes((size_t)n * cs);
@@ -586,6 +615,10 @@ int gamma_hip_group_ivfpq_update(gamma_hip_group* g, int n, const int64_t* vids,
     const int e = g->next_enc++ % W;
     const int cs = gamma_hip_ivfpq_code_size(g->m[e]);
     if (cs <= 0) return gfail(g, GAMMA_HIP_EINVAL, "update: bad code size");
+    {
+        const int rk = rows_storable(g, n, vecs);
+        if (rk) return rk;
+    }
     std::vector<int64_t> lno(n);
     std::vector<uint8_t> codes((size_t)n * cs);
     int rc = gamma_hip_ivfpq_encode_each(g->m[e], n, vecs, lno.data(), codes.data());

@@ -16,6 +16,9 @@ struct RawOps {
     int (*raw_drop)(gamma_hip_index*, int64_t, const int64_t*);
     int64_t (*raw_count)(gamma_hip_index*);
     int (*raw_clear)(gamma_hip_index*);
+    // narrow rows sharded with their lists (gamma_hip_set_sparse_narrow_rows): the members convert, the group only asks
+    int (*rows_check)(gamma_hip_index*, int64_t n, const float* vecs);   // the store's acceptance predicate over n rows, nothing written
+    int (*same_rows)(gamma_hip_index*, gamma_hip_index*);                // 1: one element type, row length and sq8 ranges
 };
 int register_raw_ops(const RawOps* ops);   // returns 1 (a value for a static initialiser)
 

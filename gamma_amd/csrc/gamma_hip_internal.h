@@ -390,6 +390,9 @@ struct gamma_hip_index {
     bool small_path = true;    // gamma_hip_set_small_path
     bool flat_narrow_rows = false;   // gamma_hip_set_flat_narrow_rows: flat search serves a float16 / uint8 / int8 raw store
     bool ivfflat_narrow_rows = false;   // gamma_hip_set_ivfflat_narrow_rows: the same for the IVFFLAT search
+    // gamma_hip_set_sparse_narrow_rows: gamma_hip_raw_put / _raw_drop and the shard's exact entries serve a float16 / uint8 /
+    // int8 / sq8 raw store (rows sharded with their lists in 2 or 1 bytes per element)
+    bool sparse_narrow_rows = false;
     bool flat_sq8_rows = false;      // gamma_hip_set_flat_sq8_rows: flat search serves an sq8 raw store
     bool ivfflat_sq8_rows = false;   // gamma_hip_set_ivfflat_sq8_rows: the same for the IVFFLAT search
     int small_presel = 0;      // 0: pre-selection by estimate, > 0: always, that many slices (tests)
@@ -523,6 +526,13 @@ inline DevExclusive& writer_exclusive(H* h) {
     } nobody;
     return h->wl ? static_cast<DevExclusive&>(*h->wl) : nobody;
 }
+
+// The raw store towards a caller that holds several handles (gamma_hip_store.cpp; the group reaches them through its table,
+// gamma_hip_group_rawshard.cpp).  raw_rows_check: the store's own acceptance predicate over n caller rows, nothing written --
+// GAMMA_HIP_OK, or the refusal of the store's writers with their message (an fp32 store takes everything).  raw_same_rows: both
+// stores hold rows of one element type and length, an sq8 store decoded through the same ranges (or neither has any yet).
+int raw_rows_check(H* h, int64_t n, const float* vecs);
+bool raw_same_rows(H* a, H* b);
 
 // the raw store's rows as the kernels of every element type take them (kernels.h): base pointer, element type and, for an sq8
 // store, the decode table

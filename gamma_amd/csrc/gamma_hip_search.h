@@ -95,6 +95,9 @@ static inline bool raw_store_served(const H* h, bool narrow_rows, bool sq8_rows)
     if (h->raw_narrow()) return narrow_rows;   // float16, uint8, int8
     return true;   // fp32 rows
 }
+// the shard's exact entries (gamma_hip_ivfpq_shard_exact / _shard_export_exact): fp32 rows always, a narrow store of either kind
+// after gamma_hip_set_sparse_narrow_rows
+static inline bool shard_exact_served(const H* h) { return raw_store_served(h, h->sparse_narrow_rows, h->sparse_narrow_rows); }
 static inline int raw_store_refuse(H* h, const char* what) {
     const int t = h->raw_elem_type();
     const char* store = t == 4 ? "sq8 raw store (gamma_hip_raw_init_sq8): "

@@ -274,12 +274,12 @@ int gamma_hip_ivfpq_shard_exact(gamma_hip_index* h, const gamma_hip_search_param
     if (!d_x || !d_ids || !d_exact) return GAMMA_HIP_EINVAL;
     SearchLock lk(h);
     GH_NO_PQ4(h, "gamma_hip_ivfpq_shard_exact");
-    if (!raw_store_served(h, false, false)) return raw_store_refuse(h, "gamma_hip_ivfpq_shard_exact");
+    if (!shard_exact_served(h)) return raw_store_refuse(h, "gamma_hip_ivfpq_shard_exact");
     GH_TRY(replay_join(h));
-    if (!h->raw_f32() || h->raw_d != h->d) return fail(h, GAMMA_HIP_EINVAL, "no raw store");
+    if (!h->has_raw_rows() || h->raw_d != h->d) return fail(h, GAMMA_HIP_EINVAL, "no raw store");
     GH_CHECK(h, hipSetDevice(h->device));
     // (a dense store answers for every id; a sharded one for the vectors it holds, the sentinel elsewhere)
-    gh::launch_rerank_dist(h->stream, p->metric == GAMMA_HIP_METRIC_L2, d_x, nq, h->d, gh::RowsRef{h->raw_f32()}, h->nraw, d_ids, R, p->min_score,
+    gh::launch_rerank_dist(h->stream, p->metric == GAMMA_HIP_METRIC_L2, d_x, nq, h->d, raw_rows_ref(h), h->nraw, d_ids, R, p->min_score,
                            p->max_score, d_exact, h->raw_sparse ? h->d_raw_slot.get() : nullptr, h->raw_sparse ? h->raw_slot_cap() : 0);
     GH_CHECK(h, hipGetLastError());
     return GAMMA_HIP_OK;
@@ -293,10 +293,10 @@ int gamma_hip_ivfpq_shard_export_exact(gamma_hip_index* h, const gamma_hip_searc
     if (!d_xf || !d_vals || !d_ids || !d_off || !d_bound_f || !d_ex || stride < 1) return GAMMA_HIP_EINVAL;
     SearchLock lk(h);
     GH_NO_PQ4(h, "gamma_hip_ivfpq_shard_export_exact");
-    if (!raw_store_served(h, false, false)) return raw_store_refuse(h, "gamma_hip_ivfpq_shard_export_exact");
-    if (!h->raw_f32() || h->raw_d != h->d || !h->raw_sparse) return fail(h, GAMMA_HIP_EINVAL, "export of exact distances: a sharded raw store (gamma_hip_raw_put)");
+    if (!shard_exact_served(h)) return raw_store_refuse(h, "gamma_hip_ivfpq_shard_export_exact");
+    if (!h->has_raw_rows() || h->raw_d != h->d || !h->raw_sparse) return fail(h, GAMMA_HIP_EINVAL, "export of exact distances: a sharded raw store (gamma_hip_raw_put)");
     GH_CHECK(h, hipSetDevice(h->device));
-    gh::launch_export_exact(h->stream, p->metric == GAMMA_HIP_METRIC_L2, d_xf, nf, h->d, h->raw_f32(), h->d_raw_slot, h->raw_slot_cap(),
+    gh::launch_export_exact(h->stream, p->metric == GAMMA_HIP_METRIC_L2, d_xf, nf, h->d, raw_rows_ref(h), h->d_raw_slot, h->raw_slot_cap(),
                             d_vals, d_ids, stride, d_off, p->nprobe, d_bound_f, d_ex);
     GH_CHECK(h, hipGetLastError());
     return GAMMA_HIP_OK;

@@ -591,6 +591,8 @@ int gamma_hip_raw_sq8_params(int d, const float* vmin, const float* vmax, float*
 static int sq8_set_ranges_locked(H* h, const float* vmin, const float* vmax) {
     if (h->raw_et != gh::ROW_SQ8) return fail(h, GAMMA_HIP_EINVAL, "gamma_hip_raw_sq8_set_ranges: the raw store is not an sq8 store (gamma_hip_raw_init_sq8)");
     if (h->nraw > 0) return fail(h, GAMMA_HIP_EINVAL, "gamma_hip_raw_sq8_set_ranges: the sq8 raw store holds rows; the ranges change only while it is empty (after gamma_hip_raw_clear)");
+    // (members of a group are compared once, when their stores take the sparse form: the ranges are fixed from then on)
+    if (h->raw_sparse) return fail(h, GAMMA_HIP_EINVAL, "gamma_hip_raw_sq8_set_ranges: the sq8 raw store has taken its sparse form (gamma_hip_raw_put); the ranges change only before that (after gamma_hip_raw_clear)");
     const int d = h->raw_d;
     std::vector<float> step(d), inv(d);
     if (gamma_hip_raw_sq8_params(d, vmin, vmax, step.data(), inv.data()) != GAMMA_HIP_OK)
@@ -754,7 +756,8 @@ int gamma_hip_raw_put(gamma_hip_index* h, int64_t n, const int64_t* vids, const 
     if (!h || n < 0 || (n > 0 && (!vids || !vecs))) return GAMMA_HIP_EINVAL;
     WriteLock lk(h);
     if (h->raw_d <= 0) return fail(h, GAMMA_HIP_EINVAL, "raw store not initialised");
-    if (h->raw_narrow()) return fail(h, GAMMA_HIP_EUNSUPPORTED, narrow_store_name(h));   // rows sharded with their lists are fp32
+    // (rows sharded with their lists are fp32 unless gamma_hip_set_sparse_narrow_rows says otherwise)
+    if (h->raw_narrow() && !h->sparse_narrow_rows) return fail(h, GAMMA_HIP_EUNSUPPORTED, narrow_store_name(h));
     if (!h->raw_sparse && h->nraw > 0) return fail(h, GAMMA_HIP_EINVAL, "raw_put on a store that holds rows by vector id");
     if (n == 0) {   // the first call turns the empty store into the sparse form, rows or not (a shard that owns no vector yet)
         if (!h->raw_sparse) {
@@ -769,6 +772,8 @@ int gamma_hip_raw_put(gamma_hip_index* h, int64_t n, const int64_t* vids, const 
         if (vids[i] < 0 || vids[i] >= ((int64_t)1 << 31)) return fail(h, GAMMA_HIP_EINVAL, "raw_put: vector id out of range");
         hi = std::max(hi, vids[i]);
     }
+    // a narrow store: the whole batch is storable, or the call fails here with nothing changed (an sq8 store: ranges first)
+    GH_TRY(raw_narrow_check(h, n * h->raw_d, vecs));
     // the row of every entry; nothing of the handle changes before the device memory is there
     std::vector<int32_t> pairs((size_t)n * 2);
     std::unordered_map<int64_t, int64_t> seen;   // vid -> its latest entry of this batch (the last one named wins)
@@ -811,10 +816,19 @@ int gamma_hip_raw_put(gamma_hip_index* h, int64_t n, const int64_t* vids, const 
     GH_TRY(raw_reserve(h, h->nraw + grow));
     GH_TRY(raw_slot_reserve(h, hi));
     GH_CHECK(h, h->we_chk.ensure((size_t)n * 2 * sizeof(int32_t)));
-    if (!in_order) GH_CHECK(h, h->we_stage.ensure((size_t)n * h->raw_d * sizeof(float)));
+    if (!in_order && !h->raw_narrow()) GH_CHECK(h, h->we_stage.ensure((size_t)n * h->raw_d * sizeof(float)));
     h->raw_sparse = true;
+    std::vector<int64_t> rows;   // (a narrow store's target rows: read by the copy below until the stream is drained)
+    if (h->raw_narrow()) {
+        // converted on the device by the store's writer, into the batch's rows (a superseded entry's is -1: skipped).  The
+        // writer's row list goes through the buffer the pairs take behind it, in stream order.
+        rows.resize((size_t)n);
+        for (int64_t i = 0; i < n; i++) rows[i] = pairs[2 * i + 1];
+        GH_TRY(raw_narrow_rows_in(h, 0, rows.data(), n, vecs, h->raw_cap()));
+    }
     GH_CHECK(h, hipMemcpyAsync(h->we_chk.p, pairs.data(), (size_t)n * 2 * sizeof(int32_t), hipMemcpyHostToDevice, h->wstream));
-    if (in_order) {
+    if (h->raw_narrow()) {   // (in place already)
+    } else if (in_order) {
         GH_TRY(raw_rows_in(h, h->nraw, n, vecs, h->raw_cap()));
     } else {
         GH_CHECK(h, hipMemcpyAsync(h->we_stage.p, vecs, (size_t)n * h->raw_d * sizeof(float), hipMemcpyHostToDevice, h->wstream));
@@ -838,7 +852,7 @@ int gamma_hip_raw_put(gamma_hip_index* h, int64_t n, const int64_t* vids, const 
 int gamma_hip_raw_drop(gamma_hip_index* h, int64_t n, const int64_t* vids) {
     if (!h || n < 0 || (n > 0 && !vids)) return GAMMA_HIP_EINVAL;
     WriteLock lk(h);
-    if (h->raw_narrow()) return fail(h, GAMMA_HIP_EUNSUPPORTED, narrow_store_name(h));
+    if (h->raw_narrow() && !h->sparse_narrow_rows) return fail(h, GAMMA_HIP_EUNSUPPORTED, narrow_store_name(h));
     if (!h->raw_sparse) {
         if (h->nraw > 0) return fail(h, GAMMA_HIP_EINVAL, "raw_drop on a store that holds rows by vector id");
         return GAMMA_HIP_OK;   // empty: nothing to forget
@@ -1825,3 +1839,29 @@ int gamma_hip_ivfpq_add(gamma_hip_index* h, int64_t n, const float* vecs, int64_
 }
 
 }  // extern "C"
+
+// ---- the store's answers to a caller that holds several handles (gamma_hip_internal.h; the group asks through its table) -------
+namespace ghi {
+
+int raw_rows_check(H* h, int64_t n, const float* vecs) {
+    if (!h || n < 0 || (n > 0 && !vecs)) return GAMMA_HIP_EINVAL;
+    std::lock_guard<std::mutex> g(h->mu);
+    if (h->raw_d <= 0) return GAMMA_HIP_OK;
+    return raw_narrow_check(h, n * h->raw_d, vecs);
+}
+
+bool raw_same_rows(H* a, H* b) {
+    if (!a || !b) return false;
+    int et, d;
+    std::vector<float> lo, hi;
+    {
+        std::lock_guard<std::mutex> g(a->mu);
+        et = a->raw_et, d = a->raw_d, lo = a->sq8_vmin, hi = a->sq8_vmax;
+    }
+    std::lock_guard<std::mutex> g(b->mu);
+    if (b->raw_et != et || b->raw_d != d || lo.size() != b->sq8_vmin.size()) return false;
+    return lo.empty() || (memcmp(lo.data(), b->sq8_vmin.data(), lo.size() * sizeof(float)) == 0 &&
+                          memcmp(hi.data(), b->sq8_vmax.data(), hi.size() * sizeof(float)) == 0);
+}
+
+}  // namespace ghi

@@ -444,15 +444,16 @@ void launch_map_candidates(hipStream_t s, const int* pos, int nq, int R, int P,
 // through raw.tab in front of the fma chain) row in the same operation order.  How a row is loaded depends on its type and d
 // (rerank_dev.h): float16 rows with d % 8 == 0 with one 16-byte load per lane, every other d with 2-byte loads; byte and sq8 rows
 // with d % 16 == 0 with 16-byte loads, d % 4 == 0 with dword loads, every other d with byte loads.
-// slot / nslot: the vid -> row table of a sparse store (below), fp32 rows only -- refused with any other element type.
+// slot / nslot: the vid -> row table of a sparse store (below), rows of any element type.
 void launch_rerank_dist(hipStream_t s, bool l2, const float* x, int nq, int d, const RowsRef& raw,
                         int64_t nraw, const int64_t* cand_ids, int R, float min_score,
                         float max_score, float* out, const int32_t* slot = nullptr, int64_t nslot = 0);
 // raw vectors sharded with their lists (round 6).  slot [nslot]: vector id -> row of `raw` on THIS shard, -1 = held elsewhere.
 // _export_exact: ex[f][j] = exact distance (no score window) of entry j of exported stream row f when its ADC value is
-// within bound[f] and its vector is held here, NaN otherwise.  _lookup_exact: cand_exact[q][r] = the exact distance that
-// travelled with candidate cand_ids[q][r] in one of the W shard tables (all_ids / all_exact [W][nq][R]), sentinel if none.
-void launch_export_exact(hipStream_t s, bool l2, const float* xf, int nf, int d, const float* raw, const int32_t* slot, int64_t nslot,
+// within bound[f] and its vector is held here, NaN otherwise (raw: the sparse store's rows, of any element type).
+// _lookup_exact: cand_exact[q][r] = the exact distance that travelled with candidate cand_ids[q][r] in one of the W shard
+// tables (all_ids / all_exact [W][nq][R]), sentinel if none.
+void launch_export_exact(hipStream_t s, bool l2, const float* xf, int nf, int d, const RowsRef& raw, const int32_t* slot, int64_t nslot,
                          const float* vals, const int64_t* ids, int64_t stride, const int32_t* off, int P, const float* bound, float* ex);
 void launch_lookup_exact(hipStream_t s, bool l2, const float* all_dis, const int64_t* all_ids, const float* all_exact, int W, int nq, int R,
                          int q0, int nql, const float* cand_dis, const int64_t* cand_ids, float* cand_exact);

@@ -95,25 +95,21 @@ void launch_rerank_dist(hipStream_t s, bool l2, const float* x, int nq, int d, c
                         const int64_t* cand_ids, int R, float min_score, float max_score, float* out, const int32_t* slot,
                         int64_t nslot) {
     if (nq <= 0) return;
-    if (slot && raw.et != ROW_F32) {   // a sparse store holds fp32 rows
-        launch_refused("launch_rerank_dist: a slot table over rows that are not fp32");
-        return;
-    }
-    switch (raw.et) {
+    switch (raw.et) {   // (slot: a sparse store's table, rows of any element type)
         case ROW_F32:
             launch_rerank_dist_t(s, l2, x, nq, d, raw.as<float>(), nullptr, nraw, cand_ids, R, min_score, max_score, out, slot, nslot);
             break;
         case ROW_F16:
-            launch_rerank_dist_t(s, l2, x, nq, d, raw.as<uint16_t>(), nullptr, nraw, cand_ids, R, min_score, max_score, out, nullptr, 0);
+            launch_rerank_dist_t(s, l2, x, nq, d, raw.as<uint16_t>(), nullptr, nraw, cand_ids, R, min_score, max_score, out, slot, nslot);
             break;
         case ROW_U8:
-            launch_rerank_dist_t(s, l2, x, nq, d, raw.as<uint8_t>(), nullptr, nraw, cand_ids, R, min_score, max_score, out, nullptr, 0);
+            launch_rerank_dist_t(s, l2, x, nq, d, raw.as<uint8_t>(), nullptr, nraw, cand_ids, R, min_score, max_score, out, slot, nslot);
             break;
         case ROW_I8:
-            launch_rerank_dist_t(s, l2, x, nq, d, raw.as<int8_t>(), nullptr, nraw, cand_ids, R, min_score, max_score, out, nullptr, 0);
+            launch_rerank_dist_t(s, l2, x, nq, d, raw.as<int8_t>(), nullptr, nraw, cand_ids, R, min_score, max_score, out, slot, nslot);
             break;
         case ROW_SQ8:   // (codes are never numbers: an sq8 store goes to the decoding kernel or nowhere)
-            launch_rerank_dist_t(s, l2, x, nq, d, raw.as<sq8_t>(), raw.tab, nraw, cand_ids, R, min_score, max_score, out, nullptr, 0);
+            launch_rerank_dist_t(s, l2, x, nq, d, raw.as<sq8_t>(), raw.tab, nraw, cand_ids, R, min_score, max_score, out, slot, nslot);
             break;
         default: launch_refused("launch_rerank_dist: unknown row element type"); break;
     }
@@ -122,11 +118,14 @@ void launch_rerank_dist(hipStream_t s, bool l2, const float* x, int nq, int d, c
 // Exact distances of the entries of an exported candidate stream that can still be members of the recall_num-heap: ADC value
 // within the query's bound and vector held on this shard.  One workgroup per exported row: the entries that qualify are
 // compacted 256 at a time (ballot), then scored 32 at a time, 8 lanes each (rerank_dist8: the arithmetic of k_rerank_topk).
-template <bool L2>
-__global__ __launch_bounds__(256) void k_export_exact(const float* __restrict__ xf, int d, const float* __restrict__ raw,
-                                                      const int32_t* __restrict__ slot, int64_t nslot, const float* __restrict__ vals,
-                                                      const int64_t* __restrict__ ids, int64_t stride, const int32_t* __restrict__ off,
-                                                      int P, const float* __restrict__ bound, float* __restrict__ ex) {
+// ROW: the sparse store's element type, as in k_rerank_dist -- a narrow row is widened exactly as it is loaded (rerank_dev.h),
+// an sq8_t row decoded through tab (null and unread for every other row type).
+template <bool L2, typename ROW>
+__global__ __launch_bounds__(256) void k_export_exact(const float* __restrict__ xf, int d, const ROW* __restrict__ raw,
+                                                      const float2* __restrict__ tab, const int32_t* __restrict__ slot, int64_t nslot,
+                                                      const float* __restrict__ vals, const int64_t* __restrict__ ids, int64_t stride,
+                                                      const int32_t* __restrict__ off, int P, const float* __restrict__ bound,
+                                                      float* __restrict__ ex) {
     __shared__ int s_pos[256];
     __shared__ int s_row[256];
     __shared__ int s_n;
@@ -165,18 +164,53 @@ __global__ __launch_bounds__(256) void k_export_exact(const float* __restrict__ 
         for (int c0 = 0; c0 < m; c0 += 32) {   // uniform trip count
             const int c = c0 + g;
             const bool live = c < m;
-            const float dis = rerank_dist8<L2>(xq, raw + (int64_t)(live ? s_row[c] : 0) * d, d, l8, live);
+            const int64_t rw = live ? s_row[c] : 0;
+            float dis;
+            if constexpr (std::is_same<ROW, sq8_t>::value)
+                dis = rerank_dist8_sq8<L2>(xq, reinterpret_cast<const uint8_t*>(raw) + rw * d, tab, d, l8, live);
+            else
+                dis = rerank_dist8<L2>(xq, raw + rw * d, d, l8, live);
             if (l8 == 0 && live) ex[(int64_t)f * stride + s_pos[c]] = dis;
         }
         __syncthreads();
         (void)wv;
     }
 }
-void launch_export_exact(hipStream_t s, bool l2, const float* xf, int nf, int d, const float* raw, const int32_t* slot, int64_t nslot,
+namespace {
+template <typename ROW>
+void launch_export_exact_t(hipStream_t s, bool l2, const float* xf, int nf, int d, const ROW* raw, const float* tab, const int32_t* slot,
+                           int64_t nslot, const float* vals, const int64_t* ids, int64_t stride, const int32_t* off, int P,
+                           const float* bound, float* ex) {
+    const float2* t = reinterpret_cast<const float2*>(tab);
+    if (l2)
+        hipLaunchKernelGGL((k_export_exact<true, ROW>), dim3(nf), dim3(256), 0, s, xf, d, raw, t, slot, nslot, vals, ids, stride, off, P,
+                           bound, ex);
+    else
+        hipLaunchKernelGGL((k_export_exact<false, ROW>), dim3(nf), dim3(256), 0, s, xf, d, raw, t, slot, nslot, vals, ids, stride, off, P,
+                           bound, ex);
+}
+}  // namespace
+void launch_export_exact(hipStream_t s, bool l2, const float* xf, int nf, int d, const RowsRef& raw, const int32_t* slot, int64_t nslot,
                          const float* vals, const int64_t* ids, int64_t stride, const int32_t* off, int P, const float* bound, float* ex) {
     if (nf <= 0) return;
-    if (l2) hipLaunchKernelGGL((k_export_exact<true>), dim3(nf), dim3(256), 0, s, xf, d, raw, slot, nslot, vals, ids, stride, off, P, bound, ex);
-    else hipLaunchKernelGGL((k_export_exact<false>), dim3(nf), dim3(256), 0, s, xf, d, raw, slot, nslot, vals, ids, stride, off, P, bound, ex);
+    switch (raw.et) {
+        case ROW_F32:
+            launch_export_exact_t(s, l2, xf, nf, d, raw.as<float>(), nullptr, slot, nslot, vals, ids, stride, off, P, bound, ex);
+            break;
+        case ROW_F16:
+            launch_export_exact_t(s, l2, xf, nf, d, raw.as<uint16_t>(), nullptr, slot, nslot, vals, ids, stride, off, P, bound, ex);
+            break;
+        case ROW_U8:
+            launch_export_exact_t(s, l2, xf, nf, d, raw.as<uint8_t>(), nullptr, slot, nslot, vals, ids, stride, off, P, bound, ex);
+            break;
+        case ROW_I8:
+            launch_export_exact_t(s, l2, xf, nf, d, raw.as<int8_t>(), nullptr, slot, nslot, vals, ids, stride, off, P, bound, ex);
+            break;
+        case ROW_SQ8:   // (codes are never numbers: an sq8 store goes to the decoding kernel or nowhere)
+            launch_export_exact_t(s, l2, xf, nf, d, raw.as<sq8_t>(), raw.tab, slot, nslot, vals, ids, stride, off, P, bound, ex);
+            break;
+        default: launch_refused("launch_export_exact: unknown row element type"); break;
+    }
 }
 
 // The exact distance that travelled with each candidate of the merged table: every shard's table row is sorted by ADC value, a

@@ -13,6 +13,8 @@
 #include <sys/stat.h>
 
 #include <algorithm>
+#include <cmath>
+#include <limits>
 #include <random>
 
 namespace tig_gamma {
@@ -145,6 +147,40 @@ int HIPIVFPQModelParams::Parse(const char *str) {
     if (v > 0) opq_nsubvector = v;
   }
   if (ncentroids <= 0 || nsubvector <= 0 || nbits_per_idx <= 0) return -1;
+  return 0;
+}
+
+// What "raw_placement" and "raw_dtype" ask of the devices, decided before one is opened: 0, or -2 behind one log line.
+// A narrow raw_dtype goes with several devices only where the rows are sharded with their lists (the members' sparse stores
+// convert: gamma_hip_set_sparse_narrow_rows); replicated rows are fp32, and sq8 keeps to one device (its trained ranges would
+// have to reach every member).
+int HIPIVFPQModelParams::CheckRawKeys() const {
+  const HIPRawShardOps *rawshard = raw_sharded ? FindHIPRawShard() : nullptr;
+  if (raw_sharded && (devices.size() < 2 || replicate || !rawshard)) {
+    HLOG("raw_placement = sharded needs several devices and placement = shard%s",
+         rawshard ? "" : " (and this build of the plugin carries no sharded raw rows)");
+    return -2;
+  }
+  const bool several = devices.size() > 1 && !rawshard;   // several devices whose rows are replicated
+  const HIPRawInitFn raw_init_f16 = raw_f16 ? FindHIPRawInitF16() : nullptr;
+  if (raw_f16 && (!raw_init_f16 || several)) {
+    HLOG("raw_dtype = float16 %s", raw_init_f16 ? "with several devices is not supported (the group's members hold fp32 rows)"
+                                                : "is not supported by this build of the plugin (it carries no float16 raw store)");
+    return -2;
+  }
+  const HIPRawI8Ops *raw_i8_ops = raw_i8 ? FindHIPRawI8() : nullptr;
+  if (raw_i8 && (!raw_i8_ops || several)) {
+    HLOG("raw_dtype = %s %s", raw_i8 == 2 ? "int8" : "uint8",
+         raw_i8_ops ? "with several devices is not supported (the group's members hold fp32 rows)"
+                     : "is not supported by this build of the plugin (it carries no 8-bit raw store)");
+    return -2;
+  }
+  const HIPRawSq8Ops *raw_sq8_ops = raw_sq8 ? FindHIPRawSq8() : nullptr;
+  if (raw_sq8 && (!raw_sq8_ops || devices.size() > 1)) {
+    HLOG("raw_dtype = sq8 %s", raw_sq8_ops ? "with several devices is not supported (the group's members hold fp32 rows)"
+                                           : "is not supported by this build of the plugin (it carries no sq8 raw store)");
+    return -2;
+  }
   return 0;
 }
 
@@ -310,36 +346,14 @@ int GammaIVFPQHIPIndex::Init(const std::string &model_parameters, int indexing_s
     HLOG("device_filters with several devices is not supported (the columns live on one handle)");
     return -2;
   }
-  if (pa.raw_sharded) {
-    rawshard_ = FindHIPRawShard();
-    if (pa.devices.size() < 2 || pa.replicate || !rawshard_) {
-      HLOG("raw_placement = sharded needs several devices and placement = shard%s",
-           rawshard_ ? "" : " (and this build of the plugin carries no sharded raw rows)");
-      return -2;
-    }
-  }
+  if (const int krc = pa.CheckRawKeys()) return krc;   // "raw_placement" / "raw_dtype" against the devices and this build
+  rawshard_ = pa.raw_sharded ? FindHIPRawShard() : nullptr;
   const HIPRawInitFn raw_init_f16 = pa.raw_f16 ? FindHIPRawInitF16() : nullptr;
-  if (pa.raw_f16 && (!raw_init_f16 || pa.devices.size() > 1)) {
-    HLOG("raw_dtype = float16 %s", raw_init_f16 ? "with several devices is not supported (the group's members hold fp32 rows)"
-                                                : "is not supported by this build of the plugin (it carries no float16 raw store)");
-    return -2;
-  }
   raw_f16_ = pa.raw_f16;
   const HIPRawI8Ops *raw_i8_ops = pa.raw_i8 ? FindHIPRawI8() : nullptr;
-  if (pa.raw_i8 && (!raw_i8_ops || pa.devices.size() > 1)) {
-    HLOG("raw_dtype = %s %s", pa.raw_i8 == 2 ? "int8" : "uint8",
-         raw_i8_ops ? "with several devices is not supported (the group's members hold fp32 rows)"
-                     : "is not supported by this build of the plugin (it carries no 8-bit raw store)");
-    return -2;
-  }
   raw_i8_ = pa.raw_i8;
   raw_i8_ops_ = raw_i8_ops;
   const HIPRawSq8Ops *raw_sq8_ops = pa.raw_sq8 ? FindHIPRawSq8() : nullptr;
-  if (pa.raw_sq8 && (!raw_sq8_ops || pa.devices.size() > 1)) {
-    HLOG("raw_dtype = sq8 %s", raw_sq8_ops ? "with several devices is not supported (the group's members hold fp32 rows)"
-                                           : "is not supported by this build of the plugin (it carries no sq8 raw store)");
-    return -2;
-  }
   raw_sq8_ops_ = raw_sq8_ops;
   if (OpenDevices(pa.devices, pa.replicate)) return -1;
   int rc = ForAll([&](gamma_hip_index *m) {
@@ -347,6 +361,7 @@ int GammaIVFPQHIPIndex::Init(const std::string &model_parameters, int indexing_s
     int r = lists_init ? lists_init(m, d_, nlist_, M_, metric, pa.bucket_init_size, pa.bucket_max_size)
                        : gamma_hip_ivfpq_init(m, d_, nlist_, M_, 8, metric, pa.bucket_init_size, pa.bucket_max_size);
     if (!r) r = raw_sq8_ops ? raw_sq8_ops->init(m, d_) : raw_i8_ops ? raw_i8_ops->init(m, d_, pa.raw_i8 == 2) : raw_init_f16 ? raw_init_f16(m, d_) : gamma_hip_raw_init(m, d_);
+    if (!r && rawshard_ && (raw_init_f16 || raw_i8_ops)) r = rawshard_->narrow_rows(m, 1);
     if (!r) r = gamma_hip_set_exact_ties(m, pa.exact_ties ? 1 : 0);
     if (!r && pa.perf_stages) r = gamma_hip_profile_enable(m, 1);
     return r;
@@ -505,6 +520,19 @@ bool GammaIVFPQHIPIndex::RowsStorable(const char *what, const float *x, int64_t 
     fprintf(stderr, "[HIPIVFPQ] %s refused: raw_dtype = sq8 stores a value only if it is finite, and element %d of row %lld is %g\n",
             what, (int)(bad % d_), (long long)(bad / d_), (double)x[bad]);
     return false;
+  }
+  if (raw_f16_ && rawshard_) {
+    // float16 rows sharded with their lists: the members' rule (a finite value that rounds to an infinite half is refused), here
+    // so that a refused Add comes before the placement switches and before any member is asked
+    for (int64_t i = 0; i < nrows * d_; i++) {
+      const float a = std::fabs(x[i]);
+      if (a >= 65520.f && a != std::numeric_limits<float>::infinity()) {
+        fprintf(stderr, "[HIPIVFPQ] %s refused: raw_dtype = float16 stores a finite value only inside binary16's range, and element %d of row %lld is %g\n",
+                what, (int)(i % d_), (long long)(i / d_), (double)x[i]);
+        return false;
+      }
+    }
+    return true;
   }
   return !raw_i8_ || HIPRowsStorableI8(raw_i8_ops_, raw_i8_ == 2, d_, "HIPIVFPQ", what, x, nrows);
 }

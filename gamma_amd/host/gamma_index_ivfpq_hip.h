@@ -63,6 +63,9 @@ struct HIPRawShardOps {
   int (*set_raw_placement)(gamma_hip_group *g, int sharded);
   int (*group_raw_put)(gamma_hip_group *g, int64_t n, const int64_t *vids, const float *vecs, int64_t *n_skipped);
   int (*raw_clear)(gamma_hip_index *h);
+  // "raw_dtype": "float16" | "uint8" | "int8" beside it: the members' stores serve narrow rows sharded with their lists
+  // (gamma_hip_set_sparse_narrow_rows)
+  int (*narrow_rows)(gamma_hip_index *h, int on);
 };
 int RegisterHIPRawShard(const HIPRawShardOps *ops);
 const HIPRawShardOps *FindHIPRawShard();
@@ -158,12 +161,17 @@ struct HIPIVFPQModelParams {
   bool raw_sharded = false;      // HIP only: "raw_placement": "sharded" -- with several devices and list placement every raw
                                  // vector lives once, on the device that owns its list; "replicated" (default): on all
   bool raw_f16 = false;          // HIP only: "raw_dtype": "float16" -- the device's raw rows (what compute_dis reads) are IEEE
-                                 // binary16, rounded from the engine's fp32 on upload; "float32" (default).  One device only.
+                                 // binary16, rounded from the engine's fp32 on upload; "float32" (default).  Several devices:
+                                 // with "raw_placement": "sharded" only.
   int raw_i8 = 0;                // HIP only: "raw_dtype": "uint8" (1) | "int8" (2) -- the device's raw rows are one byte per
-                                 // element; a row that does not convert exactly is refused by Add / Update.  One device only.
+                                 // element; a row that does not convert exactly is refused by Add / Update.  Several devices:
+                                 // with "raw_placement": "sharded" only (as "float16").
   bool raw_sq8 = false;          // HIP only: "raw_dtype": "sq8" -- the device's raw rows are one scalar-quantised byte per element
                                  // (lossy; ranges = per-dimension minimum / maximum of the training rows).  One device only.
   int Parse(const char *str);   // 0 ok, -1 bad (same rules as gamma_index_ivfpq.h:708-851)
+  // "raw_placement" / "raw_dtype" against "devices" / "placement" and what this build of the plugin carries, as HIPIVFPQ::Init
+  // decides it before a device is opened: 0 accepted, -2 rejected behind one log line
+  int CheckRawKeys() const;
 };
 
 class GammaIVFPQHIPIndex : public RetrievalModel {
@@ -236,7 +244,7 @@ class GammaIVFPQHIPIndex : public RetrievalModel {
   bool raw_f16_ = false;               // "raw_dtype": "float16": no device holds fp32 rows -- brute-force search is refused
   int raw_i8_ = 0;                     // "raw_dtype": "uint8" (1) | "int8" (2): likewise
   const HIPRawI8Ops *raw_i8_ops_ = nullptr;
-  bool RowsStorable(const char *what, const float *x, int64_t nrows);   // byte / sq8 store: one log line for the first refused value
+  bool RowsStorable(const char *what, const float *x, int64_t nrows);   // byte / sq8 store (float16: where the rows are sharded): one log line for the first refused value
   // "raw_dtype": "sq8": likewise.  The ranges are trained by Indexing() before the first row is mirrored, written by Dump to the
   // side file raw_sq8.ranges beside ivfpq.index (HIPIVFFLAT: ivfflat.index) and set again by Load before the mirror is re-encoded.
   const HIPRawSq8Ops *raw_sq8_ops_ = nullptr;

@@ -416,6 +416,13 @@ void gh_parse_ivfpq_raw_dtype(const char *str, int *out) {
   out[0] = p.Parse(str);
   out[1] = p.raw_sq8 ? 4 : p.raw_i8 ? 1 + p.raw_i8 : p.raw_f16 ? 1 : 0;
 }
+// "raw_dtype" / "raw_placement" / "devices" / "placement" of the HIPIVFPQ model's parameters as Init decides them, without a
+// device: out = {rc of Parse, rc of CheckRawKeys (0 accepted, -2 rejected; -1 when the parse failed)}
+void gh_check_ivfpq_raw_keys(const char *str, int *out) {
+  HIPIVFPQModelParams p;
+  out[0] = p.Parse(str);
+  out[1] = out[0] ? -1 : p.CheckRawKeys();
+}
 // the HIP-only "raw_dtype" key of the HIPFLAT model's parameters: out = {rc, element type as above}
 void gh_parse_flat_raw_dtype(const char *str, int *out) {
   int et = 0;

@@ -56,6 +56,7 @@ HOST_SYMBOLS = {
     "gh_parse_ivfpq_model_params": (None, [C.c_char_p, C.POINTER(C.c_int)]),
     "gh_parse_ivfpq_retrieval_params": (None, [C.c_char_p, C.POINTER(C.c_int)]),
     "gh_parse_ivfpq_raw_dtype": (None, [C.c_char_p, C.POINTER(C.c_int)]),
+    "gh_check_ivfpq_raw_keys": (None, [C.c_char_p, C.POINTER(C.c_int)]),
     "gh_parse_flat_raw_dtype": (None, [C.c_char_p, C.POINTER(C.c_int)]),
     "gh_parse_ivfflat_raw_dtype": (None, [C.c_char_p, C.POINTER(C.c_int)]),
     "gh_model_registered": (C.c_int, [C.c_char_p]),
@@ -122,6 +123,14 @@ def parse_raw_dtype(s):
     out = (C.c_int * 2)()
     load_host().gh_parse_ivfpq_raw_dtype(s.encode(), out)
     return int(out[0]), ("float32", "float16", "uint8", "int8", "sq8")[out[1]]
+
+
+def check_raw_keys(s):
+    """(rc of HIPIVFPQModelParams::Parse, rc of its CheckRawKeys) for the model parameters s: what HIPIVFPQ's Init says to
+    "raw_dtype" / "raw_placement" / "devices" / "placement" before it opens a device (0 accepted, -2 rejected)"""
+    out = (C.c_int * 2)()
+    load_host().gh_check_ivfpq_raw_keys(s.encode(), out)
+    return int(out[0]), int(out[1])
 
 
 def parse_flat_raw_dtype(s):

@@ -215,8 +215,10 @@ int gamma_hip_set_small_path(gamma_hip_index* h, int on);
  * GAMMA_HIP_EUNSUPPORTED, as every other reader of fp32 rows does; 1 = the three serve it: every row is widened to fp32
  * -- exactly -- as it is loaded and every distance is fvec_L2sqr / fvec_inner_product of the fp32 query and the widened
  * row, so distances and labels are byte-identical to those of an fp32 store that holds the widened rows (DESIGN.md
- * section 15).  Nothing else changes: IVFFLAT search (a switch of its own, below), the shard / merge / export entries, gamma_hip_raw_put / _raw_drop
- * and a sparse store keep refusing a narrow store, and an fp32 store is served as before whatever the switch says. */
+ * section 15).  Nothing else changes: IVFFLAT search (a switch of its own, below) keeps refusing a narrow store, flat search
+ * keeps refusing a sparse store, the shard / merge / export entries and gamma_hip_raw_put / _raw_drop refuse a narrow store
+ * unless gamma_hip_set_sparse_narrow_rows (below) says otherwise, and an fp32 store is served as before whatever the switch
+ * says. */
 int gamma_hip_set_flat_narrow_rows(gamma_hip_index* h, int on);
 /* IVFFLAT search over a narrow raw store; a switch of its own, independent of the one above.  on: 0 (default) =
  * gamma_hip_ivfflat_search and _ivfflat_search_device refuse a float16 / uint8 / int8 store with GAMMA_HIP_EUNSUPPORTED,
@@ -224,10 +226,25 @@ int gamma_hip_set_flat_narrow_rows(gamma_hip_index* h, int on);
  * (index/impl/gamma_index_ivfflat.h:52-75) calls faiss::fvec_L2sqr / fvec_inner_product on each; here a list holds vids and
  * the rows come from the raw store: a narrow row is widened to fp32 -- exactly -- as it is loaded and is the scanner's yj from
  * then on, so distances and labels are byte-identical to those of an fp32 store that holds the widened rows, exact ties
- * included.  Nothing else changes: the shard / merge / export entries, gamma_hip_raw_put /
- * _raw_drop, the combining queue and a sparse store keep refusing a narrow store, and an fp32 store is served as before
- * whatever the switch says. */
+ * included.  Nothing else changes: the combining queue keeps refusing a narrow store, IVFFLAT search
+ * keeps refusing a sparse store, the shard / merge / export entries and gamma_hip_raw_put / _raw_drop refuse a narrow store
+ * unless gamma_hip_set_sparse_narrow_rows (below) says otherwise, and an fp32 store is served as before whatever the switch
+ * says. */
 int gamma_hip_set_ivfflat_narrow_rows(gamma_hip_index* h, int on);
+/* Raw rows sharded with their lists (gamma_hip_raw_put) in a narrow store; a switch of its own, independent of every other.
+ * on: 0 (default) = gamma_hip_raw_put / _raw_drop and gamma_hip_ivfpq_shard_exact / _shard_export_exact refuse a float16 /
+ * uint8 / int8 / sq8 store (gamma_hip_raw_init_f16 / _i8 / _sq8) with GAMMA_HIP_EUNSUPPORTED, as before; 1 = they serve it.
+ * gamma_hip_raw_put / _raw_drop then keep the sparse fp32 store's semantics -- a held vid is rewritten in place, freed rows are
+ * reused before the store grows, the last entry of a vid named twice wins -- and the narrow stores' rules for what a row may
+ * hold: the whole batch is checked first (float16: no finite value that rounds to infinity; uint8 / int8: every value
+ * converts exactly; sq8: ranges set, every value finite), and a refused row fails the call with nothing of the handle
+ * changed.  An sq8 store sets its ranges before its first gamma_hip_raw_put, the empty one included: a sparse store's are fixed.  Rows are converted on the device.  gamma_hip_ivfpq_shard_exact serves a narrow store dense or sparse,
+ * _shard_export_exact a sparse one: a row is widened (sq8: decoded through the store's table) exactly as it is loaded and every
+ * distance is fvec_L2sqr / fvec_inner_product of the fp32 query and that row, so every result is byte-identical to that of
+ * an fp32 store holding the widened rows.  Nothing else changes: an fp32 store is served as before
+ * whatever the switch says; flat and IVFFLAT search, gamma_hip_raw_gets / _raw_append / _raw_write keep refusing a sparse store,
+ * the merges with has_rank and no travelled distances a narrow one, and 4-bit and OPQ handles every shard entry. */
+int gamma_hip_set_sparse_narrow_rows(gamma_hip_index* h, int on);
 /* The list scan of the IVFFLAT search (GammaIVFFlatScanner1::scan_codes, index/impl/gamma_index_ivfflat.h:52-75: one
  * fvec_L2sqr / fvec_inner_product per entry of a probed list) has a list-major form -- a list's rows are read once per tile
  * of the queries probing it instead of once per query (csrc/ivfflat.hip, DESIGN.md sections 9 and 22) -- for some row
