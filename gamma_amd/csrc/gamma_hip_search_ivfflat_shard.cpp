@@ -1,6 +1,6 @@
 // gamma_hip_search_ivfflat_shard.cpp -- the IVFFLAT search over list shards, entry points of the C ABI (include/gamma_hip.h):
-// a shard's coarse quantizer, its preassigned search over the lists it holds and owns (rows from a dense or a sparse fp32
-// store), the merge of the shards' top-k tables with the tie flags, the exact distances a shard exports for the flagged
+// a shard's coarse quantizer, its preassigned search over the lists it holds and owns (rows from a dense or a sparse store:
+// fp32, or float16 / uint8 / int8 after gamma_hip_set_ivfflat_narrow_rows), the merge of the shards' top-k tables with the tie flags, the exact distances a shard exports for the flagged
 // queries and the replay of the assembled streams through the IVFFLAT scanner's heap.  The kernels are the single-handle
 // search's (ivfflat.hip, rerank.hip: their sparse variants where the rows live with their lists) and the list shards' of the
 // IVFPQ path (select.hip k_merge_shards, ties.hip k_flag_merge_cut / k_shard_export / k_merge_streams / k_tie_replay).
@@ -10,14 +10,15 @@
 namespace ghi {
 namespace {
 
-// what every entry below asks of the handle; `what` names the entry in the refusal of a narrow store
+// what every entry below asks of the handle; `what` names the entry in the refusal of a narrow store.  A float16 / uint8 / int8
+// store is served where the single-handle search serves it (gamma_hip_set_ivfflat_narrow_rows); an sq8 store never is.
 int ivfflat_shard_check(H* h, const gamma_hip_search_params* p, int nq, int k, const char* what, bool need_rows) {
     GH_TRY(check_params(h, p, nq, k));
     if (!h->ivf_init || !h->ivfflat || h->binivf) return fail(h, GAMMA_HIP_EINVAL, "ivfflat not initialised");
-    if (need_rows && !raw_store_served(h, false, false)) return raw_store_refuse(h, what);
+    if (need_rows && !raw_store_served(h, h->ivfflat_narrow_rows, false)) return raw_store_refuse(h, what);
     if (!h->trained) return fail(h, GAMMA_HIP_ENOTTRAINED, "ivfflat not trained");
     if (p->nprobe <= 0 || p->nprobe > h->nlist) return fail(h, GAMMA_HIP_EINVAL, "nprobe out of range");
-    if (need_rows && (!h->raw_f32() || h->raw_d != h->d)) return fail(h, GAMMA_HIP_EINVAL, "ivfflat needs the raw store");
+    if (need_rows && (!h->has_raw_rows() || h->raw_d != h->d)) return fail(h, GAMMA_HIP_EINVAL, "ivfflat needs the raw store");
     return GAMMA_HIP_OK;
 }
 
@@ -37,6 +38,8 @@ int ivfflat_shard_scan(H* h, const gamma_hip_search_params* p, const FiltCtx& fc
     gh::launch_pair_offsets(s, probe, nc, P, h->d_list_len, h->d_list_mask, nlist, h->w_pair_off.as<int>(), h->w_qtotal.as<int>(),
                             nullptr, h->d_list_off, h->w_pair_base.as<int64_t>());
     const int need_filter = (fc.any_clause || (h->d_bitmap && h->bitmap_any)) ? 1 : 0;
+    // the store's rows as the scans take them: pointer + element type (fp32 rows: the launches they always were)
+    const gh::RowsRef rows = raw_rows_ref(h);
     StageScope t(h, GAMMA_HIP_STAGE_SCAN);
     if (h->raw_sparse && !h->d_raw_slot) {   // a sparse store that never took a row: every entry is a filtered entry
         const int64_t n = (int64_t)nc * q_stride;
@@ -59,20 +62,20 @@ int ivfflat_shard_scan(H* h, const gamma_hip_search_params* p, const FiltCtx& fc
         }
         if (h->raw_sparse)
             gh::launch_ivfflat_lm_sparse(s, l2, xq, nc, h->d, P, probe, h->w_pair_off.as<int>(), h->d_list_off, len, nlist, h->d_ids,
-                                         h->raw_f32(), h->nraw, h->d_raw_slot, h->raw_slot_cap(), q_stride, h->w_dist.as<float>(), fc.d_tab,
+                                         rows, h->nraw, h->d_raw_slot, h->raw_slot_cap(), q_stride, h->w_dist.as<float>(), fc.d_tab,
                                          need_filter, p->min_score, p->max_score, h->w_lm_units.p);
         else
             gh::launch_ivfflat_lm(s, l2, xq, nc, h->d, P, probe, h->w_pair_off.as<int>(), h->d_list_off, len, nlist, h->d_ids,
-                                  h->raw_f32(), h->nraw, q_stride, h->w_dist.as<float>(), fc.d_tab, need_filter, p->min_score,
+                                  rows, h->nraw, q_stride, h->w_dist.as<float>(), fc.d_tab, need_filter, p->min_score,
                                   p->max_score, h->w_lm_units.p);
     } else {
         h->fl_pair.fetch_add(1, std::memory_order_relaxed);
         if (h->raw_sparse)
             gh::launch_ivfflat_scan_sparse(s, l2, xq, nc, h->d, P, h->w_pair_off.as<int>(), h->w_pair_base.as<int64_t>(), h->d_ids,
-                                           h->raw_f32(), h->nraw, h->d_raw_slot, h->raw_slot_cap(), q_stride, h->w_dist.as<float>(),
+                                           rows, h->nraw, h->d_raw_slot, h->raw_slot_cap(), q_stride, h->w_dist.as<float>(),
                                            fc.d_tab, need_filter, p->min_score, p->max_score);
         else
-            gh::launch_ivfflat_scan(s, l2, xq, nc, h->d, P, h->w_pair_off.as<int>(), h->w_pair_base.as<int64_t>(), h->d_ids, h->raw_f32(),
+            gh::launch_ivfflat_scan(s, l2, xq, nc, h->d, P, h->w_pair_off.as<int>(), h->w_pair_base.as<int64_t>(), h->d_ids, rows,
                                     h->nraw, q_stride, h->w_dist.as<float>(), fc.d_tab, need_filter, p->min_score, p->max_score);
     }
     return GAMMA_HIP_OK;

@@ -229,20 +229,21 @@ __global__ __launch_bounds__(256) void k_ivfflat_lm(const float* __restrict__ x,
     ivfflat_lm_body<L2, D, Row, false>(x, P, pair_off, list_off, list_len, ids, raw, nraw, inv_start, inv_cnt, inv, ustart, nlist,
                                        q_stride, out, ftab, need_filter, min_score, max_score, tab, nullptr, 0);
 }
-// fp32 rows of a sparse store (the list shards of a group whose rows live with their lists)
-template <bool L2, int D>
+// the rows of a sparse store (the list shards of a group whose rows live with their lists): float, or float16 / uint8 / int8
+// widened as they are loaded; never sq8
+template <bool L2, int D, class Row = float>
 __global__ __launch_bounds__(256) void k_ivfflat_lm_sp(const float* __restrict__ x, int P, const int* __restrict__ pair_off,
                                                        const int64_t* __restrict__ list_off,
                                                        const int* __restrict__ list_len, const int64_t* __restrict__ ids,
-                                                       const float* __restrict__ raw, int64_t nraw,
+                                                       const Row* __restrict__ raw, int64_t nraw,
                                                        const int* __restrict__ inv_start, const int* __restrict__ inv_cnt,
                                                        const int* __restrict__ inv, const int* __restrict__ ustart,
                                                        int nlist, int64_t q_stride,
                                                        float* __restrict__ out, const FilterDesc* __restrict__ ftab,
                                                        int need_filter, float min_score, float max_score,
                                                        const int32_t* __restrict__ slot, int64_t nslot) {
-    ivfflat_lm_body<L2, D, float, true>(x, P, pair_off, list_off, list_len, ids, raw, nraw, inv_start, inv_cnt, inv, ustart, nlist,
-                                        q_stride, out, ftab, need_filter, min_score, max_score, RowTab<float>{}, slot, nslot);
+    ivfflat_lm_body<L2, D, Row, true>(x, P, pair_off, list_off, list_len, ids, raw, nraw, inv_start, inv_cnt, inv, ustart, nlist,
+                                      q_stride, out, ftab, need_filter, min_score, max_score, RowTab<Row>{}, slot, nslot);
 }
 
 // ---- rows of any d % 16 == 0 up to 4096: the row-sliced list-major kernel ------------------------------------------------
@@ -395,19 +396,19 @@ __global__ __launch_bounds__(256) void k_ivfflat_lms(const float* __restrict__ x
     ivfflat_lms_body<L2, Row, false>(x, d, P, pair_off, list_off, list_len, ids, raw, nraw, inv_start, inv_cnt, inv, ustart, nlist,
                                      q_stride, out, ftab, need_filter, min_score, max_score, tab, nullptr, 0);
 }
-template <bool L2>
+template <bool L2, class Row = float>
 __global__ __launch_bounds__(256) void k_ivfflat_lms_sp(const float* __restrict__ x, int d, int P, const int* __restrict__ pair_off,
                                                         const int64_t* __restrict__ list_off,
                                                         const int* __restrict__ list_len, const int64_t* __restrict__ ids,
-                                                        const float* __restrict__ raw, int64_t nraw,
+                                                        const Row* __restrict__ raw, int64_t nraw,
                                                         const int* __restrict__ inv_start, const int* __restrict__ inv_cnt,
                                                         const int* __restrict__ inv, const int* __restrict__ ustart,
                                                         int nlist, int64_t q_stride,
                                                         float* __restrict__ out, const FilterDesc* __restrict__ ftab,
                                                         int need_filter, float min_score, float max_score,
                                                         const int32_t* __restrict__ slot, int64_t nslot) {
-    ivfflat_lms_body<L2, float, true>(x, d, P, pair_off, list_off, list_len, ids, raw, nraw, inv_start, inv_cnt, inv, ustart, nlist,
-                                      q_stride, out, ftab, need_filter, min_score, max_score, RowTab<float>{}, slot, nslot);
+    ivfflat_lms_body<L2, Row, true>(x, d, P, pair_off, list_off, list_len, ids, raw, nraw, inv_start, inv_cnt, inv, ustart, nlist,
+                                    q_stride, out, ftab, need_filter, min_score, max_score, RowTab<Row>{}, slot, nslot);
 }
 
 // list_len with the lists a shard's mask does not own set to 0: to the list-major launch an unowned list is an empty list
@@ -454,10 +455,10 @@ void launch_ivfflat_lm_t(hipStream_t s, bool l2, const float* x, int nq, int d, 
     else hipLaunchKernelGGL(k_inv_scan, dim3(1), dim3(1024), 0, s, cnt, list_len, nlist, start, cur, ustart);
     hipLaunchKernelGGL(k_inv_fill, dim3((npairs + 255) / 256), dim3(256), 0, s, probe, npairs, nlist, list_len, start, cur, inv);
     const int grid = 256 * 8;   // persistent: every workgroup walks the unit list with stride gridDim.x
-    if constexpr (RowKind<Row>::fp32) {
+    if constexpr (!RowKind<Row>::sq8) {
         if (slot) {   // a sparse store: the same two kernels with the vid -> row table (launch_ivfflat_lm_sparse)
 #define GH_FLSP(LL, DD)                                                                                                       \
-    hipLaunchKernelGGL((k_ivfflat_lm_sp<LL, DD>), dim3(grid), dim3(256), 0, s, x, P, pair_off, list_off, list_len, ids, raw, nraw, \
+    hipLaunchKernelGGL((k_ivfflat_lm_sp<LL, DD, Row>), dim3(grid), dim3(256), 0, s, x, P, pair_off, list_off, list_len, ids, raw, nraw, \
                        start, cnt, inv, ustart, nlist, q_stride, out, ftab, need_filter, min_score, max_score, slot, nslot)
 #define GH_FLSPD(LL)                      \
     switch (d) {                          \
@@ -469,11 +470,11 @@ void launch_ivfflat_lm_t(hipStream_t s, bool l2, const float* x, int nq, int d, 
     }
             if (sliced) {
                 if (l2)
-                    hipLaunchKernelGGL((k_ivfflat_lms_sp<true>), dim3(grid), dim3(256), 0, s, x, d, P, pair_off, list_off, list_len,
+                    hipLaunchKernelGGL((k_ivfflat_lms_sp<true, Row>), dim3(grid), dim3(256), 0, s, x, d, P, pair_off, list_off, list_len,
                                        ids, raw, nraw, start, cnt, inv, ustart, nlist, q_stride, out, ftab, need_filter, min_score,
                                        max_score, slot, nslot);
                 else
-                    hipLaunchKernelGGL((k_ivfflat_lms_sp<false>), dim3(grid), dim3(256), 0, s, x, d, P, pair_off, list_off, list_len,
+                    hipLaunchKernelGGL((k_ivfflat_lms_sp<false, Row>), dim3(grid), dim3(256), 0, s, x, d, P, pair_off, list_off, list_len,
                                        ids, raw, nraw, start, cnt, inv, ustart, nlist, q_stride, out, ftab, need_filter, min_score,
                                        max_score, slot, nslot);
             } else if (l2) {
@@ -527,6 +528,24 @@ void launch_ivfflat_lm_sparse(hipStream_t s, bool l2, const float* x, int nq, in
     if (!slot) return;   // (a sparse store without a table holds no row: the caller fills the slab with the sentinel)
     launch_ivfflat_lm_t<float>(s, l2, x, nq, d, P, probe, pair_off, list_off, list_len, nlist, ids, raw, nraw, q_stride, out, ftab,
                                need_filter, min_score, max_score, scratch, RowTab<float>{}, slot, nslot);
+}
+// ... of any element type but sq8 (a sparse sq8 store is refused before it gets here: nothing is launched for one)
+void launch_ivfflat_lm_sparse(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* probe, const int* pair_off,
+                              const int64_t* list_off, const int* list_len, int nlist, const int64_t* ids, const RowsRef& raw,
+                              int64_t nraw, const int32_t* slot, int64_t nslot, int64_t q_stride, float* out, const FilterDesc* ftab,
+                              int need_filter, float min_score, float max_score, void* scratch) {
+    if (!slot) return;
+#define GH_FLRS(T)                                                                                                             \
+    launch_ivfflat_lm_t<T>(s, l2, x, nq, d, P, probe, pair_off, list_off, list_len, nlist, ids, raw.as<T>(), nraw, q_stride, out, \
+                           ftab, need_filter, min_score, max_score, scratch, RowTab<T>{}, slot, nslot)
+    switch (raw.et) {
+        case 0: GH_FLRS(float); break;
+        case 1: GH_FLRS(uint16_t); break;
+        case 2: GH_FLRS(uint8_t); break;
+        case 3: GH_FLRS(int8_t); break;
+        default: break;
+    }
+#undef GH_FLRS
 }
 // rows of any element type (gamma_hip_set_ivfflat_narrow_rows, _sq8_rows); fp32 rows: the launch above, the kernels it always ran
 void launch_ivfflat_lm(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* probe, const int* pair_off,

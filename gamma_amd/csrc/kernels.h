@@ -395,6 +395,16 @@ void launch_ivfflat_lm_sparse(hipStream_t s, bool l2, const float* x, int nq, in
                               const int64_t* list_off, const int* list_len, int nlist, const int64_t* ids, const float* raw,
                               int64_t nraw, const int32_t* slot, int64_t nslot, int64_t q_stride, float* out, const FilterDesc* ftab,
                               int need_filter, float min_score, float max_score, void* scratch);
+// ... over the rows of a sparse store of any element type but sq8 (float16 / uint8 / int8 rows widen exactly on load: the same
+// bodies, instantiated per type); element type 0 launches the kernels of the two launches above
+void launch_ivfflat_scan_sparse(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* pair_off,
+                                const int64_t* pair_base, const int64_t* ids, const RowsRef& raw, int64_t nraw,
+                                const int32_t* slot, int64_t nslot, int64_t q_stride, float* out, const FilterDesc* ftab,
+                                int need_filter, float min_score, float max_score);
+void launch_ivfflat_lm_sparse(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* probe, const int* pair_off,
+                              const int64_t* list_off, const int* list_len, int nlist, const int64_t* ids, const RowsRef& raw,
+                              int64_t nraw, const int32_t* slot, int64_t nslot, int64_t q_stride, float* out, const FilterDesc* ftab,
+                              int need_filter, float min_score, float max_score, void* scratch);
 // out[l] = mask[l] ? list_len[l] : 0 -- the list-length table of a list shard: to the list-major launch an unowned list is empty
 void launch_masked_list_len(hipStream_t s, const int* list_len, const uint8_t* mask, int nlist, int* out);
 // returns true when the walk of the tied rows went to `side` (the caller then waits for `join` before reading the result)

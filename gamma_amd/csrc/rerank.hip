@@ -583,17 +583,17 @@ __global__ __launch_bounds__(256) void k_ivfflat_scan(const float* __restrict__ 
     ivfflat_scan_body<L2, Row, false>(x, d, P, pair_off, pair_base, ids, raw, nraw, q_stride, out, ftab, need_filter, min_score,
                                       max_score, tab, nullptr, 0);
 }
-template <bool L2>
+template <bool L2, class Row = float>
 __global__ __launch_bounds__(256) void k_ivfflat_scan_sp(const float* __restrict__ x, int d, int P,
                                                          const int* __restrict__ pair_off,
                                                          const int64_t* __restrict__ pair_base,
                                                          const int64_t* __restrict__ ids,
-                                                         const float* __restrict__ raw, int64_t nraw, int64_t q_stride,
+                                                         const Row* __restrict__ raw, int64_t nraw, int64_t q_stride,
                                                          float* __restrict__ out, const FilterDesc* __restrict__ ftab,
                                                          int need_filter, float min_score, float max_score,
                                                          const int32_t* __restrict__ slot, int64_t nslot) {
-    ivfflat_scan_body<L2, float, true>(x, d, P, pair_off, pair_base, ids, raw, nraw, q_stride, out, ftab, need_filter, min_score,
-                                       max_score, RowTab<float>{}, slot, nslot);
+    ivfflat_scan_body<L2, Row, true>(x, d, P, pair_off, pair_base, ids, raw, nraw, q_stride, out, ftab, need_filter, min_score,
+                                     max_score, RowTab<Row>{}, slot, nslot);
 }
 // fp32 rows of a sparse store: slot [nslot] = vector id -> row of `raw` (nraw rows), -1 = not held here
 void launch_ivfflat_scan_sparse(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* pair_off,
@@ -608,6 +608,47 @@ void launch_ivfflat_scan_sparse(hipStream_t s, bool l2, const float* x, int nq, 
     else
         hipLaunchKernelGGL((k_ivfflat_scan_sp<false>), grid, dim3(256), 0, s, x, d, P, pair_off, pair_base, ids, raw, nraw, q_stride,
                            out, ftab, need_filter, min_score, max_score, slot, nslot);
+}
+namespace {
+template <class Row>
+void launch_ivfflat_scan_sparse_t(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* pair_off,
+                                  const int64_t* pair_base, const int64_t* ids, const Row* raw, int64_t nraw, const int32_t* slot,
+                                  int64_t nslot, int64_t q_stride, float* out, const FilterDesc* ftab, int need_filter,
+                                  float min_score, float max_score) {
+    if (nq <= 0 || P <= 0 || !slot) return;
+    const dim3 grid((unsigned)((int64_t)nq * P));
+    if (l2)
+        hipLaunchKernelGGL((k_ivfflat_scan_sp<true, Row>), grid, dim3(256), 0, s, x, d, P, pair_off, pair_base, ids, raw, nraw,
+                           q_stride, out, ftab, need_filter, min_score, max_score, slot, nslot);
+    else
+        hipLaunchKernelGGL((k_ivfflat_scan_sp<false, Row>), grid, dim3(256), 0, s, x, d, P, pair_off, pair_base, ids, raw, nraw,
+                           q_stride, out, ftab, need_filter, min_score, max_score, slot, nslot);
+}
+}  // namespace
+// ... of any element type but sq8 (a sparse sq8 store is refused before it gets here: nothing is launched for one)
+void launch_ivfflat_scan_sparse(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* pair_off,
+                                const int64_t* pair_base, const int64_t* ids, const RowsRef& raw, int64_t nraw,
+                                const int32_t* slot, int64_t nslot, int64_t q_stride, float* out, const FilterDesc* ftab,
+                                int need_filter, float min_score, float max_score) {
+    switch (raw.et) {
+        case 0:
+            launch_ivfflat_scan_sparse(s, l2, x, nq, d, P, pair_off, pair_base, ids, raw.as<float>(), nraw, slot, nslot, q_stride,
+                                       out, ftab, need_filter, min_score, max_score);
+            break;
+        case 1:
+            launch_ivfflat_scan_sparse_t(s, l2, x, nq, d, P, pair_off, pair_base, ids, raw.as<uint16_t>(), nraw, slot, nslot,
+                                         q_stride, out, ftab, need_filter, min_score, max_score);
+            break;
+        case 2:
+            launch_ivfflat_scan_sparse_t(s, l2, x, nq, d, P, pair_off, pair_base, ids, raw.as<uint8_t>(), nraw, slot, nslot,
+                                         q_stride, out, ftab, need_filter, min_score, max_score);
+            break;
+        case 3:
+            launch_ivfflat_scan_sparse_t(s, l2, x, nq, d, P, pair_off, pair_base, ids, raw.as<int8_t>(), nraw, slot, nslot,
+                                         q_stride, out, ftab, need_filter, min_score, max_score);
+            break;
+        default: break;
+    }
 }
 void launch_ivfflat_scan(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* pair_off,
                          const int64_t* pair_base, const int64_t* ids, const float* raw, int64_t nraw, int64_t q_stride,

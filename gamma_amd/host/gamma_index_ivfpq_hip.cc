@@ -1062,6 +1062,68 @@ int RegisterHIPIVFFlatGroup(HIPIVFFlatGroupSearchFn fn) {
 }
 HIPIVFFlatGroupSearchFn FindHIPIVFFlatGroup() { return IVFFlatGroupSearch(); }
 
+namespace {
+HIPIVFFlatGroupRowsFn &IVFFlatGroupRows() {
+  static HIPIVFFlatGroupRowsFn fn = nullptr;
+  return fn;
+}
+}  // namespace
+int RegisterHIPIVFFlatGroupRows(HIPIVFFlatGroupRowsFn fn) {
+  IVFFlatGroupRows() = fn;
+  return 0;
+}
+HIPIVFFlatGroupRowsFn FindHIPIVFFlatGroupRows() { return IVFFlatGroupRows(); }
+
+int GammaIVFFlatHIPIndex::DeviceKeys(const std::string &model_parameters, int et, HIPIVFPQModelParams &pa, bool *several,
+                                     bool *members_narrow) {
+  *several = *members_narrow = false;
+  // several devices ("devices": "0,1,..", HIPIVFPQ's keys and parser): the in-process group, where the build carries its IVFFLAT
+  // search (gamma_index_ivfflat_group_hip.cc); without it the keys stay unread and the model opens one handle, as it always did
+  if (!FindHIPIVFFlatGroup()) return 0;
+  utils::JsonParser jp;
+  if (model_parameters != "" && jp.Parse(model_parameters.c_str())) return -1;
+  if (ParseDeviceKeys(jp, pa)) return -1;
+  *several = pa.devices.size() > 1;
+  // "group_rows": "raw_dtype" (gamma_index_ivfflat_group_rows_hip.cc): the members hold their rows in a narrow raw_dtype
+  int narrow = 0;
+  const HIPIVFFlatGroupRowsFn group_rows = FindHIPIVFFlatGroupRows();
+  if (group_rows && group_rows(model_parameters, et, pa.devices.size(), pa.device_filters, &narrow)) return -1;
+  *members_narrow = narrow != 0;
+  if (*several && et != 0 && !narrow) {
+    HLOG("HIPIVFFLAT: raw_dtype other than float32 with several devices is not supported (the group's members hold fp32 rows)");
+    return -1;
+  }
+  if (*several && pa.device_filters) {
+    HLOG("HIPIVFFLAT: device_filters with several devices is not supported (the columns live on one handle)");
+    return -1;
+  }
+  if (pa.raw_sharded) {
+    const HIPRawShardOps *rawshard = FindHIPRawShard();
+    if (!*several || pa.replicate || !rawshard) {
+      HLOG("HIPIVFFLAT: raw_placement = sharded needs several devices and placement = shard%s",
+           rawshard ? "" : " (and this build of the plugin carries no sharded raw rows)");
+      return -1;
+    }
+  }
+  return 0;
+}
+
+void GammaIVFFlatHIPIndex::CheckGroupKeys(const std::string &model_parameters, int *out) {
+  out[0] = out[1] = out[2] = 0;
+  HIPIVFPQModelParams pa;
+  utils::JsonParser jp;
+  int v = 0, et = 0;
+  if (model_parameters != "" && jp.Parse(model_parameters.c_str())) {
+    out[0] = -1;
+    return;
+  }
+  if (!jp.GetInt("device_filters", v)) pa.device_filters = v != 0;
+  bool several = false, members_narrow = false;
+  out[0] = ParseRawDtype(model_parameters, &et) ? -1 : DeviceKeys(model_parameters, et, pa, &several, &members_narrow);
+  out[1] = !out[0] && several;
+  out[2] = !out[0] && members_narrow;
+}
+
 int GammaIVFFlatHIPIndex::ParseRawDtype(const std::string &model_parameters, int *et) {
   *et = 0;
   utils::JsonParser jp;
@@ -1139,27 +1201,15 @@ int GammaIVFFlatHIPIndex::Init(const std::string &model_parameters, int indexing
   }
   raw_f16_ = et == 1;
   raw_i8_ = narrow && et >= 2 ? et - 1 : 0;
-  // several devices ("devices": "0,1,..", HIPIVFPQ's keys and parser): the in-process group, where the build carries its IVFFLAT
-  // search (gamma_index_ivfflat_group_hip.cc); without it the keys stay unread and the model opens one handle, as it always did
+  // several devices: the in-process group (DeviceKeys: what the keys ask, decided before a device is opened)
   group_search_ = FindHIPIVFFlatGroup();
-  if (group_search_ && ParseDeviceKeys(jp, pa)) return -1;
-  const bool several = group_search_ && pa.devices.size() > 1;
-  if (several && et != 0) {
-    HLOG("HIPIVFFLAT: raw_dtype other than float32 with several devices is not supported (the group's members hold fp32 rows)");
+  bool several = false, members_narrow = false;
+  if (DeviceKeys(model_parameters, et, pa, &several, &members_narrow)) return -1;
+  rawshard_ = group_search_ && pa.raw_sharded ? FindHIPRawShard() : nullptr;
+  if (members_narrow && rawshard_ && !rawshard_->narrow_rows) {
+    HLOG("HIPIVFFLAT: group_rows = raw_dtype with raw_placement = sharded: this build of the plugin has no narrow rows sharded with their lists");
+    rawshard_ = nullptr;
     return -1;
-  }
-  if (several && pa.device_filters) {
-    HLOG("HIPIVFFLAT: device_filters with several devices is not supported (the columns live on one handle)");
-    return -1;
-  }
-  if (group_search_ && pa.raw_sharded) {
-    rawshard_ = FindHIPRawShard();
-    if (!several || pa.replicate || !rawshard_) {
-      HLOG("HIPIVFFLAT: raw_placement = sharded needs several devices and placement = shard%s",
-           rawshard_ ? "" : " (and this build of the plugin carries no sharded raw rows)");
-      rawshard_ = nullptr;
-      return -1;
-    }
   }
   if (!vector_) {
     HLOG("vector_ must be set before Init");
@@ -1171,15 +1221,26 @@ int GammaIVFFlatHIPIndex::Init(const std::string &model_parameters, int indexing
   metric_type_ = pa.metric_type;
   nprobe_ = pa.nprobe;
   int rc;
-  if (several) {   // a group of handles, lists sharded by owner or replicated; h_ is member 0 (fp32 rows on every member)
+  if (several) {
+    // a group of handles, lists sharded by owner or replicated; h_ is member 0.  fp32 rows on every member, or -- "group_rows":
+    // "raw_dtype" -- rows of raw_dtype: the typed store, the IVFFLAT search's switch for it and, where the rows are sharded with
+    // their lists, the sparse store's; the group keeps taking fp32 vectors and the members convert
     if (OpenDevices(pa.devices, pa.replicate)) return -1;
     rc = ForAll([&](gamma_hip_index *m) {
       int r = gamma_hip_ivfflat_init(m, d_, nlist_, metric_type_ == DistanceComputeType::L2 ? GAMMA_HIP_METRIC_L2 : GAMMA_HIP_METRIC_IP,
                                      pa.bucket_init_size, pa.bucket_max_size);
-      if (!r) r = gamma_hip_raw_init(m, d_);
+      if (!r) r = !members_narrow ? gamma_hip_raw_init(m, d_) : et == 1 ? init_f16(m, d_) : raw_i8_ops_->init(m, d_, et == 3);
+      if (!r && members_narrow) r = ivfflat_rows(m, 1);
+      if (!r && members_narrow && rawshard_) r = rawshard_->narrow_rows(m, 1);
       if (!r) r = gamma_hip_set_exact_ties(m, pa.exact_ties ? 1 : 0);
       return r;
     });
+    if (!rc && members_narrow) {
+      // brute_force_search and the search of an untrained model: member 0's flat search over its narrow mirror, where the build has it
+      const HIPFlatRowsFn flat_rows = FindHIPFlatRows();
+      narrow_brute_ = flat_rows != nullptr;
+      if (flat_rows) rc = flat_rows(h_, 1);
+    }
     if (rc) {
       HLOG("device init failed: %s (%s)", gamma_hip_strerror(rc), gamma_hip_last_error(h_));
       return -1;

@@ -126,6 +126,16 @@ typedef int (*HIPIVFFlatGroupSearchFn)(gamma_hip_group *g, const gamma_hip_searc
                                        float *distances, int64_t *labels);
 int RegisterHIPIVFFlatGroup(HIPIVFFlatGroupSearchFn fn);
 HIPIVFFlatGroupSearchFn FindHIPIVFFlatGroup();
+// HIPIVFFLAT's "group_rows": "float32" (the default: the members of a group hold fp32 rows, a narrow raw_dtype with several
+// devices is rejected) | "raw_dtype" (the members hold their rows in raw_dtype: float16 / uint8 / int8).  The key's parser and the
+// decision -- no device is touched -- live in gamma_index_ivfflat_group_rows_hip.cc and are registered the same way; without that
+// file the key stays unread and the model behaves as it always did.  et: the parsed raw_dtype (0 float32 .. 4 sq8); ndevices /
+// device_filters: the parsed "devices" / "device_filters".  0 accepted (*members_narrow = 1: the members get the typed store and
+// the handles' switches), -2 rejected behind one log line.
+typedef int (*HIPIVFFlatGroupRowsFn)(const std::string &model_parameters, int et, size_t ndevices, bool device_filters,
+                                     int *members_narrow);
+int RegisterHIPIVFFlatGroupRows(HIPIVFFlatGroupRowsFn fn);
+HIPIVFFlatGroupRowsFn FindHIPIVFFlatGroupRows();
 
 // "opq": the rotation's entries of the C ABI (gamma_hip_opq_train / _set / _get / _apply) reach the model through this table,
 // registered at static-initialisation time by gamma_index_ivfpq_opq_hip.cc -- the only host file that names them.  A build of
@@ -264,7 +274,8 @@ class GammaIVFPQHIPIndex : public RetrievalModel {
 // Delete and the raw mirror are inherited; Init, Indexing (coarse k-means only), Search, Dump / Load ("IvFl" file,
 // iwpq_io.h) differ.
 // HIP only: "devices": "0,1,..", "placement": "shard" | "replicate", "raw_placement": "replicated" | "sharded" with HIPIVFPQ's
-// meaning -- the index on several GPUs of this process (gamma_hip_group_*), fp32 rows only, no device_filters.
+// meaning -- the index on several GPUs of this process (gamma_hip_group_*), no device_filters; fp32 rows, or with "group_rows":
+// "raw_dtype" the members' rows in a raw_dtype of float16 / uint8 / int8 (HIPIVFFlatGroupRowsFn above).
 // HIP only: "raw_dtype": "float32" (default) | "float16" | "uint8" | "int8" -- the device's rows are 2 bytes / 1 byte per element,
 // widened exactly as the scan loads them; the byte stores take a row only if it converts exactly (HIPIVFPQ's rule, inherited).
 // Unlike HIPIVFPQ the model serves brute_force_search and the search of an untrained model over a narrow store (flat search
@@ -303,6 +314,13 @@ class GammaIVFFlatHIPIndex : public GammaIVFPQHIPIndex {
   // ivfflat.index).  -1 and one log line for "sq8" without that key (as before), any other value of the key, the key beside
   // another raw_dtype, and sq8_min / sq8_max (HIPFLAT's keys: this model's ranges are per dimension and trained)
   static int ParseRawDtype(const std::string &model_parameters, int *et);
+  // What Init says to "devices" / "placement" / "raw_placement" / "group_rows" beside raw_dtype (et) and pa.device_filters, before
+  // a device is opened: 0 accepted (pa takes the device keys; *several: a group is opened; *members_narrow: its members hold
+  // rows of raw_dtype), -1 rejected behind one log line.  In a build without the group's IVFFLAT search none of the keys is read.
+  static int DeviceKeys(const std::string &model_parameters, int et, HIPIVFPQModelParams &pa, bool *several, bool *members_narrow);
+  // the same from the model's parameters alone (the harness): out = {rc of the raw_dtype / device keys' parsing and the decision,
+  // several, members_narrow}
+  static void CheckGroupKeys(const std::string &model_parameters, int *out);
 
  private:
   HIPIVFFlatGroupSearchFn group_search_ = nullptr;   // non-null: the build carries the group's IVFFLAT search

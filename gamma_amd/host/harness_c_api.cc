@@ -435,6 +435,9 @@ void gh_parse_ivfflat_raw_dtype(const char *str, int *out) {
   out[0] = GammaIVFFlatHIPIndex::ParseRawDtype(str, &et);
   out[1] = et;
 }
+// what HIPIVFFLAT's Init says to "raw_dtype" / "devices" / "placement" / "raw_placement" / "group_rows" / "device_filters" before it
+// opens a device: out = {rc (0 accepted), a group is opened, its members hold rows of raw_dtype}
+void gh_check_ivfflat_group_keys(const char *str, int *out) { GammaIVFFlatHIPIndex::CheckGroupKeys(str, out); }
 // HIPIVFPQRetrievalParameters via Parse on an un-Init'ed model: out = {rc, metric, recall_num, nprobe}
 void gh_parse_ivfpq_retrieval_params(const char *str, int *out) {
   GammaIVFPQHIPIndex m;

@@ -59,6 +59,7 @@ HOST_SYMBOLS = {
     "gh_check_ivfpq_raw_keys": (None, [C.c_char_p, C.POINTER(C.c_int)]),
     "gh_parse_flat_raw_dtype": (None, [C.c_char_p, C.POINTER(C.c_int)]),
     "gh_parse_ivfflat_raw_dtype": (None, [C.c_char_p, C.POINTER(C.c_int)]),
+    "gh_check_ivfflat_group_keys": (None, [C.c_char_p, C.POINTER(C.c_int)]),
     "gh_model_registered": (C.c_int, [C.c_char_p]),
     "gh_iwpq_write": (C.c_int, [C.c_char_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, f32p, C.c_int, f32p,
                                 i64p, _lib.u8p, i64p]),
@@ -147,6 +148,15 @@ def parse_ivfflat_raw_dtype(s):
     out = (C.c_int * 2)()
     load_host().gh_parse_ivfflat_raw_dtype(s.encode(), out)
     return int(out[0]), ("float32", "float16", "uint8", "int8", "sq8")[out[1]]
+
+
+def check_ivfflat_group_keys(s):
+    """(rc, several, members_narrow) for the HIPIVFFLAT model parameters s: what Init says to "raw_dtype" / "devices" /
+    "placement" / "raw_placement" / "group_rows" / "device_filters" before it opens a device -- rc 0 accepted, otherwise rejected
+    behind one log line; several: a group of handles is opened; members_narrow: its members hold their rows in raw_dtype"""
+    out = (C.c_int * 3)()
+    load_host().gh_check_ivfflat_group_keys(s.encode(), out)
+    return int(out[0]), bool(out[1]), bool(out[2])
 
 
 def parse_retrieval_params(s):

@@ -226,10 +226,14 @@ int gamma_hip_set_flat_narrow_rows(gamma_hip_index* h, int on);
  * (index/impl/gamma_index_ivfflat.h:52-75) calls faiss::fvec_L2sqr / fvec_inner_product on each; here a list holds vids and
  * the rows come from the raw store: a narrow row is widened to fp32 -- exactly -- as it is loaded and is the scanner's yj from
  * then on, so distances and labels are byte-identical to those of an fp32 store that holds the widened rows, exact ties
- * included.  Nothing else changes: the combining queue keeps refusing a narrow store, IVFFLAT search
- * keeps refusing a sparse store, the shard / merge / export entries and gamma_hip_raw_put / _raw_drop refuse a narrow store
- * unless gamma_hip_set_sparse_narrow_rows (below) says otherwise, and an fp32 store is served as before whatever the switch
- * says. */
+ * included.  The IVFFLAT shard entries that read rows -- gamma_hip_ivfflat_search_shard and
+ * _ivfflat_shard_export, and through them gamma_hip_group_ivfflat_search -- follow the same switch: 0 = they refuse a float16 /
+ * uint8 / int8 store, 1 = they serve it, dense or sparse (a sparse narrow store exists only after
+ * gamma_hip_set_sparse_narrow_rows, below), byte-identical to shards holding the widened rows as fp32.
+ * Nothing else changes: the combining queue keeps refusing a narrow store, IVFFLAT search keeps refusing a sparse store, the
+ * IVFPQ shard / merge / export entries and gamma_hip_raw_put / _raw_drop refuse a narrow store unless
+ * gamma_hip_set_sparse_narrow_rows says otherwise, an sq8 store is refused at every shard entry, and an fp32 store is served
+ * as before whatever the switch says. */
 int gamma_hip_set_ivfflat_narrow_rows(gamma_hip_index* h, int on);
 /* Raw rows sharded with their lists (gamma_hip_raw_put) in a narrow store; a switch of its own, independent of every other.
  * on: 0 (default) = gamma_hip_raw_put / _raw_drop and gamma_hip_ivfpq_shard_exact / _shard_export_exact refuse a float16 /
@@ -241,7 +245,9 @@ int gamma_hip_set_ivfflat_narrow_rows(gamma_hip_index* h, int on);
  * changed.  An sq8 store sets its ranges before its first gamma_hip_raw_put, the empty one included: a sparse store's are fixed.  Rows are converted on the device.  gamma_hip_ivfpq_shard_exact serves a narrow store dense or sparse,
  * _shard_export_exact a sparse one: a row is widened (sq8: decoded through the store's table) exactly as it is loaded and every
  * distance is fvec_L2sqr / fvec_inner_product of the fp32 query and that row, so every result is byte-identical to that of
- * an fp32 store holding the widened rows.  Nothing else changes: an fp32 store is served as before
+ * an fp32 store holding the widened rows.  The IVFFLAT shard entries read a sparse float16 / uint8 /
+ * int8 store made this way after gamma_hip_set_ivfflat_narrow_rows, and only then; this switch alone
+ * leaves them refusing.  Nothing else changes: an fp32 store is served as before
  * whatever the switch says; flat and IVFFLAT search, gamma_hip_raw_gets / _raw_append / _raw_write keep refusing a sparse store,
  * the merges with has_rank and no travelled distances a narrow one, and 4-bit and OPQ handles every shard entry. */
 int gamma_hip_set_sparse_narrow_rows(gamma_hip_index* h, int on);
@@ -903,9 +909,12 @@ int gamma_hip_ivfpq_merge_replay(gamma_hip_index* h, const gamma_hip_search_para
                                  int64_t* d_labels);
 
 /* ---- IVFFLAT over list shards: one handle per shard (gamma_hip_ivfpq_set_list_mask), the single-handle building blocks.
- * Every pointer is a device address.  The rows of a shard come from a dense fp32 store (rows replicated on every shard) or
- * from a SPARSE one (gamma_hip_raw_put: the rows live with their lists); a float16, 8-bit or sq8 store answers
- * GAMMA_HIP_EUNSUPPORTED with last_error naming the store.  Limits on k and nprobe are gamma_hip_ivfflat_search's.  What the
+ * Every pointer is a device address.  The rows of a shard come from a dense store (rows replicated on every shard) or from a
+ * SPARSE one (gamma_hip_raw_put: the rows live with their lists): fp32 rows, or -- after gamma_hip_set_ivfflat_narrow_rows(h, 1),
+ * where the single-handle search serves them -- float16 / uint8 / int8 rows, widened exactly as they are loaded (results
+ * byte-identical to shards holding the widened rows as fp32).  With that switch off a float16 or 8-bit store answers
+ * GAMMA_HIP_EUNSUPPORTED with last_error naming the store, and an sq8 store always does (ivfflat_search_shard and
+ * ivfflat_shard_export: the entries that read rows).  Limits on k and nprobe are gamma_hip_ivfflat_search's.  What the
  * existing entries answer is unchanged: gamma_hip_ivfflat_search* on a sparse store stays refused.
  *   ivfflat_coarse_device  the coarse quantizer alone for a slice of the queries, [nq * nprobe] outputs
  *                   (gamma_hip_ivfpq_coarse_device refuses an IVFFLAT handle; this is its sibling);
