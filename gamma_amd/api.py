@@ -816,6 +816,24 @@ class GammaHip:
         self._ck(self.L.gamma_hip_ivfflat_scan_stats(self.h, _p(out, _lib.i64p), 1 if reset else 0), "ivfflat_scan_stats")
         return tuple(int(v) for v in out)
 
+    def set_ivfflat_lm_tails(self, on=True):
+        """True: ivfflat_search scans row lengths that are no multiple of 16 (ivfflat_lm_tail_shape: kind 3) list-major under the
+        gates of the other list-major forms, the same bits as the pair kernel's; False (the default): every call launches what
+        it always launched.  Independent of every other switch."""
+        self._ck(self.L.gamma_hip_set_ivfflat_lm_tails(self.h, 1 if on else 0), "set_ivfflat_lm_tails")
+
+    def get_ivfflat_lm_tails(self):
+        on = C.c_int(0)
+        self._ck(self.L.gamma_hip_get_ivfflat_lm_tails(self.h, C.byref(on)), "get_ivfflat_lm_tails")
+        return bool(on.value)
+
+    def ivfflat_lm_tail_stats(self, reset=False):
+        """query chunks of ivfflat_search scanned by the list-major kernel of the kind 3 lengths; none of them is counted in
+        ivfflat_scan_stats."""
+        out = np.zeros(1, np.int64)
+        self._ck(self.L.gamma_hip_ivfflat_lm_tail_stats(self.h, _p(out, _lib.i64p), 1 if reset else 0), "ivfflat_lm_tail_stats")
+        return int(out[0])
+
     def set_flat_sq8_rows(self, on=True):
         """True: flat_search serves an sq8 raw store (byte-identical to an fp32 store of the decoded rows); False (the
         default): it refuses one.  Independent of set_flat_narrow_rows."""
@@ -1090,6 +1108,17 @@ def ivfflat_lm_shape(d):
     if rc != 0:
         raise _lib.GammaHipError("ivfflat_lm_shape: %d" % rc)
     return int(kind.value), int(slab.value), int(qtile.value)
+
+
+def ivfflat_lm_tail_shape(d, elem_bytes=4):
+    """(kind, load_bytes, qtile) of the list-major scan of the lengths ivfflat_lm_shape answers 0 for: kind 3 for 1 <= d <= 4096
+    with d % 16 != 0, else 0; load_bytes = gcd(16, d * elem_bytes), the width of the kernel's row loads; qtile = the queries per
+    tile.  elem_bytes: 4 (fp32), 2 (float16), 1 (uint8 / int8).  No device call."""
+    kind, load, qtile = C.c_int(0), C.c_int(0), C.c_int(0)
+    rc = _lib.load().gamma_hip_ivfflat_lm_tail_shape(int(d), int(elem_bytes), C.byref(kind), C.byref(load), C.byref(qtile))
+    if rc != 0:
+        raise _lib.GammaHipError("ivfflat_lm_tail_shape: %d" % rc)
+    return int(kind.value), int(load.value), int(qtile.value)
 
 
 def binivf_scan_shape():

@@ -281,6 +281,32 @@ int gamma_hip_ivfflat_scan_stats(gamma_hip_index* h, int64_t* out4, int reset) {
     return GAMMA_HIP_OK;
 }
 
+int gamma_hip_ivfflat_lm_tail_shape(int d, int elem_bytes, int* kind, int* load_bytes, int* qtile) {
+    if (!kind || !load_bytes || !qtile || d < 1 || (elem_bytes != 4 && elem_bytes != 2 && elem_bytes != 1)) return GAMMA_HIP_EINVAL;
+    gh::ivfflat_lm_tail_shape(d, elem_bytes, kind, load_bytes, qtile);
+    return GAMMA_HIP_OK;
+}
+
+int gamma_hip_set_ivfflat_lm_tails(gamma_hip_index* h, int on) {
+    if (!h) return GAMMA_HIP_EINVAL;
+    SearchLock lk(h);
+    h->ivfflat_lm_tails = on != 0;
+    return GAMMA_HIP_OK;
+}
+
+int gamma_hip_get_ivfflat_lm_tails(gamma_hip_index* h, int* on) {
+    if (!h || !on) return GAMMA_HIP_EINVAL;
+    SearchLock lk(h);
+    *on = h->ivfflat_lm_tails ? 1 : 0;
+    return GAMMA_HIP_OK;
+}
+
+int gamma_hip_ivfflat_lm_tail_stats(gamma_hip_index* h, int64_t* out1, int reset) {
+    if (!h || !out1) return GAMMA_HIP_EINVAL;
+    out1[0] = reset ? h->fl_lmt.exchange(0) : h->fl_lmt.load();
+    return GAMMA_HIP_OK;
+}
+
 int gamma_hip_set_small_path(gamma_hip_index* h, int on) {
     if (!h) return GAMMA_HIP_EINVAL;
     SearchLock lk(h);

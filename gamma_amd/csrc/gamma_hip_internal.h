@@ -387,6 +387,10 @@ struct gamma_hip_index {
     // gamma_hip_ivfflat_scan_stats: calls the small path served; query chunks of the chunked path scanned by the pair kernel,
     // by the fixed-length list-major kernel, by the row-sliced one
     std::atomic<int64_t> fl_small{0}, fl_pair{0}, fl_lm{0}, fl_lms{0};
+    // gamma_hip_set_ivfflat_lm_tails: d % 16 != 0 goes list-major (k_ivfflat_lmt) where a multiple of 16 would; fl_lmt: the query
+    // chunks it scanned (gamma_hip_ivfflat_lm_tail_stats), counted in none of the four above
+    bool ivfflat_lm_tails = false;
+    std::atomic<int64_t> fl_lmt{0};
     bool small_path = true;    // gamma_hip_set_small_path
     bool flat_narrow_rows = false;   // gamma_hip_set_flat_narrow_rows: flat search serves a float16 / uint8 / int8 raw store
     bool ivfflat_narrow_rows = false;   // gamma_hip_set_ivfflat_narrow_rows: the same for the IVFFLAT search

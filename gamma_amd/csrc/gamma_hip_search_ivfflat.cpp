@@ -134,7 +134,17 @@ int ivfflat_search_device_locked(H* h, const gamma_hip_search_params* p, int nq,
             static const bool no_lm = getenv("GAMMA_HIP_NO_IVFFLAT_LM") != nullptr;
             int lm_kind = 0, lm_slab = 0, lm_qtile = 0;
             gh::ivfflat_lm_shape(h->d, &lm_kind, &lm_slab, &lm_qtile);
-            if (!no_lm && lm_kind != 0 && (int64_t)nc * P >= 2 * (int64_t)nlist && !h->d_list_mask) {
+            // d % 16 != 0 behind gamma_hip_set_ivfflat_lm_tails: the row-sliced kernel with the scanner's tail steps, under the
+            // same gates (an sq8 store has no such kernel and keeps the pair kernel)
+            int lt_kind = 0, lt_load = 0, lt_qtile = 0;
+            if (h->ivfflat_lm_tails && rows.et <= 3) gh::ivfflat_lm_tail_shape(h->d, (int)rows.esz(), &lt_kind, &lt_load, &lt_qtile);
+            if (!no_lm && lt_kind == 3 && (int64_t)nc * P >= 2 * (int64_t)nlist && !h->d_list_mask) {
+                h->fl_lmt.fetch_add(1, std::memory_order_relaxed);
+                GH_CHECK(h, h->w_lm_units.ensure(gh::ivfflat_lm_scratch_bytes(nc, P, nlist)));
+                gh::launch_ivfflat_lm_tail(s, l2, xq, nc, h->d, P, h->w_probe.as<int>(), h->w_pair_off.as<int>(), h->d_list_off,
+                                           h->d_list_len, nlist, h->d_ids, rows, h->nraw, q_stride, h->w_dist.as<float>(),
+                                           fc.d_tab, need_filter, p->min_score, p->max_score, h->w_lm_units.p);
+            } else if (!no_lm && lm_kind != 0 && (int64_t)nc * P >= 2 * (int64_t)nlist && !h->d_list_mask) {
                 (lm_kind == 1 ? h->fl_lm : h->fl_lms).fetch_add(1, std::memory_order_relaxed);
                 GH_CHECK(h, h->w_lm_units.ensure(gh::ivfflat_lm_scratch_bytes(nc, P, nlist)));
                 gh::launch_ivfflat_lm(s, l2, xq, nc, h->d, P, h->w_probe.as<int>(), h->w_pair_off.as<int>(), h->d_list_off,

@@ -411,6 +411,251 @@ __global__ __launch_bounds__(256) void k_ivfflat_lms_sp(const float* __restrict_
                                     q_stride, out, ftab, need_filter, min_score, max_score, RowTab<Row>{}, slot, nslot);
 }
 
+// ---- rows of every other length up to 4096 (d % 16 != 0): the row-sliced kernel with the scanner's tail steps -------------
+// fvec_L2sqr / fvec_inner_product end, behind the 8-wide loop, in a 4-lane step and a masked step that run AFTER the eight
+// accumulators are folded to four (rerank_dist8, rerank_dev.h: the arithmetic restated here operation for operation).  With
+// d16 = d & ~15 and r = d - d16 (1..15): elements 0 .. d16 - 1 run in k_ivfflat_lms's pieces; r >= 8: one more 8-wide step into
+// the same chains (4 elements per thread); the fold; d & 4: s[l] = fma(.., s[l]) over the next four elements; l < (d & 3): the
+// masked step; hsum4.  The work split, the inverse index and the slab positions are k_ivfflat_lms's.
+// What differs beside the tail: a row of such a d is aligned to LOADB = gcd(16, d * sizeof(Row)) bytes only, a query row to
+// gcd(16, 4 d), so both are read with loads of that width (chosen on the host, a template argument here), and nothing is read
+// at or beyond rowp + d: the tail's (at most 11) row values per thread come from whole groups of four inside the row and from
+// predicated element loads.  The tail's query elements are staged once per unit, 16 queries x 16 floats, absent ones zero.
+// The kernels carry the no-packed-fp32-ops target attribute: their subtractions and fmas are single-lane instructions.
+namespace {
+// 4 consecutive elements at p, widened; p is aligned to LOADB bytes or to the four elements, whichever is less
+template <class Row, int LOADB>
+__device__ __forceinline__ void lmt_load4(const Row* __restrict__ p, float* f) {
+    constexpr int B4 = 4 * (int)sizeof(Row), LB = LOADB < B4 ? LOADB : B4;
+    if constexpr (RowKind<Row>::fp32) {
+        if constexpr (LB == 16) {
+            const float4 v = *reinterpret_cast<const float4*>(p);
+            f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w;
+        } else if constexpr (LB == 8) {
+            const float2 a = reinterpret_cast<const float2*>(p)[0], b = reinterpret_cast<const float2*>(p)[1];
+            f[0] = a.x; f[1] = a.y; f[2] = b.x; f[3] = b.y;
+        } else {
+            f[0] = p[0]; f[1] = p[1]; f[2] = p[2]; f[3] = p[3];
+        }
+    } else if constexpr (RowKind<Row>::half) {
+        uint32_t w0, w1;
+        if constexpr (LB == 8) {
+            const uint2 v = *reinterpret_cast<const uint2*>(p);
+            w0 = v.x; w1 = v.y;
+        } else if constexpr (LB == 4) {
+            w0 = reinterpret_cast<const uint32_t*>(p)[0]; w1 = reinterpret_cast<const uint32_t*>(p)[1];
+        } else {
+            w0 = (uint32_t)p[0] | ((uint32_t)p[1] << 16); w1 = (uint32_t)p[2] | ((uint32_t)p[3] << 16);
+        }
+        row_dword_f<Row>(w0, f);
+        row_dword_f<Row>(w1, f + 2);
+    } else {
+        const uint8_t* b = reinterpret_cast<const uint8_t*>(p);
+        uint32_t w;
+        if constexpr (LB == 4) {
+            w = *reinterpret_cast<const uint32_t*>(b);
+        } else if constexpr (LB == 2) {
+            w = (uint32_t)reinterpret_cast<const uint16_t*>(b)[0] | ((uint32_t)reinterpret_cast<const uint16_t*>(b)[1] << 16);
+        } else {
+            w = (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16) | ((uint32_t)b[3] << 24);
+        }
+        row_dword_f<Row>(w, f);
+    }
+}
+// LEN elements at p (a multiple of 16 elements into the row) for the pair of threads: the registers row_pair_load fills.
+// 16-byte rows: row_pair_load itself; byte rows aligned to 8: both threads ask for the same 8 bytes = one element group and each
+// keeps its dword; every other class: each thread's own four elements of a group, in loads of LOADB bytes
+template <class Row, int LEN, int LOADB>
+__device__ __forceinline__ void lmt_row_load(const Row* __restrict__ p, int half, f32x2* yr) {
+    if constexpr (LOADB == 16) {
+        row_pair_load<Row, LEN>(p, half, yr);
+    } else {
+#pragma unroll
+        for (int i = 0; i < LEN / 8; i++) {
+            float f[4];
+            if constexpr (RowKind<Row>::b8 && LOADB == 8) {
+                const uint2 v = reinterpret_cast<const uint2*>(p)[i];
+                const uint32_t vx = v.x, vy = v.y;
+                row_dword_f<Row>(half ? vy : vx, f);
+            } else {
+                lmt_load4<Row, LOADB>(p + 8 * i + 4 * half, f);
+            }
+            yr[2 * i] = f32x2{f[0], f[1]};
+            yr[2 * i + 1] = f32x2{f[2], f[3]};
+        }
+    }
+}
+template <bool L2>
+__device__ __forceinline__ float lmt_step(float x, float y, float a) {
+    if (L2) {
+        const float t = x - y;
+        return __builtin_fmaf(t, t, a);
+    }
+    return __builtin_fmaf(x, y, a);
+}
+
+// lms_piece with the row loads above and the query elements staged QE = min(4, LOADB / sizeof(Row)) at a time (a query row is
+// aligned to QE floats); what lands in LDS, and the fma loop behind it, are lms_piece's
+template <bool L2, class Row, int LEN, int LOADB>
+__device__ __forceinline__ void lmt_piece(const Row* __restrict__ rowp, const float* __restrict__ x, int d, int e0, int half,
+                                          int tid, int nqt, const int* s_q, float4* s_x, f32x2 (&acc)[FS_QT][2]) {
+    constexpr int EL = LOADB / (int)sizeof(Row), QE = EL < 4 ? EL : 4;
+    f32x2 yr[LEN / 4];
+    lmt_row_load<Row, LEN, LOADB>(rowp + e0, half, yr);   // in flight while the tile's queries are staged
+    __syncthreads();   // the previous piece has been consumed
+    for (int e = tid; e < nqt * (LEN / QE); e += 256) {
+        const int qi = e / (LEN / QE), c = e - qi * (LEN / QE);
+        const float* src = x + (int64_t)s_q[qi] * d + e0 + c * QE;
+        if constexpr (QE == 4) s_x[e] = *reinterpret_cast<const float4*>(src);
+        else if constexpr (QE == 2) reinterpret_cast<float2*>(s_x)[e] = *reinterpret_cast<const float2*>(src);
+        else reinterpret_cast<float*>(s_x)[e] = *src;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int qi = 0; qi < FS_QT; qi++) {
+        if (qi < nqt) {
+            const float4* xq = s_x + qi * (LEN / 4) + half;
+#pragma unroll
+            for (int i0 = 0; i0 < LEN / 8; i0 += 8) {
+                float4 xa[8];
+#pragma unroll
+                for (int u = 0; u < 8; u++) xa[u] = (i0 + u) < LEN / 8 ? xq[2 * (i0 + u)] : float4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int u = 0; u < 8; u++) {
+                    const int i = i0 + u;
+                    if (i < LEN / 8) {
+                        const f32x2 xv[2] = {f32x2{xa[u].x, xa[u].y}, f32x2{xa[u].z, xa[u].w}};
+#pragma unroll
+                        for (int k = 0; k < 2; k++) {
+                            if (L2) {
+                                const f32x2 t = xv[k] - yr[2 * i + k];
+                                acc[qi][k] = __builtin_elementwise_fma(t, t, acc[qi][k]);
+                            } else {
+                                acc[qi][k] = __builtin_elementwise_fma(xv[k], yr[2 * i + k], acc[qi][k]);
+                            }
+                        }
+                    }
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+    }
+}
+}  // namespace
+
+#if defined(__HIP_DEVICE_COMPILE__)
+#define GH_SINGLE_LANE_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define GH_SINGLE_LANE_F32   // (the host pass does not know the feature)
+#endif
+template <bool L2, class Row, int LOADB>
+__global__ __launch_bounds__(256) GH_SINGLE_LANE_F32
+void k_ivfflat_lmt(const float* __restrict__ x, int d, int P, const int* __restrict__ pair_off,
+                   const int64_t* __restrict__ list_off, const int* __restrict__ list_len, const int64_t* __restrict__ ids,
+                   const Row* __restrict__ raw, int64_t nraw, const int* __restrict__ inv_start,
+                   const int* __restrict__ inv_cnt, const int* __restrict__ inv, const int* __restrict__ ustart, int nlist,
+                   int64_t q_stride, float* __restrict__ out, const FilterDesc* __restrict__ ftab, int need_filter,
+                   float min_score, float max_score) {
+    static_assert(LOADB >= (int)sizeof(Row) && LOADB <= 16 && (LOADB & (LOADB - 1)) == 0, "a power of two, a whole element");
+    __shared__ float4 s_x[FS_QT * FS_SLAB / 4];
+    __shared__ float4 s_xt[FS_QT * 4];   // the tail's query elements d16 .. d16 + 15 of every query of the tile, absent ones 0
+    __shared__ int s_q[FS_QT];
+    __shared__ int s_off[FS_QT];
+    const int tid = threadIdx.x, half = tid & 1;
+    const float sentinel = L2 ? INFINITY : -INFINITY;
+    const int nunits = ustart[nlist];
+    const int d16 = d & ~15, r = d - d16;      // r: 1 .. 15
+    const int i4 = (d & ~7) - d16;             // the 4-lane step's first element, from d16: 0 or 8
+    const int i1 = (d & ~3) - d16, rem = d & 3;   // the masked step's
+    for (int u = blockIdx.x; u < nunits; u += gridDim.x) {
+        int lo = 0, hi = nlist - 1;
+        while (lo < hi) {   // last list with ustart[l] <= u
+            const int mid = (lo + hi + 1) >> 1;
+            if (ustart[mid] <= u) lo = mid; else hi = mid - 1;
+        }
+        const int l = lo;
+        const int len = list_len[l], n = inv_cnt[l];
+        const int chunks = (len + 127) / 128, rel = u - ustart[l];
+        const int tq0 = (rel / chunks) * FS_QT, nqt = min(FS_QT, n - tq0), r0 = (rel - (rel / chunks) * chunks) * 128;
+        const int64_t base = list_off[l];
+        const int j = r0 + (tid >> 1);
+        const bool inrow = j < len;
+        int64_t id = -1;
+        if (inrow) id = ids[base + j];
+        int64_t rw;
+        const bool live = entry_row<false>(id, inrow, nraw, nullptr, 0, need_filter, ftab, &rw);
+        const Row* rowp = raw + rw * d;
+        __syncthreads();   // the previous unit has stored its distances: s_q, s_off, s_xt are free
+        if (tid < nqt) {
+            const int pr = inv[inv_start[l] + tq0 + tid];
+            const int q = pr / P;
+            s_q[tid] = q;
+            s_off[tid] = pair_off[(int64_t)q * (P + 1) + (pr - q * P)];
+        }
+        // the tail's row values, in flight from here: the thread's four of the 8-wide step, the four of the 4-lane step and the
+        // masked step's (both threads of a row ask for the same ones; only the even thread's sum is stored)
+        float y8[4] = {0.f, 0.f, 0.f, 0.f}, y4[4] = {0.f, 0.f, 0.f, 0.f}, y1[3] = {0.f, 0.f, 0.f};
+        if (r >= 8) lmt_load4<Row, LOADB>(rowp + d16 + 4 * half, y8);
+        if (d & 4) lmt_load4<Row, LOADB>(rowp + d16 + i4, y4);
+#pragma unroll
+        for (int m = 0; m < 3; m++)
+            if (m < rem) y1[m] = row_elem_f<Row>(rowp[d16 + i1 + m]);
+        __syncthreads();   // s_q is written
+        {
+            const int qi = tid >> 4, c = tid & 15;   // 256 threads: 16 queries x 16 elements
+            reinterpret_cast<float*>(s_xt)[tid] = (qi < nqt && c < r) ? x[(int64_t)s_q[qi] * d + d16 + c] : 0.f;
+        }
+        f32x2 acc[FS_QT][2];
+#pragma unroll
+        for (int qi = 0; qi < FS_QT; qi++) acc[qi][0] = acc[qi][1] = f32x2{0.f, 0.f};
+        int e0 = 0;
+        for (; e0 + FS_SLAB <= d16; e0 += FS_SLAB) lmt_piece<L2, Row, FS_SLAB, LOADB>(rowp, x, d, e0, half, tid, nqt, s_q, s_x, acc);
+        if (d16 - e0 >= 64) {
+            lmt_piece<L2, Row, 64, LOADB>(rowp, x, d, e0, half, tid, nqt, s_q, s_x, acc);
+            e0 += 64;
+        }
+        if (d16 - e0 >= 32) {
+            lmt_piece<L2, Row, 32, LOADB>(rowp, x, d, e0, half, tid, nqt, s_q, s_x, acc);
+            e0 += 32;
+        }
+        if (d16 - e0 >= 16) lmt_piece<L2, Row, 16, LOADB>(rowp, x, d, e0, half, tid, nqt, s_q, s_x, acc);
+        __syncthreads();   // s_xt is written (d < 16: no piece has put a barrier behind it)
+#pragma unroll
+        for (int qi = 0; qi < FS_QT; qi++) {
+            if (qi < nqt) {
+                const float4* xt = s_xt + 4 * qi;
+                float a0 = acc[qi][0].x, a1 = acc[qi][0].y, a2 = acc[qi][1].x, a3 = acc[qi][1].y;
+                if (r >= 8) {   // lane l takes element d16 + l into its chain: the even thread lanes 0-3, the odd one 4-7
+                    const float4 xv = xt[half];
+                    a0 = lmt_step<L2>(xv.x, y8[0], a0);
+                    a1 = lmt_step<L2>(xv.y, y8[1], a1);
+                    a2 = lmt_step<L2>(xv.z, y8[2], a2);
+                    a3 = lmt_step<L2>(xv.w, y8[3], a3);
+                }
+                // even thread: AVX lanes 0..3, odd thread: lanes 4..7;  s[l] = acc[l+4] + acc[l]
+                float s0, s1, s2, s3;
+                add_xor1_x4(a0, a1, a2, a3, s0, s1, s2, s3);
+                if (d & 4) {   // the 4-lane step, on the folded sums
+                    const float4 xv = xt[i4 >> 2];
+                    s0 = lmt_step<L2>(xv.x, y4[0], s0);
+                    s1 = lmt_step<L2>(xv.y, y4[1], s1);
+                    s2 = lmt_step<L2>(xv.z, y4[2], s2);
+                    s3 = lmt_step<L2>(xv.w, y4[3], s3);
+                }
+                if (rem) {   // the masked step: lanes at or beyond rem are left alone
+                    const float4 xv = xt[i1 >> 2];
+                    s0 = lmt_step<L2>(xv.x, y1[0], s0);
+                    if (rem > 1) s1 = lmt_step<L2>(xv.y, y1[1], s1);
+                    if (rem > 2) s2 = lmt_step<L2>(xv.z, y1[2], s2);
+                }
+                float dis = hsum4(s0, s1, s2, s3);
+                if (!live || !(dis <= max_score && dis >= min_score)) dis = sentinel;
+                if (inrow && half == 0) out[(int64_t)s_q[qi] * q_stride + s_off[qi] + j] = dis;
+            }
+        }
+    }
+}
+
 // list_len with the lists a shard's mask does not own set to 0: to the list-major launch an unowned list is an empty list
 __global__ __launch_bounds__(256) void k_masked_list_len(const int* __restrict__ list_len, const uint8_t* __restrict__ mask,
                                                          int nlist, int* __restrict__ out) {
@@ -428,6 +673,16 @@ int ivfflat_lm_shape(int d, int* kind, int* slab, int* qtile) {
     *kind = k;
     *slab = k == 1 ? d : k == 2 ? FS_SLAB : 0;
     *qtile = k == 1 ? FL_QT : k == 2 ? FS_QT : 0;
+    return k;
+}
+
+int ivfflat_lm_tail_shape(int d, int elem_bytes, int* kind, int* load_bytes, int* qtile) {
+    const int k = (d >= 1 && d <= 4096 && d % 16 != 0) ? 3 : 0;
+    int lb = 16;   // gcd(16, d * elem_bytes)
+    while (lb > 1 && ((int64_t)d * elem_bytes) % lb != 0) lb >>= 1;
+    *kind = k;
+    *load_bytes = lb;
+    *qtile = FS_QT;
     return k;
 }
 
@@ -570,6 +825,65 @@ void launch_ivfflat_lm(hipStream_t s, bool l2, const float* x, int nq, int d, in
         default: break;
     }
 #undef GH_FLR
+}
+
+// d % 16 != 0 (ivfflat_lm_tail_shape: kind 3), dense fp32 / float16 / uint8 / int8 rows: the inverse index of the row-sliced
+// kernel (k_inv_scan_s: units of FS_QT queries), then k_ivfflat_lmt with the load width the row length allows.  Returns false,
+// with nothing launched, for a store or a length it has no kernel for.
+namespace {
+template <class Row, int LOADB>
+void launch_lmt_k(hipStream_t s, bool l2, const float* x, int d, int P, const int* pair_off, const int64_t* list_off,
+                  const int* list_len, int nlist, const int64_t* ids, const Row* raw, int64_t nraw, const int* start,
+                  const int* cnt, const int* inv, const int* ustart, int64_t q_stride, float* out, const FilterDesc* ftab,
+                  int need_filter, float min_score, float max_score) {
+    const int grid = 256 * 8;   // persistent, as the two other list-major kernels
+    if (l2)
+        hipLaunchKernelGGL((k_ivfflat_lmt<true, Row, LOADB>), dim3(grid), dim3(256), 0, s, x, d, P, pair_off, list_off, list_len, ids,
+                           raw, nraw, start, cnt, inv, ustart, nlist, q_stride, out, ftab, need_filter, min_score, max_score);
+    else
+        hipLaunchKernelGGL((k_ivfflat_lmt<false, Row, LOADB>), dim3(grid), dim3(256), 0, s, x, d, P, pair_off, list_off, list_len, ids,
+                           raw, nraw, start, cnt, inv, ustart, nlist, q_stride, out, ftab, need_filter, min_score, max_score);
+}
+}  // namespace
+
+bool launch_ivfflat_lm_tail(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* probe, const int* pair_off,
+                            const int64_t* list_off, const int* list_len, int nlist, const int64_t* ids, const RowsRef& raw,
+                            int64_t nraw, int64_t q_stride, float* out, const FilterDesc* ftab, int need_filter, float min_score,
+                            float max_score, void* scratch) {
+    int kind = 0, lb = 0, qtile = 0;
+    if (raw.et < 0 || raw.et > 3 || ivfflat_lm_tail_shape(d, (int)raw.esz(), &kind, &lb, &qtile) != 3) return false;
+    if (nq <= 0 || P <= 0) return true;
+    int* inv = static_cast<int*>(scratch);
+    int* cnt = inv + (size_t)nq * P;
+    int* start = cnt + nlist;
+    int* cur = start + nlist;
+    int* ustart = cur + nlist;
+    const int npairs = nq * P;
+    (void)hipMemsetAsync(cnt, 0, (size_t)nlist * sizeof(int), s);
+    hipLaunchKernelGGL(k_inv_count, dim3((npairs + 255) / 256), dim3(256), 0, s, probe, npairs, nlist, list_len, cnt);
+    hipLaunchKernelGGL(k_inv_scan_s, dim3(1), dim3(1024), 0, s, cnt, list_len, nlist, start, cur, ustart);
+    hipLaunchKernelGGL(k_inv_fill, dim3((npairs + 255) / 256), dim3(256), 0, s, probe, npairs, nlist, list_len, start, cur, inv);
+#define GH_FLT(T, B)                                                                                                           \
+    case B:                                                                                                                    \
+        launch_lmt_k<T, B>(s, l2, x, d, P, pair_off, list_off, list_len, nlist, ids, raw.as<T>(), nraw, start, cnt, inv, ustart, \
+                           q_stride, out, ftab, need_filter, min_score, max_score);                                           \
+        break;
+    switch (raw.et) {
+        case 0:
+            switch (lb) { GH_FLT(float, 16) GH_FLT(float, 8) GH_FLT(float, 4) }
+            break;
+        case 1:
+            switch (lb) { GH_FLT(uint16_t, 16) GH_FLT(uint16_t, 8) GH_FLT(uint16_t, 4) GH_FLT(uint16_t, 2) }
+            break;
+        case 2:
+            switch (lb) { GH_FLT(uint8_t, 8) GH_FLT(uint8_t, 4) GH_FLT(uint8_t, 2) GH_FLT(uint8_t, 1) }
+            break;
+        default:
+            switch (lb) { GH_FLT(int8_t, 8) GH_FLT(int8_t, 4) GH_FLT(int8_t, 2) GH_FLT(int8_t, 1) }
+            break;
+    }
+#undef GH_FLT
+    return true;
 }
 
 }  // namespace gh

@@ -375,6 +375,16 @@ bool ivfflat_lm_supported(int d);
 // elements of a row a pair of threads holds at a time, *qtile = the queries per LDS tile (both 0 with kind 0).  Returns kind.
 int ivfflat_lm_shape(int d, int* kind, int* slab, int* qtile);
 size_t ivfflat_lm_scratch_bytes(int nq, int P, int nlist);
+// the list-major form of the lengths ivfflat_lm_shape answers 0 for: *kind 3 = row-sliced with the scanner's tail steps
+// (k_ivfflat_lmt: 1 <= d <= 4096, d % 16 != 0), else 0; *load_bytes = gcd(16, d * elem_bytes), the alignment every row of such a
+// store has and the width of the kernel's row loads; *qtile = the queries per LDS tile (k_ivfflat_lms's).  Returns kind.
+int ivfflat_lm_tail_shape(int d, int elem_bytes, int* kind, int* load_bytes, int* qtile);
+// kind 3 over the dense rows of an fp32 / float16 / uint8 / int8 store, scratch as launch_ivfflat_lm's; false = nothing launched
+// (another length, an sq8 store)
+bool launch_ivfflat_lm_tail(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* probe, const int* pair_off,
+                            const int64_t* list_off, const int* list_len, int nlist, const int64_t* ids, const RowsRef& raw,
+                            int64_t nraw, int64_t q_stride, float* out, const FilterDesc* ftab, int need_filter, float min_score,
+                            float max_score, void* scratch);
 void launch_ivfflat_lm(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* probe, const int* pair_off,
                        const int64_t* list_off, const int* list_len, int nlist, const int64_t* ids, const float* raw,
                        int64_t nraw, int64_t q_stride, float* out, const FilterDesc* ftab, int need_filter, float min_score,

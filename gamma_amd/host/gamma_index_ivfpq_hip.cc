@@ -1051,6 +1051,18 @@ int RegisterHIPIVFFlatSq8Rows(HIPIVFFlatSq8RowsFn fn) {
 HIPIVFFlatSq8RowsFn FindHIPIVFFlatSq8Rows() { return IVFFlatSq8Rows(); }
 
 namespace {
+const HIPIVFFlatTailsOps *&IVFFlatTails() {
+  static const HIPIVFFlatTailsOps *ops = nullptr;
+  return ops;
+}
+}  // namespace
+int RegisterHIPIVFFlatTails(const HIPIVFFlatTailsOps *ops) {
+  IVFFlatTails() = ops;
+  return 0;
+}
+const HIPIVFFlatTailsOps *FindHIPIVFFlatTails() { return IVFFlatTails(); }
+
+namespace {
 HIPIVFFlatGroupSearchFn &IVFFlatGroupSearch() {
   static HIPIVFFlatGroupSearchFn fn = nullptr;
   return fn;
@@ -1199,6 +1211,15 @@ int GammaIVFFlatHIPIndex::Init(const std::string &model_parameters, int indexing
     HLOG("HIPIVFFLAT: raw_dtype: this build of the plugin has no IVFFLAT search over sq8 rows");
     return -1;
   }
+  // "lm_tails": 0 (the default) | 1: row lengths that are no multiple of 16 list-major, where the build has the switch
+  const HIPIVFFlatTailsOps *lm_tails = nullptr;
+  if (jp.Contains("lm_tails")) {
+    if (!FindHIPIVFFlatTails() || jp.GetInt("lm_tails", v) || (v != 0 && v != 1)) {
+      HLOG("HIPIVFFLAT: invalid lm_tails (0 or 1, and only where this build of the plugin has the list-major scan of such rows)");
+      return -1;
+    }
+    if (v == 1) lm_tails = FindHIPIVFFlatTails();
+  }
   raw_f16_ = et == 1;
   raw_i8_ = narrow && et >= 2 ? et - 1 : 0;
   // several devices: the in-process group (DeviceKeys: what the keys ask, decided before a device is opened)
@@ -1270,11 +1291,18 @@ int GammaIVFFlatHIPIndex::Init(const std::string &model_parameters, int indexing
     if (flat_rows) rc = flat_rows(h_, 1);
   }
   if (!rc) rc = gamma_hip_set_exact_ties(h_, pa.exact_ties ? 1 : 0);
+  if (!rc && lm_tails) rc = lm_tails->set(h_, 1);   // (one handle: the group's shard entries have no such scan)
   if (rc) {
     HLOG("device init failed: %s (%s)", gamma_hip_strerror(rc), gamma_hip_last_error(h_));
     return -1;
   }
   return 0;
+}
+
+int64_t GammaIVFFlatHIPIndex::LmTailChunks() {
+  const HIPIVFFlatTailsOps *ops = FindHIPIVFFlatTails();
+  int64_t n = 0;
+  return ops && h_ && !ops->stats(h_, &n, 0) ? n : -1;
 }
 
 RetrievalParameters *GammaIVFFlatHIPIndex::Parse(const std::string &parameters) {   // gamma_index_ivfflat.cc:188-242

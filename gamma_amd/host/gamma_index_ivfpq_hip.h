@@ -119,6 +119,16 @@ typedef int (*HIPIVFFlatSq8RowsFn)(gamma_hip_index *h, int on);
 int RegisterHIPIVFFlatSq8Rows(HIPIVFFlatSq8RowsFn fn);
 HIPIVFFlatSq8RowsFn FindHIPIVFFlatSq8Rows();
 
+// HIPIVFFLAT's "lm_tails": 1: row lengths that are no multiple of 16 go to the list-major scan (the handle's switch
+// gamma_hip_set_ivfflat_lm_tails and its counter), registered the same way by gamma_index_ivfflat_tails_hip.cc -- the only host
+// file that names them.  Without that file HIPIVFFLAT::Init rejects the key.
+struct HIPIVFFlatTailsOps {
+  int (*set)(gamma_hip_index *h, int on);
+  int (*stats)(gamma_hip_index *h, int64_t *out1, int reset);
+};
+int RegisterHIPIVFFlatTails(const HIPIVFFlatTailsOps *ops);
+const HIPIVFFlatTailsOps *FindHIPIVFFlatTails();
+
 // HIPIVFFLAT with "devices": "0,1,.." (several): the in-process group's IVFFLAT search (gamma_hip_group_ivfflat_search), registered
 // the same way by gamma_index_ivfflat_group_hip.cc -- the only host file that names it.  Without that file HIPIVFFLAT reads none of
 // "devices" / "placement" / "raw_placement" and opens one handle, as it always did.
@@ -309,6 +319,8 @@ class GammaIVFFlatHIPIndex : public GammaIVFPQHIPIndex {
   int Dump(const std::string &dir) override;
   int Load(const std::string &dir) override;
   int SetTrainedCoarse(const float *coarse_centroids);
+  // query chunks the list-major scan of row lengths that are no multiple of 16 has served ("lm_tails": 1); -1: a build without it
+  int64_t LmTailChunks();
   // the "raw_dtype" key of the model's parameters: HIPParseRawDtype's answer, and *et = 4 for "sq8" together with
   // "sq8_ranges": "trained" (case-insensitive; the ranges are learned by Indexing() and kept in raw_sq8.ranges beside
   // ivfflat.index).  -1 and one log line for "sq8" without that key (as before), any other value of the key, the key beside

@@ -371,6 +371,11 @@ int gh_host_ivfpq_sq8_ranges(void *hp, float *vmin, float *vmax) {
   GammaIVFPQHIPIndex *m = dynamic_cast<GammaIVFPQHIPIndex *>(((Host *)hp)->model);
   return m ? m->Sq8Ranges(vmin, vmax) : -1;
 }
+// query chunks a HIPIVFFLAT model's list-major scan of row lengths that are no multiple of 16 has served; -1 otherwise
+int64_t gh_host_ivfflat_lm_tail_chunks(void *hp) {
+  GammaIVFFlatHIPIndex *m = dynamic_cast<GammaIVFFlatHIPIndex *>(((Host *)hp)->model);
+  return m ? m->LmTailChunks() : -1;
+}
 // IwPQ files with and without the "LTra" record (host only): `in` rewritten to `out` with the record holding A (n floats) or,
 // A == NULL, without one; and the record of a file: its float count (0: none), A_out filled up to cap floats; < 0: ReadIwPQ's
 int gh_iwpq_rewrite_opq(const char *in, const char *out, const float *A, int64_t n) {

@@ -51,6 +51,7 @@ HOST_SYMBOLS = {
     "gh_host_ivfpq_set_trained": (C.c_int, [C.c_void_p, f32p, f32p]),
     "gh_host_ivfpq_opq": (C.c_int, [C.c_void_p, f32p]),
     "gh_host_ivfpq_sq8_ranges": (C.c_int, [C.c_void_p, f32p, f32p]),
+    "gh_host_ivfflat_lm_tail_chunks": (C.c_int64, [C.c_void_p]),
     "gh_iwpq_rewrite_opq": (C.c_int, [C.c_char_p, C.c_char_p, f32p, C.c_int64]),
     "gh_iwpq_read_opq": (C.c_int64, [C.c_char_p, f32p, C.c_int64]),
     "gh_parse_ivfpq_model_params": (None, [C.c_char_p, C.POINTER(C.c_int)]),
@@ -407,6 +408,10 @@ class PluginModel:
         """(vmin, vmax) of a model created with "raw_dtype": "sq8" (after Indexing or Load), or None"""
         vmin, vmax = np.empty(self.d, np.float32), np.empty(self.d, np.float32)
         return (vmin, vmax) if self.L.gh_host_ivfpq_sq8_ranges(self.h, _f(vmin), _f(vmax)) == 1 else None
+
+    def ivfflat_lm_tail_chunks(self):
+        """query chunks a HIPIVFFLAT model's list-major scan of row lengths that are no multiple of 16 ("lm_tails": 1) has served"""
+        return int(self.L.gh_host_ivfflat_lm_tail_chunks(self.h))
 
 
 def iwpq_rewrite_opq(path_in, path_out, A=None):

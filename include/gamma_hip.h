@@ -265,6 +265,24 @@ int gamma_hip_ivfflat_lm_shape(int d, int* kind, int* slab, int* qtile);
  * synchronisation, no device read.  The reference has no counterpart (its scanner walks one list for one query:
  * gamma_index_ivfflat.h:52-75). */
 int gamma_hip_ivfflat_scan_stats(gamma_hip_index* h, int64_t* out4, int reset);
+/* The list-major form of the row lengths gamma_hip_ivfflat_lm_shape answers 0 for.  No handle, no device
+ * call: *kind = 3 for 1 <= d <= 4096 with d % 16 != 0 (the row-sliced kernel with fvec_L2sqr / fvec_inner_product's 4-lane and
+ * masked steps behind the fold, k_ivfflat_lmt), otherwise 0; *load_bytes = gcd(16, d * elem_bytes), the alignment every row of a
+ * dense store of such rows has and the width of the kernel's row loads; *qtile = the queries per tile (the row-sliced kernel's),
+ * whatever kind says.  elem_bytes: 4 (fp32), 2 (float16), 1 (uint8 / int8).  gamma_hip_ivfflat_lm_shape's answers are unchanged.
+ * Returns GAMMA_HIP_OK; GAMMA_HIP_EINVAL for a null pointer, d < 1 or another elem_bytes. */
+int gamma_hip_ivfflat_lm_tail_shape(int d, int elem_bytes, int* kind, int* load_bytes, int* qtile);
+/* A switch of the handle, independent of every other.  on: 0 (default) = every call launches what it always launched (kind 3
+ * lengths: one workgroup per (query, probe) pair); 1 = a query chunk of gamma_hip_ivfflat_search / _search_device over a dense
+ * fp32 / float16 / uint8 / int8 store of a kind 3 length is scanned list-major by k_ivfflat_lmt under the gates of the two
+ * other forms (at least 2 nlist pairs in the chunk, no list mask, GAMMA_HIP_NO_IVFFLAT_LM unset, the small path first).  The
+ * bits of every distance and label are the same either way.  An sq8 store, the shard entries and sparse stores are not served
+ * by it.  gamma_hip_get_ivfflat_lm_tails reads the switch back. */
+int gamma_hip_set_ivfflat_lm_tails(gamma_hip_index* h, int on);
+int gamma_hip_get_ivfflat_lm_tails(gamma_hip_index* h, int* on);
+/* out1 = {query chunks scanned by k_ivfflat_lmt} since creation or the last reset; such a chunk is counted in none of the four
+ * counters of gamma_hip_ivfflat_scan_stats. */
+int gamma_hip_ivfflat_lm_tail_stats(gamma_hip_index* h, int64_t* out1, int reset);
 /* Flat search over a scalar-quantised raw store (gamma_hip_raw_init_sq8); a switch of its own, independent of the two above.
  * on: 0 (default) = gamma_hip_flat_search, _flat_search_device and _flat_search_device_wait refuse an sq8 store with
  * GAMMA_HIP_EUNSUPPORTED, as before and whatever gamma_hip_set_flat_narrow_rows says; 1 = the three serve it: every code is
