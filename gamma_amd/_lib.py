@@ -137,6 +137,10 @@ SYMBOLS = {
     "gamma_hip_binivf_scan_mode": (C.c_int, [C.c_void_p]),
     "gamma_hip_binivf_scan_shape": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "gamma_hip_binivf_scan_stats": (C.c_int, [C.c_void_p, i64p, C.c_int]),
+    "gamma_hip_binivf_set_lm_scan": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "gamma_hip_binivf_lm_scan": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "gamma_hip_binivf_lm_shape": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "gamma_hip_binivf_lm_stats": (C.c_int, [C.c_void_p, i64p, C.c_int]),
     "gamma_hip_binflat_init":(C.c_int, [C.c_void_p, C.c_int]),
     "gamma_hip_binflat_append": (C.c_int, [C.c_void_p, C.c_int64, u8p]),
     "gamma_hip_binflat_count": (C.c_int64, [C.c_void_p]),

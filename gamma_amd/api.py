@@ -547,6 +547,25 @@ class GammaHip:
         self._ck(self.L.gamma_hip_binivf_scan_stats(self.h, _p(out, _lib.i64p), 1 if reset else 0), "binivf_scan_stats")
         return tuple(int(v) for v in out)
 
+    def binivf_set_lm_scan(self, on, min_nq=0):
+        """the list-major scan of large batches: calls the scan mode leaves to one wave per query, of at least min_nq
+        queries (0: binivf_lm_shape()[2]), keep a list's rows in registers for all the queries that probe it.  Off by
+        default; the answer is the same."""
+        self._ck(self.L.gamma_hip_binivf_set_lm_scan(self.h, 1 if on else 0, int(min_nq)), "binivf_set_lm_scan")
+
+    def binivf_lm_scan(self):
+        """(on, min_nq) as set"""
+        on, mn = C.c_int(0), C.c_int(0)
+        self._ck(self.L.gamma_hip_binivf_lm_scan(self.h, C.byref(on), C.byref(mn)), "binivf_lm_scan")
+        return int(on.value), int(mn.value)
+
+    def binivf_lm_stats(self, reset=False):
+        """(queries the list-major chain answered, its work units, their chunks, their candidates, queries that fell back to
+        one wave per query for lack of workspace); counted while profiling is on"""
+        out = np.zeros(5, dtype=np.int64)
+        self._ck(self.L.gamma_hip_binivf_lm_stats(self.h, _p(out, _lib.i64p), 1 if reset else 0), "binivf_lm_stats")
+        return tuple(int(v) for v in out)
+
     # ---- exact Hamming (binary flat) search: faiss:IndexBinaryFlat.cpp / utils/hamming.cpp:230-265, answered as
     #      GammaIVFBinaryScannerL2::scan_codes answers one list holding every code in vid order ----
     def binflat_init(self, nbits):
@@ -1129,6 +1148,16 @@ def binivf_scan_shape():
     if rc != 0:
         raise _lib.GammaHipError("binivf_scan_shape: %d" % rc)
     return int(c.value), int(a.value)
+
+
+def binivf_lm_shape():
+    """(chunk_rows, query_tile, auto_min_nq) of binivf_search's list-major scan: the rows of a list chunk, the queries of a
+    work unit, and the call size binivf_set_lm_scan(on, 0) starts at.  No device call."""
+    c, t, a = C.c_int(0), C.c_int(0), C.c_int(0)
+    rc = _lib.load().gamma_hip_binivf_lm_shape(C.byref(c), C.byref(t), C.byref(a))
+    if rc != 0:
+        raise _lib.GammaHipError("binivf_lm_shape: %d" % rc)
+    return int(c.value), int(t.value), int(a.value)
 
 
 def train_ivfpq(x, nlist, M, device=0):

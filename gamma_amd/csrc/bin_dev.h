@@ -51,6 +51,54 @@ __device__ __forceinline__ void bin_load_query(const uint8_t* xq, int cs, int nw
     for (int w = (int)threadIdx.x; w < nw; w += nthr) qw[w] = bin_word_bytes(xq, w, cs);
 }
 
+// ---- rows held in registers (binivf_lm.hip): W words per row, W % 4 == 0, the words beyond nw are zero ----
+// LW: the load width in bytes, 16 (cs % 16 == 0), 4 (cs % 4 == 0) or 1.  ok false: a row of zeros, nothing is read.
+template <int LW, int W>
+__device__ __forceinline__ void bin_row_load(const uint8_t* __restrict__ c, bool ok, int cs, int nw, uint32_t (&r)[W]) {
+#pragma unroll
+    for (int g = 0; g < W / 4; g++) {
+        uint4 v = make_uint4(0u, 0u, 0u, 0u);
+        if (ok && 4 * g < nw) {   // (4 g < nw is wave uniform)
+            if (LW == 16) {
+                v = reinterpret_cast<const uint4*>(c)[g];
+            } else if (LW == 4) {
+                const uint32_t* c32 = reinterpret_cast<const uint32_t*>(c);
+                v.x = c32[4 * g];
+                if (4 * g + 1 < nw) v.y = c32[4 * g + 1];
+                if (4 * g + 2 < nw) v.z = c32[4 * g + 2];
+                if (4 * g + 3 < nw) v.w = c32[4 * g + 3];
+            } else {
+                v.x = bin_word_bytes(c, 4 * g, cs);
+                v.y = bin_word_bytes(c, 4 * g + 1, cs);
+                v.z = bin_word_bytes(c, 4 * g + 2, cs);
+                v.w = bin_word_bytes(c, 4 * g + 3, cs);
+            }
+        }
+        r[4 * g] = v.x;
+        r[4 * g + 1] = v.y;
+        r[4 * g + 2] = v.z;
+        r[4 * g + 3] = v.w;
+    }
+}
+
+// the Hamming distances of R register rows to one query: q = its W words in LDS, 16-byte aligned, zero beyond nw (every
+// lane reads the same address: a broadcast, four words per read)
+template <int R, int W>
+__device__ __forceinline__ void bin_rows_hamming(const uint32_t (&r)[R][W], const uint32_t* q, int nw, int (&d)[R]) {
+#pragma unroll
+    for (int j = 0; j < R; j++) d[j] = 0;
+#pragma unroll
+    for (int g = 0; g < W / 4; g++) {
+        if (4 * g < nw) {
+            const uint4 v = reinterpret_cast<const uint4*>(q)[g];
+#pragma unroll
+            for (int j = 0; j < R; j++)
+                d[j] += __popc(r[j][4 * g] ^ v.x) + __popc(r[j][4 * g + 1] ^ v.y) + __popc(r[j][4 * g + 2] ^ v.z) +
+                        __popc(r[j][4 * g + 3] ^ v.w);
+        }
+    }
+}
+
 __device__ __forceinline__ unsigned bin_wave_sum(unsigned v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);

@@ -44,6 +44,45 @@ void launch_bin_spread(hipStream_t s, const uint8_t* x, int nq, int64_t xs, int 
                        const FilterDesc* ftab, int need_filter, float min_score, float max_score, int k, int maxch,
                        int64_t stride, uint32_t* hist, void* meta, uint2* cand, float* D, int64_t* I,
                        unsigned long long* stats, unsigned long long* sp_stats, int stage);
+// ---- the chain's two heavy passes list-major, for large batches (binivf_lm.hip) ----
+// queries of one work unit: a unit is (a kBinSpreadChunk-row chunk of a LIST) x (a tile of the queries that probe the list)
+constexpr int kBinLmQueryTile = 32;
+// the smallest call gamma_hip_binivf_set_lm_scan(on, 0) sends list-major.  Measured at workload B1: no
+// size at which the path is faster at both k = 10 and k = 100; 16384 is the one size beyond the spread chain's range at
+// which it was faster at k = 10.  The switch is an opt-in.
+constexpr int kBinLmAutoMinNq = 16384;
+// what the unit count of a call cannot exceed: every probed list has at most one ragged tile
+int64_t bin_lm_unit_bound(int nq, int P, int nlist, int max_list_len);
+// bytes of the chain's tables (bin_spread_meta_bytes) with the per-(query, probe) chunk base behind them
+size_t bin_lm_meta_bytes(int nq, int P, int maxch);
+// bytes of the call's inverse index: the (query, probe) pairs of every list, the lists' counts, starts and unit prefix
+size_t bin_lm_inv_bytes(int nq, int P, int nlist);
+// launch_bin_spread's answer with k_bin_sp_hist / k_bin_sp_collect replaced by k_bin_lm_hist / k_bin_lm_collect over
+// the call's inverse index; the table, bounds and replay kernels are the chain's.  meta: bin_lm_meta_bytes, inv:
+// bin_lm_inv_bytes, the rest as launch_bin_spread.  No limit on nq.  lm_stats (may be null): += {queries, chunks,
+// candidates, units}.  stage: 0 all, 1 inverse index + table + histograms + bounds, 2 collect, 3 replay
+void launch_bin_lm(hipStream_t s, const uint8_t* x, int nq, int64_t xs, int cs, const int* probe, int P, int nlist,
+                   int max_list_len, const int64_t* list_off, const int* list_len, const uint8_t* codes, const int64_t* ids,
+                   const FilterDesc* ftab, int need_filter, float min_score, float max_score, int k, int maxch,
+                   int64_t stride, uint32_t* hist, void* meta, void* inv, uint2* cand, float* D, int64_t* I,
+                   unsigned long long* stats, unsigned long long* lm_stats, int stage);
+// the chain's kernels launch_bin_lm launches as launch_bin_spread does (binivf_spread.hip)
+__global__ void k_bin_sp_table(const int* __restrict__ probe, int nq, int P, const int* __restrict__ list_len, int maxch,
+                               int2* __restrict__ cmap, int* __restrict__ nchq);
+__global__ void k_bin_sp_bounds(const uint32_t* __restrict__ hist, int nq, const int* __restrict__ nchq, int maxch, int nb,
+                                int k, int* __restrict__ bound, uint32_t* __restrict__ off, uint32_t* __restrict__ total);
+__global__ void k_bin_sp_replay(const uint2* __restrict__ cand, int64_t stride, const uint32_t* __restrict__ total,
+                                const int* __restrict__ nchq, int nq, int k, const int64_t* __restrict__ ids,
+                                float* __restrict__ D, int64_t* __restrict__ I, unsigned long long* __restrict__ stats,
+                                unsigned long long* __restrict__ sp_stats);
+// the counting sort of a call's (query, probe) pairs by list (ivfflat.hip), as launch_bin_lm runs it: cnt zeroed ->
+// k_inv_count -> k_inv_scan_b (units of kBinLmQueryTile queries x kBinSpreadChunk rows) -> k_inv_fill
+__global__ void k_inv_count(const int* __restrict__ probe, int npairs, int nlist, const int* __restrict__ list_len,
+                            int* __restrict__ cnt);
+__global__ void k_inv_scan_b(const int* __restrict__ cnt, const int* __restrict__ list_len, int nlist, int* __restrict__ start,
+                             int* __restrict__ cur, int* __restrict__ ustart);
+__global__ void k_inv_fill(const int* __restrict__ probe, int npairs, int nlist, const int* __restrict__ list_len,
+                           const int* __restrict__ start, int* __restrict__ cur, int* __restrict__ inv);
 // binary_to_real (faiss:utils/utils.cpp:634-638): n codes of d bits -> n x d floats of +-1
 void launch_bin_decode(hipStream_t s, const uint8_t* codes, int64_t n, int d, float* out);
 

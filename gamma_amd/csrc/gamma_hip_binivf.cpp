@@ -12,6 +12,60 @@ namespace {
 // the row stride (bytes) of the queries staged through host_search, whose rows are whole floats
 inline int bin_row_words(int cs) { return (cs + 3) / 4; }
 
+// The scan of a call list-major (binivf_lm.hip), after the coarse step has filled w_probe: the chain's workspaces plus the
+// inverse index, in sub-batches of queries -- the largest that keeps histograms + tables + slab + inverse index within half
+// the workspace budget -- each an independent chain over its slice of w_probe, the queries, D and I.  Only a call of which
+// not even one query tile fits runs k_bin_scan (counted).  Enqueued, nothing read back.
+int bin_lm_search_locked(H* h, const gamma_hip_search_params* p, int nq, const uint8_t* d_x, int64_t xs, int k, int P,
+                         const gh::FilterDesc* d_ftab, int need_filter, float* d_distances, int64_t* d_labels) {
+    hipStream_t s = h->stream;
+    const int ver = h->cur_ver;
+    int maxch = 0;
+    int64_t stride = 0;
+    gh::bin_spread_bounds(P, h->nlist, h->max_list_len, &maxch, &stride);
+    const size_t nb = (size_t)h->code_size * 8 + 1;
+    auto bytes = [&](int n) {
+        return (size_t)n * maxch * nb * sizeof(uint32_t) + gh::bin_lm_meta_bytes(n, P, maxch) +
+               (size_t)n * (size_t)stride * sizeof(uint2) + gh::bin_lm_inv_bytes(n, P, h->nlist);
+    };
+    const size_t half = h->dist_budget_bytes / 2;
+    // (the bytes grow linearly in n: an estimate from one query's share, then settled against the exact sum)
+    int qb = (int)std::min<size_t>((size_t)nq, half / std::max<size_t>(1, bytes(1)));
+    // one sub-batch's pair and unit counts are ints
+    qb = (int)std::min<int64_t>(qb, 2147483647 / std::max<int64_t>(1, (int64_t)P * std::max(1, maxch)));
+    while (qb > 0 && bytes(qb) > half) qb--;
+    while (qb < nq && bytes(qb + 1) <= half) qb++;
+    if (qb < std::min(nq, gh::kBinLmQueryTile)) {
+        if (h->profile) h->bin_lm_fallback += nq;
+        StageScope t(h, GAMMA_HIP_STAGE_SCAN);
+        gh::launch_bin_scan(s, d_x, nq, xs, h->code_size, h->w_probe.as<int>(), P, h->d_list_off, h->d_list_len, h->d_codes,
+                            h->d_ids, d_ftab, need_filter, p->min_score, p->max_score, k, d_distances, d_labels,
+                            h->profile ? h->d_bin_stats : nullptr);
+    } else {
+        GH_CHECK(h, h->w_bs_hist.ensure((size_t)qb * maxch * nb * sizeof(uint32_t)));
+        GH_CHECK(h, h->w_bs_meta.ensure(gh::bin_lm_meta_bytes(qb, P, maxch)));
+        GH_CHECK(h, h->w_bs_cand.ensure((size_t)qb * (size_t)stride * sizeof(uint2)));
+        GH_CHECK(h, h->w_bs_inv.ensure(gh::bin_lm_inv_bytes(qb, P, h->nlist)));
+        const int stages[3] = {GAMMA_HIP_STAGE_TABLES, GAMMA_HIP_STAGE_SCAN, GAMMA_HIP_STAGE_SELECT};
+        for (int q0 = 0; q0 < nq; q0 += qb) {
+            const int n = std::min(qb, nq - q0);
+            for (int st = 0; st < 3; st++) {   // inverse index + table + histograms + bounds | collect | replay
+                StageScope t(h, stages[st], q0 == 0);
+                gh::launch_bin_lm(s, d_x + (int64_t)q0 * xs, n, xs, h->code_size, h->w_probe.as<int>() + (size_t)q0 * P, P,
+                                  h->nlist, h->max_list_len, h->d_list_off, h->d_list_len, h->d_codes, h->d_ids, d_ftab,
+                                  need_filter, p->min_score, p->max_score, k, maxch, stride, h->w_bs_hist.as<uint32_t>(),
+                                  h->w_bs_meta.p, h->w_bs_inv.p, h->w_bs_cand.as<uint2>(), d_distances + (int64_t)q0 * k,
+                                  d_labels + (int64_t)q0 * k, h->profile ? h->d_bin_stats : nullptr,
+                                  h->profile ? h->d_bin_stats + 5 : nullptr, st + 1);
+            }
+        }
+    }
+    GH_CHECK(h, hipGetLastError());
+    GH_CHECK(h, hipEventRecord(h->rd_ev[ver], s));
+    h->rd_set[ver] = true;
+    return GAMMA_HIP_OK;
+}
+
 int bin_search_device_locked(H* h, const gamma_hip_search_params* p, int nq, const uint8_t* d_x, int64_t xs, int k,
                              float* d_distances, int64_t* d_labels) {
     if (!p) return fail(h, GAMMA_HIP_EINVAL, "null params");
@@ -44,6 +98,9 @@ int bin_search_device_locked(H* h, const gamma_hip_search_params* p, int nq, con
     static const bool no_spread = getenv("GAMMA_HIP_NO_BIN_SPREAD") != nullptr;
     const int mode = no_spread ? 0 : h->bin_scan_mode;
     bool spread = mode == 1 || (mode == -1 && nq <= gh::kBinSpreadAutoMaxNq);
+    // gamma_hip_binivf_set_lm_scan: a call the rule above leaves to k_bin_scan goes list-major from min_nq queries on
+    if (!spread && h->bin_lm_on && nq >= (h->bin_lm_min_nq > 0 ? h->bin_lm_min_nq : gh::kBinLmAutoMinNq))
+        return bin_lm_search_locked(h, p, nq, d_x, xs, k, P, fc.d_tab, need_filter, d_distances, d_labels);
     int maxch = 0;
     int64_t stride = 0;
     size_t hist_b = 0, meta_b = 0, cand_b = 0;
@@ -258,6 +315,55 @@ int gamma_hip_binivf_scan_stats(gamma_hip_index* h, int64_t* out4, int reset) {
         GH_CHECK(h, hipMemsetAsync(h->d_bin_stats + 2, 0, sizeof(v), h->stream));
         GH_CHECK(h, hipStreamSynchronize(h->stream));
         h->bin_sp_fallback = 0;
+    }
+    return GAMMA_HIP_OK;
+}
+
+// The list-major scan of large batches (binivf_lm.hip): scan_codes' answer (gamma_index_binary_ivf.cc:333-448) for the
+// calls the scan mode leaves to k_bin_scan, from min_nq queries on (0: the measured kBinLmAutoMinNq).  Off by default.
+int gamma_hip_binivf_set_lm_scan(gamma_hip_index* h, int on, int min_nq) {
+    if (!h) return GAMMA_HIP_EINVAL;
+    SearchLock lk(h);
+    if (!h->ivf_init || !h->binivf) return fail(h, GAMMA_HIP_EINVAL, "binivf not initialised");
+    if (min_nq < 0) return fail(h, GAMMA_HIP_EINVAL, "binivf lm scan: min_nq < 0");
+    h->bin_lm_on = on != 0;
+    h->bin_lm_min_nq = min_nq;
+    return GAMMA_HIP_OK;
+}
+
+int gamma_hip_binivf_lm_scan(const gamma_hip_index* h, int* on, int* min_nq) {
+    if (!h || !h->ivf_init || !h->binivf) return GAMMA_HIP_EINVAL;
+    if (on) *on = h->bin_lm_on ? 1 : 0;
+    if (min_nq) *min_nq = h->bin_lm_min_nq;
+    return GAMMA_HIP_OK;
+}
+
+int gamma_hip_binivf_lm_shape(int* chunk_rows, int* query_tile, int* auto_min_nq) {
+    if (chunk_rows) *chunk_rows = gh::kBinSpreadChunk;
+    if (query_tile) *query_tile = gh::kBinLmQueryTile;
+    if (auto_min_nq) *auto_min_nq = gh::kBinLmAutoMinNq;
+    return GAMMA_HIP_OK;
+}
+
+// {queries the list-major chain answered, its work units, the queries' chunks, their candidates, queries that ran
+// k_bin_scan because not one query tile fitted the workspace} of the searches made while profiling was on
+int gamma_hip_binivf_lm_stats(gamma_hip_index* h, int64_t* out5, int reset) {
+    if (!h || !out5) return GAMMA_HIP_EINVAL;
+    SearchLock lk(h);
+    if (!h->ivf_init || !h->binivf) return fail(h, GAMMA_HIP_EINVAL, "binivf not initialised");
+    GH_CHECK(h, hipSetDevice(h->device));
+    unsigned long long v[4] = {0, 0, 0, 0};   // {queries, chunks, candidates, units}: k_bin_sp_replay's three, k_bin_lm_hist's
+    GH_CHECK(h, hipMemcpyAsync(v, h->d_bin_stats + 5, sizeof(v), hipMemcpyDeviceToHost, h->stream));
+    GH_CHECK(h, hipStreamSynchronize(h->stream));
+    out5[0] = (int64_t)v[0];
+    out5[1] = (int64_t)v[3];
+    out5[2] = (int64_t)v[1];
+    out5[3] = (int64_t)v[2];
+    out5[4] = h->bin_lm_fallback;
+    if (reset) {
+        GH_CHECK(h, hipMemsetAsync(h->d_bin_stats + 5, 0, sizeof(v), h->stream));
+        GH_CHECK(h, hipStreamSynchronize(h->stream));
+        h->bin_lm_fallback = 0;
     }
     return GAMMA_HIP_OK;
 }

@@ -19,6 +19,7 @@
 
 #include <algorithm>
 
+#include "binivf.h"
 #include "device_math.h"
 #include "filter_dev.h"
 #include "flat_rows_dev.h"
@@ -42,8 +43,8 @@ __global__ __launch_bounds__(256) void k_inv_count(const int* __restrict__ probe
     if (l >= 0 && l < nlist && list_len[l] > 0) atomicAdd(&cnt[l], 1);
 }
 // start[l] = exclusive prefix of cnt; cur[l] = 0; ustart[l] = exclusive prefix of the list's work units
-// (query tiles x 128-row chunks), ustart[nlist] = their total.  One block.
-template <int UQ>
+// (query tiles x ROWS-row chunks), ustart[nlist] = their total.  One block.
+template <int UQ, int ROWS = 128>
 __device__ __forceinline__ void inv_scan_body(const int* __restrict__ cnt, const int* __restrict__ list_len, int nlist,
                                               int* __restrict__ start, int* __restrict__ cur, int* __restrict__ ustart) {
     __shared__ int s_w[2][16];
@@ -54,7 +55,7 @@ __device__ __forceinline__ void inv_scan_body(const int* __restrict__ cnt, const
     for (int b = 0; b < nlist; b += 1024) {
         const int i = b + tid;
         const int v = i < nlist ? cnt[i] : 0;
-        const int u = (i < nlist && v > 0) ? ((v + UQ - 1) / UQ) * ((list_len[i] + 127) / 128) : 0;
+        const int u = (i < nlist && v > 0) ? ((v + UQ - 1) / UQ) * ((list_len[i] + ROWS - 1) / ROWS) : 0;
         int incl = v, uincl = u;
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {
@@ -98,6 +99,12 @@ __global__ __launch_bounds__(1024) void k_inv_scan_s(const int* __restrict__ cnt
                                                      int* __restrict__ start, int* __restrict__ cur,
                                                      int* __restrict__ ustart) {
     inv_scan_body<FS_QT>(cnt, list_len, nlist, start, cur, ustart);
+}
+// the same prefix with the binary list-major scan's unit: kBinLmQueryTile queries x kBinSpreadChunk rows (binivf_lm.hip)
+__global__ __launch_bounds__(1024) void k_inv_scan_b(const int* __restrict__ cnt, const int* __restrict__ list_len, int nlist,
+                                                     int* __restrict__ start, int* __restrict__ cur,
+                                                     int* __restrict__ ustart) {
+    inv_scan_body<kBinLmQueryTile, kBinSpreadChunk>(cnt, list_len, nlist, start, cur, ustart);
 }
 __global__ __launch_bounds__(256) void k_inv_fill(const int* __restrict__ probe, int npairs, int nlist,
                                                   const int* __restrict__ list_len, const int* __restrict__ start,

@@ -18,6 +18,18 @@ REGISTER_MODEL(HIPBINARYIVF, GammaBinaryIVFHIPIndex);
     fprintf(stderr, "\n");                         \
   } while (0)
 
+namespace {
+HIPBinaryIVFLmScanFn &LmScan() {
+  static HIPBinaryIVFLmScanFn fn = nullptr;
+  return fn;
+}
+}  // namespace
+int RegisterHIPBinaryIVFLmScan(HIPBinaryIVFLmScanFn fn) {
+  LmScan() = fn;
+  return 1;
+}
+HIPBinaryIVFLmScanFn FindHIPBinaryIVFLmScan() { return LmScan(); }
+
 GammaBinaryIVFHIPIndex::~GammaBinaryIVFHIPIndex() {
   if (h_) gamma_hip_destroy(h_);
 }
@@ -28,6 +40,7 @@ GammaBinaryIVFHIPIndex::~GammaBinaryIVFHIPIndex() {
 int GammaBinaryIVFHIPIndex::Init(const std::string &model_parameters, int indexing_size) {
   indexing_size_ = indexing_size;
   if (!vector_) return -1;
+  HIPBinaryIVFLmScanFn lm_scan = nullptr;
   if (model_parameters != "") {
     utils::JsonParser jp;
     if (jp.Parse(model_parameters.c_str())) return -1;
@@ -37,13 +50,22 @@ int GammaBinaryIVFHIPIndex::Init(const std::string &model_parameters, int indexi
       else if (v != -1) return -1;
     }
     if (!jp.GetInt("device_filters", v)) device_filters_ = v != 0;   // HIP only, see filter_bridge.h
+    // "lm_scan": 0 (the default) | 1: large batches scan list-major, where the build has the switch (HIP only)
+    if (jp.Contains("lm_scan")) {
+      if (!FindHIPBinaryIVFLmScan() || jp.GetInt("lm_scan", v) || (v != 0 && v != 1)) {
+        BLOG("invalid lm_scan (0 or 1, and only where this build of the plugin has the list-major scan)");
+        return -1;
+      }
+      if (v == 1) lm_scan = FindHIPBinaryIVFLmScan();
+    }
   }
   nprobe_ = 20;
   nbits_ = vector_->MetaInfo()->Dimension() * 8;
   const int bucket_keys = std::max(1000, indexing_size_ / nlist_);
   const char *dev = getenv("GAMMA_HIP_DEVICE");
   if (gamma_hip_create(dev ? atoi(dev) : 0, &h_)) return -1;
-  const int rc = gamma_hip_binivf_init(h_, nbits_, nlist_, bucket_keys, 1280000);
+  int rc = gamma_hip_binivf_init(h_, nbits_, nlist_, bucket_keys, 1280000);
+  if (!rc && lm_scan) rc = lm_scan(h_, 1);
   if (rc) {
     BLOG("device init failed: %s (%s)", gamma_hip_strerror(rc), gamma_hip_last_error(h_));
     return -1;

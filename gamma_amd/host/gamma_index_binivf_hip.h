@@ -16,6 +16,12 @@
 
 namespace tig_gamma {
 
+// HIPBINARYIVF's "lm_scan": 1: large batches scan list-major (the handle's switch gamma_hip_binivf_set_lm_scan), registered
+// by gamma_index_binivf_lm_hip.cc -- the only host file that names it.  Without that file Init rejects the key.
+typedef int (*HIPBinaryIVFLmScanFn)(gamma_hip_index *h, int on);
+int RegisterHIPBinaryIVFLmScan(HIPBinaryIVFLmScanFn fn);
+HIPBinaryIVFLmScanFn FindHIPBinaryIVFLmScan();
+
 class HIPBinaryIVFRetrievalParameters : public RetrievalParameters {
  public:
   HIPBinaryIVFRetrievalParameters() : RetrievalParameters(), nprobe_(-1) {}

@@ -711,6 +711,26 @@ int gamma_hip_binivf_scan_shape(int* chunk_rows, int* auto_max_nq);
  * gamma_index_binary_ivf.cc:407-448), queries that ran as mode 0 under mode 1 or -1 for lack of workspace} since the
  * last reset; counted only by searches made while gamma_hip_profile_enable is on */
 int gamma_hip_binivf_scan_stats(gamma_hip_index* h, int64_t* out4, int reset);
+/* The scan of LARGE batches list-major, a switch that is off by default: GammaIVFBinaryScannerL2::
+ * scan_codes (gamma_index_binary_ivf.cc:333-448) answered by the spread chain with its two heavy passes turned around -- a
+ * workgroup keeps a chunk of a LIST in registers and runs every query that probes the list past it.  With on != 0, a call
+ * that the scan mode leaves to mode 0 (see gamma_hip_binivf_set_scan_mode) and that has at least min_nq queries takes this
+ * path; min_nq 0 means the measured default (gamma_hip_binivf_lm_shape), any positive value overrides it.  The answer --
+ * labels, distance bits, the order inside ties, the admissions gamma_hip_binivf_stats counts -- does not change.  A call
+ * whose workspace exceeds half of gamma_hip_set_workspace_budget runs in sub-batches of queries; only when not one query
+ * tile fits does it run as mode 0.  No limit on the number of queries.  It does not add to gamma_hip_binivf_scan_stats.
+ * min_nq < 0, or a handle that is not a binary IVF handle: GAMMA_HIP_EINVAL. */
+int gamma_hip_binivf_set_lm_scan(gamma_hip_index* h, int on, int min_nq);
+/* the switch and min_nq as set (the scan of gamma_index_binary_ivf.cc:333-448 list-major); either pointer may be NULL.  A
+ * handle that is not a binary IVF handle: GAMMA_HIP_EINVAL. */
+int gamma_hip_binivf_lm_scan(const gamma_hip_index* h, int* on, int* min_nq);
+/* the list-major scan's shape (gamma_index_binary_ivf.cc:333-448 is the scan it answers for): *chunk_rows = rows of a list
+ * chunk, *query_tile = queries of a work unit, *auto_min_nq = the min_nq that 0 stands for.  Any pointer may be NULL. */
+int gamma_hip_binivf_lm_shape(int* chunk_rows, int* query_tile, int* auto_min_nq);
+/* {queries the list-major chain answered, its work units (list chunk x query tile), the queries' chunks, their candidates
+ * (rows replayed through scan_codes' heap, gamma_index_binary_ivf.cc:333-448), queries that ran as mode 0 because not one
+ * query tile fitted the workspace} since the last reset; counted only while gamma_hip_profile_enable is on */
+int gamma_hip_binivf_lm_stats(gamma_hip_index* h, int64_t* out5, int reset);
 
 /* ---- exact Hamming (binary flat) search (faiss:IndexBinaryFlat.cpp, utils/hamming.cpp:230-265) ------------------------
  * Every stored code in vid order, and over them the answer GammaIVFBinaryScannerL2::scan_codes
