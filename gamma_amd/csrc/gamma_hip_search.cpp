@@ -892,7 +892,7 @@ int ivfpq_stage_b(H* h, const gamma_hip_search_params* p, int nq, const float* d
 // (kernels.hip k_small_coarse_ip, select.hip k_small_coarse_select / k_small_tail).  Each launch of the regular
 // chain costs ~4 us of launch + drain at this size, whatever it computes.
 bool ivfpq_small_ok(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int nq, int R) {
-    static const bool off = getenv("GAMMA_HIP_NO_SMALL_PATH") != nullptr;
+    const bool off = gh::IvfflatSwitches::get().no_small_path;   // (GAMMA_HIP_NO_SMALL_PATH: read in one place, ivfflat_plan.cpp)
     constexpr int max_nq = 512;   // (the section's header: the measured cross-over with the regular chain is ~1000)
     // exact coarse distances (faiss below 20 queries) come from the fused first kernel, which covers 16 queries; the
     // GEMM form (20 queries and more) from the regular matrix kernel

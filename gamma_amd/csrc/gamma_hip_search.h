@@ -171,6 +171,17 @@ int compact_lists_for_call(H* h, FiltCtx* fc, int64_t est, bool allowed, ListCom
 // vid order): the k-heap IS the result heap, score window and filters are already in the slab (sentinels)
 void flat_tie_args(H* h, gh::TieReplayArgs* tr, bool l2, int nq, int64_t q_stride, int P, int k, const float* d_x, float* cand_dis,
                    int64_t* cand_ids, float* d_distances, int64_t* d_labels, int fixed_n = 0);
+// ---- IVFFLAT, one chunk of the single handle's or a list shard's search (bodies in gamma_hip_search_ivfflat.cpp) ----
+// the scan: workspaces, pair offsets of `probe` under the handle's mask, then the scan ivfflat_scan_plan names into h->w_dist
+// (one counter of gamma_hip_ivfflat_scan_stats / _lm_tail_stats moves).  need_filter: the caller's -- the single handle's has a
+// !h->prefiltered term, the shard's has not.
+int ivfflat_scan_chunk(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int nc, const float* xq, const int* probe,
+                       int64_t q_stride, bool shard, int need_filter);
+// the tail: select, map candidates, flag cut ties, finalize, tie replay.  shard_cut != nullptr (a shard: w_shard_cut + q0) is
+// cleared and gets the narrower flags the merge reads.
+int ivfflat_select_chunk(H* h, const gamma_hip_search_params* p, int nc, int64_t q_stride, int P, int k, const float* xq,
+                         const int* probe, float* out_d, int64_t* out_i, uint8_t* shard_cut /* nullptr: single handle */);
+
 // given != nullptr: the filter context of a combined batch (p's own filter clauses are ignored)
 int ivfpq_search_device_locked(H* h, const gamma_hip_search_params* p, int nq, const float* d_x, int k, float* d_distances,
                                int64_t* d_labels, const FiltCtx* given = nullptr);

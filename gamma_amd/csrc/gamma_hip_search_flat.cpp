@@ -126,7 +126,7 @@ struct FlatCall {
 // small calls: the whole store as ONE row chunk, then the small-batch chains' selection -- three or four launches
 // instead of three per 65536 rows (1 M x 128, one query: 49 launches, 1.1 ms)
 bool FlatCall::small_ok() const {
-    static const bool off = getenv("GAMMA_HIP_NO_SMALL_PATH") != nullptr;
+    const bool off = gh::IvfflatSwitches::get().no_small_path;   // (GAMMA_HIP_NO_SMALL_PATH: read in one place, ivfflat_plan.cpp)
     return !off && h->small_path && nq <= 64 && k_out <= 1024 && N >= 1 && N <= ((int64_t)1 << 22) && !h->profile &&
            (size_t)nq * whole_row_stride() * sizeof(float) <= std::min<size_t>(h->dist_budget_bytes, (size_t)1 << 30);
 }

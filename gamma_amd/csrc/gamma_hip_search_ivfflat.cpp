@@ -6,14 +6,48 @@
 
 namespace ghi {
 
+namespace {
+// the operands of a scan launch, from the handle: nc queries at xq with the assignment `probe`, the pair offsets in w_pair_off /
+// w_pair_base, the slab in w_dist.  (scratch and a masked length table are the list-major caller's to set.)
+gh::IvfflatScanArgs ivfflat_scan_args(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int nc, const float* xq,
+                                      const int* probe, int64_t q_stride, int need_filter) {
+    gh::IvfflatScanArgs a;
+    a.l2 = p->metric == GAMMA_HIP_METRIC_L2;
+    a.x = xq;
+    a.nq = nc;
+    a.d = h->d;
+    a.P = p->nprobe;
+    a.probe = probe;
+    a.pair_off = h->w_pair_off.as<int>();
+    a.pair_base = h->w_pair_base.as<int64_t>();
+    a.list_off = h->d_list_off;
+    a.list_len = h->d_list_len;
+    a.nlist = h->nlist;
+    a.ids = h->d_ids;
+    a.rows = raw_rows_ref(h);
+    a.nraw = h->nraw;
+    if (h->raw_sparse) {
+        a.slot = h->d_raw_slot;
+        a.nslot = h->raw_slot_cap();
+    }
+    a.q_stride = q_stride;
+    a.out = h->w_dist.as<float>();
+    a.ftab = fc.d_tab;
+    a.need_filter = need_filter;
+    a.min_score = p->min_score;
+    a.max_score = p->max_score;
+    return a;
+}
+}  // namespace
+
 // ---- IVFFLAT (index/impl/gamma_index_ivfflat.cc:392-567) ------------------------------------------------------
 // coarse quantizer (the IVFPQ one) -> slab offsets -> exact distance of every entry of the probed lists
 // (k_ivfflat_scan) -> top-k of the slab in (distance, scan position) order -> ids.  The reference's k-heap keeps
 // the same k entries (up to its order inside exact ties).
 // IVFFLAT, small batches: the chain of ivfpq_small without tables and re-rank -- exact coarse distances | top-nprobe +
 // slab offsets | exact distances of the probed lists' rows, one workgroup per pair | top-k + ids + score window
-int ivfflat_small(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, const gh::RowsRef& rows, int nq, const float* d_x,
-                  int k, float* d_distances, int64_t* d_labels) {
+int ivfflat_small(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int nq, const float* d_x, int k, float* d_distances,
+                  int64_t* d_labels) {
     const int P = p->nprobe, d = h->d, nlist = h->nlist;
     const bool l2 = p->metric == GAMMA_HIP_METRIC_L2;
     hipStream_t s = h->stream;
@@ -40,8 +74,7 @@ int ivfflat_small(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, con
                                    h->w_qtotal.as<int>(), h->w_pair_base.as<int64_t>(), nullptr, nullptr, 0, nullptr, nullptr,
                                    nullptr, 0, tie_on(p) ? 1 : 0, h->d_tie_stats);
     const int need_filter = (fc.any_clause || (h->d_bitmap && h->bitmap_any)) ? 1 : 0;
-    gh::launch_ivfflat_scan(s, l2, d_x, nq, d, P, h->w_pair_off.as<int>(), h->w_pair_base.as<int64_t>(), h->d_ids, rows,
-                            h->nraw, q_stride, h->w_dist.as<float>(), fc.d_tab, need_filter, p->min_score, p->max_score);
+    gh::launch_ivfflat_pair(s, ivfflat_scan_args(h, p, fc, nq, d_x, h->w_probe.as<int>(), q_stride, need_filter));
     const int smax = small_presel_slices(h, P, nq);   // long candidate rows: two-level selection, as in ivfpq_small
     if (smax > 0) {
         GH_CHECK(h, h->w_selv.ensure((size_t)nq * smax * k * sizeof(float)));
@@ -68,6 +101,101 @@ int ivfflat_small(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, con
     return GAMMA_HIP_OK;
 }
 
+// One chunk's scan, for the single handle and for a list shard: pair offsets over the lists the handle's mask owns, then the
+// exact distances of their entries into the slab (h->w_dist, rows of q_stride) by the scan the plan names (ivfflat_plan.h).
+int ivfflat_scan_chunk(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int nc, const float* xq, const int* probe,
+                       int64_t q_stride, bool shard, int need_filter) {
+    const int P = p->nprobe, nlist = h->nlist;
+    hipStream_t s = h->stream;
+    GH_CHECK(h, h->w_pair_off.ensure((size_t)nc * (P + 1) * sizeof(int)));
+    GH_CHECK(h, h->w_pair_base.ensure((size_t)nc * P * sizeof(int64_t)));
+    GH_CHECK(h, h->w_qtotal.ensure((size_t)nc * sizeof(int)));
+    GH_CHECK(h, h->w_dist.ensure((size_t)nc * q_stride * sizeof(float)));
+    gh::launch_pair_offsets(s, probe, nc, P, h->d_list_len, h->d_list_mask, nlist, h->w_pair_off.as<int>(), h->w_qtotal.as<int>(),
+                            nullptr, h->d_list_off, h->w_pair_base.as<int64_t>());
+    StageScope t(h, GAMMA_HIP_STAGE_SCAN);
+    gh::IvfflatScanArgs a = ivfflat_scan_args(h, p, fc, nc, xq, probe, q_stride, need_filter);
+    gh::IvfflatScanShape sh;
+    sh.nc = nc;
+    sh.P = P;
+    sh.nlist = nlist;
+    sh.d = h->d;
+    sh.et = a.rows.et;
+    sh.shard = shard;
+    sh.masked = h->d_list_mask != nullptr;
+    sh.sparse = h->raw_sparse;
+    sh.sparse_empty = h->raw_sparse && !h->d_raw_slot;
+    sh.lm_tails = h->ivfflat_lm_tails;
+    const gh::IvfflatScanPlan pl = gh::ivfflat_scan_plan(sh, gh::IvfflatSwitches::get());
+    switch (pl.kind) {
+        case gh::IvfflatScanPlan::FILL: {   // a sparse store that never took a row: every entry is a filtered entry
+            const int64_t n = (int64_t)nc * q_stride;
+            for (int64_t o = 0; o < n; o += 1 << 30)
+                gh::launch_fill_f32(s, a.out + o, (int)std::min<int64_t>(n - o, 1 << 30), a.l2 ? INFINITY : -INFINITY);
+            return GAMMA_HIP_OK;
+        }
+        case gh::IvfflatScanPlan::PAIR:
+            h->fl_pair.fetch_add(1, std::memory_order_relaxed);
+            gh::launch_ivfflat_pair(s, a);
+            return GAMMA_HIP_OK;
+        case gh::IvfflatScanPlan::LM_FIXED: h->fl_lm.fetch_add(1, std::memory_order_relaxed); break;
+        case gh::IvfflatScanPlan::LM_SLICED: h->fl_lms.fetch_add(1, std::memory_order_relaxed); break;
+        case gh::IvfflatScanPlan::LM_TAIL: h->fl_lmt.fetch_add(1, std::memory_order_relaxed); break;
+    }
+    GH_CHECK(h, h->w_lm_units.ensure(pl.scratch_bytes));
+    a.scratch = h->w_lm_units.p;
+    if (pl.masked_len) {
+        int* mlen = reinterpret_cast<int*>(static_cast<char*>(h->w_lm_units.p) + pl.mlen_off);
+        gh::launch_masked_list_len(s, h->d_list_len, h->d_list_mask, nlist, mlen);
+        a.list_len = mlen;
+    }
+    gh::launch_ivfflat_lm(s, pl.kind, a);
+    return GAMMA_HIP_OK;
+}
+
+// One chunk's tail, for both: top-k of the slab, candidates to ids, the k results; with exact ties the queries with equal
+// distances at the k cut or among the k selected are flagged and replayed through the scanner's heap (ties.hip).
+// shard_cut != nullptr (a list shard, [nc]): what the merge needs is narrower than the local flags -- did the k cut go through a
+// group of equal distances? -- and is kept per query of the WHOLE call, whatever the chunking (gamma_hip_ivfpq_shard_cut_flags)
+int ivfflat_select_chunk(H* h, const gamma_hip_search_params* p, int nc, int64_t q_stride, int P, int k, const float* xq,
+                         const int* probe, float* out_d, int64_t* out_i, uint8_t* shard_cut) {
+    const bool l2 = p->metric == GAMMA_HIP_METRIC_L2;
+    hipStream_t s = h->stream;
+    StageScope t(h, GAMMA_HIP_STAGE_SELECT);
+    gh::launch_select_topk(s, l2, h->w_dist.as<float>(), q_stride, h->w_qtotal.as<int>(), 0, (int)std::min<int64_t>(q_stride, 1 << 30),
+                           nc, k, h->w_cand_dis.as<float>(), h->w_cand_pos.as<int>());
+    gh::launch_map_candidates(s, h->w_cand_pos.as<int>(), nc, k, P, probe, h->w_pair_off.as<int>(), h->d_list_off, h->d_ids,
+                              h->w_cand_ids.as<int64_t>());
+    const bool ties = tie_on(p);
+    gh::TieFlags tf;
+    if (ties) {
+        GH_CHECK(h, h->w_tcut.ensure((size_t)nc));
+        GH_CHECK(h, h->w_tlist.ensure(((size_t)nc + 1) * sizeof(int)));
+        GH_CHECK(h, hipMemsetAsync(h->w_tlist.p, 0, sizeof(int), s));
+        GH_CHECK(h, hipMemsetAsync(h->w_tcut.p, 0, (size_t)nc, s));
+        if (shard_cut) GH_CHECK(h, hipMemsetAsync(shard_cut, 0, (size_t)nc, s));
+        gh::launch_flag_cut_ties(s, h->w_dist.as<float>(), q_stride, h->w_qtotal.as<int>(), nc, k, h->w_cand_dis.as<float>(),
+                                 h->w_cand_pos.as<int>(), h->w_tcut.as<uint8_t>(), 0, 1);
+        if (shard_cut)
+            gh::launch_flag_cut_ties(s, h->w_dist.as<float>(), q_stride, h->w_qtotal.as<int>(), nc, k, h->w_cand_dis.as<float>(),
+                                     h->w_cand_pos.as<int>(), shard_cut, 0, 0);
+        tf.cut = h->w_tcut.as<uint8_t>();
+        tf.count = h->w_tlist.as<int>();
+        tf.list = h->w_tlist.as<int>() + 1;
+        tf.stats = h->d_tie_stats;
+    }
+    gh::launch_finalize_norank(s, h->w_cand_dis.as<float>(), h->w_cand_ids.as<int64_t>(), nc, k, k, p->min_score, p->max_score,
+                               neutral_of(l2), out_d, out_i, ties ? &tf : nullptr);
+    if (ties) {
+        gh::TieReplayArgs tr;
+        flat_tie_args(h, &tr, l2, nc, q_stride, P, k, xq, h->w_cand_dis.as<float>(), h->w_cand_ids.as<int64_t>(), out_d, out_i);
+        tr.list = tf.list;
+        tr.count = tf.count;
+        gh::launch_tie_replay(s, l2, tr);
+    }
+    return GAMMA_HIP_OK;
+}
+
 int ivfflat_search_device_locked(H* h, const gamma_hip_search_params* p, int nq, const float* d_x, int k,
                                  float* d_distances, int64_t* d_labels) {
     if (h->raw_sparse) return fail(h, GAMMA_HIP_EUNSUPPORTED, "the raw store holds this shard's rows only (gamma_hip_raw_put)");
@@ -83,11 +211,7 @@ int ivfflat_search_device_locked(H* h, const gamma_hip_search_params* p, int nq,
     if (p->nprobe <= 0 || p->nprobe > h->nlist) return fail(h, GAMMA_HIP_EINVAL, "nprobe out of range");
     if (!h->has_raw_rows() || h->raw_d != h->d) return fail(h, GAMMA_HIP_EINVAL, "ivfflat needs the raw store");
     if (k <= 0 || nq == 0) return GAMMA_HIP_OK;
-    // the store's rows as the scan takes them: pointer + element type (fp32 rows: the launches they always were)
-    const gh::RowsRef rows = raw_rows_ref(h);
     GH_CHECK(h, hipSetDevice(h->device));
-    const bool l2 = p->metric == GAMMA_HIP_METRIC_L2;
-    const float neutral = neutral_of(l2);
     gh::FilterDesc filt;
     GH_TRY(build_filter(h, p, &filt, nullptr, (int64_t)nq * p->nprobe * (h->ntotal / std::max(1, h->nlist))));
     FiltCtx fc;
@@ -96,14 +220,12 @@ int ivfflat_search_device_locked(H* h, const gamma_hip_search_params* p, int nq,
     if (pp.coarse_mode == 1 && blas_form_not_restated(nq, h->nlist, h->d)) h->blas_unrestated++;
     const int P = pp.nprobe, nlist = h->nlist;
     hipStream_t s = h->stream;
-    {   // small batches, as long as the pair-per-workgroup scan is the one that would run anyway (below 2 nlist pairs)
-        static const bool off = getenv("GAMMA_HIP_NO_SMALL_PATH") != nullptr;
-        if (!off && h->small_path && nq <= 512 && P <= 128 && k <= 1024 && !h->profile &&
-            !fc.d_qf && !h->d_list_mask && nlist <= 16384 && (int64_t)nq * P < 2 * (int64_t)nlist &&
-            (int64_t)P * std::max(1, h->max_list_len) <= (1 << 22)) {
-            h->fl_small.fetch_add(1, std::memory_order_relaxed);
-            return ivfflat_small(h, &pp, fc, rows, nq, d_x, k, d_distances, d_labels);
-        }
+    // small batches, as long as the pair-per-workgroup scan is the one that would run anyway (pairs that share no lists)
+    if (!gh::IvfflatSwitches::get().no_small_path && h->small_path && nq <= 512 && P <= 128 && k <= 1024 && !h->profile &&
+        !fc.d_qf && !h->d_list_mask && nlist <= 16384 && !gh::ivfflat_pairs_share_lists(nq, P, nlist) &&
+        (int64_t)P * std::max(1, h->max_list_len) <= (1 << 22)) {
+        h->fl_small.fetch_add(1, std::memory_order_relaxed);
+        return ivfflat_small(h, &pp, fc, nq, d_x, k, d_distances, d_labels);
     }
     ListCompaction restore(h);
     GH_TRY(compact_lists_for_call(h, &fc, (int64_t)nq * P * (h->ntotal / std::max(1, nlist)), true, &restore));
@@ -114,83 +236,14 @@ int ivfflat_search_device_locked(H* h, const gamma_hip_search_params* p, int nq,
         const float* xq = d_x + (size_t)q0 * h->d;
         const int ver = h->cur_ver;
         GH_CHECK(h, hipStreamWaitEvent(s, h->ver_ev[ver], 0));
-        GH_CHECK(h, h->w_pair_off.ensure((size_t)nc * (P + 1) * sizeof(int)));
-        GH_CHECK(h, h->w_pair_base.ensure((size_t)nc * P * sizeof(int64_t)));
-        GH_CHECK(h, h->w_qtotal.ensure((size_t)nc * sizeof(int)));
         GH_CHECK(h, h->w_cand_pos.ensure((size_t)nc * k * sizeof(int)));
         GH_CHECK(h, h->w_cand_dis.ensure((size_t)nc * k * sizeof(float)));
         GH_CHECK(h, h->w_cand_ids.ensure((size_t)nc * k * sizeof(int64_t)));
         GH_TRY(ivfpq_coarse(h, &pp, nc, xq));
-        gh::launch_pair_offsets(s, h->w_probe.as<int>(), nc, P, h->d_list_len, h->d_list_mask, nlist,
-                                h->w_pair_off.as<int>(), h->w_qtotal.as<int>(), nullptr, h->d_list_off,
-                                h->w_pair_base.as<int64_t>());
         const int64_t q_stride = slab_q_stride(h, P);
-        GH_CHECK(h, h->w_dist.ensure((size_t)nc * q_stride * sizeof(float)));
-        {
-            StageScope t(h, GAMMA_HIP_STAGE_SCAN);
-            // enough (query, probe) pairs that lists are shared: list-major (ivfflat.hip), a list's rows are read once
-            // for all the queries probing it (d in {16, 32, 64, 96, 128}) or once per tile of them (the row-sliced kernel: every
-            // other d % 16 == 0 up to 4096); else one workgroup per pair
-            static const bool no_lm = getenv("GAMMA_HIP_NO_IVFFLAT_LM") != nullptr;
-            int lm_kind = 0, lm_slab = 0, lm_qtile = 0;
-            gh::ivfflat_lm_shape(h->d, &lm_kind, &lm_slab, &lm_qtile);
-            // d % 16 != 0 behind gamma_hip_set_ivfflat_lm_tails: the row-sliced kernel with the scanner's tail steps, under the
-            // same gates (an sq8 store has no such kernel and keeps the pair kernel)
-            int lt_kind = 0, lt_load = 0, lt_qtile = 0;
-            if (h->ivfflat_lm_tails && rows.et <= 3) gh::ivfflat_lm_tail_shape(h->d, (int)rows.esz(), &lt_kind, &lt_load, &lt_qtile);
-            if (!no_lm && lt_kind == 3 && (int64_t)nc * P >= 2 * (int64_t)nlist && !h->d_list_mask) {
-                h->fl_lmt.fetch_add(1, std::memory_order_relaxed);
-                GH_CHECK(h, h->w_lm_units.ensure(gh::ivfflat_lm_scratch_bytes(nc, P, nlist)));
-                gh::launch_ivfflat_lm_tail(s, l2, xq, nc, h->d, P, h->w_probe.as<int>(), h->w_pair_off.as<int>(), h->d_list_off,
-                                           h->d_list_len, nlist, h->d_ids, rows, h->nraw, q_stride, h->w_dist.as<float>(),
-                                           fc.d_tab, need_filter, p->min_score, p->max_score, h->w_lm_units.p);
-            } else if (!no_lm && lm_kind != 0 && (int64_t)nc * P >= 2 * (int64_t)nlist && !h->d_list_mask) {
-                (lm_kind == 1 ? h->fl_lm : h->fl_lms).fetch_add(1, std::memory_order_relaxed);
-                GH_CHECK(h, h->w_lm_units.ensure(gh::ivfflat_lm_scratch_bytes(nc, P, nlist)));
-                gh::launch_ivfflat_lm(s, l2, xq, nc, h->d, P, h->w_probe.as<int>(), h->w_pair_off.as<int>(), h->d_list_off,
-                                      h->d_list_len, nlist, h->d_ids, rows, h->nraw, q_stride, h->w_dist.as<float>(),
-                                      fc.d_tab, need_filter, p->min_score, p->max_score, h->w_lm_units.p);
-            } else {
-                h->fl_pair.fetch_add(1, std::memory_order_relaxed);
-                gh::launch_ivfflat_scan(s, l2, xq, nc, h->d, P, h->w_pair_off.as<int>(), h->w_pair_base.as<int64_t>(),
-                                        h->d_ids, rows, h->nraw, q_stride, h->w_dist.as<float>(), fc.d_tab, need_filter,
-                                        p->min_score, p->max_score);
-            }
-        }
-        {
-            StageScope t(h, GAMMA_HIP_STAGE_SELECT);
-            gh::launch_select_topk(s, l2, h->w_dist.as<float>(), q_stride, h->w_qtotal.as<int>(), 0,
-                                   (int)std::min<int64_t>(q_stride, 1 << 30), nc, k, h->w_cand_dis.as<float>(),
-                                   h->w_cand_pos.as<int>());
-            gh::launch_map_candidates(s, h->w_cand_pos.as<int>(), nc, k, P, h->w_probe.as<int>(), h->w_pair_off.as<int>(),
-                                      h->d_list_off, h->d_ids, h->w_cand_ids.as<int64_t>());
-            const bool ties = tie_on(p);
-            gh::TieFlags tf;
-            if (ties) {
-                // equal distances at the k cut or among the k selected: the scanner's heap decides (ties.hip)
-                GH_CHECK(h, h->w_tcut.ensure((size_t)nc));
-                GH_CHECK(h, h->w_tlist.ensure(((size_t)nc + 1) * sizeof(int)));
-                GH_CHECK(h, hipMemsetAsync(h->w_tlist.p, 0, sizeof(int), s));
-                GH_CHECK(h, hipMemsetAsync(h->w_tcut.p, 0, (size_t)nc, s));
-                gh::launch_flag_cut_ties(s, h->w_dist.as<float>(), q_stride, h->w_qtotal.as<int>(), nc, k, h->w_cand_dis.as<float>(),
-                                         h->w_cand_pos.as<int>(), h->w_tcut.as<uint8_t>(), 0, 1);
-                tf.cut = h->w_tcut.as<uint8_t>();
-                tf.count = h->w_tlist.as<int>();
-                tf.list = h->w_tlist.as<int>() + 1;
-                tf.stats = h->d_tie_stats;
-            }
-            gh::launch_finalize_norank(s, h->w_cand_dis.as<float>(), h->w_cand_ids.as<int64_t>(), nc, k, k, p->min_score,
-                                       p->max_score, neutral, d_distances + (size_t)q0 * k, d_labels + (size_t)q0 * k,
-                                       ties ? &tf : nullptr);
-            if (ties) {
-                gh::TieReplayArgs tr;
-                flat_tie_args(h, &tr, l2, nc, q_stride, P, k, xq, h->w_cand_dis.as<float>(), h->w_cand_ids.as<int64_t>(),
-                              d_distances + (size_t)q0 * k, d_labels + (size_t)q0 * k);
-                tr.list = tf.list;
-                tr.count = tf.count;
-                gh::launch_tie_replay(s, l2, tr);
-            }
-        }
+        GH_TRY(ivfflat_scan_chunk(h, p, fc, nc, xq, h->w_probe.as<int>(), q_stride, false, need_filter));
+        GH_TRY(ivfflat_select_chunk(h, p, nc, q_stride, P, k, xq, h->w_probe.as<int>(), d_distances + (size_t)q0 * k,
+                                    d_labels + (size_t)q0 * k, nullptr));
         GH_CHECK(h, hipEventRecord(h->rd_ev[ver], s));
         h->rd_set[ver] = true;
         h->last_nq = nc;

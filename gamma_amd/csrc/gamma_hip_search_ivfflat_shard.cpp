@@ -22,65 +22,6 @@ int ivfflat_shard_check(H* h, const gamma_hip_search_params* p, int nq, int k, c
     return GAMMA_HIP_OK;
 }
 
-// One chunk's scan: pair offsets over the lists this handle's mask owns, then the exact distances of their entries into the
-// slab (h->w_dist, rows of q_stride).  List-major when enough pairs share lists -- under a mask too: the kernels get a
-// list-length table in which an unowned list is empty -- else one workgroup per pair.  A sparse store goes through the sparse
-// variant of the same three kernels.
-int ivfflat_shard_scan(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int nc, const float* xq, const int* probe,
-                       int64_t q_stride) {
-    const int P = p->nprobe, nlist = h->nlist;
-    const bool l2 = p->metric == GAMMA_HIP_METRIC_L2;
-    hipStream_t s = h->stream;
-    GH_CHECK(h, h->w_pair_off.ensure((size_t)nc * (P + 1) * sizeof(int)));
-    GH_CHECK(h, h->w_pair_base.ensure((size_t)nc * P * sizeof(int64_t)));
-    GH_CHECK(h, h->w_qtotal.ensure((size_t)nc * sizeof(int)));
-    GH_CHECK(h, h->w_dist.ensure((size_t)nc * q_stride * sizeof(float)));
-    gh::launch_pair_offsets(s, probe, nc, P, h->d_list_len, h->d_list_mask, nlist, h->w_pair_off.as<int>(), h->w_qtotal.as<int>(),
-                            nullptr, h->d_list_off, h->w_pair_base.as<int64_t>());
-    const int need_filter = (fc.any_clause || (h->d_bitmap && h->bitmap_any)) ? 1 : 0;
-    // the store's rows as the scans take them: pointer + element type (fp32 rows: the launches they always were)
-    const gh::RowsRef rows = raw_rows_ref(h);
-    StageScope t(h, GAMMA_HIP_STAGE_SCAN);
-    if (h->raw_sparse && !h->d_raw_slot) {   // a sparse store that never took a row: every entry is a filtered entry
-        const int64_t n = (int64_t)nc * q_stride;
-        for (int64_t o = 0; o < n; o += 1 << 30)
-            gh::launch_fill_f32(s, h->w_dist.as<float>() + o, (int)std::min<int64_t>(n - o, 1 << 30), l2 ? INFINITY : -INFINITY);
-        return GAMMA_HIP_OK;
-    }
-    static const bool no_lm = getenv("GAMMA_HIP_NO_IVFFLAT_LM") != nullptr;
-    int lm_kind = 0, lm_slab = 0, lm_qtile = 0;
-    gh::ivfflat_lm_shape(h->d, &lm_kind, &lm_slab, &lm_qtile);
-    if (!no_lm && lm_kind != 0 && (int64_t)nc * P >= 2 * (int64_t)nlist) {
-        (lm_kind == 1 ? h->fl_lm : h->fl_lms).fetch_add(1, std::memory_order_relaxed);
-        const size_t sb = (gh::ivfflat_lm_scratch_bytes(nc, P, nlist) + 15) & ~(size_t)15;
-        GH_CHECK(h, h->w_lm_units.ensure(sb + (size_t)nlist * sizeof(int)));
-        const int* len = h->d_list_len;
-        if (h->d_list_mask) {
-            int* mlen = reinterpret_cast<int*>(static_cast<char*>(h->w_lm_units.p) + sb);
-            gh::launch_masked_list_len(s, h->d_list_len, h->d_list_mask, nlist, mlen);
-            len = mlen;
-        }
-        if (h->raw_sparse)
-            gh::launch_ivfflat_lm_sparse(s, l2, xq, nc, h->d, P, probe, h->w_pair_off.as<int>(), h->d_list_off, len, nlist, h->d_ids,
-                                         rows, h->nraw, h->d_raw_slot, h->raw_slot_cap(), q_stride, h->w_dist.as<float>(), fc.d_tab,
-                                         need_filter, p->min_score, p->max_score, h->w_lm_units.p);
-        else
-            gh::launch_ivfflat_lm(s, l2, xq, nc, h->d, P, probe, h->w_pair_off.as<int>(), h->d_list_off, len, nlist, h->d_ids,
-                                  rows, h->nraw, q_stride, h->w_dist.as<float>(), fc.d_tab, need_filter, p->min_score,
-                                  p->max_score, h->w_lm_units.p);
-    } else {
-        h->fl_pair.fetch_add(1, std::memory_order_relaxed);
-        if (h->raw_sparse)
-            gh::launch_ivfflat_scan_sparse(s, l2, xq, nc, h->d, P, h->w_pair_off.as<int>(), h->w_pair_base.as<int64_t>(), h->d_ids,
-                                           rows, h->nraw, h->d_raw_slot, h->raw_slot_cap(), q_stride, h->w_dist.as<float>(),
-                                           fc.d_tab, need_filter, p->min_score, p->max_score);
-        else
-            gh::launch_ivfflat_scan(s, l2, xq, nc, h->d, P, h->w_pair_off.as<int>(), h->w_pair_base.as<int64_t>(), h->d_ids, rows,
-                                    h->nraw, q_stride, h->w_dist.as<float>(), fc.d_tab, need_filter, p->min_score, p->max_score);
-    }
-    return GAMMA_HIP_OK;
-}
-
 }  // namespace
 }  // namespace ghi
 
@@ -126,8 +67,6 @@ int gamma_hip_ivfflat_search_shard(gamma_hip_index* h, const gamma_hip_search_pa
     (void)d_coarse_dis;   // (the IVFFLAT scan takes nothing from the coarse distances; the argument keeps the IVFPQ entry's shape)
     if (!d_x || !d_probe || !d_dis || !d_ids) return fail(h, GAMMA_HIP_EINVAL, "null buffer");
     GH_CHECK(h, hipSetDevice(h->device));
-    const bool l2 = p->metric == GAMMA_HIP_METRIC_L2;
-    const float neutral = neutral_of(l2);
     const int P = p->nprobe;
     gh::FilterDesc filt;
     GH_TRY(build_filter(h, p, &filt, nullptr, (int64_t)nq * P * (h->ntotal / std::max(1, h->nlist))));
@@ -135,6 +74,7 @@ int gamma_hip_ivfflat_search_shard(gamma_hip_index* h, const gamma_hip_search_pa
     GH_TRY(filt_ctx_single(h, filt, &fc));
     hipStream_t s = h->stream;
     const bool ties = tie_on(p);
+    const int need_filter = (fc.any_clause || (h->d_bitmap && h->bitmap_any)) ? 1 : 0;
     const int chunk = scan_chunk(h, nq, P);
     const int64_t q_stride = slab_q_stride(h, P);
     if (ties) GH_CHECK(h, h->w_shard_cut.ensure(std::max<size_t>((size_t)nq, 16)));
@@ -142,50 +82,14 @@ int gamma_hip_ivfflat_search_shard(gamma_hip_index* h, const gamma_hip_search_pa
         const int nc = std::min(chunk, nq - q0);
         const float* xq = d_x + (size_t)q0 * h->d;
         const int* probe = d_probe + (size_t)q0 * P;
-        float* out_d = d_dis + (size_t)q0 * k;
-        int64_t* out_i = d_ids + (size_t)q0 * k;
         const int ver = h->cur_ver;
         GH_CHECK(h, hipStreamWaitEvent(s, h->ver_ev[ver], 0));
         GH_CHECK(h, h->w_cand_pos.ensure((size_t)nc * k * sizeof(int)));
         GH_CHECK(h, h->w_cand_dis.ensure((size_t)nc * k * sizeof(float)));
         GH_CHECK(h, h->w_cand_ids.ensure((size_t)nc * k * sizeof(int64_t)));
-        GH_TRY(ivfflat_shard_scan(h, p, fc, nc, xq, probe, q_stride));
-        {
-            StageScope t(h, GAMMA_HIP_STAGE_SELECT);
-            gh::launch_select_topk(s, l2, h->w_dist.as<float>(), q_stride, h->w_qtotal.as<int>(), 0,
-                                   (int)std::min<int64_t>(q_stride, 1 << 30), nc, k, h->w_cand_dis.as<float>(),
-                                   h->w_cand_pos.as<int>());
-            gh::launch_map_candidates(s, h->w_cand_pos.as<int>(), nc, k, P, probe, h->w_pair_off.as<int>(), h->d_list_off, h->d_ids,
-                                      h->w_cand_ids.as<int64_t>());
-            gh::TieFlags tf;
-            if (ties) {
-                // the shard's own result honours its local ties (flag + replay, as the single-handle search); what the merge
-                // needs is narrower -- did the k cut go through a group of equal distances? -- and is kept per query of the
-                // WHOLE call, whatever the chunking (gamma_hip_ivfpq_shard_cut_flags reads it)
-                GH_CHECK(h, h->w_tcut.ensure((size_t)nc));
-                GH_CHECK(h, h->w_tlist.ensure(((size_t)nc + 1) * sizeof(int)));
-                GH_CHECK(h, hipMemsetAsync(h->w_tlist.p, 0, sizeof(int), s));
-                GH_CHECK(h, hipMemsetAsync(h->w_tcut.p, 0, (size_t)nc, s));
-                GH_CHECK(h, hipMemsetAsync(h->w_shard_cut.as<uint8_t>() + q0, 0, (size_t)nc, s));
-                gh::launch_flag_cut_ties(s, h->w_dist.as<float>(), q_stride, h->w_qtotal.as<int>(), nc, k, h->w_cand_dis.as<float>(),
-                                         h->w_cand_pos.as<int>(), h->w_tcut.as<uint8_t>(), 0, 1);
-                gh::launch_flag_cut_ties(s, h->w_dist.as<float>(), q_stride, h->w_qtotal.as<int>(), nc, k, h->w_cand_dis.as<float>(),
-                                         h->w_cand_pos.as<int>(), h->w_shard_cut.as<uint8_t>() + q0, 0, 0);
-                tf.cut = h->w_tcut.as<uint8_t>();
-                tf.count = h->w_tlist.as<int>();
-                tf.list = h->w_tlist.as<int>() + 1;
-                tf.stats = h->d_tie_stats;
-            }
-            gh::launch_finalize_norank(s, h->w_cand_dis.as<float>(), h->w_cand_ids.as<int64_t>(), nc, k, k, p->min_score, p->max_score,
-                                       neutral, out_d, out_i, ties ? &tf : nullptr);
-            if (ties) {
-                gh::TieReplayArgs tr;
-                flat_tie_args(h, &tr, l2, nc, q_stride, P, k, xq, h->w_cand_dis.as<float>(), h->w_cand_ids.as<int64_t>(), out_d, out_i);
-                tr.list = tf.list;
-                tr.count = tf.count;
-                gh::launch_tie_replay(s, l2, tr);
-            }
-        }
+        GH_TRY(ivfflat_scan_chunk(h, p, fc, nc, xq, probe, q_stride, true, need_filter));
+        GH_TRY(ivfflat_select_chunk(h, p, nc, q_stride, P, k, xq, probe, d_dis + (size_t)q0 * k, d_ids + (size_t)q0 * k,
+                                    ties ? h->w_shard_cut.as<uint8_t>() + q0 : nullptr));
         GH_CHECK(h, hipEventRecord(h->rd_ev[ver], s));
         h->rd_set[ver] = true;
         h->last_nq = nc;
@@ -239,13 +143,14 @@ int gamma_hip_ivfflat_shard_export(gamma_hip_index* h, const gamma_hip_search_pa
     FiltCtx fc;
     GH_TRY(filt_ctx_single(h, filt, &fc));
     hipStream_t s = h->stream;
+    const int need_filter = (fc.any_clause || (h->d_bitmap && h->bitmap_any)) ? 1 : 0;
     const int chunk = scan_chunk(h, nf, P);
     const int64_t q_stride = slab_q_stride(h, P);
     for (int f0 = 0; f0 < nf; f0 += chunk) {
         const int nc = std::min(chunk, nf - f0);
         const int ver = h->cur_ver;
         GH_CHECK(h, hipStreamWaitEvent(s, h->ver_ev[ver], 0));
-        GH_TRY(ivfflat_shard_scan(h, p, fc, nc, d_xf + (size_t)f0 * h->d, d_probe_f + (size_t)f0 * P, q_stride));
+        GH_TRY(ivfflat_scan_chunk(h, p, fc, nc, d_xf + (size_t)f0 * h->d, d_probe_f + (size_t)f0 * P, q_stride, true, need_filter));
         gh::launch_shard_export(s, d_probe_f + (size_t)f0 * P, nc, P, h->d_list_len, h->d_list_off, h->d_list_mask, h->nlist, h->d_ids,
                                 h->w_dist.as<float>(), q_stride, stride, d_vals + (size_t)f0 * stride, d_ids + (size_t)f0 * stride,
                                 d_off + (size_t)f0 * (P + 1));

@@ -23,16 +23,14 @@
 #include "device_math.h"
 #include "filter_dev.h"
 #include "flat_rows_dev.h"
+#include "ivfflat_plan.h"   // FL_QT, FS_QT, FS_SLAB
 #include "kernels.h"
 
 namespace gh {
 
 namespace {
-constexpr int FL_QT = 32;   // queries per LDS tile
 constexpr int FL_UT = 1;    // tiles per work unit (4: no gain at 16384 queries, -12 % at 4096: fewer, longer units)
 constexpr int FL_UQ = FL_QT * FL_UT;
-constexpr int FS_QT = 16;      // row-sliced kernel: queries per LDS tile = per work unit (their partial sums stay in registers)
-constexpr int FS_SLAB = 128;   // row-sliced kernel: elements of a row a pair of threads holds at a time
 }  // namespace
 
 __global__ __launch_bounds__(256) void k_inv_count(const int* __restrict__ probe, int npairs, int nlist,
@@ -673,73 +671,61 @@ void launch_masked_list_len(hipStream_t s, const int* list_len, const uint8_t* m
     if (nlist > 0) hipLaunchKernelGGL(k_masked_list_len, dim3((nlist + 255) / 256), dim3(256), 0, s, list_len, mask, nlist, out);
 }
 
-bool ivfflat_lm_supported(int d) { return d == 16 || d == 32 || d == 64 || d == 96 || d == 128; }
-
-int ivfflat_lm_shape(int d, int* kind, int* slab, int* qtile) {
-    const int k = ivfflat_lm_supported(d) ? 1 : (d >= 16 && d <= 4096 && d % 16 == 0) ? 2 : 0;
-    *kind = k;
-    *slab = k == 1 ? d : k == 2 ? FS_SLAB : 0;
-    *qtile = k == 1 ? FL_QT : k == 2 ? FS_QT : 0;
-    return k;
-}
-
-int ivfflat_lm_tail_shape(int d, int elem_bytes, int* kind, int* load_bytes, int* qtile) {
-    const int k = (d >= 1 && d <= 4096 && d % 16 != 0) ? 3 : 0;
-    int lb = 16;   // gcd(16, d * elem_bytes)
-    while (lb > 1 && ((int64_t)d * elem_bytes) % lb != 0) lb >>= 1;
-    *kind = k;
-    *load_bytes = lb;
-    *qtile = FS_QT;
-    return k;
-}
-
-// scratch: inv [nq * P] ints, then cnt | start | cur [nlist] ints each
-size_t ivfflat_lm_scratch_bytes(int nq, int P, int nlist) { return ((size_t)nq * P + 4 * (size_t)nlist + 1) * sizeof(int); }
-
 namespace {
+// The inverse index of a list-major launch, carved from a.scratch (ivfflat_lm_scratch_bytes): inv [nq * P] the pairs sorted by
+// list, then cnt | start | cur [nlist], ustart [nlist + 1] the lists' work units.  sliced: units of FS_QT queries (the
+// row-sliced kernels), else of FL_UQ.
+struct LmIndex {
+    const int *start, *cnt, *inv, *ustart;
+};
+LmIndex lm_inverse_index(hipStream_t s, const IvfflatScanArgs& a, bool sliced) {
+    int* inv = static_cast<int*>(a.scratch);
+    int* cnt = inv + (size_t)a.nq * a.P;
+    int* start = cnt + a.nlist;
+    int* cur = start + a.nlist;
+    int* ustart = cur + a.nlist;
+    const int npairs = a.nq * a.P;
+    (void)hipMemsetAsync(cnt, 0, (size_t)a.nlist * sizeof(int), s);
+    hipLaunchKernelGGL(k_inv_count, dim3((npairs + 255) / 256), dim3(256), 0, s, a.probe, npairs, a.nlist, a.list_len, cnt);
+    if (sliced) hipLaunchKernelGGL(k_inv_scan_s, dim3(1), dim3(1024), 0, s, cnt, a.list_len, a.nlist, start, cur, ustart);
+    else hipLaunchKernelGGL(k_inv_scan, dim3(1), dim3(1024), 0, s, cnt, a.list_len, a.nlist, start, cur, ustart);
+    hipLaunchKernelGGL(k_inv_fill, dim3((npairs + 255) / 256), dim3(256), 0, s, a.probe, npairs, a.nlist, a.list_len, start, cur, inv);
+    return LmIndex{start, cnt, inv, ustart};
+}
+
+constexpr int LM_GRID = 256 * 8;   // persistent: every workgroup walks the unit list with stride gridDim.x
+
+// what every list-major kernel takes behind its leading (x[, d], P) and in front of its trailing tab or (slot, nslot)
+#define GH_LM_ARGS                                                                                                               \
+    a.pair_off, a.list_off, a.list_len, a.ids, raw, a.nraw, ix.start, ix.cnt, ix.inv, ix.ustart, a.nlist, a.q_stride, a.out, a.ftab, \
+        a.need_filter, a.min_score, a.max_score
+
+// LM_FIXED (d in {16, 32, 64, 96, 128}) and LM_SLICED, dense or -- a.slot -- sparse
 template <class Row>
-void launch_ivfflat_lm_t(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* probe, const int* pair_off,
-                         const int64_t* list_off, const int* list_len, int nlist, const int64_t* ids, const Row* raw,
-                         int64_t nraw, int64_t q_stride, float* out, const FilterDesc* ftab, int need_filter, float min_score,
-                         float max_score, void* scratch, RowTab<Row> tab = RowTab<Row>{}, const int32_t* slot = nullptr,
-                         int64_t nslot = 0) {
-    if (nq <= 0 || P <= 0) return;
-    int* inv = static_cast<int*>(scratch);
-    int* cnt = inv + (size_t)nq * P;
-    int* start = cnt + nlist;
-    int* cur = start + nlist;
-    int* ustart = cur + nlist;
-    const int npairs = nq * P;
-    (void)hipMemsetAsync(cnt, 0, (size_t)nlist * sizeof(int), s);
-    hipLaunchKernelGGL(k_inv_count, dim3((npairs + 255) / 256), dim3(256), 0, s, probe, npairs, nlist, list_len, cnt);
-    const bool sliced = !ivfflat_lm_supported(d);   // (the caller asked ivfflat_lm_shape: d % 16 == 0, d <= 4096)
-    if (sliced) hipLaunchKernelGGL(k_inv_scan_s, dim3(1), dim3(1024), 0, s, cnt, list_len, nlist, start, cur, ustart);
-    else hipLaunchKernelGGL(k_inv_scan, dim3(1), dim3(1024), 0, s, cnt, list_len, nlist, start, cur, ustart);
-    hipLaunchKernelGGL(k_inv_fill, dim3((npairs + 255) / 256), dim3(256), 0, s, probe, npairs, nlist, list_len, start, cur, inv);
-    const int grid = 256 * 8;   // persistent: every workgroup walks the unit list with stride gridDim.x
+void launch_lm_t(hipStream_t s, const IvfflatScanArgs& a, bool sliced) {
+    const LmIndex ix = lm_inverse_index(s, a, sliced);
+    const Row* raw = a.rows.as<Row>();
     if constexpr (!RowKind<Row>::sq8) {
-        if (slot) {   // a sparse store: the same two kernels with the vid -> row table (launch_ivfflat_lm_sparse)
-#define GH_FLSP(LL, DD)                                                                                                       \
-    hipLaunchKernelGGL((k_ivfflat_lm_sp<LL, DD, Row>), dim3(grid), dim3(256), 0, s, x, P, pair_off, list_off, list_len, ids, raw, nraw, \
-                       start, cnt, inv, ustart, nlist, q_stride, out, ftab, need_filter, min_score, max_score, slot, nslot)
-#define GH_FLSPD(LL)                      \
-    switch (d) {                          \
+        if (a.slot) {   // a sparse store: the same two kernels with the vid -> row table
+#define GH_FLSP(LL, DD) \
+    hipLaunchKernelGGL((k_ivfflat_lm_sp<LL, DD, Row>), dim3(LM_GRID), dim3(256), 0, s, a.x, a.P, GH_LM_ARGS, a.slot, a.nslot)
+#define GH_FLSPD(LL)                       \
+    switch (a.d) {                         \
         case 128: GH_FLSP(LL, 128); break; \
         case 96: GH_FLSP(LL, 96); break;   \
         case 64: GH_FLSP(LL, 64); break;   \
         case 32: GH_FLSP(LL, 32); break;   \
-        default: GH_FLSP(LL, 16); break;   \
+        case 16: GH_FLSP(LL, 16); break;   \
+        default: break;                    \
     }
             if (sliced) {
-                if (l2)
-                    hipLaunchKernelGGL((k_ivfflat_lms_sp<true, Row>), dim3(grid), dim3(256), 0, s, x, d, P, pair_off, list_off, list_len,
-                                       ids, raw, nraw, start, cnt, inv, ustart, nlist, q_stride, out, ftab, need_filter, min_score,
-                                       max_score, slot, nslot);
+                if (a.l2)
+                    hipLaunchKernelGGL((k_ivfflat_lms_sp<true, Row>), dim3(LM_GRID), dim3(256), 0, s, a.x, a.d, a.P, GH_LM_ARGS, a.slot,
+                                       a.nslot);
                 else
-                    hipLaunchKernelGGL((k_ivfflat_lms_sp<false, Row>), dim3(grid), dim3(256), 0, s, x, d, P, pair_off, list_off, list_len,
-                                       ids, raw, nraw, start, cnt, inv, ustart, nlist, q_stride, out, ftab, need_filter, min_score,
-                                       max_score, slot, nslot);
-            } else if (l2) {
+                    hipLaunchKernelGGL((k_ivfflat_lms_sp<false, Row>), dim3(LM_GRID), dim3(256), 0, s, a.x, a.d, a.P, GH_LM_ARGS, a.slot,
+                                       a.nslot);
+            } else if (a.l2) {
                 GH_FLSPD(true)
             } else {
                 GH_FLSPD(false)
@@ -749,140 +735,69 @@ void launch_ivfflat_lm_t(hipStream_t s, bool l2, const float* x, int nq, int d, 
             return;
         }
     }
+    const RowTab<Row> tab = row_tab<Row>(a.rows.tab);
     if (sliced) {
-        if (l2)
-            hipLaunchKernelGGL((k_ivfflat_lms<true, Row>), dim3(grid), dim3(256), 0, s, x, d, P, pair_off, list_off, list_len, ids,
-                               raw, nraw, start, cnt, inv, ustart, nlist, q_stride, out, ftab, need_filter, min_score, max_score, tab);
-        else
-            hipLaunchKernelGGL((k_ivfflat_lms<false, Row>), dim3(grid), dim3(256), 0, s, x, d, P, pair_off, list_off, list_len, ids,
-                               raw, nraw, start, cnt, inv, ustart, nlist, q_stride, out, ftab, need_filter, min_score, max_score, tab);
+        if (a.l2) hipLaunchKernelGGL((k_ivfflat_lms<true, Row>), dim3(LM_GRID), dim3(256), 0, s, a.x, a.d, a.P, GH_LM_ARGS, tab);
+        else hipLaunchKernelGGL((k_ivfflat_lms<false, Row>), dim3(LM_GRID), dim3(256), 0, s, a.x, a.d, a.P, GH_LM_ARGS, tab);
         return;
     }
-#define GH_FL(LL, DD)                                                                                                   \
-    hipLaunchKernelGGL((k_ivfflat_lm<LL, DD, Row>), dim3(grid), dim3(256), 0, s, x, P, pair_off, list_off, list_len, ids, \
-                       raw, nraw, start, cnt, inv, ustart, nlist, q_stride, out, ftab, need_filter, min_score, max_score, tab)
-#define GH_FLD(LL)                    \
-    switch (d) {                      \
+#define GH_FL(LL, DD) hipLaunchKernelGGL((k_ivfflat_lm<LL, DD, Row>), dim3(LM_GRID), dim3(256), 0, s, a.x, a.P, GH_LM_ARGS, tab)
+#define GH_FLD(LL)                       \
+    switch (a.d) {                       \
         case 128: GH_FL(LL, 128); break; \
         case 96: GH_FL(LL, 96); break;   \
         case 64: GH_FL(LL, 64); break;   \
         case 32: GH_FL(LL, 32); break;   \
-        default: GH_FL(LL, 16); break;   \
+        case 16: GH_FL(LL, 16); break;   \
+        default: break;                  \
     }
-    if (l2) { GH_FLD(true) } else { GH_FLD(false) }
+    if (a.l2) { GH_FLD(true) } else { GH_FLD(false) }
 #undef GH_FLD
 #undef GH_FL
 }
-}  // namespace
 
-void launch_ivfflat_lm(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* probe, const int* pair_off,
-                       const int64_t* list_off, const int* list_len, int nlist, const int64_t* ids, const float* raw,
-                       int64_t nraw, int64_t q_stride, float* out, const FilterDesc* ftab, int need_filter, float min_score,
-                       float max_score, void* scratch) {
-    launch_ivfflat_lm_t<float>(s, l2, x, nq, d, P, probe, pair_off, list_off, list_len, nlist, ids, raw, nraw, q_stride, out, ftab,
-                               need_filter, min_score, max_score, scratch);
-}
-// fp32 rows of a sparse store: slot [nslot] = vector id -> row of `raw` (nraw rows), -1 = not held here
-void launch_ivfflat_lm_sparse(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* probe, const int* pair_off,
-                              const int64_t* list_off, const int* list_len, int nlist, const int64_t* ids, const float* raw,
-                              int64_t nraw, const int32_t* slot, int64_t nslot, int64_t q_stride, float* out, const FilterDesc* ftab,
-                              int need_filter, float min_score, float max_score, void* scratch) {
-    if (!slot) return;   // (a sparse store without a table holds no row: the caller fills the slab with the sentinel)
-    launch_ivfflat_lm_t<float>(s, l2, x, nq, d, P, probe, pair_off, list_off, list_len, nlist, ids, raw, nraw, q_stride, out, ftab,
-                               need_filter, min_score, max_score, scratch, RowTab<float>{}, slot, nslot);
-}
-// ... of any element type but sq8 (a sparse sq8 store is refused before it gets here: nothing is launched for one)
-void launch_ivfflat_lm_sparse(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* probe, const int* pair_off,
-                              const int64_t* list_off, const int* list_len, int nlist, const int64_t* ids, const RowsRef& raw,
-                              int64_t nraw, const int32_t* slot, int64_t nslot, int64_t q_stride, float* out, const FilterDesc* ftab,
-                              int need_filter, float min_score, float max_score, void* scratch) {
-    if (!slot) return;
-#define GH_FLRS(T)                                                                                                             \
-    launch_ivfflat_lm_t<T>(s, l2, x, nq, d, P, probe, pair_off, list_off, list_len, nlist, ids, raw.as<T>(), nraw, q_stride, out, \
-                           ftab, need_filter, min_score, max_score, scratch, RowTab<T>{}, slot, nslot)
-    switch (raw.et) {
-        case 0: GH_FLRS(float); break;
-        case 1: GH_FLRS(uint16_t); break;
-        case 2: GH_FLRS(uint8_t); break;
-        case 3: GH_FLRS(int8_t); break;
-        default: break;
-    }
-#undef GH_FLRS
-}
-// rows of any element type (gamma_hip_set_ivfflat_narrow_rows, _sq8_rows); fp32 rows: the launch above, the kernels it always ran
-void launch_ivfflat_lm(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* probe, const int* pair_off,
-                       const int64_t* list_off, const int* list_len, int nlist, const int64_t* ids, const RowsRef& raw,
-                       int64_t nraw, int64_t q_stride, float* out, const FilterDesc* ftab, int need_filter, float min_score,
-                       float max_score, void* scratch) {
-#define GH_FLR(T)                                                                                                              \
-    launch_ivfflat_lm_t<T>(s, l2, x, nq, d, P, probe, pair_off, list_off, list_len, nlist, ids, raw.as<T>(), nraw, q_stride, out, \
-                           ftab, need_filter, min_score, max_score, scratch)
-    switch (raw.et) {
-        case 0:
-            launch_ivfflat_lm(s, l2, x, nq, d, P, probe, pair_off, list_off, list_len, nlist, ids, raw.as<float>(), nraw, q_stride,
-                              out, ftab, need_filter, min_score, max_score, scratch);
-            break;
-        case 1: GH_FLR(uint16_t); break;
-        case 2: GH_FLR(uint8_t); break;
-        case 3: GH_FLR(int8_t); break;
-        case 4:   // (codes are never numbers: an sq8 store goes to the decoding kernels or nowhere)
-            launch_ivfflat_lm_t<sq8_t>(s, l2, x, nq, d, P, probe, pair_off, list_off, list_len, nlist, ids, raw.as<sq8_t>(), nraw,
-                                       q_stride, out, ftab, need_filter, min_score, max_score, scratch, row_tab<sq8_t>(raw.tab));
-            break;
-        default: break;
-    }
-#undef GH_FLR
-}
-
-// d % 16 != 0 (ivfflat_lm_tail_shape: kind 3), dense fp32 / float16 / uint8 / int8 rows: the inverse index of the row-sliced
-// kernel (k_inv_scan_s: units of FS_QT queries), then k_ivfflat_lmt with the load width the row length allows.  Returns false,
-// with nothing launched, for a store or a length it has no kernel for.
-namespace {
+// LM_TAIL (d % 16 != 0): the row-sliced kernel's inverse index, then k_ivfflat_lmt with the load width the row length allows
 template <class Row, int LOADB>
-void launch_lmt_k(hipStream_t s, bool l2, const float* x, int d, int P, const int* pair_off, const int64_t* list_off,
-                  const int* list_len, int nlist, const int64_t* ids, const Row* raw, int64_t nraw, const int* start,
-                  const int* cnt, const int* inv, const int* ustart, int64_t q_stride, float* out, const FilterDesc* ftab,
-                  int need_filter, float min_score, float max_score) {
-    const int grid = 256 * 8;   // persistent, as the two other list-major kernels
-    if (l2)
-        hipLaunchKernelGGL((k_ivfflat_lmt<true, Row, LOADB>), dim3(grid), dim3(256), 0, s, x, d, P, pair_off, list_off, list_len, ids,
-                           raw, nraw, start, cnt, inv, ustart, nlist, q_stride, out, ftab, need_filter, min_score, max_score);
-    else
-        hipLaunchKernelGGL((k_ivfflat_lmt<false, Row, LOADB>), dim3(grid), dim3(256), 0, s, x, d, P, pair_off, list_off, list_len, ids,
-                           raw, nraw, start, cnt, inv, ustart, nlist, q_stride, out, ftab, need_filter, min_score, max_score);
+void launch_lmt_k(hipStream_t s, const IvfflatScanArgs& a) {
+    const LmIndex ix = lm_inverse_index(s, a, true);
+    const Row* raw = a.rows.as<Row>();
+    if (a.l2) hipLaunchKernelGGL((k_ivfflat_lmt<true, Row, LOADB>), dim3(LM_GRID), dim3(256), 0, s, a.x, a.d, a.P, GH_LM_ARGS);
+    else hipLaunchKernelGGL((k_ivfflat_lmt<false, Row, LOADB>), dim3(LM_GRID), dim3(256), 0, s, a.x, a.d, a.P, GH_LM_ARGS);
 }
+#undef GH_LM_ARGS
 }  // namespace
 
-bool launch_ivfflat_lm_tail(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* probe, const int* pair_off,
-                            const int64_t* list_off, const int* list_len, int nlist, const int64_t* ids, const RowsRef& raw,
-                            int64_t nraw, int64_t q_stride, float* out, const FilterDesc* ftab, int need_filter, float min_score,
-                            float max_score, void* scratch) {
-    int kind = 0, lb = 0, qtile = 0;
-    if (raw.et < 0 || raw.et > 3 || ivfflat_lm_tail_shape(d, (int)raw.esz(), &kind, &lb, &qtile) != 3) return false;
-    if (nq <= 0 || P <= 0) return true;
-    int* inv = static_cast<int*>(scratch);
-    int* cnt = inv + (size_t)nq * P;
-    int* start = cnt + nlist;
-    int* cur = start + nlist;
-    int* ustart = cur + nlist;
-    const int npairs = nq * P;
-    (void)hipMemsetAsync(cnt, 0, (size_t)nlist * sizeof(int), s);
-    hipLaunchKernelGGL(k_inv_count, dim3((npairs + 255) / 256), dim3(256), 0, s, probe, npairs, nlist, list_len, cnt);
-    hipLaunchKernelGGL(k_inv_scan_s, dim3(1), dim3(1024), 0, s, cnt, list_len, nlist, start, cur, ustart);
-    hipLaunchKernelGGL(k_inv_fill, dim3((npairs + 255) / 256), dim3(256), 0, s, probe, npairs, nlist, list_len, start, cur, inv);
-#define GH_FLT(T, B)                                                                                                           \
-    case B:                                                                                                                    \
-        launch_lmt_k<T, B>(s, l2, x, d, P, pair_off, list_off, list_len, nlist, ids, raw.as<T>(), nraw, start, cnt, inv, ustart, \
-                           q_stride, out, ftab, need_filter, min_score, max_score);                                           \
-        break;
-    switch (raw.et) {
-        case 0:
+void launch_ivfflat_lm(hipStream_t s, IvfflatScanPlan::Kind kind, const IvfflatScanArgs& a) {
+    if (a.nq <= 0 || a.P <= 0) return;
+    const int et = a.rows.et;
+    if (kind == IvfflatScanPlan::LM_FIXED || kind == IvfflatScanPlan::LM_SLICED) {
+        const bool sliced = kind == IvfflatScanPlan::LM_SLICED;
+        switch (et) {
+            case ROW_F32: launch_lm_t<float>(s, a, sliced); break;
+            case ROW_F16: launch_lm_t<uint16_t>(s, a, sliced); break;
+            case ROW_U8: launch_lm_t<uint8_t>(s, a, sliced); break;
+            case ROW_I8: launch_lm_t<int8_t>(s, a, sliced); break;
+            case ROW_SQ8:   // (codes are never numbers: an sq8 store goes to the decoding kernels or, sparse, nowhere)
+                if (!a.slot) launch_lm_t<sq8_t>(s, a, sliced);
+                break;
+            default: break;
+        }
+        return;
+    }
+    if (kind != IvfflatScanPlan::LM_TAIL) return;
+    int k3 = 0, lb = 0, qtile = 0;
+    // (dense rows that are numbers, of a length with a tail: an sq8 or a sparse store has no such kernel)
+    if (et < ROW_F32 || et > ROW_I8 || a.slot || ivfflat_lm_tail_shape(a.d, (int)a.rows.esz(), &k3, &lb, &qtile) != 3) return;
+#define GH_FLT(T, B) \
+    case B: launch_lmt_k<T, B>(s, a); break;
+    switch (et) {
+        case ROW_F32:
             switch (lb) { GH_FLT(float, 16) GH_FLT(float, 8) GH_FLT(float, 4) }
             break;
-        case 1:
+        case ROW_F16:
             switch (lb) { GH_FLT(uint16_t, 16) GH_FLT(uint16_t, 8) GH_FLT(uint16_t, 4) GH_FLT(uint16_t, 2) }
             break;
-        case 2:
+        case ROW_U8:
             switch (lb) { GH_FLT(uint8_t, 8) GH_FLT(uint8_t, 4) GH_FLT(uint8_t, 2) GH_FLT(uint8_t, 1) }
             break;
         default:
@@ -890,7 +805,6 @@ bool launch_ivfflat_lm_tail(hipStream_t s, bool l2, const float* x, int nq, int 
             break;
     }
 #undef GH_FLT
-    return true;
 }
 
 }  // namespace gh

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ivfflat_plan.h"
 #include "scan_plan.h"
 
 namespace gh {
@@ -359,62 +360,37 @@ void launch_small_tail(hipStream_t s, bool l2, const float* slab, int64_t q_stri
                        int fixed_n = 0,    // q_total == nullptr (flat search): every row has fixed_n entries, position = vector id
                        const TieReplayArgs* tr = nullptr,   // exact ties: a query with a tie at a cut is replayed in the kernel
                        unsigned long long* tie_stats = nullptr);
-// IVFFLAT: exact distances of every entry of the probed lists (rows from the raw store) into the query's slab
-void launch_ivfflat_scan(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* pair_off,
-                         const int64_t* pair_base, const int64_t* ids, const float* raw, int64_t nraw, int64_t q_stride,
-                         float* out, const FilterDesc* ftab, int need_filter, float min_score, float max_score);
-// ... over rows of any element type (a narrow row widens to fp32 exactly on load, an sq8 code is decoded with raw.tab); element
-// type 0 forwards to the launch above; the same for launch_ivfflat_lm below
-void launch_ivfflat_scan(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* pair_off,
-                         const int64_t* pair_base, const int64_t* ids, const RowsRef& raw, int64_t nraw, int64_t q_stride,
-                         float* out, const FilterDesc* ftab, int need_filter, float min_score, float max_score);
-// IVFFLAT, list-major (ivfflat.hip): one workgroup per list, every query probing it run past the list's rows
-bool ivfflat_lm_supported(int d);
-// the list-major form of rows of d floats: *kind 0 = none (the pair kernel), 1 = fixed-length (k_ivfflat_lm: the whole row in
-// registers, d in {16, 32, 64, 96, 128}), 2 = row-sliced (k_ivfflat_lms: every other d % 16 == 0 up to 4096); *slab = the
-// elements of a row a pair of threads holds at a time, *qtile = the queries per LDS tile (both 0 with kind 0).  Returns kind.
-int ivfflat_lm_shape(int d, int* kind, int* slab, int* qtile);
-size_t ivfflat_lm_scratch_bytes(int nq, int P, int nlist);
-// the list-major form of the lengths ivfflat_lm_shape answers 0 for: *kind 3 = row-sliced with the scanner's tail steps
-// (k_ivfflat_lmt: 1 <= d <= 4096, d % 16 != 0), else 0; *load_bytes = gcd(16, d * elem_bytes), the alignment every row of such a
-// store has and the width of the kernel's row loads; *qtile = the queries per LDS tile (k_ivfflat_lms's).  Returns kind.
-int ivfflat_lm_tail_shape(int d, int elem_bytes, int* kind, int* load_bytes, int* qtile);
-// kind 3 over the dense rows of an fp32 / float16 / uint8 / int8 store, scratch as launch_ivfflat_lm's; false = nothing launched
-// (another length, an sq8 store)
-bool launch_ivfflat_lm_tail(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* probe, const int* pair_off,
-                            const int64_t* list_off, const int* list_len, int nlist, const int64_t* ids, const RowsRef& raw,
-                            int64_t nraw, int64_t q_stride, float* out, const FilterDesc* ftab, int need_filter, float min_score,
-                            float max_score, void* scratch);
-void launch_ivfflat_lm(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* probe, const int* pair_off,
-                       const int64_t* list_off, const int* list_len, int nlist, const int64_t* ids, const float* raw,
-                       int64_t nraw, int64_t q_stride, float* out, const FilterDesc* ftab, int need_filter, float min_score,
-                       float max_score, void* scratch);
-void launch_ivfflat_lm(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* probe, const int* pair_off,
-                       const int64_t* list_off, const int* list_len, int nlist, const int64_t* ids, const RowsRef& raw,
-                       int64_t nraw, int64_t q_stride, float* out, const FilterDesc* ftab, int need_filter, float min_score,
-                       float max_score, void* scratch);
-// The three scans over the fp32 rows of a SPARSE store (gamma_hip_raw_put: a list shard's own rows): slot [nslot] = vector id ->
-// row of `raw` (nraw rows), -1 = not held here; an entry without a row here gets the sentinel and nothing is read through it.
-// Kernels of their own (the sparse instantiation of each scan's body): the launches above are untouched.  slot == nullptr (a
-// store that never took a row): nothing is launched -- the caller fills the slab with the sentinel.
-void launch_ivfflat_scan_sparse(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* pair_off,
-                                const int64_t* pair_base, const int64_t* ids, const float* raw, int64_t nraw, const int32_t* slot,
-                                int64_t nslot, int64_t q_stride, float* out, const FilterDesc* ftab, int need_filter,
-                                float min_score, float max_score);
-void launch_ivfflat_lm_sparse(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* probe, const int* pair_off,
-                              const int64_t* list_off, const int* list_len, int nlist, const int64_t* ids, const float* raw,
-                              int64_t nraw, const int32_t* slot, int64_t nslot, int64_t q_stride, float* out, const FilterDesc* ftab,
-                              int need_filter, float min_score, float max_score, void* scratch);
-// ... over the rows of a sparse store of any element type but sq8 (float16 / uint8 / int8 rows widen exactly on load: the same
-// bodies, instantiated per type); element type 0 launches the kernels of the two launches above
-void launch_ivfflat_scan_sparse(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* pair_off,
-                                const int64_t* pair_base, const int64_t* ids, const RowsRef& raw, int64_t nraw,
-                                const int32_t* slot, int64_t nslot, int64_t q_stride, float* out, const FilterDesc* ftab,
-                                int need_filter, float min_score, float max_score);
-void launch_ivfflat_lm_sparse(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* probe, const int* pair_off,
-                              const int64_t* list_off, const int* list_len, int nlist, const int64_t* ids, const RowsRef& raw,
-                              int64_t nraw, const int32_t* slot, int64_t nslot, int64_t q_stride, float* out, const FilterDesc* ftab,
-                              int need_filter, float min_score, float max_score, void* scratch);
+// IVFFLAT: exact distances of every entry of the probed lists (rows from the raw store) into the query's slab.  What a scan
+// launch reads and writes, each operand named once (ivfflat_scan_chunk and ivfflat_small fill it from the handle).
+struct IvfflatScanArgs {
+    bool l2 = true;
+    const float* x = nullptr;             // [nq][d] queries
+    int nq = 0, d = 0, P = 0;
+    const int* probe = nullptr;           // [nq][P] the assignment (list-major: the inverse index is built from it)
+    const int* pair_off = nullptr;        // [nq][P + 1] slab offsets of the pairs
+    const int64_t* pair_base = nullptr;   // [nq][P] first entry of the pair's list (pair kernel)
+    const int64_t* list_off = nullptr;    // [nlist] first entry of a list (list-major)
+    const int* list_len = nullptr;        // [nlist]; under a shard's mask the table in which an unowned list is empty
+    int nlist = 0;
+    const int64_t* ids = nullptr;         // the lists' entries: vector ids
+    RowsRef rows;                         // the store's rows of any element type: a narrow row widens to fp32 exactly on load, an
+    int64_t nraw = 0;                     //   sq8 code is decoded with rows.tab
+    const int32_t* slot = nullptr;        // a SPARSE store (gamma_hip_raw_put: a list shard's own rows): [nslot] vector id -> row,
+    int64_t nslot = 0;                    //   -1 = not held here (sentinel, nothing read); nullptr: a dense store, row = vector id
+    int64_t q_stride = 0;
+    float* out = nullptr;                 // [nq][q_stride] the slab
+    const FilterDesc* ftab = nullptr;
+    int need_filter = 0;
+    float min_score = 0.f, max_score = 0.f;
+    void* scratch = nullptr;              // list-major: ivfflat_lm_scratch_bytes(nq, P, nlist)
+};
+// one workgroup per (query, probe) pair (rerank.hip); a.slot selects the sparse body.  Nothing is launched for nq <= 0 or
+// P <= 0, nor for a sparse sq8 store (refused before it gets here).
+void launch_ivfflat_pair(hipStream_t s, const IvfflatScanArgs& a);
+// list-major (ivfflat.hip): one workgroup per list, every query probing it run past the list's rows; kind: LM_FIXED, LM_SLICED
+// (a.slot selects their sparse bodies; never with sq8) or LM_TAIL (dense fp32 / float16 / uint8 / int8 rows only: nothing is
+// launched for another store).  Nothing is launched for nq <= 0 or P <= 0.
+void launch_ivfflat_lm(hipStream_t s, IvfflatScanPlan::Kind kind, const IvfflatScanArgs& a);
 // out[l] = mask[l] ? list_len[l] : 0 -- the list-length table of a list shard: to the list-major launch an unowned list is empty
 void launch_masked_list_len(hipStream_t s, const int* list_len, const uint8_t* mask, int nlist, int* out);
 // returns true when the walk of the tied rows went to `side` (the caller then waits for `join` before reading the result)

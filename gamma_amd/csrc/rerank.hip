@@ -595,114 +595,43 @@ __global__ __launch_bounds__(256) void k_ivfflat_scan_sp(const float* __restrict
     ivfflat_scan_body<L2, Row, true>(x, d, P, pair_off, pair_base, ids, raw, nraw, q_stride, out, ftab, need_filter, min_score,
                                      max_score, RowTab<Row>{}, slot, nslot);
 }
-// fp32 rows of a sparse store: slot [nslot] = vector id -> row of `raw` (nraw rows), -1 = not held here
-void launch_ivfflat_scan_sparse(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* pair_off,
-                                const int64_t* pair_base, const int64_t* ids, const float* raw, int64_t nraw, const int32_t* slot,
-                                int64_t nslot, int64_t q_stride, float* out, const FilterDesc* ftab, int need_filter,
-                                float min_score, float max_score) {
-    if (nq <= 0 || P <= 0 || !slot) return;
-    const dim3 grid((unsigned)((int64_t)nq * P));
-    if (l2)
-        hipLaunchKernelGGL((k_ivfflat_scan_sp<true>), grid, dim3(256), 0, s, x, d, P, pair_off, pair_base, ids, raw, nraw, q_stride,
-                           out, ftab, need_filter, min_score, max_score, slot, nslot);
-    else
-        hipLaunchKernelGGL((k_ivfflat_scan_sp<false>), grid, dim3(256), 0, s, x, d, P, pair_off, pair_base, ids, raw, nraw, q_stride,
-                           out, ftab, need_filter, min_score, max_score, slot, nslot);
-}
 namespace {
-template <class Row>
-void launch_ivfflat_scan_sparse_t(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* pair_off,
-                                  const int64_t* pair_base, const int64_t* ids, const Row* raw, int64_t nraw, const int32_t* slot,
-                                  int64_t nslot, int64_t q_stride, float* out, const FilterDesc* ftab, int need_filter,
-                                  float min_score, float max_score) {
-    if (nq <= 0 || P <= 0 || !slot) return;
-    const dim3 grid((unsigned)((int64_t)nq * P));
-    if (l2)
-        hipLaunchKernelGGL((k_ivfflat_scan_sp<true, Row>), grid, dim3(256), 0, s, x, d, P, pair_off, pair_base, ids, raw, nraw,
-                           q_stride, out, ftab, need_filter, min_score, max_score, slot, nslot);
-    else
-        hipLaunchKernelGGL((k_ivfflat_scan_sp<false, Row>), grid, dim3(256), 0, s, x, d, P, pair_off, pair_base, ids, raw, nraw,
-                           q_stride, out, ftab, need_filter, min_score, max_score, slot, nslot);
-}
-}  // namespace
-// ... of any element type but sq8 (a sparse sq8 store is refused before it gets here: nothing is launched for one)
-void launch_ivfflat_scan_sparse(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* pair_off,
-                                const int64_t* pair_base, const int64_t* ids, const RowsRef& raw, int64_t nraw,
-                                const int32_t* slot, int64_t nslot, int64_t q_stride, float* out, const FilterDesc* ftab,
-                                int need_filter, float min_score, float max_score) {
-    switch (raw.et) {
-        case 0:
-            launch_ivfflat_scan_sparse(s, l2, x, nq, d, P, pair_off, pair_base, ids, raw.as<float>(), nraw, slot, nslot, q_stride,
-                                       out, ftab, need_filter, min_score, max_score);
-            break;
-        case 1:
-            launch_ivfflat_scan_sparse_t(s, l2, x, nq, d, P, pair_off, pair_base, ids, raw.as<uint16_t>(), nraw, slot, nslot,
-                                         q_stride, out, ftab, need_filter, min_score, max_score);
-            break;
-        case 2:
-            launch_ivfflat_scan_sparse_t(s, l2, x, nq, d, P, pair_off, pair_base, ids, raw.as<uint8_t>(), nraw, slot, nslot,
-                                         q_stride, out, ftab, need_filter, min_score, max_score);
-            break;
-        case 3:
-            launch_ivfflat_scan_sparse_t(s, l2, x, nq, d, P, pair_off, pair_base, ids, raw.as<int8_t>(), nraw, slot, nslot,
-                                         q_stride, out, ftab, need_filter, min_score, max_score);
-            break;
-        default: break;
+// SPARSE: k_ivfflat_scan_sp with the store's vid -> row table, else k_ivfflat_scan with the decode table (empty but for sq8 rows)
+template <class Row, bool SPARSE>
+void launch_ivfflat_pair_t(hipStream_t s, const IvfflatScanArgs& a) {
+    const dim3 grid((unsigned)((int64_t)a.nq * a.P));
+    const Row* raw = a.rows.as<Row>();
+#define GH_FP(K, ...)                                                                                                               \
+    hipLaunchKernelGGL(K, grid, dim3(256), 0, s, a.x, a.d, a.P, a.pair_off, a.pair_base, a.ids, raw, a.nraw, a.q_stride, a.out, a.ftab, \
+                       a.need_filter, a.min_score, a.max_score, __VA_ARGS__)
+    if constexpr (SPARSE) {
+        if (a.l2) GH_FP((k_ivfflat_scan_sp<true, Row>), a.slot, a.nslot);
+        else GH_FP((k_ivfflat_scan_sp<false, Row>), a.slot, a.nslot);
+    } else {
+        if (a.l2) GH_FP((k_ivfflat_scan<true, Row>), row_tab<Row>(a.rows.tab));
+        else GH_FP((k_ivfflat_scan<false, Row>), row_tab<Row>(a.rows.tab));
     }
-}
-void launch_ivfflat_scan(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* pair_off,
-                         const int64_t* pair_base, const int64_t* ids, const float* raw, int64_t nraw, int64_t q_stride,
-                         float* out, const FilterDesc* ftab, int need_filter, float min_score, float max_score) {
-    if (nq <= 0 || P <= 0) return;
-    const dim3 grid((unsigned)((int64_t)nq * P));
-    if (l2)
-        hipLaunchKernelGGL((k_ivfflat_scan<true>), grid, dim3(256), 0, s, x, d, P, pair_off, pair_base, ids, raw, nraw,
-                           q_stride, out, ftab, need_filter, min_score, max_score, RowTab<float>{});
-    else
-        hipLaunchKernelGGL((k_ivfflat_scan<false>), grid, dim3(256), 0, s, x, d, P, pair_off, pair_base, ids, raw, nraw,
-                           q_stride, out, ftab, need_filter, min_score, max_score, RowTab<float>{});
-}
-namespace {
-template <class Row>
-void launch_ivfflat_scan_t(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* pair_off,
-                           const int64_t* pair_base, const int64_t* ids, const Row* raw, int64_t nraw, int64_t q_stride,
-                           float* out, const FilterDesc* ftab, int need_filter, float min_score, float max_score,
-                           RowTab<Row> tab = RowTab<Row>{}) {
-    if (nq <= 0 || P <= 0) return;
-    const dim3 grid((unsigned)((int64_t)nq * P));
-    if (l2)
-        hipLaunchKernelGGL((k_ivfflat_scan<true, Row>), grid, dim3(256), 0, s, x, d, P, pair_off, pair_base, ids, raw, nraw,
-                           q_stride, out, ftab, need_filter, min_score, max_score, tab);
-    else
-        hipLaunchKernelGGL((k_ivfflat_scan<false, Row>), grid, dim3(256), 0, s, x, d, P, pair_off, pair_base, ids, raw, nraw,
-                           q_stride, out, ftab, need_filter, min_score, max_score, tab);
+#undef GH_FP
 }
 }  // namespace
-// rows of any element type (gamma_hip_set_ivfflat_narrow_rows, _sq8_rows); fp32 rows: the launch above, the kernels it always ran
-void launch_ivfflat_scan(hipStream_t s, bool l2, const float* x, int nq, int d, int P, const int* pair_off,
-                         const int64_t* pair_base, const int64_t* ids, const RowsRef& raw, int64_t nraw, int64_t q_stride,
-                         float* out, const FilterDesc* ftab, int need_filter, float min_score, float max_score) {
-    switch (raw.et) {
-        case 0:
-            launch_ivfflat_scan(s, l2, x, nq, d, P, pair_off, pair_base, ids, raw.as<float>(), nraw, q_stride, out, ftab,
-                                need_filter, min_score, max_score);
-            break;
-        case 1:
-            launch_ivfflat_scan_t(s, l2, x, nq, d, P, pair_off, pair_base, ids, raw.as<uint16_t>(), nraw, q_stride, out, ftab,
-                                  need_filter, min_score, max_score);
-            break;
-        case 2:
-            launch_ivfflat_scan_t(s, l2, x, nq, d, P, pair_off, pair_base, ids, raw.as<uint8_t>(), nraw, q_stride, out, ftab,
-                                  need_filter, min_score, max_score);
-            break;
-        case 3:
-            launch_ivfflat_scan_t(s, l2, x, nq, d, P, pair_off, pair_base, ids, raw.as<int8_t>(), nraw, q_stride, out, ftab,
-                                  need_filter, min_score, max_score);
-            break;
-        case 4:   // (codes are never numbers: an sq8 store goes to the decoding kernel or nowhere)
-            launch_ivfflat_scan_t(s, l2, x, nq, d, P, pair_off, pair_base, ids, raw.as<sq8_t>(), nraw, q_stride, out, ftab,
-                                  need_filter, min_score, max_score, row_tab<sq8_t>(raw.tab));
-            break;
+void launch_ivfflat_pair(hipStream_t s, const IvfflatScanArgs& a) {
+    if (a.nq <= 0 || a.P <= 0) return;
+    if (a.slot) {   // a sparse store; never sq8 (refused before it gets here: nothing is launched for one)
+        switch (a.rows.et) {
+            case ROW_F32: launch_ivfflat_pair_t<float, true>(s, a); break;
+            case ROW_F16: launch_ivfflat_pair_t<uint16_t, true>(s, a); break;
+            case ROW_U8: launch_ivfflat_pair_t<uint8_t, true>(s, a); break;
+            case ROW_I8: launch_ivfflat_pair_t<int8_t, true>(s, a); break;
+            default: break;
+        }
+        return;
+    }
+    switch (a.rows.et) {
+        case ROW_F32: launch_ivfflat_pair_t<float, false>(s, a); break;
+        case ROW_F16: launch_ivfflat_pair_t<uint16_t, false>(s, a); break;
+        case ROW_U8: launch_ivfflat_pair_t<uint8_t, false>(s, a); break;
+        case ROW_I8: launch_ivfflat_pair_t<int8_t, false>(s, a); break;
+        case ROW_SQ8: launch_ivfflat_pair_t<sq8_t, false>(s, a); break;   // (codes are never numbers: the decoding kernel)
         default: break;
     }
 }

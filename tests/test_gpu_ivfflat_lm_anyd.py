@@ -237,3 +237,20 @@ def test_fixed_lengths_keep_the_fixed_kernel_and_other_lengths_the_pair_kernel()
         h.check(c.q, 10, 4)
     finally:
         h.close()
+
+
+# ---- the pair count at which lists count as shared ----------------------------------------------------------------------------
+@pytest.mark.parametrize("metric", [L2, IP], ids=["l2", "ip"])
+@pytest.mark.parametrize("d,lm_stat", [(16, FIXED), (48, SLICED)])
+def test_two_nlist_pairs_is_the_first_list_major_chunk(d, lm_stat, metric):
+    """nlist 8, 4 probes: 4 queries are 16 pairs = 2 nlist and go list-major, 3 queries are 12 and -- the small path switched off
+    on the handle -- go to the pair kernel; the handle under the all-owning mask takes the pair kernel both times"""
+    c = LM.Case(d, "float32", metric, N=600, nlist=8, nq=4, seed=40 + d)
+    h = Handles(c, lm_stat=lm_stat)
+    try:
+        h.each(lambda g: g.set_small_path(False))
+        h.check(c.q, 5, 4)
+        h.lm_stat = PAIR
+        h.check(c.q[:3], 5, 4)
+    finally:
+        h.close()

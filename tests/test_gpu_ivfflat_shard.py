@@ -105,6 +105,25 @@ def test_shards_equal_one_handle_and_the_oracle(cases, d, metric, W, sparse):
         r.close()
 
 
+@pytest.mark.parametrize("metric", [L2, IP], ids=["l2", "ip"])
+def test_a_shard_with_lm_tails_set_keeps_the_pair_kernel(metric):
+    """d 20, nlist 8, 4 queries x 4 probes = 2 nlist pairs, gamma_hip_set_ivfflat_lm_tails on every shard: a single handle would
+    scan such a chunk with the tail kernel, a shard ignores the switch -- the pair kernel, nothing counted for the tail kernel"""
+    assert api.ivfflat_lm_tail_shape(20)[0] == 3 and api.ivfflat_lm_shape(20)[0] == 0
+    c = LM.Case(20, "float32", metric, N=600, nlist=8, nq=4, seed=80)
+    r = Rig(c, 2, SR.owners_mod(c.nlist, 2), False)
+    try:
+        for g in r.shards:
+            g.set_ivfflat_lm_tails(True)
+            g.ivfflat_lm_tail_stats(reset=True)
+        r.check(c.q, 5, 4)
+        for g in r.shards:
+            s = g.ivfflat_scan_stats()
+            assert s[PAIR] > 0 and s[FIXED] == 0 and s[SLICED] == 0 and g.ivfflat_lm_tail_stats() == 0, s
+    finally:
+        r.close()
+
+
 @pytest.mark.parametrize("sparse", [False, True], ids=["dense", "sparse"])
 def test_a_shard_without_probed_lists_and_an_empty_sparse_store(sparse):
     """edge_case: a list of exactly 128 rows, one of 129, an empty one that queries probe.  Shard 1 owns ONE list (most queries
