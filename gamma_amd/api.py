@@ -256,6 +256,21 @@ class GammaHip:
                  "ivfpq4_init")
         self.d, self.nlist, self.M, self.ksub = d, nlist, M, 16
 
+    def ivfpq4_set_lm_scan(self, on):
+        """the scan of a 4-bit handle list-major: a slab of a list's codes in registers, a tile of the
+        (query, probe) pairs that probe the list run past them.  Off by default; the answer is the same bit for bit."""
+        self._ck(self.L.gamma_hip_ivfpq4_set_lm_scan(self.h, 1 if on else 0), "ivfpq4_set_lm_scan")
+
+    def ivfpq4_lm_scan(self):
+        """the switch as set"""
+        return int(self.L.gamma_hip_ivfpq4_lm_scan(self.h))
+
+    def ivfpq4_lm_stats(self):
+        """(calls, units, pairs) of the list-major scan launches since init; units is -1 (not read back from the device)"""
+        c, u, p = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._ck(self.L.gamma_hip_ivfpq4_lm_stats(self.h, C.byref(c), C.byref(u), C.byref(p)), "ivfpq4_lm_stats")
+        return int(c.value), int(u.value), int(p.value)
+
     # ---- OPQ rotation ----
     def opq_set(self, A):
         """the d x d rotation (row-major, xt = A x) of an 8-bit IVFPQ handle whose lists are still empty; from then on add,
@@ -1148,6 +1163,16 @@ def binivf_scan_shape():
     if rc != 0:
         raise _lib.GammaHipError("binivf_scan_shape: %d" % rc)
     return int(c.value), int(a.value)
+
+
+def ivfpq4_lm_shape(M):
+    """(mt, qt, lds_bytes) of the 4-bit list-major scan for M sub-quantizers: the kernel instantiation (M for 8 / 16 / 32 / 64,
+    else 0: byte loads), the (query, probe) pairs of a work unit, the LDS of a workgroup.  No device call."""
+    mt, qt, lds = C.c_int(0), C.c_int(0), C.c_int64(0)
+    rc = _lib.load().gamma_hip_ivfpq4_lm_shape(int(M), C.byref(mt), C.byref(qt), C.byref(lds))
+    if rc != 0:
+        raise _lib.GammaHipError("ivfpq4_lm_shape: %d" % rc)
+    return int(mt.value), int(qt.value), int(lds.value)
 
 
 def binivf_lm_shape():

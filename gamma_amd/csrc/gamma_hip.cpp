@@ -4,6 +4,7 @@
 // (gamma_hip_search_ivfflat.cpp, _flat.cpp, _shard.cpp), the handle itself in
 // gamma_hip_internal.h.  No CPU fallback anywhere: an entry point runs the HIP kernels or returns an error.
 #include "gamma_hip_internal.h"
+#include "pq4.h"
 
 using namespace ghi;
 
@@ -461,6 +462,36 @@ int gamma_hip_profile_get(gamma_hip_index* h, int stage, double* total_ms, int64
     GH_TRY(drain_events(h));
     if (total_ms) *total_ms = h->stage_ms[stage];
     if (launches) *launches = h->stage_n[stage];
+    return GAMMA_HIP_OK;
+}
+
+// The 4-bit scan list-major (pq4.hip k_ivfpq4_scan_lm, gh::ScanPlan::pq4_lm): the handle's switch, off by default
+int gamma_hip_ivfpq4_set_lm_scan(gamma_hip_index* h, int on) {
+    if (!h) return GAMMA_HIP_EINVAL;
+    SearchLock lk(h);
+    if (!h->ivf_init || h->ksub != gh::kPq4Ksub)
+        return fail(h, GAMMA_HIP_EUNSUPPORTED, "ivfpq4_set_lm_scan: the list-major scan is that of a 4-bit handle (gamma_hip_ivfpq4_init)");
+    h->pq4_lm_on = on != 0;
+    return GAMMA_HIP_OK;
+}
+
+int gamma_hip_ivfpq4_lm_scan(const gamma_hip_index* h) { return h && h->ksub == gh::kPq4Ksub && h->pq4_lm_on ? 1 : 0; }
+
+int gamma_hip_ivfpq4_lm_shape(int M, int* mt, int* qt, int64_t* lds_bytes) {
+    if (M < 1 || M > 2 * gh::kPq4MaxCodeSize) return GAMMA_HIP_EINVAL;
+    if (mt) *mt = gh::pq4_lm_mt(M);
+    if (qt) *qt = gh::kPq4LmQueryTile;
+    if (lds_bytes) *lds_bytes = (int64_t)gh::pq4_lm_lds_bytes(M);
+    return GAMMA_HIP_OK;
+}
+
+// host counters only: the unit total of a launch stays on the device (no read-back, no synchronisation)
+int gamma_hip_ivfpq4_lm_stats(gamma_hip_index* h, int64_t* calls, int64_t* units, int64_t* pairs) {
+    if (!h) return GAMMA_HIP_EINVAL;
+    SearchLock lk(h);
+    if (calls) *calls = h->pq4_lm_calls;
+    if (units) *units = -1;
+    if (pairs) *pairs = h->pq4_lm_pairs;
     return GAMMA_HIP_OK;
 }
 

@@ -25,6 +25,7 @@
 #include "flat_rows_dev.h"
 #include "ivfflat_plan.h"   // FL_QT, FS_QT, FS_SLAB
 #include "kernels.h"
+#include "pq4.h"   // kPq4LmQueryTile, kPq4LmSlab
 
 namespace gh {
 
@@ -103,6 +104,12 @@ __global__ __launch_bounds__(1024) void k_inv_scan_b(const int* __restrict__ cnt
                                                      int* __restrict__ start, int* __restrict__ cur,
                                                      int* __restrict__ ustart) {
     inv_scan_body<kBinLmQueryTile, kBinSpreadChunk>(cnt, list_len, nlist, start, cur, ustart);
+}
+// the same prefix with the 4-bit list-major scan's unit: kPq4LmQueryTile pairs x kPq4LmSlab codes (pq4.hip)
+__global__ __launch_bounds__(1024) void k_inv_scan_p(const int* __restrict__ cnt, const int* __restrict__ list_len, int nlist,
+                                                     int* __restrict__ start, int* __restrict__ cur,
+                                                     int* __restrict__ ustart) {
+    inv_scan_body<kPq4LmQueryTile, kPq4LmSlab>(cnt, list_len, nlist, start, cur, ustart);
 }
 __global__ __launch_bounds__(256) void k_inv_fill(const int* __restrict__ probe, int npairs, int nlist,
                                                   const int* __restrict__ list_len, const int* __restrict__ start,

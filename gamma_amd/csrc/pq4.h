@@ -30,4 +30,30 @@ void launch_ivfpq4_scan_pair(hipStream_t s, bool l2, int nq, int M, int P, const
                              const int* pair_off, int64_t q_stride, float* out, const FilterDesc* ftab, const int* qfil,
                              int need_ids, const int* qperm, int G, int pg_cnt);
 
+// ---- the same scan list-major, for large batches over many lists ----
+// A work unit = one list x one slab of kPq4LmSlab consecutive codes (a code per lane) x one tile of up to kPq4LmQueryTile of
+// the (query, probe) pairs that probe the list: codes, T2 row, ids are fetched once per unit instead of once per pair.
+constexpr int kPq4LmQueryTile = 32;
+constexpr int kPq4LmSlab = 256;
+// the instantiation a given M takes: M itself for 8 / 16 / 32 / 64 (dword code loads, M at compile time), 0 otherwise
+inline int pq4_lm_mt(int M) { return (M == 8 || M == 16 || M == 32 || M == 64) ? M : 0; }
+// LDS of a workgroup: two tables of M x 16 fp32, and nothing else
+inline size_t pq4_lm_lds_bytes(int M) { return (size_t)2 * M * kPq4Ksub * sizeof(float); }
+// launch_ivfpq4_scan_pair's slab, byte for byte, by k_ivfpq4_scan_lm over the call's inverse index (k_inv_count ->
+// k_inv_scan_p -> k_inv_fill, ivfflat.hip) built in scratch: ivfflat_lm_scratch_bytes(nq, P, nlist) bytes.  Refuses where
+// the pair launcher refuses, and without scratch, under a list mask (a 4-bit handle has none) or beyond 2^31 - 1 pairs / units.
+void launch_ivfpq4_scan_lm(hipStream_t s, bool l2, int nq, int M, int P, const int* probe_list, const float* dis0,
+                           const float* st2, const float* T2, const int64_t* list_off, const int* list_len,
+                           const uint8_t* list_mask, int nlist, int max_list_len, const uint8_t* codes, const int64_t* ids,
+                           const int* pair_off, int64_t q_stride, float* out, const FilterDesc* ftab, const int* qfil,
+                           int need_ids, void* scratch);
+// the counting sort of a call's (query, probe) pairs by list (ivfflat.hip), as launch_ivfpq4_scan_lm runs it: cnt zeroed ->
+// k_inv_count -> k_inv_scan_p (units of kPq4LmQueryTile pairs x kPq4LmSlab codes) -> k_inv_fill
+__global__ void k_inv_count(const int* __restrict__ probe, int npairs, int nlist, const int* __restrict__ list_len,
+                            int* __restrict__ cnt);
+__global__ void k_inv_scan_p(const int* __restrict__ cnt, const int* __restrict__ list_len, int nlist, int* __restrict__ start,
+                             int* __restrict__ cur, int* __restrict__ ustart);
+__global__ void k_inv_fill(const int* __restrict__ probe, int npairs, int nlist, const int* __restrict__ list_len,
+                           const int* __restrict__ start, int* __restrict__ cur, int* __restrict__ inv);
+
 }  // namespace gh

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <type_traits>
 
 #include "device_math.h"
@@ -291,6 +292,208 @@ void launch_ivfpq4_scan_pair(hipStream_t s, bool l2, int nq, int M, int P, const
     else GH_PQ4_M(false);
 #undef GH_PQ4_M
 #undef GH_PQ4
+}
+
+// ------------------------------------------------------------------------------------
+// The list scan list-major, for large batches over many lists: the pair kernel above fetches a list's
+// codes and its T2 row once per probing query and runs every pair as one dependent chain.  Here a work unit is
+//   one list  x  one slab of kPq4LmSlab consecutive codes (a code per lane, 4 waves)  x  one tile of up to kPq4LmQueryTile of
+//   the (query, probe) pairs that probe the list (the call's inverse index: k_inv_count / k_inv_scan_p / k_inv_fill),
+// walked by a persistent grid.  Once per unit, into registers: the lane's code words, the thread's entries of the list's T2 row,
+// the id when something can reject an entry, and -- lane t of every wave -- pair t's query, dis0 and slab position, which the
+// pair loop takes out with v_readlane instead of a chain of dependent loads.  Per pair: the LUT (the pair kernel's, entry for
+// entry) goes through TWO buffers of M x 16 floats, all of the kernel's LDS.  While the waves gather pair i from buffer i & 1
+// the threads write pair i + 1's table into the other one, and the st2 entries of pair i + 2 are already on their way into
+// registers (two register sets, sa / sb, alternate): one barrier per pair.  The arithmetic per entry is the pair kernel's --
+// dis = dis0, then += lut[m][nibble_m] for m ascending -- and the store goes to the pair's slot range of the ADC slab.
+// ------------------------------------------------------------------------------------
+constexpr int PQ4_LM_GRID = 256 * 8;   // persistent: every workgroup walks the unit list with stride gridDim.x
+static_assert(kPq4LmQueryTile <= 64 && kPq4LmSlab == 256, "a tile's pairs sit in the lanes of one wave; a code per thread");
+
+__device__ __forceinline__ int pq4_lane_i(int v, int l) { return __builtin_amdgcn_readlane(v, l); }
+__device__ __forceinline__ float pq4_lane_f(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
+
+template <bool L2, int MT>
+__global__ __launch_bounds__(256) void k_ivfpq4_scan_lm(
+        int M, int P, const float* __restrict__ pair_dis0, const float* __restrict__ st2, const float* __restrict__ T2,
+        const int64_t* __restrict__ list_off, const int* __restrict__ list_len, int nlist,
+        const uint8_t* __restrict__ codes, const int64_t* __restrict__ ids, const int* __restrict__ pair_off,
+        int64_t q_stride, float* __restrict__ out, const FilterDesc* __restrict__ ftab, const int* __restrict__ qfil,
+        int need_ids, float sentinel, const int* __restrict__ inv, const int* __restrict__ inv_start,
+        const int* __restrict__ inv_cnt, const int* __restrict__ ustart) {
+    extern __shared__ float s_lm4[];   // [2][M][16] and nothing else: a gather address is (nibble << 2) + an immediate
+    constexpr int QT = kPq4LmQueryTile;
+    constexpr int NE = MT > 0 ? (MT * 16 + 255) / 256 : (2 * kPq4MaxCodeSize * 16) / 256;   // table entries per thread
+    constexpr int NW = MT > 0 ? MT / 8 : kPq4MaxCodeSize / 4;                               // code words per code
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int Mr = MT > 0 ? MT : M;
+    const int msz = Mr * 16, cs = (Mr + 1) >> 1;
+    float* const lut0 = s_lm4;
+    float* const lut1 = s_lm4 + msz;
+    const int nunits = ustart[nlist];
+    for (int u = blockIdx.x; u < nunits; u += gridDim.x) {   // (everything that decides control flow below is uniform)
+        // unit u: lists in order, a list's slabs in order, a slab's tiles in order (neighbouring workgroups read the same codes)
+        int l = 0, hi = nlist - 1;
+        while (l < hi) {   // last list with ustart[l] <= u
+            const int mid = (l + hi + 1) >> 1;
+            if (ustart[mid] <= u) l = mid; else hi = mid - 1;
+        }
+        const int n = inv_cnt[l], len = list_len[l];
+        if (n <= 0 || len <= 0) continue;   // (no such unit exists: k_inv_scan_p gives these lists none)
+        const int tiles = (n + QT - 1) / QT, rel = u - ustart[l];
+        const int slab = rel / tiles, t0 = (rel - slab * tiles) * QT;
+        const int r0 = slab * kPq4LmSlab;
+        if (r0 >= len) continue;
+        const int nt = min(QT, n - t0), first = inv_start[l] + t0;
+        const int64_t off = list_off[l];
+        const int j = r0 + tid, jc = min(j, len - 1);   // this lane's code; the lanes beyond the list read its last one
+        // ---- once per unit ----
+        uint32_t cw[NW];
+        if constexpr (MT > 0) {
+            pq4_load_code<NW>(codes + (off + jc) * cs, cw);
+        } else {
+            const uint8_t* cj = codes + (off + jc) * cs;
+#pragma unroll
+            for (int w = 0; w < NW; w++) {
+                uint32_t v = 0;
+#pragma unroll
+                for (int b = 0; b < 4; b++)
+                    if (4 * w + b < cs) v |= (uint32_t)cj[4 * w + b] << (8 * b);
+                cw[w] = v;
+            }
+        }
+        float t2r[NE];
+#pragma unroll
+        for (int k = 0; k < NE; k++) {
+            const int e = tid + 256 * k;
+            t2r[k] = (L2 && e < msz) ? T2[(int64_t)l * msz + e] : 0.f;
+        }
+        // pair t of the tile in lane t of every wave: its query, dis0, filter and the slab position of the lane-0 code
+        const int pr = inv[first + min(lane, nt - 1)];
+        const int qv = pr / P;
+        const float d0v = pair_dis0[pr];
+        const int64_t oov = (int64_t)qv * q_stride + pair_off[(int64_t)qv * (P + 1) + (pr - qv * P)] + r0;
+        const int oolo = (int)(uint32_t)oov, oohi = (int)(oov >> 32);
+        const int fv = (need_ids && qfil) ? qfil[qv] : 0;
+        auto load_s2 = [&](int i, float (&r)[NE]) {
+            const float* sq = st2 + (int64_t)pq4_lane_i(qv, i) * msz;
+#pragma unroll
+            for (int k = 0; k < NE; k++) {
+                const int e = tid + 256 * k;
+                r[k] = e < msz ? sq[e] : 0.f;
+            }
+        };
+        auto write_lut = [&](float* buf, const float (&r)[NE]) {
+#pragma unroll
+            for (int k = 0; k < NE; k++) {
+                const int e = tid + 256 * k;
+                if (e < msz) buf[e] = L2 ? __builtin_fmaf(-2.0f, r[k], t2r[k]) : r[k];
+            }
+        };
+        float sa[NE], sb[NE];
+        load_s2(0, sa);
+        if (nt > 1) load_s2(1, sb);
+        write_lut(lut0, sa);   // (the previous unit's gathers are behind its last barrier)
+        if (nt > 2) load_s2(2, sa);
+        __syncthreads();
+        // Two copies of the pair loop, with and without the validity predicates, for the pair kernel's reason: the predicate's
+        // flat loads make the compiler wait for every outstanding load behind them -- the st2 prefetch included.
+        auto scan_tile = [&](auto ids_tag) {
+            constexpr bool IDS = decltype(ids_tag)::value;
+            int64_t id = 0;
+            bool live = true;
+            if constexpr (IDS) {
+                id = ids[off + jc];
+                live = id >= 0;   // bit 63 = kDelIdxMask, once per unit
+            }
+            // pair i: gathers from `cur`, pair i + 1's table from `sn` into `nxt`, pair i + 3's st2 entries requested into `sn`
+            auto pair_step = [&](int i, const float* cur, float* nxt, float (&sn)[NE]) {
+                float dis = pq4_lane_f(d0v, i);
+                const int64_t oo = (int64_t)(((uint64_t)(uint32_t)pq4_lane_i(oohi, i) << 32) | (uint32_t)pq4_lane_i(oolo, i));
+                bool ok = true;
+                if constexpr (IDS) ok = live && is_valid_doc(ftab[pq4_lane_i(fv, i)], id);
+                if constexpr (MT > 0) {
+                    float t[MT];
+#pragma unroll
+                    for (int m = 0; m < MT; m++) t[m] = cur[m * 16 + ((cw[m >> 3] >> (4 * (m & 7))) & 15u)];
+                    __builtin_amdgcn_sched_barrier(0);   // all gathers in flight before the table write and the add chain
+                    if (i + 1 < nt) write_lut(nxt, sn);
+                    if (i + 3 < nt) load_s2(i + 3, sn);
+#pragma unroll
+                    for (int m = 0; m < MT; m++) dis += t[m];   // sequential, reference order
+                } else {
+                    if (i + 1 < nt) write_lut(nxt, sn);
+                    if (i + 3 < nt) load_s2(i + 3, sn);
+#pragma unroll
+                    for (int w = 0; w < NW; w++) {
+                        if (8 * w >= Mr) break;
+#pragma unroll
+                        for (int b = 0; b < 8; b++)
+                            if (8 * w + b < Mr) dis += cur[(8 * w + b) * 16 + ((cw[w] >> (4 * b)) & 15u)];
+                    }
+                }
+                if (j < len) out[oo + tid] = ok ? dis : sentinel;
+                __syncthreads();   // pair i's gathers are over, pair i + 1's table is in place
+            };
+            for (int i = 0; i < nt; i += 2) {
+                pair_step(i, lut0, lut1, sb);
+                if (i + 1 < nt) pair_step(i + 1, lut1, lut0, sa);
+            }
+        };
+        if (need_ids) scan_tile(std::true_type{});
+        else scan_tile(std::false_type{});
+    }
+}
+
+void launch_ivfpq4_scan_lm(hipStream_t s, bool l2, int nq, int M, int P, const int* probe_list, const float* dis0,
+                           const float* st2, const float* T2, const int64_t* list_off, const int* list_len,
+                           const uint8_t* list_mask, int nlist, int max_list_len, const uint8_t* codes, const int64_t* ids,
+                           const int* pair_off, int64_t q_stride, float* out, const FilterDesc* ftab, const int* qfil,
+                           int need_ids, void* scratch) {
+    if (nq <= 0) return;
+    if (M <= 0 || M > 2 * kPq4MaxCodeSize || (l2 && !T2)) {
+        launch_refused("launch_ivfpq4_scan_lm: M beyond 128, or L2 without a table");
+        return;
+    }
+    // what the unit count cannot exceed: every probed list has at most one ragged tile per slab
+    const int64_t pairs = (int64_t)nq * std::max(0, P);
+    const int64_t slabs = ((int64_t)std::max(0, max_list_len) + kPq4LmSlab - 1) / kPq4LmSlab;
+    const int64_t ub = (pairs / kPq4LmQueryTile + std::min<int64_t>(pairs, std::max(0, nlist))) * slabs;
+    if (!scratch || list_mask || P <= 0 || nlist <= 0 || pairs > 2147483647 || ub > 2147483647) {
+        launch_refused("launch_ivfpq4_scan_lm: no scratch for the inverse index, a list mask, or nq x nprobe / units beyond 2^31 - 1");
+        return;
+    }
+    // inv [nq * P] | cnt | start | cur [nlist] | ustart [nlist + 1]  (ivfflat_lm_scratch_bytes)
+    int* inv = static_cast<int*>(scratch);
+    int* cnt = inv + (size_t)nq * P;
+    int* start = cnt + nlist;
+    int* cur = start + nlist;
+    int* ustart = cur + nlist;
+    const int npairs = (int)pairs;
+    (void)hipMemsetAsync(cnt, 0, (size_t)nlist * sizeof(int), s);
+    hipLaunchKernelGGL(k_inv_count, dim3((npairs + 255) / 256), dim3(256), 0, s, probe_list, npairs, nlist, list_len, cnt);
+    hipLaunchKernelGGL(k_inv_scan_p, dim3(1), dim3(1024), 0, s, cnt, list_len, nlist, start, cur, ustart);
+    hipLaunchKernelGGL(k_inv_fill, dim3((npairs + 255) / 256), dim3(256), 0, s, probe_list, npairs, nlist, list_len, start, cur, inv);
+    const size_t lds = pq4_lm_lds_bytes(M);
+    const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>(ub, PQ4_LM_GRID)));
+#define GH_PQ4LM(LL, MT)                                                                                                      \
+    hipLaunchKernelGGL((k_ivfpq4_scan_lm<LL, MT>), grid, dim3(256), lds, s, M, P, dis0, st2, T2, list_off, list_len, nlist,   \
+                       codes, ids, pair_off, q_stride, out, ftab, qfil, need_ids, LL ? INFINITY : -INFINITY, inv, start, cnt, \
+                       ustart)
+#define GH_PQ4LM_M(LL)                                  \
+    do {                                                \
+        switch (pq4_lm_mt(M)) {                         \
+            case 32: GH_PQ4LM(LL, 32); break;           \
+            case 16: GH_PQ4LM(LL, 16); break;           \
+            case 64: GH_PQ4LM(LL, 64); break;           \
+            case 8: GH_PQ4LM(LL, 8); break;             \
+            default: GH_PQ4LM(LL, 0); break;            \
+        }                                               \
+    } while (0)
+    if (l2) GH_PQ4LM_M(true);
+    else GH_PQ4LM_M(false);
+#undef GH_PQ4LM_M
+#undef GH_PQ4LM
 }
 
 }  // namespace gh

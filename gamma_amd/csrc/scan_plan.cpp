@@ -138,6 +138,9 @@ void scan_plan_passes(ScanPlan& pl, const ScanShape& sh, const ScanSwitches& sw,
     pl.cf_ok = pl.q8_ok = false;
     pl.PGM = pl.nsl = PGN;
     pl.cf_span = pl.c8 = 0;
+    // 4-bit codes list-major (pq4.hip): an opt-in of the handle, on the unbounded path -- the only one a
+    // 4-bit handle has (bound_eligible above).  Off: the launch sequence of the pair scan, no inverse index, no scratch.
+    pl.pq4_lm = sh.pq4 && sh.pq4_lm_switch && !bounded;
     if (!bounded) return;
     // Filter pass of the consumers (scan.hip, CF): needs the sums beside the arena the scan reads -- not the shadow arena of
     // a call running over lists compacted under its filter.  With it ONE consumer workgroup per query takes every probe

@@ -58,6 +58,7 @@ struct ScanShape {
     int max_list_len = 0;
     int64_t q_stride_cap = 0;       // > 0: the longest candidate row of the batch, measured (list shards)
     bool l2 = true, pq4 = false;
+    bool pq4_lm_switch = false;     // gamma_hip_ivfpq4_set_lm_scan: the handle's switch (off by default)
     int table_mode = 1;
     bool have_sums = false;         // the per-code sums and t2max exist beside the arena
     bool prefiltered = false, cmp_has_sums = false, cmp_by_clause = false;   // the call runs over lists compacted under its filter
@@ -81,6 +82,7 @@ struct ScanPlan {
     int c8 = 0, cf_span = 0;
     int PGM = 1, nsl = 1, cap = SCAN_SLICE;   // probe groups of the main launch, survivor slices per query, items per slice
     int need_ids = 0;
+    bool pq4_lm = false;            // the 4-bit scan runs list-major (k_ivfpq4_scan_lm) instead of k_ivfpq4_scan_pair
     int64_t q_stride = 0;
     // bounded: rq | ready[nq] | gcnt[nq][nsl] | fl inside w_scnt (rq, at offset 0: count + list of the queries that need the repair
     // launch, 8-byte aligned; fl: count + list of the queries k_select_final left to the unfiltered selection, flag = 1)

@@ -147,6 +147,15 @@ int HIPIVFPQModelParams::Parse(const char *str) {
     if (v > 0) opq_nsubvector = v;
   }
   if (ncentroids <= 0 || nsubvector <= 0 || nbits_per_idx <= 0) return -1;
+  // "pq4_lm_scan": 0 (the default) | 1: the 4-bit lists are scanned list-major, where the build has the switch (HIP only)
+  if (jp.Contains("pq4_lm_scan")) {
+    if (jp.GetInt("pq4_lm_scan", v) || (v != 0 && v != 1) || !FindHIPPq4Lm() || (v == 1 && nbits_per_idx != 4)) {
+      HLOG("invalid pq4_lm_scan (0 or 1; 1 only beside nbits_per_idx = 4, and only where this build of the plugin has the "
+           "list-major scan)");
+      return -1;
+    }
+    pq4_lm_scan = v == 1;
+  }
   return 0;
 }
 
@@ -255,6 +264,18 @@ int RegisterHIPRawSq8(const HIPRawSq8Ops *ops) {
 }
 const HIPRawSq8Ops *FindHIPRawSq8() { return RawSq8Ops(); }
 
+namespace {
+const HIPPq4LmOps *&Pq4LmOps() {
+  static const HIPPq4LmOps *ops = nullptr;
+  return ops;
+}
+}  // namespace
+int RegisterHIPPq4Lm(const HIPPq4LmOps *ops) {
+  Pq4LmOps() = ops;
+  return 0;
+}
+const HIPPq4LmOps *FindHIPPq4Lm() { return Pq4LmOps(); }
+
 int RegisterHIPListsInit(int nbits, HIPListsInitFn fn) {
   ListsInits().push_back({nbits, fn});
   return 0;
@@ -346,6 +367,7 @@ int GammaIVFPQHIPIndex::Init(const std::string &model_parameters, int indexing_s
     HLOG("device_filters with several devices is not supported (the columns live on one handle)");
     return -2;
   }
+  pq4_lm_ = pa.pq4_lm_scan ? FindHIPPq4Lm() : nullptr;
   if (const int krc = pa.CheckRawKeys()) return krc;   // "raw_placement" / "raw_dtype" against the devices and this build
   rawshard_ = pa.raw_sharded ? FindHIPRawShard() : nullptr;
   const HIPRawInitFn raw_init_f16 = pa.raw_f16 ? FindHIPRawInitF16() : nullptr;
@@ -363,6 +385,7 @@ int GammaIVFPQHIPIndex::Init(const std::string &model_parameters, int indexing_s
     if (!r) r = raw_sq8_ops ? raw_sq8_ops->init(m, d_) : raw_i8_ops ? raw_i8_ops->init(m, d_, pa.raw_i8 == 2) : raw_init_f16 ? raw_init_f16(m, d_) : gamma_hip_raw_init(m, d_);
     if (!r && rawshard_ && (raw_init_f16 || raw_i8_ops)) r = rawshard_->narrow_rows(m, 1);
     if (!r) r = gamma_hip_set_exact_ties(m, pa.exact_ties ? 1 : 0);
+    if (!r && pq4_lm_) r = pq4_lm_->set(m, 1);
     if (!r && pa.perf_stages) r = gamma_hip_profile_enable(m, 1);
     return r;
   });
@@ -836,6 +859,10 @@ int GammaIVFPQHIPIndex::UploadEngineBitmap() {
   return ForAll([&](gamma_hip_index *m) {
     return gamma_hip_bitmap_upload(m, reinterpret_cast<const uint8_t *>(rv->Bitmap()->Bitmap()), (int64_t)rv->Bitmap()->BitSize());
   });
+}
+
+int GammaIVFPQHIPIndex::Pq4LmStats(int64_t *calls, int64_t *pairs) {
+  return pq4_lm_ && h_ ? pq4_lm_->stats(h_, calls, nullptr, pairs) : -1;
 }
 
 int GammaIVFPQHIPIndex::SetTrained(const float *coarse, const float *pq) {

@@ -55,6 +55,16 @@ typedef int (*HIPListsInitFn)(gamma_hip_index *h, int d, int nlist, int M, int m
 int RegisterHIPListsInit(int nbits, HIPListsInitFn fn);
 HIPListsInitFn FindHIPListsInit(int nbits);
 
+// "pq4_lm_scan": 1 beside "nbits_per_idx": 4: the scan of the 4-bit lists runs list-major (the handle's switch
+// gamma_hip_ivfpq4_set_lm_scan and its counters), registered the same way by gamma_index_ivfpq4_lm_hip.cc -- the only host file
+// that names them.  Without that file, or without 4-bit codes, HIPIVFPQ::Init rejects the key.
+struct HIPPq4LmOps {
+  int (*set)(gamma_hip_index *h, int on);
+  int (*stats)(gamma_hip_index *h, int64_t *calls, int64_t *units, int64_t *pairs);
+};
+int RegisterHIPPq4Lm(const HIPPq4LmOps *ops);
+const HIPPq4LmOps *FindHIPPq4Lm();
+
 // "raw_placement": "sharded" (several devices, lists sharded): every raw row once, on the device that owns its list.  The ABI
 // entries that takes beyond those of the replicated mirror -- the group's placement switch and row routing, the store's clear --
 // are registered by gamma_index_ivfpq_rawshard_hip.cc at static-initialisation time (the idiom of RegisterHIPListsInit):
@@ -188,6 +198,8 @@ struct HIPIVFPQModelParams {
                                  // with "raw_placement": "sharded" only (as "float16").
   bool raw_sq8 = false;          // HIP only: "raw_dtype": "sq8" -- the device's raw rows are one scalar-quantised byte per element
                                  // (lossy; ranges = per-dimension minimum / maximum of the training rows).  One device only.
+  bool pq4_lm_scan = false;      // HIP only: "pq4_lm_scan": 1 -- with "nbits_per_idx": 4 the list scan runs list-major (large
+                                 // batches over many lists; same results).  Rejected without 4-bit codes.
   int Parse(const char *str);   // 0 ok, -1 bad (same rules as gamma_index_ivfpq.h:708-851)
   // "raw_placement" / "raw_dtype" against "devices" / "placement" and what this build of the plugin carries, as HIPIVFPQ::Init
   // decides it before a device is opened: 0 accepted, -2 rejected behind one log line
@@ -214,6 +226,8 @@ class GammaIVFPQHIPIndex : public RetrievalModel {
   int SetTrained(const float *coarse_centroids, const float *pq_centroids);
 
   // exposed for the harness / tests
+  // "pq4_lm_scan": 1: the list-major scan launches the handle has served and their (query, probe) pairs; -1: no such model
+  int Pq4LmStats(int64_t *calls, int64_t *pairs);
   int Sq8Ranges(float *vmin, float *vmax);   // "raw_dtype": "sq8": the store's ranges, d floats each; 1 has them, 0 not, -1 no sq8 model
   bool is_trained_ = false;
   int d_ = 0, nlist_ = 0, M_ = 0, nprobe_ = 80;
@@ -224,6 +238,7 @@ class GammaIVFPQHIPIndex : public RetrievalModel {
 
  protected:
   const HIPOpqOps *opq_ = nullptr;   // non-null: the model was created with "opq"
+  const HIPPq4LmOps *pq4_lm_ = nullptr;   // non-null: the model was created with "pq4_lm_scan": 1
   int opq_M_ = 0;
   int TrainOnHost(size_t num, const float *xt);
   int TrainCoarse(size_t num, const float *xt);

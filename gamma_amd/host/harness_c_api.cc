@@ -371,6 +371,11 @@ int gh_host_ivfpq_sq8_ranges(void *hp, float *vmin, float *vmax) {
   GammaIVFPQHIPIndex *m = dynamic_cast<GammaIVFPQHIPIndex *>(((Host *)hp)->model);
   return m ? m->Sq8Ranges(vmin, vmax) : -1;
 }
+// {launches, (query, probe) pairs} a HIPIVFPQ model's 4-bit list-major scan ("pq4_lm_scan": 1) has served; -1: no such model
+int gh_host_ivfpq4_lm_stats(void *hp, int64_t *out2) {
+  GammaIVFPQHIPIndex *m = dynamic_cast<GammaIVFPQHIPIndex *>(((Host *)hp)->model);
+  return m ? m->Pq4LmStats(&out2[0], &out2[1]) : -1;
+}
 // query chunks a HIPIVFFLAT model's list-major scan of row lengths that are no multiple of 16 has served; -1 otherwise
 int64_t gh_host_ivfflat_lm_tail_chunks(void *hp) {
   GammaIVFFlatHIPIndex *m = dynamic_cast<GammaIVFFlatHIPIndex *>(((Host *)hp)->model);

@@ -474,6 +474,24 @@ int gamma_hip_ivfpq_init(gamma_hip_index* h, int d, int nlist, int M, int nbits,
  * (gamma_hip_group_*) stays 8-bit.  gamma_hip_ivfpq_init keeps refusing nbits != 8. */
 int gamma_hip_ivfpq4_init(gamma_hip_index* h, int d, int nlist, int M, int metric, int bucket_init_size,
                           int bucket_max_size);
+/* The scan of a 4-bit handle list-major, a switch that is off by default: the inverted-list scan of
+ * the reference's 4-bit scanner (gamma_index_ivfpq.h:540-601) with the work turned around -- a workgroup keeps a slab of a
+ * LIST's codes and the list's precomputed-table row in registers and runs a tile of the (query, probe) pairs that probe the
+ * list past them, instead of one workgroup per (query, probe group).  Meant for large batches over many lists.  Every ADC
+ * distance, and with it every result and the order inside ties, is the same bit for bit; with the switch off nothing changes,
+ * no inverse index is built and no workspace is taken.  GAMMA_HIP_EUNSUPPORTED with a message on a handle that is not 4-bit. */
+int gamma_hip_ivfpq4_set_lm_scan(gamma_hip_index* h, int on);
+/* the switch as set (0 on a handle that is not 4-bit) */
+int gamma_hip_ivfpq4_lm_scan(const gamma_hip_index* h);
+/* the list-major scan's shape for M sub-quantizers (gamma_index_ivfpq.h:540-601 is the scan it answers for), no handle, no
+ * device call: *mt = the kernel instantiation (M itself for 8 / 16 / 32 / 64: dword code loads; 0: any other M up to 128, byte
+ * loads), *qt = the (query, probe) pairs of a work unit, *lds_bytes = the LDS of a workgroup (two tables of M x 16 floats).
+ * Any pointer may be NULL.  M < 1 or M > 128: GAMMA_HIP_EINVAL. */
+int gamma_hip_ivfpq4_lm_shape(int M, int* mt, int* qt, int64_t* lds_bytes);
+/* the list-major launches (gamma_index_ivfpq.h:540-601 scans served that way) since init: *calls = scan launches, *pairs =
+ * their (query, probe) pairs, nq x nprobe each, both counted on the host.  *units = -1: the unit total of a launch stays on
+ * the device -- the search reads nothing back for it and this entry adds no synchronisation.  Any pointer may be NULL. */
+int gamma_hip_ivfpq4_lm_stats(gamma_hip_index* h, int64_t* calls, int64_t* units, int64_t* pairs);
 /* ---- OPQ rotation ("opq": {"nsubvector": N} of the reference's IVFPQ model) ---------------------------------------
  * Replaces faiss::OPQMatrix* opq_ as GammaIVFPQIndex uses it (index/impl/gamma_index_ivfpq.h:745, gamma_index_ivfpq.cc:
  * 155-166): every vector is rotated before the coarse quantizer and the PQ encoder (Add :424-512, Update :375-422), every

@@ -5,7 +5,12 @@ call; gamma_hip_set_scan_bound_feedback only stops the handle from backing off),
 bytes through the same plain path.
 Prints one JSON line (and writes it to --out): queries/s, microseconds per stage (the handle's stage events), code bytes
 per second of the scan, recall@10 against the flat search.
-    python tools/pq4_bench.py [--n 1000000] [--steps 10] [--warmup 3] [--out profiles/pq4_p4_bench.json]"""
+    python tools/pq4_bench.py [--n 1000000] [--steps 10] [--warmup 3] [--out profiles/pq4_p4_bench.json]
+--lm-scan: the 4-bit leg alone, ONE handle in one process, the list-major scan (gamma_hip_ivfpq4_set_lm_scan) off and on
+alternated call by call after the warm-up of both; per setting the wall time of the call and every stage's time as median and
+[min, max] over the steps -- the spread of one setting stands beside the difference between the two -- and whether the two
+settings answered with equal bytes.
+    python tools/pq4_bench.py --lm-scan [--nlist 256 --nq 2048] [--out profiles/pq4_lm_p4.json]"""
 import argparse
 import json
 import os
@@ -91,6 +96,61 @@ def run_leg(a, bits, M, base, q, flat_I):
     return out
 
 
+def run_lm(a, M, base, q):
+    import torch
+
+    from gamma_amd import api
+    g = api.GammaHip(0)
+    d = base.shape[1]
+    g.ivfpq4_init(d, a.nlist, M, api.METRIC_L2, bucket_init_size=max(1000, a.n // a.nlist))
+    cc, pq = g.ivfpq_train(base[:min(a.n, a.nlist * 64)], a.nlist, M)
+    g.ivfpq_set_trained(cc, pq, None)
+    g.raw_init(d)
+    g.raw_append(base)
+    for i0 in range(0, a.n, 1 << 18):
+        g.add(base[i0:i0 + (1 << 18)], i0)
+    k = 10
+    args = api.SearchArgs(metric=api.METRIC_L2, nprobe=a.nprobe, recall_num=a.recall_num, has_rank=True,
+                          min_score=-3e38, max_score=3e38)
+    dx = torch.from_numpy(q).cuda()
+    dD = torch.empty((a.nq, k), dtype=torch.float32, device="cuda")
+    dI = torch.empty((a.nq, k), dtype=torch.int64, device="cuda")
+
+    def call(on):
+        g.ivfpq4_set_lm_scan(on)
+        g.profile_reset()
+        t0 = time.perf_counter()
+        g.ivfpq_search_device(dx.data_ptr(), a.nq, k, args, dD.data_ptr(), dI.data_ptr())
+        g.synchronize()
+        wall = (time.perf_counter() - t0) * 1e3
+        prof = g.profile()
+        st = {name: v[0] * 1e3 for name, v in prof.items() if isinstance(v, (tuple, list)) and len(v) >= 2 and v[1]}
+        return wall, st
+
+    g.profile_enable(1)
+    for _ in range(a.warmup):
+        call(0)
+        call(1)
+    answers = {}
+    samples = {0: [], 1: []}
+    for _ in range(a.steps):
+        for on in (0, 1):
+            samples[on].append(call(on))
+            answers[on] = (dD.cpu().numpy().tobytes(), dI.cpu().numpy().tobytes())
+
+    def spread(v):
+        return {"median": round(float(np.median(v)), 1), "min_max": [round(min(v), 1), round(max(v), 1)]}
+
+    out = {"M": M, "code_size": g.code_size(), "lm_shape": list(api.ivfpq4_lm_shape(M)), "equal_bytes": answers[0] == answers[1],
+           "lm_stats_calls_units_pairs": list(g.ivfpq4_lm_stats()), "ties_not_honoured": g.ties_not_honoured()}
+    for on, name in ((0, "pair"), (1, "list_major")):
+        walls = [w * 1e3 for w, _ in samples[on]]
+        out[name] = {"call_us": spread(walls),
+                     "stage_us": {s: spread([st.get(s, 0.0) for _, st in samples[on]]) for s in samples[on][0][1]}}
+    g.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1000000)
@@ -103,10 +163,20 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--legs", default="4,8")
     ap.add_argument("--out", default="")
+    ap.add_argument("--lm-scan", action="store_true", help="the 4-bit leg with the list-major scan off / on, alternated")
     a = ap.parse_args()
     from gamma_amd import api, synth
     base = synth.sift_like(a.n, d=a.d, seed=1234)
     q = synth.sift_like(a.nq, d=a.d, seed=4321)
+    if a.lm_scan:
+        res = {"workload": "P4 list-major scan off / on", "n": a.n, "d": a.d, "nlist": a.nlist, "nprobe": a.nprobe,
+               "recall_num": a.recall_num, "nq": a.nq, "k": 10, "steps": a.steps, "pq4": run_lm(a, 32, base, q)}
+        line = json.dumps(res)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        print(line)
+        return
     # the exact neighbours of the first queries (flat search on the device)
     g = api.GammaHip(0)
     g.raw_init(a.d)
