@@ -256,6 +256,13 @@ class GammaHip:
                  "ivfpq4_init")
         self.d, self.nlist, self.M, self.ksub = d, nlist, M, 16
 
+    def ivfpq_wide_init(self, d, nlist, M, metric=METRIC_L2, bucket_init_size=1000, bucket_max_size=1280000):
+        """8-bit PQ codes of 65 .. 256 sub-quantizers: ksub = 256, code_size = M; the ivfpq_* methods serve the handle
+        afterwards, the search through the sliced-table scan (include/gamma_hip.h, DESIGN.md "Wide PQ")"""
+        self._ck(self.L.gamma_hip_ivfpq_wide_init(self.h, d, nlist, M, metric, bucket_init_size, bucket_max_size),
+                 "ivfpq_wide_init")
+        self.d, self.nlist, self.M = d, nlist, M
+
     def ivfpq4_set_lm_scan(self, on):
         """the scan of a 4-bit handle list-major: a slab of a list's codes in registers, a tile of the
         (query, probe) pairs that probe the list run past them.  Off by default; the answer is the same bit for bit."""
@@ -1163,6 +1170,18 @@ def binivf_scan_shape():
     if rc != 0:
         raise _lib.GammaHipError("binivf_scan_shape: %d" % rc)
     return int(c.value), int(a.value)
+
+
+def ivfpq_wide_shape(M):
+    """(slice_width, slices, lds_bytes, tile_codes) of the wide scan (ivfpq_wide_init) for M sub-quantizers: the sub-quantizers
+    of one LDS table slice, the slices (the last may be shorter), the LDS of a workgroup, and the codes of a tile -- a longer
+    list parks its running sums in the distance slab between slices.  No device call."""
+    out = (C.c_int * 3)()
+    L = _lib.load()
+    rc = L.gamma_hip_ivfpq_wide_shape(int(M), out)
+    if rc != 0:
+        raise _lib.GammaHipError("ivfpq_wide_shape: %d" % rc)
+    return int(out[0]), int(out[1]), int(out[2]), int(L.gamma_hip_ivfpq_wide_tile_codes())
 
 
 def ivfpq4_lm_shape(M):

@@ -486,6 +486,16 @@ int gamma_hip_ivfpq4_lm_shape(int M, int* mt, int* qt, int64_t* lds_bytes) {
 }
 
 // host counters only: the unit total of a launch stays on the device (no read-back, no synchronisation)
+// the sliced-table scan of a wide handle (pqwide.hip): no handle, no device call
+int gamma_hip_ivfpq_wide_shape(int M, int* out3) {
+    if (M <= gh::kWideMinM || M > gh::kWideMaxM || !out3) return GAMMA_HIP_EINVAL;
+    out3[0] = gh::kWideMS;
+    out3[1] = gh::wide_slices(M);
+    out3[2] = (int)gh::wide_lds_bytes();
+    return GAMMA_HIP_OK;
+}
+int gamma_hip_ivfpq_wide_tile_codes(void) { return gh::wide_tile_codes(); }
+
 int gamma_hip_ivfpq4_lm_stats(gamma_hip_index* h, int64_t* calls, int64_t* units, int64_t* pairs) {
     if (!h) return GAMMA_HIP_EINVAL;
     SearchLock lk(h);

@@ -428,6 +428,8 @@ struct gamma_hip_index {
     // gamma_hip_ivfpq4_set_lm_scan: the scan of a 4-bit handle runs list-major (pq4.hip k_ivfpq4_scan_lm); the launches it
     // served and their (query, probe) pairs since init, counted on the host
     bool pq4_lm_on = false;
+    // gamma_hip_ivfpq_wide_init: 8-bit codes of 65 .. 256 sub-quantizers -- one search path, the sliced-table scan of pqwide.hip
+    bool wide = false;
     int64_t pq4_lm_calls = 0, pq4_lm_pairs = 0;
     // gamma_hip_binflat_init (gamma_hip_binflat.cpp): every code in vid order for the exact Hamming search, rows of bf_cs
     // bytes; bf_count is published after the rows it counts are in place; {queries, candidates, heap admissions} counters

@@ -19,6 +19,7 @@ int gamma_hip_opq_set(gamma_hip_index* h, const float* A) {
     if (h->binivf) return fail(h, GAMMA_HIP_EUNSUPPORTED, "opq_set: a binary IVF handle has no rotation");
     if (h->ivfflat) return fail(h, GAMMA_HIP_EUNSUPPORTED, "opq_set: an IVFFLAT handle has no rotation");
     if (h->ksub == gh::kPq4Ksub) return fail(h, GAMMA_HIP_EUNSUPPORTED, "opq_set: OPQ with 4-bit codes is not supported");
+    if (h->wide) return fail(h, GAMMA_HIP_EUNSUPPORTED, "opq_set: OPQ on a wide handle (gamma_hip_ivfpq_wide_init) is not supported");
     if (h->group_member) return fail(h, GAMMA_HIP_EUNSUPPORTED, "opq_set: OPQ on a member of a group is not supported");
     if (!h->h_list_mask.empty()) return fail(h, GAMMA_HIP_EUNSUPPORTED, "opq_set: OPQ on a list shard is not supported");
     if (!A) return fail(h, GAMMA_HIP_EINVAL, "opq_set: null matrix");

@@ -290,6 +290,7 @@ static gh::ScanShape scan_shape(const H* h, const gamma_hip_search_params* p, co
     sh.l2 = p->metric == GAMMA_HIP_METRIC_L2;
     sh.pq4 = h->ksub == gh::kPq4Ksub;
     sh.pq4_lm_switch = h->pq4_lm_on;
+    sh.wide = h->wide;
     sh.table_mode = h->table_mode;
     sh.have_sums = h->d_sums && h->d_t2max;
     sh.prefiltered = h->prefiltered;
@@ -424,6 +425,8 @@ int ivfpq_stage_a(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int
     // passes (cf, c8, q8) are 8-bit kernels and the plan gates them off
     const bool pq4 = h->ksub == gh::kPq4Ksub;
     if (pq4 && (shard || bx)) return pq4_refuse(h, "a list-shard search");
+    // a wide handle (pqwide.hip) likewise: launch_pq_ip_table, pair offsets, k_ivfpq_scan_wide unbounded, the unfiltered selection
+    if (h->wide && (shard || bx)) return wide_refuse(h, "a list-shard search");
     hipStream_t s = h->stream;
     // this call reads the lists through the version of their (offset, length) tables that is current now:
     // behind the writer's copies (ver_ev), and the version is not reused before the kernels below are done (rd_ev)
@@ -588,6 +591,10 @@ int ivfpq_stage_a(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int
                 gh::launch_ivfpq4_scan_pair(s, l2, nq, M, P, h->w_probe.as<int>(), dis0, h->w_st2.as<float>(), h->d_T2, h->d_list_off,
                                             h->d_list_len, h->d_list_mask, nlist, h->d_codes, h->d_ids, h->w_pair_off.as<int>(),
                                             q_stride, h->w_dist.as<float>(), fc.d_tab, fc.d_qf, pl.need_ids, qperm, G, PGN);
+            else if (h->wide)
+                gh::launch_ivfpq_scan_wide(s, l2, nq, M, P, h->w_probe.as<int>(), dis0, h->w_st2.as<float>(), h->d_T2, h->d_list_off,
+                                           h->d_list_len, h->d_list_mask, nlist, h->d_codes, h->d_ids, h->w_pair_off.as<int>(),
+                                           q_stride, h->w_dist.as<float>(), fc.d_tab, fc.d_qf, pl.need_ids, qperm, G, PGN);
             else
                 scan(0, PGN, shard ? 1 : 0, nullptr, pqc);
         }
@@ -906,8 +913,8 @@ bool ivfpq_small_ok(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, i
     constexpr int max_nq = 512;   // (the section's header: the measured cross-over with the regular chain is ~1000)
     // exact coarse distances (faiss below 20 queries) come from the fused first kernel, which covers 16 queries; the
     // GEMM form (20 queries and more) from the regular matrix kernel
-    // (a 4-bit handle takes the regular chain: the small path's fused kernels are 8-bit)
-    return !off && h->ksub == 256 && h->small_path && nq >= 1 && nq <= max_nq &&
+    // (a 4-bit handle takes the regular chain: the small path's fused kernels are 8-bit; a wide one too: their scan holds a whole table)
+    return !off && h->ksub == 256 && !h->wide && h->small_path && nq >= 1 && nq <= max_nq &&
            p->nprobe <= 128 && R <= 1024 && !h->profile && !fc.d_qf && !h->d_list_mask &&
            h->nlist <= 16384 &&
            (int64_t)p->nprobe * std::max(1, h->max_list_len) <= (1 << 22) &&
@@ -1056,10 +1063,16 @@ int coarse_chunk(H* h, int nq) {
     const int64_t by_mat = (int64_t)(h->dist_budget_bytes / ((size_t)h->nlist * sizeof(float)));
     return (int)std::max<int64_t>(1, std::min<int64_t>(by_mat, nq));
 }
+// a wide handle's query tables are M KB per query (2 GB at 16384 queries and M = 128), beside a slab of ~100 KB per query: the
+// sub-batch is sized by them too, at most kWideTableBytes of tables in one piece (any other handle: no limit from here)
+static constexpr int64_t kWideTableBytes = (int64_t)1 << 30;
+static int64_t wide_table_chunk(const H* h) {
+    return h->wide ? std::max<int64_t>(1, kWideTableBytes / ((int64_t)h->M * 256 * (int64_t)sizeof(float))) : INT64_MAX;
+}
 int scan_chunk(H* h, int nq, int P) {
     const int64_t q_stride = std::max<int64_t>(1, (int64_t)P * std::max(1, h->max_list_len));
     const int64_t by_dist = (int64_t)(h->dist_budget_bytes / (q_stride * sizeof(float)));
-    return (int)std::max<int64_t>(1, std::min<int64_t>(by_dist, nq));
+    return (int)std::max<int64_t>(1, std::min<int64_t>(std::min(by_dist, wide_table_chunk(h)), nq));
 }
 int query_chunk(H* h, int nq, int P) { return std::min(coarse_chunk(h, nq), scan_chunk(h, nq, P)); }
 
@@ -1191,7 +1204,7 @@ int ivfpq_search_device_locked(H* h, const gamma_hip_search_params* p, int nq, c
             GH_CHECK(h, hipStreamSynchronize(h->stream));
             h->q_stride_cap = (std::max<int64_t>(mx[0], 1) + 3) & ~(int64_t)3;
             const int64_t by_dist = (int64_t)(h->dist_budget_bytes / ((size_t)h->q_stride_cap * sizeof(float)));
-            chunk = (int)std::max<int64_t>(chunk, std::min<int64_t>(by_dist, nq));
+            chunk = (int)std::max<int64_t>(chunk, std::min<int64_t>(std::min(by_dist, wide_table_chunk(h)), nq));
         }
     }
     // a call of several chunks: the tie replay of chunk i runs on its own stream beside chunk i + 1 (what

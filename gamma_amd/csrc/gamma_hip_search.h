@@ -78,10 +78,16 @@ static inline int opq_refuse(H* h, const char* what) {
     h->err = std::string("handle with an OPQ matrix: ") + what + " is not supported";
     return GAMMA_HIP_EUNSUPPORTED;
 }
-// (every entry point that refuses the one refuses the other: the shard, merge and export entries)
+// a wide handle (gamma_hip_ivfpq_wide_init) behind an entry point whose kernels hold a whole table in LDS: never silent
+static inline int wide_refuse(H* h, const char* what) {
+    h->err = std::string("wide handle: ") + what + " is nsubvector <= 64 only";
+    return GAMMA_HIP_EUNSUPPORTED;
+}
+// (every entry point that refuses the one refuses the others: the shard, merge and export entries)
 #define GH_NO_PQ4(h, what)                                                \
     do {                                                                  \
         if ((h)->ksub == gh::kPq4Ksub) return pq4_refuse((h), (what));    \
+        if ((h)->wide) return wide_refuse((h), (what));                   \
         if ((h)->d_opq) return opq_refuse((h), (what));                   \
     } while (0)
 

@@ -1131,6 +1131,26 @@ int gamma_hip_ivfpq4_init(gamma_hip_index* h, int d, int nlist, int M, int metri
     return rc;
 }
 
+// 8-bit codes of more sub-quantizers than one LDS table holds (pq.M = ivfpq_param.nsubvector, gamma_index_ivfpq.cc:167-170,
+// takes any M): the scan keeps the table in LDS a slice at a time (pqwide.hip)
+int gamma_hip_ivfpq_wide_init(gamma_hip_index* h, int d, int nlist, int M, int metric, int bucket_init_size,
+                              int bucket_max_size) {
+    if (!h) return GAMMA_HIP_EINVAL;
+    WriteLock lk(h);
+    if (h->ivf_init) return fail(h, GAMMA_HIP_EINVAL, "already initialised");
+    if (h->group_member) return fail(h, GAMMA_HIP_EUNSUPPORTED, "wide handle: a member of a group (gamma_hip_group_*) is nsubvector <= 64 only");
+    if (d <= 0 || nlist <= 0) return fail(h, GAMMA_HIP_EINVAL, "bad d/nlist/M");
+    if (M <= gh::kWideMinM || M > gh::kWideMaxM) return fail(h, GAMMA_HIP_EINVAL, "ivfpq_wide_init: nsubvector must be 65 .. 256 (gamma_hip_ivfpq_init serves up to 64)");
+    if (d % M != 0) return fail(h, GAMMA_HIP_EINVAL, "d must be divisible by nsubvector");
+    if (d / M > 64) return fail(h, GAMMA_HIP_EINVAL, "dsub > 64 unsupported");
+    if ((int64_t)nlist * M * 256 * (int64_t)sizeof(float) > g_table_max_bytes.load())
+        return fail(h, GAMMA_HIP_EUNSUPPORTED, "wide handle: the precomputed table would exceed precomputed_table_max_bytes (table mode 0 is nsubvector <= 64 only)");
+    h->wide = true;
+    const int rc = ivf_init_locked(h, d, nlist, M, metric, bucket_init_size, bucket_max_size, false);
+    if (rc != GAMMA_HIP_OK) h->wide = false;
+    return rc;
+}
+
 // binary: the binary IVF model -- no float centroids, PQ codebooks or tables (gamma_hip_binivf_init)
 static int ivf_init_locked(gamma_hip_index* h, int d, int nlist, int M, int metric, int bucket_init_size,
                            int bucket_max_size, bool flat, bool binary) {
@@ -1143,7 +1163,8 @@ static int ivf_init_locked(gamma_hip_index* h, int d, int nlist, int M, int metr
     const int ksub = h->ksub;   // 256, or 16 on a 4-bit handle (gamma_hip_ivfpq4_init, which has ruled table mode 0 out)
     h->table_mode = (!flat && (int64_t)nlist * M * ksub * (int64_t)sizeof(float) > g_table_max_bytes.load()) ? 0 : 1;
     // (4-bit: no code sums -- the passes built on them, cf / c8 / q8, are 8-bit kernels)
-    h->keep_sums = !flat && ksub == 256 && h->table_mode == 1 && getenv("GAMMA_HIP_NO_CODE_SUMS") == nullptr;
+    // (a wide handle neither: the same passes are kernels for M <= 64)
+    h->keep_sums = !flat && ksub == 256 && !h->wide && h->table_mode == 1 && getenv("GAMMA_HIP_NO_CODE_SUMS") == nullptr;
     h->d = d;
     h->nlist = nlist;
     h->M = M;
@@ -1651,6 +1672,7 @@ int gamma_hip_ivfpq_set_list_mask(gamma_hip_index* h, const uint8_t* owned) {
     WriteLock lk(h);
     if (!h->ivf_init) return fail(h, GAMMA_HIP_EINVAL, "ivfpq not initialised");
     if (h->ksub == gh::kPq4Ksub) return fail(h, GAMMA_HIP_EUNSUPPORTED, "4-bit handle: list shards (gamma_hip_ivfpq_set_list_mask) are 8-bit only");
+    if (h->wide) return fail(h, GAMMA_HIP_EUNSUPPORTED, "wide handle: list shards (gamma_hip_ivfpq_set_list_mask) are nsubvector <= 64 only");
     if (h->d_opq) return fail(h, GAMMA_HIP_EUNSUPPORTED, "handle with an OPQ matrix: list shards (gamma_hip_ivfpq_set_list_mask) are not supported");
     GH_CHECK(h, hipSetDevice(h->device));
     GH_CHECK(h, lk.exclusive());

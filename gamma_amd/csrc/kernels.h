@@ -615,4 +615,22 @@ void launch_centroid_update(hipStream_t s, const float* x, int d, const int* ord
 void launch_pq_encode(hipStream_t s, const float* x, int64_t n, int d, int M, const int* assign,
                       const float* cc, const float* pqc, uint8_t* codes);
 
+// ---- the list scan of a wide 8-bit handle (gamma_hip_ivfpq_wide_init, pqwide.hip): kWideMinM < M <= kWideMaxM ----
+// The pair's table (M KB) goes through LDS in slices of kWideMS sub-quantizers; a lane owns kWideU codes of a tile of
+// 256 x kWideU codes.  Both measured (DESIGN.md "Wide PQ").
+constexpr int kWideMinM = 64, kWideMaxM = 256;
+constexpr int kWideMS = 32;
+constexpr int kWideU = 2;
+inline int wide_slices(int M) { return (M + kWideMS - 1) / kWideMS; }
+inline size_t wide_lds_bytes() { return (size_t)kWideMS * 256 * sizeof(float); }
+inline int wide_tile_codes() { return 256 * kWideU; }
+// what the plain path of launch_ivfpq_scan_pair leaves in the ADC slab, bit for bit (dis = dis0, then += lut[m][code[m]] for
+// m ascending), every distance at out + q * q_stride + pair_off[q][p] + j, rejected entries as the sentinel; st2 [nq][M][256]
+// (launch_pq_ip_table), T2 [nlist][M][256], dis0 [nq][P]: the coarse distance (L2) or <x, centroid> (inner product)
+void launch_ivfpq_scan_wide(hipStream_t s, bool l2, int nq, int M, int P, const int* probe_list, const float* dis0,
+                            const float* st2, const float* T2, const int64_t* list_off, const int* list_len,
+                            const uint8_t* list_mask, int nlist, const uint8_t* codes, const int64_t* ids,
+                            const int* pair_off, int64_t q_stride, float* out, const FilterDesc* ftab, const int* qfil,
+                            int need_ids, const int* qperm, int G, int pg_cnt);
+
 }  // namespace gh

@@ -72,7 +72,7 @@ ScanPlan scan_plan_groups(const ScanShape& sh, const ScanSwitches& sw) {
     int G0 = (mean_len <= 700.0 && P <= 64) ? 8 : 4;
     // (with the byte-table filter pass a consumer probe costs a third of a producer's: five probes bound nearly as well as
     //  eight -- C3: scan 729 us at 8, 691 at 6, 676 at 5, 671 at 4 but with queries whose slices overflow; GAMMA_HIP_SCAN_G to sweep)
-    pl.c8_shape = !sh.pq4 && !sw.no_c8 && sh.l2 && M == 16 && R <= cf_maxr && sh.have_sums;
+    pl.c8_shape = !sh.pq4 && !sh.wide && !sw.no_c8 && sh.l2 && M == 16 && R <= cf_maxr && sh.have_sums;
     if (G0 == 8 && pl.c8_shape && P > 8) G0 = 5;
     pl.t2_bytes = (int64_t)sh.nlist * M * (sh.pq4 ? 16 : 256) * (int64_t)sizeof(float);
     if (sh.two_phase) {
@@ -108,7 +108,7 @@ ScanPlan scan_plan_groups(const ScanShape& sh, const ScanSwitches& sw) {
     // (recall_num up to 1024 since round 5: slices of 2048 items and k_select_final_wg beyond 256 -- the configurations that
     //  need a long short-list, full-size C5 at ~1000, keep the pre-filter)
     constexpr int scan_gmin = 4, bound_maxr = 1024;
-    pl.bound_eligible = !sh.pq4 && (!sh.shard || sh.compacted) && sh.scan_bound && R <= bound_maxr && P <= 128 &&
+    pl.bound_eligible = !sh.pq4 && !sh.wide && (!sh.shard || sh.compacted) && sh.scan_bound && R <= bound_maxr && P <= 128 &&
                         pl.G >= (sh.two_phase ? 1 : scan_gmin);
     return pl;
 }
@@ -122,8 +122,9 @@ void scan_plan_passes(ScanPlan& pl, const ScanShape& sh, const ScanSwitches& sw,
     pl.need_ids = (!sh.prefiltered && (sh.any_clause || sh.rejects)) ? 1 : 0;
     // L2 table mode 0 (no precomputed table, H::table_mode): per-list tables from the residual (scan.hip RES) -- the plain and
     // the bounded loop; no query table, none of the passes built on T2 sums (the sums are absent: cf / c8 / q8 are off by their own gates)
-    pl.res = !sh.pq4 && sh.l2 && sh.table_mode == 0;
-    pl.fuse_ip = !sh.pq4 && bounded && !pl.res && PGN == 1 && (M == 16 || M == 32) && !sw.no_fused_ip;
+    // (a wide handle, gamma_hip_ivfpq_wide_init, like a 4-bit one: one unbounded path, no residual or fused tables)
+    pl.res = !sh.pq4 && !sh.wide && sh.l2 && sh.table_mode == 0;
+    pl.fuse_ip = !sh.pq4 && !sh.wide && bounded && !pl.res && PGN == 1 && (M == 16 || M == 32) && !sw.no_fused_ip;
     // (byte-table filter pass: a first group of a few probes bounds loosely for some queries -- slices of 2048 keep them out of the
     //  unfiltered path; never beyond 2048: the selection and the tie replay hold one slice in LDS)
     pl.cap = scan_slice_cap(R);

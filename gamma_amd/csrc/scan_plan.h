@@ -58,6 +58,7 @@ struct ScanShape {
     int max_list_len = 0;
     int64_t q_stride_cap = 0;       // > 0: the longest candidate row of the batch, measured (list shards)
     bool l2 = true, pq4 = false;
+    bool wide = false;              // gamma_hip_ivfpq_wide_init: 65 .. 256 sub-quantizers, the sliced-table scan (pqwide.hip) unbounded
     bool pq4_lm_switch = false;     // gamma_hip_ivfpq4_set_lm_scan: the handle's switch (off by default)
     int table_mode = 1;
     bool have_sums = false;         // the per-code sums and t2max exist beside the arena

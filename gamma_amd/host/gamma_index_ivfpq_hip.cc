@@ -287,6 +287,18 @@ HIPListsInitFn FindHIPListsInit(int nbits) {
   return nullptr;
 }
 
+namespace {
+HIPListsInitFn &WideInit() {
+  static HIPListsInitFn fn = nullptr;
+  return fn;
+}
+}  // namespace
+int RegisterHIPWideInit(HIPListsInitFn fn) {
+  WideInit() = fn;
+  return 0;
+}
+HIPListsInitFn FindHIPWideInit() { return WideInit(); }
+
 GammaIVFPQHIPIndex::GammaIVFPQHIPIndex() {}
 
 GammaIVFPQHIPIndex::~GammaIVFPQHIPIndex() {
@@ -336,7 +348,21 @@ int GammaIVFPQHIPIndex::Init(const std::string &model_parameters, int indexing_s
     return -2;
   }
   // nbits_per_idx other than 8: through a registered lists initialiser (4: gamma_index_ivfpq4_hip.cc), else rejected
-  const HIPListsInitFn lists_init = pa.nbits_per_idx == 8 ? nullptr : FindHIPListsInit(pa.nbits_per_idx);
+  // 8 bits with "nsubvector" beyond 64: through the wide initialiser (gamma_index_ivfpq_wide_hip.cc) where this build has it
+  const HIPListsInitFn wide_init = (pa.nbits_per_idx == 8 && pa.nsubvector > 64) ? FindHIPWideInit() : nullptr;
+  if (wide_init && pa.devices.size() > 1) {
+    HLOG("nsubvector = %d with several devices is not supported (the group of handles is nsubvector <= 64 only)", pa.nsubvector);
+    return -2;
+  }
+  if (wide_init && pa.has_opq) {
+    HLOG("nsubvector = %d with opq is not supported", pa.nsubvector);
+    return -2;
+  }
+  if (pa.nbits_per_idx == 4 && pa.nsubvector > 128) {
+    HLOG("nsubvector = %d with nbits_per_idx = 4 is not supported (4-bit codes: nsubvector <= 128)", pa.nsubvector);
+    return -2;
+  }
+  const HIPListsInitFn lists_init = wide_init ? wide_init : pa.nbits_per_idx == 8 ? nullptr : FindHIPListsInit(pa.nbits_per_idx);
   opq_ = pa.has_opq ? FindHIPOpq() : nullptr;
   if (pa.has_hnsw || (pa.has_opq && !opq_) || pa.support_indivisible_nsubvector || (pa.nbits_per_idx != 8 && !lists_init)) {
     HLOG("hnsw / padded dimensions / nbits_per_idx other than 8 and 4%s are not supported by HIPIVFPQ",

@@ -54,6 +54,11 @@ typedef int (*HIPListsInitFn)(gamma_hip_index *h, int d, int nlist, int M, int m
                               int bucket_max_size);
 int RegisterHIPListsInit(int nbits, HIPListsInitFn fn);
 HIPListsInitFn FindHIPListsInit(int nbits);
+// Lists initialiser of an 8-bit index with "nsubvector" beyond 64 (gamma_hip_ivfpq_wide_init), registered the same way by
+// gamma_index_ivfpq_wide_hip.cc -- the only host file that names the entry.  A build of the plugin without that file has
+// none, and HIPIVFPQ::Init hands the value to gamma_hip_ivfpq_init, which rejects it.
+int RegisterHIPWideInit(HIPListsInitFn fn);
+HIPListsInitFn FindHIPWideInit();
 
 // "pq4_lm_scan": 1 beside "nbits_per_idx": 4: the scan of the 4-bit lists runs list-major (the handle's switch
 // gamma_hip_ivfpq4_set_lm_scan and its counters), registered the same way by gamma_index_ivfpq4_lm_hip.cc -- the only host file

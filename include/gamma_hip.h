@@ -474,6 +474,26 @@ int gamma_hip_ivfpq_init(gamma_hip_index* h, int d, int nlist, int M, int nbits,
  * (gamma_hip_group_*) stays 8-bit.  gamma_hip_ivfpq_init keeps refusing nbits != 8. */
 int gamma_hip_ivfpq4_init(gamma_hip_index* h, int d, int nlist, int M, int metric, int bucket_init_size,
                           int bucket_max_size);
+/* 8-bit PQ codes of 65 .. 256 sub-quantizers ("wide").  Replaces GammaIVFPQIndex::Init for nsubvector > 64 (pq.M =
+ * ivfpq_param.nsubvector, gamma_index_ivfpq.cc:167-170, takes any M; the scan it answers for is gamma_index_ivfpq.h:540-601):
+ * ksub = 256, code_size = M.  GAMMA_HIP_EINVAL when M is outside 65 .. 256, d % M != 0 or d / M > 64.  After this init the
+ * entry points of an 8-bit handle serve the handle: _set_trained, _get_precomputed_table, _train, _add, _encode, _encode_each,
+ * _update_batch, _apply_updates, _add_keys(_batch), _get_list, _code_size, _delete, _compact_if_need, the raw store in all its
+ * element types, _search, _search_device(_wait) (combining queue included) and _last_stages.  Results are the reference's bit
+ * for bit, ties included.  The search takes ONE path: the shared coarse quantizer, the query tables, a list scan that keeps the
+ * lookup table in LDS one slice of sub-quantizers at a time (DESIGN.md "Wide PQ"), unbounded, then the unfiltered selection,
+ * re-rank and tie replay.  No code sums are kept.  GAMMA_HIP_EUNSUPPORTED with a message, never a silent fall-back: the shard,
+ * merge and export entry points, gamma_hip_ivfpq_set_list_mask, gamma_hip_opq_set, a member of a group, and this init itself
+ * when the precomputed table nlist * M * 256 * 4 bytes would exceed precomputed_table_max_bytes (no table mode 0).
+ * gamma_hip_ivfpq_init keeps refusing M > 64. */
+int gamma_hip_ivfpq_wide_init(gamma_hip_index* h, int d, int nlist, int M, int metric, int bucket_init_size,
+                              int bucket_max_size);
+/* the wide scan's shape for M sub-quantizers, no handle, no device call: out3[0] = sub-quantizers of a table slice, out3[1] =
+ * slices (the last may be shorter), out3[2] = LDS bytes of a workgroup.  M outside 65 .. 256 or a NULL pointer: GAMMA_HIP_EINVAL. */
+int gamma_hip_ivfpq_wide_shape(int M, int* out3);
+/* codes of one tile of the wide scan: a list (inner product: a probe group) of at most that many codes keeps its running
+ * sums in registers from slice to slice, a longer one parks them in the distance slab */
+int gamma_hip_ivfpq_wide_tile_codes(void);
 /* The scan of a 4-bit handle list-major, a switch that is off by default: the inverted-list scan of
  * the reference's 4-bit scanner (gamma_index_ivfpq.h:540-601) with the work turned around -- a workgroup keeps a slab of a
  * LIST's codes and the list's precomputed-table row in registers and runs a tile of the (query, probe) pairs that probe the
