@@ -112,6 +112,10 @@ SYMBOLS = {
     "gamma_hip_ivfpq_wide_init": (C.c_int, [C.c_void_p] + [C.c_int] * 6),
     "gamma_hip_ivfpq_wide_shape": (C.c_int, [C.c_int, C.POINTER(C.c_int)]),
     "gamma_hip_ivfpq_wide_tile_codes": (C.c_int, []),
+    "gamma_hip_ivfpq_wide_set_lm_scan": (C.c_int, [C.c_void_p, C.c_int]),
+    "gamma_hip_ivfpq_wide_lm_scan": (C.c_int, [C.c_void_p]),
+    "gamma_hip_ivfpq_wide_lm_shape": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
+    "gamma_hip_ivfpq_wide_lm_stats": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_int64)] * 3),
     "gamma_hip_ivfpq4_set_lm_scan": (C.c_int, [C.c_void_p, C.c_int]),
     "gamma_hip_ivfpq4_lm_scan": (C.c_int, [C.c_void_p]),
     "gamma_hip_ivfpq4_lm_shape": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int64)]),

@@ -263,6 +263,22 @@ class GammaHip:
                  "ivfpq_wide_init")
         self.d, self.nlist, self.M = d, nlist, M
 
+    def ivfpq_wide_set_lm_scan(self, on):
+        """the scan of a wide handle list-major: a slab of a list's codes in registers, a tile of the
+        (query, probe) pairs that probe the list run past them slice by slice, their sums in registers.  Off by default; takes
+        effect where M is a multiple of 32 (ivfpq_wide_lm_shape); the answer is the same bit for bit."""
+        self._ck(self.L.gamma_hip_ivfpq_wide_set_lm_scan(self.h, 1 if on else 0), "ivfpq_wide_set_lm_scan")
+
+    def ivfpq_wide_lm_scan(self):
+        """the switch as set"""
+        return int(self.L.gamma_hip_ivfpq_wide_lm_scan(self.h))
+
+    def ivfpq_wide_lm_stats(self):
+        """(calls, units, pairs) of the wide list-major scan launches since init; units is -1 (not read back from the device)"""
+        c, u, p = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._ck(self.L.gamma_hip_ivfpq_wide_lm_stats(self.h, C.byref(c), C.byref(u), C.byref(p)), "ivfpq_wide_lm_stats")
+        return int(c.value), int(u.value), int(p.value)
+
     def ivfpq4_set_lm_scan(self, on):
         """the scan of a 4-bit handle list-major: a slab of a list's codes in registers, a tile of the
         (query, probe) pairs that probe the list run past them.  Off by default; the answer is the same bit for bit."""
@@ -1182,6 +1198,16 @@ def ivfpq_wide_shape(M):
     if rc != 0:
         raise _lib.GammaHipError("ivfpq_wide_shape: %d" % rc)
     return int(out[0]), int(out[1]), int(out[2]), int(L.gamma_hip_ivfpq_wide_tile_codes())
+
+
+def ivfpq_wide_lm_shape(M):
+    """(ms, qt, lds_bytes) of the wide list-major scan for M sub-quantizers: the sub-quantizers of a table slice (0: this M keeps
+    the scan of ivfpq_wide_init), the (query, probe) pairs of a work unit, the LDS of a workgroup.  No device call."""
+    ms, qt, lds = C.c_int(0), C.c_int(0), C.c_int64(0)
+    rc = _lib.load().gamma_hip_ivfpq_wide_lm_shape(int(M), C.byref(ms), C.byref(qt), C.byref(lds))
+    if rc != 0:
+        raise _lib.GammaHipError("ivfpq_wide_lm_shape: %d" % rc)
+    return int(ms.value), int(qt.value), int(lds.value)
 
 
 def ivfpq4_lm_shape(M):

@@ -505,6 +505,36 @@ int gamma_hip_ivfpq4_lm_stats(gamma_hip_index* h, int64_t* calls, int64_t* units
     return GAMMA_HIP_OK;
 }
 
+// The wide scan list-major (pqwide_lm.hip k_ivfpq_scan_wide_lm, gh::ScanPlan::wide_lm): the handle's switch, off by default
+int gamma_hip_ivfpq_wide_set_lm_scan(gamma_hip_index* h, int on) {
+    if (!h) return GAMMA_HIP_EINVAL;
+    SearchLock lk(h);
+    if (!h->ivf_init || !h->wide)
+        return fail(h, GAMMA_HIP_EUNSUPPORTED, "ivfpq_wide_set_lm_scan: the list-major scan is that of a wide handle (gamma_hip_ivfpq_wide_init)");
+    h->wide_lm_on = on != 0;
+    return GAMMA_HIP_OK;
+}
+
+int gamma_hip_ivfpq_wide_lm_scan(const gamma_hip_index* h) { return h && h->wide && h->wide_lm_on ? 1 : 0; }
+
+int gamma_hip_ivfpq_wide_lm_shape(int M, int* ms, int* qt, int64_t* lds_bytes) {
+    if (M <= gh::kWideMinM || M > gh::kWideMaxM) return GAMMA_HIP_EINVAL;
+    if (ms) *ms = gh::wide_lm_ms(M);
+    if (qt) *qt = gh::kWideLmQueryTile;
+    if (lds_bytes) *lds_bytes = (int64_t)gh::wide_lm_lds_bytes();
+    return GAMMA_HIP_OK;
+}
+
+// host counters only: the unit total of a launch stays on the device (no read-back, no synchronisation)
+int gamma_hip_ivfpq_wide_lm_stats(gamma_hip_index* h, int64_t* calls, int64_t* units, int64_t* pairs) {
+    if (!h) return GAMMA_HIP_EINVAL;
+    SearchLock lk(h);
+    if (calls) *calls = h->wide_lm_calls;
+    if (units) *units = -1;
+    if (pairs) *pairs = h->wide_lm_pairs;
+    return GAMMA_HIP_OK;
+}
+
 int gamma_hip_profile_scan_bytes(gamma_hip_index* h, int64_t* bytes, int64_t* pairs) {
     if (!h) return GAMMA_HIP_EINVAL;
     SearchLock lk(h);

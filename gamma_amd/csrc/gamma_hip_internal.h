@@ -431,6 +431,10 @@ struct gamma_hip_index {
     // gamma_hip_ivfpq_wide_init: 8-bit codes of 65 .. 256 sub-quantizers -- one search path, the sliced-table scan of pqwide.hip
     bool wide = false;
     int64_t pq4_lm_calls = 0, pq4_lm_pairs = 0;
+    // gamma_hip_ivfpq_wide_set_lm_scan: the scan of a wide handle runs list-major (pqwide_lm.hip k_ivfpq_scan_wide_lm) where M
+    // is whole slices; the launches it served and their (query, probe) pairs since init, counted on the host
+    bool wide_lm_on = false;
+    int64_t wide_lm_calls = 0, wide_lm_pairs = 0;
     // gamma_hip_binflat_init (gamma_hip_binflat.cpp): every code in vid order for the exact Hamming search, rows of bf_cs
     // bytes; bf_count is published after the rows it counts are in place; {queries, candidates, heap admissions} counters
     // and the number of query sub-batches (gamma_hip_binflat_stats); host images of a call's candidate totals / segment bases

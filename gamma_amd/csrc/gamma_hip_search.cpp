@@ -291,6 +291,7 @@ static gh::ScanShape scan_shape(const H* h, const gamma_hip_search_params* p, co
     sh.pq4 = h->ksub == gh::kPq4Ksub;
     sh.pq4_lm_switch = h->pq4_lm_on;
     sh.wide = h->wide;
+    sh.wide_lm_switch = h->wide_lm_on;
     sh.table_mode = h->table_mode;
     sh.have_sums = h->d_sums && h->d_t2max;
     sh.prefiltered = h->prefiltered;
@@ -591,7 +592,16 @@ int ivfpq_stage_a(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int
                 gh::launch_ivfpq4_scan_pair(s, l2, nq, M, P, h->w_probe.as<int>(), dis0, h->w_st2.as<float>(), h->d_T2, h->d_list_off,
                                             h->d_list_len, h->d_list_mask, nlist, h->d_codes, h->d_ids, h->w_pair_off.as<int>(),
                                             q_stride, h->w_dist.as<float>(), fc.d_tab, fc.d_qf, pl.need_ids, qperm, G, PGN);
-            else if (h->wide)
+            else if (pl.wide_lm) {
+                // (a wide call runs in sub-batches, wide_table_chunk: this is one of them, with an inverse index of its own)
+                GH_CHECK(h, h->w_lm_units.ensure(gh::ivfflat_lm_scratch_bytes(nq, P, nlist)));
+                gh::launch_ivfpq_scan_wide_lm(s, l2, nq, M, P, h->w_probe.as<int>(), dis0, h->w_st2.as<float>(), h->d_T2, h->d_list_off,
+                                              h->d_list_len, h->d_list_mask, nlist, h->max_list_len, h->d_codes, h->d_ids,
+                                              h->w_pair_off.as<int>(), q_stride, h->w_dist.as<float>(), fc.d_tab, fc.d_qf, pl.need_ids,
+                                              h->w_lm_units.p);
+                h->wide_lm_calls++;
+                h->wide_lm_pairs += (int64_t)nq * P;
+            } else if (h->wide)
                 gh::launch_ivfpq_scan_wide(s, l2, nq, M, P, h->w_probe.as<int>(), dis0, h->w_st2.as<float>(), h->d_T2, h->d_list_off,
                                            h->d_list_len, h->d_list_mask, nlist, h->d_codes, h->d_ids, h->w_pair_off.as<int>(),
                                            q_stride, h->w_dist.as<float>(), fc.d_tab, fc.d_qf, pl.need_ids, qperm, G, PGN);

@@ -111,6 +111,12 @@ __global__ __launch_bounds__(1024) void k_inv_scan_p(const int* __restrict__ cnt
                                                      int* __restrict__ ustart) {
     inv_scan_body<kPq4LmQueryTile, kPq4LmSlab>(cnt, list_len, nlist, start, cur, ustart);
 }
+// the same prefix with the wide list-major scan's unit: kWideLmQueryTile pairs x kWideLmSlab codes (pqwide_lm.hip)
+__global__ __launch_bounds__(1024) void k_inv_scan_w(const int* __restrict__ cnt, const int* __restrict__ list_len, int nlist,
+                                                     int* __restrict__ start, int* __restrict__ cur,
+                                                     int* __restrict__ ustart) {
+    inv_scan_body<kWideLmQueryTile, kWideLmSlab>(cnt, list_len, nlist, start, cur, ustart);
+}
 __global__ __launch_bounds__(256) void k_inv_fill(const int* __restrict__ probe, int npairs, int nlist,
                                                   const int* __restrict__ list_len, const int* __restrict__ start,
                                                   int* __restrict__ cur, int* __restrict__ inv) {

@@ -633,4 +633,22 @@ void launch_ivfpq_scan_wide(hipStream_t s, bool l2, int nq, int M, int P, const 
                             const int* pair_off, int64_t q_stride, float* out, const FilterDesc* ftab, const int* qfil,
                             int need_ids, const int* qperm, int G, int pg_cnt);
 
+// ---- the same scan list-major (pqwide_lm.hip), for M % kWideMS == 0 ----
+// A work unit = one list x one slab of kWideLmSlab consecutive codes (a code per lane) x one tile of up to kWideLmQueryTile of
+// the (query, probe) pairs that probe the list; the running sums of all pairs of the tile stay in registers across the slices.
+constexpr int kWideLmQueryTile = 8;
+constexpr int kWideLmSlab = 256;
+// the slice the list-major kernel takes for M sub-quantizers: kWideMS where M is 96, 128, ... 256; 0: the pair kernel only
+inline int wide_lm_ms(int M) { return (M > kWideMinM && M <= kWideMaxM && M % kWideMS == 0) ? kWideMS : 0; }
+// LDS of a workgroup: two table slices of kWideMS x 256 fp32, and nothing else
+inline size_t wide_lm_lds_bytes() { return 2 * wide_lds_bytes(); }
+// launch_ivfpq_scan_wide's slab, byte for byte, by k_ivfpq_scan_wide_lm over the call's inverse index (k_inv_count ->
+// k_inv_scan_w -> k_inv_fill, ivfflat.hip) built in scratch: ivfflat_lm_scratch_bytes(nq, P, nlist) bytes.  Refuses an M
+// without a slice (wide_lm_ms), no scratch, a list mask (a wide handle has none) and nq x nprobe / units beyond 2^31 - 1.
+void launch_ivfpq_scan_wide_lm(hipStream_t s, bool l2, int nq, int M, int P, const int* probe_list, const float* dis0,
+                               const float* st2, const float* T2, const int64_t* list_off, const int* list_len,
+                               const uint8_t* list_mask, int nlist, int max_list_len, const uint8_t* codes,
+                               const int64_t* ids, const int* pair_off, int64_t q_stride, float* out, const FilterDesc* ftab,
+                               const int* qfil, int need_ids, void* scratch);
+
 }  // namespace gh

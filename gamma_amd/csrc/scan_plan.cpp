@@ -142,6 +142,9 @@ void scan_plan_passes(ScanPlan& pl, const ScanShape& sh, const ScanSwitches& sw,
     // 4-bit codes list-major (pq4.hip): an opt-in of the handle, on the unbounded path -- the only one a
     // 4-bit handle has (bound_eligible above).  Off: the launch sequence of the pair scan, no inverse index, no scratch.
     pl.pq4_lm = sh.pq4 && sh.pq4_lm_switch && !bounded;
+    // a wide handle list-major (pqwide_lm.hip): the same kind of opt-in, where M is whole slices of 32
+    // sub-quantizers (96, 128, ... 256); every other M keeps k_ivfpq_scan_wide whatever the switch says
+    pl.wide_lm = sh.wide && sh.wide_lm_switch && !bounded && M > 64 && M <= 256 && M % 32 == 0;
     if (!bounded) return;
     // Filter pass of the consumers (scan.hip, CF): needs the sums beside the arena the scan reads -- not the shadow arena of
     // a call running over lists compacted under its filter.  With it ONE consumer workgroup per query takes every probe

@@ -70,6 +70,7 @@ struct ScanShape {
     bool scan_bound = true;         // the handle's switch (GAMMA_HIP_NO_SCAN_BOUND)
     bool sort_queries = false;      // the handle sorts queries and has a list rank
     ListStats lists;
+    bool wide_lm_switch = false;    // gamma_hip_ivfpq_wide_set_lm_scan: the handle's switch (off by default)
 };
 
 struct ScanPlan {
@@ -88,6 +89,7 @@ struct ScanPlan {
     // bounded: rq | ready[nq] | gcnt[nq][nsl] | fl inside w_scnt (rq, at offset 0: count + list of the queries that need the repair
     // launch, 8-byte aligned; fl: count + list of the queries k_select_final left to the unfiltered selection, flag = 1)
     size_t ready_off = 0, gcnt_off = 0, fl_off = 0, scnt_bytes = 0;
+    bool wide_lm = false;           // the wide scan runs list-major (k_ivfpq_scan_wide_lm) instead of k_ivfpq_scan_wide
 };
 // The plan is made in two calls, with the feedback between them: groups and eligibility, then everything that depends on
 // whether THIS call runs bounded.

@@ -156,6 +156,16 @@ int HIPIVFPQModelParams::Parse(const char *str) {
     }
     pq4_lm_scan = v == 1;
   }
+  // "pqwide_lm_scan": 0 (the default) | 1: the lists of a wide index (8-bit codes, nsubvector beyond 64) are scanned list-major
+  if (jp.Contains("pqwide_lm_scan")) {
+    if (jp.GetInt("pqwide_lm_scan", v) || (v != 0 && v != 1) || !FindHIPWideLm() ||
+        (v == 1 && (nbits_per_idx != 8 || nsubvector <= 64))) {
+      HLOG("invalid pqwide_lm_scan (0 or 1; 1 only beside 8-bit codes with nsubvector beyond 64, and only where this build of "
+           "the plugin has the list-major scan)");
+      return -1;
+    }
+    pqwide_lm_scan = v == 1;
+  }
   return 0;
 }
 
@@ -276,6 +286,18 @@ int RegisterHIPPq4Lm(const HIPPq4LmOps *ops) {
 }
 const HIPPq4LmOps *FindHIPPq4Lm() { return Pq4LmOps(); }
 
+namespace {
+const HIPWideLmOps *&WideLmOps() {
+  static const HIPWideLmOps *ops = nullptr;
+  return ops;
+}
+}  // namespace
+int RegisterHIPWideLm(const HIPWideLmOps *ops) {
+  WideLmOps() = ops;
+  return 0;
+}
+const HIPWideLmOps *FindHIPWideLm() { return WideLmOps(); }
+
 int RegisterHIPListsInit(int nbits, HIPListsInitFn fn) {
   ListsInits().push_back({nbits, fn});
   return 0;
@@ -394,6 +416,11 @@ int GammaIVFPQHIPIndex::Init(const std::string &model_parameters, int indexing_s
     return -2;
   }
   pq4_lm_ = pa.pq4_lm_scan ? FindHIPPq4Lm() : nullptr;
+  wide_lm_ = pa.pqwide_lm_scan ? FindHIPWideLm() : nullptr;
+  if (wide_lm_ && !wide_init) {
+    HLOG("pqwide_lm_scan needs a wide index, which this build of the plugin does not have");
+    return -2;
+  }
   if (const int krc = pa.CheckRawKeys()) return krc;   // "raw_placement" / "raw_dtype" against the devices and this build
   rawshard_ = pa.raw_sharded ? FindHIPRawShard() : nullptr;
   const HIPRawInitFn raw_init_f16 = pa.raw_f16 ? FindHIPRawInitF16() : nullptr;
@@ -412,6 +439,7 @@ int GammaIVFPQHIPIndex::Init(const std::string &model_parameters, int indexing_s
     if (!r && rawshard_ && (raw_init_f16 || raw_i8_ops)) r = rawshard_->narrow_rows(m, 1);
     if (!r) r = gamma_hip_set_exact_ties(m, pa.exact_ties ? 1 : 0);
     if (!r && pq4_lm_) r = pq4_lm_->set(m, 1);
+    if (!r && wide_lm_) r = wide_lm_->set(m, 1);
     if (!r && pa.perf_stages) r = gamma_hip_profile_enable(m, 1);
     return r;
   });
@@ -889,6 +917,10 @@ int GammaIVFPQHIPIndex::UploadEngineBitmap() {
 
 int GammaIVFPQHIPIndex::Pq4LmStats(int64_t *calls, int64_t *pairs) {
   return pq4_lm_ && h_ ? pq4_lm_->stats(h_, calls, nullptr, pairs) : -1;
+}
+
+int GammaIVFPQHIPIndex::WideLmStats(int64_t *calls, int64_t *pairs) {
+  return wide_lm_ && h_ ? wide_lm_->stats(h_, calls, nullptr, pairs) : -1;
 }
 
 int GammaIVFPQHIPIndex::SetTrained(const float *coarse, const float *pq) {

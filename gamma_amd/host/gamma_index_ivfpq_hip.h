@@ -70,6 +70,16 @@ struct HIPPq4LmOps {
 int RegisterHIPPq4Lm(const HIPPq4LmOps *ops);
 const HIPPq4LmOps *FindHIPPq4Lm();
 
+// "pqwide_lm_scan": 1 beside an "nsubvector" beyond 64: the scan of the wide lists runs list-major (the handle's switch
+// gamma_hip_ivfpq_wide_set_lm_scan and its counters), registered the same way by gamma_index_ivfpq_wide_lm_hip.cc -- the only
+// host file that names them.  Without that file, or on a model that is not wide, HIPIVFPQ::Init rejects the key.
+struct HIPWideLmOps {
+  int (*set)(gamma_hip_index *h, int on);
+  int (*stats)(gamma_hip_index *h, int64_t *calls, int64_t *units, int64_t *pairs);
+};
+int RegisterHIPWideLm(const HIPWideLmOps *ops);
+const HIPWideLmOps *FindHIPWideLm();
+
 // "raw_placement": "sharded" (several devices, lists sharded): every raw row once, on the device that owns its list.  The ABI
 // entries that takes beyond those of the replicated mirror -- the group's placement switch and row routing, the store's clear --
 // are registered by gamma_index_ivfpq_rawshard_hip.cc at static-initialisation time (the idiom of RegisterHIPListsInit):
@@ -205,6 +215,8 @@ struct HIPIVFPQModelParams {
                                  // (lossy; ranges = per-dimension minimum / maximum of the training rows).  One device only.
   bool pq4_lm_scan = false;      // HIP only: "pq4_lm_scan": 1 -- with "nbits_per_idx": 4 the list scan runs list-major (large
                                  // batches over many lists; same results).  Rejected without 4-bit codes.
+  bool pqwide_lm_scan = false;   // HIP only: "pqwide_lm_scan": 1 -- with "nsubvector" beyond 64 (8-bit codes) the list scan runs
+                                 // list-major where nsubvector is a multiple of 32 (same results).  Rejected on a narrower model.
   int Parse(const char *str);   // 0 ok, -1 bad (same rules as gamma_index_ivfpq.h:708-851)
   // "raw_placement" / "raw_dtype" against "devices" / "placement" and what this build of the plugin carries, as HIPIVFPQ::Init
   // decides it before a device is opened: 0 accepted, -2 rejected behind one log line
@@ -233,6 +245,7 @@ class GammaIVFPQHIPIndex : public RetrievalModel {
   // exposed for the harness / tests
   // "pq4_lm_scan": 1: the list-major scan launches the handle has served and their (query, probe) pairs; -1: no such model
   int Pq4LmStats(int64_t *calls, int64_t *pairs);
+  int WideLmStats(int64_t *calls, int64_t *pairs);   // the same for "pqwide_lm_scan": 1
   int Sq8Ranges(float *vmin, float *vmax);   // "raw_dtype": "sq8": the store's ranges, d floats each; 1 has them, 0 not, -1 no sq8 model
   bool is_trained_ = false;
   int d_ = 0, nlist_ = 0, M_ = 0, nprobe_ = 80;
@@ -244,6 +257,7 @@ class GammaIVFPQHIPIndex : public RetrievalModel {
  protected:
   const HIPOpqOps *opq_ = nullptr;   // non-null: the model was created with "opq"
   const HIPPq4LmOps *pq4_lm_ = nullptr;   // non-null: the model was created with "pq4_lm_scan": 1
+  const HIPWideLmOps *wide_lm_ = nullptr;   // non-null: the model was created with "pqwide_lm_scan": 1
   int opq_M_ = 0;
   int TrainOnHost(size_t num, const float *xt);
   int TrainCoarse(size_t num, const float *xt);

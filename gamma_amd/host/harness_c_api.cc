@@ -376,6 +376,11 @@ int gh_host_ivfpq4_lm_stats(void *hp, int64_t *out2) {
   GammaIVFPQHIPIndex *m = dynamic_cast<GammaIVFPQHIPIndex *>(((Host *)hp)->model);
   return m ? m->Pq4LmStats(&out2[0], &out2[1]) : -1;
 }
+// the same for a wide model's list-major scan ("pqwide_lm_scan": 1)
+int gh_host_ivfpq_wide_lm_stats(void *hp, int64_t *out2) {
+  GammaIVFPQHIPIndex *m = dynamic_cast<GammaIVFPQHIPIndex *>(((Host *)hp)->model);
+  return m ? m->WideLmStats(&out2[0], &out2[1]) : -1;
+}
 // query chunks a HIPIVFFLAT model's list-major scan of row lengths that are no multiple of 16 has served; -1 otherwise
 int64_t gh_host_ivfflat_lm_tail_chunks(void *hp) {
   GammaIVFFlatHIPIndex *m = dynamic_cast<GammaIVFFlatHIPIndex *>(((Host *)hp)->model);

@@ -53,6 +53,7 @@ HOST_SYMBOLS = {
     "gh_host_ivfpq_sq8_ranges": (C.c_int, [C.c_void_p, f32p, f32p]),
     "gh_host_ivfflat_lm_tail_chunks": (C.c_int64, [C.c_void_p]),
     "gh_host_ivfpq4_lm_stats": (C.c_int, [C.c_void_p, i64p]),
+    "gh_host_ivfpq_wide_lm_stats": (C.c_int, [C.c_void_p, i64p]),
     "gh_iwpq_rewrite_opq": (C.c_int, [C.c_char_p, C.c_char_p, f32p, C.c_int64]),
     "gh_iwpq_read_opq": (C.c_int64, [C.c_char_p, f32p, C.c_int64]),
     "gh_parse_ivfpq_model_params": (None, [C.c_char_p, C.POINTER(C.c_int)]),
@@ -414,6 +415,12 @@ class PluginModel:
         """(launches, (query, probe) pairs) a HIPIVFPQ model's 4-bit list-major scan ("pq4_lm_scan": 1) has served, or None"""
         out = np.zeros(2, dtype=np.int64)
         rc = self.L.gh_host_ivfpq4_lm_stats(self.h, out.ctypes.data_as(i64p))
+        return None if rc else (int(out[0]), int(out[1]))
+
+    def ivfpq_wide_lm_stats(self):
+        """(launches, (query, probe) pairs) a wide HIPIVFPQ model's list-major scan ("pqwide_lm_scan": 1) has served, or None"""
+        out = np.zeros(2, dtype=np.int64)
+        rc = self.L.gh_host_ivfpq_wide_lm_stats(self.h, out.ctypes.data_as(i64p))
         return None if rc else (int(out[0]), int(out[1]))
 
     def ivfflat_lm_tail_chunks(self):

@@ -494,6 +494,27 @@ int gamma_hip_ivfpq_wide_shape(int M, int* out3);
 /* codes of one tile of the wide scan: a list (inner product: a probe group) of at most that many codes keeps its running
  * sums in registers from slice to slice, a longer one parks them in the distance slab */
 int gamma_hip_ivfpq_wide_tile_codes(void);
+/* The scan of a wide handle list-major, a switch that is off by default: the inverted-list scan of
+ * the reference's scanner (gamma_index_ivfpq.h:540-601) with the work turned around -- a workgroup keeps a slab of 256 of a
+ * LIST's codes, a code per lane, and runs a tile of the (query, probe) pairs that probe the list past them, table slice by
+ * table slice, with the running sums of every pair of the tile in registers; nothing is parked in the distance slab.  Served
+ * that way: nsubvector 96, 128, 160, 192, 224 and 256 (whole slices); every other nsubvector keeps the scan of
+ * gamma_hip_ivfpq_wide_init whatever the switch says.  Every ADC distance, and with it every result and the order inside
+ * ties, is the same bit for bit; with the switch off nothing changes, no inverse index is built and no workspace is taken.
+ * GAMMA_HIP_EUNSUPPORTED with a message on a handle that is not wide. */
+int gamma_hip_ivfpq_wide_set_lm_scan(gamma_hip_index* h, int on);
+/* the switch as set (0 on a handle that is not wide) */
+int gamma_hip_ivfpq_wide_lm_scan(const gamma_hip_index* h);
+/* the list-major scan's shape for M sub-quantizers (gamma_index_ivfpq.h:540-601 is the scan it answers for), no handle, no
+ * device call: *ms = the sub-quantizers of a table slice, 0 where M is served by the scan of gamma_hip_ivfpq_wide_init only;
+ * *qt = the (query, probe) pairs of a work unit; *lds_bytes = the LDS of a workgroup (two table slices).  Any pointer may be
+ * NULL.  M outside 65 .. 256: GAMMA_HIP_EINVAL. */
+int gamma_hip_ivfpq_wide_lm_shape(int M, int* ms, int* qt, int64_t* lds_bytes);
+/* the list-major launches (gamma_index_ivfpq.h:540-601 scans served that way) since init: *calls = scan launches (one per
+ * sub-batch of a call), *pairs = their (query, probe) pairs, both counted on the host.  *units = -1: the unit total of a
+ * launch stays on the device -- the search reads nothing back for it and this entry adds no synchronisation.  Any pointer
+ * may be NULL. */
+int gamma_hip_ivfpq_wide_lm_stats(gamma_hip_index* h, int64_t* calls, int64_t* units, int64_t* pairs);
 /* The scan of a 4-bit handle list-major, a switch that is off by default: the inverted-list scan of
  * the reference's 4-bit scanner (gamma_index_ivfpq.h:540-601) with the work turned around -- a workgroup keeps a slab of a
  * LIST's codes and the list's precomputed-table row in registers and runs a tile of the (query, probe) pairs that probe the

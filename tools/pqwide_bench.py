@@ -7,6 +7,8 @@ The legs' handles are built first, then their calls ALTERNATE step by step; per 
 time from the handle's device events (summed over the call's sub-batches), as median and [min, max], and recall@10 against flat for the first 1024 queries.
 
     python tools/pqwide_bench.py [--n 1000000] [--steps 8] [--warmup 2] [--out profiles/pqwide_w.json]
+    --lm-scan            every wide leg twice on ONE handle, gamma_hip_ivfpq_wide_set_lm_scan off and on,
+                         alternating call by call after both are warmed up; the two settings' last answers are compared
     --sweep NAME=a,b,c   every wide leg additionally once per value of the environment switch NAME, alternating per call
                          (a build with an experiment switch in its launcher; the committed library reads none)"""
 import argparse
@@ -68,6 +70,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--legs", default="96,128,64")
     ap.add_argument("--sweep", default="")
+    ap.add_argument("--lm-scan", action="store_true")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     import torch
@@ -89,12 +92,15 @@ def main():
         if flat_I is None:
             flat_I = g.flat_search(q[:nf], k, args)[1]
         for v in (sw_vals if M > 64 else [""]):
-            legs.append(dict(M=M, g=g, sw=v, build_s=t_build, wall=[], stages=[]))
+            for lm in ((0, 1) if a.lm_scan and M > 64 else (None,)):
+                legs.append(dict(M=M, g=g, sw=v, lm=lm, build_s=t_build, wall=[], stages=[]))
         g.profile_enable(1)
 
     def call(leg):
         if sw_name and leg["sw"] != "":
             os.environ[sw_name] = leg["sw"]
+        if leg["lm"] is not None:
+            leg["g"].ivfpq_wide_set_lm_scan(leg["lm"])
         leg["g"].profile_reset()
         t0 = time.perf_counter()
         leg["g"].ivfpq_search_device(dx.data_ptr(), a.nq, k, args, dD.data_ptr(), dI.data_ptr())
@@ -108,11 +114,13 @@ def main():
             if step >= a.warmup:
                 leg["wall"].append(wall)
                 leg["stages"].append(st)
-    res = []
+    res, last = [], {}
     for leg in legs:
         g, M = leg["g"], leg["M"]
         call(leg)
         I = dI.cpu().numpy()
+        if leg["lm"] is not None:   # off, then on: equal bytes
+            last.setdefault((M, leg["sw"]), []).append((dD.cpu().numpy().tobytes(), I.tobytes()))
         recall = float(np.mean([len(set(I[i].tolist()) & set(flat_I[i].tolist())) / float(k) for i in range(nf)]))
         sizes = np.array([g.list_size(l) for l in range(a.nlist)], np.int64)
         # (a call of several sub-batches leaves the last one's rows: the mean over the rows that are an assignment)
@@ -122,14 +130,15 @@ def main():
         names = leg["stages"][0].keys()
         stage_us = {n: spread([s.get(n, 0.0) for s in leg["stages"]]) for n in names}
         scan_us = stage_us.get("scan", [0.0])[0]
-        res.append({"M": M, "scan": "wide" if M > 64 else "plain (GAMMA_HIP_NO_SCAN_BOUND=1)", "switch": leg["sw"],
+        res.append({"M": M, "scan": "wide" if M > 64 else "plain (GAMMA_HIP_NO_SCAN_BOUND=1)", "switch": leg["sw"], "lm_scan": leg["lm"],
+                    "lm_stats": list(g.ivfpq_wide_lm_stats()) if leg["lm"] else None,
                     "build_s": leg["build_s"], "wall_ms": spread(leg["wall"]), "qps": round(a.nq / (np.median(leg["wall"]) * 1e-3)),
                     "stage_us": stage_us, "codes_per_query": round(scanned / a.nq, 1), "max_list": int(sizes.max()),
                     "scan_code_bytes_per_s": float("%.4g" % (scanned * M / (scan_us * 1e-6))) if scan_us else None,
                     "scan_gathers_per_s": float("%.4g" % (scanned * M / (scan_us * 1e-6))) if scan_us else None,
                     "recall_at_10_vs_flat": round(recall, 4), "recall_queries": nf, "ties_not_honoured": g.ties_not_honoured()})
     out = {"workload": {k_: getattr(a, k_) for k_ in ("n", "d", "nlist", "nprobe", "recall_num", "nq", "steps", "warmup")},
-           "sweep": sw_name, "legs": res}
+           "sweep": sw_name, "lm_scan_equal_bytes": all(v[0] == v[1] for v in last.values()) if last else None, "legs": res}
     line = json.dumps(out)
     print(line)
     if a.out:
