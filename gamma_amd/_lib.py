@@ -110,6 +110,8 @@ SYMBOLS = {
     "gamma_hip_ivfpq_init": (C.c_int, [C.c_void_p] + [C.c_int] * 7),
     "gamma_hip_ivfpq4_init": (C.c_int, [C.c_void_p] + [C.c_int] * 6),
     "gamma_hip_ivfpq_wide_init": (C.c_int, [C.c_void_p] + [C.c_int] * 6),
+    "gamma_hip_ivfpq_wide_set_table_mode0": (C.c_int, [C.c_void_p, C.c_int]),
+    "gamma_hip_ivfpq_wide_table_mode0": (C.c_int, [C.c_void_p]),
     "gamma_hip_ivfpq_wide_shape": (C.c_int, [C.c_int, C.POINTER(C.c_int)]),
     "gamma_hip_ivfpq_wide_tile_codes": (C.c_int, []),
     "gamma_hip_ivfpq_wide_set_lm_scan": (C.c_int, [C.c_void_p, C.c_int]),

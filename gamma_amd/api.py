@@ -256,9 +256,21 @@ class GammaHip:
                  "ivfpq4_init")
         self.d, self.nlist, self.M, self.ksub = d, nlist, M, 16
 
-    def ivfpq_wide_init(self, d, nlist, M, metric=METRIC_L2, bucket_init_size=1000, bucket_max_size=1280000):
+    def ivfpq_wide_set_table_mode0(self, on):
+        """before ivfpq_wide_init: a precomputed table beyond precomputed_table_max_bytes makes table mode 0 (no table on the
+        device, L2 distances from the residual's tables built inside the scan) instead of a refusal"""
+        self._ck(self.L.gamma_hip_ivfpq_wide_set_table_mode0(self.h, 1 if on else 0), "ivfpq_wide_set_table_mode0")
+
+    def ivfpq_wide_table_mode0(self):
+        """the switch as set"""
+        return int(self.L.gamma_hip_ivfpq_wide_table_mode0(self.h))
+
+    def ivfpq_wide_init(self, d, nlist, M, metric=METRIC_L2, bucket_init_size=1000, bucket_max_size=1280000, table_mode0=False):
         """8-bit PQ codes of 65 .. 256 sub-quantizers: ksub = 256, code_size = M; the ivfpq_* methods serve the handle
-        afterwards, the search through the sliced-table scan (include/gamma_hip.h, DESIGN.md "Wide PQ")"""
+        afterwards, the search through the sliced-table scan (include/gamma_hip.h, DESIGN.md "Wide PQ").  table_mode0: see
+        ivfpq_wide_set_table_mode0"""
+        if table_mode0:
+            self.ivfpq_wide_set_table_mode0(True)
         self._ck(self.L.gamma_hip_ivfpq_wide_init(self.h, d, nlist, M, metric, bucket_init_size, bucket_max_size),
                  "ivfpq_wide_init")
         self.d, self.nlist, self.M = d, nlist, M

@@ -511,6 +511,8 @@ int gamma_hip_ivfpq_wide_set_lm_scan(gamma_hip_index* h, int on) {
     SearchLock lk(h);
     if (!h->ivf_init || !h->wide)
         return fail(h, GAMMA_HIP_EUNSUPPORTED, "ivfpq_wide_set_lm_scan: the list-major scan is that of a wide handle (gamma_hip_ivfpq_wide_init)");
+    if (h->table_mode == 0 && on)
+        return fail(h, GAMMA_HIP_EUNSUPPORTED, "ivfpq_wide_set_lm_scan: the list-major scan reads the precomputed table; this handle is in table mode 0");
     h->wide_lm_on = on != 0;
     return GAMMA_HIP_OK;
 }

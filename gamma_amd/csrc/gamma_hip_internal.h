@@ -434,6 +434,9 @@ struct gamma_hip_index {
     // gamma_hip_ivfpq_wide_set_lm_scan: the scan of a wide handle runs list-major (pqwide_lm.hip k_ivfpq_scan_wide_lm) where M
     // is whole slices; the launches it served and their (query, probe) pairs since init, counted on the host
     bool wide_lm_on = false;
+    // gamma_hip_ivfpq_wide_set_table_mode0, before the init: a table beyond precomputed_table_max_bytes makes table mode 0 (no
+    // T2, L2 through pqwide_res.hip) instead of a refusal
+    bool wide_mode0_on = false;
     int64_t wide_lm_calls = 0, wide_lm_pairs = 0;
     // gamma_hip_binflat_init (gamma_hip_binflat.cpp): every code in vid order for the exact Hamming search, rows of bf_cs
     // bytes; bf_count is published after the rows it counts are in place; {queries, candidates, heap admissions} counters

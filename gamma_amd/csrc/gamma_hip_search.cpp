@@ -500,7 +500,7 @@ int ivfpq_stage_a(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int
         if (pq4) {
             GH_CHECK(h, h->w_st2.ensure((size_t)nq * M * gh::kPq4Ksub * sizeof(float)));
             gh::launch_pq4_ip_table(s, d_x, nq, d, M, h->d_pqc, h->w_st2.as<float>());
-        } else if (!pl.fuse_ip && !pl.res) {
+        } else if (!pl.fuse_ip && !pl.res && !pl.wide_res) {   // (table mode 0 under L2: the scan builds its tables)
             GH_CHECK(h, h->w_st2.ensure((size_t)nq * M * 256 * sizeof(float)));
             gh::launch_pq_ip_table(s, d_x, nq, d, M, h->d_pqc, h->w_st2.as<float>());
         }
@@ -601,7 +601,12 @@ int ivfpq_stage_a(H* h, const gamma_hip_search_params* p, const FiltCtx& fc, int
                                               h->w_lm_units.p);
                 h->wide_lm_calls++;
                 h->wide_lm_pairs += (int64_t)nq * P;
-            } else if (h->wide)
+            } else if (pl.wide_res)
+                // (dis0 = 0 is the kernel's: `float dis0 = 0`, gamma_index_ivfpq.h:236)
+                gh::launch_ivfpq_scan_wide_res(s, nq, d, M, P, h->w_probe.as<int>(), d_x, h->d_cc, h->d_pqc, h->d_list_off, h->d_list_len,
+                                               h->d_list_mask, nlist, h->d_codes, h->d_ids, h->w_pair_off.as<int>(), q_stride,
+                                               h->w_dist.as<float>(), fc.d_tab, fc.d_qf, pl.need_ids, qperm);
+            else if (h->wide)
                 gh::launch_ivfpq_scan_wide(s, l2, nq, M, P, h->w_probe.as<int>(), dis0, h->w_st2.as<float>(), h->d_T2, h->d_list_off,
                                            h->d_list_len, h->d_list_mask, nlist, h->d_codes, h->d_ids, h->w_pair_off.as<int>(),
                                            q_stride, h->w_dist.as<float>(), fc.d_tab, fc.d_qf, pl.need_ids, qperm, G, PGN);
@@ -1076,13 +1081,15 @@ int coarse_chunk(H* h, int nq) {
 // a wide handle's query tables are M KB per query (2 GB at 16384 queries and M = 128), beside a slab of ~100 KB per query: the
 // sub-batch is sized by them too, at most kWideTableBytes of tables in one piece (any other handle: no limit from here)
 static constexpr int64_t kWideTableBytes = (int64_t)1 << 30;
-static int64_t wide_table_chunk(const H* h) {
+// (L2 on a handle in table mode 0 builds its tables inside the scan, k_ivfpq_scan_wide_res: no limit from here either)
+static int64_t wide_table_chunk(const H* h, bool l2_call) {
+    if (l2_call && h->table_mode == 0) return INT64_MAX;
     return h->wide ? std::max<int64_t>(1, kWideTableBytes / ((int64_t)h->M * 256 * (int64_t)sizeof(float))) : INT64_MAX;
 }
-int scan_chunk(H* h, int nq, int P) {
+int scan_chunk(H* h, int nq, int P, bool l2_call) {
     const int64_t q_stride = std::max<int64_t>(1, (int64_t)P * std::max(1, h->max_list_len));
     const int64_t by_dist = (int64_t)(h->dist_budget_bytes / (q_stride * sizeof(float)));
-    return (int)std::max<int64_t>(1, std::min<int64_t>(std::min(by_dist, wide_table_chunk(h)), nq));
+    return (int)std::max<int64_t>(1, std::min<int64_t>(std::min(by_dist, wide_table_chunk(h, l2_call)), nq));
 }
 int query_chunk(H* h, int nq, int P) { return std::min(coarse_chunk(h, nq), scan_chunk(h, nq, P)); }
 
@@ -1182,7 +1189,7 @@ int ivfpq_search_device_locked(H* h, const gamma_hip_search_params* p, int nq, c
     ListCompaction restore(h);
     GH_TRY(compact_lists_for_call(h, &fc, (int64_t)nq * p->nprobe * (h->ntotal / std::max(1, h->nlist)),
                                   !given, &restore));
-    int chunk = scan_chunk(h, nq, p->nprobe);
+    int chunk = scan_chunk(h, nq, p->nprobe, p->metric == GAMMA_HIP_METRIC_L2);
     const int P = p->nprobe;
     // long lists (C4: 64 probes x lists of tens of thousands) make the ADC slab the limit: the coarse
     // quantizer then still runs over the whole call (one GEMM instead of one per slab chunk)
@@ -1214,7 +1221,7 @@ int ivfpq_search_device_locked(H* h, const gamma_hip_search_params* p, int nq, c
             GH_CHECK(h, hipStreamSynchronize(h->stream));
             h->q_stride_cap = (std::max<int64_t>(mx[0], 1) + 3) & ~(int64_t)3;
             const int64_t by_dist = (int64_t)(h->dist_budget_bytes / ((size_t)h->q_stride_cap * sizeof(float)));
-            chunk = (int)std::max<int64_t>(chunk, std::min<int64_t>(std::min(by_dist, wide_table_chunk(h)), nq));
+            chunk = (int)std::max<int64_t>(chunk, std::min<int64_t>(std::min(by_dist, wide_table_chunk(h, p->metric == GAMMA_HIP_METRIC_L2)), nq));
         }
     }
     // a call of several chunks: the tie replay of chunk i runs on its own stream beside chunk i + 1 (what

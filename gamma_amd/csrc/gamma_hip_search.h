@@ -127,7 +127,7 @@ int ivfpq_stage_b(H* h, const gamma_hip_search_params* p, int nq, const float* d
 // queries per internal chunk: the coarse distance matrix (nlist floats per query) and the ADC distance
 // slab (nprobe x longest list floats per query) each stay inside the workspace budget
 int coarse_chunk(H* h, int nq);
-int scan_chunk(H* h, int nq, int P);
+int scan_chunk(H* h, int nq, int P, bool l2_call = false);   // l2_call: an L2 IVFPQ search (a wide handle in table mode 0 holds no query tables then)
 int query_chunk(H* h, int nq, int P);
 
 // floats per query of the distance slab of a call that scans P lists per query: P x the longest list, rows 16-byte aligned

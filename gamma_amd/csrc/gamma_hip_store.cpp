@@ -1133,6 +1133,15 @@ int gamma_hip_ivfpq4_init(gamma_hip_index* h, int d, int nlist, int M, int metri
 
 // 8-bit codes of more sub-quantizers than one LDS table holds (pq.M = ivfpq_param.nsubvector, gamma_index_ivfpq.cc:167-170,
 // takes any M): the scan keeps the table in LDS a slice at a time (pqwide.hip)
+int gamma_hip_ivfpq_wide_set_table_mode0(gamma_hip_index* h, int on) {
+    if (!h) return GAMMA_HIP_EINVAL;
+    WriteLock lk(h);
+    if (h->ivf_init) return fail(h, GAMMA_HIP_EINVAL, "ivfpq_wide_set_table_mode0: the table mode is fixed at gamma_hip_ivfpq_wide_init; set the switch before it");
+    h->wide_mode0_on = on != 0;
+    return GAMMA_HIP_OK;
+}
+int gamma_hip_ivfpq_wide_table_mode0(const gamma_hip_index* h) { return h && h->wide_mode0_on ? 1 : 0; }
+
 int gamma_hip_ivfpq_wide_init(gamma_hip_index* h, int d, int nlist, int M, int metric, int bucket_init_size,
                               int bucket_max_size) {
     if (!h) return GAMMA_HIP_EINVAL;
@@ -1143,7 +1152,8 @@ int gamma_hip_ivfpq_wide_init(gamma_hip_index* h, int d, int nlist, int M, int m
     if (M <= gh::kWideMinM || M > gh::kWideMaxM) return fail(h, GAMMA_HIP_EINVAL, "ivfpq_wide_init: nsubvector must be 65 .. 256 (gamma_hip_ivfpq_init serves up to 64)");
     if (d % M != 0) return fail(h, GAMMA_HIP_EINVAL, "d must be divisible by nsubvector");
     if (d / M > 64) return fail(h, GAMMA_HIP_EINVAL, "dsub > 64 unsupported");
-    if ((int64_t)nlist * M * 256 * (int64_t)sizeof(float) > g_table_max_bytes.load())
+    // (with gamma_hip_ivfpq_wide_set_table_mode0 the rule below, faiss's, makes table mode 0: k_ivfpq_scan_wide_res)
+    if (!h->wide_mode0_on && (int64_t)nlist * M * 256 * (int64_t)sizeof(float) > g_table_max_bytes.load())
         return fail(h, GAMMA_HIP_EUNSUPPORTED, "wide handle: the precomputed table would exceed precomputed_table_max_bytes (table mode 0 is nsubvector <= 64 only)");
     h->wide = true;
     const int rc = ivf_init_locked(h, d, nlist, M, metric, bucket_init_size, bucket_max_size, false);

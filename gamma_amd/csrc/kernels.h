@@ -651,4 +651,22 @@ void launch_ivfpq_scan_wide_lm(hipStream_t s, bool l2, int nq, int M, int P, con
                                const int64_t* ids, const int* pair_off, int64_t q_stride, float* out, const FilterDesc* ftab,
                                const int* qfil, int need_ids, void* scratch);
 
+// ---- the L2 scan of a wide handle without a precomputed table (table mode 0, pqwide_res.hip) ----
+// A workgroup owns one query and kWideResG of its probes; per slice of kWideResMS sub-quantizers it builds the kWideResG
+// residual tables from ONE pass over the slice's codebook rows, then scans the lists.  Both measured: of (32, 2), (32, 1),
+// (16, 1), (16, 2), (16, 4) and (32, 4) the kept (32, 1) is the fastest on lists of ~1000 codes, where the workgroups a CU holds
+// count for more than the shared codebook pass; lists of ~60 codes favour (16, 2).
+constexpr int kWideResMS = 32;
+constexpr int kWideResG = 1;
+// LDS of a workgroup: kWideResG table slices and kWideResG residual slices of kWideResMS x dsub floats (40 KB at dsub 64)
+inline size_t wide_res_lds_bytes(int dsub) { return (size_t)kWideResG * kWideResMS * (256 + dsub) * sizeof(float); }
+// launch_ivfpq_scan_wide's slab for L2 with the reference's mode-0 arithmetic: r = x_q - centroid_l, lut[m][j] =
+// fvec_ny_row<true>(r + m * dsub, pqc + (m * 256 + j) * dsub, dsub), dis = 0 then += lut[m][code[m]] for m ascending.
+// x [nq][d], cc [nlist][d], pqc [M][256][dsub]; any 64 < M <= 256 and d / M <= 64, anything else is refused.
+void launch_ivfpq_scan_wide_res(hipStream_t s, int nq, int d, int M, int P, const int* probe_list, const float* x,
+                                const float* cc, const float* pqc, const int64_t* list_off, const int* list_len,
+                                const uint8_t* list_mask, int nlist, const uint8_t* codes, const int64_t* ids,
+                                const int* pair_off, int64_t q_stride, float* out, const FilterDesc* ftab, const int* qfil,
+                                int need_ids, const int* qperm);
+
 }  // namespace gh

@@ -144,7 +144,11 @@ void scan_plan_passes(ScanPlan& pl, const ScanShape& sh, const ScanSwitches& sw,
     pl.pq4_lm = sh.pq4 && sh.pq4_lm_switch && !bounded;
     // a wide handle list-major (pqwide_lm.hip): the same kind of opt-in, where M is whole slices of 32
     // sub-quantizers (96, 128, ... 256); every other M keeps k_ivfpq_scan_wide whatever the switch says
-    pl.wide_lm = sh.wide && sh.wide_lm_switch && !bounded && M > 64 && M <= 256 && M % 32 == 0;
+    // L2 on a wide handle without a precomputed table (gamma_hip_ivfpq_wide_set_table_mode0, pqwide_res.hip, DESIGN.md section
+    // 40): the tables come from the residual inside the scan.  Its inner-product searches never needed T2: k_ivfpq_scan_wide.
+    pl.wide_res = sh.wide && sh.l2 && sh.table_mode == 0;
+    // (the list-major kernel reads T2: a mode-0 handle refuses its switch, and the plan keeps it off)
+    pl.wide_lm = sh.wide && sh.wide_lm_switch && !bounded && sh.table_mode != 0 && M > 64 && M <= 256 && M % 32 == 0;
     if (!bounded) return;
     // Filter pass of the consumers (scan.hip, CF): needs the sums beside the arena the scan reads -- not the shadow arena of
     // a call running over lists compacted under its filter.  With it ONE consumer workgroup per query takes every probe

@@ -90,6 +90,7 @@ struct ScanPlan {
     // launch, 8-byte aligned; fl: count + list of the queries k_select_final left to the unfiltered selection, flag = 1)
     size_t ready_off = 0, gcnt_off = 0, fl_off = 0, scnt_bytes = 0;
     bool wide_lm = false;           // the wide scan runs list-major (k_ivfpq_scan_wide_lm) instead of k_ivfpq_scan_wide
+    bool wide_res = false;          // L2 on a wide handle in table mode 0: k_ivfpq_scan_wide_res, no query tables, no T2
 };
 // The plan is made in two calls, with the feedback between them: groups and eligibility, then everything that depends on
 // whether THIS call runs bounded.

@@ -166,6 +166,17 @@ int HIPIVFPQModelParams::Parse(const char *str) {
     }
     pqwide_lm_scan = v == 1;
   }
+  // "pqwide_table_mode0": 0 (the default) | 1: a wide index whose precomputed table would exceed precomputed_table_max_bytes
+  // comes up in table mode 0 (faiss:IndexIVFPQ.cpp:441-449) instead of being rejected
+  if (jp.Contains("pqwide_table_mode0")) {
+    if (jp.GetInt("pqwide_table_mode0", v) || (v != 0 && v != 1) || !FindHIPWideMode0() ||
+        (v == 1 && (nbits_per_idx != 8 || nsubvector <= 64 || pqwide_lm_scan))) {
+      HLOG("invalid pqwide_table_mode0 (0 or 1; 1 only beside 8-bit codes with nsubvector beyond 64, never beside pqwide_lm_scan = 1, "
+           "and only where this build of the plugin has the switch)");
+      return -1;
+    }
+    pqwide_table_mode0 = v == 1;
+  }
   return 0;
 }
 
@@ -298,6 +309,18 @@ int RegisterHIPWideLm(const HIPWideLmOps *ops) {
 }
 const HIPWideLmOps *FindHIPWideLm() { return WideLmOps(); }
 
+namespace {
+HIPWideMode0Fn &WideMode0Fn() {
+  static HIPWideMode0Fn fn = nullptr;
+  return fn;
+}
+}  // namespace
+int RegisterHIPWideMode0(HIPWideMode0Fn fn) {
+  WideMode0Fn() = fn;
+  return 0;
+}
+HIPWideMode0Fn FindHIPWideMode0() { return WideMode0Fn(); }
+
 int RegisterHIPListsInit(int nbits, HIPListsInitFn fn) {
   ListsInits().push_back({nbits, fn});
   return 0;
@@ -421,6 +444,11 @@ int GammaIVFPQHIPIndex::Init(const std::string &model_parameters, int indexing_s
     HLOG("pqwide_lm_scan needs a wide index, which this build of the plugin does not have");
     return -2;
   }
+  const HIPWideMode0Fn wide_mode0 = pa.pqwide_table_mode0 ? FindHIPWideMode0() : nullptr;
+  if (wide_mode0 && !wide_init) {
+    HLOG("pqwide_table_mode0 needs a wide index, which this build of the plugin does not have");
+    return -2;
+  }
   if (const int krc = pa.CheckRawKeys()) return krc;   // "raw_placement" / "raw_dtype" against the devices and this build
   rawshard_ = pa.raw_sharded ? FindHIPRawShard() : nullptr;
   const HIPRawInitFn raw_init_f16 = pa.raw_f16 ? FindHIPRawInitF16() : nullptr;
@@ -433,7 +461,9 @@ int GammaIVFPQHIPIndex::Init(const std::string &model_parameters, int indexing_s
   if (OpenDevices(pa.devices, pa.replicate)) return -1;
   int rc = ForAll([&](gamma_hip_index *m) {
     const int metric = metric_type_ == DistanceComputeType::L2 ? GAMMA_HIP_METRIC_L2 : GAMMA_HIP_METRIC_IP;
-    int r = lists_init ? lists_init(m, d_, nlist_, M_, metric, pa.bucket_init_size, pa.bucket_max_size)
+    int r = wide_mode0 ? wide_mode0(m, 1) : 0;   // (before the lists: the initialiser fixes the table mode)
+    if (!r)
+      r = lists_init ? lists_init(m, d_, nlist_, M_, metric, pa.bucket_init_size, pa.bucket_max_size)
                        : gamma_hip_ivfpq_init(m, d_, nlist_, M_, 8, metric, pa.bucket_init_size, pa.bucket_max_size);
     if (!r) r = raw_sq8_ops ? raw_sq8_ops->init(m, d_) : raw_i8_ops ? raw_i8_ops->init(m, d_, pa.raw_i8 == 2) : raw_init_f16 ? raw_init_f16(m, d_) : gamma_hip_raw_init(m, d_);
     if (!r && rawshard_ && (raw_init_f16 || raw_i8_ops)) r = rawshard_->narrow_rows(m, 1);

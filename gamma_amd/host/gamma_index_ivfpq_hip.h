@@ -80,6 +80,14 @@ struct HIPWideLmOps {
 int RegisterHIPWideLm(const HIPWideLmOps *ops);
 const HIPWideLmOps *FindHIPWideLm();
 
+// "pqwide_table_mode0": 1 beside an "nsubvector" beyond 64: a precomputed table beyond precomputed_table_max_bytes makes
+// table mode 0 instead of a rejected Init (the handle's switch gamma_hip_ivfpq_wide_set_table_mode0, set before the lists
+// initialiser), registered the same way by gamma_index_ivfpq_wide_mode0_hip.cc -- the only host file that names it.  Without
+// that file, on a model that is not wide, or beside "pqwide_lm_scan": 1 (that scan reads the table), Init rejects the key.
+typedef int (*HIPWideMode0Fn)(gamma_hip_index *h, int on);
+int RegisterHIPWideMode0(HIPWideMode0Fn fn);
+HIPWideMode0Fn FindHIPWideMode0();
+
 // "raw_placement": "sharded" (several devices, lists sharded): every raw row once, on the device that owns its list.  The ABI
 // entries that takes beyond those of the replicated mirror -- the group's placement switch and row routing, the store's clear --
 // are registered by gamma_index_ivfpq_rawshard_hip.cc at static-initialisation time (the idiom of RegisterHIPListsInit):
@@ -217,6 +225,9 @@ struct HIPIVFPQModelParams {
                                  // batches over many lists; same results).  Rejected without 4-bit codes.
   bool pqwide_lm_scan = false;   // HIP only: "pqwide_lm_scan": 1 -- with "nsubvector" beyond 64 (8-bit codes) the list scan runs
                                  // list-major where nsubvector is a multiple of 32 (same results).  Rejected on a narrower model.
+  bool pqwide_table_mode0 = false;   // HIP only: "pqwide_table_mode0": 1 -- with "nsubvector" beyond 64 (8-bit codes) a table beyond
+                                     // precomputed_table_max_bytes makes table mode 0 (faiss's rule).  Rejected on a narrower
+                                     // model and beside "pqwide_lm_scan": 1.
   int Parse(const char *str);   // 0 ok, -1 bad (same rules as gamma_index_ivfpq.h:708-851)
   // "raw_placement" / "raw_dtype" against "devices" / "placement" and what this build of the plugin carries, as HIPIVFPQ::Init
   // decides it before a device is opened: 0 accepted, -2 rejected behind one log line

@@ -484,10 +484,24 @@ int gamma_hip_ivfpq4_init(gamma_hip_index* h, int d, int nlist, int M, int metri
  * lookup table in LDS one slice of sub-quantizers at a time (DESIGN.md "Wide PQ"), unbounded, then the unfiltered selection,
  * re-rank and tie replay.  No code sums are kept.  GAMMA_HIP_EUNSUPPORTED with a message, never a silent fall-back: the shard,
  * merge and export entry points, gamma_hip_ivfpq_set_list_mask, gamma_hip_opq_set, a member of a group, and this init itself
- * when the precomputed table nlist * M * 256 * 4 bytes would exceed precomputed_table_max_bytes (no table mode 0).
+ * when the precomputed table nlist * M * 256 * 4 bytes would exceed precomputed_table_max_bytes -- unless
+ * gamma_hip_ivfpq_wide_set_table_mode0 was set on the handle, which then comes up in table mode 0.
  * gamma_hip_ivfpq_init keeps refusing M > 64. */
 int gamma_hip_ivfpq_wide_init(gamma_hip_index* h, int d, int nlist, int M, int metric, int bucket_init_size,
                               int bucket_max_size);
+/* Table mode 0 for a wide handle, a switch that is off by default, set on a created and not yet initialised handle.  faiss
+ * leaves use_precomputed_table at 0 where the table would exceed precomputed_table_max_bytes (faiss:IndexIVFPQ.cpp:441-449),
+ * and the reference's scanner then scores each (query, list) pair with the distance table of the residual
+ * (index/impl/gamma_index_ivfpq.h:239-245: compute_residual, pq.compute_distance_table, dis0 = 0).  With the switch on,
+ * gamma_hip_ivfpq_wide_init accepts such a table size and the handle holds no precomputed table and no code sums: its L2
+ * searches build the residual tables inside the list scan, bit for bit the reference's mode-0
+ * distances; its inner-product searches are those of any wide handle.  gamma_hip_ivfpq_use_precomputed_table answers 0 and
+ * gamma_hip_ivfpq_get_precomputed_table refuses ("table mode 0").  Under the limit the switch changes nothing (mode 1, as
+ * faiss decides); with it off the init refuses as before.  Everything a wide handle refuses stays refused, and
+ * gamma_hip_ivfpq_wide_set_lm_scan(h, 1) is refused too (that scan reads the table).  GAMMA_HIP_EINVAL after the init. */
+int gamma_hip_ivfpq_wide_set_table_mode0(gamma_hip_index* h, int on);
+/* the switch as set */
+int gamma_hip_ivfpq_wide_table_mode0(const gamma_hip_index* h);
 /* the wide scan's shape for M sub-quantizers, no handle, no device call: out3[0] = sub-quantizers of a table slice, out3[1] =
  * slices (the last may be shorter), out3[2] = LDS bytes of a workgroup.  M outside 65 .. 256 or a NULL pointer: GAMMA_HIP_EINVAL. */
 int gamma_hip_ivfpq_wide_shape(int M, int* out3);

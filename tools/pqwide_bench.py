@@ -9,6 +9,9 @@ time from the handle's device events (summed over the call's sub-batches), as me
     python tools/pqwide_bench.py [--n 1000000] [--steps 8] [--warmup 2] [--out profiles/pqwide_w.json]
     --lm-scan            every wide leg twice on ONE handle, gamma_hip_ivfpq_wide_set_lm_scan off and on,
                          alternating call by call after both are warmed up; the two settings' last answers are compared
+    --table-mode0        every wide leg twice: its handle (table mode 1) and a second handle over the SAME trained state created with
+                         gamma_hip_ivfpq_wide_set_table_mode0 under a lowered precomputed_table_max_bytes (table mode 0, DESIGN.md
+                         section 40), alternating call by call; each handle's device memory is reported
     --sweep NAME=a,b,c   every wide leg additionally once per value of the environment switch NAME, alternating per call
                          (a build with an experiment switch in its launcher; the committed library reads none)"""
 import argparse
@@ -31,7 +34,8 @@ def clustered(n, d, seed, centers):
     return out
 
 
-def build(a, M, base):
+def build(a, M, base, trained=None):
+    """trained: (cc, pq) of the leg's mode-1 handle -- the handle is made in table mode 0 over that state"""
     from gamma_amd import api
     wide = M > 64
     if not wide:
@@ -40,18 +44,25 @@ def build(a, M, base):
     os.environ.pop("GAMMA_HIP_NO_SCAN_BOUND", None)
     d = base.shape[1]
     bucket = max(1000, a.n // a.nlist)
-    if wide:
+    if trained:
+        old = api.get_precomputed_table_max_bytes()
+        api.set_precomputed_table_max_bytes(a.nlist * M * 1024 - 1)
+        try:
+            g.ivfpq_wide_init(d, a.nlist, M, api.METRIC_L2, bucket_init_size=bucket, table_mode0=True)
+        finally:
+            api.set_precomputed_table_max_bytes(old)
+    elif wide:
         g.ivfpq_wide_init(d, a.nlist, M, api.METRIC_L2, bucket_init_size=bucket)
     else:
         g.ivfpq_init(d, a.nlist, M, 8, api.METRIC_L2, bucket_init_size=bucket)
     t0 = time.time()
-    cc, pq = g.ivfpq_train(base[:min(a.n, a.nlist * 40)], a.nlist, M)
+    cc, pq = trained or g.ivfpq_train(base[:min(a.n, a.nlist * 40)], a.nlist, M)
     g.ivfpq_set_trained(cc, pq, None)
     g.raw_init(d)
     g.raw_append(base)
     for i0 in range(0, a.n, 1 << 18):
         g.add(base[i0:i0 + (1 << 18)], i0)
-    return g, round(time.time() - t0, 1)
+    return g, round(time.time() - t0, 1), (cc, pq)
 
 
 def spread(v):
@@ -71,6 +82,7 @@ def main():
     ap.add_argument("--legs", default="96,128,64")
     ap.add_argument("--sweep", default="")
     ap.add_argument("--lm-scan", action="store_true")
+    ap.add_argument("--table-mode0", action="store_true")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     import torch
@@ -88,13 +100,18 @@ def main():
     sw_name, sw_vals = (a.sweep.split("=")[0], a.sweep.split("=")[1].split(",")) if a.sweep else ("", [""])
     legs, flat_I = [], None
     for M in [int(x) for x in a.legs.split(",")]:
-        g, t_build = build(a, M, base)
+        g, t_build, trained = build(a, M, base)
         if flat_I is None:
             flat_I = g.flat_search(q[:nf], k, args)[1]
         for v in (sw_vals if M > 64 else [""]):
             for lm in ((0, 1) if a.lm_scan and M > 64 else (None,)):
                 legs.append(dict(M=M, g=g, sw=v, lm=lm, build_s=t_build, wall=[], stages=[]))
         g.profile_enable(1)
+        if a.table_mode0 and M > 64:
+            g0, t_build, _ = build(a, M, base, trained)
+            assert g0.use_precomputed_table() == 0
+            legs.append(dict(M=M, g=g0, sw="", lm=None, build_s=t_build, wall=[], stages=[]))
+            g0.profile_enable(1)
 
     def call(leg):
         if sw_name and leg["sw"] != "":
@@ -131,6 +148,7 @@ def main():
         stage_us = {n: spread([s.get(n, 0.0) for s in leg["stages"]]) for n in names}
         scan_us = stage_us.get("scan", [0.0])[0]
         res.append({"M": M, "scan": "wide" if M > 64 else "plain (GAMMA_HIP_NO_SCAN_BOUND=1)", "switch": leg["sw"], "lm_scan": leg["lm"],
+                    "table_mode": g.use_precomputed_table(), "device_mem_bytes": g.total_mem_bytes(),
                     "lm_stats": list(g.ivfpq_wide_lm_stats()) if leg["lm"] else None,
                     "build_s": leg["build_s"], "wall_ms": spread(leg["wall"]), "qps": round(a.nq / (np.median(leg["wall"]) * 1e-3)),
                     "stage_us": stage_us, "codes_per_query": round(scanned / a.nq, 1), "max_list": int(sizes.max()),
@@ -145,8 +163,8 @@ def main():
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
             f.write(json.dumps(out, indent=1) + "\n")
-    for M in {leg["M"]: leg["g"] for leg in legs}.values():
-        M.close()
+    for g in {id(leg["g"]): leg["g"] for leg in legs}.values():
+        g.close()
 
 
 if __name__ == "__main__":
